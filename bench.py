@@ -41,6 +41,12 @@ launches through hipIpc-mapped mailboxes), which is tried as a tuning candidate 
 when it passes them and is faster (--no-resident-p2p: never). `python bench.py --gpus N` starts the N ranks itself
 (torch.distributed.run as a child process, before this process touches torch or the GPU) and relays rank 0's JSON line;
 under torchrun (WORLD_SIZE set) it is a rank.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of --dump-outputs DIR (the
+poses of the last timed step, DIR/poses.npy, float64 [B, 6]; the inputs are seeded, so two builds compare output for
+output) and the result line. --full adds everything else it measures or checks: the stream-read yardstick (before
+set-up) and, after the timed steps, roofline, cpu_baseline with the pose check against the CPU path (exit 3 above
+1e-4), dp_vs_cpu and the secondary workloads.
 """
 from __future__ import annotations
 
@@ -68,7 +74,12 @@ def parse():
     ap.add_argument("--psz", type=int, default=8)
     ap.add_argument("--maxiter", type=int, default=10)
     ap.add_argument("--variant", type=int, default=0, help="kernel-selection bits for A/B runs (include/ictr.h, ictr_odometer_set_variant)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: stream-read yardstick, roofline, "
+                         "cpu_baseline and pose check against the CPU path, dp_vs_cpu, secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses of the last timed step to DIR/poses.npy (float64, [batch, 6])")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--no-events", action="store_true", help="skip the in-stream HIP-event kernel timing")
     ap.add_argument("--streams", type=int, default=0,
                     help="single-GPU mode: split the B pairs over this many engines on their own HIP streams and run "
@@ -106,9 +117,9 @@ def parse():
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the N>1 code path (sharded phases + collectives) with a world of 1 (testing)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the short secondary workloads (psz 4, full-frame affine / homography, patch flow, "
+                    help="--full: skip the short secondary workloads (psz 4, full-frame affine / homography, patch flow, "
                          "pose-sample batch, small-problem latency) reported under \"secondary\"")
-    ap.add_argument("--secondary-seconds", type=float, default=1.0, help="time budget of each secondary record")
+    ap.add_argument("--secondary-seconds", type=float, default=1.0, help="--full: time budget of each secondary record")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="ranks only join a gloo group and all-reduce one number (CPU test of the --gpus N launcher)")
     ap.add_argument("--rehearse-p2p", action="store_true",
@@ -117,7 +128,10 @@ def parse():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="N>1 rehearsal on ONE GPU: all ranks use cuda:0 and the 27*B floats are all-reduced through "
                          "host memory with gloo (same kernels, same phase sequence; numbers are not a benchmark)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args, argv):
@@ -399,10 +413,11 @@ def main():
     from invcompcamtrack_amd import _lib
     _lib.check(_lib.load().ictr_set_device(local_rank if world > 1 else 0))
 
-    # yardstick: what a plain streaming read reaches on this box (2 GiB, far beyond the Infinity Cache)
+    # --full yardstick: what a plain streaming read reaches on this box (2 GiB, far beyond the Infinity Cache)
     import ctypes
     stream_gbps = ctypes.c_double(0.0)
-    _lib.check(_lib.load().ictr_stream_read_bandwidth(2 << 30, 5, ctypes.byref(stream_gbps)))
+    if args.full:
+        _lib.check(_lib.load().ictr_stream_read_bandwidth(2 << 30, 5, ctypes.byref(stream_gbps)))
     inp = build_inputs(args, rank, world)
     op, pyrs, scenes = inp["op"], inp["pyrs"], inp["scenes"]
     B, P, n_pts = args.batch, args.psz, inp["n_pts"]
@@ -614,6 +629,8 @@ def main():
     import gc
     gc.collect()
     gc.disable()
+    # the events stay on in a plain run too: event timing changes which launch forms the library may choose for some
+    # shapes (no one-launch tracker, no graph replay), so switching it off would change what the steps measure
     if not args.no_events:
         inp["ic"].timebase_mark()   # launch intervals of the timed steps are measured from here (device idle: barrier above)
     t0 = time.perf_counter()
@@ -628,6 +645,9 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_gpu else "cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "poses.npy"), np.asarray(poses, np.float64))
 
     iters_per_step = args.levels * args.maxiter * B           # per rank
     pix_per_iter = n_pts * P * P                               # per problem per rank
@@ -670,7 +690,7 @@ def main():
                                                                       "one 27-float record (H 21 + b 6) per pair per iteration"},
             "pose_err_vs_ground_truth": err,
         }
-        if not args.no_events:
+        if args.full and not args.no_events:
             eng_list = tracker.batches if sharded else holders[0].engs
             pairs_per_launch = eng_list[0].B           # pairs per engine: B / streams (B / groups in the sharded mode)
             n_eng_step = len(eng_list)
@@ -870,7 +890,7 @@ def main():
                                                              if overlapping else "")}
                                                 if setup_us and float(np.mean(setup_us)) > 0 else None)}
         pose_fail = False
-        if args.cpu_seconds > 0 and world == 1 and not sharded:
+        if args.full and args.cpu_seconds > 0 and world == 1 and not sharded:
             # the same tracking on the CPU path (the oracle: checker and baseline, never the product): problem 0 is
             # scene 0 with its unmodified points, so its pose is directly comparable (north star: <= 1e-4)
             p_cpu, cpu_trace, out["cpu_baseline"] = cpu_baseline(args, scenes[0], n_pts)
@@ -879,9 +899,9 @@ def main():
             pose_fail = not (out["pose_err_vs_cpu"] <= 1e-4)
             out["dp_vs_cpu"] = dp_vs_cpu(inp["ic"], args, scenes[0], n_pts, cpu_trace)
         else:
-            out["cpu_baseline"] = None  # measured on rank 0 at N=1 only
+            out["cpu_baseline"] = None  # measured with --full, on rank 0 at N=1 only
             out["pose_err_vs_cpu"] = None
-        if args.secondary and world == 1 and not sharded:
+        if args.full and args.secondary and world == 1 and not sharded:
             import gc as _gc
             holders = tracker = None
             _gc.collect()

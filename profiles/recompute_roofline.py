@@ -9,7 +9,7 @@ roofline.frac of the driver line = algorithmic bytes of one k_iter8 launch / mea
 ALONE / 8 TB/s. Algorithmic bytes: 16 B per patch pixel = T, Gx, Gy and one current-frame
 texel, x 64 pixels x points x frame pairs of the launch (frame pairs = the dispatch's grid size in y).
 
-* From a kernel TRACE of the default command (`rocprofv3 --kernel-trace --stats -- python3 bench.py`): the two engines'
+* From a kernel TRACE of the default command (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full`): the two engines'
   launches overlap during the timed steps; bench.py then launches a marker (k_stream_read) and runs the same engines
   once more on ONE stream. The k_iter8 dispatches behind the LAST marker with the headline's frame pairs per launch
   are that leg; their mean duration is what bench.py measured with HIP events. Also printed: all k_iter8 dispatches
