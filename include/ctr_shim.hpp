@@ -147,4 +147,29 @@ class OdometerClass {
   ictr_odometer *h_;
 };
 
+// Frame-to-frame sequence (run_odometer_test.m:172-250, ictr_sequence_* in include/ictr.h): every pair of a video tracked
+// from the pose just found for the earlier frame, the step between pairs on the device; one read-back at the end.
+class SequenceClass {
+ public:
+  SequenceClass(const CamClass *camobj_in, const optparam *op_in, int64_t nworld, int stride) : h_(nullptr) {
+    check(ictr_sequence_create(&h_, camobj_in->handle(), op_in, nworld, stride), "SequenceClass");
+  }
+  ~SequenceClass() { ictr_sequence_destroy(h_); }
+  SequenceClass(const SequenceClass &) = delete;
+  SequenceClass &operator=(const SequenceClass &) = delete;
+  void SetPoints(const double *pt3d /* SoA X..Y..Z.., nworld */) { check(ictr_sequence_set_points(h_, pt3d), "SetPoints"); }
+  void SetFrames(const float *frames /* [N][h][w] */, int64_t nframes, int w, int h, bool on_device = false) {
+    check(ictr_sequence_set_frames(h_, frames, nframes, w, h, on_device ? 1 : 0), "SetFrames");
+  }
+  void SetStream(void *hip_stream) { check(ictr_sequence_set_stream(h_, hip_stream), "SetStream"); }
+  void TrackAsync(const double *p0) { check(ictr_sequence_track_async(h_, p0), "TrackAsync"); }
+  void Wait(double *poses, int32_t *npts = nullptr, int32_t *iters = nullptr) {
+    check(ictr_sequence_wait(h_, poses, npts, iters), "Wait");
+  }
+  int LastTeam() const { return ictr_sequence_last_team(h_); }
+
+ private:
+  ictr_sequence *h_;
+};
+
 }  // namespace CTR

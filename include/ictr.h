@@ -392,6 +392,44 @@ int ictr_icgn_hess_finish(ictr_icgn *g, int level);
 int ictr_icgn_iter_accumulate(ictr_icgn *g, int level);
 int ictr_icgn_iter_finish(ictr_icgn *g, int level);
 
+/* ------------------------------------------------------------------ frame-to-frame sequence (run_odometer_test.m:172-250)
+ * Tracks frame t -> t+1 for every t of a video, each pair from the pose just found for frame t, with the step between
+ * two pairs on the device: no host synchronisation and no copy between pairs, one read-back at the end.
+ * Per pair t -> t+1, with p_t the tracked pose of frame t (p_0 given):
+ *   1. cull: every world point X projected at level 0 in f64, Xc = G(p_t) X (se3_exp<double>),
+ *      u = fx Xc / Zc + cx, v = fy Yc / Zc + cy; kept iff 1 <= u <= w and 1 <= v <= h (the script's bounds literally,
+ *      w, h the camera's unpadded size; NO depth test, as in the script);
+ *   2. subsample: the survivors of ranks 0, s, 2s, ... in world-index order, then Set3Dpoints' cap: the first
+ *      min(count, maxpttrack). The script passes the selected count itself as maxpttrack; here the cap is fixed at
+ *      creation, and npts == cap in the output shows where it bit;
+ *   3. Set3Dpoints (f64 meanshift / varval, patch and coefficient state reset), SetPose(p_t, pyr_t, pyr_t+1),
+ *      TrackPose -> p_t+1, as a fresh run_io_reprojection_test process would;
+ *   4. no point selected (deviation: the reference would divide by zero): p_t+1 = p_t, npts = iters = 0, continue.
+ * The launch form follows the cap: the team form where it serves the cap (psz 8), otherwise one workgroup per tracking
+ * (at most 2048 points); a cap neither serves is refused by ictr_sequence_create. nworld: 1 .. 2^24, stride >= 1. */
+typedef struct ictr_sequence ictr_sequence;
+int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, const ictr_optparam *op, int64_t nworld, int stride);
+void ictr_sequence_destroy(ictr_sequence *s);
+/* The setters below are refused (ICTR_ERR_STATE) while a run is in flight: call ictr_sequence_wait first.
+ * world points, f64 SoA X[nworld] Y[nworld] Z[nworld]; copied to the device once (never modified) */
+int ictr_sequence_set_points(ictr_sequence *s, const double *pt3d);
+/* frames [N][h][w] f32 of the camera's unpadded size (w, h are checked against it), N >= 2. Host frames are copied to
+ * the device once; on_device frames are borrowed until ictr_sequence_wait. */
+int ictr_sequence_set_frames(ictr_sequence *s, const float *frames, int64_t nframes, int w, int h, int on_device);
+int ictr_sequence_set_stream(ictr_sequence *s, void *hip_stream);
+/* a sequence runs the plain one-launch forms only: any robustness flag is refused (ICTR_ERR_INVALID) */
+int ictr_sequence_set_robust(ictr_sequence *s, int flags, float huber_k);
+/* enqueues the whole sequence from p0 (6 f64) and returns */
+int ictr_sequence_track_async(ictr_sequence *s, const double *p0);
+/* waits for the last run: poses [N][6] (poses[0] = p0), npts / iters [N-1] per pair (any may be NULL) */
+int ictr_sequence_wait(ictr_sequence *s, double *poses, int32_t *npts, int32_t *iters);
+/* inspection, after wait: per pair an order-aware 64-bit hash of the selected world indices,
+ * sum over k < npts of splitmix64((k << 32) | index_k) modulo 2^64 */
+int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out);
+/* workgroups per tracking launch of the last run (before the first run: the form the cap selects):
+ * 1 = the single-workgroup form, > 1 = the team form */
+int ictr_sequence_last_team(const ictr_sequence *s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,16 @@ SIGNATURES = {
     "ictr_icgn_hess_finish": (C.c_int, [VP, C.c_int]),
     "ictr_icgn_iter_accumulate": (C.c_int, [VP, C.c_int]),
     "ictr_icgn_iter_finish": (C.c_int, [VP, C.c_int]),
+    "ictr_sequence_create": (C.c_int, [C.POINTER(VP), VP, C.POINTER(OptParam), I64, C.c_int]),
+    "ictr_sequence_destroy": (None, [VP]),
+    "ictr_sequence_set_points": (C.c_int, [VP, DP]),
+    "ictr_sequence_set_frames": (C.c_int, [VP, VP, I64, C.c_int, C.c_int, C.c_int]),
+    "ictr_sequence_set_stream": (C.c_int, [VP, VP]),
+    "ictr_sequence_set_robust": (C.c_int, [VP, C.c_int, C.c_float]),
+    "ictr_sequence_track_async": (C.c_int, [VP, DP]),
+    "ictr_sequence_wait": (C.c_int, [VP, DP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ictr_sequence_selection_hashes": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "ictr_sequence_last_team": (C.c_int, [VP]),
 }
 
 _lib = None

@@ -107,6 +107,38 @@ struct EngineDev {
   DevTrace trace;
 };
 
+// frame-to-frame sequence (ictr_sequence.hip): the between-pairs step on the device
+constexpr int kSeqBlock = 256;                 // threads of the count / scatter workgroups
+constexpr int kSeqPPT = 16;                    // world points per thread there
+constexpr int kSeqChunk = kSeqBlock * kSeqPPT; // world points per workgroup (64 survivor masks)
+constexpr int kSeqFinish = 256;                // threads of the one-workgroup finish
+struct SeqState {       // carried from one pair to the next
+  double pose[6];       // p_t of the pair being prepared (f64, as TrackPose returns it)
+  double G[12];         // se3_exp<double>(p_t): the camera of the cull
+  double ms[3], varval; // normalisation of the pair's selected points (Set3Dpoints)
+  int npts;             // selected points of the pair (0: the pair is lost, its pose is carried)
+  int pad_[3];
+};
+struct SeqArgs {
+  const double *X;   // world points, SoA X[nw] Y[nw] Z[nw]
+  long long nw;
+  int nblk;          // workgroups of the count / scatter launches (kSeqChunk points each)
+  int stride, cap, M, n, donorm;
+  int t;             // pair t -> t+1 being prepared; t = N-1: finish-only (the last pose and pair N-2's iterations)
+  int tail;
+  double fx, fy, cx, cy, w, h;  // level-0 camera (f32 values) and the unpadded frame size
+  double p0[6];      // pose of frame 0
+  ProbState *st;     // the engine's record (B = 1): the previous pair's final state on entry, the next initial state out
+  SeqState *ss;
+  unsigned long long *mask;  // [nblk][kSeqChunk / 64] survivor bits, one word per wave and step
+  unsigned *cnt;             // [nblk] survivors per workgroup
+  int *sel;                  // [cap] world indices of the selected points
+  double *poses;             // [N][6]
+  unsigned long long *hash;  // [N-1] order-aware hash of each pair's selected indices
+  int *npts_out, *iters_out; // [N-1]
+  float *pt3d, *T, *Gx, *Gy, *coef;  // the engine's buffers (problem 0)
+};
+
 // per-patch translation IC-LK (ictr_patchflow.hip)
 struct PFLevel {
   const float *a, *ax, *ay, *b;  // frame A image + gradients, frame B image (padded planes)

@@ -17,6 +17,7 @@
 
 #include "ictr_dev.h"
 #include "se3_math.h"
+#include "ictr_pose_hd.h"
 
 namespace ictr {
 void launch_pyr_copy(const float *, float *, int, int, int, int, hipStream_t);
@@ -55,6 +56,7 @@ int track1_team_size(int, int);
 size_t track1_team_mail_bytes(int, int);
 size_t track1_blob_bytes(void);
 size_t track1_plan(int, int, int, int, int *);
+void launch_seq_select(const SeqArgs &, hipStream_t);
 }  // namespace ictr
 
 namespace ictr {
@@ -248,51 +250,6 @@ extern "C" void ictr_solve6(const float *H, const float *b, float *x) {
   memcpy(A, H, sizeof(A));
   lu_factor_ws<6>(A, piv, info);
   lu_apply_ws<6>(A, piv, info, b, x, c);
-}
-
-// pose.cpp:25-76
-static void host_setpose(bool donorm, const double *p_in, const double *ms, double varval, float *p_f, float *G_f) {
-  double pn[6];
-  memcpy(pn, p_in, sizeof(pn));
-  if (donorm) {
-    double G[12];
-    se3_exp<double>(G, pn);
-    double t[3];
-    t[0] = -G[0] * G[3] - G[4] * G[7] - G[8] * G[11];
-    t[1] = -G[1] * G[3] - G[5] * G[7] - G[9] * G[11];
-    t[2] = -G[2] * G[3] - G[6] * G[7] - G[10] * G[11];
-    t[0] = (t[0] - ms[0]) / varval;
-    t[1] = (t[1] - ms[1]) / varval;
-    t[2] = (t[2] - ms[2]) / varval;
-    G[3] = -G[0] * t[0] - G[1] * t[1] - G[2] * t[2];
-    G[7] = -G[4] * t[0] - G[5] * t[1] - G[6] * t[2];
-    G[11] = -G[8] * t[0] - G[9] * t[1] - G[10] * t[2];
-    se3_log<double>(pn, G);
-  }
-  for (int i = 0; i < 6; ++i) p_f[i] = (float)pn[i];
-  se3_exp<float>(G_f, p_f);
-}
-// pose.cpp:79-113 (f32 G, f64 camera centre, f32 log: the reference's mixed precision is kept)
-static void host_getpose(bool donorm, const float *p_f, const float *G_f, const double *ms, double varval,
-                         double *p_out) {
-  float pu[6];
-  memcpy(pu, p_f, sizeof(pu));
-  if (donorm) {
-    float G[12];
-    memcpy(G, G_f, sizeof(G));
-    double t[3];
-    t[0] = (double)(-G[0] * G[3] - G[4] * G[7] - G[8] * G[11]);
-    t[1] = (double)(-G[1] * G[3] - G[5] * G[7] - G[9] * G[11]);
-    t[2] = (double)(-G[2] * G[3] - G[6] * G[7] - G[10] * G[11]);
-    t[0] = t[0] * varval + ms[0];
-    t[1] = t[1] * varval + ms[1];
-    t[2] = t[2] * varval + ms[2];
-    G[3] = (float)(-G[0] * t[0] - G[1] * t[1] - G[2] * t[2]);
-    G[7] = (float)(-G[4] * t[0] - G[5] * t[1] - G[6] * t[2]);
-    G[11] = (float)(-G[8] * t[0] - G[9] * t[1] - G[10] * t[2]);
-    se3_log<float>(pu, G);
-  }
-  for (int i = 0; i < 6; ++i) p_out[i] = (double)pu[i];
 }
 
 // ---------------------------------------------------------------- pyramid
@@ -2240,3 +2197,308 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
   if (e != hipSuccess) return fail(ICTR_ERR_HIP, "patchflow failed: %s", hipGetErrorString(e));
   return ICTR_OK;
 }
+
+// ---------------------------------------------------------------- frame-to-frame sequence (run_odometer_test.m:172-250)
+// One engine of one problem (B = 1) tracks frame t -> t+1 from the pose found for frame t, for every t, with the step
+// between two pairs on the device (ictr_sequence.hip): per pair one pyramid build, the selection launches and ONE
+// one-launch tracking, all on one stream; no host synchronisation and no copy until the results come back at the end.
+// The launch form follows the cap (maxpttrack), decided once at creation: the team form where track1_team takes the
+// cap (psz 8), else one workgroup per tracking while the cap's point records fit its LDS; anything else is refused.
+struct ictr_sequence {
+  const ictr_cam *cam = nullptr;
+  ictr_optparam op;
+  ictr_batch *b = nullptr;
+  int64_t nw = 0;
+  int stride = 10, nblk = 0, team = 1;
+  hipStream_t stream = nullptr;
+  double *d_world = nullptr;
+  unsigned long long *d_mask = nullptr;
+  unsigned *d_cnt = nullptr;
+  int *d_sel = nullptr;
+  SeqState *d_ss = nullptr;
+  ictr_pyramid *ring[2] = {nullptr, nullptr};
+  PlaneSet *d_tab = nullptr;  // [2][nlev]: (ring 0 -> ring 1), (ring 1 -> ring 0)
+  const float *frames = nullptr;  // [N][h][w] on the device (borrowed, or d_frames_own)
+  float *d_frames_own = nullptr;
+  size_t own_bytes = 0;
+  int64_t nframes = 0;
+  char *d_out = nullptr, *h_out = nullptr;  // poses [N][6] f64 | hash [N-1] u64 | npts [N-1] i32 | iters [N-1] i32
+  int64_t out_frames = 0;
+  int64_t run_frames = 0;  // frames of the last run (its results' layout in h_out)
+  bool points_set = false, pending = false, ran = false;
+  hipEvent_t done = nullptr;
+};
+
+static size_t seq_out_bytes(int64_t N) { return (size_t)N * 48 + (size_t)(N - 1) * 16; }
+
+static void seq_free(ictr_sequence *s) {
+  if (!s) return;
+  if (s->pending) (void)hipEventSynchronize(s->done);
+  if (s->done) (void)hipEventDestroy(s->done);
+  if (s->h_out) (void)hipHostFree(s->h_out);
+  for (void *p : {(void *)s->d_world, (void *)s->d_mask, (void *)s->d_cnt, (void *)s->d_sel, (void *)s->d_ss,
+                  (void *)s->d_tab, (void *)s->d_frames_own, (void *)s->d_out})
+    if (p) (void)hipFree(p);
+  for (ictr_pyramid *p : s->ring) ictr_pyramid_destroy(p);
+  if (s->b) batch_free(s->b);
+  delete s;
+}
+
+// the inputs of a run stay fixed until its wait
+static int seq_refuse_pending(const ictr_sequence *s, const char *what) {
+  if (s->pending)
+    return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_sequence_wait first", what);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, const ictr_optparam *op, int64_t nworld,
+                                    int stride) {
+  if (!out || !cam || !op) return fail(ICTR_ERR_INVALID, "sequence_create: NULL argument");
+  if (nworld < 1 || nworld > (int64_t)1 << 24)
+    return fail(ICTR_ERR_INVALID, "sequence_create: %lld world points (1 .. 2^24)", (long long)nworld);
+  if (stride < 1) return fail(ICTR_ERR_INVALID, "sequence_create: the subsampling stride must be >= 1");
+  if (int rc = check_op(op, cam)) return rc;
+  if (int rc = need_device()) return rc;
+  ictr_sequence *s = new ictr_sequence;
+  s->cam = cam;
+  s->op = *op;
+  s->nw = nworld;
+  s->stride = stride;
+  s->nblk = (int)((nworld + kSeqChunk - 1) / kSeqChunk);
+  if (int rc = ictr_batch_create(&s->b, cam, &s->op, 1)) {
+    delete s;
+    return rc;
+  }
+  ictr_batch *b = s->b;
+  // the engine as every pair's tracking sees it: builder-made gradient pyramids (otf = 1, packed planes), the cap as
+  // the point capacity of the launch
+  b->maxpts = b->M;
+  b->packed = 1;
+  b->otf = 1;
+  s->team = track1_team(b);
+  if (s->team < 2) {
+    s->team = 1;
+    if ((size_t)b->M * 64 > 128 * 1024) {
+      const int cap = b->M;
+      seq_free(s);
+      return fail(ICTR_ERR_INVALID, "sequence_create: a cap (maxpttrack) of %d points has no one-launch form: one workgroup "
+                                    "holds at most 2048 point records, and the team form serves psz 8 only, up to 8192 "
+                                    "points", cap);
+    }
+  }
+  const int L = b->nlev;
+  hipError_t e = hipSuccess;
+  auto alloc = [&](void **p, size_t bytes) {
+    if (e == hipSuccess) e = hipMalloc(p, bytes);
+    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+  };
+  alloc((void **)&s->d_world, sizeof(double) * 3 * nworld);
+  alloc((void **)&s->d_mask, sizeof(unsigned long long) * (size_t)s->nblk * (kSeqChunk / 64));
+  alloc((void **)&s->d_cnt, sizeof(unsigned) * s->nblk);
+  alloc((void **)&s->d_sel, sizeof(int) * b->M);
+  alloc((void **)&s->d_ss, sizeof(SeqState));
+  alloc((void **)&s->d_tab, sizeof(PlaneSet) * 2 * L);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    seq_free(s);
+    return fail(ICTR_ERR_HIP, "sequence_create: device allocation failed: %s", hipGetErrorString(e));
+  }
+  for (int k = 0; k < 2; ++k)
+    if (int rc = pyramid_alloc(&s->ring[k], cam->wh[0], cam->wh[1], op->lv_f, 1, cam->padding)) {
+      seq_free(s);
+      return rc;
+    }
+  // both orders of the plane table, once: pair t reads table t % 2 (reference = frame t's pyramid, ring[t % 2])
+  std::vector<PlaneSet> tab(2 * L);
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < L; ++l) {
+      const ictr_pyramid *r = s->ring[k], *c = s->ring[1 - k];
+      tab[k * L + l] = PlaneSet{r->img[l], r->dx[l], r->dy[l], c->img[l], r->pack[l]};
+    }
+  e = hipMemcpy(s->d_tab, tab.data(), sizeof(PlaneSet) * 2 * L, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    seq_free(s);
+    return fail(ICTR_ERR_HIP, "sequence_create: plane table upload failed: %s", hipGetErrorString(e));
+  }
+  if (s->team > 1) {  // the mailbox now, not inside the first track_async
+    T1Team tm;
+    if (int rc = team_prepare(b, &tm)) {
+      seq_free(s);
+      return rc;
+    }
+    if (hipStreamSynchronize(b->stream) != hipSuccess) {
+      seq_free(s);
+      return fail(ICTR_ERR_HIP, "sequence_create: mailbox initialisation failed");
+    }
+  }
+  *out = s;
+  return ICTR_OK;
+}
+
+extern "C" void ictr_sequence_destroy(ictr_sequence *s) { seq_free(s); }
+
+extern "C" int ictr_sequence_set_points(ictr_sequence *s, const double *pt3d) {
+  if (!s || !pt3d) return fail(ICTR_ERR_INVALID, "sequence_set_points: NULL argument");
+  if (int rc = seq_refuse_pending(s, "sequence_set_points")) return rc;
+  HIPCHK(hipMemcpy(s->d_world, pt3d, sizeof(double) * 3 * s->nw, hipMemcpyHostToDevice));
+  s->points_set = true;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_set_frames(ictr_sequence *s, const float *frames, int64_t nframes, int w, int h,
+                                        int on_device) {
+  if (!s || !frames) return fail(ICTR_ERR_INVALID, "sequence_set_frames: NULL argument");
+  if (nframes < 2) return fail(ICTR_ERR_INVALID, "sequence_set_frames: %lld frames, a sequence needs at least 2",
+                               (long long)nframes);
+  if (w != s->cam->wh[0] || h != s->cam->wh[1])
+    return fail(ICTR_ERR_INVALID, "sequence_set_frames: frames are %dx%d, the camera's are %dx%d", w, h, s->cam->wh[0],
+                s->cam->wh[1]);
+  if (int rc = seq_refuse_pending(s, "sequence_set_frames")) return rc;
+  const size_t bytes = sizeof(float) * (size_t)w * h * nframes;
+  if (on_device) {
+    s->frames = frames;
+  } else {
+    if (bytes > s->own_bytes) {
+      if (s->d_frames_own) HIPCHK(hipFree(s->d_frames_own));
+      s->d_frames_own = nullptr;
+      s->own_bytes = 0;
+      HIPCHK(hipMalloc((void **)&s->d_frames_own, bytes));
+      s->own_bytes = bytes;
+    }
+    HIPCHK(hipMemcpy(s->d_frames_own, frames, bytes, hipMemcpyHostToDevice));
+    s->frames = s->d_frames_own;
+  }
+  if (nframes > s->out_frames) {  // result buffers sized here, so that track_async allocates nothing
+    if (s->d_out) HIPCHK(hipFree(s->d_out));
+    if (s->h_out) HIPCHK(hipHostFree(s->h_out));
+    s->d_out = s->h_out = nullptr;
+    s->out_frames = 0;
+    HIPCHK(hipMalloc((void **)&s->d_out, seq_out_bytes(nframes)));
+    HIPCHK(hipHostMalloc((void **)&s->h_out, seq_out_bytes(nframes), hipHostMallocDefault));
+    s->out_frames = nframes;
+  }
+  s->nframes = nframes;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_set_stream(ictr_sequence *s, void *hip_stream) {
+  if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
+  if (int rc = seq_refuse_pending(s, "sequence_set_stream")) return rc;
+  s->stream = (hipStream_t)hip_stream;
+  s->b->stream = s->stream;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_set_robust(ictr_sequence *s, int flags, float huber_k) {
+  if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
+  (void)huber_k;
+  if (flags != 0)
+    return fail(ICTR_ERR_INVALID, "sequence_set_robust: a sequence runs the plain one-launch forms only; robustness "
+                                  "options (0x%x) are not available", flags);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
+  if (!s || !p0) return fail(ICTR_ERR_INVALID, "sequence_track_async: NULL argument");
+  if (!s->points_set) return fail(ICTR_ERR_STATE, "sequence_track_async: ictr_sequence_set_points has not been called");
+  if (!s->frames || s->nframes < 2) return fail(ICTR_ERR_STATE, "sequence_track_async: no frames set");
+  if (s->pending) return fail(ICTR_ERR_STATE, "sequence_track_async: wait for the previous run first");
+  ictr_batch *b = s->b;
+  if (b->h_team_err && *(volatile int *)b->h_team_err) {  // an earlier run timed out (reported by its wait)
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *(volatile int *)b->h_team_err = 0;
+  }
+  const int64_t N = s->nframes;
+  const int w = s->cam->wh[0], h = s->cam->wh[1], L = b->nlev;
+  const size_t plane = (size_t)w * h;
+  LevelCam cams[16];
+  for (int l = 0; l < L; ++l) cams[l] = level_cam(s->cam, l);
+  SeqArgs a;
+  memset(&a, 0, sizeof(a));
+  a.X = s->d_world;
+  a.nw = s->nw;
+  a.nblk = s->nblk;
+  a.stride = s->stride;
+  a.cap = b->M;
+  a.M = b->M;
+  a.n = b->n;
+  a.donorm = s->op.donorm ? 1 : 0;
+  a.fx = s->cam->fx[0];
+  a.fy = s->cam->fy[0];
+  a.cx = s->cam->cx[0];
+  a.cy = s->cam->cy[0];
+  a.w = (double)w;
+  a.h = (double)h;
+  memcpy(a.p0, p0, sizeof(a.p0));
+  a.st = b->d_st;
+  a.ss = s->d_ss;
+  a.mask = s->d_mask;
+  a.cnt = s->d_cnt;
+  a.sel = s->d_sel;
+  a.poses = reinterpret_cast<double *>(s->d_out);
+  a.hash = reinterpret_cast<unsigned long long *>(s->d_out + (size_t)N * 48);
+  a.npts_out = reinterpret_cast<int *>(s->d_out + (size_t)N * 48 + (size_t)(N - 1) * 8);
+  a.iters_out = a.npts_out + (N - 1);
+  a.pt3d = b->d_pt3d;
+  a.T = b->d_T;
+  a.Gx = b->d_Gx;
+  a.Gy = b->d_Gy;
+  a.coef = b->d_coef;
+  if (int rc = pyramid_build(s->ring[0], s->frames, s->stream)) return rc;
+  for (int64_t t = 0; t + 1 < N; ++t) {
+    if (int rc = pyramid_build(s->ring[(t + 1) & 1], s->frames + (size_t)(t + 1) * plane, s->stream)) return rc;
+    a.t = (int)t;
+    a.tail = 0;
+    launch_seq_select(a, s->stream);
+    HIPCHK(hipGetLastError());
+    EngineDev e = engine_dev(b);
+    e.planes = s->d_tab + (t & 1) * L;
+    T1Team tm;
+    if (int rc = team_prepare(b, &tm)) return rc;
+    auto launch = [&]() -> int {
+      HIPCHK(launch_track1(e, cams, b->M, track1_waves(b), nullptr, nullptr, s->stream, tm.team > 1 ? &tm : nullptr,
+                           true));
+      return ICTR_OK;
+    };
+    if (tm.team > 1) {
+      if (int rc = team_launch(4 * (tm.team - 1), s->stream, launch)) return rc;
+    } else if (int rc = launch()) {
+      return rc;
+    }
+    b->last_team = tm.team;
+    b->last_path = 1;
+  }
+  a.t = (int)(N - 1);
+  a.tail = 1;
+  launch_seq_select(a, s->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s->h_out, s->d_out, seq_out_bytes(N), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipEventRecord(s->done, s->stream));
+  s->pending = true;
+  s->ran = true;
+  s->run_frames = N;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_wait(ictr_sequence *s, double *poses, int32_t *npts, int32_t *iters) {
+  if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
+  if (!s->pending) return fail(ICTR_ERR_STATE, "sequence_wait: nothing has been tracked");
+  HIPCHK(hipEventSynchronize(s->done));
+  s->pending = false;
+  if (int rc = team_error_check(s->b)) return rc;
+  const int64_t N = s->run_frames;
+  if (poses) memcpy(poses, s->h_out, sizeof(double) * 6 * N);
+  if (npts) memcpy(npts, s->h_out + (size_t)N * 48 + (size_t)(N - 1) * 8, sizeof(int32_t) * (N - 1));
+  if (iters) memcpy(iters, s->h_out + (size_t)N * 48 + (size_t)(N - 1) * 12, sizeof(int32_t) * (N - 1));
+  return ICTR_OK;
+}
+
+extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out) {
+  if (!s || !out) return fail(ICTR_ERR_INVALID, "sequence_selection_hashes: NULL argument");
+  if (s->pending || !s->ran) return fail(ICTR_ERR_STATE, "sequence_selection_hashes: no completed run");
+  memcpy(out, s->h_out + (size_t)s->run_frames * 48, sizeof(uint64_t) * (s->run_frames - 1));
+  return ICTR_OK;
+}
+
+// workgroups per tracking launch of the last run (before the first run: the form the cap selects)
+extern "C" int ictr_sequence_last_team(const ictr_sequence *s) { return !s ? 0 : s->ran ? s->b->last_team : s->team; }

@@ -17,7 +17,7 @@ import struct
 
 import numpy as np
 
-__all__ = ["read_pointcam_file", "write_pointcam_file", "read_pose_result", "write_pose_result", "read_image_gray",
+__all__ = ["read_pointcam_file", "read_pointcam_file_uncapped", "read_image_list", "write_pointcam_file", "read_pose_result", "write_pose_result", "read_image_gray",
            "read_nposes_input", "write_nposes_input", "write_nposes_result", "read_nposes_result"]
 
 MAXPTREAD = 10000  # run_io_reprojection_test.cpp:37
@@ -36,6 +36,24 @@ def read_pointcam_file(filename):
         rest = f.read(8 * n)
         xy = np.frombuffer(rest, "<f4").reshape(2, n).copy() if len(rest) == 8 * n else np.zeros((2, n), np.float32)
     return dict(pose=pose, fc=fc, cc=cc, wh=wh, pts3d=np.ascontiguousarray(xyz), pts2d=xy)
+
+
+def read_pointcam_file_uncapped(filename):
+    """read_pointcam_file without the reference's MAXPTREAD cap: a whole model (run_track_sequence) can hold more."""
+    with open(filename, "rb") as f:
+        pose = np.frombuffer(f.read(48), "<f8").copy()
+        fc = np.frombuffer(f.read(8), "<f4").copy()
+        cc = np.frombuffer(f.read(8), "<f4").copy()
+        wh = np.frombuffer(f.read(8), "<u4").astype(np.int32)
+        (n,) = struct.unpack("<Q", f.read(8))
+        xyz = np.frombuffer(f.read(24 * n), "<f8").reshape(3, n).copy()
+    return dict(pose=pose, fc=fc, cc=cc, wh=wh, pts3d=np.ascontiguousarray(xyz))
+
+
+def read_image_list(filename):
+    """One image path per line (blank lines skipped)."""
+    with open(filename) as f:
+        return [ln.strip() for ln in f if ln.strip()]
 
 
 def write_pointcam_file(filename, pose, fc, cc, wh, pts3d, pts2d=None):
