@@ -172,4 +172,32 @@ class SequenceClass {
   ictr_sequence *h_;
 };
 
+// RANSAC pose sampling from 2-D/3-D matches (func_ransac_fitcameras_odom.m:17-87, ictr_ransac_* in include/ictr.h): the
+// hypothesis stage on the device, one read-back at the end.
+class RansacClass {
+ public:
+  RansacClass(int64_t n, int64_t max_samples) : h_(nullptr), n_(n), smax_(max_samples) {
+    check(ictr_ransac_create(&h_, n, max_samples), "RansacClass");
+  }
+  ~RansacClass() { ictr_ransac_destroy(h_); }
+  RansacClass(const RansacClass &) = delete;
+  RansacClass &operator=(const RansacClass &) = delete;
+  void SetPoints(const double *pt2d /* SoA x.. y.. */, const double *pt3d /* SoA X.. Y.. Z.. */) {
+    check(ictr_ransac_set_points(h_, pt2d, pt3d), "SetPoints");
+  }
+  void Run(const double *fc, const double *cc, double kc, int64_t nsamples, int64_t maxtrials, double inlthresh,
+           uint64_t seed = 0, void *hip_stream = nullptr) {
+    check(ictr_ransac_run(h_, fc, cc, kc, nsamples, maxtrials, inlthresh, seed, hip_stream), "Run");
+  }
+  // counts[4] as ictr_ransac_wait; buffers sized for max_samples (inl_words: max_samples * WordsPerSample()) and N
+  void Wait(int64_t *counts, double *R, double *t, double *p, uint64_t *inl_words, int32_t *inl_cnt) {
+    check(ictr_ransac_wait(h_, counts, R, t, p, inl_words, inl_cnt), "Wait");
+  }
+  int64_t WordsPerSample() const { return (n_ + 63) / 64; }
+
+ private:
+  ictr_ransac *h_;
+  int64_t n_, smax_;
+};
+
 }  // namespace CTR

@@ -430,6 +430,43 @@ int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out);
  * 1 = the single-workgroup form, > 1 = the team form */
 int ictr_sequence_last_team(const ictr_sequence *s);
 
+/* ------------------------------------------------------------------ RANSAC pose sampling (func_ransac_fitcameras_odom.m:17-87)
+ * From N 2-D/3-D matches, pose samples as the script draws them, with these deviations:
+ *   - trial t (0-based) draws from a counter-based stream, u_k = mix(mix(seed) ^ ((t << 32) | k)), k = 0, 1, ...,
+ *     mix = splitmix64; index ((u_k >> 32) * N) >> 32; repeats skipped; the first 4 distinct indices in draw order.
+ *     Not reproducible against MATLAB's randsample; every run is bit-reproducible.
+ *   - 2-D points are undistorted for the solver with one radial coefficient kc (x_d = x_n (1 + kc |x_n|^2), 20
+ *     fixed-point steps); the same model distorts the reprojections. kc = 0: the plain pinhole.
+ *   - degenfn_P literally (|dot(cross(p1, p2), p3)| < 2^-52 over every triple, 3-D points and homogeneous undistorted
+ *     2-D points), then P3P (Lambda Twist) on the first three matches; of its solutions the one that reprojects the
+ *     fourth match nearest (first on ties). None: the trial fails.
+ *   - a match is an inlier when |reproj(R (X - t)) - pt2d| <= inlthresh (f64, no depth test); a trial succeeds with
+ *     >= 4 inliers. The first nsamples successes among trials 0 .. maxtrials-1 are accepted.
+ *   - post-filter: inl_cnt[j] = accepted samples that have match j as an inlier; sample s is dropped when s < N and
+ *     inl_cnt[s] <= 4 (the script's logical index over matches applied to samples); inl_cnt loses its entries <= 4.
+ * Inputs N: 4 .. 2^24, max_samples: 1 .. 2^24. */
+typedef struct ictr_ransac ictr_ransac;
+int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samples);
+void ictr_ransac_destroy(ictr_ransac *r);
+/* pt2d f64 SoA x[N] y[N] (pixels, distorted), pt3d f64 SoA X[N] Y[N] Z[N]; refused (ICTR_ERR_STATE) while a run is in
+ * flight */
+int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const double *pt3d);
+/* enqueues the trials on hip_stream (NULL: the null stream) and returns; fc, cc: 2 f64 each. nsamples: 1 .. max_samples,
+ * maxtrials: 1 .. 2^40, inlthresh finite. Runs of more than 64 chunks read a 4-byte flag between groups of 64 chunks
+ * (a host wait) and stop enqueueing once the samples are found. */
+int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples, int64_t maxtrials,
+                    double inlthresh, uint64_t seed, void *hip_stream);
+/* waits for the last run. counts[4]: samples after the post-filter (S), accepted samples before it, trials the script
+ * would have used, entries of the filtered inl_cnt. Per kept sample (any pointer may be NULL): R [S][9] row-major,
+ * camera centre t [S][3], p = se3_log([R | -R t]) [S][6], inlier bits [S][ceil(N / 64)] (bit j % 64 of word j / 64 =
+ * match j); inl_cnt [counts[3]] (at most N entries). */
+int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, double *t, double *p, uint64_t *inl_words,
+                     int32_t *inl_cnt);
+/* inspection, after wait: per kept sample its trial index and its 4 drawn match indices (draw order) */
+int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws);
+/* trials per chunk of this object (ICTR_RANSAC_CHUNK overrides the choice made from N) */
+int ictr_ransac_chunk_size(const ictr_ransac *r);
+
 #ifdef __cplusplus
 }
 #endif

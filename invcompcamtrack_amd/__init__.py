@@ -8,6 +8,7 @@ from .tracker import (CamClass, OdometerClass, PoseClass, Pyramid, TrackBatch, d
                       solve6,
                       util_constructpyramide, util_getPatch, util_getPatch_grad, util_SE3_coeff_to_group,
                       util_SE3_group_to_coeff)
+from .ransac import fit_cameras_odom, sample_poses, sample_poses_host  # noqa: F401
 from .sequence import SequenceTracker, select_points, track_sequence, track_sequence_host_loop  # noqa: F401
 
 __version__ = "0.1.0"

@@ -177,6 +177,13 @@ SIGNATURES = {
     "ictr_sequence_wait": (C.c_int, [VP, DP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ictr_sequence_selection_hashes": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
     "ictr_sequence_last_team": (C.c_int, [VP]),
+    "ictr_ransac_create": (C.c_int, [C.POINTER(VP), I64, I64]),
+    "ictr_ransac_destroy": (None, [VP]),
+    "ictr_ransac_set_points": (C.c_int, [VP, DP, DP]),
+    "ictr_ransac_run": (C.c_int, [VP, DP, DP, C.c_double, I64, I64, C.c_double, C.c_uint64, VP]),
+    "ictr_ransac_wait": (C.c_int, [VP, C.POINTER(I64), DP, DP, DP, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "ictr_ransac_samples": (C.c_int, [VP, C.POINTER(I64), C.POINTER(C.c_int32)]),
+    "ictr_ransac_chunk_size": (C.c_int, [VP]),
 }
 
 _lib = None

@@ -139,6 +139,42 @@ struct SeqArgs {
   float *pt3d, *T, *Gx, *Gy, *coef;  // the engine's buffers (problem 0)
 };
 
+// RANSAC pose sampling from 2-D/3-D matches (ictr_ransac.hip)
+constexpr int kRanHypBlock = 64;     // one lane per trial
+constexpr int kRanScoreBlock = 256;  // four waves, one 64-match block each
+constexpr int kRanSelBlock = 1024;   // the one-workgroup select / finish
+constexpr int kRanMaxDraws = 1024;   // draws per trial before it counts as failed (N >= 4: never reached in practice)
+struct RansacState {
+  long long held;         // accepted samples so far (the script's successes, trial order)
+  long long trials_used;  // trials the script would have consumed
+  long long kept;         // samples after the post-filter
+  long long n_ic;         // entries of the filtered inl_cnt
+  int done;               // nsamples held or maxtrials reached: later chunks exit at once
+  int pad_[3];
+};
+struct RansacArgs {
+  const double *pts;      // SoA u[n] v[n] X[n] Y[n] Z[n] (f64)
+  int n, nwords;          // matches, 64-bit inlier words per sample
+  double fx, fy, cx, cy, kc, thr;
+  unsigned long long seedmix;  // mix(seed)
+  long long base;         // global index of the chunk's first trial
+  int k;                  // trials of this chunk
+  long long nsamples, maxtrials;
+  double *hyp;            // [K][12]: R row-major, camera centre t
+  int *draws;             // [K][4] drawn match indices, draw order
+  int *status;            // [K] 1 = not degenerate and a P3P root chosen
+  unsigned *cnt;          // [K] inliers
+  unsigned long long *words;  // [K][nwords] inlier bits
+  RansacState *st;
+  long long *o_trial;     // [S] accepted trial indices
+  int *o_draws;           // [S][4]
+  double *o_R, *o_t;     // [S][9], [S][3]
+  unsigned long long *o_words;  // [S][nwords]
+  int *o_cnt;             // [n] inl_cnt: times each match is an inlier of an accepted sample
+  int *o_keep;            // [S] accepted samples kept by the post-filter (ascending)
+  int *o_cntf;            // [n] inl_cnt without the entries <= 4
+};
+
 // per-patch translation IC-LK (ictr_patchflow.hip)
 struct PFLevel {
   const float *a, *ax, *ay, *b;  // frame A image + gradients, frame B image (padded planes)

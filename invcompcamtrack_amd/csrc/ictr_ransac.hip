@@ -1,0 +1,531 @@
+// ictr_ransac.hip -- the hypothesis stage of func_ransac_fitcameras_odom.m (:17-87) on the device.
+//
+// The trials run in chunks of K, all enqueued on one stream with no host wait between chunks:
+//
+//   k_ransac_hyp     one lane per trial: 4 distinct match indices from the counter-based stream, undistortion of their
+//                    2-D points, the script's degeneracy test (f64), P3P (Lambda Twist) on the first three matches and
+//                    the root that reprojects the fourth best -> R, camera centre t and a status.
+//   k_ransac_score   a workgroup holds a tile of the chunk's hypotheses in LDS; each wave sweeps one 64-match block:
+//                    one ballot per hypothesis gives one 64-bit inlier word, popcounts give the counts (integers).
+//   k_ransac_select  one workgroup, trial order: successes (status 1, >= 4 inliers, trial < maxtrials) ranked with
+//                    ballots and scans, the first nsamples overall accepted; their trial index, draws, R, t and inlier
+//                    words copied to the outputs (the log map p = se3_log([R | -R t]) is taken at the read-back, on the
+//                    host: the f64 trigonometry of se3_log would put this kernel into scratch memory). Sets `done` when nsamples are held or maxtrials is reached.
+//   k_ransac_colsum  after the last chunk: inl_cnt, integer column sums of the accepted rows' inlier bits.
+//   k_ransac_finish  one workgroup: the post-filter's compactions (samples s < min(S, N) with inl_cnt[s] <= 4 dropped;
+//                    inl_cnt without its entries <= 4), both order-preserving.
+//
+// Every result is decided by integers and fixed-order f64 arithmetic: the same bits on every run and for every K.
+#include "ictr_dev.h"
+
+namespace ictr {
+
+__device__ __forceinline__ unsigned long long ran_mix(unsigned long long z) {  // splitmix64
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ double triple(const double *a, const double *b, const double *c) {
+  const double c0 = a[1] * b[2] - a[2] * b[1];
+  const double c1 = a[2] * b[0] - a[0] * b[2];
+  const double c2 = a[0] * b[1] - a[1] * b[0];
+  return c0 * c[0] + c1 * c[1] + c2 * c[2];
+}
+
+// real roots of x^2 + b x + c (stable form); false when complex
+__device__ __forceinline__ bool root2real(double b, double c, double &r1, double &r2) {
+  const double v = b * b - 4.0 * c;
+  if (v < 0.0) return false;
+  const double y = sqrt(v);
+  const double q = b < 0.0 ? 0.5 * (-b + y) : 0.5 * (-b - y);
+  r1 = q;
+  r2 = q != 0.0 ? c / q : 0.0;
+  return true;
+}
+
+// an extreme real root of x^3 + b x^2 + c x + d (Lambda Twist's cubick)
+__device__ double cubick(double b, double c, double d) {
+  double r0;
+  if (b * b >= 3.0 * c) {
+    const double v = sqrt(b * b - 3.0 * c);
+    const double t1 = (-b - v) / 3.0;
+    double k = ((t1 + b) * t1 + c) * t1 + d;
+    if (k > 0.0) {
+      r0 = t1 - sqrt(-k / (3.0 * t1 + b));
+    } else {
+      const double t2 = (-b + v) / 3.0;
+      k = ((t2 + b) * t2 + c) * t2 + d;
+      r0 = t2 + sqrt(-k / (3.0 * t2 + b));
+    }
+  } else {
+    r0 = -b / 3.0;
+    if (fabs((3.0 * r0 + 2.0 * b) * r0 + c) < 1e-4) r0 += 1.0;
+  }
+  for (int it = 0; it < 50; ++it) {
+    const double fx = ((r0 + b) * r0 + c) * r0 + d;
+    if (it >= 7 && fabs(fx) <= 1e-13) break;
+    const double fpx = (3.0 * r0 + 2.0 * b) * r0 + c;
+    r0 -= fx / fpx;
+  }
+  return r0;
+}
+
+// eigenvector of the symmetric 3x3 A (row-major) for eigenvalue lam: the longest cross product of two rows of A - lam I
+__device__ __forceinline__ void cross_keep(const double *a, const double *b, double &best, double *v) {
+  const double c0 = a[1] * b[2] - a[2] * b[1], c1 = a[2] * b[0] - a[0] * b[2], c2 = a[0] * b[1] - a[1] * b[0];
+  const double n = c0 * c0 + c1 * c1 + c2 * c2;
+  if (n > best) {
+    best = n;
+    v[0] = c0;
+    v[1] = c1;
+    v[2] = c2;
+  }
+}
+__device__ __forceinline__ void eigvec(const double *A, double lam, double *v) {
+  const double r0[3] = {A[0] - lam, A[1], A[2]}, r1[3] = {A[3], A[4] - lam, A[5]}, r2[3] = {A[6], A[7], A[8] - lam};
+  double best = -1.0;
+  cross_keep(r0, r1, best, v);
+  cross_keep(r0, r2, best, v);
+  cross_keep(r1, r2, best, v);
+  const double s = 1.0 / sqrt(best);
+  v[0] *= s;
+  v[1] *= s;
+  v[2] *= s;
+}
+
+// Gauss-Newton on the three distance equations (Lambda Twist's refinement)
+__device__ void refine_lambda(double *L, double a12, double a13, double a23, double b12, double b13, double b23) {
+  for (int it = 0; it < 5; ++it) {
+    const double l1 = L[0], l2 = L[1], l3 = L[2];
+    const double r1 = l1 * l1 + l2 * l2 + b12 * l1 * l2 - a12;
+    const double r2 = l1 * l1 + l3 * l3 + b13 * l1 * l3 - a13;
+    const double r3 = l2 * l2 + l3 * l3 + b23 * l2 * l3 - a23;
+    const double e0 = fabs(r1) + fabs(r2) + fabs(r3);
+    if (e0 < 1e-10) break;
+    const double v0 = 2.0 * l1 + b12 * l2, v1 = 2.0 * l2 + b12 * l1;
+    const double v3 = 2.0 * l1 + b13 * l3, v5 = 2.0 * l3 + b13 * l1;
+    const double v7 = 2.0 * l2 + b23 * l3, v8 = 2.0 * l3 + b23 * l2;
+    const double det = 1.0 / (-v0 * v5 * v7 - v1 * v3 * v8);
+    const double n1 = l1 - det * (-v5 * v7 * r1 - v1 * v8 * r2 + v1 * v5 * r3);
+    const double n2 = l2 - det * (-v3 * v8 * r1 + v0 * v8 * r2 - v0 * v5 * r3);
+    const double n3 = l3 - det * (v3 * v7 * r1 - v0 * v7 * r2 - v1 * v3 * r3);
+    const double s1 = n1 * n1 + n2 * n2 + b12 * n1 * n2 - a12;
+    const double s2 = n1 * n1 + n3 * n3 + b13 * n1 * n3 - a13;
+    const double s3 = n2 * n2 + n3 * n3 + b23 * n2 * n3 - a23;
+    if (fabs(s1) + fabs(s2) + fabs(s3) > e0) break;
+    L[0] = n1;
+    L[1] = n2;
+    L[2] = n3;
+  }
+}
+
+// cofactor matrix of a symmetric 3x3 (row-major; symmetric as well)
+__device__ __forceinline__ void cof3(const double *A, double *C) {
+  C[0] = A[4] * A[8] - A[5] * A[7];
+  C[1] = A[5] * A[6] - A[3] * A[8];
+  C[2] = A[3] * A[7] - A[4] * A[6];
+  C[3] = A[2] * A[7] - A[1] * A[8];
+  C[4] = A[0] * A[8] - A[2] * A[6];
+  C[5] = A[1] * A[6] - A[0] * A[7];
+  C[6] = A[1] * A[5] - A[2] * A[4];
+  C[7] = A[2] * A[3] - A[0] * A[5];
+  C[8] = A[0] * A[4] - A[1] * A[3];
+}
+
+// P3P, Lambda Twist (Persson and Nordberg 2018): bearings y (unit), world points x. Every solution (R, T), y ~ R x + T,
+// is handed to use(R, T) in a fixed order as it is found: +v before -v, the larger-magnitude tau first.
+template <class Use>
+__device__ __forceinline__ void p3p_lambda_twist(const double (*y)[3], const double (*x)[3], Use &&use) {
+  const double b12 = -2.0 * (y[0][0] * y[1][0] + y[0][1] * y[1][1] + y[0][2] * y[1][2]);
+  const double b13 = -2.0 * (y[0][0] * y[2][0] + y[0][1] * y[2][1] + y[0][2] * y[2][2]);
+  const double b23 = -2.0 * (y[1][0] * y[2][0] + y[1][1] * y[2][1] + y[1][2] * y[2][2]);
+  double d12[3], d13[3], d23[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d12[k] = x[0][k] - x[1][k];
+    d13[k] = x[0][k] - x[2][k];
+    d23[k] = x[1][k] - x[2][k];
+  }
+  const double a12 = d12[0] * d12[0] + d12[1] * d12[1] + d12[2] * d12[2];
+  const double a13 = d13[0] * d13[0] + d13[1] * d13[1] + d13[2] * d13[2];
+  const double a23 = d23[0] * d23[0] + d23[1] * d23[1] + d23[2] * d23[2];
+  // D1 = a23 M12 - a12 M23, D2 = a23 M13 - a13 M23; det(D1 - g D2) = c3 g^3 + c2 g^2 + c1 g + c0
+  const double D1[9] = {a23, 0.5 * a23 * b12, 0.0, 0.5 * a23 * b12, a23 - a12, -0.5 * a12 * b23,
+                        0.0, -0.5 * a12 * b23, -a12};
+  const double D2[9] = {a23, 0.0, 0.5 * a23 * b13, 0.0, -a13, -0.5 * a13 * b23,
+                        0.5 * a23 * b13, -0.5 * a13 * b23, a23 - a13};
+  double C1[9], C2[9];
+  cof3(D1, C1);
+  cof3(D2, C2);
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {  // the determinants along the first row
+    c0 += D1[k] * C1[k];
+    c3 += D2[k] * C2[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    c1 += C1[k] * D2[k];
+    c2 += D1[k] * C2[k];
+  }
+  c3 = -c3;
+  c1 = -c1;
+  if (!(fabs(c3) > 0.0) || !isfinite(c3)) return;
+  const double g = cubick(c2 / c3, c1 / c3, c0 / c3);
+  double A[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) A[k] = D1[k] - g * D2[k];
+  // A is of rank 2: its nonzero eigenvalues solve e^2 - tr e + m = 0 (m: sum of the principal 2x2 minors)
+  const double tr = A[0] + A[4] + A[8];
+  const double m = (A[0] * A[4] - A[1] * A[3]) + (A[0] * A[8] - A[2] * A[6]) + (A[4] * A[8] - A[5] * A[7]);
+  double e1, e2;
+  if (!root2real(-tr, m, e1, e2)) return;
+  if (fabs(e1) < fabs(e2)) {
+    const double s = e1;
+    e1 = e2;
+    e2 = s;
+  }
+  if (!(fabs(e1) > 0.0)) return;
+  double V0[3], V1[3];
+  eigvec(A, e1, V0);
+  eigvec(A, e2, V1);
+  const double v = sqrt(fmax(0.0, -e2 / e1));
+  // inv(X), X = [d12 d13 d12 x d13] (columns): cof3 is the plain cofactor matrix, inv(X) = cof^T / det
+  const double xc3[3] = {d12[1] * d13[2] - d12[2] * d13[1], d12[2] * d13[0] - d12[0] * d13[2],
+                         d12[0] * d13[1] - d12[1] * d13[0]};
+  const double X[9] = {d12[0], d13[0], xc3[0], d12[1], d13[1], xc3[1], d12[2], d13[2], xc3[2]};
+  double CX[9];
+  cof3(X, CX);
+  const double detX = X[0] * CX[0] + X[1] * CX[1] + X[2] * CX[2];
+  if (!(fabs(detX) > 0.0)) return;
+  const double idet = 1.0 / detX;
+  double Xi[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Xi[r * 3 + c] = CX[c * 3 + r] * idet;
+#pragma unroll
+  for (int sg = 0; sg < 2; ++sg) {
+    const double s = sg == 0 ? v : -v;
+    const double w2 = 1.0 / (s * V1[0] - V0[0]);
+    const double w0 = (V0[1] - s * V1[1]) * w2;
+    const double w1 = (V0[2] - s * V1[2]) * w2;
+    const double ia = 1.0 / ((a13 - a12) * w1 * w1 - a12 * b13 * w1 - a12);
+    const double qb = (a13 * b12 * w1 - a12 * b13 * w0 - 2.0 * w0 * w1 * (a12 - a13)) * ia;
+    const double qc = ((a13 - a12) * w0 * w0 + a13 * b12 * w0 + a13) * ia;
+    double tau[2];
+    if (!root2real(qb, qc, tau[0], tau[1])) continue;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!(tau[q] > 0.0)) continue;
+      const double d = a23 / (tau[q] * (b23 + tau[q]) + 1.0);
+      if (!(d > 0.0)) continue;
+      double L[3];
+      L[1] = sqrt(d);
+      L[2] = tau[q] * L[1];
+      L[0] = w0 * L[1] + w1 * L[2];
+      if (!(L[0] >= 0.0)) continue;
+      refine_lambda(L, a12, a13, a23, b12, b13, b23);
+      double ry[3][3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ry[i][k] = y[i][k] * L[i];
+      double yd1[3], yd2[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        yd1[k] = ry[0][k] - ry[1][k];
+        yd2[k] = ry[0][k] - ry[2][k];
+      }
+      const double yc[3] = {yd1[1] * yd2[2] - yd1[2] * yd2[1], yd1[2] * yd2[0] - yd1[0] * yd2[2],
+                            yd1[0] * yd2[1] - yd1[1] * yd2[0]};
+      const double Y[9] = {yd1[0], yd2[0], yc[0], yd1[1], yd2[1], yc[1], yd1[2], yd2[2], yc[2]};
+      double R[9], T[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R[r * 3 + c] = Y[r * 3 + 0] * Xi[0 * 3 + c] + Y[r * 3 + 1] * Xi[1 * 3 + c] + Y[r * 3 + 2] * Xi[2 * 3 + c];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        T[r] = ry[0][r] - (R[r * 3 + 0] * x[0][0] + R[r * 3 + 1] * x[0][1] + R[r * 3 + 2] * x[0][2]);
+      use(R, T);
+    }
+  }
+}
+
+// one trial: draws, undistortion, degeneracy, P3P and the choice of root. Returns 1 and fills R, t (camera centre)
+// on success; idx gets the drawn indices either way.
+__device__ int ransac_trial(const RansacArgs &a, long long g, int *idx, double *Rout, double *tout) {
+  int i0 = -1, i1 = -1, i2 = -1, i3 = -1, nd = 0;
+  for (int k = 0; k < kRanMaxDraws && nd < 4; ++k) {
+    const unsigned long long u = ran_mix(a.seedmix ^ (((unsigned long long)g << 32) | (unsigned long long)k));
+    const int id = (int)(((u >> 32) * (unsigned long long)a.n) >> 32);
+    if (id == i0 || id == i1 || id == i2) continue;  // (i3 is set last)
+    if (nd == 0) i0 = id;
+    else if (nd == 1) i1 = id;
+    else if (nd == 2) i2 = id;
+    else i3 = id;
+    ++nd;
+  }
+  idx[0] = i0;
+  idx[1] = i1;
+  idx[2] = i2;
+  idx[3] = i3;
+  if (nd < 4) return 0;
+  const int n = a.n;
+  double P[4][3], x2[4][3];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = idx[q];
+    P[q][0] = a.pts[2 * n + i];
+    P[q][1] = a.pts[3 * n + i];
+    P[q][2] = a.pts[4 * n + i];
+    const double xd = (a.pts[i] - a.cx) / a.fx, yd = (a.pts[n + i] - a.cy) / a.fy;
+    double xn = xd, yn = yd;
+    for (int it = 0; it < 20; ++it) {
+      const double f = 1.0 + a.kc * (xn * xn + yn * yn);
+      xn = xd / f;
+      yn = yd / f;
+    }
+    x2[q][0] = xn * a.fx + a.cx;
+    x2[q][1] = yn * a.fy + a.cy;
+    x2[q][2] = 1.0;
+  }
+  const double eps = 2.220446049250313e-16;  // MATLAB's eps
+  // degenfn_P: every triple of nchoosek(1:4, 3), 3-D points, then the homogeneous undistorted 2-D points
+  if (fabs(triple(P[0], P[1], P[2])) < eps || fabs(triple(P[0], P[1], P[3])) < eps ||
+      fabs(triple(P[0], P[2], P[3])) < eps || fabs(triple(P[1], P[2], P[3])) < eps)
+    return 0;
+  if (fabs(triple(x2[0], x2[1], x2[2])) < eps || fabs(triple(x2[0], x2[1], x2[3])) < eps ||
+      fabs(triple(x2[0], x2[2], x2[3])) < eps || fabs(triple(x2[1], x2[2], x2[3])) < eps)
+    return 0;
+  double yb[3][3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const double bx = (x2[q][0] - a.cx) / a.fx, by = (x2[q][1] - a.cy) / a.fy;
+    const double s = 1.0 / sqrt(bx * bx + by * by + 1.0);
+    yb[q][0] = bx * s;
+    yb[q][1] = by * s;
+    yb[q][2] = s;
+  }
+  double best = INFINITY;
+  int found = 0;
+  p3p_lambda_twist(yb, P, [&](const double *R, const double *T) {
+    double t[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = -(R[0 * 3 + c] * T[0] + R[1 * 3 + c] * T[1] + R[2 * 3 + c] * T[2]);
+    const double dX = P[3][0] - t[0], dY = P[3][1] - t[1], dZ = P[3][2] - t[2];
+    const double xc = R[0] * dX + R[1] * dY + R[2] * dZ;
+    const double yc = R[3] * dX + R[4] * dY + R[5] * dZ;
+    const double zc = R[6] * dX + R[7] * dY + R[8] * dZ;
+    const double iz = 1.0 / zc;
+    const double du = a.fx * (xc * iz) + a.cx - x2[3][0], dv = a.fy * (yc * iz) + a.cy - x2[3][1];
+    const double e = du * du + dv * dv;
+    if (e < best) {  // strict: the first of equal errors stays
+      best = e;
+      found = 1;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Rout[k] = R[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) tout[k] = t[k];
+    }
+  });
+  return found;
+}
+
+__global__ void __launch_bounds__(kRanHypBlock) k_ransac_hyp(RansacArgs a) {
+  const int i = blockIdx.x * kRanHypBlock + threadIdx.x;
+  if (i >= a.k) return;
+  a.cnt[i] = 0u;
+  a.status[i] = 0;
+  if (a.st->done) return;
+  const long long g = a.base + i;
+  if (g >= a.maxtrials) return;
+  int idx[4] = {0, 0, 0, 0};
+  double R[9], t[3];
+  const int ok = ransac_trial(a, g, idx, R, t);
+  for (int q = 0; q < 4; ++q) a.draws[(size_t)i * 4 + q] = idx[q];
+  if (!ok) return;
+  double *h = a.hyp + (size_t)i * 12;
+  for (int k = 0; k < 9; ++k) h[k] = R[k];
+  for (int k = 0; k < 3; ++k) h[9 + k] = t[k];
+  a.status[i] = 1;
+}
+
+template <int TH>
+__global__ void __launch_bounds__(kRanScoreBlock) k_ransac_score(RansacArgs a) {
+  __shared__ double sH[TH][12];
+  __shared__ int sOk[TH];
+  __shared__ unsigned sCnt[TH];
+  if (a.st->done) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h0 = blockIdx.x * TH;
+  if (tid < TH) {
+    sOk[tid] = h0 + tid < a.k ? a.status[h0 + tid] : 0;
+    sCnt[tid] = 0u;
+  }
+  for (int q = tid; q < TH * 12; q += kRanScoreBlock) {
+    const int h = q / 12;
+    sH[h][q - h * 12] = h0 + h < a.k ? a.hyp[(size_t)(h0 + h) * 12 + (q - h * 12)] : 0.0;
+  }
+  __syncthreads();
+  const int j = blockIdx.y * (kRanScoreBlock / 64) + wave;  // the wave's 64-match block
+  if (j < a.nwords) {
+    const int n = a.n, m = j * 64 + lane;
+    const bool in = m < n;
+    const int mm = in ? m : n - 1;
+    const double u = a.pts[mm], v = a.pts[n + mm], X = a.pts[2 * n + mm], Y = a.pts[3 * n + mm],
+                 Z = a.pts[4 * n + mm];
+    const double fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy, kc = a.kc, thr = a.thr;
+    for (int h = 0; h < TH; ++h) {
+      if (!sOk[h]) continue;
+      const double *G = sH[h];
+      const double dX = X - G[9], dY = Y - G[10], dZ = Z - G[11];
+      const double xc = G[0] * dX + G[1] * dY + G[2] * dZ;
+      const double yc = G[3] * dX + G[4] * dY + G[5] * dZ;
+      const double zc = G[6] * dX + G[7] * dY + G[8] * dZ;
+      const double iz = 1.0 / zc;
+      const double xn = xc * iz, yn = yc * iz;
+      const double f = 1.0 + kc * (xn * xn + yn * yn);
+      const double du = fx * (xn * f) + cx - u, dv = fy * (yn * f) + cy - v;
+      const bool inl = in && sqrt(du * du + dv * dv) <= thr;
+      const unsigned long long bits = __ballot(inl);
+      if (lane == 0) {
+        a.words[(size_t)(h0 + h) * a.nwords + j] = bits;
+        atomicAdd(&sCnt[h], (unsigned)__popcll(bits));
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < TH && sOk[tid] && sCnt[tid]) atomicAdd(&a.cnt[h0 + tid], sCnt[tid]);
+}
+
+// exclusive offsets of the waves' ballots (one value per wave in sW) and their total; every thread gets both
+__device__ __forceinline__ void ran_wave_scan(unsigned long long m, unsigned *sW, unsigned *off, unsigned *total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) sW[wave] = (unsigned)__popcll(m);
+  __syncthreads();
+  unsigned o = 0, t = 0;
+  for (int w = 0; w < kRanSelBlock / 64; ++w) {
+    const unsigned c = sW[w];
+    if (w < wave) o += c;
+    t += c;
+  }
+  *off = o + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+  *total = t;
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(kRanSelBlock) k_ransac_select(RansacArgs a) {
+  __shared__ unsigned sW[kRanSelBlock / 64];
+  __shared__ int sLoc[kRanSelBlock];
+  __shared__ int sLast;
+  RansacState &st = *a.st;
+  if (st.done) return;
+  const int tid = threadIdx.x;
+  long long held = st.held;
+  bool done = false;
+  for (int r0 = 0; r0 < a.k && !done; r0 += kRanSelBlock) {
+    const int i = r0 + tid;
+    const long long g = a.base + i;
+    const bool succ = i < a.k && g < a.maxtrials && a.status[i] == 1 && a.cnt[i] >= 4u;
+    unsigned off, total;
+    ran_wave_scan(__ballot(succ), sW, &off, &total);
+    const long long rank = held + off;
+    const bool acc = succ && rank < a.nsamples;
+    if (acc) {
+      const double *h = a.hyp + (size_t)i * 12;
+      a.o_trial[rank] = g;
+      for (int q = 0; q < 4; ++q) a.o_draws[rank * 4 + q] = a.draws[(size_t)i * 4 + q];
+      for (int k = 0; k < 9; ++k) a.o_R[rank * 9 + k] = h[k];
+      for (int k = 0; k < 3; ++k) a.o_t[rank * 3 + k] = h[9 + k];
+      sLoc[off] = i;
+      if (rank == a.nsamples - 1) sLast = i;  // the trial that completes the set
+    }
+    __syncthreads();
+    // the accepted rows' inlier words, copied by the whole workgroup
+    const long long nacc = min((long long)total, a.nsamples - held);
+    for (long long q = 0; q < nacc; ++q) {
+      const unsigned long long *src = a.words + (size_t)sLoc[q] * a.nwords;
+      unsigned long long *dst = a.o_words + (size_t)(held + q) * a.nwords;
+      for (int w = tid; w < a.nwords; w += kRanSelBlock) dst[w] = src[w];
+    }
+    held += nacc;
+    done = held >= a.nsamples;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    st.held = held;
+    const long long end = min(a.base + a.k, a.maxtrials);
+    if (done) {
+      st.trials_used = a.base + sLast + 1;
+      st.done = 1;
+    } else {
+      st.trials_used = end;
+      if (end >= a.maxtrials) st.done = 1;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kRanScoreBlock) k_ransac_colsum(RansacArgs a) {
+  const int lane = threadIdx.x & 63, j = blockIdx.x * (kRanScoreBlock / 64) + (threadIdx.x >> 6);
+  if (j >= a.nwords) return;
+  const int m = j * 64 + lane;
+  const long long S = a.st->held;
+  int c = 0;
+  for (long long s = 0; s < S; ++s) c += (int)((a.o_words[(size_t)s * a.nwords + j] >> lane) & 1ull);
+  if (m < a.n) a.o_cnt[m] = c;
+}
+
+__global__ void __launch_bounds__(kRanSelBlock) k_ransac_finish(RansacArgs a) {
+  __shared__ unsigned sW[kRanSelBlock / 64];
+  RansacState &st = *a.st;
+  const int tid = threadIdx.x;
+  const long long S = st.held;
+  long long kept = 0;
+  for (long long s0 = 0; s0 < S; s0 += kRanSelBlock) {  // R(idxdel) = [] with idxdel = inl_cnt <= 4 (length N)
+    const long long s = s0 + tid;
+    const bool keep = s < S && !(s < a.n && a.o_cnt[s] <= 4);
+    unsigned off, total;
+    ran_wave_scan(__ballot(keep), sW, &off, &total);
+    if (keep) a.o_keep[kept + off] = (int)s;
+    kept += total;
+  }
+  long long nic = 0;
+  for (int m0 = 0; m0 < a.n; m0 += kRanSelBlock) {  // inl_cnt(idxdel) = []
+    const int m = m0 + tid;
+    const int c = m < a.n ? a.o_cnt[m] : 0;
+    const bool keep = m < a.n && c > 4;
+    unsigned off, total;
+    ran_wave_scan(__ballot(keep), sW, &off, &total);
+    if (keep) a.o_cntf[nic + off] = c;
+    nic += total;
+  }
+  if (tid == 0) {
+    st.kept = kept;
+    st.n_ic = nic;
+  }
+}
+
+void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s) {
+  hipLaunchKernelGGL(k_ransac_hyp, dim3((a.k + kRanHypBlock - 1) / kRanHypBlock), dim3(kRanHypBlock), 0, s, a);
+  const int segs = (a.nwords + kRanScoreBlock / 64 - 1) / (kRanScoreBlock / 64);
+  if (tile == 16)
+    hipLaunchKernelGGL(k_ransac_score<16>, dim3((a.k + 15) / 16, segs), dim3(kRanScoreBlock), 0, s, a);
+  else if (tile == 64)
+    hipLaunchKernelGGL(k_ransac_score<64>, dim3((a.k + 63) / 64, segs), dim3(kRanScoreBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_ransac_score<32>, dim3((a.k + 31) / 32, segs), dim3(kRanScoreBlock), 0, s, a);
+  hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(kRanSelBlock), 0, s, a);
+}
+
+void launch_ransac_finish(const RansacArgs &a, hipStream_t s) {
+  const int segs = (a.nwords + kRanScoreBlock / 64 - 1) / (kRanScoreBlock / 64);
+  hipLaunchKernelGGL(k_ransac_colsum, dim3(segs), dim3(kRanScoreBlock), 0, s, a);
+  hipLaunchKernelGGL(k_ransac_finish, dim3(1), dim3(kRanSelBlock), 0, s, a);
+}
+
+}  // namespace ictr
