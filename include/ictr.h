@@ -194,26 +194,36 @@ int ictr_odometer_trace(ictr_odometer *odo, ictr_trace_rec *out, int64_t capacit
 int ictr_odometer_read_buffer(ictr_odometer *odo, int which, float *host_out, int64_t count);
 /* normalisation parameters of the last Set3Dpoints */
 int ictr_odometer_get_norm(const ictr_odometer *odo, double *meanshift3, double *varval);
-/* Kernel-selection bits for A/B measurements and cross-checks (0 = the tuned default; results are the same up to
- * summation order unless noted):
- *   bit 1 (2)      any-size kernels for P = 8 instead of the wave64 = 8x8-patch fast path
- *   bits 4-5       patches per pipeline step of the iteration kernel: 1 -> 1, 2 -> 2, 3 -> 4 with temporal loads
- *   bits 6-7       patches per pipeline step of the setup kernel: 2 -> 1, 3 -> 4 (default 2)
- *   bit 8 (256)    H accumulated by the setup kernel instead of by the level's first iteration launch
- *   bits 9-11      ablation switches of the 8x8 setup kernel (512 no stores; with bit 12 also 1024 one plane's taps for
- *                  all three, 2048 no taps): WRONG RESULTS, timing only
- *   bit 12 (4096)  three separate reference planes instead of the packed {img,dx,dy,0} texels
- *   bit 13 (8192)  per-iteration launches whatever the problem size; bit 14 (16384) the one-launch tracker;
- *   bit 15 (32768) plain launches instead of the hipGraph replay; bit 18 (262144) begin phase as separate operations;
- *   bit 19 (524288) one workgroup per problem in the one-launch tracker (no teams, see ictr_batch_set_team)
- *   bit 21 (2097152) never the resident-iteration form (all iterations of a level in one launch, templates in
- *                  registers: the default for up to 8 dense frame pairs of >= 8193 8x8 patches); bit 23 (8388608) that
- *                  form whatever the batch size; bit 26 (67108864) that form with the level's setup inside the launch
- *                  (A/B: measured slower); bit 25 (33554432) debug: one workgroup of every problem skips its exchange
- *                  store (tests of the time-out path: the tracking FAILS)
- *   bit 27 (134217728) 8x8 setup kernel reads the reference pyramid's gradient planes instead of forming the gradient
- *                  patches on the fly from its image plane (the default for builder-made pyramids, the only way for
- *                  pyramids built with getgrad = 2; bit-identical patches either way) */
+/* Launch-form and kernel-selection bits, for cross-checks, tests and measurements (0 = the default; results are the same
+ * up to summation order unless noted). Any other bit is refused with ICTR_ERR_INVALID.
+ * The default form of a tracking, in this order (see ictr_batch_last_path):
+ *   - 8x8 patches, no robustness option, no patch normalisation, problems of >= 8193 points (or >= 500 points with
+ *     >= 48 000 in the batch, or a peer exchange set): the resident-iteration form (4) -- per level the setup launch and
+ *     ONE launch for all iterations, templates in registers;
+ *   - problems of up to 192 8x8 patches' worth of pixels (384 with >= 16 problems), or 8x8 problems of 129..8192 points
+ *     in the team form (ictr_batch_set_team): the one-launch tracker (1; 3 when it also carries the begin phase) --
+ *     not for sharded batches, with event timing on, or with image-only reference pyramids;
+ *   - up to 65 536 points in the batch: the per-iteration launches replayed as one hipGraph (2);
+ *   - otherwise the per-iteration launches (0). */
+#define ICTR_VARIANT_ANY_SIZE 0x2              /* bit 1: any-size kernels for P = 8 instead of the 8x8 fast path */
+#define ICTR_VARIANT_H_BY_SETUP 0x100          /* bit 8: H reduced by the level's setup tail, not by the first iteration */
+#define ICTR_VARIANT_LAUNCHES 0x2000           /* bit 13: per-iteration launches whatever the problem size */
+#define ICTR_VARIANT_ONE_LAUNCH 0x4000         /* bit 14: the one-launch tracker wherever its point records fit */
+#define ICTR_VARIANT_NO_GRAPH 0x8000           /* bit 15: plain launches instead of the hipGraph replay */
+#define ICTR_VARIANT_SEPARATE_BEGIN 0x40000    /* bit 18: the begin phase as separate operations */
+#define ICTR_VARIANT_NO_TEAMS 0x80000          /* bit 19: one workgroup per problem in the one-launch tracker */
+#define ICTR_VARIANT_NO_RESIDENT 0x200000      /* bit 21: never the resident-iteration form */
+#define ICTR_VARIANT_DEBUG_MUTE 0x2000000      /* bit 25: debug, one workgroup of every problem skips its exchange store
+                                                  (tests of the time-out path: the tracking FAILS) */
+#define ICTR_VARIANT_GRAD_PLANES 0x8000000     /* bit 27: the 8x8 setup kernel reads the gradient planes instead of
+                                                  forming the gradients from the image plane (builder-made pyramids;
+                                                  bit-identical patches either way) */
+#define ICTR_VARIANT_DYNAMIC_LOOP 0x10000000   /* bit 28: the 8x8 setup kernel's dynamic patch loop instead of the
+                                                  static 16-patch groups (bit-identical patches) */
+#define ICTR_VARIANT_ALL                                                                                            \
+  (ICTR_VARIANT_ANY_SIZE | ICTR_VARIANT_H_BY_SETUP | ICTR_VARIANT_LAUNCHES | ICTR_VARIANT_ONE_LAUNCH |              \
+   ICTR_VARIANT_NO_GRAPH | ICTR_VARIANT_SEPARATE_BEGIN | ICTR_VARIANT_NO_TEAMS | ICTR_VARIANT_NO_RESIDENT |         \
+   ICTR_VARIANT_DEBUG_MUTE | ICTR_VARIANT_GRAD_PLANES | ICTR_VARIANT_DYNAMIC_LOOP)
 int ictr_odometer_set_variant(ictr_odometer *odo, int variant);
 /* one-launch tracker, team form (see ictr_batch_set_team) */
 int ictr_odometer_set_team(ictr_odometer *odo, int target_points, int min_points, int max_points);

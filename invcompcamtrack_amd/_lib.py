@@ -28,6 +28,23 @@ class IctrError(RuntimeError):
     pass
 
 
+# launch-form and kernel-selection bits of set_variant (include/ictr.h ICTR_VARIANT_*; any other bit is refused)
+VARIANT_ANY_SIZE = 1 << 1           # any-size kernels for psz 8 instead of the 8x8 fast path
+VARIANT_H_BY_SETUP = 1 << 8         # H reduced by the level's setup tail, not by the first iteration
+VARIANT_LAUNCHES = 1 << 13          # per-iteration launches whatever the problem size
+VARIANT_ONE_LAUNCH = 1 << 14        # the one-launch tracker wherever its point records fit
+VARIANT_NO_GRAPH = 1 << 15          # plain launches instead of the hipGraph replay
+VARIANT_SEPARATE_BEGIN = 1 << 18    # the begin phase as separate operations
+VARIANT_NO_TEAMS = 1 << 19          # one workgroup per problem in the one-launch tracker
+VARIANT_NO_RESIDENT = 1 << 21       # never the resident-iteration form
+VARIANT_DEBUG_MUTE = 1 << 25        # debug: one workgroup of every problem skips its exchange store (the tracking fails)
+VARIANT_GRAD_PLANES = 1 << 27       # the 8x8 setup kernel reads the gradient planes (bit-identical patches)
+VARIANT_DYNAMIC_LOOP = 1 << 28      # the 8x8 setup kernel's dynamic patch loop (bit-identical patches)
+VARIANT_ALL = (VARIANT_ANY_SIZE | VARIANT_H_BY_SETUP | VARIANT_LAUNCHES | VARIANT_ONE_LAUNCH | VARIANT_NO_GRAPH
+               | VARIANT_SEPARATE_BEGIN | VARIANT_NO_TEAMS | VARIANT_NO_RESIDENT | VARIANT_DEBUG_MUTE
+               | VARIANT_GRAD_PLANES | VARIANT_DYNAMIC_LOOP)
+
+
 class OptParam(C.Structure):
     """optparam, utilities.h:46-61 (field order preserved)."""
     _fields_ = [("maxpttrack", C.c_int), ("psz", C.c_int), ("pszd2", C.c_int), ("pszd2m3", C.c_int),

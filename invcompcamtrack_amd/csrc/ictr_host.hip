@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <deque>
 #include <map>
 #include <mutex>
@@ -20,9 +21,6 @@
 #include "ictr_pose_hd.h"
 
 namespace ictr {
-void launch_pyr_copy(const float *, float *, int, int, int, int, hipStream_t);
-void launch_pyr_down(const float *, int, int, int, float *, int, int, int, int, hipStream_t);
-void launch_pyr_finish(float *, float *, float *, int, int, int, int, int, int, hipStream_t);
 void launch_pyr_pack(const float *, const float *, const float *, float *, size_t, hipStream_t);
 void launch_pyr_level(const float *, int, int, int, int, float *, float *, float *, float *, int, int, int, int, int, int,
                       hipStream_t);
@@ -35,7 +33,7 @@ void launch_flow_gather(const void *, const void *, int, int, int, const double 
 void launch_bil_patches(const double *, int, int, int, const double *, int, int, double *, hipStream_t);
 void launch_project_generic(const float *, float *, float *, int, int, const float *, LevelCam, hipStream_t);
 void launch_project_ref(const EngineDev &, const LevelCam *, int, hipStream_t);
-void launch_ref_level(const EngineDev &, const LevelCam &, int, int, int, int, int, hipStream_t);
+void launch_ref_level(const EngineDev &, const LevelCam &, int, int, int, int, int, bool, hipStream_t);
 void launch_level_finish(const EngineDev &, int, hipStream_t);
 void launch_iter(const EngineDev &, const LevelCam &, int, int, int, int, int, int, hipStream_t);
 void launch_iter_main(const EngineDev &, const LevelCam &, int, int, int, int, int, int, hipStream_t, hipEvent_t,
@@ -45,17 +43,18 @@ void launch_iter_finish(const EngineDev &, int, int, int, hipStream_t);
 bool defer_h(const EngineDev &, int);
 hipError_t launch_track1(const EngineDev &, const LevelCam *, int, int, const void *, ProbState *, hipStream_t,
                          const T1Team *, bool project_here = false);
-hipError_t launch_level_resident(const EngineDev &, const LevelCam &, int, int, int, int, int, int, unsigned,
-                                 unsigned long long, unsigned long long *, int *, int, int, const ResXchg *, hipStream_t);
+hipError_t launch_level_resident(const EngineDev &, const LevelCam &, int, int, int, int, int, unsigned, unsigned long long,
+                                 unsigned long long *, int *, int, const ResXchg *, hipStream_t);
 hipError_t launch_debug_transpose_reduce(const float *, float *, int *, int *, int, hipStream_t);
 size_t resident_mail_bytes(int, int);
 int resident_points_per_workgroup(int);
-int resident_blocks_per_cu(int, int);
+int resident_blocks_per_cu(int);
 int track1_team_q(int, int);
 int track1_team_size(int, int);
 size_t track1_team_mail_bytes(int, int);
 size_t track1_blob_bytes(void);
 size_t track1_plan(int, int, int, int, int *);
+int cu_count();
 void launch_seq_select(const SeqArgs &, hipStream_t);
 }  // namespace ictr
 
@@ -343,31 +342,15 @@ static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad
 }
 
 static int pyramid_build(ictr_pyramid *p, const float *img_dev, hipStream_t s) {
-  // one launch per level (k_pyr_level); ICTR_PYR_UNFUSED=1: the four-kernel form it replaced (bit-identical planes,
-  // kept for the A/B and as a cross-check in the tests)
-  static const bool unfused = [] {
-    const char *v = getenv("ICTR_PYR_UNFUSED");
-    return v && atoi(v) != 0;
-  }();
   p->builder_made = 1;
   const int planes = p->getgrad == 1 ? 1 : 0;  // getgrad 2: the image levels only
-  for (int l = 0; l < p->nlev; ++l) {
-    if (!unfused || p->getgrad == 2) {
-      if (l == 0)
-        launch_pyr_level(img_dev, 1, p->w[0], p->h[0], p->w[0], p->img[0], p->dx[0], p->dy[0], p->pack[0], p->w[0],
-                         p->h[0], p->pad, p->sw[0], p->sh[0], planes, s);
-      else
-        launch_pyr_level(p->img[l - 1], 0, p->w[l - 1], p->h[l - 1], p->sw[l - 1], p->img[l], p->dx[l], p->dy[l],
-                         p->pack[l], p->w[l], p->h[l], p->pad, p->sw[l], p->sh[l], planes, s);
-      continue;
-    }
+  for (int l = 0; l < p->nlev; ++l) {  // one launch per level (k_pyr_level)
     if (l == 0)
-      launch_pyr_copy(img_dev, p->img[0], p->w[0], p->h[0], p->pad, p->sw[0], s);
+      launch_pyr_level(img_dev, 1, p->w[0], p->h[0], p->w[0], p->img[0], p->dx[0], p->dy[0], p->pack[0], p->w[0], p->h[0],
+                       p->pad, p->sw[0], p->sh[0], planes, s);
     else
-      launch_pyr_down(p->img[l - 1], p->w[l - 1], p->h[l - 1], p->sw[l - 1], p->img[l], p->w[l], p->h[l], p->pad,
-                      p->sw[l], s);
-    launch_pyr_finish(p->img[l], p->dx[l], p->dy[l], p->w[l], p->h[l], p->pad, p->sw[l], p->sh[l], p->getgrad, s);
-    if (p->getgrad) launch_pyr_pack(p->img[l], p->dx[l], p->dy[l], p->pack[l], (size_t)p->sw[l] * p->sh[l], s);
+      launch_pyr_level(p->img[l - 1], 0, p->w[l - 1], p->h[l - 1], p->sw[l - 1], p->img[l], p->dx[l], p->dy[l], p->pack[l],
+                       p->w[l], p->h[l], p->pad, p->sw[l], p->sh[l], planes, s);
   }
   HIPCHK(hipGetLastError());
   return ICTR_OK;
@@ -691,6 +674,24 @@ extern "C" int ictr_pose_project_pt_save_rotated(const ictr_pose *pose, const fl
 }
 
 // ---------------------------------------------------------------- batched engine
+// How one tracking runs (plan_tracking): the launch form and its geometry, worked out once per tracking from the
+// selection bits, the knobs and the sizes. Plain ints, no padding: the graph key holds its bytes.
+enum TrackForm : int {  // = ictr_batch_last_path
+  kFormLaunches = 0,     // per-iteration launches (ictr_kernels.hip)
+  kFormTrack1 = 1,       // the one-launch tracker k_track1 (ictr_track1.hip), one workgroup or a team per problem
+  kFormGraph = 2,        // the per-iteration launches replayed as one hipGraph
+  kFormTrack1Begin = 3,  // k_track1 that also carries ictr_batch_begin's device part and writes the host mirror
+  kFormResident = 4,     // per level: the setup launch, then ONE resident launch for all iterations (ictr_resident.hip)
+};
+struct TrackPlan {
+  int form;          // TrackForm
+  int variant;       // selection bits as the launchers see them (ICTR_VARIANT_*, ANY_SIZE forced by a robustness option)
+  int team, team_q;  // k_track1: workgroups per problem (1: not the team form), points per workgroup of a team
+  int project_here;  // kFormTrack1 without an explicit begin: the launch projects itself and mirrors the final records
+  int mute;          // ICTR_VARIANT_DEBUG_MUTE: one workgroup of every problem never posts (time-out tests)
+  int parts, slots, np;  // kFormResident: worker workgroups per pair, pairs in flight, patches per wave
+  int setup_cpw[16], setup_gridx8[16];  // kFormResident: points per wave chunk and workgroups of each level's setup
+};
 struct ProbHost {
   int npts = 0;
   double meanshift[3] = {0, 0, 0};
@@ -713,7 +714,6 @@ struct ictr_batch {
   int sharded = 0;
   int gridx = 1;
   int cpw = 64, gridx8 = 1;  // P=8 fast path: points per wave chunk, workgroups per problem
-  bool t1_project_here = false;  // this tracking's one-launch tracker projects itself and mirrors the final records
   bool trace_on = false;
   bool projected = false;
   // device
@@ -740,11 +740,10 @@ struct ictr_batch {
   ResXchg xchg = {};  // sharded resident form (ictr_batch_set_peer_exchange): xchg.world > 1 = the resident launches sum
                      // H and b over the ranks themselves
   unsigned *d_xseq = nullptr;  // [B] exchange counters of that form
-  int packed = 0;    // every reference pyramid of the current tracking has the interleaved planes
-  int otf = 0;       // ... is builder-made (1), and some of them image-only (2): see EngineDev.otf
+  int otf = 0;       // every reference pyramid of the current tracking is builder-made (1), and some of them image-only
+                     // (2): see EngineDev.otf
   int maxpts = 0;    // largest nopoints over the problems of the current tracking (set by ictr_batch_begin)
-  int last_path = 0; // 0: per-iteration launches, 1: one-launch tracker (ictr_track1.hip), 2: launches replayed as a graph,
-                     // 3: one-launch tracker that also carried the begin phase and wrote the host mirror
+  TrackPlan plan = {};  // of the last tracking (plan_tracking)
   // the per-iteration launch sequence of one tracking as an instantiated hipGraph (launch-bound sizes, enqueue_levels)
   hipGraphExec_t gexec = nullptr;
   std::string gkey;               // everything the captured launches depend on; a change rebuilds the graph
@@ -766,7 +765,6 @@ struct ictr_batch {
   unsigned long long *d_res_mail = nullptr;  // per slot: gather box + broadcast box
   size_t res_mail_bytes = 0;
   unsigned res_epoch = 0;
-  int last_team = 1;          // workgroups per problem of the last one-launch tracking
   int team_target = 0;        // points per workgroup aimed at (0: automatic, < 0: no teams); ictr_batch_set_team
   int team_lo = 128, team_hi = 8192;  // problem sizes (points) served by teams: lo < maxpts <= hi
   int *h_team_err = nullptr;  // pinned: an exchange of some launch timed out (sticky)
@@ -805,16 +803,11 @@ static void batch_free(ictr_batch *b) {
 }
 
 // kernel-selection bits as the launchers see them: any robustness option routes P = 8 through the any-size kernels
-static int engine_variant(const ictr_batch *b) {
-  static const int env_or = [] {  // ICTR_VARIANT_OR: OR extra selection bits into every engine (whole-suite A/B runs)
-    const char *v = getenv("ICTR_VARIANT_OR");
-    return v ? atoi(v) : 0;
-  }();
-  return b->variant | env_or | (b->robust ? 2 : 0);
-}
+static int engine_variant(const ictr_batch *b) { return b->variant | (b->robust ? ICTR_VARIANT_ANY_SIZE : 0); }
 
 static EngineDev engine_dev(const ictr_batch *b) {
   EngineDev e;
+  memset(&e, 0, sizeof(e));  // (graph_key compares its bytes)
   e.B = b->B;
   e.M = b->M;
   e.P = b->P;
@@ -826,7 +819,6 @@ static EngineDev engine_dev(const ictr_batch *b) {
   e.ratio = b->op->normdp_ratio;
   e.dopatchnorm = b->op->dopatchnorm ? 1 : 0;
   e.sharded = b->sharded;
-  e.packed = b->packed;
   e.otf = b->otf;
   e.robust = b->robust;
   e.huber_k = b->huber_k;
@@ -979,6 +971,10 @@ extern "C" int ictr_batch_set_peer_exchange(ictr_batch *b, ictr_p2p *p) {
 
 extern "C" int ictr_batch_set_variant(ictr_batch *b, int variant) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
+  if (variant & ~ICTR_VARIANT_ALL)
+    return fail(ICTR_ERR_INVALID, "set_variant: unknown selection bits 0x%x (known: ICTR_VARIANT_ANY_SIZE, H_BY_SETUP, "
+                                  "LAUNCHES, ONE_LAUNCH, NO_GRAPH, SEPARATE_BEGIN, NO_TEAMS, NO_RESIDENT, DEBUG_MUTE, "
+                                  "GRAD_PLANES, DYNAMIC_LOOP = 0x%x)", variant & ~ICTR_VARIANT_ALL, ICTR_VARIANT_ALL);
   b->variant = variant;
   return ICTR_OK;
 }
@@ -1088,7 +1084,12 @@ extern "C" int ictr_batch_setpose_all(ictr_batch *b, const double *p_all, const 
   return ICTR_OK;
 }
 
-static bool use_track1(const ictr_batch *b);
+// ICTR_CPW: points per wave chunk of the 8x8 / 4x4 fast paths, forced (experiments, tests); 0 = the host picks
+static int cpw_forced() {
+  const char *env = getenv("ICTR_CPW");
+  const int v = env ? atoi(env) : 0;
+  return v >= 1 && v <= 64 ? v : 0;
+}
 // ictr_batch_begin, host part: initial states, plane table and launch geometry of the coming tracking
 static int begin_prepare(ictr_batch *b) {
   if (int rc = check_op(b->op, b->cam)) return rc;
@@ -1096,7 +1097,7 @@ static int begin_prepare(ictr_batch *b) {
     return fail(ICTR_ERR_STATE, "optparam maxpttrack/psz/lv_f changed after creation");
   b->done_valid = false;
   b->phase_it = 0;
-  bool all_packed = true, all_builder = true, any_image_only = false;
+  bool all_builder = true, any_image_only = false;
   if (b->timing) std::fill(b->ev_used.begin(), b->ev_used.end(), 0);
   int maxpts = 0;
   for (int i = 0; i < b->B; ++i) {
@@ -1116,12 +1117,12 @@ static int begin_prepare(ictr_batch *b) {
       ps.dy = ph.ref->dy[l];
       ps.cur = ph.cur->img[l];
       ps.pack = ph.ref->pack[l];
-      if (!ps.pack) all_packed = false;
     }
     if (!ph.ref->builder_made) all_builder = false;
     if (ph.ref->getgrad == 2) any_image_only = true;
   }
-  b->packed = all_packed ? 1 : 0;
+  // setpose refuses a reference without gradients (getgrad 0), and every other pyramid that is not image-only carries
+  // the packed planes: they are there exactly when otf != 2
   if (any_image_only && !all_builder)
     return fail(ICTR_ERR_STATE, "a batch cannot mix image-only reference pyramids (getgrad = 2) with pyramids made from "
                                 "caller-supplied planes: the setup kernel reads either the planes or the image, for all "
@@ -1135,19 +1136,16 @@ static int begin_prepare(ictr_batch *b) {
     const int64_t total = (int64_t)std::max(maxpts, 1) * b->B;
     int cpw = 4;
     while (cpw < 64 && total / cpw > 32768) cpw *= 2;
-    if (const char *env = getenv("ICTR_CPW")) {  // experiments only
-      const int v = atoi(env);
-      if (v >= 1 && v <= 64) cpw = v;
-    }
+    if (const int v = cpw_forced()) cpw = v;
     b->cpw = cpw;
     const int64_t chunks = ((int64_t)std::max(maxpts, 1) + cpw - 1) / cpw;
     const int64_t want = (chunks + kWaves - 1) / kWaves;
     const int64_t capx = std::max<int64_t>(1, (int64_t)b->gridx);  // partial buffers are sized for gridx blocks
     b->gridx8 = (int)std::min<int64_t>(std::max<int64_t>(want, 1), capx);
-    if (b->gridx8 >= 64 && !getenv("ICTR_NO_XCD_BANDS"))  // multiple of 8: XCD-aware order (xcd_band_block)
+    if (b->gridx8 >= 64)  // multiple of 8: XCD-aware order (xcd_band_block)
       b->gridx8 = (int)std::min<int64_t>((b->gridx8 + 7) / 8 * 8, capx / 8 * 8);
   }
-  if (b->otf == 2 && (b->P != 8 || b->robust || (engine_variant(b) & 2)))
+  if (b->otf == 2 && (b->P != 8 || b->robust || (engine_variant(b) & ICTR_VARIANT_ANY_SIZE)))
     return fail(ICTR_ERR_STATE, "a reference pyramid without gradient planes (getgrad = 2: gradients formed on the fly) is "
                                 "served by the 8x8 setup kernel k_ref8 only: psz 8, no robustness option, variant bit 1 "
                                 "clear (small problems then run the per-iteration launches instead of the one-launch "
@@ -1207,7 +1205,8 @@ extern "C" int ictr_batch_level_allreduce_needed(ictr_batch *b) {
 extern "C" int ictr_batch_level_accumulate(ictr_batch *b, int level) {
   if (int rc = level_ok(b, level)) return rc;
   b->phase_it = 0;
-  launch_ref_level(engine_dev(b), level_cam(b->cam, level), level, b->gridx, engine_variant(b), b->cpw, b->gridx8, b->stream);
+  launch_ref_level(engine_dev(b), level_cam(b->cam, level), level, b->gridx, engine_variant(b), b->cpw, b->gridx8, true,
+                   b->stream);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
@@ -1241,13 +1240,36 @@ extern "C" int ictr_batch_iter_finish(ictr_batch *b, int level) {
   return ICTR_OK;
 }
 
-// Small problems (the reference's own sizes: 50-1000 points per pair) run the whole coarse-to-fine loop in ONE launch,
-// one workgroup per problem (ictr_track1.hip): below ~1000 points the per-iteration launch pairs are pure
-// dependent-launch latency. Not for sharded batches (they need collectives between phases) and not when per-launch
-// event timing is on. Variant bit 13 forces the per-iteration launches, bit 14 the one-launch tracker.
+// ---------------------------------------------------------------- launch forms of a batch tracking
+// CUs of the calling thread's current device, queried once per device
+namespace ictr {
+int cu_count() {
+  static std::atomic<int> n_cu[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    (void)hipGetLastError();
+    dev = 0;
+  }
+  int v = n_cu[dev].load(std::memory_order_relaxed);
+  if (v == 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
+      (void)hipGetLastError();
+      v = 256;
+    }
+    n_cu[dev].store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+}  // namespace ictr
+
+// Always the same workgroup shape of the one-launch tracker: which wave owns which patch -- and with it the order of every
+// sum -- then depends on the problem's own point count only, so a problem gives the same bits whatever else shares its
+// launch (run_track_nposes: any split of the pose samples over batches or ranks writes the same file).
+constexpr int kTrack1Waves = 8;
+constexpr int kTeamMaxWorkgroups = 4096;  // workgroups of one team launch
+
 // Team form ("Teams", ictr_track1.hip): 8x8 problems above the one-workgroup range are shared by several workgroups
-// that all-gather their partial sums through a device mailbox -- still one launch per tracking. Variant bit 19
-// (524288) switches the form off (A/B).
+// that all-gather their partial sums through a device mailbox -- still one launch per tracking.
 // Points per workgroup aimed at for the current tracking; 0 = no teams. Explicit (ictr_batch_set_team, ICTR_TEAM_TARGET):
 // a function of the problem size alone. Automatic (measured, tools/team_sweep.py, profiles/r02_notes.md): a lone problem
 // is fastest in shares of 40 points (five patches per wave; the all-gather of up to 64 shares is one round trip);
@@ -1258,62 +1280,144 @@ static int team_points(const ictr_batch *b) {
   if (b->team_target != 0) return b->team_target >= 8 ? b->team_target : 0;
   const int n = b->maxpts;
   const int upper = std::min(64, (n + 39) / 40), lower = (n + 159) / 160;
-  static const int n_cu = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  const int fit = std::max(1, n_cu / std::max(1, b->B));
+  const int fit = std::max(1, cu_count() / std::max(1, b->B));
   if (fit < lower && n <= 384) return 0;
   const int team = std::min(upper, std::max(lower, fit));
   return team < 2 ? 0 : (n + team - 1) / team;
 }
-// workgroups per problem of the current tracking, 1 = not the team form
-static int track1_team(const ictr_batch *b) {
-  static const int maxwg = env_int("ICTR_TEAM_MAXWG", 4096);   // workgroups of one launch
-  const int v = engine_variant(b);
-  if ((v & (1 << 19)) || b->P != 8 || b->robust) return 1;
+// workgroups per problem of the team form for the current tracking (1: not the team form); *q: points per workgroup
+static int track1_team(const ictr_batch *b, int *q) {
+  if (b->P != 8 || b->robust) return 1;
   if (b->maxpts <= b->team_lo || b->maxpts > b->team_hi) return 1;
   if ((int64_t)b->nlev * (1 + std::max(0, b->op->maxiter)) >= 4000) return 1;  // exchange number: 12 bits of the tag
   const int target = team_points(b);
   if (target < 1) return 1;
   const int team = track1_team_size(b->maxpts, target);
-  if (team < 2 || (int64_t)team * b->B > maxwg) return 1;
+  if (team < 2 || (int64_t)team * b->B > kTeamMaxWorkgroups) return 1;
+  *q = track1_team_q(b->maxpts, target);
   return team;
 }
-static bool resident_takes(const ictr_batch *b);  // (resident_plan(b).parts > 0, defined with the plan below)
-static bool use_track1(const ictr_batch *b) {
-  const int v = engine_variant(b);
-  if (b->sharded || b->timing || (v & 8192)) return false;
-  if (b->xchg.world > 1) return false;  // sharded resident form: only k_level_resident exchanges with the peer ranks
-  if (b->otf == 2) return false;  // image-only reference pyramids: only k_ref8 forms the gradient patches on the fly
-  if (b->maxpts < 8193 && resident_takes(b)) return false;  // a large batch of mid-size problems: the resident form
-  if (b->maxpts < 1) return false;
-  if (track1_team(b) > 1) return true;
-  if ((size_t)b->maxpts * 64 > 128 * 1024) return false;  // point records must fit in LDS
-  if (v & 16384) return true;
-  // Measured (tools/latency.py, r02): one problem costs 0.17 ms + 1.9 us per 8x8 patch in one launch against a flat
-  // 0.52 ms of dependent launches -> cross-over near 190 points; a batch of independent problems (run_track_nposes:
-  // one workgroup per pose sample, all CUs busy) still wins at 300 points each (64 x 300: 0.87 vs 0.98 ms).
-  static const int forced = [] {
-    const char *s = getenv("ICTR_TRACK1_MAXPTS");
-    return s ? atoi(s) : 0;
-  }();
-  const int limit = forced > 0 ? forced : (b->B >= 16 ? 384 : 192);
-  return (int64_t)b->maxpts * b->n <= (int64_t)limit * 64;
+
+// Resident-iteration form (ictr_resident.hip): problems of thousands of 8x8 patches run all iterations of a level in
+// ONE launch with their templates resident in registers -- `parts` worker workgroups of 128 points + one solver
+// workgroup per frame pair, `slots` pairs in flight -- instead of streaming T/Gx/Gy from HBM in every iteration. Needs
+// every workgroup of the launch resident at once: slots * (parts + 1) <= CUs * occupancy. Taken for problems of at least
+// 8193 points, and for batches of mid-size problems with >= 48 000 points together, which also run faster here than as
+// teams of the one-launch tracker (r03: 64 x 1000 points 0.88 -> 0.76 ms, 16 x 3000 0.91 -> 0.56, 12 x 4000 0.91 ->
+// 0.56, 8 x 6000 0.97 -> 0.58, 128 x 500 0.85 -> 0.75, 256 x 1000 3.39 -> 2.06; below that total the teams win: 8 x 5000
+// 0.49 against 0.53, 16 x 2500 0.49 / 0.54, 32 x 800 0.43 / 0.48; so do problems of 300 points at any batch size).
+// Fills p->parts / slots / np; false: not this form.
+static bool resident_plan(const ictr_batch *b, TrackPlan *p) {
+  if (b->P != 8 || b->robust || b->sharded || b->op->dopatchnorm || b->op->maxiter < 1) return false;
+  const bool xchg = b->xchg.world > 1;  // sharded resident form: any shard size (an empty shard still runs its solvers)
+  const bool big_batch = b->maxpts >= 500 && (int64_t)b->B * b->maxpts >= 48000;
+  if (b->maxpts < 8193 && !xchg && !big_batch) return false;
+  static const int max_slots = env_int("ICTR_RESIDENT_SLOTS", 1 << 20);  // experiments: pairs in flight per launch
+  // sixteen patches per wave (twice the workgroups, half the patch loop) when ALL pairs of the batch are then in flight
+  // at once; thirty-two (the most templates a CU can hold: four 1080p pairs in flight) otherwise
+  for (int np : {16, 32}) {
+    const int bpc = resident_blocks_per_cu(np);
+    if (bpc < 1) continue;
+    const int q = resident_points_per_workgroup(np);
+    const int parts = std::max(1, (b->maxpts + q - 1) / q);
+    const int64_t capacity = (int64_t)bpc * cu_count();
+    const int slots = (int)std::min<int64_t>(std::min<int64_t>(b->B, max_slots), capacity / (parts + 1));
+    if (slots < 1) continue;
+    if (np == 16 && slots < b->B && !xchg) continue;
+    if ((int64_t)((b->B + slots - 1) / slots) * b->op->maxiter >= 4000) return false;  // exchange number: 12 bits
+    p->parts = parts;
+    p->slots = slots;
+    p->np = np;
+    return true;
+  }
+  return false;
 }
-static int track1_waves(const ictr_batch *b) {
-  // Always the same workgroup shape: which wave owns which patch -- and with it the order of every sum -- then depends
-  // on the problem's own point count only, so a problem gives the same bits whatever else shares its launch
-  // (run_track_nposes: any split of the pose samples over batches or ranks writes the same file).
-  static const int forced = [] {
-    const char *s = getenv("ICTR_TRACK1_WAVES");
-    return s ? atoi(s) : 0;
-  }();
-  (void)b;
-  return forced > 0 ? forced : 8;
+// The setup launches of the resident form: their chunk size (the resident launch itself has its own geometry; the
+// batch's chunk size serves the per-iteration kernels). (1) At least 16 points per wave chunk (32 from three problems
+// on): the setup leaves one H partial per workgroup, and the pair's solver workgroup sums them before the first
+// iteration -- 2025 of them with the 4-point chunks a single dense pair gets. One / two / four dense 1080p pairs: 0.42 /
+// 0.52 / 0.73 -> 0.38 / 0.45 / 0.59 ms per tracking. (2) 64 at the coarser levels of batches of eight or more -- frames
+// that fit the caches: 32 pairs x 32 400 points 339-345 / 265-269 / 240-250 us at levels 0 / 1 / 2 with 32, 364-375 /
+// 253-260 / 214-225 with 64 (profiles/r03_notes.md 10, 12). Both as long as the launch keeps about two workgroups per
+// CU (16 x 3000 points: 32 would leave 384). A chunk size forced by ICTR_CPW holds for these launches too.
+static void resident_setup_plan(const ictr_batch *b, bool forced_cpw, TrackPlan *p) {
+  auto blocks_for = [&](int c) {  // workgroups per problem with c points per wave chunk
+    const int64_t want = (((int64_t)std::max(b->maxpts, 1) + c - 1) / c + kWaves - 1) / kWaves;
+    int g = (int)std::min<int64_t>(std::max<int64_t>(want, 1), std::max(b->gridx8, 1));
+    if (g >= 64) g = std::min((g + 7) / 8 * 8, b->gridx8);
+    return g;
+  };
+  const int64_t enough = 2 * (int64_t)cu_count() - 16;
+  for (int sl = b->op->lv_l; sl <= b->op->lv_f; ++sl) {
+    int cpw_l = b->cpw;
+    if (!forced_cpw) {
+      for (int c = b->B <= 2 ? 16 : 32; c > cpw_l; c /= 2)
+        if ((int64_t)b->B * blocks_for(c) >= enough) {
+          cpw_l = c;
+          break;
+        }
+      if (sl > 0 && b->B >= 8 && cpw_l >= 16 && (int64_t)b->B * blocks_for(64) >= enough) cpw_l = 64;
+    }
+    p->setup_cpw[sl] = cpw_l;
+    p->setup_gridx8[sl] = cpw_l != b->cpw ? blocks_for(cpw_l) : b->gridx8;
+  }
+}
+
+// The launch form of the coming tracking, in this order:
+// - the resident-iteration form where resident_plan takes the tracking and the problems have at least 8193 points;
+// - the one-launch tracker k_track1 (ictr_track1.hip): the team form where track1_team gives one, else one workgroup
+//   per problem for problems whose point records fit its LDS and that are small -- measured (tools/latency.py, r02): one
+//   problem costs 0.17 ms + 1.9 us per 8x8 patch in one launch against a flat 0.52 ms of dependent launches ->
+//   cross-over near 190 points; a batch of independent problems (run_track_nposes: one workgroup per pose sample, all
+//   CUs busy) still wins at 300 points each (64 x 300: 0.87 vs 0.98 ms). Without an explicit ictr_batch_begin the launch
+//   also carries the begin phase in its arguments when the records fit them (kFormTrack1Begin), else it projects itself
+//   and mirrors the final records (500 pose samples x 60 points: 0.42 -> 0.39 ms per frame pair). Not for sharded batches,
+//   not with event timing, not for image-only reference pyramids (only k_ref8 forms the gradient patches on the fly);
+//   - the resident-iteration form (batches of mid-size problems);
+// - launch-bound sizes (up to 65 536 points in the batch): the per-iteration launches replayed as one hipGraph;
+// - the per-iteration launches.
+// ICTR_VARIANT_LAUNCHES / ONE_LAUNCH / NO_GRAPH / SEPARATE_BEGIN / NO_TEAMS / NO_RESIDENT move a tracking off its form.
+// begun: ictr_batch_begin has run the begin phase already.
+static TrackPlan plan_tracking(const ictr_batch *b, bool begun) {
+  TrackPlan p;
+  memset(&p, 0, sizeof(p));
+  const int v = engine_variant(b);
+  p.variant = v;
+  p.team = 1;
+  p.mute = (v & ICTR_VARIANT_DEBUG_MUTE) ? 1 : 0;
+  const bool resident = !(v & (ICTR_VARIANT_NO_RESIDENT | ICTR_VARIANT_LAUNCHES | ICTR_VARIANT_ANY_SIZE)) &&
+                        resident_plan(b, &p);
+  bool t1 = !b->sharded && !b->timing && !(v & ICTR_VARIANT_LAUNCHES) && b->xchg.world <= 1 && b->otf != 2 &&
+            !(b->maxpts < 8193 && resident) && b->maxpts >= 1;
+  if (t1) {
+    int q = 0;
+    const int team = (v & ICTR_VARIANT_NO_TEAMS) ? 1 : track1_team(b, &q);
+    if (team > 1) {
+      p.team = team;
+      p.team_q = q;
+    } else if ((size_t)b->maxpts * 64 > 128 * 1024) {  // point records must fit in LDS
+      t1 = false;
+    } else if (!(v & ICTR_VARIANT_ONE_LAUNCH)) {
+      const int limit = b->B >= 16 ? 384 : 192;
+      t1 = (int64_t)b->maxpts * b->n <= (int64_t)limit * 64;
+    }
+  }
+  if (t1) {
+    p.parts = p.slots = p.np = 0;
+    const bool separate = begun || b->trace_on || !b->d_st_mirror || (v & ICTR_VARIANT_SEPARATE_BEGIN);
+    const size_t up = sizeof(ProbState) * b->B + sizeof(PlaneSet) * b->h_planes.size();
+    p.form = (!separate && up <= track1_blob_bytes()) ? kFormTrack1Begin : kFormTrack1;
+    p.project_here = p.form == kFormTrack1 && !separate;
+  } else if (resident) {
+    p.form = kFormResident;
+    resident_setup_plan(b, cpw_forced() != 0, &p);
+  } else if (!b->sharded && !b->timing && !b->graph_broken && !(v & ICTR_VARIANT_NO_GRAPH) &&
+             (int64_t)b->maxpts * b->B <= 65536) {
+    p.form = kFormGraph;
+  } else {
+    p.form = kFormLaunches;
+  }
+  return p;
 }
 
 // Admission of team launches. A team's workgroups wait for each other inside the kernel, so they must all become
@@ -1327,39 +1431,19 @@ struct TeamFlight {
   hipEvent_t ev;
   int weight;  // quarter-CU slots, see team_launch
 };
-struct TeamDevice {  // per device: launches in flight (oldest first), recycled events, CU count
+struct TeamDevice {  // per device: launches in flight (oldest first), recycled events
   std::deque<TeamFlight> flights;
   std::vector<hipEvent_t> events;
-  int n_cu = 0;
 };
 static std::mutex g_team_mu;
 static std::map<int, TeamDevice> g_team_dev;
-static int cu_count_of(int dev) {
-  int v = 0;
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-    (void)hipGetLastError();
-    v = 256;
-  }
-  return v;
-}
-static int team_cu_count() {  // of the calling thread's current device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    dev = 0;
-  }
-  std::lock_guard<std::mutex> lk(g_team_mu);
-  TeamDevice &d = g_team_dev[dev];
-  if (d.n_cu == 0) d.n_cu = cu_count_of(dev);
-  return d.n_cu;
-}
 // Admit + launch + record as ONE critical section (two host threads driving two engines must not both pass the budget
 // test before either launch is visible): make `s` wait until the launch fits beside the launches in flight on this
 // device, run `launch` (which enqueues the kernel on `s`), record an event behind it and enter it in the flight list.
 // weight, in quarter-CU slots (four workgroups of the resident-iteration kernel share a CU): a team launch
 // 4 (team - 1) -- its partly resident dispatch front, a whole CU per workgroup --, a resident-iteration launch one per
-// workgroup x (4 / workgroups per CU): ALL of them must be resident. Budget 4 CUs - 4: sum(team - 1) < CUs as before;
-// a resident launch that fills every slot but four fits alone.
+// workgroup x (4 / workgroups per CU, rounded up): ALL of them must be resident. Budget 4 CUs - 4: sum(team - 1) < CUs
+// as before; a resident launch that fills every slot but four fits alone.
 template <class F>
 static int team_launch(int weight, hipStream_t s, F &&launch) {
   int dev = 0;
@@ -1367,9 +1451,9 @@ static int team_launch(int weight, hipStream_t s, F &&launch) {
     (void)hipGetLastError();
     dev = 0;
   }
+  const int budget = 4 * cu_count() - 4;
   std::lock_guard<std::mutex> lk(g_team_mu);
   TeamDevice &d = g_team_dev[dev];
-  if (d.n_cu == 0) d.n_cu = cu_count_of(dev);
   while (!d.flights.empty() && hipEventQuery(d.flights.front().ev) == hipSuccess) {  // retire finished ones
     d.events.push_back(d.flights.front().ev);
     d.flights.pop_front();
@@ -1377,8 +1461,6 @@ static int team_launch(int weight, hipStream_t s, F &&launch) {
   (void)hipGetLastError();  // hipEventQuery's "not ready" is not an error
   int load = 0;
   for (const TeamFlight &f : d.flights) load += f.weight;
-  static const int off = env_int("ICTR_TEAM_NO_ADMISSION", 0);  // A/B only: shows what the admission is for
-  const int budget = off ? (1 << 30) : 4 * d.n_cu - 4;
   for (size_t i = 0; i < d.flights.size() && load + weight > budget; ++i) {
     HIPCHK(hipStreamWaitEvent(s, d.flights[i].ev, 0));  // this launch starts behind flight i
     load -= d.flights[i].weight;
@@ -1406,15 +1488,22 @@ static double team_timeout_s() {
   const char *s = getenv("ICTR_TEAM_TIMEOUT_S");
   return s ? std::max(0.001, atof(s)) : 5.0;
 }
-// mailbox, tag epoch and error flag of the next team launch (tm->team == 1: not a team launch, nothing allocated)
-static int team_prepare(ictr_batch *b, T1Team *tm) {
-  memset(tm, 0, sizeof(*tm));
-  tm->team = track1_team(b);
-  if (tm->team < 2) {
-    tm->team = 1;
-    return ICTR_OK;
+// the pinned sticky time-out flag of in-launch exchanges (team form, resident form), allocated on first use
+static int team_err_alloc(ictr_batch *b) {
+  if (!b->h_team_err) {
+    HIPCHK(hipHostMalloc((void **)&b->h_team_err, sizeof(int), hipHostMallocDefault));
+    *b->h_team_err = 0;
+    HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err, 0));
   }
-  tm->q = track1_team_q(b->maxpts, team_points(b));
+  return ICTR_OK;
+}
+// mailbox, tag epoch and error flag of the next team launch (p.team == 1: not a team launch, nothing allocated)
+static int team_prepare(ictr_batch *b, const TrackPlan &p, T1Team *tm) {
+  memset(tm, 0, sizeof(*tm));
+  tm->team = 1;
+  if (p.team < 2) return ICTR_OK;
+  tm->team = p.team;
+  tm->q = p.team_q;
   const size_t need = track1_team_mail_bytes(b->B, tm->team);
   if (need > b->team_mail_bytes) {
     if (b->d_team_mail) {
@@ -1434,11 +1523,7 @@ static int team_prepare(ictr_batch *b, T1Team *tm) {
     b->team_mail_bytes = need;
     b->team_epoch = 0;
   }
-  if (!b->h_team_err) {
-    HIPCHK(hipHostMalloc((void **)&b->h_team_err, sizeof(int), hipHostMallocDefault));
-    *b->h_team_err = 0;
-    HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err, 0));
-  }
+  if (int rc = team_err_alloc(b)) return rc;
   b->team_epoch += 1;
   if (b->team_epoch >= (1u << 20)) {  // the epoch field wrapped: forget every old tag
     HIPCHK(hipMemsetAsync(b->d_team_mail, 0, b->team_mail_bytes, b->stream));
@@ -1446,112 +1531,32 @@ static int team_prepare(ictr_batch *b, T1Team *tm) {
   }
   const double limit_s = team_timeout_s();
   tm->tag0 = b->team_epoch << 12;
-  tm->mute = (engine_variant(b) & (1 << 25)) ? 1 : 0;  // debug: part 0 never posts (the time-out path's test)
+  tm->mute = p.mute;  // debug: part 0 never posts (the time-out path's test)
   tm->limit = (unsigned long long)(limit_s * 1e8);
   tm->mail = b->d_team_mail;
   tm->err = b->d_team_err;
   return ICTR_OK;
 }
-
-// Launch-bound sizes (a few hundred to a few thousand points: every kernel of the per-iteration form runs 2-5 us)
-// replay the whole launch sequence of a tracking -- (setup + tail) per level, (accumulate + tail) per iteration, 111
-// kernels for 5 levels x 10 iterations -- as ONE instantiated hipGraph: the host pays one graph launch instead of 111
-// kernel launches and the GPU finds the next packet already queued. The graph is captured once per batch and reused for
-// as long as nothing the launches depend on changes (kernel arguments are passed by value: pointers, sizes, options,
-// camera, grid shapes -- all of it goes into the key). Variant bit 15 (32768) keeps the plain launches (A/B).
-struct ResPlan {  // resident-iteration form (below): worker workgroups per frame pair, pairs in flight; 0 = not this form
-  int parts = 0, slots = 0;
-  int np = 32;    // patches per wave of the kernel instantiation (32: four 1080p pairs in flight; 16: one or two pairs)
-  int fused = 0;  // variant bit 26 (67108864): the level's setup inside the launch (no k_ref8 launch, no template round trip
-                  // through HBM). Measured slower -- 4.39 against 4.04 ms per 32 pairs: the setup is ~3500 instructions per
-                  // wave and runs on ONE wave per SIMD there (80 us per pair and level) instead of on every wave slot of the
-                  // chip in k_ref8 (48 us per pair equivalent) -- so it stays an A/B form (profiles/r03_notes.md)
-};
-static ResPlan resident_plan(const ictr_batch *b);
-static bool use_graph(const ictr_batch *b) {
-  if (b->sharded || b->timing || b->graph_broken || (engine_variant(b) & 32768)) return false;
-  if (resident_plan(b).parts > 0) return false;  // three launches per level, admission events: nothing to replay
-  static const int64_t limit = [] {
-    const char *s = getenv("ICTR_GRAPH_MAXPTS");  // total points of a batch up to which the graph is used; 0 = never
-    return s ? (int64_t)atoll(s) : (int64_t)65536;
-  }();
-  return (int64_t)b->maxpts * b->B <= limit;
-}
-template <class T>
-static void key_put(std::string &k, const T &v) { k.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
-static std::string graph_key(const ictr_batch *b, const EngineDev &e) {
-  std::string k;
-  for (int v : {e.B, e.M, e.P, e.n, e.nlev, e.lv_f, e.lv_l, e.maxiter, e.dopatchnorm, e.sharded, e.packed, e.robust,
-                e.trace.capacity, engine_variant(b), b->cpw, b->gridx, b->gridx8})
-    key_put(k, v);
-  key_put(k, e.ratio);
-  key_put(k, e.huber_k);
-  for (const void *q : {(const void *)e.pt3d, (const void *)e.pt3d_ref, (const void *)e.pt2d, (const void *)e.T,
-                        (const void *)e.Gx, (const void *)e.Gy, (const void *)e.coef, (const void *)e.st,
-                        (const void *)e.planes, (const void *)e.partH, (const void *)e.partb, (const void *)e.red,
-                        (const void *)e.trace.rec, (const void *)e.trace.count})
-    key_put(k, q);
-  for (int l = 0; l < b->nlev; ++l) {
-    const LevelCam lc = level_cam(b->cam, l);
-    for (float v : {lc.fx, lc.fy, lc.cx, lc.cy, lc.swo, lc.sho}) key_put(k, v);
-    key_put(k, lc.sw);
-  }
-  return k;
+// ONE k_track1 launch for every problem of `e` on the batch's stream, through the team admission when the plan has
+// teams. blob: the begin phase in the arguments (kFormTrack1Begin); host_st: the pinned mirror the launch writes the final
+// records to; project_here: the launch projects (step 3) itself
+static int track1_launch(ictr_batch *b, const EngineDev &e, const TrackPlan &p, const void *blob, ProbState *host_st,
+                         bool project_here) {
+  LevelCam cams[16];
+  for (int l = 0; l < b->nlev; ++l) cams[l] = level_cam(b->cam, l);
+  T1Team tm;
+  if (int rc = team_prepare(b, p, &tm)) return rc;
+  auto launch = [&]() -> int {
+    HIPCHK(launch_track1(e, cams, b->maxpts, kTrack1Waves, blob, host_st, b->stream, tm.team > 1 ? &tm : nullptr,
+                         project_here));
+    return ICTR_OK;
+  };
+  if (tm.team > 1) return team_launch(4 * (tm.team - 1), b->stream, launch);
+  return launch();
 }
 
-// Resident-iteration form (ictr_resident.hip): problems of thousands of 8x8 patches run all iterations of a level in
-// ONE launch with their templates resident in registers -- `parts` worker workgroups of 128 points + one solver
-// workgroup per frame pair, `slots` pairs in flight (two workgroups per CU) -- instead of streaming T/Gx/Gy from HBM in
-// every iteration. Needs every workgroup of the launch resident at once: slots * (parts + 1) <= CUs * occupancy.
-// An iteration is then a latency chain of ~10 us per pair with two pairs in flight: the form of choice for ONE or a few
-// dense frame pairs (one 1080p pair: 0.42 against 0.72 ms; 8 pairs 1.66 against 1.82), while a large batch on two
-// streams is served as well by the streaming kernels at the HBM roofline (32 pairs: 6.5 against 6.2-6.4 ms), so the
-// default is this form up to ICTR_RESIDENT_MAXB = 8 pairs per engine. Variant bit 21 (2097152) or ICTR_RESIDENT=0:
-// never; variant bit 23 (8388608): whatever the batch size (A/B).
-static ResPlan resident_plan(const ictr_batch *b) {
-  ResPlan p;
-  static const int on = env_int("ICTR_RESIDENT", 1);
-  static const int min_pts = env_int("ICTR_RESIDENT_MINPTS", 8193);  // below: the one-launch tracker's team form
-  const int v = engine_variant(b);
-  if (!on || (v & ((1 << 21) | 8192 | 4096)) || (v & 2) || b->P != 8 || b->robust || b->sharded || b->op->dopatchnorm || !(b->packed || b->otf == 2))
-    return p;
-  const bool xchg = b->xchg.world > 1;  // sharded resident form: any shard size (an empty shard still runs its solvers)
-  // batches of mid-size problems with >= 48 000 points together also run faster here than as teams of the one-launch
-  // tracker (r03, tools/mid_ab.py: 64 x 1000 points 0.88 -> 0.76 ms, 16 x 3000 0.91 -> 0.56, 12 x 4000 0.91 -> 0.56,
-  // 8 x 6000 0.97 -> 0.58, 128 x 500 0.85 -> 0.75, 256 x 1000 3.39 -> 2.06; below that total the teams win: 8 x 5000
-  // 0.49 against 0.53, 16 x 2500 0.49 / 0.54, 32 x 800 0.43 / 0.48; so do problems of 300 points at any batch size)
-  static const int64_t batch_total = env_int("ICTR_RESIDENT_BATCH_MINTOTAL", 48000);
-  const bool big_batch = batch_total > 0 && b->maxpts >= 500 && (int64_t)b->B * b->maxpts >= batch_total;
-  if ((b->maxpts < min_pts && !xchg && !big_batch) || b->op->maxiter < 1) return p;
-  static const int max_b = env_int("ICTR_RESIDENT_MAXB", 1 << 20);
-  if (b->B > max_b && !(v & (1 << 23))) return p;
-  static const int max_slots = env_int("ICTR_RESIDENT_SLOTS", 1 << 20);  // experiments: pairs in flight per launch
-  static const int force_np = env_int("ICTR_RESIDENT_NP", 0);             // experiments: 16 or 32
-  // sixteen patches per wave (twice the workgroups, half the patch loop) when ALL pairs of the batch are then in flight
-  // at once; thirty-two (the most templates a CU can hold: four 1080p pairs in flight) otherwise
-  // (the fused setup gathers from the three reference planes: not with image-only pyramids, not with a peer exchange)
-  p.fused = ((v & (1 << 26)) && !xchg && b->otf != 2) ? 1 : 0;
-  for (int np : {16, 32}) {
-    if (force_np && np != force_np) continue;
-    const int bpc = resident_blocks_per_cu(np, p.fused);
-    if (bpc < 1) continue;
-    const int q = resident_points_per_workgroup(np);
-    const int parts = std::max(1, (b->maxpts + q - 1) / q);
-    const int64_t capacity = (int64_t)bpc * team_cu_count();
-    const int slots = (int)std::min<int64_t>(std::min<int64_t>(b->B, max_slots), capacity / (parts + 1));
-    if (slots < 1) continue;
-    if (np == 16 && slots < b->B && !force_np && !xchg) continue;
-    if ((int64_t)((b->B + slots - 1) / slots) * b->op->maxiter >= 4000) return p;  // exchange number: 12 bits of the tag
-    p.parts = parts;
-    p.slots = slots;
-    p.np = np;
-    return p;
-  }
-  return p;
-}
-static bool resident_takes(const ictr_batch *b) { return resident_plan(b).parts > 0; }
 // one level's iterations as ONE resident launch (behind the level's setup launches on the same stream)
-static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc, int level, const ResPlan &p, int nblk,
+static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc, int level, const TrackPlan &p, int nblk,
                            hipStream_t s) {
   const size_t need = resident_mail_bytes(p.parts, p.slots);
   if (need > b->res_mail_bytes) {
@@ -1571,11 +1576,7 @@ static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc
     b->res_mail_bytes = need;
     b->res_epoch = 0;
   }
-  if (!b->h_team_err) {
-    HIPCHK(hipHostMalloc((void **)&b->h_team_err, sizeof(int), hipHostMallocDefault));
-    *b->h_team_err = 0;
-    HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err, 0));
-  }
+  if (int rc = team_err_alloc(b)) return rc;
   b->res_epoch += 1;
   if (b->res_epoch >= (1u << 20)) {
     HIPCHK(hipMemsetAsync(b->d_res_mail, 0, b->res_mail_bytes, s));
@@ -1583,78 +1584,41 @@ static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc
   }
   const double limit_s = team_timeout_s();
   // every workgroup of the launch must be resident: it starts when its slots are free of team / resident launches
-  const int bpc = std::max(1, std::min(4, resident_blocks_per_cu(p.np, p.fused)));
-  const int weight = p.slots * (p.parts + 1) * (4 / bpc);
-  const int mute = (engine_variant(b) & (1 << 25)) ? 1 : 0;  // debug: worker 0 never posts its sums (time-out test)
-  static const int prio_mode = env_int("ICTR_RESIDENT_PRIO", 2);  // rotating wave priorities: 4.29 -> 4.03 ms per 32 pairs (r03 notes)
+  const int bpc = std::max(1, std::min(4, resident_blocks_per_cu(p.np)));
+  const int weight = p.slots * (p.parts + 1) * ((4 + bpc - 1) / bpc);
   return team_launch(weight, s, [&]() -> int {
-    HIPCHK(launch_level_resident(e, lc, level, p.np, p.fused, p.parts, p.slots, nblk, b->res_epoch << 12,
-                                 (unsigned long long)(limit_s * 1e8), b->d_res_mail, b->d_team_err, mute, prio_mode,
+    // (mute, debug: worker 0 never posts its sums -- the time-out test)
+    HIPCHK(launch_level_resident(e, lc, level, p.np, p.parts, p.slots, nblk, b->res_epoch << 12,
+                                 (unsigned long long)(limit_s * 1e8), b->d_res_mail, b->d_team_err, p.mute,
                                  b->xchg.world > 1 ? &b->xchg : nullptr, s));
     return ICTR_OK;
   });
 }
 
-// split launchers (ictr_kernels.hip): accumulate kernel and tail kernel separately, so that events can bracket
-// the accumulate kernel alone
-static int enqueue_level_kernels(ictr_batch *b, const EngineDev &e, hipStream_t s, bool events) {
+// the per-level launches of the plan's form (kFormLaunches / kFormGraph: the split launchers of ictr_kernels.hip --
+// accumulate kernel and tail kernel separately, so that events can bracket the accumulate kernel alone; kFormResident:
+// the setup launch, then ONE launch for all iterations of the level)
+static int enqueue_level_kernels(ictr_batch *b, const EngineDev &e, const TrackPlan &p, hipStream_t s, bool events) {
   const int mi = b->op->maxiter;
-  const ResPlan rp = resident_plan(b);
-  if (rp.parts > 0) {  // the setup launches (H included), then ONE launch for all iterations of the level
-    for (int sl = b->op->lv_f; sl >= b->op->lv_l; --sl) {
-      const LevelCam lc = level_cam(b->cam, sl);
-      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 0], s));
-      // The setup launch's chunk size in the resident path (the resident launch itself has its own geometry; the
-      // batch's chunk size serves the per-iteration kernels). (1) At least 16 points per wave chunk (32 from three
-      // problems on): the setup leaves one H partial per workgroup, and the pair's solver workgroup sums them before the
-      // first iteration -- 2025 of them with the 4-point chunks a single dense pair gets. One / two / four dense 1080p
-      // pairs: 0.42 / 0.52 / 0.73 -> 0.38 / 0.45 / 0.59 ms per tracking. (2) 64 at the coarser levels of batches of
-      // eight or more -- frames that fit the caches: 32 pairs x 32 400 points 339-345 / 265-269 / 240-250 us at levels
-      // 0 / 1 / 2 with 32, 364-375 / 253-260 / 214-225 with 64 (profiles/r03_notes.md 10, 12).
-      int cpw_l = b->cpw, g8_l = b->gridx8;
-      static const int split = env_int("ICTR_REF8_CPW_BY_LEVEL", 1);
-      auto blocks_for = [&](int c) {  // workgroups per problem with c points per wave chunk
-        const int64_t want = (((int64_t)std::max(b->maxpts, 1) + c - 1) / c + kWaves - 1) / kWaves;
-        int g = (int)std::min<int64_t>(std::max<int64_t>(want, 1), std::max(b->gridx8, 1));
-        if (g >= 64) g = std::min((g + 7) / 8 * 8, b->gridx8);
-        return g;
-      };
-      if (split && !getenv("ICTR_CPW")) {
-        // ... as long as the launch keeps about two workgroups per CU (16 x 3000 points: 32 would leave 384)
-        const int64_t enough = 2 * (int64_t)team_cu_count() - 16;
-        const int floor_cpw = b->B <= 2 ? 16 : 32;
-        for (int c = floor_cpw; c > cpw_l; c /= 2)
-          if ((int64_t)b->B * blocks_for(c) >= enough) {
-            cpw_l = c;
-            break;
-          }
-        if (sl > 0 && b->B >= 8 && cpw_l >= 16 && (int64_t)b->B * blocks_for(64) >= enough) cpw_l = 64;
-      }
-      if (cpw_l != b->cpw) g8_l = blocks_for(cpw_l);
-      if (!rp.fused) launch_ref_level(e, lc, sl, b->gridx, engine_variant(b) | 256 | (1 << 24), cpw_l, g8_l, s);
-      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
-      if (int rc = launch_resident(b, e, lc, sl, rp, g8_l, s)) return rc;
-      if (events) {
-        HIPCHK(hipEventRecord(b->ev[3 * sl + 2], s));
-        b->ev_used[sl] = 1;
-      }
-    }
-    b->evk_valid = false;  // no per-iteration launches: the kernel-time getters report zeros
-    b->last_path = 4;
-    return ICTR_OK;
-  }
-  const bool tk = events && (int)b->evk.size() >= 2 * b->nlev * mi && mi <= b->evk_iters;
-  b->evk_valid = tk;
+  const bool resident = p.form == kFormResident;
+  const bool tk = !resident && events && (int)b->evk.size() >= 2 * b->nlev * mi && mi <= b->evk_iters;
+  b->evk_valid = tk;  // (resident: no per-iteration launches, the kernel-time getters report zeros)
   for (int sl = b->op->lv_f; sl >= b->op->lv_l; --sl) {
     const LevelCam lc = level_cam(b->cam, sl);
     if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 0], s));
-    launch_ref_level(e, lc, sl, b->gridx, engine_variant(b), b->cpw, b->gridx8, s);
-    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
-    for (int it = 0; it < mi; ++it) {
-      const int ke = 2 * (sl * b->evk_iters + it);
-      launch_iter_main(e, lc, sl, b->gridx, engine_variant(b), b->cpw, b->gridx8, it == 0, s,
-                       tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
-      launch_iter_tail(e, sl, b->gridx, engine_variant(b), b->gridx8, it == 0, s);
+    if (resident) {
+      launch_ref_level(e, lc, sl, b->gridx, p.variant, p.setup_cpw[sl], p.setup_gridx8[sl], false, s);
+      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
+      if (int rc = launch_resident(b, e, lc, sl, p, p.setup_gridx8[sl], s)) return rc;
+    } else {
+      launch_ref_level(e, lc, sl, b->gridx, p.variant, b->cpw, b->gridx8, true, s);
+      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
+      for (int it = 0; it < mi; ++it) {
+        const int ke = 2 * (sl * b->evk_iters + it);
+        launch_iter_main(e, lc, sl, b->gridx, p.variant, b->cpw, b->gridx8, it == 0, s, tk ? b->evk[ke] : nullptr,
+                         tk ? b->evk[ke + 1] : nullptr);
+        launch_iter_tail(e, sl, b->gridx, p.variant, b->gridx8, it == 0, s);
+      }
     }
     if (events) {
       HIPCHK(hipEventRecord(b->ev[3 * sl + 2], s));
@@ -1664,8 +1628,27 @@ static int enqueue_level_kernels(ictr_batch *b, const EngineDev &e, hipStream_t 
   return ICTR_OK;
 }
 
+// Launch-bound sizes (a few hundred to a few thousand points: every kernel of the per-iteration form runs 2-5 us)
+// replay the whole launch sequence of a tracking -- (setup + tail) per level, (accumulate + tail) per iteration, 111
+// kernels for 5 levels x 10 iterations -- as ONE instantiated hipGraph: the host pays one graph launch instead of 111
+// kernel launches and the GPU finds the next packet already queued. The graph is captured once per batch and reused for
+// as long as nothing the launches depend on changes. Kernel arguments are passed by value, so the key is all of them:
+// the engine's device view byte for byte (engine_dev zero-fills it; it has no padding), the plan, the cameras and the
+// grid shapes -- a field added to EngineDev is covered by construction.
+template <class T>
+static void key_put(std::string &k, const T &v) { k.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
+static std::string graph_key(const ictr_batch *b, const EngineDev &e, const TrackPlan &p) {
+  static_assert(sizeof(EngineDev) == 14 * 4 + 14 * 8 + 2 * 4, "EngineDev must have no padding (graph_key)");
+  static_assert(sizeof(TrackPlan) % 4 == 0 && sizeof(LevelCam) == 7 * 4, "plain ints and floats only");
+  std::string k;
+  key_put(k, e);
+  key_put(k, p);
+  for (int l = 0; l < b->nlev; ++l) key_put(k, level_cam(b->cam, l));
+  for (int v : {b->cpw, b->gridx, b->gridx8}) key_put(k, v);
+  return k;
+}
 // (re)build the graph of the current tracking's launches; false: fall back to plain launches for good
-static bool build_graph(ictr_batch *b, const EngineDev &e, const std::string &key) {
+static bool build_graph(ictr_batch *b, const EngineDev &e, const TrackPlan &p, const std::string &key) {
   if (b->gexec) {
     (void)hipGraphExecDestroy(b->gexec);
     b->gexec = nullptr;
@@ -1673,7 +1656,7 @@ static bool build_graph(ictr_batch *b, const EngineDev &e, const std::string &ke
   b->gkey.clear();
   if (!b->cap_stream && hipStreamCreateWithFlags(&b->cap_stream, hipStreamNonBlocking) != hipSuccess) return false;
   if (hipStreamBeginCapture(b->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-  const int rc = enqueue_level_kernels(b, e, b->cap_stream, false);
+  const int rc = enqueue_level_kernels(b, e, p, b->cap_stream, false);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(b->cap_stream, &g);
   bool ok = rc == ICTR_OK && ec == hipSuccess && g != nullptr;
@@ -1688,52 +1671,36 @@ static bool build_graph(ictr_batch *b, const EngineDev &e, const std::string &ke
   return true;
 }
 
+// the launches of b->plan (any form but kFormTrack1Begin)
 static int enqueue_levels(ictr_batch *b) {
   const EngineDev e = engine_dev(b);
-  b->last_path = 0;
-  if (b->xchg.world > 1 && resident_plan(b).parts < 1)
+  TrackPlan &p = b->plan;
+  if (b->xchg.world > 1 && p.form != kFormResident)
     return fail(ICTR_ERR_STATE, "a peer exchange is set (sharded resident form) but this tracking cannot run in the "
                                 "resident-iteration form (8x8 patches, no robustness option, no patch normalisation, builder-"
                                 "made pyramids, at most 4000 pair-rounds x iterations per level)");
-  if (use_track1(b)) {
-    LevelCam cams[16];
-    for (int l = 0; l < b->nlev; ++l) cams[l] = level_cam(b->cam, l);
-    T1Team tm;
-    if (int rc = team_prepare(b, &tm)) return rc;
-    auto launch = [&]() -> int {
-      HIPCHK(launch_track1(e, cams, b->maxpts, track1_waves(b), nullptr, b->t1_project_here ? b->d_st_mirror : nullptr,
-                           b->stream, tm.team > 1 ? &tm : nullptr, b->t1_project_here));
-      return ICTR_OK;
-    };
-    if (tm.team > 1) {
-      if (int rc = team_launch(4 * (tm.team - 1), b->stream, launch)) return rc;
-    } else if (int rc = launch()) {
-      return rc;
-    }
-    b->last_team = tm.team;
-    b->last_path = 1;
-    return ICTR_OK;
-  }
-  if (use_graph(b)) {
-    const std::string key = graph_key(b, e);
-    if ((b->gexec && key == b->gkey) || build_graph(b, e, key)) {
+  if (p.form == kFormTrack1)
+    return track1_launch(b, e, p, nullptr, p.project_here ? b->d_st_mirror : nullptr, p.project_here != 0);
+  if (p.form == kFormGraph) {
+    const std::string key = graph_key(b, e, p);
+    if ((b->gexec && key == b->gkey) || build_graph(b, e, p, key)) {
       HIPCHK(hipGraphLaunch(b->gexec, b->stream));
-      b->last_path = 2;
       return ICTR_OK;
     }
     b->graph_broken = true;
+    p.form = kFormLaunches;
   }
   if (b->timing) std::fill(b->ev_used.begin(), b->ev_used.end(), 0);
-  if (int rc = enqueue_level_kernels(b, e, b->stream, b->timing)) return rc;
+  if (int rc = enqueue_level_kernels(b, e, p, b->stream, b->timing)) return rc;
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 
 // One tracking of every problem, enqueued on the stream up to and including the final states' way into the pinned host
-// mirror and the event that marks them. When SetPose has not been followed by an explicit begin and the one-launch
-// tracker is the form to use, a small batch goes out as ONE launch that also carries ictr_batch_begin's device part in
-// its arguments (T1Args in ictr_track1.hip) and writes the final states to the mirror itself: no upload copies, no fill,
-// no projection launch, no read-back copy. Variant bit 18 (262144) keeps the separate operations (A/B).
+// mirror and the event that marks them. When SetPose has not been followed by an explicit begin and the plan is
+// kFormTrack1Begin, the batch goes out as ONE launch that also carries ictr_batch_begin's device part in its arguments
+// (T1Args in ictr_track1.hip) and writes the final states to the mirror itself: no upload copies, no fill, no projection
+// launch, no read-back copy. With project_here the records are uploaded and the launch projects and mirrors itself.
 static int track_enqueue(ictr_batch *b) {
   if (b->h_team_err && *(volatile int *)b->h_team_err) {
     // the previous tracking of this batch ran into an exchange time-out (reported by its wait): let whatever it left on
@@ -1741,48 +1708,27 @@ static int track_enqueue(ictr_batch *b) {
     HIPCHK(hipStreamSynchronize(b->stream));
     *(volatile int *)b->h_team_err = 0;
   }
-  bool fused = false;
-  if (!b->projected) {
+  const bool begun = b->projected;
+  if (!begun)
     if (int rc = begin_prepare(b)) return rc;
-    const size_t nst = sizeof(ProbState) * b->B, npl = sizeof(PlaneSet) * b->h_planes.size();
-    fused = use_track1(b) && !b->trace_on && b->d_st_mirror && nst + npl <= track1_blob_bytes() &&
-            !(engine_variant(b) & (1 << 18));
-    // the one-launch tracker with a batch too large for the kernel arguments: the records are uploaded, the launch
-    // itself projects (step 3) and writes the final records into the host's pinned mirror -- no k_project_ref launch in
-    // front, no read-back copy behind (500 pose samples x 60 points: 0.42 -> 0.39 ms per frame pair)
-    b->t1_project_here = !fused && use_track1(b) && !b->trace_on && b->d_st_mirror && !(engine_variant(b) & (1 << 18));
-    if (!fused)
-      if (int rc = begin_device(b, !b->t1_project_here)) return rc;
+  b->plan = plan_tracking(b, begun);
+  const TrackPlan &p = b->plan;
+  if (!begun) {
+    if (p.form != kFormTrack1Begin)
+      if (int rc = begin_device(b, !p.project_here)) return rc;
     b->projected = true;
-  } else {
-    b->t1_project_here = false;
   }
   bool mirrored = false;
-  if (fused) {
+  if (p.form == kFormTrack1Begin) {
     const size_t nst = sizeof(ProbState) * b->B, npl = sizeof(PlaneSet) * b->h_planes.size();
     unsigned char blob[4096];
     memcpy(blob, b->h_st.data(), nst);
     memcpy(blob + nst, b->h_planes.data(), npl);
-    LevelCam cams[16];
-    for (int l = 0; l < b->nlev; ++l) cams[l] = level_cam(b->cam, l);
-    T1Team tm;
-    if (int rc = team_prepare(b, &tm)) return rc;
-    auto launch = [&]() -> int {
-      HIPCHK(launch_track1(engine_dev(b), cams, b->maxpts, track1_waves(b), blob, b->d_st_mirror, b->stream,
-                           tm.team > 1 ? &tm : nullptr));
-      return ICTR_OK;
-    };
-    if (tm.team > 1) {
-      if (int rc = team_launch(4 * (tm.team - 1), b->stream, launch)) return rc;
-    } else if (int rc = launch()) {
-      return rc;
-    }
-    b->last_team = tm.team;
-    b->last_path = 3;
+    if (int rc = track1_launch(b, engine_dev(b), p, blob, b->d_st_mirror, false)) return rc;
     mirrored = true;
   } else {
     if (int rc = enqueue_levels(b)) return rc;
-    mirrored = b->t1_project_here && b->last_path == 1;
+    mirrored = p.project_here != 0;
   }
   if (!mirrored)
     HIPCHK(hipMemcpyAsync(b->h_st_pin, b->d_st, sizeof(ProbState) * b->B, hipMemcpyDeviceToHost, b->stream));
@@ -1804,7 +1750,7 @@ static int team_error_check(const ictr_batch *b) {
     return fail(ICTR_ERR_HIP, "%s: a workgroup waited in vain for its peers' partial sums (in-launch exchange timed out "
                               "after %.3f s; are all workgroups of the launch resident?); the results of this tracking "
                               "are invalid",
-                b->last_path == 4 ? "resident-iteration form (k_level_resident)" : "one-launch tracker, team form (k_track1_p8)",
+                b->plan.form == kFormResident ? "resident-iteration form (k_level_resident)" : "one-launch tracker, team form (k_track1_p8)",
                 team_timeout_s());
   return ICTR_OK;
 }
@@ -1912,9 +1858,9 @@ extern "C" int ictr_batch_get_setup_intervals(ictr_batch *b, float *start_ms, fl
   }
   return ICTR_OK;
 }
-extern "C" int ictr_batch_last_path(const ictr_batch *b) { return b ? b->last_path : -1; }
+extern "C" int ictr_batch_last_path(const ictr_batch *b) { return b ? b->plan.form : -1; }
 extern "C" int ictr_batch_last_team(const ictr_batch *b) {
-  return b ? ((b->last_path == 1 || b->last_path == 3) ? b->last_team : 1) : -1;
+  return b ? ((b->plan.form == kFormTrack1 || b->plan.form == kFormTrack1Begin) ? b->plan.team : 1) : -1;
 }
 extern "C" int ictr_batch_set_reduction_buffer(ictr_batch *b, float *dev_ptr) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
@@ -2001,7 +1947,7 @@ extern "C" int ictr_odometer_set_team(ictr_odometer *o, int target_points, int m
 }
 extern "C" int ictr_odometer_set_variant(ictr_odometer *o, int v) {
   if (!o) return fail(ICTR_ERR_INVALID, "odometer is NULL");
-  return ictr_batch_set_variant(o->b, v);
+  return ictr_batch_set_variant(o->b, v);  // (refuses unknown bits)
 }
 extern "C" int ictr_odometer_set3dpoints(ictr_odometer *o, double *pt_in, int64_t nopoints_in) {
   if (!o) return fail(ICTR_ERR_INVALID, "odometer is NULL");
@@ -2202,14 +2148,15 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
 // One engine of one problem (B = 1) tracks frame t -> t+1 from the pose found for frame t, for every t, with the step
 // between two pairs on the device (ictr_sequence.hip): per pair one pyramid build, the selection launches and ONE
 // one-launch tracking, all on one stream; no host synchronisation and no copy until the results come back at the end.
-// The launch form follows the cap (maxpttrack), decided once at creation: the team form where track1_team takes the
-// cap (psz 8), else one workgroup per tracking while the cap's point records fit its LDS; anything else is refused.
+// The launch form follows the cap (maxpttrack), decided once at creation (the batch's plan): the team form where
+// track1_team takes the cap (psz 8), else one workgroup per tracking while the cap's point records fit its LDS; anything
+// else is refused.
 struct ictr_sequence {
   const ictr_cam *cam = nullptr;
   ictr_optparam op;
   ictr_batch *b = nullptr;
   int64_t nw = 0;
-  int stride = 10, nblk = 0, team = 1;
+  int stride = 10, nblk = 0;
   hipStream_t stream = nullptr;
   double *d_world = nullptr;
   unsigned long long *d_mask = nullptr;
@@ -2273,11 +2220,12 @@ extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, co
   // the engine as every pair's tracking sees it: builder-made gradient pyramids (otf = 1, packed planes), the cap as
   // the point capacity of the launch
   b->maxpts = b->M;
-  b->packed = 1;
   b->otf = 1;
-  s->team = track1_team(b);
-  if (s->team < 2) {
-    s->team = 1;
+  memset(&b->plan, 0, sizeof(b->plan));
+  b->plan.form = kFormTrack1;
+  b->plan.project_here = 1;
+  b->plan.team = track1_team(b, &b->plan.team_q);
+  if (b->plan.team < 2) {
     if ((size_t)b->M * 64 > 128 * 1024) {
       const int cap = b->M;
       seq_free(s);
@@ -2320,9 +2268,9 @@ extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, co
     seq_free(s);
     return fail(ICTR_ERR_HIP, "sequence_create: plane table upload failed: %s", hipGetErrorString(e));
   }
-  if (s->team > 1) {  // the mailbox now, not inside the first track_async
+  if (b->plan.team > 1) {  // the mailbox now, not inside the first track_async
     T1Team tm;
-    if (int rc = team_prepare(b, &tm)) {
+    if (int rc = team_prepare(b, b->plan, &tm)) {
       seq_free(s);
       return rc;
     }
@@ -2411,8 +2359,6 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   const int64_t N = s->nframes;
   const int w = s->cam->wh[0], h = s->cam->wh[1], L = b->nlev;
   const size_t plane = (size_t)w * h;
-  LevelCam cams[16];
-  for (int l = 0; l < L; ++l) cams[l] = level_cam(s->cam, l);
   SeqArgs a;
   memset(&a, 0, sizeof(a));
   a.X = s->d_world;
@@ -2453,20 +2399,7 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
     HIPCHK(hipGetLastError());
     EngineDev e = engine_dev(b);
     e.planes = s->d_tab + (t & 1) * L;
-    T1Team tm;
-    if (int rc = team_prepare(b, &tm)) return rc;
-    auto launch = [&]() -> int {
-      HIPCHK(launch_track1(e, cams, b->M, track1_waves(b), nullptr, nullptr, s->stream, tm.team > 1 ? &tm : nullptr,
-                           true));
-      return ICTR_OK;
-    };
-    if (tm.team > 1) {
-      if (int rc = team_launch(4 * (tm.team - 1), s->stream, launch)) return rc;
-    } else if (int rc = launch()) {
-      return rc;
-    }
-    b->last_team = tm.team;
-    b->last_path = 1;
+    if (int rc = track1_launch(b, e, b->plan, nullptr, nullptr, true)) return rc;
   }
   a.t = (int)(N - 1);
   a.tail = 1;
@@ -2501,7 +2434,7 @@ extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *
 }
 
 // workgroups per tracking launch of the last run (before the first run: the form the cap selects)
-extern "C" int ictr_sequence_last_team(const ictr_sequence *s) { return !s ? 0 : s->ran ? s->b->last_team : s->team; }
+extern "C" int ictr_sequence_last_team(const ictr_sequence *s) { return s ? s->b->plan.team : 0; }
 
 // ---------------------------------------------------------------- RANSAC pose sampling (func_ransac_fitcameras_odom.m:17-87)
 // The trials run in chunks of K on one stream (ictr_ransac.hip): hypotheses, scoring, ordered selection per chunk, then

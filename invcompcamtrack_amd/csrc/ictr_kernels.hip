@@ -702,7 +702,6 @@ __device__ __forceinline__ void res_static_for(Fn &&fn) {  // fn(integral_consta
 
 template <int kU>
 struct RefLoads {
-  TapLoads r[kU], x[kU], y[kU];
   TapLoads4 p4[kU];
   TapLoadsOTF o[kU];
   int rec[kU];
@@ -716,6 +715,7 @@ struct RefLoads {
 // instructions per patch instead of the 42 of three wave sums + selects); everything else as in the dynamic form.
 template <bool PN, int kU, bool PK, bool OTF = false, bool ST = false>  // PK: packed {img, dx, dy, 0} planes; OTF: image plane only
 __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int level, int cpw) {
+  static_assert(PK != OTF, "the taps come from either the packed planes or the image plane");
   static_assert(!ST || (OTF && !PN), "the static form exists for on-the-fly gradients without patch normalisation");
   __shared__ __attribute__((aligned(16))) float sRec[kWaves][64 * kRec];
   __shared__ float sW[kWaves][kPartHStride];
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
   float *Gx = e.Gx + (size_t)b * M * 64;
   float *Gy = e.Gy + (size_t)b * M * 64;
   float *coefb = e.coef + (size_t)b * M * kCoefStride;
-  gconst_f32 pref = (gconst_f32)pl.ref, pdx = (gconst_f32)pl.dx, pdy = (gconst_f32)pl.dy;
+  gconst_f32 pref = (gconst_f32)pl.ref;
   gconst_f32x4 ppack = (gconst_f32x4)pl.pack;
   const int sw = lc.sw;
   const int wl = (int)lc.swo, hl = (int)lc.sho, padl = (sw - wl) / 2;  // (OTF) the level's unpadded size, its padding
@@ -826,12 +826,8 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
             L.ty[u] = rlane(ty_v, jj);
             L.inner[u] = (L.tx[u] >= 2 && L.tx[u] + 7 <= wl - 2 && L.ty[u] >= 2 && L.ty[u] + 7 <= hl - 2) ? 1 : 0;
             L.o[u] = taps_issue_otf(pref + base, loff, sw);
-          } else if constexpr (PK) {
-            L.p4[u] = taps_issue4(ppack + base, loff, sw, lane);
           } else {
-            L.r[u] = taps_issue(pref + base, loff, sw, lane);
-            L.x[u] = taps_issue(pdx + base, loff, sw, lane);
-            L.y[u] = taps_issue(pdy + base, loff, sw, lane);
+            L.p4[u] = taps_issue4(ppack + base, loff, sw, lane);
           }
         }
       }
@@ -854,14 +850,10 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
           if constexpr (OTF) {
             taps_blend_otf(L.o[u], w.x, w.y, w.z, w.w, L.inner[u] != 0, L.tx[u] + (lane & 7), L.ty[u] + (lane >> 3), wl, hl,
                            t, gx, gy);
-          } else if constexpr (PK) {
+          } else {
             t = taps_blend4(L.p4[u], 0, w.x, w.y, w.z, w.w, lane);
             gx = taps_blend4(L.p4[u], 1, w.x, w.y, w.z, w.w, lane);
             gy = taps_blend4(L.p4[u], 2, w.x, w.y, w.z, w.w, lane);
-          } else {
-            t = taps_blend(L.r[u], w.x, w.y, w.z, w.w, lane);
-            gx = taps_blend(L.x[u], w.x, w.y, w.z, w.w, lane);
-            gy = taps_blend(L.y[u], w.x, w.y, w.z, w.w, lane);
           }
           if constexpr (PN) t -= wave_sum(t) / 64.0f;  // utilities.cpp:187-188
           const size_t po = (size_t)(i0 + L.rec[u]) * 64;
@@ -1459,39 +1451,6 @@ void launch_bil_patches(const double *img, int H, int W, int C, const double *pt
 }
 
 // ---------------------------------------------------------------- pyramid (utilities.cpp:14-52)
-// level 0: copy the w x h image into the interior of the padded plane
-__global__ __launch_bounds__(kBlock) void k_pyr_copy(const float *__restrict__ src, float *dst, int w, int h, int pad,
-                                                     int sw) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (x < w && y < h) dst[(size_t)(y + pad) * sw + x + pad] = src[(size_t)y * w + x];
-}
-
-// level l from level l-1: cv::resize(.5,.5,INTER_LINEAR) == 2x2 box mean for even sizes; clamped bilinear otherwise
-__global__ __launch_bounds__(kBlock) void k_pyr_down(const float *__restrict__ src, int pw, int ph, int psw,
-                                                     float *dst, int w, int h, int pad, int sw) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (x >= w || y >= h) return;
-  const float *s = src + (size_t)pad * psw + pad;  // interior origin of the previous level
-  float v;
-  if (pw == 2 * w && ph == 2 * h) {
-    const float *r0 = s + (size_t)(2 * y) * psw + 2 * x;
-    const float *r1 = r0 + psw;
-    v = ((r0[0] + r1[0]) + (r0[1] + r1[1])) * 0.25f;
-  } else {
-    int y0 = 2 * y, y1 = y0 + 1, x0 = 2 * x, x1 = x0 + 1;
-    y0 = min(y0, ph - 1);
-    y1 = min(y1, ph - 1);
-    x0 = min(x0, pw - 1);
-    x1 = min(x1, pw - 1);
-    const float top = s[(size_t)y0 * psw + x0] * 0.5f + s[(size_t)y0 * psw + x1] * 0.5f;
-    const float bot = s[(size_t)y1 * psw + x0] * 0.5f + s[(size_t)y1 * psw + x1] * 0.5f;
-    v = top * 0.5f + bot * 0.5f;
-  }
-  dst[(size_t)(y + pad) * sw + x + pad] = v;
-}
-
 __device__ __forceinline__ int reflect101(int i, int n) {
   if (n == 1) return 0;
   if (i < 0) return -i;
@@ -1499,35 +1458,11 @@ __device__ __forceinline__ int reflect101(int i, int n) {
   return i;
 }
 
-// replicate-pad the image in place (border threads read interior, write border) and write both gradient planes:
-// cv::Sobel(ksize=1) = I(x+1)-I(x-1) with reflect-101, then zero padding
-__global__ __launch_bounds__(kBlock) void k_pyr_finish(float *img, float *dx, float *dy, int w, int h, int pad, int sw,
-                                                       int sh, int getgrad) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (x >= sw || y >= sh) return;
-  const int ix = x - pad, iy = y - pad;
-  const bool inside = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h);
-  const float *I = img + (size_t)pad * sw + pad;
-  const size_t o = (size_t)y * sw + x;
-  if (!inside) {
-    const int cxx = min(max(ix, 0), w - 1), cyy = min(max(iy, 0), h - 1);
-    img[o] = I[(size_t)cyy * sw + cxx];
-    if (getgrad) {
-      dx[o] = 0.0f;
-      dy[o] = 0.0f;
-    }
-  } else if (getgrad) {
-    dx[o] = I[(size_t)iy * sw + reflect101(ix + 1, w)] - I[(size_t)iy * sw + reflect101(ix - 1, w)];
-    dy[o] = I[(size_t)reflect101(iy + 1, h) * sw + ix] - I[(size_t)reflect101(iy - 1, h) * sw + ix];
-  }
-}
-
-// One launch per level (the builder's default): every thread owns one pixel of the PADDED level and evaluates the level
-// image where it needs it straight from the level above (level 0: from the input frame) -- its own value (clamped:
-// replicate padding), and for interior pixels the four reflect-101 neighbours of the Sobel pair -- with exactly the
-// arithmetic of k_pyr_copy / k_pyr_down / k_pyr_finish / k_pyr_pack, so the planes are bit-identical to the
-// four-kernel form; the redundant evaluations are cache hits, the level is written once (img, dx, dy, packed texel).
+// One launch per level: every thread owns one pixel of the PADDED level and evaluates the level image where it needs it
+// straight from the level above (level 0: the input frame; level l: cv::resize(.5, .5, INTER_LINEAR) == 2x2 box mean for
+// even sizes, clamped bilinear otherwise) -- its own value (clamped: replicate padding), and for interior pixels the four
+// reflect-101 neighbours of the Sobel pair (cv::Sobel(ksize=1) = I(x+1) - I(x-1), zero padding); the redundant
+// evaluations are cache hits, the level is written once (img, dx, dy, packed texel).
 template <bool FIRST>
 __device__ __forceinline__ float pyr_level_value(const float *__restrict__ src, int pw, int ph, int psw, int pad, int w,
                                                  int h, int x, int y) {
@@ -1577,13 +1512,6 @@ __global__ __launch_bounds__(kBlock) void k_pyr_level(const float *__restrict__ 
 // ---------------------------------------------------------------- host-side launchers
 static inline dim3 grid2d(int w, int h) { return dim3((w + 63) / 64, (h + kWaves - 1) / kWaves); }
 
-void launch_pyr_copy(const float *src, float *dst, int w, int h, int pad, int sw, hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_copy, grid2d(w, h), dim3(kBlock), 0, s, src, dst, w, h, pad, sw);
-}
-void launch_pyr_down(const float *src, int pw, int ph, int psw, float *dst, int w, int h, int pad, int sw,
-                     hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_down, grid2d(w, h), dim3(kBlock), 0, s, src, pw, ph, psw, dst, w, h, pad, sw);
-}
 // plain streaming read (16-byte non-temporal loads, 8 in flight per lane): the practical HBM read ceiling of the
 // box, reported next to the vendor peak (ictr_stream_read_bandwidth)
 __global__ __launch_bounds__(kBlock) void k_stream_read(const f32x4_t *__restrict__ src, size_t nvec, float *sink) {
@@ -1630,10 +1558,6 @@ void launch_pyr_level(const float *src, int first, int pw, int ph, int psw, floa
     hipLaunchKernelGGL(k_pyr_level<false>, grid2d(sw, sh), dim3(kBlock), 0, s, src, pw, ph, psw, img, dx, dy,
                        reinterpret_cast<f32x4_t *>(pack), w, h, pad, sw, sh, getgrad);
 }
-void launch_pyr_finish(float *img, float *dx, float *dy, int w, int h, int pad, int sw, int sh, int getgrad,
-                       hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_finish, grid2d(sw, sh), dim3(kBlock), 0, s, img, dx, dy, w, h, pad, sw, sh, getgrad);
-}
 void launch_getpatch(const float *img, const float *dx, const float *dy, const float *mids, int K, int P, int sw,
                      int dopatchnorm, float *out, float *out_dx, float *out_dy, hipStream_t s) {
   int gx = (K + kWaves - 1) / kWaves;
@@ -1656,43 +1580,42 @@ void launch_project_ref(const EngineDev &e, const LevelCam *cams, int maxpts, hi
 // tail (k_iter_tail / k_iter_finish with first_h), not by k_level_tail -- in sharded mode H then travels in the same
 // 27-float message as the first b and the level phase needs no collective of its own. Where the partials come from:
 // P = 8: the setup kernel k_ref8 (three sums per patch, H = sum J^T S J); P = 4: the first k_iter4<.., WH> launch.
-// Variant bit 8 (256) lets k_level_tail reduce and factor H for P = 8 (cross-check in the tests).
-// wave64 fast paths: 8x8 always, 4x4 when every reference pyramid carries the packed planes
-static bool fast8(const EngineDev &e, int variant) { return e.P == 8 && !(variant & 2); }
-static bool fast4(const EngineDev &e, int variant) { return e.P == 4 && e.packed && !(variant & 2); }
-bool defer_h(const EngineDev &e, int variant) { return (fast8(e, variant) && !(variant & 256)) || fast4(e, variant); }
-// (the host sets variant bit 1 whenever a robustness option is on, see engine_variant in ictr_host.hip)
+// ICTR_VARIANT_H_BY_SETUP lets k_level_tail reduce and factor H for P = 8 (cross-check in the tests).
+// wave64 fast paths: 8x8 always, 4x4 when every reference pyramid carries the packed planes (otf != 2)
+static bool fast8(const EngineDev &e, int variant) { return e.P == 8 && !(variant & ICTR_VARIANT_ANY_SIZE); }
+static bool fast4(const EngineDev &e, int variant) { return e.P == 4 && e.otf != 2 && !(variant & ICTR_VARIANT_ANY_SIZE); }
+bool defer_h(const EngineDev &e, int variant) {
+  return (fast8(e, variant) && !(variant & ICTR_VARIANT_H_BY_SETUP)) || fast4(e, variant);
+}
+// (the host sets ICTR_VARIANT_ANY_SIZE whenever a robustness option is on, see engine_variant in ictr_host.hip)
 
-// steps 4-6 of one level for every problem: accumulate kernel + per-problem tail
+// steps 4-6 of one level for every problem: accumulate kernel + per-problem tail. tail = false (the resident path on the
+// 8x8 fast path): no k_level_tail -- the resident-iteration launch that follows reduces and factors H itself (its solver
+// workgroups are idle while the workers load their templates)
 void launch_ref_level(const EngineDev &e, const LevelCam &lc, int level, int gridx, int variant, int cpw, int gridx8,
-                      hipStream_t s) {
+                      bool tail, hipStream_t s) {
   const dim3 blk(kBlock);
   int nblk = gridx;
   const bool dh = defer_h(e, variant);
   if (fast8(e, variant)) {
     nblk = gridx8;
     const dim3 g8(gridx8, e.B);
-    const bool pk = e.packed && !(variant & 4096);  // variant bit 12: three separate planes (A/B)
     // gradients on the fly from the image plane whenever the reference pyramids are builder-made (r03: 287 -> 242 us per
-    // level-0 launch of 32 pairs; a must for image-only pyramids, e.otf == 2); variant bit 27 (134217728): read the
-    // gradient planes instead (A/B, cross-check)
-    const bool otf = e.otf == 2 || (e.otf == 1 && !(variant & (1 << 27)));
+    // level-0 launch of 32 pairs; a must for image-only pyramids, e.otf == 2); ICTR_VARIANT_GRAD_PLANES: read the
+    // packed planes instead (cross-check). Every pyramid that is not image-only carries the packed planes.
+    const bool otf = e.otf == 2 || (e.otf == 1 && !(variant & ICTR_VARIANT_GRAD_PLANES));
     // patches per pipeline step: two with the packed planes (measured r02: 1 -> 2 saves 50-120 us per level, 4 adds
     // nothing), one otherwise
     if (otf && e.dopatchnorm)
       hipLaunchKernelGGL((k_ref8<true, 1, false, true>), g8, blk, 0, s, e, lc, level, cpw);
-    else if (otf && cpw % 16 == 0 && !(variant & (1 << 28)))  // variant bit 28 (268435456): the dynamic patch loop (A/B)
+    else if (otf && cpw % 16 == 0 && !(variant & ICTR_VARIANT_DYNAMIC_LOOP))  // (the dynamic patch loop: cross-check)
       hipLaunchKernelGGL((k_ref8<false, 2, false, true, true>), g8, blk, 0, s, e, lc, level, cpw);
     else if (otf)
       hipLaunchKernelGGL((k_ref8<false, 2, false, true>), g8, blk, 0, s, e, lc, level, cpw);
-    else if (pk && e.dopatchnorm)
-      hipLaunchKernelGGL((k_ref8<true, 1, true>), g8, blk, 0, s, e, lc, level, cpw);
-    else if (pk)
-      hipLaunchKernelGGL((k_ref8<false, 2, true>), g8, blk, 0, s, e, lc, level, cpw);
     else if (e.dopatchnorm)
-      hipLaunchKernelGGL((k_ref8<true, 1, false>), g8, blk, 0, s, e, lc, level, cpw);
+      hipLaunchKernelGGL((k_ref8<true, 1, true>), g8, blk, 0, s, e, lc, level, cpw);
     else
-      hipLaunchKernelGGL((k_ref8<false, 1, false>), g8, blk, 0, s, e, lc, level, cpw);
+      hipLaunchKernelGGL((k_ref8<false, 2, true>), g8, blk, 0, s, e, lc, level, cpw);
   } else if (fast4(e, variant)) {
     nblk = gridx8;
     if (e.dopatchnorm)
@@ -1703,9 +1626,7 @@ void launch_ref_level(const EngineDev &e, const LevelCam &lc, int level, int gri
     hipLaunchKernelGGL(k_ref_level<4>, dim3(gridx, e.B), blk, 0, s, e, lc, level);
   else
     hipLaunchKernelGGL(k_ref_level<0>, dim3(gridx, e.B), blk, 0, s, e, lc, level);
-  // variant bit 24 (set by the host's resident path only): no tail -- the resident-iteration launch that follows reduces
-  // and factors H itself (its solver workgroups are idle while the workers load their templates)
-  if (!(fast8(e, variant) && (variant & (1 << 24))))
+  if (tail || !fast8(e, variant))
     hipLaunchKernelGGL(k_level_tail, dim3(e.B), blk, 0, s, e, nblk, dh ? 1 : 0);
 }
 void launch_level_finish(const EngineDev &e, int variant, hipStream_t s) {
@@ -1727,11 +1648,9 @@ void launch_iter_main(const EngineDev &e, const LevelCam &lc, int level, int gri
   } while (0)
   if (fast8(e, variant)) {
     const dim3 g8(gridx8, e.B);
-    // patches per pipeline step: 4 measured best (profiles/r01_notes.md); variant bits 4-5 = 2: two (A/B)
+    // patches per pipeline step: 4 measured best (profiles/r01_notes.md)
     if (e.dopatchnorm)
       ICTR_LAUNCH((k_iter8<true, 2>), g8, e, lc, level, cpw);
-    else if (((variant >> 4) & 3) == 2)
-      ICTR_LAUNCH((k_iter8<false, 2>), g8, e, lc, level, cpw);
     else
       ICTR_LAUNCH((k_iter8<false, 4>), g8, e, lc, level, cpw);
   } else if (fast4(e, variant)) {

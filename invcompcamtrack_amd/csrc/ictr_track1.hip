@@ -1013,6 +1013,7 @@ static hipError_t launch_t1(K kernel, size_t *granted, const EngineDev &e, const
 
 // bytes of initial state + plane table a launch can carry in its arguments (fused begin, see T1Args)
 size_t track1_blob_bytes(void) { return sizeof(unsigned) * kT1BlobWords; }
+int cu_count();  // (ictr_host.hip) CUs of the current device
 
 // Points per workgroup of the team form for a problem of `maxpts` points, and with it the team size -- a function of
 // the point count alone, so a problem's sums (and bits) do not depend on what else shares its launch.
@@ -1069,18 +1070,7 @@ hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, i
   static size_t g[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (p8) {
     // more workgroups than CUs, and two of them fit one CU's LDS: the 128-register build (see k_track1_p8)
-    int cus = 256;
-    {
-      static const int n_cu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-          v = 256;
-        return v;
-      }();
-      cus = n_cu;
-    }
-    const bool lean = (long long)e.B * team > cus && lds <= 60 * 1024;
+    const bool lean = (long long)e.B * team > cu_count() && lds <= 60 * 1024;
     if (team > 1) {  // several workgroups per problem ("Teams"); the templates of a share always fit the LDS
       if (!tl) return hipErrorInvalidValue;
       static size_t gt[4] = {0, 0, 0, 0};

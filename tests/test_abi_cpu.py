@@ -35,6 +35,21 @@ def test_library_exports_every_declared_symbol(lib):
     assert sorted(_lib.SIGNATURES) == names  # the ctypes table and the header list the same functions
 
 
+def test_variant_names_match_the_header():
+    """Every ICTR_VARIANT_* define of include/ictr.h has the same value as its Python name, and nothing else is named."""
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import _lib
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr.h")).read(), flags=re.S)
+    defs = dict(re.findall(r"#define\s+ICTR_(VARIANT_[A-Z_]+)\s+(0x[0-9a-fA-F]+)\b", txt))
+    assert len(defs) == 11, defs
+    py = {k: v for k, v in vars(_lib).items() if k.startswith("VARIANT_") and k != "VARIANT_ALL"}
+    assert sorted(py) == sorted(defs)
+    for name, value in defs.items():
+        assert py[name] == int(value, 16), name
+        assert getattr(ic, name) == py[name]
+    assert _lib.VARIANT_ALL == sum(py.values())
+
+
 def test_no_oracle_or_torch_in_the_product_path():
     """The product may not route through the oracle (or any CPU fallback)."""
     pkg = os.path.join(ROOT, "invcompcamtrack_amd")

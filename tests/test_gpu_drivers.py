@@ -229,7 +229,7 @@ def test_ncc_score_on_device_matches_numpy_restatement(oracle, psz):
 def test_verbosity_2_prints_the_reference_iteration_log(oracle, capfd):
     """odometer.cpp:416-417: printf("Sc%02i,It%02i: %g\\n", sl, it, normdp) after every iteration when verbosity == 2."""
     sc = scene(256, 224, 150, seed=12, margin=12.0)
-    for variant in (0, 8192):   # one-launch tracker and per-iteration launches
+    for variant in (0, ic.VARIANT_LAUNCHES):   # one-launch tracker and per-iteration launches
         op = ic.optparam(2, 0, 8, 4, 0.0, 0, 0, 150, 2)
         cam = ic.CamClass(3, sc["fc"], sc["cc"], sc["wh"], 8)
         pose = ic.PoseClass(cam, op)

@@ -36,6 +36,12 @@ def test_call_order_and_mismatches():
         odo.SetPose(sc["p_a"], ic.Pyramid(np.zeros((64, 96), np.float32), 2, 8), good)   # other frame size
     with pytest.raises(TypeError):
         odo.Set3Dpoints(sc["pts3d"].astype(np.float32))           # the reference takes double* and so do we
+    with pytest.raises(ic.IctrError, match="unknown selection bits"):
+        odo.set_variant(1 << 12)                                   # not an ICTR_VARIANT_* bit
+    with pytest.raises(ic.IctrError, match="unknown selection bits"):
+        odo.set_variant(ic.VARIANT_NO_GRAPH | (1 << 23))
+    odo.set_variant(ic.VARIANT_ALL & ~ic.VARIANT_DEBUG_MUTE)       # every named bit is accepted ...
+    odo.set_variant(0)                                             # ... and the default is back
     odo.SetPose(sc["p_a"], good, ic.Pyramid(sc["img_b"], 2, 8))
     p = odo.TrackPose()
     assert np.all(np.isfinite(p))
@@ -95,7 +101,7 @@ def test_in_launch_exchange_timeout_is_reported_and_the_engine_recovers(form, mo
         assert e.last_team() > 1
 
     monkeypatch.setenv("ICTR_TEAM_TIMEOUT_S", "0.05")
-    e.set_variant(1 << 25)
+    e.set_variant(ic.VARIANT_DEBUG_MUTE)
     e.SetPoseAll(P, pa, pb)
     t0 = time.perf_counter()
     e.track_async()

@@ -41,13 +41,12 @@ POSE_TOL = 1e-4
 SUM_TOL = 2e-6
 DP_TOL = 2e-3
 
-LAUNCHES = 8192   # variant bit 13: per-iteration launch pairs (k_ref* / k_iter* + tails) whatever the problem size
-ONE_LAUNCH = 16384  # variant bit 14: the one-launch tracker k_track1 (default choice for small problems)
-SEPARATE_BEGIN = 1 << 18  # variant bit 18: uploads, projection launch and read-back copy as separate operations
-NO_GRAPH = 32768  # variant bit 15: the per-iteration launches as plain launches (default below 65 536 points: one hipGraph)
-NO_TEAMS = 1 << 19  # variant bit 19: the one-launch tracker with ONE workgroup per problem whatever its size
-NO_RESIDENT = 1 << 21  # variant bit 21: never the resident-iteration form (k_level_resident)
-RESIDENT = 1 << 23  # variant bit 23: the resident-iteration form whatever the batch size (default: up to 8 pairs)
+LAUNCHES = ic.VARIANT_LAUNCHES  # per-iteration launch pairs (k_ref* / k_iter* + tails) whatever the problem size
+ONE_LAUNCH = ic.VARIANT_ONE_LAUNCH  # the one-launch tracker k_track1 (default choice for small problems)
+SEPARATE_BEGIN = ic.VARIANT_SEPARATE_BEGIN  # uploads, projection launch and read-back copy as separate operations
+NO_GRAPH = ic.VARIANT_NO_GRAPH  # the per-iteration launches as plain launches (default below 65 536 points: one hipGraph)
+NO_TEAMS = ic.VARIANT_NO_TEAMS  # the one-launch tracker with ONE workgroup per problem whatever its size
+NO_RESIDENT = ic.VARIANT_NO_RESIDENT  # never the resident-iteration form (k_level_resident)
 
 
 @pytest.fixture(params=["one_launch", "teams", "launches"])
@@ -404,7 +403,7 @@ def test_resident_iterations_equal_per_iteration_launches(oracle, B, ratio, maxi
     counts = [9000 - 173 * k for k in range(B)]
     poses0 = sc["p_a"][None, :] + np.random.default_rng(9).normal(0, 1e-3, (B, 6))
     out = {}
-    for name, variant in (("resident", RESIDENT), ("launches", NO_RESIDENT)):
+    for name, variant in (("resident", 0), ("launches", NO_RESIDENT)):
         e = ic.TrackBatch(cam, op, B)
         e.set_variant(variant)
         for k in range(B):
@@ -718,6 +717,39 @@ def test_one_launch_tracker_is_the_default_for_small_batches(oracle):
         bb.track_async()
         bb.poses()
         assert want in bb.path_name() and bb.last_team() == team, (npts, bb.path_name())
+
+
+def test_graph_replay_follows_the_reference_pyramids_origin():
+    """The hipGraph of a batch is replayed only while every kernel argument is the same. A batch on the graph path
+    tracks first with a builder-made reference pyramid (the 8x8 setup kernel forms the gradients from the image
+    plane), then with one made from caller planes whose dx / dy are NOT the central differences of its image (the
+    kernel must read them): each tracking equals that of a fresh batch, and the two differ."""
+    sc = scene(640, 368, 1000, seed=31)
+    op = ic.optparam(2, 0, 8, 4, 0.0, 0, 0, 1000)
+    cam = ic.CamClass(3, sc["fc"], sc["cc"], sc["wh"], 8)
+    pa, pb = ic.Pyramid(sc["img_a"], 2, 8), ic.Pyramid(sc["img_b"], 2, 8)
+    planes = ([pa.download(l, 0) for l in range(3)], [1.5 * pa.download(l, 1) for l in range(3)],
+              [0.5 * pa.download(l, 2) for l in range(3)])
+    ph = ic.Pyramid(lv_f=2, imgpadding=8, host_planes=planes, wh=(pa.w, pa.h))
+
+    def engine():
+        e = ic.TrackBatch(cam, op, 1)
+        e.set_variant(NO_TEAMS)   # 1000 points: past the one-workgroup tracker, below the graph's limit
+        e.Set3Dpoints(0, sc["pts3d"].copy())
+        return e
+
+    def track(e, ref):
+        e.SetPose(0, sc["p_a"], ref, pb)
+        e.track_async()
+        return e.poses().copy(), e.iterations().copy(), e.path_name()
+
+    e = engine()
+    got = [track(e, pa), track(e, ph)]
+    want = [track(engine(), pa), track(engine(), ph)]
+    for g, w in zip(got, want):
+        assert "hipGraph" in g[2] and "hipGraph" in w[2], (g[2], w[2])
+        assert np.array_equal(g[0], w[0]) and np.array_equal(g[1], w[1]), np.abs(g[0] - w[0]).max()
+    assert not np.array_equal(want[0][0], want[1][0])
 
 
 def test_points_out_of_view_and_stale_state_across_frames(oracle, launch_form):

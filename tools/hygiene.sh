@@ -7,9 +7,5 @@ run() {
   rc=${PIPESTATUS[0]}
   if [ "$rc" = 124 ] || [ "$rc" = 137 ]; then echo "killed by timeout: stopping"; exit 1; fi
 }
-run ICTR_REF8_CPW_BY_LEVEL=0
 run ICTR_RESIDENT_SLOTS=2
-run ICTR_RESIDENT_NP=32
-run ICTR_RESIDENT_NP=16
 run ICTR_CPW=64
-run ICTR_RESIDENT_PRIO=0

@@ -21,8 +21,8 @@ def one(w, h, n, psz, lv_f, maxiter, B=1, reps=40, cpu=True):
     pa, pb = ic.Pyramid(sc["img_a"], lv_f, psz), ic.Pyramid(sc["img_b"], lv_f, psz)
     out = dict(frame=f"{w}x{h}", points=n, problems=B, psz=psz, levels=lv_f + 1, maxiter=maxiter)
     poses = {}
-    forms = (("default", 0), ("one_workgroup", 16384 | (1 << 19)), ("graph", 8192),
-             ("per_iteration_launches", 8192 | 32768))
+    forms = (("default", 0), ("one_workgroup", ic.VARIANT_ONE_LAUNCH | ic.VARIANT_NO_TEAMS),
+             ("graph", ic.VARIANT_LAUNCHES), ("per_iteration_launches", ic.VARIANT_LAUNCHES | ic.VARIANT_NO_GRAPH))
     for name, variant in forms:
         if name == "one_workgroup" and n * psz * psz > 2048 * 64:
             continue

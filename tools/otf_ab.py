@@ -1,6 +1,6 @@
 """A/B of the gradients-on-the-fly path: (1) pyramid refill of a 1080p frame with gradient planes
 (getgrad 1) against image levels only (getgrad 2); (2) the headline step with the 8x8 setup kernel reading the packed
-planes (variant bit 27) against forming the gradients from the image plane (the default), resident and streaming form.
+planes (ICTR_VARIANT_GRAD_PLANES) against forming the gradients from the image plane (the default), resident and streaming form.
     python tools/otf_ab.py"""
 import json
 import sys
@@ -34,9 +34,10 @@ cam = ic.CamClass(3, sc["fc"], sc["cc"], sc["wh"], 8)
 op = ic.optparam(2, 0, 8, 10, 0.0, 0, 0, 32400)
 pb = ic.Pyramid(sc["img_b"], 2, 8, getgrad=0)
 B = 32
-for name, variant, gg in (("resident, packed planes (bit 27)", 1 << 27, 1), ("resident, on the fly", 0, 1),
-                          ("resident, image-only pyramid", 0, 2), ("streaming, packed planes", (1 << 21) | (1 << 27), 1),
-                          ("streaming, on the fly", 1 << 21, 1)):
+for name, variant, gg in (("resident, packed planes", ic.VARIANT_GRAD_PLANES, 1), ("resident, on the fly", 0, 1),
+                          ("resident, image-only pyramid", 0, 2),
+                          ("streaming, packed planes", ic.VARIANT_NO_RESIDENT | ic.VARIANT_GRAD_PLANES, 1),
+                          ("streaming, on the fly", ic.VARIANT_NO_RESIDENT, 1)):
     pa = ic.Pyramid(sc["img_a"], 2, 8, getgrad=gg)
     e = ic.TrackBatch(cam, op, B)
     e.set_variant(variant)

@@ -7,7 +7,7 @@ import invcompcamtrack_amd as ic
 from invcompcamtrack_amd import synth
 sc = synth.make_scene(256, 224, n_points=300, seed=9, margin=12.0)
 res = []
-for variant in (8192, 8192 | 2):
+for variant in (ic.VARIANT_LAUNCHES, ic.VARIANT_LAUNCHES | ic.VARIANT_ANY_SIZE):
     op = ic.optparam(2, 0, 4, 6, 0.0, 0, 0, 300)
     cam = ic.CamClass(3, sc["fc"], sc["cc"], sc["wh"], 4)
     odo = ic.OdometerClass(ic.PoseClass(cam, op), op)

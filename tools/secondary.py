@@ -235,7 +235,7 @@ def rec_dense(seconds, cpu_track=None):
     poses_1 = {}
     for B in (1, 4):
         row = {"pairs": B, "points_per_pair": n}
-        for name, variant in (("default", 0), ("streaming", 1 << 21)):
+        for name, variant in (("default", 0), ("streaming", ic.VARIANT_NO_RESIDENT)):
             eng = ic.TrackBatch(cam, op, B)
             eng.set_variant(variant)
             for k in range(B):

@@ -41,9 +41,10 @@ def main():
         pa, pb = ic.Pyramid(sc["img_a"], 4, 8), ic.Pyramid(sc["img_b"], 4, 8)
         reps = 20 if B * n < 20000 else 8
         out = dict(problems=B, points=n)
-        out["launches_ms"], _, pref = run(sc, cam, op, pa, pb, B, 8192, None, reps)
+        out["launches_ms"], _, pref = run(sc, cam, op, pa, pb, B, ic.VARIANT_LAUNCHES, None, reps)
         if n <= 1000:
-            out["one_workgroup_ms"], _, _ = run(sc, cam, op, pa, pb, B, 16384 | (1 << 19), None, reps)
+            out["one_workgroup_ms"], _, _ = run(sc, cam, op, pa, pb, B, ic.VARIANT_ONE_LAUNCH | ic.VARIANT_NO_TEAMS, None,
+                                                 reps)
         for t in targets:
             if (n + t - 1) // t < 2 or B * ((n + t - 1) // t) > 2048:
                 continue
