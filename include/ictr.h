@@ -74,6 +74,16 @@ int ictr_stream_read_bandwidth(size_t bytes, int reps, double *gbps_out);
  * 2 * patch_of_lane[lane] + kind_of_lane[lane] (all host arrays; 64 entries each) */
 int ictr_debug_transpose_reduce(const float *vals, float *out, int *patch_of_lane, int *kind_of_lane,
                                 int patches_per_wave /* 16 or 32: the kernel's two instantiations; 16 uses values 0..31 */);
+/* inspection: the solver turn's 6x6 full-pivot LU on the device (one wave per system, n systems, all host arrays):
+ * H36[n][36] symmetric (the kernel reads the upper triangle), b6[n][6] -> x6[n][6], rank[n], nonzero[n] (non-zero
+ * pivots), the composed permutations rowmap6 / colmap6 [n][6] (c[i] = b[rowmap[i]], x[i] = c[colmap[i]]) and the
+ * factors lu36[n][36]. through_state = 0: factor and substitute in registers; 1: the factors are stored to a
+ * device problem record and a second launch reloads them and substitutes (the per-iteration launch forms). */
+int ictr_debug_wave_solve(const float *H36, const float *b6, int64_t n, int through_state, float *x6, int *rank,
+                          int *nonzero, int *rowmap6, int *colmap6, float *lu36);
+/* inspection: the device builds of the f32 exponential / logarithm, one thread per input.
+ * log_not_exp = 0: in p[n][6] -> out G[n][12]; 1: in G[n][12] -> out p[n][6] */
+int ictr_debug_se3(const float *in, int64_t n, int log_not_exp, float *out);
 
 /* ------------------------------------------------------------------ CamClass (camera.h:19-31, camera.cpp:14-45) */
 typedef struct ictr_cam ictr_cam;

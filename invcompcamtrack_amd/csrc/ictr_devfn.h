@@ -136,7 +136,8 @@ __device__ __forceinline__ float taps_blend(const TapLoads &t, float w0, float w
 //   * substitution: lane i owns c[i]; c[i] is broadcast with v_readlane as soon as it is final;
 //   * the arithmetic per matrix / vector entry is EXACTLY that of lu_factor_ws / lu_apply_ws (same operations in the
 //     same order on the same operands; Eigen FullPivLU's pivot order, rank threshold and zero-filled free variables),
-//     so the results are bit-identical to the serial code (tests/test_gpu_parity.py compares the two).
+//     so the results are bit-identical to the serial code (tests/test_gpu_solver.py puts a corpus of systems through
+//     both via ictr_debug_wave_solve, and checks every launch form's trace against the serial solve of its own H, b).
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
@@ -324,9 +325,16 @@ __device__ __forceinline__ void ws_factor(WaveSolver &s, float a, int lane) {
   for (int k = 0; k < 6; ++k) {
     if (nonzero == 6) {  // wave-uniform
       const float v = (in && r >= k && c >= k) ? fabsf(a) : -1.0f;
-      const float m = wave_max_dpp(v);
+      float m = wave_max_dpp(v);
       int sidx = wave_min_dpp((v == m) ? c * 6 + r : (1 << 20));  // first maximum of the column-major scan
       if (sidx >= 36 || !(m >= 0.0f)) sidx = k * 6 + k;            // NaN candidates: the serial code keeps (k,k)
+      // The serial scan starts from |A[k][k]| and only a strictly larger value replaces it: a NaN there stays the
+      // pivot whatever the other candidates are (fmaxf above drops it while one of them is finite).
+      const float vkk = rlane(v, k * 7);
+      if (vkk != vkk) {
+        sidx = k * 7;
+        m = vkk;
+      }
       const int bc = sidx / 6, br = sidx - 6 * bc;
       if (m == 0.0f) {
         nonzero = k;

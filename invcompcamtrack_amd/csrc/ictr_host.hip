@@ -46,6 +46,9 @@ hipError_t launch_track1(const EngineDev &, const LevelCam *, int, int, const vo
 hipError_t launch_level_resident(const EngineDev &, const LevelCam &, int, int, int, int, int, unsigned, unsigned long long,
                                  unsigned long long *, int *, int, const ResXchg *, hipStream_t);
 hipError_t launch_debug_transpose_reduce(const float *, float *, int *, int *, int, hipStream_t);
+hipError_t launch_debug_wave_solve(const float *, const float *, int, ProbState *, int, float *, int *, int *, int *, int *,
+                                   float *, hipStream_t);
+hipError_t launch_debug_se3(const float *, float *, long long, int, hipStream_t);
 size_t resident_mail_bytes(int, int);
 int resident_points_per_workgroup(int);
 int resident_blocks_per_cu(int);
@@ -151,6 +154,54 @@ extern "C" int ictr_debug_transpose_reduce(const float *vals, float *out, int *p
   for (void *p : {(void *)dv, (void *)dout, (void *)dp})
     if (p) (void)hipFree(p);
   if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_transpose_reduce: %s", hipGetErrorString(e));
+  return ICTR_OK;
+}
+
+// inspection: the solver turn's linear algebra (WaveSolver, ictr_devfn.h) alone on caller systems, one wave each.
+// through_state: the factors go through ProbState (ws_store_factor) and a second launch reloads them (ws_load_factor).
+extern "C" int ictr_debug_wave_solve(const float *H36, const float *b6, int64_t n, int through_state, float *x6, int *rank,
+                                     int *nonzero, int *rowmap6, int *colmap6, float *lu36) {
+  if (!H36 || !b6 || !x6 || !rank || !nonzero || !rowmap6 || !colmap6 || !lu36 || n < 1 || n > (1 << 20))
+    return fail(ICTR_ERR_INVALID, "debug_wave_solve: bad arguments (1 .. 2^20 systems)");
+  if (int rc = need_device()) return rc;
+  const size_t N = (size_t)n;
+  float *df = nullptr;  // H[36 n] | b[6 n] | x[6 n] | lu[36 n]
+  int *di = nullptr;    // rank[n] | nonzero[n] | rowmap[6 n] | colmap[6 n]
+  ProbState *st = nullptr;
+  hipError_t e = hipMalloc((void **)&df, sizeof(float) * 84 * N);
+  if (e == hipSuccess) e = hipMalloc((void **)&di, sizeof(int) * 14 * N);
+  if (e == hipSuccess) e = hipMalloc((void **)&st, sizeof(ProbState) * N);
+  if (e == hipSuccess) e = hipMemset(st, 0, sizeof(ProbState) * N);
+  if (e == hipSuccess) e = hipMemset(df + 42 * N, 0xff, sizeof(float) * 42 * N);
+  if (e == hipSuccess) e = hipMemset(di, 0xff, sizeof(int) * 14 * N);
+  if (e == hipSuccess) e = hipMemcpy(df, H36, sizeof(float) * 36 * N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(df + 36 * N, b6, sizeof(float) * 6 * N, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = launch_debug_wave_solve(df, df + 36 * N, (int)n, st, through_state, df + 42 * N, di, di + N, di + 2 * N,
+                                di + 8 * N, df + 48 * N, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(x6, df + 42 * N, sizeof(float) * 6 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(lu36, df + 48 * N, sizeof(float) * 36 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rank, di, sizeof(int) * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(nonzero, di + N, sizeof(int) * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rowmap6, di + 2 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(colmap6, di + 8 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost);
+  for (void *p : {(void *)df, (void *)di, (void *)st})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_wave_solve: %s", hipGetErrorString(e));
+  return ICTR_OK;
+}
+// inspection: the device builds of se3_exp<float> (in p[6] -> out G[12]) / se3_log<float> (in G[12] -> out p[6])
+extern "C" int ictr_debug_se3(const float *in, int64_t n, int log_not_exp, float *out) {
+  if (!in || !out || n < 1 || n > (1 << 24)) return fail(ICTR_ERR_INVALID, "debug_se3: bad arguments");
+  if (int rc = need_device()) return rc;
+  const size_t ni = (size_t)n * (log_not_exp ? 12 : 6), no = (size_t)n * (log_not_exp ? 6 : 12);
+  float *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, sizeof(float) * (ni + no));
+  if (e == hipSuccess) e = hipMemcpy(d, in, sizeof(float) * ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_debug_se3(d, d + ni, (long long)n, log_not_exp ? 1 : 0, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, d + ni, sizeof(float) * no, hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_se3: %s", hipGetErrorString(e));
   return ICTR_OK;
 }
 

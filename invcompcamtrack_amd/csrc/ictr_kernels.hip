@@ -270,6 +270,70 @@ __global__ __launch_bounds__(64) void k_level_finish(EngineDev e, int defer_h) {
   if (lane == 0) level_reset(st, e);
 }
 
+// inspection (ictr_debug_wave_solve): the solver turn's linear algebra alone, one wave per system. The wave reads the
+// 21 upper-triangle values of its H into LDS and feeds ws_factor through h_unique_index, as the tails above do.
+// apply = 1: factor and substitute in registers (the one-launch and resident forms); apply = 0: factor and store to
+// st[] -- k_debug_wave_apply then reloads the factors in a launch of its own (the per-iteration and sharded forms).
+__device__ __forceinline__ void debug_wave_solve_out(const WaveSolver &S, float bi, int sys, int lane, float *x, int *rank,
+                                                     int *nonzero, int *rowmap, int *colmap, float *lu) {
+  const float xi = ws_apply(S, bi, lane);
+  if (lane < 6) {
+    x[(size_t)sys * 6 + lane] = xi;
+    rowmap[(size_t)sys * 6 + lane] = S.rowmap;
+    colmap[(size_t)sys * 6 + lane] = S.colmap;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) lu[(size_t)sys * 36 + lane * 6 + j] = S.lu[j];
+  }
+  if (lane == 0) {
+    rank[sys] = S.rank;
+    nonzero[sys] = S.nonzero;
+  }
+}
+__global__ __launch_bounds__(64) void k_debug_wave_factor(const float *__restrict__ H, const float *__restrict__ b,
+                                                          ProbState *st, int apply, float *x, int *rank, int *nonzero,
+                                                          int *rowmap, int *colmap, float *lu) {
+  __shared__ float sH[32];
+  const int sys = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (lane < 36 && lane / 6 <= lane % 6) sH[h_unique_index(lane)] = H[(size_t)sys * 36 + lane];
+  __syncthreads();
+  WaveSolver S;
+  ws_factor(S, sH[h_unique_index(lane)], lane);
+  if (apply)
+    debug_wave_solve_out(S, lane < 6 ? b[(size_t)sys * 6 + lane] : 0.0f, sys, lane, x, rank, nonzero, rowmap, colmap, lu);
+  else
+    ws_store_factor(S, st[sys], lane);
+}
+__global__ __launch_bounds__(64) void k_debug_wave_apply(const float *__restrict__ b, const ProbState *st, float *x,
+                                                         int *rank, int *nonzero, int *rowmap, int *colmap, float *lu) {
+  const int sys = blockIdx.x;
+  const int lane = threadIdx.x;
+  WaveSolver S;
+  ws_load_factor(S, st[sys], lane);
+  debug_wave_solve_out(S, lane < 6 ? b[(size_t)sys * 6 + lane] : 0.0f, sys, lane, x, rank, nonzero, rowmap, colmap, lu);
+}
+// inspection (ictr_debug_se3): the device builds of se3_exp<float> (p[6] -> G[12]) and se3_log<float>, one thread each
+__global__ __launch_bounds__(64) void k_debug_se3(const float *__restrict__ in, float *__restrict__ out, long long n,
+                                                  int log_not_exp) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  if (log_not_exp) {
+    float G[12], p[6];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) G[k] = in[i * 12 + k];
+    se3_log<float>(p, G);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[i * 6 + k] = p[k];
+  } else {
+    float G[12], p[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p[k] = in[i * 6 + k];
+    se3_exp<float>(G, p);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) out[i * 12 + k] = G[k];
+  }
+}
+
 // ---------------------------------------------------------------- steps 7-9a: one Gauss-Newton iteration (any patch size)
 template <int PT>
 __global__ __launch_bounds__(kBlock) void k_iter(EngineDev e, LevelCam lc, int level) {
@@ -1682,6 +1746,19 @@ void launch_iter(const EngineDev &e, const LevelCam &lc, int level, int gridx, i
 }
 void launch_iter_finish(const EngineDev &e, int level, int variant, int first, hipStream_t s) {
   hipLaunchKernelGGL(k_iter_finish, dim3(e.B), dim3(64), 0, s, e, level, (first && defer_h(e, variant)) ? 1 : 0);
+}
+
+hipError_t launch_debug_wave_solve(const float *H, const float *b, int n, ProbState *st, int through_state, float *x,
+                                   int *rank, int *nonzero, int *rowmap, int *colmap, float *lu, hipStream_t s) {
+  hipLaunchKernelGGL(k_debug_wave_factor, dim3(n), dim3(64), 0, s, H, b, st, through_state ? 0 : 1, x, rank, nonzero,
+                     rowmap, colmap, lu);
+  if (through_state)
+    hipLaunchKernelGGL(k_debug_wave_apply, dim3(n), dim3(64), 0, s, b, st, x, rank, nonzero, rowmap, colmap, lu);
+  return hipGetLastError();
+}
+hipError_t launch_debug_se3(const float *in, float *out, long long n, int log_not_exp, hipStream_t s) {
+  hipLaunchKernelGGL(k_debug_se3, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, in, out, n, log_not_exp);
+  return hipGetLastError();
 }
 
 }  // namespace ictr

@@ -93,6 +93,17 @@ def test_host_math_is_bit_identical_to_oracle(lib, oracle):
     assert np.array_equal(ic.solve6(Hk, bk), oracle.solve6(Hk, bk))
 
 
+def test_solve6_matches_oracle_on_the_solver_corpus(lib, oracle):
+    """The two serial implementations stay pinned to each other on the finite systems of tests/test_gpu_solver.py's
+    corpus (ranks 0..6, pivots on the threshold, ties, denormal and huge scales, indefinite matrices)."""
+    import invcompcamtrack_amd as ic
+    from parity_util import finite_corpus, same_bits
+    corpus = finite_corpus()
+    assert len(corpus) > 2000
+    bad = [name for name, H, b in corpus if not same_bits(ic.solve6(H, b), oracle.solve6(H, b))]
+    assert not bad, bad
+
+
 def test_cam_and_pose_host_side(lib, oracle):
     import invcompcamtrack_amd as ic
     op = ic.optparam(4, 0, 8, 10, 0.01, 1, 0, 16)

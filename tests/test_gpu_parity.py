@@ -33,7 +33,7 @@ import numpy as np
 import pytest
 
 import invcompcamtrack_amd as ic
-from parity_util import Pair, rel, scene
+from parity_util import Pair, check_solver_turns, rel, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +85,8 @@ def _check_patches(pr, exact_T=True):
 
 
 def _check_trace(pr, check_iters=True, traj_tol=2e-5):
+    # the device's own turn first: every record is the serial solve / update / loop rule of its own H and b, bit for bit
+    check_solver_turns(pr.odo, pr.p_start, pr.op, p_final=pr.p_final)
     to, tg = pr.otr.trace(), pr.odo.trace()
     if check_iters:
         assert [(r["level"], r["iter"]) for r in to] == [(r["level"], r["iter"]) for r in tg]
