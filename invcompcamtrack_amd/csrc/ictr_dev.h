@@ -49,16 +49,6 @@ struct ProbState {
   int pad_;
 };
 
-// team form of the one-launch tracker (ictr_track1.hip, "Teams"): several workgroups per problem
-struct T1Team {
-  int team, q;               // workgroups per problem, points per workgroup
-  unsigned tag0;             // launch epoch << 12
-  unsigned long long limit;  // polling limit, wall_clock64 ticks (100 MHz)
-  unsigned long long *mail;  // [B][2][team][32] granules
-  int *err;                  // sticky time-out flag (pinned host memory as the device sees it)
-  int mute;                  // debug (variant bit 25): part `mute - 1` never posts its values (time-out test); 0 = off
-};
-
 // Cross-GPU exchange inside the resident-iteration launch (ictr_resident.hip, "sharded resident form"): the mailboxes of
 // an ictr_p2p object (ictr_p2p.hip: one per rank, hipIpc-mapped into every peer) as the kernel sees them. world == 1: off.
 constexpr int kXchgMaxWorld = 16;

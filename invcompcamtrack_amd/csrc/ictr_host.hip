@@ -17,59 +17,15 @@
 #include <vector>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "se3_math.h"
 #include "ictr_pose_hd.h"
-
-namespace ictr {
-void launch_pyr_pack(const float *, const float *, const float *, float *, size_t, hipStream_t);
-void launch_pyr_level(const float *, int, int, int, int, float *, float *, float *, float *, int, int, int, int, int, int,
-                      hipStream_t);
-void launch_stream_read(const float *, size_t, float *, hipStream_t);
-void launch_getpatch(const float *, const float *, const float *, const float *, int, int, int, int, float *, float *,
-                     float *, hipStream_t);
-void launch_ncc(const float *, const float *, const float *, const float *, int, int, int, float, float, float, float,
-                float *, hipStream_t);
-void launch_flow_gather(const void *, const void *, int, int, int, const double *, int, double *, hipStream_t);
-void launch_bil_patches(const double *, int, int, int, const double *, int, int, double *, hipStream_t);
-void launch_project_generic(const float *, float *, float *, int, int, const float *, LevelCam, hipStream_t);
-void launch_project_ref(const EngineDev &, const LevelCam *, int, hipStream_t);
-void launch_ref_level(const EngineDev &, const LevelCam &, int, int, int, int, int, bool, hipStream_t);
-void launch_level_finish(const EngineDev &, int, hipStream_t);
-void launch_iter(const EngineDev &, const LevelCam &, int, int, int, int, int, int, hipStream_t);
-void launch_iter_main(const EngineDev &, const LevelCam &, int, int, int, int, int, int, hipStream_t, hipEvent_t,
-                      hipEvent_t);
-void launch_iter_tail(const EngineDev &, int, int, int, int, int, hipStream_t);
-void launch_iter_finish(const EngineDev &, int, int, int, hipStream_t);
-bool defer_h(const EngineDev &, int);
-hipError_t launch_track1(const EngineDev &, const LevelCam *, int, int, const void *, ProbState *, hipStream_t,
-                         const T1Team *, bool project_here = false);
-hipError_t launch_level_resident(const EngineDev &, const LevelCam &, int, int, int, int, int, unsigned, unsigned long long,
-                                 unsigned long long *, int *, int, const ResXchg *, hipStream_t);
-hipError_t launch_debug_transpose_reduce(const float *, float *, int *, int *, int, hipStream_t);
-hipError_t launch_debug_wave_solve(const float *, const float *, int, ProbState *, int, float *, int *, int *, int *, int *,
-                                   float *, hipStream_t);
-hipError_t launch_debug_se3(const float *, float *, long long, int, hipStream_t);
-size_t resident_mail_bytes(int, int);
-int resident_points_per_workgroup(int);
-int resident_blocks_per_cu(int);
-int track1_team_q(int, int);
-int track1_team_size(int, int);
-size_t track1_team_mail_bytes(int, int);
-size_t track1_blob_bytes(void);
-size_t track1_plan(int, int, int, int, int *);
-int cu_count();
-void launch_seq_select(const SeqArgs &, hipStream_t);
-}  // namespace ictr
-
-namespace ictr {
-void launch_patchflow(const PFArgs &, hipStream_t);
-}  // namespace ictr
 
 using namespace ictr;
 
 // ---------------------------------------------------------------- errors
 static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...) {
+int ictr::fail(int code, const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -78,20 +34,6 @@ static int fail(int code, const char *fmt, ...) {
   g_err = buf;
   return code;
 }
-int ictr_fail_(int code, const char *fmt, ...) {  // for the other translation units (ictr_icgn.hip)
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) return fail(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
 
 extern "C" const char *ictr_last_error(void) { return g_err.c_str(); }
 extern "C" int ictr_version(void) { return 100; }
@@ -104,7 +46,6 @@ extern "C" int ictr_set_device(int device) {
   HIPCHK(hipSetDevice(device));
   return ICTR_OK;
 }
-static int need_device();
 // Measured streaming-read bandwidth of this GPU in GB/s: `bytes` of freshly allocated memory (>> the 256 MB Infinity
 // Cache) read `reps` times with plain wide loads. A yardstick for roofline reports next to the vendor peak.
 extern "C" int ictr_stream_read_bandwidth(size_t bytes, int reps, double *gbps_out) {
@@ -205,7 +146,7 @@ extern "C" int ictr_debug_se3(const float *in, int64_t n, int log_not_exp, float
   return ICTR_OK;
 }
 
-static int need_device() {
+int ictr::need_device() {
   if (ictr_device_count() <= 0)
     return fail(ICTR_ERR_NO_DEVICE, "no usable HIP device: the tracker has no CPU fallback");
   return ICTR_OK;
@@ -314,12 +255,7 @@ struct ictr_pyramid {
   float *stage = nullptr;  // device copy of a host frame handed to ictr_pyramid_rebuild (allocated on first use)
 };
 
-struct ictr_pyramid_view {  // internal: what ictr_icgn.hip needs to know about a pyramid
-  int nlev, pad;
-  const int *w, *h, *sw;
-  float *const *img, *const *dx, *const *dy;
-  int getgrad;
-};
+// internal: what ictr_icgn.hip needs to know about a pyramid
 extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v) {
   v->nlev = p->nlev;
   v->pad = p->pad;
@@ -740,8 +676,14 @@ struct TrackPlan {
   int team, team_q;  // k_track1: workgroups per problem (1: not the team form), points per workgroup of a team
   int project_here;  // kFormTrack1 without an explicit begin: the launch projects itself and mirrors the final records
   int mute;          // ICTR_VARIANT_DEBUG_MUTE: one workgroup of every problem never posts (time-out tests)
-  int parts, slots, np;  // kFormResident: worker workgroups per pair, pairs in flight, patches per wave
+  ResidentGeom res;  // kFormResident: worker workgroups per pair, pairs in flight, patches per wave
   int setup_cpw[16], setup_gridx8[16];  // kFormResident: points per wave chunk and workgroups of each level's setup
+};
+// device mailbox of an in-launch exchange; it grows, never shrinks
+struct Mailbox {
+  unsigned long long *d = nullptr;
+  size_t bytes = 0;
+  unsigned epoch = 0;  // tags of a launch: epoch << 12 | exchange number
 };
 struct ProbHost {
   int npts = 0;
@@ -808,14 +750,10 @@ struct ictr_batch {
   ProbState *h_st_pin = nullptr;
   ProbState *d_st_mirror = nullptr;  // h_st_pin as the device sees it (the one-launch tracker stores final states there)
   char *h_up_pin = nullptr;  // pinned staging of the per-tracking uploads (states + plane table): truly asynchronous
-  // team form of the one-launch tracker (several workgroups per problem, ictr_track1.hip "Teams")
-  unsigned long long *d_team_mail = nullptr;  // granule mailboxes [B][2][team][32]; allocated on first use
-  size_t team_mail_bytes = 0;
-  unsigned team_epoch = 0;    // tags of a launch: epoch << 12 | exchange number
-  // resident-iteration form (ictr_resident.hip): all iterations of a level in one launch, templates in registers
-  unsigned long long *d_res_mail = nullptr;  // per slot: gather box + broadcast box
-  size_t res_mail_bytes = 0;
-  unsigned res_epoch = 0;
+  // mailboxes of the in-launch exchanges, allocated on first use (exchange_prepare): the team form of the one-launch
+  // tracker ([B][2][team][32] granules, ictr_track1.hip "Teams") and the resident-iteration form (per slot a gather box
+  // and a broadcast box, ictr_resident.hip)
+  Mailbox team_mail, res_mail;
   int team_target = 0;        // points per workgroup aimed at (0: automatic, < 0: no teams); ictr_batch_set_team
   int team_lo = 128, team_hi = 8192;  // problem sizes (points) served by teams: lo < maxpts <= hi
   int *h_team_err = nullptr;  // pinned: an exchange of some launch timed out (sticky)
@@ -826,7 +764,7 @@ struct ictr_batch {
 
 // the plane table's place behind the B records in their common device block / staging buffer (16-byte aligned)
 static size_t up_planes_offset(int B) { return (sizeof(ProbState) * (size_t)B + 15) / 16 * 16; }
-static int env_int(const char *name, int dflt) {
+int ictr::env_int(const char *name, int dflt) {
   const char *s = getenv(name);
   return s ? atoi(s) : dflt;
 }
@@ -842,8 +780,8 @@ static void batch_free(ictr_batch *b) {
   if (b->h_st_pin) (void)hipHostFree(b->h_st_pin);
   if (b->h_up_pin) (void)hipHostFree(b->h_up_pin);
   if (b->h_team_err) (void)hipHostFree(b->h_team_err);
-  if (b->d_team_mail) (void)hipFree(b->d_team_mail);
-  if (b->d_res_mail) (void)hipFree(b->d_res_mail);
+  if (b->team_mail.d) (void)hipFree(b->team_mail.d);
+  if (b->res_mail.d) (void)hipFree(b->res_mail.d);
   if (b->d_xseq) (void)hipFree(b->d_xseq);
   b->d_red = b->d_red_own;
   for (void *p : {(void *)b->d_pt3d, (void *)b->d_pt3d_ref, (void *)b->d_pt2d, (void *)b->d_T, (void *)b->d_Gx,
@@ -994,7 +932,6 @@ extern "C" int ictr_batch_set_team(ictr_batch *b, int target_points, int min_poi
   b->team_hi = max_points;
   return ICTR_OK;
 }
-extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 // Sharded resident form: the batch holds this rank's SHARD of every problem's points; its resident-iteration launches
 // then add H (once per level) and b (once per iteration) over the ranks themselves -- the solver workgroup of a frame
 // pair writes its sums into every rank's mailbox and polls its own (ictr_p2p.hip's one-hop protocol, inside the launch).
@@ -1241,6 +1178,18 @@ extern "C" int ictr_batch_enable_sharding(ictr_batch *b, int enable) {
 }
 extern "C" float *ictr_batch_reduction_buffer(ictr_batch *b) { return b ? b->d_red : nullptr; }
 
+// Launch geometry of one level's kernels. p: the tracking's plan (NULL: the phase API, which has none) -- the setup
+// launches of the resident form have a chunk size of their own (resident_setup_plan)
+static LevelLaunch level_launch(const ictr_batch *b, const TrackPlan *p, int level) {
+  const bool res = p && p->form == kFormResident;
+  LevelLaunch ll;
+  ll.level = level;
+  ll.variant = p ? p->variant : engine_variant(b);
+  ll.gridx = b->gridx;
+  ll.cpw = res ? p->setup_cpw[level] : b->cpw;
+  ll.gridx8 = res ? p->setup_gridx8[level] : b->gridx8;
+  return ll;
+}
 static int level_ok(ictr_batch *b, int level) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
   if (!b->projected) return fail(ICTR_ERR_STATE, "ictr_batch_begin has not run since the last SetPose");
@@ -1256,15 +1205,14 @@ extern "C" int ictr_batch_level_allreduce_needed(ictr_batch *b) {
 extern "C" int ictr_batch_level_accumulate(ictr_batch *b, int level) {
   if (int rc = level_ok(b, level)) return rc;
   b->phase_it = 0;
-  launch_ref_level(engine_dev(b), level_cam(b->cam, level), level, b->gridx, engine_variant(b), b->cpw, b->gridx8, true,
-                   b->stream);
+  launch_ref_level(engine_dev(b), level_cam(b->cam, level), level_launch(b, nullptr, level), true, b->stream);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 extern "C" int ictr_batch_level_finish(ictr_batch *b, int level) {
   if (int rc = level_ok(b, level)) return rc;
   b->phase_it = 0;
-  if (b->sharded) launch_level_finish(engine_dev(b), engine_variant(b), b->stream);
+  if (b->sharded) launch_level_finish(engine_dev(b), level_launch(b, nullptr, level), b->stream);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
@@ -1274,27 +1222,26 @@ extern "C" int ictr_batch_iter_accumulate(ictr_batch *b, int level) {
   const bool tk = b->timing && b->phase_it < b->evk_iters && (int)b->evk.size() >= 2 * b->nlev * b->evk_iters;
   const EngineDev e = engine_dev(b);
   const LevelCam lc = level_cam(b->cam, level);
+  const LevelLaunch ll = level_launch(b, nullptr, level);
   const int first = b->phase_it == 0;
   const int ke = 2 * (level * b->evk_iters + b->phase_it);
-  launch_iter_main(e, lc, level, b->gridx, engine_variant(b), b->cpw, b->gridx8, first, b->stream,
-                   tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
+  launch_iter_main(e, lc, ll, first, b->stream, tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
   if (tk && b->phase_it + 1 == std::min(b->op->maxiter, b->evk_iters)) b->ev_used[level] = 2;  // kernel events complete
   b->phase_it++;
-  launch_iter_tail(e, level, b->gridx, engine_variant(b), b->gridx8, first, b->stream);
+  launch_iter_tail(e, ll, first, b->stream);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 extern "C" int ictr_batch_iter_finish(ictr_batch *b, int level) {
   if (int rc = level_ok(b, level)) return rc;
-  if (b->sharded) launch_iter_finish(engine_dev(b), level, engine_variant(b), b->phase_it == 1, b->stream);
+  if (b->sharded) launch_iter_finish(engine_dev(b), level_launch(b, nullptr, level), b->phase_it == 1, b->stream);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 
 // ---------------------------------------------------------------- launch forms of a batch tracking
 // CUs of the calling thread's current device, queried once per device
-namespace ictr {
-int cu_count() {
+int ictr::cu_count() {
   static std::atomic<int> n_cu[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
@@ -1311,7 +1258,6 @@ int cu_count() {
   }
   return v;
 }
-}  // namespace ictr
 
 // Always the same workgroup shape of the one-launch tracker: which wave owns which patch -- and with it the order of every
 // sum -- then depends on the problem's own point count only, so a problem gives the same bits whatever else shares its
@@ -1357,7 +1303,7 @@ static int track1_team(const ictr_batch *b, int *q) {
 // teams of the one-launch tracker (r03: 64 x 1000 points 0.88 -> 0.76 ms, 16 x 3000 0.91 -> 0.56, 12 x 4000 0.91 ->
 // 0.56, 8 x 6000 0.97 -> 0.58, 128 x 500 0.85 -> 0.75, 256 x 1000 3.39 -> 2.06; below that total the teams win: 8 x 5000
 // 0.49 against 0.53, 16 x 2500 0.49 / 0.54, 32 x 800 0.43 / 0.48; so do problems of 300 points at any batch size).
-// Fills p->parts / slots / np; false: not this form.
+// Fills p->res; false: not this form.
 static bool resident_plan(const ictr_batch *b, TrackPlan *p) {
   if (b->P != 8 || b->robust || b->sharded || b->op->dopatchnorm || b->op->maxiter < 1) return false;
   const bool xchg = b->xchg.world > 1;  // sharded resident form: any shard size (an empty shard still runs its solvers)
@@ -1376,9 +1322,7 @@ static bool resident_plan(const ictr_batch *b, TrackPlan *p) {
     if (slots < 1) continue;
     if (np == 16 && slots < b->B && !xchg) continue;
     if ((int64_t)((b->B + slots - 1) / slots) * b->op->maxiter >= 4000) return false;  // exchange number: 12 bits
-    p->parts = parts;
-    p->slots = slots;
-    p->np = np;
+    p->res = ResidentGeom{parts, slots, np};
     return true;
   }
   return false;
@@ -1454,7 +1398,7 @@ static TrackPlan plan_tracking(const ictr_batch *b, bool begun) {
     }
   }
   if (t1) {
-    p.parts = p.slots = p.np = 0;
+    p.res = ResidentGeom{0, 0, 0};
     const bool separate = begun || b->trace_on || !b->d_st_mirror || (v & ICTR_VARIANT_SEPARATE_BEGIN);
     const size_t up = sizeof(ProbState) * b->B + sizeof(PlaneSet) * b->h_planes.size();
     p.form = (!separate && up <= track1_blob_bytes()) ? kFormTrack1Begin : kFormTrack1;
@@ -1539,54 +1483,55 @@ static double team_timeout_s() {
   const char *s = getenv("ICTR_TEAM_TIMEOUT_S");
   return s ? std::max(0.001, atof(s)) : 5.0;
 }
-// the pinned sticky time-out flag of in-launch exchanges (team form, resident form), allocated on first use
-static int team_err_alloc(ictr_batch *b) {
-  if (!b->h_team_err) {
+// Mailbox, tag epoch, polling limit and error flag of the next launch with an in-launch exchange (team form of k_track1,
+// k_level_resident) that will run on `s` and needs `need` bytes of mailbox `m`. The protocol's host side, whole: a granule
+// counts when its tag is the launch's epoch << 12 | exchange number, so a mailbox is cleared (tag 0: "nothing yet") when it
+// is made and when the 20-bit epoch wraps, on the stream of the launch; every launch gets the next epoch, and nothing an
+// earlier or failed launch left behind can match. what: the mailbox's name in the error text.
+static int exchange_prepare(ictr_batch *b, Mailbox *m, size_t need, const char *what, int mute, hipStream_t s,
+                            Exchange *x) {
+  if (need > m->bytes) {
+    if (m->d) {
+      HIPCHK(hipStreamSynchronize(s));  // an earlier launch may still be polling the old mailbox
+      HIPCHK(hipFree(m->d));
+      *m = Mailbox{};
+    }
+    // granules are written and polled with agent-scope accesses; uncached device memory keeps them out of the L2s
+    hipError_t e = hipExtMallocWithFlags((void **)&m->d, need, hipDeviceMallocUncached);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      e = hipMalloc((void **)&m->d, need);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(m->d, 0, need, s);
+    if (e != hipSuccess) return fail(ICTR_ERR_HIP, "%s mailbox allocation failed: %s", what, hipGetErrorString(e));
+    m->bytes = need;
+    m->epoch = 0;
+  }
+  if (!b->h_team_err) {  // the pinned sticky time-out flag, shared by every exchange of the batch
     HIPCHK(hipHostMalloc((void **)&b->h_team_err, sizeof(int), hipHostMallocDefault));
     *b->h_team_err = 0;
     HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err, 0));
   }
+  m->epoch += 1;
+  if (m->epoch >= (1u << 20)) {  // the epoch field wrapped: forget every old tag
+    HIPCHK(hipMemsetAsync(m->d, 0, m->bytes, s));
+    m->epoch = 1;
+  }
+  x->tag0 = m->epoch << 12;
+  x->limit = (unsigned long long)(team_timeout_s() * 1e8);
+  x->mail = m->d;
+  x->err = b->d_team_err;
+  x->mute = mute;
   return ICTR_OK;
 }
-// mailbox, tag epoch and error flag of the next team launch (p.team == 1: not a team launch, nothing allocated)
+// the team of the next k_track1 launch with its exchange (p.team == 1: not a team launch, nothing allocated)
 static int team_prepare(ictr_batch *b, const TrackPlan &p, T1Team *tm) {
   memset(tm, 0, sizeof(*tm));
   tm->team = 1;
   if (p.team < 2) return ICTR_OK;
   tm->team = p.team;
   tm->q = p.team_q;
-  const size_t need = track1_team_mail_bytes(b->B, tm->team);
-  if (need > b->team_mail_bytes) {
-    if (b->d_team_mail) {
-      HIPCHK(hipStreamSynchronize(b->stream));  // an earlier launch may still be polling the old mailbox
-      HIPCHK(hipFree(b->d_team_mail));
-      b->d_team_mail = nullptr;
-      b->team_mail_bytes = 0;
-    }
-    // granules are written and polled with agent-scope accesses; uncached device memory keeps them out of the L2s
-    hipError_t e = hipExtMallocWithFlags((void **)&b->d_team_mail, need, hipDeviceMallocUncached);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      e = hipMalloc((void **)&b->d_team_mail, need);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(b->d_team_mail, 0, need, b->stream);  // tag 0: "nothing yet"
-    if (e != hipSuccess) return fail(ICTR_ERR_HIP, "team mailbox allocation failed: %s", hipGetErrorString(e));
-    b->team_mail_bytes = need;
-    b->team_epoch = 0;
-  }
-  if (int rc = team_err_alloc(b)) return rc;
-  b->team_epoch += 1;
-  if (b->team_epoch >= (1u << 20)) {  // the epoch field wrapped: forget every old tag
-    HIPCHK(hipMemsetAsync(b->d_team_mail, 0, b->team_mail_bytes, b->stream));
-    b->team_epoch = 1;
-  }
-  const double limit_s = team_timeout_s();
-  tm->tag0 = b->team_epoch << 12;
-  tm->mute = p.mute;  // debug: part 0 never posts (the time-out path's test)
-  tm->limit = (unsigned long long)(limit_s * 1e8);
-  tm->mail = b->d_team_mail;
-  tm->err = b->d_team_err;
-  return ICTR_OK;
+  return exchange_prepare(b, &b->team_mail, track1_team_mail_bytes(b->B, p.team), "team", p.mute, b->stream, &tm->x);
 }
 // ONE k_track1 launch for every problem of `e` on the batch's stream, through the team admission when the plan has
 // teams. blob: the begin phase in the arguments (kFormTrack1Begin); host_st: the pinned mirror the launch writes the final
@@ -1607,41 +1552,16 @@ static int track1_launch(ictr_batch *b, const EngineDev &e, const TrackPlan &p, 
 }
 
 // one level's iterations as ONE resident launch (behind the level's setup launches on the same stream)
-static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc, int level, const TrackPlan &p, int nblk,
-                           hipStream_t s) {
-  const size_t need = resident_mail_bytes(p.parts, p.slots);
-  if (need > b->res_mail_bytes) {
-    if (b->d_res_mail) {
-      HIPCHK(hipStreamSynchronize(s));
-      HIPCHK(hipFree(b->d_res_mail));
-      b->d_res_mail = nullptr;
-      b->res_mail_bytes = 0;
-    }
-    hipError_t er = hipExtMallocWithFlags((void **)&b->d_res_mail, need, hipDeviceMallocUncached);
-    if (er != hipSuccess) {
-      (void)hipGetLastError();
-      er = hipMalloc((void **)&b->d_res_mail, need);
-    }
-    if (er == hipSuccess) er = hipMemsetAsync(b->d_res_mail, 0, need, s);  // tag 0: "nothing yet"
-    if (er != hipSuccess) return fail(ICTR_ERR_HIP, "resident mailbox allocation failed: %s", hipGetErrorString(er));
-    b->res_mail_bytes = need;
-    b->res_epoch = 0;
-  }
-  if (int rc = team_err_alloc(b)) return rc;
-  b->res_epoch += 1;
-  if (b->res_epoch >= (1u << 20)) {
-    HIPCHK(hipMemsetAsync(b->d_res_mail, 0, b->res_mail_bytes, s));
-    b->res_epoch = 1;
-  }
-  const double limit_s = team_timeout_s();
+static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc, const LevelLaunch &ll,
+                           const TrackPlan &p, hipStream_t s) {
+  const ResidentGeom &g = p.res;
+  Exchange x;
+  if (int rc = exchange_prepare(b, &b->res_mail, resident_mail_bytes(g.parts, g.slots), "resident", p.mute, s, &x)) return rc;
   // every workgroup of the launch must be resident: it starts when its slots are free of team / resident launches
-  const int bpc = std::max(1, std::min(4, resident_blocks_per_cu(p.np)));
-  const int weight = p.slots * (p.parts + 1) * ((4 + bpc - 1) / bpc);
+  const int bpc = std::max(1, std::min(4, resident_blocks_per_cu(g.np)));
+  const int weight = g.slots * (g.parts + 1) * ((4 + bpc - 1) / bpc);
   return team_launch(weight, s, [&]() -> int {
-    // (mute, debug: worker 0 never posts its sums -- the time-out test)
-    HIPCHK(launch_level_resident(e, lc, level, p.np, p.parts, p.slots, nblk, b->res_epoch << 12,
-                                 (unsigned long long)(limit_s * 1e8), b->d_res_mail, b->d_team_err, p.mute,
-                                 b->xchg.world > 1 ? &b->xchg : nullptr, s));
+    HIPCHK(launch_level_resident(e, lc, ll.level, g, tail_partials(e, ll), x, b->xchg.world > 1 ? &b->xchg : nullptr, s));
     return ICTR_OK;
   });
 }
@@ -1657,18 +1577,16 @@ static int enqueue_level_kernels(ictr_batch *b, const EngineDev &e, const TrackP
   for (int sl = b->op->lv_f; sl >= b->op->lv_l; --sl) {
     const LevelCam lc = level_cam(b->cam, sl);
     if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 0], s));
+    const LevelLaunch ll = level_launch(b, &p, sl);
+    launch_ref_level(e, lc, ll, !resident, s);
+    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
     if (resident) {
-      launch_ref_level(e, lc, sl, b->gridx, p.variant, p.setup_cpw[sl], p.setup_gridx8[sl], false, s);
-      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
-      if (int rc = launch_resident(b, e, lc, sl, p, p.setup_gridx8[sl], s)) return rc;
+      if (int rc = launch_resident(b, e, lc, ll, p, s)) return rc;
     } else {
-      launch_ref_level(e, lc, sl, b->gridx, p.variant, b->cpw, b->gridx8, true, s);
-      if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
       for (int it = 0; it < mi; ++it) {
         const int ke = 2 * (sl * b->evk_iters + it);
-        launch_iter_main(e, lc, sl, b->gridx, p.variant, b->cpw, b->gridx8, it == 0, s, tk ? b->evk[ke] : nullptr,
-                         tk ? b->evk[ke + 1] : nullptr);
-        launch_iter_tail(e, sl, b->gridx, p.variant, b->gridx8, it == 0, s);
+        launch_iter_main(e, lc, ll, it == 0, s, tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
+        launch_iter_tail(e, ll, it == 0, s);
       }
     }
     if (events) {
@@ -2486,251 +2404,3 @@ extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *
 
 // workgroups per tracking launch of the last run (before the first run: the form the cap selects)
 extern "C" int ictr_sequence_last_team(const ictr_sequence *s) { return s ? s->b->plan.team : 0; }
-
-// ---------------------------------------------------------------- RANSAC pose sampling (func_ransac_fitcameras_odom.m:17-87)
-// The trials run in chunks of K on one stream (ictr_ransac.hip): hypotheses, scoring, ordered selection per chunk, then
-// the post-filter once. Chunks are enqueued in groups; between two groups the run reads the 4-byte `done` flag, so a
-// run whose samples are found early does not enqueue the rest. One read-back at the end.
-namespace ictr {
-void launch_ransac_chunk(const RansacArgs &, int, hipStream_t);
-void launch_ransac_finish(const RansacArgs &, hipStream_t);
-}  // namespace ictr
-
-static constexpr int kRanGroup = 64;  // chunks enqueued between two reads of `done`
-
-struct ictr_ransac {
-  int n = 0, nwords = 0;
-  int64_t smax = 0;
-  int chunk = 0, tile = 32;
-  hipStream_t stream = nullptr;
-  double *d_pts = nullptr;
-  double *d_hyp = nullptr;
-  int *d_draws = nullptr, *d_status = nullptr;
-  unsigned *d_cnt = nullptr;
-  unsigned long long *d_words = nullptr;
-  char *d_out = nullptr, *h_out = nullptr;  // RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] |
-                                            // t [smax][3] | words [smax][nwords] | cnt [n] | keep [smax] | cntf [n]
-  size_t out_bytes = 0;
-  bool points_set = false, pending = false, ran = false;
-  hipEvent_t done = nullptr;
-};
-
-struct RanLayout {
-  size_t trial, draws, R, t, words, cnt, keep, cntf, end;
-};
-static RanLayout ran_layout(const ictr_ransac *r) {
-  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-  RanLayout L;
-  const size_t S = (size_t)r->smax;
-  L.trial = up(sizeof(RansacState));
-  L.draws = up(L.trial + 8 * S);
-  L.R = up(L.draws + 16 * S);
-  L.t = up(L.R + 72 * S);
-  L.words = up(L.t + 24 * S);
-  L.cnt = up(L.words + 8 * S * r->nwords);
-  L.keep = up(L.cnt + 4 * (size_t)r->n);
-  L.cntf = up(L.keep + 4 * S);
-  L.end = up(L.cntf + 4 * (size_t)r->n);
-  return L;
-}
-
-// trials per chunk: enough that one chunk's scoring (K x N lane tests) fills the device; ICTR_RANSAC_CHUNK overrides.
-// Constants from tools/ransac_bench.py --sweep (profiles/ransac_sweep.json).
-static int ransac_chunk(int n) {
-  const int env = env_int("ICTR_RANSAC_CHUNK", 0);
-  if (env > 0) return env;
-  long long k = (1ll << 23) / n;
-  k = std::max(256ll, std::min(16384ll, k));
-  return (int)((k + 255) / 256 * 256);
-}
-
-static void ran_free(ictr_ransac *r) {
-  if (!r) return;
-  if (r->pending) (void)hipEventSynchronize(r->done);
-  if (r->done) (void)hipEventDestroy(r->done);
-  if (r->h_out) (void)hipHostFree(r->h_out);
-  for (void *p : {(void *)r->d_pts, (void *)r->d_hyp, (void *)r->d_draws, (void *)r->d_status, (void *)r->d_cnt,
-                  (void *)r->d_words, (void *)r->d_out})
-    if (p) (void)hipFree(p);
-  delete r;
-}
-
-static int ran_refuse_pending(const ictr_ransac *r, const char *what) {
-  if (r->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_ransac_wait first", what);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samples) {
-  if (!out) return fail(ICTR_ERR_INVALID, "ransac_create: NULL argument");
-  if (n < 4 || n > ((int64_t)1 << 24))
-    return fail(ICTR_ERR_INVALID, "ransac_create: %lld matches (4 .. 2^24)", (long long)n);
-  if (max_samples < 1 || max_samples > ((int64_t)1 << 24))
-    return fail(ICTR_ERR_INVALID, "ransac_create: max_samples %lld (1 .. 2^24)", (long long)max_samples);
-  if (int rc = need_device()) return rc;
-  ictr_ransac *r = new ictr_ransac;
-  r->n = (int)n;
-  r->nwords = (int)((n + 63) / 64);
-  r->smax = max_samples;
-  r->chunk = ransac_chunk(r->n);
-  const int tile = env_int("ICTR_RANSAC_TILE", 32);
-  r->tile = (tile == 16 || tile == 64) ? tile : 32;
-  const size_t K = (size_t)r->chunk;
-  r->out_bytes = ran_layout(r).end;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-  };
-  alloc((void **)&r->d_pts, sizeof(double) * 5 * n);
-  alloc((void **)&r->d_hyp, sizeof(double) * 12 * K);
-  alloc((void **)&r->d_draws, sizeof(int) * 4 * K);
-  alloc((void **)&r->d_status, sizeof(int) * K);
-  alloc((void **)&r->d_cnt, sizeof(unsigned) * K);
-  alloc((void **)&r->d_words, sizeof(unsigned long long) * K * r->nwords);
-  alloc((void **)&r->d_out, r->out_bytes);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_out, r->out_bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    ran_free(r);
-    return fail(ICTR_ERR_HIP, "ransac_create: device allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = r;
-  return ICTR_OK;
-}
-
-extern "C" void ictr_ransac_destroy(ictr_ransac *r) { ran_free(r); }
-
-extern "C" int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const double *pt3d) {
-  if (!r || !pt2d || !pt3d) return fail(ICTR_ERR_INVALID, "ransac_set_points: NULL argument");
-  if (int rc = ran_refuse_pending(r, "ransac_set_points")) return rc;
-  const size_t n = (size_t)r->n;
-  HIPCHK(hipMemcpy(r->d_pts, pt2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(r->d_pts + 2 * n, pt3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
-  r->points_set = true;
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ransac_chunk_size(const ictr_ransac *r) { return r ? r->chunk : 0; }
-
-extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples,
-                               int64_t maxtrials, double inlthresh, uint64_t seed, void *hip_stream) {
-  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ransac_run: NULL argument");
-  if (int rc = ran_refuse_pending(r, "ransac_run")) return rc;
-  if (!r->points_set) return fail(ICTR_ERR_STATE, "ransac_run: ictr_ransac_set_points has not been called");
-  if (nsamples < 1 || nsamples > r->smax)
-    return fail(ICTR_ERR_INVALID, "ransac_run: nsamples %lld (1 .. %lld, the size given at creation)",
-                (long long)nsamples, (long long)r->smax);
-  if (maxtrials < 1 || maxtrials > ((int64_t)1 << 40))
-    return fail(ICTR_ERR_INVALID, "ransac_run: maxtrials %lld (1 .. 2^40)", (long long)maxtrials);
-  if (!std::isfinite(inlthresh)) return fail(ICTR_ERR_INVALID, "ransac_run: inlthresh is not finite");
-  if (!std::isfinite(kc) || !std::isfinite(fc[0]) || !std::isfinite(fc[1]) || fc[0] == 0.0 || fc[1] == 0.0 ||
-      !std::isfinite(cc[0]) || !std::isfinite(cc[1]))
-    return fail(ICTR_ERR_INVALID, "ransac_run: the camera (fc, cc, kc) must be finite, fc non-zero");
-  r->stream = (hipStream_t)hip_stream;
-  const RanLayout L = ran_layout(r);
-  RansacArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pts = r->d_pts;
-  a.n = r->n;
-  a.nwords = r->nwords;
-  a.fx = fc[0];
-  a.fy = fc[1];
-  a.cx = cc[0];
-  a.cy = cc[1];
-  a.kc = kc;
-  a.thr = inlthresh;
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull;  // splitmix64 (the device's ran_mix)
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  a.seedmix = z ^ (z >> 31);
-  a.nsamples = nsamples;
-  a.maxtrials = maxtrials;
-  a.hyp = r->d_hyp;
-  a.draws = r->d_draws;
-  a.status = r->d_status;
-  a.cnt = r->d_cnt;
-  a.words = r->d_words;
-  a.st = reinterpret_cast<RansacState *>(r->d_out);
-  a.o_trial = reinterpret_cast<long long *>(r->d_out + L.trial);
-  a.o_draws = reinterpret_cast<int *>(r->d_out + L.draws);
-  a.o_R = reinterpret_cast<double *>(r->d_out + L.R);
-  a.o_t = reinterpret_cast<double *>(r->d_out + L.t);
-  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out + L.words);
-  a.o_cnt = reinterpret_cast<int *>(r->d_out + L.cnt);
-  a.o_keep = reinterpret_cast<int *>(r->d_out + L.keep);
-  a.o_cntf = reinterpret_cast<int *>(r->d_out + L.cntf);
-  HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), r->stream));
-  const int64_t K = r->chunk;
-  const int64_t nchunks = (maxtrials + K - 1) / K;
-  for (int64_t c = 0; c < nchunks; ++c) {
-    if (c > 0 && c % kRanGroup == 0) {  // a long run: stop enqueueing once the samples are found
-      RansacState *hs = reinterpret_cast<RansacState *>(r->h_out);
-      HIPCHK(hipMemcpyAsync(&hs->done, &a.st->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
-      HIPCHK(hipStreamSynchronize(r->stream));
-      if (*(volatile int *)&hs->done) break;
-    }
-    a.base = c * K;
-    a.k = (int)std::min<int64_t>(K, maxtrials - a.base);
-    launch_ransac_chunk(a, r->tile, r->stream);
-    HIPCHK(hipGetLastError());
-  }
-  launch_ransac_finish(a, r->stream);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out, r->out_bytes, hipMemcpyDeviceToHost, r->stream));
-  HIPCHK(hipEventRecord(r->done, r->stream));
-  r->pending = true;
-  r->ran = true;
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, double *t, double *p, uint64_t *inl_words,
-                                int32_t *inl_cnt) {
-  if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
-  if (!r->pending) return fail(ICTR_ERR_STATE, "ransac_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(r->done));
-  r->pending = false;
-  const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
-  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
-  const double *hR = reinterpret_cast<const double *>(r->h_out + L.R);
-  const double *ht = reinterpret_cast<const double *>(r->h_out + L.t);
-  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->h_out + L.words);
-  if (counts) {
-    counts[0] = st.kept;
-    counts[1] = st.held;
-    counts[2] = st.trials_used;
-    counts[3] = st.n_ic;
-  }
-  for (long long q = 0; q < st.kept; ++q) {
-    const size_t s = (size_t)keep[q];
-    if (R) memcpy(R + 9 * q, hR + 9 * s, 9 * sizeof(double));
-    if (t) memcpy(t + 3 * q, ht + 3 * s, 3 * sizeof(double));
-    if (p) {  // p = se3_log([R | -R t]) (ictr_ransac.hip: on the host, at the read-back)
-      const double *Rs = hR + 9 * s, *ts = ht + 3 * s;
-      double G[12];
-      for (int i = 0; i < 3; ++i) {
-        for (int c = 0; c < 3; ++c) G[i * 4 + c] = Rs[i * 3 + c];
-        G[i * 4 + 3] = -Rs[i * 3 + 0] * ts[0] - Rs[i * 3 + 1] * ts[1] - Rs[i * 3 + 2] * ts[2];
-      }
-      se3_log<double>(p + 6 * q, G);
-    }
-    if (inl_words) memcpy(inl_words + (size_t)r->nwords * q, hw + (size_t)r->nwords * s, 8 * (size_t)r->nwords);
-  }
-  if (inl_cnt) memcpy(inl_cnt, r->h_out + L.cntf, sizeof(int32_t) * (size_t)st.n_ic);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws) {
-  if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
-  if (r->pending || !r->ran) return fail(ICTR_ERR_STATE, "ransac_samples: no completed run");
-  const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
-  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
-  const long long *ht = reinterpret_cast<const long long *>(r->h_out + L.trial);
-  const int *hd = reinterpret_cast<const int *>(r->h_out + L.draws);
-  for (long long q = 0; q < st.kept; ++q) {
-    if (trial) trial[q] = ht[keep[q]];
-    if (draws) memcpy(draws + 4 * q, hd + 4 * (size_t)keep[q], 4 * sizeof(int32_t));
-  }
-  return ICTR_OK;
-}

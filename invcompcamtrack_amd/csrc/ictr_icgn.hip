@@ -29,15 +29,13 @@
 #include <vector>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "se3_math.h"
 
 // Nothing in this file has to round like the reference's CPU build (there is no reference for it): let the compiler
 // contract a*b+c into FMAs here although the library is built with -ffp-contract=off. The kernels are within 2x of
 // being VALU-bound (about 80 lane-instructions per pixel for the homography without FMA), so this matters.
 #pragma clang fp contract(fast)
-
-extern "C" const char *ictr_last_error(void);
-int ictr_fail_(int code, const char *fmt, ...);  // ictr_host.hip
 
 namespace ictr {
 
@@ -641,20 +639,6 @@ __global__ __launch_bounds__(kBlock) void k_icgn_iter_tail(IcDev e, float f_leve
 using namespace ictr;
 
 // ---------------------------------------------------------------- host side
-#define HIPCHK_IC(expr)                                                                                     \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) return ictr_fail_(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
-
-struct ictr_pyramid_view {  // what ictr_host.hip exposes about a pyramid
-  int nlev, pad;
-  const int *w, *h, *sw;
-  float *const *img, *const *dx, *const *dy;
-  int getgrad;
-};
-extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v);  // ictr_host.hip
-
 struct ictr_icgn {
   int model = 0, w = 0, h = 0, lv_f = 0, lv_l = 0, maxiter = 0, B = 0, nlev = 0, pad = -1;
   float eps = 0;
@@ -727,10 +711,10 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
                                 const int *region_xywh, int64_t nproblems) {
   if (!out || model < 0 || model > 3 || w < 8 || h < 8 || lv_l < 0 || lv_f < lv_l || lv_f > 15 || maxiter < 0 ||
       nproblems < 1 || nproblems > 65535)
-    return ictr_fail_(ICTR_ERR_INVALID, "icgn_create: bad arguments");
+    return fail(ICTR_ERR_INVALID, "icgn_create: bad arguments");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return ictr_fail_(ICTR_ERR_NO_DEVICE, "no usable HIP device: the alignment engine has no CPU fallback");
+    return fail(ICTR_ERR_NO_DEVICE, "no usable HIP device: the alignment engine has no CPU fallback");
   ictr_icgn *g = new ictr_icgn;
   g->model = model;
   g->w = w;
@@ -751,7 +735,7 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
   if (g->region[0] < 0 || g->region[1] < 0 || g->region[2] < 1 || g->region[3] < 1 || g->region[0] + g->region[2] > w ||
       g->region[1] + g->region[3] > h) {
     delete g;
-    return ictr_fail_(ICTR_ERR_INVALID, "icgn_create: template region outside the frame");
+    return fail(ICTR_ERR_INVALID, "icgn_create: template region outside the frame");
   }
   g->rows[0] = 0;
   g->rows[1] = h;
@@ -777,7 +761,7 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
   alloc((void **)&g->d_red, sizeof(float) * (size_t)g->B * kIcRed);
   if (e != hipSuccess) {
     delete g;
-    return ictr_fail_(ICTR_ERR_HIP, "icgn_create: device allocation failed: %s", hipGetErrorString(e));
+    return fail(ICTR_ERR_HIP, "icgn_create: device allocation failed: %s", hipGetErrorString(e));
   }
   g->d_red_own = g->d_red;
   g->h_st.resize(g->B);
@@ -796,19 +780,19 @@ extern "C" void ictr_icgn_destroy(ictr_icgn *g) {
   delete g;
 }
 extern "C" int ictr_icgn_set_stream(ictr_icgn *g, void *s) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   g->stream = (hipStream_t)s;
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_set_frames(ictr_icgn *g, int64_t problem, const ictr_pyramid *tmpl, const ictr_pyramid *cur) {
-  if (!g || problem < 0 || problem >= g->B || !tmpl || !cur) return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_frames: bad arguments");
+  if (!g || problem < 0 || problem >= g->B || !tmpl || !cur) return fail(ICTR_ERR_INVALID, "icgn_set_frames: bad arguments");
   ictr_pyramid_view a, c;
   ictr_pyramid_view_(tmpl, &a);
   ictr_pyramid_view_(cur, &c);
   if (a.nlev < g->nlev || c.nlev < g->nlev || !a.getgrad || a.pad < 2 || a.pad != c.pad || a.w[0] != g->w || a.h[0] != g->h ||
       c.w[0] != g->w || c.h[0] != g->h)
-    return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_frames: pyramids do not match the engine (size, levels, pad >= 2, gradients)");
-  if (g->pad >= 0 && g->pad != a.pad) return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_frames: all pyramids must share one padding");
+    return fail(ICTR_ERR_INVALID, "icgn_set_frames: pyramids do not match the engine (size, levels, pad >= 2, gradients)");
+  if (g->pad >= 0 && g->pad != a.pad) return fail(ICTR_ERR_INVALID, "icgn_set_frames: all pyramids must share one padding");
   g->pad = a.pad;
   if (g->lw.empty()) {
     g->lw.assign(a.w, a.w + g->nlev);
@@ -817,7 +801,7 @@ extern "C" int ictr_icgn_set_frames(ictr_icgn *g, int64_t problem, const ictr_py
   }
   for (int l = 0; l < g->nlev; ++l) {
     if (a.w[l] != g->lw[l] || c.w[l] != g->lw[l] || a.h[l] != g->lh[l] || c.h[l] != g->lh[l])
-      return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_frames: level %d size mismatch", l);
+      return fail(ICTR_ERR_INVALID, "icgn_set_frames: level %d size mismatch", l);
     PlaneSet &ps = g->h_planes[(size_t)problem * g->nlev + l];
     ps.ref = a.img[l];
     ps.dx = a.dx[l];
@@ -829,11 +813,11 @@ extern "C" int ictr_icgn_set_frames(ictr_icgn *g, int64_t problem, const ictr_py
 }
 // M9: row-major 3x3 in level-0 PIXEL coordinates (template pixel -> current-frame pixel); NULL = identity
 extern "C" int ictr_icgn_set_warp(ictr_icgn *g, int64_t problem, const double *M9) {
-  if (!g || problem < 0 || problem >= g->B) return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_warp: bad arguments");
+  if (!g || problem < 0 || problem >= g->B) return fail(ICTR_ERR_INVALID, "icgn_set_warp: bad arguments");
   double K[9], Ki[9], t[9], Mn[9];
   const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   if (M9 && g->model != kHomog && (M9[6] != 0.0 || M9[7] != 0.0 || M9[8] == 0.0))
-    return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_warp: a projective initial warp needs the homography model");
+    return fail(ICTR_ERR_INVALID, "icgn_set_warp: a projective initial warp needs the homography model");
   icgn_K(g, K, Ki);
   m3_mul(Ki, M9 ? M9 : I, t);
   m3_mul(t, K, Mn);
@@ -841,37 +825,37 @@ extern "C" int ictr_icgn_set_warp(ictr_icgn *g, int64_t problem, const double *M
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_set_rows(ictr_icgn *g, int row_lo, int row_hi) {
-  if (!g || row_lo < 0 || row_hi < row_lo) return ictr_fail_(ICTR_ERR_INVALID, "icgn_set_rows: bad arguments");
+  if (!g || row_lo < 0 || row_hi < row_lo) return fail(ICTR_ERR_INVALID, "icgn_set_rows: bad arguments");
   g->rows[0] = row_lo;
   g->rows[1] = row_hi;
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_enable_sharding(ictr_icgn *g, int enable, float *red_dev) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   g->sharded = enable ? 1 : 0;
   g->d_red = red_dev ? red_dev : g->d_red_own;
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_set_timing(ictr_icgn *g, int enable) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   if (enable && g->ev.empty()) {
     g->ev.resize((size_t)2 * g->nlev * std::max(1, g->maxiter));
-    for (auto &e : g->ev) HIPCHK_IC(hipEventCreate(&e));
+    for (auto &e : g->ev) HIPCHK(hipEventCreate(&e));
   }
   g->timing = enable != 0;
   return ICTR_OK;
 }
 
 extern "C" int ictr_icgn_begin(ictr_icgn *g) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   for (int b = 0; b < g->B; ++b) {
-    if (!g->frames_set[b]) return ictr_fail_(ICTR_ERR_STATE, "icgn: frames of problem %d not set", b);
+    if (!g->frames_set[b]) return fail(ICTR_ERR_STATE, "icgn: frames of problem %d not set", b);
     IcState &st = g->h_st[b];
     memset(&st, 0, sizeof(st));
     memcpy(st.M, &g->h_M0[9 * b], sizeof(float) * 9);
   }
-  HIPCHK_IC(hipMemcpyAsync(g->d_st, g->h_st.data(), sizeof(IcState) * g->B, hipMemcpyHostToDevice, g->stream));
-  HIPCHK_IC(hipMemcpyAsync(g->d_planes, g->h_planes.data(), sizeof(PlaneSet) * g->h_planes.size(), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(g->d_st, g->h_st.data(), sizeof(IcState) * g->B, hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipMemcpyAsync(g->d_planes, g->h_planes.data(), sizeof(PlaneSet) * g->h_planes.size(), hipMemcpyHostToDevice,
                            g->stream));
   return ICTR_OK;
 }
@@ -896,20 +880,20 @@ template <typename F> static void icgn_dispatch(int model, F &&f) {
 }
 
 extern "C" int ictr_icgn_hess_accumulate(ictr_icgn *g, int level) {
-  if (!g || level < g->lv_l || level > g->lv_f) return ictr_fail_(ICTR_ERR_INVALID, "icgn: bad level");
+  if (!g || level < g->lv_l || level > g->lv_f) return fail(ICTR_ERR_INVALID, "icgn: bad level");
   const IcDev e = icgn_dev(g);
   const IcLevel L = icgn_level(g, level);
   const int nblk = icgn_grid(g, level, false);
   const dim3 grid(nblk, g->B), blk(kBlock);
   icgn_dispatch(g->model, [&](auto m) { hipLaunchKernelGGL((k_icgn_hess<decltype(m)::value>), grid, blk, 0, g->stream, e, L, level); });
   hipLaunchKernelGGL(k_icgn_hess_tail, dim3(g->B), blk, 0, g->stream, e, nblk, 0);
-  HIPCHK_IC(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_hess_finish(ictr_icgn *g, int level) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   if (g->sharded) hipLaunchKernelGGL(k_icgn_hess_tail, dim3(g->B), dim3(kBlock), 0, g->stream, icgn_dev(g), 0, 1);
-  HIPCHK_IC(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 static int icgn_iter_main(ictr_icgn *g, const IcDev &e, const IcLevel &L, int level) {  // returns workgroups per problem
@@ -927,27 +911,27 @@ static int icgn_iter_main(ictr_icgn *g, const IcDev &e, const IcLevel &L, int le
   return nblk;
 }
 extern "C" int ictr_icgn_iter_accumulate(ictr_icgn *g, int level) {
-  if (!g || level < g->lv_l || level > g->lv_f) return ictr_fail_(ICTR_ERR_INVALID, "icgn: bad level");
+  if (!g || level < g->lv_l || level > g->lv_f) return fail(ICTR_ERR_INVALID, "icgn: bad level");
   const IcDev e = icgn_dev(g);
   const IcLevel L = icgn_level(g, level);
   const int nblk = icgn_iter_main(g, e, L, level);
   hipLaunchKernelGGL(k_icgn_iter_tail, dim3(g->B), dim3(kBlock), 0, g->stream, e, L.f, nblk, 0);
-  HIPCHK_IC(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_iter_finish(ictr_icgn *g, int level) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   if (g->sharded) {
     const IcLevel L = icgn_level(g, level);
     hipLaunchKernelGGL(k_icgn_iter_tail, dim3(g->B), dim3(kBlock), 0, g->stream, icgn_dev(g), L.f, 0, 1);
   }
-  HIPCHK_IC(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 
 extern "C" int ictr_icgn_run_async(ictr_icgn *g) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
-  if (g->sharded) return ictr_fail_(ICTR_ERR_STATE, "sharded engines are driven phase by phase");
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
+  if (g->sharded) return fail(ICTR_ERR_STATE, "sharded engines are driven phase by phase");
   if (int rc = ictr_icgn_begin(g)) return rc;
   const IcDev e = icgn_dev(g);
   for (int l = g->lv_f; l >= g->lv_l; --l) {
@@ -955,21 +939,21 @@ extern "C" int ictr_icgn_run_async(ictr_icgn *g) {
     if (int rc = ictr_icgn_hess_accumulate(g, l)) return rc;
     for (int it = 0; it < g->maxiter; ++it) {
       const bool tk = g->timing && !g->ev.empty();
-      if (tk) HIPCHK_IC(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it)], g->stream));
+      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it)], g->stream));
       const int nblk = icgn_iter_main(g, e, L, l);
-      if (tk) HIPCHK_IC(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it) + 1], g->stream));
+      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it) + 1], g->stream));
       hipLaunchKernelGGL(k_icgn_iter_tail, dim3(g->B), dim3(kBlock), 0, g->stream, e, L.f, nblk, 0);
     }
   }
-  HIPCHK_IC(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 
 // results: warps (row-major 3x3, level-0 pixel coordinates), iterations, last dp
 extern "C" int ictr_icgn_get_results(ictr_icgn *g, double *M9_out, int *iters, float *last_dp) {
-  if (!g) return ictr_fail_(ICTR_ERR_INVALID, "icgn is NULL");
-  HIPCHK_IC(hipMemcpyAsync(g->h_st.data(), g->d_st, sizeof(IcState) * g->B, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK_IC(hipStreamSynchronize(g->stream));
+  if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
+  HIPCHK(hipMemcpyAsync(g->h_st.data(), g->d_st, sizeof(IcState) * g->B, hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
   double K[9], Ki[9], t[9], Mp[9], Mn[9];
   icgn_K(g, K, Ki);
   for (int b = 0; b < g->B; ++b) {
@@ -986,15 +970,15 @@ extern "C" int ictr_icgn_get_results(ictr_icgn *g, double *M9_out, int *iters, f
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_get_kernel_times(ictr_icgn *g, float *ms_per_level) {
-  if (!g || !ms_per_level) return ictr_fail_(ICTR_ERR_INVALID, "icgn_get_kernel_times: NULL argument");
-  if (g->ev.empty()) return ictr_fail_(ICTR_ERR_STATE, "timing was never enabled");
-  HIPCHK_IC(hipStreamSynchronize(g->stream));
+  if (!g || !ms_per_level) return fail(ICTR_ERR_INVALID, "icgn_get_kernel_times: NULL argument");
+  if (g->ev.empty()) return fail(ICTR_ERR_STATE, "timing was never enabled");
+  HIPCHK(hipStreamSynchronize(g->stream));
   for (int l = 0; l < g->nlev; ++l) {
     ms_per_level[l] = 0.0f;
     if (l < g->lv_l) continue;
     for (int it = 0; it < g->maxiter; ++it) {
       float ms = 0.0f;
-      HIPCHK_IC(hipEventElapsedTime(&ms, g->ev[2 * ((size_t)l * g->maxiter + it)], g->ev[2 * ((size_t)l * g->maxiter + it) + 1]));
+      HIPCHK(hipEventElapsedTime(&ms, g->ev[2 * ((size_t)l * g->maxiter + it)], g->ev[2 * ((size_t)l * g->maxiter + it) + 1]));
       ms_per_level[l] += ms;
     }
   }

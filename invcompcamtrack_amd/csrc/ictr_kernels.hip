@@ -29,6 +29,7 @@
 #include <hip/hip_ext.h>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "ictr_devfn.h"
 #include "se3_math.h"
 
@@ -1652,17 +1653,19 @@ bool defer_h(const EngineDev &e, int variant) {
   return (fast8(e, variant) && !(variant & ICTR_VARIANT_H_BY_SETUP)) || fast4(e, variant);
 }
 // (the host sets ICTR_VARIANT_ANY_SIZE whenever a robustness option is on, see engine_variant in ictr_host.hip)
+// the wave64 fast paths leave one partial per workgroup of their own grid, the any-size kernels one per gridx workgroup
+int tail_partials(const EngineDev &e, const LevelLaunch &ll) {
+  return (fast8(e, ll.variant) || fast4(e, ll.variant)) ? ll.gridx8 : ll.gridx;
+}
 
 // steps 4-6 of one level for every problem: accumulate kernel + per-problem tail. tail = false (the resident path on the
 // 8x8 fast path): no k_level_tail -- the resident-iteration launch that follows reduces and factors H itself (its solver
 // workgroups are idle while the workers load their templates)
-void launch_ref_level(const EngineDev &e, const LevelCam &lc, int level, int gridx, int variant, int cpw, int gridx8,
-                      bool tail, hipStream_t s) {
+void launch_ref_level(const EngineDev &e, const LevelCam &lc, const LevelLaunch &ll, bool tail, hipStream_t s) {
   const dim3 blk(kBlock);
-  int nblk = gridx;
+  const int level = ll.level, gridx = ll.gridx, variant = ll.variant, cpw = ll.cpw, gridx8 = ll.gridx8;
   const bool dh = defer_h(e, variant);
   if (fast8(e, variant)) {
-    nblk = gridx8;
     const dim3 g8(gridx8, e.B);
     // gradients on the fly from the image plane whenever the reference pyramids are builder-made (r03: 287 -> 242 us per
     // level-0 launch of 32 pairs; a must for image-only pyramids, e.otf == 2); ICTR_VARIANT_GRAD_PLANES: read the
@@ -1681,7 +1684,6 @@ void launch_ref_level(const EngineDev &e, const LevelCam &lc, int level, int gri
     else
       hipLaunchKernelGGL((k_ref8<false, 2, true>), g8, blk, 0, s, e, lc, level, cpw);
   } else if (fast4(e, variant)) {
-    nblk = gridx8;
     if (e.dopatchnorm)
       hipLaunchKernelGGL((k_ref4<true>), dim3(gridx8, e.B), blk, 0, s, e, lc, level, cpw);
     else
@@ -1691,18 +1693,19 @@ void launch_ref_level(const EngineDev &e, const LevelCam &lc, int level, int gri
   else
     hipLaunchKernelGGL(k_ref_level<0>, dim3(gridx, e.B), blk, 0, s, e, lc, level);
   if (tail || !fast8(e, variant))
-    hipLaunchKernelGGL(k_level_tail, dim3(e.B), blk, 0, s, e, nblk, dh ? 1 : 0);
+    hipLaunchKernelGGL(k_level_tail, dim3(e.B), blk, 0, s, e, tail_partials(e, ll), dh ? 1 : 0);
 }
-void launch_level_finish(const EngineDev &e, int variant, hipStream_t s) {
-  hipLaunchKernelGGL(k_level_finish, dim3(e.B), dim3(64), 0, s, e, defer_h(e, variant) ? 1 : 0);
+void launch_level_finish(const EngineDev &e, const LevelLaunch &ll, hipStream_t s) {
+  hipLaunchKernelGGL(k_level_finish, dim3(e.B), dim3(64), 0, s, e, defer_h(e, ll.variant) ? 1 : 0);
 }
 // steps 7-9a of one Gauss-Newton iteration for every problem (the accumulate kernel) ...
 // first: the level's first iteration (P = 4 with deferred H: it also accumulates the H partials)
 // ev0 / ev1 (optional, timing runs): HIP events that take the kernel's own start and end time stamps (hipExtLaunchKernelGGL:
 // the dispatch's completion-signal times, what rocprofv3's kernel trace lists), not the time between two event packets
-void launch_iter_main(const EngineDev &e, const LevelCam &lc, int level, int gridx, int variant, int cpw, int gridx8,
-                      int first, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+void launch_iter_main(const EngineDev &e, const LevelCam &lc, const LevelLaunch &ll, int first, hipStream_t s,
+                      hipEvent_t ev0, hipEvent_t ev1) {
   const dim3 blk(kBlock);
+  const int level = ll.level, gridx = ll.gridx, variant = ll.variant, cpw = ll.cpw, gridx8 = ll.gridx8;
 #define ICTR_LAUNCH(kern, grid, ...)                                                      \
   do {                                                                                    \
     if (ev0 && ev1)                                                                       \
@@ -1735,17 +1738,12 @@ void launch_iter_main(const EngineDev &e, const LevelCam &lc, int level, int gri
 #undef ICTR_LAUNCH
 }
 // ... and steps 9b-10 (one workgroup per problem)
-void launch_iter_tail(const EngineDev &e, int level, int gridx, int variant, int gridx8, int first, hipStream_t s) {
-  const int nblk = (fast8(e, variant) || fast4(e, variant)) ? gridx8 : gridx;
-  hipLaunchKernelGGL(k_iter_tail, dim3(e.B), dim3(kBlock), 0, s, e, level, nblk, (first && defer_h(e, variant)) ? 1 : 0);
+void launch_iter_tail(const EngineDev &e, const LevelLaunch &ll, int first, hipStream_t s) {
+  hipLaunchKernelGGL(k_iter_tail, dim3(e.B), dim3(kBlock), 0, s, e, ll.level, tail_partials(e, ll),
+                     (first && defer_h(e, ll.variant)) ? 1 : 0);
 }
-void launch_iter(const EngineDev &e, const LevelCam &lc, int level, int gridx, int variant, int cpw, int gridx8,
-                 int first, hipStream_t s) {
-  launch_iter_main(e, lc, level, gridx, variant, cpw, gridx8, first, s, nullptr, nullptr);
-  launch_iter_tail(e, level, gridx, variant, gridx8, first, s);
-}
-void launch_iter_finish(const EngineDev &e, int level, int variant, int first, hipStream_t s) {
-  hipLaunchKernelGGL(k_iter_finish, dim3(e.B), dim3(64), 0, s, e, level, (first && defer_h(e, variant)) ? 1 : 0);
+void launch_iter_finish(const EngineDev &e, const LevelLaunch &ll, int first, hipStream_t s) {
+  hipLaunchKernelGGL(k_iter_finish, dim3(e.B), dim3(64), 0, s, e, ll.level, (first && defer_h(e, ll.variant)) ? 1 : 0);
 }
 
 hipError_t launch_debug_wave_solve(const float *H, const float *b, int n, ProbState *st, int through_state, float *x,

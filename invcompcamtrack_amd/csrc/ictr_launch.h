@@ -1,0 +1,155 @@
+// ictr_launch.h -- host-side interface between the translation units of the library: every function that one .hip file
+// defines and another calls, the argument bundles of the launchers, the error helper and the HIP-check macro. Included by
+// every .hip file, the defining one too, so that a definition that drifts from its declaration does not compile or link.
+// Nothing here is seen by a kernel: kernel arguments are the structs of ictr_dev.h, which the launchers fill field by field.
+#pragma once
+
+#include <stddef.h>
+
+#include "ictr_dev.h"
+
+struct ictr_pyramid;
+struct ictr_p2p;
+
+// what ictr_host.hip exposes about a pyramid (ictr_icgn.hip)
+struct ictr_pyramid_view {
+  int nlev, pad;
+  const int *w, *h, *sw;
+  float *const *img, *const *dx, *const *dy;
+  int getgrad;  // 1: the gradient planes exist (image-only pyramids of the tracker's on-the-fly path have none)
+};
+extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v);  // ictr_host.hip
+// the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
+extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
+extern "C" const char *ictr_last_error(void);
+
+namespace ictr {
+
+// ---------------------------------------------------------------- errors, device, environment (ictr_host.hip)
+// records the message for ictr_last_error (per thread) and returns `code`
+int fail(int code, const char *fmt, ...);
+#define HIPCHK(expr)                                                                                  \
+  do {                                                                                                \
+    hipError_t _e = (expr);                                                                           \
+    if (_e != hipSuccess) return fail(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
+  } while (0)
+int need_device();                          // ICTR_OK, or ICTR_ERR_NO_DEVICE with its message: there is no CPU fallback
+int env_int(const char *name, int dflt);    // integer value of an environment variable, dflt when unset
+int cu_count();                             // CUs of the calling thread's current device, queried once per device
+
+// ---------------------------------------------------------------- argument bundles of the launchers (host side only)
+// launch geometry of one pyramid level's kernels
+struct LevelLaunch {
+  int level;
+  int variant;  // selection bits as the launchers see them (ICTR_VARIANT_*)
+  int gridx;    // workgroups per problem of the any-size kernels
+  int cpw;      // wave64 fast paths (8x8, 4x4): points per wave chunk ...
+  int gridx8;   // ... and workgroups per problem
+};
+// workgroups of a resident-iteration launch (ictr_resident.hip)
+struct ResidentGeom {
+  int parts, slots, np;  // worker workgroups per frame pair, pairs in flight, patches per wave (16 or 32)
+};
+// one in-launch exchange (team form of k_track1, k_level_resident): the mailbox and what bounds the polling
+struct Exchange {
+  unsigned tag0;             // launch epoch << 12; the kernels add the exchange number
+  unsigned long long limit;  // polling limit, wall_clock64 ticks (100 MHz)
+  unsigned long long *mail;  // granules {float bits, tag}; tag 0 = "nothing yet"
+  int *err;                  // sticky time-out flag (pinned host memory as the device sees it)
+  int mute;                  // debug (ICTR_VARIANT_DEBUG_MUTE), 0 = off: part (k_track1) / worker (k_level_resident)
+                             // `mute - 1` of every problem never posts its values (time-out tests)
+};
+// team form of the one-launch tracker (ictr_track1.hip, "Teams"): several workgroups per problem
+struct T1Team {
+  int team, q;  // workgroups per problem, points per workgroup
+  Exchange x;   // mailbox [B][2][team][32] granules
+};
+
+// ---------------------------------------------------------------- ictr_kernels.hip
+// plain streaming read of nfloats floats (ictr_stream_read_bandwidth); sink: 8192 * kBlock floats, never written
+void launch_stream_read(const float *src, size_t nfloats, float *sink, hipStream_t s);
+// interleave a finished level into {img, dx, dy, 0} texels (read by k_ref8's packed taps)
+void launch_pyr_pack(const float *img, const float *dx, const float *dy, float *pack, size_t n, hipStream_t s);
+// one pyramid level. src: the input frame (first, unpadded, stride w) or the previous level's padded image plane
+// (pw x ph, stride psw)
+void launch_pyr_level(const float *src, int first, int pw, int ph, int psw, float *img, float *dx, float *dy, float *pack,
+                      int w, int h, int pad, int sw, int sh, int getgrad, hipStream_t s);
+// K patches of P x P (and their gradient patches) around mids[2K]
+void launch_getpatch(const float *img, const float *dx, const float *dy, const float *mids, int K, int P, int sw,
+                     int dopatchnorm, float *out, float *out_dx, float *out_dy, hipStream_t s);
+// weighted NCC of the patches of frame r against frames b (back) and f (forward) at mids[2K]
+void launch_ncc(const float *img_b, const float *img_r, const float *img_f, const float *mids, int K, int P, int sw,
+                float swo, float sho, float w_back, float w_fwd, float *out, hipStream_t s);
+// func_get_transf_position: K points moved by a displacement field (H x W, f32 or f64) sampled bilinearly, in f64
+void launch_flow_gather(const void *du, const void *dv, int is_f64, int H, int W, const double *xy, int K, double *out,
+                        hipStream_t s);
+// func_extract_bil_patch, batched: K raw (2 half x 2 half x C) bilinear patches of an (H, W, C) f64 image
+void launch_bil_patches(const double *img, int H, int W, int C, const double *pts, int K, int half, double *out,
+                        hipStream_t s);
+// n points of a cloud of capacity M through the pose G[12] and the level camera; pt3d_rot (may be NULL): the rotated points
+void launch_project_generic(const float *pt3d, float *pt3d_rot, float *pt2d, int n, int M, const float *G, LevelCam lc,
+                            hipStream_t s);
+// step 3 for every problem and level (and clears the trace counter); cams[e.nlev]
+void launch_project_ref(const EngineDev &e, const LevelCam *cams, int maxpts, hipStream_t s);
+// deferred H: the level's H partials are reduced and factored by the level's first iteration tail, not by the level tail
+bool defer_h(const EngineDev &e, int variant);
+// partials per problem that the tail behind an accumulate launch of this geometry adds
+int tail_partials(const EngineDev &e, const LevelLaunch &ll);
+// steps 4-6 of one level for every problem: accumulate kernel + per-problem tail. tail = false (the resident form on the
+// 8x8 fast path): no tail, the resident-iteration launch that follows reduces and factors H itself
+void launch_ref_level(const EngineDev &e, const LevelCam &lc, const LevelLaunch &ll, bool tail, hipStream_t s);
+// sharded phase API: the level's solve on the summed record
+void launch_level_finish(const EngineDev &e, const LevelLaunch &ll, hipStream_t s);
+// steps 7-9a of one Gauss-Newton iteration for every problem (the accumulate kernel). first: the level's first iteration;
+// ev0 / ev1 (optional, timing runs): HIP events that take the kernel's own start and end time stamps
+void launch_iter_main(const EngineDev &e, const LevelCam &lc, const LevelLaunch &ll, int first, hipStream_t s,
+                      hipEvent_t ev0, hipEvent_t ev1);
+// ... and steps 9b-10 (one workgroup per problem)
+void launch_iter_tail(const EngineDev &e, const LevelLaunch &ll, int first, hipStream_t s);
+// sharded phase API: the iteration's solve and update on the summed record
+void launch_iter_finish(const EngineDev &e, const LevelLaunch &ll, int first, hipStream_t s);
+// inspection: WaveSolver on n systems, one wave each; through_state: factors stored in st by one launch, reloaded by a second
+hipError_t launch_debug_wave_solve(const float *H, const float *b, int n, ProbState *st, int through_state, float *x,
+                                   int *rank, int *nonzero, int *rowmap, int *colmap, float *lu, hipStream_t s);
+// inspection: the device builds of se3_exp<float> / se3_log<float> on n inputs
+hipError_t launch_debug_se3(const float *in, float *out, long long n, int log_not_exp, hipStream_t s);
+
+// ---------------------------------------------------------------- ictr_track1.hip
+// dynamic LDS bytes of a k_track1 workgroup; *tmpl_lds: 0 when the templates do not fit and stay in device memory
+size_t track1_plan(int npts_cap, int n, int p8, int waves, int *tmpl_lds);
+// bytes of initial state + plane table a launch can carry in its arguments (fused begin)
+size_t track1_blob_bytes(void);
+// points per workgroup of the team form for a problem of maxpts points, and with it the team size: functions of the
+// point count alone
+int track1_team_q(int maxpts, int target);
+int track1_team_size(int maxpts, int target);
+size_t track1_team_mail_bytes(int B, int team);
+// ONE launch for the whole tracking of every problem. blob (may be NULL): [ProbState x B][PlaneSet x B x nlev] for the
+// fused begin; host_st (may be NULL): pinned mirror of the final records; project_here (without a blob): the records and
+// the plane table have been uploaded, the launch projects (step 3) itself; tm (may be NULL): team form
+hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, int waves, const void *blob,
+                         ProbState *host_st, hipStream_t s, const T1Team *tm, bool project_here = false);
+
+// ---------------------------------------------------------------- ictr_resident.hip
+size_t resident_mail_bytes(int parts, int slots);
+int resident_points_per_workgroup(int np);
+int resident_blocks_per_cu(int np);  // workgroups of the kernel that one CU holds at once (0: the kernel cannot run)
+// all iterations of one level in ONE launch, (g.parts + 1) * g.slots workgroups that must all be resident. nblk: H partials
+// per problem left by the level's setup launch (tail_partials); xchg (may be NULL): sums over the ranks inside the launch
+hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int level, const ResidentGeom &g, int nblk,
+                                 const Exchange &x, const ResXchg *xchg, hipStream_t s);
+// inspection: the transposing wave reduction alone, np = 16 or 32 patches per wave
+hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *patch_of_lane, int *kind_of_lane, int np,
+                                         hipStream_t s);
+
+// ---------------------------------------------------------------- ictr_sequence.hip, ictr_ransac.hip, ictr_patchflow.hip
+// the between-pairs step (three launches), or with a.tail the last frame's bookkeeping (one)
+void launch_seq_select(const SeqArgs &a, hipStream_t s);
+// one chunk of a.k trials: hypotheses, scoring (tile = 16 / 32 / 64 hypotheses per workgroup), ordered selection
+void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s);
+// after the last chunk: inl_cnt and the post-filter
+void launch_ransac_finish(const RansacArgs &a, hipStream_t s);
+// per-patch translation IC-LK, all levels, a.K points
+void launch_patchflow(const PFArgs &a, hipStream_t s);
+
+}  // namespace ictr

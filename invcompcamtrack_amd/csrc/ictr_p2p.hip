@@ -23,8 +23,7 @@
 #include <string>
 
 #include "ictr_dev.h"
-
-extern int ictr_fail_(int code, const char *fmt, ...);
+#include "ictr_launch.h"
 
 namespace ictr {
 
@@ -83,18 +82,10 @@ struct ictr_p2p {
   double timeout_s = 2.0;
 };
 
-#define P2PCHK(expr)                                                                                       \
-  do {                                                                                                     \
-    hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess) return ictr_fail_(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
 extern "C" int ictr_p2p_create(ictr_p2p **out, int rank, int world, int64_t count) {
   if (!out || world < 1 || world > kP2PMaxWorld || rank < 0 || rank >= world || count < 1 || count > (1 << 24))
-    return ictr_fail_(ICTR_ERR_INVALID, "p2p_create: bad arguments (world 1..%d)", kP2PMaxWorld);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return ictr_fail_(ICTR_ERR_NO_DEVICE, "no usable HIP device: the tracker has no CPU fallback");
+    return fail(ICTR_ERR_INVALID, "p2p_create: bad arguments (world 1..%d)", kP2PMaxWorld);
+  if (int rc = need_device()) return rc;
   ictr_p2p *p = new ictr_p2p;
   p->rank = rank;
   p->world = world;
@@ -111,7 +102,7 @@ extern "C" int ictr_p2p_create(ictr_p2p **out, int rank, int world, int64_t coun
     if (p->mail) (void)hipFree(p->mail);
     if (p->d_err) (void)hipFree(p->d_err);
     delete p;
-    return ictr_fail_(ICTR_ERR_HIP, "p2p_create: mailbox allocation failed: %s", hipGetErrorString(e));
+    return fail(ICTR_ERR_HIP, "p2p_create: mailbox allocation failed: %s", hipGetErrorString(e));
   }
   if (const char *t = getenv("ICTR_P2P_TIMEOUT_S")) p->timeout_s = std::max(0.01, atof(t));
   p->peer[rank] = p->mail;
@@ -123,22 +114,22 @@ extern "C" int ictr_p2p_handle_bytes(void) { return (int)sizeof(hipIpcMemHandle_
 
 // the handle other processes open to reach this rank's mailbox (hipIpcMemHandle_t, ictr_p2p_handle_bytes() bytes)
 extern "C" int ictr_p2p_local_handle(ictr_p2p *p, void *handle_out) {
-  if (!p || !handle_out) return ictr_fail_(ICTR_ERR_INVALID, "p2p_local_handle: NULL argument");
+  if (!p || !handle_out) return fail(ICTR_ERR_INVALID, "p2p_local_handle: NULL argument");
   hipIpcMemHandle_t h;
-  P2PCHK(hipIpcGetMemHandle(&h, p->mail));
+  HIPCHK(hipIpcGetMemHandle(&h, p->mail));
   memcpy(handle_out, &h, sizeof(h));
   return ICTR_OK;
 }
 
 // all_handles: world handles in rank order (this rank's own entry is ignored)
 extern "C" int ictr_p2p_connect(ictr_p2p *p, const void *all_handles) {
-  if (!p || !all_handles) return ictr_fail_(ICTR_ERR_INVALID, "p2p_connect: NULL argument");
+  if (!p || !all_handles) return fail(ICTR_ERR_INVALID, "p2p_connect: NULL argument");
   for (int r = 0; r < p->world; ++r) {
     if (r == p->rank || p->opened[r]) continue;
     hipIpcMemHandle_t h;
     memcpy(&h, (const char *)all_handles + (size_t)r * sizeof(h), sizeof(h));
     void *ptr = nullptr;
-    P2PCHK(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
+    HIPCHK(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
     p->peer[r] = (uint64_t *)ptr;
     p->opened[r] = true;
   }
@@ -149,8 +140,8 @@ extern "C" int ictr_p2p_connect(ictr_p2p *p, const void *all_handles) {
 // in-place sum of dev_buf[0..count) over all ranks, enqueued on `hip_stream`; every rank must call it the same
 // number of times with the same count
 extern "C" int ictr_p2p_allreduce(ictr_p2p *p, float *dev_buf, int64_t count, void *hip_stream) {
-  if (!p || !dev_buf || count < 1 || count > p->cap) return ictr_fail_(ICTR_ERR_INVALID, "p2p_allreduce: bad arguments");
-  if (!p->connected && p->world > 1) return ictr_fail_(ICTR_ERR_STATE, "p2p_allreduce before p2p_connect");
+  if (!p || !dev_buf || count < 1 || count > p->cap) return fail(ICTR_ERR_INVALID, "p2p_allreduce: bad arguments");
+  if (!p->connected && p->world > 1) return fail(ICTR_ERR_STATE, "p2p_allreduce before p2p_connect");
   P2PArgs a;
   memset(&a, 0, sizeof(a));
   for (int r = 0; r < p->world; ++r) a.peer[r] = p->peer[r];
@@ -163,7 +154,7 @@ extern "C" int ictr_p2p_allreduce(ictr_p2p *p, float *dev_buf, int64_t count, vo
   p->seq += 1;
   if (p->seq == 0) p->seq = 1;  // tag 0 is reserved for "empty"
   hipLaunchKernelGGL(k_p2p_allreduce, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, a, dev_buf, (int)count, p->seq);
-  P2PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
 

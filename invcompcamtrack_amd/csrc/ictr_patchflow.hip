@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "ictr_devfn.h"
 
 namespace ictr {

@@ -16,7 +16,15 @@
 //                    inl_cnt without its entries <= 4), both order-preserving.
 //
 // Every result is decided by integers and fixed-order f64 arithmetic: the same bits on every run and for every K.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+
 #include "ictr_dev.h"
+#include "ictr_launch.h"
+#include "se3_math.h"
 
 namespace ictr {
 
@@ -529,3 +537,248 @@ void launch_ransac_finish(const RansacArgs &a, hipStream_t s) {
 }
 
 }  // namespace ictr
+
+using namespace ictr;
+
+// ---------------------------------------------------------------- host side (func_ransac_fitcameras_odom.m:17-87)
+// The trials run in chunks of K on one stream (ictr_ransac.hip): hypotheses, scoring, ordered selection per chunk, then
+// the post-filter once. Chunks are enqueued in groups; between two groups the run reads the 4-byte `done` flag, so a
+// run whose samples are found early does not enqueue the rest. One read-back at the end.
+static constexpr int kRanGroup = 64;  // chunks enqueued between two reads of `done`
+
+struct ictr_ransac {
+  int n = 0, nwords = 0;
+  int64_t smax = 0;
+  int chunk = 0, tile = 32;
+  hipStream_t stream = nullptr;
+  double *d_pts = nullptr;
+  double *d_hyp = nullptr;
+  int *d_draws = nullptr, *d_status = nullptr;
+  unsigned *d_cnt = nullptr;
+  unsigned long long *d_words = nullptr;
+  char *d_out = nullptr, *h_out = nullptr;  // RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] |
+                                            // t [smax][3] | words [smax][nwords] | cnt [n] | keep [smax] | cntf [n]
+  size_t out_bytes = 0;
+  bool points_set = false, pending = false, ran = false;
+  hipEvent_t done = nullptr;
+};
+
+struct RanLayout {
+  size_t trial, draws, R, t, words, cnt, keep, cntf, end;
+};
+static RanLayout ran_layout(const ictr_ransac *r) {
+  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
+  RanLayout L;
+  const size_t S = (size_t)r->smax;
+  L.trial = up(sizeof(RansacState));
+  L.draws = up(L.trial + 8 * S);
+  L.R = up(L.draws + 16 * S);
+  L.t = up(L.R + 72 * S);
+  L.words = up(L.t + 24 * S);
+  L.cnt = up(L.words + 8 * S * r->nwords);
+  L.keep = up(L.cnt + 4 * (size_t)r->n);
+  L.cntf = up(L.keep + 4 * S);
+  L.end = up(L.cntf + 4 * (size_t)r->n);
+  return L;
+}
+
+// trials per chunk: enough that one chunk's scoring (K x N lane tests) fills the device; ICTR_RANSAC_CHUNK overrides.
+// Constants from tools/ransac_bench.py --sweep (profiles/ransac_sweep.json).
+static int ransac_chunk(int n) {
+  const int env = env_int("ICTR_RANSAC_CHUNK", 0);
+  if (env > 0) return env;
+  long long k = (1ll << 23) / n;
+  k = std::max(256ll, std::min(16384ll, k));
+  return (int)((k + 255) / 256 * 256);
+}
+
+static void ran_free(ictr_ransac *r) {
+  if (!r) return;
+  if (r->pending) (void)hipEventSynchronize(r->done);
+  if (r->done) (void)hipEventDestroy(r->done);
+  if (r->h_out) (void)hipHostFree(r->h_out);
+  for (void *p : {(void *)r->d_pts, (void *)r->d_hyp, (void *)r->d_draws, (void *)r->d_status, (void *)r->d_cnt,
+                  (void *)r->d_words, (void *)r->d_out})
+    if (p) (void)hipFree(p);
+  delete r;
+}
+
+static int ran_refuse_pending(const ictr_ransac *r, const char *what) {
+  if (r->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_ransac_wait first", what);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samples) {
+  if (!out) return fail(ICTR_ERR_INVALID, "ransac_create: NULL argument");
+  if (n < 4 || n > ((int64_t)1 << 24))
+    return fail(ICTR_ERR_INVALID, "ransac_create: %lld matches (4 .. 2^24)", (long long)n);
+  if (max_samples < 1 || max_samples > ((int64_t)1 << 24))
+    return fail(ICTR_ERR_INVALID, "ransac_create: max_samples %lld (1 .. 2^24)", (long long)max_samples);
+  if (int rc = need_device()) return rc;
+  ictr_ransac *r = new ictr_ransac;
+  r->n = (int)n;
+  r->nwords = (int)((n + 63) / 64);
+  r->smax = max_samples;
+  r->chunk = ransac_chunk(r->n);
+  const int tile = env_int("ICTR_RANSAC_TILE", 32);
+  r->tile = (tile == 16 || tile == 64) ? tile : 32;
+  const size_t K = (size_t)r->chunk;
+  r->out_bytes = ran_layout(r).end;
+  hipError_t e = hipSuccess;
+  auto alloc = [&](void **p, size_t bytes) {
+    if (e == hipSuccess) e = hipMalloc(p, bytes);
+    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+  };
+  alloc((void **)&r->d_pts, sizeof(double) * 5 * n);
+  alloc((void **)&r->d_hyp, sizeof(double) * 12 * K);
+  alloc((void **)&r->d_draws, sizeof(int) * 4 * K);
+  alloc((void **)&r->d_status, sizeof(int) * K);
+  alloc((void **)&r->d_cnt, sizeof(unsigned) * K);
+  alloc((void **)&r->d_words, sizeof(unsigned long long) * K * r->nwords);
+  alloc((void **)&r->d_out, r->out_bytes);
+  if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_out, r->out_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    ran_free(r);
+    return fail(ICTR_ERR_HIP, "ransac_create: device allocation failed: %s", hipGetErrorString(e));
+  }
+  *out = r;
+  return ICTR_OK;
+}
+
+extern "C" void ictr_ransac_destroy(ictr_ransac *r) { ran_free(r); }
+
+extern "C" int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const double *pt3d) {
+  if (!r || !pt2d || !pt3d) return fail(ICTR_ERR_INVALID, "ransac_set_points: NULL argument");
+  if (int rc = ran_refuse_pending(r, "ransac_set_points")) return rc;
+  const size_t n = (size_t)r->n;
+  HIPCHK(hipMemcpy(r->d_pts, pt2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(r->d_pts + 2 * n, pt3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  r->points_set = true;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ransac_chunk_size(const ictr_ransac *r) { return r ? r->chunk : 0; }
+
+extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples,
+                               int64_t maxtrials, double inlthresh, uint64_t seed, void *hip_stream) {
+  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ransac_run: NULL argument");
+  if (int rc = ran_refuse_pending(r, "ransac_run")) return rc;
+  if (!r->points_set) return fail(ICTR_ERR_STATE, "ransac_run: ictr_ransac_set_points has not been called");
+  if (nsamples < 1 || nsamples > r->smax)
+    return fail(ICTR_ERR_INVALID, "ransac_run: nsamples %lld (1 .. %lld, the size given at creation)",
+                (long long)nsamples, (long long)r->smax);
+  if (maxtrials < 1 || maxtrials > ((int64_t)1 << 40))
+    return fail(ICTR_ERR_INVALID, "ransac_run: maxtrials %lld (1 .. 2^40)", (long long)maxtrials);
+  if (!std::isfinite(inlthresh)) return fail(ICTR_ERR_INVALID, "ransac_run: inlthresh is not finite");
+  if (!std::isfinite(kc) || !std::isfinite(fc[0]) || !std::isfinite(fc[1]) || fc[0] == 0.0 || fc[1] == 0.0 ||
+      !std::isfinite(cc[0]) || !std::isfinite(cc[1]))
+    return fail(ICTR_ERR_INVALID, "ransac_run: the camera (fc, cc, kc) must be finite, fc non-zero");
+  r->stream = (hipStream_t)hip_stream;
+  const RanLayout L = ran_layout(r);
+  RansacArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pts = r->d_pts;
+  a.n = r->n;
+  a.nwords = r->nwords;
+  a.fx = fc[0];
+  a.fy = fc[1];
+  a.cx = cc[0];
+  a.cy = cc[1];
+  a.kc = kc;
+  a.thr = inlthresh;
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull;  // splitmix64 (the device's ran_mix)
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  a.seedmix = z ^ (z >> 31);
+  a.nsamples = nsamples;
+  a.maxtrials = maxtrials;
+  a.hyp = r->d_hyp;
+  a.draws = r->d_draws;
+  a.status = r->d_status;
+  a.cnt = r->d_cnt;
+  a.words = r->d_words;
+  a.st = reinterpret_cast<RansacState *>(r->d_out);
+  a.o_trial = reinterpret_cast<long long *>(r->d_out + L.trial);
+  a.o_draws = reinterpret_cast<int *>(r->d_out + L.draws);
+  a.o_R = reinterpret_cast<double *>(r->d_out + L.R);
+  a.o_t = reinterpret_cast<double *>(r->d_out + L.t);
+  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out + L.words);
+  a.o_cnt = reinterpret_cast<int *>(r->d_out + L.cnt);
+  a.o_keep = reinterpret_cast<int *>(r->d_out + L.keep);
+  a.o_cntf = reinterpret_cast<int *>(r->d_out + L.cntf);
+  HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), r->stream));
+  const int64_t K = r->chunk;
+  const int64_t nchunks = (maxtrials + K - 1) / K;
+  for (int64_t c = 0; c < nchunks; ++c) {
+    if (c > 0 && c % kRanGroup == 0) {  // a long run: stop enqueueing once the samples are found
+      RansacState *hs = reinterpret_cast<RansacState *>(r->h_out);
+      HIPCHK(hipMemcpyAsync(&hs->done, &a.st->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
+      HIPCHK(hipStreamSynchronize(r->stream));
+      if (*(volatile int *)&hs->done) break;
+    }
+    a.base = c * K;
+    a.k = (int)std::min<int64_t>(K, maxtrials - a.base);
+    launch_ransac_chunk(a, r->tile, r->stream);
+    HIPCHK(hipGetLastError());
+  }
+  launch_ransac_finish(a, r->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out, r->out_bytes, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipEventRecord(r->done, r->stream));
+  r->pending = true;
+  r->ran = true;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, double *t, double *p, uint64_t *inl_words,
+                                int32_t *inl_cnt) {
+  if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
+  if (!r->pending) return fail(ICTR_ERR_STATE, "ransac_wait: nothing has been run");
+  HIPCHK(hipEventSynchronize(r->done));
+  r->pending = false;
+  const RanLayout L = ran_layout(r);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
+  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
+  const double *hR = reinterpret_cast<const double *>(r->h_out + L.R);
+  const double *ht = reinterpret_cast<const double *>(r->h_out + L.t);
+  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->h_out + L.words);
+  if (counts) {
+    counts[0] = st.kept;
+    counts[1] = st.held;
+    counts[2] = st.trials_used;
+    counts[3] = st.n_ic;
+  }
+  for (long long q = 0; q < st.kept; ++q) {
+    const size_t s = (size_t)keep[q];
+    if (R) memcpy(R + 9 * q, hR + 9 * s, 9 * sizeof(double));
+    if (t) memcpy(t + 3 * q, ht + 3 * s, 3 * sizeof(double));
+    if (p) {  // p = se3_log([R | -R t]) (ictr_ransac.hip: on the host, at the read-back)
+      const double *Rs = hR + 9 * s, *ts = ht + 3 * s;
+      double G[12];
+      for (int i = 0; i < 3; ++i) {
+        for (int c = 0; c < 3; ++c) G[i * 4 + c] = Rs[i * 3 + c];
+        G[i * 4 + 3] = -Rs[i * 3 + 0] * ts[0] - Rs[i * 3 + 1] * ts[1] - Rs[i * 3 + 2] * ts[2];
+      }
+      se3_log<double>(p + 6 * q, G);
+    }
+    if (inl_words) memcpy(inl_words + (size_t)r->nwords * q, hw + (size_t)r->nwords * s, 8 * (size_t)r->nwords);
+  }
+  if (inl_cnt) memcpy(inl_cnt, r->h_out + L.cntf, sizeof(int32_t) * (size_t)st.n_ic);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws) {
+  if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
+  if (r->pending || !r->ran) return fail(ICTR_ERR_STATE, "ransac_samples: no completed run");
+  const RanLayout L = ran_layout(r);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
+  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
+  const long long *ht = reinterpret_cast<const long long *>(r->h_out + L.trial);
+  const int *hd = reinterpret_cast<const int *>(r->h_out + L.draws);
+  for (long long q = 0; q < st.kept; ++q) {
+    if (trial) trial[q] = ht[keep[q]];
+    if (draws) memcpy(draws + 4 * q, hd + 4 * (size_t)keep[q], 4 * sizeof(int32_t));
+  }
+  return ICTR_OK;
+}

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "ictr_devfn.h"
 #include "se3_math.h"
 
@@ -655,9 +656,8 @@ int resident_blocks_per_cu(int np) {
   static const int n[2] = {res_occupancy<16>(), res_occupancy<32>()};
   return n[np == 32 ? 1 : 0];
 }
-hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int level, int np, int parts, int slots, int nblk,
-                                 unsigned tag0, unsigned long long limit, unsigned long long *mail, int *err, int dbg_mute,
-                                 const ResXchg *xchg, hipStream_t s) {
+hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int level, const ResidentGeom &g, int nblk,
+                                 const Exchange &x, const ResXchg *xchg, hipStream_t s) {
   ResArgs a;
   if (xchg)
     a.x = *xchg;
@@ -670,15 +670,15 @@ hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int lev
   a.nblk = nblk;
   a.lc = lc;
   a.level = level;
-  a.parts = parts;
-  a.slots = slots;
-  a.dbg_mute = dbg_mute;
-  a.tag0 = tag0;
-  a.limit = limit;
-  a.mail = mail;
-  a.err = err;
-  const dim3 grid((parts + 1) * slots), blk(kResThreads);
-  if (np == 32)
+  a.parts = g.parts;
+  a.slots = g.slots;
+  a.dbg_mute = x.mute;
+  a.tag0 = x.tag0;
+  a.limit = x.limit;
+  a.mail = x.mail;
+  a.err = x.err;
+  const dim3 grid((g.parts + 1) * g.slots), blk(kResThreads);
+  if (g.np == 32)
     hipLaunchKernelGGL((k_level_resident<32>), grid, blk, 0, s, e, a);
   else
     hipLaunchKernelGGL((k_level_resident<16>), grid, blk, 0, s, e, a);

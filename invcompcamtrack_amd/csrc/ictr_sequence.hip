@@ -22,6 +22,7 @@
 //
 // Every value is decided by integer counts and fixed-order sums: no float atomics, the same bits on every run.
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "ictr_pose_hd.h"
 #include "se3_math.h"
 

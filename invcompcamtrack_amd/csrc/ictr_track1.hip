@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "ictr_dev.h"
+#include "ictr_launch.h"
 #include "ictr_devfn.h"
 #include "se3_math.h"
 
@@ -1013,7 +1014,6 @@ static hipError_t launch_t1(K kernel, size_t *granted, const EngineDev &e, const
 
 // bytes of initial state + plane table a launch can carry in its arguments (fused begin, see T1Args)
 size_t track1_blob_bytes(void) { return sizeof(unsigned) * kT1BlobWords; }
-int cu_count();  // (ictr_host.hip) CUs of the current device
 
 // Points per workgroup of the team form for a problem of `maxpts` points, and with it the team size -- a function of
 // the point count alone, so a problem's sums (and bits) do not depend on what else shares its launch.
@@ -1038,13 +1038,13 @@ hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, i
   const int team = (tm && p8 && tm->team > 1) ? tm->team : 1;
   a.team = team;
   a.team_q = team > 1 ? tm->q : 0x7fffffff;
-  a.team_tag0 = team > 1 ? tm->tag0 : 0;
-  a.team_limit = team > 1 ? tm->limit : 0;
-  a.team_mail = team > 1 ? tm->mail : nullptr;
-  a.team_err = team > 1 ? tm->err : nullptr;
-  a.team_mute = team > 1 ? tm->mute : 0;
+  a.team_tag0 = team > 1 ? tm->x.tag0 : 0;
+  a.team_limit = team > 1 ? tm->x.limit : 0;
+  a.team_mail = team > 1 ? tm->x.mail : nullptr;
+  a.team_err = team > 1 ? tm->x.err : nullptr;
+  a.team_mute = team > 1 ? tm->x.mute : 0;
   if (team > 1) {
-    if (team > kTeamMax || !tm->mail || !tm->err || (long long)tm->q * team < maxpts) return hipErrorInvalidValue;
+    if (team > kTeamMax || !tm->x.mail || !tm->x.err || (long long)tm->q * team < maxpts) return hipErrorInvalidValue;
     maxpts = std::min(maxpts, tm->q);  // LDS records and patches: this workgroup's share only
   }
   a.npts_cap = (std::max(maxpts, 1) + 3) & ~3;  // keeps the LDS template arrays 16-byte aligned
