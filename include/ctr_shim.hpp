@@ -200,4 +200,33 @@ class RansacClass {
   int64_t n_, smax_;
 };
 
+// Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one
+// read-back at the end. Mode: ICTR_TRIANG_DLT / _GN / _LM / _DEPTH.
+class TriangClass {
+ public:
+  TriangClass(int64_t max_points, int64_t max_obs, int64_t max_frames) : h_(nullptr) {
+    check(ictr_triang_create(&h_, max_points, max_obs, max_frames), "TriangClass");
+  }
+  ~TriangClass() { ictr_triang_destroy(h_); }
+  TriangClass(const TriangClass &) = delete;
+  TriangClass &operator=(const TriangClass &) = delete;
+  void SetCameras(const float *P /* [F][12] */, int64_t nframes) {
+    check(ictr_triang_set_cameras(h_, P, nframes), "SetCameras");
+  }
+  void SetTracks(int64_t n, const int64_t *offsets /* [n + 1] */, const int32_t *view, const float *x, const float *y) {
+    check(ictr_triang_set_tracks(h_, n, offsets, view, x, y), "SetTracks");
+  }
+  void Run(int mode, const ictr_triang_params *params = nullptr, const float *init_pts = nullptr,
+           const float *campos = nullptr, const float *ptdir = nullptr, void *hip_stream = nullptr) {
+    check(ictr_triang_run(h_, mode, params, init_pts, campos, ptdir, hip_stream), "Run");
+  }
+  // buffers sized for the tracks set: pts [n][3], cov [n][9], iters [n], status [n]; any may be NULL
+  void Wait(float *pts, float *cov, int32_t *iters = nullptr, int32_t *status = nullptr) {
+    check(ictr_triang_wait(h_, pts, cov, iters, status), "Wait");
+  }
+
+ private:
+  ictr_triang *h_;
+};
+
 }  // namespace CTR

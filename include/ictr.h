@@ -487,6 +487,58 @@ int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws);
 /* trials per chunk of this object (ICTR_RANSAC_CHUNK overrides the choice made from N) */
 int ictr_ransac_chunk_size(const ictr_ransac *r);
 
+/* ------------------------------------------------------------------ multi-view point triangulation (misc_src/triang.c)
+ * A track set (10^4 .. 10^5 points, 2 .. 30 views each) triangulated in one launch, one lane per point, with the
+ * arithmetic of the reference routine of each mode: every product and sum in f32, in its order and grouping, so the
+ * results carry the bits of the reference binary built without contraction (DESIGN.md §4 "Triangulation").
+ *   DLT    triangulate_DLT: normal equations of the rows x P2 - P0, y P2 - P1; cov = inverse of A^T A
+ *   GN     triangulate_full3D: Gauss-Newton on the reprojection error; cov = (J^T J)^-1 of the last iteration
+ *   LM     triangulate_full3D_LM: Levenberg-Marquardt, diagonal damping; cov = the last damped inverse
+ *   DEPTH  triangulate_depthonly: Gauss-Newton on the depth along a ray from a centre; cov[0] = 1 / sum j^2
+ * The reference prints a line per iteration; here the count comes back per point. */
+#define ICTR_TRIANG_DLT 0
+#define ICTR_TRIANG_GN 1
+#define ICTR_TRIANG_LM 2
+#define ICTR_TRIANG_DEPTH 3
+/* status word of a point (it changes no value) */
+#define ICTR_TRIANG_NONFINITE 1 /* bit 0: a non-finite word in the point or its covariance */
+#define ICTR_TRIANG_BEHIND 2    /* bit 1: not in front of its first view's camera (P2 . X <= 0) */
+typedef struct ictr_triang_params {
+  int32_t noiter;                      /* iterations at most (0: the start point comes back, covariance 0) */
+  float minres;                        /* stop once the mean squared residual is <= minres */
+  float damp_init, damp_fct, maxdamp;  /* LM: first damping, its factor, stop once damp >= maxdamp */
+} ictr_triang_params;
+typedef struct ictr_triang ictr_triang;
+/* caps: max_points 1 .. 2^24, max_obs 2 * max_points .. 2^28 (observations of all tracks), max_frames 1 .. 2^20 */
+int ictr_triang_create(ictr_triang **out, int64_t max_points, int64_t max_obs, int64_t max_frames);
+void ictr_triang_destroy(ictr_triang *t);
+/* P [nframes][12]: row-major 3x4 camera matrices, f32. The setters are refused (ICTR_ERR_STATE) while a run is in flight. */
+int ictr_triang_set_cameras(ictr_triang *t, const float *P, int64_t nframes);
+/* the ragged track list: point i owns observations offsets[i] .. offsets[i+1]-1 (offsets[0] = 0, n + 1 entries) of
+ * view[] (frame index), x[], y[] (pixels). ICTR_ERR_INVALID for a track of fewer than 2 views or a view >= nframes.
+ * Repacks the list for the kernel on the device and waits for that (the null stream). */
+int ictr_triang_set_tracks(ictr_triang *t, int64_t n, const int64_t *offsets, const int32_t *view, const float *x,
+                           const float *y);
+/* enqueues upload, kernel and read-back on hip_stream (NULL: the null stream) and returns. params: NULL allowed for DLT.
+ * init_pts [n][3]: the start points of GN / LM / DEPTH (required there); campos, ptdir [n][3]: centre and unit ray of
+ * DEPTH (required there). The arrays are copied before the call returns. */
+int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_params *params, const float *init_pts,
+                    const float *campos, const float *ptdir, void *hip_stream);
+/* waits for the last run; any pointer may be NULL. pts [n][3], cov [n][9] (row-major 3x3; DEPTH: the scalar in word 0,
+ * zeros beyond), iters [n], status [n] (ICTR_TRIANG_NONFINITE | ICTR_TRIANG_BEHIND) */
+int ictr_triang_wait(ictr_triang *t, float *pts, float *cov, int32_t *iters, int32_t *status);
+/* The reference library's four entry points with its parameter lists and layouts (P [12][noviews], pt2d [2][noviews],
+ * pt3d in place, cov 9 floats or, for the depth, 1): the same kernels on a batch of one point. Unlike the reference
+ * they return a status. */
+int ictr_triangulate_DLT(float *pt3d, float *AtAinv, const float *pt2d, const float *P, const int noviews);
+int ictr_triangulate_full3D(float *pt3d, float *pt3d_cov, const float *pt2d, const float *P, const int noviews,
+                            const int noiter, const float minres);
+int ictr_triangulate_full3D_LM(float *pt3d, float *pt3d_cov, const float *pt2d, const float *P, const int noviews,
+                               const int noiter, const float damp_init, const float damp_fct, const float minres,
+                               const float maxdamp);
+int ictr_triangulate_depthonly(float *pt3d, float *depth_cov, const float *campos, const float *ptdir, const float *pt2d,
+                               const float *P, const int noviews, const int noiter, const float minres);
+
 #ifdef __cplusplus
 }
 #endif

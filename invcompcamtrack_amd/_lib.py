@@ -58,6 +58,12 @@ class TraceRec(C.Structure):
                 ("dp", C.c_float * 6), ("p", C.c_float * 6)]
 
 
+class TriangParams(C.Structure):
+    """ictr_triang_params (include/ictr.h)."""
+    _fields_ = [("noiter", C.c_int32), ("minres", C.c_float), ("damp_init", C.c_float), ("damp_fct", C.c_float),
+                ("maxdamp", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/ictr.h
 SIGNATURES = {
     "ictr_optparam_init": (C.c_int, [C.POINTER(OptParam), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
@@ -203,6 +209,20 @@ SIGNATURES = {
     "ictr_ransac_wait": (C.c_int, [VP, C.POINTER(I64), DP, DP, DP, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "ictr_ransac_samples": (C.c_int, [VP, C.POINTER(I64), C.POINTER(C.c_int32)]),
     "ictr_ransac_chunk_size": (C.c_int, [VP]),
+    "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
+    "ictr_triang_destroy": (None, [VP]),
+    "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),
+    "ictr_triang_set_tracks": (C.c_int, [VP, I64, C.POINTER(I64), C.POINTER(C.c_int32), FP, FP]),
+    "ictr_triang_run": (C.c_int, [VP, C.c_int, C.POINTER(TriangParams), FP, FP, FP, VP]),
+    "ictr_triang_wait": (C.c_int, [VP, FP, FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ictr_triangulate_depthonly": (C.c_int, [FP, FP, FP, FP, FP, FP, C.c_int, C.c_int, C.c_float]),
+}
+# the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
+SIGNATURES_REFERENCE_NAMES = {
+    "ictr_triangulate_DLT": (C.c_int, [FP, FP, FP, FP, C.c_int]),
+    "ictr_triangulate_full3D": (C.c_int, [FP, FP, FP, FP, C.c_int, C.c_int, C.c_float]),
+    "ictr_triangulate_full3D_LM": (C.c_int, [FP, FP, FP, FP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                             C.c_float]),
 }
 
 _lib = None
@@ -246,7 +266,7 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items()):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args
