@@ -215,7 +215,9 @@ int ictr_odometer_get_norm(const ictr_odometer *odo, double *meanshift3, double 
  *     not for sharded batches, with event timing on, or with image-only reference pyramids;
  *   - up to 65 536 points in the batch: the per-iteration launches replayed as one hipGraph (2);
  *   - otherwise the per-iteration launches (0). */
-#define ICTR_VARIANT_ANY_SIZE 0x2              /* bit 1: any-size kernels for P = 8 instead of the 8x8 fast path */
+#define ICTR_VARIANT_ANY_SIZE 0x2              /* bit 1: any-size kernels for P = 8 instead of the 8x8 fast path, in
+                                                  the per-iteration launches and in the one-launch tracker (one
+                                                  workgroup per problem: the team form is an 8x8 form) */
 #define ICTR_VARIANT_H_BY_SETUP 0x100          /* bit 8: H reduced by the level's setup tail, not by the first iteration */
 #define ICTR_VARIANT_LAUNCHES 0x2000           /* bit 13: per-iteration launches whatever the problem size */
 #define ICTR_VARIANT_ONE_LAUNCH 0x4000         /* bit 14: the one-launch tracker wherever its point records fit */
@@ -238,6 +240,9 @@ int ictr_odometer_set_variant(ictr_odometer *odo, int variant);
 /* one-launch tracker, team form (see ictr_batch_set_team) */
 int ictr_odometer_set_team(ictr_odometer *odo, int target_points, int min_points, int max_points);
 int ictr_odometer_set_robust(ictr_odometer *odo, int flags, float huber_k); /* see ictr_batch_set_robust */
+/* launch form and workgroups per problem of the last TrackPose (see ictr_batch_last_path / ictr_batch_last_team) */
+int ictr_odometer_last_path(const ictr_odometer *odo);
+int ictr_odometer_last_team(const ictr_odometer *odo);
 
 /* ------------------------------------------------------------------ batched engine (B independent problems) */
 typedef struct ictr_batch ictr_batch;
@@ -274,7 +279,8 @@ int ictr_batch_set_team(ictr_batch *b, int target_points, int min_points, int ma
 /* Behaviour-changing robustness options, all OFF by default (the default reproduces the reference, quirks included).
  * flags: ICTR_ROBUST_CLEAN  points outside the reference view at a level contribute nothing (the reference reuses
  *                           their stale patches and sd coefficients, odometer.cpp:304);
- *        ICTR_ROBUST_COMPOSE left-compositional update G <- exp(dp) G instead of p += dp (pose.cpp:118-123);
+ *        ICTR_ROBUST_COMPOSE left-compositional update G <- exp(dp) G instead of p += dp (pose.cpp:118-123); a step of
+ *                           exactly zero leaves p as it is;
  *        ICTR_ROBUST_HUBER  residuals weighted min(1, huber_k / |r|) in J^T r (H stays the precomputed one).
  * With any flag set the 8x8 fast path is bypassed (any-size kernels). Oracle: oracle/np_oracle.py (same options). */
 #define ICTR_ROBUST_CLEAN 1

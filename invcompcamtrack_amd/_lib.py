@@ -129,6 +129,8 @@ SIGNATURES = {
     "ictr_odometer_set_variant": (C.c_int, [VP, C.c_int]),
     "ictr_odometer_set_team": (C.c_int, [VP, C.c_int, C.c_int, C.c_int]),
     "ictr_odometer_set_robust": (C.c_int, [VP, C.c_int, C.c_float]),
+    "ictr_odometer_last_path": (C.c_int, [VP]),
+    "ictr_odometer_last_team": (C.c_int, [VP]),
     "ictr_batch_create": (C.c_int, [C.POINTER(VP), VP, C.POINTER(OptParam), I64]),
     "ictr_batch_destroy": (None, [VP]),
     "ictr_batch_set_stream": (C.c_int, [VP, VP]),

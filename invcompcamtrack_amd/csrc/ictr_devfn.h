@@ -443,7 +443,10 @@ __device__ __forceinline__ void ws_iterate(WaveSolver &s, float bi, const SolveO
   float dp[6], p[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) dp[k] = rlane(dpi, k);
-  if (e.robust & ICTR_ROBUST_COMPOSE) {  // option: left-compositional update G <- exp(dp) G, p = log(G)
+  // option: left-compositional update G <- exp(dp) G, p = log(G). A zero step (no points, identical frames) leaves the
+  // pose alone, as the additive update does: log(exp(p)) would move it by its rounding error in every iteration.
+  const bool moved = (dp[0] != 0.0f) | (dp[1] != 0.0f) | (dp[2] != 0.0f) | (dp[3] != 0.0f) | (dp[4] != 0.0f) | (dp[5] != 0.0f);
+  if ((e.robust & ICTR_ROBUST_COMPOSE) && moved) {
     float D[12], Go[12], Gn[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Go[k] = G[k];

@@ -1284,7 +1284,7 @@ static int team_points(const ictr_batch *b) {
 }
 // workgroups per problem of the team form for the current tracking (1: not the team form); *q: points per workgroup
 static int track1_team(const ictr_batch *b, int *q) {
-  if (b->P != 8 || b->robust) return 1;
+  if (b->P != 8 || (engine_variant(b) & ICTR_VARIANT_ANY_SIZE)) return 1;  // teams: the lean 8x8 form only
   if (b->maxpts <= b->team_lo || b->maxpts > b->team_hi) return 1;
   if ((int64_t)b->nlev * (1 + std::max(0, b->op->maxiter)) >= 4000) return 1;  // exchange number: 12 bits of the tag
   const int target = team_points(b);
@@ -1544,7 +1544,7 @@ static int track1_launch(ictr_batch *b, const EngineDev &e, const TrackPlan &p, 
   if (int rc = team_prepare(b, p, &tm)) return rc;
   auto launch = [&]() -> int {
     HIPCHK(launch_track1(e, cams, b->maxpts, kTrack1Waves, blob, host_st, b->stream, tm.team > 1 ? &tm : nullptr,
-                         project_here));
+                         project_here, (p.variant & ICTR_VARIANT_ANY_SIZE) != 0));
     return ICTR_OK;
   };
   if (tm.team > 1) return team_launch(4 * (tm.team - 1), b->stream, launch);
@@ -1918,6 +1918,8 @@ extern "C" int ictr_odometer_set_variant(ictr_odometer *o, int v) {
   if (!o) return fail(ICTR_ERR_INVALID, "odometer is NULL");
   return ictr_batch_set_variant(o->b, v);  // (refuses unknown bits)
 }
+extern "C" int ictr_odometer_last_path(const ictr_odometer *o) { return o ? ictr_batch_last_path(o->b) : -1; }
+extern "C" int ictr_odometer_last_team(const ictr_odometer *o) { return o ? ictr_batch_last_team(o->b) : -1; }
 extern "C" int ictr_odometer_set3dpoints(ictr_odometer *o, double *pt_in, int64_t nopoints_in) {
   if (!o) return fail(ICTR_ERR_INVALID, "odometer is NULL");
   return ictr_batch_set3dpoints(o->b, 0, pt_in, nopoints_in);

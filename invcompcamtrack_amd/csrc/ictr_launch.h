@@ -126,9 +126,11 @@ int track1_team_size(int maxpts, int target);
 size_t track1_team_mail_bytes(int B, int team);
 // ONE launch for the whole tracking of every problem. blob (may be NULL): [ProbState x B][PlaneSet x B x nlev] for the
 // fused begin; host_st (may be NULL): pinned mirror of the final records; project_here (without a blob): the records and
-// the plane table have been uploaded, the launch projects (step 3) itself; tm (may be NULL): team form
+// the plane table have been uploaded, the launch projects (step 3) itself; tm (may be NULL): team form; any_size:
+// ICTR_VARIANT_ANY_SIZE, 8x8 patches in the any-size form k_track1 too (a robustness option takes them there anyway)
 hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, int waves, const void *blob,
-                         ProbState *host_st, hipStream_t s, const T1Team *tm, bool project_here = false);
+                         ProbState *host_st, hipStream_t s, const T1Team *tm, bool project_here = false,
+                         bool any_size = false);
 
 // ---------------------------------------------------------------- ictr_resident.hip
 size_t resident_mail_bytes(int parts, int slots);

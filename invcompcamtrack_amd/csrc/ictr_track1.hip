@@ -1031,10 +1031,11 @@ size_t track1_team_mail_bytes(int B, int team) { return sizeof(unsigned long lon
 // project_here (without a blob): the records and the plane table have been uploaded, the launch projects (step 3) itself;
 // tm (may be NULL): team form -- tm->team workgroups of tm->q points per problem, mailbox, tag epoch, error flag
 hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, int waves, const void *blob,
-                         ProbState *host_st, hipStream_t s, const T1Team *tm, bool project_here) {
+                         ProbState *host_st, hipStream_t s, const T1Team *tm, bool project_here, bool any_size) {
   T1Args a;
   for (int l = 0; l < 16; ++l) a.lc[l] = cams[l < e.nlev ? l : 0];
-  const bool p8 = e.P == 8 && !e.robust;  // the lean 8x8 form; behaviour-changing options run in the any-size form
+  // the lean 8x8 form; behaviour-changing options and ICTR_VARIANT_ANY_SIZE run in the any-size form
+  const bool p8 = e.P == 8 && !e.robust && !any_size;
   const int team = (tm && p8 && tm->team > 1) ? tm->team : 1;
   a.team = team;
   a.team_q = team > 1 ? tm->q : 0x7fffffff;

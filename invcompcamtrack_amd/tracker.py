@@ -285,6 +285,14 @@ class PoseClass:
         return p, G
 
 
+def _path_name(form, team):
+    name = {0: "k_iter* (per-iteration launches)", 1: "k_track1 (one launch per tracking)",
+            2: "k_iter* (per-iteration launches replayed as one hipGraph)",
+            3: "k_track1 (one launch per tracking, begin phase and read-back included)",
+            4: "k_level_resident (one launch per level: all iterations, templates resident in registers)"}.get(form, "?")
+    return name + (f" x {team} workgroups per problem" if team > 1 else "")
+
+
 class OdometerClass:
     """odometer.h:21-30 -- the Gauss-Newton tracker; every step of TrackPose runs on the GPU."""
 
@@ -311,7 +319,9 @@ class OdometerClass:
 
     def set_robust(self, clean_invisible=False, compositional=False, huber_k=0.0):
         """Behaviour-changing options, off by default (see ictr_batch_set_robust)."""
-        flags = (1 if clean_invisible else 0) | (2 if compositional else 0) | (4 if huber_k > 0 else 0)
+        # huber_k == 0 is "off"; anything else asks for the weights, so that a negative or NaN threshold is refused by
+        # the library instead of silently switching them off
+        flags = (1 if clean_invisible else 0) | (2 if compositional else 0) | (4 if huber_k != 0 else 0)
         check(_lib.load().ictr_odometer_set_robust(self._h, flags, float(huber_k)))
 
     def Set3Dpoints(self, pt_in, nopoints_in=None):
@@ -349,6 +359,11 @@ class OdometerClass:
         return np.ctypeslib.as_array(ptr, shape=(2 * self.op.maxpttrack,)).copy()
 
     # ---- inspection helpers for the parity tests
+    def path_name(self):
+        """Launch form of the last TrackPose (see TrackBatch.path_name)."""
+        L = _lib.load()
+        return _path_name(L.ictr_odometer_last_path(self._h), L.ictr_odometer_last_team(self._h))
+
     def enable_trace(self, on=True):
         check(_lib.load().ictr_odometer_enable_trace(self._h, int(on)))
 
@@ -411,7 +426,9 @@ class TrackBatch:
 
     def set_robust(self, clean_invisible=False, compositional=False, huber_k=0.0):
         """Behaviour-changing options, off by default (see ictr_batch_set_robust)."""
-        flags = (1 if clean_invisible else 0) | (2 if compositional else 0) | (4 if huber_k > 0 else 0)
+        # huber_k == 0 is "off"; anything else asks for the weights, so that a negative or NaN threshold is refused by
+        # the library instead of silently switching them off
+        flags = (1 if clean_invisible else 0) | (2 if compositional else 0) | (4 if huber_k != 0 else 0)
         check(_lib.load().ictr_batch_set_robust(self._h, flags, float(huber_k)))
 
     def Set3Dpoints(self, problem, pt_in, nopoints_in=None):
@@ -512,13 +529,8 @@ class TrackBatch:
     def path_name(self):
         """Launch form of the last tracking: per-iteration launches (plain, or replayed as one hipGraph) or the
         one-launch small-problem tracker."""
-        name = {0: "k_iter* (per-iteration launches)", 1: "k_track1 (one launch per tracking)",
-                2: "k_iter* (per-iteration launches replayed as one hipGraph)",
-                3: "k_track1 (one launch per tracking, begin phase and read-back included)",
-                4: "k_level_resident (one launch per level: all iterations, templates resident in registers)"}.get(
-            _lib.load().ictr_batch_last_path(self._h), "?")
-        team = _lib.load().ictr_batch_last_team(self._h)
-        return name + (f" x {team} workgroups per problem" if team > 1 else "")
+        L = _lib.load()
+        return _path_name(L.ictr_batch_last_path(self._h), L.ictr_batch_last_team(self._h))
 
     def last_team(self):
         """Workgroups per problem of the last tracking when it ran as one launch (1 otherwise)."""

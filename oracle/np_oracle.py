@@ -3,7 +3,8 @@
 TEST INFRASTRUCTURE ONLY (same rules as oracle.py). Written from the reference's formulas without looking at
 ictr_oracle.c's structure: vectorised over points and patch pixels, no materialised sd planes. Used to
 cross-check the C oracle: element-wise quantities (projections, patches, coefficients) must agree bit for
-bit, sums to float tolerance. Does not reproduce the stale-patch quirk (all test points stay in view).
+bit, sums to float tolerance. Restates visibility (points outside the reference or the new view), patch
+normalisation and the loop rule for a FIRST frame pair; the stale-patch quirk across frame pairs stays with the C oracle.
 """
 from __future__ import annotations
 
@@ -88,39 +89,97 @@ def sd_coefs(X, Y, Z, fx, fy):
     return cx, cy
 
 
-def track(pts3d, p_in, pyr_ref, pyr_new, cam, lv_f, lv_l, psz, maxiter, solve, compose=None, huber_k=0.0):
-    """No-normalisation TrackPose (odometer.cpp:257-426) for points that stay in view.
-    pyr_*: object with .img/.dx/.dy lists of padded planes; cam(which, level) -> float; solve(H,b) -> dp.
-    Returns (p float32[6], trace list of dict(level, iter, H, b, dp)).
+def in_view(mx, my, swo, sho):
+    """odometer.cpp:273-276, 369-377: inclusive bounds; NaN is outside."""
+    with np.errstate(invalid="ignore"):
+        return (mx >= 0) & (my >= 0) & (mx <= swo) & (my <= sho)
+
+
+def normdp32(dp):
+    """delta_p.lpNorm<1>() in Eigen's redux order for 6 coefficients, f32."""
+    d = np.abs(np.asarray(dp, f32))
+    with np.errstate(all="ignore"):
+        return f32(f32(d[0] + f32(d[1] + d[2])) + f32(d[3] + f32(d[4] + d[5])))
+
+
+def _patchnorm(pat):
+    """utilities.cpp:111-112, 187-188: the patch mean, summed and divided in f32, taken off the intensity patch."""
+    n = pat.shape[1] * pat.shape[2]
+    mean = pat.reshape(len(pat), -1).sum(1, dtype=f32) / f32(n)
+    return pat - mean[:, None, None]
+
+
+def track(pts3d, p_in, pyr_ref, pyr_new, cam, lv_f, lv_l, psz, maxiter, solve, compose=None, huber_k=0.0, *,
+          clean_invisible=False, dopatchnorm=False, normdp_ratio=None, exp=None, detail=None):
+    """No-normalisation TrackPose (odometer.cpp:257-426) of a FIRST frame pair after Set3Dpoints.
+    pyr_*: object with .img/.dx/.dy lists of padded planes; cam(which, level) -> float (0..3 fx fy cx cy, 4 5 the
+    unpadded level size swo sho); solve(H,b) -> dp.
+    Returns (p float32[6], trace list of dict(level, iter, H, b, dp, p, vis_new, over)).
+    Visibility (in_view): points outside the reference view at a level get no fresh T/Gx/Gy/coefficients -- they keep
+    what the buffers hold, the zeros of Set3Dpoints or a coarser level's values (odometer.cpp:304) --, points outside the
+    new view at an iteration do not enter b; the patches of neither are fetched. The stale state ACROSS frame pairs is
+    not restated (the C oracle owns it).
+    dopatchnorm: patch mean (f32) taken off T and I. normdp_ratio: None runs maxiter iterations per level; a number
+    applies the loop rule of odometer.cpp:341-346 (iteration k + 1 iff k + 1 < maxiter and normdp_k / normdp_0 > ratio).
+    exp: p float32[6] -> G float32[12], default exp_se3 (NumPy's sinf; a caller that wants the bits of another build's
+    libm passes that build's exp map). detail: a dict that receives, per level, dict(vis_ref, mx, my, T, Gx, Gy, cx, cy).
     Options of the build's robustness extension (not reference behaviour): compose(p, dp) -> p_new replaces the
-    additive update (the test passes log(exp(dp) exp(p))); huber_k > 0 weights residuals min(1, k/|r|) in b."""
+    additive update (the test passes log(exp(dp) exp(p))); huber_k > 0 weights residuals min(1, k/|r|) in b;
+    clean_invisible zeroes Gx, Gy of the points outside the reference view at a level, so that they add nothing to H
+    or b there."""
+    exp = exp_se3 if exp is None else exp
     X, Y, Z = (pts3d[k].astype(f32) for k in range(3))
+    K = len(X)
     p = np.asarray(p_in, np.float64).astype(f32)
-    G0 = exp_se3(p)
+    G0 = np.asarray(exp(p), f32)
     trace = []
     _, _, Xc, Yc, Zc = project(G0, X, Y, Z, f32(1), f32(1), f32(0), f32(0))
+    T, Gx, Gy = (np.zeros((K, psz, psz), f32) for _ in range(3))
+    cxk, cyk = np.zeros((K, 6), f32), np.zeros((K, 6), f32)
     for sl in range(lv_f, lv_l - 1, -1):
         fx, fy, cx_, cy_ = (f32(cam(k, sl)) for k in range(4))
+        swo, sho = f32(cam(4, sl)), f32(cam(5, sl))
         mx, my, _, _, _ = project(G0, X, Y, Z, fx, fy, cx_, cy_)
-        T = patches(pyr_ref.img[sl], mx, my, psz)
-        Gx = patches(pyr_ref.dx[sl], mx, my, psz)
-        Gy = patches(pyr_ref.dy[sl], mx, my, psz)
-        cxk, cyk = sd_coefs(Xc, Yc, Zc, fx, fy)
+        vr = in_view(mx, my, swo, sho)
+        t_new = patches(pyr_ref.img[sl], mx[vr], my[vr], psz)
+        T[vr] = _patchnorm(t_new) if dopatchnorm else t_new
+        Gx[vr] = patches(pyr_ref.dx[sl], mx[vr], my[vr], psz)
+        Gy[vr] = patches(pyr_ref.dy[sl], mx[vr], my[vr], psz)
+        cxk[vr], cyk[vr] = sd_coefs(Xc[vr], Yc[vr], Zc[vr], fx, fy)
+        if clean_invisible:
+            Gx[~vr] = 0
+            Gy[~vr] = 0
+        if detail is not None:
+            detail[sl] = dict(vis_ref=vr.copy(), mx=mx, my=my, T=T.copy(), Gx=Gx.copy(), Gy=Gy.copy(), cx=cxk.copy(),
+                              cy=cyk.copy())
         sd = Gx[:, None] * cxk[:, :, None, None] + Gy[:, None] * cyk[:, :, None, None]  # (K,6,P,P)
         sd[:, 0] = Gx * cxk[:, 0, None, None]
         sd[:, 1] = Gy * cyk[:, 1, None, None]
-        sdf = sd.reshape(len(X), 6, -1).astype(np.float64)
+        sdf = sd.reshape(K, 6, -1).astype(np.float64)
         H = np.einsum("kip,kjp->ij", sdf, sdf).astype(f32)
-        for it in range(maxiter):
-            G = exp_se3(p)
+        it, nd, nd0 = 0, f32(1e-10), f32(1e-10)
+        while it < maxiter:
+            if normdp_ratio is not None:
+                with np.errstate(all="ignore"):
+                    if not f32(nd / nd0) > f32(normdp_ratio):
+                        break
+            G = np.asarray(exp(p), f32)
             nx, ny, _, _, _ = project(G, X, Y, Z, fx, fy, cx_, cy_)
-            I = patches(pyr_new.img[sl], nx, ny, psz)
-            r = T - I
+            vn = in_view(nx, ny, swo, sho)
+            I = patches(pyr_new.img[sl], nx[vn], ny[vn], psz)
+            if dopatchnorm:
+                I = _patchnorm(I)
+            r = T[vn] - I
+            over = float(np.mean(np.abs(r) > f32(huber_k))) if huber_k > 0 and r.size else 0.0
             if huber_k > 0:
                 ar = np.abs(r)
                 r = np.where(ar > f32(huber_k), r * (f32(huber_k) / np.where(ar > 0, ar, f32(1))), r).astype(f32)
-            b = (sd * r[:, None]).reshape(len(X), 6, -1).astype(np.float64).sum((0, 2)).astype(f32)
+            b = (sd[vn] * r[:, None]).reshape(int(vn.sum()), 6, -1).astype(np.float64).sum((0, 2)).astype(f32)
             dp = solve(H, b)
             p = (p + dp) if compose is None else np.asarray(compose(p, dp), f32)
-            trace.append(dict(level=sl, iter=it, H=H, b=b, dp=dp, p=p.copy()))
+            trace.append(dict(level=sl, iter=it, H=H, b=b, dp=dp, p=p.copy(), vis_new=vn, over=over))
+            nd = normdp32(dp)
+            if it == 0:
+                nd0 = nd
+            it += 1
     return p, trace

@@ -15,7 +15,9 @@ pytestmark = pytest.mark.gpu
 
 
 def _compose(O):
-    def f(p, dp):  # p_new = log(exp(dp) * exp(p)), float32 like the device code
+    def f(p, dp):  # p_new = log(exp(dp) * exp(p)), float32 like the device code; a zero step leaves p alone
+        if not np.any(np.asarray(dp) != 0):
+            return np.asarray(p, np.float32)
         D = O.se3_exp(np.asarray(dp, np.float32)).reshape(3, 4).astype(np.float32)
         G = O.se3_exp(np.asarray(p, np.float32)).reshape(3, 4).astype(np.float32)
         D4, G4 = np.eye(4, dtype=np.float32), np.eye(4, dtype=np.float32)

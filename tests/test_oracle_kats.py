@@ -335,3 +335,103 @@ def test_c_oracle_agrees_with_numpy_restatement(oracle):
         assert np.allclose(a["H"], b["H"], rtol=1e-4, atol=1e-4 * np.abs(a["H"]).max())
     assert np.allclose(trace_c[0]["b"], trace_n[0]["b"], rtol=1e-3, atol=1e-3 * np.abs(trace_c[0]["b"]).max())
     assert np.allclose(p_c, p_n.astype(np.float64), atol=2e-5)
+
+
+def _np_vs_c(oracle, sc, p_start, lv_f, lv_l, P, maxiter, ratio=0.0, dpn=0, **np_opts):
+    """The same first frame pair through a fresh C oracle and through np_oracle.track (the C build's exp map, so that
+    the projections carry the same bits). Returns (tr, p_c, p_n, trace_n, detail)."""
+    from oracle import np_oracle as N
+    n = sc["pts3d"].shape[1]
+    op = oracle.make_op(lv_f, lv_l, P, maxiter, ratio, 0, dpn, n)
+    pa, pb = oracle.Pyramid(sc["img_a"], lv_f, P), oracle.Pyramid(sc["img_b"], lv_f, P)
+    tr = oracle.Tracker(op, sc["fc"], sc["cc"], sc["wh"])
+    tr.set3dpoints(sc["pts3d"].copy())
+    tr.setpose(p_start, pa, pb)
+    p_c = tr.trackpose()
+    detail = {}
+    p_n, trace_n = N.track(sc["pts3d"], p_start, pa, pb, tr.cam_get, lv_f, lv_l, P, maxiter, oracle.solve6,
+                           exp=oracle.se3_exp, detail=detail, **np_opts)
+    return tr, p_c, p_n, trace_n, detail
+
+
+def _out_of_view_start(sc, shift):
+    """A start pose whose x translation moves every projection by ~ fx * shift / depth pixels (depth 10)."""
+    p = sc["p_a"].copy()
+    p[0] += shift
+    return p
+
+
+@pytest.mark.parametrize("clean", [False, True])
+def test_numpy_restatement_masks_points_out_of_view_like_the_c_oracle(oracle, clean):
+    """A third of the points outside the reference view on a fresh tracker's first pair: the NumPy visibility masks are
+    the C oracle's ind_ref / ind_new (which it keeps for the last level and iteration only, hence one run per last
+    level), the patches of the visible points carry the same bits, and the invisible points hold the zeros of
+    Set3Dpoints -- so the default and clean_invisible coincide here and both are held to the C oracle."""
+    sc = synth.make_scene(240, 208, n_points=90, seed=12, margin=2.0,  # a true motion of ~6 px: the new view differs
+                          dp_gt=np.array([0.3, -0.18, 0.04, 0.004, -0.003, 0.005]))
+    lv_f, P, n = 2, 8, 90
+    p0 = _out_of_view_start(sc, 4.0)  # 4.0 * 187.5 / 10 = 75 px of 240
+    for lv_l in (2, 1, 0):
+        tr, p_c, p_n, trace_n, detail = _np_vs_c(oracle, sc, p0, lv_f, lv_l, P, 4, clean_invisible=clean)
+        vr = detail[lv_l]["vis_ref"]
+        assert 0.15 < 1.0 - vr.mean() < 0.6
+        assert np.array_equal(vr, tr.ind(0)[:n].astype(bool)), lv_l
+        assert np.array_equal(trace_n[-1]["vis_new"], tr.ind(1)[:n].astype(bool)), lv_l
+        for w, key in ((0, "T"), (1, "Gx"), (2, "Gy")):
+            c = tr.buffer(w, n * P * P).reshape(n, P, P)
+            assert np.array_equal(c[vr], detail[lv_l][key][vr]), (lv_l, key)
+            assert not c[~vr].any() and not detail[lv_l][key][~vr].any()  # never seen: Set3Dpoints' zeros
+        trace_c = tr.trace()
+        assert [(r["level"], r["iter"]) for r in trace_c] == [(r["level"], r["iter"]) for r in trace_n]
+        for a, b in zip(trace_c, trace_n):
+            assert np.allclose(a["H"], b["H"], rtol=1e-4, atol=1e-4 * np.abs(a["H"]).max())
+        assert np.allclose(trace_c[0]["b"], trace_n[0]["b"], rtol=1e-3, atol=1e-3 * np.abs(trace_c[0]["b"]).max())
+        assert np.allclose(p_c, p_n.astype(np.float64), atol=1e-4)
+    # the new-view mask is not the reference-view mask: it follows the pose
+    assert any(not np.array_equal(r["vis_new"], detail[r["level"]]["vis_ref"]) for r in trace_n)
+
+
+def test_numpy_restatement_patch_normalisation_like_the_c_oracle(oracle):
+    """dopatchnorm=1: T agrees to 1e-4 (the mean is a 64-term f32 sum in another order), Gx and Gy bit for bit, sums and
+    pose to the bars of the cross-check above."""
+    sc = synth.make_scene(240, 208, n_points=80, seed=14, margin=40.0)
+    P, n = 8, 80
+    tr, p_c, p_n, trace_n, detail = _np_vs_c(oracle, sc, sc["p_a"], 2, 0, P, 4, dpn=1, dopatchnorm=True)
+    assert detail[0]["vis_ref"].all()
+    T = tr.buffer(0, n * P * P).reshape(n, P, P)
+    assert np.abs(T - detail[0]["T"]).max() <= 1e-4
+    assert np.abs(T.reshape(n, -1).mean(1)).max() < 1e-4 and np.abs(T).max() > 1.0
+    assert np.array_equal(tr.buffer(1, n * P * P), detail[0]["Gx"].ravel())
+    assert np.array_equal(tr.buffer(2, n * P * P), detail[0]["Gy"].ravel())
+    trace_c = tr.trace()
+    assert len(trace_c) == len(trace_n) == 12
+    for a, b in zip(trace_c, trace_n):
+        assert np.allclose(a["H"], b["H"], rtol=1e-4, atol=1e-4 * np.abs(a["H"]).max())
+    assert np.allclose(trace_c[0]["b"], trace_n[0]["b"], rtol=1e-3, atol=1e-3 * np.abs(trace_c[0]["b"]).max())
+    assert np.allclose(p_c, p_n.astype(np.float64), atol=1e-4)
+    # and it is not the unnormalised run
+    _, _, _, trace_0, _ = _np_vs_c(oracle, sc, sc["p_a"], 2, 0, P, 1)
+    assert not np.array_equal(trace_0[0]["b"], trace_n[0]["b"])
+
+
+def test_numpy_restatement_loop_rule_like_the_c_oracle(oracle):
+    """normdp_ratio=0.01: the same (level, iteration) records, fewer than levels x maxiter."""
+    sc = synth.make_scene(240, 208, n_points=80, seed=15, margin=40.0)
+    tr, p_c, p_n, trace_n, _ = _np_vs_c(oracle, sc, sc["p_a"], 2, 0, 8, 10, ratio=0.01, normdp_ratio=0.01)
+    seq = [(r["level"], r["iter"]) for r in tr.trace()]
+    assert seq == [(r["level"], r["iter"]) for r in trace_n]
+    assert 3 < len(seq) < 30 and {lv for lv, _ in seq} == {0, 1, 2}
+    assert np.allclose(p_c, p_n.astype(np.float64), atol=1e-4)
+
+
+def test_numpy_restatement_keeps_its_bits_for_points_in_view(oracle):
+    """The extension changes nothing for its earlier callers: every mask is all-true and the loop runs maxiter times."""
+    from oracle import np_oracle as N
+    sc = synth.make_scene(240, 208, n_points=40, seed=16, margin=40.0)
+    pa, pb = oracle.Pyramid(sc["img_a"], 1, 8), oracle.Pyramid(sc["img_b"], 1, 8)
+    tr = oracle.Tracker(oracle.make_op(1, 0, 8, 3, 0.0, 0, 0, 40), sc["fc"], sc["cc"], sc["wh"])
+    p_1, t_1 = N.track(sc["pts3d"], sc["p_a"], pa, pb, tr.cam_get, 1, 0, 8, 3, oracle.solve6, huber_k=5.0)
+    p_2, t_2 = N.track(sc["pts3d"], sc["p_a"], pa, pb, tr.cam_get, 1, 0, 8, 3, oracle.solve6, huber_k=5.0,
+                       clean_invisible=True, normdp_ratio=0.0)
+    assert len(t_1) == len(t_2) == 6 and all(r["vis_new"].all() for r in t_1)
+    assert np.array_equal(p_1, p_2) and all(np.array_equal(a["b"], b["b"]) for a, b in zip(t_1, t_2))
