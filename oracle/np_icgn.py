@@ -62,10 +62,11 @@ def K_matrix(w, h):
 class NpEngine:
     """The phase API of the HIP engine (begin / hess_accumulate / hess_finish / iter_accumulate / iter_finish) for one
     problem; ``rows`` restricts the template to a band (row-band sharding), ``red`` is the 44-float reduction record
-    the caller all-reduces between accumulate and finish."""
+    the caller all-reduces between accumulate and finish. ``solve(H, b)`` replaces the linear solve (default
+    ``np.linalg.solve``); rank-deficient systems need one that accepts them, e.g. a least-squares solve."""
 
     def __init__(self, planes_a, planes_b, pad, w, h, model, maxiter=10, eps=0.0, region=None, M0_px=None, rows=None,
-                 trace=None):
+                 trace=None, solve=None):
         self.pa, self.pb, self.pad, self.w, self.h, self.model = planes_a, planes_b, pad, w, h, model
         self.n, self.maxiter, self.eps, self.rows, self.trace = NP[model], maxiter, eps, rows, trace
         self.region = (2, 2, w - 4, h - 4) if region is None else tuple(region)
@@ -73,6 +74,7 @@ class NpEngine:
         self.Ki = np.linalg.inv(self.K)
         self.M0 = np.eye(3) if M0_px is None else self.Ki @ np.asarray(M0_px, np.float64) @ self.K
         self.red = np.zeros(44)
+        self.solve = np.linalg.solve if solve is None else solve
 
     def begin(self):
         M = self.M0 / self.M0[2, 2]
@@ -128,7 +130,7 @@ class NpEngine:
             return
         b = self.red[36:36 + self.n].copy()
         self.red[:] = 0
-        dp = np.linalg.solve(self.H, b) * (2.0 / self.f)
+        dp = np.asarray(self.solve(self.H, b), np.float64) * (2.0 / self.f)
         if self.trace is not None:
             self.trace.append((l, self.it, self.H.copy(), b, dp.copy()))
         M = self.M @ np.linalg.inv(param_matrix(self.model, dp))
@@ -143,10 +145,10 @@ class NpEngine:
 
 
 def align(planes_a, planes_b, pad, w, h, model, lv_f, lv_l=0, maxiter=10, eps=0.0, region=None, M0_px=None,
-          trace=None):
+          trace=None, solve=None):
     """planes_a: list over levels of (img, dx, dy) padded arrays; planes_b: list of padded images.
     Returns (M_px (3,3), iterations). trace (list) receives (level, it, H, b, dp) tuples."""
-    e = NpEngine(planes_a, planes_b, pad, w, h, model, maxiter, eps, region, M0_px, None, trace)
+    e = NpEngine(planes_a, planes_b, pad, w, h, model, maxiter, eps, region, M0_px, None, trace, solve)
     e.begin()
     for l in range(lv_f, lv_l - 1, -1):
         e.hess_accumulate(l)
