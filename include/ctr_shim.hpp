@@ -229,4 +229,38 @@ class TriangClass {
   ictr_triang *h_;
 };
 
+// The point-track front end (ictr_pointtrack_* in include/ictr.h): the loop of misc_src/run_OF_point_track.py.ipynb on the
+// device. Push the frames in order; block b (opened by the pair b, b + 1) is read back when it is wanted.
+class PointTrackClass {
+ public:
+  PointTrackClass(int w, int h, int bsize, int maxcorners, int lv_f, int psz, int step, int maxiter = 10, float eps = 0.01f,
+                  double quality = 0.001, int mindist = 5, int win = 3, double th_ratio = 0.2, double th_abs = 1.0)
+      : h_(nullptr), bsize_(bsize), maxcorners_(maxcorners) {
+    check(ictr_pointtrack_create(&h_, w, h, bsize, maxcorners, lv_f, psz, step, maxiter, eps, quality, mindist, win, th_ratio,
+                                 th_abs),
+          "PointTrackClass");
+  }
+  ~PointTrackClass() { ictr_pointtrack_destroy(h_); }
+  PointTrackClass(const PointTrackClass &) = delete;
+  PointTrackClass &operator=(const PointTrackClass &) = delete;
+  void PushFrame(const float *img /* [h][w] */) { check(ictr_pointtrack_push_frame(h_, img), "PushFrame"); }
+  int64_t FrameCounter() const {
+    int64_t n = 0;
+    check(ictr_pointtrack_frcounter(h_, &n), "FrameCounter");
+    return n;
+  }
+  // buffers sized for maxcorners rows: tracks [.][2][bsize], valid [.], absmovement [.]; any may be NULL. Returns the rows.
+  int ReadBlock(int64_t block, float *tracks, uint8_t *valid, double *absmovement) {
+    int n = 0;
+    check(ictr_pointtrack_read_block(h_, block, tracks, valid, absmovement, &n), "ReadBlock");
+    return n;
+  }
+  int BlockSize() const { return bsize_; }
+  int MaxCorners() const { return maxcorners_; }
+
+ private:
+  ictr_pointtrack *h_;
+  int bsize_, maxcorners_;
+};
+
 }  // namespace CTR

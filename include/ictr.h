@@ -545,6 +545,52 @@ int ictr_triangulate_full3D_LM(float *pt3d, float *pt3d_cov, const float *pt2d, 
 int ictr_triangulate_depthonly(float *pt3d, float *depth_cov, const float *campos, const float *ptdir, const float *pt2d,
                                const float *P, const int noviews, const int noiter, const float minres);
 
+/* ---------------------------------------------------------------- point-track front end (ictr_frontend.hip)
+ * The stage in front of the device code, on the device: corners, forward / backward flow on a node grid, the sliding
+ * window of tracks. Each part equals host code of the Python package bit for bit (DESIGN.md §4 "Point-track front end"):
+ * patchflow.good_features, patchflow.dense_flow, classoftrack.func_get_transf_position, classoftrack.oftrack.addframe. */
+
+/* patchflow.good_features(img, maxcorners, quality, mindist, win): the plane is level 0 of pyr, or, with pyr NULL, the
+ * host image img [h][w] f32 (w, h are read from the pyramid otherwise). mindist >= 1, 0 <= win <= 8, maxcorners >= 1.
+ * out_xy [maxcorners][2] (x, y) strongest first, *out_count of them are written. */
+int ictr_good_features(const ictr_pyramid *pyr, const float *img, int w, int h, int maxcorners, double quality,
+                       int mindist, int win, float *out_xy, int *out_count);
+
+/* one direction of one frame pair on a `step` grid: nodes x = step/2 + i step < w, likewise y */
+typedef struct ictr_flowgrid ictr_flowgrid;
+int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step);
+void ictr_flowgrid_destroy(ictr_flowgrid *g);
+int ictr_flowgrid_dims(const ictr_flowgrid *g, int *nx, int *ny);
+/* tracks the nodes from pyr_a to pyr_b (the kernel and arguments of ictr_patchflow, lv_l = 0), forms d = out - pts and
+ * fills the lost nodes (dense_flow's rule); enqueued on hip_stream (NULL: the null stream), no host wait */
+int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, int psz, int lv_f,
+                          int maxiter, float eps, void *hip_stream);
+/* injects node displacements d [ny][nx][2] and the lost mask [ny][nx] (1 = lost, its d is ignored) and fills */
+int ictr_flowgrid_set_nodes(ictr_flowgrid *g, const float *d, const uint8_t *lost);
+/* d after the fill and the lost mask; either may be NULL */
+int ictr_flowgrid_nodes(const ictr_flowgrid *g, float *d, uint8_t *lost);
+/* func_get_transf_position(xy, F[:,:,0], F[:,:,1]) with F = the dense field, which is not formed. xy, out [K][2] f64 */
+int ictr_flowgrid_gather(const ictr_flowgrid *g, const double *xy, int64_t K, double *out);
+/* the dense field [h][w][2] f32 of dense_flow into out (a device pointer when on_device != 0) */
+int ictr_flowgrid_dense(const ictr_flowgrid *g, float *out, int on_device);
+
+/* the loop of patchflow.run_OF_point_track with a ring of bsize block slots on the device: device memory does not grow
+ * with the sequence, a block that leaves the window is copied to a host store of the object */
+typedef struct ictr_pointtrack ictr_pointtrack;
+int ictr_pointtrack_create(ictr_pointtrack **out, int w, int h, int bsize, int maxcorners, int lv_f, int psz, int step,
+                           int maxiter, float eps, double quality, int mindist, int win, double th_ratio, double th_abs);
+void ictr_pointtrack_destroy(ictr_pointtrack *t);
+/* img [h][w] f32 in host memory (copied before the call returns). From the second frame on: the pair's two grids, the
+ * corners of its first frame, oftrack.addframe. Everything is enqueued; the host reads nothing back. */
+int ictr_pointtrack_push_frame(ictr_pointtrack *t, const float *img);
+/* oftrack.frcounter: frame pairs so far = blocks */
+int ictr_pointtrack_frcounter(const ictr_pointtrack *t, int64_t *frcounter);
+/* block `block` as addframe holds it before any compaction: *count rows (0: the frame had no corner) of tracks
+ * [count][2][bsize] f32, valid [count], absmovement [count] f64; buffers sized for maxcorners rows, any but count may be
+ * NULL. A block b <= frcounter - bsize has left the window (oftrack keeps its valid rows only). Waits for the device. */
+int ictr_pointtrack_read_block(ictr_pointtrack *t, int64_t block, float *tracks, uint8_t *valid, double *absmovement,
+                               int *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libictr_hip.so")
 FP = C.POINTER(C.c_float)
 DP = C.POINTER(C.c_double)
 IP = C.POINTER(C.c_int)
+U8P = C.POINTER(C.c_uint8)
 FPP = C.POINTER(FP)
 VP = C.c_void_p
 I64 = C.c_int64
@@ -218,6 +219,21 @@ SIGNATURES = {
     "ictr_triang_run": (C.c_int, [VP, C.c_int, C.POINTER(TriangParams), FP, FP, FP, VP]),
     "ictr_triang_wait": (C.c_int, [VP, FP, FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ictr_triangulate_depthonly": (C.c_int, [FP, FP, FP, FP, FP, FP, C.c_int, C.c_int, C.c_float]),
+    "ictr_good_features": (C.c_int, [VP, FP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, FP, IP]),
+    "ictr_flowgrid_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int]),
+    "ictr_flowgrid_destroy": (None, [VP]),
+    "ictr_flowgrid_dims": (C.c_int, [VP, IP, IP]),
+    "ictr_flowgrid_compute": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP]),
+    "ictr_flowgrid_set_nodes": (C.c_int, [VP, FP, U8P]),
+    "ictr_flowgrid_nodes": (C.c_int, [VP, FP, U8P]),
+    "ictr_flowgrid_gather": (C.c_int, [VP, DP, I64, DP]),
+    "ictr_flowgrid_dense": (C.c_int, [VP, VP, C.c_int]),
+    "ictr_pointtrack_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_float, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "ictr_pointtrack_destroy": (None, [VP]),
+    "ictr_pointtrack_push_frame": (C.c_int, [VP, FP]),
+    "ictr_pointtrack_frcounter": (C.c_int, [VP, C.POINTER(I64)]),
+    "ictr_pointtrack_read_block": (C.c_int, [VP, I64, FP, U8P, DP, IP]),
 }
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {

@@ -1,0 +1,777 @@
+// ictr_frontend.hip -- the point-track front end on the device: corners, flow grid, track window (DESIGN.md §4 "Point-track
+// front end"). Everything here restates host code of the package bit for bit:
+//   patchflow.good_features            -> k_gf_response / k_gf_cells / k_gf_select / k_gf_compact / k_gf_rank
+//   patchflow.dense_flow's fill + bilinear up-sampling -> k_fg_nodes / k_fg_diff / k_fg_rowfill / k_fg_colfill, fg_value()
+//   classoftrack.func_get_transf_position on that field -> fg_gather() (the field is never formed), k_fg_gather, k_fg_dense
+//   classoftrack.oftrack.addframe      -> k_pt_open / k_pt_advance on a ring of block slots
+// All float64 arithmetic is written in the host code's operation order; the library is built with -ffp-contract=off, and /
+// and sqrt on doubles are the correctly rounded sequences, so the results carry NumPy's bits.
+//
+// The host decides no launch from device data: corner counts stay in device memory and the kernels read them there.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ictr_dev.h"
+#include "ictr_launch.h"
+
+namespace ictr {
+
+// ---------------------------------------------------------------- corner picker
+constexpr int kGfTW = 32, kGfTH = 16;  // response tile (outputs) of one workgroup
+constexpr int kGfSelBlock = 1024;
+constexpr size_t kGfMaxLds = 64 * 1024;
+
+struct GfCtl {
+  unsigned long long maxbits;  // bits of max(lam) (lam >= 0 there: the border is 0)
+  unsigned long long thr;      // key of the maxcorners-th strongest cell winner (0: every winner survives)
+  int nsurv;                   // survivors in the list (key >= thr)
+  int pad;
+};
+
+static size_t gf_lds_bytes(int win) {
+  const size_t ph = kGfTH + 2 * win, pw = kGfTW + 2 * win;
+  return sizeof(double) * 3 * (ph * pw + ph * kGfTW);
+}
+
+// lam = smaller eigenvalue of the (2 win + 1)^2 zero-padded window sums of [gx^2 gx gy; gx gy gy^2], float64, central
+// differences (0 in the first / last column / row); window sums separable: rows (dx ascending) first, then columns (dy
+// ascending). lam = 0 in the outer `mindist` rows and columns. The block maximum goes to ctl->maxbits by an unsigned max.
+__global__ __launch_bounds__(kBlock) void k_gf_response(const float *__restrict__ img, int stride, int W, int H, int win,
+                                                        int mindist, double *__restrict__ lam, GfCtl *ctl) {
+  extern __shared__ __attribute__((aligned(16))) char gf_smem[];
+  const int PH = kGfTH + 2 * win, PW = kGfTW + 2 * win;
+  double *P = reinterpret_cast<double *>(gf_smem);  // [3][PH][PW] products
+  double *R = P + 3 * PH * PW;                      // [3][PH][TW] row sums
+  const int x0 = blockIdx.x * kGfTW, y0 = blockIdx.y * kGfTH;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < PH * PW; e += kBlock) {
+    const int ly = e / PW, lx = e - ly * PW;
+    const int X = x0 - win + lx, Y = y0 - win + ly;
+    double gx = 0.0, gy = 0.0;
+    if (X >= 0 && X < W && Y >= 0 && Y < H) {
+      const float *p = img + (size_t)Y * stride + X;
+      if (X >= 1 && X <= W - 2) gx = (double)p[1] - (double)p[-1];
+      if (Y >= 1 && Y <= H - 2) gy = (double)p[stride] - (double)p[-stride];
+    }
+    P[e] = gx * gx;
+    P[PH * PW + e] = gx * gy;
+    P[2 * PH * PW + e] = gy * gy;
+  }
+  __syncthreads();
+  for (int e = tid; e < PH * kGfTW; e += kBlock) {
+    const int ly = e / kGfTW, lx = e - ly * kGfTW;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double *row = P + c * PH * PW + ly * PW + lx;
+      double s = 0.0;
+      for (int d = 0; d <= 2 * win; ++d) s += row[d];
+      R[c * PH * kGfTW + e] = s;
+    }
+  }
+  __syncthreads();
+  double m = 0.0;
+  for (int e = tid; e < kGfTH * kGfTW; e += kBlock) {
+    const int ly = e / kGfTW, lx = e - ly * kGfTW;
+    const int X = x0 + lx, Y = y0 + ly;
+    if (X >= W || Y >= H) continue;
+    double s[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double *col = R + c * PH * kGfTW + ly * kGfTW + lx;
+      double a = 0.0;
+      for (int d = 0; d <= 2 * win; ++d) a += col[d * kGfTW];
+      s[c] = a;
+    }
+    const double sxx = s[0], sxy = s[1], syy = s[2];
+    const double df = sxx - syy;
+    double v = 0.5 * (sxx + syy) - sqrt(0.25 * (df * df) + sxy * sxy);
+    if (X < mindist || X >= W - mindist || Y < mindist || Y >= H - mindist) v = 0.0;
+    lam[(size_t)Y * W + X] = v;
+    if (v > m) m = v;
+  }
+  __syncthreads();  // P is free: the workgroup's maximum
+  P[tid] = m;
+  __syncthreads();
+  for (int o = kBlock / 2; o > 0; o >>= 1) {
+    if (tid < o && P[tid + o] > P[tid]) P[tid] = P[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0 && P[0] > 0.0) atomicMax(&ctl->maxbits, (unsigned long long)__double_as_longlong(P[0]));
+}
+
+// one thread per mindist x mindist cell: its candidate (lam > thr, lam >= each neighbour inside the image) with the largest
+// lam, ties to the smallest y W + x (the scan order). key = bits of that lam (> 0), 0 for a cell without a candidate
+__global__ __launch_bounds__(kBlock) void k_gf_cells(const double *__restrict__ lam, int W, int H, int mindist, double quality,
+                                                     const GfCtl *ctl, int ncx, int ncells,
+                                                     unsigned long long *__restrict__ key, int *__restrict__ idx) {
+  const int c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= ncells) return;
+  const double thr = quality * __longlong_as_double((long long)ctl->maxbits);
+  const int cy = c / ncx, cx = c - cy * ncx;
+  const int ys = cy * mindist, xs = cx * mindist;
+  const int ye = min(ys + mindist, H), xe = min(xs + mindist, W);
+  double best = 0.0;
+  int bi = -1;
+  for (int y = ys; y < ye; ++y)
+    for (int x = xs; x < xe; ++x) {
+      const double v = lam[(size_t)y * W + x];
+      if (!(v > thr) || !(v > best)) continue;
+      bool ismax = true;
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int yy = y + dy, xx = x + dx;
+          if ((dy | dx) == 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) continue;  // outside counts as -1 < v
+          ismax &= v >= lam[(size_t)yy * W + xx];
+        }
+      if (ismax) {
+        best = v;
+        bi = y * W + x;
+      }
+    }
+  key[c] = bi >= 0 ? (unsigned long long)__double_as_longlong(best) : 0ull;
+  idx[c] = bi;
+}
+
+// one workgroup: radix select (8 passes of 8 bits, most significant first) of the maxcorners-th largest key. Writes the
+// threshold key (0 when there are no more than maxcorners winners), the corner count min(winners, maxcorners) to *count and
+// clears the survivor counter.
+__global__ __launch_bounds__(kGfSelBlock) void k_gf_select(const unsigned long long *__restrict__ key, int ncells,
+                                                           int maxcorners, GfCtl *ctl, int *count) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned long long s_prefix;
+  __shared__ unsigned s_k;
+  __shared__ int s_done;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    s_prefix = 0;
+    s_k = (unsigned)maxcorners;
+    s_done = 0;
+  }
+  for (int pass = 7; pass >= 0; --pass) {
+    const int shift = 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    const unsigned long long prefix = s_prefix;
+    for (int i = tid; i < ncells; i += kGfSelBlock) {
+      const unsigned long long k = key[i];
+      if (k == 0) continue;
+      if (pass < 7 && (k >> (shift + 8)) != (prefix >> (shift + 8))) continue;
+      atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      unsigned total = 0;
+      for (int d = 0; d < 256; ++d) total += hist[d];
+      if (pass == 7 && total <= (unsigned)maxcorners) {  // every winner is a corner
+        ctl->thr = 0;
+        *count = (int)total;
+        s_done = 1;
+      } else {
+        unsigned cum = 0, k = s_k;
+        int d = 255;
+        for (; d > 0; --d) {
+          if (cum + hist[d] >= k) break;
+          cum += hist[d];
+        }
+        s_k = k - cum;
+        s_prefix = prefix | ((unsigned long long)d << shift);
+      }
+    }
+    __syncthreads();
+    if (s_done) break;
+  }
+  if (tid == 0) {
+    if (!s_done) {
+      ctl->thr = s_prefix;
+      *count = maxcorners;
+    }
+    ctl->nsurv = 0;
+  }
+}
+
+// the winners with key >= thr, in any order (their ranks do not depend on it)
+__global__ __launch_bounds__(kBlock) void k_gf_compact(const unsigned long long *__restrict__ key, const int *__restrict__ idx,
+                                                       int ncells, GfCtl *ctl, unsigned long long *__restrict__ lkey,
+                                                       int *__restrict__ lidx) {
+  const int c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= ncells) return;
+  const unsigned long long k = key[c];
+  if (k == 0 || k < ctl->thr) return;
+  const int slot = atomicAdd(&ctl->nsurv, 1);  // < ncells: the list has ncells entries
+  lkey[slot] = k;
+  lidx[slot] = idx[c];
+}
+
+// rank of a survivor = survivors that precede it (lam descending, then index ascending); rank < maxcorners: out[rank]
+__global__ __launch_bounds__(kBlock) void k_gf_rank(const unsigned long long *__restrict__ lkey, const int *__restrict__ lidx,
+                                                    const GfCtl *ctl, int maxcorners, int W, float *__restrict__ out) {
+  __shared__ unsigned long long sk[kBlock];
+  __shared__ int si[kBlock];
+  const int n = ctl->nsurv;
+  for (int base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {  // uniform per workgroup
+    const int i = base + threadIdx.x;
+    const bool have = i < n;
+    const unsigned long long k = have ? lkey[i] : 0ull;
+    const int id = have ? lidx[i] : 0;
+    int rank = 0;
+    for (int t0 = 0; t0 < n; t0 += kBlock) {
+      __syncthreads();
+      const int j = t0 + threadIdx.x;
+      sk[threadIdx.x] = j < n ? lkey[j] : 0ull;  // key 0 precedes nothing
+      si[threadIdx.x] = j < n ? lidx[j] : 0;
+      __syncthreads();
+      const int m = min(kBlock, n - t0);
+      for (int q = 0; q < m; ++q) rank += (sk[q] > k) | ((sk[q] == k) & (si[q] < id));
+    }
+    if (have && rank < maxcorners) {
+      const int y = id / W, x = id - y * W;
+      out[2 * rank] = (float)x;
+      out[2 * rank + 1] = (float)y;
+    }
+  }
+}
+
+struct GfWork {
+  int w = 0, h = 0, mindist = 0, win = 0, ncx = 0, ncells = 0;
+  double *lam = nullptr;
+  unsigned long long *key = nullptr, *lkey = nullptr;
+  int *idx = nullptr, *lidx = nullptr;
+  GfCtl *ctl = nullptr;
+};
+
+static void gf_free(GfWork *g) {
+  if (g->lam) hipFree(g->lam);
+  if (g->key) hipFree(g->key);
+  if (g->lkey) hipFree(g->lkey);
+  if (g->idx) hipFree(g->idx);
+  if (g->lidx) hipFree(g->lidx);
+  if (g->ctl) hipFree(g->ctl);
+  *g = GfWork();
+}
+
+static int gf_alloc(GfWork *g, int w, int h, int mindist, int win) {
+  if (w < 1 || h < 1 || mindist < 1 || win < 0) return fail(ICTR_ERR_INVALID, "good_features: needs mindist >= 1 and win >= 0");
+  if ((int64_t)w * h > (int64_t)1 << 30) return fail(ICTR_ERR_INVALID, "good_features: the image is too large");
+  if (gf_lds_bytes(win) > kGfMaxLds)
+    return fail(ICTR_ERR_INVALID, "good_features: win = %d needs more than 64 KiB of LDS per tile (win <= 8)", win);
+  g->w = w;
+  g->h = h;
+  g->mindist = mindist;
+  g->win = win;
+  g->ncx = (w + mindist - 1) / mindist;
+  g->ncells = g->ncx * ((h + mindist - 1) / mindist);
+  const size_t nc = (size_t)g->ncells;
+  HIPCHK(hipMalloc((void **)&g->lam, sizeof(double) * (size_t)w * h));
+  HIPCHK(hipMalloc((void **)&g->key, sizeof(unsigned long long) * nc));
+  HIPCHK(hipMalloc((void **)&g->lkey, sizeof(unsigned long long) * nc));
+  HIPCHK(hipMalloc((void **)&g->idx, sizeof(int) * nc));
+  HIPCHK(hipMalloc((void **)&g->lidx, sizeof(int) * nc));
+  HIPCHK(hipMalloc((void **)&g->ctl, sizeof(GfCtl)));
+  return ICTR_OK;
+}
+
+// corners of the plane img (stride floats per row) -> out[maxcorners][2] (rows past the count are left as they are) and
+// *count, both in device memory
+static int gf_run(const GfWork &g, const float *img, int stride, int maxcorners, double quality, float *out, int *count,
+                  hipStream_t s) {
+  HIPCHK(hipMemsetAsync(g.ctl, 0, sizeof(GfCtl), s));
+  const dim3 tiles((g.w + kGfTW - 1) / kGfTW, (g.h + kGfTH - 1) / kGfTH);
+  hipLaunchKernelGGL(k_gf_response, tiles, dim3(kBlock), gf_lds_bytes(g.win), s, img, stride, g.w, g.h, g.win, g.mindist, g.lam,
+                     g.ctl);
+  const dim3 cg((g.ncells + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(k_gf_cells, cg, dim3(kBlock), 0, s, g.lam, g.w, g.h, g.mindist, quality, g.ctl, g.ncx, g.ncells, g.key,
+                     g.idx);
+  hipLaunchKernelGGL(k_gf_select, dim3(1), dim3(kGfSelBlock), 0, s, g.key, g.ncells, maxcorners, g.ctl, count);
+  hipLaunchKernelGGL(k_gf_compact, cg, dim3(kBlock), 0, s, g.key, g.idx, g.ncells, g.ctl, g.lkey, g.lidx);
+  const int rg = std::max(1, std::min((std::min(g.ncells, maxcorners) + kBlock - 1) / kBlock, 256));
+  hipLaunchKernelGGL(k_gf_rank, dim3(rg), dim3(kBlock), 0, s, g.lkey, g.lidx, g.ctl, maxcorners, g.w, out);
+  HIPCHK(hipGetLastError());
+  return ICTR_OK;
+}
+
+static int pyr_level0(const ictr_pyramid *p, const float **img, int *stride, int *w, int *h) {
+  ictr_pyramid_view v;
+  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "pyramid is NULL");
+  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
+  *stride = v.sw[0];
+  *w = v.w[0];
+  *h = v.h[0];
+  return ICTR_OK;
+}
+
+// ---------------------------------------------------------------- flow grid
+struct FgDev {
+  const float *d;  // [ny][nx][2] node displacements after the fill
+  int nx, ny, step, w, h;
+};
+
+// dense_flow's field at the integer pixel (X, Y), component c: the bilinear blend of the four surrounding nodes
+__device__ __forceinline__ void fg_value(const FgDev &g, int X, int Y, float *u, float *v) {
+  const int half = g.step / 2;
+  const double fx = fmin(fmax((double)(X - half) / (double)g.step, 0.0), (double)(g.nx - 1));
+  const double fy = fmin(fmax((double)(Y - half) / (double)g.step, 0.0), (double)(g.ny - 1));
+  const double flx = floor(fx), fly = floor(fy);
+  const int x0 = (int)flx, y0 = (int)fly;
+  const int x1 = min(x0 + 1, g.nx - 1), y1 = min(y0 + 1, g.ny - 1);
+  const double ax = fx - flx, ay = fy - fly;
+  const float2 *d = reinterpret_cast<const float2 *>(g.d);
+  const float2 a = d[y0 * g.nx + x0], b = d[y0 * g.nx + x1], c = d[y1 * g.nx + x0], e = d[y1 * g.nx + x1];
+  const double topu = (double)a.x * (1 - ax) + (double)b.x * ax, botu = (double)c.x * (1 - ax) + (double)e.x * ax;
+  const double topv = (double)a.y * (1 - ax) + (double)b.y * ax, botv = (double)c.y * (1 - ax) + (double)e.y * ax;
+  *u = (float)(topu * (1 - ay) + botu * ay);
+  *v = (float)(topv * (1 - ay) + botv * ay);
+}
+
+// func_get_transf_position(xy, F[:, :, 0], F[:, :, 1]) with F = the dense field of the grid, never formed
+__device__ __forceinline__ void fg_gather(const FgDev &g, double x, double y, double *ox, double *oy) {
+  const double flx = floor(x), fly = floor(y);
+  const double nan = __builtin_nan("");
+  *ox = nan;
+  *oy = nan;
+  // NaN / out-of-range coordinates fail the range test (written positively), like the INT_MIN cast in NumPy
+  if (flx >= 0.0 && fly >= 0.0 && flx + 1.0 < (double)g.w && fly + 1.0 < (double)g.h) {
+    const int x0 = (int)flx, y0 = (int)fly;
+    const double fx = x - flx, fy = y - fly;
+    const double w0 = fx * fy, w1 = (1 - fx) * fy, w2 = fx * (1 - fy), w3 = (1 - fx) * (1 - fy);
+    float u11, v11, u01, v01, u10, v10, u00, v00;
+    fg_value(g, x0 + 1, y0 + 1, &u11, &v11);
+    fg_value(g, x0, y0 + 1, &u01, &v01);
+    fg_value(g, x0 + 1, y0, &u10, &v10);
+    fg_value(g, x0, y0, &u00, &v00);
+    *ox = x + ((double)u11 * w0 + (double)u01 * w1 + (double)u10 * w2 + (double)u00 * w3);
+    *oy = y + ((double)v11 * w0 + (double)v01 * w1 + (double)v10 * w2 + (double)v00 * w3);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_fg_nodes(float *__restrict__ pts, int nx, int K, int step) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= K) return;
+  const int j = k / nx, i = k - j * nx;
+  pts[k] = (float)(step / 2 + i * step);
+  pts[k + K] = (float)(step / 2 + j * step);
+}
+__global__ __launch_bounds__(kBlock) void k_fg_diff(const float *__restrict__ pts, const float *__restrict__ out,
+                                                    const int *__restrict__ status, int K, float *__restrict__ draw,
+                                                    unsigned char *__restrict__ lost) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= K) return;
+  draw[2 * k] = out[k] - pts[k];
+  draw[2 * k + 1] = out[k + K] - pts[k + K];
+  lost[k] = status[k] ? 0 : 1;
+}
+// a lost node takes the nearest tracked node to its left in its row, else the nearest to its right; rowhas[y] = the row has
+// a tracked node (cleared before the launch). Nodes of a row without one are left for k_fg_colfill.
+__global__ __launch_bounds__(kBlock) void k_fg_rowfill(const float *__restrict__ draw, const unsigned char *__restrict__ lost,
+                                                       int nx, int K, float *__restrict__ d, int *__restrict__ rowhas) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= K) return;
+  const int j = k / nx, i = k - j * nx;
+  const unsigned char *lr = lost + (size_t)j * nx;
+  int src = -1;
+  for (int q = i; q >= 0 && src < 0; --q)
+    if (!lr[q]) src = q;
+  for (int q = i + 1; q < nx && src < 0; ++q)
+    if (!lr[q]) src = q;
+  if (src < 0) return;
+  d[2 * k] = draw[2 * (j * nx + src)];
+  d[2 * k + 1] = draw[2 * (j * nx + src) + 1];
+  if (src == i) rowhas[j] = 1;
+}
+// a row without a tracked node takes, node by node, the nearest row above that has one, else the nearest below, else 0
+__global__ __launch_bounds__(kBlock) void k_fg_colfill(float *__restrict__ d, const int *__restrict__ rowhas, int nx, int ny,
+                                                       int K) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= K) return;
+  const int j = k / nx, i = k - j * nx;
+  if (rowhas[j]) return;
+  int src = -1;
+  for (int q = j - 1; q >= 0 && src < 0; --q)
+    if (rowhas[q]) src = q;
+  for (int q = j + 1; q < ny && src < 0; ++q)
+    if (rowhas[q]) src = q;
+  d[2 * k] = src >= 0 ? d[2 * (src * nx + i)] : 0.0f;  // rows that have a tracked node are not written by this launch
+  d[2 * k + 1] = src >= 0 ? d[2 * (src * nx + i) + 1] : 0.0f;
+}
+__global__ __launch_bounds__(kBlock) void k_fg_gather(FgDev g, const double *__restrict__ xy, int K, double *__restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= K) return;
+  double ox, oy;
+  fg_gather(g, xy[2 * i], xy[2 * i + 1], &ox, &oy);
+  out[2 * i] = ox;
+  out[2 * i + 1] = oy;
+}
+__global__ __launch_bounds__(kBlock) void k_fg_dense(FgDev g, float2 *__restrict__ out) {
+  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (X >= g.w || Y >= g.h) return;
+  float u, v;
+  fg_value(g, X, Y, &u, &v);
+  out[(size_t)Y * g.w + X] = make_float2(u, v);
+}
+
+// ---------------------------------------------------------------- track window
+// one block slot: absmovement f64 [mc] | tracks f32 [mc][2][bsize] | count i32 (+ 4 bytes) | valid u8 [mc]
+struct PtSlot {
+  double *absmov;
+  float *tracks;
+  int *count;
+  unsigned char *valid;
+};
+struct PtGeom {
+  int mc, bsize;
+  size_t off_tracks, off_count, off_valid, bytes;
+};
+static PtGeom pt_geom(int mc, int bsize) {
+  PtGeom g;
+  g.mc = mc;
+  g.bsize = bsize;
+  g.off_tracks = sizeof(double) * (size_t)mc;
+  g.off_count = g.off_tracks + sizeof(float) * 2 * (size_t)mc * bsize;
+  g.off_valid = g.off_count + 8;
+  g.bytes = (g.off_valid + (size_t)mc + 15) / 16 * 16;
+  return g;
+}
+template <typename B>
+static PtSlot pt_slot(B *base, const PtGeom &g) {
+  char *p = (char *)base;
+  return PtSlot{reinterpret_cast<double *>(p), reinterpret_cast<float *>(p + g.off_tracks),
+                reinterpret_cast<int *>(p + g.off_count), reinterpret_cast<unsigned char *>(p + g.off_valid)};
+}
+
+// a new block: column 0 = the corners (already written to tracks[i][.][0]'s staging `corners`), every other column NaN
+__global__ __launch_bounds__(kBlock) void k_pt_open(PtSlot s, const float *__restrict__ corners, int mc, int bsize) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= mc) return;
+  const bool have = i < *s.count;
+  const float nanv = __int_as_float(0x7fc00000);
+  float *t = s.tracks + (size_t)i * 2 * bsize;
+  for (int c = 0; c < 2 * bsize; ++c) t[c] = nanv;
+  if (have) {
+    t[0] = corners[2 * i];
+    t[bsize] = corners[2 * i + 1];
+  }
+  s.valid[i] = have ? 1 : 0;
+  s.absmov[i] = 0.0;
+}
+
+// oftrack.addframe for the live points of one block: column col -> col + 1
+__global__ __launch_bounds__(kBlock) void k_pt_advance(PtSlot s, int bsize, int col, FgDev fw, FgDev bw, double th_ratio,
+                                                       double th_abs) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= *s.count || !s.valid[i]) return;
+  float *t = s.tracks + (size_t)i * 2 * bsize;
+  const double xl = (double)t[col], yl = (double)t[bsize + col];
+  double xf, yf, xb, yb;
+  fg_gather(fw, xl, yl, &xf, &yf);
+  fg_gather(bw, xf, yf, &xb, &yb);
+  const double ex = xl - xb, ey = yl - yb;
+  const double fb = sqrt(ex * ex + ey * ey);
+  const double mx = xl - xf, my = yl - yf;
+  const double mv = sqrt(mx * mx + my * my);
+  const bool ok = (fb / mv < th_ratio) & (fb < th_abs);  // NaN compares false
+  if (!ok) xf = yf = __builtin_nan("");
+  t[col + 1] = (float)xf;
+  t[bsize + col + 1] = (float)yf;
+  const double ax = (double)t[0] - xf, ay = (double)t[bsize] - yf;
+  s.absmov[i] = sqrt(ax * ax + ay * ay);
+  s.valid[i] = ((xf == xf) | (yf == yf)) ? 1 : 0;
+}
+
+}  // namespace ictr
+
+using namespace ictr;
+
+// ================================================================ C-ABI
+extern "C" int ictr_good_features(const ictr_pyramid *pyr, const float *img, int w, int h, int maxcorners, double quality,
+                                  int mindist, int win, float *out_xy, int *out_count) {
+  if ((!pyr && !img) || maxcorners < 1 || !out_count || !out_xy)
+    return fail(ICTR_ERR_INVALID, "good_features: bad arguments (a pyramid or an image, maxcorners >= 1)");
+  if (int rc = need_device()) return rc;
+  const float *plane = nullptr;
+  int stride = w;
+  float *stage = nullptr;
+  if (pyr) {
+    if (int rc = pyr_level0(pyr, &plane, &stride, &w, &h)) return rc;
+  } else if (w < 1 || h < 1) {
+    return fail(ICTR_ERR_INVALID, "good_features: bad image size");
+  }
+  GfWork g;
+  int rc = gf_alloc(&g, w, h, mindist, win);
+  float *d_out = nullptr;
+  hipError_t e = hipSuccess;
+  if (!rc && !pyr) {
+    e = hipMalloc((void **)&stage, sizeof(float) * (size_t)w * h);
+    if (e == hipSuccess) e = hipMemcpy(stage, img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice);
+    plane = stage;
+  }
+  if (!rc && e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(float) * 2 * (size_t)maxcorners + sizeof(int));
+  if (!rc && e == hipSuccess) {
+    int *d_count = reinterpret_cast<int *>(d_out + 2 * (size_t)maxcorners);
+    rc = gf_run(g, plane, stride, maxcorners, quality, d_out, d_count, nullptr);
+    if (!rc) e = hipMemcpy(out_count, d_count, sizeof(int), hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && *out_count > 0)
+      e = hipMemcpy(out_xy, d_out, sizeof(float) * 2 * (size_t)*out_count, hipMemcpyDeviceToHost);
+  }
+  if (stage) hipFree(stage);
+  if (d_out) hipFree(d_out);
+  gf_free(&g);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "good_features failed: %s", hipGetErrorString(e));
+  return ICTR_OK;
+}
+
+struct ictr_flowgrid {
+  int w = 0, h = 0, step = 0, nx = 0, ny = 0, K = 0;
+  int filled = 0;  // d holds a field
+  float *pts = nullptr, *out = nullptr, *draw = nullptr, *d = nullptr;
+  int *status = nullptr, *iters = nullptr, *rowhas = nullptr;
+  unsigned char *lost = nullptr;
+  char *arena = nullptr;
+};
+static FgDev fg_dev(const ictr_flowgrid *g) { return FgDev{g->d, g->nx, g->ny, g->step, g->w, g->h}; }
+
+extern "C" void ictr_flowgrid_destroy(ictr_flowgrid *g) {
+  if (!g) return;
+  if (g->arena) hipFree(g->arena);
+  delete g;
+}
+extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step) {
+  if (!out || w < 1 || h < 1 || step < 1 || step / 2 >= w || step / 2 >= h)
+    return fail(ICTR_ERR_INVALID, "flowgrid: bad arguments (the grid needs at least one node)");
+  if (int rc = need_device()) return rc;
+  ictr_flowgrid *g = new ictr_flowgrid;
+  g->w = w;
+  g->h = h;
+  g->step = step;
+  g->nx = (w - step / 2 + step - 1) / step;
+  g->ny = (h - step / 2 + step - 1) / step;
+  g->K = g->nx * g->ny;
+  const size_t K = (size_t)g->K;
+  // pts 2K f32 | out 2K | draw 2K | d 2K | status K i32 | iters K | rowhas ny | lost K u8
+  const size_t bytes = 4 * (8 * K + 2 * K + (size_t)g->ny) + K;
+  hipError_t e = hipMalloc((void **)&g->arena, bytes);
+  if (e != hipSuccess) {
+    delete g;
+    return fail(ICTR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  }
+  float *f = reinterpret_cast<float *>(g->arena);
+  g->pts = f;
+  g->out = f + 2 * K;
+  g->draw = f + 4 * K;
+  g->d = f + 6 * K;
+  g->status = reinterpret_cast<int *>(f + 8 * K);
+  g->iters = g->status + K;
+  g->rowhas = g->iters + K;
+  g->lost = reinterpret_cast<unsigned char *>(g->rowhas + g->ny);
+  *out = g;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_dims(const ictr_flowgrid *g, int *nx, int *ny) {
+  if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  if (nx) *nx = g->nx;
+  if (ny) *ny = g->ny;
+  return ICTR_OK;
+}
+// draw + lost -> d
+static int fg_fill(ictr_flowgrid *g, hipStream_t s) {
+  const dim3 grid((g->K + kBlock - 1) / kBlock), blk(kBlock);
+  HIPCHK(hipMemsetAsync(g->rowhas, 0, sizeof(int) * (size_t)g->ny, s));
+  hipLaunchKernelGGL(k_fg_rowfill, grid, blk, 0, s, g->draw, g->lost, g->nx, g->K, g->d, g->rowhas);
+  hipLaunchKernelGGL(k_fg_colfill, grid, blk, 0, s, g->d, g->rowhas, g->nx, g->ny, g->K);
+  HIPCHK(hipGetLastError());
+  g->filled = 1;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f,
+                                     int maxiter, float eps, void *hip_stream) {
+  if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  PFArgs a;
+  if (int rc = patchflow_args(pa, pb, psz, lv_f, 0, maxiter, eps, &a)) return rc;
+  if ((int)a.lv[0].swo != g->w || (int)a.lv[0].sho != g->h)
+    return fail(ICTR_ERR_INVALID, "flowgrid: the pyramids are not %d x %d", g->w, g->h);
+  hipStream_t s = (hipStream_t)hip_stream;
+  a.K = g->K;
+  a.pts = g->pts;
+  a.out = g->out;
+  a.status = g->status;
+  a.iters = g->iters;
+  const dim3 grid((g->K + kBlock - 1) / kBlock), blk(kBlock);
+  hipLaunchKernelGGL(k_fg_nodes, grid, blk, 0, s, g->pts, g->nx, g->K, g->step);
+  launch_patchflow(a, s);
+  hipLaunchKernelGGL(k_fg_diff, grid, blk, 0, s, g->pts, g->out, g->status, g->K, g->draw, g->lost);
+  return fg_fill(g, s);
+}
+extern "C" int ictr_flowgrid_set_nodes(ictr_flowgrid *g, const float *d, const unsigned char *lost) {
+  if (!g || !d || !lost) return fail(ICTR_ERR_INVALID, "flowgrid_set_nodes: NULL argument");
+  HIPCHK(hipMemcpy(g->draw, d, sizeof(float) * 2 * (size_t)g->K, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g->lost, lost, (size_t)g->K, hipMemcpyHostToDevice));
+  if (int rc = fg_fill(g, nullptr)) return rc;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_nodes(const ictr_flowgrid *g, float *d, unsigned char *lost) {
+  if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
+  HIPCHK(hipDeviceSynchronize());
+  if (d) HIPCHK(hipMemcpy(d, g->d, sizeof(float) * 2 * (size_t)g->K, hipMemcpyDeviceToHost));
+  if (lost) HIPCHK(hipMemcpy(lost, g->lost, (size_t)g->K, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_gather(const ictr_flowgrid *g, const double *xy, int64_t K, double *out) {
+  if (!g || K < 0 || (K > 0 && (!xy || !out)) || K > INT32_MAX) return fail(ICTR_ERR_INVALID, "flowgrid_gather: bad arguments");
+  if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
+  if (K == 0) return ICTR_OK;
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, sizeof(double) * 4 * (size_t)K));
+  hipError_t e = hipDeviceSynchronize();  // a compute on another stream has finished
+  if (e == hipSuccess) e = hipMemcpy(d, xy, sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_fg_gather, dim3(((int)K + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, fg_dev(g), d, (int)K,
+                       d + 2 * K);
+    e = hipMemcpy(out, d + 2 * K, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost);
+  }
+  hipFree(d);
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "flowgrid_gather failed: %s", hipGetErrorString(e));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_dense(const ictr_flowgrid *g, float *out, int on_device) {
+  if (!g || !out) return fail(ICTR_ERR_INVALID, "flowgrid_dense: NULL argument");
+  if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
+  const size_t bytes = sizeof(float) * 2 * (size_t)g->w * g->h;
+  float *d = out;
+  if (!on_device) HIPCHK(hipMalloc((void **)&d, bytes));
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_fg_dense, dim3((g->w + 63) / 64, (g->h + kWaves - 1) / kWaves), dim3(kBlock), 0, nullptr, fg_dev(g),
+                       reinterpret_cast<float2 *>(d));
+    e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+  }
+  if (!on_device) hipFree(d);
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "flowgrid_dense failed: %s", hipGetErrorString(e));
+  return ICTR_OK;
+}
+
+struct ictr_pointtrack {
+  int w = 0, h = 0, bsize = 0, mc = 0, lv_f = 0, psz = 0, step = 0, maxiter = 0, mindist = 0, win = 0;
+  float eps = 0;
+  double quality = 0, th_ratio = 0, th_abs = 0;
+  int64_t nframes = 0;          // frames pushed; frcounter = max(nframes - 1, 0)
+  ictr_pyramid *pyr[2] = {nullptr, nullptr};
+  ictr_flowgrid *fw = nullptr, *bw = nullptr;
+  GfWork gf;
+  PtGeom geom;
+  char *ring = nullptr;        // bsize slots
+  float *corners = nullptr;    // [mc][2] staging of the corner picker
+  std::vector<void *> store;   // pinned host copies of the blocks that left the window, in block order
+};
+
+extern "C" void ictr_pointtrack_destroy(ictr_pointtrack *t) {
+  if (!t) return;
+  (void)hipDeviceSynchronize();
+  for (void *p : t->store) hipHostFree(p);
+  ictr_pyramid_destroy(t->pyr[0]);
+  ictr_pyramid_destroy(t->pyr[1]);
+  ictr_flowgrid_destroy(t->fw);
+  ictr_flowgrid_destroy(t->bw);
+  gf_free(&t->gf);
+  if (t->ring) hipFree(t->ring);
+  if (t->corners) hipFree(t->corners);
+  delete t;
+}
+extern "C" int ictr_pointtrack_create(ictr_pointtrack **out, int w, int h, int bsize, int maxcorners, int lv_f, int psz,
+                                      int step, int maxiter, float eps, double quality, int mindist, int win,
+                                      double th_ratio, double th_abs) {
+  if (!out || bsize < 1 || maxcorners < 1 || psz < 1 || psz > 32 || lv_f < 0 || lv_f > 15 || maxiter < 0)
+    return fail(ICTR_ERR_INVALID, "pointtrack: bad arguments (bsize >= 1, maxcorners >= 1, psz 1..32)");
+  if (int rc = need_device()) return rc;
+  ictr_pointtrack *t = new ictr_pointtrack;
+  t->w = w, t->h = h, t->bsize = bsize, t->mc = maxcorners, t->lv_f = lv_f, t->psz = psz, t->step = step;
+  t->maxiter = maxiter, t->eps = eps, t->quality = quality, t->mindist = mindist, t->win = win;
+  t->th_ratio = th_ratio, t->th_abs = th_abs;
+  t->geom = pt_geom(maxcorners, bsize);
+  int rc = ictr_flowgrid_create(&t->fw, w, h, step);
+  if (!rc) rc = ictr_flowgrid_create(&t->bw, w, h, step);
+  if (!rc) rc = gf_alloc(&t->gf, w, h, mindist, win);
+  if (!rc) {
+    hipError_t e = hipMalloc((void **)&t->ring, t->geom.bytes * (size_t)bsize);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->corners, sizeof(float) * 2 * (size_t)maxcorners);
+    if (e == hipSuccess) e = hipMemset(t->ring, 0, t->geom.bytes * (size_t)bsize);
+    if (e != hipSuccess) rc = fail(ICTR_ERR_HIP, "pointtrack: allocation failed: %s", hipGetErrorString(e));
+  }
+  if (rc) {
+    ictr_pointtrack_destroy(t);
+    return rc;
+  }
+  *out = t;
+  return ICTR_OK;
+}
+extern "C" int ictr_pointtrack_push_frame(ictr_pointtrack *t, const float *img) {
+  if (!t || !img) return fail(ICTR_ERR_INVALID, "pointtrack_push_frame: NULL argument");
+  hipStream_t s = nullptr;
+  const int64_t f = t->nframes;
+  ictr_pyramid *&cur = t->pyr[f & 1];
+  if (!cur) {  // the first two frames allocate their pyramids
+    if (int rc = ictr_pyramid_create(&cur, img, t->w, t->h, t->lv_f, 1, t->psz)) return rc;
+  } else if (int rc = ictr_pyramid_rebuild(cur, img, s)) {
+    return rc;
+  }
+  t->nframes = f + 1;
+  if (f == 0) return ICTR_OK;
+  const int64_t k = f - 1;  // the pair (k, k + 1); addframe number k + 1
+  ictr_pyramid *pa = t->pyr[k & 1], *pb = cur;
+  if (int rc = ictr_flowgrid_compute(t->fw, pa, pb, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
+  if (int rc = ictr_flowgrid_compute(t->bw, pb, pa, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
+  const float *plane;
+  int stride, w, h;
+  if (int rc = pyr_level0(pa, &plane, &stride, &w, &h)) return rc;
+  const PtGeom &g = t->geom;
+  const dim3 grid((g.mc + kBlock - 1) / kBlock), blk(kBlock);
+  const PtSlot open = pt_slot(t->ring + g.bytes * (size_t)(k % g.bsize), g);
+  if (int rc = gf_run(t->gf, plane, stride, g.mc, t->quality, t->corners, open.count, s)) return rc;
+  hipLaunchKernelGGL(k_pt_open, grid, blk, 0, s, open, t->corners, g.mc, g.bsize);
+  for (int age = 0; age <= g.bsize - 2 && age <= k; ++age) {  // the blocks k - age, column age -> age + 1
+    const PtSlot sl = pt_slot(t->ring + g.bytes * (size_t)((k - age) % g.bsize), g);
+    hipLaunchKernelGGL(k_pt_advance, grid, blk, 0, s, sl, g.bsize, age, fg_dev(t->fw), fg_dev(t->bw), t->th_ratio, t->th_abs);
+  }
+  HIPCHK(hipGetLastError());
+  const int64_t gone = k - g.bsize + 1;  // leaves the window with this pair; its slot is opened again by pair k + 1
+  if (gone >= 0) {
+    void *hp = nullptr;
+    HIPCHK(hipHostMalloc(&hp, g.bytes, hipHostMallocDefault));
+    t->store.push_back(hp);
+    HIPCHK(hipMemcpyAsync(hp, t->ring + g.bytes * (size_t)(gone % g.bsize), g.bytes, hipMemcpyDeviceToHost, s));
+  }
+  return ICTR_OK;
+}
+extern "C" int ictr_pointtrack_frcounter(const ictr_pointtrack *t, int64_t *frcounter) {
+  if (!t || !frcounter) return fail(ICTR_ERR_INVALID, "pointtrack_frcounter: NULL argument");
+  *frcounter = t->nframes > 0 ? t->nframes - 1 : 0;
+  return ICTR_OK;
+}
+extern "C" int ictr_pointtrack_read_block(ictr_pointtrack *t, int64_t block, float *tracks, unsigned char *valid,
+                                          double *absmovement, int *count) {
+  if (!t || !count) return fail(ICTR_ERR_INVALID, "pointtrack_read_block: NULL argument");
+  const int64_t frc = t->nframes > 0 ? t->nframes - 1 : 0;
+  if (block < 0 || block >= frc) return fail(ICTR_ERR_INVALID, "pointtrack_read_block: no such block");
+  const PtGeom &g = t->geom;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  std::vector<char> tmp;
+  const char *src;
+  if (block < (int64_t)t->store.size()) {
+    src = (const char *)t->store[(size_t)block];
+  } else {
+    tmp.resize(g.bytes);
+    HIPCHK(hipMemcpy(tmp.data(), t->ring + g.bytes * (size_t)(block % g.bsize), g.bytes, hipMemcpyDeviceToHost));
+    src = tmp.data();
+  }
+  const PtSlot sl = pt_slot(src, g);
+  const int n = *sl.count;
+  *count = n;
+  if (tracks) memcpy(tracks, sl.tracks, sizeof(float) * 2 * (size_t)g.bsize * n);
+  if (valid) memcpy(valid, sl.valid, (size_t)n);
+  if (absmovement) memcpy(absmovement, sl.absmov, sizeof(double) * (size_t)n);
+  return ICTR_OK;
+}

@@ -2057,9 +2057,12 @@ extern "C" int ictr_odometer_get_norm(const ictr_odometer *o, double *meanshift3
 // ---------------------------------------------------------------- per-patch translation IC-LK (flow producer)
 static thread_local float g_pf_ms = -1.0f;
 extern "C" float ictr_patchflow_last_kernel_ms(void) { return g_pf_ms; }
-extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
-                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
-  if (!pa || !pb || K < 0 || (K > 0 && (!pts || !out)) || psz < 1 || psz > 32 || lv_l < 0 || lv_f < lv_l || maxiter < 0)
+// the argument checks of a patch tracking and the level table of its launch (a.pts / out / status / iters and a.K are the
+// caller's): shared by ictr_patchflow and the flow grid of ictr_frontend.hip, so that both launch the same kernel on the
+// same arguments
+int ictr::patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
+                         PFArgs *out) {
+  if (!pa || !pb || psz < 1 || psz > 32 || lv_l < 0 || lv_f < lv_l || maxiter < 0)
     return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
   if (lv_f >= pa->nlev || lv_f >= pb->nlev || lv_f > 15)
     return fail(ICTR_ERR_INVALID, "patchflow: pyramids have fewer than lv_f+1 levels");
@@ -2068,9 +2071,7 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
   for (int l = lv_l; l <= lv_f; ++l)
     if (pa->w[l] != pb->w[l] || pa->h[l] != pb->h[l] || pa->sw[l] != pb->sw[l])
       return fail(ICTR_ERR_INVALID, "patchflow: the two pyramids differ in size at level %d", l);
-  if (K == 0) return ICTR_OK;
-  if (int rc = need_device()) return rc;
-  PFArgs a;
+  PFArgs &a = *out;
   memset(&a, 0, sizeof(a));
   for (int l = lv_l; l <= lv_f; ++l) {
     a.lv[l].a = pa->img[l];
@@ -2086,9 +2087,18 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
   a.lv_l = lv_l;
   a.P = psz;
   a.maxiter = maxiter;
-  a.K = (int)K;
   a.eps2 = eps * eps;
   a.min_det = 1e-4f;
+  return ICTR_OK;
+}
+extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
+                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
+  if (K < 0 || (K > 0 && (!pts || !out))) return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
+  PFArgs a;
+  if (int rc = patchflow_args(pa, pb, psz, lv_f, lv_l, maxiter, eps, &a)) return rc;
+  if (K == 0) return ICTR_OK;
+  if (int rc = need_device()) return rc;
+  a.K = (int)K;
   float *d = nullptr;
   HIPCHK(hipMalloc((void **)&d, sizeof(float) * 6 * K));
   float *d_pts = d, *d_out = d + 2 * K;

@@ -153,5 +153,8 @@ void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s);
 void launch_ransac_finish(const RansacArgs &a, hipStream_t s);
 // per-patch translation IC-LK, all levels, a.K points
 void launch_patchflow(const PFArgs &a, hipStream_t s);
+// ictr_host.hip: the argument checks of a patch tracking and its level table; the point buffers and a->K stay the caller's
+int patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
+                   PFArgs *a);
 
 }  // namespace ictr

@@ -6,6 +6,10 @@ which is not part of the reference. This module replaces it with the in-tree HIP
 per-patch translation inverse-compositional Lucas-Kanade, pyramidal, one wave64 per patch) and re-creates the
 notebook's loop: corners -> forward / backward flow -> ``oftrack.addframe`` -> ``savetofile``.
 
+The loop exists twice: ``run_OF_point_track`` (corners, fill, up-sampling and ``addframe`` in NumPy on the host) and
+``run_OF_point_track_hip`` (``good_features_hip``, ``FlowGrid``, ``PointTracker``: the same stages in ictr_frontend.hip,
+bit for bit the same tracks, nothing but the frames crossing the bus per pair).
+
 Build-defined (no reference implementation exists to pin it): oracle = ``oracle/np_patchflow.py``.
 """
 from __future__ import annotations
@@ -19,7 +23,8 @@ from ._lib import check, fp
 from .classoftrack import oftrack
 from .tracker import Pyramid
 
-__all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms"]
+__all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms",
+           "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
 
 
 def last_kernel_ms():
@@ -161,6 +166,163 @@ def run_OF_point_track(frames, bsize=10, psz=15, lv_f=3, step=4, maxcorners=1000
         of_back = dense_flow(pyrs[k + 1], pyrs[k], step=step, psz=psz, lv_f=lv_f)
         corners = good_features(frames[k], maxcorners, 0.001, 5)
         tracker.addframe(of_forw, of_back, corners if len(corners) else None)
+    if savefile is not None:
+        tracker.savetofile(savefile)
+    return tracker
+
+
+# ---------------------------------------------------------------- the same stages on the device (ictr_frontend.hip)
+def good_features_hip(img, maxcorners=1000, quality=0.001, mindist=5, win=3):
+    """good_features on the device (``ictr_good_features``): same arguments, same (K,2) float32 result in the same order.
+    img: a host image, or a Pyramid whose level 0 is the image. The host function sums its windows through an integral
+    image, the device sums them directly; the two agree wherever the integral image is exact (integer-valued frames).
+    No CPU fallback: raises IctrError without a GPU."""
+    out = np.empty((int(maxcorners), 2), np.float32)
+    n = C.c_int(0)
+    L = _lib.load()
+    if isinstance(img, Pyramid):
+        check(L.ictr_good_features(img._h, None, 0, 0, int(maxcorners), float(quality), int(mindist), int(win), fp(out),
+                                   C.byref(n)))
+    else:
+        img = _lib.f32c(img)
+        if img.ndim != 2:
+            raise ValueError("img must be (H, W)")
+        check(L.ictr_good_features(None, fp(img), img.shape[1], img.shape[0], int(maxcorners), float(quality),
+                                   int(mindist), int(win), fp(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+class FlowGrid:
+    """One direction of one frame pair on a `step` grid (``ictr_flowgrid_*``): the node displacements of dense_flow
+    after its fill, kept on the device. ``gather`` moves points by the dense field without forming it; ``dense``
+    materialises it for callers that write .flo files."""
+
+    def __init__(self, w, h, step=4):
+        self._h = C.c_void_p()
+        check(_lib.load().ictr_flowgrid_create(C.byref(self._h), int(w), int(h), int(step)))
+        self.w, self.h, self.step = int(w), int(h), int(step)
+        nx, ny = C.c_int(), C.c_int()
+        check(_lib.load().ictr_flowgrid_dims(self._h, C.byref(nx), C.byref(ny)))
+        self.nx, self.ny = nx.value, ny.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_flowgrid_destroy(self._h)
+            self._h = None
+
+    def compute(self, pyr_a, pyr_b, psz=15, lv_f=None, maxiter=10, eps=0.01, stream=None):
+        """Track the nodes A -> B (k_patchflow), d = out - pts, fill the lost nodes. Enqueued, no host wait."""
+        lv_f = pyr_a.lv_f if lv_f is None else lv_f
+        check(_lib.load().ictr_flowgrid_compute(self._h, pyr_a._h, pyr_b._h, int(psz), int(lv_f), int(maxiter),
+                                                float(eps), C.c_void_p(stream or 0)))
+        return self
+
+    def set_nodes(self, d, lost):
+        """Inject node displacements d (ny, nx, 2) and the lost mask (ny, nx); the fill runs on them."""
+        d = _lib.f32c(d)
+        lost = np.ascontiguousarray(lost, np.uint8)
+        if d.shape != (self.ny, self.nx, 2) or lost.shape != (self.ny, self.nx):
+            raise ValueError(f"set_nodes needs d ({self.ny}, {self.nx}, 2) and lost ({self.ny}, {self.nx})")
+        check(_lib.load().ictr_flowgrid_set_nodes(self._h, fp(d), lost.ctypes.data_as(_lib.U8P)))
+        return self
+
+    def nodes(self):
+        """(d after the fill (ny, nx, 2) float32, lost mask (ny, nx) bool)."""
+        d = np.empty((self.ny, self.nx, 2), np.float32)
+        lost = np.empty((self.ny, self.nx), np.uint8)
+        check(_lib.load().ictr_flowgrid_nodes(self._h, fp(d), lost.ctypes.data_as(_lib.U8P)))
+        return d, lost.astype(bool)
+
+    def gather(self, xy):
+        """func_get_transf_position(xy, F[:, :, 0], F[:, :, 1]) with F = dense(), bit for bit, without forming F."""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        out = np.empty_like(xy)
+        check(_lib.load().ictr_flowgrid_gather(self._h, _lib.dp(xy), xy.shape[0], _lib.dp(out)))
+        return out
+
+    def dense(self, out=None, on_device=False):
+        """The (H, W, 2) float32 field of dense_flow. on_device: `out` is a device pointer that receives it."""
+        if on_device:
+            check(_lib.load().ictr_flowgrid_dense(self._h, C.c_void_p(out), 1))
+            return out
+        if out is None:
+            out = np.empty((self.h, self.w, 2), np.float32)
+        check(_lib.load().ictr_flowgrid_dense(self._h, out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+
+class PointTracker:
+    """The loop of run_OF_point_track on the device (``ictr_pointtrack_*``): push the frames one by one, read the
+    oftrack object back when it is wanted. Device memory is a ring of bsize block slots; blocks that left the window
+    wait in a host store of the object."""
+
+    def __init__(self, w, h, bsize=10, maxcorners=1000, lv_f=3, psz=15, step=4, maxiter=10, eps=0.01, quality=0.001,
+                 mindist=5, win=3, th_flowvalid_ratio=0.2, th_flowvalid_abs=1.0):
+        self._h = C.c_void_p()
+        check(_lib.load().ictr_pointtrack_create(C.byref(self._h), int(w), int(h), int(bsize), int(maxcorners), int(lv_f),
+                                                 int(psz), int(step), int(maxiter), float(eps), float(quality),
+                                                 int(mindist), int(win), float(th_flowvalid_ratio),
+                                                 float(th_flowvalid_abs)))
+        self.w, self.h, self.bsize, self.maxcorners = int(w), int(h), int(bsize), int(maxcorners)
+        self.th_flowvalid_ratio, self.th_flowvalid_abs = th_flowvalid_ratio, th_flowvalid_abs
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_pointtrack_destroy(self._h)
+            self._h = None
+
+    def push_frame(self, img):
+        img = _lib.f32c(img)
+        if img.shape != (self.h, self.w):
+            raise ValueError(f"push_frame needs a {self.w}x{self.h} frame, got {img.shape[1]}x{img.shape[0]}")
+        check(_lib.load().ictr_pointtrack_push_frame(self._h, fp(img)))
+
+    @property
+    def frcounter(self):
+        n = C.c_int64()
+        check(_lib.load().ictr_pointtrack_frcounter(self._h, C.byref(n)))
+        return int(n.value)
+
+    def read_block(self, b):
+        """Block b as addframe holds it before compaction: (tracks (K,2,bsize) f32, valid (K,) bool, absmovement (K,)
+        f64), K = its corner count (0: the frame had no corner)."""
+        tr = np.empty((self.maxcorners, 2, self.bsize), np.float32)
+        va = np.empty(self.maxcorners, np.uint8)
+        am = np.empty(self.maxcorners, np.float64)
+        n = C.c_int()
+        check(_lib.load().ictr_pointtrack_read_block(self._h, int(b), fp(tr), va.ctypes.data_as(_lib.U8P), _lib.dp(am),
+                                                     C.byref(n)))
+        k = n.value
+        return tr[:k].copy(), va[:k].astype(bool), am[:k].copy()
+
+    def tracks(self):
+        """The oftrack object that run_OF_point_track would hold now: tracks, tracks_valid, tracks_absmovement,
+        frcounter; blocks that left the window compacted, frames without corners as None."""
+        o = oftrack(self.bsize, self.w, self.h, self.th_flowvalid_ratio, self.th_flowvalid_abs)
+        o.frcounter = self.frcounter
+        for b in range(o.frcounter):
+            tr, va, am = self.read_block(b)
+            if len(tr) == 0:
+                tr = va = am = None
+            elif b <= o.frcounter - self.bsize:
+                live = np.nonzero(va)[0]
+                tr, va, am = tr[live], np.ones(len(live), bool), am[live]
+            o.tracks.append(tr)
+            o.tracks_valid.append(va)
+            o.tracks_absmovement.append(am)
+        return o
+
+
+def run_OF_point_track_hip(frames, bsize=10, psz=15, lv_f=3, step=4, maxcorners=1000, th_flowvalid_ratio=0.2,
+                           th_flowvalid_abs=1.0, savefile=None):
+    """run_OF_point_track with every stage on the device (PointTracker): same parameters, the same oftrack object bit
+    for bit on integer-valued frames (where the host corner picker's integral image is exact)."""
+    h, w = np.asarray(frames[0]).shape
+    pt = PointTracker(w, h, bsize, maxcorners, lv_f, psz, step, 10, 0.01, 0.001, 5, 3, th_flowvalid_ratio,
+                      th_flowvalid_abs)
+    for f in frames:
+        pt.push_frame(f)
+    tracker = pt.tracks()
     if savefile is not None:
         tracker.savetofile(savefile)
     return tracker
