@@ -381,6 +381,10 @@ int ictr_patchflow(const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, const f
                    int lv_l, int maxiter, float eps, float *out, int *status, int *iters);
 /* duration in ms of the k_patchflow launch of this thread's last ictr_patchflow call (HIP events), < 0 if unknown */
 float ictr_patchflow_last_kernel_ms(void);
+/* kernel form of this thread's last k_patchflow launch (ictr_patchflow or a flow grid): pixels per lane * 10 + waves per
+ * patch, one of 11, 41, 161, 82; 0 before the first launch. ICTR_PF_WPP=1 / 2 (read once per process) forces one / two
+ * waves per patch; unset, patches of more than 256 pixels take two. */
+int ictr_patchflow_last_form(void);
 
 /* ------------------------------------------------------------------ full-frame parametric alignment (extension)
  * Inverse-compositional Gauss-Newton alignment of a whole template region under one parametric warp:

@@ -178,6 +178,7 @@ SIGNATURES = {
     "ictr_batch_set_peer_exchange": (C.c_int, [VP, VP]),
     "ictr_patchflow": (C.c_int, [VP, VP, FP, I64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, FP, IP, IP]),
     "ictr_patchflow_last_kernel_ms": (C.c_float, []),
+    "ictr_patchflow_last_form": (C.c_int, []),
     "ictr_icgn_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, IP,
                                    I64]),
     "ictr_icgn_destroy": (None, [VP]),

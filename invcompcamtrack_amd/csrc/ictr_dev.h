@@ -170,6 +170,7 @@ struct RansacArgs {
 struct PFLevel {
   const float *a, *ax, *ay, *b;  // frame A image + gradients, frame B image (padded planes)
   int sw;
+  int shift;  // (pad - P) * (sw + 1): pf_taps' base is the patch's corner in a plane padded by exactly P
   float swo, sho, scale;  // unpadded size, 0.5^level
 };
 struct PFArgs {

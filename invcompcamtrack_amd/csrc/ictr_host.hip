@@ -2057,6 +2057,7 @@ extern "C" int ictr_odometer_get_norm(const ictr_odometer *o, double *meanshift3
 // ---------------------------------------------------------------- per-patch translation IC-LK (flow producer)
 static thread_local float g_pf_ms = -1.0f;
 extern "C" float ictr_patchflow_last_kernel_ms(void) { return g_pf_ms; }
+extern "C" int ictr_patchflow_last_form(void) { return patchflow_last_form(); }
 // the argument checks of a patch tracking and the level table of its launch (a.pts / out / status / iters and a.K are the
 // caller's): shared by ictr_patchflow and the flow grid of ictr_frontend.hip, so that both launch the same kernel on the
 // same arguments
@@ -2079,6 +2080,7 @@ int ictr::patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz
     a.lv[l].ay = pa->dy[l];
     a.lv[l].b = pb->img[l];
     a.lv[l].sw = pa->sw[l];
+    a.lv[l].shift = (pa->pad - psz) * (pa->sw[l] + 1);
     a.lv[l].swo = (float)pa->w[l];
     a.lv[l].sho = (float)pa->h[l];
     a.lv[l].scale = (float)(1 / pow(2, l));

@@ -153,6 +153,8 @@ void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s);
 void launch_ransac_finish(const RansacArgs &a, hipStream_t s);
 // per-patch translation IC-LK, all levels, a.K points
 void launch_patchflow(const PFArgs &a, hipStream_t s);
+// NPL * 10 + WPP of this thread's last launch_patchflow (11, 41, 161 or 82), 0 before the first
+int patchflow_last_form();
 // ictr_host.hip: the argument checks of a patch tracking and its level table; the point buffers and a->K stay the caller's
 int patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
                    PFArgs *a);

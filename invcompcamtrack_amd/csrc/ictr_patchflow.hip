@@ -35,7 +35,8 @@ struct PFTaps {
   float w0, w1, w2, w3;
   int base;
 };
-__device__ __forceinline__ PFTaps pf_taps(float mx, float my, int P, int sw) {
+// shift = (pad - P) * (sw + 1): (p + P/2) is the patch's first pixel only in a plane padded by exactly P
+__device__ __forceinline__ PFTaps pf_taps(float mx, float my, int P, int sw, int shift) {
   PFTaps t;
   const int p0 = (int)ceilf(mx + .00001f), p1 = (int)ceilf(my + .00001f);
   const float r0 = mx - floorf(mx), r1 = my - floorf(my);
@@ -43,7 +44,7 @@ __device__ __forceinline__ PFTaps pf_taps(float mx, float my, int P, int sw) {
   t.w1 = (1 - r0) * r1;
   t.w2 = r0 * (1 - r1);
   t.w3 = (1 - r0) * (1 - r1);
-  t.base = (p1 + P / 2) * sw + p0 + P / 2;
+  t.base = (p1 + P / 2) * sw + p0 + P / 2 + shift;
   return t;
 }
 struct PFWin {
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void k_patchflow(PFArgs a) {
     const float xl = x0 * L.scale, yl = y0 * L.scale;
     if (ok && !pf_in_view(xl, yl, L.swo, L.sho)) ok = false;
     if (WPP == 1 && !ok) break;
-    const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw);  // (1,1): a harmless in-plane window
+    const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);  // (1,1): a harmless in-plane window
     gconst_f32 pa = (gconst_f32)L.a, pax = (gconst_f32)L.ax, pay = (gconst_f32)L.ay, pb = (gconst_f32)L.b;
     float T[NPL], Gx[NPL], Gy[NPL];
     float hxx = 0.0f, hxy = 0.0f, hyy = 0.0f;
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_patchflow(PFArgs a) {
         run = false;
         if (WPP == 1) break;
       }
-      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw);
+      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
       float bx = 0.0f, by = 0.0f, dummy = 0.0f;
       PFWin w[NPL];
 #pragma unroll
@@ -188,6 +189,9 @@ __global__ __launch_bounds__(kBlock) void k_patchflow(PFArgs a) {
   }
 }
 
+static thread_local int g_pf_form = 0;
+int patchflow_last_form() { return g_pf_form; }
+
 void launch_patchflow(const PFArgs &a, hipStream_t s) {
   const int n = a.P * a.P;
   const int npl = (n + 63) / 64;
@@ -201,10 +205,12 @@ void launch_patchflow(const PFArgs &a, hipStream_t s) {
   const bool two = wpp_env ? wpp_env == 2 : npl > 4;
   if (two) {
     const dim3 g((a.K + kWaves / 2 - 1) / (kWaves / 2));
+    g_pf_form = 82;
     hipLaunchKernelGGL((k_patchflow<8, 2>), g, blk, 0, s, a);
     return;
   }
   const dim3 g((a.K + kWaves - 1) / kWaves);
+  g_pf_form = npl <= 1 ? 11 : npl <= 4 ? 41 : 161;
   if (npl <= 1)
     hipLaunchKernelGGL((k_patchflow<1, 1>), g, blk, 0, s, a);
   else if (npl <= 4)

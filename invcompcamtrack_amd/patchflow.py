@@ -24,13 +24,19 @@ from .classoftrack import oftrack
 from .tracker import Pyramid
 
 __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms",
-           "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
+           "last_form", "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
 
 
 def last_kernel_ms():
     """Duration of the k_patchflow launch of the last track_points call (HIP events), or None."""
     ms = float(_lib.load().ictr_patchflow_last_kernel_ms())
     return ms if ms >= 0 else None
+
+
+def last_form():
+    """Kernel form of this thread's last k_patchflow launch: pixels per lane * 10 + waves per patch (11, 41, 161 or 82),
+    0 before the first. ICTR_PF_WPP=1 / 2 in the environment (read once per process) forces one / two waves per patch."""
+    return int(_lib.load().ictr_patchflow_last_form())
 
 
 def partition_patches(npatches, world):

@@ -1,0 +1,136 @@
+"""f32 NumPy restatement of k_patchflow (csrc/ictr_patchflow.hip) for test_patchflow_cpu.py: the kernel's per-pixel
+expressions in their order, every operation rounded to f32 (the build has -ffp-contract=off: no fused multiply-add), and
+a selectable summation shape. It is written from the kernel, not from oracle/np_patchflow.py, and shares no code with it.
+
+shape = (NPL, WPP): pixel q of the patch belongs to wave (q // 64) % WPP, lane q % 64, slot q // (64 WPP); a lane adds its
+slots serially from 0, the 64 lanes meet in a pairwise tree (wave_sum_dpp: 1, 2, half row, row, then (r0 + r1) + (r2 + r3)),
+the WPP wave totals are added in wave order from 0.  shape = None: one serial sum over the pixels in q order.
+
+defect (None or one of DEFECTS) injects one mistake the tests must be able to see.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+f32 = np.float32
+ONE, ZERO = f32(1), f32(0)
+DEFECTS = ("drop last column", "drop last row", "swap w1 w2", "half of P-1", "omit second wave", "rescale by lv_f")
+
+
+def _taps(x, y, P, defect):
+    x, y = f32(x), f32(y)
+    p0, p1 = int(np.ceil(f32(x + f32(.00001)))), int(np.ceil(f32(y + f32(.00001))))
+    r0, r1 = f32(x - np.floor(x)), f32(y - np.floor(y))
+    w0, w1, w2, w3 = f32(r0 * r1), f32(f32(ONE - r0) * r1), f32(r0 * f32(ONE - r1)), f32(f32(ONE - r0) * f32(ONE - r1))
+    if defect == "swap w1 w2":
+        w1, w2 = w2, w1
+    half = (P - 1) // 2 if defect == "half of P-1" else P // 2
+    return (w0, w1, w2, w3), p1 + half, p0 + half
+
+
+def _fetch(plane, taps, P):
+    """(P*P,) f32 in q order: t.w0 * (x, y) + t.w1 * (x-1, y) + t.w2 * (x, y-1) + t.w3 * (x-1, y-1), left to right."""
+    (w0, w1, w2, w3), row, col = taps
+    a = plane[row:row + P, col:col + P]
+    b = plane[row:row + P, col - 1:col - 1 + P]
+    c = plane[row - 1:row - 1 + P, col:col + P]
+    d = plane[row - 1:row - 1 + P, col - 1:col - 1 + P]
+    v = ((w0 * a + w1 * b) + w2 * c) + w3 * d
+    assert v.dtype == f32
+    return v.ravel()
+
+
+def _sum(terms, shape, defect):
+    """One patch sum of (P*P,) f32 terms in the given shape."""
+    n = len(terms)
+    if shape is None:
+        acc = ZERO
+        for t in terms:
+            acc = f32(acc + t)
+        return acc
+    npl, wpp = shape
+    assert n <= 64 * npl * wpp
+    slots = np.zeros(64 * npl * wpp, f32)
+    slots[:n] = terms
+    slots = slots.reshape(npl, wpp, 64)           # [slot i][wave][lane]: q = wave * 64 + lane + 64 * wpp * i
+    acc = np.zeros((wpp, 64), f32)
+    for i in range(npl):
+        acc = acc + slots[i]
+    for _ in range(6):
+        acc = acc[:, 0::2] + acc[:, 1::2]
+    assert acc.dtype == f32 and acc.shape == (wpp, 1)
+    if wpp == 1:
+        return acc[0, 0]
+    tot = ZERO
+    for q in range(1 if defect == "omit second wave" else wpp):
+        tot = f32(tot + acc[q, 0])
+    return tot
+
+
+def track_points(pyr_a, pyr_b, pts, psz, lv_f, lv_l=0, maxiter=10, eps=0.01, min_det=1e-4, shape=None, defect=None):
+    """The kernel's control flow for one patch after the other. pyr_*: oracle.Pyramid."""
+    pts = np.asarray(pts, f32)
+    K, P = len(pts), psz
+    out = np.full((K, 2), np.nan, f32)
+    status, iters = np.zeros(K, bool), np.zeros(K, np.int32)
+    sh = pyr_a.pad - P
+    eps2, min_det = f32(f32(eps) * f32(eps)), f32(min_det)
+    q = np.arange(P * P)
+    keep = np.ones(P * P, bool)
+    if defect == "drop last column":
+        keep = q % P != P - 1
+    elif defect == "drop last row":
+        keep = q // P != P - 1
+
+    def view(plane):
+        return plane[sh:, sh:] if sh else plane
+
+    def in_view(x, y, w, h):
+        return x >= 0 and y >= 0 and x <= w and y <= h
+
+    for k in range(K):
+        x0, y0 = pts[k]
+        ok = bool(x0 == x0 and y0 == y0)
+        px = py = ZERO
+        nit = 0
+        for l in range(lv_f, lv_l - 1, -1):
+            if not ok:
+                break
+            if l != lv_f:
+                px, py = f32(px * f32(2)), f32(py * f32(2))
+            scale = f32(1 / 2 ** l)
+            wl, hl = f32(pyr_a.img[l].shape[1] - 2 * pyr_a.pad), f32(pyr_a.img[l].shape[0] - 2 * pyr_a.pad)
+            xl, yl = f32(x0 * scale), f32(y0 * scale)
+            if not in_view(xl, yl, wl, hl):
+                ok = False
+                break
+            ta = _taps(xl, yl, P, defect)
+            T = np.where(keep, _fetch(view(pyr_a.img[l]), ta, P), ZERO)
+            Gx = np.where(keep, _fetch(view(pyr_a.dx[l]), ta, P), ZERO)
+            Gy = np.where(keep, _fetch(view(pyr_a.dy[l]), ta, P), ZERO)
+            hxx, hxy, hyy = _sum(Gx * Gx, shape, defect), _sum(Gx * Gy, shape, defect), _sum(Gy * Gy, shape, defect)
+            det = f32(f32(hxx * hyy) - f32(hxy * hxy))
+            tr = f32(hxx + hyy)
+            if not (det > f32(f32(min_det * tr) * tr)) or not (tr > 0):
+                ok = False
+                break
+            with np.errstate(over="ignore"):
+                idet = f32(ONE / det)
+            for _ in range(maxiter):
+                cx, cy = f32(xl + px), f32(yl + py)
+                if not in_view(cx, cy, wl, hl):
+                    ok = False
+                    break
+                r = np.where(keep, T - _fetch(view(pyr_b.img[l]), _taps(cx, cy, P, defect), P), ZERO)
+                bx, by = _sum(Gx * r, shape, defect), _sum(Gy * r, shape, defect)
+                dx = f32(f32(f32(hyy * bx) - f32(hxy * by)) * idet)
+                dy = f32(f32(f32(hxx * by) - f32(hxy * bx)) * idet)
+                px, py = f32(px + dx), f32(py + dy)
+                nit += 1
+                if f32(f32(dx * dx) + f32(dy * dy)) < eps2:
+                    break
+        if ok:
+            s = f32(ONE / f32(1 / 2 ** (lv_f if defect == "rescale by lv_f" else lv_l)))
+            out[k] = (f32(x0 + f32(px * s)), f32(y0 + f32(py * s)))
+        status[k], iters[k] = ok, nit
+    return out, status, iters
