@@ -1,8 +1,9 @@
-// ictr_devfn.h -- device helpers shared by the kernel translation units (ictr_kernels.hip, ictr_track1.hip):
-// bilinear tap selection (utilities.cpp:66-107), visibility (odometer.cpp:273-276), steepest-descent coefficients
-// (odometer.cpp:313-326), the per-level LU factorisation and the per-iteration solve + pose update + loop condition
-// (odometer.cpp:341-346, 407-418, 509-515; pose.cpp:116-129). Everything keeps the reference's operand order; the
-// translation units are compiled with -ffp-contract=off.
+// ictr_devfn.h -- device helpers shared by the kernel translation units (ictr_kernels.hip, ictr_track1.hip,
+// ictr_resident.hip): bilinear tap selection (utilities.cpp:66-107), visibility (odometer.cpp:273-276), steepest-descent
+// coefficients (odometer.cpp:313-326), the per-point and per-patch steps that must give the same bits in every launch
+// form (projection, iteration point, setup point, any-size patch bodies), the per-level LU factorisation and the
+// per-iteration solve + pose update + loop condition (odometer.cpp:341-346, 407-418, 509-515; pose.cpp:116-129).
+// Everything keeps the reference's operand order; the translation units are compiled with -ffp-contract=off.
 #pragma once
 
 #include <type_traits>
@@ -80,6 +81,183 @@ __device__ __forceinline__ void sd_values(float gx, float gy, const float *cx, c
   sd[1] = gy * cy[1];
 #pragma unroll
   for (int k = 2; k < 6; ++k) sd[k] = gx * cx[k] + gy * cy[k];
+}
+
+// ---------------------------------------------------------------- the bit-pinned per-point and per-patch steps
+// Every launch form (per-iteration, 8x8 / 4x4 fast paths, one-launch tracker, resident) takes these steps from here, so
+// that projections, visibility, taps and sd coefficients are the same bits in all of them by construction.
+
+// pose.cpp:384-391 : the point in the camera frame, G (X, Y, Z, 1) ...
+__device__ __forceinline__ void rotate_point(const float *G, float X, float Y, float Z, float &tx, float &ty, float &tz) {
+  tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
+  ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
+  tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
+}
+// ... and its pinhole projection at one level (one axis: t = tx, f = fx, c = cx or their y counterparts)
+__device__ __forceinline__ float pinhole_axis(float t, float tz, float f, float c) { return (t / tz) * f + c; }
+__device__ __forceinline__ void project_pinhole(float tx, float ty, float tz, const LevelCam &lc, float &mx, float &my) {
+  mx = pinhole_axis(tx, tz, lc.fx, lc.cx);
+  my = pinhole_axis(ty, tz, lc.fy, lc.cy);
+}
+
+// The taps of a visible point; an invisible lane gets the window of (1, 1), a harmless in-plane one: its weights and
+// base go through the same records and shuffles as everybody's, and its base is never dereferenced.
+__device__ __forceinline__ Taps taps_or_fallback(bool vis, float mx, float my, int pszd2) {
+  return make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, pszd2);
+}
+
+// Stage 1 of an iteration: step 7 (pose.cpp:384-391), ind_new (odometer.cpp:369-377), the window's taps. `valid`: the
+// lane has a point at all. What a kernel packs into its own record from this stays in the kernel. (k_track1_p8 calls
+// the four steps itself, see there.)
+struct IterPoint {
+  bool vis;
+  Taps tp;
+};
+__device__ __forceinline__ IterPoint iter_point(const float *G, float X, float Y, float Z, const LevelCam &lc, bool valid,
+                                                int pszd2) {
+  float tx, ty, tz, mx, my;
+  rotate_point(G, X, Y, Z, tx, ty, tz);
+  project_pinhole(tx, ty, tz, lc, mx, my);
+  IterPoint p;
+  p.vis = valid && in_view(mx, my, lc.swo, lc.sho);
+  p.tp = taps_or_fallback(p.vis, mx, my, pszd2);
+  return p;
+}
+
+// A point's coefficient line in device memory: cx0..3 | cx4 cx5 cy0 cy1 | cy2..5
+__device__ __forceinline__ void coef_line_store(float4 *c4, const float *cx, const float *cy) {
+  c4[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
+  c4[1] = make_float4(cx[4], cx[5], cy[0], cy[1]);
+  c4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
+}
+__device__ __forceinline__ void coef_line_load(const float4 *c4, float *cx, float *cy) {
+  const float4 a0 = c4[0], a1 = c4[1], a2 = c4[2];
+  cx[0] = a0.x; cx[1] = a0.y; cx[2] = a0.z; cx[3] = a0.w; cx[4] = a1.x; cx[5] = a1.y;
+  cy[0] = a1.z; cy[1] = a1.w; cy[2] = a2.x; cy[3] = a2.y; cy[4] = a2.z; cy[5] = a2.w;
+}
+// The setup point (odometer.cpp:273-282, 313-326): in the reference view -> this level's coefficients from the rotated
+// point i of p3r (SoA, stride M), stored to the line; out of it -> the stale line stays in force (odometer.cpp:304;
+// zeros if the point was never seen).
+__device__ __forceinline__ void setup_point(bool vis, const float *p3r, int i, int M, const LevelCam &lc, float4 *c4,
+                                            float *cx, float *cy) {
+  if (vis) {
+    sd_coefs(p3r[i], p3r[i + M], p3r[i + 2 * M], lc.fx, lc.fy, cx, cy);
+    coef_line_store(c4, cx, cy);
+  } else {
+    coef_line_load(c4, cx, cy);
+  }
+}
+
+// Any patch size: which pixels of which patch a lane owns. n = P * P pixels; a wave takes 64 / n whole patches when n
+// divides 64 (lane = patch `sub`, pixel q0), else one patch with the lanes striding over its pixels.
+struct PatchGeom {
+  int ppw, sub, q0, qstride, gwidth;  // patches per wave; the lane's patch; its first pixel; pixel stride; lanes per patch
+};
+__device__ __forceinline__ PatchGeom patch_geom(int n, int lane) {
+  PatchGeom g;
+  g.ppw = (n <= 64 && (64 % n) == 0) ? 64 / n : 1;
+  g.sub = g.ppw > 1 ? lane / n : 0;
+  g.q0 = g.ppw > 1 ? lane % n : lane;
+  g.qstride = g.ppw > 1 ? n : 64;
+  g.gwidth = g.ppw > 1 ? n : 64;
+  return g;
+}
+struct PatchBufs {  // where the T, Gx, Gy patches of a problem live: [point][n]
+  float *T, *Gx, *Gy;
+};
+
+// What the patch bodies need of the engine's parameters, by value. (A kernel that hands its EngineDev argument on by
+// reference no longer has the plane pointers it loads from e.planes recognised as global: their taps become flat loads.)
+struct PatchOpts {
+  int dopatchnorm, robust;
+  float huber_k;
+};
+
+// utilities.cpp:111-112, 187-188 : the mean of the patch's blended intensities (0 without dopatchnorm)
+__device__ __forceinline__ float patch_mean(const PatchOpts &e, const float *__restrict__ img, int sw, int P, int n,
+                                            const PatchGeom &pg, bool vis, const Taps &tp, int base) {
+  float mean = 0.0f;
+  if (e.dopatchnorm) {
+    float s = 0.0f;
+    for (int q = pg.q0; q < n; q += pg.qstride)
+      if (vis) s += tap4(img, base + (q / P) * sw + (q % P), sw, tp);
+    s = group_sum(s, pg.gwidth);
+    mean = s / (float)n;
+  }
+  return mean;
+}
+
+// Steps 4-6 for the lane's pixels of point i (utilities.cpp:115-189, odometer.cpp:428-455): reference patch (intensity
+// only is normalised) and gradient patches into `g`, the 21 unique sums of H into acc. A point out of the reference view
+// keeps its stale patch (odometer.cpp:304), or with ICTR_ROBUST_CLEAN contributes nothing, neither to H nor (through
+// sd) to b. LDS: also keep the point's three patches, stale or new, in `l`.
+template <bool LDS>
+__device__ __forceinline__ void setup_patch_body(const PatchOpts &e, const float *__restrict__ ref, const float *__restrict__ dx,
+                                                 const float *__restrict__ dy, int sw, int P, int n,
+                                                 const PatchGeom &pg, int i, bool valid, bool vis, const Taps &tp, int base,
+                                                 const float *cx, const float *cy, const PatchBufs &g, const PatchBufs &l,
+                                                 float *acc) {
+  const float mean = patch_mean(e, ref, sw, P, n, pg, vis, tp, base);
+  for (int q = pg.q0; q < n; q += pg.qstride) {
+    float t = 0.0f, gx = 0.0f, gy = 0.0f;
+    const size_t o = (size_t)i * n + q;
+    if (vis) {
+      const int idx = base + (q / P) * sw + (q % P);
+      t = tap4(ref, idx, sw, tp);
+      if (e.dopatchnorm) t -= mean;
+      gx = tap4(dx, idx, sw, tp);
+      gy = tap4(dy, idx, sw, tp);
+      g.T[o] = t;
+      g.Gx[o] = gx;
+      g.Gy[o] = gy;
+    } else if (valid) {
+      if (e.robust & ICTR_ROBUST_CLEAN) {
+        g.Gx[o] = 0.0f;
+        g.Gy[o] = 0.0f;
+      } else {
+        gx = g.Gx[o];
+        gy = g.Gy[o];
+      }
+      if (LDS) t = g.T[o];
+    }
+    if (LDS && valid) {
+      l.T[o] = t;
+      l.Gx[o] = gx;
+      l.Gy[o] = gy;
+    }
+    float sd[6];
+    sd_values(gx, gy, cx, cy, sd);
+    int jk = 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int k = j; k < 6; ++k) acc[jk++] += sd[j] * sd[k];
+  }
+}
+
+// Steps 7-9a for the lane's pixels of point i (utilities.cpp:55-113, odometer.cpp:381-404): current patch, residual
+// against T (with ICTR_ROBUST_HUBER scaled down beyond huber_k), the six sd * r sums into acc. `p`: where the point's
+// T, Gx, Gy are read from.
+__device__ __forceinline__ void iter_patch_body(const PatchOpts &e, const float *__restrict__ cur, int sw, int P, int n,
+                                                const PatchGeom &pg, int i, bool vis, const Taps &tp, int base,
+                                                const float *cx, const float *cy, const PatchBufs &p, float *acc) {
+  const float mean = patch_mean(e, cur, sw, P, n, pg, vis, tp, base);
+  for (int q = pg.q0; q < n; q += pg.qstride) {
+    if (vis) {
+      const size_t o = (size_t)i * n + q;
+      float inew = tap4(cur, base + (q / P) * sw + (q % P), sw, tp);
+      if (e.dopatchnorm) inew -= mean;
+      float r = p.T[o] - inew;  // pdiff (odometer.cpp:381)
+      if (e.robust & ICTR_ROBUST_HUBER) {
+        const float ar = fabsf(r);
+        if (ar > e.huber_k) r *= e.huber_k / ar;
+      }
+      float sd[6];
+      sd_values(p.Gx[o], p.Gy[o], cx, cy, sd);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc[k] += sd[k] * r;  // sd*_proj summed (odometer.cpp:386-404)
+    }
+  }
 }
 
 __device__ __forceinline__ void level_reset(ProbState &st, const EngineDev &e) {

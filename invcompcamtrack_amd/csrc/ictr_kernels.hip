@@ -51,16 +51,14 @@ __global__ __launch_bounds__(kBlock) void k_project_ref(EngineDev e, AllCams cam
   const float *p3 = e.pt3d + (size_t)b * 3 * e.M;
   float *p3r = e.pt3d_ref + (size_t)b * 3 * e.M;
   const float X = p3[i], Y = p3[i + e.M], Z = p3[i + 2 * e.M];
-  const float tx = st.G[0] * X + st.G[1] * Y + st.G[2] * Z + st.G[3];
-  const float ty = st.G[4] * X + st.G[5] * Y + st.G[6] * Z + st.G[7];
-  const float tz = st.G[8] * X + st.G[9] * Y + st.G[10] * Z + st.G[11];
+  float tx, ty, tz;
+  rotate_point(st.G, X, Y, Z, tx, ty, tz);
   p3r[i] = tx;
   p3r[i + e.M] = ty;
   p3r[i + 2 * e.M] = tz;
   for (int l = e.lv_l; l <= e.lv_f; ++l) {
     float *p2 = e.pt2d + ((size_t)b * e.nlev + l) * 2 * e.M;
-    p2[i] = (tx / tz) * cams.lc[l].fx + cams.lc[l].cx;
-    p2[i + e.M] = (ty / tz) * cams.lc[l].fy + cams.lc[l].cy;
+    project_pinhole(tx, ty, tz, cams.lc[l], p2[i], p2[i + e.M]);
   }
 }
 
@@ -71,16 +69,15 @@ __global__ __launch_bounds__(kBlock) void k_project_generic(const float *__restr
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const float X = pt3d[i], Y = pt3d[i + M], Z = pt3d[i + 2 * M];
-  const float tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
-  const float ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
-  const float tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
+  float tx, ty, tz;
+  rotate_point(G, X, Y, Z, tx, ty, tz);
   if (pt3d_rot) {
     pt3d_rot[i] = tx;
     pt3d_rot[i + M] = ty;
     pt3d_rot[i + 2 * M] = tz;
   }
-  pt2d[i] = (tx / tz) * lc.fx + lc.cx;
-  pt2d[i + M] = (ty / tz) * lc.fy + lc.cy;
+  pt2d[i] = pinhole_axis(tx, tz, lc.fx, lc.cx);  // (stored one by one: pt2d may alias pt3d_rot)
+  pt2d[i + M] = pinhole_axis(ty, tz, lc.fy, lc.cy);
 }
 
 // ---------------------------------------------------------------- steps 4-6: per level setup (any patch size)
@@ -99,92 +96,39 @@ __global__ __launch_bounds__(kBlock) void k_ref_level(EngineDev e, LevelCam lc, 
   const PlaneSet pl = e.planes[b * e.nlev + level];
   const float *pt2d = e.pt2d + ((size_t)b * e.nlev + level) * 2 * M;
   const float *p3r = e.pt3d_ref + (size_t)b * 3 * M;
-  float *T = e.T + (size_t)b * M * n;
-  float *Gx = e.Gx + (size_t)b * M * n;
-  float *Gy = e.Gy + (size_t)b * M * n;
+  const PatchBufs pb = {e.T + (size_t)b * M * n, e.Gx + (size_t)b * M * n, e.Gy + (size_t)b * M * n};
   float *coefb = e.coef + (size_t)b * M * kCoefStride;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int ppw = (n <= 64 && (64 % n) == 0) ? 64 / n : 1;  // patches per wave
-  const int sub = ppw > 1 ? lane / n : 0;
-  const int q0 = ppw > 1 ? lane % n : lane;
-  const int qstride = ppw > 1 ? n : 64;
-  const int gwidth = ppw > 1 ? n : 64;
+  const PatchGeom pg = patch_geom(n, lane);
+  const PatchOpts po = {e.dopatchnorm, e.robust, e.huber_k};
 
   float acc[kHUnique];
 #pragma unroll
   for (int j = 0; j < kHUnique; ++j) acc[j] = 0.0f;
 
   const int nw = gridDim.x * kWaves;
-  for (int g = blockIdx.x * kWaves + wave; g * ppw < npts; g += nw) {
-    const int i = g * ppw + sub;
+  for (int g = blockIdx.x * kWaves + wave; g * pg.ppw < npts; g += nw) {
+    const int i = g * pg.ppw + pg.sub;
     const bool valid = i < npts;
     const float mx = valid ? pt2d[i] : -1.0f;
     const float my = valid ? pt2d[i + M] : -1.0f;
     const bool vis = valid && in_view(mx, my, lc.swo, lc.sho);
     float cx[6], cy[6];
+    float4 *c4 = reinterpret_cast<float4 *>(coefb + (size_t)i * kCoefStride);
     if (vis) {
       sd_coefs(p3r[i], p3r[i + M], p3r[i + 2 * M], lc.fx, lc.fy, cx, cy);
-      if (q0 == 0) {
-        float *c = coefb + (size_t)i * kCoefStride;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          c[k] = cx[k];
-          c[6 + k] = cy[k];
-        }
-      }
+      if (pg.q0 == 0) coef_line_store(c4, cx, cy);
     } else if (valid) {  // out of the reference view at this level: keep the stale coefficients (quirk, odometer.cpp:304)
-      const float *c = coefb + (size_t)i * kCoefStride;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        cx[k] = c[k];
-        cy[k] = c[6 + k];
-      }
+      coef_line_load(c4, cx, cy);
     } else {
 #pragma unroll
       for (int k = 0; k < 6; ++k) cx[k] = cy[k] = 0.0f;
     }
-    const Taps tp = make_taps(vis ? mx : 0.0f, vis ? my : 0.0f, pszd2);
-    const int base = (tp.row0)*lc.sw + tp.col0;
-
-    float mean = 0.0f;
-    if (e.dopatchnorm) {  // utilities.cpp:187-188 : intensity patch only
-      float s = 0.0f;
-      for (int q = q0; q < n; q += qstride)
-        if (vis) s += tap4(pl.ref, base + (q / P) * lc.sw + (q % P), lc.sw, tp);
-      s = group_sum(s, gwidth);
-      mean = s / (float)n;
-    }
-    for (int q = q0; q < n; q += qstride) {
-      float gx = 0.0f, gy = 0.0f;
-      const size_t o = (size_t)i * n + q;
-      if (vis) {
-        const int idx = base + (q / P) * lc.sw + (q % P);
-        float t = tap4(pl.ref, idx, lc.sw, tp);
-        if (e.dopatchnorm) t -= mean;
-        gx = tap4(pl.dx, idx, lc.sw, tp);
-        gy = tap4(pl.dy, idx, lc.sw, tp);
-        T[o] = t;
-        Gx[o] = gx;
-        Gy[o] = gy;
-      } else if (valid) {
-        if (e.robust & ICTR_ROBUST_CLEAN) {  // option: no stale contributions, neither to H nor (through sd) to b
-          Gx[o] = 0.0f;
-          Gy[o] = 0.0f;
-        } else {
-          gx = Gx[o];
-          gy = Gy[o];
-        }
-      }
-      float sd[6];
-      sd_values(gx, gy, cx, cy, sd);
-      int jk = 0;
-#pragma unroll
-      for (int j = 0; j < 6; ++j)
-#pragma unroll
-        for (int k = j; k < 6; ++k) acc[jk++] += sd[j] * sd[k];
-    }
+    const Taps tp = taps_or_fallback(vis, mx, my, pszd2);
+    const int base = tp.row0 * lc.sw + tp.col0;
+    setup_patch_body<false>(po, pl.ref, pl.dx, pl.dy, lc.sw, P, n, pg, i, valid, vis, tp, base, cx, cy, pb, pb, acc);
   }
 
 #pragma unroll
@@ -349,11 +293,8 @@ __global__ __launch_bounds__(kBlock) void k_iter(EngineDev e, LevelCam lc, int l
   const int M = e.M;
   const PlaneSet pl = e.planes[b * e.nlev + level];
   const float *__restrict__ p3 = e.pt3d + (size_t)b * 3 * M;
-  const float *__restrict__ T = e.T + (size_t)b * M * n;
-  const float *__restrict__ Gx = e.Gx + (size_t)b * M * n;
-  const float *__restrict__ Gy = e.Gy + (size_t)b * M * n;
+  const PatchBufs pb = {e.T + (size_t)b * M * n, e.Gx + (size_t)b * M * n, e.Gy + (size_t)b * M * n};
   const float *__restrict__ coefb = e.coef + (size_t)b * M * kCoefStride;
-  const float *__restrict__ cur = pl.cur;
 
   float G[12];
 #pragma unroll
@@ -361,62 +302,23 @@ __global__ __launch_bounds__(kBlock) void k_iter(EngineDev e, LevelCam lc, int l
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int ppw = (n <= 64 && (64 % n) == 0) ? 64 / n : 1;
-  const int sub = ppw > 1 ? lane / n : 0;
-  const int q0 = ppw > 1 ? lane % n : lane;
-  const int qstride = ppw > 1 ? n : 64;
-  const int gwidth = ppw > 1 ? n : 64;
+  const PatchGeom pg = patch_geom(n, lane);
+  const PatchOpts po = {e.dopatchnorm, e.robust, e.huber_k};
 
   float acc[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) acc[k] = 0.0f;
 
   const int nw = gridDim.x * kWaves;
-  for (int g = blockIdx.x * kWaves + wave; g * ppw < npts; g += nw) {
-    const int i = g * ppw + sub;
+  for (int g = blockIdx.x * kWaves + wave; g * pg.ppw < npts; g += nw) {
+    const int i = g * pg.ppw + pg.sub;
     const bool valid = i < npts;
-    // step 7 (pose.cpp:384-391)
     const float X = valid ? p3[i] : 0.0f, Y = valid ? p3[i + M] : 0.0f, Z = valid ? p3[i + 2 * M] : 1.0f;
-    const float tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
-    const float ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
-    const float tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
-    const float mx = (tx / tz) * lc.fx + lc.cx;
-    const float my = (ty / tz) * lc.fy + lc.cy;
-    const bool vis = valid && in_view(mx, my, lc.swo, lc.sho);  // ind_new (odometer.cpp:369-377)
+    const IterPoint pt = iter_point(G, X, Y, Z, lc, valid, pszd2);
     float cx[6], cy[6];
-    {
-      const float4 *c4 = reinterpret_cast<const float4 *>(coefb + (size_t)(valid ? i : 0) * kCoefStride);
-      const float4 c0 = c4[0], c1 = c4[1], c2 = c4[2];
-      cx[0] = c0.x; cx[1] = c0.y; cx[2] = c0.z; cx[3] = c0.w; cx[4] = c1.x; cx[5] = c1.y;
-      cy[0] = c1.z; cy[1] = c1.w; cy[2] = c2.x; cy[3] = c2.y; cy[4] = c2.z; cy[5] = c2.w;
-    }
-    const Taps tp = make_taps(vis ? mx : 0.0f, vis ? my : 0.0f, pszd2);
-    const int base = tp.row0 * lc.sw + tp.col0;
-
-    float mean = 0.0f;
-    if (e.dopatchnorm) {  // utilities.cpp:111-112
-      float s = 0.0f;
-      for (int q = q0; q < n; q += qstride)
-        if (vis) s += tap4(cur, base + (q / P) * lc.sw + (q % P), lc.sw, tp);
-      s = group_sum(s, gwidth);
-      mean = s / (float)n;
-    }
-    for (int q = q0; q < n; q += qstride) {
-      if (vis) {
-        const size_t o = (size_t)i * n + q;
-        float inew = tap4(cur, base + (q / P) * lc.sw + (q % P), lc.sw, tp);
-        if (e.dopatchnorm) inew -= mean;
-        float r = T[o] - inew;  // pdiff (odometer.cpp:381)
-        if (e.robust & ICTR_ROBUST_HUBER) {
-          const float ar = fabsf(r);
-          if (ar > e.huber_k) r *= e.huber_k / ar;
-        }
-        float sd[6];
-        sd_values(Gx[o], Gy[o], cx, cy, sd);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc[k] += sd[k] * r;  // sd*_proj summed (odometer.cpp:386-404)
-      }
-    }
+    coef_line_load(reinterpret_cast<const float4 *>(coefb + (size_t)(valid ? i : 0) * kCoefStride), cx, cy);
+    const int base = pt.tp.row0 * lc.sw + pt.tp.col0;
+    iter_patch_body(po, pl.cur, lc.sw, P, n, pg, i, pt.vis, pt.tp, base, cx, cy, pb, acc);
   }
 
 #pragma unroll
@@ -611,23 +513,18 @@ __global__ __launch_bounds__(kBlock) void k_iter8(EngineDev e, LevelCam lc, int 
     const bool pv = lane < cnt;
     const int ip = i0 + (pv ? lane : 0);
     const float X = p3[ip], Y = p3[ip + M], Z = p3[ip + 2 * M];
-    const float4 *c4 = reinterpret_cast<const float4 *>(coefb + (size_t)ip * kCoefStride);
-    const float4 q0 = c4[0], q1 = c4[1], q2 = c4[2];  // cx0..3 | cx4 cx5 cy0 cy1 | cy2..5
-    const float tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
-    const float ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
-    const float tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
-    const float mx = (tx / tz) * lc.fx + lc.cx;
-    const float my = (ty / tz) * lc.fy + lc.cy;
-    const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
-    const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 4);  // (1,1): a harmless in-plane window
+    float cx[6], cy[6];
+    coef_line_load(reinterpret_cast<const float4 *>(coefb + (size_t)ip * kCoefStride), cx, cy);
+    const IterPoint pt = iter_point(G, X, Y, Z, lc, pv, 4);
+    const Taps &tp = pt.tp;
     const int base_v = tp.row0 * sw + tp.col0;
     const int so_v = (base_v - sw - 1) * 4;  // bytes to the window's top-left texel (tap d of pixel 0)
     {
       float4 *r4 = reinterpret_cast<float4 *>(rec + lane * kRec);
       r4[0] = make_float4(tp.w1, tp.w0, tp.w3, tp.w2);
-      r4[1] = make_float4(q0.z, q0.w, q1.x, q1.y);  // cx2 cx3 cx4 cx5
-      r4[2] = make_float4(q2.x, q2.y, q2.z, q2.w);  // cy2 cy3 cy4 cy5
-      r4[3] = make_float4(q0.x, q1.w, vis ? 1.0f : 0.0f, 0.0f);  // cx0 cy1 vis -
+      r4[1] = make_float4(cx[2], cx[3], cx[4], cx[5]);
+      r4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
+      r4[3] = make_float4(cx[0], cy[1], pt.vis ? 1.0f : 0.0f, 0.0f);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -817,7 +714,7 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
     const int ip = i0 + (pv ? lane : 0);
     const float mx = pt2d[ip], my = pt2d[ip + M];
     const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
-    const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 4);
+    const Taps tp = taps_or_fallback(vis, mx, my, 4);
 #ifndef ICTR_REF8_TOUCH
 #define ICTR_REF8_TOUCH 6  // line touches per lane and chunk (0: none)
 #endif
@@ -849,17 +746,7 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
       }
     }
     float cx[6], cy[6];
-    float4 *c4 = reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride);
-    if (vis) {
-      sd_coefs(p3r[ip], p3r[ip + M], p3r[ip + 2 * M], lc.fx, lc.fy, cx, cy);
-      c4[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
-      c4[1] = make_float4(cx[4], cx[5], cy[0], cy[1]);
-      c4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
-    } else {  // stale coefficients stay in force (odometer.cpp:304); zeros if the point was never seen
-      const float4 a0 = c4[0], a1 = c4[1], a2 = c4[2];
-      cx[0] = a0.x; cx[1] = a0.y; cx[2] = a0.z; cx[3] = a0.w; cx[4] = a1.x; cx[5] = a1.y;
-      cy[0] = a1.z; cy[1] = a1.w; cy[2] = a2.x; cy[3] = a2.y; cy[4] = a2.z; cy[5] = a2.w;
-    }
+    setup_point(vis, p3r, ip, M, lc, reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride), cx, cy);
     const int base_v = tp.row0 * sw + tp.col0;
     const int vis_v = vis ? 1 : 0;
     const int tx_v = tp.col0 - padl, ty_v = tp.row0 - padl;  // (OTF) tap a of pixel (0,0) in unpadded image coordinates
@@ -1121,22 +1008,17 @@ __global__ __launch_bounds__(kBlock) void k_iter4(EngineDev e, LevelCam lc, int 
     const bool pv = lane < cnt;
     const int ip = i0 + (pv ? lane : 0);
     const float X = p3[ip], Y = p3[ip + M], Z = p3[ip + 2 * M];
-    const float4 *c4 = reinterpret_cast<const float4 *>(coefb + (size_t)ip * kCoefStride);
-    const float4 q0 = c4[0], q1 = c4[1], q2 = c4[2];
-    const float tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
-    const float ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
-    const float tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
-    const float mx = (tx / tz) * lc.fx + lc.cx;
-    const float my = (ty / tz) * lc.fy + lc.cy;
-    const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
-    const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 2);
+    float cx[6], cy[6];
+    coef_line_load(reinterpret_cast<const float4 *>(coefb + (size_t)ip * kCoefStride), cx, cy);
+    const IterPoint pt = iter_point(G, X, Y, Z, lc, pv, 2);
+    const Taps &tp = pt.tp;
     const int base_v = tp.row0 * sw + tp.col0;
     {
       float4 *r4 = reinterpret_cast<float4 *>(rec + lane * kRec);
       r4[0] = make_float4(tp.w0, tp.w1, tp.w2, tp.w3);
-      r4[1] = make_float4(q0.x, q0.z, q0.w, q1.x);
-      r4[2] = make_float4(q1.y, q1.w, q2.x, q2.y);
-      r4[3] = make_float4(q2.z, q2.w, vis ? 1.0f : 0.0f, 0.0f);
+      r4[1] = make_float4(cx[0], cx[2], cx[3], cx[4]);
+      r4[2] = make_float4(cx[5], cy[1], cy[2], cy[3]);
+      r4[3] = make_float4(cy[4], cy[5], pt.vis ? 1.0f : 0.0f, 0.0f);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1275,12 +1157,9 @@ __global__ __launch_bounds__(kBlock) void k_ref4(EngineDev e, LevelCam lc, int l
     if (vis) {  // invisible points keep their stale coefficients (odometer.cpp:304): nothing to do for them
       float cx[6], cy[6];
       sd_coefs(p3r[ip], p3r[ip + M], p3r[ip + 2 * M], lc.fx, lc.fy, cx, cy);
-      float4 *c4 = reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride);
-      c4[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
-      c4[1] = make_float4(cx[4], cx[5], cy[0], cy[1]);
-      c4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
+      coef_line_store(reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride), cx, cy);
     }
-    const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 2);
+    const Taps tp = taps_or_fallback(vis, mx, my, 2);
     const int base_v = tp.row0 * sw + tp.col0;
     const int vis_v = vis ? 1 : 0;
     const float w0 = tp.w0, w1 = tp.w1, w2 = tp.w2, w3 = tp.w3;

@@ -519,15 +519,10 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
         float Gc[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) Gc[k] = sG[k];
-        const float tx = Gc[0] * X + Gc[1] * Y + Gc[2] * Z + Gc[3];
-        const float ty = Gc[4] * X + Gc[5] * Y + Gc[6] * Z + Gc[7];
-        const float tz = Gc[8] * X + Gc[9] * Y + Gc[10] * Z + Gc[11];
-        const float mx = (tx / tz) * lc.fx + lc.cx;
-        const float my = (ty / tz) * lc.fy + lc.cy;
-        const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
-        const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 4);  // (1,1): a harmless in-plane window
-        base_v = ((tp.row0 - 1) * sw + tp.col0 - 1) * 4;                 // bytes: the buffer load's scalar offset
-        vis_f = vis ? 1.0f : 0.0f;
+        const IterPoint pt = iter_point(Gc, X, Y, Z, lc, pv, 4);
+        const Taps &tp = pt.tp;
+        base_v = ((tp.row0 - 1) * sw + tp.col0 - 1) * 4;  // bytes: the buffer load's scalar offset
+        vis_f = pt.vis ? 1.0f : 0.0f;
         if (lane < kResPPW) recs[lane] = make_float4(tp.w1, tp.w0, tp.w3, tp.w2);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

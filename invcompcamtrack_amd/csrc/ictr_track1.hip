@@ -121,16 +121,14 @@ __device__ __forceinline__ void t1_fused_begin(const EngineDev &e, const T1Args 
   float *p3r = e.pt3d_ref + (size_t)b * 3 * e.M;
   for (int i = lo + tid; i < npts; i += nthr) {
     const float X = p3[i], Y = p3[i + e.M], Z = p3[i + 2 * e.M];
-    const float tx = G[0] * X + G[1] * Y + G[2] * Z + G[3];
-    const float ty = G[4] * X + G[5] * Y + G[6] * Z + G[7];
-    const float tz = G[8] * X + G[9] * Y + G[10] * Z + G[11];
+    float tx, ty, tz;
+    rotate_point(G, X, Y, Z, tx, ty, tz);
     p3r[i] = tx;
     p3r[i + e.M] = ty;
     p3r[i + 2 * e.M] = tz;
     for (int l = e.lv_l; l <= e.lv_f; ++l) {
       float *p2 = e.pt2d + ((size_t)b * e.nlev + l) * 2 * e.M;
-      p2[i] = (tx / tz) * a.lc[l].fx + a.lc[l].cx;
-      p2[i + e.M] = (ty / tz) * a.lc[l].fy + a.lc[l].cy;
+      project_pinhole(tx, ty, tz, a.lc[l], p2[i], p2[i + e.M]);
     }
   }
   __syncthreads();  // the projections are read back by other threads of this workgroup
@@ -206,18 +204,14 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
   const int n = P * P;
   const int pszd2 = P / 2;
   const int M = e.M;
-  const int ppw = (n <= 64 && (64 % n) == 0) ? 64 / n : 1;  // patches per wave
-  const int sub = ppw > 1 ? lane / n : 0;
-  const int q0 = ppw > 1 ? lane % n : lane;
-  const int qstride = ppw > 1 ? n : 64;
-  const int gwidth = ppw > 1 ? n : 64;
+  const PatchGeom pg = patch_geom(n, lane);
+  const PatchOpts po = {e.dopatchnorm, e.robust, e.huber_k};
 
   T1Rec *rec = reinterpret_cast<T1Rec *>(sDyn);
   int *sBase = reinterpret_cast<int *>(sDyn + (size_t)a.npts_cap * 16);
-  float *lT = sDyn + (size_t)a.npts_cap * 17;   // any-size form: three planes [npts_cap * n]
+  float *lT = sDyn + (size_t)a.npts_cap * 17;   // three planes [npts_cap * n]
   float *lGx = lT + (size_t)a.npts_cap * n;
-  float *lGy = lGx + (size_t)a.npts_cap * n;
-  float *lTpl = lT;                              // 8x8 form: [point][T | Gx | Gy][64], one address + fixed offsets
+  const PatchBufs lpb = {lT, lGx, lGx + (size_t)a.npts_cap * n};
 
   if (a.fused_begin) t1_fused_begin(e, a, b, tid, blockDim.x);
   const ProbState &gst = *t1_initial_state(e, a, b);
@@ -238,12 +232,9 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
 
   const float *__restrict__ p3 = e.pt3d + (size_t)b * 3 * M;
   const float *__restrict__ p3r = e.pt3d_ref + (size_t)b * 3 * M;
-  float *gT = e.T + (size_t)b * M * n;
-  float *gGx = e.Gx + (size_t)b * M * n;
-  float *gGy = e.Gy + (size_t)b * M * n;
+  const PatchBufs gpb = {e.T + (size_t)b * M * n, e.Gx + (size_t)b * M * n, e.Gy + (size_t)b * M * n};
   float *coefb = e.coef + (size_t)b * M * kCoefStride;
-  const int ngroups = (npts + ppw - 1) / ppw;
-  const int mycnt = wave < npts ? (npts - wave + nwaves - 1) / nwaves : 0;  // 8x8: patches wave, wave + nwaves, ...
+  const int ngroups = (npts + pg.ppw - 1) / pg.ppw;
 
 #ifdef ICTR_T1_PROF
   unsigned long long tp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0_ = 0, t1_ = 0;
@@ -260,18 +251,8 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
         const float mx = pt2d[i], my = pt2d[i + M];
         const bool vis = in_view(mx, my, lc.swo, lc.sho);
         float cx[6], cy[6];
-        float4 *c4 = reinterpret_cast<float4 *>(coefb + (size_t)i * kCoefStride);
-        if (vis) {
-          sd_coefs(p3r[i], p3r[i + M], p3r[i + 2 * M], lc.fx, lc.fy, cx, cy);
-          c4[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
-          c4[1] = make_float4(cx[4], cx[5], cy[0], cy[1]);
-          c4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
-        } else {  // stale coefficients stay in force (odometer.cpp:304); zeros if the point was never seen
-          const float4 a0 = c4[0], a1 = c4[1], a2 = c4[2];
-          cx[0] = a0.x; cx[1] = a0.y; cx[2] = a0.z; cx[3] = a0.w; cx[4] = a1.x; cx[5] = a1.y;
-          cy[0] = a1.z; cy[1] = a1.w; cy[2] = a2.x; cy[3] = a2.y; cy[4] = a2.z; cy[5] = a2.w;
-        }
-        const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, pszd2);  // (1,1): a harmless in-plane window
+        setup_point(vis, p3r, i, M, lc, reinterpret_cast<float4 *>(coefb + (size_t)i * kCoefStride), cx, cy);
+        const Taps tp = taps_or_fallback(vis, mx, my, pszd2);
         float4 *r4 = reinterpret_cast<float4 *>(&rec[i]);
         const int base = tp.row0 * sw + tp.col0;
         r4[0] = make_float4(tp.w0, tp.w1, tp.w2, tp.w3);
@@ -289,61 +270,18 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
 #pragma unroll
       for (int j = 0; j < kHUnique; ++j) acc[j] = 0.0f;
       for (int g = wave; g < ngroups; g += nwaves) {
-        const int i = g * ppw + sub;
+        const int i = g * pg.ppw + pg.sub;
         const bool valid = i < npts;
         const T1Rec r = rec[valid ? i : 0];
         const bool vis = valid && r.vis != 0.0f;
         Taps tp;
         tp.w0 = r.w0; tp.w1 = r.w1; tp.w2 = r.w2; tp.w3 = r.w3;
-        const int base = r.base;
         float cx[6], cy[6];
         cx[0] = valid ? r.cx0 : 0.0f; cx[1] = 0.0f; cx[2] = valid ? r.cx2 : 0.0f; cx[3] = valid ? r.cx3 : 0.0f;
         cx[4] = valid ? r.cx4 : 0.0f; cx[5] = valid ? r.cx5 : 0.0f;
         cy[0] = 0.0f; cy[1] = valid ? r.cy1 : 0.0f; cy[2] = valid ? r.cy2 : 0.0f; cy[3] = valid ? r.cy3 : 0.0f;
         cy[4] = valid ? r.cy4 : 0.0f; cy[5] = valid ? r.cy5 : 0.0f;
-        float mean = 0.0f;
-        if (e.dopatchnorm) {  // utilities.cpp:187-188 : intensity patch only
-          float s = 0.0f;
-          for (int q = q0; q < n; q += qstride)
-            if (vis) s += tap4(pl.ref, base + (q / P) * sw + (q % P), sw, tp);
-          s = group_sum(s, gwidth);
-          mean = s / (float)n;
-        }
-        for (int q = q0; q < n; q += qstride) {
-          float t = 0.0f, gx = 0.0f, gy = 0.0f;
-          const size_t o = (size_t)i * n + q;
-          if (vis) {
-            const int idx = base + (q / P) * sw + (q % P);
-            t = tap4(pl.ref, idx, sw, tp);
-            if (e.dopatchnorm) t -= mean;
-            gx = tap4(pl.dx, idx, sw, tp);
-            gy = tap4(pl.dy, idx, sw, tp);
-            gT[o] = t;
-            gGx[o] = gx;
-            gGy[o] = gy;
-          } else if (valid) {
-            if (e.robust & ICTR_ROBUST_CLEAN) {  // option: no stale contributions
-              gGx[o] = 0.0f;
-              gGy[o] = 0.0f;
-            } else {
-              gx = gGx[o];
-              gy = gGy[o];
-            }
-            if (TL) t = gT[o];
-          }
-          if (TL && valid) {
-            lT[o] = t;
-            lGx[o] = gx;
-            lGy[o] = gy;
-          }
-          float sd[6];
-          sd_values(gx, gy, cx, cy, sd);
-          int jk = 0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j)
-#pragma unroll
-            for (int k = j; k < 6; ++k) acc[jk++] += sd[j] * sd[k];
-        }
+        setup_patch_body<TL>(po, pl.ref, pl.dx, pl.dy, sw, P, n, pg, i, valid, vis, tp, r.base, cx, cy, gpb, lpb, acc);
       }
       T1_REDUCE_STORE(kHUnique, acc, sPart[wave])
     }
@@ -353,10 +291,7 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
       double hs = 0.0;
       if (lane < kHUnique)
         for (int w = 0; w < nwaves; ++w) hs += (double)sPart[w][lane];
-      const int r = lane / 6, c = lane - 6 * r;
-      const int lo = r < c ? r : c, hi = r < c ? c : r;
-      const int j = lane < 36 ? lo * 6 - lo * (lo - 1) / 2 + (hi - lo) : 0;
-      ws_factor(S, lane_gather((float)hs, j), lane);
+      ws_factor(S, lane_gather((float)hs, h_unique_index(lane)), lane);
       ws_level_reset(S, solve_opts(e));
       if (lane == 0) sActive = S.active;
     }
@@ -371,18 +306,12 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
 #pragma unroll
         for (int k = 0; k < 12; ++k) Gc[k] = sG[k];
         for (int i = tid; i < npts; i += nthr) {
-          const float X = p3[i], Y = p3[i + M], Z = p3[i + 2 * M];
-          const float tx = Gc[0] * X + Gc[1] * Y + Gc[2] * Z + Gc[3];
-          const float ty = Gc[4] * X + Gc[5] * Y + Gc[6] * Z + Gc[7];
-          const float tz = Gc[8] * X + Gc[9] * Y + Gc[10] * Z + Gc[11];
-          const float mx = (tx / tz) * lc.fx + lc.cx;
-          const float my = (ty / tz) * lc.fy + lc.cy;
-          const bool vis = in_view(mx, my, lc.swo, lc.sho);
-          const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, pszd2);
+          const IterPoint pt = iter_point(Gc, p3[i], p3[i + M], p3[i + 2 * M], lc, true, pszd2);
+          const Taps &tp = pt.tp;
           const int base = tp.row0 * sw + tp.col0;
           T1Rec &r = rec[i];
           *reinterpret_cast<float4 *>(&r) = make_float4(tp.w0, tp.w1, tp.w2, tp.w3);
-          r.vis = vis ? 1.0f : 0.0f;
+          r.vis = pt.vis ? 1.0f : 0.0f;
           r.base = base;
           sBase[i] = base;
         }
@@ -394,40 +323,16 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
 #pragma unroll
       for (int k = 0; k < 6; ++k) acc[k] = 0.0f;
       for (int g = wave; g < ngroups; g += nwaves) {
-        const int i = g * ppw + sub;
+        const int i = g * pg.ppw + pg.sub;
         const bool valid = i < npts;
         const T1Rec r = rec[valid ? i : 0];
         const bool vis = valid && r.vis != 0.0f;
         Taps tp;
         tp.w0 = r.w0; tp.w1 = r.w1; tp.w2 = r.w2; tp.w3 = r.w3;
-        const int base = r.base;
         float cx[6], cy[6];
         cx[0] = r.cx0; cx[1] = 0.0f; cx[2] = r.cx2; cx[3] = r.cx3; cx[4] = r.cx4; cx[5] = r.cx5;
         cy[0] = 0.0f; cy[1] = r.cy1; cy[2] = r.cy2; cy[3] = r.cy3; cy[4] = r.cy4; cy[5] = r.cy5;
-        float mean = 0.0f;
-        if (e.dopatchnorm) {  // utilities.cpp:111-112
-          float s = 0.0f;
-          for (int q = q0; q < n; q += qstride)
-            if (vis) s += tap4(cur, base + (q / P) * sw + (q % P), sw, tp);
-          s = group_sum(s, gwidth);
-          mean = s / (float)n;
-        }
-        for (int q = q0; q < n; q += qstride) {
-          if (vis) {
-            const size_t o = (size_t)i * n + q;
-            float inew = tap4(cur, base + (q / P) * sw + (q % P), sw, tp);
-            if (e.dopatchnorm) inew -= mean;
-            float rr = (TL ? lT[o] : gT[o]) - inew;  // pdiff (odometer.cpp:381)
-            if (e.robust & ICTR_ROBUST_HUBER) {
-              const float ar = fabsf(rr);
-              if (ar > e.huber_k) rr *= e.huber_k / ar;
-            }
-            float sd[6];
-            sd_values(TL ? lGx[o] : gGx[o], TL ? lGy[o] : gGy[o], cx, cy, sd);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) acc[k] += sd[k] * rr;  // sd*_proj summed (odometer.cpp:386-404)
-          }
-        }
+        iter_patch_body(po, cur, sw, P, n, pg, i, vis, tp, r.base, cx, cy, TL ? lpb : gpb, acc);
       }
       T1_MARK(4)  // stage 2 of wave 0
       T1_REDUCE_STORE(6, acc, sPart[wave])
@@ -709,18 +614,8 @@ __global__ __launch_bounds__(64 * kT8MaxWaves, LEAN ? 4 : 2) void k_track1_p8(En
         const float mx = pt2d[ip], my = pt2d[ip + M];
         const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
         float cx[6], cy[6];
-        float4 *c4 = reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride);
-        if (vis) {
-          sd_coefs(p3r[ip], p3r[ip + M], p3r[ip + 2 * M], lc.fx, lc.fy, cx, cy);
-          c4[0] = make_float4(cx[0], cx[1], cx[2], cx[3]);
-          c4[1] = make_float4(cx[4], cx[5], cy[0], cy[1]);
-          c4[2] = make_float4(cy[2], cy[3], cy[4], cy[5]);
-        } else {  // stale coefficients stay in force (odometer.cpp:304); zeros if the point was never seen
-          const float4 a0 = c4[0], a1 = c4[1], a2 = c4[2];
-          cx[0] = a0.x; cx[1] = a0.y; cx[2] = a0.z; cx[3] = a0.w; cx[4] = a1.x; cx[5] = a1.y;
-          cy[0] = a1.z; cy[1] = a1.w; cy[2] = a2.x; cy[3] = a2.y; cy[4] = a2.z; cy[5] = a2.w;
-        }
-        const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 4);  // (1,1): a harmless in-plane window
+        setup_point(vis, p3r, ip, M, lc, reinterpret_cast<float4 *>(coefb + (size_t)ip * kCoefStride), cx, cy);
+        const Taps tp = taps_or_fallback(vis, mx, my, 4);
         const int base_v = (tp.row0 - 1) * sw + tp.col0 - 1;
         const int vis_v = vis ? 1 : 0;
         float4 *const recs = lRec + (size_t)(slot0 + c0) * 4;  // this chunk's records
@@ -817,9 +712,7 @@ __global__ __launch_bounds__(64 * kT8MaxWaves, LEAN ? 4 : 2) void k_track1_p8(En
       double hs = 0.0;
       if (lane < kHUnique)
         for (int w = 0; w < nwaves; ++w) hs += (double)sPart[w][lane];
-      const int r = lane / 6, c = lane - 6 * r;
-      const int lo = r < c ? r : c, hi = r < c ? c : r;
-      const int j = lane < 36 ? lo * 6 - lo * (lo - 1) / 2 + (hi - lo) : 0;
+      const int j = h_unique_index(lane);
       float hv = (float)hs;
       if constexpr (TEAM) hv = (float)team_allsum<kHUnique, 32>(tc, hv, lane);
       WaveSolver S;  // wave 0 is the solver (ictr_devfn.h)
@@ -852,13 +745,13 @@ __global__ __launch_bounds__(64 * kT8MaxWaves, LEAN ? 4 : 2) void k_track1_p8(En
         // registers for the whole tracking: no memory round trip in front of the projection
         float X = X1, Y = Y1, Z = Z1;
         if (!single) X = p3[ip], Y = p3[ip + M], Z = p3[ip + 2 * M];
-        const float tx = Gc[0] * X + Gc[1] * Y + Gc[2] * Z + Gc[3];
-        const float ty = Gc[4] * X + Gc[5] * Y + Gc[6] * Z + Gc[7];
-        const float tz = Gc[8] * X + Gc[9] * Y + Gc[10] * Z + Gc[11];
-        const float mx = (tx / tz) * lc.fx + lc.cx;
-        const float my = (ty / tz) * lc.fy + lc.cy;
+        // (iter_point's steps spelt out: through the helper the compiler orders X, Y, Z differently and commutes a few
+        // operands -- the same values, but this kernel's code is held identical to what was measured)
+        float tx, ty, tz, mx, my;
+        rotate_point(Gc, X, Y, Z, tx, ty, tz);
+        project_pinhole(tx, ty, tz, lc, mx, my);
         const bool vis = pv && in_view(mx, my, lc.swo, lc.sho);
-        const Taps tp = make_taps(vis ? mx : 1.0f, vis ? my : 1.0f, 4);  // (1,1): a harmless in-plane window
+        const Taps tp = taps_or_fallback(vis, mx, my, 4);
         const int base_v = ((tp.row0 - 1) * sw + tp.col0 - 1) * 4;  // bytes: the buffer load's scalar offset
         float4 *const recs = lRec + (size_t)(slot0 + c0) * 4;  // this chunk's records
         if (pv) {
