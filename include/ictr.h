@@ -496,6 +496,15 @@ int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, double *t, doub
 int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws);
 /* trials per chunk of this object (ICTR_RANSAC_CHUNK overrides the choice made from N) */
 int ictr_ransac_chunk_size(const ictr_ransac *r);
+/* inspection: k_ransac_hyp and k_ransac_score<tile> alone over trials first_trial .. first_trial + count - 1 (count:
+ * 1 .. 2^20, trials below 2^40), in the object's own chunks and tile, on the null stream; no selection, so every trial
+ * of the range is computed whatever came before it. Needs set_points; refused (ICTR_ERR_STATE) while a run is in
+ * flight. Per trial (host arrays): status[count] (1 = not degenerate and a P3P root chosen), draws[count][4] (draw
+ * order, -1 = not drawn), hyp[count][12] (R row-major, then the camera centre), cnt[count] inliers,
+ * words[count][ceil(N / 64)] inlier bits. hyp, cnt and words of a trial with status 0 are undefined. */
+int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const double *cc, double kc, double inlthresh,
+                             uint64_t seed, int64_t first_trial, int64_t count, int32_t *status, int32_t *draws,
+                             double *hyp, uint32_t *cnt, uint64_t *words);
 
 /* ------------------------------------------------------------------ multi-view point triangulation (misc_src/triang.c)
  * A track set (10^4 .. 10^5 points, 2 .. 30 views each) triangulated in one launch, one lane per point, with the

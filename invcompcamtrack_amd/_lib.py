@@ -213,6 +213,9 @@ SIGNATURES = {
     "ictr_ransac_wait": (C.c_int, [VP, C.POINTER(I64), DP, DP, DP, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "ictr_ransac_samples": (C.c_int, [VP, C.POINTER(I64), C.POINTER(C.c_int32)]),
     "ictr_ransac_chunk_size": (C.c_int, [VP]),
+    "ictr_debug_ransac_trials": (C.c_int, [VP, DP, DP, C.c_double, C.c_double, C.c_uint64, I64, I64,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), DP, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint64)]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

@@ -147,7 +147,9 @@ hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *pat
 // ---------------------------------------------------------------- ictr_sequence.hip, ictr_ransac.hip, ictr_patchflow.hip
 // the between-pairs step (three launches), or with a.tail the last frame's bookkeeping (one)
 void launch_seq_select(const SeqArgs &a, hipStream_t s);
-// one chunk of a.k trials: hypotheses, scoring (tile = 16 / 32 / 64 hypotheses per workgroup), ordered selection
+// one chunk of a.k trials: hypotheses and scoring (tile = 16 / 32 / 64 hypotheses per workgroup) ...
+void launch_ransac_hyp_score(const RansacArgs &a, int tile, hipStream_t s);
+// ... and the same followed by the ordered selection
 void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s);
 // after the last chunk: inl_cnt and the post-filter
 void launch_ransac_finish(const RansacArgs &a, hipStream_t s);

@@ -518,7 +518,9 @@ __global__ void __launch_bounds__(kRanSelBlock) k_ransac_finish(RansacArgs a) {
   }
 }
 
-void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s) {
+// the hypotheses and scores of one chunk: the launch geometry of k_ransac_hyp and k_ransac_score<tile>, stated once for
+// the run (launch_ransac_chunk) and the inspection entry (ictr_debug_ransac_trials)
+void launch_ransac_hyp_score(const RansacArgs &a, int tile, hipStream_t s) {
   hipLaunchKernelGGL(k_ransac_hyp, dim3((a.k + kRanHypBlock - 1) / kRanHypBlock), dim3(kRanHypBlock), 0, s, a);
   const int segs = (a.nwords + kRanScoreBlock / 64 - 1) / (kRanScoreBlock / 64);
   if (tile == 16)
@@ -527,6 +529,10 @@ void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s) {
     hipLaunchKernelGGL(k_ransac_score<64>, dim3((a.k + 63) / 64, segs), dim3(kRanScoreBlock), 0, s, a);
   else
     hipLaunchKernelGGL(k_ransac_score<32>, dim3((a.k + 31) / 32, segs), dim3(kRanScoreBlock), 0, s, a);
+}
+
+void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s) {
+  launch_ransac_hyp_score(a, tile, s);
   hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(kRanSelBlock), 0, s, a);
 }
 
@@ -660,23 +666,14 @@ extern "C" int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const 
 
 extern "C" int ictr_ransac_chunk_size(const ictr_ransac *r) { return r ? r->chunk : 0; }
 
-extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples,
-                               int64_t maxtrials, double inlthresh, uint64_t seed, void *hip_stream) {
-  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ransac_run: NULL argument");
-  if (int rc = ran_refuse_pending(r, "ransac_run")) return rc;
-  if (!r->points_set) return fail(ICTR_ERR_STATE, "ransac_run: ictr_ransac_set_points has not been called");
-  if (nsamples < 1 || nsamples > r->smax)
-    return fail(ICTR_ERR_INVALID, "ransac_run: nsamples %lld (1 .. %lld, the size given at creation)",
-                (long long)nsamples, (long long)r->smax);
-  if (maxtrials < 1 || maxtrials > ((int64_t)1 << 40))
-    return fail(ICTR_ERR_INVALID, "ransac_run: maxtrials %lld (1 .. 2^40)", (long long)maxtrials);
-  if (!std::isfinite(inlthresh)) return fail(ICTR_ERR_INVALID, "ransac_run: inlthresh is not finite");
+// the camera checked, and every field of the kernels' argument block that does not depend on the trial range
+static int ran_fill_args(const ictr_ransac *r, const char *what, const double *fc, const double *cc, double kc,
+                         double inlthresh, uint64_t seed, RansacArgs &a) {
+  if (!std::isfinite(inlthresh)) return fail(ICTR_ERR_INVALID, "%s: inlthresh is not finite", what);
   if (!std::isfinite(kc) || !std::isfinite(fc[0]) || !std::isfinite(fc[1]) || fc[0] == 0.0 || fc[1] == 0.0 ||
       !std::isfinite(cc[0]) || !std::isfinite(cc[1]))
-    return fail(ICTR_ERR_INVALID, "ransac_run: the camera (fc, cc, kc) must be finite, fc non-zero");
-  r->stream = (hipStream_t)hip_stream;
+    return fail(ICTR_ERR_INVALID, "%s: the camera (fc, cc, kc) must be finite, fc non-zero", what);
   const RanLayout L = ran_layout(r);
-  RansacArgs a;
   memset(&a, 0, sizeof(a));
   a.pts = r->d_pts;
   a.n = r->n;
@@ -691,8 +688,6 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   a.seedmix = z ^ (z >> 31);
-  a.nsamples = nsamples;
-  a.maxtrials = maxtrials;
   a.hyp = r->d_hyp;
   a.draws = r->d_draws;
   a.status = r->d_status;
@@ -707,6 +702,24 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   a.o_cnt = reinterpret_cast<int *>(r->d_out + L.cnt);
   a.o_keep = reinterpret_cast<int *>(r->d_out + L.keep);
   a.o_cntf = reinterpret_cast<int *>(r->d_out + L.cntf);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples,
+                               int64_t maxtrials, double inlthresh, uint64_t seed, void *hip_stream) {
+  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ransac_run: NULL argument");
+  if (int rc = ran_refuse_pending(r, "ransac_run")) return rc;
+  if (!r->points_set) return fail(ICTR_ERR_STATE, "ransac_run: ictr_ransac_set_points has not been called");
+  if (nsamples < 1 || nsamples > r->smax)
+    return fail(ICTR_ERR_INVALID, "ransac_run: nsamples %lld (1 .. %lld, the size given at creation)",
+                (long long)nsamples, (long long)r->smax);
+  if (maxtrials < 1 || maxtrials > ((int64_t)1 << 40))
+    return fail(ICTR_ERR_INVALID, "ransac_run: maxtrials %lld (1 .. 2^40)", (long long)maxtrials);
+  RansacArgs a;
+  if (int rc = ran_fill_args(r, "ransac_run", fc, cc, kc, inlthresh, seed, a)) return rc;
+  r->stream = (hipStream_t)hip_stream;
+  a.nsamples = nsamples;
+  a.maxtrials = maxtrials;
   HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), r->stream));
   const int64_t K = r->chunk;
   const int64_t nchunks = (maxtrials + K - 1) / K;
@@ -779,6 +792,40 @@ extern "C" int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t
   for (long long q = 0; q < st.kept; ++q) {
     if (trial) trial[q] = ht[keep[q]];
     if (draws) memcpy(draws + 4 * q, hd + 4 * (size_t)keep[q], 4 * sizeof(int32_t));
+  }
+  return ICTR_OK;
+}
+
+// inspection: hypotheses and scores of trials [first_trial, first_trial + count), in the object's own chunks and tile,
+// on the null stream. No select runs and `done` stays clear, so every trial of the range is computed.
+extern "C" int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const double *cc, double kc, double inlthresh,
+                                        uint64_t seed, int64_t first_trial, int64_t count, int32_t *status,
+                                        int32_t *draws, double *hyp, uint32_t *cnt, uint64_t *words) {
+  if (!r || !fc || !cc || !status || !draws || !hyp || !cnt || !words)
+    return fail(ICTR_ERR_INVALID, "debug_ransac_trials: NULL argument");
+  if (int rc = ran_refuse_pending(r, "debug_ransac_trials")) return rc;
+  if (!r->points_set) return fail(ICTR_ERR_STATE, "debug_ransac_trials: ictr_ransac_set_points has not been called");
+  if (count < 1 || count > ((int64_t)1 << 20) || first_trial < 0 || first_trial > ((int64_t)1 << 40) - count)
+    return fail(ICTR_ERR_INVALID, "debug_ransac_trials: trials %lld + %lld (1 .. 2^20 trials below 2^40)",
+                (long long)first_trial, (long long)count);
+  RansacArgs a;
+  if (int rc = ran_fill_args(r, "debug_ransac_trials", fc, cc, kc, inlthresh, seed, a)) return rc;
+  a.nsamples = 1;
+  a.maxtrials = first_trial + count;
+  HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), nullptr));
+  const int64_t K = r->chunk;
+  const size_t W = (size_t)r->nwords;
+  for (int64_t done = 0; done < count; done += K) {
+    a.base = first_trial + done;
+    a.k = (int)std::min<int64_t>(K, count - done);
+    const size_t k = (size_t)a.k, o = (size_t)done;
+    launch_ransac_hyp_score(a, r->tile, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(status + o, r->d_status, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(draws + 4 * o, r->d_draws, sizeof(int32_t) * 4 * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hyp + 12 * o, r->d_hyp, sizeof(double) * 12 * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt + o, r->d_cnt, sizeof(uint32_t) * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(words + W * o, r->d_words, sizeof(uint64_t) * W * k, hipMemcpyDeviceToHost));
   }
   return ICTR_OK;
 }

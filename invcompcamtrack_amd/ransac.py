@@ -7,6 +7,8 @@ Semantics (0-based inside, 1-based inlier ids in files; deviations from the scri
 - trial ``t`` draws from a counter-based stream: ``u_k = mix(mix(seed) ^ ((t << 32) | k))``, ``mix`` = splitmix64,
   index ``((u_k >> 32) * N) >> 32``; repeats are skipped, the first 4 distinct indices are kept in draw order. This
   replaces ``randsample``: samples are not reproducible against MATLAB, but every run is bit-reproducible.
+  The shift is taken in 64 bits, so the stream has period 2^32 in ``t``: trial ``2^32 + j`` draws what trial ``j``
+  draws (and so computes the same hypothesis). Runs of 2^32 trials or more repeat themselves.
 - undistortion for the solver (:22-24): normalise, ``x_n <- x_d / (1 + kc |x_n|^2)`` 20 times, back to pixels. The
   one-coefficient model is not pinned by the reference (its ``func_undist_kc`` / ``func_reproject`` are not part of
   it); ``kc = 0`` is the plain pinhole.
@@ -426,6 +428,22 @@ class RansacSampler:
         sp = getattr(stream, "cuda_stream", stream)
         check(_lib.load().ictr_ransac_run(self._h, dp(fc), dp(cc), float(kc), int(nsamples), int(maxtrials),
                                           float(inlthresh), int(seed) & _M64, C.c_void_p(sp or 0)))
+
+    def debug_trials(self, fc, cc, inlthresh, kc=0.0, seed=0, first_trial=0, count=1):
+        """Inspection (ictr_debug_ransac_trials): the hypothesis and score kernels alone over trials first_trial ..
+        first_trial + count - 1, no selection. dict: status (count,), draws (count, 4), hyp (count, 12) = R row-major
+        then the camera centre, cnt (count,), words (count, nwords); hyp, cnt and words of a status-0 trial are
+        undefined."""
+        fc, cc = _fc_cc(fc, cc)
+        n = int(count)
+        status, draws = np.zeros(n, np.int32), np.zeros((n, 4), np.int32)
+        hyp, cnt, words = np.zeros((n, 12)), np.zeros(n, np.uint32), np.zeros((n, self.nwords), np.uint64)
+        i32 = C.POINTER(C.c_int32)
+        check(_lib.load().ictr_debug_ransac_trials(
+            self._h, dp(fc), dp(cc), float(kc), float(inlthresh), int(seed) & _M64, int(first_trial), n,
+            status.ctypes.data_as(i32), draws.ctypes.data_as(i32), dp(hyp), cnt.ctypes.data_as(C.POINTER(C.c_uint32)),
+            words.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return dict(status=status, draws=draws, hyp=hyp, cnt=cnt, words=words)
 
     def wait(self):
         L = _lib.load()
