@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "ictr_dev.h"
@@ -237,21 +238,11 @@ __global__ __launch_bounds__(kBlock) void k_gf_rank(const unsigned long long *__
 
 struct GfWork {
   int w = 0, h = 0, mindist = 0, win = 0, ncx = 0, ncells = 0;
-  double *lam = nullptr;
-  unsigned long long *key = nullptr, *lkey = nullptr;
-  int *idx = nullptr, *lidx = nullptr;
-  GfCtl *ctl = nullptr;
+  DevBuf<double> lam;
+  DevBuf<unsigned long long> key, lkey;
+  DevBuf<int> idx, lidx;
+  DevBuf<GfCtl> ctl;
 };
-
-static void gf_free(GfWork *g) {
-  if (g->lam) hipFree(g->lam);
-  if (g->key) hipFree(g->key);
-  if (g->lkey) hipFree(g->lkey);
-  if (g->idx) hipFree(g->idx);
-  if (g->lidx) hipFree(g->lidx);
-  if (g->ctl) hipFree(g->ctl);
-  *g = GfWork();
-}
 
 static int gf_alloc(GfWork *g, int w, int h, int mindist, int win) {
   if (w < 1 || h < 1 || mindist < 1 || win < 0) return fail(ICTR_ERR_INVALID, "good_features: needs mindist >= 1 and win >= 0");
@@ -265,30 +256,32 @@ static int gf_alloc(GfWork *g, int w, int h, int mindist, int win) {
   g->ncx = (w + mindist - 1) / mindist;
   g->ncells = g->ncx * ((h + mindist - 1) / mindist);
   const size_t nc = (size_t)g->ncells;
-  HIPCHK(hipMalloc((void **)&g->lam, sizeof(double) * (size_t)w * h));
-  HIPCHK(hipMalloc((void **)&g->key, sizeof(unsigned long long) * nc));
-  HIPCHK(hipMalloc((void **)&g->lkey, sizeof(unsigned long long) * nc));
-  HIPCHK(hipMalloc((void **)&g->idx, sizeof(int) * nc));
-  HIPCHK(hipMalloc((void **)&g->lidx, sizeof(int) * nc));
-  HIPCHK(hipMalloc((void **)&g->ctl, sizeof(GfCtl)));
-  return ICTR_OK;
+  if (int rc = g->lam.alloc(sizeof(double) * (size_t)w * h)) return rc;
+  if (int rc = g->key.alloc(sizeof(unsigned long long) * nc)) return rc;
+  if (int rc = g->lkey.alloc(sizeof(unsigned long long) * nc)) return rc;
+  if (int rc = g->idx.alloc(sizeof(int) * nc)) return rc;
+  if (int rc = g->lidx.alloc(sizeof(int) * nc)) return rc;
+  return g->ctl.alloc(sizeof(GfCtl));
 }
 
 // corners of the plane img (stride floats per row) -> out[maxcorners][2] (rows past the count are left as they are) and
 // *count, both in device memory
 static int gf_run(const GfWork &g, const float *img, int stride, int maxcorners, double quality, float *out, int *count,
                   hipStream_t s) {
-  HIPCHK(hipMemsetAsync(g.ctl, 0, sizeof(GfCtl), s));
+  double *lam = g.lam.get();
+  unsigned long long *key = g.key.get(), *lkey = g.lkey.get();
+  int *idx = g.idx.get(), *lidx = g.lidx.get();
+  GfCtl *ctl = g.ctl.get();
+  HIPCHK(hipMemsetAsync(ctl, 0, sizeof(GfCtl), s));
   const dim3 tiles((g.w + kGfTW - 1) / kGfTW, (g.h + kGfTH - 1) / kGfTH);
-  hipLaunchKernelGGL(k_gf_response, tiles, dim3(kBlock), gf_lds_bytes(g.win), s, img, stride, g.w, g.h, g.win, g.mindist, g.lam,
-                     g.ctl);
+  hipLaunchKernelGGL(k_gf_response, tiles, dim3(kBlock), gf_lds_bytes(g.win), s, img, stride, g.w, g.h, g.win, g.mindist, lam,
+                     ctl);
   const dim3 cg((g.ncells + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_gf_cells, cg, dim3(kBlock), 0, s, g.lam, g.w, g.h, g.mindist, quality, g.ctl, g.ncx, g.ncells, g.key,
-                     g.idx);
-  hipLaunchKernelGGL(k_gf_select, dim3(1), dim3(kGfSelBlock), 0, s, g.key, g.ncells, maxcorners, g.ctl, count);
-  hipLaunchKernelGGL(k_gf_compact, cg, dim3(kBlock), 0, s, g.key, g.idx, g.ncells, g.ctl, g.lkey, g.lidx);
+  hipLaunchKernelGGL(k_gf_cells, cg, dim3(kBlock), 0, s, lam, g.w, g.h, g.mindist, quality, ctl, g.ncx, g.ncells, key, idx);
+  hipLaunchKernelGGL(k_gf_select, dim3(1), dim3(kGfSelBlock), 0, s, key, g.ncells, maxcorners, ctl, count);
+  hipLaunchKernelGGL(k_gf_compact, cg, dim3(kBlock), 0, s, key, idx, g.ncells, ctl, lkey, lidx);
   const int rg = std::max(1, std::min((std::min(g.ncells, maxcorners) + kBlock - 1) / kBlock, 256));
-  hipLaunchKernelGGL(k_gf_rank, dim3(rg), dim3(kBlock), 0, s, g.lkey, g.lidx, g.ctl, maxcorners, g.w, out);
+  hipLaunchKernelGGL(k_gf_rank, dim3(rg), dim3(kBlock), 0, s, lkey, lidx, ctl, maxcorners, g.w, out);
   HIPCHK(hipGetLastError());
   return ICTR_OK;
 }
@@ -492,34 +485,24 @@ extern "C" int ictr_good_features(const ictr_pyramid *pyr, const float *img, int
   if (int rc = need_device()) return rc;
   const float *plane = nullptr;
   int stride = w;
-  float *stage = nullptr;
   if (pyr) {
     if (int rc = pyr_level0(pyr, &plane, &stride, &w, &h)) return rc;
   } else if (w < 1 || h < 1) {
     return fail(ICTR_ERR_INVALID, "good_features: bad image size");
   }
   GfWork g;
-  int rc = gf_alloc(&g, w, h, mindist, win);
-  float *d_out = nullptr;
-  hipError_t e = hipSuccess;
-  if (!rc && !pyr) {
-    e = hipMalloc((void **)&stage, sizeof(float) * (size_t)w * h);
-    if (e == hipSuccess) e = hipMemcpy(stage, img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice);
-    plane = stage;
+  if (int rc = gf_alloc(&g, w, h, mindist, win)) return rc;
+  DevBuf<float> stage, d_out;
+  if (!pyr) {
+    if (int rc = stage.alloc(sizeof(float) * (size_t)w * h)) return rc;
+    HIPCHK(hipMemcpy(stage.get(), img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice));
+    plane = stage.get();
   }
-  if (!rc && e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(float) * 2 * (size_t)maxcorners + sizeof(int));
-  if (!rc && e == hipSuccess) {
-    int *d_count = reinterpret_cast<int *>(d_out + 2 * (size_t)maxcorners);
-    rc = gf_run(g, plane, stride, maxcorners, quality, d_out, d_count, nullptr);
-    if (!rc) e = hipMemcpy(out_count, d_count, sizeof(int), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && *out_count > 0)
-      e = hipMemcpy(out_xy, d_out, sizeof(float) * 2 * (size_t)*out_count, hipMemcpyDeviceToHost);
-  }
-  if (stage) hipFree(stage);
-  if (d_out) hipFree(d_out);
-  gf_free(&g);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "good_features failed: %s", hipGetErrorString(e));
+  if (int rc = d_out.alloc(sizeof(float) * 2 * (size_t)maxcorners + sizeof(int))) return rc;
+  int *d_count = reinterpret_cast<int *>(d_out.get() + 2 * (size_t)maxcorners);
+  if (int rc = gf_run(g, plane, stride, maxcorners, quality, d_out.get(), d_count, nullptr)) return rc;
+  HIPCHK(hipMemcpy(out_count, d_count, sizeof(int), hipMemcpyDeviceToHost));
+  if (*out_count > 0) HIPCHK(hipMemcpy(out_xy, d_out.get(), sizeof(float) * 2 * (size_t)*out_count, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -529,20 +512,16 @@ struct ictr_flowgrid {
   float *pts = nullptr, *out = nullptr, *draw = nullptr, *d = nullptr;
   int *status = nullptr, *iters = nullptr, *rowhas = nullptr;
   unsigned char *lost = nullptr;
-  char *arena = nullptr;
+  DevBuf<char> arena;  // everything above
 };
 static FgDev fg_dev(const ictr_flowgrid *g) { return FgDev{g->d, g->nx, g->ny, g->step, g->w, g->h}; }
 
-extern "C" void ictr_flowgrid_destroy(ictr_flowgrid *g) {
-  if (!g) return;
-  if (g->arena) hipFree(g->arena);
-  delete g;
-}
+extern "C" void ictr_flowgrid_destroy(ictr_flowgrid *g) { delete g; }
 extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step) {
   if (!out || w < 1 || h < 1 || step < 1 || step / 2 >= w || step / 2 >= h)
     return fail(ICTR_ERR_INVALID, "flowgrid: bad arguments (the grid needs at least one node)");
   if (int rc = need_device()) return rc;
-  ictr_flowgrid *g = new ictr_flowgrid;
+  auto g = std::make_unique<ictr_flowgrid>();
   g->w = w;
   g->h = h;
   g->step = step;
@@ -552,12 +531,8 @@ extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step)
   const size_t K = (size_t)g->K;
   // pts 2K f32 | out 2K | draw 2K | d 2K | status K i32 | iters K | rowhas ny | lost K u8
   const size_t bytes = 4 * (8 * K + 2 * K + (size_t)g->ny) + K;
-  hipError_t e = hipMalloc((void **)&g->arena, bytes);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ICTR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  }
-  float *f = reinterpret_cast<float *>(g->arena);
+  if (int rc = g->arena.alloc(bytes)) return rc;
+  float *f = reinterpret_cast<float *>(g->arena.get());
   g->pts = f;
   g->out = f + 2 * K;
   g->draw = f + 4 * K;
@@ -566,7 +541,7 @@ extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step)
   g->iters = g->status + K;
   g->rowhas = g->iters + K;
   g->lost = reinterpret_cast<unsigned char *>(g->rowhas + g->ny);
-  *out = g;
+  *out = g.release();
   return ICTR_OK;
 }
 extern "C" int ictr_flowgrid_dims(const ictr_flowgrid *g, int *nx, int *ny) {
@@ -624,33 +599,28 @@ extern "C" int ictr_flowgrid_gather(const ictr_flowgrid *g, const double *xy, in
   if (!g || K < 0 || (K > 0 && (!xy || !out)) || K > INT32_MAX) return fail(ICTR_ERR_INVALID, "flowgrid_gather: bad arguments");
   if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
   if (K == 0) return ICTR_OK;
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, sizeof(double) * 4 * (size_t)K));
-  hipError_t e = hipDeviceSynchronize();  // a compute on another stream has finished
-  if (e == hipSuccess) e = hipMemcpy(d, xy, sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_fg_gather, dim3(((int)K + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, fg_dev(g), d, (int)K,
-                       d + 2 * K);
-    e = hipMemcpy(out, d + 2 * K, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "flowgrid_gather failed: %s", hipGetErrorString(e));
+  DevBuf<double> buf;
+  if (int rc = buf.alloc(sizeof(double) * 4 * (size_t)K)) return rc;
+  double *d = buf.get();
+  HIPCHK(hipDeviceSynchronize());  // a compute on another stream has finished
+  HIPCHK(hipMemcpy(d, xy, sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_fg_gather, dim3(((int)K + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, fg_dev(g), d, (int)K,
+                     d + 2 * K);
+  HIPCHK(hipMemcpy(out, d + 2 * K, sizeof(double) * 2 * (size_t)K, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 extern "C" int ictr_flowgrid_dense(const ictr_flowgrid *g, float *out, int on_device) {
   if (!g || !out) return fail(ICTR_ERR_INVALID, "flowgrid_dense: NULL argument");
   if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
   const size_t bytes = sizeof(float) * 2 * (size_t)g->w * g->h;
-  float *d = out;
-  if (!on_device) HIPCHK(hipMalloc((void **)&d, bytes));
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_fg_dense, dim3((g->w + 63) / 64, (g->h + kWaves - 1) / kWaves), dim3(kBlock), 0, nullptr, fg_dev(g),
-                       reinterpret_cast<float2 *>(d));
-    e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
-  }
-  if (!on_device) hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "flowgrid_dense failed: %s", hipGetErrorString(e));
+  DevBuf<float> own;  // the field on the device when `out` is host memory
+  if (!on_device)
+    if (int rc = own.alloc(bytes)) return rc;
+  float *d = on_device ? out : own.get();
+  HIPCHK(hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_fg_dense, dim3((g->w + 63) / 64, (g->h + kWaves - 1) / kWaves), dim3(kBlock), 0, nullptr, fg_dev(g),
+                     reinterpret_cast<float2 *>(d));
+  HIPCHK(on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -659,53 +629,42 @@ struct ictr_pointtrack {
   float eps = 0;
   double quality = 0, th_ratio = 0, th_abs = 0;
   int64_t nframes = 0;          // frames pushed; frcounter = max(nframes - 1, 0)
-  ictr_pyramid *pyr[2] = {nullptr, nullptr};
-  ictr_flowgrid *fw = nullptr, *bw = nullptr;
+  ictr_pyramid *pyr[2] = {nullptr, nullptr};  // owned; opaque here, so released through ictr_pyramid_destroy
+  std::unique_ptr<ictr_flowgrid> fw, bw;
   GfWork gf;
   PtGeom geom;
-  char *ring = nullptr;        // bsize slots
-  float *corners = nullptr;    // [mc][2] staging of the corner picker
-  std::vector<void *> store;   // pinned host copies of the blocks that left the window, in block order
+  DevBuf<char> ring;                 // bsize slots
+  DevBuf<float> corners;             // [mc][2] staging of the corner picker
+  std::vector<PinBuf<char>> store;   // pinned host copies of the blocks that left the window, in block order
+  ~ictr_pointtrack() {
+    (void)hipDeviceSynchronize();  // nothing in flight reads what goes now
+    ictr_pyramid_destroy(pyr[0]);
+    ictr_pyramid_destroy(pyr[1]);
+  }
 };
 
-extern "C" void ictr_pointtrack_destroy(ictr_pointtrack *t) {
-  if (!t) return;
-  (void)hipDeviceSynchronize();
-  for (void *p : t->store) hipHostFree(p);
-  ictr_pyramid_destroy(t->pyr[0]);
-  ictr_pyramid_destroy(t->pyr[1]);
-  ictr_flowgrid_destroy(t->fw);
-  ictr_flowgrid_destroy(t->bw);
-  gf_free(&t->gf);
-  if (t->ring) hipFree(t->ring);
-  if (t->corners) hipFree(t->corners);
-  delete t;
-}
+extern "C" void ictr_pointtrack_destroy(ictr_pointtrack *t) { delete t; }
 extern "C" int ictr_pointtrack_create(ictr_pointtrack **out, int w, int h, int bsize, int maxcorners, int lv_f, int psz,
                                       int step, int maxiter, float eps, double quality, int mindist, int win,
                                       double th_ratio, double th_abs) {
   if (!out || bsize < 1 || maxcorners < 1 || psz < 1 || psz > 32 || lv_f < 0 || lv_f > 15 || maxiter < 0)
     return fail(ICTR_ERR_INVALID, "pointtrack: bad arguments (bsize >= 1, maxcorners >= 1, psz 1..32)");
   if (int rc = need_device()) return rc;
-  ictr_pointtrack *t = new ictr_pointtrack;
+  auto t = std::make_unique<ictr_pointtrack>();
   t->w = w, t->h = h, t->bsize = bsize, t->mc = maxcorners, t->lv_f = lv_f, t->psz = psz, t->step = step;
   t->maxiter = maxiter, t->eps = eps, t->quality = quality, t->mindist = mindist, t->win = win;
   t->th_ratio = th_ratio, t->th_abs = th_abs;
   t->geom = pt_geom(maxcorners, bsize);
-  int rc = ictr_flowgrid_create(&t->fw, w, h, step);
-  if (!rc) rc = ictr_flowgrid_create(&t->bw, w, h, step);
-  if (!rc) rc = gf_alloc(&t->gf, w, h, mindist, win);
-  if (!rc) {
-    hipError_t e = hipMalloc((void **)&t->ring, t->geom.bytes * (size_t)bsize);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->corners, sizeof(float) * 2 * (size_t)maxcorners);
-    if (e == hipSuccess) e = hipMemset(t->ring, 0, t->geom.bytes * (size_t)bsize);
-    if (e != hipSuccess) rc = fail(ICTR_ERR_HIP, "pointtrack: allocation failed: %s", hipGetErrorString(e));
+  for (auto *grid : {&t->fw, &t->bw}) {
+    ictr_flowgrid *g = nullptr;
+    if (int rc = ictr_flowgrid_create(&g, w, h, step)) return rc;
+    grid->reset(g);
   }
-  if (rc) {
-    ictr_pointtrack_destroy(t);
-    return rc;
-  }
-  *out = t;
+  if (int rc = gf_alloc(&t->gf, w, h, mindist, win)) return rc;
+  if (int rc = t->ring.alloc(t->geom.bytes * (size_t)bsize)) return rc;
+  if (int rc = t->corners.alloc(sizeof(float) * 2 * (size_t)maxcorners)) return rc;
+  HIPCHK(hipMemset(t->ring.get(), 0, t->geom.bytes * (size_t)bsize));
+  *out = t.release();
   return ICTR_OK;
 }
 extern "C" int ictr_pointtrack_push_frame(ictr_pointtrack *t, const float *img) {
@@ -722,27 +681,30 @@ extern "C" int ictr_pointtrack_push_frame(ictr_pointtrack *t, const float *img) 
   if (f == 0) return ICTR_OK;
   const int64_t k = f - 1;  // the pair (k, k + 1); addframe number k + 1
   ictr_pyramid *pa = t->pyr[k & 1], *pb = cur;
-  if (int rc = ictr_flowgrid_compute(t->fw, pa, pb, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
-  if (int rc = ictr_flowgrid_compute(t->bw, pb, pa, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
+  if (int rc = ictr_flowgrid_compute(t->fw.get(), pa, pb, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
+  if (int rc = ictr_flowgrid_compute(t->bw.get(), pb, pa, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
   const float *plane;
   int stride, w, h;
   if (int rc = pyr_level0(pa, &plane, &stride, &w, &h)) return rc;
   const PtGeom &g = t->geom;
   const dim3 grid((g.mc + kBlock - 1) / kBlock), blk(kBlock);
-  const PtSlot open = pt_slot(t->ring + g.bytes * (size_t)(k % g.bsize), g);
-  if (int rc = gf_run(t->gf, plane, stride, g.mc, t->quality, t->corners, open.count, s)) return rc;
-  hipLaunchKernelGGL(k_pt_open, grid, blk, 0, s, open, t->corners, g.mc, g.bsize);
+  char *ring = t->ring.get();
+  const PtSlot open = pt_slot(ring + g.bytes * (size_t)(k % g.bsize), g);
+  if (int rc = gf_run(t->gf, plane, stride, g.mc, t->quality, t->corners.get(), open.count, s)) return rc;
+  hipLaunchKernelGGL(k_pt_open, grid, blk, 0, s, open, t->corners.get(), g.mc, g.bsize);
   for (int age = 0; age <= g.bsize - 2 && age <= k; ++age) {  // the blocks k - age, column age -> age + 1
-    const PtSlot sl = pt_slot(t->ring + g.bytes * (size_t)((k - age) % g.bsize), g);
-    hipLaunchKernelGGL(k_pt_advance, grid, blk, 0, s, sl, g.bsize, age, fg_dev(t->fw), fg_dev(t->bw), t->th_ratio, t->th_abs);
+    const PtSlot sl = pt_slot(ring + g.bytes * (size_t)((k - age) % g.bsize), g);
+    hipLaunchKernelGGL(k_pt_advance, grid, blk, 0, s, sl, g.bsize, age, fg_dev(t->fw.get()), fg_dev(t->bw.get()), t->th_ratio,
+                       t->th_abs);
   }
   HIPCHK(hipGetLastError());
   const int64_t gone = k - g.bsize + 1;  // leaves the window with this pair; its slot is opened again by pair k + 1
   if (gone >= 0) {
-    void *hp = nullptr;
-    HIPCHK(hipHostMalloc(&hp, g.bytes, hipHostMallocDefault));
-    t->store.push_back(hp);
-    HIPCHK(hipMemcpyAsync(hp, t->ring + g.bytes * (size_t)(gone % g.bsize), g.bytes, hipMemcpyDeviceToHost, s));
+    PinBuf<char> hp;
+    if (int rc = hp.alloc(g.bytes)) return rc;
+    t->store.push_back(std::move(hp));
+    HIPCHK(hipMemcpyAsync(t->store.back().get(), ring + g.bytes * (size_t)(gone % g.bsize), g.bytes, hipMemcpyDeviceToHost,
+                          s));
   }
   return ICTR_OK;
 }
@@ -761,10 +723,10 @@ extern "C" int ictr_pointtrack_read_block(ictr_pointtrack *t, int64_t block, flo
   std::vector<char> tmp;
   const char *src;
   if (block < (int64_t)t->store.size()) {
-    src = (const char *)t->store[(size_t)block];
+    src = t->store[(size_t)block].get();
   } else {
     tmp.resize(g.bytes);
-    HIPCHK(hipMemcpy(tmp.data(), t->ring + g.bytes * (size_t)(block % g.bsize), g.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), t->ring.get() + g.bytes * (size_t)(block % g.bsize), g.bytes, hipMemcpyDeviceToHost));
     src = tmp.data();
   }
   const PtSlot sl = pt_slot(src, g);

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -51,27 +52,20 @@ extern "C" int ictr_set_device(int device) {
 extern "C" int ictr_stream_read_bandwidth(size_t bytes, int reps, double *gbps_out) {
   if (!gbps_out || bytes < (1u << 20) || reps < 1) return fail(ICTR_ERR_INVALID, "stream_read_bandwidth: bad arguments");
   if (int rc = need_device()) return rc;
-  float *buf = nullptr, *sink = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc((void **)&buf, bytes);
-  if (e == hipSuccess) e = hipMalloc((void **)&sink, sizeof(float) * 8192 * kBlock);
-  if (e == hipSuccess) e = hipMemset(buf, 0, bytes);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
+  DevBuf<float> buf, sink;
+  Event e0, e1;
+  if (int rc = buf.alloc(bytes)) return rc;
+  if (int rc = sink.alloc(sizeof(float) * 8192 * kBlock)) return rc;
+  HIPCHK(hipMemset(buf.get(), 0, bytes));
+  if (int rc = e0.create()) return rc;
+  if (int rc = e1.create()) return rc;
   float ms = 0.0f;
-  if (e == hipSuccess) {
-    launch_stream_read(buf, bytes / 4, sink, nullptr);  // warm-up
-    e = hipEventRecord(e0, nullptr);
-    for (int r = 0; r < reps && e == hipSuccess; ++r) launch_stream_read(buf, bytes / 4, sink, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (buf) (void)hipFree(buf);
-  if (sink) (void)hipFree(sink);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "stream_read_bandwidth: %s", hipGetErrorString(e));
+  launch_stream_read(buf.get(), bytes / 4, sink.get(), nullptr);  // warm-up
+  HIPCHK(hipEventRecord(e0.get(), nullptr));
+  for (int r = 0; r < reps; ++r) launch_stream_read(buf.get(), bytes / 4, sink.get(), nullptr);
+  HIPCHK(hipEventRecord(e1.get(), nullptr));
+  HIPCHK(hipEventSynchronize(e1.get()));
+  HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
   *gbps_out = (double)bytes * reps / (ms * 1e-3) / 1e9;
   return ICTR_OK;
 }
@@ -82,19 +76,17 @@ extern "C" int ictr_debug_transpose_reduce(const float *vals, float *out, int *p
   if (!vals || !out || !patch_of_lane || !kind_of_lane || (patches_per_wave != 16 && patches_per_wave != 32))
     return fail(ICTR_ERR_INVALID, "debug_transpose_reduce: bad arguments (patches per wave 16 or 32)");
   if (int rc = need_device()) return rc;
-  float *dv = nullptr, *dout = nullptr;
-  int *dp = nullptr;
-  hipError_t e = hipMalloc((void **)&dv, sizeof(float) * 64 * 64);
-  if (e == hipSuccess) e = hipMalloc((void **)&dout, sizeof(float) * 64);
-  if (e == hipSuccess) e = hipMalloc((void **)&dp, sizeof(int) * 128);
-  if (e == hipSuccess) e = hipMemcpy(dv, vals, sizeof(float) * 64 * 64, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_debug_transpose_reduce(dv, dout, dp, dp + 64, patches_per_wave, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(float) * 64, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(patch_of_lane, dp, sizeof(int) * 64, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(kind_of_lane, dp + 64, sizeof(int) * 64, hipMemcpyDeviceToHost);
-  for (void *p : {(void *)dv, (void *)dout, (void *)dp})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_transpose_reduce: %s", hipGetErrorString(e));
+  DevBuf<float> dv, dout;
+  DevBuf<int> dpb;
+  if (int rc = dv.alloc(sizeof(float) * 64 * 64)) return rc;
+  if (int rc = dout.alloc(sizeof(float) * 64)) return rc;
+  if (int rc = dpb.alloc(sizeof(int) * 128)) return rc;
+  int *dp = dpb.get();
+  HIPCHK(hipMemcpy(dv.get(), vals, sizeof(float) * 64 * 64, hipMemcpyHostToDevice));
+  HIPCHK(launch_debug_transpose_reduce(dv.get(), dout.get(), dp, dp + 64, patches_per_wave, nullptr));
+  HIPCHK(hipMemcpy(out, dout.get(), sizeof(float) * 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(patch_of_lane, dp, sizeof(int) * 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(kind_of_lane, dp + 64, sizeof(int) * 64, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -106,29 +98,26 @@ extern "C" int ictr_debug_wave_solve(const float *H36, const float *b6, int64_t 
     return fail(ICTR_ERR_INVALID, "debug_wave_solve: bad arguments (1 .. 2^20 systems)");
   if (int rc = need_device()) return rc;
   const size_t N = (size_t)n;
-  float *df = nullptr;  // H[36 n] | b[6 n] | x[6 n] | lu[36 n]
-  int *di = nullptr;    // rank[n] | nonzero[n] | rowmap[6 n] | colmap[6 n]
-  ProbState *st = nullptr;
-  hipError_t e = hipMalloc((void **)&df, sizeof(float) * 84 * N);
-  if (e == hipSuccess) e = hipMalloc((void **)&di, sizeof(int) * 14 * N);
-  if (e == hipSuccess) e = hipMalloc((void **)&st, sizeof(ProbState) * N);
-  if (e == hipSuccess) e = hipMemset(st, 0, sizeof(ProbState) * N);
-  if (e == hipSuccess) e = hipMemset(df + 42 * N, 0xff, sizeof(float) * 42 * N);
-  if (e == hipSuccess) e = hipMemset(di, 0xff, sizeof(int) * 14 * N);
-  if (e == hipSuccess) e = hipMemcpy(df, H36, sizeof(float) * 36 * N, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(df + 36 * N, b6, sizeof(float) * 6 * N, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = launch_debug_wave_solve(df, df + 36 * N, (int)n, st, through_state, df + 42 * N, di, di + N, di + 2 * N,
-                                di + 8 * N, df + 48 * N, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(x6, df + 42 * N, sizeof(float) * 6 * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(lu36, df + 48 * N, sizeof(float) * 36 * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(rank, di, sizeof(int) * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(nonzero, di + N, sizeof(int) * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(rowmap6, di + 2 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(colmap6, di + 8 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost);
-  for (void *p : {(void *)df, (void *)di, (void *)st})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_wave_solve: %s", hipGetErrorString(e));
+  DevBuf<float> dfb;  // H[36 n] | b[6 n] | x[6 n] | lu[36 n]
+  DevBuf<int> dib;    // rank[n] | nonzero[n] | rowmap[6 n] | colmap[6 n]
+  DevBuf<ProbState> st;
+  if (int rc = dfb.alloc(sizeof(float) * 84 * N)) return rc;
+  if (int rc = dib.alloc(sizeof(int) * 14 * N)) return rc;
+  if (int rc = st.alloc(sizeof(ProbState) * N, true)) return rc;
+  float *df = dfb.get();
+  int *di = dib.get();
+  HIPCHK(hipMemset(df + 42 * N, 0xff, sizeof(float) * 42 * N));
+  HIPCHK(hipMemset(di, 0xff, sizeof(int) * 14 * N));
+  HIPCHK(hipMemcpy(df, H36, sizeof(float) * 36 * N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(df + 36 * N, b6, sizeof(float) * 6 * N, hipMemcpyHostToDevice));
+  HIPCHK(launch_debug_wave_solve(df, df + 36 * N, (int)n, st.get(), through_state, df + 42 * N, di, di + N, di + 2 * N,
+                                 di + 8 * N, df + 48 * N, nullptr));
+  HIPCHK(hipMemcpy(x6, df + 42 * N, sizeof(float) * 6 * N, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(lu36, df + 48 * N, sizeof(float) * 36 * N, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rank, di, sizeof(int) * N, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nonzero, di + N, sizeof(int) * N, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rowmap6, di + 2 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(colmap6, di + 8 * N, sizeof(int) * 6 * N, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 // inspection: the device builds of se3_exp<float> (in p[6] -> out G[12]) / se3_log<float> (in G[12] -> out p[6])
@@ -136,13 +125,12 @@ extern "C" int ictr_debug_se3(const float *in, int64_t n, int log_not_exp, float
   if (!in || !out || n < 1 || n > (1 << 24)) return fail(ICTR_ERR_INVALID, "debug_se3: bad arguments");
   if (int rc = need_device()) return rc;
   const size_t ni = (size_t)n * (log_not_exp ? 12 : 6), no = (size_t)n * (log_not_exp ? 6 : 12);
-  float *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, sizeof(float) * (ni + no));
-  if (e == hipSuccess) e = hipMemcpy(d, in, sizeof(float) * ni, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_debug_se3(d, d + ni, (long long)n, log_not_exp ? 1 : 0, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, d + ni, sizeof(float) * no, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "debug_se3: %s", hipGetErrorString(e));
+  DevBuf<float> buf;
+  if (int rc = buf.alloc(sizeof(float) * (ni + no))) return rc;
+  float *d = buf.get();
+  HIPCHK(hipMemcpy(d, in, sizeof(float) * ni, hipMemcpyHostToDevice));
+  HIPCHK(launch_debug_se3(d, d + ni, (long long)n, log_not_exp ? 1 : 0, nullptr));
+  HIPCHK(hipMemcpy(out, d + ni, sizeof(float) * no, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -251,8 +239,8 @@ struct ictr_pyramid {
   std::vector<int> w, h, sw, sh;
   std::vector<float *> img, dx, dy;  // device planes
   std::vector<float *> pack;         // with gradients: the level again as interleaved {img, dx, dy, 0} texels
-  float *arena = nullptr;
-  float *stage = nullptr;  // device copy of a host frame handed to ictr_pyramid_rebuild (allocated on first use)
+  DevBuf<float> arena;  // every plane of every level
+  DevBuf<float> stage;  // device copy of a host frame handed to ictr_pyramid_rebuild (allocated on first use)
 };
 
 // internal: what ictr_icgn.hip needs to know about a pyramid
@@ -287,7 +275,7 @@ static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad
   if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f > 15 || pad < 0 || getgrad < 0 || getgrad > 2)
     return fail(ICTR_ERR_INVALID, "pyramid: bad arguments");
   if (int rc = need_device()) return rc;
-  ictr_pyramid *p = new ictr_pyramid;
+  auto p = std::make_unique<ictr_pyramid>();
   p->nlev = lv_f + 1;
   p->pad = pad;
   p->w0 = w;
@@ -297,10 +285,7 @@ static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad
   for (int l = 0; l <= lv_f; ++l) {
     int wl, hl;
     level_size(w, h, l, &wl, &hl);
-    if (wl < 1 || hl < 1) {
-      delete p;
-      return fail(ICTR_ERR_INVALID, "pyramid: level %d is empty", l);
-    }
+    if (wl < 1 || hl < 1) return fail(ICTR_ERR_INVALID, "pyramid: level %d is empty", l);
     p->w.push_back(wl);
     p->h.push_back(hl);
     p->sw.push_back(wl + 2 * pad);
@@ -309,12 +294,8 @@ static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad
     plane = (plane + 63) / 64 * 64;  // 256-B aligned planes
     total += plane * (getgrad == 1 ? 7 : getgrad == 2 ? 1 : 3);
   }
-  hipError_t e = hipMalloc((void **)&p->arena, total * sizeof(float));
-  if (e != hipSuccess) {
-    delete p;
-    return fail(ICTR_ERR_HIP, "hipMalloc(%zu) failed: %s", total * sizeof(float), hipGetErrorString(e));
-  }
-  float *cur = p->arena;
+  if (int rc = p->arena.alloc(total * sizeof(float))) return rc;
+  float *cur = p->arena.get();
   for (int l = 0; l <= lv_f; ++l) {
     size_t plane = (size_t)p->sw[l] * p->sh[l];
     plane = (plane + 63) / 64 * 64;
@@ -324,7 +305,7 @@ static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad
     p->pack.push_back(getgrad == 1 ? cur + 3 * plane : nullptr);
     cur += (getgrad == 1 ? 7 : getgrad == 2 ? 1 : 3) * plane;
   }
-  *out = p;
+  *out = p.release();
   return ICTR_OK;
 }
 
@@ -352,23 +333,21 @@ extern "C" int ictr_pyramid_rebuild_device(ictr_pyramid *p, const float *img_dev
 extern "C" int ictr_pyramid_rebuild(ictr_pyramid *p, const float *img, void *hip_stream) {
   if (!p || !img) return fail(ICTR_ERR_INVALID, "pyramid_rebuild: NULL argument");
   const size_t bytes = sizeof(float) * (size_t)p->w0 * p->h0;
-  if (!p->stage) HIPCHK(hipMalloc((void **)&p->stage, bytes));
+  if (!p->stage)
+    if (int rc = p->stage.alloc(bytes)) return rc;
   // pageable host memory: the copy has left `img` when the call returns; the kernels are ordered behind it on the stream
-  HIPCHK(hipMemcpyAsync(p->stage, img, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
-  return pyramid_build(p, p->stage, (hipStream_t)hip_stream);
+  HIPCHK(hipMemcpyAsync(p->stage.get(), img, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+  return pyramid_build(p, p->stage.get(), (hipStream_t)hip_stream);
 }
 
 extern "C" int ictr_pyramid_create_device(ictr_pyramid **out, const float *img_dev, int w, int h, int lv_f, int getgrad,
                                           int pad, void *hip_stream) {
   if (!img_dev) return fail(ICTR_ERR_INVALID, "pyramid: img is NULL");
-  ictr_pyramid *p = nullptr;
-  if (int rc = pyramid_alloc(&p, w, h, lv_f, getgrad, pad)) return rc;
-  int rc = pyramid_build(p, img_dev, (hipStream_t)hip_stream);
-  if (rc) {
-    ictr_pyramid_destroy(p);
-    return rc;
-  }
-  *out = p;
+  ictr_pyramid *raw = nullptr;
+  if (int rc = pyramid_alloc(&raw, w, h, lv_f, getgrad, pad)) return rc;
+  std::unique_ptr<ictr_pyramid> p(raw);
+  if (int rc = pyramid_build(raw, img_dev, (hipStream_t)hip_stream)) return rc;
+  *out = p.release();
   return ICTR_OK;
 }
 
@@ -376,53 +355,40 @@ extern "C" int ictr_pyramid_create(ictr_pyramid **out, const float *img, int w, 
                                    int pad) {
   if (!img) return fail(ICTR_ERR_INVALID, "pyramid: img is NULL");
   if (int rc = need_device()) return rc;
-  float *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, sizeof(float) * (size_t)w * h));
-  hipError_t e = hipMemcpy(d, img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(d);
-    return fail(ICTR_ERR_HIP, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
-  }
-  int rc = ictr_pyramid_create_device(out, d, w, h, lv_f, getgrad, pad, nullptr);
-  hipError_t e2 = hipDeviceSynchronize();
-  hipFree(d);
+  DevBuf<float> d;
+  if (int rc = d.alloc(sizeof(float) * (size_t)w * h)) return rc;
+  HIPCHK(hipMemcpy(d.get(), img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice));
+  ictr_pyramid *raw = nullptr;
+  const int rc = ictr_pyramid_create_device(&raw, d.get(), w, h, lv_f, getgrad, pad, nullptr);
+  std::unique_ptr<ictr_pyramid> p(raw);
+  const hipError_t e = hipDeviceSynchronize();  // the kernels have read `d` before it goes
   if (rc) return rc;
-  if (e2 != hipSuccess) return fail(ICTR_ERR_HIP, "pyramid kernels failed: %s", hipGetErrorString(e2));
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "pyramid kernels failed: %s", hipGetErrorString(e));
+  *out = p.release();
   return ICTR_OK;
 }
 
 extern "C" int ictr_pyramid_create_from_host_planes(ictr_pyramid **out, const float **img_pyr, const float **dx_pyr,
                                                     const float **dy_pyr, int w, int h, int lv_f, int pad) {
   if (!img_pyr) return fail(ICTR_ERR_INVALID, "pyramid: img_pyr is NULL");
-  ictr_pyramid *p = nullptr;
-  if (int rc = pyramid_alloc(&p, w, h, lv_f, dx_pyr && dy_pyr, pad)) return rc;
+  ictr_pyramid *raw = nullptr;
+  if (int rc = pyramid_alloc(&raw, w, h, lv_f, dx_pyr && dy_pyr, pad)) return rc;
+  std::unique_ptr<ictr_pyramid> p(raw);
   for (int l = 0; l <= lv_f; ++l) {
     const size_t bytes = sizeof(float) * (size_t)p->sw[l] * p->sh[l];
-    hipError_t e = hipMemcpy(p->img[l], img_pyr[l], bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && dx_pyr && dy_pyr) {
-      e = hipMemcpy(p->dx[l], dx_pyr[l], bytes, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(p->dy[l], dy_pyr[l], bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-      ictr_pyramid_destroy(p);
-      return fail(ICTR_ERR_HIP, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
+    HIPCHK(hipMemcpy(p->img[l], img_pyr[l], bytes, hipMemcpyHostToDevice));
+    if (dx_pyr && dy_pyr) {
+      HIPCHK(hipMemcpy(p->dx[l], dx_pyr[l], bytes, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(p->dy[l], dy_pyr[l], bytes, hipMemcpyHostToDevice));
     }
     if (p->getgrad) launch_pyr_pack(p->img[l], p->dx[l], p->dy[l], p->pack[l], (size_t)p->sw[l] * p->sh[l], nullptr);
   }
-  if (p->getgrad && hipStreamSynchronize(nullptr) != hipSuccess) {
-    ictr_pyramid_destroy(p);
-    return fail(ICTR_ERR_HIP, "pyramid: packing kernels failed");
-  }
-  *out = p;
+  if (p->getgrad) HIPCHK(hipStreamSynchronize(nullptr));
+  *out = p.release();
   return ICTR_OK;
 }
 
-extern "C" void ictr_pyramid_destroy(ictr_pyramid *p) {
-  if (!p) return;
-  if (p->arena) hipFree(p->arena);
-  if (p->stage) hipFree(p->stage);
-  delete p;
-}
+extern "C" void ictr_pyramid_destroy(ictr_pyramid *p) { delete p; }
 extern "C" int ictr_pyramid_levels(const ictr_pyramid *p) { return p ? p->nlev : 0; }
 extern "C" int ictr_pyramid_level_dims(const ictr_pyramid *p, int level, int *sw, int *sh) {
   if (!p || level < 0 || level >= p->nlev) return fail(ICTR_ERR_INVALID, "pyramid: bad level");
@@ -455,26 +421,18 @@ static int get_patch_impl(const ictr_pyramid *pyr, int level, const float *mids,
     if (!(mids[i] >= 0 && mids[i] <= (float)pyr->w[level] && mids[i + K] >= 0 && mids[i + K] <= (float)pyr->h[level]))
       return fail(ICTR_ERR_INVALID, "get_patch: centre %lld outside the image", (long long)i);
   const size_t nf = (size_t)K * psz * psz;
-  float *d_m = nullptr, *d_o = nullptr;
-  HIPCHK(hipMalloc((void **)&d_m, sizeof(float) * 2 * K));
-  hipError_t e = hipMalloc((void **)&d_o, sizeof(float) * nf * (grad ? 3 : 1));
-  if (e != hipSuccess) {
-    hipFree(d_m);
-    return fail(ICTR_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
+  DevBuf<float> d_m, d_ob;
+  if (int rc = d_m.alloc(sizeof(float) * 2 * K)) return rc;
+  if (int rc = d_ob.alloc(sizeof(float) * nf * (grad ? 3 : 1))) return rc;
+  float *d_o = d_ob.get();
+  HIPCHK(hipMemcpy(d_m.get(), mids, sizeof(float) * 2 * K, hipMemcpyHostToDevice));
+  launch_getpatch(pyr->img[level], grad ? pyr->dx[level] : nullptr, grad ? pyr->dy[level] : nullptr, d_m.get(), (int)K, psz,
+                  pyr->sw[level], dopatchnorm, d_o, grad ? d_o + nf : nullptr, grad ? d_o + 2 * nf : nullptr, nullptr);
+  HIPCHK(hipMemcpy(out, d_o, sizeof(float) * nf, hipMemcpyDeviceToHost));
+  if (grad) {
+    HIPCHK(hipMemcpy(out_dx, d_o + nf, sizeof(float) * nf, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_dy, d_o + 2 * nf, sizeof(float) * nf, hipMemcpyDeviceToHost));
   }
-  e = hipMemcpy(d_m, mids, sizeof(float) * 2 * K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_getpatch(pyr->img[level], grad ? pyr->dx[level] : nullptr, grad ? pyr->dy[level] : nullptr, d_m, (int)K, psz,
-                    pyr->sw[level], dopatchnorm, d_o, grad ? d_o + nf : nullptr, grad ? d_o + 2 * nf : nullptr, nullptr);
-    e = hipMemcpy(out, d_o, sizeof(float) * nf, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && grad) {
-      e = hipMemcpy(out_dx, d_o + nf, sizeof(float) * nf, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_dy, d_o + 2 * nf, sizeof(float) * nf, hipMemcpyDeviceToHost);
-    }
-  }
-  hipFree(d_m);
-  hipFree(d_o);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "get_patch failed: %s", hipGetErrorString(e));
   return ICTR_OK;
 }
 extern "C" int ictr_get_patch(const ictr_pyramid *pyr, int level, const float *mids, int64_t K, int psz,
@@ -498,16 +456,13 @@ extern "C" int ictr_ncc_score(const ictr_pyramid *pyr_back, const ictr_pyramid *
       return fail(ICTR_ERR_INVALID, "ncc_score: pyramids differ at level %d or padding < psz", level);
   if (K == 0) return ICTR_OK;
   if (int rc = need_device()) return rc;
-  float *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, sizeof(float) * 7 * K));
-  hipError_t e = hipMemcpy(d, mids, sizeof(float) * 6 * K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_ncc(pyr_back->img[level], pyr_ref->img[level], pyr_fwd->img[level], d, (int)K, psz, pyr_ref->sw[level],
-               (float)pyr_ref->w[level], (float)pyr_ref->h[level], w_back, w_fwd, d + 6 * K, nullptr);
-    e = hipMemcpy(out_corr, d + 6 * K, sizeof(float) * K, hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "ncc_score failed: %s", hipGetErrorString(e));
+  DevBuf<float> buf;
+  if (int rc = buf.alloc(sizeof(float) * 7 * K)) return rc;
+  float *d = buf.get();
+  HIPCHK(hipMemcpy(d, mids, sizeof(float) * 6 * K, hipMemcpyHostToDevice));
+  launch_ncc(pyr_back->img[level], pyr_ref->img[level], pyr_fwd->img[level], d, (int)K, psz, pyr_ref->sw[level],
+             (float)pyr_ref->w[level], (float)pyr_ref->h[level], w_back, w_fwd, d + 6 * K, nullptr);
+  HIPCHK(hipMemcpy(out_corr, d + 6 * K, sizeof(float) * K, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -521,25 +476,20 @@ extern "C" int ictr_flow_gather(const void *disp_u, const void *disp_v, int is_f
   if (K == 0) return ICTR_OK;
   if (int rc = need_device()) return rc;
   const size_t fb = (size_t)H * W * (is_f64 ? 8 : 4);
-  char *d_f = nullptr;
-  double *d_xy = nullptr;
-  hipError_t e = hipMalloc((void **)&d_xy, sizeof(double) * 4 * K);
+  DevBuf<char> d_f;
+  DevBuf<double> d_xy;
+  if (int rc = d_xy.alloc(sizeof(double) * 4 * K)) return rc;
   const void *du = disp_u, *dv = disp_v;
-  if (e == hipSuccess && !fields_on_device) {
-    e = hipMalloc((void **)&d_f, fb * 2);
-    if (e == hipSuccess) e = hipMemcpy(d_f, disp_u, fb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && disp_v) e = hipMemcpy(d_f + fb, disp_v, fb, hipMemcpyHostToDevice);
-    du = d_f;
-    dv = disp_v ? d_f + fb : nullptr;
+  if (!fields_on_device) {
+    if (int rc = d_f.alloc(fb * 2)) return rc;
+    HIPCHK(hipMemcpy(d_f.get(), disp_u, fb, hipMemcpyHostToDevice));
+    if (disp_v) HIPCHK(hipMemcpy(d_f.get() + fb, disp_v, fb, hipMemcpyHostToDevice));
+    du = d_f.get();
+    dv = disp_v ? d_f.get() + fb : nullptr;
   }
-  if (e == hipSuccess) e = hipMemcpy(d_xy, xy, sizeof(double) * 2 * K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_flow_gather(du, dv, is_f64, H, W, d_xy, (int)K, d_xy + 2 * K, nullptr);
-    e = hipMemcpy(out, d_xy + 2 * K, sizeof(double) * 2 * K, hipMemcpyDeviceToHost);
-  }
-  if (d_f) hipFree(d_f);
-  if (d_xy) hipFree(d_xy);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "flow_gather failed: %s", hipGetErrorString(e));
+  HIPCHK(hipMemcpy(d_xy.get(), xy, sizeof(double) * 2 * K, hipMemcpyHostToDevice));
+  launch_flow_gather(du, dv, is_f64, H, W, d_xy.get(), (int)K, d_xy.get() + 2 * K, nullptr);
+  HIPCHK(hipMemcpy(out, d_xy.get() + 2 * K, sizeof(double) * 2 * K, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -558,19 +508,14 @@ extern "C" int ictr_extract_bil_patches(const double *img, int H, int W, int C, 
   if (K == 0) return ICTR_OK;
   if (int rc = need_device()) return rc;
   const size_t ib = sizeof(double) * (size_t)H * W * C, ob = sizeof(double) * (size_t)K * 4 * half * half * C;
-  double *d_img = nullptr, *d_pts = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc((void **)&d_img, ib);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_pts, sizeof(double) * 2 * K);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_out, ob);
-  if (e == hipSuccess) e = hipMemcpy(d_img, img, ib, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_pts, pts, sizeof(double) * 2 * K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_bil_patches(d_img, H, W, C, d_pts, (int)K, half, d_out, nullptr);
-    e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
-  }
-  for (void *p_ : {(void *)d_img, (void *)d_pts, (void *)d_out})
-    if (p_) hipFree(p_);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "extract_bil_patches failed: %s", hipGetErrorString(e));
+  DevBuf<double> d_img, d_pts, d_out;
+  if (int rc = d_img.alloc(ib)) return rc;
+  if (int rc = d_pts.alloc(sizeof(double) * 2 * K)) return rc;
+  if (int rc = d_out.alloc(ob)) return rc;
+  HIPCHK(hipMemcpy(d_img.get(), img, ib, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_pts.get(), pts, sizeof(double) * 2 * K, hipMemcpyHostToDevice));
+  launch_bil_patches(d_img.get(), H, W, C, d_pts.get(), (int)K, half, d_out.get(), nullptr);
+  HIPCHK(hipMemcpy(out, d_out.get(), ob, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -635,20 +580,16 @@ static int project_impl(const ictr_pose *pose, const float *pt3d, float *pt3d_ro
   const int M = pose->op->maxpttrack;
   if (nopoints > M) return fail(ICTR_ERR_INVALID, "project_pt: nopoints > maxpttrack");
   if (nopoints == 0) return ICTR_OK;
-  float *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, sizeof(float) * (size_t)(8 * M + 12)));
-  float *d3 = d, *dr = d + 3 * M, *d2 = d + 6 * M, *dG = d + 8 * M;
-  hipError_t e = hipMemcpy(d3, pt3d, sizeof(float) * 3 * M, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dG, pose->G, sizeof(float) * 12, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d2, pt2d, sizeof(float) * 2 * M, hipMemcpyHostToDevice);
-  if (e == hipSuccess && pt3d_rot) e = hipMemcpy(dr, pt3d_rot, sizeof(float) * 3 * M, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_project_generic(d3, pt3d_rot ? dr : nullptr, d2, (int)nopoints, M, dG, level_cam(pose->cam, sc), nullptr);
-    e = hipMemcpy(pt2d, d2, sizeof(float) * 2 * M, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && pt3d_rot) e = hipMemcpy(pt3d_rot, dr, sizeof(float) * 3 * M, hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "project_pt failed: %s", hipGetErrorString(e));
+  DevBuf<float> buf;
+  if (int rc = buf.alloc(sizeof(float) * (size_t)(8 * M + 12))) return rc;
+  float *d3 = buf.get(), *dr = d3 + 3 * M, *d2 = d3 + 6 * M, *dG = d3 + 8 * M;
+  HIPCHK(hipMemcpy(d3, pt3d, sizeof(float) * 3 * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dG, pose->G, sizeof(float) * 12, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d2, pt2d, sizeof(float) * 2 * M, hipMemcpyHostToDevice));
+  if (pt3d_rot) HIPCHK(hipMemcpy(dr, pt3d_rot, sizeof(float) * 3 * M, hipMemcpyHostToDevice));
+  launch_project_generic(d3, pt3d_rot ? dr : nullptr, d2, (int)nopoints, M, dG, level_cam(pose->cam, sc), nullptr);
+  HIPCHK(hipMemcpy(pt2d, d2, sizeof(float) * 2 * M, hipMemcpyDeviceToHost));
+  if (pt3d_rot) HIPCHK(hipMemcpy(pt3d_rot, dr, sizeof(float) * 3 * M, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 extern "C" int ictr_pose_project_pt(const ictr_pose *pose, const float *pt3d, float *pt2d, int64_t nopoints, int sc) {
@@ -681,7 +622,7 @@ struct TrackPlan {
 };
 // device mailbox of an in-launch exchange; it grows, never shrinks
 struct Mailbox {
-  unsigned long long *d = nullptr;
+  DevBuf<unsigned long long> d;
   size_t bytes = 0;
   unsigned epoch = 0;  // tags of a launch: epoch << 12 | exchange number
 };
@@ -710,12 +651,12 @@ struct ictr_batch {
   bool trace_on = false;
   bool projected = false;
   // device
-  float *d_pt3d = nullptr, *d_pt3d_ref = nullptr, *d_pt2d = nullptr, *d_T = nullptr, *d_Gx = nullptr,
-        *d_Gy = nullptr, *d_coef = nullptr, *d_partH = nullptr, *d_partb = nullptr, *d_red = nullptr;
-  ProbState *d_st = nullptr;
-  PlaneSet *d_planes = nullptr;
-  ictr_trace_rec *d_trace = nullptr;
-  int *d_trace_count = nullptr;
+  DevBuf<float> d_pt3d, d_pt3d_ref, d_pt2d, d_T, d_Gx, d_Gy, d_coef, d_partH, d_partb, d_red_own;
+  float *d_red = nullptr;  // d_red_own, or the caller's (ictr_batch_set_reduction_buffer)
+  DevBuf<ProbState> d_st;  // the records, and behind them the plane table ...
+  PlaneSet *d_planes = nullptr;  // ... (inside d_st's block, up_planes_offset)
+  DevBuf<ictr_trace_rec> d_trace;
+  DevBuf<int> d_trace_count;
   int trace_cap = 0;
   // host mirrors
   std::vector<ProbHost> probs;
@@ -725,14 +666,14 @@ struct ictr_batch {
   std::vector<float> h_stage;
   // optional HIP-event timing (bench.py): per level e0 -> setup kernel -> e1 -> iteration launches -> e2
   bool timing = false;
-  std::vector<hipEvent_t> ev;  // 3 per level
+  std::vector<Event> ev;  // 3 per level
   std::vector<char> ev_used;
-  std::vector<hipEvent_t> evk;  // 2 per (level, iteration): around the accumulate kernel alone
+  std::vector<Event> evk;  // 2 per (level, iteration): around the accumulate kernel alone
   int evk_iters = 0;
   bool evk_valid = true;  // the per-iteration kernel events of the last tracking were recorded (not in the resident form)
   ResXchg xchg = {};  // sharded resident form (ictr_batch_set_peer_exchange): xchg.world > 1 = the resident launches sum
                      // H and b over the ranks themselves
-  unsigned *d_xseq = nullptr;  // [B] exchange counters of that form
+  DevBuf<unsigned> d_xseq;  // [B] exchange counters of that form
   int otf = 0;       // every reference pyramid of the current tracking is builder-made (1), and some of them image-only
                      // (2): see EngineDev.otf
   int maxpts = 0;    // largest nopoints over the problems of the current tracking (set by ictr_batch_begin)
@@ -743,23 +684,26 @@ struct ictr_batch {
   hipStream_t cap_stream = nullptr;  // capture needs a non-null stream; nothing ever executes on it
   bool graph_broken = false;      // capture / instantiate failed once: plain launches from then on
   int phase_it = 0;  // iteration counter of the phase API (event slot of the next iter_accumulate)
-  float *d_red_own = nullptr;
   // results of the last track_async: the final states are copied to pinned host memory in-stream and an event marks
   // the end, so that get_poses / the timing getters wait for THIS tracking only and the caller may already have
   // enqueued the next one on the same stream (another engine): the host runs one step ahead of the GPU
-  ProbState *h_st_pin = nullptr;
+  PinBuf<ProbState> h_st_pin;
   ProbState *d_st_mirror = nullptr;  // h_st_pin as the device sees it (the one-launch tracker stores final states there)
-  char *h_up_pin = nullptr;  // pinned staging of the per-tracking uploads (states + plane table): truly asynchronous
+  PinBuf<char> h_up_pin;  // pinned staging of the per-tracking uploads (states + plane table): truly asynchronous
   // mailboxes of the in-launch exchanges, allocated on first use (exchange_prepare): the team form of the one-launch
   // tracker ([B][2][team][32] granules, ictr_track1.hip "Teams") and the resident-iteration form (per slot a gather box
   // and a broadcast box, ictr_resident.hip)
   Mailbox team_mail, res_mail;
   int team_target = 0;        // points per workgroup aimed at (0: automatic, < 0: no teams); ictr_batch_set_team
   int team_lo = 128, team_hi = 8192;  // problem sizes (points) served by teams: lo < maxpts <= hi
-  int *h_team_err = nullptr;  // pinned: an exchange of some launch timed out (sticky)
+  PinBuf<int> h_team_err;     // an exchange of some launch timed out (sticky)
   int *d_team_err = nullptr;  // ... as the device sees it
-  hipEvent_t done_ev = nullptr, up_ev = nullptr;
+  Event done_ev, up_ev;
   bool done_valid = false, up_pending = false;
+  ~ictr_batch() {  // the graph and its capture stream go before any buffer
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    if (cap_stream) (void)hipStreamDestroy(cap_stream);
+  }
 };
 
 // the plane table's place behind the B records in their common device block / staging buffer (16-byte aligned)
@@ -767,28 +711,6 @@ static size_t up_planes_offset(int B) { return (sizeof(ProbState) * (size_t)B + 
 int ictr::env_int(const char *name, int dflt) {
   const char *s = getenv(name);
   return s ? atoi(s) : dflt;
-}
-
-static void batch_free(ictr_batch *b) {
-  if (!b) return;
-  for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : b->evk) (void)hipEventDestroy(e);
-  if (b->gexec) (void)hipGraphExecDestroy(b->gexec);
-  if (b->cap_stream) (void)hipStreamDestroy(b->cap_stream);
-  if (b->done_ev) (void)hipEventDestroy(b->done_ev);
-  if (b->up_ev) (void)hipEventDestroy(b->up_ev);
-  if (b->h_st_pin) (void)hipHostFree(b->h_st_pin);
-  if (b->h_up_pin) (void)hipHostFree(b->h_up_pin);
-  if (b->h_team_err) (void)hipHostFree(b->h_team_err);
-  if (b->team_mail.d) (void)hipFree(b->team_mail.d);
-  if (b->res_mail.d) (void)hipFree(b->res_mail.d);
-  if (b->d_xseq) (void)hipFree(b->d_xseq);
-  b->d_red = b->d_red_own;
-  for (void *p : {(void *)b->d_pt3d, (void *)b->d_pt3d_ref, (void *)b->d_pt2d, (void *)b->d_T, (void *)b->d_Gx,
-                  (void *)b->d_Gy, (void *)b->d_coef, (void *)b->d_partH, (void *)b->d_partb, (void *)b->d_red,
-                  (void *)b->d_st, (void *)b->d_trace, (void *)b->d_trace_count})  // (d_planes lives in d_st's block)
-    if (p) hipFree(p);
-  delete b;
 }
 
 // kernel-selection bits as the launchers see them: any robustness option routes P = 8 through the any-size kernels
@@ -811,20 +733,20 @@ static EngineDev engine_dev(const ictr_batch *b) {
   e.otf = b->otf;
   e.robust = b->robust;
   e.huber_k = b->huber_k;
-  e.pt3d = b->d_pt3d;
-  e.pt3d_ref = b->d_pt3d_ref;
-  e.pt2d = b->d_pt2d;
-  e.T = b->d_T;
-  e.Gx = b->d_Gx;
-  e.Gy = b->d_Gy;
-  e.coef = b->d_coef;
-  e.st = b->d_st;
+  e.pt3d = b->d_pt3d.get();
+  e.pt3d_ref = b->d_pt3d_ref.get();
+  e.pt2d = b->d_pt2d.get();
+  e.T = b->d_T.get();
+  e.Gx = b->d_Gx.get();
+  e.Gy = b->d_Gy.get();
+  e.coef = b->d_coef.get();
+  e.st = b->d_st.get();
   e.planes = b->d_planes;
-  e.partH = b->d_partH;
-  e.partb = b->d_partb;
+  e.partH = b->d_partH.get();
+  e.partb = b->d_partb.get();
   e.red = b->d_red;
-  e.trace.rec = b->trace_on ? b->d_trace : nullptr;
-  e.trace.count = b->d_trace_count;
+  e.trace.rec = b->trace_on ? b->d_trace.get() : nullptr;
+  e.trace.count = b->d_trace_count.get();
   e.trace.capacity = b->trace_cap;
   return e;
 }
@@ -845,7 +767,7 @@ extern "C" int ictr_batch_create(ictr_batch **out, const ictr_cam *cam, const ic
     return fail(ICTR_ERR_INVALID, "batch_create: bad arguments (1..65535 problems)");
   if (int rc = check_op(op, cam)) return rc;
   if (int rc = need_device()) return rc;
-  ictr_batch *b = new ictr_batch;
+  auto b = std::make_unique<ictr_batch>();
   b->cam = cam;
   b->op = op;
   b->B = (int)nproblems;
@@ -864,50 +786,40 @@ extern "C" int ictr_batch_create(ictr_batch **out, const ictr_cam *cam, const ic
   const int64_t cap = std::min<int64_t>(kMaxGridX, std::max<int64_t>(64, 2 * kMaxGridX / (int64_t)B));
   b->gridx = (int)std::min<int64_t>(std::max<int64_t>((groups + kWaves - 1) / kWaves, 1), cap);
   b->trace_cap = std::max(1, (int)L * std::max(1, op->maxiter));
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-  };
-  alloc((void **)&b->d_pt3d, sizeof(float) * B * 3 * M);
-  alloc((void **)&b->d_pt3d_ref, sizeof(float) * B * 3 * M);
-  alloc((void **)&b->d_pt2d, sizeof(float) * B * L * 2 * M);
-  alloc((void **)&b->d_T, sizeof(float) * B * M * n);
-  alloc((void **)&b->d_Gx, sizeof(float) * B * M * n);
-  alloc((void **)&b->d_Gy, sizeof(float) * B * M * n);
-  alloc((void **)&b->d_coef, sizeof(float) * B * M * kCoefStride);
-  alloc((void **)&b->d_partH, sizeof(float) * B * b->gridx * kPartHStride);
-  alloc((void **)&b->d_partb, sizeof(float) * B * b->gridx * kPartBStride);
-  alloc((void **)&b->d_red, sizeof(float) * B * kRedStride);
+  if (int rc = b->d_pt3d.alloc(sizeof(float) * B * 3 * M, true)) return rc;
+  if (int rc = b->d_pt3d_ref.alloc(sizeof(float) * B * 3 * M, true)) return rc;
+  if (int rc = b->d_pt2d.alloc(sizeof(float) * B * L * 2 * M, true)) return rc;
+  if (int rc = b->d_T.alloc(sizeof(float) * B * M * n, true)) return rc;
+  if (int rc = b->d_Gx.alloc(sizeof(float) * B * M * n, true)) return rc;
+  if (int rc = b->d_Gy.alloc(sizeof(float) * B * M * n, true)) return rc;
+  if (int rc = b->d_coef.alloc(sizeof(float) * B * M * kCoefStride, true)) return rc;
+  if (int rc = b->d_partH.alloc(sizeof(float) * B * b->gridx * kPartHStride, true)) return rc;
+  if (int rc = b->d_partb.alloc(sizeof(float) * B * b->gridx * kPartBStride, true)) return rc;
+  if (int rc = b->d_red_own.alloc(sizeof(float) * B * kRedStride, true)) return rc;
+  b->d_red = b->d_red_own.get();
   // the records and the plane table in ONE block: one upload per SetPose round instead of two (each small transfer is an
   // engine switch of 5-8 us in front of the tracking's first kernel)
-  alloc((void **)&b->d_st, up_planes_offset(B) + sizeof(PlaneSet) * B * L);
-  if (e == hipSuccess) b->d_planes = reinterpret_cast<PlaneSet *>(reinterpret_cast<char *>(b->d_st) + up_planes_offset(B));
-  alloc((void **)&b->d_trace, sizeof(ictr_trace_rec) * b->trace_cap);
-  alloc((void **)&b->d_trace_count, sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_st_pin, sizeof(ProbState) * B, hipHostMallocDefault);
-  if (e == hipSuccess)
-    e = hipHostMalloc((void **)&b->h_up_pin, up_planes_offset(B) + sizeof(PlaneSet) * B * L, hipHostMallocDefault);
-  if (e == hipSuccess && hipHostGetDevicePointer((void **)&b->d_st_mirror, b->h_st_pin, 0) != hipSuccess) {
+  if (int rc = b->d_st.alloc(up_planes_offset(B) + sizeof(PlaneSet) * B * L, true)) return rc;
+  b->d_planes = reinterpret_cast<PlaneSet *>(reinterpret_cast<char *>(b->d_st.get()) + up_planes_offset(B));
+  if (int rc = b->d_trace.alloc(sizeof(ictr_trace_rec) * b->trace_cap, true)) return rc;
+  if (int rc = b->d_trace_count.alloc(sizeof(int), true)) return rc;
+  if (int rc = b->h_st_pin.alloc(sizeof(ProbState) * B)) return rc;
+  if (int rc = b->h_up_pin.alloc(up_planes_offset(B) + sizeof(PlaneSet) * B * L)) return rc;
+  if (hipHostGetDevicePointer((void **)&b->d_st_mirror, b->h_st_pin.get(), 0) != hipSuccess) {
     (void)hipGetLastError();
     b->d_st_mirror = nullptr;  // no mapped view: final states come back by copy
   }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&b->done_ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&b->up_ev, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    batch_free(b);
-    return fail(ICTR_ERR_HIP, "batch_create: device allocation failed: %s", hipGetErrorString(e));
-  }
-  b->d_red_own = b->d_red;
+  if (int rc = b->done_ev.create(hipEventDisableTiming)) return rc;
+  if (int rc = b->up_ev.create(hipEventDisableTiming)) return rc;
   b->probs.resize(B);
   b->h_st.resize(B);
   b->h_planes.resize(B * L);
   b->h_pt2d.assign(2 * M, 0.0f);
   b->h_stage.assign(3 * M, 0.0f);
-  *out = b;
+  *out = b.release();
   return ICTR_OK;
 }
-extern "C" void ictr_batch_destroy(ictr_batch *b) { batch_free(b); }
+extern "C" void ictr_batch_destroy(ictr_batch *b) { delete b; }
 extern "C" int ictr_batch_set_stream(ictr_batch *b, void *hip_stream) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
   b->stream = (hipStream_t)hip_stream;
@@ -950,9 +862,10 @@ extern "C" int ictr_batch_set_peer_exchange(ictr_batch *b, ictr_p2p *p) {
   if (x.cap < (long long)kXchgPerPair * b->B)
     return fail(ICTR_ERR_INVALID, "set_peer_exchange: the mailboxes hold %lld granules per rank, %d x %d needed", x.cap,
                 kXchgPerPair, b->B);
-  if (!b->d_xseq) HIPCHK(hipMalloc((void **)&b->d_xseq, sizeof(unsigned) * b->B));
-  HIPCHK(hipMemsetAsync(b->d_xseq, 0, sizeof(unsigned) * b->B, b->stream));
-  x.xseq = b->d_xseq;
+  if (!b->d_xseq)
+    if (int rc = b->d_xseq.alloc(sizeof(unsigned) * b->B)) return rc;
+  HIPCHK(hipMemsetAsync(b->d_xseq.get(), 0, sizeof(unsigned) * b->B, b->stream));
+  x.xseq = b->d_xseq.get();
   b->xchg = x;
   return ICTR_OK;
 }
@@ -976,10 +889,10 @@ static int set3dpoints_impl(ictr_batch *b, int64_t problem, double *pt_in, int64
   ProbHost &ph = b->probs[problem];
   const size_t M = b->M, n = b->n;
   // ResetOdometer (odometer.cpp:580-609): patch / sd state of this problem back to zero
-  HIPCHK(hipMemsetAsync(b->d_T + problem * M * n, 0, sizeof(float) * M * n, b->stream));
-  HIPCHK(hipMemsetAsync(b->d_Gx + problem * M * n, 0, sizeof(float) * M * n, b->stream));
-  HIPCHK(hipMemsetAsync(b->d_Gy + problem * M * n, 0, sizeof(float) * M * n, b->stream));
-  HIPCHK(hipMemsetAsync(b->d_coef + problem * M * kCoefStride, 0, sizeof(float) * M * kCoefStride, b->stream));
+  HIPCHK(hipMemsetAsync(b->d_T.get() + problem * M * n, 0, sizeof(float) * M * n, b->stream));
+  HIPCHK(hipMemsetAsync(b->d_Gx.get() + problem * M * n, 0, sizeof(float) * M * n, b->stream));
+  HIPCHK(hipMemsetAsync(b->d_Gy.get() + problem * M * n, 0, sizeof(float) * M * n, b->stream));
+  HIPCHK(hipMemsetAsync(b->d_coef.get() + problem * M * kCoefStride, 0, sizeof(float) * M * kCoefStride, b->stream));
   ph.meanshift[0] = ph.meanshift[1] = ph.meanshift[2] = 0;
   ph.varval = 0;
   ph.npts = (int)std::min<int64_t>(nopoints_in, b->M);
@@ -1020,7 +933,7 @@ static int set3dpoints_impl(ictr_batch *b, int64_t problem, double *pt_in, int64
       s[i + 2 * M] = (float)p3[i];
     }
   }
-  HIPCHK(hipMemcpyAsync(b->d_pt3d + problem * 3 * M, s, sizeof(float) * 3 * M, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->d_pt3d.get() + problem * 3 * M, s, sizeof(float) * 3 * M, hipMemcpyHostToDevice, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));  // h_stage is reused by the next call
   return ICTR_OK;
 }
@@ -1145,12 +1058,13 @@ static int begin_device(ictr_batch *b, bool project = true) {
   const int maxpts = project ? b->maxpts : 0;  // (!project: the tracking's own launch projects, see track_enqueue)
   {
     const size_t nst = sizeof(ProbState) * b->B, npl = sizeof(PlaneSet) * b->h_planes.size();
-    if (b->up_pending) HIPCHK(hipEventSynchronize(b->up_ev));  // the previous upload has left the staging buffer
+    if (b->up_pending) HIPCHK(hipEventSynchronize(b->up_ev.get()));  // the previous upload has left the staging buffer
     const size_t off = up_planes_offset(b->B);
-    memcpy(b->h_up_pin, b->h_st.data(), nst);
-    memcpy(b->h_up_pin + off, b->h_planes.data(), npl);
-    HIPCHK(hipMemcpyAsync(b->d_st, b->h_up_pin, off + npl, hipMemcpyHostToDevice, b->stream));  // (d_planes follows d_st)
-    HIPCHK(hipEventRecord(b->up_ev, b->stream));
+    memcpy(b->h_up_pin.get(), b->h_st.data(), nst);
+    memcpy(b->h_up_pin.get() + off, b->h_planes.data(), npl);
+    // (d_planes follows d_st)
+    HIPCHK(hipMemcpyAsync(b->d_st.get(), b->h_up_pin.get(), off + npl, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(b->up_ev.get(), b->stream));
     b->up_pending = true;
   }
   if (maxpts > 0) {  // (the launch also clears the trace counter)
@@ -1158,7 +1072,7 @@ static int begin_device(ictr_batch *b, bool project = true) {
     for (int l = 0; l < b->nlev; ++l) cams[l] = level_cam(b->cam, l);
     launch_project_ref(engine_dev(b), cams, maxpts, b->stream);
   } else {
-    HIPCHK(hipMemsetAsync(b->d_trace_count, 0, sizeof(int), b->stream));
+    HIPCHK(hipMemsetAsync(b->d_trace_count.get(), 0, sizeof(int), b->stream));
   }
   HIPCHK(hipGetLastError());
   return ICTR_OK;
@@ -1225,7 +1139,7 @@ extern "C" int ictr_batch_iter_accumulate(ictr_batch *b, int level) {
   const LevelLaunch ll = level_launch(b, nullptr, level);
   const int first = b->phase_it == 0;
   const int ke = 2 * (level * b->evk_iters + b->phase_it);
-  launch_iter_main(e, lc, ll, first, b->stream, tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
+  launch_iter_main(e, lc, ll, first, b->stream, tk ? b->evk[ke].get() : nullptr, tk ? b->evk[ke + 1].get() : nullptr);
   if (tk && b->phase_it + 1 == std::min(b->op->maxiter, b->evk_iters)) b->ev_used[level] = 2;  // kernel events complete
   b->phase_it++;
   launch_iter_tail(e, ll, first, b->stream);
@@ -1491,35 +1405,34 @@ static double team_timeout_s() {
 static int exchange_prepare(ictr_batch *b, Mailbox *m, size_t need, const char *what, int mute, hipStream_t s,
                             Exchange *x) {
   if (need > m->bytes) {
-    if (m->d) {
-      HIPCHK(hipStreamSynchronize(s));  // an earlier launch may still be polling the old mailbox
-      HIPCHK(hipFree(m->d));
-      *m = Mailbox{};
-    }
+    if (m->d) HIPCHK(hipStreamSynchronize(s));  // an earlier launch may still be polling the old mailbox
+    m->d.reset();
+    m->bytes = 0;
     // granules are written and polled with agent-scope accesses; uncached device memory keeps them out of the L2s
-    hipError_t e = hipExtMallocWithFlags((void **)&m->d, need, hipDeviceMallocUncached);
-    if (e != hipSuccess) {
+    unsigned long long *uncached = nullptr;
+    if (hipExtMallocWithFlags((void **)&uncached, need, hipDeviceMallocUncached) == hipSuccess) {
+      m->d.adopt(uncached);
+    } else {
       (void)hipGetLastError();
-      e = hipMalloc((void **)&m->d, need);
+      if (m->d.alloc(need)) return fail(ICTR_ERR_HIP, "%s mailbox allocation failed (%zu bytes)", what, need);
     }
-    if (e == hipSuccess) e = hipMemsetAsync(m->d, 0, need, s);
-    if (e != hipSuccess) return fail(ICTR_ERR_HIP, "%s mailbox allocation failed: %s", what, hipGetErrorString(e));
+    HIPCHK(hipMemsetAsync(m->d.get(), 0, need, s));
     m->bytes = need;
     m->epoch = 0;
   }
   if (!b->h_team_err) {  // the pinned sticky time-out flag, shared by every exchange of the batch
-    HIPCHK(hipHostMalloc((void **)&b->h_team_err, sizeof(int), hipHostMallocDefault));
-    *b->h_team_err = 0;
-    HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err, 0));
+    if (int rc = b->h_team_err.alloc(sizeof(int))) return rc;
+    *b->h_team_err.get() = 0;
+    HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err.get(), 0));
   }
   m->epoch += 1;
   if (m->epoch >= (1u << 20)) {  // the epoch field wrapped: forget every old tag
-    HIPCHK(hipMemsetAsync(m->d, 0, m->bytes, s));
+    HIPCHK(hipMemsetAsync(m->d.get(), 0, m->bytes, s));
     m->epoch = 1;
   }
   x->tag0 = m->epoch << 12;
   x->limit = (unsigned long long)(team_timeout_s() * 1e8);
-  x->mail = m->d;
+  x->mail = m->d.get();
   x->err = b->d_team_err;
   x->mute = mute;
   return ICTR_OK;
@@ -1576,21 +1489,21 @@ static int enqueue_level_kernels(ictr_batch *b, const EngineDev &e, const TrackP
   b->evk_valid = tk;  // (resident: no per-iteration launches, the kernel-time getters report zeros)
   for (int sl = b->op->lv_f; sl >= b->op->lv_l; --sl) {
     const LevelCam lc = level_cam(b->cam, sl);
-    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 0], s));
+    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 0].get(), s));
     const LevelLaunch ll = level_launch(b, &p, sl);
     launch_ref_level(e, lc, ll, !resident, s);
-    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1], s));
+    if (events) HIPCHK(hipEventRecord(b->ev[3 * sl + 1].get(), s));
     if (resident) {
       if (int rc = launch_resident(b, e, lc, ll, p, s)) return rc;
     } else {
       for (int it = 0; it < mi; ++it) {
         const int ke = 2 * (sl * b->evk_iters + it);
-        launch_iter_main(e, lc, ll, it == 0, s, tk ? b->evk[ke] : nullptr, tk ? b->evk[ke + 1] : nullptr);
+        launch_iter_main(e, lc, ll, it == 0, s, tk ? b->evk[ke].get() : nullptr, tk ? b->evk[ke + 1].get() : nullptr);
         launch_iter_tail(e, ll, it == 0, s);
       }
     }
     if (events) {
-      HIPCHK(hipEventRecord(b->ev[3 * sl + 2], s));
+      HIPCHK(hipEventRecord(b->ev[3 * sl + 2].get(), s));
       b->ev_used[sl] = 1;
     }
   }
@@ -1671,11 +1584,11 @@ static int enqueue_levels(ictr_batch *b) {
 // (T1Args in ictr_track1.hip) and writes the final states to the mirror itself: no upload copies, no fill, no projection
 // launch, no read-back copy. With project_here the records are uploaded and the launch projects and mirrors itself.
 static int track_enqueue(ictr_batch *b) {
-  if (b->h_team_err && *(volatile int *)b->h_team_err) {
+  if (b->h_team_err && *(volatile int *)b->h_team_err.get()) {
     // the previous tracking of this batch ran into an exchange time-out (reported by its wait): let whatever it left on
     // the stream finish, then start clean -- mailbox tags carry the launch epoch, nothing of the failed launch survives
     HIPCHK(hipStreamSynchronize(b->stream));
-    *(volatile int *)b->h_team_err = 0;
+    *(volatile int *)b->h_team_err.get() = 0;
   }
   const bool begun = b->projected;
   if (!begun)
@@ -1700,8 +1613,8 @@ static int track_enqueue(ictr_batch *b) {
     mirrored = p.project_here != 0;
   }
   if (!mirrored)
-    HIPCHK(hipMemcpyAsync(b->h_st_pin, b->d_st, sizeof(ProbState) * b->B, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipEventRecord(b->done_ev, b->stream));
+    HIPCHK(hipMemcpyAsync(b->h_st_pin.get(), b->d_st.get(), sizeof(ProbState) * b->B, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipEventRecord(b->done_ev.get(), b->stream));
   b->done_valid = true;
   return ICTR_OK;
 }
@@ -1715,7 +1628,7 @@ extern "C" int ictr_batch_track_async(ictr_batch *b) {
 // an in-launch exchange of the last tracking timed out (team form of the one-launch tracker, resident-iteration form):
 // its results are invalid. The flag stays set until the next tracking is enqueued (track_enqueue).
 static int team_error_check(const ictr_batch *b) {
-  if (b->h_team_err && *(volatile int *)b->h_team_err)
+  if (b->h_team_err && *(volatile int *)b->h_team_err.get())
     return fail(ICTR_ERR_HIP, "%s: a workgroup waited in vain for its peers' partial sums (in-launch exchange timed out "
                               "after %.3f s; are all workgroups of the launch resident?); the results of this tracking "
                               "are invalid",
@@ -1726,7 +1639,7 @@ static int team_error_check(const ictr_batch *b) {
 // wait for the engine's last tracking (not for whatever else was enqueued on the stream after it)
 static int batch_wait(ictr_batch *b) {
   if (b->done_valid)
-    HIPCHK(hipEventSynchronize(b->done_ev));
+    HIPCHK(hipEventSynchronize(b->done_ev.get()));
   else
     HIPCHK(hipStreamSynchronize(b->stream));
   return team_error_check(b);
@@ -1734,13 +1647,17 @@ static int batch_wait(ictr_batch *b) {
 
 extern "C" int ictr_batch_set_timing(ictr_batch *b, int enable) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
-  if (enable && b->ev.empty()) {
-    b->ev.resize(3 * b->nlev);
+  if (enable && b->ev.empty()) {  // all events or none: a failure half way leaves the batch without timing
+    const int iters = std::max(1, b->op->maxiter);
+    std::vector<Event> ev(3 * b->nlev), evk((size_t)2 * b->nlev * iters);
+    for (Event &e : ev)
+      if (int rc = e.create()) return rc;
+    for (Event &e : evk)
+      if (int rc = e.create()) return rc;
+    b->ev = std::move(ev);
+    b->evk = std::move(evk);
     b->ev_used.assign(b->nlev, 0);
-    for (auto &e : b->ev) HIPCHK(hipEventCreate(&e));
-    b->evk_iters = std::max(1, b->op->maxiter);
-    b->evk.resize((size_t)2 * b->nlev * b->evk_iters);
-    for (auto &e : b->evk) HIPCHK(hipEventCreate(&e));
+    b->evk_iters = iters;
   }
   b->timing = enable != 0;
   return ICTR_OK;
@@ -1752,8 +1669,8 @@ extern "C" int ictr_batch_get_level_times(ictr_batch *b, float *ms_setup, float 
   for (int l = 0; l < b->nlev; ++l) {
     ms_setup[l] = ms_iters[l] = 0.0f;
     if (b->ev_used[l] != 1) continue;
-    HIPCHK(hipEventElapsedTime(&ms_setup[l], b->ev[3 * l + 0], b->ev[3 * l + 1]));
-    HIPCHK(hipEventElapsedTime(&ms_iters[l], b->ev[3 * l + 1], b->ev[3 * l + 2]));
+    HIPCHK(hipEventElapsedTime(&ms_setup[l], b->ev[3 * l + 0].get(), b->ev[3 * l + 1].get()));
+    HIPCHK(hipEventElapsedTime(&ms_iters[l], b->ev[3 * l + 1].get(), b->ev[3 * l + 2].get()));
   }
   return ICTR_OK;
 }
@@ -1767,7 +1684,8 @@ extern "C" int ictr_batch_get_kernel_times(ictr_batch *b, float *ms_kernel) {
     if (!b->ev_used[l] || !b->evk_valid) continue;
     for (int it = 0; it < mi; ++it) {
       float ms = 0.0f;
-      HIPCHK(hipEventElapsedTime(&ms, b->evk[2 * (l * b->evk_iters + it)], b->evk[2 * (l * b->evk_iters + it) + 1]));
+      const int ke = 2 * (l * b->evk_iters + it);
+      HIPCHK(hipEventElapsedTime(&ms, b->evk[ke].get(), b->evk[ke + 1].get()));
       ms_kernel[l] += ms;
     }
   }
@@ -1782,7 +1700,7 @@ extern "C" int ictr_batch_get_first_iter_times(ictr_batch *b, float *ms_first) {
   for (int l = 0; l < b->nlev; ++l) {
     ms_first[l] = 0.0f;
     if (!b->ev_used[l] || !b->evk_valid || b->op->maxiter < 1) continue;
-    HIPCHK(hipEventElapsedTime(&ms_first[l], b->evk[2 * (l * b->evk_iters)], b->evk[2 * (l * b->evk_iters) + 1]));
+    HIPCHK(hipEventElapsedTime(&ms_first[l], b->evk[2 * (l * b->evk_iters)].get(), b->evk[2 * (l * b->evk_iters) + 1].get()));
   }
   return ICTR_OK;
 }
@@ -1808,8 +1726,8 @@ extern "C" int ictr_batch_get_kernel_intervals(ictr_batch *b, float *start_ms, f
       const int k = l * b->evk_iters + it;
       start_ms[k] = end_ms[k] = 0.0f;
       if (!b->ev_used[l] || !b->evk_valid || it >= mi) continue;
-      HIPCHK(hipEventElapsedTime(&start_ms[k], g_timebase, b->evk[2 * k]));
-      HIPCHK(hipEventElapsedTime(&end_ms[k], g_timebase, b->evk[2 * k + 1]));
+      HIPCHK(hipEventElapsedTime(&start_ms[k], g_timebase, b->evk[2 * k].get()));
+      HIPCHK(hipEventElapsedTime(&end_ms[k], g_timebase, b->evk[2 * k + 1].get()));
     }
   return ICTR_OK;
 }
@@ -1822,8 +1740,8 @@ extern "C" int ictr_batch_get_setup_intervals(ictr_batch *b, float *start_ms, fl
   for (int l = 0; l < b->nlev; ++l) {
     start_ms[l] = end_ms[l] = 0.0f;
     if (b->ev_used[l] != 1) continue;
-    HIPCHK(hipEventElapsedTime(&start_ms[l], g_timebase, b->ev[3 * l + 0]));
-    HIPCHK(hipEventElapsedTime(&end_ms[l], g_timebase, b->ev[3 * l + 1]));
+    HIPCHK(hipEventElapsedTime(&start_ms[l], g_timebase, b->ev[3 * l + 0].get()));
+    HIPCHK(hipEventElapsedTime(&end_ms[l], g_timebase, b->ev[3 * l + 1].get()));
   }
   return ICTR_OK;
 }
@@ -1833,16 +1751,16 @@ extern "C" int ictr_batch_last_team(const ictr_batch *b) {
 }
 extern "C" int ictr_batch_set_reduction_buffer(ictr_batch *b, float *dev_ptr) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
-  b->d_red = dev_ptr ? dev_ptr : b->d_red_own;
+  b->d_red = dev_ptr ? dev_ptr : b->d_red_own.get();
   return ICTR_OK;
 }
 
 static int batch_fetch_state(ictr_batch *b) {
   if (b->done_valid) {
-    HIPCHK(hipEventSynchronize(b->done_ev));
-    memcpy(b->h_st.data(), b->h_st_pin, sizeof(ProbState) * b->B);
+    HIPCHK(hipEventSynchronize(b->done_ev.get()));
+    memcpy(b->h_st.data(), b->h_st_pin.get(), sizeof(ProbState) * b->B);
   } else {
-    HIPCHK(hipMemcpyAsync(b->h_st.data(), b->d_st, sizeof(ProbState) * b->B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(b->h_st.data(), b->d_st.get(), sizeof(ProbState) * b->B, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
   }
   if (int rc = team_error_check(b)) return rc;  // never hand out the poses of a tracking whose exchanges timed out
@@ -1872,7 +1790,7 @@ extern "C" int ictr_batch_get2dpoints(ictr_batch *b, int64_t problem, float *hos
   if (!b->projected)
     if (int rc = ictr_batch_begin(b)) return rc;
   const size_t M = b->M;
-  HIPCHK(hipMemcpyAsync(host_out, b->d_pt2d + ((size_t)problem * b->nlev + b->op->lv_l) * 2 * M, sizeof(float) * 2 * M,
+  HIPCHK(hipMemcpyAsync(host_out, b->d_pt2d.get() + ((size_t)problem * b->nlev + b->op->lv_l) * 2 * M, sizeof(float) * 2 * M,
                         hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   return ICTR_OK;
@@ -1883,6 +1801,11 @@ struct ictr_odometer {
   ictr_batch *b = nullptr;
   ictr_pose *pose = nullptr;
   ictr_pyramid *own_ref = nullptr, *own_new = nullptr;  // uploads made by setpose_host
+  ~ictr_odometer() {
+    delete own_ref;
+    delete own_new;
+    delete b;
+  }
 };
 
 extern "C" int ictr_odometer_create(ictr_odometer **out, ictr_pose *pose, const ictr_optparam *op) {
@@ -1895,13 +1818,7 @@ extern "C" int ictr_odometer_create(ictr_odometer **out, ictr_pose *pose, const 
   *out = o;
   return ICTR_OK;
 }
-extern "C" void ictr_odometer_destroy(ictr_odometer *o) {
-  if (!o) return;
-  ictr_pyramid_destroy(o->own_ref);
-  ictr_pyramid_destroy(o->own_new);
-  batch_free(o->b);
-  delete o;
-}
+extern "C" void ictr_odometer_destroy(ictr_odometer *o) { delete o; }
 extern "C" int ictr_odometer_set_stream(ictr_odometer *o, void *s) {
   if (!o) return fail(ICTR_ERR_INVALID, "odometer is NULL");
   return ictr_batch_set_stream(o->b, s);
@@ -1943,8 +1860,8 @@ extern "C" int ictr_odometer_setpose_host(ictr_odometer *o, const double *p_in, 
   if (!o || !img_ref || !img_ref_dx || !img_ref_dy || !img_new)
     return fail(ICTR_ERR_INVALID, "setpose_host: NULL argument");
   const ictr_cam *c = o->b->cam;
-  ictr_pyramid_destroy(o->own_ref);
-  ictr_pyramid_destroy(o->own_new);
+  delete o->own_ref;
+  delete o->own_new;
   o->own_ref = o->own_new = nullptr;
   if (int rc = ictr_pyramid_create_from_host_planes(&o->own_ref, img_ref, img_ref_dx, img_ref_dy, c->wh[0], c->wh[1],
                                                     o->b->op->lv_f, c->padding))
@@ -1963,7 +1880,7 @@ extern "C" int ictr_odometer_trackpose(ictr_odometer *o, double *p_out) {
   const bool verbose = b->op->verbosity == 2, trace_was_on = b->trace_on;
   if (verbose && !trace_was_on) {
     b->trace_on = true;
-    if (b->projected) HIPCHK(hipMemsetAsync(b->d_trace_count, 0, sizeof(int), b->stream));  // else: the begin phase
+    if (b->projected) HIPCHK(hipMemsetAsync(b->d_trace_count.get(), 0, sizeof(int), b->stream));  // else: the begin phase
   }
   int rc_enq = track_enqueue(b);
   b->trace_on = trace_was_on;
@@ -1973,10 +1890,10 @@ extern "C" int ictr_odometer_trackpose(ictr_odometer *o, double *p_out) {
   if (int rc = batch_fetch_state(b)) return rc;
   if (verbose) {
     int c = 0;
-    HIPCHK(hipMemcpy(&c, b->d_trace_count, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, b->d_trace_count.get(), sizeof(int), hipMemcpyDeviceToHost));
     c = std::min(c, b->trace_cap);
     std::vector<ictr_trace_rec> recs((size_t)std::max(c, 0));
-    if (c > 0) HIPCHK(hipMemcpy(recs.data(), b->d_trace, sizeof(ictr_trace_rec) * c, hipMemcpyDeviceToHost));
+    if (c > 0) HIPCHK(hipMemcpy(recs.data(), b->d_trace.get(), sizeof(ictr_trace_rec) * c, hipMemcpyDeviceToHost));
     for (const ictr_trace_rec &r : recs) {
       const float *d = r.dp;  // delta_p.lpNorm<1>() in Eigen's redux order, as on the device
       const float nd = (fabsf(d[0]) + (fabsf(d[1]) + fabsf(d[2]))) + (fabsf(d[3]) + (fabsf(d[4]) + fabsf(d[5])));
@@ -2001,11 +1918,11 @@ extern "C" int ictr_odometer_enable_trace(ictr_odometer *o, int enable) {
 extern "C" int ictr_odometer_trace(ictr_odometer *o, ictr_trace_rec *out, int64_t capacity, int64_t *count) {
   if (!o || !count) return fail(ICTR_ERR_INVALID, "trace: NULL argument");
   int c = 0;
-  HIPCHK(hipMemcpy(&c, o->b->d_trace_count, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&c, o->b->d_trace_count.get(), sizeof(int), hipMemcpyDeviceToHost));
   c = std::min(c, o->b->trace_cap);
   *count = c;
   const int64_t ncopy = std::min<int64_t>(c, capacity);
-  if (out && ncopy > 0) HIPCHK(hipMemcpy(out, o->b->d_trace, sizeof(ictr_trace_rec) * ncopy, hipMemcpyDeviceToHost));
+  if (out && ncopy > 0) HIPCHK(hipMemcpy(out, o->b->d_trace.get(), sizeof(ictr_trace_rec) * ncopy, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 // which: 0 T, 1 Gx, 2 Gy (novals*M), 4 pt3d, 5 pt3d_ref (3*M), 7 sd coefficients (16*M), 8 ProbState as floats,
@@ -2017,18 +1934,18 @@ extern "C" int ictr_batch_read_buffer(ictr_batch *b, int64_t problem, int which,
   const float *src = nullptr;
   size_t avail = 0;
   switch (which) {
-    case 0: src = b->d_T + pr * M * n; avail = M * n; break;
-    case 1: src = b->d_Gx + pr * M * n; avail = M * n; break;
-    case 2: src = b->d_Gy + pr * M * n; avail = M * n; break;
-    case 4: src = b->d_pt3d + pr * 3 * M; avail = 3 * M; break;
-    case 5: src = b->d_pt3d_ref + pr * 3 * M; avail = 3 * M; break;
-    case 7: src = b->d_coef + pr * M * kCoefStride; avail = M * kCoefStride; break;
-    case 8: src = reinterpret_cast<const float *>(b->d_st + pr); avail = sizeof(ProbState) / sizeof(float); break;
-    case 9: src = b->d_partH + pr * 8; avail = pr == 0 ? 16 : 8; break;  // k_track1 phase cycle counters (ICTR_T1_PROF builds only)
-    case 10: src = b->d_partH + (size_t)b->B * 8 + pr * 4; avail = 4; break;  // ... and the solver's
+    case 0: src = b->d_T.get() + pr * M * n; avail = M * n; break;
+    case 1: src = b->d_Gx.get() + pr * M * n; avail = M * n; break;
+    case 2: src = b->d_Gy.get() + pr * M * n; avail = M * n; break;
+    case 4: src = b->d_pt3d.get() + pr * 3 * M; avail = 3 * M; break;
+    case 5: src = b->d_pt3d_ref.get() + pr * 3 * M; avail = 3 * M; break;
+    case 7: src = b->d_coef.get() + pr * M * kCoefStride; avail = M * kCoefStride; break;
+    case 8: src = reinterpret_cast<const float *>(b->d_st.get() + pr); avail = sizeof(ProbState) / sizeof(float); break;
+    case 9: src = b->d_partH.get() + pr * 8; avail = pr == 0 ? 16 : 8; break;  // k_track1 phase cycle counters (ICTR_T1_PROF builds only)
+    case 10: src = b->d_partH.get() + (size_t)b->B * 8 + pr * 4; avail = 4; break;  // ... and the solver's
     default:
       if (which >= 100 && which < 100 + b->nlev) {
-        src = b->d_pt2d + (pr * b->nlev + (size_t)(which - 100)) * 2 * M;
+        src = b->d_pt2d.get() + (pr * b->nlev + (size_t)(which - 100)) * 2 * M;
         avail = 2 * M;
       }
   }
@@ -2054,79 +1971,6 @@ extern "C" int ictr_odometer_get_norm(const ictr_odometer *o, double *meanshift3
   return ICTR_OK;
 }
 
-// ---------------------------------------------------------------- per-patch translation IC-LK (flow producer)
-static thread_local float g_pf_ms = -1.0f;
-extern "C" float ictr_patchflow_last_kernel_ms(void) { return g_pf_ms; }
-extern "C" int ictr_patchflow_last_form(void) { return patchflow_last_form(); }
-// the argument checks of a patch tracking and the level table of its launch (a.pts / out / status / iters and a.K are the
-// caller's): shared by ictr_patchflow and the flow grid of ictr_frontend.hip, so that both launch the same kernel on the
-// same arguments
-int ictr::patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
-                         PFArgs *out) {
-  if (!pa || !pb || psz < 1 || psz > 32 || lv_l < 0 || lv_f < lv_l || maxiter < 0)
-    return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
-  if (lv_f >= pa->nlev || lv_f >= pb->nlev || lv_f > 15)
-    return fail(ICTR_ERR_INVALID, "patchflow: pyramids have fewer than lv_f+1 levels");
-  if (pa->getgrad != 1) return fail(ICTR_ERR_INVALID, "patchflow: the first pyramid needs gradient planes (getgrad = 1)");
-  if (pa->pad < psz || pb->pad < psz) return fail(ICTR_ERR_INVALID, "patchflow: pyramid padding must be >= psz");
-  for (int l = lv_l; l <= lv_f; ++l)
-    if (pa->w[l] != pb->w[l] || pa->h[l] != pb->h[l] || pa->sw[l] != pb->sw[l])
-      return fail(ICTR_ERR_INVALID, "patchflow: the two pyramids differ in size at level %d", l);
-  PFArgs &a = *out;
-  memset(&a, 0, sizeof(a));
-  for (int l = lv_l; l <= lv_f; ++l) {
-    a.lv[l].a = pa->img[l];
-    a.lv[l].ax = pa->dx[l];
-    a.lv[l].ay = pa->dy[l];
-    a.lv[l].b = pb->img[l];
-    a.lv[l].sw = pa->sw[l];
-    a.lv[l].shift = (pa->pad - psz) * (pa->sw[l] + 1);
-    a.lv[l].swo = (float)pa->w[l];
-    a.lv[l].sho = (float)pa->h[l];
-    a.lv[l].scale = (float)(1 / pow(2, l));
-  }
-  a.lv_f = lv_f;
-  a.lv_l = lv_l;
-  a.P = psz;
-  a.maxiter = maxiter;
-  a.eps2 = eps * eps;
-  a.min_det = 1e-4f;
-  return ICTR_OK;
-}
-extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
-                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
-  if (K < 0 || (K > 0 && (!pts || !out))) return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
-  PFArgs a;
-  if (int rc = patchflow_args(pa, pb, psz, lv_f, lv_l, maxiter, eps, &a)) return rc;
-  if (K == 0) return ICTR_OK;
-  if (int rc = need_device()) return rc;
-  a.K = (int)K;
-  float *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, sizeof(float) * 6 * K));
-  float *d_pts = d, *d_out = d + 2 * K;
-  int *d_status = reinterpret_cast<int *>(d + 4 * K), *d_iters = reinterpret_cast<int *>(d + 5 * K);
-  a.pts = d_pts;
-  a.out = d_out;
-  a.status = d_status;
-  a.iters = d_iters;
-  hipError_t e = hipMemcpy(d_pts, pts, sizeof(float) * 2 * K, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    static thread_local hipEvent_t ev0 = nullptr, ev1 = nullptr;  // duration of the one kernel, for callers that report it
-    if (!ev0 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
-    if (ev0) (void)hipEventRecord(ev0, nullptr);
-    launch_patchflow(a, nullptr);
-    if (ev0) (void)hipEventRecord(ev1, nullptr);
-    e = hipMemcpy(out, d_out, sizeof(float) * 2 * K, hipMemcpyDeviceToHost);
-    g_pf_ms = -1.0f;
-    if (ev0 && e == hipSuccess && hipEventElapsedTime(&g_pf_ms, ev0, ev1) != hipSuccess) g_pf_ms = -1.0f;
-    if (e == hipSuccess && status) e = hipMemcpy(status, d_status, sizeof(int) * K, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && iters) e = hipMemcpy(iters, d_iters, sizeof(int) * K, hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "patchflow failed: %s", hipGetErrorString(e));
-  return ICTR_OK;
-}
-
 // ---------------------------------------------------------------- frame-to-frame sequence (run_odometer_test.m:172-250)
 // One engine of one problem (B = 1) tracks frame t -> t+1 from the pose found for frame t, for every t, with the step
 // between two pairs on the device (ictr_sequence.hip): per pair one pyramid build, the selection launches and ONE
@@ -2137,42 +1981,34 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
 struct ictr_sequence {
   const ictr_cam *cam = nullptr;
   ictr_optparam op;
-  ictr_batch *b = nullptr;
+  // declared first, so released last: the inner batch, then the ring pyramids, after the sequence's own buffers
+  std::unique_ptr<ictr_batch> b;
+  std::unique_ptr<ictr_pyramid> ring[2];
   int64_t nw = 0;
   int stride = 10, nblk = 0;
   hipStream_t stream = nullptr;
-  double *d_world = nullptr;
-  unsigned long long *d_mask = nullptr;
-  unsigned *d_cnt = nullptr;
-  int *d_sel = nullptr;
-  SeqState *d_ss = nullptr;
-  ictr_pyramid *ring[2] = {nullptr, nullptr};
-  PlaneSet *d_tab = nullptr;  // [2][nlev]: (ring 0 -> ring 1), (ring 1 -> ring 0)
+  DevBuf<double> d_world;
+  DevBuf<unsigned long long> d_mask;
+  DevBuf<unsigned> d_cnt;
+  DevBuf<int> d_sel;
+  DevBuf<SeqState> d_ss;
+  DevBuf<PlaneSet> d_tab;  // [2][nlev]: (ring 0 -> ring 1), (ring 1 -> ring 0)
   const float *frames = nullptr;  // [N][h][w] on the device (borrowed, or d_frames_own)
-  float *d_frames_own = nullptr;
+  DevBuf<float> d_frames_own;
   size_t own_bytes = 0;
   int64_t nframes = 0;
-  char *d_out = nullptr, *h_out = nullptr;  // poses [N][6] f64 | hash [N-1] u64 | npts [N-1] i32 | iters [N-1] i32
+  DevBuf<char> d_out;  // poses [N][6] f64 | hash [N-1] u64 | npts [N-1] i32 | iters [N-1] i32
+  PinBuf<char> h_out;
   int64_t out_frames = 0;
   int64_t run_frames = 0;  // frames of the last run (its results' layout in h_out)
   bool points_set = false, pending = false, ran = false;
-  hipEvent_t done = nullptr;
+  Event done;
+  ~ictr_sequence() {
+    if (pending) (void)hipEventSynchronize(done.get());
+  }
 };
 
 static size_t seq_out_bytes(int64_t N) { return (size_t)N * 48 + (size_t)(N - 1) * 16; }
-
-static void seq_free(ictr_sequence *s) {
-  if (!s) return;
-  if (s->pending) (void)hipEventSynchronize(s->done);
-  if (s->done) (void)hipEventDestroy(s->done);
-  if (s->h_out) (void)hipHostFree(s->h_out);
-  for (void *p : {(void *)s->d_world, (void *)s->d_mask, (void *)s->d_cnt, (void *)s->d_sel, (void *)s->d_ss,
-                  (void *)s->d_tab, (void *)s->d_frames_own, (void *)s->d_out})
-    if (p) (void)hipFree(p);
-  for (ictr_pyramid *p : s->ring) ictr_pyramid_destroy(p);
-  if (s->b) batch_free(s->b);
-  delete s;
-}
 
 // the inputs of a run stay fixed until its wait
 static int seq_refuse_pending(const ictr_sequence *s, const char *what) {
@@ -2189,17 +2025,15 @@ extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, co
   if (stride < 1) return fail(ICTR_ERR_INVALID, "sequence_create: the subsampling stride must be >= 1");
   if (int rc = check_op(op, cam)) return rc;
   if (int rc = need_device()) return rc;
-  ictr_sequence *s = new ictr_sequence;
+  auto s = std::make_unique<ictr_sequence>();
   s->cam = cam;
   s->op = *op;
   s->nw = nworld;
   s->stride = stride;
   s->nblk = (int)((nworld + kSeqChunk - 1) / kSeqChunk);
-  if (int rc = ictr_batch_create(&s->b, cam, &s->op, 1)) {
-    delete s;
-    return rc;
-  }
-  ictr_batch *b = s->b;
+  ictr_batch *b = nullptr;
+  if (int rc = ictr_batch_create(&b, cam, &s->op, 1)) return rc;
+  s->b.reset(b);
   // the engine as every pair's tracking sees it: builder-made gradient pyramids (otf = 1, packed planes), the cap as
   // the point capacity of the launch
   b->maxpts = b->M;
@@ -2208,70 +2042,46 @@ extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, co
   b->plan.form = kFormTrack1;
   b->plan.project_here = 1;
   b->plan.team = track1_team(b, &b->plan.team_q);
-  if (b->plan.team < 2) {
-    if ((size_t)b->M * 64 > 128 * 1024) {
-      const int cap = b->M;
-      seq_free(s);
-      return fail(ICTR_ERR_INVALID, "sequence_create: a cap (maxpttrack) of %d points has no one-launch form: one workgroup "
-                                    "holds at most 2048 point records, and the team form serves psz 8 only, up to 8192 "
-                                    "points", cap);
-    }
-  }
+  if (b->plan.team < 2 && (size_t)b->M * 64 > 128 * 1024)
+    return fail(ICTR_ERR_INVALID, "sequence_create: a cap (maxpttrack) of %d points has no one-launch form: one workgroup "
+                                  "holds at most 2048 point records, and the team form serves psz 8 only, up to 8192 "
+                                  "points", b->M);
   const int L = b->nlev;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-  };
-  alloc((void **)&s->d_world, sizeof(double) * 3 * nworld);
-  alloc((void **)&s->d_mask, sizeof(unsigned long long) * (size_t)s->nblk * (kSeqChunk / 64));
-  alloc((void **)&s->d_cnt, sizeof(unsigned) * s->nblk);
-  alloc((void **)&s->d_sel, sizeof(int) * b->M);
-  alloc((void **)&s->d_ss, sizeof(SeqState));
-  alloc((void **)&s->d_tab, sizeof(PlaneSet) * 2 * L);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    seq_free(s);
-    return fail(ICTR_ERR_HIP, "sequence_create: device allocation failed: %s", hipGetErrorString(e));
+  if (int rc = s->d_world.alloc(sizeof(double) * 3 * nworld, true)) return rc;
+  if (int rc = s->d_mask.alloc(sizeof(unsigned long long) * (size_t)s->nblk * (kSeqChunk / 64), true)) return rc;
+  if (int rc = s->d_cnt.alloc(sizeof(unsigned) * s->nblk, true)) return rc;
+  if (int rc = s->d_sel.alloc(sizeof(int) * b->M, true)) return rc;
+  if (int rc = s->d_ss.alloc(sizeof(SeqState), true)) return rc;
+  if (int rc = s->d_tab.alloc(sizeof(PlaneSet) * 2 * L, true)) return rc;
+  if (int rc = s->done.create(hipEventDisableTiming)) return rc;
+  for (int k = 0; k < 2; ++k) {
+    ictr_pyramid *p = nullptr;
+    if (int rc = pyramid_alloc(&p, cam->wh[0], cam->wh[1], op->lv_f, 1, cam->padding)) return rc;
+    s->ring[k].reset(p);
   }
-  for (int k = 0; k < 2; ++k)
-    if (int rc = pyramid_alloc(&s->ring[k], cam->wh[0], cam->wh[1], op->lv_f, 1, cam->padding)) {
-      seq_free(s);
-      return rc;
-    }
   // both orders of the plane table, once: pair t reads table t % 2 (reference = frame t's pyramid, ring[t % 2])
   std::vector<PlaneSet> tab(2 * L);
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < L; ++l) {
-      const ictr_pyramid *r = s->ring[k], *c = s->ring[1 - k];
+      const ictr_pyramid *r = s->ring[k].get(), *c = s->ring[1 - k].get();
       tab[k * L + l] = PlaneSet{r->img[l], r->dx[l], r->dy[l], c->img[l], r->pack[l]};
     }
-  e = hipMemcpy(s->d_tab, tab.data(), sizeof(PlaneSet) * 2 * L, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    seq_free(s);
-    return fail(ICTR_ERR_HIP, "sequence_create: plane table upload failed: %s", hipGetErrorString(e));
-  }
+  HIPCHK(hipMemcpy(s->d_tab.get(), tab.data(), sizeof(PlaneSet) * 2 * L, hipMemcpyHostToDevice));
   if (b->plan.team > 1) {  // the mailbox now, not inside the first track_async
     T1Team tm;
-    if (int rc = team_prepare(b, b->plan, &tm)) {
-      seq_free(s);
-      return rc;
-    }
-    if (hipStreamSynchronize(b->stream) != hipSuccess) {
-      seq_free(s);
-      return fail(ICTR_ERR_HIP, "sequence_create: mailbox initialisation failed");
-    }
+    if (int rc = team_prepare(b, b->plan, &tm)) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
   }
-  *out = s;
+  *out = s.release();
   return ICTR_OK;
 }
 
-extern "C" void ictr_sequence_destroy(ictr_sequence *s) { seq_free(s); }
+extern "C" void ictr_sequence_destroy(ictr_sequence *s) { delete s; }
 
 extern "C" int ictr_sequence_set_points(ictr_sequence *s, const double *pt3d) {
   if (!s || !pt3d) return fail(ICTR_ERR_INVALID, "sequence_set_points: NULL argument");
   if (int rc = seq_refuse_pending(s, "sequence_set_points")) return rc;
-  HIPCHK(hipMemcpy(s->d_world, pt3d, sizeof(double) * 3 * s->nw, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(s->d_world.get(), pt3d, sizeof(double) * 3 * s->nw, hipMemcpyHostToDevice));
   s->points_set = true;
   return ICTR_OK;
 }
@@ -2290,22 +2100,19 @@ extern "C" int ictr_sequence_set_frames(ictr_sequence *s, const float *frames, i
     s->frames = frames;
   } else {
     if (bytes > s->own_bytes) {
-      if (s->d_frames_own) HIPCHK(hipFree(s->d_frames_own));
-      s->d_frames_own = nullptr;
       s->own_bytes = 0;
-      HIPCHK(hipMalloc((void **)&s->d_frames_own, bytes));
+      if (int rc = s->d_frames_own.alloc(bytes)) return rc;
       s->own_bytes = bytes;
     }
-    HIPCHK(hipMemcpy(s->d_frames_own, frames, bytes, hipMemcpyHostToDevice));
-    s->frames = s->d_frames_own;
+    HIPCHK(hipMemcpy(s->d_frames_own.get(), frames, bytes, hipMemcpyHostToDevice));
+    s->frames = s->d_frames_own.get();
   }
   if (nframes > s->out_frames) {  // result buffers sized here, so that track_async allocates nothing
-    if (s->d_out) HIPCHK(hipFree(s->d_out));
-    if (s->h_out) HIPCHK(hipHostFree(s->h_out));
-    s->d_out = s->h_out = nullptr;
     s->out_frames = 0;
-    HIPCHK(hipMalloc((void **)&s->d_out, seq_out_bytes(nframes)));
-    HIPCHK(hipHostMalloc((void **)&s->h_out, seq_out_bytes(nframes), hipHostMallocDefault));
+    s->d_out.reset();
+    s->h_out.reset();
+    if (int rc = s->d_out.alloc(seq_out_bytes(nframes))) return rc;
+    if (int rc = s->h_out.alloc(seq_out_bytes(nframes))) return rc;
     s->out_frames = nframes;
   }
   s->nframes = nframes;
@@ -2334,17 +2141,17 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   if (!s->points_set) return fail(ICTR_ERR_STATE, "sequence_track_async: ictr_sequence_set_points has not been called");
   if (!s->frames || s->nframes < 2) return fail(ICTR_ERR_STATE, "sequence_track_async: no frames set");
   if (s->pending) return fail(ICTR_ERR_STATE, "sequence_track_async: wait for the previous run first");
-  ictr_batch *b = s->b;
-  if (b->h_team_err && *(volatile int *)b->h_team_err) {  // an earlier run timed out (reported by its wait)
+  ictr_batch *b = s->b.get();
+  if (b->h_team_err && *(volatile int *)b->h_team_err.get()) {  // an earlier run timed out (reported by its wait)
     HIPCHK(hipStreamSynchronize(s->stream));
-    *(volatile int *)b->h_team_err = 0;
+    *(volatile int *)b->h_team_err.get() = 0;
   }
   const int64_t N = s->nframes;
   const int w = s->cam->wh[0], h = s->cam->wh[1], L = b->nlev;
   const size_t plane = (size_t)w * h;
   SeqArgs a;
   memset(&a, 0, sizeof(a));
-  a.X = s->d_world;
+  a.X = s->d_world.get();
   a.nw = s->nw;
   a.nblk = s->nblk;
   a.stride = s->stride;
@@ -2359,37 +2166,37 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   a.w = (double)w;
   a.h = (double)h;
   memcpy(a.p0, p0, sizeof(a.p0));
-  a.st = b->d_st;
-  a.ss = s->d_ss;
-  a.mask = s->d_mask;
-  a.cnt = s->d_cnt;
-  a.sel = s->d_sel;
-  a.poses = reinterpret_cast<double *>(s->d_out);
-  a.hash = reinterpret_cast<unsigned long long *>(s->d_out + (size_t)N * 48);
-  a.npts_out = reinterpret_cast<int *>(s->d_out + (size_t)N * 48 + (size_t)(N - 1) * 8);
+  a.st = b->d_st.get();
+  a.ss = s->d_ss.get();
+  a.mask = s->d_mask.get();
+  a.cnt = s->d_cnt.get();
+  a.sel = s->d_sel.get();
+  a.poses = reinterpret_cast<double *>(s->d_out.get());
+  a.hash = reinterpret_cast<unsigned long long *>(s->d_out.get() + (size_t)N * 48);
+  a.npts_out = reinterpret_cast<int *>(s->d_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 8);
   a.iters_out = a.npts_out + (N - 1);
-  a.pt3d = b->d_pt3d;
-  a.T = b->d_T;
-  a.Gx = b->d_Gx;
-  a.Gy = b->d_Gy;
-  a.coef = b->d_coef;
-  if (int rc = pyramid_build(s->ring[0], s->frames, s->stream)) return rc;
+  a.pt3d = b->d_pt3d.get();
+  a.T = b->d_T.get();
+  a.Gx = b->d_Gx.get();
+  a.Gy = b->d_Gy.get();
+  a.coef = b->d_coef.get();
+  if (int rc = pyramid_build(s->ring[0].get(), s->frames, s->stream)) return rc;
   for (int64_t t = 0; t + 1 < N; ++t) {
-    if (int rc = pyramid_build(s->ring[(t + 1) & 1], s->frames + (size_t)(t + 1) * plane, s->stream)) return rc;
+    if (int rc = pyramid_build(s->ring[(t + 1) & 1].get(), s->frames + (size_t)(t + 1) * plane, s->stream)) return rc;
     a.t = (int)t;
     a.tail = 0;
     launch_seq_select(a, s->stream);
     HIPCHK(hipGetLastError());
     EngineDev e = engine_dev(b);
-    e.planes = s->d_tab + (t & 1) * L;
+    e.planes = s->d_tab.get() + (t & 1) * L;
     if (int rc = track1_launch(b, e, b->plan, nullptr, nullptr, true)) return rc;
   }
   a.t = (int)(N - 1);
   a.tail = 1;
   launch_seq_select(a, s->stream);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(s->h_out, s->d_out, seq_out_bytes(N), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipEventRecord(s->done, s->stream));
+  HIPCHK(hipMemcpyAsync(s->h_out.get(), s->d_out.get(), seq_out_bytes(N), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipEventRecord(s->done.get(), s->stream));
   s->pending = true;
   s->ran = true;
   s->run_frames = N;
@@ -2399,20 +2206,20 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
 extern "C" int ictr_sequence_wait(ictr_sequence *s, double *poses, int32_t *npts, int32_t *iters) {
   if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
   if (!s->pending) return fail(ICTR_ERR_STATE, "sequence_wait: nothing has been tracked");
-  HIPCHK(hipEventSynchronize(s->done));
+  HIPCHK(hipEventSynchronize(s->done.get()));
   s->pending = false;
-  if (int rc = team_error_check(s->b)) return rc;
+  if (int rc = team_error_check(s->b.get())) return rc;
   const int64_t N = s->run_frames;
-  if (poses) memcpy(poses, s->h_out, sizeof(double) * 6 * N);
-  if (npts) memcpy(npts, s->h_out + (size_t)N * 48 + (size_t)(N - 1) * 8, sizeof(int32_t) * (N - 1));
-  if (iters) memcpy(iters, s->h_out + (size_t)N * 48 + (size_t)(N - 1) * 12, sizeof(int32_t) * (N - 1));
+  if (poses) memcpy(poses, s->h_out.get(), sizeof(double) * 6 * N);
+  if (npts) memcpy(npts, s->h_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 8, sizeof(int32_t) * (N - 1));
+  if (iters) memcpy(iters, s->h_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 12, sizeof(int32_t) * (N - 1));
   return ICTR_OK;
 }
 
 extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out) {
   if (!s || !out) return fail(ICTR_ERR_INVALID, "sequence_selection_hashes: NULL argument");
   if (s->pending || !s->ran) return fail(ICTR_ERR_STATE, "sequence_selection_hashes: no completed run");
-  memcpy(out, s->h_out + (size_t)s->run_frames * 48, sizeof(uint64_t) * (s->run_frames - 1));
+  memcpy(out, s->h_out.get() + (size_t)s->run_frames * 48, sizeof(uint64_t) * (s->run_frames - 1));
   return ICTR_OK;
 }
 

@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "ictr_dev.h"
@@ -650,15 +651,16 @@ struct ictr_icgn {
   bool lds = false;          // ICTR_ICGN_LDS=1: LDS-staged footprint instead of direct tap gathers (measured: no gain)
   bool scalar_only = false;  // ICTR_ICGN_SCALAR=1: force the one-pixel-per-lane kernels (A/B measurements)
   hipStream_t stream = nullptr;
-  IcState *d_st = nullptr;
-  PlaneSet *d_planes = nullptr;
-  float *d_partH = nullptr, *d_partb = nullptr, *d_red = nullptr, *d_red_own = nullptr;
+  DevBuf<IcState> d_st;
+  DevBuf<PlaneSet> d_planes;
+  DevBuf<float> d_partH, d_partb, d_red_own;
+  float *d_red = nullptr;  // d_red_own, or the caller's (ictr_icgn_enable_sharding)
   std::vector<IcState> h_st;
   std::vector<PlaneSet> h_planes;
   std::vector<char> frames_set;
   std::vector<int> lw, lh, lsw;
   bool timing = false;
-  std::vector<hipEvent_t> ev;  // 2 per (level, iteration)
+  std::vector<Event> ev;  // 2 per (level, iteration)
   std::vector<float> h_M0;     // initial warps (normalised), 9 per problem
 };
 
@@ -685,10 +687,10 @@ static IcDev icgn_dev(const ictr_icgn *g) {
   e.row_lo = g->rows[0];
   e.row_hi = g->rows[1];
   e.eps = g->eps;
-  e.planes = g->d_planes;
-  e.st = g->d_st;
-  e.partH = g->d_partH;
-  e.partb = g->d_partb;
+  e.planes = g->d_planes.get();
+  e.st = g->d_st.get();
+  e.partH = g->d_partH.get();
+  e.partb = g->d_partb.get();
   e.red = g->d_red;
   e.nlev = g->nlev;
   return e;
@@ -715,7 +717,7 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(ICTR_ERR_NO_DEVICE, "no usable HIP device: the alignment engine has no CPU fallback");
-  ictr_icgn *g = new ictr_icgn;
+  auto g = std::make_unique<ictr_icgn>();
   g->model = model;
   g->w = w;
   g->h = h;
@@ -733,10 +735,8 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
     g->region[3] = h - 4;
   }
   if (g->region[0] < 0 || g->region[1] < 0 || g->region[2] < 1 || g->region[3] < 1 || g->region[0] + g->region[2] > w ||
-      g->region[1] + g->region[3] > h) {
-    delete g;
+      g->region[1] + g->region[3] > h)
     return fail(ICTR_ERR_INVALID, "icgn_create: template region outside the frame");
-  }
   g->rows[0] = 0;
   g->rows[1] = h;
   if (const char *sv = getenv("ICTR_ICGN_SCALAR")) g->scalar_only = atoi(sv) != 0;
@@ -749,36 +749,21 @@ extern "C" int ictr_icgn_create(ictr_icgn **out, int model, int w, int h, int lv
   long want = std::max<long>(64, 8192 / g->B);
   if (const char *sv = getenv("ICTR_ICGN_GRIDX")) want = atol(sv);
   g->gridx = (int)std::max<long>(want, 1);
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-  };
-  alloc((void **)&g->d_st, sizeof(IcState) * g->B);
-  alloc((void **)&g->d_planes, sizeof(PlaneSet) * g->B * g->nlev);
-  alloc((void **)&g->d_partH, sizeof(float) * (size_t)g->B * g->gridx * kIcPartH);
-  alloc((void **)&g->d_partb, sizeof(float) * (size_t)g->B * g->gridx * kIcPartB);
-  alloc((void **)&g->d_red, sizeof(float) * (size_t)g->B * kIcRed);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(ICTR_ERR_HIP, "icgn_create: device allocation failed: %s", hipGetErrorString(e));
-  }
-  g->d_red_own = g->d_red;
+  if (int rc = g->d_st.alloc(sizeof(IcState) * g->B, true)) return rc;
+  if (int rc = g->d_planes.alloc(sizeof(PlaneSet) * g->B * g->nlev, true)) return rc;
+  if (int rc = g->d_partH.alloc(sizeof(float) * (size_t)g->B * g->gridx * kIcPartH, true)) return rc;
+  if (int rc = g->d_partb.alloc(sizeof(float) * (size_t)g->B * g->gridx * kIcPartB, true)) return rc;
+  if (int rc = g->d_red_own.alloc(sizeof(float) * (size_t)g->B * kIcRed, true)) return rc;
+  g->d_red = g->d_red_own.get();
   g->h_st.resize(g->B);
   g->h_planes.resize((size_t)g->B * g->nlev);
   g->frames_set.assign(g->B, 0);
   g->h_M0.assign((size_t)9 * g->B, 0.0f);
   for (int b = 0; b < g->B; ++b) g->h_M0[9 * b] = g->h_M0[9 * b + 4] = g->h_M0[9 * b + 8] = 1.0f;
-  *out = g;
+  *out = g.release();
   return ICTR_OK;
 }
-extern "C" void ictr_icgn_destroy(ictr_icgn *g) {
-  if (!g) return;
-  for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
-  for (void *p : {(void *)g->d_st, (void *)g->d_planes, (void *)g->d_partH, (void *)g->d_partb, (void *)g->d_red_own})
-    if (p) hipFree(p);
-  delete g;
-}
+extern "C" void ictr_icgn_destroy(ictr_icgn *g) { delete g; }
 extern "C" int ictr_icgn_set_stream(ictr_icgn *g, void *s) {
   if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   g->stream = (hipStream_t)s;
@@ -833,14 +818,16 @@ extern "C" int ictr_icgn_set_rows(ictr_icgn *g, int row_lo, int row_hi) {
 extern "C" int ictr_icgn_enable_sharding(ictr_icgn *g, int enable, float *red_dev) {
   if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
   g->sharded = enable ? 1 : 0;
-  g->d_red = red_dev ? red_dev : g->d_red_own;
+  g->d_red = red_dev ? red_dev : g->d_red_own.get();
   return ICTR_OK;
 }
 extern "C" int ictr_icgn_set_timing(ictr_icgn *g, int enable) {
   if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
-  if (enable && g->ev.empty()) {
-    g->ev.resize((size_t)2 * g->nlev * std::max(1, g->maxiter));
-    for (auto &e : g->ev) HIPCHK(hipEventCreate(&e));
+  if (enable && g->ev.empty()) {  // all events or none
+    std::vector<Event> ev((size_t)2 * g->nlev * std::max(1, g->maxiter));
+    for (Event &e : ev)
+      if (int rc = e.create()) return rc;
+    g->ev = std::move(ev);
   }
   g->timing = enable != 0;
   return ICTR_OK;
@@ -854,8 +841,8 @@ extern "C" int ictr_icgn_begin(ictr_icgn *g) {
     memset(&st, 0, sizeof(st));
     memcpy(st.M, &g->h_M0[9 * b], sizeof(float) * 9);
   }
-  HIPCHK(hipMemcpyAsync(g->d_st, g->h_st.data(), sizeof(IcState) * g->B, hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipMemcpyAsync(g->d_planes, g->h_planes.data(), sizeof(PlaneSet) * g->h_planes.size(), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(g->d_st.get(), g->h_st.data(), sizeof(IcState) * g->B, hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipMemcpyAsync(g->d_planes.get(), g->h_planes.data(), sizeof(PlaneSet) * g->h_planes.size(), hipMemcpyHostToDevice,
                            g->stream));
   return ICTR_OK;
 }
@@ -939,9 +926,9 @@ extern "C" int ictr_icgn_run_async(ictr_icgn *g) {
     if (int rc = ictr_icgn_hess_accumulate(g, l)) return rc;
     for (int it = 0; it < g->maxiter; ++it) {
       const bool tk = g->timing && !g->ev.empty();
-      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it)], g->stream));
+      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it)].get(), g->stream));
       const int nblk = icgn_iter_main(g, e, L, l);
-      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it) + 1], g->stream));
+      if (tk) HIPCHK(hipEventRecord(g->ev[2 * ((size_t)l * g->maxiter + it) + 1].get(), g->stream));
       hipLaunchKernelGGL(k_icgn_iter_tail, dim3(g->B), dim3(kBlock), 0, g->stream, e, L.f, nblk, 0);
     }
   }
@@ -952,7 +939,7 @@ extern "C" int ictr_icgn_run_async(ictr_icgn *g) {
 // results: warps (row-major 3x3, level-0 pixel coordinates), iterations, last dp
 extern "C" int ictr_icgn_get_results(ictr_icgn *g, double *M9_out, int *iters, float *last_dp) {
   if (!g) return fail(ICTR_ERR_INVALID, "icgn is NULL");
-  HIPCHK(hipMemcpyAsync(g->h_st.data(), g->d_st, sizeof(IcState) * g->B, hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipMemcpyAsync(g->h_st.data(), g->d_st.get(), sizeof(IcState) * g->B, hipMemcpyDeviceToHost, g->stream));
   HIPCHK(hipStreamSynchronize(g->stream));
   double K[9], Ki[9], t[9], Mp[9], Mn[9];
   icgn_K(g, K, Ki);
@@ -978,7 +965,8 @@ extern "C" int ictr_icgn_get_kernel_times(ictr_icgn *g, float *ms_per_level) {
     if (l < g->lv_l) continue;
     for (int it = 0; it < g->maxiter; ++it) {
       float ms = 0.0f;
-      HIPCHK(hipEventElapsedTime(&ms, g->ev[2 * ((size_t)l * g->maxiter + it)], g->ev[2 * ((size_t)l * g->maxiter + it) + 1]));
+      const size_t k = 2 * ((size_t)l * g->maxiter + it);
+      HIPCHK(hipEventElapsedTime(&ms, g->ev[k].get(), g->ev[k + 1].get()));
       ms_per_level[l] += ms;
     }
   }

@@ -7,11 +7,13 @@
 #include <stddef.h>
 
 #include "ictr_dev.h"
+#include "ictr_own.h"
 
 struct ictr_pyramid;
 struct ictr_p2p;
 
-// what ictr_host.hip exposes about a pyramid (ictr_icgn.hip)
+// what ictr_host.hip, the only file that sees inside ictr_pyramid, exposes about one (ictr_icgn.hip, ictr_patchflow.hip,
+// ictr_frontend.hip)
 struct ictr_pyramid_view {
   int nlev, pad;
   const int *w, *h, *sw;
@@ -157,7 +159,7 @@ void launch_ransac_finish(const RansacArgs &a, hipStream_t s);
 void launch_patchflow(const PFArgs &a, hipStream_t s);
 // NPL * 10 + WPP of this thread's last launch_patchflow (11, 41, 161 or 82), 0 before the first
 int patchflow_last_form();
-// ictr_host.hip: the argument checks of a patch tracking and its level table; the point buffers and a->K stay the caller's
+// the argument checks of a patch tracking and its level table; the point buffers and a->K stay the caller's
 int patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
                    PFArgs *a);
 

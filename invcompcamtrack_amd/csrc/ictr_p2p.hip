@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 
 #include "ictr_dev.h"
@@ -73,40 +74,41 @@ using namespace ictr;
 struct ictr_p2p {
   int rank = 0, world = 1;
   int64_t cap = 0;
-  uint64_t *mail = nullptr;
-  uint64_t *peer[kP2PMaxWorld] = {};
+  DevBuf<uint64_t> mail;
+  uint64_t *peer[kP2PMaxWorld] = {};  // peer[rank] = mail; the others are opened IPC handles
   bool opened[kP2PMaxWorld] = {};
-  int *d_err = nullptr;
+  DevBuf<int> d_err;
   unsigned seq = 0;
   bool connected = false;
   double timeout_s = 2.0;
+  ~ictr_p2p() {  // the peers' mailboxes are closed before this rank's own goes
+    (void)hipDeviceSynchronize();
+    for (int r = 0; r < world; ++r)
+      if (opened[r] && peer[r]) (void)hipIpcCloseMemHandle(peer[r]);
+  }
 };
 
 extern "C" int ictr_p2p_create(ictr_p2p **out, int rank, int world, int64_t count) {
   if (!out || world < 1 || world > kP2PMaxWorld || rank < 0 || rank >= world || count < 1 || count > (1 << 24))
     return fail(ICTR_ERR_INVALID, "p2p_create: bad arguments (world 1..%d)", kP2PMaxWorld);
   if (int rc = need_device()) return rc;
-  ictr_p2p *p = new ictr_p2p;
+  auto p = std::make_unique<ictr_p2p>();
   p->rank = rank;
   p->world = world;
   p->cap = (count + 31) / 32 * 32;
   const size_t bytes = sizeof(uint64_t) * 2 * (size_t)world * p->cap;
   // mailbox memory that remote stores and local polls see coherently: uncached (fine-grained) device memory
-  hipError_t e = hipExtMallocWithFlags((void **)&p->mail, bytes, hipDeviceMallocUncached);
-  if (e != hipSuccess) e = hipExtMallocWithFlags((void **)&p->mail, bytes, hipDeviceMallocFinegrained);
-  if (e == hipSuccess) e = hipMemset(p->mail, 0, bytes);  // tag 0 = "nothing yet"; sequence numbers start at 1
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_err, sizeof(int));
-  if (e == hipSuccess) e = hipMemset(p->d_err, 0, sizeof(int));
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    if (p->mail) (void)hipFree(p->mail);
-    if (p->d_err) (void)hipFree(p->d_err);
-    delete p;
-    return fail(ICTR_ERR_HIP, "p2p_create: mailbox allocation failed: %s", hipGetErrorString(e));
-  }
+  uint64_t *mail = nullptr;
+  hipError_t e = hipExtMallocWithFlags((void **)&mail, bytes, hipDeviceMallocUncached);
+  if (e != hipSuccess) e = hipExtMallocWithFlags((void **)&mail, bytes, hipDeviceMallocFinegrained);
+  if (e != hipSuccess) return fail(ICTR_ERR_HIP, "p2p_create: mailbox allocation failed: %s", hipGetErrorString(e));
+  p->mail.adopt(mail);
+  HIPCHK(hipMemset(mail, 0, bytes));  // tag 0 = "nothing yet"; sequence numbers start at 1
+  if (int rc = p->d_err.alloc(sizeof(int), true)) return rc;
+  HIPCHK(hipDeviceSynchronize());
   if (const char *t = getenv("ICTR_P2P_TIMEOUT_S")) p->timeout_s = std::max(0.01, atof(t));
-  p->peer[rank] = p->mail;
-  *out = p;
+  p->peer[rank] = mail;
+  *out = p.release();
   return ICTR_OK;
 }
 
@@ -116,7 +118,7 @@ extern "C" int ictr_p2p_handle_bytes(void) { return (int)sizeof(hipIpcMemHandle_
 extern "C" int ictr_p2p_local_handle(ictr_p2p *p, void *handle_out) {
   if (!p || !handle_out) return fail(ICTR_ERR_INVALID, "p2p_local_handle: NULL argument");
   hipIpcMemHandle_t h;
-  HIPCHK(hipIpcGetMemHandle(&h, p->mail));
+  HIPCHK(hipIpcGetMemHandle(&h, p->mail.get()));
   memcpy(handle_out, &h, sizeof(h));
   return ICTR_OK;
 }
@@ -145,11 +147,11 @@ extern "C" int ictr_p2p_allreduce(ictr_p2p *p, float *dev_buf, int64_t count, vo
   P2PArgs a;
   memset(&a, 0, sizeof(a));
   for (int r = 0; r < p->world; ++r) a.peer[r] = p->peer[r];
-  a.local = p->mail;
+  a.local = p->mail.get();
   a.rank = p->rank;
   a.world = p->world;
   a.cap = p->cap;
-  a.err = p->d_err;
+  a.err = p->d_err.get();
   a.limit = (unsigned long long)(p->timeout_s * 1e8);  // wall_clock64 ticks at 100 MHz
   p->seq += 1;
   if (p->seq == 0) p->seq = 1;  // tag 0 is reserved for "empty"
@@ -163,7 +165,7 @@ extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x) {
   if (!p || !x || (!p->connected && p->world > 1)) return 1;
   memset(x, 0, sizeof(*x));
   for (int r = 0; r < p->world; ++r) x->peer[r] = (unsigned long long *)p->peer[r];
-  x->local = (unsigned long long *)p->mail;
+  x->local = (unsigned long long *)p->mail.get();
   x->rank = p->rank;
   x->world = p->world;
   x->cap = p->cap;
@@ -175,16 +177,8 @@ extern "C" int ictr_p2p_error(ictr_p2p *p) {
   if (!p) return 1;
   int e = 1;
   if (hipDeviceSynchronize() != hipSuccess) return 1;
-  if (hipMemcpy(&e, p->d_err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (hipMemcpy(&e, p->d_err.get(), sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
   return e;
 }
 
-extern "C" void ictr_p2p_destroy(ictr_p2p *p) {
-  if (!p) return;
-  (void)hipDeviceSynchronize();
-  for (int r = 0; r < p->world; ++r)
-    if (p->opened[r] && p->peer[r]) (void)hipIpcCloseMemHandle(p->peer[r]);
-  if (p->mail) (void)hipFree(p->mail);
-  if (p->d_err) (void)hipFree(p->d_err);
-  delete p;
-}
+extern "C" void ictr_p2p_destroy(ictr_p2p *p) { delete p; }

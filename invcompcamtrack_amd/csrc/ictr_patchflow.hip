@@ -21,7 +21,9 @@
 // every lane's loads of an iteration are issued before the first is consumed (pixels beyond the patch read the patch's
 // first pixel and carry zero templates: no branch in the loop), and the wave sums use DPP (11 instructions) instead of
 // six dependent ds_bpermute round trips each. Same expressions in the same order per pixel: same values.
+#include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "ictr_dev.h"
 #include "ictr_launch.h"
@@ -220,3 +222,77 @@ void launch_patchflow(const PFArgs &a, hipStream_t s) {
 }
 
 }  // namespace ictr
+
+using namespace ictr;
+
+// ---------------------------------------------------------------- C-ABI
+static thread_local float g_pf_ms = -1.0f;
+extern "C" float ictr_patchflow_last_kernel_ms(void) { return g_pf_ms; }
+extern "C" int ictr_patchflow_last_form(void) { return patchflow_last_form(); }
+// the argument checks of a patch tracking and the level table of its launch (a.pts / out / status / iters and a.K are the
+// caller's): shared by ictr_patchflow and the flow grid of ictr_frontend.hip, so that both launch the same kernel on the
+// same arguments
+int ictr::patchflow_args(const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, int psz, int lv_f, int lv_l, int maxiter,
+                         float eps, PFArgs *out) {
+  if (!pyr_a || !pyr_b || psz < 1 || psz > 32 || lv_l < 0 || lv_f < lv_l || maxiter < 0)
+    return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
+  ictr_pyramid_view pa, pb;
+  ictr_pyramid_view_(pyr_a, &pa);
+  ictr_pyramid_view_(pyr_b, &pb);
+  if (lv_f >= pa.nlev || lv_f >= pb.nlev || lv_f > 15)
+    return fail(ICTR_ERR_INVALID, "patchflow: pyramids have fewer than lv_f+1 levels");
+  if (!pa.getgrad) return fail(ICTR_ERR_INVALID, "patchflow: the first pyramid needs gradient planes (getgrad = 1)");
+  if (pa.pad < psz || pb.pad < psz) return fail(ICTR_ERR_INVALID, "patchflow: pyramid padding must be >= psz");
+  for (int l = lv_l; l <= lv_f; ++l)
+    if (pa.w[l] != pb.w[l] || pa.h[l] != pb.h[l] || pa.sw[l] != pb.sw[l])
+      return fail(ICTR_ERR_INVALID, "patchflow: the two pyramids differ in size at level %d", l);
+  PFArgs &a = *out;
+  memset(&a, 0, sizeof(a));
+  for (int l = lv_l; l <= lv_f; ++l) {
+    a.lv[l].a = pa.img[l];
+    a.lv[l].ax = pa.dx[l];
+    a.lv[l].ay = pa.dy[l];
+    a.lv[l].b = pb.img[l];
+    a.lv[l].sw = pa.sw[l];
+    a.lv[l].shift = (pa.pad - psz) * (pa.sw[l] + 1);
+    a.lv[l].swo = (float)pa.w[l];
+    a.lv[l].sho = (float)pa.h[l];
+    a.lv[l].scale = (float)(1 / pow(2, l));
+  }
+  a.lv_f = lv_f;
+  a.lv_l = lv_l;
+  a.P = psz;
+  a.maxiter = maxiter;
+  a.eps2 = eps * eps;
+  a.min_det = 1e-4f;
+  return ICTR_OK;
+}
+extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
+                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
+  if (K < 0 || (K > 0 && (!pts || !out))) return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
+  PFArgs a;
+  if (int rc = patchflow_args(pa, pb, psz, lv_f, lv_l, maxiter, eps, &a)) return rc;
+  if (K == 0) return ICTR_OK;
+  if (int rc = need_device()) return rc;
+  a.K = (int)K;
+  DevBuf<float> buf;  // pts [2 K] | out [2 K] | status [K] i32 | iters [K] i32
+  if (int rc = buf.alloc(sizeof(float) * 6 * K)) return rc;
+  float *d = buf.get();
+  a.pts = d;
+  a.out = d + 2 * K;
+  a.status = reinterpret_cast<int *>(d + 4 * K);
+  a.iters = reinterpret_cast<int *>(d + 5 * K);
+  HIPCHK(hipMemcpy(d, pts, sizeof(float) * 2 * K, hipMemcpyHostToDevice));
+  // duration of the one kernel, for callers that report it; the two events live as long as their thread
+  static thread_local hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (!ev0 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
+  if (ev0) (void)hipEventRecord(ev0, nullptr);
+  launch_patchflow(a, nullptr);
+  if (ev0) (void)hipEventRecord(ev1, nullptr);
+  g_pf_ms = -1.0f;  // ... unless the launch and the first copy back succeed
+  HIPCHK(hipMemcpy(out, a.out, sizeof(float) * 2 * K, hipMemcpyDeviceToHost));
+  if (ev0 && hipEventElapsedTime(&g_pf_ms, ev0, ev1) != hipSuccess) g_pf_ms = -1.0f;
+  if (status) HIPCHK(hipMemcpy(status, a.status, sizeof(int) * K, hipMemcpyDeviceToHost));
+  if (iters) HIPCHK(hipMemcpy(iters, a.iters, sizeof(int) * K, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 
 #include "ictr_dev.h"
 #include "ictr_launch.h"
@@ -557,16 +558,18 @@ struct ictr_ransac {
   int64_t smax = 0;
   int chunk = 0, tile = 32;
   hipStream_t stream = nullptr;
-  double *d_pts = nullptr;
-  double *d_hyp = nullptr;
-  int *d_draws = nullptr, *d_status = nullptr;
-  unsigned *d_cnt = nullptr;
-  unsigned long long *d_words = nullptr;
-  char *d_out = nullptr, *h_out = nullptr;  // RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] |
-                                            // t [smax][3] | words [smax][nwords] | cnt [n] | keep [smax] | cntf [n]
+  DevBuf<double> d_pts, d_hyp;
+  DevBuf<int> d_draws, d_status;
+  DevBuf<unsigned> d_cnt;
+  DevBuf<unsigned long long> d_words;
+  DevBuf<char> d_out;  // RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] | t [smax][3] |
+  PinBuf<char> h_out;  // words [smax][nwords] | cnt [n] | keep [smax] | cntf [n]
   size_t out_bytes = 0;
   bool points_set = false, pending = false, ran = false;
-  hipEvent_t done = nullptr;
+  Event done;
+  ~ictr_ransac() {
+    if (pending) (void)hipEventSynchronize(done.get());
+  }
 };
 
 struct RanLayout {
@@ -598,17 +601,6 @@ static int ransac_chunk(int n) {
   return (int)((k + 255) / 256 * 256);
 }
 
-static void ran_free(ictr_ransac *r) {
-  if (!r) return;
-  if (r->pending) (void)hipEventSynchronize(r->done);
-  if (r->done) (void)hipEventDestroy(r->done);
-  if (r->h_out) (void)hipHostFree(r->h_out);
-  for (void *p : {(void *)r->d_pts, (void *)r->d_hyp, (void *)r->d_draws, (void *)r->d_status, (void *)r->d_cnt,
-                  (void *)r->d_words, (void *)r->d_out})
-    if (p) (void)hipFree(p);
-  delete r;
-}
-
 static int ran_refuse_pending(const ictr_ransac *r, const char *what) {
   if (r->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_ransac_wait first", what);
   return ICTR_OK;
@@ -621,7 +613,7 @@ extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samp
   if (max_samples < 1 || max_samples > ((int64_t)1 << 24))
     return fail(ICTR_ERR_INVALID, "ransac_create: max_samples %lld (1 .. 2^24)", (long long)max_samples);
   if (int rc = need_device()) return rc;
-  ictr_ransac *r = new ictr_ransac;
+  auto r = std::make_unique<ictr_ransac>();
   r->n = (int)n;
   r->nwords = (int)((n + 63) / 64);
   r->smax = max_samples;
@@ -629,37 +621,28 @@ extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samp
   const int tile = env_int("ICTR_RANSAC_TILE", 32);
   r->tile = (tile == 16 || tile == 64) ? tile : 32;
   const size_t K = (size_t)r->chunk;
-  r->out_bytes = ran_layout(r).end;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-  };
-  alloc((void **)&r->d_pts, sizeof(double) * 5 * n);
-  alloc((void **)&r->d_hyp, sizeof(double) * 12 * K);
-  alloc((void **)&r->d_draws, sizeof(int) * 4 * K);
-  alloc((void **)&r->d_status, sizeof(int) * K);
-  alloc((void **)&r->d_cnt, sizeof(unsigned) * K);
-  alloc((void **)&r->d_words, sizeof(unsigned long long) * K * r->nwords);
-  alloc((void **)&r->d_out, r->out_bytes);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_out, r->out_bytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    ran_free(r);
-    return fail(ICTR_ERR_HIP, "ransac_create: device allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = r;
+  r->out_bytes = ran_layout(r.get()).end;
+  if (int rc = r->d_pts.alloc(sizeof(double) * 5 * n, true)) return rc;
+  if (int rc = r->d_hyp.alloc(sizeof(double) * 12 * K, true)) return rc;
+  if (int rc = r->d_draws.alloc(sizeof(int) * 4 * K, true)) return rc;
+  if (int rc = r->d_status.alloc(sizeof(int) * K, true)) return rc;
+  if (int rc = r->d_cnt.alloc(sizeof(unsigned) * K, true)) return rc;
+  if (int rc = r->d_words.alloc(sizeof(unsigned long long) * K * r->nwords, true)) return rc;
+  if (int rc = r->d_out.alloc(r->out_bytes, true)) return rc;
+  if (int rc = r->h_out.alloc(r->out_bytes)) return rc;
+  if (int rc = r->done.create(hipEventDisableTiming)) return rc;
+  *out = r.release();
   return ICTR_OK;
 }
 
-extern "C" void ictr_ransac_destroy(ictr_ransac *r) { ran_free(r); }
+extern "C" void ictr_ransac_destroy(ictr_ransac *r) { delete r; }
 
 extern "C" int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const double *pt3d) {
   if (!r || !pt2d || !pt3d) return fail(ICTR_ERR_INVALID, "ransac_set_points: NULL argument");
   if (int rc = ran_refuse_pending(r, "ransac_set_points")) return rc;
   const size_t n = (size_t)r->n;
-  HIPCHK(hipMemcpy(r->d_pts, pt2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(r->d_pts + 2 * n, pt3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(r->d_pts.get(), pt2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(r->d_pts.get() + 2 * n, pt3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
   r->points_set = true;
   return ICTR_OK;
 }
@@ -675,7 +658,7 @@ static int ran_fill_args(const ictr_ransac *r, const char *what, const double *f
     return fail(ICTR_ERR_INVALID, "%s: the camera (fc, cc, kc) must be finite, fc non-zero", what);
   const RanLayout L = ran_layout(r);
   memset(&a, 0, sizeof(a));
-  a.pts = r->d_pts;
+  a.pts = r->d_pts.get();
   a.n = r->n;
   a.nwords = r->nwords;
   a.fx = fc[0];
@@ -688,20 +671,20 @@ static int ran_fill_args(const ictr_ransac *r, const char *what, const double *f
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   a.seedmix = z ^ (z >> 31);
-  a.hyp = r->d_hyp;
-  a.draws = r->d_draws;
-  a.status = r->d_status;
-  a.cnt = r->d_cnt;
-  a.words = r->d_words;
-  a.st = reinterpret_cast<RansacState *>(r->d_out);
-  a.o_trial = reinterpret_cast<long long *>(r->d_out + L.trial);
-  a.o_draws = reinterpret_cast<int *>(r->d_out + L.draws);
-  a.o_R = reinterpret_cast<double *>(r->d_out + L.R);
-  a.o_t = reinterpret_cast<double *>(r->d_out + L.t);
-  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out + L.words);
-  a.o_cnt = reinterpret_cast<int *>(r->d_out + L.cnt);
-  a.o_keep = reinterpret_cast<int *>(r->d_out + L.keep);
-  a.o_cntf = reinterpret_cast<int *>(r->d_out + L.cntf);
+  a.hyp = r->d_hyp.get();
+  a.draws = r->d_draws.get();
+  a.status = r->d_status.get();
+  a.cnt = r->d_cnt.get();
+  a.words = r->d_words.get();
+  a.st = reinterpret_cast<RansacState *>(r->d_out.get());
+  a.o_trial = reinterpret_cast<long long *>(r->d_out.get() + L.trial);
+  a.o_draws = reinterpret_cast<int *>(r->d_out.get() + L.draws);
+  a.o_R = reinterpret_cast<double *>(r->d_out.get() + L.R);
+  a.o_t = reinterpret_cast<double *>(r->d_out.get() + L.t);
+  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out.get() + L.words);
+  a.o_cnt = reinterpret_cast<int *>(r->d_out.get() + L.cnt);
+  a.o_keep = reinterpret_cast<int *>(r->d_out.get() + L.keep);
+  a.o_cntf = reinterpret_cast<int *>(r->d_out.get() + L.cntf);
   return ICTR_OK;
 }
 
@@ -720,12 +703,12 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   r->stream = (hipStream_t)hip_stream;
   a.nsamples = nsamples;
   a.maxtrials = maxtrials;
-  HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), r->stream));
+  HIPCHK(hipMemsetAsync(r->d_out.get(), 0, sizeof(RansacState), r->stream));
   const int64_t K = r->chunk;
   const int64_t nchunks = (maxtrials + K - 1) / K;
   for (int64_t c = 0; c < nchunks; ++c) {
     if (c > 0 && c % kRanGroup == 0) {  // a long run: stop enqueueing once the samples are found
-      RansacState *hs = reinterpret_cast<RansacState *>(r->h_out);
+      RansacState *hs = reinterpret_cast<RansacState *>(r->h_out.get());
       HIPCHK(hipMemcpyAsync(&hs->done, &a.st->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
       HIPCHK(hipStreamSynchronize(r->stream));
       if (*(volatile int *)&hs->done) break;
@@ -737,8 +720,8 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   }
   launch_ransac_finish(a, r->stream);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out, r->out_bytes, hipMemcpyDeviceToHost, r->stream));
-  HIPCHK(hipEventRecord(r->done, r->stream));
+  HIPCHK(hipMemcpyAsync(r->h_out.get(), r->d_out.get(), r->out_bytes, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipEventRecord(r->done.get(), r->stream));
   r->pending = true;
   r->ran = true;
   return ICTR_OK;
@@ -748,14 +731,14 @@ extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, doub
                                 int32_t *inl_cnt) {
   if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
   if (!r->pending) return fail(ICTR_ERR_STATE, "ransac_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(r->done));
+  HIPCHK(hipEventSynchronize(r->done.get()));
   r->pending = false;
   const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
-  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
-  const double *hR = reinterpret_cast<const double *>(r->h_out + L.R);
-  const double *ht = reinterpret_cast<const double *>(r->h_out + L.t);
-  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->h_out + L.words);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out.get());
+  const int *keep = reinterpret_cast<const int *>(r->h_out.get() + L.keep);
+  const double *hR = reinterpret_cast<const double *>(r->h_out.get() + L.R);
+  const double *ht = reinterpret_cast<const double *>(r->h_out.get() + L.t);
+  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->h_out.get() + L.words);
   if (counts) {
     counts[0] = st.kept;
     counts[1] = st.held;
@@ -777,7 +760,7 @@ extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, doub
     }
     if (inl_words) memcpy(inl_words + (size_t)r->nwords * q, hw + (size_t)r->nwords * s, 8 * (size_t)r->nwords);
   }
-  if (inl_cnt) memcpy(inl_cnt, r->h_out + L.cntf, sizeof(int32_t) * (size_t)st.n_ic);
+  if (inl_cnt) memcpy(inl_cnt, r->h_out.get() + L.cntf, sizeof(int32_t) * (size_t)st.n_ic);
   return ICTR_OK;
 }
 
@@ -785,10 +768,10 @@ extern "C" int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t
   if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
   if (r->pending || !r->ran) return fail(ICTR_ERR_STATE, "ransac_samples: no completed run");
   const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out);
-  const int *keep = reinterpret_cast<const int *>(r->h_out + L.keep);
-  const long long *ht = reinterpret_cast<const long long *>(r->h_out + L.trial);
-  const int *hd = reinterpret_cast<const int *>(r->h_out + L.draws);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out.get());
+  const int *keep = reinterpret_cast<const int *>(r->h_out.get() + L.keep);
+  const long long *ht = reinterpret_cast<const long long *>(r->h_out.get() + L.trial);
+  const int *hd = reinterpret_cast<const int *>(r->h_out.get() + L.draws);
   for (long long q = 0; q < st.kept; ++q) {
     if (trial) trial[q] = ht[keep[q]];
     if (draws) memcpy(draws + 4 * q, hd + 4 * (size_t)keep[q], 4 * sizeof(int32_t));
@@ -812,7 +795,7 @@ extern "C" int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const 
   if (int rc = ran_fill_args(r, "debug_ransac_trials", fc, cc, kc, inlthresh, seed, a)) return rc;
   a.nsamples = 1;
   a.maxtrials = first_trial + count;
-  HIPCHK(hipMemsetAsync(r->d_out, 0, sizeof(RansacState), nullptr));
+  HIPCHK(hipMemsetAsync(r->d_out.get(), 0, sizeof(RansacState), nullptr));
   const int64_t K = r->chunk;
   const size_t W = (size_t)r->nwords;
   for (int64_t done = 0; done < count; done += K) {
@@ -821,11 +804,11 @@ extern "C" int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const 
     const size_t k = (size_t)a.k, o = (size_t)done;
     launch_ransac_hyp_score(a, r->tile, nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(status + o, r->d_status, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(draws + 4 * o, r->d_draws, sizeof(int32_t) * 4 * k, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hyp + 12 * o, r->d_hyp, sizeof(double) * 12 * k, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cnt + o, r->d_cnt, sizeof(uint32_t) * k, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(words + W * o, r->d_words, sizeof(uint64_t) * W * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status + o, r->d_status.get(), sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(draws + 4 * o, r->d_draws.get(), sizeof(int32_t) * 4 * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hyp + 12 * o, r->d_hyp.get(), sizeof(double) * 12 * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt + o, r->d_cnt.get(), sizeof(uint32_t) * k, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(words + W * o, r->d_words.get(), sizeof(uint64_t) * W * k, hipMemcpyDeviceToHost));
   }
   return ICTR_OK;
 }

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "ictr_dev.h"
@@ -369,28 +370,20 @@ using namespace ictr;
 struct ictr_triang {
   int64_t max_points = 0, max_obs = 0, max_frames = 0;
   int64_t n = 0, m = 0, F = 0, packed_cap = 0;
-  float *d_P = nullptr;
-  long long *d_off = nullptr, *d_tbase = nullptr, *d_meta = nullptr;
-  int *d_view = nullptr, *d_tlen = nullptr, *d_pv = nullptr;
-  float *d_x = nullptr, *d_y = nullptr, *d_px = nullptr, *d_py = nullptr;
-  float *d_in = nullptr, *h_in = nullptr;   // init | campos | ptdir, [max_points][3] each; h_in pinned
-  char *d_out = nullptr, *h_out = nullptr;  // pts [n][3] | cov [n][9] | iters [n] | status [n]; h_out pinned
-  hipEvent_t done = nullptr;
+  DevBuf<float> d_P;
+  DevBuf<long long> d_off, d_tbase, d_meta;
+  DevBuf<int> d_view, d_tlen, d_pv;
+  DevBuf<float> d_x, d_y, d_px, d_py;
+  DevBuf<float> d_in;  // init | campos | ptdir, [max_points][3] each
+  PinBuf<float> h_in;
+  DevBuf<char> d_out;  // pts [n][3] | cov [n][9] | iters [n] | status [n]
+  PinBuf<char> h_out;
+  Event done;
   bool cams_set = false, tracks_set = false, pending = false;
+  ~ictr_triang() {
+    if (pending) (void)hipEventSynchronize(done.get());
+  }
 };
-
-static void tri_free(ictr_triang *t) {
-  if (!t) return;
-  if (t->pending) (void)hipEventSynchronize(t->done);
-  if (t->done) (void)hipEventDestroy(t->done);
-  if (t->h_in) (void)hipHostFree(t->h_in);
-  if (t->h_out) (void)hipHostFree(t->h_out);
-  for (void *p : {(void *)t->d_P, (void *)t->d_off, (void *)t->d_tbase, (void *)t->d_meta, (void *)t->d_view,
-                  (void *)t->d_tlen, (void *)t->d_pv, (void *)t->d_x, (void *)t->d_y, (void *)t->d_px, (void *)t->d_py,
-                  (void *)t->d_in, (void *)t->d_out})
-    if (p) (void)hipFree(p);
-  delete t;
-}
 
 static int tri_refuse_pending(const ictr_triang *t, const char *what) {
   if (t->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_triang_wait first", what);
@@ -406,37 +399,29 @@ extern "C" int ictr_triang_create(ictr_triang **out, int64_t max_points, int64_t
   if (max_frames < 1 || max_frames > ((int64_t)1 << 20))
     return fail(ICTR_ERR_INVALID, "triang_create: max_frames %lld (1 .. 2^20)", (long long)max_frames);
   if (int rc = need_device()) return rc;
-  ictr_triang *t = new ictr_triang;
+  auto t = std::make_unique<ictr_triang>();
   t->max_points = max_points;
   t->max_obs = max_obs;
   t->max_frames = max_frames;
   const size_t N = (size_t)max_points, M = (size_t)max_obs, tiles = (N + 63) / 64;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void **p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-  };
-  alloc((void **)&t->d_P, sizeof(float) * 12 * (size_t)max_frames);
-  alloc((void **)&t->d_off, sizeof(long long) * (N + 1));
-  alloc((void **)&t->d_tbase, sizeof(long long) * tiles);
-  alloc((void **)&t->d_tlen, sizeof(int) * tiles);
-  alloc((void **)&t->d_meta, sizeof(long long) * 2);
-  alloc((void **)&t->d_view, sizeof(int) * M);
-  alloc((void **)&t->d_x, sizeof(float) * M);
-  alloc((void **)&t->d_y, sizeof(float) * M);
-  alloc((void **)&t->d_in, sizeof(float) * 9 * N);
-  alloc((void **)&t->d_out, sizeof(float) * 14 * N);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_in, sizeof(float) * 9 * N, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_out, sizeof(float) * 14 * N, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    tri_free(t);
-    return fail(ICTR_ERR_HIP, "triang_create: device allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = t;
+  if (int rc = t->d_P.alloc(sizeof(float) * 12 * (size_t)max_frames)) return rc;
+  if (int rc = t->d_off.alloc(sizeof(long long) * (N + 1))) return rc;
+  if (int rc = t->d_tbase.alloc(sizeof(long long) * tiles)) return rc;
+  if (int rc = t->d_tlen.alloc(sizeof(int) * tiles)) return rc;
+  if (int rc = t->d_meta.alloc(sizeof(long long) * 2)) return rc;
+  if (int rc = t->d_view.alloc(sizeof(int) * M)) return rc;
+  if (int rc = t->d_x.alloc(sizeof(float) * M)) return rc;
+  if (int rc = t->d_y.alloc(sizeof(float) * M)) return rc;
+  if (int rc = t->d_in.alloc(sizeof(float) * 9 * N)) return rc;
+  if (int rc = t->d_out.alloc(sizeof(float) * 14 * N)) return rc;
+  if (int rc = t->h_in.alloc(sizeof(float) * 9 * N)) return rc;
+  if (int rc = t->h_out.alloc(sizeof(float) * 14 * N)) return rc;
+  if (int rc = t->done.create(hipEventDisableTiming)) return rc;
+  *out = t.release();
   return ICTR_OK;
 }
 
-extern "C" void ictr_triang_destroy(ictr_triang *t) { tri_free(t); }
+extern "C" void ictr_triang_destroy(ictr_triang *t) { delete t; }
 
 extern "C" int ictr_triang_set_cameras(ictr_triang *t, const float *P, int64_t nframes) {
   if (!t || !P) return fail(ICTR_ERR_INVALID, "triang_set_cameras: NULL argument");
@@ -444,7 +429,7 @@ extern "C" int ictr_triang_set_cameras(ictr_triang *t, const float *P, int64_t n
   if (nframes < 1 || nframes > t->max_frames)
     return fail(ICTR_ERR_INVALID, "triang_set_cameras: %lld frames (1 .. %lld, the size given at creation)",
                 (long long)nframes, (long long)t->max_frames);
-  HIPCHK(hipMemcpy(t->d_P, P, sizeof(float) * 12 * (size_t)nframes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->d_P.get(), P, sizeof(float) * 12 * (size_t)nframes, hipMemcpyHostToDevice));
   if (nframes < t->F) t->tracks_set = false;  // the tracks were checked against more frames
   t->F = nframes;
   t->cams_set = true;
@@ -465,52 +450,51 @@ extern "C" int ictr_triang_set_tracks(ictr_triang *t, int64_t n, const int64_t *
                 "triang_set_tracks: offsets run from %lld to %lld (0 .. at least 2 views per point, at most %lld, the "
                 "size given at creation)", (long long)offsets[0], (long long)M, (long long)t->max_obs);
   t->tracks_set = false;
-  HIPCHK(hipMemcpy(t->d_off, offsets, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(t->d_view, view, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(t->d_x, x, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(t->d_y, y, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->d_off.get(), offsets, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->d_view.get(), view, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->d_x.get(), x, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->d_y.get(), y, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
   TriPack a;
-  a.off = t->d_off;
-  a.view = t->d_view;
-  a.x = t->d_x;
-  a.y = t->d_y;
+  a.off = t->d_off.get();
+  a.view = t->d_view.get();
+  a.x = t->d_x.get();
+  a.y = t->d_y.get();
   a.n = (int)n;
   a.tiles = (int)((n + 63) / 64);
   a.F = (int)t->F;
-  a.tlen = t->d_tlen;
-  a.tbase = t->d_tbase;
-  a.meta = t->d_meta;
+  a.tlen = t->d_tlen.get();
+  a.tbase = t->d_tbase.get();
+  a.meta = t->d_meta.get();
   a.pv = nullptr;
   a.px = a.py = nullptr;
-  HIPCHK(hipMemset(t->d_meta, 0, sizeof(long long) * 2));
+  HIPCHK(hipMemset(t->d_meta.get(), 0, sizeof(long long) * 2));
   hipLaunchKernelGGL(k_tri_tiles, dim3((a.tiles + kTriBlock - 1) / kTriBlock), dim3(kTriBlock), 0, nullptr, a);
   hipLaunchKernelGGL(k_tri_scan, dim3(1), dim3(kTriBlock), 0, nullptr, a);
   HIPCHK(hipGetLastError());
   long long meta[2] = {0, 0};
-  HIPCHK(hipMemcpy(meta, t->d_meta, sizeof(meta), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(meta, t->d_meta.get(), sizeof(meta), hipMemcpyDeviceToHost));
   if (meta[1] & 1) return fail(ICTR_ERR_INVALID, "triang_set_tracks: a track has fewer than 2 views");
   // every length is >= 2 and the offsets end at M: they ascend inside 0 .. M, and no tile is longer than M
   if (meta[0] < 64 || meta[0] > 64 * M || meta[0] > ((long long)1 << 31))
     return fail(ICTR_ERR_INVALID, "triang_set_tracks: the tile-major track table needs %lld slots (at most 2^31)", meta[0]);
   if (meta[0] > t->packed_cap) {
-    for (void *p : {(void *)t->d_pv, (void *)t->d_px, (void *)t->d_py})
-      if (p) (void)hipFree(p);
-    t->d_pv = nullptr;
-    t->d_px = t->d_py = nullptr;
     t->packed_cap = 0;
-    HIPCHK(hipMalloc((void **)&t->d_pv, sizeof(int) * (size_t)meta[0]));
-    HIPCHK(hipMalloc((void **)&t->d_px, sizeof(float) * (size_t)meta[0]));
-    HIPCHK(hipMalloc((void **)&t->d_py, sizeof(float) * (size_t)meta[0]));
+    t->d_pv.reset();
+    t->d_px.reset();
+    t->d_py.reset();
+    if (int rc = t->d_pv.alloc(sizeof(int) * (size_t)meta[0])) return rc;
+    if (int rc = t->d_px.alloc(sizeof(float) * (size_t)meta[0])) return rc;
+    if (int rc = t->d_py.alloc(sizeof(float) * (size_t)meta[0])) return rc;
     t->packed_cap = meta[0];
   }
-  a.pv = t->d_pv;
-  a.px = t->d_px;
-  a.py = t->d_py;
+  a.pv = t->d_pv.get();
+  a.px = t->d_px.get();
+  a.py = t->d_py.get();
   // slots beyond a track's end are never read; the index table still starts from zeros, not from stale words
-  HIPCHK(hipMemset(t->d_pv, 0, sizeof(int) * (size_t)meta[0]));
+  HIPCHK(hipMemset(t->d_pv.get(), 0, sizeof(int) * (size_t)meta[0]));
   hipLaunchKernelGGL(k_tri_pack, dim3((a.n + kTriBlock - 1) / kTriBlock), dim3(kTriBlock), 0, nullptr, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(meta, t->d_meta, sizeof(meta), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(meta, t->d_meta.get(), sizeof(meta), hipMemcpyDeviceToHost));
   if (meta[1] & 2)
     return fail(ICTR_ERR_INVALID, "triang_set_tracks: a view index is outside 0 .. %lld (the frames set)",
                 (long long)t->F - 1);
@@ -540,12 +524,12 @@ extern "C" int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_param
   const size_t n = (size_t)t->n;
   TriArgs a;
   memset(&a, 0, sizeof(a));
-  a.P = t->d_P;
-  a.off = t->d_off;
-  a.tbase = t->d_tbase;
-  a.pv = t->d_pv;
-  a.px = t->d_px;
-  a.py = t->d_py;
+  a.P = t->d_P.get();
+  a.off = t->d_off.get();
+  a.tbase = t->d_tbase.get();
+  a.pv = t->d_pv.get();
+  a.px = t->d_px.get();
+  a.py = t->d_py.get();
   a.n = (int)t->n;
   if (iterative) {
     a.noiter = params->noiter;
@@ -554,27 +538,27 @@ extern "C" int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_param
     a.damp_fct = params->damp_fct;
     a.maxdamp = params->maxdamp;
     // through the object's pinned buffer: the copies below are then asynchronous for any caller memory
-    memcpy(t->h_in, init_pts, sizeof(float) * 3 * n);
+    memcpy(t->h_in.get(), init_pts, sizeof(float) * 3 * n);
     size_t words = 3 * n;
     if (mode == ICTR_TRIANG_DEPTH) {
-      memcpy(t->h_in + 3 * n, campos, sizeof(float) * 3 * n);
-      memcpy(t->h_in + 6 * n, ptdir, sizeof(float) * 3 * n);
+      memcpy(t->h_in.get() + 3 * n, campos, sizeof(float) * 3 * n);
+      memcpy(t->h_in.get() + 6 * n, ptdir, sizeof(float) * 3 * n);
       words = 9 * n;
     }
-    HIPCHK(hipMemcpyAsync(t->d_in, t->h_in, sizeof(float) * words, hipMemcpyHostToDevice, s));
-    a.init = t->d_in;
-    a.campos = t->d_in + 3 * n;
-    a.ptdir = t->d_in + 6 * n;
+    HIPCHK(hipMemcpyAsync(t->d_in.get(), t->h_in.get(), sizeof(float) * words, hipMemcpyHostToDevice, s));
+    a.init = t->d_in.get();
+    a.campos = t->d_in.get() + 3 * n;
+    a.ptdir = t->d_in.get() + 6 * n;
   }
-  float *o = reinterpret_cast<float *>(t->d_out);
+  float *o = reinterpret_cast<float *>(t->d_out.get());
   a.pts = o;
   a.cov = o + 3 * n;
   a.iters = reinterpret_cast<int *>(o + 12 * n);
   a.status = reinterpret_cast<int *>(o + 13 * n);
   launch_triang(mode, a, s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->h_out, t->d_out, sizeof(float) * 14 * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(t->done, s));
+  HIPCHK(hipMemcpyAsync(t->h_out.get(), t->d_out.get(), sizeof(float) * 14 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(t->done.get(), s));
   t->pending = true;
   return ICTR_OK;
 }
@@ -582,10 +566,10 @@ extern "C" int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_param
 extern "C" int ictr_triang_wait(ictr_triang *t, float *pts, float *cov, int32_t *iters, int32_t *status) {
   if (!t) return fail(ICTR_ERR_INVALID, "triang is NULL");
   if (!t->pending) return fail(ICTR_ERR_STATE, "triang_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(t->done));
+  HIPCHK(hipEventSynchronize(t->done.get()));
   t->pending = false;
   const size_t n = (size_t)t->n;
-  const float *o = reinterpret_cast<const float *>(t->h_out);
+  const float *o = reinterpret_cast<const float *>(t->h_out.get());
   if (pts) memcpy(pts, o, sizeof(float) * 3 * n);
   if (cov) memcpy(cov, o + 3 * n, sizeof(float) * 9 * n);
   if (iters) memcpy(iters, o + 12 * n, sizeof(int32_t) * n);
@@ -601,6 +585,7 @@ static int tri_single(int mode, float *pt3d, float *cov, const float *campos, co
   if (noviews < 2 || noviews > (1 << 20)) return fail(ICTR_ERR_INVALID, "triangulate: %d views (2 .. 2^20)", noviews);
   ictr_triang *t = nullptr;
   if (int rc = ictr_triang_create(&t, 1, noviews, noviews)) return rc;
+  const std::unique_ptr<ictr_triang> own(t);
   std::vector<float> Pt((size_t)noviews * 12);
   std::vector<int32_t> view((size_t)noviews);
   for (int v = 0; v < noviews; ++v) {
@@ -614,7 +599,6 @@ static int tri_single(int mode, float *pt3d, float *cov, const float *campos, co
   if (!rc) rc = ictr_triang_set_tracks(t, 1, off, view.data(), pt2d, pt2d + noviews);
   if (!rc) rc = ictr_triang_run(t, mode, prm, pt3d, campos, ptdir, nullptr);
   if (!rc) rc = ictr_triang_wait(t, out, c9, &it, nullptr);
-  ictr_triang_destroy(t);
   if (rc) return rc;
   memcpy(pt3d, out, sizeof(out));
   // a loop that never ran leaves the caller's covariance as it was, as the reference does
