@@ -236,6 +236,11 @@ int ictr_odometer_get_norm(const ictr_odometer *odo, double *meanshift3, double 
   (ICTR_VARIANT_ANY_SIZE | ICTR_VARIANT_H_BY_SETUP | ICTR_VARIANT_LAUNCHES | ICTR_VARIANT_ONE_LAUNCH |              \
    ICTR_VARIANT_NO_GRAPH | ICTR_VARIANT_SEPARATE_BEGIN | ICTR_VARIANT_NO_TEAMS | ICTR_VARIANT_NO_RESIDENT |         \
    ICTR_VARIANT_DEBUG_MUTE | ICTR_VARIANT_GRAD_PLANES | ICTR_VARIANT_DYNAMIC_LOOP)
+/* A kernel-form bit of the same word, accepted beside the ICTR_VARIANT_* bits (a family of its own: it selects inside
+ * one kernel, not a launch form). Bit 29: the 8x8 setup kernel's static groups read the reference image with direct
+ * taps and line touches at every level, never through the per-wave LDS tile (bit-identical patches, sums and poses). */
+#define ICTR_REF8_DIRECT_TAPS 0x20000000
+#define ICTR_SELECT_ALL (ICTR_VARIANT_ALL | ICTR_REF8_DIRECT_TAPS)
 int ictr_odometer_set_variant(ictr_odometer *odo, int variant);
 /* one-launch tracker, team form (see ictr_batch_set_team) */
 int ictr_odometer_set_team(ictr_odometer *odo, int target_points, int min_points, int max_points);

@@ -3,6 +3,7 @@ per-frame tracking hot path). See DESIGN.md. The HIP library is loaded lazily by
 importing this package never touches the GPU and never falls back to a CPU implementation."""
 from . import _lib  # noqa: F401
 from ._lib import IctrError  # noqa: F401
+from ._lib import REF8_DIRECT_TAPS  # noqa: F401
 from ._lib import (VARIANT_ALL, VARIANT_ANY_SIZE, VARIANT_DEBUG_MUTE, VARIANT_DYNAMIC_LOOP, VARIANT_GRAD_PLANES,  # noqa: F401
                    VARIANT_H_BY_SETUP, VARIANT_LAUNCHES, VARIANT_NO_GRAPH, VARIANT_NO_RESIDENT, VARIANT_NO_TEAMS,
                    VARIANT_ONE_LAUNCH, VARIANT_SEPARATE_BEGIN)

@@ -44,6 +44,9 @@ VARIANT_DYNAMIC_LOOP = 1 << 28      # the 8x8 setup kernel's dynamic patch loop 
 VARIANT_ALL = (VARIANT_ANY_SIZE | VARIANT_H_BY_SETUP | VARIANT_LAUNCHES | VARIANT_ONE_LAUNCH | VARIANT_NO_GRAPH
                | VARIANT_SEPARATE_BEGIN | VARIANT_NO_TEAMS | VARIANT_NO_RESIDENT | VARIANT_DEBUG_MUTE
                | VARIANT_GRAD_PLANES | VARIANT_DYNAMIC_LOOP)
+# a kernel-form bit of the same word (include/ictr.h ICTR_REF8_DIRECT_TAPS): the 8x8 setup kernel's direct taps at every
+# level, never the LDS tile (same bits)
+REF8_DIRECT_TAPS = 1 << 29
 
 
 class OptParam(C.Structure):

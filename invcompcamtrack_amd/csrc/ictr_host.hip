@@ -872,10 +872,10 @@ extern "C" int ictr_batch_set_peer_exchange(ictr_batch *b, ictr_p2p *p) {
 
 extern "C" int ictr_batch_set_variant(ictr_batch *b, int variant) {
   if (!b) return fail(ICTR_ERR_INVALID, "batch is NULL");
-  if (variant & ~ICTR_VARIANT_ALL)
+  if (variant & ~ICTR_SELECT_ALL)
     return fail(ICTR_ERR_INVALID, "set_variant: unknown selection bits 0x%x (known: ICTR_VARIANT_ANY_SIZE, H_BY_SETUP, "
                                   "LAUNCHES, ONE_LAUNCH, NO_GRAPH, SEPARATE_BEGIN, NO_TEAMS, NO_RESIDENT, DEBUG_MUTE, "
-                                  "GRAD_PLANES, DYNAMIC_LOOP = 0x%x)", variant & ~ICTR_VARIANT_ALL, ICTR_VARIANT_ALL);
+                                  "GRAD_PLANES, DYNAMIC_LOOP, ICTR_REF8_DIRECT_TAPS = 0x%x)", variant & ~ICTR_SELECT_ALL, ICTR_SELECT_ALL);
   b->variant = variant;
   return ICTR_OK;
 }

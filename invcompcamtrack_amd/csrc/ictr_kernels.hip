@@ -675,12 +675,33 @@ struct RefLoads {
 // ST (with OTF, without PN): the chunk's patches in statically unrolled groups of SIXTEEN -- three windows in flight,
 // and the three sums of S per patch by the transposing wave reduction of the resident kernel (TrAcc, ictr_devfn.h: ~10
 // instructions per patch instead of the 42 of three wave sums + selects); everything else as in the dynamic form.
-template <bool PN, int kU, bool PK, bool OTF = false, bool ST = false>  // PK: packed {img, dx, dy, 0} planes; OTF: image plane only
+//
+// TB > 0 (with ST), the STAGED form: the reference image reaches the lanes through LDS instead of the L1. Per wave and
+// 16-patch group the bounding box of the group's windows (rows rmin-2 .. rmax+8, columns cmin-2 .. cmax+8 rounded out to
+// 128-byte lines) is copied into a tile of TB bytes that is private to the wave: one direct-to-LDS buffer load per box
+// row, 16 bytes per lane, consecutive lanes along the row -- every line of the box is requested once, by one
+// instruction, so no load ever finds its line "miss pending" behind another one of the kernel's own. The tile holds the
+// padded plane's bytes as they are (row r at r * pitch, from the row's own line boundary on); the twelve texels per lane
+// come out of it with LDS reads into the same TapLoadsOTF, and taps_blend_otf runs on them unchanged: the same bits.
+// pitch = lines * 128 plus, where the tile has the room, the few bytes that put four consecutive rows on different LDS
+// banks. A group whose box does not fit the tile (scattered points) takes the direct taps; the choice is wave-uniform.
+// The buffer resource is bounded by the plane: what the rounding to lines adds beyond it reads as zeros and is never
+// consumed. The line touches of the ST form go away here.
+struct RefBox {
+  int on;        // the group's taps come from the tile
+  int a0;        // byte address (mod 2^32 of the plane's line grid) of the box's first texel
+  int pitch;     // bytes from one tile row to the next
+  int r0, c0;    // padded coordinates of the box's first texel
+};
+template <bool PN, int kU, bool PK, bool OTF = false, bool ST = false, int TB = 0>  // PK: packed {img, dx, dy, 0} planes; OTF: image plane only
 __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int level, int cpw) {
   static_assert(PK != OTF, "the taps come from either the packed planes or the image plane");
   static_assert(!ST || (OTF && !PN), "the static form exists for on-the-fly gradients without patch normalisation");
+  static_assert(TB == 0 || (ST && TB % 16 == 0), "the staged form is a static form; 16-byte pieces");
+  constexpr bool STG = TB > 0;
   __shared__ __attribute__((aligned(16))) float sRec[kWaves][64 * kRec];
   __shared__ float sW[kWaves][kPartHStride];
+  __shared__ __attribute__((aligned(16))) char sTile[STG ? kWaves * TB : 16];
   const int b = blockIdx.y;
   const ProbState &st = e.st[b];
   const int npts = st.npts;
@@ -705,6 +726,66 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
 
   float accH = 0.0f;  // lane j < 21: the wave's sum of H entry j (upper triangle, row-major)
 
+  // (STG) the wave's tile; the image plane as a bounded buffer (the pointer is wave-uniform but comes out of a table in
+  // memory: say so, as the resident prologue does); the plane's position on the 128-byte line grid; the tile rows' bank
+  // stagger: image rows are sw floats apart, four consecutive ones are read by one 32-lane half of an LDS read, 8 lanes
+  // each -- the pad makes the step from row to row 8 or 24 banks (mod 32) where sw alone would not
+  char *const tile = sTile + (STG ? wave * TB : 0);
+  const int tile_lds = __builtin_amdgcn_readfirstlane((int)(unsigned long long)(__attribute__((address_space(3))) char *)tile);
+  const int sw4 = sw * 4;
+  int base_low = 0, pad_b = 0;
+  typedef int i32x4_t __attribute__((ext_vector_type(4)));
+  i32x4_t rimg = {0, 0, 0, 0};  // the buffer resource: base, no stride, the plane's bytes, raw 32-bit data
+  if constexpr (STG) {
+    const unsigned long long pr64 = reinterpret_cast<unsigned long long>(pl.ref);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pr64), hi = __builtin_amdgcn_readfirstlane((unsigned)(pr64 >> 32));
+    rimg = (i32x4_t){(int)lo, (int)(hi & 0xffffu), __builtin_amdgcn_readfirstlane(sw4 * (hl + 2 * padl)), 0x00020000};
+    base_low = (int)(lo & 127u);
+    const int to8 = (8 - sw) & 31, to24 = (24 - sw) & 31;
+    pad_b = (min(to8, to24) * 4 + 8) & ~15;
+  }
+  int bx_rmin = 0, bx_rmax = 0, bx_cmin = 0, bx_cmax = 0;  // (STG) per 16-lane row: the bounding box of its points' windows
+  // (STG) box of the chunk's group g0 -> tile: one load per box row, lanes = the row's 16-byte pieces
+  auto stage_box = [&](int g0) {
+    RefBox bx;
+    const int rmin = rlane(bx_rmin, g0), rmax = rlane(bx_rmax, g0), cmin = rlane(bx_cmin, g0), cmax = rlane(bx_cmax, g0);
+    const bool any = rmin <= rmax;  // some point of the group is in view
+    const int nrows = any ? rmax - rmin + 11 : 0, wb = any ? (cmax - cmin + 11) * 4 : 0;
+    bx.r0 = any ? rmin - 2 : 0;
+    bx.c0 = any ? cmin - 2 : 0;
+    bx.a0 = base_low + (bx.r0 * sw + bx.c0) * 4;
+    // lines per tile row: the most that any of the box's rows needs from its own line boundary on
+    const int nl_lo = (wb + 127) >> 7;
+    const bool more = lane < nrows && ((((bx.a0 + lane * sw4) & 127) + wb + 127) >> 7) > nl_lo;
+    const int nl = nl_lo + (__builtin_amdgcn_ballot_w64(more) != 0ull ? 1 : 0);
+    int pitch = nl * 128 + pad_b;
+    bool fits = nrows * pitch - pad_b <= TB;
+    if (!fits) {
+      pitch = nl * 128;
+      fits = nrows * pitch <= TB;
+    }
+    bx.pitch = pitch;
+    bx.on = (any && fits && nl <= 8) ? 1 : 0;
+    if (bx.on) {
+      for (int r = 0; r < nrows; ++r) {  // (wave-uniform)
+        const int ar = bx.a0 + r * sw4;
+        const int need = ((ar & 127) + wb + 127) >> 7;  // whole lines of this row
+        // (as a statement of its own: to the compiler a direct-to-LDS load is a pending write of ALL of LDS, and every
+        // record read and write of the patch loop would wait for the box and for the patch stores queued before it.
+        // The group loop waits for the tile itself, once, before its first read. M0 = the row's place in LDS.)
+        if (lane < need * 8) {
+          int keep;
+          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\t"
+                       "s_mov_b32 m0, %0"
+                       : "=&s"(keep)
+                       : "s"(tile_lds + r * pitch), "v"((ar & ~127) - base_low + lane * 16), "s"(rimg)
+                       : "memory");
+        }
+      }
+    }
+    return bx;
+  };
+
   const int nchunks = (npts + cpw - 1) / cpw;
   for (int ch = xcd_band_block(blockIdx.x, gridDim.x) * kWaves + wave; ch < nchunks; ch += gridDim.x * kWaves) {
     const int i0 = ch * cpw;
@@ -727,7 +808,14 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
     // so no two lanes of one load and no two loads of a group ask for the same line. Issued before the coefficients
     // are formed, waited for before the first window. Boxes of scattered points (more than 16 rows or kTouch lines
     // per row) are not touched.
-    constexpr int kTouch = ST ? ICTR_REF8_TOUCH : 0;
+    constexpr int kTouch = (ST && !STG) ? ICTR_REF8_TOUCH : 0;
+    RefBox box0;
+    if constexpr (STG) {  // the first group's box is on its way while the coefficients are formed
+      const int kBig = 1 << 28;
+      bx_rmin = row_min_dpp(vis ? tp.row0 : kBig), bx_rmax = -row_min_dpp(vis ? -tp.row0 : kBig);
+      bx_cmin = row_min_dpp(vis ? tp.col0 : kBig), bx_cmax = -row_min_dpp(vis ? -tp.col0 : kBig);
+      box0 = stage_box(0);
+    }
     float touch[kTouch > 0 ? kTouch : 1];
     if constexpr (kTouch > 0) {
       const int kBig = 1 << 28;
@@ -825,20 +913,58 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
 #pragma unroll
         for (int k = 0; k < kTouch; ++k) asm volatile("" ::"v"(touch[k]));
       }
-      for (int g0 = 0; g0 < cnt; g0 += 16) {  // (wave-uniform trip count: cnt is)
-        const unsigned vmask = (unsigned)(__builtin_amdgcn_ballot_w64(vis) >> g0) & 0xffffu;  // the group's visible points
+#ifndef ICTR_REF8_PREFETCH
+#define ICTR_REF8_PREFETCH 1  // (STG) 1: the next group's box is requested behind the current group's last window's reads,
+#endif                        // 0: behind its last store
+      RefBox cur = box0, nxt = box0;
 #ifndef ICTR_REF8_D
 #define ICTR_REF8_D 3  // windows in flight per wave (12 registers each)
 #endif
-        constexpr int kD = ICTR_REF8_D;
+      constexpr int kD = ICTR_REF8_D;
+      // one group of sixteen patches; tiled_c: its taps come out of the wave's tile. (Two bodies, not one with a branch
+      // per window: where the same registers could take a window from either source, every LDS read would first wait
+      // for a global load that might still be writing them -- on the in-order counter, for the patch stores.)
+      auto run_group = [&](int g0, auto tiled_c) {
+        constexpr bool kTiled = decltype(tiled_c)::value;
+        const unsigned vmask = (unsigned)(__builtin_amdgcn_ballot_w64(vis) >> g0) & 0xffffu;  // the group's visible points
         TapLoadsOTF W3[kD];
+        // (STG) the window's twelve texels out of the tile: image row Y of the box is tile row Y - r0, its texel X at
+        // ((a0 + (Y - r0) sw4) & 127) + 4 (X - c0) bytes from the tile row's start
+        auto taps_lds = [&](int j) {
+          TapLoadsOTF t;
+          const int trow = rlane(ty_v, g0 + j) + padl - 2 - cur.r0 + (lane >> 3);  // tile row of image row y - 2
+          const int xo = (rlane(tx_v, g0 + j) + padl - cur.c0 + (lane & 7)) * 4;   // bytes from column c0 to column x
+          int ar = cur.a0 + trow * sw4, lp = trow * cur.pitch + xo;
+          auto at = [&](int o) { return *reinterpret_cast<const float *>(tile + o); };
+          const int o_dn = lp + (ar & 127);
+          ar += sw4, lp += cur.pitch;
+          const int o_r1 = lp + (ar & 127);
+          ar += sw4, lp += cur.pitch;
+          const int o_r0 = lp + (ar & 127);
+          ar += sw4, lp += cur.pitch;
+          const int o_up = lp + (ar & 127);
+          t.r0 = (f32x4_a4){at(o_r0 - 8), at(o_r0 - 4), at(o_r0), at(o_r0 + 4)};
+          t.r1 = (f32x4_a4){at(o_r1 - 8), at(o_r1 - 4), at(o_r1), at(o_r1 + 4)};
+          t.up = (f32x2_a4){at(o_up - 4), at(o_up)};
+          t.dn = (f32x2_a4){at(o_dn - 4), at(o_dn)};
+          return t;
+        };
         auto issue_s = [&](int j) {
+          if (!((vmask >> j) & 1u)) return;
+          if constexpr (kTiled) {
+            W3[j % kD] = taps_lds(j);
+            return;
+          }
 #if defined(ICTR_REF8_ABL) && (ICTR_REF8_ABL & 2)  // measurement build: every window = the plane's first (L1 hits)
-          if ((vmask >> j) & 1u) W3[j % kD] = taps_issue_otf(pref + 2 * sw + 2 + (rlane(base_v, g0 + j) & 7), loff, sw);
+          W3[j % kD] = taps_issue_otf(pref + 2 * sw + 2 + (rlane(base_v, g0 + j) & 7), loff, sw);
 #else
-          if ((vmask >> j) & 1u) W3[j % kD] = taps_issue_otf(pref + rlane(base_v, g0 + j), loff, sw);
+          W3[j % kD] = taps_issue_otf(pref + rlane(base_v, g0 + j), loff, sw);
 #endif
         };
+        if constexpr (kTiled) {  // the tile is written by loads: their counter, then the reads
+          __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+          asm volatile("" ::: "memory");
+        }
         res_static_for<0, kD>([&](auto jc) { issue_s(decltype(jc)::value); });
         TrAcc<16> accS, accX;
         tr_for_each_patch<16, 0>([&](auto jc) {
@@ -859,6 +985,12 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
 #endif
           }
           if constexpr (j + kD < 16) issue_s(j + kD);
+          if constexpr (STG && ICTR_REF8_PREFETCH != 0 && j + kD == 15) {
+            if (g0 + 16 < cnt) {  // every read of the tile has been issued: once they are back it is the next group's
+              if constexpr (kTiled) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+              nxt = stage_box(g0 + 16);
+            }
+          }
           accS.template push<j>(gx * gx, gy * gy, lane);
           accX.template push<j>(gx * gy, 0.0f, lane);
         });
@@ -870,6 +1002,20 @@ __global__ __launch_bounds__(kBlock) void k_ref8(EngineDev e, LevelCam lc, int l
         sxx_v = mine ? sxx : sxx_v;
         sxy_v = mine ? sxy : sxy_v;
         syy_v = mine ? syy : syy_v;
+      };
+      for (int g0 = 0; g0 < cnt; g0 += 16) {  // (wave-uniform trip count: cnt is)
+        if (STG && cur.on)  // wave-uniform
+          run_group(g0, std::integral_constant<bool, STG>{});
+        else
+          run_group(g0, std::false_type{});
+        if constexpr (STG) {
+          static_assert(kD < 16, "the prefetch sits behind window 15's reads");
+          if (ICTR_REF8_PREFETCH == 0 && g0 + 16 < cnt) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            nxt = stage_box(g0 + 16);
+          }
+          cur = nxt;
+        }
       }
     } else {
     RefLoads<kU> A, B;
@@ -1554,9 +1700,32 @@ void launch_ref_level(const EngineDev &e, const LevelCam &lc, const LevelLaunch 
     // nothing), one otherwise
     if (otf && e.dopatchnorm)
       hipLaunchKernelGGL((k_ref8<true, 1, false, true>), g8, blk, 0, s, e, lc, level, cpw);
-    else if (otf && cpw % 16 == 0 && !(variant & ICTR_VARIANT_DYNAMIC_LOOP))  // (the dynamic patch loop: cross-check)
-      hipLaunchKernelGGL((k_ref8<false, 2, false, true, true>), g8, blk, 0, s, e, lc, level, cpw);
-    else if (otf)
+    else if (otf && cpw % 16 == 0 && !(variant & ICTR_VARIANT_DYNAMIC_LOOP)) {  // (the dynamic patch loop: cross-check)
+      // the static form, per level with the reference windows staged through a per-wave LDS tile of this many bytes or
+      // (0, and always with ICTR_REF8_DIRECT_TAPS) with the direct taps and their line touches. 32 distinct dense
+      // 1080p pairs, us per level 0 / 1 / 2 (profiles/r04_notes.md): direct taps 355 / 275 / 232; 9216 bytes (12 rows x
+      // 6 lines, the box of sixteen neighbours of a dense 8-px grid: the most that leaves three workgroups per CU)
+      // 260 / 243 / 218; 6016 bytes (four workgroups per CU; the level-0 box does not fit) 448 / 239 / 204; 14592
+      // bytes (two) 317 / 298 / 273.
+#ifndef ICTR_REF8_TILE0
+#define ICTR_REF8_TILE0 9216  // level 0
+#endif
+#ifndef ICTR_REF8_TILE1
+#define ICTR_REF8_TILE1 9216  // level 1
+#endif
+#ifndef ICTR_REF8_TILE2
+#define ICTR_REF8_TILE2 6016  // levels 2 and up (227 / 222 / 221 with the direct taps -> 205 / 195 / 196)
+#endif
+      const int tb = (variant & ICTR_REF8_DIRECT_TAPS) ? 0 : level == 0 ? ICTR_REF8_TILE0 : level == 1 ? ICTR_REF8_TILE1 : ICTR_REF8_TILE2;
+      if (tb != 0 && tb == ICTR_REF8_TILE0)
+        hipLaunchKernelGGL((k_ref8<false, 2, false, true, true, ICTR_REF8_TILE0>), g8, blk, 0, s, e, lc, level, cpw);
+      else if (tb != 0 && tb == ICTR_REF8_TILE1)
+        hipLaunchKernelGGL((k_ref8<false, 2, false, true, true, ICTR_REF8_TILE1>), g8, blk, 0, s, e, lc, level, cpw);
+      else if (tb != 0)
+        hipLaunchKernelGGL((k_ref8<false, 2, false, true, true, ICTR_REF8_TILE2>), g8, blk, 0, s, e, lc, level, cpw);
+      else
+        hipLaunchKernelGGL((k_ref8<false, 2, false, true, true>), g8, blk, 0, s, e, lc, level, cpw);
+    } else if (otf)
       hipLaunchKernelGGL((k_ref8<false, 2, false, true>), g8, blk, 0, s, e, lc, level, cpw);
     else if (e.dopatchnorm)
       hipLaunchKernelGGL((k_ref8<true, 1, true>), g8, blk, 0, s, e, lc, level, cpw);
