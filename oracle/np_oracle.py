@@ -5,6 +5,8 @@ ictr_oracle.c's structure: vectorised over points and patch pixels, no materiali
 cross-check the C oracle: element-wise quantities (projections, patches, coefficients) must agree bit for
 bit, sums to float tolerance. Restates visibility (points outside the reference or the new view), patch
 normalisation and the loop rule for a FIRST frame pair; the stale-patch quirk across frame pairs stays with the C oracle.
+track is made of new_state, level_setup and iteration, which tests/iter_judge.py calls on their own to judge a traced
+run at its own poses.
 """
 from __future__ import annotations
 
@@ -109,6 +111,55 @@ def _patchnorm(pat):
     return pat - mean[:, None, None]
 
 
+def new_state(pts3d, G0, psz):
+    """What Set3Dpoints and SetPose leave: the points (f32), the points rotated by G0, zeroed T/Gx/Gy patches and
+    coefficient lines. level_setup updates the buffers in place."""
+    X, Y, Z = (np.asarray(pts3d[k]).astype(f32) for k in range(3))
+    K = len(X)
+    _, _, Xc, Yc, Zc = project(G0, X, Y, Z, f32(1), f32(1), f32(0), f32(0))
+    T, Gx, Gy = (np.zeros((K, psz, psz), f32) for _ in range(3))
+    return dict(X=X, Y=Y, Z=Z, Xc=Xc, Yc=Yc, Zc=Zc, T=T, Gx=Gx, Gy=Gy, cx=np.zeros((K, 6), f32), cy=np.zeros((K, 6), f32))
+
+
+def level_setup(st, G0, sl, pyr_ref, cam, psz, *, dopatchnorm=False, clean_invisible=False):
+    """The setup of level sl (odometer.cpp:263-335) on the buffers of `st`: fresh T/Gx/Gy and coefficient lines for the
+    points in the reference view, the sd planes of all points. Returns dict(fx, fy, cx, cy, swo, sho: the level's camera;
+    mx, my, vis_ref; sd (K,6,P,P) f32)."""
+    T, Gx, Gy, cxk, cyk = st["T"], st["Gx"], st["Gy"], st["cx"], st["cy"]
+    fx, fy, cx_, cy_ = (f32(cam(k, sl)) for k in range(4))
+    swo, sho = f32(cam(4, sl)), f32(cam(5, sl))
+    mx, my, _, _, _ = project(G0, st["X"], st["Y"], st["Z"], fx, fy, cx_, cy_)
+    vr = in_view(mx, my, swo, sho)
+    t_new = patches(pyr_ref.img[sl], mx[vr], my[vr], psz)
+    T[vr] = _patchnorm(t_new) if dopatchnorm else t_new
+    Gx[vr] = patches(pyr_ref.dx[sl], mx[vr], my[vr], psz)
+    Gy[vr] = patches(pyr_ref.dy[sl], mx[vr], my[vr], psz)
+    cxk[vr], cyk[vr] = sd_coefs(st["Xc"][vr], st["Yc"][vr], st["Zc"][vr], fx, fy)
+    if clean_invisible:
+        Gx[~vr] = 0
+        Gy[~vr] = 0
+    sd = Gx[:, None] * cxk[:, :, None, None] + Gy[:, None] * cyk[:, :, None, None]  # (K,6,P,P)
+    sd[:, 0] = Gx * cxk[:, 0, None, None]
+    sd[:, 1] = Gy * cyk[:, 1, None, None]
+    return dict(fx=fx, fy=fy, cx=cx_, cy=cy_, swo=swo, sho=sho, mx=mx, my=my, vis_ref=vr, sd=sd)
+
+
+def iteration(st, lev, G, sl, pyr_new, psz, *, dopatchnorm=False, huber_k=0.0):
+    """One iteration's per-pixel part at the pose G (odometer.cpp:360-404): the points in the new view and their
+    residuals r = T - I, weighted where huber_k > 0. Returns dict(nx, ny, vis_new, r (points in view, P, P), over)."""
+    nx, ny, _, _, _ = project(G, st["X"], st["Y"], st["Z"], lev["fx"], lev["fy"], lev["cx"], lev["cy"])
+    vn = in_view(nx, ny, lev["swo"], lev["sho"])
+    I = patches(pyr_new.img[sl], nx[vn], ny[vn], psz)
+    if dopatchnorm:
+        I = _patchnorm(I)
+    r = st["T"][vn] - I
+    over = float(np.mean(np.abs(r) > f32(huber_k))) if huber_k > 0 and r.size else 0.0
+    if huber_k > 0:
+        ar = np.abs(r)
+        r = np.where(ar > f32(huber_k), r * (f32(huber_k) / np.where(ar > 0, ar, f32(1))), r).astype(f32)
+    return dict(nx=nx, ny=ny, vis_new=vn, r=r, over=over)
+
+
 def track(pts3d, p_in, pyr_ref, pyr_new, cam, lv_f, lv_l, psz, maxiter, solve, compose=None, huber_k=0.0, *,
           clean_invisible=False, dopatchnorm=False, normdp_ratio=None, exp=None, detail=None):
     """No-normalisation TrackPose (odometer.cpp:257-426) of a FIRST frame pair after Set3Dpoints.
@@ -128,33 +179,17 @@ def track(pts3d, p_in, pyr_ref, pyr_new, cam, lv_f, lv_l, psz, maxiter, solve, c
     clean_invisible zeroes Gx, Gy of the points outside the reference view at a level, so that they add nothing to H
     or b there."""
     exp = exp_se3 if exp is None else exp
-    X, Y, Z = (pts3d[k].astype(f32) for k in range(3))
-    K = len(X)
     p = np.asarray(p_in, np.float64).astype(f32)
     G0 = np.asarray(exp(p), f32)
     trace = []
-    _, _, Xc, Yc, Zc = project(G0, X, Y, Z, f32(1), f32(1), f32(0), f32(0))
-    T, Gx, Gy = (np.zeros((K, psz, psz), f32) for _ in range(3))
-    cxk, cyk = np.zeros((K, 6), f32), np.zeros((K, 6), f32)
+    st = new_state(pts3d, G0, psz)
+    K = len(st["X"])
     for sl in range(lv_f, lv_l - 1, -1):
-        fx, fy, cx_, cy_ = (f32(cam(k, sl)) for k in range(4))
-        swo, sho = f32(cam(4, sl)), f32(cam(5, sl))
-        mx, my, _, _, _ = project(G0, X, Y, Z, fx, fy, cx_, cy_)
-        vr = in_view(mx, my, swo, sho)
-        t_new = patches(pyr_ref.img[sl], mx[vr], my[vr], psz)
-        T[vr] = _patchnorm(t_new) if dopatchnorm else t_new
-        Gx[vr] = patches(pyr_ref.dx[sl], mx[vr], my[vr], psz)
-        Gy[vr] = patches(pyr_ref.dy[sl], mx[vr], my[vr], psz)
-        cxk[vr], cyk[vr] = sd_coefs(Xc[vr], Yc[vr], Zc[vr], fx, fy)
-        if clean_invisible:
-            Gx[~vr] = 0
-            Gy[~vr] = 0
+        lev = level_setup(st, G0, sl, pyr_ref, cam, psz, dopatchnorm=dopatchnorm, clean_invisible=clean_invisible)
+        sd = lev["sd"]
         if detail is not None:
-            detail[sl] = dict(vis_ref=vr.copy(), mx=mx, my=my, T=T.copy(), Gx=Gx.copy(), Gy=Gy.copy(), cx=cxk.copy(),
-                              cy=cyk.copy())
-        sd = Gx[:, None] * cxk[:, :, None, None] + Gy[:, None] * cyk[:, :, None, None]  # (K,6,P,P)
-        sd[:, 0] = Gx * cxk[:, 0, None, None]
-        sd[:, 1] = Gy * cyk[:, 1, None, None]
+            detail[sl] = dict(vis_ref=lev["vis_ref"].copy(), mx=lev["mx"], my=lev["my"], T=st["T"].copy(),
+                              Gx=st["Gx"].copy(), Gy=st["Gy"].copy(), cx=st["cx"].copy(), cy=st["cy"].copy())
         sdf = sd.reshape(K, 6, -1).astype(np.float64)
         H = np.einsum("kip,kjp->ij", sdf, sdf).astype(f32)
         it, nd, nd0 = 0, f32(1e-10), f32(1e-10)
@@ -163,21 +198,12 @@ def track(pts3d, p_in, pyr_ref, pyr_new, cam, lv_f, lv_l, psz, maxiter, solve, c
                 with np.errstate(all="ignore"):
                     if not f32(nd / nd0) > f32(normdp_ratio):
                         break
-            G = np.asarray(exp(p), f32)
-            nx, ny, _, _, _ = project(G, X, Y, Z, fx, fy, cx_, cy_)
-            vn = in_view(nx, ny, swo, sho)
-            I = patches(pyr_new.img[sl], nx[vn], ny[vn], psz)
-            if dopatchnorm:
-                I = _patchnorm(I)
-            r = T[vn] - I
-            over = float(np.mean(np.abs(r) > f32(huber_k))) if huber_k > 0 and r.size else 0.0
-            if huber_k > 0:
-                ar = np.abs(r)
-                r = np.where(ar > f32(huber_k), r * (f32(huber_k) / np.where(ar > 0, ar, f32(1))), r).astype(f32)
+            cur = iteration(st, lev, np.asarray(exp(p), f32), sl, pyr_new, psz, dopatchnorm=dopatchnorm, huber_k=huber_k)
+            vn, r = cur["vis_new"], cur["r"]
             b = (sd[vn] * r[:, None]).reshape(int(vn.sum()), 6, -1).astype(np.float64).sum((0, 2)).astype(f32)
             dp = solve(H, b)
             p = (p + dp) if compose is None else np.asarray(compose(p, dp), f32)
-            trace.append(dict(level=sl, iter=it, H=H, b=b, dp=dp, p=p.copy(), vis_new=vn, over=over))
+            trace.append(dict(level=sl, iter=it, H=H, b=b, dp=dp, p=p.copy(), vis_new=vn, over=cur["over"]))
             nd = normdp32(dp)
             if it == 0:
                 nd0 = nd

@@ -19,7 +19,9 @@ kernels, see test_get_patch_bit_exact_incl_borders). With coordinates ~300 it fi
 coordinate and iteration; which iteration hits it depends on the last ulp of the pose, so two correct
 implementations can take visibly different steps at one iteration (observed: b jumps by 64*sd*gradient ~ 7e5
 from a 6e-8 pose difference) and then re-converge. Below 256 px that form of the quirk cannot fire and trajectories are
-comparable step by step; above, only first-iteration sums and final poses are.
+comparable step by step; above, only first-iteration sums and final poses are -- between two runs, that is: every
+iteration's H and b of ONE run, at its own traced pose, is held to a float64 judge at any frame size in
+tests/test_gpu_iter_sums.py.
 A second, rarer form exists at every size: the ONE float32 value just below an integer n (x = n - 1 ulp, ulp < 1e-5)
 gives ceil(x + .00001f) = n + 1 with floor(x) = n - 1, i.e. weight ~1 on the tap one pixel to the right. It fires with
 probability ~1 ulp per coordinate and iteration (~1e-5 around x = 100); in the middle of a trajectory the next
