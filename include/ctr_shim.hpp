@@ -200,6 +200,33 @@ class RansacClass {
   int64_t n_, smax_;
 };
 
+// Static / moving split of a track window (misc_src/run_test_OF_track.py:309-343, ictr_fsplit_* in include/ictr.h): RANSAC
+// over 8-point fundamental matrices of several view pairs of the same points, one read-back at the end.
+class StaticSplitClass {
+ public:
+  StaticSplitClass(int64_t n, int64_t npairs) : h_(nullptr), n_(n), npairs_(npairs) {
+    check(ictr_fsplit_create(&h_, n, npairs), "StaticSplitClass");
+  }
+  ~StaticSplitClass() { ictr_fsplit_destroy(h_); }
+  StaticSplitClass(const StaticSplitClass &) = delete;
+  StaticSplitClass &operator=(const StaticSplitClass &) = delete;
+  void SetPairs(const double *xy /* [npairs][4][n]: xa, ya, xb, yb */) { check(ictr_fsplit_set_pairs(h_, xy), "SetPairs"); }
+  void Run(int64_t ntrials, double thresh, uint64_t seed = 0, void *hip_stream = nullptr) {
+    check(ictr_fsplit_run(h_, ntrials, thresh, seed, hip_stream), "Run");
+  }
+  // draws [8], F [npairs][9], inl_words [Words()], dd [n]; any may be NULL
+  void Wait(int64_t *best_trial, int64_t *best_count, int32_t *draws, double *F, uint64_t *inl_words, double *dd) {
+    check(ictr_fsplit_wait(h_, best_trial, best_count, draws, F, inl_words, dd), "Wait");
+  }
+  int64_t Words() const { return (n_ + 63) / 64; }
+  int64_t Points() const { return n_; }
+  int64_t Pairs() const { return npairs_; }
+
+ private:
+  ictr_fsplit *h_;
+  int64_t n_, npairs_;
+};
+
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one
 // read-back at the end. Mode: ICTR_TRIANG_DLT / _GN / _LM / _DEPTH.
 class TriangClass {

@@ -511,6 +511,46 @@ int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const double *cc,
                              uint64_t seed, int64_t first_trial, int64_t count, int32_t *status, int32_t *draws,
                              double *hyp, uint32_t *cnt, uint64_t *words);
 
+/* ------------------------------------------------------------------ static split (misc_src/run_test_OF_track.py:309-343)
+ * "Divide points in static and dynamic using the fundamental matrix": RANSAC over 8-point fundamental matrices of P view
+ * pairs of the same N points (DESIGN.md §4 "Static split"):
+ *   - trial t (0-based) draws 8 distinct point indices from the counter-based stream of the pose sampling above
+ *     (u_k = mix(mix(seed) ^ ((t << 32) | k)), index ((u_k >> 32) N) >> 32, repeats skipped, at most 1024 draws); the
+ *     same 8 serve every pair;
+ *   - per (trial, pair) the fundamental matrix F, xb^T F xa = 0, of the 8 correspondences: Hartley normalisation, null
+ *     vector of the 8x9 design matrix by Gaussian elimination with full pivoting, rank 2 by a one-sided Jacobi SVD,
+ *     denormalisation, unit Frobenius norm; all f64 in a fixed order. A fit fails (F = NaN) when a mean distance is 0, a
+ *     pivot is exactly 0 or an entry of F is not finite; a trial with a failed fit has no inliers;
+ *   - per point and pair the distance of xb to the line F xa (func_F_transfer_points), per point the maximum over the
+ *     pairs (a NaN stays); inlier iff that maximum < thresh;
+ *   - the trial with the most inliers wins, the lowest trial on ties; no inlier anywhere is a normal result
+ *     (best_count 0, best_trial the lowest trial).
+ * Inputs N: 8 .. 2^22, npairs: 1 .. 64, ntrials: 1 .. 2^20. Coordinates that are not finite are admitted: such a point
+ * is never an inlier, and a trial that draws it fails. */
+typedef struct ictr_fsplit ictr_fsplit;
+int ictr_fsplit_create(ictr_fsplit **out, int64_t n, int64_t npairs);
+void ictr_fsplit_destroy(ictr_fsplit *r);
+/* xy: f64 [npairs][4][N], per pair the rows xa, ya, xb, yb; refused (ICTR_ERR_STATE) while a run is in flight */
+int ictr_fsplit_set_pairs(ictr_fsplit *r, const double *xy);
+/* enqueues the trials on hip_stream (NULL: the null stream) and returns; thresh must not be NaN */
+int ictr_fsplit_run(ictr_fsplit *r, int64_t ntrials, double thresh, uint64_t seed, void *hip_stream);
+/* waits for the last run; any output may be NULL. draws[8]: the winner's point indices (draw order, -1 = not drawn),
+ * F [npairs][9] row-major (nine NaN where a fit failed), inl_words [ceil(N / 64)] (bit j % 64 of word j / 64 = point
+ * j), dd [N]: every point's largest distance under the winner. */
+int ictr_fsplit_wait(ictr_fsplit *r, int64_t *best_trial, int64_t *best_count, int32_t *draws, double *F,
+                     uint64_t *inl_words, double *dd);
+/* on: the next runs record device time stamps between their stages; get: ms[4] of the last waited run spent in
+ * k_fsplit_fit, k_fsplit_score, k_fsplit_select (summed over the chunks) and k_fsplit_mask */
+int ictr_fsplit_set_timing(ictr_fsplit *r, int on);
+int ictr_fsplit_get_kernel_times(const ictr_fsplit *r, float *ms);
+/* inspection: k_fsplit_fit and k_fsplit_score<tile> alone over trials first_trial .. first_trial + count - 1 (within
+ * 0 .. 2^20), through the launch helper of the run, in the object's own chunks (ICTR_FSPLIT_CHUNK, default 4096
+ * trials) and tile (ICTR_FSPLIT_TILE = 16 / 32 / 64, default 32), on the null stream. Per trial (host arrays):
+ * status[count] (1 = every pair's fit succeeded), draws[count][8], F[count][npairs][9], cnt[count] inliers (0 for a
+ * trial with status 0). */
+int ictr_debug_fsplit_trials(ictr_fsplit *r, double thresh, uint64_t seed, int64_t first_trial, int64_t count,
+                             int32_t *status, int32_t *draws, double *F, uint32_t *cnt);
+
 /* ------------------------------------------------------------------ multi-view point triangulation (misc_src/triang.c)
  * A track set (10^4 .. 10^5 points, 2 .. 30 views each) triangulated in one launch, one lane per point, with the
  * arithmetic of the reference routine of each mode: every product and sum in f32, in its order and grouping, so the

@@ -13,6 +13,8 @@ from .tracker import (CamClass, OdometerClass, PoseClass, Pyramid, TrackBatch, d
                       util_constructpyramide, util_getPatch, util_getPatch_grad, util_SE3_coeff_to_group,
                       util_SE3_group_to_coeff)
 from .ransac import fit_cameras_odom, sample_poses, sample_poses_host  # noqa: F401
+from .fsplit import (StaticSplitter, epiline_dist, fit_f8, pairs_from_stereo_tracks, pairs_from_tracks, split_static,  # noqa: F401
+                     split_static_host)
 from .triang import Triangulator, cameras_from_poses, rays_from_first_view, tracks_from_oftrack, triangulate_tracks  # noqa: F401
 from .sequence import SequenceTracker, select_points, track_sequence, track_sequence_host_loop  # noqa: F401
 

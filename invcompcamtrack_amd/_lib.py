@@ -219,6 +219,16 @@ SIGNATURES = {
     "ictr_debug_ransac_trials": (C.c_int, [VP, DP, DP, C.c_double, C.c_double, C.c_uint64, I64, I64,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), DP, C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint64)]),
+    "ictr_fsplit_create": (C.c_int, [C.POINTER(VP), I64, I64]),
+    "ictr_fsplit_destroy": (None, [VP]),
+    "ictr_fsplit_set_pairs": (C.c_int, [VP, DP]),
+    "ictr_fsplit_run": (C.c_int, [VP, I64, C.c_double, C.c_uint64, VP]),
+    "ictr_fsplit_wait": (C.c_int, [VP, C.POINTER(I64), C.POINTER(I64), C.POINTER(C.c_int32), DP,
+                                   C.POINTER(C.c_uint64), DP]),
+    "ictr_fsplit_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_fsplit_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_debug_fsplit_trials": (C.c_int, [VP, C.c_double, C.c_uint64, I64, I64, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), DP, C.POINTER(C.c_uint32)]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

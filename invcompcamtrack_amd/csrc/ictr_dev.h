@@ -166,6 +166,34 @@ struct RansacArgs {
   int *o_cntf;            // [n] inl_cnt without the entries <= 4
 };
 
+// static / moving split of a track window by fundamental-matrix RANSAC (ictr_fsplit.hip)
+constexpr int kFsFitBlock = 64;     // one lane per (trial, pair)
+constexpr int kFsScoreBlock = 256;  // four waves, one 64-point block each
+constexpr int kFsSelBlock = 1024;   // the one-workgroup select
+constexpr int kFsMaxDraws = 1024;   // draws per trial before it counts as failed
+constexpr int kFsTileMats = 320;    // matrices of a score workgroup's LDS tile (23040 B): 320 / T pairs of T trials
+constexpr int kFsMaxPairs = 64;
+struct FsplitState {
+  long long best_trial, best_count;
+  int draws[8];
+};
+struct FsplitArgs {
+  const double *xy;     // [P][4][n]: xa, ya, xb, yb per pair (f64)
+  int n, nwords, np;    // points, 64-bit inlier words, pairs
+  double thr;
+  unsigned long long seedmix;
+  long long base;       // first trial of this chunk
+  int k;                // trials in this chunk
+  double *F;            // [K][np][9]; nine NaN where the fit failed
+  int *draws;           // [K][8], -1 = not drawn
+  int *pst;             // [K][np] 1 = the fit of this pair succeeded
+  unsigned *cnt;        // [K] inliers
+  FsplitState *st;      // the best trial so far ...
+  double *o_F;          // ... its matrices [np][9]
+  unsigned long long *o_words;  // [nwords] its inlier bits
+  double *o_dd;         // [n] its distances
+};
+
 // per-patch translation IC-LK (ictr_patchflow.hip)
 struct PFLevel {
   const float *a, *ax, *ay, *b;  // frame A image + gradients, frame B image (padded planes)

@@ -146,7 +146,7 @@ hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int lev
 hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *patch_of_lane, int *kind_of_lane, int np,
                                          hipStream_t s);
 
-// ---------------------------------------------------------------- ictr_sequence.hip, ictr_ransac.hip, ictr_patchflow.hip
+// ---------------------------------------------------------------- ictr_sequence.hip, ictr_ransac.hip, ictr_fsplit.hip, ictr_patchflow.hip
 // the between-pairs step (three launches), or with a.tail the last frame's bookkeeping (one)
 void launch_seq_select(const SeqArgs &a, hipStream_t s);
 // one chunk of a.k trials: hypotheses and scoring (tile = 16 / 32 / 64 hypotheses per workgroup) ...
@@ -155,6 +155,12 @@ void launch_ransac_hyp_score(const RansacArgs &a, int tile, hipStream_t s);
 void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s);
 // after the last chunk: inl_cnt and the post-filter
 void launch_ransac_finish(const RansacArgs &a, hipStream_t s);
+// one chunk of a.k trials of the static split: fits and scoring (tile = 16 / 32 / 64 trials per workgroup) ...
+void launch_fsplit_fit_score(const FsplitArgs &a, int tile, hipStream_t s, hipEvent_t after_fit = nullptr);
+// ... the chunk's best trial against the best so far ...
+void launch_fsplit_select(const FsplitArgs &a, hipStream_t s);
+// ... and after the last chunk the distances and inlier bits of the winner
+void launch_fsplit_mask(const FsplitArgs &a, hipStream_t s);
 // per-patch translation IC-LK, all levels, a.K points
 void launch_patchflow(const PFArgs &a, hipStream_t s);
 // NPL * 10 + WPP of this thread's last launch_patchflow (11, 41, 161 or 82), 0 before the first

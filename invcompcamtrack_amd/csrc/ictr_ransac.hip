@@ -24,17 +24,11 @@
 #include <memory>
 
 #include "ictr_dev.h"
+#include "ictr_devfn.h"
 #include "ictr_launch.h"
 #include "se3_math.h"
 
 namespace ictr {
-
-__device__ __forceinline__ unsigned long long ran_mix(unsigned long long z) {  // splitmix64
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ double triple(const double *a, const double *b, const double *c) {
   const double c0 = a[1] * b[2] - a[2] * b[1];
