@@ -134,7 +134,6 @@ struct SeqArgs {
 constexpr int kRanHypBlock = 64;     // one lane per trial
 constexpr int kRanScoreBlock = 256;  // four waves, one 64-match block each
 constexpr int kRanSelBlock = 1024;   // the one-workgroup select / finish
-constexpr int kRanMaxDraws = 1024;   // draws per trial before it counts as failed (N >= 4: never reached in practice)
 struct RansacState {
   long long held;         // accepted samples so far (the script's successes, trial order)
   long long trials_used;  // trials the script would have consumed
@@ -170,7 +169,6 @@ struct RansacArgs {
 constexpr int kFsFitBlock = 64;     // one lane per (trial, pair)
 constexpr int kFsScoreBlock = 256;  // four waves, one 64-point block each
 constexpr int kFsSelBlock = 1024;   // the one-workgroup select
-constexpr int kFsMaxDraws = 1024;   // draws per trial before it counts as failed
 constexpr int kFsTileMats = 320;    // matrices of a score workgroup's LDS tile (23040 B): 320 / T pairs of T trials
 constexpr int kFsMaxPairs = 64;
 struct FsplitState {

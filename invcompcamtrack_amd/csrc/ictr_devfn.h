@@ -1,5 +1,5 @@
 // ictr_devfn.h -- device helpers shared by the kernel translation units (ictr_kernels.hip, ictr_track1.hip,
-// ictr_resident.hip; ran_mix: ictr_ransac.hip, ictr_fsplit.hip): bilinear tap selection (utilities.cpp:66-107), visibility (odometer.cpp:273-276), steepest-descent
+// ictr_resident.hip): bilinear tap selection (utilities.cpp:66-107), visibility (odometer.cpp:273-276), steepest-descent
 // coefficients (odometer.cpp:313-326), the per-point and per-patch steps that must give the same bits in every launch
 // form (projection, iteration point, setup point, any-size patch bodies), the per-level LU factorisation and the
 // per-iteration solve + pose update + loop condition (odometer.cpp:341-346, 407-418, 509-515; pose.cpp:116-129).
@@ -23,14 +23,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float group_sum(float v, int width) {
   for (int m = width >> 1; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
-}
-
-// splitmix64: the counter-based draw stream of the RANSAC stages (ictr_ransac.hip, ictr_fsplit.hip)
-__device__ __forceinline__ unsigned long long ran_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 struct Taps {

@@ -27,36 +27,18 @@
 
 #include "ictr_dev.h"
 #include "ictr_devfn.h"
+#include "ictr_draw_hd.h"
 #include "ictr_fsplit_hd.h"
 #include "ictr_launch.h"
 
 namespace ictr {
-
-// the 8 distinct indices of trial g in draw order (-1: not drawn); returns how many were drawn
-__device__ __forceinline__ int fs_draw(unsigned long long seedmix, long long g, int n, int *idx) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) idx[q] = -1;
-  int nd = 0;
-  for (int k = 0; k < kFsMaxDraws && nd < 8; ++k) {
-    const unsigned long long u = ran_mix(seedmix ^ (((unsigned long long)g << 32) | (unsigned long long)k));
-    const int id = (int)(((u >> 32) * (unsigned long long)n) >> 32);
-    bool dup = false;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) dup = dup || idx[q] == id;
-    if (dup) continue;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) idx[q] = nd == q ? id : idx[q];
-    ++nd;
-  }
-  return nd;
-}
 
 __global__ void __launch_bounds__(kFsFitBlock) k_fsplit_fit(FsplitArgs a) {
   const long long g = (long long)blockIdx.x * kFsFitBlock + threadIdx.x;
   if (g >= (long long)a.k * a.np) return;
   const int i = (int)(g / a.np), p = (int)(g - (long long)i * a.np);
   int idx[8];
-  const int nd = fs_draw(a.seedmix, a.base + i, a.n, idx);
+  const int nd = ran_draw<8>(a.seedmix, a.base + i, a.n, idx);
   if (p == 0) {
     a.cnt[i] = 0u;
 #pragma unroll
@@ -203,7 +185,7 @@ void launch_fsplit_fit_score(const FsplitArgs &a, int tile, hipStream_t s, hipEv
   const long long fits = (long long)a.k * a.np;
   hipLaunchKernelGGL(k_fsplit_fit, dim3((unsigned)((fits + kFsFitBlock - 1) / kFsFitBlock)), dim3(kFsFitBlock), 0, s, a);
   if (after_fit) (void)hipEventRecord(after_fit, s);
-  const int segs = (a.nwords + kFsScoreBlock / 64 - 1) / (kFsScoreBlock / 64);
+  const int segs = ran_segs(a.nwords, kFsScoreBlock);
   if (tile == 16)
     hipLaunchKernelGGL(k_fsplit_score<16>, dim3((a.k + 15) / 16, segs), dim3(kFsScoreBlock), 0, s, a);
   else if (tile == 64)
@@ -217,7 +199,7 @@ void launch_fsplit_select(const FsplitArgs &a, hipStream_t s) {
 }
 
 void launch_fsplit_mask(const FsplitArgs &a, hipStream_t s) {
-  const int segs = (a.nwords + kFsScoreBlock / 64 - 1) / (kFsScoreBlock / 64);
+  const int segs = ran_segs(a.nwords, kFsScoreBlock);
   hipLaunchKernelGGL(k_fsplit_mask, dim3(segs), dim3(kFsScoreBlock), 0, s, a);
 }
 
@@ -229,39 +211,25 @@ using namespace ictr;
 struct ictr_fsplit {
   int n = 0, nwords = 0, np = 0;
   int chunk = 0, tile = 32;
-  hipStream_t stream = nullptr;
   DevBuf<double> d_xy, d_F;
   DevBuf<int> d_draws, d_pst;
   DevBuf<unsigned> d_cnt;
-  DevBuf<char> d_out;  // FsplitState | F [np][9] | words [nwords] | dd [n]
-  PinBuf<char> h_out;
-  size_t out_bytes = 0;
-  bool pairs_set = false, pending = false;
+  bool pairs_set = false;
   bool timing = false, timed = false;  // timed: the run in flight (or last waited) carries events
   std::vector<Event> tev;              // per chunk: before fit, after fit, after score, after select; then after mask
   float ms[4] = {0, 0, 0, 0};
-  Event done;
-  ~ictr_fsplit() {
-    if (pending) (void)hipEventSynchronize(done.get());
-  }
+  // (fs_layout) declared last, so destroyed first: a run in flight ends before a buffer or a timing event goes
+  Readback out;
 };
 
-struct FsLayout {
-  size_t F, words, dd, end;
+struct FsLayout {  // FsplitState | F [np][9] | words [nwords] | dd [n], each on a 16-byte boundary
+  Part F, words, dd, end;  // end: empty, at the block's size
 };
 static FsLayout fs_layout(const ictr_fsplit *r) {
-  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-  FsLayout L;
-  L.F = up(sizeof(FsplitState));
-  L.words = up(L.F + 72 * (size_t)r->np);
-  L.dd = up(L.words + 8 * (size_t)r->nwords);
-  L.end = up(L.dd + 8 * (size_t)r->n);
-  return L;
-}
-
-static int fs_refuse_pending(const ictr_fsplit *r, const char *what) {
-  if (r->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_fsplit_wait first", what);
-  return ICTR_OK;
+  Carve c;
+  c.take(sizeof(FsplitState), 16);  // at the front
+  return {c.take(72 * (size_t)r->np, 16), c.take(8 * (size_t)r->nwords, 16), c.take(8 * (size_t)r->n, 16),
+          c.take(0, 16)};  // braces: evaluated in this order
 }
 
 extern "C" int ictr_fsplit_create(ictr_fsplit **out, int64_t n, int64_t npairs) {
@@ -278,18 +246,14 @@ extern "C" int ictr_fsplit_create(ictr_fsplit **out, int64_t n, int64_t npairs) 
   // trials per chunk: the matrices of a chunk (K x P x 72 B) stay below 19 MB; ICTR_FSPLIT_CHUNK overrides
   const int chunk = env_int("ICTR_FSPLIT_CHUNK", 0);
   r->chunk = chunk > 0 ? std::min(chunk, 1 << 16) : 4096;
-  const int tile = env_int("ICTR_FSPLIT_TILE", 32);
-  r->tile = (tile == 16 || tile == 64) ? tile : 32;
+  r->tile = ran_tile_env("ICTR_FSPLIT_TILE");
   const size_t K = (size_t)r->chunk, P = (size_t)r->np;
-  r->out_bytes = fs_layout(r.get()).end;
   if (int rc = r->d_xy.alloc(sizeof(double) * 4 * P * (size_t)n, true)) return rc;
   if (int rc = r->d_F.alloc(sizeof(double) * 9 * K * P, true)) return rc;
   if (int rc = r->d_draws.alloc(sizeof(int) * 8 * K, true)) return rc;
   if (int rc = r->d_pst.alloc(sizeof(int) * K * P, true)) return rc;
   if (int rc = r->d_cnt.alloc(sizeof(unsigned) * K, true)) return rc;
-  if (int rc = r->d_out.alloc(r->out_bytes, true)) return rc;
-  if (int rc = r->h_out.alloc(r->out_bytes)) return rc;
-  if (int rc = r->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = r->out.reserve(fs_layout(r.get()).end.at, true)) return rc;
   *out = r.release();
   return ICTR_OK;
 }
@@ -298,7 +262,7 @@ extern "C" void ictr_fsplit_destroy(ictr_fsplit *r) { delete r; }
 
 extern "C" int ictr_fsplit_set_pairs(ictr_fsplit *r, const double *xy) {
   if (!r || !xy) return fail(ICTR_ERR_INVALID, "fsplit_set_pairs: NULL argument");
-  if (int rc = fs_refuse_pending(r, "fsplit_set_pairs")) return rc;
+  if (int rc = r->out.refuse("fsplit_set_pairs", "fsplit")) return rc;
   HIPCHK(hipMemcpy(r->d_xy.get(), xy, sizeof(double) * 4 * (size_t)r->np * (size_t)r->n, hipMemcpyHostToDevice));
   r->pairs_set = true;
   return ICTR_OK;
@@ -306,7 +270,7 @@ extern "C" int ictr_fsplit_set_pairs(ictr_fsplit *r, const double *xy) {
 
 extern "C" int ictr_fsplit_set_timing(ictr_fsplit *r, int on) {
   if (!r) return fail(ICTR_ERR_INVALID, "fsplit is NULL");
-  if (int rc = fs_refuse_pending(r, "fsplit_set_timing")) return rc;
+  if (int rc = r->out.refuse("fsplit_set_timing", "fsplit")) return rc;
   r->timing = on != 0;
   return ICTR_OK;
 }
@@ -321,24 +285,21 @@ static int fs_fill_args(const ictr_fsplit *r, const char *what, double thresh, u
   a.nwords = r->nwords;
   a.np = r->np;
   a.thr = thresh;
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull;  // splitmix64 (the device's ran_mix)
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  a.seedmix = z ^ (z >> 31);
+  a.seedmix = ran_seed(seed);
   a.F = r->d_F.get();
   a.draws = r->d_draws.get();
   a.pst = r->d_pst.get();
   a.cnt = r->d_cnt.get();
-  a.st = reinterpret_cast<FsplitState *>(r->d_out.get());
-  a.o_F = reinterpret_cast<double *>(r->d_out.get() + L.F);
-  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out.get() + L.words);
-  a.o_dd = reinterpret_cast<double *>(r->d_out.get() + L.dd);
+  a.st = reinterpret_cast<FsplitState *>(r->out.dev());
+  a.o_F = reinterpret_cast<double *>(r->out.dev() + L.F.at);
+  a.o_words = reinterpret_cast<unsigned long long *>(r->out.dev() + L.words.at);
+  a.o_dd = reinterpret_cast<double *>(r->out.dev() + L.dd.at);
   return ICTR_OK;
 }
 
 extern "C" int ictr_fsplit_run(ictr_fsplit *r, int64_t ntrials, double thresh, uint64_t seed, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "fsplit is NULL");
-  if (int rc = fs_refuse_pending(r, "fsplit_run")) return rc;
+  if (int rc = r->out.refuse("fsplit_run", "fsplit")) return rc;
   if (!r->pairs_set) return fail(ICTR_ERR_STATE, "fsplit_run: ictr_fsplit_set_pairs has not been called");
   if (ntrials < 1 || ntrials > ((int64_t)1 << 20))
     return fail(ICTR_ERR_INVALID, "fsplit_run: ntrials %lld (1 .. 2^20)", (long long)ntrials);
@@ -367,29 +328,25 @@ extern "C" int ictr_fsplit_run(ictr_fsplit *r, int64_t ntrials, double thresh, u
   launch_fsplit_mask(a, s);
   HIPCHK(hipGetLastError());
   if (r->timing) HIPCHK(hipEventRecord(tev.back().get(), s));
-  HIPCHK(hipMemcpyAsync(r->h_out.get(), r->d_out.get(), r->out_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(r->done.get(), s));
-  r->stream = s;
+  if (int rc = r->out.post(fs_layout(r).end.at, s)) return rc;
   r->tev = std::move(tev);
   r->timed = r->timing;
-  r->pending = true;
   return ICTR_OK;
 }
 
 extern "C" int ictr_fsplit_wait(ictr_fsplit *r, int64_t *best_trial, int64_t *best_count, int32_t *draws, double *F,
                                 uint64_t *inl_words, double *dd) {
   if (!r) return fail(ICTR_ERR_INVALID, "fsplit is NULL");
-  if (!r->pending) return fail(ICTR_ERR_STATE, "fsplit_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(r->done.get()));
-  r->pending = false;
+  if (!r->out.pending()) return fail(ICTR_ERR_STATE, "fsplit_wait: nothing has been run");
+  if (int rc = r->out.wait()) return rc;
   const FsLayout L = fs_layout(r);
-  const FsplitState &st = *reinterpret_cast<const FsplitState *>(r->h_out.get());
+  const FsplitState &st = *reinterpret_cast<const FsplitState *>(r->out.host());
   if (best_trial) *best_trial = st.best_trial;
   if (best_count) *best_count = st.best_count;
   if (draws) memcpy(draws, st.draws, sizeof(st.draws));
-  if (F) memcpy(F, r->h_out.get() + L.F, 72 * (size_t)r->np);
-  if (inl_words) memcpy(inl_words, r->h_out.get() + L.words, 8 * (size_t)r->nwords);
-  if (dd) memcpy(dd, r->h_out.get() + L.dd, 8 * (size_t)r->n);
+  if (F) memcpy(F, r->out.host() + L.F.at, L.F.bytes);
+  if (inl_words) memcpy(inl_words, r->out.host() + L.words.at, L.words.bytes);
+  if (dd) memcpy(dd, r->out.host() + L.dd.at, L.dd.bytes);
   if (r->timed) {
     float ms[4] = {0, 0, 0, 0};
     const size_t nchunks = (r->tev.size() - 1) / 4;
@@ -408,7 +365,7 @@ extern "C" int ictr_fsplit_wait(ictr_fsplit *r, int64_t *best_trial, int64_t *be
 
 extern "C" int ictr_fsplit_get_kernel_times(const ictr_fsplit *r, float *ms) {
   if (!r || !ms) return fail(ICTR_ERR_INVALID, "fsplit_get_kernel_times: NULL argument");
-  if (r->pending || !r->timed) return fail(ICTR_ERR_STATE, "fsplit_get_kernel_times: no completed timed run");
+  if (r->out.pending() || !r->timed) return fail(ICTR_ERR_STATE, "fsplit_get_kernel_times: no completed timed run");
   memcpy(ms, r->ms, sizeof(r->ms));
   return ICTR_OK;
 }
@@ -418,7 +375,7 @@ extern "C" int ictr_fsplit_get_kernel_times(const ictr_fsplit *r, float *ms) {
 extern "C" int ictr_debug_fsplit_trials(ictr_fsplit *r, double thresh, uint64_t seed, int64_t first_trial, int64_t count,
                                         int32_t *status, int32_t *draws, double *F, uint32_t *cnt) {
   if (!r || !status || !draws || !F || !cnt) return fail(ICTR_ERR_INVALID, "debug_fsplit_trials: NULL argument");
-  if (int rc = fs_refuse_pending(r, "debug_fsplit_trials")) return rc;
+  if (int rc = r->out.refuse("debug_fsplit_trials", "fsplit")) return rc;
   if (!r->pairs_set) return fail(ICTR_ERR_STATE, "debug_fsplit_trials: ictr_fsplit_set_pairs has not been called");
   if (count < 1 || count > ((int64_t)1 << 20) || first_trial < 0 || first_trial > ((int64_t)1 << 20) - count)
     return fail(ICTR_ERR_INVALID, "debug_fsplit_trials: trials %lld + %lld (1 .. 2^20 trials below 2^20)",

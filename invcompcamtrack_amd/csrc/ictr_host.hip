@@ -1997,24 +1997,20 @@ struct ictr_sequence {
   DevBuf<float> d_frames_own;
   size_t own_bytes = 0;
   int64_t nframes = 0;
-  DevBuf<char> d_out;  // poses [N][6] f64 | hash [N-1] u64 | npts [N-1] i32 | iters [N-1] i32
-  PinBuf<char> h_out;
-  int64_t out_frames = 0;
-  int64_t run_frames = 0;  // frames of the last run (its results' layout in h_out)
-  bool points_set = false, pending = false, ran = false;
-  Event done;
-  ~ictr_sequence() {
-    if (pending) (void)hipEventSynchronize(done.get());
-  }
+  int64_t run_frames = 0;  // frames of the last run (its results' layout in the result block)
+  bool points_set = false;
+  // (seq_layout) declared last, so destroyed first: a run in flight ends before a buffer, a pyramid or the batch goes
+  Readback out;
 };
 
-static size_t seq_out_bytes(int64_t N) { return (size_t)N * 48 + (size_t)(N - 1) * 16; }
-
-// the inputs of a run stay fixed until its wait
-static int seq_refuse_pending(const ictr_sequence *s, const char *what) {
-  if (s->pending)
-    return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_sequence_wait first", what);
-  return ICTR_OK;
+struct SeqLayout {  // poses [N][6] f64 | hash [N-1] u64 | npts [N-1] i32 | iters [N-1] i32, packed
+  Part poses, hash, npts, iters, end;  // end: empty, at the block's size
+};
+static SeqLayout seq_layout(int64_t N) {
+  Carve c;
+  const size_t n = (size_t)N, p = (size_t)(N - 1);  // frames, pairs
+  return {c.take(sizeof(double) * 6 * n), c.take(sizeof(uint64_t) * p), c.take(sizeof(int32_t) * p),
+          c.take(sizeof(int32_t) * p), c.take(0)};  // braces: evaluated in this order
 }
 
 extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, const ictr_optparam *op, int64_t nworld,
@@ -2053,7 +2049,6 @@ extern "C" int ictr_sequence_create(ictr_sequence **out, const ictr_cam *cam, co
   if (int rc = s->d_sel.alloc(sizeof(int) * b->M, true)) return rc;
   if (int rc = s->d_ss.alloc(sizeof(SeqState), true)) return rc;
   if (int rc = s->d_tab.alloc(sizeof(PlaneSet) * 2 * L, true)) return rc;
-  if (int rc = s->done.create(hipEventDisableTiming)) return rc;
   for (int k = 0; k < 2; ++k) {
     ictr_pyramid *p = nullptr;
     if (int rc = pyramid_alloc(&p, cam->wh[0], cam->wh[1], op->lv_f, 1, cam->padding)) return rc;
@@ -2080,7 +2075,7 @@ extern "C" void ictr_sequence_destroy(ictr_sequence *s) { delete s; }
 
 extern "C" int ictr_sequence_set_points(ictr_sequence *s, const double *pt3d) {
   if (!s || !pt3d) return fail(ICTR_ERR_INVALID, "sequence_set_points: NULL argument");
-  if (int rc = seq_refuse_pending(s, "sequence_set_points")) return rc;
+  if (int rc = s->out.refuse("sequence_set_points", "sequence")) return rc;
   HIPCHK(hipMemcpy(s->d_world.get(), pt3d, sizeof(double) * 3 * s->nw, hipMemcpyHostToDevice));
   s->points_set = true;
   return ICTR_OK;
@@ -2094,7 +2089,7 @@ extern "C" int ictr_sequence_set_frames(ictr_sequence *s, const float *frames, i
   if (w != s->cam->wh[0] || h != s->cam->wh[1])
     return fail(ICTR_ERR_INVALID, "sequence_set_frames: frames are %dx%d, the camera's are %dx%d", w, h, s->cam->wh[0],
                 s->cam->wh[1]);
-  if (int rc = seq_refuse_pending(s, "sequence_set_frames")) return rc;
+  if (int rc = s->out.refuse("sequence_set_frames", "sequence")) return rc;
   const size_t bytes = sizeof(float) * (size_t)w * h * nframes;
   if (on_device) {
     s->frames = frames;
@@ -2107,21 +2102,15 @@ extern "C" int ictr_sequence_set_frames(ictr_sequence *s, const float *frames, i
     HIPCHK(hipMemcpy(s->d_frames_own.get(), frames, bytes, hipMemcpyHostToDevice));
     s->frames = s->d_frames_own.get();
   }
-  if (nframes > s->out_frames) {  // result buffers sized here, so that track_async allocates nothing
-    s->out_frames = 0;
-    s->d_out.reset();
-    s->h_out.reset();
-    if (int rc = s->d_out.alloc(seq_out_bytes(nframes))) return rc;
-    if (int rc = s->h_out.alloc(seq_out_bytes(nframes))) return rc;
-    s->out_frames = nframes;
-  }
+  // result buffers sized here, so that track_async allocates nothing
+  if (int rc = s->out.reserve(seq_layout(nframes).end.at, false)) return rc;
   s->nframes = nframes;
   return ICTR_OK;
 }
 
 extern "C" int ictr_sequence_set_stream(ictr_sequence *s, void *hip_stream) {
   if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
-  if (int rc = seq_refuse_pending(s, "sequence_set_stream")) return rc;
+  if (int rc = s->out.refuse("sequence_set_stream", "sequence")) return rc;
   s->stream = (hipStream_t)hip_stream;
   s->b->stream = s->stream;
   return ICTR_OK;
@@ -2140,7 +2129,7 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   if (!s || !p0) return fail(ICTR_ERR_INVALID, "sequence_track_async: NULL argument");
   if (!s->points_set) return fail(ICTR_ERR_STATE, "sequence_track_async: ictr_sequence_set_points has not been called");
   if (!s->frames || s->nframes < 2) return fail(ICTR_ERR_STATE, "sequence_track_async: no frames set");
-  if (s->pending) return fail(ICTR_ERR_STATE, "sequence_track_async: wait for the previous run first");
+  if (s->out.pending()) return fail(ICTR_ERR_STATE, "sequence_track_async: wait for the previous run first");
   ictr_batch *b = s->b.get();
   if (b->h_team_err && *(volatile int *)b->h_team_err.get()) {  // an earlier run timed out (reported by its wait)
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -2171,10 +2160,11 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   a.mask = s->d_mask.get();
   a.cnt = s->d_cnt.get();
   a.sel = s->d_sel.get();
-  a.poses = reinterpret_cast<double *>(s->d_out.get());
-  a.hash = reinterpret_cast<unsigned long long *>(s->d_out.get() + (size_t)N * 48);
-  a.npts_out = reinterpret_cast<int *>(s->d_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 8);
-  a.iters_out = a.npts_out + (N - 1);
+  const SeqLayout lay = seq_layout(N);
+  a.poses = reinterpret_cast<double *>(s->out.dev() + lay.poses.at);
+  a.hash = reinterpret_cast<unsigned long long *>(s->out.dev() + lay.hash.at);
+  a.npts_out = reinterpret_cast<int *>(s->out.dev() + lay.npts.at);
+  a.iters_out = reinterpret_cast<int *>(s->out.dev() + lay.iters.at);
   a.pt3d = b->d_pt3d.get();
   a.T = b->d_T.get();
   a.Gx = b->d_Gx.get();
@@ -2195,31 +2185,28 @@ extern "C" int ictr_sequence_track_async(ictr_sequence *s, const double *p0) {
   a.tail = 1;
   launch_seq_select(a, s->stream);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(s->h_out.get(), s->d_out.get(), seq_out_bytes(N), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipEventRecord(s->done.get(), s->stream));
-  s->pending = true;
-  s->ran = true;
+  if (int rc = s->out.post(lay.end.at, s->stream)) return rc;
   s->run_frames = N;
   return ICTR_OK;
 }
 
 extern "C" int ictr_sequence_wait(ictr_sequence *s, double *poses, int32_t *npts, int32_t *iters) {
   if (!s) return fail(ICTR_ERR_INVALID, "sequence is NULL");
-  if (!s->pending) return fail(ICTR_ERR_STATE, "sequence_wait: nothing has been tracked");
-  HIPCHK(hipEventSynchronize(s->done.get()));
-  s->pending = false;
+  if (!s->out.pending()) return fail(ICTR_ERR_STATE, "sequence_wait: nothing has been tracked");
+  if (int rc = s->out.wait()) return rc;
   if (int rc = team_error_check(s->b.get())) return rc;
-  const int64_t N = s->run_frames;
-  if (poses) memcpy(poses, s->h_out.get(), sizeof(double) * 6 * N);
-  if (npts) memcpy(npts, s->h_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 8, sizeof(int32_t) * (N - 1));
-  if (iters) memcpy(iters, s->h_out.get() + (size_t)N * 48 + (size_t)(N - 1) * 12, sizeof(int32_t) * (N - 1));
+  const SeqLayout L = seq_layout(s->run_frames);
+  if (poses) memcpy(poses, s->out.host() + L.poses.at, L.poses.bytes);
+  if (npts) memcpy(npts, s->out.host() + L.npts.at, L.npts.bytes);
+  if (iters) memcpy(iters, s->out.host() + L.iters.at, L.iters.bytes);
   return ICTR_OK;
 }
 
 extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out) {
   if (!s || !out) return fail(ICTR_ERR_INVALID, "sequence_selection_hashes: NULL argument");
-  if (s->pending || !s->ran) return fail(ICTR_ERR_STATE, "sequence_selection_hashes: no completed run");
-  memcpy(out, s->h_out.get() + (size_t)s->run_frames * 48, sizeof(uint64_t) * (s->run_frames - 1));
+  if (s->out.pending() || !s->out.ran()) return fail(ICTR_ERR_STATE, "sequence_selection_hashes: no completed run");
+  const SeqLayout L = seq_layout(s->run_frames);
+  memcpy(out, s->out.host() + L.hash.at, L.hash.bytes);
   return ICTR_OK;
 }
 

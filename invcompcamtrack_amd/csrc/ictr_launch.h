@@ -29,15 +29,18 @@ namespace ictr {
 
 // ---------------------------------------------------------------- errors, device, environment (ictr_host.hip)
 // records the message for ictr_last_error (per thread) and returns `code`
-int fail(int code, const char *fmt, ...);
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) return fail(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
+int fail(int code, const char *fmt, ...);  // and HIPCHK(expr), which returns through it: ictr_own.h
 int need_device();                          // ICTR_OK, or ICTR_ERR_NO_DEVICE with its message: there is no CPU fallback
 int env_int(const char *name, int dflt);    // integer value of an environment variable, dflt when unset
 int cu_count();                             // CUs of the calling thread's current device, queried once per device
+
+// the two RANSAC stages: trials per score workgroup from an environment variable, 16, 64 or (anything else) 32 ...
+inline int ran_tile_env(const char *name) {
+  const int tile = env_int(name, 32);
+  return (tile == 16 || tile == 64) ? tile : 32;
+}
+// ... and the workgroups of `block` threads that give each of nwords 64-item words one wave
+inline int ran_segs(int nwords, int block) { return (nwords + block / 64 - 1) / (block / 64); }
 
 // ---------------------------------------------------------------- argument bundles of the launchers (host side only)
 // launch geometry of one pyramid level's kernels

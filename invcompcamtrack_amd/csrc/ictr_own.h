@@ -1,4 +1,5 @@
-// ictr_own.h -- who releases what on the host side: move-only holders of device memory, pinned host memory and HIP events.
+// ictr_own.h -- who releases what on the host side: move-only holders of device memory, pinned host memory and HIP events,
+// and the result block with the run / wait state of an object that is run now and waited for later (Readback).
 // A holder owns; a raw pointer next to it borrows. An object that carves one block up itself (a pyramid's planes, the flow
 // grid's arena) holds that block with ONE holder. Host only; included through ictr_launch.h.
 #pragma once
@@ -13,6 +14,11 @@
 namespace ictr {
 
 int fail(int code, const char *fmt, ...);  // ictr_launch.h
+#define HIPCHK(expr)                                                                                  \
+  do {                                                                                                \
+    hipError_t _e = (expr);                                                                           \
+    if (_e != hipSuccess) return fail(ICTR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
+  } while (0)
 
 // `bytes` of device memory (hipMalloc / hipFree) or, Pinned, of page-locked host memory (hipHostMalloc / hipHostFree)
 template <class T, bool Pinned>
@@ -74,6 +80,69 @@ class Event {
 
  private:
   hipEvent_t e_ = nullptr;
+};
+
+// One array of a carved block, and the carving: take() rounds the end up to `align`, places `bytes` there and moves on. A
+// result layout is ONE function that fills a struct of Parts; the kernel arguments and the copy-out both read that struct.
+struct Part {
+  size_t at = 0, bytes = 0;
+};
+struct Carve {
+  size_t end = 0;
+  Part take(size_t bytes, size_t align = 1) {
+    const Part p{(end + align - 1) / align * align, bytes};
+    end = p.at + bytes;
+    return p;
+  }
+};
+
+// The result block of an object that runs now and is waited for later: the device block its kernels write, the pinned
+// mirror, the event behind the copy, and whether a run is in flight / was ever enqueued. Declare it LAST in its object:
+// members go in reverse order, so the wait in this destructor comes before any buffer of a run in flight is released.
+class Readback {
+ public:
+  ~Readback() {
+    if (pending_) (void)hipEventSynchronize(done_.get());
+  }
+  // only grows, and releases both blocks before it allocates; the device block zero-filled on request
+  int reserve(size_t bytes, bool zero) {
+    if (int rc = done_ ? ICTR_OK : done_.create(hipEventDisableTiming)) return rc;
+    if (bytes <= cap_) return ICTR_OK;
+    cap_ = 0;
+    dev_.reset();
+    host_.reset();
+    if (int rc = dev_.alloc(bytes, zero)) return rc;
+    if (int rc = host_.alloc(bytes)) return rc;
+    cap_ = bytes;
+    return ICTR_OK;
+  }
+  char *dev() const { return dev_.get(); }
+  char *host() const { return host_.get(); }
+  bool pending() const { return pending_; }
+  bool ran() const { return ran_; }
+  int refuse(const char *what, const char *object) const {
+    // the inputs of a run stay fixed until its wait
+    return pending_ ? fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_%s_wait first", what, object) : ICTR_OK;
+  }
+  // the tail of every run: the block's first `bytes` to the mirror, behind everything enqueued on s
+  int post(size_t bytes, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(host_.get(), dev_.get(), bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(done_.get(), s));
+    pending_ = ran_ = true;
+    return ICTR_OK;
+  }
+  int wait() {  // the head of every wait (the caller has checked pending())
+    HIPCHK(hipEventSynchronize(done_.get()));
+    pending_ = false;
+    return ICTR_OK;
+  }
+
+ private:
+  DevBuf<char> dev_;
+  PinBuf<char> host_;
+  size_t cap_ = 0;
+  Event done_;
+  bool pending_ = false, ran_ = false;
 };
 
 }  // namespace ictr

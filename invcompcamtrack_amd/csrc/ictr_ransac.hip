@@ -25,6 +25,7 @@
 
 #include "ictr_dev.h"
 #include "ictr_devfn.h"
+#include "ictr_draw_hd.h"
 #include "ictr_launch.h"
 #include "se3_math.h"
 
@@ -262,22 +263,7 @@ __device__ __forceinline__ void p3p_lambda_twist(const double (*y)[3], const dou
 // one trial: draws, undistortion, degeneracy, P3P and the choice of root. Returns 1 and fills R, t (camera centre)
 // on success; idx gets the drawn indices either way.
 __device__ int ransac_trial(const RansacArgs &a, long long g, int *idx, double *Rout, double *tout) {
-  int i0 = -1, i1 = -1, i2 = -1, i3 = -1, nd = 0;
-  for (int k = 0; k < kRanMaxDraws && nd < 4; ++k) {
-    const unsigned long long u = ran_mix(a.seedmix ^ (((unsigned long long)g << 32) | (unsigned long long)k));
-    const int id = (int)(((u >> 32) * (unsigned long long)a.n) >> 32);
-    if (id == i0 || id == i1 || id == i2) continue;  // (i3 is set last)
-    if (nd == 0) i0 = id;
-    else if (nd == 1) i1 = id;
-    else if (nd == 2) i2 = id;
-    else i3 = id;
-    ++nd;
-  }
-  idx[0] = i0;
-  idx[1] = i1;
-  idx[2] = i2;
-  idx[3] = i3;
-  if (nd < 4) return 0;
+  if (ran_draw<4>(a.seedmix, g, a.n, idx) < 4) return 0;
   const int n = a.n;
   double P[4][3], x2[4][3];
 #pragma unroll
@@ -517,7 +503,7 @@ __global__ void __launch_bounds__(kRanSelBlock) k_ransac_finish(RansacArgs a) {
 // the run (launch_ransac_chunk) and the inspection entry (ictr_debug_ransac_trials)
 void launch_ransac_hyp_score(const RansacArgs &a, int tile, hipStream_t s) {
   hipLaunchKernelGGL(k_ransac_hyp, dim3((a.k + kRanHypBlock - 1) / kRanHypBlock), dim3(kRanHypBlock), 0, s, a);
-  const int segs = (a.nwords + kRanScoreBlock / 64 - 1) / (kRanScoreBlock / 64);
+  const int segs = ran_segs(a.nwords, kRanScoreBlock);
   if (tile == 16)
     hipLaunchKernelGGL(k_ransac_score<16>, dim3((a.k + 15) / 16, segs), dim3(kRanScoreBlock), 0, s, a);
   else if (tile == 64)
@@ -532,7 +518,7 @@ void launch_ransac_chunk(const RansacArgs &a, int tile, hipStream_t s) {
 }
 
 void launch_ransac_finish(const RansacArgs &a, hipStream_t s) {
-  const int segs = (a.nwords + kRanScoreBlock / 64 - 1) / (kRanScoreBlock / 64);
+  const int segs = ran_segs(a.nwords, kRanScoreBlock);
   hipLaunchKernelGGL(k_ransac_colsum, dim3(segs), dim3(kRanScoreBlock), 0, s, a);
   hipLaunchKernelGGL(k_ransac_finish, dim3(1), dim3(kRanSelBlock), 0, s, a);
 }
@@ -556,33 +542,21 @@ struct ictr_ransac {
   DevBuf<int> d_draws, d_status;
   DevBuf<unsigned> d_cnt;
   DevBuf<unsigned long long> d_words;
-  DevBuf<char> d_out;  // RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] | t [smax][3] |
-  PinBuf<char> h_out;  // words [smax][nwords] | cnt [n] | keep [smax] | cntf [n]
-  size_t out_bytes = 0;
-  bool points_set = false, pending = false, ran = false;
-  Event done;
-  ~ictr_ransac() {
-    if (pending) (void)hipEventSynchronize(done.get());
-  }
+  bool points_set = false;
+  Readback out;  // (ran_layout) declared last, so destroyed first: a run in flight ends before a buffer goes
 };
 
+// RansacState | trial [smax] i64 | draws [smax][4] i32 | R [smax][9] | t [smax][3] | words [smax][nwords] | cnt [n] |
+// keep [smax] | cntf [n], each on a 16-byte boundary
 struct RanLayout {
-  size_t trial, draws, R, t, words, cnt, keep, cntf, end;
+  Part trial, draws, R, t, words, cnt, keep, cntf, end;  // end: empty, at the block's size
 };
 static RanLayout ran_layout(const ictr_ransac *r) {
-  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-  RanLayout L;
-  const size_t S = (size_t)r->smax;
-  L.trial = up(sizeof(RansacState));
-  L.draws = up(L.trial + 8 * S);
-  L.R = up(L.draws + 16 * S);
-  L.t = up(L.R + 72 * S);
-  L.words = up(L.t + 24 * S);
-  L.cnt = up(L.words + 8 * S * r->nwords);
-  L.keep = up(L.cnt + 4 * (size_t)r->n);
-  L.cntf = up(L.keep + 4 * S);
-  L.end = up(L.cntf + 4 * (size_t)r->n);
-  return L;
+  Carve c;
+  const size_t S = (size_t)r->smax, n = (size_t)r->n;
+  c.take(sizeof(RansacState), 16);  // at the front
+  return {c.take(8 * S, 16), c.take(16 * S, 16), c.take(72 * S, 16), c.take(24 * S, 16), c.take(8 * S * r->nwords, 16),
+          c.take(4 * n, 16), c.take(4 * S, 16), c.take(4 * n, 16), c.take(0, 16)};  // braces: evaluated in this order
 }
 
 // trials per chunk: enough that one chunk's scoring (K x N lane tests) fills the device; ICTR_RANSAC_CHUNK overrides.
@@ -593,11 +567,6 @@ static int ransac_chunk(int n) {
   long long k = (1ll << 23) / n;
   k = std::max(256ll, std::min(16384ll, k));
   return (int)((k + 255) / 256 * 256);
-}
-
-static int ran_refuse_pending(const ictr_ransac *r, const char *what) {
-  if (r->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_ransac_wait first", what);
-  return ICTR_OK;
 }
 
 extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samples) {
@@ -612,19 +581,15 @@ extern "C" int ictr_ransac_create(ictr_ransac **out, int64_t n, int64_t max_samp
   r->nwords = (int)((n + 63) / 64);
   r->smax = max_samples;
   r->chunk = ransac_chunk(r->n);
-  const int tile = env_int("ICTR_RANSAC_TILE", 32);
-  r->tile = (tile == 16 || tile == 64) ? tile : 32;
+  r->tile = ran_tile_env("ICTR_RANSAC_TILE");
   const size_t K = (size_t)r->chunk;
-  r->out_bytes = ran_layout(r.get()).end;
   if (int rc = r->d_pts.alloc(sizeof(double) * 5 * n, true)) return rc;
   if (int rc = r->d_hyp.alloc(sizeof(double) * 12 * K, true)) return rc;
   if (int rc = r->d_draws.alloc(sizeof(int) * 4 * K, true)) return rc;
   if (int rc = r->d_status.alloc(sizeof(int) * K, true)) return rc;
   if (int rc = r->d_cnt.alloc(sizeof(unsigned) * K, true)) return rc;
   if (int rc = r->d_words.alloc(sizeof(unsigned long long) * K * r->nwords, true)) return rc;
-  if (int rc = r->d_out.alloc(r->out_bytes, true)) return rc;
-  if (int rc = r->h_out.alloc(r->out_bytes)) return rc;
-  if (int rc = r->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = r->out.reserve(ran_layout(r.get()).end.at, true)) return rc;
   *out = r.release();
   return ICTR_OK;
 }
@@ -633,7 +598,7 @@ extern "C" void ictr_ransac_destroy(ictr_ransac *r) { delete r; }
 
 extern "C" int ictr_ransac_set_points(ictr_ransac *r, const double *pt2d, const double *pt3d) {
   if (!r || !pt2d || !pt3d) return fail(ICTR_ERR_INVALID, "ransac_set_points: NULL argument");
-  if (int rc = ran_refuse_pending(r, "ransac_set_points")) return rc;
+  if (int rc = r->out.refuse("ransac_set_points", "ransac")) return rc;
   const size_t n = (size_t)r->n;
   HIPCHK(hipMemcpy(r->d_pts.get(), pt2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(r->d_pts.get() + 2 * n, pt3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
@@ -661,31 +626,28 @@ static int ran_fill_args(const ictr_ransac *r, const char *what, const double *f
   a.cy = cc[1];
   a.kc = kc;
   a.thr = inlthresh;
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull;  // splitmix64 (the device's ran_mix)
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  a.seedmix = z ^ (z >> 31);
+  a.seedmix = ran_seed(seed);
   a.hyp = r->d_hyp.get();
   a.draws = r->d_draws.get();
   a.status = r->d_status.get();
   a.cnt = r->d_cnt.get();
   a.words = r->d_words.get();
-  a.st = reinterpret_cast<RansacState *>(r->d_out.get());
-  a.o_trial = reinterpret_cast<long long *>(r->d_out.get() + L.trial);
-  a.o_draws = reinterpret_cast<int *>(r->d_out.get() + L.draws);
-  a.o_R = reinterpret_cast<double *>(r->d_out.get() + L.R);
-  a.o_t = reinterpret_cast<double *>(r->d_out.get() + L.t);
-  a.o_words = reinterpret_cast<unsigned long long *>(r->d_out.get() + L.words);
-  a.o_cnt = reinterpret_cast<int *>(r->d_out.get() + L.cnt);
-  a.o_keep = reinterpret_cast<int *>(r->d_out.get() + L.keep);
-  a.o_cntf = reinterpret_cast<int *>(r->d_out.get() + L.cntf);
+  a.st = reinterpret_cast<RansacState *>(r->out.dev());
+  a.o_trial = reinterpret_cast<long long *>(r->out.dev() + L.trial.at);
+  a.o_draws = reinterpret_cast<int *>(r->out.dev() + L.draws.at);
+  a.o_R = reinterpret_cast<double *>(r->out.dev() + L.R.at);
+  a.o_t = reinterpret_cast<double *>(r->out.dev() + L.t.at);
+  a.o_words = reinterpret_cast<unsigned long long *>(r->out.dev() + L.words.at);
+  a.o_cnt = reinterpret_cast<int *>(r->out.dev() + L.cnt.at);
+  a.o_keep = reinterpret_cast<int *>(r->out.dev() + L.keep.at);
+  a.o_cntf = reinterpret_cast<int *>(r->out.dev() + L.cntf.at);
   return ICTR_OK;
 }
 
 extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *cc, double kc, int64_t nsamples,
                                int64_t maxtrials, double inlthresh, uint64_t seed, void *hip_stream) {
   if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ransac_run: NULL argument");
-  if (int rc = ran_refuse_pending(r, "ransac_run")) return rc;
+  if (int rc = r->out.refuse("ransac_run", "ransac")) return rc;
   if (!r->points_set) return fail(ICTR_ERR_STATE, "ransac_run: ictr_ransac_set_points has not been called");
   if (nsamples < 1 || nsamples > r->smax)
     return fail(ICTR_ERR_INVALID, "ransac_run: nsamples %lld (1 .. %lld, the size given at creation)",
@@ -697,12 +659,12 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   r->stream = (hipStream_t)hip_stream;
   a.nsamples = nsamples;
   a.maxtrials = maxtrials;
-  HIPCHK(hipMemsetAsync(r->d_out.get(), 0, sizeof(RansacState), r->stream));
+  HIPCHK(hipMemsetAsync(a.st, 0, sizeof(RansacState), r->stream));
   const int64_t K = r->chunk;
   const int64_t nchunks = (maxtrials + K - 1) / K;
   for (int64_t c = 0; c < nchunks; ++c) {
     if (c > 0 && c % kRanGroup == 0) {  // a long run: stop enqueueing once the samples are found
-      RansacState *hs = reinterpret_cast<RansacState *>(r->h_out.get());
+      RansacState *hs = reinterpret_cast<RansacState *>(r->out.host());
       HIPCHK(hipMemcpyAsync(&hs->done, &a.st->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
       HIPCHK(hipStreamSynchronize(r->stream));
       if (*(volatile int *)&hs->done) break;
@@ -714,25 +676,20 @@ extern "C" int ictr_ransac_run(ictr_ransac *r, const double *fc, const double *c
   }
   launch_ransac_finish(a, r->stream);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r->h_out.get(), r->d_out.get(), r->out_bytes, hipMemcpyDeviceToHost, r->stream));
-  HIPCHK(hipEventRecord(r->done.get(), r->stream));
-  r->pending = true;
-  r->ran = true;
-  return ICTR_OK;
+  return r->out.post(ran_layout(r).end.at, r->stream);
 }
 
 extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, double *t, double *p, uint64_t *inl_words,
                                 int32_t *inl_cnt) {
   if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
-  if (!r->pending) return fail(ICTR_ERR_STATE, "ransac_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(r->done.get()));
-  r->pending = false;
+  if (!r->out.pending()) return fail(ICTR_ERR_STATE, "ransac_wait: nothing has been run");
+  if (int rc = r->out.wait()) return rc;
   const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out.get());
-  const int *keep = reinterpret_cast<const int *>(r->h_out.get() + L.keep);
-  const double *hR = reinterpret_cast<const double *>(r->h_out.get() + L.R);
-  const double *ht = reinterpret_cast<const double *>(r->h_out.get() + L.t);
-  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->h_out.get() + L.words);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->out.host());
+  const int *keep = reinterpret_cast<const int *>(r->out.host() + L.keep.at);
+  const double *hR = reinterpret_cast<const double *>(r->out.host() + L.R.at);
+  const double *ht = reinterpret_cast<const double *>(r->out.host() + L.t.at);
+  const uint64_t *hw = reinterpret_cast<const uint64_t *>(r->out.host() + L.words.at);
   if (counts) {
     counts[0] = st.kept;
     counts[1] = st.held;
@@ -754,18 +711,18 @@ extern "C" int ictr_ransac_wait(ictr_ransac *r, int64_t *counts, double *R, doub
     }
     if (inl_words) memcpy(inl_words + (size_t)r->nwords * q, hw + (size_t)r->nwords * s, 8 * (size_t)r->nwords);
   }
-  if (inl_cnt) memcpy(inl_cnt, r->h_out.get() + L.cntf, sizeof(int32_t) * (size_t)st.n_ic);
+  if (inl_cnt) memcpy(inl_cnt, r->out.host() + L.cntf.at, sizeof(int32_t) * (size_t)st.n_ic);
   return ICTR_OK;
 }
 
 extern "C" int ictr_ransac_samples(const ictr_ransac *r, int64_t *trial, int32_t *draws) {
   if (!r) return fail(ICTR_ERR_INVALID, "ransac is NULL");
-  if (r->pending || !r->ran) return fail(ICTR_ERR_STATE, "ransac_samples: no completed run");
+  if (r->out.pending() || !r->out.ran()) return fail(ICTR_ERR_STATE, "ransac_samples: no completed run");
   const RanLayout L = ran_layout(r);
-  const RansacState &st = *reinterpret_cast<const RansacState *>(r->h_out.get());
-  const int *keep = reinterpret_cast<const int *>(r->h_out.get() + L.keep);
-  const long long *ht = reinterpret_cast<const long long *>(r->h_out.get() + L.trial);
-  const int *hd = reinterpret_cast<const int *>(r->h_out.get() + L.draws);
+  const RansacState &st = *reinterpret_cast<const RansacState *>(r->out.host());
+  const int *keep = reinterpret_cast<const int *>(r->out.host() + L.keep.at);
+  const long long *ht = reinterpret_cast<const long long *>(r->out.host() + L.trial.at);
+  const int *hd = reinterpret_cast<const int *>(r->out.host() + L.draws.at);
   for (long long q = 0; q < st.kept; ++q) {
     if (trial) trial[q] = ht[keep[q]];
     if (draws) memcpy(draws + 4 * q, hd + 4 * (size_t)keep[q], 4 * sizeof(int32_t));
@@ -780,7 +737,7 @@ extern "C" int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const 
                                         int32_t *draws, double *hyp, uint32_t *cnt, uint64_t *words) {
   if (!r || !fc || !cc || !status || !draws || !hyp || !cnt || !words)
     return fail(ICTR_ERR_INVALID, "debug_ransac_trials: NULL argument");
-  if (int rc = ran_refuse_pending(r, "debug_ransac_trials")) return rc;
+  if (int rc = r->out.refuse("debug_ransac_trials", "ransac")) return rc;
   if (!r->points_set) return fail(ICTR_ERR_STATE, "debug_ransac_trials: ictr_ransac_set_points has not been called");
   if (count < 1 || count > ((int64_t)1 << 20) || first_trial < 0 || first_trial > ((int64_t)1 << 40) - count)
     return fail(ICTR_ERR_INVALID, "debug_ransac_trials: trials %lld + %lld (1 .. 2^20 trials below 2^40)",
@@ -789,7 +746,7 @@ extern "C" int ictr_debug_ransac_trials(ictr_ransac *r, const double *fc, const 
   if (int rc = ran_fill_args(r, "debug_ransac_trials", fc, cc, kc, inlthresh, seed, a)) return rc;
   a.nsamples = 1;
   a.maxtrials = first_trial + count;
-  HIPCHK(hipMemsetAsync(r->d_out.get(), 0, sizeof(RansacState), nullptr));
+  HIPCHK(hipMemsetAsync(a.st, 0, sizeof(RansacState), nullptr));
   const int64_t K = r->chunk;
   const size_t W = (size_t)r->nwords;
   for (int64_t done = 0; done < count; done += K) {

@@ -376,18 +376,17 @@ struct ictr_triang {
   DevBuf<float> d_x, d_y, d_px, d_py;
   DevBuf<float> d_in;  // init | campos | ptdir, [max_points][3] each
   PinBuf<float> h_in;
-  DevBuf<char> d_out;  // pts [n][3] | cov [n][9] | iters [n] | status [n]
-  PinBuf<char> h_out;
-  Event done;
-  bool cams_set = false, tracks_set = false, pending = false;
-  ~ictr_triang() {
-    if (pending) (void)hipEventSynchronize(done.get());
-  }
+  bool cams_set = false, tracks_set = false;
+  Readback out;  // (tri_layout) declared last, so destroyed first: a run in flight ends before a buffer goes
 };
 
-static int tri_refuse_pending(const ictr_triang *t, const char *what) {
-  if (t->pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_triang_wait first", what);
-  return ICTR_OK;
+struct TriLayout {  // pts [n][3] | cov [n][9] | iters [n] | status [n], packed
+  Part pts, cov, iters, status, end;  // end: empty, at the block's size
+};
+static TriLayout tri_layout(int64_t n) {
+  Carve c;
+  const size_t f = sizeof(float) * (size_t)n, i = sizeof(int32_t) * (size_t)n;
+  return {c.take(3 * f), c.take(9 * f), c.take(i), c.take(i), c.take(0)};  // braces: evaluated in this order
 }
 
 extern "C" int ictr_triang_create(ictr_triang **out, int64_t max_points, int64_t max_obs, int64_t max_frames) {
@@ -413,10 +412,8 @@ extern "C" int ictr_triang_create(ictr_triang **out, int64_t max_points, int64_t
   if (int rc = t->d_x.alloc(sizeof(float) * M)) return rc;
   if (int rc = t->d_y.alloc(sizeof(float) * M)) return rc;
   if (int rc = t->d_in.alloc(sizeof(float) * 9 * N)) return rc;
-  if (int rc = t->d_out.alloc(sizeof(float) * 14 * N)) return rc;
   if (int rc = t->h_in.alloc(sizeof(float) * 9 * N)) return rc;
-  if (int rc = t->h_out.alloc(sizeof(float) * 14 * N)) return rc;
-  if (int rc = t->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = t->out.reserve(tri_layout(max_points).end.at, false)) return rc;
   *out = t.release();
   return ICTR_OK;
 }
@@ -425,7 +422,7 @@ extern "C" void ictr_triang_destroy(ictr_triang *t) { delete t; }
 
 extern "C" int ictr_triang_set_cameras(ictr_triang *t, const float *P, int64_t nframes) {
   if (!t || !P) return fail(ICTR_ERR_INVALID, "triang_set_cameras: NULL argument");
-  if (int rc = tri_refuse_pending(t, "triang_set_cameras")) return rc;
+  if (int rc = t->out.refuse("triang_set_cameras", "triang")) return rc;
   if (nframes < 1 || nframes > t->max_frames)
     return fail(ICTR_ERR_INVALID, "triang_set_cameras: %lld frames (1 .. %lld, the size given at creation)",
                 (long long)nframes, (long long)t->max_frames);
@@ -439,7 +436,7 @@ extern "C" int ictr_triang_set_cameras(ictr_triang *t, const float *P, int64_t n
 extern "C" int ictr_triang_set_tracks(ictr_triang *t, int64_t n, const int64_t *offsets, const int32_t *view,
                                       const float *x, const float *y) {
   if (!t || !offsets || !view || !x || !y) return fail(ICTR_ERR_INVALID, "triang_set_tracks: NULL argument");
-  if (int rc = tri_refuse_pending(t, "triang_set_tracks")) return rc;
+  if (int rc = t->out.refuse("triang_set_tracks", "triang")) return rc;
   if (!t->cams_set) return fail(ICTR_ERR_STATE, "triang_set_tracks: ictr_triang_set_cameras has not been called");
   if (n < 1 || n > t->max_points)
     return fail(ICTR_ERR_INVALID, "triang_set_tracks: %lld points (1 .. %lld, the size given at creation)", (long long)n,
@@ -507,7 +504,7 @@ extern "C" int ictr_triang_set_tracks(ictr_triang *t, int64_t n, const int64_t *
 extern "C" int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_params *params, const float *init_pts,
                                const float *campos, const float *ptdir, void *hip_stream) {
   if (!t) return fail(ICTR_ERR_INVALID, "triang is NULL");
-  if (int rc = tri_refuse_pending(t, "triang_run")) return rc;
+  if (int rc = t->out.refuse("triang_run", "triang")) return rc;
   if (mode < ICTR_TRIANG_DLT || mode > ICTR_TRIANG_DEPTH) return fail(ICTR_ERR_INVALID, "triang_run: mode %d (0 .. 3)", mode);
   if (!t->cams_set || !t->tracks_set)
     return fail(ICTR_ERR_STATE, "triang_run: cameras and tracks have to be set first");
@@ -550,30 +547,25 @@ extern "C" int ictr_triang_run(ictr_triang *t, int mode, const ictr_triang_param
     a.campos = t->d_in.get() + 3 * n;
     a.ptdir = t->d_in.get() + 6 * n;
   }
-  float *o = reinterpret_cast<float *>(t->d_out.get());
-  a.pts = o;
-  a.cov = o + 3 * n;
-  a.iters = reinterpret_cast<int *>(o + 12 * n);
-  a.status = reinterpret_cast<int *>(o + 13 * n);
+  const TriLayout L = tri_layout(t->n);
+  a.pts = reinterpret_cast<float *>(t->out.dev() + L.pts.at);
+  a.cov = reinterpret_cast<float *>(t->out.dev() + L.cov.at);
+  a.iters = reinterpret_cast<int *>(t->out.dev() + L.iters.at);
+  a.status = reinterpret_cast<int *>(t->out.dev() + L.status.at);
   launch_triang(mode, a, s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->h_out.get(), t->d_out.get(), sizeof(float) * 14 * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(t->done.get(), s));
-  t->pending = true;
-  return ICTR_OK;
+  return t->out.post(L.end.at, s);
 }
 
 extern "C" int ictr_triang_wait(ictr_triang *t, float *pts, float *cov, int32_t *iters, int32_t *status) {
   if (!t) return fail(ICTR_ERR_INVALID, "triang is NULL");
-  if (!t->pending) return fail(ICTR_ERR_STATE, "triang_wait: nothing has been run");
-  HIPCHK(hipEventSynchronize(t->done.get()));
-  t->pending = false;
-  const size_t n = (size_t)t->n;
-  const float *o = reinterpret_cast<const float *>(t->h_out.get());
-  if (pts) memcpy(pts, o, sizeof(float) * 3 * n);
-  if (cov) memcpy(cov, o + 3 * n, sizeof(float) * 9 * n);
-  if (iters) memcpy(iters, o + 12 * n, sizeof(int32_t) * n);
-  if (status) memcpy(status, o + 13 * n, sizeof(int32_t) * n);
+  if (!t->out.pending()) return fail(ICTR_ERR_STATE, "triang_wait: nothing has been run");
+  if (int rc = t->out.wait()) return rc;
+  const TriLayout L = tri_layout(t->n);
+  if (pts) memcpy(pts, t->out.host() + L.pts.at, L.pts.bytes);
+  if (cov) memcpy(cov, t->out.host() + L.cov.at, L.cov.bytes);
+  if (iters) memcpy(iters, t->out.host() + L.iters.at, L.iters.bytes);
+  if (status) memcpy(status, t->out.host() + L.status.at, L.status.bytes);
   return ICTR_OK;
 }
 

@@ -25,32 +25,16 @@ import math
 import numpy as np
 
 from . import _lib
+from ._hostmath import M64 as _M64, div as _div, draw_indices_n
 from ._lib import check, dp, f64c
-from .ransac import _M64, _div, _mix
 
 __all__ = ["fit_f8", "epiline_dist", "draw_indices_n", "trials_host", "split_static_host", "split_static", "StaticSplitter",
            "pairs_from_tracks", "pairs_from_stereo_tracks", "SWEEPS"]
 
 SWEEPS = 5          # kFsSweeps of csrc/ictr_fsplit_hd.h
-MAX_DRAWS = 1024    # kFsMaxDraws
 MAX_TRIALS = 1 << 20
 _SQRT2 = 1.4142135623730951
 _NAN9 = [math.nan] * 9
-
-
-def draw_indices_n(seed, t, n, count, max_draws=MAX_DRAWS):
-    """The first `count` distinct indices of trial t's stream (draw order); fewer than `count` (a shorter list) when
-    max_draws draws do not give them. ransac.draw_indices is this with count = 4."""
-    sm = _mix(int(seed) & _M64)
-    out = []
-    for k in range(max_draws):
-        u = _mix(sm ^ (((int(t) << 32) | k) & _M64))
-        i = ((u >> 32) * int(n)) >> 32
-        if i not in out:
-            out.append(i)
-            if len(out) == count:
-                break
-    return out
 
 
 def _normalise(x, y):

@@ -33,34 +33,19 @@ import os
 import numpy as np
 
 from . import _lib
+from ._hostmath import M64 as _M64, div as _div, draw_indices_n, se3_exp_d as _se3_exp_d
 from ._lib import check, dp, f64c
 
 __all__ = ["sample_poses", "sample_poses_host", "fit_cameras_odom", "best_sample", "draw_indices", "undistort",
            "distort", "is_degenerate", "p3p"]
 
-_M64 = (1 << 64) - 1
 _EPS = 2.0 ** -52
-
-
-def _mix(z):
-    z = (z + 0x9E3779B97F4A7C15) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
 
 
 def draw_indices(seed, t, n, max_draws=1024):
     """The 4 distinct match indices of trial t (draw order), or None when max_draws draws do not give 4."""
-    sm = _mix(int(seed) & _M64)
-    out = []
-    for k in range(max_draws):
-        u = _mix(sm ^ (((int(t) << 32) | k) & _M64))
-        i = ((u >> 32) * int(n)) >> 32
-        if i not in out:
-            out.append(i)
-            if len(out) == 4:
-                return out
-    return None
+    out = draw_indices_n(seed, t, n, 4, max_draws)
+    return out if len(out) == 4 else None
 
 
 def undistort(xd, yd, kc):
@@ -128,13 +113,6 @@ def _cubick(b, c, d):
 
 def _sqrt(x):
     return math.sqrt(x) if x >= 0.0 else math.nan
-
-
-def _div(a, b):
-    try:
-        return a / b
-    except ZeroDivisionError:
-        return math.nan if a == 0.0 or a != a else math.copysign(math.inf, a) * math.copysign(1.0, b)
 
 
 def _cof3(A):
@@ -492,12 +470,6 @@ def best_sample(corr):
     if np.all(np.isnan(means)):
         return 0, means
     return int(np.nanargmax(means)), means
-
-
-def _se3_exp_d(p):
-    G = np.empty(12, np.float64)
-    _lib.load().ictr_se3_coeff_to_group_d(dp(G), dp(f64c(p)))
-    return G.reshape(3, 4)
 
 
 def _op_dict(op, n):

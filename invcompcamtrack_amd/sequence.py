@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._hostmath import se3_exp_d
 from ._lib import check, dp, f64c
 from .tracker import Pyramid, TrackBatch
 
@@ -38,17 +39,11 @@ def _cam_params(cam):
             int(cam._wh[1]))
 
 
-def _se3_exp_d(p):
-    G = np.empty(12, np.float64)
-    _lib.load().ictr_se3_coeff_to_group_d(dp(G), dp(f64c(p)))
-    return G
-
-
 def select_points(pts3d_world, p, cam, stride=10, cap=None):
     """Steps 1-2 for one pair: world indices (int64, world order) of the points the pair tracks."""
     X = np.asarray(pts3d_world, np.float64).reshape(3, -1)
     fx, fy, cx, cy, w, h = _cam_params(cam)
-    G = _se3_exp_d(p)
+    G = se3_exp_d(p).reshape(-1)
     xc = G[0] * X[0] + G[1] * X[1] + G[2] * X[2] + G[3]
     yc = G[4] * X[0] + G[5] * X[1] + G[6] * X[2] + G[7]
     zc = G[8] * X[0] + G[9] * X[1] + G[10] * X[2] + G[11]

@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._hostmath import se3_exp_d as _se3_exp
 from ._lib import check, dp, f32c, f64c, fp
 
 __all__ = ["Triangulator", "triangulate_tracks", "cameras_from_poses", "rays_from_first_view", "tracks_from_oftrack",
@@ -47,12 +48,6 @@ def _rot_vec(R, v, transpose=False):
     if transpose:
         R = R.T
     return np.array([(R[i, 0] * v[0] + R[i, 1] * v[1]) + R[i, 2] * v[2] for i in range(3)])
-
-
-def _se3_exp(p):
-    G = np.empty(12, np.float64)
-    _lib.load().ictr_se3_coeff_to_group_d(dp(G), dp(f64c(p)))
-    return G.reshape(3, 4)
 
 
 def cameras_from_poses(cam, poses):

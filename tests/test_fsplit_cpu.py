@@ -248,3 +248,35 @@ def test_shared_header_on_the_host_equals_the_restatement(tmp_path):
         d = S._dist(F, s8[0:1], s8[8:9], s8[16:17], s8[24:25])[0]
         assert np.array_equal(np.array(F + [ok, d]).view(np.uint64), g.view(np.uint64))
     assert 60 <= failed < len(smp) // 10
+
+
+def test_shared_draw_header_on_the_host_equals_draw_indices_n(tmp_path):
+    """csrc/ictr_draw_hd.h compiled as plain C++ (tests/cxx/draw_hd_host.cpp, address and undefined-behaviour
+    sanitizers): ran_seed and the indices of ran_draw<4> / ran_draw<8> are those of draw_indices_n, exactly, at the
+    smallest and largest n, at trial indices around 2^31, 2^32 and 2^40 and at the seeds' corners; where n < K the
+    draw ends with n indices and -1 in the rest. (That it ends after kRanMaxDraws draws and not another number is not
+    seen from outside: every index of so small an n is drawn long before.) The sanitizers stay silent."""
+    import os
+    import subprocess
+    from invcompcamtrack_amd import _hostmath as H
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tests", "cxx", "draw_hd_host")
+    r = subprocess.run(["g++", "-std=c++17", "-O2", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                        "-Werror", "-Wno-unknown-pragmas", "-I" + os.path.join(root, "invcompcamtrack_amd", "csrc"),
+                        "-o", exe, exe + ".cpp"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    recs = [(seed, t, n, k) for k in (4, 8) for n in (4, 7, 8, 9, 64, 1 << 22, 1 << 24)
+            for t in (0, (1 << 31) - 1, 1 << 31, (1 << 32) - 1, 1 << 32, (1 << 40) - 1)
+            for seed in (0, 1, 1 << 63, (1 << 64) - 1)]
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    np.array(recs, np.uint64).tofile(fin)
+    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stderr
+    got = np.fromfile(fout, np.int64).reshape(-1, 10)
+    assert len(got) == len(recs) == 336
+    for (seed, t, n, k), g in zip(recs, got):
+        idx = S.draw_indices_n(seed, t, n, k)
+        assert len(idx) == min(n, k) and len(set(idx)) == len(idx)  # 1024 draws reach every index of a small n
+        assert int(g[0]) & H.M64 == H.mix(seed)
+        assert g[1] == len(idx) and g[2:].tolist() == idx + [-1] * (8 - len(idx)), (seed, t, n, k)
+    assert S.draw_indices_n(0, 0, 7, 8, max_draws=1 << 16) == S.draw_indices_n(0, 0, 7, 8)  # seven, however long

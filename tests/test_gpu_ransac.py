@@ -103,6 +103,22 @@ def test_refusals():
     s.set_points(x, X)
 
 
+def test_destroy_with_a_run_pending(monkeypatch):
+    """A sampler dropped with its run in flight ends that run before its buffers go; a fresh one then gives the host's
+    result. 67 matches (one full and one ragged 64-block) in chunks of 16 trials."""
+    monkeypatch.setenv("ICTR_RANSAC_CHUNK", "16")
+    x, X = _matches(67, 0.6, 0.0, seed=67)
+    s = R.RansacSampler(67, 5)
+    assert s.chunk == 16
+    s.set_points(x, X)
+    s.run_async(FC, CC, 5, 300, 2.0, seed=2)
+    del s
+    host = R.sample_poses_host(x, X, FC, CC, 5, 300, 2.0, 0.0, seed=2, detail=True)
+    _check_margins(host, 2.0)
+    assert host["accepted"] > 0
+    _same(R.sample_poses(x, X, FC, CC, 5, 300, 2.0, 0.0, seed=2), host)
+
+
 def _e2e_scene():
     w, h = 320, 240
     pref = np.array([0.02, -0.03, 0.05, 0.01, -0.02, 0.015])

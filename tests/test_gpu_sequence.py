@@ -240,6 +240,28 @@ def test_refusals(scene):
     assert st.wait()["npts"].shape == (2,)
 
 
+def test_destroy_with_a_run_pending(scene):
+    """A tracker dropped with its run in flight ends that run before its buffers, ring pyramids and inner batch go; a
+    fresh one then gives what the host loop gives (the bars of test_device_chain_equals_host_loop)."""
+    args, cap, stride, _ = SETS["p8_single"]
+    op, cam = _setup(scene, args, cap)
+    frames, p0 = scene["frames"][:3], scene["poses"][0]
+    st = sq.SequenceTracker(cam, op, scene["pts3d"], stride)
+    st.track_async(frames, p0)
+    del st
+    st = sq.SequenceTracker(cam, op, scene["pts3d"], stride)
+    st.track_async(frames, p0)
+    dev = st.wait()
+    host = sq.track_sequence_host_loop(cam, op, scene["pts3d"], frames, p0, stride, return_selection=True)
+    assert (host["npts"] > 0).all()
+    np.testing.assert_array_equal(dev["npts"], host["npts"])
+    want_hash = np.array([sq.selection_hash(s) for s in host["selection"]], np.uint64)
+    np.testing.assert_array_equal(st.selection_hashes(), want_hash)
+    np.testing.assert_array_equal(dev["iters"], host["iters"])
+    assert np.abs(dev["poses"] - host["poses"]).max() <= 1e-5
+    np.testing.assert_array_equal(dev["poses"][0], host["poses"][0])
+
+
 def test_inputs_stay_fixed_while_a_run_is_in_flight(scene):
     args, cap, stride, _ = SETS["p8_single"]
     op, cam = _setup(scene, args, cap)

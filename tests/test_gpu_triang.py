@@ -147,6 +147,22 @@ def test_device_equals_numpy_on_100000_ragged_tracks(big, big_dlt, mode):
         assert np.median(err) < 0.1
 
 
+def test_destroy_with_a_run_pending():
+    """A triangulator dropped with its run in flight ends that run before its buffers go; a fresh one then gives the
+    NumPy restatement's bits. 65 two-view tracks: one full wave and one of a single track."""
+    sc = _big_scene(65, nf=4, lmin=2, lmax=2, seed=65)
+    t = T.Triangulator(65, 130, 4)
+    t.set_cameras(sc["P"])
+    t.set_tracks(sc["off"], sc["view"], sc["xy"])
+    t.run_async("dlt")
+    del t
+    want = TN.triangulate(sc["P"], sc["off"], sc["view"], sc["xy"][:, 0], sc["xy"][:, 1], "dlt")
+    r = T.triangulate_tracks(sc["P"], sc["off"], sc["view"], sc["xy"], "dlt")
+    _assert_bits(r["pts"], want["pts"], "dlt points")
+    _assert_bits(_cov9(r), want["cov"], "dlt covariances")
+    assert np.array_equal(r["iters"], want["iters"]) and np.array_equal(r["status"], want["status"])
+
+
 @pytest.mark.timeout(300)
 def test_single_point_entry_points_and_reference_named_wrappers(golden):
     g = golden
