@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/ictr.h"
+#include "ictr_xchg.h"
 
 namespace ictr {
 

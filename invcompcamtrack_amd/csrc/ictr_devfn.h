@@ -304,6 +304,33 @@ __device__ __forceinline__ float taps_blend(const TapLoads &t, float w0, float w
   return w0 * a + w1 * b + w2 * c + w3 * d;
 }
 
+// fixed-order f64 reduction of the H partials of `nblk` workgroups into sH[0..20] (all THREADS threads of the workgroup:
+// THREADS / 32 slices x 32 components, then the slices in order); sRed: [THREADS / 32][32]. k_level_tail, k_iter_tail and
+// the resident form's solver workgroup: the same sum in the same order
+template <int THREADS>
+__device__ __forceinline__ void reduce_partH(const EngineDev &e, int b, int nblk, double (*sRed)[32], float *sH) {
+  {
+    const int j = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    double s = 0.0;
+    const float *ph = e.partH + (size_t)b * nblk * kPartHStride + j;
+    // (unrolled: eight loads in flight, the additions stay in the same order -- with thousands of partials, e.g. one
+    // dense 1080p pair in 4-point chunks, the serial load latency of this loop was 60 us per level)
+    if (j < kHUnique) {
+#pragma unroll 8
+      for (int k = sl; k < nblk; k += THREADS / 32) s += (double)ph[(size_t)k * kPartHStride];
+    }
+    sRed[sl][j] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kHUnique) {
+    double s = 0.0;
+#pragma unroll
+    for (int sl = 0; sl < THREADS / 32; ++sl) s += sRed[sl][threadIdx.x];
+    sH[threadIdx.x] = (float)s;
+  }
+  __syncthreads();
+}
+
 // ---------------------------------------------------------------- wave-parallel 6x6 solver state (one wave64)
 // The per-iteration tail of the Gauss-Newton loop (final sum -> fullPivLu solve -> pose update -> exp map -> loop
 // condition, odometer.cpp:407-418,509-515) is a serial dependency chain on the critical path of every iteration. Run

@@ -624,7 +624,7 @@ struct TrackPlan {
 struct Mailbox {
   DevBuf<unsigned long long> d;
   size_t bytes = 0;
-  unsigned epoch = 0;  // tags of a launch: epoch << 12 | exchange number
+  unsigned epoch = 0;  // of the last launch on it (ictr_xchg.h)
 };
 struct ProbHost {
   int npts = 0;
@@ -1200,7 +1200,7 @@ static int team_points(const ictr_batch *b) {
 static int track1_team(const ictr_batch *b, int *q) {
   if (b->P != 8 || (engine_variant(b) & ICTR_VARIANT_ANY_SIZE)) return 1;  // teams: the lean 8x8 form only
   if (b->maxpts <= b->team_lo || b->maxpts > b->team_hi) return 1;
-  if ((int64_t)b->nlev * (1 + std::max(0, b->op->maxiter)) >= 4000) return 1;  // exchange number: 12 bits of the tag
+  if ((int64_t)b->nlev * (1 + std::max(0, b->op->maxiter)) >= kXchgMaxSeq) return 1;  // exchange number of the tag
   const int target = team_points(b);
   if (target < 1) return 1;
   const int team = track1_team_size(b->maxpts, target);
@@ -1235,7 +1235,7 @@ static bool resident_plan(const ictr_batch *b, TrackPlan *p) {
     const int slots = (int)std::min<int64_t>(std::min<int64_t>(b->B, max_slots), capacity / (parts + 1));
     if (slots < 1) continue;
     if (np == 16 && slots < b->B && !xchg) continue;
-    if ((int64_t)((b->B + slots - 1) / slots) * b->op->maxiter >= 4000) return false;  // exchange number: 12 bits
+    if ((int64_t)((b->B + slots - 1) / slots) * b->op->maxiter >= kXchgMaxSeq) return false;  // exchange number
     p->res = ResidentGeom{parts, slots, np};
     return true;
   }
@@ -1398,12 +1398,11 @@ static double team_timeout_s() {
   return s ? std::max(0.001, atof(s)) : 5.0;
 }
 // Mailbox, tag epoch, polling limit and error flag of the next launch with an in-launch exchange (team form of k_track1,
-// k_level_resident) that will run on `s` and needs `need` bytes of mailbox `m`. The protocol's host side, whole: a granule
-// counts when its tag is the launch's epoch << 12 | exchange number, so a mailbox is cleared (tag 0: "nothing yet") when it
-// is made and when the 20-bit epoch wraps, on the stream of the launch; every launch gets the next epoch, and nothing an
-// earlier or failed launch left behind can match. what: the mailbox's name in the error text.
-static int exchange_prepare(ictr_batch *b, Mailbox *m, size_t need, const char *what, int mute, hipStream_t s,
+// k_level_resident) that will run on `s` and needs `granules` granules of mailbox `m`: the host side of ictr_xchg.h's
+// protocol, whole. The mailbox is cleared on the stream of the launch. what: the mailbox's name in the error text.
+static int exchange_prepare(ictr_batch *b, Mailbox *m, size_t granules, const char *what, int mute, hipStream_t s,
                             Exchange *x) {
+  const size_t need = sizeof(unsigned long long) * granules;
   if (need > m->bytes) {
     if (m->d) HIPCHK(hipStreamSynchronize(s));  // an earlier launch may still be polling the old mailbox
     m->d.reset();
@@ -1425,13 +1424,11 @@ static int exchange_prepare(ictr_batch *b, Mailbox *m, size_t need, const char *
     *b->h_team_err.get() = 0;
     HIPCHK(hipHostGetDevicePointer((void **)&b->d_team_err, b->h_team_err.get(), 0));
   }
-  m->epoch += 1;
-  if (m->epoch >= (1u << 20)) {  // the epoch field wrapped: forget every old tag
-    HIPCHK(hipMemsetAsync(m->d.get(), 0, m->bytes, s));
-    m->epoch = 1;
-  }
-  x->tag0 = m->epoch << 12;
-  x->limit = (unsigned long long)(team_timeout_s() * 1e8);
+  const XchgEpoch next = xchg_next_epoch(m->epoch);
+  if (next.clear) HIPCHK(hipMemsetAsync(m->d.get(), 0, m->bytes, s));
+  m->epoch = next.epoch;
+  x->tag0 = xchg_tag0(m->epoch);
+  x->limit = (unsigned long long)(team_timeout_s() * kWallClockHz);
   x->mail = m->d.get();
   x->err = b->d_team_err;
   x->mute = mute;
@@ -1444,7 +1441,7 @@ static int team_prepare(ictr_batch *b, const TrackPlan &p, T1Team *tm) {
   if (p.team < 2) return ICTR_OK;
   tm->team = p.team;
   tm->q = p.team_q;
-  return exchange_prepare(b, &b->team_mail, track1_team_mail_bytes(b->B, p.team), "team", p.mute, b->stream, &tm->x);
+  return exchange_prepare(b, &b->team_mail, team_mail_granules(b->B, p.team), "team", p.mute, b->stream, &tm->x);
 }
 // ONE k_track1 launch for every problem of `e` on the batch's stream, through the team admission when the plan has
 // teams. blob: the begin phase in the arguments (kFormTrack1Begin); host_st: the pinned mirror the launch writes the final
@@ -1469,7 +1466,7 @@ static int launch_resident(ictr_batch *b, const EngineDev &e, const LevelCam &lc
                            const TrackPlan &p, hipStream_t s) {
   const ResidentGeom &g = p.res;
   Exchange x;
-  if (int rc = exchange_prepare(b, &b->res_mail, resident_mail_bytes(g.parts, g.slots), "resident", p.mute, s, &x)) return rc;
+  if (int rc = exchange_prepare(b, &b->res_mail, res_mail_granules(g.parts, g.slots), "resident", p.mute, s, &x)) return rc;
   // every workgroup of the launch must be resident: it starts when its slots are free of team / resident launches
   const int bpc = std::max(1, std::min(4, resident_blocks_per_cu(g.np)));
   const int weight = g.slots * (g.parts + 1) * ((4 + bpc - 1) / bpc);
@@ -1560,7 +1557,7 @@ static int enqueue_levels(ictr_batch *b) {
   if (b->xchg.world > 1 && p.form != kFormResident)
     return fail(ICTR_ERR_STATE, "a peer exchange is set (sharded resident form) but this tracking cannot run in the "
                                 "resident-iteration form (8x8 patches, no robustness option, no patch normalisation, builder-"
-                                "made pyramids, at most 4000 pair-rounds x iterations per level)");
+                                "made pyramids, at most %d pair-rounds x iterations per level)", kXchgMaxSeq);
   if (p.form == kFormTrack1)
     return track1_launch(b, e, p, nullptr, p.project_here ? b->d_st_mirror : nullptr, p.project_here != 0);
   if (p.form == kFormGraph) {

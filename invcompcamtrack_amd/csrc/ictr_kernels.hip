@@ -145,29 +145,6 @@ __global__ __launch_bounds__(kBlock) void k_ref_level(EngineDev e, LevelCam lc, 
 
 // One workgroup per problem: fixed-order f64 reduction of the H partials of `nblk` workgroups (8 slices x 32
 // components, then the slices in order), publish H (or the rank-local sum when sharded), reset the loop state.
-// fixed-order f64 reduction of the H partials of `nblk` workgroups into sH[0..20] (all threads of the workgroup)
-__device__ __forceinline__ void reduce_partH(const EngineDev &e, int b, int nblk, double (*sRed)[32], float *sH) {
-  {
-    const int j = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    double s = 0.0;
-    const float *ph = e.partH + (size_t)b * nblk * kPartHStride + j;
-    // (unrolled: eight loads in flight, the additions stay in the same order -- with thousands of partials, e.g. one
-    // dense 1080p pair in 4-point chunks, the serial load latency of this loop was 60 us per level)
-    if (j < kHUnique) {
-#pragma unroll 8
-      for (int k = sl; k < nblk; k += kBlock / 32) s += (double)ph[(size_t)k * kPartHStride];
-    }
-    sRed[sl][j] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHUnique) {
-    double s = 0.0;
-#pragma unroll
-    for (int sl = 0; sl < kBlock / 32; ++sl) s += sRed[sl][threadIdx.x];
-    sH[threadIdx.x] = (float)s;
-  }
-  __syncthreads();
-}
 // defer_h: the P = 8 fast path accumulates H inside the level's FIRST iteration launch (k_iter8<.., WH = true>: it
 // streams Gx, Gy and the coefficients anyway), so the setup kernel is a pure gather/store kernel and this tail only
 // resets the loop state; the first k_iter_tail / k_iter_finish of the level reduces and factors H.
@@ -183,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_level_tail(EngineDev e, int nblk, in
     if (threadIdx.x == 0) level_reset(st, e);
     return;
   }
-  reduce_partH(e, b, nblk, sRed, sH);
+  reduce_partH<kBlock>(e, b, nblk, sRed, sH);
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x;
   if (e.sharded) {
@@ -344,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void k_iter_tail(EngineDev e, int level, in
   ProbState &st = e.st[b];
   if (!st.active) return;
   // deferred H: the launch before this one also wrote the H partials (workgroup-uniform branch)
-  if (first_h) reduce_partH(e, b, nblk, sRedH, sH);
+  if (first_h) reduce_partH<kBlock>(e, b, nblk, sRedH, sH);
   {
     const int j = threadIdx.x & 7, sl = threadIdx.x >> 3;
     double s = 0.0;

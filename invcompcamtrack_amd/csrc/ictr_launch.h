@@ -1,7 +1,8 @@
 // ictr_launch.h -- host-side interface between the translation units of the library: every function that one .hip file
 // defines and another calls, the argument bundles of the launchers, the error helper and the HIP-check macro. Included by
 // every .hip file, the defining one too, so that a definition that drifts from its declaration does not compile or link.
-// Nothing here is seen by a kernel: kernel arguments are the structs of ictr_dev.h, which the launchers fill field by field.
+// Nothing here is seen by a kernel: kernel arguments are the structs of ictr_dev.h (and Exchange of ictr_xchg.h), which the
+// launchers fill.
 #pragma once
 
 #include <stddef.h>
@@ -55,19 +56,10 @@ struct LevelLaunch {
 struct ResidentGeom {
   int parts, slots, np;  // worker workgroups per frame pair, pairs in flight, patches per wave (16 or 32)
 };
-// one in-launch exchange (team form of k_track1, k_level_resident): the mailbox and what bounds the polling
-struct Exchange {
-  unsigned tag0;             // launch epoch << 12; the kernels add the exchange number
-  unsigned long long limit;  // polling limit, wall_clock64 ticks (100 MHz)
-  unsigned long long *mail;  // granules {float bits, tag}; tag 0 = "nothing yet"
-  int *err;                  // sticky time-out flag (pinned host memory as the device sees it)
-  int mute;                  // debug (ICTR_VARIANT_DEBUG_MUTE), 0 = off: part (k_track1) / worker (k_level_resident)
-                             // `mute - 1` of every problem never posts its values (time-out tests)
-};
 // team form of the one-launch tracker (ictr_track1.hip, "Teams"): several workgroups per problem
 struct T1Team {
   int team, q;  // workgroups per problem, points per workgroup
-  Exchange x;   // mailbox [B][2][team][32] granules
+  Exchange x;   // ictr_xchg.h; the mailbox in the team layout
 };
 
 // ---------------------------------------------------------------- ictr_kernels.hip
@@ -128,7 +120,6 @@ size_t track1_blob_bytes(void);
 // point count alone
 int track1_team_q(int maxpts, int target);
 int track1_team_size(int maxpts, int target);
-size_t track1_team_mail_bytes(int B, int team);
 // ONE launch for the whole tracking of every problem. blob (may be NULL): [ProbState x B][PlaneSet x B x nlev] for the
 // fused begin; host_st (may be NULL): pinned mirror of the final records; project_here (without a blob): the records and
 // the plane table have been uploaded, the launch projects (step 3) itself; tm (may be NULL): team form; any_size:
@@ -138,7 +129,6 @@ hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, i
                          bool any_size = false);
 
 // ---------------------------------------------------------------- ictr_resident.hip
-size_t resident_mail_bytes(int parts, int slots);
 int resident_points_per_workgroup(int np);
 int resident_blocks_per_cu(int np);  // workgroups of the kernel that one CU holds at once (0: the kernel cannot run)
 // all iterations of one level in ONE launch, (g.parts + 1) * g.slots workgroups that must all be resident. nblk: H partials

@@ -7,14 +7,8 @@
 // own mailbox in rank order. No communicator, no proxy thread, no second stream: one small kernel enqueued on the
 // compute stream between the tail and the finish kernels.
 //
-// Protocol (no fences, no flags): a value travels as one naturally aligned 8-byte granule {float bits, tag} written by
-// ONE system-scope store; the tag is the exchange's sequence number, so a reader polls the granule itself until the
-// tag matches -- a granule is either old or complete (MI355X_MICROARCH.md, "Valid forms", R2). Mailboxes are
-// double-buffered by the parity of the sequence number: a peer can be at most one exchange ahead (it needs this
-// rank's granules of exchange k+1 before it can finish k+1 and start k+2), so slot k & 1 is never overwritten while
-// it is still being read. Every rank adds the slots in the same order (rank 0, 1, ...): identical bits everywhere, the
-// redundant solves stay in lockstep. Polling is bounded by a wall-clock limit; a timeout raises a sticky error flag
-// instead of hanging the GPU.
+// The protocol is the one of ictr_xchg.h (granules, parity slots, bounded polling) over the rank mailbox layout, with
+// system-scope stores and loads; the tag is the object's sequence number, the sticky error flag lives in device memory.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -36,32 +30,34 @@ struct P2PArgs {
   int rank, world;
   int64_t cap;                // granules per slot
   int *err;                   // sticky device flag: an exchange timed out
-  unsigned long long limit;   // polling limit in wall_clock64 ticks (100 MHz)
+  unsigned long long limit;   // polling limit in wall_clock64 ticks
 };
 
 __global__ __launch_bounds__(256) void k_p2p_allreduce(P2PArgs a, float *buf, int count, unsigned seq) {
-  const size_t par = (size_t)(seq & 1u) * a.world;
+  const size_t par = rank_mail_slot(seq, a.world);
   for (int i = threadIdx.x; i < count; i += blockDim.x) {
-    const uint64_t g = ((uint64_t)seq << 32) | (uint64_t)__builtin_bit_cast(unsigned, buf[i]);
+    const uint64_t g = xchg_pack(seq, buf[i]);
     for (int r = 0; r < a.world; ++r)  // my record into slot [rank] of every mailbox, mine included
-      __hip_atomic_store(a.peer[r] + (par + a.rank) * a.cap + i, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(a.peer[r] + rank_mail_index(par + a.rank, a.cap, i), g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  // this kernel's own variant of the time-out step (xchg_timed_out): the clock starts before the first load, the flag
+  // is a device word raised by every lane that gives up, and there is no dead state -- one exchange per launch
   const unsigned long long t0 = wall_clock64();
   for (int i = threadIdx.x; i < count; i += blockDim.x) {
     float sum = 0.0f;
     for (int r = 0; r < a.world; ++r) {
-      const uint64_t *src = a.local + (par + r) * a.cap + i;
+      const uint64_t *src = a.local + rank_mail_index(par + r, a.cap, i);
       uint64_t g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      while ((unsigned)(g >> 32) != seq) {
+      while (xchg_miss(g, seq)) {
         if (wall_clock64() - t0 > a.limit) {  // a peer never arrived: give up, flag it, leave the kernel
           atomicExch(a.err, 1);
-          g = (uint64_t)seq << 32;
+          g = xchg_empty(seq);
           break;
         }
         __builtin_amdgcn_s_sleep(2);
         g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
-      sum += __builtin_bit_cast(float, (unsigned)(g & 0xffffffffu));  // rank order: the same bits on every rank
+      sum += xchg_value(g);  // rank order: the same bits on every rank
     }
     buf[i] = sum;
   }
@@ -96,7 +92,7 @@ extern "C" int ictr_p2p_create(ictr_p2p **out, int rank, int world, int64_t coun
   p->rank = rank;
   p->world = world;
   p->cap = (count + 31) / 32 * 32;
-  const size_t bytes = sizeof(uint64_t) * 2 * (size_t)world * p->cap;
+  const size_t bytes = sizeof(uint64_t) * rank_mail_granules(world, p->cap);
   // mailbox memory that remote stores and local polls see coherently: uncached (fine-grained) device memory
   uint64_t *mail = nullptr;
   hipError_t e = hipExtMallocWithFlags((void **)&mail, bytes, hipDeviceMallocUncached);
@@ -152,7 +148,7 @@ extern "C" int ictr_p2p_allreduce(ictr_p2p *p, float *dev_buf, int64_t count, vo
   a.world = p->world;
   a.cap = p->cap;
   a.err = p->d_err.get();
-  a.limit = (unsigned long long)(p->timeout_s * 1e8);  // wall_clock64 ticks at 100 MHz
+  a.limit = (unsigned long long)(p->timeout_s * kWallClockHz);
   p->seq += 1;
   if (p->seq == 0) p->seq = 1;  // tag 0 is reserved for "empty"
   hipLaunchKernelGGL(k_p2p_allreduce, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, a, dev_buf, (int)count, p->seq);

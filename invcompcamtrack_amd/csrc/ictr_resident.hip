@@ -22,8 +22,7 @@
 //     partials); the pair's SOLVER workgroup polls them in one round trip (256 lanes x 8 granules), adds in a fixed
 //     order in f64, one wave runs the solver turn (WaveSolver, ictr_devfn.h: substitution with the level's LU factors,
 //     pose update, exp map, loop condition; odometer.cpp:407-418, 509-515) and broadcasts cpos_G + the loop flag.
-// The mailbox protocol is the one of the team form (ictr_track1.hip "Teams"): 8-byte granules {float bits, tag},
-// tags = launch epoch << 12 | exchange number, double-buffered by parity, bounded polling with a sticky error flag.
+// The mailbox protocol and this form's mailbox layout: ictr_xchg.h.
 // H partials come from the level's setup launch (k_ref8: three sums per patch) and are reduced + factored by the pair's
 // solver workgroup at the start of the pair (what k_level_tail does in the other launch forms); templates and (possibly
 // stale) coefficients come from the buffers that launch wrote: patches, coefficients and projections are bit-identical
@@ -43,7 +42,6 @@ constexpr int kResWaves = 4;                // waves per workgroup
 constexpr int kResThreads = 64 * kResWaves;
 // patches (points) per wave: template parameter NP of the kernel, 32 (large batches: four pairs in flight) or 16 (one
 // or two pairs: twice the workgroups, half the patch loop); points per workgroup = kResWaves * NP
-constexpr int kResSlot = 8;                 // granules per worker workgroup in the gather box (6 used)
 #ifndef ICTR_RES_AUX
 #define ICTR_RES_AUX 2  // template loads of the pair prologue: slc (streamed)
 #endif
@@ -57,29 +55,18 @@ struct ResArgs {
   int level;
   int parts, slots;          // worker workgroups per frame pair; pairs in flight (grid = slots * (parts + 1))
   int nblk;                  // workgroups per problem of the level's setup launch (their H partials: e.partH)
-  int dbg_mute;              // debug (variant bit 25): worker `dbg_mute - 1` never posts its sums (time-out test); 0 = off
   int prof_slot;             // ICTR_RES_PROF builds: the slot whose worker 0 / solver report their cycle counters
   ResXchg x;                 // x.world > 1: the solver workgroups sum H and b over the ranks (one-hop mailbox exchange)
-  unsigned tag0;             // launch epoch << 12
-  unsigned long long limit;  // polling limit, wall_clock64 ticks (100 MHz)
-  unsigned long long *mail;  // per slot: gather box [2][parts][kResSlot], broadcast box [2][16]
-  int *err;                  // sticky time-out flag (pinned host memory as the device sees it)
+  Exchange ex;               // the launch's exchange; the mailbox in the resident layout (ictr_xchg.h)
 };
 
-__host__ __device__ __forceinline__ size_t res_slot_granules(int parts) { return (size_t)2 * parts * kResSlot + 2 * 16; }
-
-struct ResPoll {
-  unsigned long long limit;
-  int *err;
-  int dead;
-};
 // poll up to eight granules per lane until every tag matches; lanes / entries without a granule pass nullptr
 // (entries written out one by one: everything stays in registers). TWO sets of requests are kept in flight, half a
 // round trip apart: a granule is seen at most half a memory round trip after it became visible (one set: a whole one).
 #define RES_EACH8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-__device__ __forceinline__ void res_poll(ResPoll &pc, const unsigned long long *(&src)[8], unsigned long long (&g)[8],
+__device__ __forceinline__ void res_poll(XchgPoll &pc, const unsigned long long *(&src)[8], unsigned long long (&g)[8],
                                          unsigned tag, int lane) {
-  const unsigned long long empty = (unsigned long long)tag << 32;
+  const unsigned long long empty = xchg_empty(tag);
 #define RES_LOAD(u) g[u] = src[u] ? __hip_atomic_load(src[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : empty;
   RES_EACH8(RES_LOAD)
   if (pc.dead) return;
@@ -91,20 +78,13 @@ __device__ __forceinline__ void res_poll(ResPoll &pc, const unsigned long long *
   unsigned long long t0 = 0;
   for (;;) {
     bool miss = false;
-#define RES_MISS(u) miss |= (unsigned)(g[u] >> 32) != tag;
+#define RES_MISS(u) miss |= xchg_miss(g[u], tag);
     RES_EACH8(RES_MISS)
     if (__builtin_amdgcn_ballot_w64(miss) == 0) break;  // wave-uniform
-    if (!started) {
-      t0 = wall_clock64();
-      started = true;
-    } else if (wall_clock64() - t0 > pc.limit) {  // a peer never arrived: flag it, never wait again
-      if (lane == 0) __hip_atomic_store(pc.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      pc.dead = 1;
-      break;
-    }
+    XCHG_TIMEOUT_STEP(pc, started, t0, lane)
     // the older set's answers replace what is still missing; that set is requested again for what is missing then
 #define RES_ROTATE(u)                                                                                         \
-  if ((unsigned)(g[u] >> 32) != tag) {                                                                        \
+  if (xchg_miss(g[u], tag)) {                                                                                 \
     g[u] = h[u];                                                                                              \
     h[u] = __hip_atomic_load(src[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                             \
   }
@@ -112,8 +92,8 @@ __device__ __forceinline__ void res_poll(ResPoll &pc, const unsigned long long *
   }
 }
 // one granule per lane (the workers' wait for the broadcast): three requests in flight
-__device__ __forceinline__ unsigned long long res_poll1(ResPoll &pc, const unsigned long long *src, unsigned tag, int lane) {
-  const unsigned long long empty = (unsigned long long)tag << 32;
+__device__ __forceinline__ unsigned long long res_poll1(XchgPoll &pc, const unsigned long long *src, unsigned tag, int lane) {
+  const unsigned long long empty = xchg_empty(tag);
   unsigned long long g = src ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : empty;
   if (pc.dead) return g;
   __builtin_amdgcn_s_sleep(3);
@@ -122,16 +102,9 @@ __device__ __forceinline__ unsigned long long res_poll1(ResPoll &pc, const unsig
   unsigned long long h2 = src ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : empty;
   bool started = false;
   unsigned long long t0 = 0;
-  while (__builtin_amdgcn_ballot_w64((unsigned)(g >> 32) != tag) != 0) {
-    if (!started) {
-      t0 = wall_clock64();
-      started = true;
-    } else if (wall_clock64() - t0 > pc.limit) {
-      if (lane == 0) __hip_atomic_store(pc.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      pc.dead = 1;
-      break;
-    }
-    if ((unsigned)(g >> 32) != tag) {
+  while (__builtin_amdgcn_ballot_w64(xchg_miss(g, tag)) != 0) {
+    XCHG_TIMEOUT_STEP(pc, started, t0, lane)
+    if (xchg_miss(g, tag)) {
       g = h1;
       h1 = h2;
       h2 = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -163,56 +136,47 @@ hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *pl,
   return hipGetLastError();
 }
 
-// Sharded resident form: lanes [0, n) of the solver's wave 0 each hold one local value; it goes as one granule {value,
-// tag} into slot [parity][rank][pair * kXchgPerPair + off + lane] of EVERY rank's mailbox (system-scope stores over the
+// Sharded resident form: lanes [0, n) of the solver's wave 0 each hold one local value; it goes as one granule into
+// [pair * kXchgPerPair + off + lane] of this rank's slot of EVERY rank's mailbox (system-scope stores over the
 // point-to-point links), then the lane polls its own mailbox for the same granule of every rank and adds them in rank
-// order in f64 -- the same bits on every rank, so the redundant solves stay in lockstep (the protocol of ictr_p2p.hip,
-// inside the launch: no kernel boundary, no host, no communicator). Tags live in the upper half of the 32-bit space
-// (the p2p object's own self-test uses the small sequence numbers).
-__device__ __forceinline__ double res_xchg_sum(const ResXchg &x, ResPoll &pc, int pair, unsigned xs, int off, int n, float v,
+// order in f64 (ictr_xchg.h's protocol with rank tags, inside the launch: no kernel boundary, no host, no communicator).
+__device__ __forceinline__ double res_xchg_sum(const ResXchg &x, XchgPoll &pc, int pair, unsigned xs, int off, int n, float v,
                                                int lane) {
-  const unsigned tag = 0x80000000u | xs;
-  const size_t par = (size_t)(xs & 1u) * x.world;
+  const unsigned tag = xchg_rank_tag(xs);
+  const size_t par = rank_mail_slot(xs, x.world);
   const size_t idx = (size_t)pair * kXchgPerPair + off + lane;
   if (lane < n) {
-    const unsigned long long g = ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, v);
+    const unsigned long long g = xchg_pack(tag, v);
     for (int r = 0; r < x.world; ++r)
-      __hip_atomic_store(x.peer[r] + (par + x.rank) * x.cap + idx, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(x.peer[r] + rank_mail_index(par + x.rank, x.cap, idx), g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // the peers' granules: eight ranks' requests in flight at a time (one fabric round trip for a node of eight), re-polled
   // until every tag matches; added in rank order
   double sum = 0.0;
   bool started = false;
   unsigned long long t0 = 0;
-  const unsigned long long empty = (unsigned long long)tag << 32;
+  const unsigned long long empty = xchg_empty(tag);
   for (int r0 = 0; r0 < x.world; r0 += 8) {
     unsigned long long g[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u)
       g[u] = (lane < n && r0 + u < x.world)
-                 ? __hip_atomic_load(x.local + (par + r0 + u) * x.cap + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
+                 ? __hip_atomic_load(x.local + rank_mail_index(par + r0 + u, x.cap, idx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
                  : empty;
     while (!pc.dead) {
       bool miss = false;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) miss |= (unsigned)(g[u] >> 32) != tag;
+      for (int u = 0; u < 8; ++u) miss |= xchg_miss(g[u], tag);
       if (__builtin_amdgcn_ballot_w64(miss) == 0) break;  // wave-uniform
-      if (!started) {
-        t0 = wall_clock64();
-        started = true;
-      } else if (wall_clock64() - t0 > pc.limit) {  // a peer rank never arrived: flag it, never wait again
-        if (lane == 0) __hip_atomic_store(pc.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        pc.dead = 1;
-        break;
-      }
+      XCHG_TIMEOUT_STEP(pc, started, t0, lane)
       __builtin_amdgcn_s_sleep(1);
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        if ((unsigned)(g[u] >> 32) != tag)
-          g[u] = __hip_atomic_load(x.local + (par + r0 + u) * x.cap + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (xchg_miss(g[u], tag))
+          g[u] = __hip_atomic_load(x.local + rank_mail_index(par + r0 + u, x.cap, idx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) sum += (double)__builtin_bit_cast(float, (unsigned)(g[u] & 0xffffffffu));
+    for (int u = 0; u < 8; ++u) sum += (double)xchg_value(g[u]);
   }
   return sum;
 }
@@ -278,12 +242,9 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = e.M;
-  unsigned long long *gbox = a.mail + (size_t)slot * res_slot_granules(parts);
-  unsigned long long *bbox = gbox + (size_t)2 * parts * kResSlot;
-  ResPoll pc;
-  pc.limit = a.limit;
-  pc.err = a.err;
-  pc.dead = 0;
+  unsigned long long *gbox = a.ex.mail + res_gather_box(slot, parts);
+  unsigned long long *bbox = gbox + res_bcast_box(parts);
+  XchgPoll pc{a.ex.limit, a.ex.err, 0};
   unsigned seq = 0;
 #ifdef ICTR_RES_PROF
   const int tr_row = part == parts ? (slot < 8 ? 8 + slot : -1) : ((part == 0 && slot < 8) ? slot : -1);
@@ -308,27 +269,9 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
         unsigned *dst = reinterpret_cast<unsigned *>(&sSt);
         for (int i = tid; i < (int)(sizeof(ProbState) / 4); i += kResThreads) dst[i] = src[i];
       }
-      // ---- what k_level_tail does in the other launch forms: fixed-order f64 sum of the H partials (8 slices x 32
-      // components, then the slices in order), full-pivot LU once per level, loop state reset: the setup launch's partials
-      // (e.partH), while the pair's workers load their templates
-      {
-        const int j = tid & 31, sl = tid >> 5;
-        double sacc = 0.0;
-        const float *ph = e.partH + (size_t)b * a.nblk * kPartHStride + j;
-        if (j < kHUnique) {
-#pragma unroll 8
-          for (int k = sl; k < a.nblk; k += kResThreads / 32) sacc += (double)ph[(size_t)k * kPartHStride];
-        }
-        sRedH[sl][j] = sacc;
-      }
-      __syncthreads();
-      if (tid < kHUnique) {
-        double sacc = 0.0;
-#pragma unroll
-        for (int sl = 0; sl < kResThreads / 32; ++sl) sacc += sRedH[sl][tid];
-        sH[tid] = (float)sacc;
-      }
-      __syncthreads();
+      // ---- what k_level_tail does in the other launch forms: fixed-order f64 sum of the H partials, full-pivot LU once
+      // per level, loop state reset: the setup launch's partials (e.partH), while the pair's workers load their templates
+      reduce_partH<kResThreads>(e, b, a.nblk, sRedH, sH);
       unsigned xs = 0;  // (sharded resident form) this pair's exchange count, wave 0 only
       if (wave == 0) {
         float hl = lane < kHUnique ? sH[lane] : 0.0f;
@@ -350,9 +293,9 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
       __syncthreads();
       while (active) {
         seq += 1;
-        const unsigned tag = a.tag0 + seq;
-        const unsigned long long *gslot = gbox + (size_t)(seq & 1u) * parts * kResSlot;
-        unsigned long long *bslot = bbox + (size_t)(seq & 1u) * 16;
+        const unsigned tag = xchg_tag(a.ex.tag0, seq);
+        const unsigned long long *gslot = gbox + res_gather_slot(seq, parts);
+        unsigned long long *bslot = bbox + res_bcast_slot(seq);
         // lane (k, rr) = 8 k + rr (k < 6) reads value k of the workers ((8 wave + u) 8 + rr), u = 0..7: eight granule
         // loads in flight per lane, 256 workers per round trip; sums in a fixed order: u, rounds, rr, waves
         RES_MARK(0)  // solver: loop overhead / barrier behind the previous broadcast
@@ -365,11 +308,11 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
 #define RES_SRC(u)                                                                   \
   {                                                                                  \
     const int r = r0 + (wave * 8 + u) * 8 + rr;                                      \
-    src[u] = (k < 6 && r < parts) ? gslot + (size_t)r * kResSlot + k : nullptr;      \
+    src[u] = (k < 6 && r < parts) ? gslot + res_gather_row(r) + k : nullptr;        \
   }
           RES_EACH8(RES_SRC)
           res_poll(pc, src, g, tag, lane);
-#define RES_ACC(u) accd += (double)__builtin_bit_cast(float, (unsigned)(g[u] & 0xffffffffu));
+#define RES_ACC(u) accd += (double)xchg_value(g[u]);
           RES_EACH8(RES_ACC)
         }
         const double tot = res_sum8(accd);
@@ -406,9 +349,7 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
           const int act = pc.dead ? 0 : S.active;  // a time-out ends the pair (the host reports the failure)
           if (lane == 12) gv = __builtin_bit_cast(float, act);
           if (lane < 13)
-            __hip_atomic_store(bslot + lane,
-                               ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, gv),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(bslot + lane, xchg_pack(tag, gv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (lane == 0) sG[12] = __builtin_bit_cast(float, act);
           RES_MARK(3)  // solver: solve + broadcast
           RES_STAMP(tr_row, tr_it, 3)
@@ -588,21 +529,20 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
       RES_STAMP(tr_row, tr_it, 2)
       // ---- gather: the workgroup's six sums -> the pair's mailbox; then the broadcast
       seq += 1;
-      const unsigned tag = a.tag0 + seq;
-      unsigned long long *gslot = gbox + (size_t)(seq & 1u) * parts * kResSlot;
-      const unsigned long long *bslot = bbox + (size_t)(seq & 1u) * 16;
+      const unsigned tag = xchg_tag(a.ex.tag0, seq);
+      unsigned long long *gslot = gbox + res_gather_slot(seq, parts);
+      const unsigned long long *bslot = bbox + res_bcast_slot(seq);
       if (wave == 0) {
         int lane_v = lane;  // (opaque copy: the two mailbox addresses are formed here, not kept in registers over the loop)
         asm volatile("" : "+v"(lane_v));
         float bs = 0.0f;
         if (lane < 6) bs = (sPart[0][lane] + sPart[1][lane]) + (sPart[2][lane] + sPart[3][lane]);
-        if (lane < 6 && part + 1 != a.dbg_mute)
-          __hip_atomic_store(gslot + (size_t)part * kResSlot + lane_v,
-                             ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, bs),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane < 6 && part + 1 != a.ex.mute)
+          __hip_atomic_store(gslot + res_gather_row(part) + lane_v, xchg_pack(tag, bs), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long g = res_poll1(pc, lane < 13 ? bslot + lane_v : nullptr, tag, lane);
         // a time-out ends the pair in this workgroup (bounded time; the host reports the tracking as failed)
-        if (lane < 13) sG[lane] = (lane == 12 && pc.dead) ? 0.0f : __builtin_bit_cast(float, (unsigned)(g & 0xffffffffu));
+        if (lane < 13) sG[lane] = (lane == 12 && pc.dead) ? 0.0f : xchg_value(g);
         RES_MARK(4)  // worker (wave 0): gather store + waiting for the broadcast
         RES_STAMP(tr_row, tr_it, 3)
       }
@@ -632,9 +572,6 @@ extern "C" int ictr_prof_res_trace(unsigned long long *out, int clear) {  // out
   return 0;
 }
 #endif
-size_t resident_mail_bytes(int parts, int slots) {
-  return sizeof(unsigned long long) * (size_t)slots * res_slot_granules(parts);
-}
 int resident_points_per_workgroup(int np) { return kResWaves * np; }
 template <int NP>
 static int res_occupancy() {
@@ -667,11 +604,7 @@ hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int lev
   a.level = level;
   a.parts = g.parts;
   a.slots = g.slots;
-  a.dbg_mute = x.mute;
-  a.tag0 = x.tag0;
-  a.limit = x.limit;
-  a.mail = x.mail;
-  a.err = x.err;
+  a.ex = x;
   const dim3 grid((g.parts + 1) * g.slots), blk(kResThreads);
   if (g.np == 32)
     hipLaunchKernelGGL((k_level_resident<32>), grid, blk, 0, s, e, a);

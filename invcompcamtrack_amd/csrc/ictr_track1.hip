@@ -45,7 +45,6 @@ constexpr int kT8MaxWaves = 8;  // 8x8 form
 // table, byte for byte what ictr_batch_begin would copy), workgroup b stores its problem's part to device memory for
 // later readers, runs step 3 (k_project_ref's arithmetic) for its own points, and at the end writes the final state
 // straight into the host's pinned mirror as well: one launch and one event per tracking.
-constexpr int kTeamSlot = 32;     // granules per workgroup and exchange (21 of H or 6 of b)
 constexpr int kTeamMax = 64;      // workgroups per problem
 constexpr int kT1BlobWords = 704;  // 2816 B: 4 problems x (ProbState 496 B + 5 levels x 40 B)
 struct T1Args {
@@ -59,14 +58,10 @@ struct T1Args {
   ProbState *host_st;      // pinned host mirror of the final states [B], or nullptr
   // team form (k_track1_p8<..., TEAM>): `team` workgroups share one problem, see "Teams" below
   int team, team_q;                // workgroups per problem; points per workgroup (the last one may own fewer)
-  unsigned team_tag0;              // launch epoch << 12: granule tags of this launch are team_tag0 + exchange number
-  unsigned long long team_limit;   // polling limit in wall_clock64 ticks (100 MHz)
-  unsigned long long *team_mail;   // [B][2][team][kTeamSlot] granules {float bits, tag}
-  int *team_err;                   // sticky flag (pinned host memory): an exchange timed out
-  int team_mute;                   // debug (variant bit 25): part `team_mute - 1` of every problem never posts its values
-                                   // (its peers' polls run into the limit: the time-out path's test); 0 = off
+  Exchange ex;                     // the launch's exchange; the mailbox in the team layout (ictr_xchg.h)
   __attribute__((aligned(8))) unsigned blob[kT1BlobWords];  // [ProbState x B][PlaneSet x B x nlev]
 };
+static_assert(sizeof(EngineDev) + sizeof(T1Args) <= 4096, "k_track1's arguments must fit the 4 KB kernel-argument segment");
 
 // Initial state / plane table of problem b: from the kernel arguments (fused begin) or from device memory. The source
 // is chosen at run time, so these few loads are flat loads into vector registers; v_readfirstlane puts every value back
@@ -375,21 +370,14 @@ __global__ __launch_bounds__(64 * kT1MaxWaves) void k_track1(EngineDev e, T1Args
 // ever read by another workgroup -- and the only exchange is the one the multi-GPU form has: the 21
 // sums of H once per level and the 6 of b once per iteration, all-gathered through a mailbox in device memory; every
 // workgroup then adds the parts in part order and runs the same solver turn on the same bits, so the redundant poses and
-// loop conditions stay in lockstep without a second hop. A value travels as ONE naturally aligned 8-byte granule
-// {float bits, tag} written by one agent-scope store and polled on its tag (ictr_p2p.hip's protocol; no flag, no fence:
-// MI355X_MICROARCH.md "Valid forms", R2); tags = launch epoch << 12 | exchange number, so nothing is cleared between
-// launches; slots are double-buffered by the exchange number's parity (a workgroup can be at most one exchange ahead of
-// its slowest peer, which still owes it that exchange's granules). Polling is bounded by a wall-clock limit: on a
-// time-out the workgroup raises a sticky flag in pinned host memory and stops waiting for good, so every wave reaches
-// the end of the kernel (the host reports the tracking as failed). Progress needs the team's workgroups resident
-// together: they are consecutive block ids of an in-order dispatch, so the lowest unfinished problem always holds its CUs.
+// loop conditions stay in lockstep without a second hop. The exchange's protocol and mailbox layout: ictr_xchg.h (agent-
+// scope stores and loads). Progress needs the team's workgroups resident together: they are consecutive block ids of an
+// in-order dispatch, so the lowest unfinished problem always holds its CUs.
 struct TeamCtx {
-  unsigned long long *mail;  // this problem's mailbox [2][team][kTeamSlot]
+  unsigned long long *mail;  // this problem's box of the mailbox
   int team, part;
   unsigned tag0, seq;        // seq: exchanges done so far in this launch
-  unsigned long long limit;
-  int *err;
-  int dead;                  // a poll timed out: never wait again
+  XchgPoll poll;
   int mute;                  // debug: this workgroup never posts (time-out test)
 };
 __device__ __forceinline__ double lane_gather64(double v, int src_lane) {
@@ -404,16 +392,14 @@ __device__ __forceinline__ double lane_gather64(double v, int src_lane) {
 template <int N, int LPP>
 __device__ __forceinline__ double team_allsum(TeamCtx &c, float v, int lane) {
   c.seq += 1;
-  const unsigned tag = c.tag0 + c.seq;
-  unsigned long long *slot = c.mail + (size_t)(c.seq & 1u) * c.team * kTeamSlot;
+  const unsigned tag = xchg_tag(c.tag0, c.seq);
+  unsigned long long *slot = c.mail + team_mail_slot(c.seq, c.team);
   if (lane < N && !c.mute)
-    __hip_atomic_store(slot + c.part * kTeamSlot + lane,
-                       ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, v),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot + team_mail_row(c.part) + lane, xchg_pack(tag, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   constexpr int PPP = 64 / LPP;  // parts per sweep
   constexpr int CH = 8;          // sweeps in flight
   const int k = lane & (LPP - 1), rr = lane / LPP;
-  const unsigned long long empty = (unsigned long long)tag << 32;  // "arrived, value +0": lanes without a granule
+  const unsigned long long empty = xchg_empty(tag);  // lanes without a granule
   double acc = 0.0;
   for (int r0 = 0; r0 < c.team; r0 += CH * PPP) {
     unsigned long long g[CH];
@@ -422,34 +408,27 @@ __device__ __forceinline__ double team_allsum(TeamCtx &c, float v, int lane) {
     for (int u = 0; u < CH; ++u) {
       const int r = r0 + u * PPP + rr;
       const bool mine = k < N && r < c.team;
-      src[u] = slot + (size_t)(mine ? r : 0) * kTeamSlot + (mine ? k : 0);
+      src[u] = slot + team_mail_row(mine ? r : 0) + (mine ? k : 0);
       g[u] = empty;
       if (mine) g[u] = __hip_atomic_load(src[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!c.dead) {
+    if (!c.poll.dead) {
       bool started = false;
       unsigned long long t0 = 0;
       for (;;) {
         bool miss = false;
 #pragma unroll
-        for (int u = 0; u < CH; ++u) miss |= (unsigned)(g[u] >> 32) != tag;
+        for (int u = 0; u < CH; ++u) miss |= xchg_miss(g[u], tag);
         if (__builtin_amdgcn_ballot_w64(miss) == 0) break;  // wave-uniform
-        if (!started) {
-          t0 = wall_clock64();
-          started = true;
-        } else if (wall_clock64() - t0 > c.limit) {  // a peer never arrived: flag it, never wait again
-          if (lane == 0) __hip_atomic_store(c.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          c.dead = 1;
-          break;
-        }
+        XCHG_TIMEOUT_STEP(c.poll, started, t0, lane)
         __builtin_amdgcn_s_sleep(1);
 #pragma unroll
         for (int u = 0; u < CH; ++u)
-          if ((unsigned)(g[u] >> 32) != tag) g[u] = __hip_atomic_load(src[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (xchg_miss(g[u], tag)) g[u] = __hip_atomic_load(src[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
 #pragma unroll
-    for (int u = 0; u < CH; ++u) acc += (double)__builtin_bit_cast(float, (unsigned)(g[u] & 0xffffffffu));
+    for (int u = 0; u < CH; ++u) acc += (double)xchg_value(g[u]);
   }
   double tot = acc;
 #pragma unroll
@@ -550,15 +529,13 @@ __global__ __launch_bounds__(64 * kT8MaxWaves, LEAN ? 4 : 2) void k_track1_p8(En
   const int npts = TEAM ? min(a.team_q, npts_all - lo) : npts_all;
   TeamCtx tc;
   if constexpr (TEAM) {
-    tc.mail = a.team_mail + (size_t)b * 2 * team * kTeamSlot;
+    tc.mail = a.ex.mail + team_mail_box(b, team);
     tc.team = team;
     tc.part = part;
-    tc.tag0 = a.team_tag0;
+    tc.tag0 = a.ex.tag0;
     tc.seq = 0;
-    tc.limit = a.team_limit;
-    tc.err = a.team_err;
-    tc.dead = 0;
-    tc.mute = (a.team_mute != 0 && part + 1 == a.team_mute) ? 1 : 0;
+    tc.poll = XchgPoll{a.ex.limit, a.ex.err, 0};
+    tc.mute = (a.ex.mute != 0 && part + 1 == a.ex.mute) ? 1 : 0;
   }
   SolveOpts sopt = solve_opts(e);
   sopt.robust = 0;  // the host routes every behaviour-changing option to the any-size form: no compose / log code here
@@ -918,7 +895,6 @@ int track1_team_size(int maxpts, int target) {
   const int q = track1_team_q(maxpts, target);
   return std::max(1, (maxpts + q - 1) / q);
 }
-size_t track1_team_mail_bytes(int B, int team) { return sizeof(unsigned long long) * (size_t)B * 2 * team * kTeamSlot; }
 
 // blob (may be NULL): [ProbState x B][PlaneSet x B x nlev] for the fused begin; host_st (may be NULL): pinned mirror;
 // project_here (without a blob): the records and the plane table have been uploaded, the launch projects (step 3) itself;
@@ -932,11 +908,7 @@ hipError_t launch_track1(const EngineDev &e, const LevelCam *cams, int maxpts, i
   const int team = (tm && p8 && tm->team > 1) ? tm->team : 1;
   a.team = team;
   a.team_q = team > 1 ? tm->q : 0x7fffffff;
-  a.team_tag0 = team > 1 ? tm->x.tag0 : 0;
-  a.team_limit = team > 1 ? tm->x.limit : 0;
-  a.team_mail = team > 1 ? tm->x.mail : nullptr;
-  a.team_err = team > 1 ? tm->x.err : nullptr;
-  a.team_mute = team > 1 ? tm->x.mute : 0;
+  a.ex = team > 1 ? tm->x : Exchange{};
   if (team > 1) {
     if (team > kTeamMax || !tm->x.mail || !tm->x.err || (long long)tm->q * team < maxpts) return hipErrorInvalidValue;
     maxpts = std::min(maxpts, tm->q);  // LDS records and patches: this workgroup's share only
