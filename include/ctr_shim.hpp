@@ -227,6 +227,44 @@ class StaticSplitClass {
   int64_t n_, npairs_;
 };
 
+// One camera per frame of a track window (misc_src/run_test_OF_track.py:374-411, ictr_camfit_* in include/ictr.h):
+// Levenberg-Marquardt on the reprojection error of the same points in every frame, one read-back at the end.
+class CamFitClass {
+ public:
+  CamFitClass(int64_t n, int64_t nframes) : h_(nullptr), n_(n), nframes_(nframes) {
+    check(ictr_camfit_create(&h_, n, nframes), "CamFitClass");
+  }
+  ~CamFitClass() { ictr_camfit_destroy(h_); }
+  CamFitClass(const CamFitClass &) = delete;
+  CamFitClass &operator=(const CamFitClass &) = delete;
+  void SetPoints(const double *X /* [3][n] */) { check(ictr_camfit_set_points(h_, X), "SetPoints"); }
+  void SetObservations(const double *xy /* [nframes][2][n] */) {
+    check(ictr_camfit_set_observations(h_, xy), "SetObservations");
+  }
+  void SetMask(const uint64_t *words /* [Words()] or NULL: every point */) { check(ictr_camfit_set_mask(h_, words), "SetMask"); }
+  void SetCamera(const double *fc, const double *cc) { check(ictr_camfit_set_camera(h_, fc, cc), "SetCamera"); }
+  // the schedule of triang.c:327
+  void Run(const double *G0 /* [nframes][12] */, int32_t noiter = 20, double damp_init = 2.0, double damp_fct = 10.0,
+           double minres = 1e-5, double maxdamp = 1e10, void *hip_stream = nullptr) {
+    check(ictr_camfit_run(h_, G0, noiter, damp_init, damp_fct, minres, maxdamp, hip_stream), "Run");
+  }
+  // per frame: G [12], cost, damp, iters, status (ICTR_CAMFIT_*), n; any may be NULL
+  void Wait(double *G, double *cost, double *damp, int32_t *iters, int32_t *status, int64_t *n) {
+    check(ictr_camfit_wait(h_, G, cost, damp, iters, status, n), "Wait");
+  }
+  // per frame the mean reprojection distance at the poses G with dt [3] (NULL: zero) added to every translation
+  void Reproject(const double *G, const double *dt, double *mean_err, int64_t *n = nullptr) {
+    check(ictr_camfit_reproj(h_, G, dt, mean_err, n), "Reproject");
+  }
+  int64_t Words() const { return (n_ + 63) / 64; }
+  int64_t Points() const { return n_; }
+  int64_t Frames() const { return nframes_; }
+
+ private:
+  ictr_camfit *h_;
+  int64_t n_, nframes_;
+};
+
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one
 // read-back at the end. Mode: ICTR_TRIANG_DLT / _GN / _LM / _DEPTH.
 class TriangClass {

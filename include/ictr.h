@@ -551,6 +551,49 @@ int ictr_fsplit_get_kernel_times(const ictr_fsplit *r, float *ms);
 int ictr_debug_fsplit_trials(ictr_fsplit *r, double thresh, uint64_t seed, int64_t first_trial, int64_t count,
                              int32_t *status, int32_t *draws, double *F, uint32_t *cnt);
 
+/* ------------------------------------------------------------------ camera fit (misc_src/run_test_OF_track.py:374-411)
+ * "Fit cameras": one pose per frame of a track window, each by Levenberg-Marquardt on the mean squared reprojection
+ * residual of the same N points (DESIGN.md §4 "Camera fit"); nframes independent fits run side by side:
+ *   - x_cam = R X + t, pinhole fc, cc without distortion; an observation counts in a frame iff its mask bit is set and
+ *     its three point and two pixel coordinates are finite (no depth test); c = sum(rx^2 + ry^2) / n;
+ *   - per pass H (21), b (6), s summed in an order that is a function of N alone (csrc/ictr_camfit_hd.h);
+ *     (H + damp diag(H)) d = b by LDL^T without pivoting; the pose moves by the Cayley retraction of d;
+ *   - schedule of triang.c:327 (noiter 20, damp_init 2, damp_fct 10, minres 1e-5, maxdamp 1e10): a trial pose is
+ *     accepted iff its cost is finite and smaller; stops, tested in this order: cost <= minres or an accepted improvement
+ *     <= minres (converged), noiter iterations, damp >= maxdamp.
+ * All f64 in a fixed order: the same bits on every run. N: 1 .. 2^22, nframes: 1 .. 4096, noiter: 0 .. 1000. */
+#define ICTR_CAMFIT_CONVERGED 0
+#define ICTR_CAMFIT_NOITER 1
+#define ICTR_CAMFIT_MAXDAMP 2
+#define ICTR_CAMFIT_FEW_OBS 3          /* fewer than 3 counted observations: G = G0 */
+#define ICTR_CAMFIT_START_NOT_FINITE 4 /* the cost at G0 is not finite: G = G0 */
+typedef struct ictr_camfit ictr_camfit;
+int ictr_camfit_create(ictr_camfit **out, int64_t n, int64_t nframes);
+void ictr_camfit_destroy(ictr_camfit *r);
+/* X: f64 [3][N]; xy: f64 [nframes][2][N] (pixels); words: the inlier words of ictr_fsplit_wait (bit j % 64 of word j / 64
+ * = point j), NULL: every point; fc[2] (finite, not 0), cc[2]. All refused (ICTR_ERR_STATE) while a run is in flight. */
+int ictr_camfit_set_points(ictr_camfit *r, const double *X);
+int ictr_camfit_set_observations(ictr_camfit *r, const double *xy);
+int ictr_camfit_set_mask(ictr_camfit *r, const uint64_t *words);
+int ictr_camfit_set_camera(ictr_camfit *r, const double *fc, const double *cc);
+/* enqueues 2 + 2 noiter launches on hip_stream (NULL: the null stream) and returns. G0 [nframes][12]: row-major [R | t]
+ * start poses (finite). Needs damp_init > 0, damp_fct > 1, minres >= 0, all finite, and maxdamp > 0. */
+int ictr_camfit_run(ictr_camfit *r, const double *G0, int32_t noiter, double damp_init, double damp_fct, double minres,
+                    double maxdamp, void *hip_stream);
+/* waits for the last run; any output may be NULL. Per frame: G [12], cost, damp, iters (solves tried), status
+ * (ICTR_CAMFIT_*), n (counted observations). */
+int ictr_camfit_wait(ictr_camfit *r, double *G, double *cost, double *damp, int32_t *iters, int32_t *status, int64_t *n);
+/* per frame the mean of sqrt(rx^2 + ry^2) over the counted observations at the poses G [nframes][12], with dt[3] (NULL:
+ * zero) added to every translation, and their number n (may be NULL); NaN where n is 0. Synchronous, null stream. */
+int ictr_camfit_reproj(ictr_camfit *r, const double *G, const double *dt, double *mean_err, int64_t *n);
+/* on: the next runs record device time stamps around their launches; get: ms[2] of the last waited run spent in
+ * k_camfit_pass and k_camfit_step */
+int ictr_camfit_set_timing(ictr_camfit *r, int on);
+int ictr_camfit_get_kernel_times(const ictr_camfit *r, float *ms);
+/* inspection: k_camfit_pass at the poses G [nframes][12] and the ordered sum of k_camfit_step alone, on the null stream.
+ * Per frame: n, s, H [21] (upper triangle, row-major), b [6]. */
+int ictr_debug_camfit_pass(ictr_camfit *r, const double *G, int64_t *n, double *s, double *H, double *b);
+
 /* ------------------------------------------------------------------ multi-view point triangulation (misc_src/triang.c)
  * A track set (10^4 .. 10^5 points, 2 .. 30 views each) triangulated in one launch, one lane per point, with the
  * arithmetic of the reference routine of each mode: every product and sum in f32, in its order and grouping, so the

@@ -15,6 +15,9 @@ from .tracker import (CamClass, OdometerClass, PoseClass, Pyramid, TrackBatch, d
 from .ransac import fit_cameras_odom, sample_poses, sample_poses_host  # noqa: F401
 from .fsplit import (StaticSplitter, epiline_dist, fit_f8, pairs_from_stereo_tracks, pairs_from_tracks, split_static,  # noqa: F401
                      split_static_host)
+from .camfit import (CameraFitter, depth_from_disparity, fit_cameras, fit_cameras_host,  # noqa: F401
+                     observations_from_stereo_tracks, points_from_first_view, reprojection_errors,
+                     reprojection_errors_host)
 from .triang import Triangulator, cameras_from_poses, rays_from_first_view, tracks_from_oftrack, triangulate_tracks  # noqa: F401
 from .sequence import SequenceTracker, select_points, track_sequence, track_sequence_host_loop  # noqa: F401
 

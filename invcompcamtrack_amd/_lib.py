@@ -229,6 +229,18 @@ SIGNATURES = {
     "ictr_fsplit_get_kernel_times": (C.c_int, [VP, FP]),
     "ictr_debug_fsplit_trials": (C.c_int, [VP, C.c_double, C.c_uint64, I64, I64, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), DP, C.POINTER(C.c_uint32)]),
+    "ictr_camfit_create": (C.c_int, [C.POINTER(VP), I64, I64]),
+    "ictr_camfit_destroy": (None, [VP]),
+    "ictr_camfit_set_points": (C.c_int, [VP, DP]),
+    "ictr_camfit_set_observations": (C.c_int, [VP, DP]),
+    "ictr_camfit_set_mask": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "ictr_camfit_set_camera": (C.c_int, [VP, DP, DP]),
+    "ictr_camfit_run": (C.c_int, [VP, DP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, VP]),
+    "ictr_camfit_wait": (C.c_int, [VP, DP, DP, DP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(I64)]),
+    "ictr_camfit_reproj": (C.c_int, [VP, DP, DP, DP, C.POINTER(I64)]),
+    "ictr_camfit_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_camfit_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_debug_camfit_pass": (C.c_int, [VP, DP, C.POINTER(I64), DP, DP, DP]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),
