@@ -265,6 +265,54 @@ class CamFitClass {
   int64_t n_, nframes_;
 };
 
+// The checked stereo track window (misc_src/run_test_OF_track.py:170-223, ictr_stereotrack_* in include/ictr.h): Open with
+// the stereo fields of frame 0, Advance once per later frame, Count, Read. A field is an ictr_field; the helpers below
+// fill one.
+class StereoTrackClass {
+ public:
+  StereoTrackClass(int w, int h, int bsize, double th_ratio = 0.2, double th_abs = 1.0) : h_(nullptr), bsize_(bsize) {
+    check(ictr_stereotrack_create(&h_, w, h, bsize, th_ratio, th_abs), "StereoTrackClass");
+  }
+  ~StereoTrackClass() { ictr_stereotrack_destroy(h_); }
+  StereoTrackClass(const StereoTrackClass &) = delete;
+  StereoTrackClass &operator=(const StereoTrackClass &) = delete;
+  // a float32 plane [h][w] (moves x only) or interleaved flow [h][w][2], in host or device memory; sign +1 or -1
+  static ictr_field Plane(const float *p, int sign = 1, bool on_device = false) {
+    ictr_field f = {ICTR_FIELD_PLANE, sign, on_device ? 1 : 0, 1, p};
+    return f;
+  }
+  static ictr_field Flow(const float *p, int sign = 1, bool on_device = false, bool x_only = false) {
+    ictr_field f = {ICTR_FIELD_FLOW, sign, on_device ? 1 : 0, x_only ? 1 : 0, p};
+    return f;
+  }
+  // a flow grid that holds a field; x_only for the stereo pair
+  static ictr_field Grid(const ictr_flowgrid *g, bool x_only = false, int sign = 1) {
+    ictr_field f = {ICTR_FIELD_GRID, sign, 1, x_only ? 1 : 0, g};
+    return f;
+  }
+  // xy0 [n][2] or NULL: every pixel (n = 0). lr: the field that moves a left point to the right frame (the script's
+  // -imgs_d[fr][0] is Plane(p, -1)), rl: the way back
+  void Open(const double *xy0, int64_t n, const ictr_field &lr, const ictr_field &rl) {
+    check(ictr_stereotrack_open(h_, xy0, n, &lr, &rl), "Open");
+  }
+  void Advance(const ictr_field &l_fwd, const ictr_field &l_bwd, const ictr_field &r_fwd, const ictr_field &r_bwd,
+               const ictr_field &lr_next, const ictr_field &rl_next) {
+    check(ictr_stereotrack_advance(h_, &l_fwd, &l_bwd, &r_fwd, &r_bwd, &lr_next, &rl_next), "Advance");
+  }
+  int64_t Count() {
+    int64_t m = 0;
+    check(ictr_stereotrack_count(h_, &m), "Count");
+    return m;
+  }
+  // xy_t [Count()][4][bsize], rows [Count()]; either may be NULL
+  void Read(double *xy_t, int64_t *rows) { check(ictr_stereotrack_read(h_, xy_t, rows), "Read"); }
+  int Frames() const { return bsize_; }
+
+ private:
+  ictr_stereotrack *h_;
+  int bsize_;
+};
+
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one
 // read-back at the end. Mode: ICTR_TRIANG_DLT / _GN / _LM / _DEPTH.
 class TriangClass {

@@ -692,6 +692,49 @@ int ictr_pointtrack_frcounter(const ictr_pointtrack *t, int64_t *frcounter);
 int ictr_pointtrack_read_block(ictr_pointtrack *t, int64_t block, float *tracks, uint8_t *valid, double *absmovement,
                                int *count);
 
+/* ---------------------------------------------------------------- stereo track window (ictr_stereotrack.hip)
+ * misc_src/run_test_OF_track.py:170-223 on the device, equal to stereotrack.stereo_track_window_host bit for bit
+ * (DESIGN.md §4 "Stereo track window"): start points are sent to the right frame through the disparity and checked back
+ * (open), then carried through the left and right flows of one frame pair per advance with the script's eight tests; a
+ * point that fails once is dead. count / read compact the survivors in start order into xy_t [M][4][bsize]. One step's
+ * fields are resident at a time: device memory is the window state [bsize][4][N] f64 and does not grow with the sequence.
+ * Everything is enqueued on the null stream; the host waits in count (for M) and in read (for the M rows) only. */
+
+/* a displacement field: a kind, an exact sign (+1 or -1; the script's -imgs_d is sign -1) and where it lives */
+#define ICTR_FIELD_PLANE 0 /* float32 [h][w], moves x only (a disparity) */
+#define ICTR_FIELD_FLOW 1  /* float32 [h][w][2] interleaved (u, v) */
+#define ICTR_FIELD_GRID 2  /* an ictr_flowgrid* of the window's size that holds a field; its dense field is not formed */
+typedef struct ictr_field {
+  int32_t kind;      /* ICTR_FIELD_* */
+  int32_t sign;      /* +1 or -1 */
+  int32_t on_device; /* plane, flow: data is device memory (read when the step runs) instead of host memory (copied
+                        before the call returns) */
+  int32_t x_only;    /* flow, grid: the first component alone moves the point (the stereo pair); a plane always is */
+  const void *data;
+} ictr_field;
+/* float64 fields have no kind: a caller that holds them converts exactly or not at all. */
+
+typedef struct ictr_stereotrack ictr_stereotrack;
+/* 2 <= w, h; 1 <= bsize <= 256 */
+int ictr_stereotrack_create(ictr_stereotrack **out, int w, int h, int bsize, double th_ratio, double th_abs);
+void ictr_stereotrack_destroy(ictr_stereotrack *t);
+/* frame 0. xy0: f64 [n][2] start points in host memory, or NULL: every pixel in the script's meshgrid order (n = w h, or
+ * 0). 1 <= n <= 2^24. lr, rl: the x-only fields left -> right and right -> left of frame 0. Starts a new window. */
+int ictr_stereotrack_open(ictr_stereotrack *t, const double *xy0, int64_t n, const ictr_field *lr, const ictr_field *rl);
+/* frame fr = 1 .. bsize-1, in order: the four two-component flows of the pair fr-1 -> fr and the x-only fields of frame
+ * fr; ICTR_ERR_STATE before open and after bsize-1 calls */
+int ictr_stereotrack_advance(ictr_stereotrack *t, const ictr_field *l_fwd, const ictr_field *l_bwd,
+                             const ictr_field *r_fwd, const ictr_field *r_bwd, const ictr_field *lr_next,
+                             const ictr_field *rl_next);
+/* after the last advance: the ordered compaction (counts per workgroup, a scan, the rows); *m = survivors */
+int ictr_stereotrack_count(ictr_stereotrack *t, int64_t *m);
+/* after count: xy_t f64 [m][4][bsize] and rows int64 [m] (start indices, ascending); either may be NULL */
+int ictr_stereotrack_read(ictr_stereotrack *t, double *xy_t, int64_t *rows);
+/* per-launch timing with HIP events; ms[2] of the window completed by read: the open and advance kernels, the
+ * compaction kernels. Both refused (ICTR_ERR_STATE) while a window is open and not read. */
+int ictr_stereotrack_set_timing(ictr_stereotrack *t, int on);
+int ictr_stereotrack_get_kernel_times(const ictr_stereotrack *t, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ from .fsplit import (StaticSplitter, epiline_dist, fit_f8, pairs_from_stereo_tra
 from .camfit import (CameraFitter, depth_from_disparity, fit_cameras, fit_cameras_host,  # noqa: F401
                      observations_from_stereo_tracks, points_from_first_view, reprojection_errors,
                      reprojection_errors_host)
+from .stereotrack import (StereoPointTracker, StereoTrackWindow, stereo_track_window,  # noqa: F401
+                          stereo_track_window_host)
 from .triang import Triangulator, cameras_from_poses, rays_from_first_view, tracks_from_oftrack, triangulate_tracks  # noqa: F401
 from .sequence import SequenceTracker, select_points, track_sequence, track_sequence_host_loop  # noqa: F401
 

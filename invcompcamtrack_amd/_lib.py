@@ -62,6 +62,12 @@ class TraceRec(C.Structure):
                 ("dp", C.c_float * 6), ("p", C.c_float * 6)]
 
 
+class Field(C.Structure):
+    """ictr_field (include/ictr.h)."""
+    _fields_ = [("kind", C.c_int32), ("sign", C.c_int32), ("on_device", C.c_int32), ("x_only", C.c_int32),
+                ("data", C.c_void_p)]
+
+
 class TriangParams(C.Structure):
     """ictr_triang_params (include/ictr.h)."""
     _fields_ = [("noiter", C.c_int32), ("minres", C.c_float), ("damp_init", C.c_float), ("damp_fct", C.c_float),
@@ -241,6 +247,14 @@ SIGNATURES = {
     "ictr_camfit_set_timing": (C.c_int, [VP, C.c_int]),
     "ictr_camfit_get_kernel_times": (C.c_int, [VP, FP]),
     "ictr_debug_camfit_pass": (C.c_int, [VP, DP, C.POINTER(I64), DP, DP, DP]),
+    "ictr_stereotrack_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "ictr_stereotrack_destroy": (None, [VP]),
+    "ictr_stereotrack_open": (C.c_int, [VP, DP, I64, C.POINTER(Field), C.POINTER(Field)]),
+    "ictr_stereotrack_advance": (C.c_int, [VP] + [C.POINTER(Field)] * 6),
+    "ictr_stereotrack_count": (C.c_int, [VP, C.POINTER(I64)]),
+    "ictr_stereotrack_read": (C.c_int, [VP, DP, C.POINTER(I64)]),
+    "ictr_stereotrack_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_stereotrack_get_kernel_times": (C.c_int, [VP, FP]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

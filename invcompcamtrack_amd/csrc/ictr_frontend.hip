@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ictr_dev.h"
+#include "ictr_flowgrid_dev.h"
 #include "ictr_launch.h"
 
 namespace ictr {
@@ -297,48 +298,7 @@ static int pyr_level0(const ictr_pyramid *p, const float **img, int *stride, int
 }
 
 // ---------------------------------------------------------------- flow grid
-struct FgDev {
-  const float *d;  // [ny][nx][2] node displacements after the fill
-  int nx, ny, step, w, h;
-};
-
-// dense_flow's field at the integer pixel (X, Y), component c: the bilinear blend of the four surrounding nodes
-__device__ __forceinline__ void fg_value(const FgDev &g, int X, int Y, float *u, float *v) {
-  const int half = g.step / 2;
-  const double fx = fmin(fmax((double)(X - half) / (double)g.step, 0.0), (double)(g.nx - 1));
-  const double fy = fmin(fmax((double)(Y - half) / (double)g.step, 0.0), (double)(g.ny - 1));
-  const double flx = floor(fx), fly = floor(fy);
-  const int x0 = (int)flx, y0 = (int)fly;
-  const int x1 = min(x0 + 1, g.nx - 1), y1 = min(y0 + 1, g.ny - 1);
-  const double ax = fx - flx, ay = fy - fly;
-  const float2 *d = reinterpret_cast<const float2 *>(g.d);
-  const float2 a = d[y0 * g.nx + x0], b = d[y0 * g.nx + x1], c = d[y1 * g.nx + x0], e = d[y1 * g.nx + x1];
-  const double topu = (double)a.x * (1 - ax) + (double)b.x * ax, botu = (double)c.x * (1 - ax) + (double)e.x * ax;
-  const double topv = (double)a.y * (1 - ax) + (double)b.y * ax, botv = (double)c.y * (1 - ax) + (double)e.y * ax;
-  *u = (float)(topu * (1 - ay) + botu * ay);
-  *v = (float)(topv * (1 - ay) + botv * ay);
-}
-
-// func_get_transf_position(xy, F[:, :, 0], F[:, :, 1]) with F = the dense field of the grid, never formed
-__device__ __forceinline__ void fg_gather(const FgDev &g, double x, double y, double *ox, double *oy) {
-  const double flx = floor(x), fly = floor(y);
-  const double nan = __builtin_nan("");
-  *ox = nan;
-  *oy = nan;
-  // NaN / out-of-range coordinates fail the range test (written positively), like the INT_MIN cast in NumPy
-  if (flx >= 0.0 && fly >= 0.0 && flx + 1.0 < (double)g.w && fly + 1.0 < (double)g.h) {
-    const int x0 = (int)flx, y0 = (int)fly;
-    const double fx = x - flx, fy = y - fly;
-    const double w0 = fx * fy, w1 = (1 - fx) * fy, w2 = fx * (1 - fy), w3 = (1 - fx) * (1 - fy);
-    float u11, v11, u01, v01, u10, v10, u00, v00;
-    fg_value(g, x0 + 1, y0 + 1, &u11, &v11);
-    fg_value(g, x0, y0 + 1, &u01, &v01);
-    fg_value(g, x0 + 1, y0, &u10, &v10);
-    fg_value(g, x0, y0, &u00, &v00);
-    *ox = x + ((double)u11 * w0 + (double)u01 * w1 + (double)u10 * w2 + (double)u00 * w3);
-    *oy = y + ((double)v11 * w0 + (double)v01 * w1 + (double)v10 * w2 + (double)v00 * w3);
-  }
-}
+// FgDev, fg_value, fg_gather: ictr_flowgrid_dev.h
 
 __global__ __launch_bounds__(kBlock) void k_fg_nodes(float *__restrict__ pts, int nx, int K, int step) {
   const int k = blockIdx.x * kBlock + threadIdx.x;
@@ -515,6 +475,12 @@ struct ictr_flowgrid {
   DevBuf<char> arena;  // everything above
 };
 static FgDev fg_dev(const ictr_flowgrid *g) { return FgDev{g->d, g->nx, g->ny, g->step, g->w, g->h}; }
+extern "C" int ictr_flowgrid_view_(const ictr_flowgrid *g, FgDev *v) {
+  if (!g || !v) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  if (!g->filled) return fail(ICTR_ERR_STATE, "flowgrid: no field yet (compute or set_nodes first)");
+  *v = fg_dev(g);
+  return ICTR_OK;
+}
 
 extern "C" void ictr_flowgrid_destroy(ictr_flowgrid *g) { delete g; }
 extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step) {

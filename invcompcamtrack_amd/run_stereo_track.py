@@ -1,0 +1,72 @@
+"""The checked stereo track window of a sequence (run_test_OF_track.py:170-223):
+
+  python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
+         [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0]
+
+listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
+Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
+(StereoPointTracker). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
+(>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
+keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
+restatement on the same fields instead (same bits; from a listfile the grids' dense fields are formed for it).
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+import numpy as np
+
+from . import io_formats as iof
+from . import stereotrack as S
+
+
+def dense_fields_of(tracker):
+    """The dense fields of a StereoPointTracker built with keep_grids=True, in the host function's layout."""
+    g = tracker.grids
+    lr = [-x["lr"].dense()[:, :, 0] for x in g]  # a left -> right grid is the script's -imgs_d[fr][0]
+    rl = [np.ascontiguousarray(x["rl"].dense()[:, :, 0]) for x in g]
+    fl = [(x["l_fwd"].dense(), x["l_bwd"].dense()) for x in g[1:]]
+    fr = [(x["r_fwd"].dense(), x["r_bwd"].dense()) for x in g[1:]]
+    return lr, rl, fl, fr
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m invcompcamtrack_amd.run_stereo_track", description=__doc__.split("\n")[0])
+    ap.add_argument("listfile")
+    ap.add_argument("output")
+    ap.add_argument("--bsize", type=int, default=14)
+    ap.add_argument("--fields")
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--psz", type=int, default=15)
+    ap.add_argument("--lv_f", type=int, default=3)
+    ap.add_argument("--step", type=int, default=4)
+    ap.add_argument("--th_ratio", type=float, default=0.2)
+    ap.add_argument("--th_abs", type=float, default=1.0)
+    a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
+    th = dict(th_ratio=a.th_ratio, th_abs=a.th_abs)
+    if a.fields:
+        with np.load(a.fields) as z:
+            b = min(a.bsize, len(z["disp_lr"]))
+            lr, rl, fl, fr = z["disp_lr"][:b], z["disp_rl"][:b], z["flow_l"], z["flow_r"]
+            xy0 = z["xy0"] if "xy0" in z else None
+        xy_t, rows = (S.stereo_track_window_host if a.host else S.stereo_track_window)(lr, rl, fl, fr, xy0=xy0, **th)
+    else:
+        pairs = [ln.split() for ln in iof.read_image_list(a.listfile)][:a.bsize]
+        if not pairs or any(len(p) != 2 for p in pairs):
+            print("the list needs a left and a right path per line", file=sys.stderr)
+            return 2
+        frames = [[np.asarray(iof.read_image_gray(fn), np.float32) for fn in p] for p in pairs]
+        h, w = frames[0][0].shape
+        t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, **th)
+        for left, right in frames:
+            t.push_frames(left, right)
+        xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()
+    np.savez(a.output, xy_t=xy_t, rows=rows)
+    print("kept %d points in %d frames" % (len(rows), xy_t.shape[2]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
