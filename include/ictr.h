@@ -461,6 +461,13 @@ int ictr_sequence_wait(ictr_sequence *s, double *poses, int32_t *npts, int32_t *
 /* inspection, after wait: per pair an order-aware 64-bit hash of the selected world indices,
  * sum over k < npts of splitmix64((k << 32) | index_k) modulo 2^64 */
 int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *out);
+/* inspection, after wait (ICTR_ERR_STATE without a completed run): what the LAST pair's selection left on the device.
+ * npts; sel[0 .. npts) the selected world indices in order (room for maxpttrack entries, the rest is not written);
+ * ms3 / varval the f64 normalisation of the selected points (0, 0, 0 and 1 without donorm); pt3d the engine's
+ * normalised f32 points, SoA X[M] Y[M] Z[M] with M = maxpttrack, zero behind npts. Neither the tracking nor the last
+ * frame's bookkeeping writes any of them. Any output may be NULL. Synchronous copies; no kernel runs. */
+int ictr_sequence_last_selection(const ictr_sequence *s, int32_t *npts, int32_t *sel, double *ms3, double *varval,
+                                 float *pt3d);
 /* workgroups per tracking launch of the last run (before the first run: the form the cap selects):
  * 1 = the single-workgroup form, > 1 = the team form */
 int ictr_sequence_last_team(const ictr_sequence *s);

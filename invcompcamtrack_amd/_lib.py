@@ -214,6 +214,7 @@ SIGNATURES = {
     "ictr_sequence_track_async": (C.c_int, [VP, DP]),
     "ictr_sequence_wait": (C.c_int, [VP, DP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ictr_sequence_selection_hashes": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "ictr_sequence_last_selection": (C.c_int, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), DP, DP, FP]),
     "ictr_sequence_last_team": (C.c_int, [VP]),
     "ictr_ransac_create": (C.c_int, [C.POINTER(VP), I64, I64]),
     "ictr_ransac_destroy": (None, [VP]),

@@ -2207,5 +2207,25 @@ extern "C" int ictr_sequence_selection_hashes(const ictr_sequence *s, uint64_t *
   return ICTR_OK;
 }
 
+// inspection: what the LAST pair's selection left on the device. d_ss (ms, varval, npts), d_sel and the engine's pt3d
+// are written by k_seq_select_finish / k_seq_select_scatter only; the tracking reads pt3d and the tail launch writes
+// ss->pose alone, so after the wait they still hold the last pair's selection. Plain copies behind a stream sync.
+extern "C" int ictr_sequence_last_selection(const ictr_sequence *s, int32_t *npts, int32_t *sel, double *ms3,
+                                            double *varval, float *pt3d) {
+  if (!s) return fail(ICTR_ERR_INVALID, "sequence_last_selection: NULL argument");
+  if (s->out.pending() || !s->out.ran()) return fail(ICTR_ERR_STATE, "sequence_last_selection: no completed run");
+  HIPCHK(hipStreamSynchronize(s->stream));
+  SeqState ss;
+  HIPCHK(hipMemcpy(&ss, s->d_ss.get(), sizeof(ss), hipMemcpyDeviceToHost));
+  const int M = s->b->M;
+  if (ss.npts < 0 || ss.npts > M) return fail(ICTR_ERR_STATE, "sequence_last_selection: %d points selected, cap %d", ss.npts, M);
+  if (npts) *npts = ss.npts;
+  if (ms3) memcpy(ms3, ss.ms, sizeof(double) * 3);
+  if (varval) *varval = ss.varval;
+  if (sel && ss.npts > 0) HIPCHK(hipMemcpy(sel, s->d_sel.get(), sizeof(int) * (size_t)ss.npts, hipMemcpyDeviceToHost));
+  if (pt3d) HIPCHK(hipMemcpy(pt3d, s->b->d_pt3d.get(), sizeof(float) * 3 * (size_t)M, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+
 // workgroups per tracking launch of the last run (before the first run: the form the cap selects)
 extern "C" int ictr_sequence_last_team(const ictr_sequence *s) { return s ? s->b->plan.team : 0; }

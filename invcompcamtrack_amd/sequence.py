@@ -44,10 +44,10 @@ def select_points(pts3d_world, p, cam, stride=10, cap=None):
     X = np.asarray(pts3d_world, np.float64).reshape(3, -1)
     fx, fy, cx, cy, w, h = _cam_params(cam)
     G = se3_exp_d(p).reshape(-1)
-    xc = G[0] * X[0] + G[1] * X[1] + G[2] * X[2] + G[3]
-    yc = G[4] * X[0] + G[5] * X[1] + G[6] * X[2] + G[7]
-    zc = G[8] * X[0] + G[9] * X[1] + G[10] * X[2] + G[11]
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore"):  # (a NaN or infinite coordinate fails every comparison)
+        xc = G[0] * X[0] + G[1] * X[1] + G[2] * X[2] + G[3]
+        yc = G[4] * X[0] + G[5] * X[1] + G[6] * X[2] + G[7]
+        zc = G[8] * X[0] + G[9] * X[1] + G[10] * X[2] + G[11]
         u = fx * xc / zc + cx
         v = fy * yc / zc + cy
     keep = np.nonzero((u >= 1.0) & (u <= w) & (v >= 1.0) & (v <= h))[0]
@@ -147,6 +147,20 @@ class SequenceTracker:
         out = np.zeros(max(self._n - 1, 1), np.uint64)
         check(_lib.load().ictr_sequence_selection_hashes(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
+
+    def last_selection(self):
+        """Inspection, after wait: what the last pair's selection left on the device -- dict(npts int, sel (npts,) int32
+        world indices, ms (3,) f64, varval f64, pt3d (3, M) f32 with M = op.maxpttrack: the normalised points, zero
+        behind npts)."""
+        M = int(self.op.maxpttrack)
+        n = C.c_int32(0)
+        sel = np.full(M, -1, np.int32)
+        ms = np.zeros(3, np.float64)
+        vv = C.c_double(0.0)
+        pt3d = np.zeros((3, M), np.float32)
+        check(_lib.load().ictr_sequence_last_selection(self._h, C.byref(n), sel.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       dp(ms), C.byref(vv), pt3d.ctypes.data_as(_lib.FP)))
+        return dict(npts=int(n.value), sel=sel[:n.value].copy(), ms=ms, varval=float(vv.value), pt3d=pt3d)
 
 
 def track_sequence(cam, op, pts3d_world, frames, p0, stride=10, stream=None):

@@ -167,3 +167,184 @@ def test_cpu_tensor_frames_are_copied_not_borrowed(monkeypatch):
     st.track_async(frames.numpy(), np.zeros(6))
     assert fake.frames_calls == [(3, 8, 6, 0), (3, 8, 6, 0)]
     st._h = None  # (nothing to destroy)
+
+
+# ---------------------------------------------------------------- the selection case table (tests/seq_select_cases.py)
+# Conditions on the INPUTS of tests/test_gpu_sequence_select.py, decided by select_points alone: every case reaches the
+# workgroup bounds, cap limits and cull edges it is in the table for.
+import math  # noqa: E402
+
+import seq_select_cases as sc  # noqa: E402
+
+
+def test_identity_pose_gives_the_identity_exactly():
+    from invcompcamtrack_amd._hostmath import se3_exp_d
+    np.testing.assert_array_equal(se3_exp_d(np.zeros(6)), np.eye(4)[:3])
+
+
+@pytest.mark.parametrize("case", list(sc.TABLE))
+def test_case_selections_contain_the_workgroups_they_name(case):
+    wname, _, reach = sc.TABLE[case]
+    wd = sc.world(wname)
+    got = set()
+    for _, stride, _, cap in sc.runs(case):
+        sel = sc.expected(case, stride, cap)
+        assert sel.size <= cap
+        got |= set((sel // sc.C).tolist())
+    assert reach <= got, (sorted(reach), sorted(got))
+    assert max(reach, default=0) < sc.nblk(wd["X"].shape[1])
+    assert bool(reach) == (case != "none") and (got or case == "none")
+    if wd["keep"] is not None:  # the world keeps exactly the points it was built to keep
+        np.testing.assert_array_equal(sc.survivors(case), np.nonzero(wd["keep"])[0])
+
+
+def test_case_tail1_and_edge_pairs():
+    assert sc.world("tail1")["X"].shape[1] == sc.C + 1 and sc.nblk(sc.C + 1) == 2
+    assert sc.expected("tail1", 1, 2048).tolist() == list(range(2048))          # the cap binds inside workgroup 0
+    assert sc.expected("tail1", 1, 8192).tolist() == list(range(sc.C + 1))      # never: the last workgroup's one point
+    assert sc.expected("edge_pairs", 1, 2048).tolist() == [sc.C - 1, sc.C, 2 * sc.C - 1, 2 * sc.C]
+    counts = np.bincount(sc.survivors("edge_pairs") // sc.C, minlength=3)
+    assert np.cumsum(counts)[:2].tolist() == [1, 3]                              # `before` of workgroups 1 and 2
+
+
+def test_case_phase_carries_the_stride_over_two_bounds():
+    nw = sc.world("phase")["X"].shape[1]
+    assert nw == 2 * sc.C + 100
+    for _, stride, _, cap in sc.runs("phase"):
+        sel = sc.expected("phase", stride, cap)
+        np.testing.assert_array_equal(sel, np.arange(0, nw, stride)[:cap])
+        if stride >= nw:
+            assert sel.tolist() == [0]                                           # stride >= total keeps rank 0 only
+    for stride in (3, 7):  # the first rank of workgroups 1 and 2 is no multiple of the stride: the phase is carried
+        assert sc.C % stride != 0 and (2 * sc.C) % stride != 0
+        sel = sc.expected("phase", stride, 4096)
+        assert {0, 1, 2} <= set((sel // sc.C).tolist())
+
+
+def test_case_cap_at_bound_limits():
+    for _, stride, _, cap in sc.runs("cap_at_bound"):
+        sel = sc.expected("cap_at_bound", stride, cap)
+        assert cap % 4 == 0 and cap * stride == sc.CAP_LIMITS[(stride, cap)]
+        assert len(sel) == cap
+        assert len(sc.expected("cap_at_bound", stride, 1 << 30)) > cap          # the uncapped list is longer
+        assert sel[-1] == (cap - 1) * stride
+    lim = sorted(set(sc.CAP_LIMITS.values()))
+    assert lim == [sc.C, sc.C + 4, 4 * 1366, 2 * sc.C + 1780]
+    assert sc.expected("cap_at_bound", 1366, 4)[-1] == sc.C + 2                  # the last selected point: workgroup 1
+    assert sc.expected("cap_at_bound", 1, 4100)[-1] == sc.C + 3
+    assert sc.expected("cap_at_bound", 1, 4096)[-1] == sc.C - 1                  # the limit at the end of workgroup 0
+    assert sc.expected("cap_at_bound", 9, 1108)[-1] // sc.C == 2                 # mid workgroup 2
+
+
+def test_case_holes_slots_sparse():
+    s = sc.survivors("holes")
+    counts = np.bincount(s // sc.C, minlength=5)
+    assert sc.world("holes")["X"].shape[1] == 4 * sc.C + 613 and 613 % 64 != 0
+    assert counts[0] == 0 and counts[2] == 0 and counts[1] > 1000 and counts[3] > 1000 and counts[4] > 100
+    s = sc.survivors("slots")
+    slot = s // 64                                                               # (workgroup, step, wave) in world order
+    assert slot.tolist() == list(range(2 * sc.C // 64))                          # exactly one per slot
+    lanes = (s % 64).reshape(2, 64)
+    assert all(sorted(l.tolist()) == list(range(64)) for l in lanes)             # each at a different lane
+    s = sc.survivors("sparse")
+    counts = np.bincount(s // sc.C, minlength=6)
+    assert sc.world("sparse")["X"].shape[1] == 5 * sc.C + 613
+    assert 100 < s.size < 400 and (counts > 0).all()
+    masks = np.bincount(s // 64, minlength=sc.nblk(5 * sc.C + 613) * 64)
+    assert (masks == 0).sum() > 200                                              # many (step, wave) slots count zero
+
+
+def test_case_bounds_keeps_exactly_the_points_on_a_bound():
+    sp, kp = sc.bounds_specials()
+    assert sp.shape[1] == 15 and kp.sum() == 7
+    got = sq.select_points(sp, sc.P_ZERO, sc.CAM_ID, 1)
+    np.testing.assert_array_equal(got, np.nonzero(kp)[0])
+    np.testing.assert_array_equal(got, [0, 1, 2, 3, 8, 9, 13])                   # four bounds, two corners, Z < 0 inside
+    # one ulp outside is not on the bound
+    assert sp[0, 4] * 32 < 1.0 and sp[0, 5] * 32 > sc.W and sp[1, 6] * 32 < 1.0 and sp[1, 7] * 32 > sc.H
+    wd = sc.world("bounds")
+    s = sc.survivors("bounds")
+    np.testing.assert_array_equal(s, np.nonzero(wd["keep"])[0])
+    assert s.size == 6 * 7
+    ends = set()
+    for blk in range(3):
+        head, tail = wd["keep"][blk * sc.C:blk * sc.C + 15], wd["keep"][blk * sc.C + sc.C - 15:(blk + 1) * sc.C]
+        assert head.sum() == 7 and tail.sum() == 7
+        assert wd["keep"][blk * sc.C + 15:blk * sc.C + sc.C - 15].sum() == 0
+        ends |= {(blk, 0, bool(head[0])), (blk, 1, bool(tail[-1]))}
+    assert {e[2] for e in ends} == {True, False}   # first / last lanes of a workgroup: kept in some, dropped in others
+
+
+@pytest.mark.parametrize("case", ["many_wg_30", "many_wg_01"])
+def test_case_many_wg_takes_a_second_trip_through_the_prefix_loop(case):
+    nw = sc.world(case)["X"].shape[1]
+    assert nw == 257 * sc.C + 5 and nw // sc.C == 257       # 257 full workgroups and one of five points
+    assert sc.nblk(nw) == 258 and sc.nblk(nw) > sc.BLOCK    # thread tid of seq_prefix also adds cnt[tid + 256]
+    counts = np.bincount(sc.survivors(case) // sc.C, minlength=258)
+    assert counts[256] > 0 and counts[257] > 0
+    frac = sc.survivors(case).size / nw
+    assert abs(frac - (0.3 if case == "many_wg_30" else 0.001)) < 0.1 * (0.3 if case == "many_wg_30" else 0.001)
+    assert sc.expected(case, 1, 2048).size == (2048 if case == "many_wg_30" else sc.survivors(case).size)
+
+
+def test_case_general_has_no_point_on_a_bound():
+    from seq_scene import bound_margin
+    wd = sc.world("general")
+    assert wd["X"].shape[1] == 3 * sc.C + 37 and np.abs(wd["p0"]).min() > 0
+    assert bound_margin(wd["X"], wd["p0"], wd["cam"]) > 1e-6
+    s = sc.survivors("general")
+    assert 0.1 < s.size / wd["X"].shape[1] < 0.9
+    np.testing.assert_array_equal(s, script_select(wd["X"], wd["p0"], wd["cam"], 1))
+
+
+def test_kept_points_of_the_identity_worlds_are_well_inside():
+    """A kept filler point projects at least half a pixel inside the view and a dropped one far outside, so that only
+    the `bounds` case decides anything on a bound."""
+    for case, (wname, _, _) in sc.TABLE.items():
+        wd = sc.world(wname)
+        if wd["keep"] is None or case == "bounds":
+            continue
+        X = wd["X"]
+        u, v = 32.0 * X[0] / X[2], 32.0 * X[1] / X[2]
+        k = wd["keep"]
+        assert not k.any() or u[k].min() > 1.5 and u[k].max() < sc.W - 0.5 and v[k].min() > 1.5 and v[k].max() < sc.H - 0.5
+        assert k.all() or u[~k].min() > 10 * sc.W
+
+
+@pytest.mark.parametrize("case,stride,cap", [("phase", 3, 4096), ("holes", 1, 4096), ("sparse", 10, 2048),
+                                             ("edge_pairs", 1, 2048), ("many_wg_30", 1000, 2048),
+                                             ("general", 1, 4096)])
+def test_finish_sums_restatement_against_fsum(case, stride, cap):
+    """The restated order (256 strided partial sums, then the halving tree) against exactly rounded sums. Any order of
+    n f64 additions is within (n - 1) u sum|terms| of the exact sum, u = 2^-53 (Higham, Accuracy and Stability of
+    Numerical Algorithms, eq. 4.4 to first order), and fsum rounds the exact sum once; so the means differ by at most
+    n 2^-53 sum|terms| / n. varval's terms are formed about the restated mean, itself off by that much, hence twice the
+    bound there. The bound is derived, not measured: it guards the restatement against a misreading of the kernel's
+    order (a sum that skips or repeats a term misses it by orders of magnitude), not the other way round."""
+    wd = sc.world(sc.TABLE[case][0])
+    sel = sc.expected(case, stride, cap)
+    n = sel.size
+    assert n > 0
+    ms, varval = sc.finish_sums(wd["X"], sel)
+    P = wd["X"][:, sel]
+    u = 2.0 ** -53
+    ms_ref = np.array([math.fsum(P[c]) / n for c in range(3)])
+    for c in range(3):
+        assert abs(ms[c] - ms_ref[c]) <= n * u * math.fsum(np.abs(P[c])) / n
+    terms = (P[0] - ms_ref[0]) ** 2 + (P[1] - ms_ref[1]) ** 2 + (P[2] - ms_ref[2]) ** 2
+    assert abs(varval - math.fsum(terms) / n) <= 2 * n * u * math.fsum(terms) / n
+    if n > 1:
+        assert varval > 0
+
+
+def test_finish_sums_order_is_the_strided_one():
+    """Terms chosen so that the order shows: thread 0 adds 1e16, 1, -1e16 (its 256-strided terms) left to right."""
+    t = np.zeros(3 * 256)
+    t[0], t[256], t[512] = 1e16, 1.0, -1e16
+    t[1] = 3.0
+    assert sc._kernel_order_sum(t) == 3.0        # (1e16 + 1) - 1e16 = 0 in thread 0; thread 1 holds 3
+    t[256], t[257] = 0.0, 1.0                    # now the 1 is thread 1's: 3 + 1, and thread 0 cancels exactly
+    assert sc._kernel_order_sum(t) == 4.0
+    t2 = np.zeros(256)
+    t2[0], t2[128], t2[1] = 1e16, -1e16, 1.0     # the tree's first level adds slot 128 onto slot 0
+    assert sc._kernel_order_sum(t2) == 1.0
