@@ -200,6 +200,8 @@ class RansacClass {
   int64_t n_, smax_;
 };
 
+class StereoTrackClass;
+
 // Static / moving split of a track window (misc_src/run_test_OF_track.py:309-343, ictr_fsplit_* in include/ictr.h): RANSAC
 // over 8-point fundamental matrices of several view pairs of the same points, one read-back at the end.
 class StaticSplitClass {
@@ -211,6 +213,9 @@ class StaticSplitClass {
   StaticSplitClass(const StaticSplitClass &) = delete;
   StaticSplitClass &operator=(const StaticSplitClass &) = delete;
   void SetPairs(const double *xy /* [npairs][4][n]: xa, ya, xb, yb */) { check(ictr_fsplit_set_pairs(h_, xy), "SetPairs"); }
+  // the view pairs of a counted window, written on the device (needs n = Count(), npairs = 2 (Frames() / 2))
+  inline void SetPairsFromWindow(const StereoTrackClass &win);
+  ictr_fsplit *Handle() const { return h_; }
   void Run(int64_t ntrials, double thresh, uint64_t seed = 0, void *hip_stream = nullptr) {
     check(ictr_fsplit_run(h_, ntrials, thresh, seed, hip_stream), "Run");
   }
@@ -243,6 +248,13 @@ class CamFitClass {
   }
   void SetMask(const uint64_t *words /* [Words()] or NULL: every point */) { check(ictr_camfit_set_mask(h_, words), "SetMask"); }
   void SetCamera(const double *fc, const double *cc) { check(ictr_camfit_set_camera(h_, fc, cc), "SetCamera"); }
+  // points (after SetCamera; baseline: P1[0, 3] of the script) and one side's observations of a counted window, written
+  // on the device (needs n = Count(), nframes = Frames()); the inlier words of a split's last run, waited for or in flight
+  inline void SetPointsFromWindow(const StereoTrackClass &win, double baseline);
+  inline void SetObservationsFromWindow(const StereoTrackClass &win, bool right = false);
+  void SetMaskFromSplit(const StaticSplitClass &split, void *hip_stream = nullptr) {
+    check(ictr_camfit_set_mask_from_fsplit(h_, split.Handle(), hip_stream), "SetMaskFromSplit");
+  }
   // the schedule of triang.c:327
   void Run(const double *G0 /* [nframes][12] */, int32_t noiter = 20, double damp_init = 2.0, double damp_fct = 10.0,
            double minres = 1e-5, double maxdamp = 1e10, void *hip_stream = nullptr) {
@@ -307,11 +319,22 @@ class StereoTrackClass {
   // xy_t [Count()][4][bsize], rows [Count()]; either may be NULL
   void Read(double *xy_t, int64_t *rows) { check(ictr_stereotrack_read(h_, xy_t, rows), "Read"); }
   int Frames() const { return bsize_; }
+  const ictr_stereotrack *Handle() const { return h_; }
 
  private:
   ictr_stereotrack *h_;
   int bsize_;
 };
+
+inline void StaticSplitClass::SetPairsFromWindow(const StereoTrackClass &win) {
+  check(ictr_fsplit_set_pairs_from_window(h_, win.Handle()), "SetPairsFromWindow");
+}
+inline void CamFitClass::SetPointsFromWindow(const StereoTrackClass &win, double baseline) {
+  check(ictr_camfit_set_points_from_window(h_, win.Handle(), baseline), "SetPointsFromWindow");
+}
+inline void CamFitClass::SetObservationsFromWindow(const StereoTrackClass &win, bool right) {
+  check(ictr_camfit_set_observations_from_window(h_, win.Handle(), right ? 1 : 0), "SetObservationsFromWindow");
+}
 
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one
 // read-back at the end. Mode: ICTR_TRIANG_DLT / _GN / _LM / _DEPTH.

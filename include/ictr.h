@@ -742,6 +742,37 @@ int ictr_stereotrack_read(ictr_stereotrack *t, double *xy_t, int64_t *rows);
 int ictr_stereotrack_set_timing(ictr_stereotrack *t, int on);
 int ictr_stereotrack_get_kernel_times(const ictr_stereotrack *t, float *ms);
 
+/* ---------------------------------------------------------------- window hand-over (ictr_handover.hip)
+ * A counted window (ictr_stereotrack_count has run; before or after ictr_stereotrack_read) handed to the static split and
+ * the camera fit on the device (DESIGN.md §4 "Window hand-over"): the history and the rows stay where they are, kernels
+ * write the split's view pairs (fsplit.pairs_from_stereo_tracks), the fit's points (camfit.depth_from_disparity and
+ * points_from_first_view) and observations (camfit.observations_from_stereo_tracks) from them, bit for bit what the host
+ * functions make of the xy_t that read returns. The window is not changed: read afterwards returns the same xy_t.
+ * The split and the fit are made for exactly n = M points (the fit's summation order is a function of n), so after count;
+ * an object is reused when the next window keeps the same M. Limits: 2 <= bsize <= 65 (the split's 64 view pairs),
+ * 8 <= M <= 2^22.
+ * The three from-window entries enqueue on the null stream, like the window, and return without waiting; a run on the
+ * null stream or on a blocking stream follows in order, a run on a non-blocking stream is the caller's to order behind
+ * them. Each returns ICTR_ERR_STATE when the window is not counted or a run of r is in flight, ICTR_ERR_INVALID when r
+ * was not made for the window's M (and the frames named below); nothing is launched then. */
+/* needs r made for n = M, npairs = 2 (bsize / 2); pair 2 g = (left g, right g + ceil(bsize / 2)), pair 2 g + 1 = (right g,
+ * left g + ceil(bsize / 2)); the middle frame of an odd window is in no pair */
+int ictr_fsplit_set_pairs_from_window(ictr_fsplit *r, const ictr_stereotrack *t);
+/* X = ((xl - cx) / fx d, (yl - cy) / fy d, d), d = baseline fx / (xr - xl) on frame 0 (baseline: P1[0, 3] of the script,
+ * signed like the disparity), with the camera of ictr_camfit_set_camera, which comes first (ICTR_ERR_STATE). A zero
+ * disparity gives a point that is not finite, which the fit leaves out. */
+int ictr_camfit_set_points_from_window(ictr_camfit *r, const ictr_stereotrack *t, double baseline);
+/* the left (right = 0) or right (right != 0) x, y of every frame; needs r made for nframes = bsize */
+int ictr_camfit_set_observations_from_window(ictr_camfit *r, const ictr_stereotrack *t, int right);
+/* the inlier words of the last run of s, waited for or still in flight, copied device to device on hip_stream, which is
+ * to be the stream of that run (NULL: the null stream). ICTR_ERR_STATE when s has never run or a run of r is in flight,
+ * ICTR_ERR_INVALID when the point counts differ. */
+int ictr_camfit_set_mask_from_fsplit(ictr_camfit *r, const ictr_fsplit *s, void *hip_stream);
+/* inspection: the input buffers as they stand on the device, after everything enqueued so far: xy [npairs][4][N];
+ * X [3][N], xy [nframes][2][N], words [ceil(N / 64)] (any of the three may be NULL) */
+int ictr_debug_fsplit_pairs(const ictr_fsplit *r, double *xy);
+int ictr_debug_camfit_inputs(const ictr_camfit *r, double *X, double *xy, uint64_t *words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,12 @@ SIGNATURES = {
     "ictr_stereotrack_read": (C.c_int, [VP, DP, C.POINTER(I64)]),
     "ictr_stereotrack_set_timing": (C.c_int, [VP, C.c_int]),
     "ictr_stereotrack_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_fsplit_set_pairs_from_window": (C.c_int, [VP, VP]),
+    "ictr_camfit_set_points_from_window": (C.c_int, [VP, VP, C.c_double]),
+    "ictr_camfit_set_observations_from_window": (C.c_int, [VP, VP, C.c_int]),
+    "ictr_camfit_set_mask_from_fsplit": (C.c_int, [VP, VP, VP]),
+    "ictr_debug_fsplit_pairs": (C.c_int, [VP, DP]),
+    "ictr_debug_camfit_inputs": (C.c_int, [VP, DP, DP, C.POINTER(C.c_uint64)]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

@@ -416,6 +416,29 @@ class CameraFitter:
         fx, fy, cx, cy = _as_cam(cam)
         check(_lib.load().ictr_camfit_set_camera(self._h, dp(np.array([fx, fy])), dp(np.array([cx, cy]))))
 
+    def set_points_from_window(self, win, baseline):
+        """points_from_first_view(depth_from_disparity(...)) of a counted StereoTrackWindow, on the device
+        (ictr_camfit_set_points_from_window) with the camera of set_camera, which comes first."""
+        check(_lib.load().ictr_camfit_set_points_from_window(self._h, win._h, float(baseline)))
+
+    def set_observations_from_window(self, win, right=False):
+        """One side of observations_from_stereo_tracks of a counted StereoTrackWindow, on the device."""
+        check(_lib.load().ictr_camfit_set_observations_from_window(self._h, win._h, int(bool(right))))
+
+    def set_mask_from_fsplit(self, splitter, stream=None):
+        """The inlier words of the StaticSplitter's last run, waited for or in flight, copied on the device on `stream`
+        (the stream of that run)."""
+        sp = getattr(stream, "cuda_stream", stream)
+        check(_lib.load().ictr_camfit_set_mask_from_fsplit(self._h, splitter._h, C.c_void_p(sp or 0)))
+
+    def debug_inputs(self):
+        """Inspection (ictr_debug_camfit_inputs): dict X (3, N), xy (F, 2, N), words (ceil(N / 64),) as they stand on the
+        device."""
+        X, xy = np.zeros((3, self.n)), np.zeros((self.nframes, 2, self.n))
+        words = np.zeros((self.n + 63) // 64, np.uint64)
+        check(_lib.load().ictr_debug_camfit_inputs(self._h, dp(X), dp(xy), words.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return dict(X=X, xy=xy, words=words)
+
     def run_async(self, init=None, stream=None, **schedule):
         prm = dict(DEFAULTS)
         prm.update(schedule)

@@ -214,6 +214,28 @@ extern "C" int ictr_camfit_set_camera(ictr_camfit *r, const double *fc, const do
   return ICTR_OK;
 }
 
+extern "C" int ictr_camfit_view_(const ictr_camfit *r, ictr_camfit_view *v) {
+  v->X = r->d_X.get();
+  v->xy = r->d_xy.get();
+  v->words = r->d_words.get();
+  v->n = r->n;
+  v->nwords = r->nwords;
+  v->nframes = r->nframes;
+  v->pending = r->out.pending();
+  v->cam_set = r->cam_set;
+  v->fc[0] = r->cam.fx;
+  v->fc[1] = r->cam.fy;
+  v->cc[0] = r->cam.cx;
+  v->cc[1] = r->cam.cy;
+  return ICTR_OK;
+}
+
+extern "C" void ictr_camfit_filled_(ictr_camfit *r, int points, int obs, int mask) {
+  r->points_set = r->points_set || points != 0;
+  r->obs_set = r->obs_set || obs != 0;
+  r->use_mask = r->use_mask || mask != 0;
+}
+
 extern "C" int ictr_camfit_set_timing(ictr_camfit *r, int on) {
   if (!r) return fail(ICTR_ERR_INVALID, "camfit is NULL");
   if (int rc = r->out.refuse("camfit_set_timing", "camfit")) return rc;

@@ -268,6 +268,19 @@ extern "C" int ictr_fsplit_set_pairs(ictr_fsplit *r, const double *xy) {
   return ICTR_OK;
 }
 
+extern "C" int ictr_fsplit_view_(const ictr_fsplit *r, ictr_fsplit_view *v) {
+  v->xy = r->d_xy.get();
+  v->words = reinterpret_cast<const unsigned long long *>(r->out.dev() + fs_layout(r).words.at);
+  v->n = r->n;
+  v->nwords = r->nwords;
+  v->np = r->np;
+  v->pending = r->out.pending();
+  v->ran = r->out.ran();
+  return ICTR_OK;
+}
+
+extern "C" void ictr_fsplit_pairs_filled_(ictr_fsplit *r) { r->pairs_set = true; }
+
 extern "C" int ictr_fsplit_set_timing(ictr_fsplit *r, int on) {
   if (!r) return fail(ICTR_ERR_INVALID, "fsplit is NULL");
   if (int rc = r->out.refuse("fsplit_set_timing", "fsplit")) return rc;

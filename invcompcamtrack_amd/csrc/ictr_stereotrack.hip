@@ -408,6 +408,16 @@ extern "C" int ictr_stereotrack_read(ictr_stereotrack *t, double *xy_t, int64_t 
   return ICTR_OK;
 }
 
+extern "C" int ictr_stereotrack_view_(const ictr_stereotrack *t, ictr_stereotrack_view *v) {
+  v->hist = t->d_hist.get();
+  v->rows = t->d_rows.get();
+  v->n = t->n;
+  v->bsize = t->bsize;
+  v->counted = t->state == kStCounted;
+  v->m = t->m;
+  return ICTR_OK;
+}
+
 extern "C" int ictr_stereotrack_set_timing(ictr_stereotrack *t, int on) {
   if (!t) return fail(ICTR_ERR_INVALID, "stereotrack is NULL");
   if (t->state == kStOpen) return fail(ICTR_ERR_STATE, "stereotrack_set_timing: a window is open; count and read it first");

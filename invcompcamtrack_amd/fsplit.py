@@ -315,6 +315,17 @@ class StaticSplitter:
             raise ValueError(f"pairs {a.shape}, the splitter was made for ({self.npairs}, 4, {self.n})")
         check(_lib.load().ictr_fsplit_set_pairs(self._h, dp(a)))
 
+    def set_pairs_from_window(self, win):
+        """The view pairs of a counted StereoTrackWindow, written on the device (ictr_fsplit_set_pairs_from_window):
+        pairs_from_stereo_tracks of the window's xy_t, which is not formed. Enqueued on the null stream."""
+        check(_lib.load().ictr_fsplit_set_pairs_from_window(self._h, win._h))
+
+    def debug_pairs(self):
+        """Inspection (ictr_debug_fsplit_pairs): the pairs (P, 4, N) as they stand on the device."""
+        a = np.zeros((self.npairs, 4, self.n))
+        check(_lib.load().ictr_debug_fsplit_pairs(self._h, dp(a)))
+        return a
+
     def run_async(self, ntrials=100, thresh=2.0, seed=0, stream=None):
         sp = getattr(stream, "cuda_stream", stream)
         check(_lib.load().ictr_fsplit_run(self._h, int(ntrials), float(thresh), int(seed) & _M64, C.c_void_p(sp or 0)))

@@ -212,7 +212,7 @@ class StereoTrackWindow:
         check(_lib.load().ictr_stereotrack_create(C.byref(self._h), int(w), int(h), int(bsize), float(th_ratio),
                                                   float(th_abs)))
         self.w, self.h, self.bsize = int(w), int(h), int(bsize)
-        self._keep, self._m = [], None
+        self._keep, self._m, self._counted = [], None, None
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -221,7 +221,7 @@ class StereoTrackWindow:
 
     def open(self, lr, rl, xy0=None):
         ds = [_descriptor(f, True, self.w, self.h) for f in (lr, rl)]
-        self._keep, self._m = [k for _, k in ds], None
+        self._keep, self._m, self._counted = [k for _, k in ds], None, None
         n, p = 0, None
         if xy0 is not None:
             xy0 = np.ascontiguousarray(xy0, np.float64).reshape(-1, 2)
@@ -238,13 +238,18 @@ class StereoTrackWindow:
     def count(self):
         m = C.c_int64()
         check(_lib.load().ictr_stereotrack_count(self._h, C.byref(m)))
-        self._m = int(m.value)
+        self._m = self._counted = int(m.value)
         self._keep = []
         return self._m
 
+    @property
+    def survivors(self):
+        """M of the counted window (it stays counted through read() and a hand-over), None before count()."""
+        return self._counted
+
     def read(self):
         """(xy_t (M, 4, bsize) float64, rows (M,) int64); count() runs first if it has not."""
-        m = self._m if self._m is not None else self.count()
+        m = self._m if self._m is not None else (self._counted if self._counted is not None else self.count())
         self._m = None
         xy_t = np.empty((m, 4, self.bsize), np.float64)
         rows = np.empty(m, np.int64)
@@ -345,3 +350,11 @@ class StereoPointTracker:
         if self.nframes != self.bsize:
             raise ValueError(f"{self.nframes} of {self.bsize} frames pushed")
         return self.win.read()
+
+    def cameras(self, cam, baseline, **kw):
+        """Frames in, cameras out: the counted window handed to windowcams.cameras_from_window on the device (its
+        arguments and its dict); xy_t is never formed."""
+        from .windowcams import cameras_from_window
+        if self.nframes != self.bsize:
+            raise ValueError(f"{self.nframes} of {self.bsize} frames pushed")
+        return cameras_from_window(self.win, cam, baseline, **kw)

@@ -1,0 +1,147 @@
+"""A stereo track window to one camera per frame without leaving the device: misc_src/run_test_OF_track.py:170-223 (the
+checked window), 309-343 (the static split) and 360-411 (depth, camera fit, the two reprojection means) as one pipeline.
+
+The window's history stays where ``StereoTrackWindow.count`` left it; kernels write the split's view pairs and the fit's
+points and observations from it (``ictr_*_from_window``), the split's inlier words reach the fit on the device, and what
+comes back is what the script prints and plots: poses, statuses, the mask words, two vectors of means.
+
+  window_cameras_host    the definition: the host stages of stereotrack, fsplit and camfit in the script's order
+  cameras_from_window    a counted StereoTrackWindow -> the result, on the device
+  window_cameras         fields in -> the result, on the device
+  cameras_from_tracks    a read-back xy_t -> the result through the host-array device stages (split_static, fit_cameras,
+                         reprojection_errors): the way without the hand-over, same bits
+
+The result is a dict: ``m``; the split's ``words``, ``mask``, ``inliers``, ``best_trial``, ``best_count``, ``draws``,
+``F``, ``dd``; the fit's ``G``, ``p``, ``cost``, ``damp``, ``iters``, ``status``, ``n``; ``err_left`` and ``err_right``
+(bsize,), the mean reprojection distance per frame in the left camera and, with ``offset`` (default (baseline, 0, 0))
+added to every translation, against the right observations. Limits (DESIGN.md §4 "Window hand-over"): 2 <= bsize <= 65,
+8 <= M <= 2^22.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import camfit as F
+from . import fsplit as S
+from . import stereotrack as T
+
+__all__ = ["window_cameras_host", "window_cameras", "cameras_from_window", "cameras_from_tracks", "MAX_BSIZE", "MIN_POINTS",
+           "MAX_POINTS"]
+
+MAX_BSIZE = 65          # 2 (bsize // 2) view pairs, the split holds 64
+MIN_POINTS = 8          # one draw of the split
+MAX_POINTS = 1 << 22    # the split's and the fit's
+
+_SPLIT_KEYS = ("words", "mask", "inliers", "best_trial", "best_count", "draws", "F", "dd")
+_FIT_KEYS = ("G", "p", "cost", "damp", "iters", "status", "n")
+
+
+def _check_size(m, bsize):
+    if bsize < 2 or bsize > MAX_BSIZE:
+        raise ValueError(f"a window of {bsize} frames cannot be split: bsize 2 .. {MAX_BSIZE}")
+    if m < MIN_POINTS or m > MAX_POINTS:
+        raise ValueError(f"the window kept {m} points: the split and the fit take {MIN_POINTS} .. 2^22")
+
+
+def _offset(offset, baseline):
+    return [float(baseline), 0.0, 0.0] if offset is None else [float(v) for v in np.asarray(offset, np.float64).reshape(3)]
+
+
+def _result(m, split, fit, err_left, err_right):
+    out = dict(m=int(m))
+    out.update({k: split[k] for k in _SPLIT_KEYS})
+    out.update({k: fit[k] for k in _FIT_KEYS})
+    out.update(err_left=np.asarray(err_left, np.float64), err_right=np.asarray(err_right, np.float64))
+    return out
+
+
+def _from_tracks(xy_t, cam, baseline, ntrials, thresh, seed, offset, init, schedule, split_fn, fit_fn, reproj_fn):
+    xy_t = np.asarray(xy_t, np.float64)
+    if xy_t.ndim != 3 or xy_t.shape[1] != 4:
+        raise ValueError(f"xy_t must be (M, 4, bsize), got {xy_t.shape}")
+    pairs, rows = S.pairs_from_stereo_tracks(xy_t)
+    _check_size(len(rows), xy_t.shape[2])
+    split = split_fn(pairs, ntrials, thresh, seed)
+    xy = xy_t[rows]
+    X = F.points_from_first_view(xy, cam, F.depth_from_disparity(xy, F._as_cam(cam)[0], baseline))
+    left, right = F.observations_from_stereo_tracks(xy)
+    fit = fit_fn(X, left, cam, mask=split["words"], init=init, **schedule)
+    err_l, _ = reproj_fn(X, left, cam, fit["G"], mask=split["words"])
+    err_r, _ = reproj_fn(X, right, cam, fit["G"], mask=split["words"], offset=_offset(offset, baseline))
+    return _result(len(rows), split, fit, err_l, err_r)
+
+
+def cameras_from_tracks(xy_t, cam, baseline, ntrials=100, thresh=2.0, seed=0, offset=None, init=None, **schedule):
+    """The result from a read-back block xy_t (M, 4, bsize) through the host-array device stages: NumPy repacks, the split,
+    the fit and the means run on the device."""
+    return _from_tracks(xy_t, cam, baseline, ntrials, thresh, seed, offset, init, schedule, S.split_static, F.fit_cameras,
+                        F.reprojection_errors)
+
+
+def window_cameras_host(disp_lr, disp_rl, flow_l, flow_r, cam, baseline, xy0=None, th_ratio=0.2, th_abs=1.0, ntrials=100,
+                        thresh=2.0, seed=0, offset=None, init=None, tracks=False, **schedule):
+    """The definition: stereo_track_window_host -> pairs_from_stereo_tracks -> split_static_host -> depth_from_disparity
+    -> points_from_first_view -> observations_from_stereo_tracks -> fit_cameras_host on the inliers -> both
+    reprojection_errors_host. tracks=True adds ``xy_t`` and ``rows``."""
+    xy_t, rows = T.stereo_track_window_host(disp_lr, disp_rl, flow_l, flow_r, xy0=xy0, th_ratio=th_ratio, th_abs=th_abs)
+    out = _from_tracks(xy_t, cam, baseline, ntrials, thresh, seed, offset, init, schedule, S.split_static_host,
+                       F.fit_cameras_host, F.reprojection_errors_host)
+    if tracks:
+        out.update(xy_t=xy_t, rows=rows)
+    return out
+
+
+def cameras_from_window(win, cam, baseline, ntrials=100, thresh=2.0, seed=0, offset=None, init=None, objects=None,
+                        **schedule):
+    """The result from a StereoTrackWindow whose frames are all in (count() runs here if it has not): the hand-over, the
+    split, the fit and the means on the device, everything on the null stream. ``objects``: a dict that keeps the
+    StaticSplitter and the CameraFitter between calls; they are reused when the next window keeps the same M and bsize.
+    ValueError for fewer than 8 survivors, more than 2^22, or bsize outside 2 .. 65; nothing is launched then."""
+    m = win.survivors if win.survivors is not None else win.count()
+    _check_size(m, win.bsize)
+    F._params(schedule)
+    key = (m, win.bsize)
+    if objects is not None and objects.get("key") == key:
+        split, fit = objects["split"], objects["fit"]
+    else:
+        split, fit = S.StaticSplitter(m, 2 * (win.bsize // 2)), F.CameraFitter(m, win.bsize)
+        if objects is not None:
+            objects.update(key=key, split=split, fit=fit)
+    split.set_pairs_from_window(win)
+    split.run_async(ntrials, thresh, seed)
+    fit.set_camera(cam)
+    fit.set_points_from_window(win, baseline)
+    fit.set_observations_from_window(win, right=False)
+    fit.set_mask_from_fsplit(split)
+    fit.run_async(init, **schedule)
+    s, f = split.wait(), fit.wait()
+    err_l, _ = fit.reprojection_errors(f["G"])
+    fit.set_observations_from_window(win, right=True)
+    err_r, _ = fit.reprojection_errors(f["G"], _offset(offset, baseline))
+    return _result(m, s, f, err_l, err_r)
+
+
+def window_cameras(disp_lr, disp_rl, flow_l, flow_r, cam, baseline, xy0=None, th_ratio=0.2, th_abs=1.0, window=None,
+                   tracks=False, ntrials=100, thresh=2.0, seed=0, offset=None, init=None, objects=None, **schedule):
+    """window_cameras_host on the device, bit for bit: the fields of stereo_track_window (float32 in host memory or torch
+    tensors on the device) in, the result out; xy_t is formed only with tracks=True, which adds ``xy_t`` and ``rows``.
+    ``window``: a StereoTrackWindow of the right size to reuse; ``objects``: see cameras_from_window."""
+    bsize = len(disp_lr)
+    if bsize < 1 or len(disp_rl) != bsize:
+        raise ValueError("disp_lr and disp_rl need one plane per frame, at least one frame")
+    if len(flow_l) < bsize - 1 or len(flow_r) < bsize - 1:
+        raise ValueError("flow_l and flow_r need bsize - 1 (fwd, bwd) pairs")
+    if bsize < 2 or bsize > MAX_BSIZE:
+        raise ValueError(f"a window of {bsize} frames cannot be split: bsize 2 .. {MAX_BSIZE}")
+    h, w = tuple(disp_lr[0].shape)
+    win = window if window is not None else T.StereoTrackWindow(w, h, bsize, th_ratio, th_abs)
+    win.open(T.field(disp_lr[0], -1), disp_rl[0], xy0)
+    for fr in range(1, bsize):
+        win.advance(flow_l[fr - 1][0], flow_l[fr - 1][1], flow_r[fr - 1][0], flow_r[fr - 1][1], T.field(disp_lr[fr], -1),
+                    disp_rl[fr])
+    win.count()
+    out = cameras_from_window(win, cam, baseline, ntrials, thresh, seed, offset, init, objects, **schedule)
+    if tracks:
+        xy_t, rows = win.read()
+        out.update(xy_t=xy_t, rows=rows)
+    return out
