@@ -277,6 +277,47 @@ class CamFitClass {
   int64_t n_, nframes_;
 };
 
+// Window bundle adjustment (item 3 of the list that ends misc_src/run_test_OF_track.py, ictr_ba_* in include/ictr.h): the
+// poses of frames 1 .. nframes - 1 and the adjusted points moved together, one read-back at the end.
+class BundleClass {
+ public:
+  BundleClass(int64_t n, int64_t nframes, int64_t nsides) : h_(nullptr), n_(n), nframes_(nframes), nsides_(nsides) {
+    check(ictr_ba_create(&h_, n, nframes, nsides), "BundleClass");
+  }
+  ~BundleClass() { ictr_ba_destroy(h_); }
+  BundleClass(const BundleClass &) = delete;
+  BundleClass &operator=(const BundleClass &) = delete;
+  void SetPoints(const double *X /* [3][n] */) { check(ictr_ba_set_points(h_, X), "SetPoints"); }
+  void SetObservations(const double *xy /* [nsides][nframes][2][n] */) {
+    check(ictr_ba_set_observations(h_, xy), "SetObservations");
+  }
+  void SetMask(const uint64_t *words /* [Words()] or NULL: every point */) { check(ictr_ba_set_mask(h_, words), "SetMask"); }
+  void SetCamera(const double *fc, const double *cc) { check(ictr_ba_set_camera(h_, fc, cc), "SetCamera"); }
+  void SetOffset(const double *offset /* [3]: P1[:, 3] of the script */) { check(ictr_ba_set_offset(h_, offset), "SetOffset"); }
+  // points (after SetCamera), every side's observations of a counted window and a split's inlier words, on the device
+  inline void SetPointsFromWindow(const StereoTrackClass &win, double baseline);
+  inline void SetObservationsFromWindow(const StereoTrackClass &win);
+  void SetMaskFromSplit(const StaticSplitClass &split, void *hip_stream = nullptr) {
+    check(ictr_ba_set_mask_from_fsplit(h_, split.Handle(), hip_stream), "SetMaskFromSplit");
+  }
+  void Run(const double *G0 /* [nframes][12] */, int32_t noiter = 20, double damp_init = 2.0, double damp_fct = 10.0,
+           double minres = 1e-5, double maxdamp = 1e10, void *hip_stream = nullptr) {
+    check(ictr_ba_run(h_, G0, noiter, damp_init, damp_fct, minres, maxdamp, hip_stream), "Run");
+  }
+  // G [nframes][12], X [3][n], cost, damp, iters, status (ICTR_CAMFIT_*), n; any may be NULL
+  void Wait(double *G, double *X, double *cost, double *damp, int32_t *iters, int32_t *status, int64_t *n) {
+    check(ictr_ba_wait(h_, G, X, cost, damp, iters, status, n), "Wait");
+  }
+  int64_t Words() const { return (n_ + 63) / 64; }
+  int64_t Points() const { return n_; }
+  int64_t Frames() const { return nframes_; }
+  int64_t Sides() const { return nsides_; }
+
+ private:
+  ictr_ba *h_;
+  int64_t n_, nframes_, nsides_;
+};
+
 // The checked stereo track window (misc_src/run_test_OF_track.py:170-223, ictr_stereotrack_* in include/ictr.h): Open with
 // the stereo fields of frame 0, Advance once per later frame, Count, Read. A field is an ictr_field; the helpers below
 // fill one.
@@ -334,6 +375,12 @@ inline void CamFitClass::SetPointsFromWindow(const StereoTrackClass &win, double
 }
 inline void CamFitClass::SetObservationsFromWindow(const StereoTrackClass &win, bool right) {
   check(ictr_camfit_set_observations_from_window(h_, win.Handle(), right ? 1 : 0), "SetObservationsFromWindow");
+}
+inline void BundleClass::SetPointsFromWindow(const StereoTrackClass &win, double baseline) {
+  check(ictr_ba_set_points_from_window(h_, win.Handle(), baseline), "SetPointsFromWindow");
+}
+inline void BundleClass::SetObservationsFromWindow(const StereoTrackClass &win) {
+  check(ictr_ba_set_observations_from_window(h_, win.Handle()), "SetObservationsFromWindow");
 }
 
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one

@@ -601,6 +601,47 @@ int ictr_camfit_get_kernel_times(const ictr_camfit *r, float *ms);
  * Per frame: n, s, H [21] (upper triangle, row-major), b [6]. */
 int ictr_debug_camfit_pass(ictr_camfit *r, const double *G, int64_t *n, double *s, double *H, double *b);
 
+/* ------------------------------------------------------------------ window bundle adjustment (run_test_OF_track.py, TODO 3)
+ * "BA Adjust cameras and static points": the poses of frames 1 .. F - 1 and the adjusted points of a track window moved
+ * together by Levenberg-Marquardt on the reprojection residuals of nsides = 1 or 2 cameras per frame (DESIGN.md §4 "Window
+ * bundle adjustment"):
+ *   - side s of frame f sees x_cam = R_f X + t_f + o_s, o_0 = 0, o_1 = the offset; a point is adjusted iff its mask bit
+ *     is set and its 3 coordinates and all its 2 S F observation coordinates are finite; any other point adds exact zeros
+ *     and comes back unchanged; c = sum(rx^2 + ry^2) / (n S F) over the n adjusted points; frame 0 keeps its start pose;
+ *   - one step: the damped normal equations through the Schur complement of the points, a 3 x 3 LDL^T per point and a
+ *     dense 6 (F - 1) LDL^T for the cameras, both without pivoting, every sum over points in the order of
+ *     csrc/ictr_camfit_hd.h (csrc/ictr_ba_hd.h); a pivot that is not finite or not > 0 fails the solve;
+ *   - the schedule, the accept test, the stops and the status codes of the camera fit (ICTR_CAMFIT_*); status 3: fewer
+ *     than 3 adjusted points; a failed solve raises the damping, counts an iteration and is tried again.
+ * All f64 in a fixed order: the same bits on every run. N: 8 .. 2^22, nframes: 2 .. 32, nsides: 1 or 2, noiter: 0 .. 1000. */
+typedef struct ictr_ba ictr_ba;
+int ictr_ba_create(ictr_ba **out, int64_t n, int64_t nframes, int64_t nsides);
+void ictr_ba_destroy(ictr_ba *r);
+/* X: f64 [3][N]; xy: f64 [nsides][nframes][2][N] (pixels); words, fc, cc as ictr_camfit_*; offset[3] finite (needed with
+ * two sides). All refused (ICTR_ERR_STATE) while a run is in flight. */
+int ictr_ba_set_points(ictr_ba *r, const double *X);
+int ictr_ba_set_observations(ictr_ba *r, const double *xy);
+int ictr_ba_set_mask(ictr_ba *r, const uint64_t *words);
+int ictr_ba_set_camera(ictr_ba *r, const double *fc, const double *cc);
+int ictr_ba_set_offset(ictr_ba *r, const double *offset);
+/* enqueues 2 + 7 (noiter + 1) launches on hip_stream (NULL: the null stream) and returns. G0 [nframes][12]: the start
+ * poses (finite); the schedule as ictr_camfit_run. */
+int ictr_ba_run(ictr_ba *r, const double *G0, int32_t noiter, double damp_init, double damp_fct, double minres,
+                double maxdamp, void *hip_stream);
+/* waits for the last run; any output may be NULL. G [nframes][12], X [3][N] (24 bytes per point, copied only when asked
+ * for), cost, damp, iters, status (ICTR_CAMFIT_*), n (adjusted points). */
+int ictr_ba_wait(ictr_ba *r, double *G, double *X, double *cost, double *damp, int32_t *iters, int32_t *status, int64_t *n);
+/* on: the next runs record device time stamps around their launches; get: ms[7] of the last waited run spent in
+ * k_ba_point, k_ba_frames, k_ba_decide, k_ba_schur, k_ba_gather, k_ba_solve, k_ba_back */
+int ictr_ba_set_timing(ictr_ba *r, int on);
+int ictr_ba_get_kernel_times(const ictr_ba *r, float *ms);
+/* inspection: the passes, the Schur pass and the assembly alone at the poses G [nframes][12], the points X [3][N] (NULL:
+ * the set ones) and the damping damp, on the null stream. n, cost, A [dim (dim + 1) / 2] the reduced system's upper
+ * triangle (row-major, packed, dim = 6 (nframes - 1)), rhs [dim], V [6][N], gp [3][N], nfail: the adjusted points whose
+ * 3 x 3 factorisation failed. */
+int ictr_debug_ba_system(ictr_ba *r, const double *G, const double *X, double damp, int64_t *n, double *cost, double *A,
+                         double *rhs, double *V, double *gp, int64_t *nfail);
+
 /* ------------------------------------------------------------------ multi-view point triangulation (misc_src/triang.c)
  * A track set (10^4 .. 10^5 points, 2 .. 30 views each) triangulated in one launch, one lane per point, with the
  * arithmetic of the reference routine of each mode: every product and sum in f32, in its order and grouping, so the
@@ -772,6 +813,13 @@ int ictr_camfit_set_mask_from_fsplit(ictr_camfit *r, const ictr_fsplit *s, void 
  * X [3][N], xy [nframes][2][N], words [ceil(N / 64)] (any of the three may be NULL) */
 int ictr_debug_fsplit_pairs(const ictr_fsplit *r, double *xy);
 int ictr_debug_camfit_inputs(const ictr_camfit *r, double *X, double *xy, uint64_t *words);
+/* The same for the bundle adjustment: the points as ictr_camfit_set_points_from_window (ictr_ba_set_camera comes first),
+ * the left observations into side 0 and, with two sides, the right ones into side 1, the split's words as the mask; and
+ * the adjuster's device inputs read back (any of X [3][N], xy [nsides][nframes][2][N], words may be NULL). */
+int ictr_ba_set_points_from_window(ictr_ba *r, const ictr_stereotrack *t, double baseline);
+int ictr_ba_set_observations_from_window(ictr_ba *r, const ictr_stereotrack *t);
+int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, void *hip_stream);
+int ictr_debug_ba_inputs(const ictr_ba *r, double *X, double *xy, uint64_t *words);
 
 #ifdef __cplusplus
 }

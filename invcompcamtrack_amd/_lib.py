@@ -248,6 +248,18 @@ SIGNATURES = {
     "ictr_camfit_set_timing": (C.c_int, [VP, C.c_int]),
     "ictr_camfit_get_kernel_times": (C.c_int, [VP, FP]),
     "ictr_debug_camfit_pass": (C.c_int, [VP, DP, C.POINTER(I64), DP, DP, DP]),
+    "ictr_ba_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
+    "ictr_ba_destroy": (None, [VP]),
+    "ictr_ba_set_points": (C.c_int, [VP, DP]),
+    "ictr_ba_set_observations": (C.c_int, [VP, DP]),
+    "ictr_ba_set_mask": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "ictr_ba_set_camera": (C.c_int, [VP, DP, DP]),
+    "ictr_ba_set_offset": (C.c_int, [VP, DP]),
+    "ictr_ba_run": (C.c_int, [VP, DP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, VP]),
+    "ictr_ba_wait": (C.c_int, [VP, DP, DP, DP, DP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(I64)]),
+    "ictr_ba_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_ba_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_debug_ba_system": (C.c_int, [VP, DP, DP, C.c_double, C.POINTER(I64), DP, DP, DP, DP, DP, C.POINTER(I64)]),
     "ictr_stereotrack_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
     "ictr_stereotrack_destroy": (None, [VP]),
     "ictr_stereotrack_open": (C.c_int, [VP, DP, I64, C.POINTER(Field), C.POINTER(Field)]),
@@ -262,6 +274,10 @@ SIGNATURES = {
     "ictr_camfit_set_mask_from_fsplit": (C.c_int, [VP, VP, VP]),
     "ictr_debug_fsplit_pairs": (C.c_int, [VP, DP]),
     "ictr_debug_camfit_inputs": (C.c_int, [VP, DP, DP, C.POINTER(C.c_uint64)]),
+    "ictr_ba_set_points_from_window": (C.c_int, [VP, VP, C.c_double]),
+    "ictr_ba_set_observations_from_window": (C.c_int, [VP, VP]),
+    "ictr_ba_set_mask_from_fsplit": (C.c_int, [VP, VP, VP]),
+    "ictr_debug_ba_inputs": (C.c_int, [VP, DP, DP, C.POINTER(C.c_uint64)]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

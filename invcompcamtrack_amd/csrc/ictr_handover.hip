@@ -8,6 +8,8 @@
 //   k_ho_obs     same grid: the two words of one side into the observations [bsize][2][M]
 //   k_ho_points  one thread per survivor: ho_point of ictr_handover_hd.h on frame 0 into X [3][M]
 //
+// The adjuster (ictr_ba.hip) takes its points, both sides of its observations and its mask by the same kernels.
+//
 // Every thread reads rows[m] once; rows is ascending, so neighbouring lanes read neighbouring (or the same cache line's)
 // words of a history column, and every store is coalesced over m. No atomics, no LDS, plain vector stores. The three
 // from-window entries enqueue on the null stream, like the window itself, and do not wait.
@@ -166,6 +168,69 @@ extern "C" int ictr_camfit_set_mask_from_fsplit(ictr_camfit *r, const ictr_fspli
   HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
                         (hipStream_t)hip_stream));
   ictr_camfit_filled_(r, 0, 0, 1);
+  return ICTR_OK;
+}
+
+// the adjuster's inputs from the same window: ho_point into the points as set, k_ho_obs once per side
+extern "C" int ictr_ba_set_points_from_window(ictr_ba *r, const ictr_stereotrack *t, double baseline) {
+  const char *what = "ba_set_points_from_window";
+  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_ba_view d;
+  if (int rc = ictr_ba_view_(r, &d)) return rc;
+  HoArgs a;
+  if (int rc = ho_window(t, d.n, what, &a)) return rc;
+  if (d.pending) return ho_in_flight(what, "ba");
+  if (!d.cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_ba_set_camera comes first", what);
+  const HoCam cam = {d.fc[0], d.fc[1], d.cc[0], d.cc[1]};
+  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.X);
+  HIPCHK(hipGetLastError());
+  ictr_ba_filled_(r, 1, 0, 0);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ba_set_observations_from_window(ictr_ba *r, const ictr_stereotrack *t) {
+  const char *what = "ba_set_observations_from_window";
+  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_ba_view d;
+  if (int rc = ictr_ba_view_(r, &d)) return rc;
+  HoArgs a;
+  if (int rc = ho_window(t, d.n, what, &a)) return rc;
+  if (d.pending) return ho_in_flight(what, "ba");
+  if (d.nframes != a.bsize)
+    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the adjuster was made for %d", what, a.bsize, d.nframes);
+  for (int s = 0; s < d.nsides; ++s)
+    hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, s,
+                       d.xy + (size_t)s * (size_t)a.bsize * 2 * (size_t)a.m);
+  HIPCHK(hipGetLastError());
+  ictr_ba_filled_(r, 0, 1, 0);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, void *hip_stream) {
+  const char *what = "ba_set_mask_from_fsplit";
+  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_ba_view d;
+  ictr_fsplit_view v;
+  if (int rc = ictr_ba_view_(r, &d)) return rc;
+  if (int rc = ictr_fsplit_view_(s, &v)) return rc;
+  if (d.pending) return ho_in_flight(what, "ba");
+  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the split has never run", what);
+  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the split has %d points, the adjuster %d", what, v.n, d.n);
+  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
+                        (hipStream_t)hip_stream));
+  ictr_ba_filled_(r, 0, 0, 1);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_debug_ba_inputs(const ictr_ba *r, double *X, double *xy, uint64_t *words) {
+  if (!r) return fail(ICTR_ERR_INVALID, "debug_ba_inputs: ba is NULL");
+  ictr_ba_view v;
+  if (int rc = ictr_ba_view_(r, &v)) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  const size_t n = (size_t)v.n;
+  if (X) HIPCHK(hipMemcpy(X, v.X, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (xy) HIPCHK(hipMemcpy(xy, v.xy, sizeof(double) * 2 * (size_t)v.nsides * (size_t)v.nframes * n, hipMemcpyDeviceToHost));
+  if (words) HIPCHK(hipMemcpy(words, v.words, sizeof(uint64_t) * (size_t)v.nwords, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 

@@ -26,11 +26,13 @@ extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v); 
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);
 
-// Device views for the window hand-over (ictr_handover.hip): what the three files that see inside their objects expose so
-// that the window's history can be written into the split's and the fit's input buffers without leaving the device.
+// Device views for the window hand-over (ictr_handover.hip): what the files that see inside their objects expose so
+// that the window's history can be written into the split's, the fit's and the bundle adjuster's input buffers without
+// leaving the device.
 struct ictr_stereotrack;
 struct ictr_fsplit;
 struct ictr_camfit;
+struct ictr_ba;
 struct ictr_stereotrack_view {
   const double *hist;     // [bsize][4][n]
   const long long *rows;  // [m] start indices of the survivors, ascending
@@ -50,12 +52,21 @@ struct ictr_camfit_view {
   int pending, cam_set;
   double fc[2], cc[2];
 };
+struct ictr_ba_view {
+  double *X, *xy;             // [3][n] the points as set, [nsides][nframes][2][n]
+  unsigned long long *words;  // [nwords]
+  int n, nwords, nframes, nsides;
+  int pending, cam_set;
+  double fc[2], cc[2];
+};
 extern "C" int ictr_stereotrack_view_(const ictr_stereotrack *t, ictr_stereotrack_view *v);  // ictr_stereotrack.hip
 extern "C" int ictr_fsplit_view_(const ictr_fsplit *r, ictr_fsplit_view *v);                // ictr_fsplit.hip
 extern "C" int ictr_camfit_view_(const ictr_camfit *r, ictr_camfit_view *v);                // ictr_camfit.hip
 // the inputs a hand-over has filled on the device count as set (any of points, obs; mask: the words are to be used)
 extern "C" void ictr_fsplit_pairs_filled_(ictr_fsplit *r);
 extern "C" void ictr_camfit_filled_(ictr_camfit *r, int points, int obs, int mask);
+extern "C" int ictr_ba_view_(const ictr_ba *r, ictr_ba_view *v);  // ictr_ba.hip
+extern "C" void ictr_ba_filled_(ictr_ba *r, int points, int obs, int mask);
 
 namespace ictr {
 

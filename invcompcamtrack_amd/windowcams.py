@@ -10,23 +10,31 @@ comes back is what the script prints and plots: poses, statuses, the mask words,
   window_cameras         fields in -> the result, on the device
   cameras_from_tracks    a read-back xy_t -> the result through the host-array device stages (split_static, fit_cameras,
                          reprojection_errors): the way without the hand-over, same bits
+  window_bundle_host     window_cameras_host, then the bundle adjustment (bundle.adjust_window_host) of the fit's poses and
+                         the inliers' points over both cameras
+  bundle_from_window     cameras_from_window, then the same adjustment on the device from the window's own buffers
 
 The result is a dict: ``m``; the split's ``words``, ``mask``, ``inliers``, ``best_trial``, ``best_count``, ``draws``,
 ``F``, ``dd``; the fit's ``G``, ``p``, ``cost``, ``damp``, ``iters``, ``status``, ``n``; ``err_left`` and ``err_right``
 (bsize,), the mean reprojection distance per frame in the left camera and, with ``offset`` (default (baseline, 0, 0))
 added to every translation, against the right observations. Limits (DESIGN.md §4 "Window hand-over"): 2 <= bsize <= 65,
 8 <= M <= 2^22.
+
+The two bundle functions add ``ba`` (the result of the adjustment: G, p, X, cost, damp, iters, status, n) and ``err_left_ba``,
+``err_right_ba``, the two means at the adjusted poses and points. The adjustment starts from the fit's poses (12 bsize
+doubles that cross the host) and takes 2 <= bsize <= 32.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import bundle as B
 from . import camfit as F
 from . import fsplit as S
 from . import stereotrack as T
 
-__all__ = ["window_cameras_host", "window_cameras", "cameras_from_window", "cameras_from_tracks", "MAX_BSIZE", "MIN_POINTS",
-           "MAX_POINTS"]
+__all__ = ["window_cameras_host", "window_cameras", "cameras_from_window", "cameras_from_tracks", "window_bundle_host",
+           "bundle_from_window", "MAX_BSIZE", "MIN_POINTS", "MAX_POINTS"]
 
 MAX_BSIZE = 65          # 2 (bsize // 2) view pairs, the split holds 64
 MIN_POINTS = 8          # one draw of the split
@@ -144,4 +152,63 @@ def window_cameras(disp_lr, disp_rl, flow_l, flow_r, cam, baseline, xy0=None, th
     if tracks:
         xy_t, rows = win.read()
         out.update(xy_t=xy_t, rows=rows)
+    return out
+
+
+def _check_bundle(bsize, ba_schedule):
+    if bsize > B.MAX_FRAMES:
+        raise ValueError(f"a window of {bsize} frames cannot be adjusted: bsize 2 .. {B.MAX_FRAMES}")
+    return F._params(dict(ba_schedule or {}))
+
+
+def window_bundle_host(disp_lr, disp_rl, flow_l, flow_r, cam, baseline, xy0=None, th_ratio=0.2, th_abs=1.0, ntrials=100,
+                       thresh=2.0, seed=0, offset=None, init=None, tracks=False, ba_schedule=None, **schedule):
+    """The definition of bundle_from_window: window_cameras_host as it is, then adjust_window_host over the left and the
+    right observations with the split's words as the mask, started from the fit's poses, and both
+    reprojection_errors_host at the adjusted poses and points. ba_schedule: the adjustment's schedule (a dict)."""
+    _check_bundle(len(disp_lr), ba_schedule)
+    out = window_cameras_host(disp_lr, disp_rl, flow_l, flow_r, cam, baseline, xy0=xy0, th_ratio=th_ratio, th_abs=th_abs,
+                              ntrials=ntrials, thresh=thresh, seed=seed, offset=offset, init=init, tracks=True, **schedule)
+    _, keep = S.pairs_from_stereo_tracks(out["xy_t"])
+    xy = out["xy_t"][keep]
+    X = F.points_from_first_view(xy, cam, F.depth_from_disparity(xy, F._as_cam(cam)[0], baseline))
+    left, right = F.observations_from_stereo_tracks(xy)
+    off = _offset(offset, baseline)
+    ba = B.adjust_window_host(X, np.stack([left, right]), cam, offset=off, mask=out["words"], init=out["G"],
+                              **dict(ba_schedule or {}))
+    err_l, _ = F.reprojection_errors_host(ba["X"], left, cam, ba["G"], mask=out["words"])
+    err_r, _ = F.reprojection_errors_host(ba["X"], right, cam, ba["G"], mask=out["words"], offset=off)
+    out.update(ba=ba, err_left_ba=err_l, err_right_ba=err_r)
+    if not tracks:
+        del out["xy_t"], out["rows"]
+    return out
+
+
+def bundle_from_window(win, cam, baseline, ntrials=100, thresh=2.0, seed=0, offset=None, init=None, objects=None,
+                       ba_schedule=None, **schedule):
+    """cameras_from_window as it is, then the adjustment on the device: the adjuster's points, both sides of its
+    observations and its mask come from the window's and the split's device buffers, its start poses from the fit. The
+    means at the adjusted poses and points are the fitter's, on the adjusted points. ``objects`` also keeps the
+    BundleAdjuster."""
+    _check_bundle(win.bsize, ba_schedule)
+    objects = {} if objects is None else objects
+    out = cameras_from_window(win, cam, baseline, ntrials, thresh, seed, offset, init, objects, **schedule)
+    split, fit = objects["split"], objects["fit"]
+    if objects.get("ba_key") != objects["key"]:
+        objects.update(ba_key=objects["key"], ba=B.BundleAdjuster(out["m"], win.bsize, 2))
+    ba = objects["ba"]
+    off = _offset(offset, baseline)
+    ba.set_camera(cam)
+    ba.set_offset(off)
+    ba.set_points_from_window(win, baseline)
+    ba.set_observations_from_window(win)
+    ba.set_mask_from_fsplit(split)
+    ba.run_async(out["G"], **dict(ba_schedule or {}))
+    res = ba.wait()
+    fit.set_points(res["X"])
+    fit.set_observations_from_window(win, right=False)
+    err_l, _ = fit.reprojection_errors(res["G"])
+    fit.set_observations_from_window(win, right=True)
+    err_r, _ = fit.reprojection_errors(res["G"], off)
+    out.update(ba=res, err_left_ba=err_l, err_right_ba=err_r)
     return out
