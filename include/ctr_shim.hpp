@@ -201,6 +201,7 @@ class RansacClass {
 };
 
 class StereoTrackClass;
+class CamRansacClass;
 
 // Static / moving split of a track window (misc_src/run_test_OF_track.py:309-343, ictr_fsplit_* in include/ictr.h): RANSAC
 // over 8-point fundamental matrices of several view pairs of the same points, one read-back at the end.
@@ -255,6 +256,8 @@ class CamFitClass {
   void SetMaskFromSplit(const StaticSplitClass &split, void *hip_stream = nullptr) {
     check(ictr_camfit_set_mask_from_fsplit(h_, split.Handle(), hip_stream), "SetMaskFromSplit");
   }
+  // the winner's inlier words of a window camera RANSAC's last run, waited for or in flight
+  inline void SetMaskFromRansac(const CamRansacClass &ransac, void *hip_stream = nullptr);
   // the schedule of triang.c:327
   void Run(const double *G0 /* [nframes][12] */, int32_t noiter = 20, double damp_init = 2.0, double damp_fct = 10.0,
            double minres = 1e-5, double maxdamp = 1e10, void *hip_stream = nullptr) {
@@ -300,6 +303,7 @@ class BundleClass {
   void SetMaskFromSplit(const StaticSplitClass &split, void *hip_stream = nullptr) {
     check(ictr_ba_set_mask_from_fsplit(h_, split.Handle(), hip_stream), "SetMaskFromSplit");
   }
+  inline void SetMaskFromRansac(const CamRansacClass &ransac, void *hip_stream = nullptr);
   void Run(const double *G0 /* [nframes][12] */, int32_t noiter = 20, double damp_init = 2.0, double damp_fct = 10.0,
            double minres = 1e-5, double maxdamp = 1e10, void *hip_stream = nullptr) {
     check(ictr_ba_run(h_, G0, noiter, damp_init, damp_fct, minres, maxdamp, hip_stream), "Run");
@@ -317,6 +321,55 @@ class BundleClass {
   ictr_ba *h_;
   int64_t n_, nframes_, nsides_;
 };
+
+// Window camera RANSAC (item 1 of the list that ends misc_src/run_test_OF_track.py, ictr_camransac_* in include/ictr.h):
+// one P3P draw per trial over all frames of a track window, scored in both cameras, one read-back at the end.
+class CamRansacClass {
+ public:
+  CamRansacClass(int64_t n, int64_t nframes, int64_t nsides) : h_(nullptr), n_(n), nframes_(nframes), nsides_(nsides) {
+    check(ictr_camransac_create(&h_, n, nframes, nsides), "CamRansacClass");
+  }
+  ~CamRansacClass() { ictr_camransac_destroy(h_); }
+  CamRansacClass(const CamRansacClass &) = delete;
+  CamRansacClass &operator=(const CamRansacClass &) = delete;
+  void SetPoints(const double *X /* [3][n] */) { check(ictr_camransac_set_points(h_, X), "SetPoints"); }
+  void SetObservations(const double *xy /* [nsides][nframes][2][n] */) {
+    check(ictr_camransac_set_observations(h_, xy), "SetObservations");
+  }
+  void SetMask(const uint64_t *words /* [Words()] or NULL: every point */) { check(ictr_camransac_set_mask(h_, words), "SetMask"); }
+  void SetCamera(const double *fc, const double *cc) { check(ictr_camransac_set_camera(h_, fc, cc), "SetCamera"); }
+  void SetOffset(const double *offset /* [3]: P1[:, 3] of the script */) {
+    check(ictr_camransac_set_offset(h_, offset), "SetOffset");
+  }
+  // points (after SetCamera) and every side's observations of a counted window, on the device
+  inline void SetPointsFromWindow(const StereoTrackClass &win, double baseline);
+  inline void SetObservationsFromWindow(const StereoTrackClass &win);
+  const ictr_camransac *Handle() const { return h_; }
+  void Run(int64_t ntrials, double thresh, uint64_t seed = 0, void *hip_stream = nullptr) {
+    check(ictr_camransac_run(h_, ntrials, thresh, seed, hip_stream), "Run");
+  }
+  // draws [4], G [nframes][12], p [nframes][6], inl_words [Words()], dd [n]; any may be NULL. best_trial -1: no trial
+  // succeeded
+  void Wait(int64_t *best_trial, int64_t *best_count, int32_t *draws, double *G, double *p, uint64_t *inl_words,
+            double *dd) {
+    check(ictr_camransac_wait(h_, best_trial, best_count, draws, G, p, inl_words, dd), "Wait");
+  }
+  int64_t Words() const { return (n_ + 63) / 64; }
+  int64_t Points() const { return n_; }
+  int64_t Frames() const { return nframes_; }
+  int64_t Sides() const { return nsides_; }
+
+ private:
+  ictr_camransac *h_;
+  int64_t n_, nframes_, nsides_;
+};
+
+inline void CamFitClass::SetMaskFromRansac(const CamRansacClass &ransac, void *hip_stream) {
+  check(ictr_camfit_set_mask_from_camransac(h_, ransac.Handle(), hip_stream), "SetMaskFromRansac");
+}
+inline void BundleClass::SetMaskFromRansac(const CamRansacClass &ransac, void *hip_stream) {
+  check(ictr_ba_set_mask_from_camransac(h_, ransac.Handle(), hip_stream), "SetMaskFromRansac");
+}
 
 // The checked stereo track window (misc_src/run_test_OF_track.py:170-223, ictr_stereotrack_* in include/ictr.h): Open with
 // the stereo fields of frame 0, Advance once per later frame, Count, Read. A field is an ictr_field; the helpers below
@@ -381,6 +434,12 @@ inline void BundleClass::SetPointsFromWindow(const StereoTrackClass &win, double
 }
 inline void BundleClass::SetObservationsFromWindow(const StereoTrackClass &win) {
   check(ictr_ba_set_observations_from_window(h_, win.Handle()), "SetObservationsFromWindow");
+}
+inline void CamRansacClass::SetPointsFromWindow(const StereoTrackClass &win, double baseline) {
+  check(ictr_camransac_set_points_from_window(h_, win.Handle(), baseline), "SetPointsFromWindow");
+}
+inline void CamRansacClass::SetObservationsFromWindow(const StereoTrackClass &win) {
+  check(ictr_camransac_set_observations_from_window(h_, win.Handle()), "SetObservationsFromWindow");
 }
 
 // Multi-view point triangulation (misc_src/triang.c, ictr_triang_* in include/ictr.h): a whole track set per launch, one

@@ -783,6 +783,42 @@ int ictr_stereotrack_read(ictr_stereotrack *t, double *xy_t, int64_t *rows);
 int ictr_stereotrack_set_timing(ictr_stereotrack *t, int on);
 int ictr_stereotrack_get_kernel_times(const ictr_stereotrack *t, float *ms);
 
+/* ---------------------------------------------------------------- window camera RANSAC (ictr_camransac.hip)
+ * "RANSAC camera estimation ... for whole sequence, check right for consistency" (misc_src/run_test_OF_track.py, TODO 1;
+ * DESIGN.md §4 "Window camera RANSAC"): ntrials trials over the N points of a track window seen in nframes frames from
+ * nsides = 1 (left) or 2 (left, right) cameras. Trial g draws 4 points once (the pose sampler's stream over all N) and
+ * fits one pose per frame by P3P from their left observations; a point is an inlier of the trial iff it counts (mask bit
+ * set, its 3 coordinates and its 2 nsides nframes observation coordinates finite) and reprojects within thresh (strictly)
+ * in every frame and on every side, the right camera at t_f + offset. The largest count wins, the lowest trial on ties.
+ * X: f64 [3][N] in the first view's frame; xy: f64 [nsides][nframes][2][N] (the bundle adjuster's layout); words: bit
+ * j % 64 of word j / 64 is point j, NULL: every point. 4 <= N <= 2^22, 1 <= nframes <= 64, 1 <= ntrials <= 2^20.
+ * run enqueues on hip_stream (NULL: the null stream) and returns; wait blocks and copies out: best_trial (-1: no trial
+ * succeeded; then best_count 0, G NaN, words 0, dd NaN, draws -1), best_count, draws [4], G [nframes][12] row-major
+ * [R | t], p [nframes][6] = se3_log(G) taken on the host, inl_words [ceil(N / 64)], dd [N] each point's largest
+ * reprojection distance under the winner (any may be NULL). The setters, run and the debug entry return ICTR_ERR_STATE
+ * while a run is in flight; run needs points, observations and the camera, and with two sides the offset. */
+typedef struct ictr_camransac ictr_camransac;
+int ictr_camransac_create(ictr_camransac **out, int64_t n, int64_t nframes, int64_t nsides);
+void ictr_camransac_destroy(ictr_camransac *r);
+int ictr_camransac_set_camera(ictr_camransac *r, const double *fc, const double *cc);
+int ictr_camransac_set_offset(ictr_camransac *r, const double *offset);
+int ictr_camransac_set_points(ictr_camransac *r, const double *X);
+int ictr_camransac_set_observations(ictr_camransac *r, const double *xy);
+int ictr_camransac_set_mask(ictr_camransac *r, const uint64_t *words);
+int ictr_camransac_run(ictr_camransac *r, int64_t ntrials, double thresh, uint64_t seed, void *hip_stream);
+int ictr_camransac_wait(ictr_camransac *r, int64_t *best_trial, int64_t *best_count, int32_t *draws, double *G, double *p,
+                        uint64_t *inl_words, double *dd);
+/* per-kernel timing with HIP events around the launches of the next runs; ms[4] of the last waited run: k_cr_hyp,
+ * k_cr_score, k_cr_select (summed over the chunks) and k_cr_flags + k_cr_mask */
+int ictr_camransac_set_timing(ictr_camransac *r, int on);
+int ictr_camransac_get_kernel_times(const ictr_camransac *r, float *ms);
+int ictr_camransac_chunk_size(const ictr_camransac *r);
+/* inspection: k_cr_hyp and k_cr_score<tile> alone over trials first_trial .. first_trial + count - 1 (below 2^20), in the
+ * object's own chunks and tile, on the null stream; no selection. status [count], draws [count][4],
+ * G [count][nframes][12], cnt [count] (0 for a failed trial) */
+int ictr_debug_camransac_trials(ictr_camransac *r, double thresh, uint64_t seed, int64_t first_trial, int64_t count,
+                                int32_t *status, int32_t *draws, double *G, uint32_t *cnt);
+
 /* ---------------------------------------------------------------- window hand-over (ictr_handover.hip)
  * A counted window (ictr_stereotrack_count has run; before or after ictr_stereotrack_read) handed to the static split and
  * the camera fit on the device (DESIGN.md §4 "Window hand-over"): the history and the rows stay where they are, kernels
@@ -820,6 +856,19 @@ int ictr_ba_set_points_from_window(ictr_ba *r, const ictr_stereotrack *t, double
 int ictr_ba_set_observations_from_window(ictr_ba *r, const ictr_stereotrack *t);
 int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, void *hip_stream);
 int ictr_debug_ba_inputs(const ictr_ba *r, double *X, double *xy, uint64_t *words);
+
+/* The same for the window camera RANSAC (ictr_camransac_set_camera comes first for the points; both sides of an object of
+ * two sides are written), its winner's inlier words, of a run waited for or still in flight, copied on hip_stream into
+ * the fit's or the adjuster's mask, and its device inputs read back. As for ictr_camfit_set_mask_from_fsplit, hip_stream
+ * is to be the stream of that run (NULL: the null stream): the copy is ordered behind the run by the stream alone, and on
+ * another non-blocking stream it is the caller's to order. ictr_debug_camransac_inputs returns in words the mask in
+ * effect: the words of the last ictr_camransac_set_mask, or every point's bit (bits past N clear) where that was NULL or
+ * never called. */
+int ictr_camransac_set_points_from_window(ictr_camransac *r, const ictr_stereotrack *t, double baseline);
+int ictr_camransac_set_observations_from_window(ictr_camransac *r, const ictr_stereotrack *t);
+int ictr_camfit_set_mask_from_camransac(ictr_camfit *r, const ictr_camransac *s, void *hip_stream);
+int ictr_ba_set_mask_from_camransac(ictr_ba *r, const ictr_camransac *s, void *hip_stream);
+int ictr_debug_camransac_inputs(const ictr_camransac *r, double *X, double *xy, uint64_t *words);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,8 @@ from .stereotrack import (StereoPointTracker, StereoTrackWindow, stereo_track_wi
                           stereo_track_window_host)
 from .windowcams import cameras_from_tracks, cameras_from_window, window_cameras, window_cameras_host  # noqa: F401
 from .windowcams import bundle_from_window, window_bundle_host  # noqa: F401
+from .windowcams import ransac_cameras, ransac_cameras_from_window, window_ransac_cameras_host  # noqa: F401
+from .camransac import CameraRansac, window_ransac, window_ransac_host  # noqa: F401
 from .bundle import BundleAdjuster, adjust_window, adjust_window_host  # noqa: F401
 from .triang import Triangulator, cameras_from_poses, rays_from_first_view, tracks_from_oftrack, triangulate_tracks  # noqa: F401
 from .sequence import SequenceTracker, select_points, track_sequence, track_sequence_host_loop  # noqa: F401

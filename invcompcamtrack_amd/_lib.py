@@ -278,6 +278,26 @@ SIGNATURES = {
     "ictr_ba_set_observations_from_window": (C.c_int, [VP, VP]),
     "ictr_ba_set_mask_from_fsplit": (C.c_int, [VP, VP, VP]),
     "ictr_debug_ba_inputs": (C.c_int, [VP, DP, DP, C.POINTER(C.c_uint64)]),
+    "ictr_camransac_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
+    "ictr_camransac_destroy": (None, [VP]),
+    "ictr_camransac_set_camera": (C.c_int, [VP, DP, DP]),
+    "ictr_camransac_set_offset": (C.c_int, [VP, DP]),
+    "ictr_camransac_set_points": (C.c_int, [VP, DP]),
+    "ictr_camransac_set_observations": (C.c_int, [VP, DP]),
+    "ictr_camransac_set_mask": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "ictr_camransac_run": (C.c_int, [VP, I64, C.c_double, C.c_uint64, VP]),
+    "ictr_camransac_wait": (C.c_int, [VP, C.POINTER(I64), C.POINTER(I64), C.POINTER(C.c_int32), DP, DP,
+                                      C.POINTER(C.c_uint64), DP]),
+    "ictr_camransac_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_camransac_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_camransac_chunk_size": (C.c_int, [VP]),
+    "ictr_debug_camransac_trials": (C.c_int, [VP, C.c_double, C.c_uint64, I64, I64, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), DP, C.POINTER(C.c_uint32)]),
+    "ictr_camransac_set_points_from_window": (C.c_int, [VP, VP, C.c_double]),
+    "ictr_camransac_set_observations_from_window": (C.c_int, [VP, VP]),
+    "ictr_camfit_set_mask_from_camransac": (C.c_int, [VP, VP, VP]),
+    "ictr_ba_set_mask_from_camransac": (C.c_int, [VP, VP, VP]),
+    "ictr_debug_camransac_inputs": (C.c_int, [VP, DP, DP, C.POINTER(C.c_uint64)]),
     "ictr_triang_create": (C.c_int, [C.POINTER(VP), I64, I64, I64]),
     "ictr_triang_destroy": (None, [VP]),
     "ictr_triang_set_cameras": (C.c_int, [VP, FP, I64]),

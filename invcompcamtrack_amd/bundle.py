@@ -444,6 +444,12 @@ class BundleAdjuster:
         sp = getattr(stream, "cuda_stream", stream)
         check(_lib.load().ictr_ba_set_mask_from_fsplit(self._h, splitter._h, C.c_void_p(sp or 0)))
 
+    def set_mask_from_camransac(self, ransac, stream=None):
+        """The winner's inlier words of the CameraRansac's last run, waited for or in flight, copied on the device on
+        `stream` (the stream of that run)."""
+        sp = getattr(stream, "cuda_stream", stream)
+        check(_lib.load().ictr_ba_set_mask_from_camransac(self._h, ransac._h, C.c_void_p(sp or 0)))
+
     def debug_inputs(self):
         """Inspection (ictr_debug_ba_inputs): dict X (3, N), xy (S, F, 2, N), words (ceil(N / 64),) as they stand on the
         device."""

@@ -1,5 +1,5 @@
 // ictr_draw_hd.h -- the counter-based draw stream of the RANSAC stages, stated once: the mixer, the seed as the kernels
-// take it and the distinct indices of one trial. The same text compiles for the device (k_ransac_hyp: 4 matches,
+// take it and the distinct indices of one trial. The same text compiles for the device (k_ransac_hyp and k_cr_hyp: 4 matches,
 // k_fsplit_fit: 8 points), for the host code that fills the kernels' seed and, as plain C++ under sanitizers, for
 // tests/cxx/draw_hd_host.cpp (tests/test_fsplit_cpu.py); invcompcamtrack_amd/_hostmath.py restates it. Integers only.
 #pragma once

@@ -8,7 +8,8 @@
 //   k_ho_obs     same grid: the two words of one side into the observations [bsize][2][M]
 //   k_ho_points  one thread per survivor: ho_point of ictr_handover_hd.h on frame 0 into X [3][M]
 //
-// The adjuster (ictr_ba.hip) takes its points, both sides of its observations and its mask by the same kernels.
+// The adjuster (ictr_ba.hip) takes its points, both sides of its observations and its mask by the same kernels, and so
+// does the window camera RANSAC (ictr_camransac.hip), whose winner's words in turn mask the fit and the adjuster.
 //
 // Every thread reads rows[m] once; rows is ascending, so neighbouring lanes read neighbouring (or the same cache line's)
 // words of a history column, and every store is coalesced over m. No atomics, no LDS, plain vector stores. The three
@@ -219,6 +220,92 @@ extern "C" int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, vo
   HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
                         (hipStream_t)hip_stream));
   ictr_ba_filled_(r, 0, 0, 1);
+  return ICTR_OK;
+}
+
+// the window camera RANSAC's inputs from the same window, by the same kernels; its winner's words as a mask
+extern "C" int ictr_camransac_set_points_from_window(ictr_camransac *r, const ictr_stereotrack *t, double baseline) {
+  const char *what = "camransac_set_points_from_window";
+  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_camransac_view d;
+  if (int rc = ictr_camransac_view_(r, &d)) return rc;
+  HoArgs a;
+  if (int rc = ho_window(t, d.n, what, &a)) return rc;
+  if (d.pending) return ho_in_flight(what, "camransac");
+  if (!d.cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_camransac_set_camera comes first", what);
+  const HoCam cam = {d.fc[0], d.fc[1], d.cc[0], d.cc[1]};
+  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.X);
+  HIPCHK(hipGetLastError());
+  ictr_camransac_filled_(r, 1, 0);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_camransac_set_observations_from_window(ictr_camransac *r, const ictr_stereotrack *t) {
+  const char *what = "camransac_set_observations_from_window";
+  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_camransac_view d;
+  if (int rc = ictr_camransac_view_(r, &d)) return rc;
+  HoArgs a;
+  if (int rc = ho_window(t, d.n, what, &a)) return rc;
+  if (d.pending) return ho_in_flight(what, "camransac");
+  if (d.nframes != a.bsize)
+    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the RANSAC was made for %d", what, a.bsize, d.nframes);
+  for (int s = 0; s < d.nsides; ++s)
+    hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, s,
+                       d.xy + (size_t)s * (size_t)a.bsize * 2 * (size_t)a.m);
+  HIPCHK(hipGetLastError());
+  ictr_camransac_filled_(r, 0, 1);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_camfit_set_mask_from_camransac(ictr_camfit *r, const ictr_camransac *s, void *hip_stream) {
+  const char *what = "camfit_set_mask_from_camransac";
+  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_camfit_view d;
+  ictr_camransac_view v;
+  if (int rc = ictr_camfit_view_(r, &d)) return rc;
+  if (int rc = ictr_camransac_view_(s, &v)) return rc;
+  if (d.pending) return ho_in_flight(what, "camfit");
+  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the RANSAC has never run", what);
+  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the RANSAC has %d points, the fit %d", what, v.n, d.n);
+  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
+                        (hipStream_t)hip_stream));
+  ictr_camfit_filled_(r, 0, 0, 1);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_ba_set_mask_from_camransac(ictr_ba *r, const ictr_camransac *s, void *hip_stream) {
+  const char *what = "ba_set_mask_from_camransac";
+  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  ictr_ba_view d;
+  ictr_camransac_view v;
+  if (int rc = ictr_ba_view_(r, &d)) return rc;
+  if (int rc = ictr_camransac_view_(s, &v)) return rc;
+  if (d.pending) return ho_in_flight(what, "ba");
+  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the RANSAC has never run", what);
+  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the RANSAC has %d points, the adjuster %d", what, v.n, d.n);
+  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
+                        (hipStream_t)hip_stream));
+  ictr_ba_filled_(r, 0, 0, 1);
+  return ICTR_OK;
+}
+
+extern "C" int ictr_debug_camransac_inputs(const ictr_camransac *r, double *X, double *xy, uint64_t *words) {
+  if (!r) return fail(ICTR_ERR_INVALID, "debug_camransac_inputs: camransac is NULL");
+  ictr_camransac_view v;
+  if (int rc = ictr_camransac_view_(r, &v)) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  const size_t n = (size_t)v.n;
+  if (X) HIPCHK(hipMemcpy(X, v.X, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (xy) HIPCHK(hipMemcpy(xy, v.xy, sizeof(double) * 2 * (size_t)v.nsides * (size_t)v.nframes * n, hipMemcpyDeviceToHost));
+  if (words) {  // the mask in effect: every point where none is in use (bits past n clear)
+    if (v.use_mask) {
+      HIPCHK(hipMemcpy(words, v.mask, sizeof(uint64_t) * (size_t)v.nwords, hipMemcpyDeviceToHost));
+    } else {
+      for (int w = 0; w < v.nwords; ++w) words[w] = ~0ull;
+      if (v.n & 63) words[v.nwords - 1] = (1ull << (v.n & 63)) - 1ull;
+    }
+  }
   return ICTR_OK;
 }
 

@@ -33,6 +33,7 @@ struct ictr_stereotrack;
 struct ictr_fsplit;
 struct ictr_camfit;
 struct ictr_ba;
+struct ictr_camransac;
 struct ictr_stereotrack_view {
   const double *hist;     // [bsize][4][n]
   const long long *rows;  // [m] start indices of the survivors, ascending
@@ -67,6 +68,16 @@ extern "C" void ictr_fsplit_pairs_filled_(ictr_fsplit *r);
 extern "C" void ictr_camfit_filled_(ictr_camfit *r, int points, int obs, int mask);
 extern "C" int ictr_ba_view_(const ictr_ba *r, ictr_ba_view *v);  // ictr_ba.hip
 extern "C" void ictr_ba_filled_(ictr_ba *r, int points, int obs, int mask);
+struct ictr_camransac_view {
+  double *X, *xy;                   // [3][n], [nsides][nframes][2][n]
+  unsigned long long *mask;         // [nwords] the mask words as set
+  const unsigned long long *words;  // [nwords] the winner's inlier bits of the last run, in the result block on the device
+  int n, nwords, nframes, nsides;
+  int pending, ran, cam_set, use_mask;  // use_mask: the mask words are in use (a non-NULL ictr_camransac_set_mask came last)
+  double fc[2], cc[2];
+};
+extern "C" int ictr_camransac_view_(const ictr_camransac *r, ictr_camransac_view *v);  // ictr_camransac.hip
+extern "C" void ictr_camransac_filled_(ictr_camransac *r, int points, int obs);
 
 namespace ictr {
 
