@@ -27,6 +27,7 @@ import math
 import numpy as np
 
 from . import _lib
+from . import _wininputs as W
 from . import camfit as F
 from ._hostmath import div as _div
 from ._lib import check, dp, f64c
@@ -269,13 +270,7 @@ def _cost(P, sums):
 
 # ---------------------------------------------------------------- arguments
 def _as_obs(xy, n):
-    a = f64c(xy)
-    if a.ndim == 3:
-        a = a[None]
-    if a.ndim != 4 or a.shape[0] not in (1, 2) or a.shape[2] != 2 or a.shape[3] != n:
-        raise ValueError(f"xy must be (S, F, 2, {n}) with S = 1 or 2, got {a.shape}")
-    if not 2 <= a.shape[1] <= MAX_FRAMES:
-        raise ValueError(f"{a.shape[1]} frames (2 .. {MAX_FRAMES})")
+    a = W._as_obs(xy, n, (2, MAX_FRAMES), sides=True)
     if n < MIN_POINTS:
         raise ValueError(f"{n} points (at least {MIN_POINTS})")
     return a
@@ -392,79 +387,24 @@ def adjust_window_host(X, xy, cam, offset=None, mask=None, init=None, detail=Fal
 
 
 # ---------------------------------------------------------------- the device path
-class BundleAdjuster:
+class BundleAdjuster(W._MaskedWindowInputs):
     """The device path: one ictr_ba object for N points seen from S sides in F frames."""
+    KERNELS = ("point", "frames", "decide", "schur", "gather", "solve", "back")
+    _PREFIX, _NOUN, _KINDS = "ba", "adjuster", KERNELS
+    _as_obs = staticmethod(_as_obs)
 
     def __init__(self, n, nframes, nsides=1):
-        self._h = C.c_void_p()
-        check(_lib.load().ictr_ba_create(C.byref(self._h), int(n), int(nframes), int(nsides)))
-        self.n, self.nframes, self.nsides = int(n), int(nframes), int(nsides)
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            _lib.load().ictr_ba_destroy(self._h)
-            self._h = None
-
-    def set_points(self, X):
-        a = F._as_points(X)
-        if a.shape[1] != self.n:
-            raise ValueError(f"X {a.shape}, the adjuster was made for (3, {self.n})")
-        check(_lib.load().ictr_ba_set_points(self._h, dp(a)))
-
-    def set_observations(self, xy):
-        a = _as_obs(xy, self.n)
-        if a.shape[:2] != (self.nsides, self.nframes):
-            raise ValueError(f"xy {a.shape}, the adjuster was made for ({self.nsides}, {self.nframes}, 2, {self.n})")
-        check(_lib.load().ictr_ba_set_observations(self._h, dp(a)))
-
-    def set_mask(self, mask=None):
-        w = F._words_of(mask, self.n)
-        check(_lib.load().ictr_ba_set_mask(self._h, None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint64))))
-
-    def set_camera(self, cam):
-        fx, fy, cx, cy = F._as_cam(cam)
-        check(_lib.load().ictr_ba_set_camera(self._h, dp(np.array([fx, fy])), dp(np.array([cx, cy]))))
+        self._create(n, nframes, nsides)
 
     def set_offset(self, offset=None):
         check(_lib.load().ictr_ba_set_offset(self._h, dp(np.array(_as_offset(offset)))))
-
-    def set_points_from_window(self, win, baseline):
-        """points_from_first_view(depth_from_disparity(...)) of a counted StereoTrackWindow, on the device, with the
-        camera of set_camera, which comes first."""
-        check(_lib.load().ictr_ba_set_points_from_window(self._h, win._h, float(baseline)))
-
-    def set_observations_from_window(self, win):
-        """observations_from_stereo_tracks of a counted StereoTrackWindow, on the device: the left side and, for an
-        adjuster of two sides, the right one."""
-        check(_lib.load().ictr_ba_set_observations_from_window(self._h, win._h))
-
-    def set_mask_from_fsplit(self, splitter, stream=None):
-        """The inlier words of the StaticSplitter's last run, waited for or in flight, copied on the device on `stream`
-        (the stream of that run)."""
-        sp = getattr(stream, "cuda_stream", stream)
-        check(_lib.load().ictr_ba_set_mask_from_fsplit(self._h, splitter._h, C.c_void_p(sp or 0)))
-
-    def set_mask_from_camransac(self, ransac, stream=None):
-        """The winner's inlier words of the CameraRansac's last run, waited for or in flight, copied on the device on
-        `stream` (the stream of that run)."""
-        sp = getattr(stream, "cuda_stream", stream)
-        check(_lib.load().ictr_ba_set_mask_from_camransac(self._h, ransac._h, C.c_void_p(sp or 0)))
-
-    def debug_inputs(self):
-        """Inspection (ictr_debug_ba_inputs): dict X (3, N), xy (S, F, 2, N), words (ceil(N / 64),) as they stand on the
-        device."""
-        X, xy = np.zeros((3, self.n)), np.zeros((self.nsides, self.nframes, 2, self.n))
-        words = np.zeros((self.n + 63) // 64, np.uint64)
-        check(_lib.load().ictr_debug_ba_inputs(self._h, dp(X), dp(xy), words.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return dict(X=X, xy=xy, words=words)
 
     def run_async(self, init=None, stream=None, **schedule):
         prm = dict(DEFAULTS)
         prm.update(schedule)
         G0 = F._as_poses(init, self.nframes)
-        sp = getattr(stream, "cuda_stream", stream)
         check(_lib.load().ictr_ba_run(self._h, dp(G0), int(prm["noiter"]), float(prm["damp_init"]), float(prm["damp_fct"]),
-                                      float(prm["minres"]), float(prm["maxdamp"]), C.c_void_p(sp or 0)))
+                                      float(prm["minres"]), float(prm["maxdamp"]), W._stream(stream)))
 
     def wait(self, points=True):
         """The result of the run in flight; points = False leaves the points on the device (X is None)."""
@@ -474,18 +414,6 @@ class BundleAdjuster:
         check(_lib.load().ictr_ba_wait(self._h, dp(G), None if X is None else dp(X), C.byref(cost), C.byref(damp),
                                        C.byref(iters), C.byref(status), C.byref(n)))
         return _result(G, X, cost.value, damp.value, iters.value, status.value, n.value)
-
-    def set_timing(self, on=True):
-        """Record device time stamps around the launches of the next runs (kernel_times)."""
-        check(_lib.load().ictr_ba_set_timing(self._h, int(bool(on))))
-
-    KERNELS = ("point", "frames", "decide", "schur", "gather", "solve", "back")
-
-    def kernel_times(self):
-        """ms of the last waited run per kernel kind, summed over its launches."""
-        ms = np.zeros(len(self.KERNELS), np.float32)
-        check(_lib.load().ictr_ba_get_kernel_times(self._h, ms.ctypes.data_as(_lib.FP)))
-        return dict(zip(self.KERNELS, (float(v) for v in ms)))
 
     def debug_system(self, G, damp, X=None):
         """Inspection (ictr_debug_ba_system): the passes, the Schur pass and the assembly alone at the poses G and the

@@ -31,6 +31,7 @@ import numpy as np
 from . import _lib
 from ._hostmath import div as _div
 from ._lib import check, dp, f64c
+from ._wininputs import _MaskedWindowInputs, _as_cam, _as_obs, _as_points, _stream, _words_of
 
 __all__ = ["CameraFitter", "fit_cameras", "fit_cameras_host", "reprojection_errors", "reprojection_errors_host",
            "pass_host", "depth_from_disparity", "points_from_first_view", "observations_from_stereo_tracks", "CHUNK",
@@ -234,30 +235,6 @@ def _step(s, sums, prm):
 
 
 # ---------------------------------------------------------------- arguments
-def _as_points(X):
-    a = f64c(X)
-    if a.ndim != 2 or a.shape[0] != 3 or a.shape[1] < 1:
-        raise ValueError(f"X must be (3, N), got {a.shape}")
-    return a
-
-
-def _as_obs(xy, n):
-    a = f64c(xy)
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim != 3 or a.shape[1] != 2 or a.shape[2] != n:
-        raise ValueError(f"xy must be (F, 2, {n}), got {a.shape}")
-    return a
-
-
-def _as_cam(cam):
-    fc, cc = cam
-    fc, cc = f64c(fc).reshape(-1), f64c(cc).reshape(-1)
-    if fc.size != 2 or cc.size != 2:
-        raise ValueError("cam must be (fc (2,), cc (2,))")
-    return float(fc[0]), float(fc[1]), float(cc[0]), float(cc[1])
-
-
 def _as_poses(G, nframes):
     if G is None:
         G = np.tile(np.eye(3, 4).reshape(1, 12), (nframes, 1))
@@ -265,23 +242,6 @@ def _as_poses(G, nframes):
     if a.shape[0] != nframes:
         raise ValueError(f"{a.shape[0]} poses for {nframes} frames")
     return a
-
-
-def _words_of(mask, n):
-    """The inlier words of a mask: None, bool (N,), or uint64 words already (ceil(N / 64),)."""
-    if mask is None:
-        return None
-    m = np.asarray(mask)
-    nwords = (n + 63) // 64
-    if m.dtype == np.uint64:
-        if m.shape != (nwords,):
-            raise ValueError(f"{m.shape} mask words for {n} points")
-        return np.ascontiguousarray(m)
-    if m.dtype != bool or m.shape != (n,):
-        raise ValueError(f"mask must be bool ({n},) or uint64 ({nwords},)")
-    bits = np.zeros(nwords * 64, np.uint8)
-    bits[:n] = m
-    return np.packbits(bits.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view(np.uint64).copy()
 
 
 def _bits_of(words, n):
@@ -383,76 +343,24 @@ def reprojection_errors_host(X, xy, cam, G, mask=None, offset=None):
 
 
 # ---------------------------------------------------------------- the device path
-class CameraFitter:
+class CameraFitter(_MaskedWindowInputs):
     """The device path: one ictr_camfit object for N points seen in F frames."""
+    _PREFIX, _NOUN, _KINDS = "camfit", "fitter", ("pass", "step")
 
     def __init__(self, n, nframes):
-        self._h = C.c_void_p()
-        check(_lib.load().ictr_camfit_create(C.byref(self._h), int(n), int(nframes)))
-        self.n, self.nframes = int(n), int(nframes)
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            _lib.load().ictr_camfit_destroy(self._h)
-            self._h = None
-
-    def set_points(self, X):
-        a = _as_points(X)
-        if a.shape[1] != self.n:
-            raise ValueError(f"X {a.shape}, the fitter was made for (3, {self.n})")
-        check(_lib.load().ictr_camfit_set_points(self._h, dp(a)))
-
-    def set_observations(self, xy):
-        a = _as_obs(xy, self.n)
-        if a.shape[0] != self.nframes:
-            raise ValueError(f"xy {a.shape}, the fitter was made for ({self.nframes}, 2, {self.n})")
-        check(_lib.load().ictr_camfit_set_observations(self._h, dp(a)))
-
-    def set_mask(self, mask=None):
-        w = _words_of(mask, self.n)
-        check(_lib.load().ictr_camfit_set_mask(self._h, None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint64))))
-
-    def set_camera(self, cam):
-        fx, fy, cx, cy = _as_cam(cam)
-        check(_lib.load().ictr_camfit_set_camera(self._h, dp(np.array([fx, fy])), dp(np.array([cx, cy]))))
-
-    def set_points_from_window(self, win, baseline):
-        """points_from_first_view(depth_from_disparity(...)) of a counted StereoTrackWindow, on the device
-        (ictr_camfit_set_points_from_window) with the camera of set_camera, which comes first."""
-        check(_lib.load().ictr_camfit_set_points_from_window(self._h, win._h, float(baseline)))
+        self._create(n, nframes)
 
     def set_observations_from_window(self, win, right=False):
         """One side of observations_from_stereo_tracks of a counted StereoTrackWindow, on the device."""
-        check(_lib.load().ictr_camfit_set_observations_from_window(self._h, win._h, int(bool(right))))
-
-    def set_mask_from_fsplit(self, splitter, stream=None):
-        """The inlier words of the StaticSplitter's last run, waited for or in flight, copied on the device on `stream`
-        (the stream of that run)."""
-        sp = getattr(stream, "cuda_stream", stream)
-        check(_lib.load().ictr_camfit_set_mask_from_fsplit(self._h, splitter._h, C.c_void_p(sp or 0)))
-
-    def set_mask_from_camransac(self, ransac, stream=None):
-        """The winner's inlier words of the CameraRansac's last run, waited for or in flight, copied on the device on
-        `stream` (the stream of that run)."""
-        sp = getattr(stream, "cuda_stream", stream)
-        check(_lib.load().ictr_camfit_set_mask_from_camransac(self._h, ransac._h, C.c_void_p(sp or 0)))
-
-    def debug_inputs(self):
-        """Inspection (ictr_debug_camfit_inputs): dict X (3, N), xy (F, 2, N), words (ceil(N / 64),) as they stand on the
-        device."""
-        X, xy = np.zeros((3, self.n)), np.zeros((self.nframes, 2, self.n))
-        words = np.zeros((self.n + 63) // 64, np.uint64)
-        check(_lib.load().ictr_debug_camfit_inputs(self._h, dp(X), dp(xy), words.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return dict(X=X, xy=xy, words=words)
+        check(self._c("set_observations_from_window")(self._h, win._h, int(bool(right))))
 
     def run_async(self, init=None, stream=None, **schedule):
         prm = dict(DEFAULTS)
         prm.update(schedule)
         G0 = _as_poses(init, self.nframes)
-        sp = getattr(stream, "cuda_stream", stream)
         check(_lib.load().ictr_camfit_run(self._h, dp(G0), int(prm["noiter"]), float(prm["damp_init"]),
                                           float(prm["damp_fct"]), float(prm["minres"]), float(prm["maxdamp"]),
-                                          C.c_void_p(sp or 0)))
+                                          _stream(stream)))
 
     def wait(self):
         F = self.nframes
@@ -470,16 +378,6 @@ class CameraFitter:
         check(_lib.load().ictr_camfit_reproj(self._h, dp(G), None if dt is None else dp(dt), dp(err),
                                              n.ctypes.data_as(C.POINTER(C.c_int64))))
         return err, n
-
-    def set_timing(self, on=True):
-        """Record device time stamps around the launches of the next runs (kernel_times)."""
-        check(_lib.load().ictr_camfit_set_timing(self._h, int(bool(on))))
-
-    def kernel_times(self):
-        """ms of the last waited run spent in (pass, step), summed over its launches."""
-        ms = np.zeros(2, np.float32)
-        check(_lib.load().ictr_camfit_get_kernel_times(self._h, ms.ctypes.data_as(_lib.FP)))
-        return dict(zip(("pass", "step"), (float(v) for v in ms)))
 
     def debug_pass(self, G):
         """Inspection (ictr_debug_camfit_pass): k_camfit_pass and the ordered sum alone at the poses G. dict: n (F,),

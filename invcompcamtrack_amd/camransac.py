@@ -28,9 +28,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _wininputs as W
 from . import ransac as _ransac
 from ._hostmath import M64 as _M64, draw_indices_n
 from ._lib import check, dp, f64c
+from ._wininputs import _pack_words
 from .camfit import _DBL_MAX, _as_cam, _as_points, _bits_of, _project, _words_of
 
 __all__ = ["window_ransac", "window_ransac_host", "CameraRansac", "MAX_TRIALS", "MAX_FRAMES"]
@@ -41,14 +43,7 @@ MAX_FRAMES = 64  # kCrMaxFrames
 
 def _as_obs(xy, n):
     """(S, F, 2, N); (F, 2, N) is one side."""
-    a = f64c(xy)
-    if a.ndim == 3:
-        a = a[None]
-    if a.ndim != 4 or a.shape[0] not in (1, 2) or a.shape[2] != 2 or a.shape[3] != n:
-        raise ValueError(f"xy must be (S, F, 2, {n}) with S = 1 or 2, got {a.shape}")
-    if not 1 <= a.shape[1] <= MAX_FRAMES:
-        raise ValueError(f"{a.shape[1]} frames (1 .. {MAX_FRAMES})")
-    return a
+    return W._as_obs(xy, n, (1, MAX_FRAMES), sides=True)
 
 
 def _as_offset(offset, nsides):
@@ -121,13 +116,6 @@ def _distances(G, X, xy, cam, off):
     return np.where(dd != dd, np.nan, dd)
 
 
-def _pack_words(mask):
-    n = mask.size
-    bits = np.zeros((n + 63) // 64 * 64, np.uint8)
-    bits[:n] = mask
-    return np.packbits(bits.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view(np.uint64).copy()
-
-
 def _log(G):
     """p (F, 6) = se3_log(G) by the library's host log map; NaN where G is."""
     G = f64c(G).reshape(-1, 12)
@@ -190,78 +178,24 @@ def window_ransac_host(X, xy, cam, offset=None, mask=None, ntrials=100, thresh=2
     return out
 
 
-class CameraRansac:
-    """The device path: one ictr_camransac object for N points seen in F frames from S sides."""
+class CameraRansac(W._WindowInputs):
+    """The device path: one ictr_camransac object for N points seen in F frames from S sides. debug_inputs answers in
+    words the mask in effect: every point's bit where no mask is set."""
+    _PREFIX, _NOUN, _KINDS = "camransac", "RANSAC", ("hyp", "score", "select", "mask")  # mask: flags + mask
+    _as_obs = staticmethod(_as_obs)
 
     def __init__(self, n, nframes, nsides=2):
-        self._h = C.c_void_p()
-        check(_lib.load().ictr_camransac_create(C.byref(self._h), int(n), int(nframes), int(nsides)))
-        self.n, self.nframes, self.nsides = int(n), int(nframes), int(nsides)
-        self.nwords = (self.n + 63) // 64
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            _lib.load().ictr_camransac_destroy(self._h)
-            self._h = None
+        self._create(n, nframes, nsides)
 
     @property
     def chunk(self):
         return _lib.load().ictr_camransac_chunk_size(self._h)
 
-    def set_points(self, X):
-        a = _as_points(X)
-        if a.shape[1] != self.n:
-            raise ValueError(f"X {a.shape}, the RANSAC was made for (3, {self.n})")
-        check(_lib.load().ictr_camransac_set_points(self._h, dp(a)))
-
-    def set_observations(self, xy):
-        a = _as_obs(xy, self.n)
-        if a.shape[0] != self.nsides or a.shape[1] != self.nframes:
-            raise ValueError(f"xy {a.shape}, the RANSAC was made for ({self.nsides}, {self.nframes}, 2, {self.n})")
-        check(_lib.load().ictr_camransac_set_observations(self._h, dp(a)))
-
-    def set_mask(self, mask=None):
-        w = _words_of(mask, self.n)
-        check(_lib.load().ictr_camransac_set_mask(self._h, None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint64))))
-
-    def set_camera(self, cam):
-        fx, fy, cx, cy = _as_cam(cam)
-        check(_lib.load().ictr_camransac_set_camera(self._h, dp(np.array([fx, fy])), dp(np.array([cx, cy]))))
-
     def set_offset(self, offset):
         check(_lib.load().ictr_camransac_set_offset(self._h, dp(f64c(offset).reshape(3))))
 
-    def set_points_from_window(self, win, baseline):
-        """points_from_first_view(depth_from_disparity(...)) of a counted StereoTrackWindow, on the device, with the
-        camera of set_camera, which comes first."""
-        check(_lib.load().ictr_camransac_set_points_from_window(self._h, win._h, float(baseline)))
-
-    def set_observations_from_window(self, win):
-        """observations_from_stereo_tracks of a counted StereoTrackWindow, on the device: the left side and, with two
-        sides, the right one."""
-        check(_lib.load().ictr_camransac_set_observations_from_window(self._h, win._h))
-
-    def debug_inputs(self):
-        """Inspection (ictr_debug_camransac_inputs): dict X (3, N), xy (S, F, 2, N), words (the mask in effect: every
-        point's bit where no mask is set)."""
-        X, xy = np.zeros((3, self.n)), np.zeros((self.nsides, self.nframes, 2, self.n))
-        words = np.zeros(self.nwords, np.uint64)
-        check(_lib.load().ictr_debug_camransac_inputs(self._h, dp(X), dp(xy), words.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return dict(X=X, xy=xy, words=words)
-
     def run_async(self, ntrials=100, thresh=2.0, seed=0, stream=None):
-        sp = getattr(stream, "cuda_stream", stream)
-        check(_lib.load().ictr_camransac_run(self._h, int(ntrials), float(thresh), int(seed) & _M64, C.c_void_p(sp or 0)))
-
-    def set_timing(self, on=True):
-        """Record the stages' device time stamps on the next runs (kernel_times)."""
-        check(_lib.load().ictr_camransac_set_timing(self._h, int(bool(on))))
-
-    def kernel_times(self):
-        """ms of the last waited run spent in (hyp, score, select, flags + mask), summed over the chunks."""
-        ms = np.zeros(4, np.float32)
-        check(_lib.load().ictr_camransac_get_kernel_times(self._h, ms.ctypes.data_as(_lib.FP)))
-        return dict(zip(("hyp", "score", "select", "mask"), (float(v) for v in ms)))
+        check(_lib.load().ictr_camransac_run(self._h, int(ntrials), float(thresh), int(seed) & _M64, W._stream(stream)))
 
     def debug_trials(self, thresh=2.0, seed=0, first_trial=0, count=1):
         """Inspection (ictr_debug_camransac_trials): the hypothesis and score kernels alone over trials first_trial ..

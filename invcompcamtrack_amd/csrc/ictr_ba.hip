@@ -33,6 +33,7 @@
 #include "ictr_ba_hd.h"
 #include "ictr_dev.h"
 #include "ictr_launch.h"
+#include "ictr_wininputs.h"
 
 namespace ictr {
 
@@ -349,13 +350,11 @@ using namespace ictr;
 
 // ---------------------------------------------------------------- host side
 struct ictr_ba {
-  int n = 0, nwords = 0, nchunks = 0, nframes = 0, nsides = 0, npairs = 0, dim = 0;
-  DevBuf<double> d_xy, d_Xin, d_X[2], d_V[2], d_gp[2], d_Xout, d_fpart, d_ppart, d_fsums, d_T, d_A, d_rhs;
-  DevBuf<unsigned long long> d_words, d_adjw;
+  WinInputs in;  // in.X: the points as set
+  int nchunks = 0, npairs = 0, dim = 0;
+  DevBuf<double> d_X[2], d_V[2], d_gp[2], d_Xout, d_fpart, d_ppart, d_fsums, d_T, d_A, d_rhs;
+  DevBuf<unsigned long long> d_adjw;
   PinBuf<char> up;  // the initial state of a run, uploaded on its stream
-  CfCam cam = {0, 0, 0, 0};
-  double off[3] = {0, 0, 0};
-  bool points_set = false, obs_set = false, cam_set = false, off_set = false, use_mask = false;
   bool timing = false, timed = false;  // timed: the run in flight (or last waited) carries events
   std::vector<Event> tev;              // one before every launch of a round and one after the last
   float ms[kBaKinds] = {0, 0, 0, 0, 0, 0, 0};
@@ -371,21 +370,16 @@ extern "C" int ictr_ba_create(ictr_ba **out, int64_t n, int64_t nframes, int64_t
   if (nsides < 1 || nsides > 2) return fail(ICTR_ERR_INVALID, "ba_create: %lld sides (1 or 2)", (long long)nsides);
   if (int rc = need_device()) return rc;
   auto r = std::make_unique<ictr_ba>();
-  r->n = (int)n;
-  r->nwords = (int)((n + 63) / 64);
   r->nchunks = (int)((n + kCfChunk - 1) / kCfChunk);
-  r->nframes = (int)nframes;
-  r->nsides = (int)nsides;
-  r->npairs = ba_npairs(r->nframes);
-  r->dim = 6 * (r->nframes - 1);
-  const size_t N = (size_t)n, F = (size_t)nframes, S = (size_t)nsides, D = sizeof(double);
-  if (int rc = r->d_xy.alloc(D * 2 * S * F * N, true)) return rc;
+  r->npairs = ba_npairs((int)nframes);
+  r->dim = 6 * ((int)nframes - 1);
+  const size_t N = (size_t)n, F = (size_t)nframes, D = sizeof(double);
+  if (int rc = r->in.alloc((int)n, (int)nframes, (int)nsides)) return rc;
   for (int e = 0; e < 2; ++e) {
     if (int rc = r->d_X[e].alloc(D * 3 * N, true)) return rc;
     if (int rc = r->d_V[e].alloc(D * 6 * N, true)) return rc;
     if (int rc = r->d_gp[e].alloc(D * 3 * N, true)) return rc;
   }
-  if (int rc = r->d_Xin.alloc(D * 3 * N, true)) return rc;
   if (int rc = r->d_Xout.alloc(D * 3 * N, true)) return rc;
   if (int rc = r->d_fpart.alloc(D * kCfSlots * F * (size_t)r->nchunks, true)) return rc;
   if (int rc = r->d_ppart.alloc(D * kBaPairSlots * (size_t)r->npairs * (size_t)r->nchunks, true)) return rc;
@@ -393,8 +387,7 @@ extern "C" int ictr_ba_create(ictr_ba **out, int64_t n, int64_t nframes, int64_t
   if (int rc = r->d_T.alloc(D * kBaPairSlots * (size_t)r->npairs, true)) return rc;
   if (int rc = r->d_A.alloc(D * (size_t)(r->dim * (r->dim + 1) / 2), true)) return rc;
   if (int rc = r->d_rhs.alloc(D * (size_t)r->dim, true)) return rc;
-  if (int rc = r->d_words.alloc(sizeof(unsigned long long) * (size_t)r->nwords, true)) return rc;
-  if (int rc = r->d_adjw.alloc(sizeof(unsigned long long) * (size_t)r->nwords, true)) return rc;
+  if (int rc = r->d_adjw.alloc(sizeof(unsigned long long) * (size_t)r->in.nwords, true)) return rc;
   if (int rc = r->up.alloc(sizeof(BaState))) return rc;
   if (int rc = r->out.reserve(sizeof(BaState), true)) return rc;
   *out = r.release();
@@ -404,72 +397,24 @@ extern "C" int ictr_ba_create(ictr_ba **out, int64_t n, int64_t nframes, int64_t
 extern "C" void ictr_ba_destroy(ictr_ba *r) { delete r; }
 
 extern "C" int ictr_ba_set_points(ictr_ba *r, const double *X) {
-  if (!r || !X) return fail(ICTR_ERR_INVALID, "ba_set_points: NULL argument");
-  if (int rc = r->out.refuse("ba_set_points", "ba")) return rc;
-  HIPCHK(hipMemcpy(r->d_Xin.get(), X, sizeof(double) * 3 * (size_t)r->n, hipMemcpyHostToDevice));
-  r->points_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_points("ba_set_points", "ba", r->out, X) : null_object("ba_set_points");
 }
-
 extern "C" int ictr_ba_set_observations(ictr_ba *r, const double *xy) {
-  if (!r || !xy) return fail(ICTR_ERR_INVALID, "ba_set_observations: NULL argument");
-  if (int rc = r->out.refuse("ba_set_observations", "ba")) return rc;
-  HIPCHK(hipMemcpy(r->d_xy.get(), xy, sizeof(double) * 2 * (size_t)r->nsides * (size_t)r->nframes * (size_t)r->n,
-                   hipMemcpyHostToDevice));
-  r->obs_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_observations("ba_set_observations", "ba", r->out, xy) : null_object("ba_set_observations");
 }
-
 extern "C" int ictr_ba_set_mask(ictr_ba *r, const uint64_t *words) {
-  if (!r) return fail(ICTR_ERR_INVALID, "ba is NULL");
-  if (int rc = r->out.refuse("ba_set_mask", "ba")) return rc;
-  if (words) HIPCHK(hipMemcpy(r->d_words.get(), words, sizeof(uint64_t) * (size_t)r->nwords, hipMemcpyHostToDevice));
-  r->use_mask = words != nullptr;
-  return ICTR_OK;
+  return r ? r->in.set_mask("ba_set_mask", "ba", r->out, words) : fail(ICTR_ERR_INVALID, "ba is NULL");
 }
-
 extern "C" int ictr_ba_set_camera(ictr_ba *r, const double *fc, const double *cc) {
-  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "ba_set_camera: NULL argument");
-  if (int rc = r->out.refuse("ba_set_camera", "ba")) return rc;
-  for (int q = 0; q < 2; ++q)
-    if (!cf_finite(fc[q]) || !cf_finite(cc[q]) || fc[q] == 0.0)
-      return fail(ICTR_ERR_INVALID, "ba_set_camera: fc must be finite and not 0, cc finite");
-  r->cam = {fc[0], fc[1], cc[0], cc[1]};
-  r->cam_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_camera("ba_set_camera", "ba", r->out, fc, cc) : null_object("ba_set_camera");
 }
-
 extern "C" int ictr_ba_set_offset(ictr_ba *r, const double *offset) {
-  if (!r || !offset) return fail(ICTR_ERR_INVALID, "ba_set_offset: NULL argument");
-  if (int rc = r->out.refuse("ba_set_offset", "ba")) return rc;
-  for (int q = 0; q < 3; ++q)
-    if (!cf_finite(offset[q])) return fail(ICTR_ERR_INVALID, "ba_set_offset: the offset is not finite");
-  memcpy(r->off, offset, sizeof(r->off));
-  r->off_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_offset("ba_set_offset", "ba", r->out, offset) : null_object("ba_set_offset");
 }
 
-extern "C" int ictr_ba_view_(const ictr_ba *r, ictr_ba_view *v) {
-  v->X = r->d_Xin.get();
-  v->xy = r->d_xy.get();
-  v->words = r->d_words.get();
-  v->n = r->n;
-  v->nwords = r->nwords;
-  v->nframes = r->nframes;
-  v->nsides = r->nsides;
-  v->pending = r->out.pending();
-  v->cam_set = r->cam_set;
-  v->fc[0] = r->cam.fx;
-  v->fc[1] = r->cam.fy;
-  v->cc[0] = r->cam.cx;
-  v->cc[1] = r->cam.cy;
+extern "C" int ictr_ba_inputs_(ictr_ba *r, WinDest *d) {
+  *d = {&r->in, &r->out, "ba", "adjuster"};
   return ICTR_OK;
-}
-
-extern "C" void ictr_ba_filled_(ictr_ba *r, int points, int obs, int mask) {
-  r->points_set = r->points_set || points != 0;
-  r->obs_set = r->obs_set || obs != 0;
-  r->use_mask = r->use_mask || mask != 0;
 }
 
 extern "C" int ictr_ba_set_timing(ictr_ba *r, int on) {
@@ -479,36 +424,27 @@ extern "C" int ictr_ba_set_timing(ictr_ba *r, int on) {
   return ICTR_OK;
 }
 
-// what every entry that launches needs first
-static int ba_ready(const ictr_ba *r, const char *what) {
-  if (int rc = r->out.refuse(what, "ba")) return rc;
-  if (!r->points_set || !r->obs_set || !r->cam_set || (r->nsides == 2 && !r->off_set))
-    return fail(ICTR_ERR_STATE, "%s: set_points, set_observations, set_camera and, with two sides, set_offset come first",
-                what);
-  return ICTR_OK;
-}
-
 static void ba_fill_args(const ictr_ba *r, const CfParams &p, BaArgs &a) {
   memset(&a, 0, sizeof(a));
-  a.xy = r->d_xy.get();
-  a.words = r->use_mask ? r->d_words.get() : nullptr;
+  a.xy = r->in.xy.get();
+  a.words = r->in.mask_or_null();
   a.adjw = r->d_adjw.get();
-  a.Xin = r->d_Xin.get();
+  a.Xin = r->in.X.get();
   for (int e = 0; e < 2; ++e) {
     a.X[e] = r->d_X[e].get();
     a.V[e] = r->d_V[e].get();
     a.gp[e] = r->d_gp[e].get();
   }
   a.Xout = r->d_Xout.get();
-  a.n = r->n;
-  a.nwords = r->nwords;
+  a.n = r->in.n;
+  a.nwords = r->in.nwords;
   a.nchunks = r->nchunks;
-  a.nframes = r->nframes;
-  a.nsides = r->nsides;
+  a.nframes = r->in.nframes;
+  a.nsides = r->in.nsides;
   a.npairs = r->npairs;
-  a.cam = r->cam;
+  a.cam = r->in.cam;
   a.prm = p;
-  for (int q = 0; q < 3; ++q) a.off[1][q] = r->off[q];
+  for (int q = 0; q < 3; ++q) a.off[1][q] = r->in.off[q];
   a.fpart = r->d_fpart.get();
   a.ppart = r->d_ppart.get();
   a.fsums = r->d_fsums.get();
@@ -527,12 +463,12 @@ static int ba_poses_finite(const double *G, int nframes, const char *what) {
 extern "C" int ictr_ba_run(ictr_ba *r, const double *G0, int32_t noiter, double damp_init, double damp_fct, double minres,
                            double maxdamp, void *hip_stream) {
   if (!r || !G0) return fail(ICTR_ERR_INVALID, "ba_run: NULL argument");
-  if (int rc = ba_ready(r, "ba_run")) return rc;
+  if (int rc = r->in.ready("ba_run", r->out, "ba")) return rc;
   if (noiter < 0 || noiter > kBaMaxIter) return fail(ICTR_ERR_INVALID, "ba_run: noiter %d (0 .. %d)", noiter, kBaMaxIter);
   if (!(damp_init > 0.0) || !cf_finite(damp_init) || !(damp_fct > 1.0) || !cf_finite(damp_fct) || !(minres >= 0.0) ||
       !cf_finite(minres) || !(maxdamp > 0.0))
     return fail(ICTR_ERR_INVALID, "ba_run: needs damp_init > 0, damp_fct > 1, minres >= 0 (all finite), maxdamp > 0");
-  if (int rc = ba_poses_finite(G0, r->nframes, "ba_run")) return rc;
+  if (int rc = ba_poses_finite(G0, r->in.nframes, "ba_run")) return rc;
   const CfParams p = {noiter, damp_init, damp_fct, minres, maxdamp};
   BaArgs a;
   ba_fill_args(r, p, a);
@@ -542,10 +478,10 @@ extern "C" int ictr_ba_run(ictr_ba *r, const double *G0, int32_t noiter, double 
     for (Event &e : tev)
       if (int rc = e.create()) return rc;
   }
-  ba_init(*reinterpret_cast<BaState *>(r->up.get()), G0, r->nframes, p);
+  ba_init(*reinterpret_cast<BaState *>(r->up.get()), G0, r->in.nframes, p);
   hipStream_t s = (hipStream_t)hip_stream;
   HIPCHK(hipMemcpyAsync(r->out.dev(), r->up.get(), sizeof(BaState), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_ba_flags, dim3(ba_grid((size_t)r->n)), dim3(kBaBlock), 0, s, a);
+  hipLaunchKernelGGL(k_ba_flags, dim3(ba_grid((size_t)r->in.n)), dim3(kBaBlock), 0, s, a);
   size_t e = 0;
   for (int it = 0; it <= noiter; ++it) {
     for (int kind = 0; kind < kBaKinds; ++kind) {
@@ -555,7 +491,7 @@ extern "C" int ictr_ba_run(ictr_ba *r, const double *G0, int32_t noiter, double 
     HIPCHK(hipGetLastError());
   }
   if (r->timing) HIPCHK(hipEventRecord(tev[e++].get(), s));
-  hipLaunchKernelGGL(k_ba_final, dim3(ba_grid(3 * (size_t)r->n)), dim3(kBaBlock), 0, s, a);
+  hipLaunchKernelGGL(k_ba_final, dim3(ba_grid(3 * (size_t)r->in.n)), dim3(kBaBlock), 0, s, a);
   HIPCHK(hipGetLastError());
   if (int rc = r->out.post(sizeof(BaState), s)) return rc;
   r->tev = std::move(tev);
@@ -569,7 +505,7 @@ extern "C" int ictr_ba_wait(ictr_ba *r, double *G, double *X, double *cost, doub
   if (!r->out.pending()) return fail(ICTR_ERR_STATE, "ba_wait: nothing has been run");
   if (int rc = r->out.wait()) return rc;
   const BaState *st = reinterpret_cast<const BaState *>(r->out.host());
-  if (G) memcpy(G, st->G, sizeof(double) * 12 * (size_t)r->nframes);
+  if (G) memcpy(G, st->G, sizeof(double) * 12 * (size_t)r->in.nframes);
   if (cost) *cost = st->c;
   if (damp) *damp = st->damp;
   if (iters) *iters = st->it;
@@ -585,7 +521,7 @@ extern "C" int ictr_ba_wait(ictr_ba *r, double *G, double *X, double *cost, doub
     memcpy(r->ms, ms, sizeof(ms));
     r->tev.clear();
   }
-  if (X) HIPCHK(hipMemcpy(X, r->d_Xout.get(), sizeof(double) * 3 * (size_t)r->n, hipMemcpyDeviceToHost));
+  if (X) HIPCHK(hipMemcpy(X, r->d_Xout.get(), sizeof(double) * 3 * (size_t)r->in.n, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 
@@ -600,21 +536,21 @@ extern "C" int ictr_debug_ba_system(ictr_ba *r, const double *G, const double *X
                                     double *A, double *rhs, double *V, double *gp, int64_t *nfail) {
   if (!r || !G || !n || !cost || !A || !rhs || !V || !gp || !nfail)
     return fail(ICTR_ERR_INVALID, "debug_ba_system: NULL argument");
-  if (int rc = ba_ready(r, "debug_ba_system")) return rc;
-  if (int rc = ba_poses_finite(G, r->nframes, "debug_ba_system")) return rc;
+  if (int rc = r->in.ready("debug_ba_system", r->out, "ba")) return rc;
+  if (int rc = ba_poses_finite(G, r->in.nframes, "debug_ba_system")) return rc;
   if (!(damp >= 0.0) || !cf_finite(damp)) return fail(ICTR_ERR_INVALID, "debug_ba_system: damp must be finite and >= 0");
   const CfParams p = {0, damp > 0.0 ? damp : 1.0, 2.0, 0.0, 1.0};
   BaArgs a;
   ba_fill_args(r, p, a);
   a.debug = 1;
   const int e = X ? 1 : 0;
-  const size_t N = (size_t)r->n, D = sizeof(double);
+  const size_t N = (size_t)r->in.n, D = sizeof(double);
   if (X) {  // the given points go through the second set
     HIPCHK(hipMemcpy(r->d_X[1].get(), X, D * 3 * N, hipMemcpyHostToDevice));
     a.Xin = r->d_X[1].get();
   }
   auto st = std::make_unique<BaState>();
-  ba_init(*st, G, r->nframes, p);
+  ba_init(*st, G, r->in.nframes, p);
   st->damp = damp;
   st->cur = st->tset = e;
   HIPCHK(hipMemcpy(r->out.dev(), st.get(), sizeof(BaState), hipMemcpyHostToDevice));

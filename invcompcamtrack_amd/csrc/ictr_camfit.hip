@@ -22,6 +22,7 @@
 #include "ictr_camfit_hd.h"
 #include "ictr_dev.h"
 #include "ictr_launch.h"
+#include "ictr_wininputs.h"
 
 namespace ictr {
 
@@ -139,12 +140,10 @@ using namespace ictr;
 
 // ---------------------------------------------------------------- host side
 struct ictr_camfit {
-  int n = 0, nwords = 0, nchunks = 0, nframes = 0;
-  DevBuf<double> d_X, d_xy, d_part;
-  DevBuf<unsigned long long> d_words;
+  WinInputs in;  // one side
+  int nchunks = 0;
+  DevBuf<double> d_part;
   PinBuf<char> up;  // the frames' initial states of a run, uploaded on its stream
-  CfCam cam = {0, 0, 0, 0};
-  bool points_set = false, obs_set = false, cam_set = false, use_mask = false;
   bool timing = false, timed = false;  // timed: the run in flight (or last waited) carries events
   std::vector<Event> tev;              // one before every launch and one after the last
   float ms[2] = {0, 0};
@@ -152,7 +151,7 @@ struct ictr_camfit {
   Readback out;  // CfState [nframes]
 };
 
-static size_t cf_bytes(const ictr_camfit *r) { return sizeof(CfState) * (size_t)r->nframes; }
+static size_t cf_bytes(const ictr_camfit *r) { return sizeof(CfState) * (size_t)r->in.nframes; }
 
 extern "C" int ictr_camfit_create(ictr_camfit **out, int64_t n, int64_t nframes) {
   if (!out) return fail(ICTR_ERR_INVALID, "camfit_create: NULL argument");
@@ -162,15 +161,9 @@ extern "C" int ictr_camfit_create(ictr_camfit **out, int64_t n, int64_t nframes)
     return fail(ICTR_ERR_INVALID, "camfit_create: %lld frames (1 .. %d)", (long long)nframes, kCfMaxFrames);
   if (int rc = need_device()) return rc;
   auto r = std::make_unique<ictr_camfit>();
-  r->n = (int)n;
-  r->nwords = (int)((n + 63) / 64);
   r->nchunks = (int)((n + kCfChunk - 1) / kCfChunk);
-  r->nframes = (int)nframes;
-  const size_t N = (size_t)n, F = (size_t)nframes;
-  if (int rc = r->d_X.alloc(sizeof(double) * 3 * N, true)) return rc;
-  if (int rc = r->d_xy.alloc(sizeof(double) * 2 * F * N, true)) return rc;
-  if (int rc = r->d_part.alloc(sizeof(double) * kCfSlots * F * (size_t)r->nchunks, true)) return rc;
-  if (int rc = r->d_words.alloc(sizeof(unsigned long long) * (size_t)r->nwords, true)) return rc;
+  if (int rc = r->in.alloc((int)n, (int)nframes, 1)) return rc;
+  if (int rc = r->d_part.alloc(sizeof(double) * kCfSlots * (size_t)nframes * (size_t)r->nchunks, true)) return rc;
   if (int rc = r->up.alloc(cf_bytes(r.get()))) return rc;
   if (int rc = r->out.reserve(cf_bytes(r.get()), true)) return rc;
   *out = r.release();
@@ -180,60 +173,22 @@ extern "C" int ictr_camfit_create(ictr_camfit **out, int64_t n, int64_t nframes)
 extern "C" void ictr_camfit_destroy(ictr_camfit *r) { delete r; }
 
 extern "C" int ictr_camfit_set_points(ictr_camfit *r, const double *X) {
-  if (!r || !X) return fail(ICTR_ERR_INVALID, "camfit_set_points: NULL argument");
-  if (int rc = r->out.refuse("camfit_set_points", "camfit")) return rc;
-  HIPCHK(hipMemcpy(r->d_X.get(), X, sizeof(double) * 3 * (size_t)r->n, hipMemcpyHostToDevice));
-  r->points_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_points("camfit_set_points", "camfit", r->out, X) : null_object("camfit_set_points");
 }
-
 extern "C" int ictr_camfit_set_observations(ictr_camfit *r, const double *xy) {
-  if (!r || !xy) return fail(ICTR_ERR_INVALID, "camfit_set_observations: NULL argument");
-  if (int rc = r->out.refuse("camfit_set_observations", "camfit")) return rc;
-  HIPCHK(hipMemcpy(r->d_xy.get(), xy, sizeof(double) * 2 * (size_t)r->nframes * (size_t)r->n, hipMemcpyHostToDevice));
-  r->obs_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_observations("camfit_set_observations", "camfit", r->out, xy)
+           : null_object("camfit_set_observations");
 }
-
 extern "C" int ictr_camfit_set_mask(ictr_camfit *r, const uint64_t *words) {
-  if (!r) return fail(ICTR_ERR_INVALID, "camfit is NULL");
-  if (int rc = r->out.refuse("camfit_set_mask", "camfit")) return rc;
-  if (words) HIPCHK(hipMemcpy(r->d_words.get(), words, sizeof(uint64_t) * (size_t)r->nwords, hipMemcpyHostToDevice));
-  r->use_mask = words != nullptr;
-  return ICTR_OK;
+  return r ? r->in.set_mask("camfit_set_mask", "camfit", r->out, words) : fail(ICTR_ERR_INVALID, "camfit is NULL");
 }
-
 extern "C" int ictr_camfit_set_camera(ictr_camfit *r, const double *fc, const double *cc) {
-  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "camfit_set_camera: NULL argument");
-  if (int rc = r->out.refuse("camfit_set_camera", "camfit")) return rc;
-  for (int q = 0; q < 2; ++q)
-    if (!cf_finite(fc[q]) || !cf_finite(cc[q]) || fc[q] == 0.0)
-      return fail(ICTR_ERR_INVALID, "camfit_set_camera: fc must be finite and not 0, cc finite");
-  r->cam = {fc[0], fc[1], cc[0], cc[1]};
-  r->cam_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_camera("camfit_set_camera", "camfit", r->out, fc, cc) : null_object("camfit_set_camera");
 }
 
-extern "C" int ictr_camfit_view_(const ictr_camfit *r, ictr_camfit_view *v) {
-  v->X = r->d_X.get();
-  v->xy = r->d_xy.get();
-  v->words = r->d_words.get();
-  v->n = r->n;
-  v->nwords = r->nwords;
-  v->nframes = r->nframes;
-  v->pending = r->out.pending();
-  v->cam_set = r->cam_set;
-  v->fc[0] = r->cam.fx;
-  v->fc[1] = r->cam.fy;
-  v->cc[0] = r->cam.cx;
-  v->cc[1] = r->cam.cy;
+extern "C" int ictr_camfit_inputs_(ictr_camfit *r, WinDest *d) {
+  *d = {&r->in, &r->out, "camfit", "fit"};
   return ICTR_OK;
-}
-
-extern "C" void ictr_camfit_filled_(ictr_camfit *r, int points, int obs, int mask) {
-  r->points_set = r->points_set || points != 0;
-  r->obs_set = r->obs_set || obs != 0;
-  r->use_mask = r->use_mask || mask != 0;
 }
 
 extern "C" int ictr_camfit_set_timing(ictr_camfit *r, int on) {
@@ -243,22 +198,14 @@ extern "C" int ictr_camfit_set_timing(ictr_camfit *r, int on) {
   return ICTR_OK;
 }
 
-// what every entry that launches needs first
-static int cf_ready(const ictr_camfit *r, const char *what) {
-  if (int rc = r->out.refuse(what, "camfit")) return rc;
-  if (!r->points_set || !r->obs_set || !r->cam_set)
-    return fail(ICTR_ERR_STATE, "%s: set_points, set_observations and set_camera come first", what);
-  return ICTR_OK;
-}
-
 static void cf_fill_args(const ictr_camfit *r, const CfParams &p, CamfitArgs &a) {
   memset(&a, 0, sizeof(a));
-  a.X = r->d_X.get();
-  a.xy = r->d_xy.get();
-  a.words = r->use_mask ? r->d_words.get() : nullptr;
-  a.n = r->n;
+  a.X = r->in.X.get();
+  a.xy = r->in.xy.get();
+  a.words = r->in.mask_or_null();
+  a.n = r->in.n;
   a.nchunks = r->nchunks;
-  a.cam = r->cam;
+  a.cam = r->in.cam;
   a.prm = p;
   a.part = r->d_part.get();
   a.st = reinterpret_cast<CfState *>(r->out.dev());
@@ -273,12 +220,12 @@ static int cf_poses_finite(const double *G, int nframes, const char *what) {
 extern "C" int ictr_camfit_run(ictr_camfit *r, const double *G0, int32_t noiter, double damp_init, double damp_fct,
                                double minres, double maxdamp, void *hip_stream) {
   if (!r || !G0) return fail(ICTR_ERR_INVALID, "camfit_run: NULL argument");
-  if (int rc = cf_ready(r, "camfit_run")) return rc;
+  if (int rc = r->in.ready("camfit_run", r->out, "camfit")) return rc;
   if (noiter < 0 || noiter > kCfMaxIter) return fail(ICTR_ERR_INVALID, "camfit_run: noiter %d (0 .. %d)", noiter, kCfMaxIter);
   if (!(damp_init > 0.0) || !cf_finite(damp_init) || !(damp_fct > 1.0) || !cf_finite(damp_fct) || !(minres >= 0.0) ||
       !cf_finite(minres) || !(maxdamp > 0.0))
     return fail(ICTR_ERR_INVALID, "camfit_run: needs damp_init > 0, damp_fct > 1, minres >= 0 (all finite), maxdamp > 0");
-  if (int rc = cf_poses_finite(G0, r->nframes, "camfit_run")) return rc;
+  if (int rc = cf_poses_finite(G0, r->in.nframes, "camfit_run")) return rc;
   const CfParams p = {noiter, damp_init, damp_fct, minres, maxdamp};
   CamfitArgs a;
   cf_fill_args(r, p, a);
@@ -289,15 +236,15 @@ extern "C" int ictr_camfit_run(ictr_camfit *r, const double *G0, int32_t noiter,
       if (int rc = e.create()) return rc;
   }
   CfState *init = reinterpret_cast<CfState *>(r->up.get());
-  for (int f = 0; f < r->nframes; ++f) cf_init(init[f], G0 + 12 * f, p);
+  for (int f = 0; f < r->in.nframes; ++f) cf_init(init[f], G0 + 12 * f, p);
   hipStream_t s = (hipStream_t)hip_stream;
   HIPCHK(hipMemcpyAsync(r->out.dev(), r->up.get(), cf_bytes(r), hipMemcpyHostToDevice, s));
   size_t e = 0;
   for (int it = 0; it <= noiter; ++it) {
     if (r->timing) HIPCHK(hipEventRecord(tev[e++].get(), s));
-    launch_camfit_pass(a, r->nframes, s);
+    launch_camfit_pass(a, r->in.nframes, s);
     if (r->timing) HIPCHK(hipEventRecord(tev[e++].get(), s));
-    launch_camfit_step(a, r->nframes, s);
+    launch_camfit_step(a, r->in.nframes, s);
     HIPCHK(hipGetLastError());
   }
   if (r->timing) HIPCHK(hipEventRecord(tev[e++].get(), s));
@@ -313,7 +260,7 @@ extern "C" int ictr_camfit_wait(ictr_camfit *r, double *G, double *cost, double 
   if (!r->out.pending()) return fail(ICTR_ERR_STATE, "camfit_wait: nothing has been run");
   if (int rc = r->out.wait()) return rc;
   const CfState *st = reinterpret_cast<const CfState *>(r->out.host());
-  for (int f = 0; f < r->nframes; ++f) {
+  for (int f = 0; f < r->in.nframes; ++f) {
     if (G) memcpy(G + 12 * f, st[f].G, sizeof(st[f].G));
     if (cost) cost[f] = st[f].c;
     if (damp) damp[f] = st[f].damp;
@@ -349,14 +296,14 @@ static int cf_sums_at(ictr_camfit *r, const double *G, const double *dt, std::ve
   a.sums_only = 1;
   if (dt)
     for (int q = 0; q < 3; ++q) a.dt[q] = dt[q];
-  st.resize((size_t)r->nframes);
-  for (int f = 0; f < r->nframes; ++f) cf_init(st[(size_t)f], G + 12 * f, p);
+  st.resize((size_t)r->in.nframes);
+  for (int f = 0; f < r->in.nframes; ++f) cf_init(st[(size_t)f], G + 12 * f, p);
   HIPCHK(hipMemcpy(r->out.dev(), st.data(), cf_bytes(r), hipMemcpyHostToDevice));
   if (dt)
-    launch_camfit_reproj(a, r->nframes, nullptr);
+    launch_camfit_reproj(a, r->in.nframes, nullptr);
   else
-    launch_camfit_pass(a, r->nframes, nullptr);
-  launch_camfit_step(a, r->nframes, nullptr);
+    launch_camfit_pass(a, r->in.nframes, nullptr);
+  launch_camfit_step(a, r->in.nframes, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(st.data(), r->out.dev(), cf_bytes(r), hipMemcpyDeviceToHost));
   return ICTR_OK;
@@ -364,15 +311,15 @@ static int cf_sums_at(ictr_camfit *r, const double *G, const double *dt, std::ve
 
 extern "C" int ictr_camfit_reproj(ictr_camfit *r, const double *G, const double *dt, double *mean_err, int64_t *n) {
   if (!r || !G || !mean_err) return fail(ICTR_ERR_INVALID, "camfit_reproj: NULL argument");
-  if (int rc = cf_ready(r, "camfit_reproj")) return rc;
-  if (int rc = cf_poses_finite(G, r->nframes, "camfit_reproj")) return rc;
+  if (int rc = r->in.ready("camfit_reproj", r->out, "camfit")) return rc;
+  if (int rc = cf_poses_finite(G, r->in.nframes, "camfit_reproj")) return rc;
   const double zero[3] = {0.0, 0.0, 0.0};
   if (dt)
     for (int q = 0; q < 3; ++q)
       if (!cf_finite(dt[q])) return fail(ICTR_ERR_INVALID, "camfit_reproj: dt is not finite");
   std::vector<CfState> st;
   if (int rc = cf_sums_at(r, G, dt ? dt : zero, st)) return rc;
-  for (int f = 0; f < r->nframes; ++f) {
+  for (int f = 0; f < r->in.nframes; ++f) {
     const double cnt = st[(size_t)f].sums[kCfCountSlot];
     mean_err[f] = cnt > 0.0 ? cf_canon(st[(size_t)f].sums[0] / cnt) : cf_nan();
     if (n) n[f] = (int64_t)cnt;
@@ -383,11 +330,11 @@ extern "C" int ictr_camfit_reproj(ictr_camfit *r, const double *G, const double 
 // inspection: k_camfit_pass at the poses G [nframes][12] and the ordered sum of k_camfit_step alone, on the null stream
 extern "C" int ictr_debug_camfit_pass(ictr_camfit *r, const double *G, int64_t *n, double *s, double *H, double *b) {
   if (!r || !G || !n || !s || !H || !b) return fail(ICTR_ERR_INVALID, "debug_camfit_pass: NULL argument");
-  if (int rc = cf_ready(r, "debug_camfit_pass")) return rc;
-  if (int rc = cf_poses_finite(G, r->nframes, "debug_camfit_pass")) return rc;
+  if (int rc = r->in.ready("debug_camfit_pass", r->out, "camfit")) return rc;
+  if (int rc = cf_poses_finite(G, r->in.nframes, "debug_camfit_pass")) return rc;
   std::vector<CfState> st;
   if (int rc = cf_sums_at(r, G, nullptr, st)) return rc;
-  for (int f = 0; f < r->nframes; ++f) {
+  for (int f = 0; f < r->in.nframes; ++f) {
     const double *v = st[(size_t)f].sums;
     n[f] = (int64_t)v[kCfCountSlot];
     s[f] = v[27];

@@ -33,6 +33,7 @@
 #include "ictr_camransac_hd.h"
 #include "ictr_dev.h"
 #include "ictr_launch.h"
+#include "ictr_wininputs.h"
 
 namespace ictr {
 
@@ -274,15 +275,12 @@ using namespace ictr;
 
 // ---------------------------------------------------------------- host side
 struct ictr_camransac {
-  int n = 0, nwords = 0, nframes = 0, nsides = 0;
+  WinInputs in;  // in.words: the mask words as set
   int chunk = 0, tile = 32;
-  DevBuf<double> d_X, d_xy, d_G;
-  DevBuf<unsigned long long> d_mask, d_cw;
+  DevBuf<double> d_G;
+  DevBuf<unsigned long long> d_cw;
   DevBuf<int> d_draws, d_fst, d_status;
   DevBuf<unsigned> d_cnt;
-  CfCam cam = {0, 0, 0, 0};
-  double off[3] = {0, 0, 0};
-  bool points_set = false, obs_set = false, cam_set = false, off_set = false, use_mask = false;
   bool timing = false, timed = false;  // timed: the run in flight (or last waited) carries events
   std::vector<Event> tev;              // before flags, after flags, per chunk after hyp / score / select, after mask
   float ms[4] = {0, 0, 0, 0};
@@ -296,7 +294,7 @@ struct CrLayout {  // CrState | G [F][12] | words [nwords] | dd [n], each on a 1
 static CrLayout cr_layout(const ictr_camransac *r) {
   Carve c;
   c.take(sizeof(CrState), 16);  // at the front
-  return {c.take(96 * (size_t)r->nframes, 16), c.take(8 * (size_t)r->nwords, 16), c.take(8 * (size_t)r->n, 16),
+  return {c.take(96 * (size_t)r->in.nframes, 16), c.take(8 * (size_t)r->in.nwords, 16), c.take(8 * (size_t)r->in.n, 16),
           c.take(0, 16)};  // braces: evaluated in this order
 }
 
@@ -309,21 +307,15 @@ extern "C" int ictr_camransac_create(ictr_camransac **out, int64_t n, int64_t nf
   if (nsides < 1 || nsides > 2) return fail(ICTR_ERR_INVALID, "camransac_create: %lld sides (1 or 2)", (long long)nsides);
   if (int rc = need_device()) return rc;
   auto r = std::make_unique<ictr_camransac>();
-  r->n = (int)n;
-  r->nwords = (int)((n + 63) / 64);
-  r->nframes = (int)nframes;
-  r->nsides = (int)nsides;
+  if (int rc = r->in.alloc((int)n, (int)nframes, (int)nsides)) return rc;
   // trials per chunk: at the default the poses of a chunk (K x F x 96 B) stay below 26 MB; ICTR_CAMRANSAC_CHUNK
   // overrides (tests and sweeps; up to 65536, whose poses are allocated as asked: 400 MB at F = 64)
   const int chunk = env_int("ICTR_CAMRANSAC_CHUNK", 0);
   r->chunk = chunk > 0 ? std::min(chunk, 1 << 16) : 4096;
   r->tile = ran_tile_env("ICTR_CAMRANSAC_TILE");
-  const size_t K = (size_t)r->chunk, F = (size_t)nframes, N = (size_t)n, W = (size_t)r->nwords;
-  if (int rc = r->d_X.alloc(sizeof(double) * 3 * N, true)) return rc;
-  if (int rc = r->d_xy.alloc(sizeof(double) * 2 * (size_t)nsides * F * N, true)) return rc;
+  const size_t K = (size_t)r->chunk, F = (size_t)nframes;
   if (int rc = r->d_G.alloc(sizeof(double) * 12 * K * F, true)) return rc;
-  if (int rc = r->d_mask.alloc(sizeof(unsigned long long) * W, true)) return rc;
-  if (int rc = r->d_cw.alloc(sizeof(unsigned long long) * W, true)) return rc;
+  if (int rc = r->d_cw.alloc(sizeof(unsigned long long) * (size_t)r->in.nwords, true)) return rc;
   if (int rc = r->d_draws.alloc(sizeof(int) * 4 * K, true)) return rc;
   if (int rc = r->d_fst.alloc(sizeof(int) * K * F, true)) return rc;
   if (int rc = r->d_status.alloc(sizeof(int) * K, true)) return rc;
@@ -338,74 +330,31 @@ extern "C" void ictr_camransac_destroy(ictr_camransac *r) { delete r; }
 extern "C" int ictr_camransac_chunk_size(const ictr_camransac *r) { return r ? r->chunk : 0; }
 
 extern "C" int ictr_camransac_set_points(ictr_camransac *r, const double *X) {
-  if (!r || !X) return fail(ICTR_ERR_INVALID, "camransac_set_points: NULL argument");
-  if (int rc = r->out.refuse("camransac_set_points", "camransac")) return rc;
-  HIPCHK(hipMemcpy(r->d_X.get(), X, sizeof(double) * 3 * (size_t)r->n, hipMemcpyHostToDevice));
-  r->points_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_points("camransac_set_points", "camransac", r->out, X) : null_object("camransac_set_points");
 }
-
 extern "C" int ictr_camransac_set_observations(ictr_camransac *r, const double *xy) {
-  if (!r || !xy) return fail(ICTR_ERR_INVALID, "camransac_set_observations: NULL argument");
-  if (int rc = r->out.refuse("camransac_set_observations", "camransac")) return rc;
-  HIPCHK(hipMemcpy(r->d_xy.get(), xy, sizeof(double) * 2 * (size_t)r->nsides * (size_t)r->nframes * (size_t)r->n,
-                   hipMemcpyHostToDevice));
-  r->obs_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_observations("camransac_set_observations", "camransac", r->out, xy)
+           : null_object("camransac_set_observations");
 }
-
 extern "C" int ictr_camransac_set_mask(ictr_camransac *r, const uint64_t *words) {
-  if (!r) return fail(ICTR_ERR_INVALID, "camransac is NULL");
-  if (int rc = r->out.refuse("camransac_set_mask", "camransac")) return rc;
-  if (words) HIPCHK(hipMemcpy(r->d_mask.get(), words, sizeof(uint64_t) * (size_t)r->nwords, hipMemcpyHostToDevice));
-  r->use_mask = words != nullptr;
-  return ICTR_OK;
+  return r ? r->in.set_mask("camransac_set_mask", "camransac", r->out, words) : fail(ICTR_ERR_INVALID, "camransac is NULL");
 }
-
 extern "C" int ictr_camransac_set_camera(ictr_camransac *r, const double *fc, const double *cc) {
-  if (!r || !fc || !cc) return fail(ICTR_ERR_INVALID, "camransac_set_camera: NULL argument");
-  if (int rc = r->out.refuse("camransac_set_camera", "camransac")) return rc;
-  for (int q = 0; q < 2; ++q)
-    if (!cf_finite(fc[q]) || !cf_finite(cc[q]) || fc[q] == 0.0)
-      return fail(ICTR_ERR_INVALID, "camransac_set_camera: fc must be finite and not 0, cc finite");
-  r->cam = {fc[0], fc[1], cc[0], cc[1]};
-  r->cam_set = true;
-  return ICTR_OK;
+  return r ? r->in.set_camera("camransac_set_camera", "camransac", r->out, fc, cc) : null_object("camransac_set_camera");
 }
-
 extern "C" int ictr_camransac_set_offset(ictr_camransac *r, const double *offset) {
-  if (!r || !offset) return fail(ICTR_ERR_INVALID, "camransac_set_offset: NULL argument");
-  if (int rc = r->out.refuse("camransac_set_offset", "camransac")) return rc;
-  for (int q = 0; q < 3; ++q)
-    if (!cf_finite(offset[q])) return fail(ICTR_ERR_INVALID, "camransac_set_offset: the offset is not finite");
-  memcpy(r->off, offset, sizeof(r->off));
-  r->off_set = true;
+  return r ? r->in.set_offset("camransac_set_offset", "camransac", r->out, offset) : null_object("camransac_set_offset");
+}
+
+extern "C" int ictr_camransac_inputs_(ictr_camransac *r, WinDest *d) {
+  *d = {&r->in, &r->out, "camransac", "RANSAC"};
   return ICTR_OK;
 }
 
-extern "C" int ictr_camransac_view_(const ictr_camransac *r, ictr_camransac_view *v) {
-  v->X = r->d_X.get();
-  v->xy = r->d_xy.get();
-  v->mask = r->d_mask.get();
-  v->use_mask = r->use_mask;
-  v->words = reinterpret_cast<const unsigned long long *>(r->out.dev() + cr_layout(r).words.at);
-  v->n = r->n;
-  v->nwords = r->nwords;
-  v->nframes = r->nframes;
-  v->nsides = r->nsides;
-  v->pending = r->out.pending();
-  v->ran = r->out.ran();
-  v->cam_set = r->cam_set;
-  v->fc[0] = r->cam.fx;
-  v->fc[1] = r->cam.fy;
-  v->cc[0] = r->cam.cx;
-  v->cc[1] = r->cam.cy;
+// the winner's inlier bits of the last run, in the result block on the device
+extern "C" int ictr_camransac_mask_(const ictr_camransac *r, WinMaskSrc *m) {
+  *m = {reinterpret_cast<const unsigned long long *>(r->out.dev() + cr_layout(r).words.at), r->in.n, r->out.ran(), "RANSAC"};
   return ICTR_OK;
-}
-
-extern "C" void ictr_camransac_filled_(ictr_camransac *r, int points, int obs) {
-  r->points_set = r->points_set || points != 0;
-  r->obs_set = r->obs_set || obs != 0;
 }
 
 extern "C" int ictr_camransac_set_timing(ictr_camransac *r, int on) {
@@ -418,24 +367,20 @@ extern "C" int ictr_camransac_set_timing(ictr_camransac *r, int on) {
 // what every entry that launches needs first, and every field of the kernels' argument block that does not depend on the
 // trial range
 static int cr_fill_args(const ictr_camransac *r, const char *what, double thresh, uint64_t seed, CrArgs &a) {
-  if (int rc = r->out.refuse(what, "camransac")) return rc;
-  if (!r->points_set || !r->obs_set || !r->cam_set)
-    return fail(ICTR_ERR_STATE, "%s: set_points, set_observations and set_camera come first", what);
-  if (r->nsides == 2 && !r->off_set)
-    return fail(ICTR_ERR_STATE, "%s: two sides need ictr_camransac_set_offset", what);
+  if (int rc = r->in.ready(what, r->out, "camransac")) return rc;
   if (std::isnan(thresh)) return fail(ICTR_ERR_INVALID, "%s: thresh is NaN", what);
   const CrLayout L = cr_layout(r);
   memset(&a, 0, sizeof(a));
-  a.X = r->d_X.get();
-  a.xy = r->d_xy.get();
-  a.mask = r->use_mask ? r->d_mask.get() : nullptr;
+  a.X = r->in.X.get();
+  a.xy = r->in.xy.get();
+  a.mask = r->in.mask_or_null();
   a.cw = r->d_cw.get();
-  a.n = r->n;
-  a.nwords = r->nwords;
-  a.nframes = r->nframes;
-  a.nsides = r->nsides;
-  a.cam = r->cam;
-  for (int q = 0; q < 3; ++q) a.off[q] = r->nsides == 2 ? r->off[q] : 0.0;
+  a.n = r->in.n;
+  a.nwords = r->in.nwords;
+  a.nframes = r->in.nframes;
+  a.nsides = r->in.nsides;
+  a.cam = r->in.cam;
+  for (int q = 0; q < 3; ++q) a.off[q] = r->in.nsides == 2 ? r->in.off[q] : 0.0;
   a.thr = thresh;
   a.seedmix = ran_seed(seed);
   a.G = r->d_G.get();
@@ -502,7 +447,7 @@ extern "C" int ictr_camransac_wait(ictr_camransac *r, int64_t *best_trial, int64
   if (draws) memcpy(draws, st.draws, sizeof(st.draws));
   if (G) memcpy(G, hG, L.G.bytes);
   if (p)  // p = se3_log(G), on the host at the read-back (as ictr_ransac_wait); NaN without a winner
-    for (int f = 0; f < r->nframes; ++f) {
+    for (int f = 0; f < r->in.nframes; ++f) {
       if (st.found) {
         se3_log<double>(p + 6 * f, hG + 12 * f);
       } else {
@@ -543,7 +488,7 @@ extern "C" int ictr_debug_camransac_trials(ictr_camransac *r, double thresh, uin
   if (int rc = cr_fill_args(r, "debug_camransac_trials", thresh, seed, a)) return rc;
   launch_cr_flags(a, nullptr);
   const int64_t K = r->chunk;
-  const size_t F = (size_t)r->nframes;
+  const size_t F = (size_t)r->in.nframes;
   for (int64_t done = 0; done < count; done += K) {
     a.base = first_trial + done;
     a.k = (int)std::min<int64_t>(K, count - done);

@@ -270,12 +270,14 @@ extern "C" int ictr_fsplit_set_pairs(ictr_fsplit *r, const double *xy) {
 
 extern "C" int ictr_fsplit_view_(const ictr_fsplit *r, ictr_fsplit_view *v) {
   v->xy = r->d_xy.get();
-  v->words = reinterpret_cast<const unsigned long long *>(r->out.dev() + fs_layout(r).words.at);
   v->n = r->n;
-  v->nwords = r->nwords;
   v->np = r->np;
   v->pending = r->out.pending();
-  v->ran = r->out.ran();
+  return ICTR_OK;
+}
+
+extern "C" int ictr_fsplit_mask_(const ictr_fsplit *r, WinMaskSrc *m) {
+  *m = {reinterpret_cast<const unsigned long long *>(r->out.dev() + fs_layout(r).words.at), r->n, r->out.ran(), "split"};
   return ICTR_OK;
 }
 

@@ -1,25 +1,27 @@
 // ictr_handover.hip -- the window hand-over (DESIGN.md §4 "Window hand-over"): the history [bsize][4][N] and the rows [M]
-// of a counted stereo track window written, on the device, into the input buffers of the static split and of the camera
-// fit, and the split's inlier words copied into the fit. The objects' structs stay in their own files; this file sees
-// them through the views of ictr_launch.h.
+// of a counted stereo track window written, on the device, into the input buffers of the stages that follow, and one
+// stage's inlier words copied into the mask of another. The objects' structs stay in their own files. The split's pairs
+// are seen through ictr_fsplit_view; the fit, the adjuster and the window camera RANSAC each hand out their one input
+// block (ictr_wininputs.h) as a WinDest (ictr_launch.h), so each hand-over is written once: ho_points, ho_obs, ho_mask,
+// ho_debug_inputs. The public entries name the object and pass it on.
 //
 //   k_ho_pairs   grid (chunks of kBlock survivors, frames): the frame's four words into its places among the view pairs
 //                [2 npairs][4][M] of fsplit.pairs_from_stereo_tracks; the middle frame of an odd window returns at once
-//   k_ho_obs     same grid: the two words of one side into the observations [bsize][2][M]
+//   k_ho_obs     same grid: the two words of one side into that side's observations [bsize][2][M]
 //   k_ho_points  one thread per survivor: ho_point of ictr_handover_hd.h on frame 0 into X [3][M]
 //
-// The adjuster (ictr_ba.hip) takes its points, both sides of its observations and its mask by the same kernels, and so
-// does the window camera RANSAC (ictr_camransac.hip), whose winner's words in turn mask the fit and the adjuster.
-//
 // Every thread reads rows[m] once; rows is ascending, so neighbouring lanes read neighbouring (or the same cache line's)
-// words of a history column, and every store is coalesced over m. No atomics, no LDS, plain vector stores. The three
-// from-window entries enqueue on the null stream, like the window itself, and do not wait.
+// words of a history column, and every store is coalesced over m. No atomics, no LDS, plain vector stores. The
+// from-window entries enqueue on the null stream, like the window itself, and do not wait. They refuse in one order:
+// NULL, window not counted, bsize < 2, size mismatch, run in flight, then camera not set or frame count; a refused call
+// launches nothing and sets no flag.
 #include <stdint.h>
 #include <string.h>
 
 #include "ictr_dev.h"
 #include "ictr_handover_hd.h"
 #include "ictr_launch.h"
+#include "ictr_wininputs.h"
 
 namespace ictr {
 
@@ -101,20 +103,86 @@ int ho_window(const ictr_stereotrack *t, int n_dest, const char *what, HoArgs *a
 
 unsigned ho_chunks(int m) { return (unsigned)((m + kBlock - 1) / kBlock); }
 
-int ho_in_flight(const char *what, const char *object) {
-  return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_%s_wait first", what, object);
+// a public entry's object as a destination (V = WinDest) or a mask source (WinMaskSrc) through its accessor `get`; all
+// zero for a NULL object, which the helpers refuse
+template <class T, class V>
+V ho_of(T *r, int (*get)(T *, V *)) {
+  V v = {};
+  if (r) get(r, &v);
+  return v;
+}
+
+// ho_point of frame 0 into the points, with the camera of the destination's set_camera
+int ho_points(const WinDest &d, const ictr_stereotrack *t, double baseline, const char *what) {
+  if (!d.in || !t) return null_object(what);
+  HoArgs a;
+  if (int rc = ho_window(t, d.in->n, what, &a)) return rc;
+  if (int rc = d.out->refuse(what, d.object)) return rc;
+  if (!d.in->cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_%s_set_camera comes first", what, d.object);
+  const HoCam cam = {d.in->cam.fx, d.in->cam.fy, d.in->cam.cx, d.in->cam.cy};
+  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.in->X.get());
+  HIPCHK(hipGetLastError());
+  d.in->filled(true, false, false);
+  return ICTR_OK;
+}
+
+// sides first_side .. first_side + nsides - 1 of the window into sides 0 .. nsides - 1 of the observations
+int ho_obs(const WinDest &d, const ictr_stereotrack *t, int first_side, int nsides, const char *what) {
+  if (!d.in || !t) return null_object(what);
+  HoArgs a;
+  if (int rc = ho_window(t, d.in->n, what, &a)) return rc;
+  if (int rc = d.out->refuse(what, d.object)) return rc;
+  if (d.in->nframes != a.bsize)
+    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the %s was made for %d", what, a.bsize, d.noun,
+                d.in->nframes);
+  for (int s = 0; s < nsides; ++s)
+    hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, first_side + s,
+                       d.in->xy.get() + (size_t)s * (size_t)a.bsize * 2 * (size_t)a.m);
+  HIPCHK(hipGetLastError());
+  d.in->filled(false, true, false);
+  return ICTR_OK;
+}
+
+// the inlier words of the source's last run, waited for or in flight, into the mask words, on the device on `stream`
+int ho_mask(const WinDest &d, const WinMaskSrc &src, void *stream, const char *what) {
+  if (!d.in || !src.noun) return null_object(what);
+  if (int rc = d.out->refuse(what, d.object)) return rc;
+  if (!src.ran) return fail(ICTR_ERR_STATE, "%s: the %s has never run", what, src.noun);
+  if (src.n != d.in->n)
+    return fail(ICTR_ERR_INVALID, "%s: the %s has %d points, the %s %d", what, src.noun, src.n, d.noun, d.in->n);
+  HIPCHK(hipMemcpyAsync(d.in->words.get(), src.words, sizeof(unsigned long long) * (size_t)d.in->nwords,
+                        hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  d.in->filled(false, false, true);
+  return ICTR_OK;
+}
+
+// inspection: the device buffers as they stand, after everything enqueued so far on any stream. in_effect: where no mask
+// is in use the words answer every point's bit (bits past n clear), not the buffer
+int ho_debug_inputs(const WinDest &d, double *X, double *xy, uint64_t *words, bool in_effect = false) {
+  const WinInputs &in = *d.in;
+  HIPCHK(hipDeviceSynchronize());
+  if (X) HIPCHK(hipMemcpy(X, in.X.get(), sizeof(double) * 3 * (size_t)in.n, hipMemcpyDeviceToHost));
+  if (xy) HIPCHK(hipMemcpy(xy, in.xy.get(), sizeof(double) * in.obs_count(), hipMemcpyDeviceToHost));
+  if (words && in_effect && !in.use_mask) {
+    for (int w = 0; w < in.nwords; ++w) words[w] = ~0ull;
+    if (in.n & 63) words[in.nwords - 1] = (1ull << (in.n & 63)) - 1ull;
+  } else if (words) {
+    HIPCHK(hipMemcpy(words, in.words.get(), sizeof(uint64_t) * (size_t)in.nwords, hipMemcpyDeviceToHost));
+  }
+  return ICTR_OK;
 }
 
 }  // namespace
 
+// ---------------------------------------------------------------- the split's pairs
 extern "C" int ictr_fsplit_set_pairs_from_window(ictr_fsplit *r, const ictr_stereotrack *t) {
   const char *what = "fsplit_set_pairs_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
+  if (!r || !t) return null_object(what);
   ictr_fsplit_view d;
   if (int rc = ictr_fsplit_view_(r, &d)) return rc;
   HoArgs a;
   if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "fsplit");
+  if (d.pending) return fail(ICTR_ERR_STATE, "%s: a run is in flight; call ictr_fsplit_wait first", what);
   if (d.np != 2 * ho_npairs(a.bsize))
     return fail(ICTR_ERR_INVALID, "%s: a window of %d frames gives %d view pairs, the split was made for %d", what, a.bsize,
                 2 * ho_npairs(a.bsize), d.np);
@@ -124,206 +192,8 @@ extern "C" int ictr_fsplit_set_pairs_from_window(ictr_fsplit *r, const ictr_ster
   return ICTR_OK;
 }
 
-extern "C" int ictr_camfit_set_points_from_window(ictr_camfit *r, const ictr_stereotrack *t, double baseline) {
-  const char *what = "camfit_set_points_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camfit_view d;
-  if (int rc = ictr_camfit_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "camfit");
-  if (!d.cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_camfit_set_camera comes first", what);
-  const HoCam cam = {d.fc[0], d.fc[1], d.cc[0], d.cc[1]};
-  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.X);
-  HIPCHK(hipGetLastError());
-  ictr_camfit_filled_(r, 1, 0, 0);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_camfit_set_observations_from_window(ictr_camfit *r, const ictr_stereotrack *t, int right) {
-  const char *what = "camfit_set_observations_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camfit_view d;
-  if (int rc = ictr_camfit_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "camfit");
-  if (d.nframes != a.bsize)
-    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the fit was made for %d", what, a.bsize, d.nframes);
-  hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, right != 0 ? 1 : 0, d.xy);
-  HIPCHK(hipGetLastError());
-  ictr_camfit_filled_(r, 0, 1, 0);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_camfit_set_mask_from_fsplit(ictr_camfit *r, const ictr_fsplit *s, void *hip_stream) {
-  const char *what = "camfit_set_mask_from_fsplit";
-  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camfit_view d;
-  ictr_fsplit_view v;
-  if (int rc = ictr_camfit_view_(r, &d)) return rc;
-  if (int rc = ictr_fsplit_view_(s, &v)) return rc;
-  if (d.pending) return ho_in_flight(what, "camfit");
-  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the split has never run", what);
-  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the split has %d points, the fit %d", what, v.n, d.n);
-  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
-                        (hipStream_t)hip_stream));
-  ictr_camfit_filled_(r, 0, 0, 1);
-  return ICTR_OK;
-}
-
-// the adjuster's inputs from the same window: ho_point into the points as set, k_ho_obs once per side
-extern "C" int ictr_ba_set_points_from_window(ictr_ba *r, const ictr_stereotrack *t, double baseline) {
-  const char *what = "ba_set_points_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_ba_view d;
-  if (int rc = ictr_ba_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "ba");
-  if (!d.cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_ba_set_camera comes first", what);
-  const HoCam cam = {d.fc[0], d.fc[1], d.cc[0], d.cc[1]};
-  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.X);
-  HIPCHK(hipGetLastError());
-  ictr_ba_filled_(r, 1, 0, 0);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ba_set_observations_from_window(ictr_ba *r, const ictr_stereotrack *t) {
-  const char *what = "ba_set_observations_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_ba_view d;
-  if (int rc = ictr_ba_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "ba");
-  if (d.nframes != a.bsize)
-    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the adjuster was made for %d", what, a.bsize, d.nframes);
-  for (int s = 0; s < d.nsides; ++s)
-    hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, s,
-                       d.xy + (size_t)s * (size_t)a.bsize * 2 * (size_t)a.m);
-  HIPCHK(hipGetLastError());
-  ictr_ba_filled_(r, 0, 1, 0);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, void *hip_stream) {
-  const char *what = "ba_set_mask_from_fsplit";
-  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_ba_view d;
-  ictr_fsplit_view v;
-  if (int rc = ictr_ba_view_(r, &d)) return rc;
-  if (int rc = ictr_fsplit_view_(s, &v)) return rc;
-  if (d.pending) return ho_in_flight(what, "ba");
-  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the split has never run", what);
-  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the split has %d points, the adjuster %d", what, v.n, d.n);
-  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
-                        (hipStream_t)hip_stream));
-  ictr_ba_filled_(r, 0, 0, 1);
-  return ICTR_OK;
-}
-
-// the window camera RANSAC's inputs from the same window, by the same kernels; its winner's words as a mask
-extern "C" int ictr_camransac_set_points_from_window(ictr_camransac *r, const ictr_stereotrack *t, double baseline) {
-  const char *what = "camransac_set_points_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camransac_view d;
-  if (int rc = ictr_camransac_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "camransac");
-  if (!d.cam_set) return fail(ICTR_ERR_STATE, "%s: ictr_camransac_set_camera comes first", what);
-  const HoCam cam = {d.fc[0], d.fc[1], d.cc[0], d.cc[1]};
-  hipLaunchKernelGGL(k_ho_points, dim3(ho_chunks(a.m)), dim3(kBlock), 0, nullptr, a, baseline * cam.fx, cam, d.X);
-  HIPCHK(hipGetLastError());
-  ictr_camransac_filled_(r, 1, 0);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_camransac_set_observations_from_window(ictr_camransac *r, const ictr_stereotrack *t) {
-  const char *what = "camransac_set_observations_from_window";
-  if (!r || !t) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camransac_view d;
-  if (int rc = ictr_camransac_view_(r, &d)) return rc;
-  HoArgs a;
-  if (int rc = ho_window(t, d.n, what, &a)) return rc;
-  if (d.pending) return ho_in_flight(what, "camransac");
-  if (d.nframes != a.bsize)
-    return fail(ICTR_ERR_INVALID, "%s: the window has %d frames, the RANSAC was made for %d", what, a.bsize, d.nframes);
-  for (int s = 0; s < d.nsides; ++s)
-    hipLaunchKernelGGL(k_ho_obs, dim3(ho_chunks(a.m), (unsigned)a.bsize), dim3(kBlock), 0, nullptr, a, s,
-                       d.xy + (size_t)s * (size_t)a.bsize * 2 * (size_t)a.m);
-  HIPCHK(hipGetLastError());
-  ictr_camransac_filled_(r, 0, 1);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_camfit_set_mask_from_camransac(ictr_camfit *r, const ictr_camransac *s, void *hip_stream) {
-  const char *what = "camfit_set_mask_from_camransac";
-  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_camfit_view d;
-  ictr_camransac_view v;
-  if (int rc = ictr_camfit_view_(r, &d)) return rc;
-  if (int rc = ictr_camransac_view_(s, &v)) return rc;
-  if (d.pending) return ho_in_flight(what, "camfit");
-  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the RANSAC has never run", what);
-  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the RANSAC has %d points, the fit %d", what, v.n, d.n);
-  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
-                        (hipStream_t)hip_stream));
-  ictr_camfit_filled_(r, 0, 0, 1);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_ba_set_mask_from_camransac(ictr_ba *r, const ictr_camransac *s, void *hip_stream) {
-  const char *what = "ba_set_mask_from_camransac";
-  if (!r || !s) return fail(ICTR_ERR_INVALID, "%s: NULL argument", what);
-  ictr_ba_view d;
-  ictr_camransac_view v;
-  if (int rc = ictr_ba_view_(r, &d)) return rc;
-  if (int rc = ictr_camransac_view_(s, &v)) return rc;
-  if (d.pending) return ho_in_flight(what, "ba");
-  if (!v.ran) return fail(ICTR_ERR_STATE, "%s: the RANSAC has never run", what);
-  if (v.n != d.n) return fail(ICTR_ERR_INVALID, "%s: the RANSAC has %d points, the adjuster %d", what, v.n, d.n);
-  HIPCHK(hipMemcpyAsync(d.words, v.words, sizeof(unsigned long long) * (size_t)d.nwords, hipMemcpyDeviceToDevice,
-                        (hipStream_t)hip_stream));
-  ictr_ba_filled_(r, 0, 0, 1);
-  return ICTR_OK;
-}
-
-extern "C" int ictr_debug_camransac_inputs(const ictr_camransac *r, double *X, double *xy, uint64_t *words) {
-  if (!r) return fail(ICTR_ERR_INVALID, "debug_camransac_inputs: camransac is NULL");
-  ictr_camransac_view v;
-  if (int rc = ictr_camransac_view_(r, &v)) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)v.n;
-  if (X) HIPCHK(hipMemcpy(X, v.X, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (xy) HIPCHK(hipMemcpy(xy, v.xy, sizeof(double) * 2 * (size_t)v.nsides * (size_t)v.nframes * n, hipMemcpyDeviceToHost));
-  if (words) {  // the mask in effect: every point where none is in use (bits past n clear)
-    if (v.use_mask) {
-      HIPCHK(hipMemcpy(words, v.mask, sizeof(uint64_t) * (size_t)v.nwords, hipMemcpyDeviceToHost));
-    } else {
-      for (int w = 0; w < v.nwords; ++w) words[w] = ~0ull;
-      if (v.n & 63) words[v.nwords - 1] = (1ull << (v.n & 63)) - 1ull;
-    }
-  }
-  return ICTR_OK;
-}
-
-extern "C" int ictr_debug_ba_inputs(const ictr_ba *r, double *X, double *xy, uint64_t *words) {
-  if (!r) return fail(ICTR_ERR_INVALID, "debug_ba_inputs: ba is NULL");
-  ictr_ba_view v;
-  if (int rc = ictr_ba_view_(r, &v)) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)v.n;
-  if (X) HIPCHK(hipMemcpy(X, v.X, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (xy) HIPCHK(hipMemcpy(xy, v.xy, sizeof(double) * 2 * (size_t)v.nsides * (size_t)v.nframes * n, hipMemcpyDeviceToHost));
-  if (words) HIPCHK(hipMemcpy(words, v.words, sizeof(uint64_t) * (size_t)v.nwords, hipMemcpyDeviceToHost));
-  return ICTR_OK;
-}
-
-// inspection: the device buffers as they stand, after everything enqueued so far on any stream
 extern "C" int ictr_debug_fsplit_pairs(const ictr_fsplit *r, double *xy) {
-  if (!r || !xy) return fail(ICTR_ERR_INVALID, "debug_fsplit_pairs: NULL argument");
+  if (!r || !xy) return null_object("debug_fsplit_pairs");
   ictr_fsplit_view v;
   if (int rc = ictr_fsplit_view_(r, &v)) return rc;
   HIPCHK(hipDeviceSynchronize());
@@ -331,14 +201,53 @@ extern "C" int ictr_debug_fsplit_pairs(const ictr_fsplit *r, double *xy) {
   return ICTR_OK;
 }
 
+// ---------------------------------------------------------------- the camera fit (one side: left, or with `right` the right)
+extern "C" int ictr_camfit_set_points_from_window(ictr_camfit *r, const ictr_stereotrack *t, double baseline) {
+  return ho_points(ho_of(r, ictr_camfit_inputs_), t, baseline, "camfit_set_points_from_window");
+}
+extern "C" int ictr_camfit_set_observations_from_window(ictr_camfit *r, const ictr_stereotrack *t, int right) {
+  return ho_obs(ho_of(r, ictr_camfit_inputs_), t, right != 0 ? 1 : 0, 1, "camfit_set_observations_from_window");
+}
+extern "C" int ictr_camfit_set_mask_from_fsplit(ictr_camfit *r, const ictr_fsplit *s, void *hip_stream) {
+  return ho_mask(ho_of(r, ictr_camfit_inputs_), ho_of(s, ictr_fsplit_mask_), hip_stream, "camfit_set_mask_from_fsplit");
+}
+extern "C" int ictr_camfit_set_mask_from_camransac(ictr_camfit *r, const ictr_camransac *s, void *hip_stream) {
+  return ho_mask(ho_of(r, ictr_camfit_inputs_), ho_of(s, ictr_camransac_mask_), hip_stream,
+                 "camfit_set_mask_from_camransac");
+}
 extern "C" int ictr_debug_camfit_inputs(const ictr_camfit *r, double *X, double *xy, uint64_t *words) {
   if (!r) return fail(ICTR_ERR_INVALID, "debug_camfit_inputs: camfit is NULL");
-  ictr_camfit_view v;
-  if (int rc = ictr_camfit_view_(r, &v)) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)v.n;
-  if (X) HIPCHK(hipMemcpy(X, v.X, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (xy) HIPCHK(hipMemcpy(xy, v.xy, sizeof(double) * 2 * (size_t)v.nframes * n, hipMemcpyDeviceToHost));
-  if (words) HIPCHK(hipMemcpy(words, v.words, sizeof(uint64_t) * (size_t)v.nwords, hipMemcpyDeviceToHost));
-  return ICTR_OK;
+  return ho_debug_inputs(ho_of(const_cast<ictr_camfit *>(r), ictr_camfit_inputs_), X, xy, words);
+}
+
+// ---------------------------------------------------------------- the bundle adjuster (every side it was made for)
+extern "C" int ictr_ba_set_points_from_window(ictr_ba *r, const ictr_stereotrack *t, double baseline) {
+  return ho_points(ho_of(r, ictr_ba_inputs_), t, baseline, "ba_set_points_from_window");
+}
+extern "C" int ictr_ba_set_observations_from_window(ictr_ba *r, const ictr_stereotrack *t) {
+  const WinDest d = ho_of(r, ictr_ba_inputs_);
+  return ho_obs(d, t, 0, d.in ? d.in->nsides : 0, "ba_set_observations_from_window");
+}
+extern "C" int ictr_ba_set_mask_from_fsplit(ictr_ba *r, const ictr_fsplit *s, void *hip_stream) {
+  return ho_mask(ho_of(r, ictr_ba_inputs_), ho_of(s, ictr_fsplit_mask_), hip_stream, "ba_set_mask_from_fsplit");
+}
+extern "C" int ictr_ba_set_mask_from_camransac(ictr_ba *r, const ictr_camransac *s, void *hip_stream) {
+  return ho_mask(ho_of(r, ictr_ba_inputs_), ho_of(s, ictr_camransac_mask_), hip_stream, "ba_set_mask_from_camransac");
+}
+extern "C" int ictr_debug_ba_inputs(const ictr_ba *r, double *X, double *xy, uint64_t *words) {
+  if (!r) return fail(ICTR_ERR_INVALID, "debug_ba_inputs: ba is NULL");
+  return ho_debug_inputs(ho_of(const_cast<ictr_ba *>(r), ictr_ba_inputs_), X, xy, words);
+}
+
+// ---------------------------------------------------------------- the window camera RANSAC (every side it was made for)
+extern "C" int ictr_camransac_set_points_from_window(ictr_camransac *r, const ictr_stereotrack *t, double baseline) {
+  return ho_points(ho_of(r, ictr_camransac_inputs_), t, baseline, "camransac_set_points_from_window");
+}
+extern "C" int ictr_camransac_set_observations_from_window(ictr_camransac *r, const ictr_stereotrack *t) {
+  const WinDest d = ho_of(r, ictr_camransac_inputs_);
+  return ho_obs(d, t, 0, d.in ? d.in->nsides : 0, "camransac_set_observations_from_window");
+}
+extern "C" int ictr_debug_camransac_inputs(const ictr_camransac *r, double *X, double *xy, uint64_t *words) {
+  if (!r) return fail(ICTR_ERR_INVALID, "debug_camransac_inputs: camransac is NULL");
+  return ho_debug_inputs(ho_of(const_cast<ictr_camransac *>(r), ictr_camransac_inputs_), X, xy, words, true);  // in effect
 }

@@ -26,9 +26,11 @@ extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v); 
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);
 
-// Device views for the window hand-over (ictr_handover.hip): what the files that see inside their objects expose so
-// that the window's history can be written into the split's, the fit's and the bundle adjuster's input buffers without
-// leaving the device.
+// The window hand-over (ictr_handover.hip, DESIGN.md §4 "Window hand-over"): what the files that see inside their objects
+// expose so that a counted window's history can be written into the next stages' input buffers without leaving the
+// device. The split's pairs buffer has a layout of its own (ictr_fsplit_view). The fit, the adjuster and the window
+// camera RANSAC each embed one ictr::WinInputs (ictr_wininputs.h) and hand it out as a WinDest; the split and the RANSAC
+// hand out the inlier words of their last run as a WinMaskSrc.
 struct ictr_stereotrack;
 struct ictr_fsplit;
 struct ictr_camfit;
@@ -41,43 +43,33 @@ struct ictr_stereotrack_view {
   long long m;
 };
 struct ictr_fsplit_view {
-  double *xy;                       // [np][4][n]
-  const unsigned long long *words;  // [nwords] inlier bits of the last run, in the result block on the device
-  int n, nwords, np;
-  int pending, ran;  // a run is in flight / was ever enqueued
+  double *xy;  // [np][4][n]
+  int n, np;
+  int pending;  // a run is in flight
 };
-struct ictr_camfit_view {
-  double *X, *xy;             // [3][n], [nframes][2][n]
-  unsigned long long *words;  // [nwords]
-  int n, nwords, nframes;
-  int pending, cam_set;
-  double fc[2], cc[2];
+namespace ictr {
+struct WinInputs;
+struct WinDest {
+  WinInputs *in;
+  const Readback *out;  // of the object: a run in flight fixes its inputs
+  const char *object;   // "camfit", "ba", "camransac": ictr_<object>_wait, ictr_<object>_set_camera in the messages
+  const char *noun;     // "fit", "adjuster", "RANSAC"
 };
-struct ictr_ba_view {
-  double *X, *xy;             // [3][n] the points as set, [nsides][nframes][2][n]
-  unsigned long long *words;  // [nwords]
-  int n, nwords, nframes, nsides;
-  int pending, cam_set;
-  double fc[2], cc[2];
+struct WinMaskSrc {
+  const unsigned long long *words;  // [ceil(n / 64)] inlier bits of the last run, in the result block on the device
+  int n;
+  bool ran;          // a run was ever enqueued
+  const char *noun;  // "split", "RANSAC"
 };
+}  // namespace ictr
 extern "C" int ictr_stereotrack_view_(const ictr_stereotrack *t, ictr_stereotrack_view *v);  // ictr_stereotrack.hip
 extern "C" int ictr_fsplit_view_(const ictr_fsplit *r, ictr_fsplit_view *v);                // ictr_fsplit.hip
-extern "C" int ictr_camfit_view_(const ictr_camfit *r, ictr_camfit_view *v);                // ictr_camfit.hip
-// the inputs a hand-over has filled on the device count as set (any of points, obs; mask: the words are to be used)
-extern "C" void ictr_fsplit_pairs_filled_(ictr_fsplit *r);
-extern "C" void ictr_camfit_filled_(ictr_camfit *r, int points, int obs, int mask);
-extern "C" int ictr_ba_view_(const ictr_ba *r, ictr_ba_view *v);  // ictr_ba.hip
-extern "C" void ictr_ba_filled_(ictr_ba *r, int points, int obs, int mask);
-struct ictr_camransac_view {
-  double *X, *xy;                   // [3][n], [nsides][nframes][2][n]
-  unsigned long long *mask;         // [nwords] the mask words as set
-  const unsigned long long *words;  // [nwords] the winner's inlier bits of the last run, in the result block on the device
-  int n, nwords, nframes, nsides;
-  int pending, ran, cam_set, use_mask;  // use_mask: the mask words are in use (a non-NULL ictr_camransac_set_mask came last)
-  double fc[2], cc[2];
-};
-extern "C" int ictr_camransac_view_(const ictr_camransac *r, ictr_camransac_view *v);  // ictr_camransac.hip
-extern "C" void ictr_camransac_filled_(ictr_camransac *r, int points, int obs);
+extern "C" void ictr_fsplit_pairs_filled_(ictr_fsplit *r);  // the pairs a hand-over has filled count as set
+extern "C" int ictr_fsplit_mask_(const ictr_fsplit *r, ictr::WinMaskSrc *m);
+extern "C" int ictr_camfit_inputs_(ictr_camfit *r, ictr::WinDest *d);        // ictr_camfit.hip
+extern "C" int ictr_ba_inputs_(ictr_ba *r, ictr::WinDest *d);                // ictr_ba.hip
+extern "C" int ictr_camransac_inputs_(ictr_camransac *r, ictr::WinDest *d);  // ictr_camransac.hip
+extern "C" int ictr_camransac_mask_(const ictr_camransac *r, ictr::WinMaskSrc *m);
 
 namespace ictr {
 

@@ -27,6 +27,7 @@ import numpy as np
 from . import _lib
 from ._hostmath import M64 as _M64, div as _div, draw_indices_n
 from ._lib import check, dp, f64c
+from ._wininputs import _pack_words
 
 __all__ = ["fit_f8", "epiline_dist", "draw_indices_n", "trials_host", "split_static_host", "split_static", "StaticSplitter",
            "pairs_from_tracks", "pairs_from_stereo_tracks", "SWEEPS"]
@@ -279,13 +280,6 @@ def split_static_host(pairs, ntrials=100, thresh=2.0, seed=0, detail=False):
         out.update(status=np.array(status, np.int32), cnt=np.array(cnt, np.uint32),
                    all_draws=np.array(all_draws, np.int32), all_F=np.array(all_F))
     return out
-
-
-def _pack_words(mask):
-    n = mask.size
-    bits = np.zeros((n + 63) // 64 * 64, np.uint8)
-    bits[:n] = mask
-    return np.packbits(bits.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view(np.uint64).copy()
 
 
 def _result(best_trial, best_count, draws, F, mask, dd):

@@ -12,7 +12,9 @@ import pytest
 import camfit_cases as K
 import windowcams_cases as WC
 from invcompcamtrack_amd import IctrError
+from invcompcamtrack_amd import bundle as B
 from invcompcamtrack_amd import camfit as F
+from invcompcamtrack_amd import camransac as R
 from invcompcamtrack_amd import fsplit
 from invcompcamtrack_amd import stereotrack as S
 from invcompcamtrack_amd import windowcams as W
@@ -228,6 +230,92 @@ def test_refusals_come_with_a_message_and_launch_nothing():
         W.window_cameras(*args, K.CAM, K.BASELINE, xy0=xy0)
     with pytest.raises(TypeError):
         W.window_cameras(*args, K.CAM, K.BASELINE, no_such_parameter=1)
+
+
+_OBJECTS = {  # name -> (constructor of (n, nframes), C prefix, has two sides)
+    "fitter": (F.CameraFitter, "camfit", False),
+    "adjuster": (lambda n, f: B.BundleAdjuster(n, f, 2), "ba", True),
+    "ransac": (lambda n, f: R.CameraRansac(n, f, 2), "camransac", True),
+}
+
+
+@pytest.mark.parametrize("name", list(_OBJECTS))
+def test_every_window_stage_refuses_alike_and_takes_the_window_alike(name):
+    """The from-window refusals of test_refusals_come_with_a_message_and_launch_nothing for the fitter, the adjuster and
+    the RANSAC: same order, same messages, nothing written; then the good setters against the host functions. The objects
+    differ in two things, kept as they are: the RANSAC takes no mask from another object's run, and its debug_inputs
+    answers in words the mask in effect (every point's bit while none is set) where the other two return the buffer."""
+    make, prefix, two = _OBJECTS[name]
+    c = golden()["two_frames"]
+    lr, rl, fl, fr = fields(c)
+    xy_t, m = c["xy_t"], len(c["rows"])
+    unset = F._words_of(np.ones(m, bool), m) if name == "ransac" else np.zeros((m + 63) // 64, np.uint64)
+
+    def untouched(o, words=unset):
+        d = o.debug_inputs()
+        assert not d["X"].any() and not d["xy"].any() and d["words"].tobytes() == words.tobytes()
+
+    def refused(o, call, match, words=unset):
+        with pytest.raises(IctrError, match=match):
+            call()
+        untouched(o, words)
+
+    obj = make(m, 2)
+    obj.set_camera(K.CAM)
+    win = S.StereoTrackWindow(lr.shape[2], lr.shape[1], 2)
+    win.open(S.field(lr[0], -1), rl[0])
+    for stage in range(2):  # open, then every frame in: not counted
+        refused(obj, lambda: obj.set_points_from_window(win, K.BASELINE), "not counted")
+        refused(obj, lambda: obj.set_observations_from_window(win), "not counted")
+        if stage == 0:
+            win.advance(fl[0][0], fl[0][1], fr[0][0], fr[0][1], S.field(lr[1], -1), rl[1])
+    assert win.count() == m
+    other, nocam, frames3 = make(m + 1, 2), make(m, 2), make(m, 3)  # n != M is looked at before the camera
+    other_unset = F._words_of(np.ones(m + 1, bool), m + 1) if name == "ransac" else unset
+    refused(other, lambda: other.set_points_from_window(win, K.BASELINE), "was made for", other_unset)
+    refused(other, lambda: other.set_observations_from_window(win), "was made for", other_unset)
+    refused(nocam, lambda: nocam.set_points_from_window(win, K.BASELINE), "set_camera comes first")
+    refused(frames3, lambda: frames3.set_observations_from_window(win), "frames")
+    # a mask from a source that never ran, and from one of another size that did
+    sources = []
+    if name == "ransac":
+        assert not hasattr(obj, "set_mask_from_fsplit") and not hasattr(obj, "set_mask_from_camransac")
+    else:
+        split, ran = fsplit.StaticSplitter(m, 2), R.CameraRansac(m, 2, 1)
+        refused(obj, lambda: obj.set_mask_from_fsplit(split), "never run")
+        refused(obj, lambda: obj.set_mask_from_camransac(ran), "never run")
+        split.set_pairs_from_window(win)
+        split.run_async(8, WC.TIGHT, 0)
+        ran.set_camera(K.CAM)
+        ran.set_points_from_window(win, K.BASELINE)
+        ran.set_observations_from_window(win)
+        ran.run_async(8, 2.0, 0)
+        refused(other, lambda: other.set_mask_from_fsplit(split), "points")
+        refused(other, lambda: other.set_mask_from_camransac(ran), "points")
+        sources = [split, ran]
+    # the good setters write what the host functions give, both sides for an object of two
+    obj.set_points_from_window(win, K.BASELINE)
+    obj.set_observations_from_window(win)
+    X = F.points_from_first_view(xy_t, K.CAM, F.depth_from_disparity(xy_t, K.FC[0], K.BASELINE))
+    left, right = F.observations_from_stereo_tracks(xy_t)
+    want = np.stack([left, right]) if two else left
+    got = obj.debug_inputs()
+    assert got["X"].tobytes() == np.ascontiguousarray(X).tobytes() and got["xy"].tobytes() == want.tobytes()
+    assert got["words"].tobytes() == unset.tobytes()
+    # a from-window setter while a run is in flight: refused with the object's own wait, nothing moves
+    if two:
+        obj.set_offset((K.BASELINE, 0.0, 0.0))
+    obj.run_async(8) if name == "ransac" else obj.run_async(noiter=2)
+    calls = [lambda: obj.set_points_from_window(win, K.BASELINE), lambda: obj.set_observations_from_window(win)]
+    if sources:
+        calls += [lambda: obj.set_mask_from_fsplit(sources[0]), lambda: obj.set_mask_from_camransac(sources[1])]
+    for call in calls:
+        with pytest.raises(IctrError, match="in flight.*ictr_%s_wait" % prefix):
+            call()
+    now = obj.debug_inputs()
+    assert all(now[k].tobytes() == got[k].tobytes() for k in ("X", "xy", "words"))
+    for o in sources + [obj]:
+        o.wait()
 
 
 def test_native_caller_and_cli(tmp_path, capsys):
