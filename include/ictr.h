@@ -391,6 +391,19 @@ float ictr_patchflow_last_kernel_ms(void);
  * waves per patch; unset, patches of more than 256 pixels take two. */
 int ictr_patchflow_last_form(void);
 
+/* The disparity of a rectified stereo pair: the same patches, layouts, refusals and pyramid walk as ictr_patchflow with
+ * ONE parameter per patch. The patch moves along x only (p += sum Gx (T - I) / sum Gx^2), y never moves and comes back
+ * with its input bits. A patch is lost iff its gradients vanish or sum Gx^2 <= 0.01 (sum Gx^2 + sum Gy^2): horizontal
+ * edges alone carry no disparity; vertical edges alone, which the 2-D call refuses, are kept. psz 1..32 (psz 1 is a
+ * legal 1-D patch). K = 0 is accepted. Build-defined: the statement of record is tests/patchdisp_np.py. */
+int ictr_patchdisp(const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, const float *pts, int64_t K, int psz, int lv_f,
+                   int lv_l, int maxiter, float eps, float *out, int *status, int *iters);
+/* duration in ms of the k_patchdisp launch of this thread's last ictr_patchdisp call (HIP events), < 0 if unknown */
+float ictr_patchdisp_last_kernel_ms(void);
+/* kernel form of this thread's last k_patchdisp launch (ictr_patchdisp or ictr_flowgrid_compute_x): pixels per lane * 10
+ * + waves per patch, one of 11, 41, 82, chosen by the patch size alone; 0 before the first launch */
+int ictr_patchdisp_last_form(void);
+
 /* ------------------------------------------------------------------ full-frame parametric alignment (extension)
  * Inverse-compositional Gauss-Newton alignment of a whole template region under one parametric warp:
  * model 0 translation (2), 1 SE(2) (3), 2 affine (6), 3 homography (8). These are the warp models BASELINE.json's
@@ -714,6 +727,10 @@ int ictr_flowgrid_dims(const ictr_flowgrid *g, int *nx, int *ny);
  * fills the lost nodes (dense_flow's rule); enqueued on hip_stream (NULL: the null stream), no host wait */
 int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, int psz, int lv_f,
                           int maxiter, float eps, void *hip_stream);
+/* the same with the 1-D kernel of ictr_patchdisp (a rectified stereo pair): same grid object, fill, gather and dense
+ * field; after the fill every y displacement of the grid is exactly +0.0 */
+int ictr_flowgrid_compute_x(ictr_flowgrid *g, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, int psz, int lv_f,
+                            int maxiter, float eps, void *hip_stream);
 /* injects node displacements d [ny][nx][2] and the lost mask [ny][nx] (1 = lost, its d is ignored) and fills */
 int ictr_flowgrid_set_nodes(ictr_flowgrid *g, const float *d, const uint8_t *lost);
 /* d after the fill and the lost mask; either may be NULL */

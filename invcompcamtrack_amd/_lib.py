@@ -188,6 +188,9 @@ SIGNATURES = {
     "ictr_patchflow": (C.c_int, [VP, VP, FP, I64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, FP, IP, IP]),
     "ictr_patchflow_last_kernel_ms": (C.c_float, []),
     "ictr_patchflow_last_form": (C.c_int, []),
+    "ictr_patchdisp": (C.c_int, [VP, VP, FP, I64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, FP, IP, IP]),
+    "ictr_patchdisp_last_kernel_ms": (C.c_float, []),
+    "ictr_patchdisp_last_form": (C.c_int, []),
     "ictr_icgn_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, IP,
                                    I64]),
     "ictr_icgn_destroy": (None, [VP]),
@@ -310,6 +313,7 @@ SIGNATURES = {
     "ictr_flowgrid_destroy": (None, [VP]),
     "ictr_flowgrid_dims": (C.c_int, [VP, IP, IP]),
     "ictr_flowgrid_compute": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP]),
+    "ictr_flowgrid_compute_x": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP]),
     "ictr_flowgrid_set_nodes": (C.c_int, [VP, FP, U8P]),
     "ictr_flowgrid_nodes": (C.c_int, [VP, FP, U8P]),
     "ictr_flowgrid_gather": (C.c_int, [VP, DP, I64, DP]),

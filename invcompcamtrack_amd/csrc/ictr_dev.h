@@ -209,6 +209,7 @@ struct PFArgs {
   float *out;        // SoA x'[K] y'[K] at level 0 (NaN when lost)
   int *status;       // 1 tracked, 0 lost
   int *iters;        // executed iterations (all levels)
+  float min_hx;      // k_patchdisp: the patch is kept iff hxx > min_hx * (hxx + hyy)
 };
 
 }  // namespace ictr

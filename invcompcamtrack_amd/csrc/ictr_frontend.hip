@@ -526,8 +526,9 @@ static int fg_fill(ictr_flowgrid *g, hipStream_t s) {
   g->filled = 1;
   return ICTR_OK;
 }
-extern "C" int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f,
-                                     int maxiter, float eps, void *hip_stream) {
+// nodes -> tracking (the 2-D launch or the 1-D one) -> d = out - pts -> fill
+static int fg_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int maxiter,
+                      float eps, void *hip_stream, void (*launch)(const PFArgs &, hipStream_t)) {
   if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
   PFArgs a;
   if (int rc = patchflow_args(pa, pb, psz, lv_f, 0, maxiter, eps, &a)) return rc;
@@ -541,9 +542,18 @@ extern "C" int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pa, c
   a.iters = g->iters;
   const dim3 grid((g->K + kBlock - 1) / kBlock), blk(kBlock);
   hipLaunchKernelGGL(k_fg_nodes, grid, blk, 0, s, g->pts, g->nx, g->K, g->step);
-  launch_patchflow(a, s);
+  launch(a, s);
   hipLaunchKernelGGL(k_fg_diff, grid, blk, 0, s, g->pts, g->out, g->status, g->K, g->draw, g->lost);
   return fg_fill(g, s);
+}
+extern "C" int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f,
+                                     int maxiter, float eps, void *hip_stream) {
+  return fg_compute(g, pa, pb, psz, lv_f, maxiter, eps, hip_stream, launch_patchflow);
+}
+// the 1-D kernel returns a node's y with its input bits: every y displacement of the grid is y0 - y0 = +0.0
+extern "C" int ictr_flowgrid_compute_x(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f,
+                                       int maxiter, float eps, void *hip_stream) {
+  return fg_compute(g, pa, pb, psz, lv_f, maxiter, eps, hip_stream, launch_patchdisp);
 }
 extern "C" int ictr_flowgrid_set_nodes(ictr_flowgrid *g, const float *d, const unsigned char *lost) {
   if (!g || !d || !lost) return fail(ICTR_ERR_INVALID, "flowgrid_set_nodes: NULL argument");

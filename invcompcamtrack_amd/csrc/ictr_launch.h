@@ -203,6 +203,9 @@ void launch_fsplit_mask(const FsplitArgs &a, hipStream_t s);
 void launch_patchflow(const PFArgs &a, hipStream_t s);
 // NPL * 10 + WPP of this thread's last launch_patchflow (11, 41, 161 or 82), 0 before the first
 int patchflow_last_form();
+// the 1-D (x only) search of a rectified stereo pair on the same arguments; its form (11, 41 or 82) likewise
+void launch_patchdisp(const PFArgs &a, hipStream_t s);
+int patchdisp_last_form();
 // the argument checks of a patch tracking and its level table; the point buffers and a->K stay the caller's
 int patchflow_args(const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int lv_l, int maxiter, float eps,
                    PFArgs *a);

@@ -221,6 +221,152 @@ void launch_patchflow(const PFArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((k_patchflow<16, 1>), g, blk, 0, s, a);
 }
 
+// ---------------------------------------------------------------- 1-D (x only) search for a rectified stereo pair
+// The same patches, pyramid walk and stopping rule as k_patchflow with ONE parameter: p moves along x, y never moves.
+//     hxx = sum Gx^2 (once per level),  bx = sum Gx (T - I(x + p, y)),  p += bx * (1 / hxx).
+// Conditioning: the patch is lost iff !(tr > 0) or !(hxx > min_hx * tr), tr = hxx + hyy: horizontal edges alone carry
+// no disparity, vertical edges alone (which the 2x2 system refuses) are kept. Gy lives only until hyy is summed; T and
+// Gx stay in registers; one wave sum per iteration sits on the chain. Forms and the two-wave exchange are
+// k_patchflow's (above): every patch of a two-wave workgroup runs every level and iteration slot.
+template <int NPL, int WPP>
+__global__ __launch_bounds__(kBlock) void k_patchdisp(PFArgs a) {
+  constexpr int PPB = kWaves / WPP;  // patches per workgroup
+  __shared__ float sSum[WPP > 1 ? kWaves : 1][2];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wsub = wave % WPP;
+  const int k = blockIdx.x * PPB + wave / WPP;
+  const bool valid = k < a.K;
+  if (WPP == 1 && !valid) return;
+  const int P = a.P, n = P * P;
+  const int kk = valid ? k : 0;
+  const float x0 = a.pts[kk], y0 = a.pts[kk + a.K];
+  float px = 0.0f;
+  bool ok = valid & (x0 == x0) & (y0 == y0);
+  int nit = 0;
+  int off[NPL];
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) off[i] = 0;
+  // sum over the patch's WPP waves of two / one per-wave totals (all waves of the patch get the same bits)
+  auto patch_sum2 = [&](float &u, float &v) {
+    u = pf_wave_sum(u);
+    v = pf_wave_sum(v);
+    if constexpr (WPP > 1) {
+      __syncthreads();  // (the previous reduction's partials have been read)
+      if (lane == 0) {
+        sSum[wave][0] = u;
+        sSum[wave][1] = v;
+      }
+      __syncthreads();
+      const int w0 = wave - wsub;
+      u = v = 0.0f;
+#pragma unroll
+      for (int q = 0; q < WPP; ++q) {
+        u += sSum[w0 + q][0];
+        v += sSum[w0 + q][1];
+      }
+    }
+  };
+  auto patch_sum1 = [&](float &u) {
+    u = pf_wave_sum(u);
+    if constexpr (WPP > 1) {
+      __syncthreads();
+      if (lane == 0) sSum[wave][0] = u;
+      __syncthreads();
+      const int w0 = wave - wsub;
+      u = 0.0f;
+#pragma unroll
+      for (int q = 0; q < WPP; ++q) u += sSum[w0 + q][0];
+    }
+  };
+
+  for (int l = a.lv_f; l >= a.lv_l && (WPP > 1 || ok); --l) {
+    const PFLevel L = a.lv[l];
+    if (l != a.lv_f) px *= 2.0f;
+    const float xl = x0 * L.scale, yl = y0 * L.scale;
+    if (ok && !pf_in_view(xl, yl, L.swo, L.sho)) ok = false;
+    if (WPP == 1 && !ok) break;
+    const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);  // (1,1): a harmless in-plane window
+    gconst_f32 pa = (gconst_f32)L.a, pax = (gconst_f32)L.ax, pay = (gconst_f32)L.ay, pb = (gconst_f32)L.b;
+    float T[NPL], Gx[NPL];
+    float hxx = 0.0f, hyy = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      const int q = wsub * 64 + lane + 64 * WPP * i;
+      const bool in = q < n;
+      off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
+      const int idx = ta.base + off[i];
+      const float t = pf_fetch(pa, idx, L.sw, ta), gx = pf_fetch(pax, idx, L.sw, ta), gy = pf_fetch(pay, idx, L.sw, ta);
+      T[i] = in ? t : 0.0f;
+      Gx[i] = in ? gx : 0.0f;
+      const float gyi = in ? gy : 0.0f;
+      hxx += Gx[i] * Gx[i];
+      hyy += gyi * gyi;
+    }
+    patch_sum2(hxx, hyy);
+    const float tr = hxx + hyy;
+    if (ok && (!(tr > 0.0f) || !(hxx > a.min_hx * tr))) ok = false;  // textureless, or horizontal edges alone
+    if (WPP == 1 && !ok) break;
+    const float ihx = 1.0f / hxx;
+    bool run = ok;  // this patch still iterates at this level
+    for (int it = 0; it < a.maxiter; ++it) {
+      if (WPP == 1 && !run) break;
+      const float cx = xl + px;
+      if (run && !pf_in_view(cx, yl, L.swo, L.sho)) {
+        ok = false;
+        run = false;
+        if (WPP == 1) break;
+      }
+      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? yl : 1.0f, P, L.sw, L.shift);
+      float bx = 0.0f;
+      PFWin w[NPL];
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) w[i] = pf_load(pb, tb.base + off[i], L.sw);  // all in flight before the first use
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) {
+        float r = T[i] - pf_blend(w[i], tb);
+        r = (wsub * 64 + lane + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+        bx += Gx[i] * r;
+      }
+      patch_sum1(bx);
+      if (run) {
+        const float dx = bx * ihx;
+        px += dx;
+        ++nit;
+        if (dx * dx < a.eps2) run = false;
+      }
+    }
+  }
+  if (lane == 0 && wsub == 0 && valid) {
+    const float s = 1.0f / a.lv[a.lv_l].scale;  // back to level-0 pixels
+    const float nanv = __int_as_float(0x7fc00000);
+    a.out[k] = ok ? x0 + px * s : nanv;
+    a.out[k + a.K] = ok ? y0 : nanv;  // the input's bits
+    a.status[k] = ok ? 1 : 0;
+    a.iters[k] = nit;
+  }
+}
+
+static thread_local int g_pd_form = 0;
+int patchdisp_last_form() { return g_pd_form; }
+
+// the form follows from the patch size alone: up to 4 pixels per lane one wave per patch, above that two
+void launch_patchdisp(const PFArgs &a, hipStream_t s) {
+  const int npl = (a.P * a.P + 63) / 64;
+  const dim3 blk(kBlock);
+  if (npl > 4) {
+    g_pd_form = 82;
+    hipLaunchKernelGGL((k_patchdisp<8, 2>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
+    return;
+  }
+  const dim3 g((a.K + kWaves - 1) / kWaves);
+  g_pd_form = npl <= 1 ? 11 : 41;
+  if (npl <= 1)
+    hipLaunchKernelGGL((k_patchdisp<1, 1>), g, blk, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_patchdisp<4, 1>), g, blk, 0, s, a);
+}
+
 }  // namespace ictr
 
 using namespace ictr;
@@ -265,10 +411,13 @@ int ictr::patchflow_args(const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, i
   a.maxiter = maxiter;
   a.eps2 = eps * eps;
   a.min_det = 1e-4f;
+  a.min_hx = 1e-2f;
   return ICTR_OK;
 }
-extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
-                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
+// one tracking call from host arrays: the 2-D launch (ictr_patchflow) or the 1-D one (ictr_patchdisp), timed into *ms
+static int pf_track_host(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz, int lv_f,
+                         int lv_l, int maxiter, float eps, float *out, int *status, int *iters,
+                         void (*launch)(const PFArgs &, hipStream_t), float *ms) {
   if (K < 0 || (K > 0 && (!pts || !out))) return fail(ICTR_ERR_INVALID, "patchflow: bad arguments (psz must be 1..32)");
   PFArgs a;
   if (int rc = patchflow_args(pa, pb, psz, lv_f, lv_l, maxiter, eps, &a)) return rc;
@@ -287,12 +436,23 @@ extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, co
   static thread_local hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (!ev0 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
   if (ev0) (void)hipEventRecord(ev0, nullptr);
-  launch_patchflow(a, nullptr);
+  launch(a, nullptr);
   if (ev0) (void)hipEventRecord(ev1, nullptr);
-  g_pf_ms = -1.0f;  // ... unless the launch and the first copy back succeed
+  *ms = -1.0f;  // ... unless the launch and the first copy back succeed
   HIPCHK(hipMemcpy(out, a.out, sizeof(float) * 2 * K, hipMemcpyDeviceToHost));
-  if (ev0 && hipEventElapsedTime(&g_pf_ms, ev0, ev1) != hipSuccess) g_pf_ms = -1.0f;
+  if (ev0 && hipEventElapsedTime(ms, ev0, ev1) != hipSuccess) *ms = -1.0f;
   if (status) HIPCHK(hipMemcpy(status, a.status, sizeof(int) * K, hipMemcpyDeviceToHost));
   if (iters) HIPCHK(hipMemcpy(iters, a.iters, sizeof(int) * K, hipMemcpyDeviceToHost));
   return ICTR_OK;
+}
+extern "C" int ictr_patchflow(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
+                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
+  return pf_track_host(pa, pb, pts, K, psz, lv_f, lv_l, maxiter, eps, out, status, iters, launch_patchflow, &g_pf_ms);
+}
+static thread_local float g_pd_ms = -1.0f;
+extern "C" float ictr_patchdisp_last_kernel_ms(void) { return g_pd_ms; }
+extern "C" int ictr_patchdisp_last_form(void) { return patchdisp_last_form(); }
+extern "C" int ictr_patchdisp(const ictr_pyramid *pa, const ictr_pyramid *pb, const float *pts, int64_t K, int psz,
+                              int lv_f, int lv_l, int maxiter, float eps, float *out, int *status, int *iters) {
+  return pf_track_host(pa, pb, pts, K, psz, lv_f, lv_l, maxiter, eps, out, status, iters, launch_patchdisp, &g_pd_ms);
 }

@@ -24,7 +24,8 @@ from .classoftrack import oftrack
 from .tracker import Pyramid
 
 __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms",
-           "last_form", "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
+           "last_form", "track_disparity", "dense_disparity", "disparity_last_kernel_ms", "disparity_last_form",
+           "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
 
 
 def last_kernel_ms():
@@ -85,7 +86,40 @@ def track_points(pyr_a, pyr_b, pts, psz=15, lv_f=None, lv_l=0, maxiter=10, eps=0
     return np.ascontiguousarray(out.T), status.astype(bool), iters
 
 
-def dense_flow(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01):
+def disparity_last_kernel_ms():
+    """Duration of the k_patchdisp launch of the last track_disparity call (HIP events), or None."""
+    ms = float(_lib.load().ictr_patchdisp_last_kernel_ms())
+    return ms if ms >= 0 else None
+
+
+def disparity_last_form():
+    """Kernel form of this thread's last k_patchdisp launch: 11, 41 or 82 by the patch size alone, 0 before the first."""
+    return int(_lib.load().ictr_patchdisp_last_form())
+
+
+def track_disparity(pyr_a, pyr_b, pts, psz=15, lv_f=None, lv_l=0, maxiter=10, eps=0.01):
+    """track_points for a rectified stereo pair (``ictr_patchdisp``): a 1-parameter search along x. Same arguments and
+    types; new[:, 1] has pts[:, 1]'s bits for a tracked point. A patch of vertical edges alone is kept (track_points
+    loses it), a patch of horizontal edges alone is lost."""
+    pts = np.atleast_2d(np.asarray(pts, np.float32))
+    K = pts.shape[0]
+    lv_f = pyr_a.lv_f if lv_f is None else lv_f
+    soa = np.ascontiguousarray(pts.T)
+    out = np.empty((2, K), np.float32)
+    status = np.zeros(K, np.int32)
+    iters = np.zeros(K, np.int32)
+    check(_lib.load().ictr_patchdisp(pyr_a._h, pyr_b._h, fp(soa), K, psz, lv_f, lv_l, maxiter, float(eps), fp(out),
+                                     status.ctypes.data_as(_lib.IP), iters.ctypes.data_as(_lib.IP)))
+    return np.ascontiguousarray(out.T), status.astype(bool), iters
+
+
+def dense_disparity(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01):
+    """dense_flow with the nodes tracked by track_disparity: the definition of FlowGrid.compute_x's result. The y plane
+    is +0.0 everywhere."""
+    return dense_flow(pyr_a, pyr_b, step, psz, lv_f, maxiter, eps, _track=track_disparity)
+
+
+def dense_flow(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01, _track=None):
     """(H, W, 2) float32 displacement field A -> B: patches tracked on a `step`-pixel grid, bilinearly up-sampled;
     lost grid points take the displacement of the nearest tracked one in their row/column scan (0 if none)."""
     w, h = pyr_a.w, pyr_a.h
@@ -93,7 +127,7 @@ def dense_flow(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01):
     ys = np.arange(step // 2, h, step, dtype=np.float32)
     gx, gy = np.meshgrid(xs, ys)
     pts = np.stack([gx.ravel(), gy.ravel()], 1)
-    new, ok, _ = track_points(pyr_a, pyr_b, pts, psz=psz, lv_f=lv_f, maxiter=maxiter, eps=eps)
+    new, ok, _ = (_track or track_points)(pyr_a, pyr_b, pts, psz=psz, lv_f=lv_f, maxiter=maxiter, eps=eps)
     d = (new - pts).reshape(len(ys), len(xs), 2)
     bad = ~ok.reshape(len(ys), len(xs))
     if bad.any():
@@ -221,6 +255,14 @@ class FlowGrid:
         lv_f = pyr_a.lv_f if lv_f is None else lv_f
         check(_lib.load().ictr_flowgrid_compute(self._h, pyr_a._h, pyr_b._h, int(psz), int(lv_f), int(maxiter),
                                                 float(eps), C.c_void_p(stream or 0)))
+        return self
+
+    def compute_x(self, pyr_a, pyr_b, psz=15, lv_f=None, maxiter=10, eps=0.01, stream=None):
+        """compute for a rectified stereo pair: the nodes are tracked along x only (k_patchdisp); every y displacement
+        of the grid is +0.0. The field equals dense_disparity's. Enqueued, no host wait."""
+        lv_f = pyr_a.lv_f if lv_f is None else lv_f
+        check(_lib.load().ictr_flowgrid_compute_x(self._h, pyr_a._h, pyr_b._h, int(psz), int(lv_f), int(maxiter),
+                                                  float(eps), C.c_void_p(stream or 0)))
         return self
 
     def set_nodes(self, d, lost):

@@ -1,11 +1,12 @@
 """The checked stereo track window of a sequence (run_test_OF_track.py:170-223):
 
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
-         [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0]
+         [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
-(StereoPointTracker). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+(StereoPointTracker); --disparity 1d computes the stereo grids with the 1-D search along x (FlowGrid.compute_x) instead of
+the 2-D tracker with y dropped. With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -44,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--step", type=int, default=4)
     ap.add_argument("--th_ratio", type=float, default=0.2)
     ap.add_argument("--th_abs", type=float, default=1.0)
+    ap.add_argument("--disparity", choices=("2d", "1d"), default="2d")
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
     th = dict(th_ratio=a.th_ratio, th_abs=a.th_abs)
     if a.fields:
@@ -59,7 +61,7 @@ def main(argv=None):
             return 2
         frames = [[np.asarray(iof.read_image_gray(fn), np.float32) for fn in p] for p in pairs]
         h, w = frames[0][0].shape
-        t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, **th)
+        t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity, **th)
         for left, right in frames:
             t.push_frames(left, right)
         xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()

@@ -290,10 +290,15 @@ class StereoPointTracker:
     Per stereo frame the two pyramids and the two stereo FlowGrids (left -> right, right -> left, used x only), per frame
     pair the four temporal grids; the grid handles go to a StereoTrackWindow. No dense field is formed and the host reads
     nothing back before window(). keep_grids=True keeps every frame's grids in ``grids`` (a list of dicts lr, rl and, from
-    the second frame on, l_fwd, l_bwd, r_fwd, r_bwd) for inspection; otherwise two sets are reused in turn."""
+    the second frame on, l_fwd, l_bwd, r_fwd, r_bwd) for inspection; otherwise two sets are reused in turn.
+    disparity="2d" (the default) computes the stereo grids with the 2-D tracker and drops y; "1d" computes them with the
+    1-D search along x (FlowGrid.compute_x), which keeps vertical edges and is not misled by tilted 1-D structure."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
-                 xy0=None, keep_grids=False):
+                 xy0=None, keep_grids=False, disparity="2d"):
+        if disparity not in ("2d", "1d"):
+            raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
+        self.disparity = disparity
         self.w, self.h, self.bsize = int(w), int(h), int(bsize)
         self.step, self.psz, self.lv_f, self.maxiter, self.eps = int(step), int(psz), int(lv_f), int(maxiter), float(eps)
         self.xy0, self.keep_grids = xy0, bool(keep_grids)
@@ -330,8 +335,12 @@ class StereoPointTracker:
         pl, pr = slot
         kw = dict(psz=self.psz, lv_f=self.lv_f, maxiter=self.maxiter, eps=self.eps)
         g = self._grid_set(k)
-        g["lr"].compute(pl, pr, **kw)
-        g["rl"].compute(pr, pl, **kw)
+        if self.disparity == "1d":
+            g["lr"].compute_x(pl, pr, **kw)
+            g["rl"].compute_x(pr, pl, **kw)
+        else:
+            g["lr"].compute(pl, pr, **kw)
+            g["rl"].compute(pr, pl, **kw)
         if k == 0:
             self.win.open(g["lr"], g["rl"], self.xy0)
         else:
