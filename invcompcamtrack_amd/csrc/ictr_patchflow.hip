@@ -7,10 +7,13 @@
 // same Gauss-Newton skeleton as the camera tracker with J = identity:
 //     H = sum [Gx Gy]^T [Gx Gy] over the template patch (once per level),
 //     b = sum [Gx Gy]^T (T - I(x + p)),   p += H^-1 b.
-// Sampling convention = util_getPatch's (utilities.cpp:55-113: patch-constant bilinear weights, ceil(x+1e-5f) taps,
-// offsets -(P - P/2)...), so the patches it sees are the tracker's patches. The algorithm itself is build-defined:
-// there is no reference implementation to pin it ("parity unpinned by the reference"); the oracle is
-// oracle/np_patchflow.py.
+// Sampling convention = util_getPatch's (utilities.cpp:55-113: patch-constant bilinear weights from x - floor(x),
+// offsets -(P - P/2)...) except for the first tap: util_getPatch takes it at ceil(x + 1e-5f), this kernel at
+// floor(x) + 1. The two agree wherever x + 1e-5f is not rounded across an integer; they differ at integer x >= 256
+// (the sum rounds back to x: taps (x-1, x) with all the weight on x-1, the patch one pixel left or up) and at the f32
+// value one ulp below an integer n <= 64 (ceil gives n + 1 against floor's n - 1: the weight lands one pixel right or
+// down). floor(x) + 1 is the pair the weights are taken for at every x. The algorithm itself is build-defined: there is
+// no reference implementation to pin it ("parity unpinned by the reference"); the oracle is oracle/np_patchflow.py.
 //
 // MI355X mapping: one wave64 per patch does ALL levels and ALL iterations of its patch inside one launch (the
 // problems are independent: no global reduction, no launch per iteration). The template T/Gx/Gy of the patch lives
@@ -40,8 +43,9 @@ struct PFTaps {
 // shift = (pad - P) * (sw + 1): (p + P/2) is the patch's first pixel only in a plane padded by exactly P
 __device__ __forceinline__ PFTaps pf_taps(float mx, float my, int P, int sw, int shift) {
   PFTaps t;
-  const int p0 = (int)ceilf(mx + .00001f), p1 = (int)ceilf(my + .00001f);
-  const float r0 = mx - floorf(mx), r1 = my - floorf(my);
+  const float f0 = floorf(mx), f1 = floorf(my);
+  const int p0 = (int)f0 + 1, p1 = (int)f1 + 1;  // taps (floor, floor + 1): the pair the weights are taken for
+  const float r0 = mx - f0, r1 = my - f1;
   t.w0 = r0 * r1;
   t.w1 = (1 - r0) * r1;
   t.w2 = r0 * (1 - r1);

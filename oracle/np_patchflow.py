@@ -2,7 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY. The algorithm is build-defined (the reference obtains flow from an external binary that is
 not in its repository), so this oracle pins the HIP kernel against an independent implementation, not against the
-reference: "parity unpinned by the reference". Sampling = np_oracle.patches (util_getPatch's convention).
+reference: "parity unpinned by the reference". Sampling = util_getPatch's convention (np_oracle.patches) except for the
+first tap, which is floor(x) + 1 here and ceil(x + 1e-5f) there: the two differ at integer x >= 256 and one ulp below an
+integer <= 64, where f32 rounds that sum across an integer and the reference's taps are not the pair its weights mean.
 
 The sampling (_sample) takes (p + psz // 2) for the patch's first pixel, which holds in a plane padded by exactly psz. A
 pyramid padded by more (pad >= psz is the contract) is sampled through the view plane[pad - psz:, pad - psz:], whose
@@ -49,12 +51,14 @@ def _view(plane, pad, psz):
 
 
 def _sample(plane, x, y, psz, pad):
-    """(value, majorant sum w|v|) of the patch at (x, y), both (psz, psz) f64. The value is np_oracle.patches' for one
-    centre, bit for bit (same f32 expressions in the same order, the four taps as slices; tests/test_patchflow_cpu.py
-    compares the two)."""
+    """(value, majorant sum w|v|) of the patch at (x, y), both (psz, psz) f64. Taps (floor, floor + 1) in x and in y,
+    weights from x - floor(x), y - floor(y): at an integer centre the value is the plane's own pixels. Wherever
+    f32(x + 1e-5) is not rounded across an integer the value is np_oracle.patches' for one centre, bit for bit (same
+    f32 expressions in the same order, the four taps as slices; tests/test_patchflow_cpu.py compares the two, and
+    states where they differ)."""
     v = _view(plane, pad, psz)
     x, y = f32(x), f32(y)
-    p0, p1 = int(np.ceil(x + f32(.00001))), int(np.ceil(y + f32(.00001)))
+    p0, p1 = int(np.floor(x)) + 1, int(np.floor(y)) + 1
     r0, r1 = x - np.floor(x), y - np.floor(y)
     w0, w1, w2, w3 = r0 * r1, (f32(1) - r0) * r1, r0 * (f32(1) - r1), (f32(1) - r0) * (f32(1) - r1)
     row, col = p1 + psz // 2, p0 + psz // 2

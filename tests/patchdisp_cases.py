@@ -15,6 +15,9 @@ Tolerances (nothing here is fitted to the device):
              the 2-D tests, because the device adds in another order than the restatement.
   decisions  status and iters are demanded exactly. The interior points are chosen so that every decision of the oracle
              (in view along x, conditioning, convergence) is further from its threshold than the run's tolerance.
+
+The far jobs (far_jobs) run patchflow_cases' x-shift far frame and points through the three forms: x of 256 and more with
+a displacement known in advance (check_truth, check_continuity, and patchflow_cases.check_grid for compute_x).
 """
 from __future__ import annotations
 
@@ -142,6 +145,31 @@ def jobs():
     return OrderedDict((j.key, j) for j in _jobs())
 
 
+# ---------------------------------------------------------------- the far jobs: coordinates of 256 and more
+FAR_FRAME = "farx-320x64"               # patchflow_cases' analytic pair with B = A shifted by 1.7 px along x
+# |new_x - x - 1.7| px of a full run at every point, per patch size: twice the f64 oracle's worst error over the far
+# jobs' points with x < 255 (patchflow_cases.far_low). Measured on the CPU by test_patchdisp_cpu.py, which fails if a
+# bar is exceeded there or is above 0.25 px.
+TRUTH_BAR = {8: 0.069, 15: 0.055, 31: 0.053}             # 2 x (0.0342, 0.0273, 0.0264), rounded up
+
+
+def _far_jobs(pts_of=PC.far_points):
+    out = []
+    pts = pts_of(FAR_FRAME)
+    for psz in FORM_PSZ:
+        for l in range(LV + 1):
+            out.append(Job(f"far-step-p{psz}-l{l}", "step", FAR_FRAME, psz, psz, l, l, 1, pts))
+        for lv_f, lv_l in PC.FAR_RANGES:
+            out.append(Job(f"far-full-p{psz}-{lv_f}{lv_l}", "full", FAR_FRAME, psz, psz, lv_f, lv_l, PC.FAR_MAXITER, pts))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def far_jobs():
+    """patchflow_cases' far frame and points for the three forms: 'step' at each level and 'full' over FAR_RANGES."""
+    return OrderedDict((j.key, j) for j in _far_jobs())
+
+
 def perm_of(psz):
     return np.random.default_rng(psz).permutation(N_INTERIOR)
 
@@ -191,14 +219,21 @@ def full_tolerance(new_o, detail):
     return FULL_MARGIN * FULL_FACTOR * base_tolerance(new_o, detail)
 
 
-def margins_ok(new_o, detail):
-    """Per point: every decision the oracle took is further from its threshold than an f32 evaluation can move it."""
-    tol = full_tolerance(new_o, detail)  # positions at level l move by tol / 2^l <= tol
+def out_ulp(new_o):
+    """Per point: the spacing of f32 at the returned x, 0 for a lost point."""
+    with np.errstate(invalid="ignore"):
+        return np.nan_to_num(np.spacing(np.abs(new_o[:, 0])).astype(np.float64))
+
+
+def margins_ok(new_o, detail, far=False):
+    """Per point: every decision the oracle took is further from its threshold than an f32 evaluation can move it (far:
+    one spacing of f32 at the position included, see patchflow_cases.compare_full)."""
+    tol = full_tolerance(new_o, detail) + (out_ulp(new_o) if far else 0.0)  # positions at level l move by tol / 2^l <= tol
     return (detail["view"] > tol) & (detail["eps_px"] > tol) & (detail["hx"] > HX_MARGIN)
 
 
 def check_margins(job, new_o, detail):
-    tol = full_tolerance(new_o, detail)
+    tol = full_tolerance(new_o, detail) + (out_ulp(new_o) if PC.is_far(job) else 0.0)
     assert np.all(detail["view"] > tol), (job.key, "pick other points: in-view margin", detail["view"], tol)
     assert np.all(detail["eps_px"] > tol), (job.key, "pick other points: convergence margin", detail["eps_px"], tol)
     assert np.all(detail["hx"] > HX_MARGIN), (job.key, "pick other points: conditioning margin", detail["hx"])
@@ -227,7 +262,8 @@ def compare_step(job, new, status, iters, O):
 
 def compare_full(job, new, status, iters, O):
     """Full-run check: status and iters exactly, x within full_tolerance, y with the input's bits, lost points NaN;
-    returns the worst ratio of the x error against bound sum + u |new_x|."""
+    returns the worst ratio of the x error against bound sum + u |new_x|. On the far frame one spacing of f32 at the
+    returned x is taken off the error first, as in patchflow_cases.compare_full and for its reason."""
     new_o, ok_o, it_o, det = oracle_full(O, job)
     check_margins(job, new_o, det)
     assert np.array_equal(status, ok_o), (job.key, status, ok_o)
@@ -237,6 +273,8 @@ def compare_full(job, new, status, iters, O):
     if not ok_o.any():
         return 0.0
     err = np.abs(new[ok_o, 0].astype(np.float64) - new_o[ok_o, 0].astype(np.float64))
+    if PC.is_far(job):
+        err = np.maximum(err - out_ulp(new_o)[ok_o], 0.0)
     base = base_tolerance(new_o, det)[ok_o]
     assert np.all(err <= FULL_MARGIN * FULL_FACTOR * base), (job.key, "worst error / tolerance",
                                                             float((err / (FULL_MARGIN * FULL_FACTOR * base)).max()))
@@ -282,3 +320,42 @@ def scene_errors(new, ok):
     """(kept, median |x error|, max |x error|) against the truth -3.3 px."""
     e = np.abs((new[ok, 0].astype(np.float64) - scene_nodes()[ok, 0]) + SCENE_SHIFT)
     return int(ok.sum()), float(np.median(e)) if e.size else np.inf, float(e.max()) if e.size else np.inf
+
+
+# ---------------------------------------------------------------- the far jobs' checks
+def truth_error(job, new):
+    """|new_x - x - s| per point, level-0 px (NaN where new is)."""
+    return np.abs(new[:, 0].astype(np.float64) - job.pts[:, 0].astype(np.float64) - PC.far_shift(job.frame)[0])
+
+
+def check_truth(job, new, status):
+    """A full far job: every point is kept and is within the patch size's bar of the known shift."""
+    assert status.all(), (job.key, "lost", np.nonzero(~status)[0].tolist())
+    err = truth_error(job, new)
+    bad = np.nonzero(~(err <= TRUTH_BAR[job.psz]))[0]
+    assert bad.size == 0, (job.key, "truth: |new_x - x - shift| above", TRUTH_BAR[job.psz], "at",
+                           [(job.pts[k].tolist(), round(float(err[k]), 4)) for k in bad])
+    return float(err.max())
+
+
+def discontinuous(job, new, status, iters, O):
+    """[(n, largest difference of the x displacements inside the triple, iters)] of the triples that break the rule of
+    check_continuity, and the largest difference over all triples."""
+    new_o, _, _, det = oracle_full(O, job)
+    tol = full_tolerance(new_o, det)
+    d = new[:, 0].astype(np.float64) - job.pts[:, 0].astype(np.float64)
+    worst, bad = 0.0, []
+    for n, ks in PC.far_triples(job.frame):
+        diff = float(d[ks].max() - d[ks].min()) if status[ks].all() else np.inf
+        worst = max(worst, diff)
+        if not diff <= 4 * tol[ks].max() or len(set(iters[ks].tolist())) != 1:
+            bad.append((n, round(diff, 6), iters[ks].tolist()))
+    return bad, worst
+
+
+def check_continuity(job, new, status, iters, O):
+    """A full far job: inside a triple (three x one ulp apart) the displacements differ by no more than 4 x the job's
+    tolerance, and status and iters are equal. Returns the largest difference."""
+    bad, worst = discontinuous(job, new, status, iters, O)
+    assert not bad, (job.key, "continuity: (n, largest difference inside the triple, iters)", bad)
+    return worst

@@ -4,14 +4,15 @@ from the kernel and shares no code with the oracle (patchdisp_np.py). The kernel
 functions k_patchflow takes them from (pf_taps, pf_blend, wave_sum_dpp, the wave-order LDS sum); so does this file, from
 their restatement in patchflow_f32.py (_taps, _fetch, _sum; shape = (NPL, WPP) or None for one serial sum, see there).
 
-defect (None or one of DEFECTS) injects one mistake the tests must be able to see: patchflow_f32's six, which act in the
-shared functions, and three of the 1-D rule itself.
+defect (None or one of DEFECTS + TAP_DEFECTS) injects one mistake the tests must be able to see: patchflow_f32's six and
+its two tap defects, which act in the shared functions, and three of the 1-D rule itself.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from patchflow_f32 import DEFECTS as _SHARED
+from patchflow_f32 import TAP_DEFECTS  # noqa: F401  (the two failure forms of a rounded-up first tap, in _taps)
 from patchflow_f32 import ONE, ZERO, _fetch, _sum, _taps, f32
 
 DEFECTS = _SHARED + ("solve by tr", "y follows x", "no doubling")

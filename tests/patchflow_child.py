@@ -1,4 +1,5 @@
-"""Runs the patch-flow jobs of one group of patchflow_cases on the device and keeps what came back.
+"""Runs the patch-flow jobs of one group of patchflow_cases (its table and its far jobs) on the device and keeps what came
+back.
 
 Imported by test_gpu_patchflow_forms.py for group 0 (default dispatch). Groups 1 and 2 need ICTR_PF_WPP=1 / 2, which
 launch_patchflow reads once per process, so the test starts this file as a fresh process for each:
@@ -36,12 +37,17 @@ def run_jobs(jobs):
     return out
 
 
+def all_jobs(group):
+    """The group's job table, then its far jobs (patchflow_cases.far_jobs): one process runs both."""
+    return list(PC.jobs(group).values()) + list(PC.far_jobs(group).values())
+
+
 def main(argv):
     group, path = int(argv[1]), argv[2]
     if os.environ.get("ICTR_PF_WPP") != str(group):
         raise SystemExit(f"ICTR_PF_WPP must be {group} for group {group}")
     flat = {}
-    for key, (new, ok, it, form) in run_jobs(PC.jobs(group).values()).items():
+    for key, (new, ok, it, form) in run_jobs(all_jobs(group)).items():
         flat[key + "/new"], flat[key + "/ok"], flat[key + "/it"], flat[key + "/form"] = new, ok, it, np.int32(form)
     np.savez(path, **flat)
 

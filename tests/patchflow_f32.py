@@ -6,7 +6,7 @@ shape = (NPL, WPP): pixel q of the patch belongs to wave (q // 64) % WPP, lane q
 slots serially from 0, the 64 lanes meet in a pairwise tree (wave_sum_dpp: 1, 2, half row, row, then (r0 + r1) + (r2 + r3)),
 the WPP wave totals are added in wave order from 0.  shape = None: one serial sum over the pixels in q order.
 
-defect (None or one of DEFECTS) injects one mistake the tests must be able to see.
+defect (None or one of DEFECTS + TAP_DEFECTS) injects one mistake the tests must be able to see.
 """
 from __future__ import annotations
 
@@ -15,11 +15,26 @@ import numpy as np
 f32 = np.float32
 ONE, ZERO = f32(1), f32(0)
 DEFECTS = ("drop last column", "drop last row", "swap w1 w2", "half of P-1", "omit second wave", "rescale by lv_f")
+# the two ways in which a first tap taken by rounding up x plus a small constant leaves the pair (floor, floor + 1) that
+# the weights are taken for; injected like DEFECTS, seen by the truth and continuity checks of the far frames
+TAP_DEFECTS = ("tap pair one back at large integers", "tap pair one ahead just below small integers")
+
+
+def _first_tap(x, defect):
+    """floor(x) + 1: the kernel's first tap (the second is floor(x))."""
+    fl = np.floor(x)
+    p = int(fl) + 1
+    if defect == "tap pair one back at large integers" and x == fl and x >= 256:
+        p -= 1                                    # taps (x - 1, x), all the weight on x - 1
+    if defect == "tap pair one ahead just below small integers" and x != fl and fl + 1 <= 64 \
+            and np.nextafter(x, f32(np.inf)) == fl + 1:
+        p += 1                                    # taps (n, n + 1) for x = n - 1 ulp, weight ~1 on n + 1
+    return p
 
 
 def _taps(x, y, P, defect):
     x, y = f32(x), f32(y)
-    p0, p1 = int(np.ceil(f32(x + f32(.00001)))), int(np.ceil(f32(y + f32(.00001))))
+    p0, p1 = _first_tap(x, defect), _first_tap(y, defect)
     r0, r1 = f32(x - np.floor(x)), f32(y - np.floor(y))
     w0, w1, w2, w3 = f32(r0 * r1), f32(f32(ONE - r0) * r1), f32(r0 * f32(ONE - r1)), f32(f32(ONE - r0) * f32(ONE - r1))
     if defect == "swap w1 w2":

@@ -24,12 +24,12 @@ def O(oracle):
 
 @pytest.fixture(scope="module")
 def res():
-    """{job key: (new, status, iters, form)} of every job of the table on the device."""
+    """{job key: (new, status, iters, form)} of every job of the table, and of the far jobs, on the device."""
     if not _results:
         import invcompcamtrack_amd as ic
         from invcompcamtrack_amd import patchflow as pf
         pyr = {}
-        for job in DC.jobs().values():
+        for job in list(DC.jobs().values()) + list(DC.far_jobs().values()):
             if (job.frame, job.pad) not in pyr:
                 a, b = DC.pair(job.frame)
                 pyr[job.frame, job.pad] = (ic.Pyramid(a, DC.LV, job.pad), ic.Pyramid(b, DC.LV, job.pad))
@@ -172,6 +172,58 @@ def test_a_patch_does_not_depend_on_its_launch(res):
             on, ok1, oi, of = res[f"indep-one{k}-p{psz}"]
             assert of == form and ok1.all()
             assert np.array_equal(_bits(on[0]), _bits(new[k])) and oi[0] == it[k], (psz, k, on[0], new[k])
+
+
+# ---------------------------------------------------------------- the far jobs: x of 256 and more
+def test_far_one_step_within_the_derived_bound(O, res):
+    """The far frame's 'step' jobs in the three forms: integer x of 40, 255, 256, 300, the values one ulp to either
+    side, half-pixel and two-decimal points, each level."""
+    def one(job):
+        new, ok, it, form = res[job.key]
+        assert form == DC.form(job) and ok.all(), job.key
+        return DC.compare_step(job, new, ok, it, O)
+
+    worst = _collect([j for j in DC.far_jobs().values() if j.kind == "step"], one)
+    print(f"\nfar frame: device one-step error / bound, worst per form: {worst}")
+    assert len(worst) == 3
+
+
+def test_far_full_runs_truth_and_continuity(O, res):
+    """The far frame's full runs: status and iters equal the oracle's, x within compare_full's tolerance (one spacing of
+    f32 at x taken off first), y with the input's bits; every point kept and within TRUTH_BAR of the 1.7 px the frame was
+    made with; inside a triple of x one ulp apart the displacements agree to 4 x the tolerance, with equal iters."""
+    truth, cont = {}, [0.0]
+
+    def one(job):
+        new, ok, it, form = res[job.key]
+        assert form == DC.form(job), job.key
+        r = DC.compare_full(job, new, ok, it, O)
+        truth[job.psz] = max(truth.get(job.psz, 0.0), DC.check_truth(job, new, ok))
+        cont[0] = max(cont[0], DC.check_continuity(job, new, ok, it, O))
+        return r
+
+    worst = _collect([j for j in DC.far_jobs().values() if j.kind == "full"], one)
+    print(f"\nfar frame: device full-run error beyond one spacing / (bound sum + u |new_x|), worst per form: {worst}; "
+          f"worst truth error per psz {truth} (bars {DC.TRUTH_BAR}); largest difference inside a triple {cont[0]:.2e} px")
+    assert len(worst) == 3
+
+
+def test_flow_grid_compute_x_on_the_far_pair():
+    """FlowGrid.compute_x on the far pair, its dense field read at the node pixels (so after the fill): patchflow_cases.
+    check_grid with the 1-D bar."""
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    PC = DC.PC
+    a, b = DC.pair(DC.FAR_FRAME)
+    w, h = PC.frame_size(DC.FAR_FRAME)
+    pa, pb = ic.Pyramid(a, PC.GRID_LV, PC.GRID_PSZ), ic.Pyramid(b, PC.GRID_LV, PC.GRID_PSZ)
+    g = pf.FlowGrid(w, h, PC.GRID_STEP).compute_x(pa, pb, psz=PC.GRID_PSZ, lv_f=PC.GRID_LV)
+    assert pf.disparity_last_form() == 41
+    field = g.dense()
+    assert not field[..., 1].any()
+    got = PC.check_grid(DC.FAR_FRAME, field, g.nodes()[1], DC.TRUTH_BAR[PC.GRID_PSZ])
+    print(f"\ndevice grid (x only), largest interior error {got[0]:.4f} px, median below 256 {got[1]:.4f}, from 256 on "
+          f"{got[2]:.4f}")
 
 
 # ---------------------------------------------------------------- usefulness

@@ -1,6 +1,9 @@
 """k_patchflow in each of its four launch forms against the f64 oracle (oracle/np_patchflow.py), over the job table of
 patchflow_cases.py: raw one-iteration steps against the derived bound, full runs with status and iters exact, lv_l > 0,
-pyramids padded by more than psz, and a patch's independence of what else is in its launch.
+pyramids padded by more than psz, and a patch's independence of what else is in its launch. The far jobs of the same
+module (frames up to 576 px with a displacement known in advance) hold the tap rule at coordinates of 256 and more in every
+form: the one-step bound, the full-run check, the truth, continuity inside a triple of points one ulp apart, and the flow
+grid on such a pair.
 
 Group 0 (default dispatch: <1,1>, <4,1>, <8,2>) runs in this process. <16,1> needs ICTR_PF_WPP=1 and <8,2> on small patches
 ICTR_PF_WPP=2; the launcher reads the variable once per process, so groups 1 and 2 each run in a fresh child process
@@ -48,7 +51,8 @@ def _run_child(group, workdir):
     if r.returncode != 0:
         return f"child of group {group} ended with {r.returncode}:\n{r.stdout[-3000:]}"
     z = np.load(out)
-    return {key: (z[key + "/new"], z[key + "/ok"], z[key + "/it"], int(z[key + "/form"])) for key in PC.jobs(group)}
+    return {j.key: (z[j.key + "/new"], z[j.key + "/ok"], z[j.key + "/it"], int(z[j.key + "/form"]))
+            for j in child.all_jobs(group)}
 
 
 @pytest.fixture
@@ -57,7 +61,7 @@ def results(workdir):
     def get(group):
         if group not in _results:
             if group == 0:
-                _results[0] = child.run_jobs(PC.jobs(0).values())
+                _results[0] = child.run_jobs(child.all_jobs(0))
             elif _child_died:  # (group 0 ran before any child: the groups are parametrised in order)
                 pytest.skip(f"the child of group {_child_died[0]} faulted or hung: no further child is started")
             else:
@@ -120,6 +124,8 @@ def test_refusals_and_the_empty_launch():
 def test_every_launch_took_its_form(results, group):
     res = results(group)
     for key, job in PC.jobs(group).items():
+        assert res[key][3] == PC.form(job), (key, res[key][3], PC.form(job))
+    for key, job in PC.far_jobs(group).items():
         assert res[key][3] == PC.form(job), (key, res[key][3], PC.form(job))
     assert set(PC.GROUP_FORM[group].values()) == {res[k][3] for k in res}
 
@@ -214,3 +220,67 @@ def test_a_patch_does_not_depend_on_its_launch(results, group):
             on, ok1, oi, of = res[f"g{group}-indep-one{k}-p{psz}"]
             assert of == form and ok1.all()
             assert np.array_equal(_bits(on[0]), _bits(new[k])) and oi[0] == it[k], (psz, k, on[0], new[k])
+
+
+# ---------------------------------------------------------------- the far jobs: coordinates of 256 and more
+@pytest.mark.parametrize("group", GROUPS)
+def test_far_one_step_within_the_derived_bound(O, results, group):
+    """The far frames' 'step' jobs: integer centres of 40, 255, 256, 300 (512 at level 1), the values one ulp to either
+    side, half-pixel and two-decimal points, each level. At an integer centre the patch is the plane's own pixels (the
+    oracle's are, test_patchflow_cpu.py), so a tap pair off by one leaves the bound by orders of magnitude."""
+    res = results(group)
+
+    def one(job):
+        new, ok, it, form = res[job.key]
+        assert form == PC.form(job) and ok.all(), job.key
+        return PC.compare_step(job, new, ok, it, O)
+
+    worst = _collect([j for j in PC.far_jobs(group).values() if j.kind == "step"], one)
+    print(f"\ngroup {group}: far frames, device one-step error / bound, worst per form: {worst}")
+    assert set(worst) == {PC.GROUP_FORM[group][p] for p in PC.GROUP_FORM_PSZ[group]}
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_far_full_runs_truth_and_continuity(O, results, group):
+    """The far frames' full runs: status and iters equal the oracle's and positions are within compare_full's tolerance
+    (one spacing of f32 at the position taken off first, see there); every point is kept and within TRUTH_BAR of the
+    shift the frame was made with; the three points of a triple, one ulp apart, get displacements within 4 x the
+    tolerance of each other with equal iters."""
+    res = results(group)
+    truth, cont = {}, [0.0]
+
+    def one(job):
+        new, ok, it, form = res[job.key]
+        assert form == PC.form(job), job.key
+        r = PC.compare_full(job, new, ok, it, O)
+        truth[job.psz] = max(truth.get(job.psz, 0.0), PC.check_truth(job, new, ok))
+        cont[0] = max(cont[0], PC.check_continuity(job, new, ok, it, O))
+        return r
+
+    worst = _collect([j for j in PC.far_jobs(group).values() if j.kind == "full"], one)
+    print(f"\ngroup {group}: far frames, device full-run error beyond one spacing / (bound sum + u |new|), worst per form: "
+          f"{worst}; worst truth error per psz {truth} (bars {PC.TRUTH_BAR}); largest difference inside a triple "
+          f"{cont[0]:.2e} px")
+    assert set(worst) == {PC.GROUP_FORM[group][p] for p in PC.GROUP_FORM_PSZ[group]}
+
+
+def test_far_jobs_reached_all_four_forms(results):
+    forms = {results(g)[k][3] for g in GROUPS for k in PC.far_jobs(g)}
+    assert forms == {11, 41, 161, 82}
+
+
+@pytest.mark.parametrize("frame", ("farx-320x64", "fary-64x320"))
+def test_flow_grid_on_a_far_pair(frame):
+    """FlowGrid.compute on a far pair, its dense field read at the node pixels (so after the fill): no interior node is
+    lost, every interior node is within the bar of the known shift, and the nodes from 256 on are no worse than the
+    others (median, factor 2). With the first tap one back at integers >= 256 every node from 256 on is a pixel off."""
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    a, b = PC.pair(frame)
+    w, h = PC.frame_size(frame)
+    pa, pb = ic.Pyramid(a, PC.GRID_LV, PC.GRID_PSZ), ic.Pyramid(b, PC.GRID_LV, PC.GRID_PSZ)
+    g = pf.FlowGrid(w, h, PC.GRID_STEP).compute(pa, pb, psz=PC.GRID_PSZ, lv_f=PC.GRID_LV)
+    assert pf.last_form() == 41
+    got = PC.check_grid(frame, g.dense(), g.nodes()[1], PC.TRUTH_BAR[PC.GRID_PSZ])
+    print(f"\n{frame}: device grid, largest interior error {got[0]:.4f} px, median below 256 {got[1]:.4f}, from 256 on "
+          f"{got[2]:.4f}")

@@ -229,3 +229,138 @@ def test_usefulness_on_the_oracle(O, tilt, seed):
     print(f"tilt {tilt} seed {seed}: 1-D kept {k1}, median {med1:.4f} max {max1:.4f} px; 2-D kept {k2}, median {med2:.4f} px")
     assert k1 == 98 and med1 <= DC.BAR_1D
     assert med2 >= DC.BAR_2D
+
+
+# ---------------------------------------------------------------- the far frame: x of 256 and more
+def _far_fulls():
+    return [j for j in DC.far_jobs().values() if j.kind == "full"]
+
+
+def test_far_jobs_are_the_2d_tests_frame_and_points():
+    jobs = DC.far_jobs()
+    assert not set(jobs) & set(DC.jobs()) and len(jobs) == 3 * 6
+    assert {DC.form(j) for j in jobs.values()} == {11, 41, 82}
+    for j in jobs.values():
+        assert j.frame == DC.FAR_FRAME and np.array_equal(j.pts, DC.PC.far_points(DC.FAR_FRAME))
+    assert {(j.lv_f, j.lv_l) for j in _far_fulls()} == set(DC.PC.FAR_RANGES)
+
+
+def test_far_restatement_stays_within_the_one_step_bound(O):
+    worst = {}
+    for job in DC.far_jobs().values():
+        if job.kind != "step":
+            continue
+        for shape in ("form", None):
+            new, ok, it = _restate(O, job, shape)
+            assert ok.all(), job.key
+            key = (DC.form(job), "form" if shape else "serial")
+            worst[key] = max(worst.get(key, 0.0), DC.compare_step(job, new, ok, it, O))
+    print("far frame, one-step restatement / bound:", worst)
+    assert len(worst) == 6 and max(worst.values()) <= 1.0
+
+
+def test_far_full_runs_truth_and_continuity(O):
+    """Every full far job, on the oracle and on the restatement: margins, equal decisions and x (compare_full, FULL_FACTOR
+    as for the old table once one spacing of the returned f32 x is taken off), every point within the bar of the known
+    shift, every triple continuous. An excess over FULL_FACTOR with the spacing left in is exactly one spacing."""
+    worst, raw, truth, cont = {}, (0.0, None), {}, 0.0
+    for job in _far_fulls():
+        new_o, ok_o, it_o, det = DC.oracle_full(O, job)
+        new, ok, it = _restate(O, job)
+        f = DC.form(job)
+        worst[f] = max(worst.get(f, 0.0), DC.compare_full(job, new, ok, it, O))
+        err = np.abs(new[:, 0].astype(np.float64) - new_o[:, 0])
+        base = DC.base_tolerance(new_o, det)
+        k = int(np.argmax(err / base))
+        if err[k] / base[k] > raw[0]:
+            raw = (float(err[k] / base[k]), (job.key, job.pts[k].tolist()))
+        over = err > DC.FULL_FACTOR * base
+        assert np.array_equal(err[over], DC.out_ulp(new_o)[over]), (job.key, "an excess that is not one spacing of f32")
+        for res in ((new_o, ok_o, it_o), (new, ok, it)):
+            truth[job.psz] = max(truth.get(job.psz, 0.0), DC.check_truth(job, res[0], res[1]))
+            cont = max(cont, DC.check_continuity(job, *res, O))
+    print(f"far frame: full-run restatement / (bound sum + u |new_x|) beyond one spacing: {worst}; with the spacing left "
+          f"in: {raw[0]:.4f} at {raw[1]}; worst truth error per psz {truth} (bars {DC.TRUTH_BAR}); largest difference "
+          f"inside a triple {cont:.2e} px")
+    assert len(worst) == 3 and max(worst.values()) <= DC.FULL_FACTOR
+
+
+def test_truth_bars_are_twice_the_oracles_error_below_255(O):
+    worst = {}
+    low = DC.PC.far_low(DC.FAR_FRAME)
+    for job in _far_fulls():
+        new_o, ok_o, _, _ = DC.oracle_full(O, job)
+        assert ok_o.all()
+        worst[job.psz] = max(worst.get(job.psz, 0.0), float(DC.truth_error(job, new_o)[low].max()))
+    print("far frame: oracle's worst truth error below 255, per psz:", {k: round(v, 4) for k, v in worst.items()})
+    assert set(worst) == set(DC.TRUTH_BAR)
+    for psz, bar in DC.TRUTH_BAR.items():
+        assert 2 * worst[psz] <= bar <= 2 * worst[psz] + 0.001 and bar <= 0.25, (psz, worst[psz], bar)
+
+
+def _hits(job, level, large):
+    a = (job.pts[:, 0] * np.float32(0.5 ** level)).astype(np.float32)
+    if large:
+        return (a == np.floor(a)) & (a >= 256)
+    up = np.nextafter(a, np.float32(np.inf))
+    return (up == np.floor(up)) & (up <= 64) & (a != np.floor(a))
+
+
+@pytest.mark.parametrize("defect", F32.TAP_DEFECTS)
+def test_tap_defects_are_seen(O, defect):
+    """The two failure forms of a first tap at ceil(x + 1e-5f), injected (they act in x and in y; on this frame the y are
+    below 64 and none is one ulp below an integer). At integers >= 256: the truth check fails at exactly the points that
+    are one at the run's last level, by one pixel of that level, and the continuity check at their triples. One ulp
+    below an integer <= 64: the continuity check fails at exactly the triples that hold such a value at a level of the
+    run. Every other point keeps the sound restatement's bits."""
+    large = defect == F32.TAP_DEFECTS[0]
+    seen = 0
+    for job in _far_fulls():
+        new, ok, it = _restate(O, job, defect=defect)
+        ref = _restate(O, job)
+        hit = np.zeros(len(job.pts), bool)
+        for l in range(job.lv_l, job.lv_f + 1):
+            hit |= _hits(job, l, large)
+        assert ok.all()
+        assert np.array_equal(new[~hit], ref[0][~hit]) and np.array_equal(it[~hit], ref[2][~hit]), job.key
+        last = _hits(job, job.lv_l, large)
+        triples = DC.PC.far_triples(job.frame)
+        broken = {b[0] for b in DC.discontinuous(job, new, ok, it, O)[0]}
+        if large:
+            e = DC.truth_error(job, new)
+            assert np.array_equal(~(e <= DC.TRUTH_BAR[job.psz]), last), (job.key, e)
+            assert np.all(np.abs(e[last] - 2.0 ** job.lv_l) <= DC.TRUTH_BAR[job.psz]), (job.key, e[last])
+            assert broken == {n for n, ks in triples if last[ks].any()}, (job.key, broken)
+            if last.any():
+                with pytest.raises(AssertionError):
+                    DC.check_truth(job, new, ok)
+            else:
+                DC.check_truth(job, new, ok)
+        else:
+            assert broken == {n for n, ks in triples if hit[ks].any()}, (job.key, broken)
+        if broken:
+            with pytest.raises(AssertionError):
+                DC.check_continuity(job, new, ok, it, O)
+        else:
+            DC.check_continuity(job, new, ok, it, O)
+        seen += int(last.sum())
+    assert seen >= 9
+
+
+def test_flow_grid_compute_x_on_the_far_pair_on_the_oracle(O):
+    """dense_disparity's host path (the definition of FlowGrid.compute_x's field) with the 1-D oracle tracking the nodes."""
+    from invcompcamtrack_amd import patchflow as pf
+    PC = DC.PC
+    pa, pb = DC.oracle_pyramids(O, DC.FAR_FRAME, PC.GRID_PSZ)
+    kept = {}
+
+    def track(a, b, pts, psz, lv_f, maxiter, eps):
+        out = DN.track_disparity(a, b, pts, psz, lv_f, 0, maxiter, eps)
+        kept["ok"] = out[1]
+        return out
+
+    field = pf.dense_flow(pa, pb, PC.GRID_STEP, PC.GRID_PSZ, PC.GRID_LV, _track=track)
+    assert not field[..., 1].any()
+    xy, _ = PC.grid_nodes(DC.FAR_FRAME)
+    got = PC.check_grid(DC.FAR_FRAME, field, ~kept["ok"].reshape(xy.shape[:2]), DC.TRUTH_BAR[PC.GRID_PSZ])
+    print(f"oracle grid (x only), largest interior error {got[0]:.4f} px, median below 256 {got[1]:.4f}, from 256 on {got[2]:.4f}")

@@ -1,7 +1,9 @@
 """The patch-flow oracle (oracle/np_patchflow.py) and the case table (patchflow_cases.py) on the CPU: an f32 restatement
 of the kernel in each launch form's summation shape stays inside one_step's derived bound, six injected defects each leave
 it, every decision of the oracle over the table has the margin that lets the GPU module demand equal status and iters,
-the padding of the pyramid does not move a result, and the final rescale is 2^lv_l."""
+the padding of the pyramid does not move a result, and the final rescale is 2^lv_l. The far frames (coordinates of 256 and
+more, a displacement known in advance) hold the tap rule: truth, continuity across an integer, the plane's own pixels at
+integer centres, the flow grid, and the two ways a rounded-up first tap fails, injected and seen."""
 import numpy as np
 import pytest
 
@@ -43,8 +45,11 @@ def test_dispatch_table_matches_the_launcher():
 
 
 def test_oracle_sampling_is_np_oracle_patches(O):
-    """np_patchflow._sample (slices) against np_oracle.patches (gathers), which defines the sampling: the same bits, on
-    a plane padded by psz and through the view of a plane padded by more."""
+    """np_patchflow._sample (slices) against np_oracle.patches (gathers), the reference's util_getPatch: the same bits,
+    on a plane padded by psz and through the view of a plane padded by more, at points below 256 with two-decimal
+    fractions, where the two first-tap rules (floor(x) + 1 here, ceil(x + 1e-5f) there) choose the same taps.
+    np_oracle.patches no longer defines the patch-flow sampling: where the rules differ, _sample is held by
+    test_integer_centres_sample_the_planes_own_pixels below, which also shows what np_oracle.patches returns there."""
     from oracle import np_oracle as N
     for frame in PC.SIZES:
         pts = np.concatenate([PC.interior(frame), PC.special(frame)[:3]])
@@ -227,3 +232,229 @@ def test_one_iteration_at_one_level_is_one_step(O, l):
         # p = f32(step) (u |step|), out = f32(x0 + p * 2^l) (u |out|)
         assert np.all(np.abs(got - step) <= PC.U * (np.abs(step) + np.abs(new) / 2.0 ** l))
         assert np.abs(step).max() > 0.02
+
+
+# ---------------------------------------------------------------- the far frames: coordinates of 256 and more
+def _far_fulls(group):
+    return [j for j in PC.far_jobs(group).values() if j.kind == "full"]
+
+
+def test_far_points_and_jobs():
+    """The triples are one ulp apart around the integers the tap rule needs, there are half-pixel and two-decimal points
+    on both sides of 256, every point is the first of its candidates' kind, and the far jobs reach all four forms."""
+    for frame in PC.FAR:
+        pts, axis = PC.far_points(frame), PC.far_axis(frame)
+        w, h = PC.frame_size(frame)
+        assert np.all(pts >= 0) and np.all(pts[:, 0] <= w) and np.all(pts[:, 1] <= h)
+        ns = [n for n, _ in PC.far_triples(frame)]
+        assert set(ns) >= ({512, 514} if max(w, h) == 576 else {24, 63, 64, 100, 255, 256, 257, 300})
+        for n, ks in PC.far_triples(frame):
+            a = pts[ks, axis]
+            assert a[1] == n and np.nextafter(a[0], np.float32(np.inf)) == a[1] == np.nextafter(a[2], np.float32(-np.inf))
+            assert len(set(pts[ks, 1 - axis].tolist())) == 1
+            if n in PC.FAR_INTEGER:
+                assert pts[ks[1], 1 - axis] == np.floor(pts[ks[1], 1 - axis])
+        more = pts[3 * len(ns):, axis]
+        mid = 512 if max(w, h) == 576 else 256
+        assert (more < mid).sum() >= 2 and (more > mid).sum() >= 2
+        assert (more % 1 == 0.5).sum() >= 2 and ((more * 100) % 50 != 0).sum() >= 2
+        low = PC.far_low(frame)
+        assert low.sum() >= (1 if max(w, h) == 576 else 10) and (~low).sum() >= 6
+    forms = {PC.form(j) for g in GROUPS for j in PC.far_jobs(g).values()}
+    assert forms == {11, 41, 82, 161}
+    assert sum(len(PC.far_jobs(g)) for g in GROUPS) == 5 * (3 * 6 + 4)
+    for g in GROUPS:
+        assert not set(PC.far_jobs(g)) & set(PC.jobs(g))
+        big = [j for j in PC.far_jobs(g).values() if j.frame == "farx-576x64"]
+        assert {(j.lv_f, j.lv_l) for j in big if j.kind == "full"} == {(1, 1), (2, 0)}
+    assert not set(PC.FAR) & set(PC.SIZES)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_far_restatement_stays_within_the_one_step_bound(O, group):
+    worst = {}
+    for job in PC.far_jobs(group).values():
+        if job.kind != "step":
+            continue
+        for shape in ("form", None):
+            new, ok, it = _restate(O, job, shape)
+            assert ok.all(), job.key
+            key = (PC.form(job), "form" if shape else "serial")
+            worst[key] = max(worst.get(key, 0.0), PC.compare_step(job, new, ok, it, O))
+    print("far frames, one-step restatement / bound:", worst)
+    assert worst and max(worst.values()) <= 1.0
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_far_full_runs_truth_and_continuity(O, group):
+    """Every full far job, on the oracle and on the restatement: margins, equal decisions and positions (compare_full,
+    FULL_FACTOR as for the old table once one spacing of the returned f32 position is taken off, see compare_full), every
+    point within the bar of the known shift, every triple continuous. The ratio with that spacing left in is printed with
+    its job: it is what exceeds FULL_FACTOR on these frames, and it is exactly one spacing wherever it does."""
+    worst, raw, truth, cont = {}, (0.0, None), {}, 0.0
+    for job in _far_fulls(group):
+        new_o, ok_o, it_o, det = PC.oracle_full(O, job)
+        new, ok, it = _restate(O, job)
+        f = PC.form(job)
+        worst[f] = max(worst.get(f, 0.0), PC.compare_full(job, new, ok, it, O))
+        err = np.abs(new.astype(np.float64) - new_o).max(axis=1)
+        base = det["bound"] + PC.U * np.abs(new_o).max(axis=1)
+        k = int(np.argmax(err / base))
+        if err[k] / base[k] > raw[0]:
+            raw = (float(err[k] / base[k]), (job.key, job.pts[k].tolist()))
+        over = err > PC.FULL_FACTOR * base
+        assert np.array_equal(err[over], PC.out_ulp(new_o)[over]), (job.key, "an excess that is not one spacing of f32")
+        for res in ((new_o, ok_o, it_o), (new, ok, it)):
+            truth[job.psz] = max(truth.get(job.psz, 0.0), PC.check_truth(job, res[0], res[1]))
+            cont = max(cont, PC.check_continuity(job, *res, O))
+    print(f"far frames, group {group}: full-run restatement / (bound sum + u |new|) beyond one spacing: {worst}; with the "
+          f"spacing left in: {raw[0]:.4f} at {raw[1]}; worst truth error per psz {truth} (bars {PC.TRUTH_BAR}); largest "
+          f"difference inside a triple {cont:.2e} px")
+    assert max(worst.values()) <= PC.FULL_FACTOR
+
+
+def test_truth_bars_are_twice_the_oracles_error_below_255(O):
+    """TRUTH_BAR[psz] = 2 x the f64 oracle's worst |new - pts - shift| over the far jobs' points with every level-0
+    coordinate below 255 (and not one ulp below an integer), rounded up to 0.001 px; at most 0.25 px."""
+    worst = {}
+    for group in GROUPS:
+        for job in _far_fulls(group):
+            low = PC.far_low(job.frame)
+            new_o, ok_o, _, _ = PC.oracle_full(O, job)
+            assert ok_o.all()
+            worst[job.psz] = max(worst.get(job.psz, 0.0), float(PC.truth_error(job, new_o)[low].max()))
+    print("far frames: oracle's worst truth error below 255, per psz:", {k: round(v, 4) for k, v in worst.items()})
+    assert set(worst) == set(PC.TRUTH_BAR)
+    for psz, bar in PC.TRUTH_BAR.items():
+        assert 2 * worst[psz] <= bar <= 2 * worst[psz] + 0.001 and bar <= 0.25, (psz, worst[psz], bar)
+
+
+INTEGER_CENTRES = (40, 255, 256, 300)
+
+
+@pytest.mark.parametrize("frame", ("farx-320x64", "fary-64x320"))
+def test_integer_centres_sample_the_planes_own_pixels(O, frame):
+    """At an integer centre the fraction is 0 and the patch is the plane's own pixels, bit for bit, from row
+    y - (P - P/2) and column x - (P - P/2) of the image on (util_getPatch's window, test_oracle_kats.py; P/2 for an even
+    P): in the oracle, in the restatement, on a plane padded by psz and by more. np_oracle.patches, the reference's rule,
+    gives the same below 256 and the window one pixel back along the long axis from 256 on: the defect this rule
+    does not have."""
+    from oracle import np_oracle as N
+    img = PC.pair(frame)[0]
+    axis = PC.far_axis(frame)
+    for psz, pad in ((1, 1), (8, 8), (15, 15), (15, 19), (31, 31), (32, 32)):
+        pa, _ = PC.oracle_pyramids(O, frame, pad)
+        assert np.array_equal(pa.img[0][pad:-pad, pad:-pad], img)
+        sh = pad - psz
+        view = pa.img[0][sh:, sh:] if sh else pa.img[0]
+        for n in INTEGER_CENTRES:
+            x, y = (n, 32) if axis == 0 else (32, n)
+            r0, c0 = y - (psz - psz // 2), x - (psz - psz // 2)
+            own = np.pad(img, psz, mode="edge")[r0 + psz:r0 + 2 * psz, c0 + psz:c0 + 2 * psz]
+            assert own.shape == (psz, psz)
+            if psz <= 15:
+                assert np.array_equal(own, img[r0:r0 + psz, c0:c0 + psz])      # (inside the image: no padding read)
+            got, _ = NP._sample(pa.img[0], x, y, psz, pad)
+            assert np.array_equal(got, own.astype(np.float64)), (psz, pad, n)
+            assert np.array_equal(F32._fetch(view, F32._taps(x, y, psz, None), psz), own.ravel()), (psz, pad, n)
+            if pad == psz:
+                ref = N.patches(pa.img[0], np.array([x], np.float32), np.array([y], np.float32), psz)[0].reshape(psz, psz)
+                back = np.pad(img, psz + 1, mode="edge")
+                back = back[r0 + psz + (axis == 0 or n < 256):, c0 + psz + (axis == 1 or n < 256):][:psz, :psz]
+                assert np.array_equal(ref, back), (psz, n)
+                assert np.array_equal(ref, own) == (n < 256), (psz, n)
+
+
+def _where(job, level):
+    """The coordinate along the long axis at a level, f32 as the kernel forms it."""
+    return (job.pts[:, PC.far_axis(job.frame)] * np.float32(0.5 ** level)).astype(np.float32)
+
+
+def _is_large_integer(job, level):
+    a = _where(job, level)
+    return (a == np.floor(a)) & (a >= 256)
+
+
+def _is_just_below_small_integer(job, level):
+    a = _where(job, level)
+    up = np.nextafter(a, np.float32(np.inf))
+    return (up == np.floor(up)) & (up <= 64) & (a != np.floor(a))
+
+
+def _fails(check, *args):
+    try:
+        check(*args)
+    except AssertionError:
+        return True
+    return False
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_tap_pair_one_back_at_large_integers_is_seen_by_truth_and_continuity(O, group):
+    """The first tap of ceil(x + 1e-5f) at an integer x >= 256, injected into the restatement: the truth check fails at
+    exactly the points whose coordinate at the run's last level is such an integer, the continuity check at exactly
+    their triples; everywhere else the results are the sound restatement's bits."""
+    defect = "tap pair one back at large integers"
+    seen = 0
+    for job in _far_fulls(group):
+        new, ok, it = _restate(O, job, defect=defect)
+        ref = _restate(O, job)
+        hit = np.zeros(len(job.pts), bool)
+        for l in range(job.lv_l, job.lv_f + 1):
+            hit |= _is_large_integer(job, l)
+        assert np.array_equal(new[~hit], ref[0][~hit]) and np.array_equal(it[~hit], ref[2][~hit]), job.key
+        last = _is_large_integer(job, job.lv_l)
+        assert ok.all()
+        bad = ~(PC.truth_error(job, new) <= PC.TRUTH_BAR[job.psz])
+        assert np.array_equal(bad, last), (job.key, np.nonzero(bad)[0], np.nonzero(last)[0])
+        assert _fails(PC.check_truth, job, new, ok) == bool(last.any()), job.key
+        broken = {b[0] for b in PC.discontinuous(job, new, ok, it, O)[0]}
+        assert broken == {n for n, ks in PC.far_triples(job.frame) if last[ks].any()}, (job.key, broken)
+        assert _fails(PC.check_continuity, job, new, ok, it, O) == bool(last.any()), job.key
+        seen += int(last.sum())
+        if last.any():
+            e = PC.truth_error(job, new)[last]
+            # one pixel of the run's last level, as the parent reports it
+            assert np.all(np.abs(e - 2.0 ** job.lv_l) <= PC.TRUTH_BAR[job.psz]), (job.key, e)
+    assert seen >= 3
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_tap_pair_one_ahead_just_below_small_integers_is_seen_by_continuity(O, group):
+    """The first tap of ceil(x + 1e-5f) one ulp below an integer n <= 64, injected: the continuity check fails at
+    exactly the triples whose lower point is such a value at a level of the run (100 - 1 ulp is one at level 2 only: 25
+    - 1 ulp), and the points that are no such value at any level keep the sound restatement's bits."""
+    defect = "tap pair one ahead just below small integers"
+    seen, coarse = 0, 0
+    for job in _far_fulls(group):
+        new, ok, it = _restate(O, job, defect=defect)
+        ref = _restate(O, job)
+        hit = np.zeros(len(job.pts), bool)
+        for l in range(job.lv_l, job.lv_f + 1):
+            hit |= _is_just_below_small_integer(job, l)
+        assert np.array_equal(new[~hit], ref[0][~hit], equal_nan=True) and np.array_equal(it[~hit], ref[2][~hit]), job.key
+        last = _is_just_below_small_integer(job, job.lv_l)
+        broken = {b[0] for b in PC.discontinuous(job, new, ok, it, O)[0]}
+        assert _fails(PC.check_continuity, job, new, ok, it, O) == bool(broken), job.key
+        assert broken == {n for n, ks in PC.far_triples(job.frame) if hit[ks].any()}, (job.key, broken)
+        seen += sum(bool(last[ks].any()) for _, ks in PC.far_triples(job.frame))
+        coarse += sum(bool(hit[ks].any() and not last[ks].any()) for _, ks in PC.far_triples(job.frame))
+    assert seen >= 4 * len(PC.GROUP_FORM_PSZ[group]) and coarse >= len(PC.GROUP_FORM_PSZ[group])
+
+
+@pytest.mark.parametrize("frame", ("farx-320x64", "fary-64x320"))
+def test_flow_grid_on_a_far_pair_on_the_oracle(O, frame):
+    """dense_flow (the definition of FlowGrid.compute's field) with the oracle tracking the nodes: check_grid."""
+    from invcompcamtrack_amd import patchflow as pf
+    pa, pb = PC.oracle_pyramids(O, frame, PC.GRID_PSZ)
+    kept = {}
+
+    def track(a, b, pts, psz, lv_f, maxiter, eps):
+        out = NP.track_points(a, b, pts, psz, lv_f, 0, maxiter, eps)
+        kept["ok"] = out[1]
+        return out
+
+    field = pf.dense_flow(pa, pb, PC.GRID_STEP, PC.GRID_PSZ, PC.GRID_LV, _track=track)
+    xy, _ = PC.grid_nodes(frame)
+    got = PC.check_grid(frame, field, ~kept["ok"].reshape(xy.shape[:2]), PC.TRUTH_BAR[PC.GRID_PSZ])
+    print(f"{frame}: oracle grid, largest interior error {got[0]:.4f} px, median below 256 {got[1]:.4f}, from 256 on {got[2]:.4f}")

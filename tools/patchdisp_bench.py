@@ -1,6 +1,6 @@
 """The 1-D stereo search against the 2-D tracker on the same pyramids and nodes -> profiles/patchdisp_bench.json.
 
-  python tools/patchdisp_bench.py [--reps 7] [--out profiles/patchdisp_bench.json]
+  python tools/patchdisp_bench.py [--reps 7] [--out profiles/patchdisp_bench.json] [--parent parent_run.json]
 
 Per shape (1242x375 and 1920x1080, step 4, psz 15, lv_f 3, the defaults maxiter 10 and eps 0.01): the HIP-event time of
 the k_patchdisp launch (track_disparity) and of the k_patchflow launch (track_points) on the nodes of the step grid,
@@ -8,10 +8,14 @@ interleaved, `reps` runs each after a warm-up of both; and the wall time per ste
 StereoPointTracker.push_frames with disparity "2d" and "1d" (4 frames pushed and the window counted, which waits for the
 device, over 4), interleaved likewise. Minimum, median and maximum of each. The frames are seeded sums of gratings of all
 directions; the right frame is the left one shifted by 6.3 px, a later frame is moved by (1.2, 0.4) px per frame.
-The x error against the true -6.3 px is taken over the nodes with x, y < 256 only: the patch sampling inherited from the
-reference takes its first tap at ceil(x + 1e-5f), and at an integer coordinate of 256 or more that sum rounds back to x
-in float32, so the template of such a node sits one pixel to the left (up) and both kernels report the shift less one.
+The x error against the true -6.3 px is taken over all tracked nodes, and separately (signed median) over the nodes
+with x or y >= 256 and over the others: both kernels take their first tap at floor(x) + 1, the pair their weights are
+taken for at every x. (Before that rule the first tap was the reference's ceil(x + 1e-5f); at an integer coordinate of
+256 or more that sum rounds back to x in float32, the template sat one pixel to the left or up, and both kernels
+reported the shift less one pixel there.)
 The bar: the median of the 1-D launch is not above the median of the 2-D launch of the same run (exit status 1 if it is).
+--parent: the file another build's run of this tool wrote (its "shapes" are copied into the output as "parent_shapes");
+then a second bar holds: each kernel's median is not above that run's median by more than that run's own max - min.
 """
 import argparse
 import json
@@ -88,6 +92,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "patchdisp_bench.json"))
+    ap.add_argument("--parent", default=None, help="the output of another build's run, to compare the kernel medians with")
     a = ap.parse_args()
     if a.reps < 7:
         ap.error("at least 7 runs each")
@@ -96,6 +101,11 @@ def main():
     out = {"bench": "patchdisp", "step": STEP, "psz": PSZ, "lv_f": LV_F, "maxiter": 10, "eps": 0.01, "reps": a.reps,
            "frames_per_window": NFRAMES, "true_disparity_px": -DISP, "shapes": []}
     ok = True
+    parent = None
+    if a.parent:
+        with open(a.parent) as f:
+            parent = {(r["w"], r["h"]): r for r in json.load(f)["shapes"]}
+        out["parent_shapes"] = list(parent.values())
     for w, h in ((1242, 375), (1920, 1080)):
         fr = frames(w, h)
         pa, pb = ic.Pyramid(fr[0][0], LV_F, PSZ, True), ic.Pyramid(fr[0][1], LV_F, PSZ, True)
@@ -106,12 +116,15 @@ def main():
         rec = {"w": w, "h": h, "nodes": len(pts), "form_1d": pf.disparity_last_form(), "form_2d": pf.last_form()}
         for name in ("1d", "2d"):
             new, st, it = res[name]
-            low = st & (pts[:, 0] < 256) & (pts[:, 1] < 256)  # (see the module docstring)
-            err = np.abs(new[low, 0] - pts[low, 0] + DISP)
+            e = (new[:, 0] - pts[:, 0] + DISP).astype(np.float64)
+            far = st & ((pts[:, 0] >= 256) | (pts[:, 1] >= 256))  # (see the module docstring)
+            near = st & ~far
             rec[f"kernel_ms_{name}"] = stats(kms[name])
             rec[f"tracked_{name}"] = int(st.sum())
             rec[f"mean_iters_{name}"] = round(float(it[st].mean()), 3)
-            rec[f"median_abs_x_error_px_below_256_{name}"] = round(float(np.median(err)), 4)
+            rec[f"median_abs_x_error_px_{name}"] = round(float(np.median(np.abs(e[st]))), 4)
+            rec[f"median_x_error_px_from_256_{name}"] = round(float(np.median(e[far])), 4)
+            rec[f"median_x_error_px_below_256_{name}"] = round(float(np.median(e[near])), 4)
             rec[f"push_frames_wall_ms_per_stereo_frame_{name}"] = stats(wms[name])
             rec[f"window_survivors_{name}"] = int(kept[name])
         rec["kernel_median_ratio_1d_over_2d"] = round(rec["kernel_ms_1d"]["median"] / rec["kernel_ms_2d"]["median"], 4)
@@ -119,6 +132,12 @@ def main():
             rec["push_frames_wall_ms_per_stereo_frame_2d"]["median"] - rec["push_frames_wall_ms_per_stereo_frame_1d"]["median"], 4)
         rec["bar_1d_median_not_above_2d_median"] = rec["kernel_ms_1d"]["median"] <= rec["kernel_ms_2d"]["median"]
         ok &= rec["bar_1d_median_not_above_2d_median"]
+        if parent:
+            for name in ("1d", "2d"):
+                p = parent[w, h][f"kernel_ms_{name}"]
+                rec[f"bar_{name}_median_within_parent_spread"] = bool(
+                    rec[f"kernel_ms_{name}"]["median"] <= p["median"] + (p["max"] - p["min"]))
+                ok &= rec[f"bar_{name}_median_within_parent_spread"]
         out["shapes"].append(rec)
         print(json.dumps(rec), flush=True)
     with open(a.out, "w") as f:
