@@ -505,4 +505,33 @@ class PointTrackClass {
   int bsize_, maxcorners_;
 };
 
+// Variational refinement of a dense flow field at level 0 (ictr_flowrefine_* in include/ictr.h). Run enqueues, Result
+// waits. A field is an ictr_field (StereoTrackClass::Flow / Grid fill one); Field() is this object's refined field on the
+// device, for the stereo track window.
+class FlowRefineClass {
+ public:
+  FlowRefineClass(int w, int h) : h_(nullptr) { check(ictr_flowrefine_create(&h_, w, h), "FlowRefineClass"); }
+  ~FlowRefineClass() { ictr_flowrefine_destroy(h_); }
+  FlowRefineClass(const FlowRefineClass &) = delete;
+  FlowRefineClass &operator=(const FlowRefineClass &) = delete;
+  void SetParams(float alpha = 16.0f, float gamma = 13.0f, float delta = 4.5f, int n_outer = 8, int n_sor = 5,
+                 float omega = 1.6f) {
+    check(ictr_flowrefine_set_params(h_, alpha, gamma, delta, n_outer, n_sor, omega), "SetParams");
+  }
+  void Run(const Pyramid &a, const Pyramid &b, const ictr_field &src, bool x_only = false, void *hip_stream = nullptr) {
+    check(ictr_flowrefine_run(h_, a.handle(), b.handle(), &src, x_only ? 1 : 0, hip_stream), "Run");
+  }
+  // out [h][w][2], in host memory or (on_device) device memory
+  void Result(float *out, bool on_device = false) { check(ictr_flowrefine_result(h_, out, on_device ? 1 : 0), "Result"); }
+  ictr_field Field(bool x_only = false) const {
+    ictr_field f = {ICTR_FIELD_FLOW, 1, 1, x_only ? 1 : 0, ictr_flowrefine_device_ptr(h_)};
+    return f;
+  }
+  // which: 0 Bw, 1..5 a11 a12 a22 b1 b2, 6 7 the edge weights, 8 9 du dv, 10 11 u v of the last outer iteration; out [h][w]
+  void ReadStage(int which, float *out) { check(ictr_flowrefine_read_stage(h_, which, out), "ReadStage"); }
+
+ private:
+  ictr_flowrefine *h_;
+};
+
 }  // namespace CTR

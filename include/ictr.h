@@ -887,6 +887,44 @@ int ictr_camfit_set_mask_from_camransac(ictr_camfit *r, const ictr_camransac *s,
 int ictr_ba_set_mask_from_camransac(ictr_ba *r, const ictr_camransac *s, void *hip_stream);
 int ictr_debug_camransac_inputs(const ictr_camransac *r, double *X, double *xy, uint64_t *words);
 
+/* ---------------------------------------------------------------- variational refinement (ictr_flowrefine.hip)
+ * A dense flow A -> B refined per pixel at level 0 (DESIGN.md §4 "Variational refinement of a dense field"): n_outer
+ * times warp B by the field, linearise brightness and gradient constancy with robust weights, and solve for an increment
+ * with n_sor red-black SOR sweeps under a robust smoothness term. The rule is patchflow.refine_flow_host's, in f32.
+ * Planes are [h][w] f32, fields [h][w][2] f32 interleaved (u, v). */
+typedef struct ictr_flowrefine ictr_flowrefine;
+/* 4 <= w, h <= 32768 */
+int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h);
+void ictr_flowrefine_destroy(ictr_flowrefine *r);
+/* defaults 16, 13, 4.5, 8, 5, 1.6. Refused: a negative or non-finite value, n_outer or n_sor above 1024, omega outside
+ * (0, 2). n_outer = 0 returns the source's bits. */
+int ictr_flowrefine_set_params(ictr_flowrefine *r, float alpha, float gamma, float delta, int n_outer, int n_sor,
+                               float omega);
+/* src: an ICTR_FIELD_FLOW in host memory (checked for finiteness and copied before the call returns; a value that is not
+ * finite is refused) or in device memory (read when the run executes; not checked), or an ICTR_FIELD_GRID, whose dense
+ * field is formed into the refiner's own buffer. sign must be +1; the descriptor's x_only is not read. x_only != 0 (a
+ * stereo pair): only u moves, v comes back with its input bits. Both pyramids and the field are of the refiner's size
+ * (ICTR_ERR_INVALID otherwise); only the level-0 image planes are read, with any padding. Everything is enqueued on
+ * hip_stream (NULL: the null stream); the call waits for nothing but the copy of a host field. */
+int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, const ictr_field *src,
+                        int x_only, void *hip_stream);
+/* waits for the last run and copies its field [h][w][2] to out (a device pointer when on_device != 0) */
+int ictr_flowrefine_result(ictr_flowrefine *r, float *out, int on_device);
+/* the result buffer on the device (a device ICTR_FIELD_FLOW for the stereo track window), valid behind the run's stream */
+const float *ictr_flowrefine_device_ptr(const ictr_flowrefine *r);
+/* HIP events around the launches of the next runs; ms[4] of the last run (waits for it): k_fr_warp, k_fr_coef, k_fr_sor
+ * summed over the outer iterations, and k_fr_init + k_fr_final. All 0 when timing was off. */
+int ictr_flowrefine_set_timing(ictr_flowrefine *r, int on);
+int ictr_flowrefine_get_kernel_times(ictr_flowrefine *r, float *ms);
+/* the planes of the last outer iteration (waits for the run): which = 0 Bw, 1..5 a11 a12 a22 b1 b2, 6 7 the right and
+ * down edge weights, 8 9 du dv after the last sweep, 10 11 the u, v that the iteration started from */
+#define ICTR_FLOWREFINE_STAGES 12
+int ictr_flowrefine_read_stage(ictr_flowrefine *r, int which, float *out);
+/* inspection: a plane written from host memory, and one half-sweep k_fr_sor<colour> on the planes as they stand (null
+ * stream, waited for) */
+int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, const float *in);
+int ictr_debug_flowrefine_half_sweep(ictr_flowrefine *r, int colour, int x_only);
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,17 @@ SIGNATURES = {
     "ictr_pointtrack_push_frame": (C.c_int, [VP, FP]),
     "ictr_pointtrack_frcounter": (C.c_int, [VP, C.POINTER(I64)]),
     "ictr_pointtrack_read_block": (C.c_int, [VP, I64, FP, U8P, DP, IP]),
+    "ictr_flowrefine_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int]),
+    "ictr_flowrefine_destroy": (None, [VP]),
+    "ictr_flowrefine_set_params": (C.c_int, [VP, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float]),
+    "ictr_flowrefine_run": (C.c_int, [VP, VP, VP, C.POINTER(Field), C.c_int, VP]),
+    "ictr_flowrefine_result": (C.c_int, [VP, VP, C.c_int]),
+    "ictr_flowrefine_device_ptr": (VP, [VP]),
+    "ictr_flowrefine_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_flowrefine_get_kernel_times": (C.c_int, [VP, FP]),
+    "ictr_flowrefine_read_stage": (C.c_int, [VP, C.c_int, FP]),
+    "ictr_debug_flowrefine_write_stage": (C.c_int, [VP, C.c_int, FP]),
+    "ictr_debug_flowrefine_half_sweep": (C.c_int, [VP, C.c_int, C.c_int]),
 }
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {

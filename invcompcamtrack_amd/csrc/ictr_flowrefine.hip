@@ -1,0 +1,470 @@
+// ictr_flowrefine.hip -- variational refinement of a dense flow field at level 0 (DESIGN.md §4 "Variational refinement of
+// a dense field"). The rule is build-defined; its statement of record is patchflow.refine_flow_host (NumPy, f64). This
+// file is the same rule in f32 with one fixed operation order, restated in NumPy f32 by tests/flowrefine_f32.py.
+//
+// One outer iteration is   k_fr_warp -> k_fr_coef -> n_sor x (k_fr_sor<0>, k_fr_sor<1>)   on planes of the frame's size:
+//   k_fr_warp   (u, v) += (du, dv) of the previous outer iteration (step 6 folded in), then Bw = bilinear(B, x + u, y + v).
+//               The position is clamped with fmaxf / fminf BEFORE any index is formed: no index depends on a non-finite
+//               value, every tap lies in the frame.
+//   k_fr_coef   one 16 x 16 tile per workgroup with a 2-pixel halo of Bw, A, u, v in LDS (the stencil reaches +-2: a
+//               derivative of a derivative, and the edge weight of s). Writes a11, a12, a22, b1, b2, the right and down
+//               edge weights, and du = dv = 0.
+//   k_fr_sor<c> one half-sweep: a lane per pixel of colour (x + y) & 1 == c. All four neighbours have the other colour,
+//               which this launch does not write: no order inside a half-sweep, the result is deterministic. The five
+//               coefficient planes are stored compacted by colour (fr_ci).
+// k_fr_final adds the last (du, dv) into the interleaved result. Memory bound throughout: plain vector loads and stores,
+// no atomics. Everything is enqueued on the caller's stream; run waits for nothing but the copy of a field that lives in
+// host memory.
+#include <math.h>
+#include <string.h>
+
+#include <memory>
+#include <vector>
+
+#include "ictr_dev.h"
+#include "ictr_launch.h"
+#include "ictr_flowgrid_dev.h"
+
+namespace ictr {
+
+constexpr int kFrTile = 16;                   // kFrTile^2 = kBlock: one pixel per lane
+constexpr int kFrHalo = 2;
+constexpr int kFrSide = kFrTile + 2 * kFrHalo;  // 20
+constexpr float kFrEps2 = 1e-3f * 1e-3f;
+constexpr float kFrZeta2 = 0.1f * 0.1f;
+static_assert(kFrTile * kFrTile == kBlock, "k_fr_coef maps one lane to one pixel of its tile");
+
+struct FrArgs {
+  const float *A, *B;  // level-0 planes at pixel (0, 0), strides sa, sb
+  int sa, sb, w, h;
+  float *u, *v, *du, *dv, *bw, *a11, *a12, *a22, *b1, *b2, *wr, *wd;  // planes [h][w]
+  float alpha, gamma, delta, omega;
+  int x_only;
+};
+
+// interleaved (u, v) -> the two working planes
+__global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v,
+                                                    int n) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float2 f = f0[i];
+  u[i] = f.x;
+  v[i] = f.y;
+}
+// the dense field of a flow grid, interleaved
+__global__ __launch_bounds__(kBlock) void k_fr_from_grid(FgDev g, float2 *__restrict__ out) {
+  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (X >= g.w || Y >= g.h) return;
+  float u, v;
+  fg_value(g, X, Y, &u, &v);
+  out[(size_t)Y * g.w + X] = make_float2(u, v);
+}
+
+// Where a coefficient (a11, a12, a22, b1, b2) of pixel (X, Y) lives in its plane: the plane is compacted by colour, first
+// all pixels of colour 0 row by row, then those of colour 1, rows of ceil(w / 2). A half-sweep, which reads the
+// coefficients of one colour only, then reads whole lines (measured against the pixel order: DESIGN.md).
+__host__ __device__ __forceinline__ int fr_ci(int X, int Y, int w, int h) {
+  const int wc = (w + 1) >> 1;
+  return ((X + Y) & 1) * wc * h + Y * wc + (X >> 1);
+}
+
+__device__ __forceinline__ bool fr_inside(float px, float py, int w, int h) {
+  return (px >= 0.0f) & (px <= (float)(w - 1)) & (py >= 0.0f) & (py <= (float)(h - 1));  // NaN: outside
+}
+
+__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgs a, int fold) {
+  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (X >= a.w || Y >= a.h) return;
+  const int i = Y * a.w + X;
+  float u = a.u[i], v = a.v[i];
+  if (fold) {
+    u += a.du[i];
+    a.u[i] = u;
+    if (!a.x_only) {
+      v += a.dv[i];
+      a.v[i] = v;
+    }
+  }
+  const float px = fminf(fmaxf((float)X + u, 0.0f), (float)(a.w - 1));  // fmaxf(NaN, 0) = 0
+  const float py = fminf(fmaxf((float)Y + v, 0.0f), (float)(a.h - 1));
+  const int x0 = min((int)floorf(px), a.w - 2), y0 = min((int)floorf(py), a.h - 2);
+  const float fx = px - (float)x0, fy = py - (float)y0;
+  const float *b = a.B + (size_t)y0 * a.sb + x0;
+  const float b00 = b[0], b01 = b[1], b10 = b[a.sb], b11 = b[a.sb + 1];
+  const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
+  a.bw[i] = ((w00 * b00 + w01 * b01) + w10 * b10) + w11 * b11;
+}
+
+// a tile with its halo; (cx, cy) are tile coordinates, the frame coordinate is (gx0 + cx, gy0 + cy)
+struct FrTile {
+  const float (*p)[kFrSide];
+  int gx0, gy0, w, h;
+  __device__ __forceinline__ float at(int cx, int cy) const { return p[cy][cx]; }
+  // dx(a) = (a[x+1] - a[x-1]) / 2, and 0 in the first and last column; dy likewise
+  __device__ __forceinline__ float dx(int cx, int cy) const {
+    const int X = gx0 + cx;
+    return (X <= 0 || X >= w - 1) ? 0.0f : 0.5f * (p[cy][cx + 1] - p[cy][cx - 1]);
+  }
+  __device__ __forceinline__ float dy(int cx, int cy) const {
+    const int Y = gy0 + cy;
+    return (Y <= 0 || Y >= h - 1) ? 0.0f : 0.5f * (p[cy + 1][cx] - p[cy - 1][cx]);
+  }
+  __device__ __forceinline__ float dxx(int cx, int cy) const {
+    const int X = gx0 + cx;
+    return (X <= 0 || X >= w - 1) ? 0.0f : 0.5f * (dx(cx + 1, cy) - dx(cx - 1, cy));
+  }
+  __device__ __forceinline__ float dxy(int cx, int cy) const {  // dy(dx(a))
+    const int Y = gy0 + cy;
+    return (Y <= 0 || Y >= h - 1) ? 0.0f : 0.5f * (dx(cx, cy + 1) - dx(cx, cy - 1));
+  }
+  __device__ __forceinline__ float dyy(int cx, int cy) const {
+    const int Y = gy0 + cy;
+    return (Y <= 0 || Y >= h - 1) ? 0.0f : 0.5f * (dy(cx, cy + 1) - dy(cx, cy - 1));
+  }
+};
+// s = alpha / 2 / sqrt(|grad u|^2 + |grad v|^2 + eps^2)
+__device__ __forceinline__ float fr_smooth(const FrTile &tu, const FrTile &tv, int cx, int cy, float half_alpha) {
+  const float ux = tu.dx(cx, cy), uy = tu.dy(cx, cy), vx = tv.dx(cx, cy), vy = tv.dy(cx, cy);
+  float t = ux * ux + uy * uy;
+  t = t + vx * vx;
+  t = t + vy * vy;
+  t = t + kFrEps2;
+  return half_alpha / sqrtf(t);
+}
+
+__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgs a) {
+  __shared__ float sB[kFrSide][kFrSide], sA[kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
+  const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
+  // the halo is read at the nearest pixel of the frame; what lies outside is never used (the border rules above)
+  for (int q = threadIdx.x; q < kFrSide * kFrSide; q += kBlock) {
+    const int cy = q / kFrSide, cx = q - cy * kFrSide;
+    const int X = min(max(gx0 + cx, 0), a.w - 1), Y = min(max(gy0 + cy, 0), a.h - 1);
+    const int i = Y * a.w + X;
+    sB[cy][cx] = a.bw[i];
+    sU[cy][cx] = a.u[i];
+    sV[cy][cx] = a.v[i];
+    sA[cy][cx] = a.A[(size_t)Y * a.sa + X];
+  }
+  __syncthreads();
+  const int cx = (threadIdx.x & (kFrTile - 1)) + kFrHalo, cy = threadIdx.x / kFrTile + kFrHalo;
+  const int X = gx0 + cx, Y = gy0 + cy;
+  if (X >= a.w || Y >= a.h) return;
+  const int i = Y * a.w + X;
+  const FrTile tb{sB, gx0, gy0, a.w, a.h}, ta{sA, gx0, gy0, a.w, a.h}, tu{sU, gx0, gy0, a.w, a.h},
+      tv{sV, gx0, gy0, a.w, a.h};
+  // step 2
+  const float Ix = tb.dx(cx, cy), Iy = tb.dy(cx, cy), Iz = tb.at(cx, cy) - ta.at(cx, cy);
+  const float Ixx = tb.dxx(cx, cy), Ixy = tb.dxy(cx, cy), Iyy = tb.dyy(cx, cy);
+  const float Ixz = Ix - ta.dx(cx, cy), Iyz = Iy - ta.dy(cx, cy);
+  // step 3
+  const bool in = fr_inside((float)X + tu.at(cx, cy), (float)Y + tv.at(cx, cy), a.w, a.h);
+  const float n0 = 1.0f / ((Ix * Ix + Iy * Iy) + kFrZeta2);
+  const float n1 = 1.0f / ((Ixx * Ixx + Ixy * Ixy) + kFrZeta2);
+  const float n2 = 1.0f / ((Ixy * Ixy + Iyy * Iyy) + kFrZeta2);
+  const float w0 = in ? ((a.delta * n0) * 0.5f) / sqrtf((n0 * Iz) * Iz + kFrEps2) : 0.0f;
+  const float wg = in ? (a.gamma * 0.5f) / sqrtf(((n1 * Ixz) * Ixz + (n2 * Iyz) * Iyz) + kFrEps2) : 0.0f;
+  const int c = fr_ci(X, Y, a.w, a.h);
+  a.a11[c] = w0 * (Ix * Ix) + wg * (n1 * (Ixx * Ixx) + n2 * (Ixy * Ixy));
+  a.a12[c] = w0 * (Ix * Iy) + wg * (n1 * (Ixx * Ixy) + n2 * (Ixy * Iyy));
+  a.a22[c] = w0 * (Iy * Iy) + wg * (n1 * (Ixy * Ixy) + n2 * (Iyy * Iyy));
+  a.b1[c] = -(w0 * (Ix * Iz) + wg * (n1 * (Ixx * Ixz) + n2 * (Ixy * Iyz)));
+  a.b2[c] = -(w0 * (Iy * Iz) + wg * (n1 * (Ixy * Ixz) + n2 * (Iyy * Iyz)));
+  // step 4: the edge to the right and the edge down carry the mean of their two pixels' s; no edge leaves the frame
+  const float ha = a.alpha * 0.5f;
+  const float s0 = fr_smooth(tu, tv, cx, cy, ha);
+  a.wr[i] = X < a.w - 1 ? 0.5f * (s0 + fr_smooth(tu, tv, cx + 1, cy, ha)) : 0.0f;
+  a.wd[i] = Y < a.h - 1 ? 0.5f * (s0 + fr_smooth(tu, tv, cx, cy + 1, ha)) : 0.0f;
+  // step 5 starts from du = dv = 0
+  a.du[i] = 0.0f;
+  a.dv[i] = 0.0f;
+}
+
+// One half-sweep. A lane owns one pixel of the active colour: x = 2 p + ((y + COLOUR) & 1). The reads of du / dv / u / v
+// of a wave cover whole lines (the pixel and its two row neighbours alternate), and so do those of the coefficient
+// planes, which are compacted by colour; only wd is read at stride 2.
+template <int COLOUR>
+__global__ __launch_bounds__(kBlock) void k_fr_sor(FrArgs a) {
+  const int Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (Y >= a.h) return;
+  const int X = 2 * (blockIdx.x * 64 + (threadIdx.x & 63)) + ((Y + COLOUR) & 1);
+  if (X >= a.w) return;
+  const int i = Y * a.w + X;
+  const bool hl = X > 0, hr = X < a.w - 1, hu = Y > 0, hd = Y < a.h - 1;
+  const int il = hl ? i - 1 : i, ir = hr ? i + 1 : i, iu = hu ? i - a.w : i, id = hd ? i + a.w : i;
+  const float wl = hl ? a.wr[il] : 0.0f, wr = hr ? a.wr[i] : 0.0f;
+  const float wu = hu ? a.wd[iu] : 0.0f, wd = hd ? a.wd[i] : 0.0f;
+  const float sw = ((wl + wr) + wu) + wd;
+  const int c = fr_ci(X, Y, a.w, a.h);
+  const float u = a.u[i], du = a.du[i], dv = a.dv[i], a12 = a.a12[c];
+  const float tl = hl ? wl * (a.u[il] + a.du[il]) : 0.0f, tr = hr ? wr * (a.u[ir] + a.du[ir]) : 0.0f;
+  const float tu = hu ? wu * (a.u[iu] + a.du[iu]) : 0.0f, td = hd ? wd * (a.u[id] + a.du[id]) : 0.0f;
+  const float su = ((tl + tr) + tu) + td;
+  const float om = a.omega;
+  const float dun = (1.0f - om) * du + om * ((((a.b1[c] - a12 * dv) + su) - sw * u) / (a.a11[c] + sw));
+  a.du[i] = dun;
+  if (a.x_only) return;
+  const float v = a.v[i];
+  const float sl = hl ? wl * (a.v[il] + a.dv[il]) : 0.0f, sr = hr ? wr * (a.v[ir] + a.dv[ir]) : 0.0f;
+  const float st = hu ? wu * (a.v[iu] + a.dv[iu]) : 0.0f, sd = hd ? wd * (a.v[id] + a.dv[id]) : 0.0f;
+  const float sv = ((sl + sr) + st) + sd;
+  a.dv[i] = (1.0f - om) * dv + om * ((((a.b2[c] - a12 * dun) + sv) - sw * v) / (a.a22[c] + sw));
+}
+
+// step 6 of the last outer iteration, into the interleaved result; u and v keep the last outer iteration's field
+__global__ __launch_bounds__(kBlock) void k_fr_final(FrArgs a, float2 *__restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.w * a.h) return;
+  const float v = a.v[i];
+  out[i] = make_float2(a.u[i] + a.du[i], a.x_only ? v : v + a.dv[i]);
+}
+
+}  // namespace ictr
+
+using namespace ictr;
+
+// ---------------------------------------------------------------- C-ABI
+constexpr int kFrPlanes = 12;  // u v du dv bw a11 a12 a22 b1 b2 wr wd (the enum below)
+struct ictr_flowrefine {
+  int w = 0, h = 0;
+  float alpha = 16.0f, gamma = 13.0f, delta = 4.5f, omega = 1.6f;
+  int n_outer = 8, n_sor = 5;
+  int timing = 0, ran = 0;
+  float *plane[kFrPlanes] = {};
+  float *f0 = nullptr, *out = nullptr;  // interleaved [h][w][2]: the source formed or copied here, the result
+  DevBuf<float> arena;                  // everything above
+  std::vector<Event> ev;                // timing: four per outer iteration and four around init and final
+  int nev = 0;                          // events recorded by the last run
+  Event done;                           // behind the last run
+};
+enum { FR_U, FR_V, FR_DU, FR_DV, FR_BW, FR_A11, FR_A12, FR_A22, FR_B1, FR_B2, FR_WR, FR_WD };
+// ictr_flowrefine_read_stage's `which` -> plane
+static const int kFrStage[ICTR_FLOWREFINE_STAGES] = {FR_BW, FR_A11, FR_A12, FR_A22, FR_B1, FR_B2, FR_WR, FR_WD, FR_DU, FR_DV,
+                                                     FR_U,  FR_V};
+
+static bool fr_compacted(int plane) { return plane >= FR_A11 && plane <= FR_B2; }  // stored in fr_ci's order
+static size_t fr_plane_floats(const ictr_flowrefine *r) { return (size_t)2 * ((r->w + 1) / 2) * r->h; }
+
+static FrArgs fr_args(const ictr_flowrefine *r, int x_only) {
+  FrArgs a;
+  memset(&a, 0, sizeof(a));
+  a.w = r->w;
+  a.h = r->h;
+  a.u = r->plane[FR_U];
+  a.v = r->plane[FR_V];
+  a.du = r->plane[FR_DU];
+  a.dv = r->plane[FR_DV];
+  a.bw = r->plane[FR_BW];
+  a.a11 = r->plane[FR_A11];
+  a.a12 = r->plane[FR_A12];
+  a.a22 = r->plane[FR_A22];
+  a.b1 = r->plane[FR_B1];
+  a.b2 = r->plane[FR_B2];
+  a.wr = r->plane[FR_WR];
+  a.wd = r->plane[FR_WD];
+  a.alpha = r->alpha;
+  a.gamma = r->gamma;
+  a.delta = r->delta;
+  a.omega = r->omega;
+  a.x_only = x_only ? 1 : 0;
+  return a;
+}
+static dim3 fr_grid_rows(const ictr_flowrefine *r, int cols) { return dim3((cols + 63) / 64, (r->h + kWaves - 1) / kWaves); }
+static void fr_half_sweep(const ictr_flowrefine *r, const FrArgs &a, int colour, hipStream_t s) {
+  const dim3 g = fr_grid_rows(r, (r->w + 1) / 2);
+  if (colour == 0)
+    hipLaunchKernelGGL(k_fr_sor<0>, g, dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_fr_sor<1>, g, dim3(kBlock), 0, s, a);
+}
+
+extern "C" void ictr_flowrefine_destroy(ictr_flowrefine *r) {
+  if (r && r->ran) (void)hipEventSynchronize(r->done.get());
+  delete r;
+}
+extern "C" int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h) {
+  if (!out || w < 4 || h < 4 || w > 32768 || h > 32768)  // (pixel indices are int, rows / 4 a grid dimension)
+    return fail(ICTR_ERR_INVALID, "flowrefine: bad arguments (4 <= w, h <= 32768)");
+  if (int rc = need_device()) return rc;
+  auto r = std::make_unique<ictr_flowrefine>();
+  r->w = w;
+  r->h = h;
+  const size_t n = fr_plane_floats(r.get());  // a plane: two colours of ceil(w / 2) x h (fr_ci)
+  if (int rc = r->arena.alloc(sizeof(float) * n * (kFrPlanes + 4), true)) return rc;
+  for (int k = 0; k < kFrPlanes; ++k) r->plane[k] = r->arena.get() + n * k;
+  r->f0 = r->arena.get() + n * kFrPlanes;
+  r->out = r->f0 + 2 * n;
+  if (int rc = r->done.create(hipEventDisableTiming)) return rc;
+  *out = r.release();
+  return ICTR_OK;
+}
+extern "C" int ictr_flowrefine_set_params(ictr_flowrefine *r, float alpha, float gamma, float delta, int n_outer, int n_sor,
+                                          float omega) {
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  if (!isfinite(alpha) || !isfinite(gamma) || !isfinite(delta) || !isfinite(omega) || alpha < 0 || gamma < 0 || delta < 0 ||
+      n_outer < 0 || n_sor < 0 || n_outer > 1024 || n_sor > 1024 || !(omega > 0.0f) || !(omega < 2.0f))
+    return fail(ICTR_ERR_INVALID,
+                "flowrefine_set_params: finite alpha, gamma, delta >= 0, 0 <= n_outer, n_sor <= 1024, 0 < omega < 2");
+  r->alpha = alpha;
+  r->gamma = gamma;
+  r->delta = delta;
+  r->n_outer = n_outer;
+  r->n_sor = n_sor;
+  r->omega = omega;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowrefine_set_timing(ictr_flowrefine *r, int on) {
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  r->timing = on ? 1 : 0;
+  return ICTR_OK;
+}
+
+// level 0 of a pyramid of the refiner's size: the plane at pixel (0, 0) and its stride
+static int fr_level0(const ictr_flowrefine *r, const ictr_pyramid *p, const float **img, int *stride) {
+  ictr_pyramid_view v;
+  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is NULL");
+  if (v.w[0] != r->w || v.h[0] != r->h)
+    return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", v.w[0], v.h[0], r->w, r->h);
+  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
+  *stride = v.sw[0];
+  return ICTR_OK;
+}
+
+extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
+                                   const ictr_field *src, int x_only, void *hip_stream) {
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  if (!src || !src->data) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field (or its data) is NULL");
+  if (src->sign != 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field's sign is %d (+1)", src->sign);
+  FrArgs a = fr_args(r, x_only);
+  if (int rc = fr_level0(r, pyr_a, &a.A, &a.sa)) return rc;
+  if (int rc = fr_level0(r, pyr_b, &a.B, &a.sb)) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const size_t n = (size_t)r->w * r->h;
+  const float *f0 = r->f0;
+  if (src->kind == ICTR_FIELD_GRID) {
+    FgDev g;
+    if (int rc = ictr_flowgrid_view_(static_cast<const ictr_flowgrid *>(src->data), &g)) return rc;
+    if (g.w != r->w || g.h != r->h)
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: the flow grid is %d x %d, the refiner %d x %d", g.w, g.h, r->w, r->h);
+    hipLaunchKernelGGL(k_fr_from_grid, fr_grid_rows(r, r->w), dim3(kBlock), 0, s, g, reinterpret_cast<float2 *>(r->f0));
+  } else if (src->kind == ICTR_FIELD_FLOW) {
+    if (src->on_device) {
+      f0 = static_cast<const float *>(src->data);
+    } else {
+      const float *f = static_cast<const float *>(src->data);
+      for (size_t i = 0; i < 2 * n; ++i)
+        if (!isfinite(f[i])) return fail(ICTR_ERR_INVALID, "flowrefine_run: the host field is not finite at float %zu", i);
+      if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));  // the last run has read f0
+      HIPCHK(hipMemcpyAsync(r->f0, f, sizeof(float) * 2 * n, hipMemcpyHostToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));  // the caller's array is free when this returns; the kernels follow on s
+    }
+  } else {
+    return fail(ICTR_ERR_INVALID, "flowrefine_run: field kind %d (ICTR_FIELD_FLOW or _GRID)", src->kind);
+  }
+  const int want = r->timing ? 4 * (r->n_outer + 1) : 0;
+  while ((int)r->ev.size() < want) {
+    r->ev.emplace_back();
+    if (int rc = r->ev.back().create()) return rc;
+  }
+  r->nev = 0;
+  auto mark = [&]() {
+    if (r->timing) (void)hipEventRecord(r->ev[r->nev++].get(), s);
+  };
+  if (r->n_outer == 0) {  // the input's bits
+    HIPCHK(hipMemcpyAsync(r->out, f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
+  } else {
+    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
+    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
+    mark();
+    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(f0), a.u, a.v, (int)n);
+    mark();
+    for (int o = 0; o < r->n_outer; ++o) {
+      mark();
+      hipLaunchKernelGGL(k_fr_warp, fr_grid_rows(r, r->w), blk, 0, s, a, o > 0 ? 1 : 0);
+      mark();
+      hipLaunchKernelGGL(k_fr_coef, tiles, blk, 0, s, a);
+      mark();
+      for (int k = 0; k < r->n_sor; ++k) {
+        fr_half_sweep(r, a, 0, s);
+        fr_half_sweep(r, a, 1, s);
+      }
+      mark();
+    }
+    mark();
+    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, a, reinterpret_cast<float2 *>(r->out));
+    mark();
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(r->done.get(), s));
+  r->ran = 1;
+  return ICTR_OK;
+}
+
+static int fr_wait(ictr_flowrefine *r, const char *what) {
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  if (!r->ran) return fail(ICTR_ERR_STATE, "%s: no run yet", what);
+  HIPCHK(hipEventSynchronize(r->done.get()));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowrefine_result(ictr_flowrefine *r, float *out, int on_device) {
+  if (int rc = fr_wait(r, "flowrefine_result")) return rc;
+  if (!out) return fail(ICTR_ERR_INVALID, "flowrefine_result: out is NULL");
+  HIPCHK(hipMemcpy(out, r->out, sizeof(float) * 2 * (size_t)r->w * r->h,
+                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" const float *ictr_flowrefine_device_ptr(const ictr_flowrefine *r) { return r ? r->out : nullptr; }
+extern "C" int ictr_flowrefine_get_kernel_times(ictr_flowrefine *r, float *ms) {
+  if (int rc = fr_wait(r, "flowrefine_get_kernel_times")) return rc;
+  if (!ms) return fail(ICTR_ERR_INVALID, "flowrefine_get_kernel_times: ms is NULL");
+  ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
+  if (r->nev < 4) return ICTR_OK;  // timing was off, or n_outer = 0
+  auto span = [&](int k, float *acc) {
+    float v = 0.0f;
+    if (hipEventElapsedTime(&v, r->ev[k].get(), r->ev[k + 1].get()) == hipSuccess) *acc += v;
+  };
+  span(0, &ms[3]);
+  for (int o = 0; 2 + 4 * o + 3 < r->nev - 2; ++o) {
+    span(2 + 4 * o, &ms[0]);
+    span(3 + 4 * o, &ms[1]);
+    span(4 + 4 * o, &ms[2]);
+  }
+  span(r->nev - 2, &ms[3]);
+  return ICTR_OK;
+}
+extern "C" int ictr_flowrefine_read_stage(ictr_flowrefine *r, int which, float *out) {
+  if (!r || !out || which < 0 || which >= ICTR_FLOWREFINE_STAGES)
+    return fail(ICTR_ERR_INVALID, "flowrefine_read_stage: bad arguments (which is 0..%d)", ICTR_FLOWREFINE_STAGES - 1);
+  if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));
+  const int k = kFrStage[which];
+  if (!fr_compacted(k)) {
+    HIPCHK(hipMemcpy(out, r->plane[k], sizeof(float) * (size_t)r->w * r->h, hipMemcpyDeviceToHost));
+    return ICTR_OK;
+  }
+  std::vector<float> tmp(fr_plane_floats(r));
+  HIPCHK(hipMemcpy(tmp.data(), r->plane[k], sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+  for (int Y = 0; Y < r->h; ++Y)
+    for (int X = 0; X < r->w; ++X) out[(size_t)Y * r->w + X] = tmp[fr_ci(X, Y, r->w, r->h)];
+  return ICTR_OK;
+}
+extern "C" int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, const float *in) {
+  if (!r || !in || which < 0 || which >= ICTR_FLOWREFINE_STAGES)
+    return fail(ICTR_ERR_INVALID, "flowrefine_write_stage: bad arguments (which is 0..%d)", ICTR_FLOWREFINE_STAGES - 1);
+  if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));
+  const int k = kFrStage[which];
+  if (!fr_compacted(k)) {
+    HIPCHK(hipMemcpy(r->plane[k], in, sizeof(float) * (size_t)r->w * r->h, hipMemcpyHostToDevice));
+    return ICTR_OK;
+  }
+  std::vector<float> tmp(fr_plane_floats(r), 0.0f);
+  for (int Y = 0; Y < r->h; ++Y)
+    for (int X = 0; X < r->w; ++X) tmp[fr_ci(X, Y, r->w, r->h)] = in[(size_t)Y * r->w + X];
+  HIPCHK(hipMemcpy(r->plane[k], tmp.data(), sizeof(float) * tmp.size(), hipMemcpyHostToDevice));
+  return ICTR_OK;
+}
+extern "C" int ictr_debug_flowrefine_half_sweep(ictr_flowrefine *r, int colour, int x_only) {
+  if (!r || (colour != 0 && colour != 1)) return fail(ICTR_ERR_INVALID, "flowrefine_half_sweep: colour is 0 or 1");
+  fr_half_sweep(r, fr_args(r, x_only), colour, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return ICTR_OK;
+}

@@ -25,7 +25,8 @@ from .tracker import Pyramid
 
 __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms",
            "last_form", "track_disparity", "dense_disparity", "disparity_last_kernel_ms", "disparity_last_form",
-           "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip"]
+           "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip", "refine_flow_host", "refine_flow",
+           "FlowRefiner", "REFINE_DEFAULTS", "FR_STAGES"]
 
 
 def last_kernel_ms():
@@ -150,6 +151,210 @@ def dense_flow(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01, _t
     top = d[y0][:, x0] * (1 - ax) + d[y0][:, x1] * ax
     bot = d[y1][:, x0] * (1 - ax) + d[y1][:, x1] * ax
     return (top * (1 - ay) + bot * ay).astype(np.float32)
+
+
+# ---------------------------------------------------------------- variational refinement of a dense field
+REFINE_DEFAULTS = dict(alpha=16.0, gamma=13.0, delta=4.5, n_outer=8, n_sor=5, omega=1.6)
+_FR_EPS, _FR_ZETA = 1e-3, 0.1
+FR_STAGES = ("bw", "a11", "a12", "a22", "b1", "b2", "wr", "wd", "du", "dv", "u", "v")  # ictr_flowrefine_read_stage
+
+
+def _fr_dx(a):
+    """(a[x+1] - a[x-1]) / 2, and 0 in the first and last column."""
+    out = np.zeros_like(a)
+    out[:, 1:-1] = 0.5 * (a[:, 2:] - a[:, :-2])
+    return out
+
+
+def _fr_dy(a):
+    out = np.zeros_like(a)
+    out[1:-1, :] = 0.5 * (a[2:, :] - a[:-2, :])
+    return out
+
+
+def _fr_warp(B, px, py):
+    """Step 1 at given positions: (bilinear(B) at the position clamped to the frame, the inside mask as 0 / 1)."""
+    h, w = B.shape
+    inside = ((px >= 0) & (px <= w - 1) & (py >= 0) & (py <= h - 1)).astype(B.dtype)
+    pxc = np.fmin(np.fmax(px, 0), w - 1)  # fmax / fmin: a NaN position goes to 0, no index depends on it
+    pyc = np.fmin(np.fmax(py, 0), h - 1)
+    x0 = np.minimum(np.floor(pxc).astype(np.int64), w - 2)
+    y0 = np.minimum(np.floor(pyc).astype(np.int64), h - 2)
+    fx, fy = pxc - x0, pyc - y0
+    bw = (((1 - fx) * (1 - fy)) * B[y0, x0] + (fx * (1 - fy)) * B[y0, x0 + 1] + ((1 - fx) * fy) * B[y0 + 1, x0]
+          + (fx * fy) * B[y0 + 1, x0 + 1])
+    return bw, inside
+
+
+def _fr_coef(A, bw, inside, u, v, alpha, gamma, delta):
+    """Steps 2-4: a11, a12, a22, b1, b2 and the weights of the edges to the right and down (0 where the edge would leave
+    the frame)."""
+    e2, z2 = _FR_EPS ** 2, _FR_ZETA ** 2
+    Ix, Iy, Iz = _fr_dx(bw), _fr_dy(bw), bw - A
+    Ixx, Ixy, Iyy = _fr_dx(Ix), _fr_dy(Ix), _fr_dy(Iy)
+    Ixz, Iyz = Ix - _fr_dx(A), Iy - _fr_dy(A)
+    n0 = 1 / (Ix * Ix + Iy * Iy + z2)
+    w0 = delta * inside * n0 * 0.5 / np.sqrt(n0 * Iz * Iz + e2)
+    n1 = 1 / (Ixx * Ixx + Ixy * Ixy + z2)
+    n2 = 1 / (Ixy * Ixy + Iyy * Iyy + z2)
+    wg = gamma * inside * 0.5 / np.sqrt(n1 * Ixz * Ixz + n2 * Iyz * Iyz + e2)
+    a11 = w0 * Ix * Ix + wg * (n1 * Ixx * Ixx + n2 * Ixy * Ixy)
+    a12 = w0 * Ix * Iy + wg * (n1 * Ixx * Ixy + n2 * Ixy * Iyy)
+    a22 = w0 * Iy * Iy + wg * (n1 * Ixy * Ixy + n2 * Iyy * Iyy)
+    b1 = -(w0 * Ix * Iz + wg * (n1 * Ixx * Ixz + n2 * Ixy * Iyz))
+    b2 = -(w0 * Iy * Iz + wg * (n1 * Ixy * Ixz + n2 * Iyy * Iyz))
+    s = alpha * 0.5 / np.sqrt(_fr_dx(u) ** 2 + _fr_dy(u) ** 2 + _fr_dx(v) ** 2 + _fr_dy(v) ** 2 + e2)
+    wr, wd = np.zeros_like(s), np.zeros_like(s)
+    wr[:, :-1] = 0.5 * (s[:, :-1] + s[:, 1:])
+    wd[:-1, :] = 0.5 * (s[:-1, :] + s[1:, :])
+    return a11, a12, a22, b1, b2, wr, wd
+
+
+def _fr_shift(a):
+    """The four neighbours' values (left, right, up, down), 0 beyond the frame (where the edge weight is 0 too)."""
+    p = np.pad(a, 1)
+    return p[1:-1, :-2], p[1:-1, 2:], p[:-2, 1:-1], p[2:, 1:-1]
+
+
+def _fr_half_sweep(colour, omega, x_only, u, v, du, dv, a11, a12, a22, b1, b2, wr, wd):
+    """Step 5, one colour, in place on du / dv."""
+    h, w = u.shape
+    yy, xx = np.mgrid[0:h, 0:w]
+    m = ((xx + yy) & 1) == colour
+    wl, wu = _fr_shift(wr)[0], _fr_shift(wd)[2]
+    sw = wl + wr + wu + wd
+    ul, ur, uu, ud = _fr_shift(u + du)
+    su = wl * ul + wr * ur + wu * uu + wd * ud
+    dun = (1 - omega) * du + omega * (b1 - a12 * dv + su - sw * u) / (a11 + sw)
+    du[m] = dun[m]
+    if x_only:
+        return
+    vl, vr, vu, vd = _fr_shift(v + dv)
+    sv = wl * vl + wr * vr + wu * vu + wd * vd
+    dvn = (1 - omega) * dv + omega * (b2 - a12 * du + sv - sw * v) / (a22 + sw)
+    dv[m] = dvn[m]
+
+
+def refine_flow_host(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_outer=8, n_sor=5, omega=1.6, x_only=False,
+                     _trace=None):
+    """Variational refinement of the dense flow A -> B at level 0: the definition (build-defined; NumPy, f64 arithmetic
+    on the f32 inputs; DESIGN.md §4 "Variational refinement of a dense field" states the rule). img_a, img_b: (H, W) grey
+    frames; flow: (H, W, 2). Returns (H, W, 2) float32. x_only (a stereo pair): only u moves, v keeps its input bits.
+    n_outer = 0 returns the input's bits. _trace: a list that receives one dict of the stage planes per outer iteration
+    (FR_STAGES' names, and "px", "py", the warp positions)."""
+    f0 = np.ascontiguousarray(flow, np.float32)
+    A = np.asarray(np.asarray(img_a, np.float32), np.float64)
+    B = np.asarray(np.asarray(img_b, np.float32), np.float64)
+    h, w = A.shape
+    if B.shape != A.shape or f0.shape != (h, w, 2) or w < 4 or h < 4:
+        raise ValueError("refine_flow_host needs two (H, W) frames and an (H, W, 2) flow, H, W >= 4")
+    if not (0 < omega < 2) or min(alpha, gamma, delta, n_outer, n_sor) < 0:
+        raise ValueError("refine_flow_host: negative parameter, or omega outside (0, 2)")
+    if n_outer == 0:
+        return f0.copy()
+    u, v = f0[..., 0].astype(np.float64), f0[..., 1].astype(np.float64)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for _ in range(n_outer):
+        px, py = xx + u, yy + v
+        bw, inside = _fr_warp(B, px, py)
+        a11, a12, a22, b1, b2, wr, wd = _fr_coef(A, bw, inside, u, v, alpha, gamma, delta)
+        du, dv = np.zeros_like(u), np.zeros_like(v)
+        for _k in range(n_sor):
+            for colour in (0, 1):
+                _fr_half_sweep(colour, omega, x_only, u, v, du, dv, a11, a12, a22, b1, b2, wr, wd)
+        if _trace is not None:
+            _trace.append(dict(bw=bw, a11=a11, a12=a12, a22=a22, b1=b1, b2=b2, wr=wr, wd=wd, du=du.copy(), dv=dv.copy(),
+                               u=u.copy(), v=v.copy(), px=px, py=py))
+        u, v = u + du, v + dv
+    out = np.empty((h, w, 2), np.float32)
+    out[..., 0] = u
+    out[..., 1] = f0[..., 1] if x_only else v
+    return out
+
+
+class FlowRefiner:
+    """refine_flow_host on the device (``ictr_flowrefine_*``) for w x h frames; parameters as REFINE_DEFAULTS. ``run``
+    enqueues and returns; ``dense`` waits. The object is a device ICTR_FIELD_FLOW for the stereo track window."""
+
+    def __init__(self, w, h, **params):
+        unknown = set(params) - set(REFINE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"FlowRefiner: unknown parameter(s) {sorted(unknown)}")
+        self._h = C.c_void_p()
+        check(_lib.load().ictr_flowrefine_create(C.byref(self._h), int(w), int(h)))
+        self.w, self.h = int(w), int(h)
+        self.params = dict(REFINE_DEFAULTS, **params)
+        p = self.params
+        check(_lib.load().ictr_flowrefine_set_params(self._h, float(p["alpha"]), float(p["gamma"]), float(p["delta"]),
+                                                     int(p["n_outer"]), int(p["n_sor"]), float(p["omega"])))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_flowrefine_destroy(self._h)
+            self._h = None
+
+    def run(self, pyr_a, pyr_b, src, x_only=False, stream=None):
+        """src: an (H, W, 2) host array (checked for finiteness, copied now), a FlowGrid that holds a field, or a device
+        tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
+        f = _lib.Field(kind=1, sign=1, on_device=0, x_only=0, data=None)
+        keep = None
+        if isinstance(src, FlowGrid):
+            f.kind, f.data = 2, src._h.value
+        elif hasattr(src, "data_ptr"):
+            if tuple(src.shape) != (self.h, self.w, 2) or "float32" not in str(src.dtype) or not src.is_contiguous():
+                raise ValueError(f"FlowRefiner.run needs a contiguous float32 ({self.h}, {self.w}, 2) device field")
+            f.on_device, f.data = 1, src.data_ptr()
+        else:
+            keep = _lib.f32c(src)
+            if keep.shape != (self.h, self.w, 2):
+                raise ValueError(f"FlowRefiner.run needs an ({self.h}, {self.w}, 2) field, got {keep.shape}")
+            f.data = keep.ctypes.data
+        check(_lib.load().ictr_flowrefine_run(self._h, pyr_a._h, pyr_b._h, C.byref(f), int(bool(x_only)),
+                                              C.c_void_p(stream or 0)))
+        return self
+
+    def dense(self, out=None, on_device=False):
+        """The refined (H, W, 2) float32 field. on_device: `out` is a device pointer that receives it."""
+        if on_device:
+            check(_lib.load().ictr_flowrefine_result(self._h, C.c_void_p(out), 1))
+            return out
+        if out is None:
+            out = np.empty((self.h, self.w, 2), np.float32)
+        check(_lib.load().ictr_flowrefine_result(self._h, out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def device_ptr(self):
+        return int(_lib.load().ictr_flowrefine_device_ptr(self._h) or 0)
+
+    def stage(self, name):
+        """One (H, W) plane of the last outer iteration: a name of FR_STAGES."""
+        out = np.empty((self.h, self.w), np.float32)
+        check(_lib.load().ictr_flowrefine_read_stage(self._h, FR_STAGES.index(name), fp(out)))
+        return out
+
+    def _write_stage(self, name, plane):
+        plane = _lib.f32c(plane)
+        if plane.shape != (self.h, self.w):
+            raise ValueError(f"a stage plane is ({self.h}, {self.w})")
+        check(_lib.load().ictr_debug_flowrefine_write_stage(self._h, FR_STAGES.index(name), fp(plane)))
+
+    def _half_sweep(self, colour, x_only=False):
+        check(_lib.load().ictr_debug_flowrefine_half_sweep(self._h, int(colour), int(bool(x_only))))
+
+    def set_timing(self, on=True):
+        check(_lib.load().ictr_flowrefine_set_timing(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """(k_fr_warp, k_fr_coef, k_fr_sor, k_fr_init + k_fr_final) of the last run in ms; zeros when timing was off."""
+        ms = np.zeros(4, np.float32)
+        check(_lib.load().ictr_flowrefine_get_kernel_times(self._h, fp(ms)))
+        return ms
+
+
+def refine_flow(pyr_a, pyr_b, flow, x_only=False, **params):
+    """refine_flow_host's result from the device: host arrays in and out, one FlowRefiner for the call."""
+    flow = _lib.f32c(flow)
+    return FlowRefiner(pyr_a.w, pyr_a.h, **params).run(pyr_a, pyr_b, flow, x_only=x_only).dense()
 
 
 def good_features(img, maxcorners=1000, quality=0.001, mindist=5, win=3):

@@ -2,11 +2,14 @@
 
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
          [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
+         [--refine [alpha,gamma,delta,outer,sor,omega]]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
 (StereoPointTracker); --disparity 1d computes the stereo grids with the 1-D search along x (FlowGrid.compute_x) instead of
-the 2-D tracker with y dropped. With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+the 2-D tracker with y dropped. --refine refines every grid's dense field per pixel on the device before the window reads it
+(patchflow.FlowRefiner; without a value its defaults 16,13,4.5,8,5,1.6; the stereo fields move along x only). With
+--fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -24,13 +27,27 @@ from . import stereotrack as S
 
 
 def dense_fields_of(tracker):
-    """The dense fields of a StereoPointTracker built with keep_grids=True, in the host function's layout."""
-    g = tracker.grids
+    """The dense fields of a StereoPointTracker built with keep_grids=True, in the host function's layout: of its
+    refiners when it refines, else of its grids."""
+    g = tracker.refiners if tracker.refine is not None else tracker.grids
     lr = [-x["lr"].dense()[:, :, 0] for x in g]  # a left -> right grid is the script's -imgs_d[fr][0]
     rl = [np.ascontiguousarray(x["rl"].dense()[:, :, 0]) for x in g]
     fl = [(x["l_fwd"].dense(), x["l_bwd"].dense()) for x in g[1:]]
     fr = [(x["r_fwd"].dense(), x["r_bwd"].dense()) for x in g[1:]]
     return lr, rl, fl, fr
+
+
+def refine_params(text):
+    """'alpha,gamma,delta,outer,sor,omega' (a prefix will do; '' for the defaults) -> the dict StereoPointTracker takes."""
+    from .patchflow import REFINE_DEFAULTS
+    names = ("alpha", "gamma", "delta", "n_outer", "n_sor", "omega")
+    vals = [v for v in text.split(",") if v.strip()] if text else []
+    if len(vals) > len(names):
+        raise argparse.ArgumentTypeError("--refine takes at most alpha,gamma,delta,outer,sor,omega")
+    try:
+        return {n: type(REFINE_DEFAULTS[n])(float(v)) for n, v in zip(names, vals)}
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--refine: not a number in {text!r}")
 
 
 def main(argv=None):
@@ -46,6 +63,7 @@ def main(argv=None):
     ap.add_argument("--th_ratio", type=float, default=0.2)
     ap.add_argument("--th_abs", type=float, default=1.0)
     ap.add_argument("--disparity", choices=("2d", "1d"), default="2d")
+    ap.add_argument("--refine", nargs="?", const="", default=None, type=refine_params)
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
     th = dict(th_ratio=a.th_ratio, th_abs=a.th_abs)
     if a.fields:
@@ -61,7 +79,8 @@ def main(argv=None):
             return 2
         frames = [[np.asarray(iof.read_image_gray(fn), np.float32) for fn in p] for p in pairs]
         h, w = frames[0][0].shape
-        t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity, **th)
+        t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity,
+                                 refine=a.refine, **th)
         for left, right in frames:
             t.push_frames(left, right)
         xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()
