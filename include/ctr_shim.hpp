@@ -534,4 +534,30 @@ class FlowRefineClass {
   ictr_flowrefine *h_;
 };
 
+// Photometric densification of a flow grid at level 0 (ictr_flowdensify_* in include/ictr.h). Run enqueues, Result waits.
+// Field() is this object's field on the device, for FlowRefineClass::Run and the stereo track window.
+class FlowDensifyClass {
+ public:
+  FlowDensifyClass(int w, int h) : h_(nullptr) { check(ictr_flowdensify_create(&h_, w, h), "FlowDensifyClass"); }
+  ~FlowDensifyClass() { ictr_flowdensify_destroy(h_); }
+  FlowDensifyClass(const FlowDensifyClass &) = delete;
+  FlowDensifyClass &operator=(const FlowDensifyClass &) = delete;
+  void SetParams(float minerr = 2.0f, int power = 1) { check(ictr_flowdensify_set_params(h_, minerr, power), "SetParams"); }
+  // grid: an ictr_flowgrid that holds a field, tracked a -> b with patches of psz
+  void Run(const ictr_flowgrid *grid, const Pyramid &a, const Pyramid &b, int psz, void *hip_stream = nullptr) {
+    check(ictr_flowdensify_run(h_, grid, a.handle(), b.handle(), psz, hip_stream), "Run");
+  }
+  // out [h][w][2], in host memory or (on_device) device memory
+  void Result(float *out, bool on_device = false) { check(ictr_flowdensify_result(h_, out, on_device ? 1 : 0), "Result"); }
+  ictr_field Field(bool x_only = false) const {
+    ictr_field f = {ICTR_FIELD_FLOW, 1, 1, x_only ? 1 : 0, ictr_flowdensify_device_ptr(h_)};
+    return f;
+  }
+  // which: 0 the votes a pixel took, 1 their summed weight; out [h][w]
+  void ReadStage(int which, float *out) { check(ictr_flowdensify_read_stage(h_, which, out), "ReadStage"); }
+
+ private:
+  ictr_flowdensify *h_;
+};
+
 }  // namespace CTR

@@ -925,6 +925,36 @@ int ictr_flowrefine_read_stage(ictr_flowrefine *r, int which, float *out);
 int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, const float *in);
 int ictr_debug_flowrefine_half_sweep(ictr_flowrefine *r, int colour, int x_only);
 
+/* ---------------------------------------------------------------- densification of a flow grid (ictr_densify.hip)
+ * The dense field of a flow grid at level 0 by photometric voting (DESIGN.md §4 "Densification of a flow grid"): every
+ * pixel takes the weighted mean of the displacements of all nodes that are not lost and whose psz x psz patch covers it,
+ * in ascending node row, then column; a node's vote is dropped when it moves the pixel out of the frame, and weighs
+ * 1 / max(|B(x + d) - A(x)|, minerr)^power otherwise. A pixel without a vote takes the grid's up-sampled value
+ * (ictr_flowgrid_dense). The rule is patchflow.densify_flow_host's, in f32. The object owns its [h][w][2] f32 result. */
+typedef struct ictr_flowdensify ictr_flowdensify;
+/* 2 <= w, h <= 32768 */
+int ictr_flowdensify_create(ictr_flowdensify **out, int w, int h);
+void ictr_flowdensify_destroy(ictr_flowdensify *z);
+/* defaults 2.0, 1. Refused: a minerr that is not finite or not positive, a power outside 1..4. */
+int ictr_flowdensify_set_params(ictr_flowdensify *z, float minerr, int power);
+/* grid: holds a field of the object's size, tracked with patches of psz (1 .. 32); both pyramids are of that size
+ * (ICTR_ERR_INVALID otherwise; ICTR_ERR_STATE for a grid without a field). A step and psz whose node table does not fit
+ * a workgroup's LDS are refused (ICTR_ERR_INVALID). Only the level-0 image planes are read, with any padding. One launch,
+ * enqueued on hip_stream (NULL: the null stream); the call does not wait. */
+int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                         const ictr_pyramid *pyr_b, int psz, void *hip_stream);
+/* waits for the last run and copies its field [h][w][2] to out (a device pointer when on_device != 0) */
+int ictr_flowdensify_result(ictr_flowdensify *z, float *out, int on_device);
+/* the result buffer on the device (a device ICTR_FIELD_FLOW for the refinement and for the stereo track window), valid
+ * behind the run's stream */
+const float *ictr_flowdensify_device_ptr(const ictr_flowdensify *z);
+/* HIP events around the launch of the next runs; *ms of the last run's k_densify (waits for it), 0 when timing was off */
+int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on);
+int ictr_flowdensify_get_kernel_ms(ictr_flowdensify *z, float *ms);
+/* planes [h][w] f32 of the last run (waits for it): which = 0 the votes a pixel took, 1 their summed weight */
+#define ICTR_FLOWDENSIFY_STAGES 2
+int ictr_flowdensify_read_stage(ictr_flowdensify *z, int which, float *out);
+
 #ifdef __cplusplus
 }
 #endif

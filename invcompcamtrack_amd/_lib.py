@@ -335,6 +335,15 @@ SIGNATURES = {
     "ictr_flowrefine_read_stage": (C.c_int, [VP, C.c_int, FP]),
     "ictr_debug_flowrefine_write_stage": (C.c_int, [VP, C.c_int, FP]),
     "ictr_debug_flowrefine_half_sweep": (C.c_int, [VP, C.c_int, C.c_int]),
+    "ictr_flowdensify_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int]),
+    "ictr_flowdensify_destroy": (None, [VP]),
+    "ictr_flowdensify_set_params": (C.c_int, [VP, C.c_float, C.c_int]),
+    "ictr_flowdensify_run": (C.c_int, [VP, VP, VP, VP, C.c_int, VP]),
+    "ictr_flowdensify_result": (C.c_int, [VP, VP, C.c_int]),
+    "ictr_flowdensify_device_ptr": (VP, [VP]),
+    "ictr_flowdensify_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_flowdensify_get_kernel_ms": (C.c_int, [VP, FP]),
+    "ictr_flowdensify_read_stage": (C.c_int, [VP, C.c_int, FP]),
 }
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {

@@ -1,0 +1,233 @@
+// ictr_densify.hip -- photometric densification of a patch flow grid at level 0 (DESIGN.md §4 "Densification of a flow
+// grid"). The rule is build-defined; its statement of record is patchflow.densify_flow_host (NumPy, f64). This file is the
+// same rule in f32 with one fixed operation order, restated in NumPy f32 by tests/densify_f32.py.
+//
+// k_densify, one launch per field: a lane per pixel, one wave per 64 consecutive pixels of a row, four rows per workgroup
+// (k_fr_warp's mapping). Node (i, j) at (X, Y) = step / 2 + (i, j) step covers the pixels X - (psz - psz / 2) ..
+// X + psz / 2 - 1 (and Y likewise): the pixels k_patchflow samples at an integer centre. The records (dx, dy) of the nodes
+// whose footprint reaches the workgroup's 64 x 4 pixels are staged once in LDS, a lost node as dx = NaN: its position is
+// then not inside, which is how a vote is dropped anyway. A lane walks its covering nodes in ascending node row, then
+// ascending node column, warps B by each node's displacement (fr_bilinear, the refinement's warp) and weighs it with
+// wgt = 1 / max(|Bw - A|, minerr)^power. A pixel without a vote takes fg_value. f32 throughout.
+// The mean is taken about the pixel's first vote d0: F = d0 + sum(wgt (d - d0)) / sum(wgt), which is sum(wgt d) / sum(wgt).
+// In f32 the plain form carries one rounding per vote into a value of d's size: a constant table came back up to 18 ulp
+// off over the 64 votes of psz 32 at step 4, and a single vote an ulp off. About d0 the roundings act on the differences:
+// a constant table and a single vote come back to the bit (d - d0 = 0, and d0 + 0 = d0; a d0 of -0.0 comes back +0.0).
+// B's taps come from global memory: neighbouring lanes share the node for most votes, so a vote's four tap loads of a
+// wave are four contiguous row segments. Plain vector loads and stores, no atomics; enqueued on the caller's stream.
+#include <math.h>
+#include <string.h>
+
+#include <memory>
+
+#include "ictr_dev.h"
+#include "ictr_launch.h"
+#include "ictr_flowgrid_dev.h"
+#include "ictr_warp_dev.h"
+
+namespace ictr {
+
+constexpr int kDzMaxPsz = 32;          // the tracker's forms allow 1 .. 32
+constexpr size_t kDzMaxLds = 65536;    // bytes of LDS a workgroup may ask for
+
+struct DzArgs {
+  const float *A, *B;  // level-0 planes at pixel (0, 0), strides sa, sb
+  int sa, sb, w, h;
+  FgDev g;
+  const unsigned char *lost;  // [ny][nx]
+  int lo, hi;                 // a node at X covers X - lo .. X + hi
+  float minerr;
+  int power;
+  float2 *out;       // [h][w]
+  float *cnt, *sw;   // [h][w]: votes taken, and their summed weight
+};
+
+// the nodes i >= 0 with a <= i step, and those i <= n - 1 with i step <= b (-1: none)
+__host__ __device__ __forceinline__ int dz_first(int a, int step) { return a <= 0 ? 0 : (a + step - 1) / step; }
+__host__ __device__ __forceinline__ int dz_last(int b, int step, int n) { return b < 0 ? -1 : min(b / step, n - 1); }
+// the most nodes along an axis whose footprints reach `span` consecutive pixels: node positions step apart in an interval
+// of span - 1 + psz - 1 pixels
+static int dz_capacity(int span, int psz, int step) { return (span + psz - 2) / step + 1; }
+
+__global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
+  extern __shared__ float2 s_node[];  // [ncy][ncx] records of the nodes i0 .. i1 x j0 .. j1
+  const int step = a.g.step, half = step / 2;
+  const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * kWaves;
+  const int i0 = dz_first(bx0 - a.hi - half, step), i1 = dz_last(bx0 + 63 + a.lo - half, step, a.g.nx);
+  const int j0 = dz_first(by0 - a.hi - half, step), j1 = dz_last(by0 + kWaves - 1 + a.lo - half, step, a.g.ny);
+  const int ncx = max(i1 - i0 + 1, 0), ncy = max(j1 - j0 + 1, 0);
+  const float nanv = __int_as_float(0x7fc00000);
+  for (int q = threadIdx.x; q < ncx * ncy; q += kBlock) {
+    const int jj = q / ncx, ii = q - jj * ncx;
+    const int k = (j0 + jj) * a.g.nx + (i0 + ii);
+    float2 d = reinterpret_cast<const float2 *>(a.g.d)[k];
+    if (a.lost[k]) d.x = nanv;
+    s_node[q] = d;
+  }
+  __syncthreads();
+  const int X = bx0 + (threadIdx.x & 63), Y = by0 + (threadIdx.x >> 6);
+  if (X >= a.w || Y >= a.h) return;
+  // this pixel's nodes: a part of the workgroup's, since bx0 <= X <= bx0 + 63 and by0 <= Y <= by0 + kWaves - 1
+  const int li0 = dz_first(X - a.hi - half, step), li1 = dz_last(X + a.lo - half, step, a.g.nx);
+  const int lj0 = dz_first(Y - a.hi - half, step), lj1 = dz_last(Y + a.lo - half, step, a.g.ny);
+  const float av = a.A[(size_t)Y * a.sa + X];
+  float su = 0.0f, sv = 0.0f, sw = 0.0f;
+  float2 d0 = make_float2(0.0f, 0.0f);  // the first vote's displacement
+  int n = 0;
+  for (int j = lj0; j <= lj1; ++j) {
+    const float2 *row = s_node + (j - j0) * ncx - i0;
+    for (int i = li0; i <= li1; ++i) {
+      const float2 d = row[i];
+      const float px = (float)X + d.x, py = (float)Y + d.y;
+      if (!fr_inside(px, py, a.w, a.h)) continue;  // a lost node (NaN) too
+      const float r = fr_bilinear(a.B, a.sb, a.w, a.h, px, py) - av;
+      const float m = fmaxf(fabsf(r), a.minerr);
+      const float m2 = m * m;
+      const float mp = a.power == 1 ? m : a.power == 2 ? m2 : a.power == 3 ? m2 * m : m2 * m2;
+      const float wgt = 1.0f / mp;
+      if (n == 0) d0 = d;
+      su = su + wgt * (d.x - d0.x);
+      sv = sv + wgt * (d.y - d0.y);
+      sw = sw + wgt;
+      ++n;
+    }
+  }
+  float u, v;
+  if (n > 0) {
+    u = d0.x + su / sw;
+    v = d0.y + sv / sw;
+  } else {
+    fg_value(a.g, X, Y, &u, &v);
+  }
+  const size_t o = (size_t)Y * a.w + X;
+  a.out[o] = make_float2(u, v);
+  a.cnt[o] = (float)n;
+  a.sw[o] = sw;
+}
+
+}  // namespace ictr
+
+using namespace ictr;
+
+// ---------------------------------------------------------------- C-ABI
+struct ictr_flowdensify {
+  int w = 0, h = 0;
+  float minerr = 2.0f;
+  int power = 1;
+  int timing = 0, ran = 0, timed = 0;
+  float *out = nullptr, *cnt = nullptr, *sw = nullptr;  // [h][w][2], [h][w], [h][w]
+  DevBuf<float> arena;                                  // everything above
+  Event ev0, ev1;                                       // around the launch when timing is on
+  Event done;                                           // behind the last run
+};
+
+extern "C" void ictr_flowdensify_destroy(ictr_flowdensify *z) {
+  if (z && z->ran) (void)hipEventSynchronize(z->done.get());
+  delete z;
+}
+extern "C" int ictr_flowdensify_create(ictr_flowdensify **out, int w, int h) {
+  if (!out || w < 2 || h < 2 || w > 32768 || h > 32768)  // (the warp needs two taps each way; pixel indices are int)
+    return fail(ICTR_ERR_INVALID, "flowdensify: bad arguments (2 <= w, h <= 32768)");
+  if (int rc = need_device()) return rc;
+  auto z = std::make_unique<ictr_flowdensify>();
+  z->w = w;
+  z->h = h;
+  const size_t n = (size_t)w * h;
+  if (int rc = z->arena.alloc(sizeof(float) * 4 * n, true)) return rc;
+  z->out = z->arena.get();
+  z->cnt = z->out + 2 * n;
+  z->sw = z->cnt + n;
+  if (int rc = z->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = z->ev0.create()) return rc;
+  if (int rc = z->ev1.create()) return rc;
+  *out = z.release();
+  return ICTR_OK;
+}
+extern "C" int ictr_flowdensify_set_params(ictr_flowdensify *z, float minerr, int power) {
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  if (!isfinite(minerr) || !(minerr > 0.0f) || power < 1 || power > 4)
+    return fail(ICTR_ERR_INVALID, "flowdensify_set_params: finite minerr > 0, 1 <= power <= 4");
+  z->minerr = minerr;
+  z->power = power;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on) {
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  z->timing = on ? 1 : 0;
+  return ICTR_OK;
+}
+
+// level 0 of a pyramid of the object's size: the plane at pixel (0, 0) and its stride
+static int dz_level0(const ictr_flowdensify *z, const ictr_pyramid *p, const float **img, int *stride) {
+  ictr_pyramid_view v;
+  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is NULL");
+  if (v.w[0] != z->w || v.h[0] != z->h)
+    return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is %d x %d, the object %d x %d", v.w[0], v.h[0], z->w, z->h);
+  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
+  *stride = v.sw[0];
+  return ICTR_OK;
+}
+
+extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                    const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
+  DzArgs a;
+  memset(&a, 0, sizeof(a));
+  if (int rc = ictr_flowgrid_view_lost_(grid, &a.g, &a.lost)) return rc;
+  if (a.g.w != z->w || a.g.h != z->h)
+    return fail(ICTR_ERR_INVALID, "flowdensify_run: the flow grid is %d x %d, the object %d x %d", a.g.w, a.g.h, z->w, z->h);
+  if (int rc = dz_level0(z, pyr_a, &a.A, &a.sa)) return rc;
+  if (int rc = dz_level0(z, pyr_b, &a.B, &a.sb)) return rc;
+  a.w = z->w;
+  a.h = z->h;
+  a.lo = psz - psz / 2;
+  a.hi = psz / 2 - 1;
+  a.minerr = z->minerr;
+  a.power = z->power;
+  a.out = reinterpret_cast<float2 *>(z->out);
+  a.cnt = z->cnt;
+  a.sw = z->sw;
+  const size_t lds = sizeof(float2) * (size_t)dz_capacity(64, psz, a.g.step) * dz_capacity(kWaves, psz, a.g.step);
+  if (lds > kDzMaxLds)
+    return fail(ICTR_ERR_INVALID, "flowdensify_run: step %d with psz %d needs a node table of %zu bytes of LDS (limit %zu)",
+                a.g.step, psz, lds, kDzMaxLds);
+  hipStream_t s = (hipStream_t)hip_stream;
+  z->timed = z->timing;
+  if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
+  hipLaunchKernelGGL(k_densify, dim3((z->w + 63) / 64, (z->h + kWaves - 1) / kWaves), dim3(kBlock), lds, s, a);
+  if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(z->done.get(), s));
+  z->ran = 1;
+  return ICTR_OK;
+}
+
+static int dz_wait(ictr_flowdensify *z, const char *what) {
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  if (!z->ran) return fail(ICTR_ERR_STATE, "%s: no run yet", what);
+  HIPCHK(hipEventSynchronize(z->done.get()));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowdensify_result(ictr_flowdensify *z, float *out, int on_device) {
+  if (int rc = dz_wait(z, "flowdensify_result")) return rc;
+  if (!out) return fail(ICTR_ERR_INVALID, "flowdensify_result: out is NULL");
+  HIPCHK(hipMemcpy(out, z->out, sizeof(float) * 2 * (size_t)z->w * z->h,
+                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" const float *ictr_flowdensify_device_ptr(const ictr_flowdensify *z) { return z ? z->out : nullptr; }
+extern "C" int ictr_flowdensify_get_kernel_ms(ictr_flowdensify *z, float *ms) {
+  if (int rc = dz_wait(z, "flowdensify_get_kernel_ms")) return rc;
+  if (!ms) return fail(ICTR_ERR_INVALID, "flowdensify_get_kernel_ms: ms is NULL");
+  *ms = 0.0f;
+  if (z->timed) HIPCHK(hipEventElapsedTime(ms, z->ev0.get(), z->ev1.get()));
+  return ICTR_OK;
+}
+extern "C" int ictr_flowdensify_read_stage(ictr_flowdensify *z, int which, float *out) {
+  if (!out || which < 0 || which >= ICTR_FLOWDENSIFY_STAGES)
+    return fail(ICTR_ERR_INVALID, "flowdensify_read_stage: bad arguments (which is 0..%d)", ICTR_FLOWDENSIFY_STAGES - 1);
+  if (int rc = dz_wait(z, "flowdensify_read_stage")) return rc;
+  HIPCHK(hipMemcpy(out, which == 0 ? z->cnt : z->sw, sizeof(float) * (size_t)z->w * z->h, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}

@@ -57,3 +57,5 @@ __device__ __forceinline__ void fg_gather(const FgDev &g, double x, double y, do
 
 // the node table of a grid that holds a field; non-zero (with its message): NULL, or no field yet (ictr_frontend.hip)
 extern "C" int ictr_flowgrid_view_(const ictr_flowgrid *g, ictr::FgDev *v);
+// the same with the lost mask [ny][nx] (1: the node was lost and v->d holds its filled value), for k_densify
+extern "C" int ictr_flowgrid_view_lost_(const ictr_flowgrid *g, ictr::FgDev *v, const unsigned char **lost);

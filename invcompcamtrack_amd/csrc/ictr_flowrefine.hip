@@ -24,6 +24,7 @@
 #include "ictr_dev.h"
 #include "ictr_launch.h"
 #include "ictr_flowgrid_dev.h"
+#include "ictr_warp_dev.h"
 
 namespace ictr {
 
@@ -68,9 +69,7 @@ __host__ __device__ __forceinline__ int fr_ci(int X, int Y, int w, int h) {
   return ((X + Y) & 1) * wc * h + Y * wc + (X >> 1);
 }
 
-__device__ __forceinline__ bool fr_inside(float px, float py, int w, int h) {
-  return (px >= 0.0f) & (px <= (float)(w - 1)) & (py >= 0.0f) & (py <= (float)(h - 1));  // NaN: outside
-}
+// fr_inside, fr_bilinear: ictr_warp_dev.h
 
 __global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgs a, int fold) {
   const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
@@ -85,14 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgs a, int fold) {
       a.v[i] = v;
     }
   }
-  const float px = fminf(fmaxf((float)X + u, 0.0f), (float)(a.w - 1));  // fmaxf(NaN, 0) = 0
-  const float py = fminf(fmaxf((float)Y + v, 0.0f), (float)(a.h - 1));
-  const int x0 = min((int)floorf(px), a.w - 2), y0 = min((int)floorf(py), a.h - 2);
-  const float fx = px - (float)x0, fy = py - (float)y0;
-  const float *b = a.B + (size_t)y0 * a.sb + x0;
-  const float b00 = b[0], b01 = b[1], b10 = b[a.sb], b11 = b[a.sb + 1];
-  const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
-  a.bw[i] = ((w00 * b00 + w01 * b01) + w10 * b10) + w11 * b11;
+  a.bw[i] = fr_bilinear(a.B, a.sb, a.w, a.h, (float)X + u, (float)Y + v);
 }
 
 // a tile with its halo; (cx, cy) are tile coordinates, the frame coordinate is (gx0 + cx, gy0 + cy)

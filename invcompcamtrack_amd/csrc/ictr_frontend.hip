@@ -481,6 +481,12 @@ extern "C" int ictr_flowgrid_view_(const ictr_flowgrid *g, FgDev *v) {
   *v = fg_dev(g);
   return ICTR_OK;
 }
+extern "C" int ictr_flowgrid_view_lost_(const ictr_flowgrid *g, FgDev *v, const unsigned char **lost) {
+  if (!lost) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  if (int rc = ictr_flowgrid_view_(g, v)) return rc;
+  *lost = g->lost;
+  return ICTR_OK;
+}
 
 extern "C" void ictr_flowgrid_destroy(ictr_flowgrid *g) { delete g; }
 extern "C" int ictr_flowgrid_create(ictr_flowgrid **out, int w, int h, int step) {

@@ -26,7 +26,8 @@ from .tracker import Pyramid
 __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "run_OF_point_track", "last_kernel_ms",
            "last_form", "track_disparity", "dense_disparity", "disparity_last_kernel_ms", "disparity_last_form",
            "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip", "refine_flow_host", "refine_flow",
-           "FlowRefiner", "REFINE_DEFAULTS", "FR_STAGES"]
+           "FlowRefiner", "REFINE_DEFAULTS", "FR_STAGES", "densify_flow_host", "densify_flow", "FlowDensifier",
+           "DENSIFY_DEFAULTS", "DZ_STAGES"]
 
 
 def last_kernel_ms():
@@ -129,8 +130,12 @@ def dense_flow(pyr_a, pyr_b, step=4, psz=15, lv_f=None, maxiter=10, eps=0.01, _t
     gx, gy = np.meshgrid(xs, ys)
     pts = np.stack([gx.ravel(), gy.ravel()], 1)
     new, ok, _ = (_track or track_points)(pyr_a, pyr_b, pts, psz=psz, lv_f=lv_f, maxiter=maxiter, eps=eps)
-    d = (new - pts).reshape(len(ys), len(xs), 2)
-    bad = ~ok.reshape(len(ys), len(xs))
+    return _dense_from_nodes((new - pts).reshape(len(ys), len(xs), 2), ~ok.reshape(len(ys), len(xs)), w, h, step)
+
+
+def _dense_from_nodes(d, bad, w, h, step):
+    """dense_flow from its node table on: d (ny, nx, 2) float32 (overwritten by the fill), bad (ny, nx) the lost nodes."""
+    xs, ys = range(step // 2, w, step), range(step // 2, h, step)
     if bad.any():
         d[bad] = np.nan
         for axis in (1, 0):  # forward/backward fill along rows, then columns
@@ -294,12 +299,17 @@ class FlowRefiner:
             self._h = None
 
     def run(self, pyr_a, pyr_b, src, x_only=False, stream=None):
-        """src: an (H, W, 2) host array (checked for finiteness, copied now), a FlowGrid that holds a field, or a device
-        tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
+        """src: an (H, W, 2) host array (checked for finiteness, copied now), a FlowGrid that holds a field, a
+        FlowDensifier that has run (its buffer on the device, read when the run executes: run it on the same stream), or a
+        device tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
         f = _lib.Field(kind=1, sign=1, on_device=0, x_only=0, data=None)
         keep = None
         if isinstance(src, FlowGrid):
             f.kind, f.data = 2, src._h.value
+        elif isinstance(src, FlowDensifier):
+            if (src.h, src.w) != (self.h, self.w):
+                raise ValueError(f"a densifier of {src.w} x {src.h} for a refiner of {self.w} x {self.h}")
+            f.on_device, f.data, keep = 1, src.device_ptr(), src
         elif hasattr(src, "data_ptr"):
             if tuple(src.shape) != (self.h, self.w, 2) or "float32" not in str(src.dtype) or not src.is_contiguous():
                 raise ValueError(f"FlowRefiner.run needs a contiguous float32 ({self.h}, {self.w}, 2) device field")
@@ -355,6 +365,155 @@ def refine_flow(pyr_a, pyr_b, flow, x_only=False, **params):
     """refine_flow_host's result from the device: host arrays in and out, one FlowRefiner for the call."""
     flow = _lib.f32c(flow)
     return FlowRefiner(pyr_a.w, pyr_a.h, **params).run(pyr_a, pyr_b, flow, x_only=x_only).dense()
+
+
+# ---------------------------------------------------------------- photometric densification of a flow grid
+DENSIFY_DEFAULTS = dict(minerr=2.0, power=1)
+DZ_STAGES = ("count", "wsum")  # ictr_flowdensify_read_stage
+DZ_MAX_PSZ = 32
+
+
+def _dz_nodes(n_px, n_nodes, step, psz):
+    """Per pixel coordinate 0 .. n_px - 1: (first, last) node index along the axis whose footprint covers it; a node at
+    X = step // 2 + i step covers X - (psz - psz // 2) .. X + psz // 2 - 1, the pixels k_patchflow samples at an integer
+    centre. last < first: no node."""
+    x = np.arange(n_px)
+    lo, hi, half = psz - psz // 2, psz // 2 - 1, step // 2
+    first = np.maximum(-((-(x - hi - half)) // step), 0)
+    last = np.minimum((x + lo - half) // step, n_nodes - 1)
+    return first, last
+
+
+def _dz_power(m, power):
+    m2 = m * m
+    return m if power == 1 else m2 if power == 2 else m2 * m if power == 3 else m2 * m2
+
+
+def _dz_check(img_a, img_b, d, lost, step, psz, minerr, power):
+    A, B = np.asarray(img_a, np.float32), np.asarray(img_b, np.float32)
+    h, w = A.shape if A.ndim == 2 else (0, 0)
+    if B.shape != A.shape or A.ndim != 2 or w < 2 or h < 2:
+        raise ValueError("densify needs two (H, W) frames, H, W >= 2")
+    if int(step) != step or step < 1 or step // 2 >= min(w, h):
+        raise ValueError("densify: the grid needs a step >= 1 and at least one node")
+    nx, ny = len(range(step // 2, w, step)), len(range(step // 2, h, step))
+    d = np.ascontiguousarray(d, np.float32)
+    lost = np.asarray(lost).astype(bool)
+    if d.shape != (ny, nx, 2) or lost.shape != (ny, nx):
+        raise ValueError(f"densify needs d ({ny}, {nx}, 2) and lost ({ny}, {nx})")
+    if int(psz) != psz or not 1 <= psz <= DZ_MAX_PSZ:
+        raise ValueError(f"densify: psz is 1 .. {DZ_MAX_PSZ}")
+    if not (np.isfinite(minerr) and minerr > 0) or int(power) != power or not 1 <= power <= 4:
+        raise ValueError("densify: minerr is finite and positive, power an integer 1 .. 4")
+    return A, B, d, lost
+
+
+def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _stages=None):
+    """Photometric densification of a flow grid A -> B at level 0: the definition (build-defined; NumPy, f64 arithmetic on
+    the f32 inputs; DESIGN.md §4 "Densification of a flow grid" states the rule). img_a, img_b: (H, W) grey frames; d
+    (ny, nx, 2), lost (ny, nx): the node table of a grid of `step` (nodes at step // 2 + k step) tracked with patches of
+    psz. Every pixel takes sum(wgt d) / sum(wgt) over the nodes that are not lost and whose patch covers it (_dz_nodes), in
+    ascending node row, then column: a vote whose position (x, y) + d is not inside the frame is dropped; otherwise
+    wgt = 1 / max(|Bw - A[y, x]|, minerr)^power with Bw by refine_flow_host's warp (_fr_warp). A pixel without a vote
+    takes dense_flow's value. The sums are plain f64 sums of exact products, the quotient is rounded to f32 once.
+    Returns (H, W, 2) float32. _stages: a dict that receives "count" (votes taken, int), "wsum" (their summed weight,
+    f64) and "edge" (the least distance of a pixel's vote positions to the inside boundary in px, inf without one)."""
+    A32, B32, d, lost = _dz_check(img_a, img_b, d, lost, step, psz, minerr, power)
+    A, B = A32.astype(np.float64), B32.astype(np.float64)
+    h, w = A.shape
+    ny, nx = lost.shape
+    i0, i1 = _dz_nodes(w, nx, step, psz)
+    j0, j1 = _dz_nodes(h, ny, step, psz)
+    d64 = d.astype(np.float64)
+    yy, xx = np.mgrid[0:h, 0:w]
+    su, sv, sw = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
+    cnt = np.zeros((h, w), np.int64)
+    edge = np.full((h, w), np.inf)
+    for a in range(max(int((j1 - j0).max()) + 1, 0)):
+        j, vj = np.minimum(j0 + a, ny - 1), j0 + a <= j1
+        for b in range(max(int((i1 - i0).max()) + 1, 0)):
+            i, vi = np.minimum(i0 + b, nx - 1), i0 + b <= i1
+            votes = vj[:, None] & vi[None, :] & ~lost[j][:, i]
+            dx, dy = d64[j][:, i, 0], d64[j][:, i, 1]
+            px, py = xx + dx, yy + dy
+            with np.errstate(invalid="ignore"):
+                bw, inside = _fr_warp(B, px, py)
+                near = np.minimum(np.minimum(np.abs(px), np.abs(px - (w - 1))), np.minimum(np.abs(py), np.abs(py - (h - 1))))
+                edge = np.where(votes & (near < edge), near, edge)
+                ok = votes & (inside > 0)
+                wgt = 1.0 / _dz_power(np.fmax(np.abs(bw - A), float(minerr)), power)
+                su, sv, sw = np.where(ok, su + wgt * dx, su), np.where(ok, sv + wgt * dy, sv), np.where(ok, sw + wgt, sw)
+            cnt += ok
+    out = _dense_from_nodes(d.copy(), lost, w, h, step)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[..., 0] = np.where(cnt > 0, su / sw, out[..., 0])
+        out[..., 1] = np.where(cnt > 0, sv / sw, out[..., 1])
+    if _stages is not None:
+        _stages.update(count=cnt, wsum=sw, edge=edge)
+    return out
+
+
+class FlowDensifier:
+    """densify_flow_host on the device (``ictr_flowdensify_*``, one k_densify launch per field) for w x h frames;
+    parameters as DENSIFY_DEFAULTS. ``run`` enqueues and returns; ``dense`` waits. The object is a device ICTR_FIELD_FLOW
+    for FlowRefiner.run and for the stereo track window."""
+
+    def __init__(self, w, h, **params):
+        unknown = set(params) - set(DENSIFY_DEFAULTS)
+        if unknown:
+            raise TypeError(f"FlowDensifier: unknown parameter(s) {sorted(unknown)}")
+        self._h = C.c_void_p()
+        check(_lib.load().ictr_flowdensify_create(C.byref(self._h), int(w), int(h)))
+        self.w, self.h = int(w), int(h)
+        self.params = dict(DENSIFY_DEFAULTS, **params)
+        if int(self.params["power"]) != self.params["power"]:
+            raise ValueError("FlowDensifier: power is an integer 1 .. 4")
+        check(_lib.load().ictr_flowdensify_set_params(self._h, float(self.params["minerr"]), int(self.params["power"])))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_flowdensify_destroy(self._h)
+            self._h = None
+
+    def run(self, grid, pyr_a, pyr_b, psz=15, stream=None):
+        """grid: a FlowGrid of the object's size that holds a field, tracked A -> B with patches of psz."""
+        if not isinstance(grid, FlowGrid):
+            raise TypeError("FlowDensifier.run needs a FlowGrid")
+        check(_lib.load().ictr_flowdensify_run(self._h, grid._h, pyr_a._h, pyr_b._h, int(psz), C.c_void_p(stream or 0)))
+        return self
+
+    def dense(self, out=None, on_device=False):
+        """The densified (H, W, 2) float32 field. on_device: `out` is a device pointer that receives it."""
+        if on_device:
+            check(_lib.load().ictr_flowdensify_result(self._h, C.c_void_p(out), 1))
+            return out
+        if out is None:
+            out = np.empty((self.h, self.w, 2), np.float32)
+        check(_lib.load().ictr_flowdensify_result(self._h, out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def device_ptr(self):
+        return int(_lib.load().ictr_flowdensify_device_ptr(self._h) or 0)
+
+    def stage(self, name):
+        """One (H, W) float32 plane of the last run: a name of DZ_STAGES."""
+        out = np.empty((self.h, self.w), np.float32)
+        check(_lib.load().ictr_flowdensify_read_stage(self._h, DZ_STAGES.index(name), fp(out)))
+        return out
+
+    def set_timing(self, on=True):
+        check(_lib.load().ictr_flowdensify_set_timing(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """k_densify of the last run in ms; 0 when timing was off."""
+        ms = np.zeros(1, np.float32)
+        check(_lib.load().ictr_flowdensify_get_kernel_ms(self._h, fp(ms)))
+        return float(ms[0])
+
+
+def densify_flow(pyr_a, pyr_b, grid, psz, **params):
+    """densify_flow_host's result from the device: a FlowGrid in, a host array out, one FlowDensifier for the call."""
+    return FlowDensifier(pyr_a.w, pyr_a.h, **params).run(grid, pyr_a, pyr_b, psz).dense()
 
 
 def good_features(img, maxcorners=1000, quality=0.001, mindist=5, win=3):

@@ -157,9 +157,9 @@ def stereo_track_window_host(disp_lr, disp_rl, flow_l, flow_r, xy0=None, th_rati
 class field:
     """A displacement field with an exact sign for StereoTrackWindow: ``data`` is a float32 array (H, W) (a plane, moves x
     only) or (H, W, 2) (a flow) in host memory, a torch tensor of one of those shapes on the device, or a FlowGrid (its
-    dense field is never formed), or a FlowRefiner that has run (its refined field on the device). float64 arrays are
-    accepted only where every value is a float32 value. In a stereo slot
-    (lr, rl) a flow or a grid moves x only."""
+    dense field is never formed), or a FlowRefiner or FlowDensifier that has run (its field on the device). float64
+    arrays are accepted only where every value is a float32 value. In a stereo slot (lr, rl) a flow or a grid moves x
+    only."""
 
     def __init__(self, data, sign=1):
         if sign not in (1, -1):
@@ -181,15 +181,15 @@ def _exact_f32(a):
 
 def _descriptor(f, stereo, w, h):
     """-> (_lib.Field, what must stay alive until the step has run)"""
-    from .patchflow import FlowGrid, FlowRefiner
+    from .patchflow import FlowDensifier, FlowGrid, FlowRefiner
     f = f if isinstance(f, field) else field(f)
     d = _lib.Field(sign=f.sign, x_only=int(stereo))
     data = f.data
     if isinstance(data, FlowGrid):
         d.kind, d.data, keep = FIELD_GRID, data._h.value, data
-    elif isinstance(data, FlowRefiner):  # its result buffer, read when the step runs (behind the refiner's run)
+    elif isinstance(data, (FlowRefiner, FlowDensifier)):  # its result buffer, read when the step runs (behind its run)
         if (data.h, data.w) != (h, w):
-            raise ValueError(f"a refiner of {data.w} x {data.h} in a window of {w} x {h}")
+            raise ValueError(f"a {type(data).__name__} of {data.w} x {data.h} in a window of {w} x {h}")
         d.kind, d.on_device, d.data, keep = FIELD_FLOW, 1, data.device_ptr(), data
     else:
         on_device = hasattr(data, "data_ptr")
@@ -300,16 +300,22 @@ class StereoPointTracker:
     1-D search along x (FlowGrid.compute_x), which keeps vertical edges and is not misled by tilted 1-D structure.
     refine=None: the grids go to the window as they are. refine=dict (parameters of patchflow.FlowRefiner, {} for its
     defaults): every grid's dense field is refined per pixel on the device (the stereo fields with x_only) and the
-    refiners go to the window in the grids' place; keep_grids=True keeps them too, in ``refiners`` (same layout)."""
+    refiners go to the window in the grids' place; keep_grids=True keeps them too, in ``refiners`` (same layout).
+    densify=None: nothing is made or launched. densify=dict (parameters of patchflow.FlowDensifier, {} for its defaults):
+    every grid is densified photometrically on the device (grid -> densify -> refine): with refine the refiners read the
+    densifiers, without it the window does; keep_grids=True keeps them in ``densifiers`` (same layout)."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
-                 xy0=None, keep_grids=False, disparity="2d", refine=None):
+                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         self.disparity = disparity
         self.refine = None if refine is None else dict(refine)
         self.refiners = []
         self._rsets = [None, None]
+        self.densify = None if densify is None else dict(densify)
+        self.densifiers = []
+        self._dsets = [None, None]
         self.w, self.h, self.bsize = int(w), int(h), int(bsize)
         self.step, self.psz, self.lv_f, self.maxiter, self.eps = int(step), int(psz), int(lv_f), int(maxiter), float(eps)
         self.xy0, self.keep_grids = xy0, bool(keep_grids)
@@ -337,6 +343,15 @@ class StereoPointTracker:
             self._rsets[k & 1] = {n: FlowRefiner(self.w, self.h, **self.refine) for n in names}
         return self._rsets[k & 1]
 
+    def _densifier_set(self, k):
+        from .patchflow import FlowDensifier
+        names = ("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")
+        if self.keep_grids:
+            return {n: FlowDensifier(self.w, self.h, **self.densify) for n in names}
+        if self._dsets[k & 1] is None:
+            self._dsets[k & 1] = {n: FlowDensifier(self.w, self.h, **self.densify) for n in names}
+        return self._dsets[k & 1]
+
     def push_frames(self, left, right):
         from .tracker import Pyramid
         k = self.nframes
@@ -361,11 +376,17 @@ class StereoPointTracker:
         else:
             g["lr"].compute(pl, pr, **kw)
             g["rl"].compute(pr, pl, **kw)
-        f = g  # what the window reads: the grids, or the refiners of their dense fields
+        f = g  # what the window reads: the grids, their densifiers, or the refiners of either
+        z = None
+        if self.densify is not None:
+            f = z = self._densifier_set(k)
+            z["lr"].run(g["lr"], pl, pr, self.psz)
+            z["rl"].run(g["rl"], pr, pl, self.psz)
         if self.refine is not None:
+            src = f
             f = self._refiner_set(k)
-            f["lr"].run(pl, pr, g["lr"], x_only=True)
-            f["rl"].run(pr, pl, g["rl"], x_only=True)
+            f["lr"].run(pl, pr, src["lr"], x_only=True)
+            f["rl"].run(pr, pl, src["rl"], x_only=True)
         if k == 0:
             self.win.open(f["lr"], f["rl"], self.xy0)
         else:
@@ -374,16 +395,24 @@ class StereoPointTracker:
             g["l_bwd"].compute(pl, ql, **kw)
             g["r_fwd"].compute(qr, pr, **kw)
             g["r_bwd"].compute(pr, qr, **kw)
+            if z is not None:
+                z["l_fwd"].run(g["l_fwd"], ql, pl, self.psz)
+                z["l_bwd"].run(g["l_bwd"], pl, ql, self.psz)
+                z["r_fwd"].run(g["r_fwd"], qr, pr, self.psz)
+                z["r_bwd"].run(g["r_bwd"], pr, qr, self.psz)
             if self.refine is not None:
-                f["l_fwd"].run(ql, pl, g["l_fwd"])
-                f["l_bwd"].run(pl, ql, g["l_bwd"])
-                f["r_fwd"].run(qr, pr, g["r_fwd"])
-                f["r_bwd"].run(pr, qr, g["r_bwd"])
+                src = g if z is None else z
+                f["l_fwd"].run(ql, pl, src["l_fwd"])
+                f["l_bwd"].run(pl, ql, src["l_bwd"])
+                f["r_fwd"].run(qr, pr, src["r_fwd"])
+                f["r_bwd"].run(pr, qr, src["r_bwd"])
             self.win.advance(f["l_fwd"], f["l_bwd"], f["r_fwd"], f["r_bwd"], f["lr"], f["rl"])
         if self.keep_grids:
             self.grids.append(g if k else {n: g[n] for n in ("lr", "rl")})
             if self.refine is not None:
                 self.refiners.append(f if k else {n: f[n] for n in ("lr", "rl")})
+            if z is not None:
+                self.densifiers.append(z if k else {n: z[n] for n in ("lr", "rl")})
         self.nframes = k + 1
 
     def window(self):
