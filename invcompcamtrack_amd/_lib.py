@@ -68,6 +68,9 @@ class Field(C.Structure):
                 ("data", C.c_void_p)]
 
 
+FIELD_PLANE, FIELD_FLOW, FIELD_GRID = 0, 1, 2  # ICTR_FIELD_*, the `kind` of a Field
+
+
 class TriangParams(C.Structure):
     """ictr_triang_params (include/ictr.h)."""
     _fields_ = [("noiter", C.c_int32), ("minres", C.c_float), ("damp_init", C.c_float), ("damp_fct", C.c_float),

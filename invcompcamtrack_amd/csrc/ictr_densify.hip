@@ -114,17 +114,14 @@ struct ictr_flowdensify {
   int w = 0, h = 0;
   float minerr = 2.0f;
   int power = 1;
-  int timing = 0, ran = 0, timed = 0;
-  float *out = nullptr, *cnt = nullptr, *sw = nullptr;  // [h][w][2], [h][w], [h][w]
-  DevBuf<float> arena;                                  // everything above
-  Event ev0, ev1;                                       // around the launch when timing is on
-  Event done;                                           // behind the last run
+  int timing = 0, timed = 0;
+  float *cnt = nullptr, *sw = nullptr;  // [h][w], [h][w]
+  DevBuf<float> arena;                  // the result [h][w][2], then the two above
+  Event ev0, ev1;                       // around the launch when timing is on
+  DenseResult res;                      // last: its destructor waits for a run in flight
 };
 
-extern "C" void ictr_flowdensify_destroy(ictr_flowdensify *z) {
-  if (z && z->ran) (void)hipEventSynchronize(z->done.get());
-  delete z;
-}
+extern "C" void ictr_flowdensify_destroy(ictr_flowdensify *z) { delete z; }
 extern "C" int ictr_flowdensify_create(ictr_flowdensify **out, int w, int h) {
   if (!out || w < 2 || h < 2 || w > 32768 || h > 32768)  // (the warp needs two taps each way; pixel indices are int)
     return fail(ICTR_ERR_INVALID, "flowdensify: bad arguments (2 <= w, h <= 32768)");
@@ -134,10 +131,9 @@ extern "C" int ictr_flowdensify_create(ictr_flowdensify **out, int w, int h) {
   z->h = h;
   const size_t n = (size_t)w * h;
   if (int rc = z->arena.alloc(sizeof(float) * 4 * n, true)) return rc;
-  z->out = z->arena.get();
-  z->cnt = z->out + 2 * n;
+  z->cnt = z->arena.get() + 2 * n;
   z->sw = z->cnt + n;
-  if (int rc = z->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = z->res.bind(z->arena.get(), w, h)) return rc;
   if (int rc = z->ev0.create()) return rc;
   if (int rc = z->ev1.create()) return rc;
   *out = z.release();
@@ -157,17 +153,6 @@ extern "C" int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on) {
   return ICTR_OK;
 }
 
-// level 0 of a pyramid of the object's size: the plane at pixel (0, 0) and its stride
-static int dz_level0(const ictr_flowdensify *z, const ictr_pyramid *p, const float **img, int *stride) {
-  ictr_pyramid_view v;
-  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is NULL");
-  if (v.w[0] != z->w || v.h[0] != z->h)
-    return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is %d x %d, the object %d x %d", v.w[0], v.h[0], z->w, z->h);
-  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
-  *stride = v.sw[0];
-  return ICTR_OK;
-}
-
 extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
                                     const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
   if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
@@ -177,15 +162,21 @@ extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *gr
   if (int rc = ictr_flowgrid_view_lost_(grid, &a.g, &a.lost)) return rc;
   if (a.g.w != z->w || a.g.h != z->h)
     return fail(ICTR_ERR_INVALID, "flowdensify_run: the flow grid is %d x %d, the object %d x %d", a.g.w, a.g.h, z->w, z->h);
-  if (int rc = dz_level0(z, pyr_a, &a.A, &a.sa)) return rc;
-  if (int rc = dz_level0(z, pyr_b, &a.B, &a.sb)) return rc;
+  ictr_level0 l[2];
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowdensify_run", &l[k])) return rc;
+    if (l[k].w != z->w || l[k].h != z->h)
+      return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is %d x %d, the object %d x %d", l[k].w, l[k].h, z->w, z->h);
+  }
+  a.A = l[0].img, a.sa = l[0].stride;
+  a.B = l[1].img, a.sb = l[1].stride;
   a.w = z->w;
   a.h = z->h;
   a.lo = psz - psz / 2;
   a.hi = psz / 2 - 1;
   a.minerr = z->minerr;
   a.power = z->power;
-  a.out = reinterpret_cast<float2 *>(z->out);
+  a.out = reinterpret_cast<float2 *>(z->res.get());
   a.cnt = z->cnt;
   a.sw = z->sw;
   const size_t lds = sizeof(float2) * (size_t)dz_capacity(64, psz, a.g.step) * dz_capacity(kWaves, psz, a.g.step);
@@ -195,30 +186,20 @@ extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *gr
   hipStream_t s = (hipStream_t)hip_stream;
   z->timed = z->timing;
   if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
-  hipLaunchKernelGGL(k_densify, dim3((z->w + 63) / 64, (z->h + kWaves - 1) / kWaves), dim3(kBlock), lds, s, a);
+  hipLaunchKernelGGL(k_densify, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
   if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(z->done.get(), s));
-  z->ran = 1;
-  return ICTR_OK;
+  return z->res.record(s);
 }
 
-static int dz_wait(ictr_flowdensify *z, const char *what) {
-  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
-  if (!z->ran) return fail(ICTR_ERR_STATE, "%s: no run yet", what);
-  HIPCHK(hipEventSynchronize(z->done.get()));
-  return ICTR_OK;
-}
 extern "C" int ictr_flowdensify_result(ictr_flowdensify *z, float *out, int on_device) {
-  if (int rc = dz_wait(z, "flowdensify_result")) return rc;
-  if (!out) return fail(ICTR_ERR_INVALID, "flowdensify_result: out is NULL");
-  HIPCHK(hipMemcpy(out, z->out, sizeof(float) * 2 * (size_t)z->w * z->h,
-                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-  return ICTR_OK;
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  return z->res.copy_out("flowdensify_result", out, on_device);
 }
-extern "C" const float *ictr_flowdensify_device_ptr(const ictr_flowdensify *z) { return z ? z->out : nullptr; }
+extern "C" const float *ictr_flowdensify_device_ptr(const ictr_flowdensify *z) { return z ? z->res.get() : nullptr; }
 extern "C" int ictr_flowdensify_get_kernel_ms(ictr_flowdensify *z, float *ms) {
-  if (int rc = dz_wait(z, "flowdensify_get_kernel_ms")) return rc;
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  if (int rc = z->res.wait("flowdensify_get_kernel_ms")) return rc;
   if (!ms) return fail(ICTR_ERR_INVALID, "flowdensify_get_kernel_ms: ms is NULL");
   *ms = 0.0f;
   if (z->timed) HIPCHK(hipEventElapsedTime(ms, z->ev0.get(), z->ev1.get()));
@@ -227,7 +208,8 @@ extern "C" int ictr_flowdensify_get_kernel_ms(ictr_flowdensify *z, float *ms) {
 extern "C" int ictr_flowdensify_read_stage(ictr_flowdensify *z, int which, float *out) {
   if (!out || which < 0 || which >= ICTR_FLOWDENSIFY_STAGES)
     return fail(ICTR_ERR_INVALID, "flowdensify_read_stage: bad arguments (which is 0..%d)", ICTR_FLOWDENSIFY_STAGES - 1);
-  if (int rc = dz_wait(z, "flowdensify_read_stage")) return rc;
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  if (int rc = z->res.wait("flowdensify_read_stage")) return rc;
   HIPCHK(hipMemcpy(out, which == 0 ? z->cnt : z->sw, sizeof(float) * (size_t)z->w * z->h, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }

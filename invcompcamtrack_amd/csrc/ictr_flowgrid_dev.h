@@ -59,3 +59,7 @@ __device__ __forceinline__ void fg_gather(const FgDev &g, double x, double y, do
 extern "C" int ictr_flowgrid_view_(const ictr_flowgrid *g, ictr::FgDev *v);
 // the same with the lost mask [ny][nx] (1: the node was lost and v->d holds its filled value), for k_densify
 extern "C" int ictr_flowgrid_view_lost_(const ictr_flowgrid *g, ictr::FgDev *v, const unsigned char **lost);
+// the dense field of a grid, interleaved [h][w][2], into device memory: k_fg_dense on s (ictr_frontend.hip)
+namespace ictr {
+void launch_fg_dense(const FgDev &g, float2 *out, hipStream_t s);
+}

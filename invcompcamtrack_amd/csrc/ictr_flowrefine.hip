@@ -52,14 +52,7 @@ __global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f
   u[i] = f.x;
   v[i] = f.y;
 }
-// the dense field of a flow grid, interleaved
-__global__ __launch_bounds__(kBlock) void k_fr_from_grid(FgDev g, float2 *__restrict__ out) {
-  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (X >= g.w || Y >= g.h) return;
-  float u, v;
-  fg_value(g, X, Y, &u, &v);
-  out[(size_t)Y * g.w + X] = make_float2(u, v);
-}
+// (a flow grid's dense field is formed by launch_fg_dense: ictr_flowgrid_dev.h)
 
 // Where a coefficient (a11, a12, a22, b1, b2) of pixel (X, Y) lives in its plane: the plane is compacted by colour, first
 // all pixels of colour 0 row by row, then those of colour 1, rows of ceil(w / 2). A half-sweep, which reads the
@@ -220,13 +213,13 @@ struct ictr_flowrefine {
   int w = 0, h = 0;
   float alpha = 16.0f, gamma = 13.0f, delta = 4.5f, omega = 1.6f;
   int n_outer = 8, n_sor = 5;
-  int timing = 0, ran = 0;
+  int timing = 0;
   float *plane[kFrPlanes] = {};
-  float *f0 = nullptr, *out = nullptr;  // interleaved [h][w][2]: the source formed or copied here, the result
-  DevBuf<float> arena;                  // everything above
-  std::vector<Event> ev;                // timing: four per outer iteration and four around init and final
-  int nev = 0;                          // events recorded by the last run
-  Event done;                           // behind the last run
+  float *f0 = nullptr;    // interleaved [h][w][2]: the source formed or copied here
+  DevBuf<float> arena;    // everything above, then the result
+  std::vector<Event> ev;  // timing: four per outer iteration and four around init and final
+  int nev = 0;            // events recorded by the last run
+  DenseResult res;        // last: its destructor waits for a run in flight
 };
 enum { FR_U, FR_V, FR_DU, FR_DV, FR_BW, FR_A11, FR_A12, FR_A22, FR_B1, FR_B2, FR_WR, FR_WD };
 // ictr_flowrefine_read_stage's `which` -> plane
@@ -260,19 +253,15 @@ static FrArgs fr_args(const ictr_flowrefine *r, int x_only) {
   a.x_only = x_only ? 1 : 0;
   return a;
 }
-static dim3 fr_grid_rows(const ictr_flowrefine *r, int cols) { return dim3((cols + 63) / 64, (r->h + kWaves - 1) / kWaves); }
 static void fr_half_sweep(const ictr_flowrefine *r, const FrArgs &a, int colour, hipStream_t s) {
-  const dim3 g = fr_grid_rows(r, (r->w + 1) / 2);
+  const dim3 g = pixel_rows_grid((r->w + 1) / 2, r->h);
   if (colour == 0)
     hipLaunchKernelGGL(k_fr_sor<0>, g, dim3(kBlock), 0, s, a);
   else
     hipLaunchKernelGGL(k_fr_sor<1>, g, dim3(kBlock), 0, s, a);
 }
 
-extern "C" void ictr_flowrefine_destroy(ictr_flowrefine *r) {
-  if (r && r->ran) (void)hipEventSynchronize(r->done.get());
-  delete r;
-}
+extern "C" void ictr_flowrefine_destroy(ictr_flowrefine *r) { delete r; }
 extern "C" int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h) {
   if (!out || w < 4 || h < 4 || w > 32768 || h > 32768)  // (pixel indices are int, rows / 4 a grid dimension)
     return fail(ICTR_ERR_INVALID, "flowrefine: bad arguments (4 <= w, h <= 32768)");
@@ -284,8 +273,7 @@ extern "C" int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h) {
   if (int rc = r->arena.alloc(sizeof(float) * n * (kFrPlanes + 4), true)) return rc;
   for (int k = 0; k < kFrPlanes; ++k) r->plane[k] = r->arena.get() + n * k;
   r->f0 = r->arena.get() + n * kFrPlanes;
-  r->out = r->f0 + 2 * n;
-  if (int rc = r->done.create(hipEventDisableTiming)) return rc;
+  if (int rc = r->res.bind(r->f0 + 2 * n, w, h)) return rc;
   *out = r.release();
   return ICTR_OK;
 }
@@ -310,25 +298,20 @@ extern "C" int ictr_flowrefine_set_timing(ictr_flowrefine *r, int on) {
   return ICTR_OK;
 }
 
-// level 0 of a pyramid of the refiner's size: the plane at pixel (0, 0) and its stride
-static int fr_level0(const ictr_flowrefine *r, const ictr_pyramid *p, const float **img, int *stride) {
-  ictr_pyramid_view v;
-  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is NULL");
-  if (v.w[0] != r->w || v.h[0] != r->h)
-    return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", v.w[0], v.h[0], r->w, r->h);
-  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
-  *stride = v.sw[0];
-  return ICTR_OK;
-}
-
 extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                    const ictr_field *src, int x_only, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
   if (!src || !src->data) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field (or its data) is NULL");
   if (src->sign != 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field's sign is %d (+1)", src->sign);
   FrArgs a = fr_args(r, x_only);
-  if (int rc = fr_level0(r, pyr_a, &a.A, &a.sa)) return rc;
-  if (int rc = fr_level0(r, pyr_b, &a.B, &a.sb)) return rc;
+  ictr_level0 l[2];
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowrefine_run", &l[k])) return rc;
+    if (l[k].w != r->w || l[k].h != r->h)
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
+  }
+  a.A = l[0].img, a.sa = l[0].stride;
+  a.B = l[1].img, a.sb = l[1].stride;
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t n = (size_t)r->w * r->h;
   const float *f0 = r->f0;
@@ -337,7 +320,7 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
     if (int rc = ictr_flowgrid_view_(static_cast<const ictr_flowgrid *>(src->data), &g)) return rc;
     if (g.w != r->w || g.h != r->h)
       return fail(ICTR_ERR_INVALID, "flowrefine_run: the flow grid is %d x %d, the refiner %d x %d", g.w, g.h, r->w, r->h);
-    hipLaunchKernelGGL(k_fr_from_grid, fr_grid_rows(r, r->w), dim3(kBlock), 0, s, g, reinterpret_cast<float2 *>(r->f0));
+    launch_fg_dense(g, reinterpret_cast<float2 *>(r->f0), s);
   } else if (src->kind == ICTR_FIELD_FLOW) {
     if (src->on_device) {
       f0 = static_cast<const float *>(src->data);
@@ -345,7 +328,7 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
       const float *f = static_cast<const float *>(src->data);
       for (size_t i = 0; i < 2 * n; ++i)
         if (!isfinite(f[i])) return fail(ICTR_ERR_INVALID, "flowrefine_run: the host field is not finite at float %zu", i);
-      if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));  // the last run has read f0
+      if (int rc = r->res.settle()) return rc;  // the last run has read f0
       HIPCHK(hipMemcpyAsync(r->f0, f, sizeof(float) * 2 * n, hipMemcpyHostToDevice, s));
       HIPCHK(hipStreamSynchronize(s));  // the caller's array is free when this returns; the kernels follow on s
     }
@@ -362,7 +345,7 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
     if (r->timing) (void)hipEventRecord(r->ev[r->nev++].get(), s);
   };
   if (r->n_outer == 0) {  // the input's bits
-    HIPCHK(hipMemcpyAsync(r->out, f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(r->res.get(), f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
   } else {
     const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
     const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
@@ -371,7 +354,7 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
     mark();
     for (int o = 0; o < r->n_outer; ++o) {
       mark();
-      hipLaunchKernelGGL(k_fr_warp, fr_grid_rows(r, r->w), blk, 0, s, a, o > 0 ? 1 : 0);
+      hipLaunchKernelGGL(k_fr_warp, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
       mark();
       hipLaunchKernelGGL(k_fr_coef, tiles, blk, 0, s, a);
       mark();
@@ -382,31 +365,21 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
       mark();
     }
     mark();
-    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, a, reinterpret_cast<float2 *>(r->out));
+    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, a, reinterpret_cast<float2 *>(r->res.get()));
     mark();
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(r->done.get(), s));
-  r->ran = 1;
-  return ICTR_OK;
+  return r->res.record(s);
 }
 
-static int fr_wait(ictr_flowrefine *r, const char *what) {
-  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
-  if (!r->ran) return fail(ICTR_ERR_STATE, "%s: no run yet", what);
-  HIPCHK(hipEventSynchronize(r->done.get()));
-  return ICTR_OK;
-}
 extern "C" int ictr_flowrefine_result(ictr_flowrefine *r, float *out, int on_device) {
-  if (int rc = fr_wait(r, "flowrefine_result")) return rc;
-  if (!out) return fail(ICTR_ERR_INVALID, "flowrefine_result: out is NULL");
-  HIPCHK(hipMemcpy(out, r->out, sizeof(float) * 2 * (size_t)r->w * r->h,
-                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-  return ICTR_OK;
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  return r->res.copy_out("flowrefine_result", out, on_device);
 }
-extern "C" const float *ictr_flowrefine_device_ptr(const ictr_flowrefine *r) { return r ? r->out : nullptr; }
+extern "C" const float *ictr_flowrefine_device_ptr(const ictr_flowrefine *r) { return r ? r->res.get() : nullptr; }
 extern "C" int ictr_flowrefine_get_kernel_times(ictr_flowrefine *r, float *ms) {
-  if (int rc = fr_wait(r, "flowrefine_get_kernel_times")) return rc;
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  if (int rc = r->res.wait("flowrefine_get_kernel_times")) return rc;
   if (!ms) return fail(ICTR_ERR_INVALID, "flowrefine_get_kernel_times: ms is NULL");
   ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
   if (r->nev < 4) return ICTR_OK;  // timing was off, or n_outer = 0
@@ -426,7 +399,7 @@ extern "C" int ictr_flowrefine_get_kernel_times(ictr_flowrefine *r, float *ms) {
 extern "C" int ictr_flowrefine_read_stage(ictr_flowrefine *r, int which, float *out) {
   if (!r || !out || which < 0 || which >= ICTR_FLOWREFINE_STAGES)
     return fail(ICTR_ERR_INVALID, "flowrefine_read_stage: bad arguments (which is 0..%d)", ICTR_FLOWREFINE_STAGES - 1);
-  if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));
+  if (int rc = r->res.settle()) return rc;
   const int k = kFrStage[which];
   if (!fr_compacted(k)) {
     HIPCHK(hipMemcpy(out, r->plane[k], sizeof(float) * (size_t)r->w * r->h, hipMemcpyDeviceToHost));
@@ -441,7 +414,7 @@ extern "C" int ictr_flowrefine_read_stage(ictr_flowrefine *r, int which, float *
 extern "C" int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, const float *in) {
   if (!r || !in || which < 0 || which >= ICTR_FLOWREFINE_STAGES)
     return fail(ICTR_ERR_INVALID, "flowrefine_write_stage: bad arguments (which is 0..%d)", ICTR_FLOWREFINE_STAGES - 1);
-  if (r->ran) HIPCHK(hipEventSynchronize(r->done.get()));
+  if (int rc = r->res.settle()) return rc;
   const int k = kFrStage[which];
   if (!fr_compacted(k)) {
     HIPCHK(hipMemcpy(r->plane[k], in, sizeof(float) * (size_t)r->w * r->h, hipMemcpyHostToDevice));

@@ -287,16 +287,6 @@ static int gf_run(const GfWork &g, const float *img, int stride, int maxcorners,
   return ICTR_OK;
 }
 
-static int pyr_level0(const ictr_pyramid *p, const float **img, int *stride, int *w, int *h) {
-  ictr_pyramid_view v;
-  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return fail(ICTR_ERR_INVALID, "pyramid is NULL");
-  *img = v.img[0] + (size_t)v.pad * v.sw[0] + v.pad;
-  *stride = v.sw[0];
-  *w = v.w[0];
-  *h = v.h[0];
-  return ICTR_OK;
-}
-
 // ---------------------------------------------------------------- flow grid
 // FgDev, fg_value, fg_gather: ictr_flowgrid_dev.h
 
@@ -363,6 +353,9 @@ __global__ __launch_bounds__(kBlock) void k_fg_dense(FgDev g, float2 *__restrict
   float u, v;
   fg_value(g, X, Y, &u, &v);
   out[(size_t)Y * g.w + X] = make_float2(u, v);
+}
+void launch_fg_dense(const FgDev &g, float2 *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_fg_dense, pixel_rows_grid(g.w, g.h), dim3(kBlock), 0, s, g, out);
 }
 
 // ---------------------------------------------------------------- track window
@@ -443,24 +436,23 @@ extern "C" int ictr_good_features(const ictr_pyramid *pyr, const float *img, int
   if ((!pyr && !img) || maxcorners < 1 || !out_count || !out_xy)
     return fail(ICTR_ERR_INVALID, "good_features: bad arguments (a pyramid or an image, maxcorners >= 1)");
   if (int rc = need_device()) return rc;
-  const float *plane = nullptr;
-  int stride = w;
+  ictr_level0 l0{nullptr, w, w, h};  // a host image is staged below, rows of w
   if (pyr) {
-    if (int rc = pyr_level0(pyr, &plane, &stride, &w, &h)) return rc;
+    if (int rc = ictr_pyramid_level0(pyr, "good_features", &l0)) return rc;
   } else if (w < 1 || h < 1) {
     return fail(ICTR_ERR_INVALID, "good_features: bad image size");
   }
   GfWork g;
-  if (int rc = gf_alloc(&g, w, h, mindist, win)) return rc;
+  if (int rc = gf_alloc(&g, l0.w, l0.h, mindist, win)) return rc;
   DevBuf<float> stage, d_out;
   if (!pyr) {
     if (int rc = stage.alloc(sizeof(float) * (size_t)w * h)) return rc;
     HIPCHK(hipMemcpy(stage.get(), img, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice));
-    plane = stage.get();
+    l0.img = stage.get();
   }
   if (int rc = d_out.alloc(sizeof(float) * 2 * (size_t)maxcorners + sizeof(int))) return rc;
   int *d_count = reinterpret_cast<int *>(d_out.get() + 2 * (size_t)maxcorners);
-  if (int rc = gf_run(g, plane, stride, maxcorners, quality, d_out.get(), d_count, nullptr)) return rc;
+  if (int rc = gf_run(g, l0.img, l0.stride, maxcorners, quality, d_out.get(), d_count, nullptr)) return rc;
   HIPCHK(hipMemcpy(out_count, d_count, sizeof(int), hipMemcpyDeviceToHost));
   if (*out_count > 0) HIPCHK(hipMemcpy(out_xy, d_out.get(), sizeof(float) * 2 * (size_t)*out_count, hipMemcpyDeviceToHost));
   return ICTR_OK;
@@ -600,8 +592,7 @@ extern "C" int ictr_flowgrid_dense(const ictr_flowgrid *g, float *out, int on_de
     if (int rc = own.alloc(bytes)) return rc;
   float *d = on_device ? out : own.get();
   HIPCHK(hipDeviceSynchronize());
-  hipLaunchKernelGGL(k_fg_dense, dim3((g->w + 63) / 64, (g->h + kWaves - 1) / kWaves), dim3(kBlock), 0, nullptr, fg_dev(g),
-                     reinterpret_cast<float2 *>(d));
+  launch_fg_dense(fg_dev(g), reinterpret_cast<float2 *>(d), nullptr);
   HIPCHK(on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
@@ -665,14 +656,13 @@ extern "C" int ictr_pointtrack_push_frame(ictr_pointtrack *t, const float *img) 
   ictr_pyramid *pa = t->pyr[k & 1], *pb = cur;
   if (int rc = ictr_flowgrid_compute(t->fw.get(), pa, pb, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
   if (int rc = ictr_flowgrid_compute(t->bw.get(), pb, pa, t->psz, t->lv_f, t->maxiter, t->eps, s)) return rc;
-  const float *plane;
-  int stride, w, h;
-  if (int rc = pyr_level0(pa, &plane, &stride, &w, &h)) return rc;
+  ictr_level0 l0;
+  if (int rc = ictr_pyramid_level0(pa, "pointtrack_push_frame", &l0)) return rc;
   const PtGeom &g = t->geom;
   const dim3 grid((g.mc + kBlock - 1) / kBlock), blk(kBlock);
   char *ring = t->ring.get();
   const PtSlot open = pt_slot(ring + g.bytes * (size_t)(k % g.bsize), g);
-  if (int rc = gf_run(t->gf, plane, stride, g.mc, t->quality, t->corners.get(), open.count, s)) return rc;
+  if (int rc = gf_run(t->gf, l0.img, l0.stride, g.mc, t->quality, t->corners.get(), open.count, s)) return rc;
   hipLaunchKernelGGL(k_pt_open, grid, blk, 0, s, open, t->corners.get(), g.mc, g.bsize);
   for (int age = 0; age <= g.bsize - 2 && age <= k; ++age) {  // the blocks k - age, column age -> age + 1
     const PtSlot sl = pt_slot(ring + g.bytes * (size_t)((k - age) % g.bsize), g);

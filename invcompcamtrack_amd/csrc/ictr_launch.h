@@ -22,6 +22,18 @@ struct ictr_pyramid_view {
   int getgrad;  // 1: the gradient planes exist (image-only pyramids of the tracker's on-the-fly path have none)
 };
 extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v);  // ictr_host.hip
+// Level 0 of a pyramid as a kernel reads a frame: the plane at pixel (0, 0), inside the padding, and its row stride. The
+// one place that forms this address; `who` opens the message about a NULL or empty pyramid. Size checks are the caller's.
+struct ictr_level0 {
+  const float *img;
+  int stride, w, h;
+};
+inline int ictr_pyramid_level0(const ictr_pyramid *p, const char *who, ictr_level0 *l) {
+  ictr_pyramid_view v;
+  if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return ictr::fail(ICTR_ERR_INVALID, "%s: a pyramid is NULL", who);
+  *l = ictr_level0{v.img[0] + (size_t)v.pad * v.sw[0] + v.pad, v.sw[0], v.w[0], v.h[0]};
+  return ICTR_OK;
+}
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);
@@ -87,6 +99,8 @@ inline int ran_tile_env(const char *name) {
 }
 // ... and the workgroups of `block` threads that give each of nwords 64-item words one wave
 inline int ran_segs(int nwords, int block) { return (nwords + block / 64 - 1) / (block / 64); }
+// the per-pixel kernels of the flow stages: a wave per 64 consecutive columns of a row, kWaves rows per workgroup
+inline dim3 pixel_rows_grid(int cols, int rows) { return dim3((cols + 63) / 64, (rows + kWaves - 1) / kWaves); }
 
 // ---------------------------------------------------------------- argument bundles of the launchers (host side only)
 // launch geometry of one pyramid level's kernels

@@ -1,5 +1,6 @@
 // ictr_own.h -- who releases what on the host side: move-only holders of device memory, pinned host memory and HIP events,
-// and the result block with the run / wait state of an object that is run now and waited for later (Readback).
+// and the run / wait state of an object that is run now and waited for later: with its result block and pinned mirror
+// (Readback), or around a dense field that stays on the device (DenseResult).
 // A holder owns; a raw pointer next to it borrows. An object that carves one block up itself (a pyramid's planes, the flow
 // grid's arena) holds that block with ONE holder. Host only; included through ictr_launch.h.
 #pragma once
@@ -143,6 +144,46 @@ class Readback {
   size_t cap_ = 0;
   Event done_;
   bool pending_ = false, ran_ = false;
+};
+
+// The dense field [h][w][2] f32 that a run fills on the caller's stream and a later call waits for (the flow refiner, the
+// flow densifier). No Readback: there is no pinned mirror, the array is BORROWED from the object's arena. The holder owns
+// the event behind the last run and whether one was ever enqueued. Declare it LAST in its object, as a Readback.
+class DenseResult {
+ public:
+  ~DenseResult() { (void)settle(); }
+  int bind(float *out, int w, int h) {
+    out_ = out;
+    bytes_ = sizeof(float) * 2 * (size_t)w * h;
+    return done_.create(hipEventDisableTiming);
+  }
+  float *get() const { return out_; }
+  // the tail of every run: behind everything enqueued on s
+  int record(hipStream_t s) {
+    HIPCHK(hipEventRecord(done_.get(), s));
+    ran_ = true;
+    return ICTR_OK;
+  }
+  // waits if a run was enqueued: before the host reads or overwrites what that run reads or writes
+  int settle() {
+    if (ran_) HIPCHK(hipEventSynchronize(done_.get()));
+    return ICTR_OK;
+  }
+  // waits for the last run, or refuses when there was none
+  int wait(const char *what) { return ran_ ? settle() : fail(ICTR_ERR_STATE, "%s: no run yet", what); }
+  // wait(what), then the field to `out` in host or device memory
+  int copy_out(const char *what, float *out, int on_device) {
+    if (int rc = wait(what)) return rc;
+    if (!out) return fail(ICTR_ERR_INVALID, "%s: out is NULL", what);
+    HIPCHK(hipMemcpy(out, out_, bytes_, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return ICTR_OK;
+  }
+
+ private:
+  float *out_ = nullptr;
+  size_t bytes_ = 0;
+  Event done_;
+  bool ran_ = false;
 };
 
 }  // namespace ictr

@@ -158,6 +158,82 @@ def _dense_from_nodes(d, bad, w, h, step):
     return (top * (1 - ay) + bot * ay).astype(np.float32)
 
 
+# ---------------------------------------------------------------- a dense field on the device: its owner, its sources
+def _dense_out(result, handle, w, h, out, on_device):
+    """``dense(out, on_device)`` of every object here: ``result`` is its C function (handle, pointer, on_device)."""
+    if on_device:
+        check(result(handle, C.c_void_p(out), 1))
+        return out
+    if out is None:
+        out = np.empty((h, w, 2), np.float32)
+    check(result(handle, out.ctypes.data_as(C.c_void_p), 0))
+    return out
+
+
+class _DenseStage:
+    """An object ``ictr_<_C>_*`` that owns an (H, W, 2) float32 result on the device for w x h frames: ``run`` (the
+    subclass's) enqueues and returns, ``dense`` and ``stage`` wait. A subclass names its C prefix, its parameters with
+    their defaults and its stage planes, and sends the parameters down in ``_set_params``."""
+    _C, _DEFAULTS, _STAGES = None, {}, ()
+
+    def __init__(self, w, h, **params):
+        unknown = set(params) - set(self._DEFAULTS)
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown parameter(s) {sorted(unknown)}")
+        self._h = C.c_void_p()
+        check(self._c("create")(C.byref(self._h), int(w), int(h)))
+        self.w, self.h = int(w), int(h)
+        self.params = dict(self._DEFAULTS, **params)
+        self._set_params()
+
+    def _c(self, name):
+        return getattr(_lib.load(), f"ictr_{self._C}_{name}")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._c("destroy")(self._h)
+            self._h = None
+
+    def dense(self, out=None, on_device=False):
+        """The (H, W, 2) float32 result of the last run. on_device: `out` is a device pointer that receives it."""
+        return _dense_out(self._c("result"), self._h, self.w, self.h, out, on_device)
+
+    def device_ptr(self):
+        return int(self._c("device_ptr")(self._h) or 0)
+
+    def stage(self, name):
+        """One (H, W) float32 plane of the last run: a name of the class's stages (FR_STAGES, DZ_STAGES)."""
+        out = np.empty((self.h, self.w), np.float32)
+        check(self._c("read_stage")(self._h, self._STAGES.index(name), fp(out)))
+        return out
+
+    def set_timing(self, on=True):
+        check(self._c("set_timing")(self._h, int(bool(on))))
+
+
+def _device_source(src, w, h, stages):
+    """What a field source on the device is, for frames of w x h: (kind, device pointer, the object to keep alive until
+    the reader has run, components), or None for anything else (a host array: its rules are the caller's). A FlowGrid
+    (FIELD_GRID, its handle; never formed), an object of one of the classes ``stages`` that has run (its result buffer),
+    or an object with ``data_ptr()`` (a torch tensor): float32, contiguous, on the GPU where it says where it is, (H, W)
+    (FIELD_PLANE, 1 component) or (H, W, 2) (FIELD_FLOW, 2). A wrong size or shape is a ValueError, a wrong dtype,
+    layout or residence a TypeError."""
+    if isinstance(src, FlowGrid):
+        return _lib.FIELD_GRID, src._h.value, src, 2
+    if isinstance(src, stages):
+        if (src.h, src.w) != (h, w):
+            raise ValueError(f"a {type(src).__name__} of {src.w} x {src.h} where the frames are {w} x {h}")
+        return _lib.FIELD_FLOW, src.device_ptr(), src, 2
+    if not hasattr(src, "data_ptr"):
+        return None
+    if not str(src.dtype).endswith("float32") or not src.is_contiguous() or not getattr(src, "is_cuda", True):
+        raise TypeError("a device field is a contiguous float32 tensor on the GPU")
+    shape = tuple(src.shape)
+    if shape not in ((h, w), (h, w, 2)):
+        raise ValueError(f"a field is ({h}, {w}) or ({h}, {w}, 2), not {shape}")
+    return (_lib.FIELD_PLANE if len(shape) == 2 else _lib.FIELD_FLOW), src.data_ptr(), src, len(shape) - 1
+
+
 # ---------------------------------------------------------------- variational refinement of a dense field
 REFINE_DEFAULTS = dict(alpha=16.0, gamma=13.0, delta=4.5, n_outer=8, n_sor=5, omega=1.6)
 _FR_EPS, _FR_ZETA = 1e-3, 0.1
@@ -277,70 +353,40 @@ def refine_flow_host(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_ou
     return out
 
 
-class FlowRefiner:
+class FlowRefiner(_DenseStage):
     """refine_flow_host on the device (``ictr_flowrefine_*``) for w x h frames; parameters as REFINE_DEFAULTS. ``run``
-    enqueues and returns; ``dense`` waits. The object is a device ICTR_FIELD_FLOW for the stereo track window."""
+    enqueues and returns; ``dense`` (the refined field) waits. ``stage``: a plane of the last outer iteration. The object
+    is a device ICTR_FIELD_FLOW for the stereo track window."""
+    _C, _DEFAULTS, _STAGES = "flowrefine", REFINE_DEFAULTS, FR_STAGES
 
-    def __init__(self, w, h, **params):
-        unknown = set(params) - set(REFINE_DEFAULTS)
-        if unknown:
-            raise TypeError(f"FlowRefiner: unknown parameter(s) {sorted(unknown)}")
-        self._h = C.c_void_p()
-        check(_lib.load().ictr_flowrefine_create(C.byref(self._h), int(w), int(h)))
-        self.w, self.h = int(w), int(h)
-        self.params = dict(REFINE_DEFAULTS, **params)
+    def _set_params(self):
         p = self.params
-        check(_lib.load().ictr_flowrefine_set_params(self._h, float(p["alpha"]), float(p["gamma"]), float(p["delta"]),
-                                                     int(p["n_outer"]), int(p["n_sor"]), float(p["omega"])))
+        check(self._c("set_params")(self._h, float(p["alpha"]), float(p["gamma"]), float(p["delta"]), int(p["n_outer"]),
+                                    int(p["n_sor"]), float(p["omega"])))
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            _lib.load().ictr_flowrefine_destroy(self._h)
-            self._h = None
+    def _source(self, src):
+        """-> (the _lib.Field of `src`, what must stay alive until ictr_flowrefine_run has returned)"""
+        f = _lib.Field(kind=_lib.FIELD_FLOW, sign=1, on_device=0, x_only=0, data=None)
+        dev = _device_source(src, self.w, self.h, (FlowDensifier,))
+        if dev is None:
+            keep = _lib.f32c(src)
+            if keep.shape != (self.h, self.w, 2):
+                raise ValueError(f"FlowRefiner.run needs an ({self.h}, {self.w}, 2) field, got {keep.shape}")
+            f.data = keep.ctypes.data
+            return f, keep
+        f.kind, f.data, keep, components = dev
+        if components != 2:
+            raise ValueError(f"FlowRefiner.run needs a ({self.h}, {self.w}, 2) device field, not a plane")
+        f.on_device = int(f.kind != _lib.FIELD_GRID)
+        return f, keep
 
     def run(self, pyr_a, pyr_b, src, x_only=False, stream=None):
         """src: an (H, W, 2) host array (checked for finiteness, copied now), a FlowGrid that holds a field, a
         FlowDensifier that has run (its buffer on the device, read when the run executes: run it on the same stream), or a
         device tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
-        f = _lib.Field(kind=1, sign=1, on_device=0, x_only=0, data=None)
-        keep = None
-        if isinstance(src, FlowGrid):
-            f.kind, f.data = 2, src._h.value
-        elif isinstance(src, FlowDensifier):
-            if (src.h, src.w) != (self.h, self.w):
-                raise ValueError(f"a densifier of {src.w} x {src.h} for a refiner of {self.w} x {self.h}")
-            f.on_device, f.data, keep = 1, src.device_ptr(), src
-        elif hasattr(src, "data_ptr"):
-            if tuple(src.shape) != (self.h, self.w, 2) or "float32" not in str(src.dtype) or not src.is_contiguous():
-                raise ValueError(f"FlowRefiner.run needs a contiguous float32 ({self.h}, {self.w}, 2) device field")
-            f.on_device, f.data = 1, src.data_ptr()
-        else:
-            keep = _lib.f32c(src)
-            if keep.shape != (self.h, self.w, 2):
-                raise ValueError(f"FlowRefiner.run needs an ({self.h}, {self.w}, 2) field, got {keep.shape}")
-            f.data = keep.ctypes.data
-        check(_lib.load().ictr_flowrefine_run(self._h, pyr_a._h, pyr_b._h, C.byref(f), int(bool(x_only)),
-                                              C.c_void_p(stream or 0)))
+        f, _keep = self._source(src)
+        check(self._c("run")(self._h, pyr_a._h, pyr_b._h, C.byref(f), int(bool(x_only)), C.c_void_p(stream or 0)))
         return self
-
-    def dense(self, out=None, on_device=False):
-        """The refined (H, W, 2) float32 field. on_device: `out` is a device pointer that receives it."""
-        if on_device:
-            check(_lib.load().ictr_flowrefine_result(self._h, C.c_void_p(out), 1))
-            return out
-        if out is None:
-            out = np.empty((self.h, self.w, 2), np.float32)
-        check(_lib.load().ictr_flowrefine_result(self._h, out.ctypes.data_as(C.c_void_p), 0))
-        return out
-
-    def device_ptr(self):
-        return int(_lib.load().ictr_flowrefine_device_ptr(self._h) or 0)
-
-    def stage(self, name):
-        """One (H, W) plane of the last outer iteration: a name of FR_STAGES."""
-        out = np.empty((self.h, self.w), np.float32)
-        check(_lib.load().ictr_flowrefine_read_stage(self._h, FR_STAGES.index(name), fp(out)))
-        return out
 
     def _write_stage(self, name, plane):
         plane = _lib.f32c(plane)
@@ -351,13 +397,10 @@ class FlowRefiner:
     def _half_sweep(self, colour, x_only=False):
         check(_lib.load().ictr_debug_flowrefine_half_sweep(self._h, int(colour), int(bool(x_only))))
 
-    def set_timing(self, on=True):
-        check(_lib.load().ictr_flowrefine_set_timing(self._h, int(bool(on))))
-
     def kernel_ms(self):
         """(k_fr_warp, k_fr_coef, k_fr_sor, k_fr_init + k_fr_final) of the last run in ms; zeros when timing was off."""
         ms = np.zeros(4, np.float32)
-        check(_lib.load().ictr_flowrefine_get_kernel_times(self._h, fp(ms)))
+        check(self._c("get_kernel_times")(self._h, fp(ms)))
         return ms
 
 
@@ -453,61 +496,28 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     return out
 
 
-class FlowDensifier:
+class FlowDensifier(_DenseStage):
     """densify_flow_host on the device (``ictr_flowdensify_*``, one k_densify launch per field) for w x h frames;
-    parameters as DENSIFY_DEFAULTS. ``run`` enqueues and returns; ``dense`` waits. The object is a device ICTR_FIELD_FLOW
-    for FlowRefiner.run and for the stereo track window."""
+    parameters as DENSIFY_DEFAULTS. ``run`` enqueues and returns; ``dense`` (the densified field) waits. The object is a
+    device ICTR_FIELD_FLOW for FlowRefiner.run and for the stereo track window."""
+    _C, _DEFAULTS, _STAGES = "flowdensify", DENSIFY_DEFAULTS, DZ_STAGES
 
-    def __init__(self, w, h, **params):
-        unknown = set(params) - set(DENSIFY_DEFAULTS)
-        if unknown:
-            raise TypeError(f"FlowDensifier: unknown parameter(s) {sorted(unknown)}")
-        self._h = C.c_void_p()
-        check(_lib.load().ictr_flowdensify_create(C.byref(self._h), int(w), int(h)))
-        self.w, self.h = int(w), int(h)
-        self.params = dict(DENSIFY_DEFAULTS, **params)
+    def _set_params(self):
         if int(self.params["power"]) != self.params["power"]:
             raise ValueError("FlowDensifier: power is an integer 1 .. 4")
-        check(_lib.load().ictr_flowdensify_set_params(self._h, float(self.params["minerr"]), int(self.params["power"])))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            _lib.load().ictr_flowdensify_destroy(self._h)
-            self._h = None
+        check(self._c("set_params")(self._h, float(self.params["minerr"]), int(self.params["power"])))
 
     def run(self, grid, pyr_a, pyr_b, psz=15, stream=None):
         """grid: a FlowGrid of the object's size that holds a field, tracked A -> B with patches of psz."""
         if not isinstance(grid, FlowGrid):
             raise TypeError("FlowDensifier.run needs a FlowGrid")
-        check(_lib.load().ictr_flowdensify_run(self._h, grid._h, pyr_a._h, pyr_b._h, int(psz), C.c_void_p(stream or 0)))
+        check(self._c("run")(self._h, grid._h, pyr_a._h, pyr_b._h, int(psz), C.c_void_p(stream or 0)))
         return self
-
-    def dense(self, out=None, on_device=False):
-        """The densified (H, W, 2) float32 field. on_device: `out` is a device pointer that receives it."""
-        if on_device:
-            check(_lib.load().ictr_flowdensify_result(self._h, C.c_void_p(out), 1))
-            return out
-        if out is None:
-            out = np.empty((self.h, self.w, 2), np.float32)
-        check(_lib.load().ictr_flowdensify_result(self._h, out.ctypes.data_as(C.c_void_p), 0))
-        return out
-
-    def device_ptr(self):
-        return int(_lib.load().ictr_flowdensify_device_ptr(self._h) or 0)
-
-    def stage(self, name):
-        """One (H, W) float32 plane of the last run: a name of DZ_STAGES."""
-        out = np.empty((self.h, self.w), np.float32)
-        check(_lib.load().ictr_flowdensify_read_stage(self._h, DZ_STAGES.index(name), fp(out)))
-        return out
-
-    def set_timing(self, on=True):
-        check(_lib.load().ictr_flowdensify_set_timing(self._h, int(bool(on))))
 
     def kernel_ms(self):
         """k_densify of the last run in ms; 0 when timing was off."""
         ms = np.zeros(1, np.float32)
-        check(_lib.load().ictr_flowdensify_get_kernel_ms(self._h, fp(ms)))
+        check(self._c("get_kernel_ms")(self._h, fp(ms)))
         return float(ms[0])
 
 
@@ -654,13 +664,7 @@ class FlowGrid:
 
     def dense(self, out=None, on_device=False):
         """The (H, W, 2) float32 field of dense_flow. on_device: `out` is a device pointer that receives it."""
-        if on_device:
-            check(_lib.load().ictr_flowgrid_dense(self._h, C.c_void_p(out), 1))
-            return out
-        if out is None:
-            out = np.empty((self.h, self.w, 2), np.float32)
-        check(_lib.load().ictr_flowgrid_dense(self._h, out.ctypes.data_as(C.c_void_p), 0))
-        return out
+        return _dense_out(_lib.load().ictr_flowgrid_dense, self._h, self.w, self.h, out, on_device)
 
 
 class PointTracker:

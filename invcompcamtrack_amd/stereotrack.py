@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import FIELD_FLOW, FIELD_GRID, FIELD_PLANE, check  # FIELD_*: include/ictr.h ICTR_FIELD_*
 
 __all__ = ["stereo_track_window_host", "stereo_track_window", "StereoTrackWindow", "StereoPointTracker", "field", "TESTS",
            "FIELD_PLANE", "FIELD_FLOW", "FIELD_GRID"]
@@ -37,8 +37,6 @@ __all__ = ["stereo_track_window_host", "stereo_track_window", "StereoTrackWindow
 # bit 6, the tests of the later frames that compare the same pair of positions (left against left-through-right-and-back).
 TESTS = ("range", "ratio rf/rf_verif_d", "ratio lf/lf_verif_d", "ratio l/l_verif_f", "ratio r/r_verif_f",
          "abs rf/rf_verif_d", "abs lf/lf_verif_d", "abs l/l_verif_f", "abs r/r_verif_f")
-
-FIELD_PLANE, FIELD_FLOW, FIELD_GRID = 0, 1, 2  # include/ictr.h ICTR_FIELD_*
 
 
 def _gather(xy, du, dv=None):
@@ -181,28 +179,19 @@ def _exact_f32(a):
 
 def _descriptor(f, stereo, w, h):
     """-> (_lib.Field, what must stay alive until the step has run)"""
-    from .patchflow import FlowDensifier, FlowGrid, FlowRefiner
+    from .patchflow import FlowDensifier, FlowRefiner, _device_source
     f = f if isinstance(f, field) else field(f)
     d = _lib.Field(sign=f.sign, x_only=int(stereo))
-    data = f.data
-    if isinstance(data, FlowGrid):
-        d.kind, d.data, keep = FIELD_GRID, data._h.value, data
-    elif isinstance(data, (FlowRefiner, FlowDensifier)):  # its result buffer, read when the step runs (behind its run)
-        if (data.h, data.w) != (h, w):
-            raise ValueError(f"a {type(data).__name__} of {data.w} x {data.h} in a window of {w} x {h}")
-        d.kind, d.on_device, d.data, keep = FIELD_FLOW, 1, data.device_ptr(), data
-    else:
-        on_device = hasattr(data, "data_ptr")
-        if on_device:
-            if str(data.dtype) != "torch.float32" or not data.is_contiguous() or not data.is_cuda:
-                raise TypeError("a device field is a contiguous float32 tensor on the GPU")
-            shape, ptr, keep = tuple(data.shape), data.data_ptr(), data
-        else:
-            keep = _exact_f32(data)
-            shape, ptr = keep.shape, keep.ctypes.data
-        if shape not in ((h, w), (h, w, 2)):
-            raise ValueError(f"a field is ({h}, {w}) or ({h}, {w}, 2), not {shape}")
-        d.kind, d.on_device, d.data = (FIELD_PLANE if len(shape) == 2 else FIELD_FLOW), int(on_device), ptr
+    # a grid, a stage's result buffer (read when the step runs, behind its run) or a tensor; else a host array
+    dev = _device_source(f.data, w, h, (FlowRefiner, FlowDensifier))
+    if dev is not None:
+        d.kind, d.data, keep, _ = dev
+        d.on_device = int(d.kind != FIELD_GRID)
+        return d, keep
+    keep = _exact_f32(f.data)
+    if keep.shape not in ((h, w), (h, w, 2)):
+        raise ValueError(f"a field is ({h}, {w}) or ({h}, {w}, 2), not {keep.shape}")
+    d.kind, d.data = (FIELD_PLANE if keep.ndim == 2 else FIELD_FLOW), keep.ctypes.data
     return d, keep
 
 
@@ -325,34 +314,18 @@ class StereoPointTracker:
         self._pyr = [None, None]  # (left, right) of the previous frame and of the one before, reused in turn
         self._sets = [None, None]
 
-    def _grid_set(self, k):
-        from .patchflow import FlowGrid
+    def _set(self, cache, k, make):
+        """Frame k's six objects of one kind, by name: new ones when the grids are kept, else one of the two sets of
+        `cache`, reused in turn."""
         names = ("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")
         if self.keep_grids:
-            return {n: FlowGrid(self.w, self.h, self.step) for n in names}
-        if self._sets[k & 1] is None:
-            self._sets[k & 1] = {n: FlowGrid(self.w, self.h, self.step) for n in names}
-        return self._sets[k & 1]
-
-    def _refiner_set(self, k):
-        from .patchflow import FlowRefiner
-        names = ("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")
-        if self.keep_grids:
-            return {n: FlowRefiner(self.w, self.h, **self.refine) for n in names}
-        if self._rsets[k & 1] is None:
-            self._rsets[k & 1] = {n: FlowRefiner(self.w, self.h, **self.refine) for n in names}
-        return self._rsets[k & 1]
-
-    def _densifier_set(self, k):
-        from .patchflow import FlowDensifier
-        names = ("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")
-        if self.keep_grids:
-            return {n: FlowDensifier(self.w, self.h, **self.densify) for n in names}
-        if self._dsets[k & 1] is None:
-            self._dsets[k & 1] = {n: FlowDensifier(self.w, self.h, **self.densify) for n in names}
-        return self._dsets[k & 1]
+            return {n: make() for n in names}
+        if cache[k & 1] is None:
+            cache[k & 1] = {n: make() for n in names}
+        return cache[k & 1]
 
     def push_frames(self, left, right):
+        from .patchflow import FlowDensifier, FlowGrid, FlowRefiner
         from .tracker import Pyramid
         k = self.nframes
         if k >= self.bsize:
@@ -369,50 +342,34 @@ class StereoPointTracker:
                 p.rebuild(im)
         pl, pr = slot
         kw = dict(psz=self.psz, lv_f=self.lv_f, maxiter=self.maxiter, eps=self.eps)
-        g = self._grid_set(k)
-        if self.disparity == "1d":
-            g["lr"].compute_x(pl, pr, **kw)
-            g["rl"].compute_x(pr, pl, **kw)
-        else:
-            g["lr"].compute(pl, pr, **kw)
-            g["rl"].compute(pr, pl, **kw)
-        f = g  # what the window reads: the grids, their densifiers, or the refiners of either
-        z = None
-        if self.densify is not None:
-            f = z = self._densifier_set(k)
-            z["lr"].run(g["lr"], pl, pr, self.psz)
-            z["rl"].run(g["rl"], pr, pl, self.psz)
-        if self.refine is not None:
-            src = f
-            f = self._refiner_set(k)
-            f["lr"].run(pl, pr, src["lr"], x_only=True)
-            f["rl"].run(pr, pl, src["rl"], x_only=True)
+        # the frame's fields (name, A, B, x_only): the stereo pair, then from the second frame on the four temporal ones
+        fields = [("lr", pl, pr, True), ("rl", pr, pl, True)]
+        if k:
+            ql, qr = self._pyr[(k - 1) & 1]
+            fields += [("l_fwd", ql, pl, False), ("l_bwd", pl, ql, False), ("r_fwd", qr, pr, False),
+                       ("r_bwd", pr, qr, False)]
+        g = self._set(self._sets, k, lambda: FlowGrid(self.w, self.h, self.step))
+        z = r = None  # made when the stereo group reaches them
+        for group in (fields[:2], fields[2:]):  # within each group: grid, then densify, then refine
+            for n, a, b, x_only in group:
+                (g[n].compute_x if x_only and self.disparity == "1d" else g[n].compute)(a, b, **kw)
+            if self.densify is not None:
+                z = z or self._set(self._dsets, k, lambda: FlowDensifier(self.w, self.h, **self.densify))
+                for n, a, b, _ in group:
+                    z[n].run(g[n], a, b, self.psz)
+            if self.refine is not None:
+                r = r or self._set(self._rsets, k, lambda: FlowRefiner(self.w, self.h, **self.refine))
+                for n, a, b, x_only in group:
+                    r[n].run(a, b, (z or g)[n], x_only=x_only)
+        f = r or z or g  # what the window reads: the grids, their densifiers, or the refiners of either
         if k == 0:
             self.win.open(f["lr"], f["rl"], self.xy0)
         else:
-            ql, qr = self._pyr[(k - 1) & 1]
-            g["l_fwd"].compute(ql, pl, **kw)
-            g["l_bwd"].compute(pl, ql, **kw)
-            g["r_fwd"].compute(qr, pr, **kw)
-            g["r_bwd"].compute(pr, qr, **kw)
-            if z is not None:
-                z["l_fwd"].run(g["l_fwd"], ql, pl, self.psz)
-                z["l_bwd"].run(g["l_bwd"], pl, ql, self.psz)
-                z["r_fwd"].run(g["r_fwd"], qr, pr, self.psz)
-                z["r_bwd"].run(g["r_bwd"], pr, qr, self.psz)
-            if self.refine is not None:
-                src = g if z is None else z
-                f["l_fwd"].run(ql, pl, src["l_fwd"])
-                f["l_bwd"].run(pl, ql, src["l_bwd"])
-                f["r_fwd"].run(qr, pr, src["r_fwd"])
-                f["r_bwd"].run(pr, qr, src["r_bwd"])
             self.win.advance(f["l_fwd"], f["l_bwd"], f["r_fwd"], f["r_bwd"], f["lr"], f["rl"])
         if self.keep_grids:
-            self.grids.append(g if k else {n: g[n] for n in ("lr", "rl")})
-            if self.refine is not None:
-                self.refiners.append(f if k else {n: f[n] for n in ("lr", "rl")})
-            if z is not None:
-                self.densifiers.append(z if k else {n: z[n] for n in ("lr", "rl")})
+            for kept, s in ((self.grids, g), (self.refiners, r), (self.densifiers, z)):
+                if s is not None:
+                    kept.append(s if k else {n: s[n] for n in ("lr", "rl")})
         self.nframes = k + 1
 
     def window(self):

@@ -215,6 +215,37 @@ def _same_sources(frame, r, f, want, stream):
     assert np.array_equal(_bits(pf.refine_flow(pa, pb, f, **r.params)), _bits(want))
 
 
+@pytest.mark.parametrize("w,h,step", ((4, 4, 1), (65, 5, 3), (67, 53, 4)))
+def test_one_dense_from_grid_launch_for_the_grid_and_the_refiner(w, h, step):
+    """The dense field of a grid is one kernel with one launcher behind FlowGrid.dense (to host, into device memory) and
+    behind a grid source of FlowRefiner.run (null stream, a stream of the test's own): the bits of the NumPy restatement
+    from all four. One partial wave; a wave and a lane; a partial last row group; 4 x 4 is the refiner's smallest."""
+    import ctypes as C
+
+    import frontend_np as FN
+    d, lost = FN.grid_nodes(w, h, step, 0.3, 11)
+    assert lost.any() and not lost.all()
+    g = pf.FlowGrid(w, h, step).set_nodes(d, lost)
+    ys, xs = np.mgrid[0:h, 0:w]
+    want = _bits(FN.field_at(FN.fill(d, lost), step, w, h, xs.ravel(), ys.ravel()).reshape(h, w, 2))
+    img = np.zeros((h, w), np.float32)
+    pa, pb = ic.Pyramid(img, 0, PSZ, False), ic.Pyramid(img, 0, PSZ, False)
+    assert np.array_equal(_bits(g.dense()), want)
+    sink = pf.FlowRefiner(w, h, n_outer=0).run(pa, pb, np.zeros((h, w, 2), np.float32))
+    sink.dense()  # waited for; its result buffer is device memory of the field's size
+    g.dense(out=sink.device_ptr(), on_device=True)
+    assert np.array_equal(_bits(sink.dense()), want)
+    r = pf.FlowRefiner(w, h, n_outer=0)
+    assert np.array_equal(_bits(r.run(pa, pb, g).dense()), want)
+    hip, stream = _hip_runtime(), C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0 and stream.value
+    try:
+        r.run(pa, pb, np.zeros((h, w, 2), np.float32))  # the result buffer no longer holds the field
+        assert np.array_equal(_bits(r.run(pa, pb, g, stream=stream.value).dense()), want)
+    finally:
+        assert hip.hipStreamDestroy(stream) == 0
+
+
 # ---------------------------------------------------------------- dependence cone
 @pytest.mark.parametrize("frame,at", (("farxy-320x64", (160, 32)), ("farxy-64x320", (32, 160))))
 @pytest.mark.parametrize("run", FC.RUNS[:2])
