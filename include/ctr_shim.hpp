@@ -560,4 +560,44 @@ class FlowDensifyClass {
   ictr_flowdensify *h_;
 };
 
+// Coarse-to-fine dense flow: search, densification and optional refinement per pyramid level (ictr_c2fflow_* in
+// include/ictr.h). Run enqueues, Result and ReadLevel wait. Field() is level 0's field on the device, for
+// FlowRefineClass::Run and the stereo track window.
+class CoarseFlowClass {
+ public:
+  CoarseFlowClass(int w, int h, int lv_f, int step = 4, int psz = 8) : h_(nullptr) {
+    check(ictr_c2fflow_create(&h_, w, h, lv_f, step, psz), "CoarseFlowClass");
+  }
+  ~CoarseFlowClass() { ictr_c2fflow_destroy(h_); }
+  CoarseFlowClass(const CoarseFlowClass &) = delete;
+  CoarseFlowClass &operator=(const CoarseFlowClass &) = delete;
+  void SetParams(int maxiter = 10, float eps = 0.01f, float minerr = 2.0f, int power = 1) {
+    check(ictr_c2fflow_set_params(h_, maxiter, eps, minerr, power), "SetParams");
+  }
+  void SetRefine(bool on, float alpha = 16.0f, float gamma = 13.0f, float delta = 4.5f, int n_outer = 8, int n_sor = 5,
+                 float omega = 1.6f) {
+    check(ictr_c2fflow_set_refine(h_, on ? 1 : 0, alpha, gamma, delta, n_outer, n_sor, omega), "SetRefine");
+  }
+  // a, b: pyramids of the object's size with levels 0 .. lv_f, padded by at least psz, a with gradient planes
+  void Run(const Pyramid &a, const Pyramid &b, void *hip_stream = nullptr) {
+    check(ictr_c2fflow_run(h_, a.handle(), b.handle(), hip_stream), "Run");
+  }
+  // out [h][w][2], in host memory or (on_device) device memory
+  void Result(float *out, bool on_device = false) { check(ictr_c2fflow_result(h_, out, on_device ? 1 : 0), "Result"); }
+  ictr_field Field(bool x_only = false) const {
+    ictr_field f = {ICTR_FIELD_FLOW, 1, 1, x_only ? 1 : 0, ictr_c2fflow_device_ptr(h_)};
+    return f;
+  }
+  void LevelDims(int level, int *w, int *h, int *nx, int *ny) const {
+    check(ictr_c2fflow_level_dims(h_, level, w, h, nx, ny), "LevelDims");
+  }
+  // field [h_l][w_l][2], d [ny][nx][2] after the fill, status [ny][nx]; any pointer may be NULL
+  void ReadLevel(int level, float *field, float *d, unsigned char *status) {
+    check(ictr_c2fflow_read_level(h_, level, field, d, status), "ReadLevel");
+  }
+
+ private:
+  ictr_c2fflow *h_;
+};
+
 }  // namespace CTR

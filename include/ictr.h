@@ -955,6 +955,48 @@ int ictr_flowdensify_get_kernel_ms(ictr_flowdensify *z, float *ms);
 #define ICTR_FLOWDENSIFY_STAGES 2
 int ictr_flowdensify_read_stage(ictr_flowdensify *z, int which, float *out);
 
+/* ---------------------------------------------------------------- coarse-to-fine dense flow (ictr_c2fflow.hip)
+ * The dense field A -> B built level by level (DESIGN.md §4 "Coarse-to-fine dense flow"): for l = lv_f .. 0 a grid of
+ * nodes at step / 2 + k step of the level's own size is searched at that level alone, every node started from twice the
+ * coarser level's dense field at (min(X >> 1, w' - 1), min(Y >> 1, h' - 1)) ((0, 0) at lv_f); the node displacements are
+ * filled (the flow grid's fill), densified (ictr_flowdensify's rule) and, when switched on, refined (ictr_flowrefine's
+ * rule) on the level's planes. The result is level 0's field. The rule is patchflow.c2f_flow_host's, in f32.
+ * Status of a node: 0 lost (its start is out of view, or not finite: no vote, filled from its neighbours), 1 tracked,
+ * 2 held by the conditioning test, 3 held because it left the view while iterating, 4 held because it ended further than
+ * psz from its start (or not finite). A held node keeps its start's bits and votes. */
+typedef struct ictr_c2fflow ictr_c2fflow;
+#define ICTR_C2F_LOST 0
+#define ICTR_C2F_TRACKED 1
+#define ICTR_C2F_HELD_COND 2
+#define ICTR_C2F_HELD_VIEW 3
+#define ICTR_C2F_HELD_FAR 4
+/* w x h frames, levels lv_f .. 0 (0 <= lv_f <= 15), step >= 1, psz 1 .. 32. Refused with a message: a level smaller than
+ * 2 x 2, a level without a node (step / 2 >= its width or height). */
+int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, int step, int psz);
+void ictr_c2fflow_destroy(ictr_c2fflow *c);
+/* defaults 10, 0.01, 2.0, 1: the search's iterations per level and stop (|step| < eps), the densifier's parameters */
+int ictr_c2fflow_set_params(ictr_c2fflow *c, int maxiter, float eps, float minerr, int power);
+/* on != 0: refine every level with these parameters (ictr_flowrefine_set_params' rules; every level must be at least
+ * 4 x 4, refused otherwise). Default off. */
+int ictr_c2fflow_set_refine(ictr_c2fflow *c, int on, float alpha, float gamma, float delta, int n_outer, int n_sor,
+                            float omega);
+/* Both pyramids: levels 0 .. lv_f of the object's level sizes (refused otherwise), padding >= psz, the first with
+ * gradient planes. A step and psz whose node table does not fit the densifier's LDS are refused (ictr_flowdensify_run). Everything is enqueued on hip_stream (NULL: the null stream); the call does not wait. */
+int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, void *hip_stream);
+/* waits for the last run and copies level 0's field [h][w][2] to out (a device pointer when on_device != 0) */
+int ictr_c2fflow_result(ictr_c2fflow *c, float *out, int on_device);
+/* the result buffer on the device (a device ICTR_FIELD_FLOW), valid behind the run's stream */
+const float *ictr_c2fflow_device_ptr(const ictr_c2fflow *c);
+/* size and node counts of a level; any pointer may be NULL */
+int ictr_c2fflow_level_dims(const ictr_c2fflow *c, int level, int *w, int *h, int *nx, int *ny);
+/* of the last run (waits for it): the level's field [h_l][w_l][2], its node displacements after the fill [ny][nx][2] and
+ * the status bytes [ny][nx]; any pointer may be NULL */
+int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field, float *d, unsigned char *status);
+/* HIP events around the stages of the next runs; ms[3 (lv_f + 1)] of the last run (waits for it): per level from 0 the
+ * search (k_c2f_level and the fill), the densification and the refinement, zeros when timing was off */
+int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on);
+int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

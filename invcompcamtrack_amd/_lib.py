@@ -347,6 +347,17 @@ SIGNATURES = {
     "ictr_flowdensify_set_timing": (C.c_int, [VP, C.c_int]),
     "ictr_flowdensify_get_kernel_ms": (C.c_int, [VP, FP]),
     "ictr_flowdensify_read_stage": (C.c_int, [VP, C.c_int, FP]),
+    "ictr_c2fflow_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ictr_c2fflow_destroy": (None, [VP]),
+    "ictr_c2fflow_set_params": (C.c_int, [VP, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "ictr_c2fflow_set_refine": (C.c_int, [VP, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float]),
+    "ictr_c2fflow_run": (C.c_int, [VP, VP, VP, VP]),
+    "ictr_c2fflow_result": (C.c_int, [VP, VP, C.c_int]),
+    "ictr_c2fflow_device_ptr": (VP, [VP]),
+    "ictr_c2fflow_level_dims": (C.c_int, [VP, C.c_int, IP, IP, IP, IP]),
+    "ictr_c2fflow_read_level": (C.c_int, [VP, C.c_int, FP, FP, U8P]),
+    "ictr_c2fflow_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_get_kernel_ms": (C.c_int, [VP, FP]),
 }
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {

@@ -1,0 +1,415 @@
+// ictr_c2fflow.hip -- coarse-to-fine dense flow (DESIGN.md §4 "Coarse-to-fine dense flow"): per pyramid level a patch
+// search on a grid of the level's own size, started from the coarser level's dense field, then the flow grid's fill, the
+// densification and (optionally) the variational refinement on the level's planes. The rule is build-defined; its
+// statement of record is patchflow.c2f_flow_host (NumPy, f64). This file is the same rule in f32 with one fixed operation
+// order, restated in NumPy f32 by tests/c2fflow_f32.py.
+//
+// k_c2f_level<NPL, WPP>, one launch per level: a wave (two for patches of more than 4 pixels per lane) per node, in
+// k_patchflow's forms and two-wave exchange. What FlowGrid.compute spends three launches on is one here: the node position
+// follows from the node index, the start is ONE 8-byte load of the coarser field (times 2: exact), the template and the H
+// sums, the iterations at this level alone, the hold rules, and the node's displacement, lost byte and status byte
+// written directly. The per-pixel expressions and the sum shape are k_patchflow's (ictr_patchflow_dev.h; lane-serial
+// slots, the DPP tree, wave order): a node's step is the same f32 value as a k_patchflow step at the same position.
+// At the coarse levels a launch has a few waves per SIMD: an iteration is a latency chain per wave, so all of a lane's
+// loads of an iteration are issued before the first is consumed. f32 throughout, plain vector loads and stores, no atomics.
+#include <math.h>
+#include <string.h>
+
+#include <memory>
+#include <vector>
+
+#include "ictr_dev.h"
+#include "ictr_launch.h"
+#include "ictr_devfn.h"
+#include "ictr_patchflow_dev.h"
+
+namespace ictr {
+
+struct C2fArgs {
+  const float *a, *ax, *ay, *b;  // this level: frame A image + gradients, frame B image (padded planes)
+  int sw, shift;                 // row stride; (pad - P) * (sw + 1), as PFLevel
+  float swo, sho;                // the level's unpadded size
+  int nx, K, step;               // nodes per row, nodes, node spacing
+  const float2 *coarse;          // the coarser level's dense field [ch][cw], NULL at the coarsest level
+  int cw, ch;
+  int P, maxiter;
+  float eps2, min_det, far2;     // stop when |dp|^2 < eps2; conditioning; (float)(P * P)
+  float *d;                      // [K][2] raw node displacements (the fill's input)
+  unsigned char *lost, *status;  // [K], [K]
+};
+
+template <int NPL, int WPP>
+__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
+  constexpr int PPB = kWaves / WPP;  // nodes per workgroup
+  __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wsub = wave % WPP;
+  const int k = blockIdx.x * PPB + wave / WPP;
+  const bool valid = k < a.K;
+  if (WPP == 1 && !valid) return;
+  const int P = a.P, n = P * P;
+  const int kk = valid ? k : 0;
+  const int nj = kk / a.nx, ni = kk - nj * a.nx;
+  const int X = a.step / 2 + ni * a.step, Y = a.step / 2 + nj * a.step;  // inside the level: the template needs no test
+  const float xl = (float)X, yl = (float)Y;
+  float ix = 0.0f, iy = 0.0f;
+  if (a.coarse) {
+    const float2 c = a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)];
+    ix = 2.0f * c.x;
+    iy = 2.0f * c.y;
+  }
+  const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
+  int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
+  bool ok = st == ICTR_C2F_TRACKED;
+  float px = ix, py = iy;
+  // sum over the node's WPP waves of three per-wave totals (all waves of the node get the same bits)
+  auto patch_sum3 = [&](float &u, float &v, float &w) {
+    u = pf_wave_sum(u);
+    v = pf_wave_sum(v);
+    w = pf_wave_sum(w);
+    if constexpr (WPP > 1) {
+      __syncthreads();  // (the previous reduction's partials have been read)
+      if (lane == 0) {
+        sSum[wave][0] = u;
+        sSum[wave][1] = v;
+        sSum[wave][2] = w;
+      }
+      __syncthreads();
+      const int w0 = wave - wsub;
+      u = v = w = 0.0f;
+#pragma unroll
+      for (int q = 0; q < WPP; ++q) {
+        u += sSum[w0 + q][0];
+        v += sSum[w0 + q][1];
+        w += sSum[w0 + q][2];
+      }
+    }
+  };
+  // One wave per node leaves at the first decision against it; two waves per node share barriers: every node of the
+  // workgroup runs every iteration slot, and one that is lost, held or converged only stops updating.
+  do {
+    if (WPP == 1 && !ok) break;
+    const PFTaps ta = pf_taps(xl, yl, P, a.sw, a.shift);
+    gconst_f32 pa = (gconst_f32)a.a, pax = (gconst_f32)a.ax, pay = (gconst_f32)a.ay, pb = (gconst_f32)a.b;
+    int off[NPL];
+    float T[NPL], Gx[NPL], Gy[NPL];
+    float hxx = 0.0f, hxy = 0.0f, hyy = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      const int q = wsub * 64 + lane + 64 * WPP * i;
+      const bool in = q < n;
+      off[i] = in ? (q / P) * a.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
+      const int idx = ta.base + off[i];
+      const float t = pf_fetch(pa, idx, a.sw, ta), gx = pf_fetch(pax, idx, a.sw, ta), gy = pf_fetch(pay, idx, a.sw, ta);
+      T[i] = in ? t : 0.0f;
+      Gx[i] = in ? gx : 0.0f;
+      Gy[i] = in ? gy : 0.0f;
+      hxx += Gx[i] * Gx[i];
+      hxy += Gx[i] * Gy[i];
+      hyy += Gy[i] * Gy[i];
+    }
+    patch_sum3(hxx, hxy, hyy);
+    const float det = hxx * hyy - hxy * hxy;
+    const float tr = hxx + hyy;
+    if (ok && (!(det > a.min_det * tr * tr) || !(tr > 0.0f))) {  // textureless or 1-D structure
+      ok = false;
+      st = ICTR_C2F_HELD_COND;
+    }
+    if (WPP == 1 && !ok) break;
+    const float idet = 1.0f / det;
+    bool run = ok;  // this node still iterates
+    for (int it = 0; it < a.maxiter; ++it) {
+      if (WPP == 1 && !run) break;
+      const float cx = xl + px, cy = yl + py;
+      if (run && !pf_in_view(cx, cy, a.swo, a.sho)) {
+        ok = false;
+        run = false;
+        st = ICTR_C2F_HELD_VIEW;
+        if (WPP == 1) break;
+      }
+      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, a.sw, a.shift);  // (1,1): a harmless in-plane window
+      float bx = 0.0f, by = 0.0f, dummy = 0.0f;
+      PFWin w[NPL];
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) w[i] = pf_load(pb, tb.base + off[i], a.sw);  // all in flight before the first use
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) {
+        float r = T[i] - pf_blend(w[i], tb);
+        r = (wsub * 64 + lane + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+        bx += Gx[i] * r;
+        by += Gy[i] * r;
+      }
+      patch_sum3(bx, by, dummy);
+      if (run) {
+        const float dx = (hyy * bx - hxy * by) * idet;
+        const float dy = (hxx * by - hxy * bx) * idet;
+        px += dx;
+        py += dy;
+        if (dx * dx + dy * dy < a.eps2) run = false;
+      }
+    }
+    if (ok) {  // a runaway patch: further than P from its start, or not finite (the test is written positively)
+      const float dx = px - ix, dy = py - iy;
+      if (!(dx * dx + dy * dy <= a.far2)) {
+        ok = false;
+        st = ICTR_C2F_HELD_FAR;
+      }
+    }
+  } while (0);
+  if (lane == 0 && wsub == 0 && valid) {
+    const float nanv = __int_as_float(0x7fc00000);
+    const bool held = st >= ICTR_C2F_HELD_COND;
+    a.d[2 * k] = st == ICTR_C2F_LOST ? nanv : held ? ix : px;  // a held node: its start's bits
+    a.d[2 * k + 1] = st == ICTR_C2F_LOST ? nanv : held ? iy : py;
+    a.lost[k] = st == ICTR_C2F_LOST ? 1 : 0;
+    a.status[k] = (unsigned char)st;
+  }
+}
+
+// the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
+static void launch_c2f_level(const C2fArgs &a, hipStream_t s) {
+  const int npl = (a.P * a.P + 63) / 64;
+  const dim3 blk(kBlock);
+  if (npl > 4) {
+    hipLaunchKernelGGL((k_c2f_level<8, 2>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
+    return;
+  }
+  const dim3 g((a.K + kWaves - 1) / kWaves);
+  if (npl <= 1)
+    hipLaunchKernelGGL((k_c2f_level<1, 1>), g, blk, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_c2f_level<4, 1>), g, blk, 0, s, a);
+}
+
+}  // namespace ictr
+
+using namespace ictr;
+
+// ---------------------------------------------------------------- C-ABI
+namespace {
+struct GridDel {
+  void operator()(ictr_flowgrid *p) const { ictr_flowgrid_destroy(p); }
+};
+struct DensDel {
+  void operator()(ictr_flowdensify *p) const { ictr_flowdensify_destroy(p); }
+};
+struct RefDel {
+  void operator()(ictr_flowrefine *p) const { ictr_flowrefine_destroy(p); }
+};
+struct C2fLevel {
+  int w = 0, h = 0, nx = 0, ny = 0;
+  unsigned char *status = nullptr;  // [ny][nx], in the object's status block
+  std::unique_ptr<ictr_flowgrid, GridDel> grid;
+  std::unique_ptr<ictr_flowdensify, DensDel> dens;
+  std::unique_ptr<ictr_flowrefine, RefDel> ref;  // made when the refinement is switched on
+  Event ev[4];                                    // before the search, after the fill, the densifier, the refiner
+};
+}  // namespace
+
+struct ictr_c2fflow {
+  int w = 0, h = 0, lv_f = 0, step = 0, psz = 0;
+  int maxiter = 10;
+  float eps = 0.01f;
+  int refine = 0;  // refiners exist for every level and hold their parameters
+  int timing = 0, timed = 0, ran = 0, ran_refined = 0;
+  std::vector<C2fLevel> lv;  // [lv_f + 1]
+  DevBuf<unsigned char> status;
+  Event done;  // behind the last run
+};
+
+// the field a level hands on: the refiner's when the run refined, else the densifier's
+static const float *c2f_field(const C2fLevel &L, int refined) {
+  return refined ? ictr_flowrefine_device_ptr(L.ref.get()) : ictr_flowdensify_device_ptr(L.dens.get());
+}
+
+extern "C" void ictr_c2fflow_destroy(ictr_c2fflow *c) {
+  if (c && c->ran) (void)hipEventSynchronize(c->done.get());  // before any buffer of a run in flight is released
+  delete c;
+}
+extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, int step, int psz) {
+  if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f > 15 || step < 1)
+    return fail(ICTR_ERR_INVALID, "c2fflow: bad arguments (w, h, step >= 1, 0 <= lv_f <= 15)");
+  if (psz < 1 || psz > 32) return fail(ICTR_ERR_INVALID, "c2fflow: psz is %d (1 .. 32)", psz);
+  if (int rc = need_device()) return rc;
+  auto c = std::make_unique<ictr_c2fflow>();
+  c->w = w;
+  c->h = h;
+  c->lv_f = lv_f;
+  c->step = step;
+  c->psz = psz;
+  c->lv.resize((size_t)lv_f + 1);
+  size_t nodes = 0;
+  for (int l = 0; l <= lv_f; ++l) {
+    C2fLevel &L = c->lv[l];
+    pyramid_level_size(w, h, l, &L.w, &L.h);
+    if (L.w < 2 || L.h < 2) return fail(ICTR_ERR_INVALID, "c2fflow: level %d is %d x %d, smaller than 2 px", l, L.w, L.h);
+    if (step / 2 >= L.w || step / 2 >= L.h)
+      return fail(ICTR_ERR_INVALID, "c2fflow: level %d (%d x %d) has no node at step %d", l, L.w, L.h, step);
+    ictr_flowgrid *g = nullptr;
+    if (int rc = ictr_flowgrid_create(&g, L.w, L.h, step)) return rc;
+    L.grid.reset(g);
+    if (int rc = ictr_flowgrid_dims(g, &L.nx, &L.ny)) return rc;
+    ictr_flowdensify *z = nullptr;
+    if (int rc = ictr_flowdensify_create(&z, L.w, L.h)) return rc;
+    L.dens.reset(z);
+    for (Event &e : L.ev)
+      if (int rc = e.create()) return rc;
+    nodes += (size_t)L.nx * L.ny;
+  }
+  if (int rc = c->status.alloc(nodes, true)) return rc;
+  unsigned char *cur = c->status.get();
+  for (C2fLevel &L : c->lv) {
+    L.status = cur;
+    cur += (size_t)L.nx * L.ny;
+  }
+  if (int rc = c->done.create(hipEventDisableTiming)) return rc;
+  *out = c.release();
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_set_params(ictr_c2fflow *c, int maxiter, float eps, float minerr, int power) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (maxiter < 0 || !isfinite(eps) || eps < 0.0f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_set_params: maxiter >= 0, finite eps >= 0");
+  for (C2fLevel &L : c->lv)
+    if (int rc = ictr_flowdensify_set_params(L.dens.get(), minerr, power)) return rc;
+  c->maxiter = maxiter;
+  c->eps = eps;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_set_refine(ictr_c2fflow *c, int on, float alpha, float gamma, float delta, int n_outer,
+                                       int n_sor, float omega) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (!on) {
+    c->refine = 0;
+    return ICTR_OK;
+  }
+  for (size_t l = 0; l < c->lv.size(); ++l)
+    if (c->lv[l].w < 4 || c->lv[l].h < 4)
+      return fail(ICTR_ERR_INVALID, "c2fflow_set_refine: level %d is %d x %d, the refinement needs 4 x 4", (int)l, c->lv[l].w,
+                  c->lv[l].h);
+  for (C2fLevel &L : c->lv) {
+    if (!L.ref) {
+      ictr_flowrefine *r = nullptr;
+      if (int rc = ictr_flowrefine_create(&r, L.w, L.h)) return rc;
+      L.ref.reset(r);
+    }
+    if (int rc = ictr_flowrefine_set_params(L.ref.get(), alpha, gamma, delta, n_outer, n_sor, omega)) return rc;
+  }
+  c->refine = 1;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  c->timing = on ? 1 : 0;
+  return ICTR_OK;
+}
+
+extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, void *hip_stream) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  PFArgs pf;  // the argument checks and the level table of a patch search: pads, gradient planes, equal sizes
+  if (int rc = patchflow_args(pyr_a, pyr_b, c->psz, c->lv_f, 0, c->maxiter, c->eps, &pf)) return rc;
+  for (int l = 0; l <= c->lv_f; ++l)
+    if ((int)pf.lv[l].swo != c->lv[l].w || (int)pf.lv[l].sho != c->lv[l].h)
+      return fail(ICTR_ERR_INVALID, "c2fflow_run: level %d of the pyramids is %d x %d, of the object %d x %d", l,
+                  (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int refined = c->refine;
+  c->timed = c->timing;
+  for (int l = c->lv_f; l >= 0; --l) {
+    C2fLevel &L = c->lv[l];
+    C2fArgs a;
+    memset(&a, 0, sizeof(a));
+    a.a = pf.lv[l].a, a.ax = pf.lv[l].ax, a.ay = pf.lv[l].ay, a.b = pf.lv[l].b;
+    a.sw = pf.lv[l].sw;
+    a.shift = pf.lv[l].shift;
+    a.swo = pf.lv[l].swo;
+    a.sho = pf.lv[l].sho;
+    a.nx = L.nx;
+    a.K = L.nx * L.ny;
+    a.step = c->step;
+    if (l < c->lv_f) {
+      a.coarse = reinterpret_cast<const float2 *>(c2f_field(c->lv[l + 1], refined));
+      a.cw = c->lv[l + 1].w;
+      a.ch = c->lv[l + 1].h;
+    }
+    a.P = c->psz;
+    a.maxiter = c->maxiter;
+    a.eps2 = pf.eps2;
+    a.min_det = pf.min_det;
+    a.far2 = (float)(c->psz * c->psz);
+    if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
+    a.status = L.status;
+    if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
+    launch_c2f_level(a, s);
+    if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
+    if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
+    if (int rc = ictr_flowdensify_run_level_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l, s)) return rc;
+    if (c->timed) HIPCHK(hipEventRecord(L.ev[2].get(), s));
+    if (refined) {
+      ictr_field f;
+      memset(&f, 0, sizeof(f));
+      f.kind = ICTR_FIELD_FLOW;
+      f.sign = 1;
+      f.on_device = 1;
+      f.data = ictr_flowdensify_device_ptr(L.dens.get());
+      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, &f, 0, l, s)) return rc;
+    }
+    if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->done.get(), s));
+  c->ran = 1;
+  c->ran_refined = refined;
+  return ICTR_OK;
+}
+
+static int c2f_wait(ictr_c2fflow *c, const char *what) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (!c->ran) return fail(ICTR_ERR_STATE, "%s: no run yet", what);
+  HIPCHK(hipEventSynchronize(c->done.get()));
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_result(ictr_c2fflow *c, float *out, int on_device) {
+  if (int rc = c2f_wait(c, "c2fflow_result")) return rc;
+  if (!out) return fail(ICTR_ERR_INVALID, "c2fflow_result: out is NULL");
+  HIPCHK(hipMemcpy(out, c2f_field(c->lv[0], c->ran_refined), sizeof(float) * 2 * (size_t)c->w * c->h,
+                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" const float *ictr_c2fflow_device_ptr(const ictr_c2fflow *c) {
+  if (!c) return nullptr;
+  return c2f_field(c->lv[0], c->ran ? c->ran_refined : c->refine);
+}
+extern "C" int ictr_c2fflow_level_dims(const ictr_c2fflow *c, int level, int *w, int *h, int *nx, int *ny) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (level < 0 || level > c->lv_f) return fail(ICTR_ERR_INVALID, "c2fflow_level_dims: level is %d (0 .. %d)", level, c->lv_f);
+  const C2fLevel &L = c->lv[level];
+  if (w) *w = L.w;
+  if (h) *h = L.h;
+  if (nx) *nx = L.nx;
+  if (ny) *ny = L.ny;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field, float *d, unsigned char *status) {
+  if (int rc = c2f_wait(c, "c2fflow_read_level")) return rc;
+  if (level < 0 || level > c->lv_f) return fail(ICTR_ERR_INVALID, "c2fflow_read_level: level is %d (0 .. %d)", level, c->lv_f);
+  const C2fLevel &L = c->lv[level];
+  const size_t K = (size_t)L.nx * L.ny;
+  if (field)
+    HIPCHK(hipMemcpy(field, c2f_field(L, c->ran_refined), sizeof(float) * 2 * (size_t)L.w * L.h, hipMemcpyDeviceToHost));
+  if (d)
+    if (int rc = ictr_flowgrid_nodes(L.grid.get(), d, nullptr)) return rc;
+  if (status) HIPCHK(hipMemcpy(status, L.status, K, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {
+  if (int rc = c2f_wait(c, "c2fflow_get_kernel_ms")) return rc;
+  if (!ms) return fail(ICTR_ERR_INVALID, "c2fflow_get_kernel_ms: ms is NULL");
+  for (int l = 0; l <= c->lv_f; ++l)
+    for (int k = 0; k < 3; ++k) {
+      ms[3 * l + k] = 0.0f;
+      if (c->timed) HIPCHK(hipEventElapsedTime(&ms[3 * l + k], c->lv[l].ev[k].get(), c->lv[l].ev[k + 1].get()));
+    }
+  return ICTR_OK;
+}

@@ -155,6 +155,11 @@ extern "C" int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on) {
 
 extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
                                     const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
+  return ictr_flowdensify_run_level_(z, grid, pyr_a, pyr_b, psz, 0, hip_stream);
+}
+// the run on level `level` of the pyramids (grid and object of that level's size)
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                           const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream) {
   if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
   if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
   DzArgs a;
@@ -164,7 +169,7 @@ extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *gr
     return fail(ICTR_ERR_INVALID, "flowdensify_run: the flow grid is %d x %d, the object %d x %d", a.g.w, a.g.h, z->w, z->h);
   ictr_level0 l[2];
   for (int k = 0; k < 2; ++k) {
-    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowdensify_run", &l[k])) return rc;
+    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowdensify_run", &l[k], level)) return rc;
     if (l[k].w != z->w || l[k].h != z->h)
       return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is %d x %d, the object %d x %d", l[k].w, l[k].h, z->w, z->h);
   }

@@ -300,13 +300,18 @@ extern "C" int ictr_flowrefine_set_timing(ictr_flowrefine *r, int on) {
 
 extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                    const ictr_field *src, int x_only, void *hip_stream) {
+  return ictr_flowrefine_run_level_(r, pyr_a, pyr_b, src, x_only, 0, hip_stream);
+}
+// the run on level `level` of the pyramids (field and refiner of that level's size)
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
+                                          const ictr_field *src, int x_only, int level, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
   if (!src || !src->data) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field (or its data) is NULL");
   if (src->sign != 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field's sign is %d (+1)", src->sign);
   FrArgs a = fr_args(r, x_only);
   ictr_level0 l[2];
   for (int k = 0; k < 2; ++k) {
-    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowrefine_run", &l[k])) return rc;
+    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowrefine_run", &l[k], level)) return rc;
     if (l[k].w != r->w || l[k].h != r->h)
       return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
   }

@@ -524,6 +524,16 @@ static int fg_fill(ictr_flowgrid *g, hipStream_t s) {
   g->filled = 1;
   return ICTR_OK;
 }
+extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsigned char **lost) {
+  if (!g || !draw || !lost) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  *draw = g->draw;
+  *lost = g->lost;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream) {
+  if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
+  return fg_fill(g, (hipStream_t)hip_stream);
+}
 // nodes -> tracking (the 2-D launch or the 1-D one) -> d = out - pts -> fill
 static int fg_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f, int maxiter,
                       float eps, void *hip_stream, void (*launch)(const PFArgs &, hipStream_t)) {

@@ -271,6 +271,8 @@ static void level_size(int w, int h, int level, int *wl, int *hl) {
   *hl = h;
 }
 
+void ictr::pyramid_level_size(int w, int h, int level, int *wl, int *hl) { level_size(w, h, level, wl, hl); }
+
 static int pyramid_alloc(ictr_pyramid **out, int w, int h, int lv_f, int getgrad, int pad) {
   if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f > 15 || pad < 0 || getgrad < 0 || getgrad > 2)
     return fail(ICTR_ERR_INVALID, "pyramid: bad arguments");

@@ -22,18 +22,32 @@ struct ictr_pyramid_view {
   int getgrad;  // 1: the gradient planes exist (image-only pyramids of the tracker's on-the-fly path have none)
 };
 extern "C" int ictr_pyramid_view_(const ictr_pyramid *p, ictr_pyramid_view *v);  // ictr_host.hip
-// Level 0 of a pyramid as a kernel reads a frame: the plane at pixel (0, 0), inside the padding, and its row stride. The
-// one place that forms this address; `who` opens the message about a NULL or empty pyramid. Size checks are the caller's.
+// A level of a pyramid (level 0 unless the caller names another) as a kernel reads a frame: the plane at pixel (0, 0),
+// inside the padding, and its row stride. The one place that forms this address; `who` opens the message about a NULL or
+// empty pyramid, or one without the level. Size checks are the caller's.
 struct ictr_level0 {
   const float *img;
   int stride, w, h;
 };
-inline int ictr_pyramid_level0(const ictr_pyramid *p, const char *who, ictr_level0 *l) {
+inline int ictr_pyramid_level0(const ictr_pyramid *p, const char *who, ictr_level0 *l, int level = 0) {
   ictr_pyramid_view v;
   if (!p || ictr_pyramid_view_(p, &v) || v.nlev < 1) return ictr::fail(ICTR_ERR_INVALID, "%s: a pyramid is NULL", who);
-  *l = ictr_level0{v.img[0] + (size_t)v.pad * v.sw[0] + v.pad, v.sw[0], v.w[0], v.h[0]};
+  if (level < 0 || level >= v.nlev) return ictr::fail(ICTR_ERR_INVALID, "%s: a pyramid has no level %d", who, level);
+  *l = ictr_level0{v.img[level] + (size_t)v.pad * v.sw[level] + v.pad, v.sw[level], v.w[level], v.h[level]};
   return ICTR_OK;
 }
+// The stages that the coarse-to-fine flow (ictr_c2fflow.hip) runs per level on objects of the level's size: the node
+// buffers of a flow grid that its search kernel writes (raw displacements [K][2] and the lost bytes [K]) and the grid's fill
+// on a stream; the densifier's and the refiner's run reading level `level` of the pyramids (the public runs pass 0).
+struct ictr_flowgrid;
+struct ictr_flowdensify;
+struct ictr_flowrefine;
+extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsigned char **lost);  // ictr_frontend.hip
+extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream);  // ictr_frontend.hip
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                           const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream);
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
+                                          const ictr_field *src, int x_only, int level, void *hip_stream);
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);
@@ -91,6 +105,7 @@ int fail(int code, const char *fmt, ...);  // and HIPCHK(expr), which returns th
 int need_device();                          // ICTR_OK, or ICTR_ERR_NO_DEVICE with its message: there is no CPU fallback
 int env_int(const char *name, int dflt);    // integer value of an environment variable, dflt when unset
 int cu_count();                             // CUs of the calling thread's current device, queried once per device
+void pyramid_level_size(int w, int h, int level, int *wl, int *hl);  // the size of a pyramid's level (round-half-even halving)
 
 // the two RANSAC stages: trials per score workgroup from an environment variable, 16, 64 or (anything else) 32 ...
 inline int ran_tile_env(const char *name) {

@@ -27,7 +27,7 @@ __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "
            "last_form", "track_disparity", "dense_disparity", "disparity_last_kernel_ms", "disparity_last_form",
            "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip", "refine_flow_host", "refine_flow",
            "FlowRefiner", "REFINE_DEFAULTS", "FR_STAGES", "densify_flow_host", "densify_flow", "FlowDensifier",
-           "DENSIFY_DEFAULTS", "DZ_STAGES"]
+           "DENSIFY_DEFAULTS", "DZ_STAGES", "c2f_flow_host", "c2f_flow", "CoarseToFineFlow"]
 
 
 def last_kernel_ms():
@@ -367,7 +367,7 @@ class FlowRefiner(_DenseStage):
     def _source(self, src):
         """-> (the _lib.Field of `src`, what must stay alive until ictr_flowrefine_run has returned)"""
         f = _lib.Field(kind=_lib.FIELD_FLOW, sign=1, on_device=0, x_only=0, data=None)
-        dev = _device_source(src, self.w, self.h, (FlowDensifier,))
+        dev = _device_source(src, self.w, self.h, (FlowDensifier, CoarseToFineFlow))
         if dev is None:
             keep = _lib.f32c(src)
             if keep.shape != (self.h, self.w, 2):
@@ -382,7 +382,8 @@ class FlowRefiner(_DenseStage):
 
     def run(self, pyr_a, pyr_b, src, x_only=False, stream=None):
         """src: an (H, W, 2) host array (checked for finiteness, copied now), a FlowGrid that holds a field, a
-        FlowDensifier that has run (its buffer on the device, read when the run executes: run it on the same stream), or a
+        FlowDensifier or CoarseToFineFlow that has run (its buffer on the device, read when the run executes: run it on the
+        same stream), or a
         device tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
         f, _keep = self._source(src)
         check(self._c("run")(self._h, pyr_a._h, pyr_b._h, C.byref(f), int(bool(x_only)), C.c_void_p(stream or 0)))
@@ -524,6 +525,235 @@ class FlowDensifier(_DenseStage):
 def densify_flow(pyr_a, pyr_b, grid, psz, **params):
     """densify_flow_host's result from the device: a FlowGrid in, a host array out, one FlowDensifier for the call."""
     return FlowDensifier(pyr_a.w, pyr_a.h, **params).run(grid, pyr_a, pyr_b, psz).dense()
+
+
+# ---------------------------------------------------------------- coarse-to-fine dense flow
+C2F_LOST, C2F_TRACKED, C2F_HELD_COND, C2F_HELD_VIEW, C2F_HELD_FAR = range(5)  # ICTR_C2F_*, a node's status byte
+
+
+def _c2f_level_size(pyr, l):
+    return pyr.img[l].shape[1] - 2 * pyr.pad, pyr.img[l].shape[0] - 2 * pyr.pad
+
+
+def _c2f_sample(plane, pad, psz, x, y):
+    """The (psz, psz) patch k_patchflow samples at the centre (x, y) of a plane padded by pad >= psz, in f64: taps
+    (floor, floor + 1) both ways, weights from x - floor(x), y - floor(y)."""
+    v = plane[pad - psz:, pad - psz:]
+    fx, fy = np.floor(x), np.floor(y)
+    r0, r1 = x - fx, y - fy
+    row, col = int(fy) + 1 + psz // 2, int(fx) + 1 + psz // 2
+    a, b = v[row:row + psz, col:col + psz], v[row:row + psz, col - 1:col - 1 + psz]
+    c, d = v[row - 1:row - 1 + psz, col:col + psz], v[row - 1:row - 1 + psz, col - 1:col - 1 + psz]
+    return ((r0 * r1) * a.astype(np.float64) + ((1 - r0) * r1) * b + (r0 * (1 - r1)) * c) + ((1 - r0) * (1 - r1)) * d
+
+
+def _c2f_init(coarse, w, h, step):
+    """Step 2 of c2f_flow_host: (ny, nx, 2) float32 starts of a level's nodes from the coarser level's field (None: the
+    coarsest level, zeros). Nearest neighbour at (min(X >> 1, w' - 1), min(Y >> 1, h' - 1)), times 2: exact in f32."""
+    xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
+    if coarse is None:
+        return np.zeros((len(ys), len(xs), 2), np.float32)
+    coarse = np.asarray(coarse, np.float32)
+    ch, cw = coarse.shape[:2]
+    return np.float32(2) * coarse[np.minimum(ys >> 1, ch - 1)][:, np.minimum(xs >> 1, cw - 1)]
+
+
+def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det):
+    """Step 3 of c2f_flow_host at level l from the starts `init` (ny, nx, 2) float32. Returns (d (ny, nx, 2) float32
+    before the fill (NaN at a lost node), status (ny, nx) uint8, margins): margins is a dict of (ny, nx) f64 arrays, the
+    least distance of a node's decisions from their thresholds (inf where the decision was not taken):
+      "eps"   | |step| - eps | over the steps taken, in px
+      "view"  distance of a tested position from the border it is tested against, in px
+      "far"   | |p - init| - psz | at the rejection test, in px
+      "det"   | det / tr^2 - min_det |"""
+    w, h = _c2f_level_size(pyr_a, l)
+    xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
+    ny, nx = len(ys), len(xs)
+    d = np.full((ny, nx, 2), np.nan, np.float32)
+    status = np.zeros((ny, nx), np.uint8)
+    m = {k: np.full((ny, nx), np.inf) for k in ("eps", "view", "far", "det")}
+
+    def in_view(j, i, x, y):
+        with np.errstate(invalid="ignore"):
+            near = np.min(np.abs(np.array([x, y, x - w, y - h], np.float64)))
+        if np.isfinite(near):
+            m["view"][j, i] = min(m["view"][j, i], near)
+        return bool(0 <= x <= w and 0 <= y <= h)
+
+    for j, Y in enumerate(ys):
+        for i, X in enumerate(xs):
+            i0 = init[j, i].astype(np.float64)
+            if not (np.isfinite(i0).all() and in_view(j, i, X + i0[0], Y + i0[1])):
+                continue  # lost
+            d[j, i] = init[j, i]
+            T = _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y))
+            Gx = _c2f_sample(pyr_a.dx[l], pyr_a.pad, psz, float(X), float(Y))
+            Gy = _c2f_sample(pyr_a.dy[l], pyr_a.pad, psz, float(X), float(Y))
+            hxx, hxy, hyy = (Gx * Gx).sum(), (Gx * Gy).sum(), (Gy * Gy).sum()
+            det, tr = hxx * hyy - hxy * hxy, hxx + hyy
+            if tr > 0:
+                m["det"][j, i] = abs(det / (tr * tr) - min_det)
+            if not (det > min_det * tr * tr) or not (tr > 0):
+                status[j, i] = C2F_HELD_COND
+                continue
+            p = i0.copy()
+            st = C2F_TRACKED
+            for _ in range(maxiter):
+                cx, cy = X + p[0], Y + p[1]
+                if not in_view(j, i, cx, cy):
+                    st = C2F_HELD_VIEW
+                    break
+                r = T - _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, cx, cy)
+                bx, by = (Gx * r).sum(), (Gy * r).sum()
+                dx, dy = (hyy * bx - hxy * by) / det, (hxx * by - hxy * bx) / det
+                p += (dx, dy)
+                n = np.hypot(dx, dy)
+                m["eps"][j, i] = min(m["eps"][j, i], abs(n - eps))
+                if n * n < eps * eps:
+                    break
+            if st == C2F_TRACKED:
+                far = np.hypot(p[0] - i0[0], p[1] - i0[1])
+                if np.isfinite(far):
+                    m["far"][j, i] = abs(far - psz)
+                if not (far * far <= psz * psz):
+                    st = C2F_HELD_FAR
+            status[j, i] = st
+            if st == C2F_TRACKED:
+                d[j, i] = p
+    return d, status, m
+
+
+def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine):
+    if int(psz) != psz or not 1 <= psz <= 32:
+        raise ValueError("c2f flow: psz is 1 .. 32")
+    if int(step) != step or step < 1:
+        raise ValueError("c2f flow: step is an integer >= 1")
+    if pyr_a.pad < psz or pyr_b.pad < psz:
+        raise ValueError(f"c2f flow: pyramid padding must be >= psz ({psz})")
+    have = min(len(pyr_a.img), len(pyr_b.img)) - 1
+    lv_f = have if lv_f is None else int(lv_f)
+    if not 0 <= lv_f <= have:
+        raise ValueError(f"c2f flow: lv_f is {lv_f}, the pyramids have levels 0 .. {have}")
+    for l in range(lv_f + 1):
+        w, h = _c2f_level_size(pyr_a, l)
+        if _c2f_level_size(pyr_b, l) != (w, h):
+            raise ValueError(f"c2f flow: the two pyramids differ in size at level {l}")
+        if w < 2 or h < 2:
+            raise ValueError(f"c2f flow: level {l} is {w} x {h}, smaller than 2 px")
+        if step // 2 >= w or step // 2 >= h:
+            raise ValueError(f"c2f flow: level {l} ({w} x {h}) has no node at step {step}")
+        if refine is not None and (w < 4 or h < 4):
+            raise ValueError(f"c2f flow: level {l} is {w} x {h}, the refinement needs 4 x 4")
+    return lv_f
+
+
+def _c2f_plane(pyr, l):
+    p = pyr.pad
+    return np.ascontiguousarray(pyr.img[l][p:pyr.img[l].shape[0] - p, p:pyr.img[l].shape[1] - p])
+
+
+def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, min_det=1e-4, densify=None, refine=None,
+                  _stages=None):
+    """Coarse-to-fine dense flow A -> B: the definition (build-defined; NumPy, f64 arithmetic on the f32 planes; DESIGN.md
+    §4 "Coarse-to-fine dense flow" states the rule). pyr_a, pyr_b: host pyramids with ``.img / .dx / .dy[l]`` padded by
+    ``.pad >= psz`` (oracle.Pyramid's shape). For l = lv_f .. 0: nodes at step // 2 + k step of the level's own size; a
+    node starts at init = 2 U_{l+1}[min(Y >> 1, h' - 1), min(X >> 1, w' - 1)] ((0, 0) at lv_f); the search runs at this
+    level only with k_patchflow's sampling, H, step and stopping rule from p = init and ends in a status (C2F_*): 0 lost
+    (the start is out of view or not finite: no vote, filled from its neighbours), 1 tracked (d = p), 2 held by the
+    conditioning test, 3 held because it left the view while iterating, 4 held because |p - init| > psz (or not finite);
+    a held node keeps d = init, bit for bit, and votes. U_l = densify_flow_host(A_l, B_l, d, lost, step, psz, **densify),
+    then with `refine` a dict U_l = refine_flow_host(A_l, B_l, U_l, **refine). Returns U_0 (H, W, 2) float32.
+    _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
+    "margins" (_c2f_search_host's) and "field" (U_l)."""
+    lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine)
+    U = None
+    for l in range(lv_f, -1, -1):
+        w, h = _c2f_level_size(pyr_a, l)
+        init = _c2f_init(U, w, h, step)
+        d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det)
+        lost = status == C2F_LOST
+        A, B = _c2f_plane(pyr_a, l), _c2f_plane(pyr_b, l)
+        U = densify_flow_host(A, B, np.where(lost[..., None], np.float32(0), d), lost, step, psz, **(densify or {}))
+        if refine is not None:
+            U = refine_flow_host(A, B, U, **refine)
+        if _stages is not None:
+            filled = d.copy()
+            _dense_from_nodes(filled, lost, w, h, step)
+            _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U))
+    return U
+
+
+class CoarseToFineFlow:
+    """c2f_flow_host on the device (``ictr_c2fflow_*``: k_c2f_level, the grid's fill, k_densify and optionally the
+    refinement per level) for w x h frames and levels lv_f .. 0. densify / refine: the per-level parameters
+    (DENSIFY_DEFAULTS' / REFINE_DEFAULTS' names; refine=None: no refinement). ``run`` enqueues and returns; ``dense``
+    (level 0's field) and ``level`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
+
+    def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None):
+        dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
+        unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
+        if unknown:
+            raise TypeError(f"CoarseToFineFlow: unknown parameter(s) {sorted(unknown)}")
+        if int(dz["power"]) != dz["power"]:
+            raise ValueError("CoarseToFineFlow: power is an integer 1 .. 4")
+        L = _lib.load()
+        self._h = C.c_void_p()
+        check(L.ictr_c2fflow_create(C.byref(self._h), int(w), int(h), int(lv_f), int(step), int(psz)))
+        self.w, self.h, self.lv_f, self.step, self.psz = int(w), int(h), int(lv_f), int(step), int(psz)
+        self.params = dict(maxiter=int(maxiter), eps=float(eps), densify=dz,
+                           refine=None if refine is None else dict(REFINE_DEFAULTS, **refine))
+        check(L.ictr_c2fflow_set_params(self._h, int(maxiter), float(eps), float(dz["minerr"]), int(dz["power"])))
+        if refine is not None:
+            r = self.params["refine"]
+            check(L.ictr_c2fflow_set_refine(self._h, 1, float(r["alpha"]), float(r["gamma"]), float(r["delta"]),
+                                            int(r["n_outer"]), int(r["n_sor"]), float(r["omega"])))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_c2fflow_destroy(self._h)
+            self._h = None
+
+    def run(self, pyr_a, pyr_b, stream=None):
+        check(_lib.load().ictr_c2fflow_run(self._h, pyr_a._h, pyr_b._h, C.c_void_p(stream or 0)))
+        return self
+
+    def dense(self, out=None, on_device=False):
+        """The (H, W, 2) float32 field of the last run. on_device: `out` is a device pointer that receives it."""
+        return _dense_out(_lib.load().ictr_c2fflow_result, self._h, self.w, self.h, out, on_device)
+
+    def device_ptr(self):
+        return int(_lib.load().ictr_c2fflow_device_ptr(self._h) or 0)
+
+    def level_dims(self, l):
+        """(w, h, nx, ny) of level l."""
+        v = [C.c_int() for _ in range(4)]
+        check(_lib.load().ictr_c2fflow_level_dims(self._h, int(l), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def level(self, l):
+        """Level l of the last run: (field (h_l, w_l, 2) float32, d after the fill (ny, nx, 2) float32, status (ny, nx)
+        uint8)."""
+        w, h, nx, ny = self.level_dims(l)
+        field, d = np.empty((h, w, 2), np.float32), np.empty((ny, nx, 2), np.float32)
+        status = np.empty((ny, nx), np.uint8)
+        check(_lib.load().ictr_c2fflow_read_level(self._h, int(l), fp(field), fp(d), status.ctypes.data_as(_lib.U8P)))
+        return field, d, status
+
+    def set_timing(self, on=True):
+        check(_lib.load().ictr_c2fflow_set_timing(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """(lv_f + 1, 3) ms of the last run: per level from 0 the search with its fill, the densification, the refinement;
+        zeros when timing was off."""
+        ms = np.zeros((self.lv_f + 1, 3), np.float32)
+        check(_lib.load().ictr_c2fflow_get_kernel_ms(self._h, fp(ms)))
+        return ms
+
+
+def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
+    """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call."""
+    lv_f = pyr_a.lv_f if lv_f is None else lv_f
+    return CoarseToFineFlow(pyr_a.w, pyr_a.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
 
 
 def good_features(img, maxcorners=1000, quality=0.001, mindist=5, win=3):

@@ -179,11 +179,11 @@ def _exact_f32(a):
 
 def _descriptor(f, stereo, w, h):
     """-> (_lib.Field, what must stay alive until the step has run)"""
-    from .patchflow import FlowDensifier, FlowRefiner, _device_source
+    from .patchflow import CoarseToFineFlow, FlowDensifier, FlowRefiner, _device_source
     f = f if isinstance(f, field) else field(f)
     d = _lib.Field(sign=f.sign, x_only=int(stereo))
     # a grid, a stage's result buffer (read when the step runs, behind its run) or a tensor; else a host array
-    dev = _device_source(f.data, w, h, (FlowRefiner, FlowDensifier))
+    dev = _device_source(f.data, w, h, (FlowRefiner, FlowDensifier, CoarseToFineFlow))
     if dev is not None:
         d.kind, d.data, keep, _ = dev
         d.on_device = int(d.kind != FIELD_GRID)
@@ -292,12 +292,24 @@ class StereoPointTracker:
     refiners go to the window in the grids' place; keep_grids=True keeps them too, in ``refiners`` (same layout).
     densify=None: nothing is made or launched. densify=dict (parameters of patchflow.FlowDensifier, {} for its defaults):
     every grid is densified photometrically on the device (grid -> densify -> refine): with refine the refiners read the
-    densifiers, without it the window does; keep_grids=True keeps them in ``densifiers`` (same layout)."""
+    densifiers, without it the window does; keep_grids=True keeps them in ``densifiers`` (same layout).
+    flow="grid" (the default) is all of the above. flow="c2f" computes the six fields of a frame with
+    patchflow.CoarseToFineFlow objects instead (the stereo ones 2-D, y dropped by the window): no grid, densifier or
+    refiner of the tracker's own is made; densify and refine are then the per-level parameters (densify=None: the
+    densifier's defaults), and keep_grids=True keeps the objects in ``flows`` (same layout). disparity="1d" is refused
+    with flow="c2f": the 1-D form is not built."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
-                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None):
+                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid"):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
+        if flow not in ("grid", "c2f"):
+            raise ValueError(f"flow is 'grid' (a FlowGrid per field) or 'c2f' (a CoarseToFineFlow per field), not {flow!r}")
+        if flow == "c2f" and disparity == "1d":
+            raise ValueError("flow='c2f' with disparity='1d': the 1-D form of the coarse-to-fine flow is not built")
+        self.flow = flow
+        self.flows = []
+        self._fsets = [None, None]
         self.disparity = disparity
         self.refine = None if refine is None else dict(refine)
         self.refiners = []
@@ -348,6 +360,8 @@ class StereoPointTracker:
             ql, qr = self._pyr[(k - 1) & 1]
             fields += [("l_fwd", ql, pl, False), ("l_bwd", pl, ql, False), ("r_fwd", qr, pr, False),
                        ("r_bwd", pr, qr, False)]
+        if self.flow == "c2f":
+            return self._push_c2f(k, fields)
         g = self._set(self._sets, k, lambda: FlowGrid(self.w, self.h, self.step))
         z = r = None  # made when the stereo group reaches them
         for group in (fields[:2], fields[2:]):  # within each group: grid, then densify, then refine
@@ -370,6 +384,21 @@ class StereoPointTracker:
             for kept, s in ((self.grids, g), (self.refiners, r), (self.densifiers, z)):
                 if s is not None:
                     kept.append(s if k else {n: s[n] for n in ("lr", "rl")})
+        self.nframes = k + 1
+
+    def _push_c2f(self, k, fields):
+        """push_frames with flow="c2f": one CoarseToFineFlow per field, handed to the window."""
+        from .patchflow import CoarseToFineFlow
+        c = self._set(self._fsets, k, lambda: CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter,
+                                                                self.eps, densify=self.densify, refine=self.refine))
+        for n, a, b, _ in fields:
+            c[n].run(a, b)
+        if k == 0:
+            self.win.open(c["lr"], c["rl"], self.xy0)
+        else:
+            self.win.advance(c["l_fwd"], c["l_bwd"], c["r_fwd"], c["r_bwd"], c["lr"], c["rl"])
+        if self.keep_grids:
+            self.flows.append(c if k else {n: c[n] for n in ("lr", "rl")})
         self.nframes = k + 1
 
     def window(self):

@@ -1,0 +1,159 @@
+"""The coarse-to-fine dense flow at frame sizes a user runs -> profiles/c2fflow_bench.json.
+
+  python tools/c2fflow_bench.py [--reps 7] [--out profiles/c2fflow_bench.json] [--parent-root DIR]
+
+Per shape (1242x375 and 1920x1080) and patch size (8 and 15) at step 4, lv_f 3, with the default parameters and no
+refinement, `reps` runs after a warm-up, HIP events throughout, minimum / median / maximum of each:
+  - per level the search (k_c2f_level and the grid's fill) and the densification (the object's own events), and the
+    whole run (events around CoarseToFineFlow.run);
+  - in the same run FlowGrid.compute + FlowDensifier.run of the same pair (what the stage is an alternative to), and a
+    device-to-device copy of 16 B per pixel (half read, half written).
+These are recorded without a bar: the stage does more work per pair than the grid path, by construction.
+--parent-root: a built checkout of the parent commit. The untouched default paths, FlowGrid.compute (HIP events) and
+StereoPointTracker.push_frames with flow="grid" (wall time per stereo frame, 4 frames and the window counted), are then
+measured in child processes of this tree and of that one in turn (two each, `reps` runs per child after a warm-up). The one
+bar (exit status 1): this tree's median is not above the parent's own maximum; whether it is below the parent's minimum is
+recorded too.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STEP, LV_F, NFRAMES = 4, 3, 4
+PSZS = (8, 15)
+SHAPES = ((1242, 375), (1920, 1080))
+BYTES_COPY = 4 * 4.0  # bytes per pixel of the copy that the totals are set against
+
+
+def _timed(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def default_child(root, reps):
+    """Runs in a child process: the default paths of the tree at `root`, which may be a checkout without the stage."""
+    sys.path.insert(0, root)
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from invcompcamtrack_amd import stereotrack as S
+    from tools.patchdisp_bench import frames
+    out = {}
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        psz = PSZS[1]
+        pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+        grid = pf.FlowGrid(w, h, STEP)
+        compute, push = [], []
+        for rep in range(reps + 1):
+            tc = _timed(torch, lambda: grid.compute(pa, pb, psz=psz, lv_f=LV_F))
+            t = S.StereoPointTracker(w, h, NFRAMES, STEP, psz, LV_F)
+            t0 = time.perf_counter()
+            for left, right in fr:
+                t.push_frames(left, right)
+            t.win.count()  # waits for the device
+            if rep:
+                compute.append(float(tc))
+                push.append((time.perf_counter() - t0) * 1e3 / NFRAMES)
+        out[f"{w}x{h}"] = {"flowgrid_compute_ms": compute, "push_frames_wall_ms_per_stereo_frame": push}
+    print("DEFAULT " + json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "c2fflow_bench.json"))
+    ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.default_child:
+        return default_child(a.default_child, a.reps)
+    if a.reps < 7:
+        ap.error("at least 7 runs each")
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from tools.patchdisp_bench import frames, stats
+    if ic.device_count() < 1:
+        raise SystemExit("no HIP device: nothing is measured without one")
+
+    out = {"bench": "c2fflow", "step": STEP, "lv_f": LV_F, "reps": a.reps, "densify": pf.DENSIFY_DEFAULTS, "refine": None,
+           "copy_bytes_per_pixel": BYTES_COPY, "shapes": []}
+    ok = True
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        n = w * h
+        for psz in PSZS:
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            c = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz)
+            c.set_timing(True)
+            grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
+            k = int(BYTES_COPY * n / 2) // 4  # floats copied: as many bytes read as written
+            src, dst = torch.zeros(k, dtype=torch.float32, device="cuda"), torch.empty(k, dtype=torch.float32, device="cuda")
+            ms = {key: [] for key in ("total", "grid_densify", "copy")}
+            levels = []
+            for rep in range(a.reps + 1):  # the first round warms everything up
+                tt = _timed(torch, lambda: c.run(pa, pb))
+                per = c.kernel_ms()
+                tg = _timed(torch, lambda: dz.run(grid.compute(pa, pb, psz=psz, lv_f=LV_F), pa, pb, psz))
+                tcopy = _timed(torch, lambda: dst.copy_(src))
+                if rep:
+                    levels.append(per)
+                    for key, v in zip(("total", "grid_densify", "copy"), (tt, tg, tcopy)):
+                        ms[key].append(float(v))
+            levels = np.stack(levels)  # [rep][level][search, densify, refine]
+            rec = {"w": w, "h": h, "psz": psz, "levels": []}
+            for l in range(LV_F, -1, -1):
+                lw, lh, nx, ny = c.level_dims(l)
+                status = np.bincount(c.level(l)[2].ravel(), minlength=5)
+                rec["levels"].append({"level": l, "w": lw, "h": lh, "nodes": nx * ny, "status_counts": status.tolist(),
+                                      "search_ms": stats(levels[:, l, 0]), "densify_ms": stats(levels[:, l, 1])})
+            for key, v in ms.items():
+                rec[key + "_ms"] = stats(v)
+            rec["sum_of_stage_events_ms"] = round(float(np.median(levels[:, :, :2].sum(axis=(1, 2)))), 4)
+            rec["total_over_grid_densify"] = round(rec["total_ms"]["median"] / rec["grid_densify_ms"]["median"], 2)
+            rec["total_over_copy"] = round(rec["total_ms"]["median"] / rec["copy_ms"]["median"], 1)
+            rec["mean_abs_difference_to_grid_densify_px"] = round(float(np.abs(c.dense() - dz.dense()).mean()), 4)
+            out["shapes"].append(rec)
+            print(json.dumps(rec), flush=True)
+    if a.parent_root:
+        runs = {"this": {}, "parent": {}}
+        for _ in range(2):
+            for side, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--default-child", root, "--reps", str(a.reps)],
+                                   capture_output=True, text=True, timeout=600, cwd=root)
+                if r.returncode != 0:
+                    raise SystemExit(f"the {side} child failed:\n{r.stdout}\n{r.stderr}")
+                line = [ln for ln in r.stdout.splitlines() if ln.startswith("DEFAULT ")][-1]
+                for shape, d in json.loads(line[8:]).items():
+                    for key, v in d.items():
+                        runs[side].setdefault((shape, key), []).extend(v)
+        out["default_paths"] = {}
+        for (shape, key), v in runs["this"].items():
+            t, q = stats(v), stats(runs["parent"][shape, key])
+            bar = bool(t["median"] <= q["max"])
+            out["default_paths"].setdefault(shape, {})[key] = {
+                "this_tree": t, "parent": q, "bar_median_not_above_parent_max": bar,
+                "median_below_parent_min": bool(t["median"] < q["min"])}
+            ok &= bar
+        print(json.dumps(out["default_paths"]), flush=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
