@@ -6,12 +6,10 @@
 //
 // k_c2f_level<NPL, WPP>, one launch per level: a wave (two for patches of more than 4 pixels per lane) per node, in
 // k_patchflow's forms and two-wave exchange. What FlowGrid.compute spends three launches on is one here: the node position
-// follows from the node index, the start is ONE 8-byte load of the coarser field (times 2: exact), the template and the H
-// sums, the iterations at this level alone, the hold rules, and the node's displacement, lost byte and status byte
-// written directly. The per-pixel expressions and the sum shape are k_patchflow's (ictr_patchflow_dev.h; lane-serial
-// slots, the DPP tree, wave order): a node's step is the same f32 value as a k_patchflow step at the same position.
-// At the coarse levels a launch has a few waves per SIMD: an iteration is a latency chain per wave, so all of a lane's
-// loads of an iteration are issued before the first is consumed. f32 throughout, plain vector loads and stores, no atomics.
+// follows from the node index, the start is ONE 8-byte load of the coarser field (times 2: exact), the search at this
+// level alone is k_patchflow's (pf_level_search of ictr_patchflow_dev.h: a node's step is the same f32 value as a
+// k_patchflow step at the same position), then the hold rules, and the node's displacement, lost byte and status byte
+// written directly. f32 throughout, plain vector loads and stores, no atomics.
 #include <math.h>
 #include <string.h>
 
@@ -44,11 +42,9 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
   __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int wsub = wave % WPP;
   const int k = blockIdx.x * PPB + wave / WPP;
   const bool valid = k < a.K;
   if (WPP == 1 && !valid) return;
-  const int P = a.P, n = P * P;
   const int kk = valid ? k : 0;
   const int nj = kk / a.nx, ni = kk - nj * a.nx;
   const int X = a.step / 2 + ni * a.step, Y = a.step / 2 + nj * a.step;  // inside the level: the template needs no test
@@ -61,103 +57,20 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
   }
   const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
   int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
-  bool ok = st == ICTR_C2F_TRACKED;
   float px = ix, py = iy;
-  // sum over the node's WPP waves of three per-wave totals (all waves of the node get the same bits)
-  auto patch_sum3 = [&](float &u, float &v, float &w) {
-    u = pf_wave_sum(u);
-    v = pf_wave_sum(v);
-    w = pf_wave_sum(w);
-    if constexpr (WPP > 1) {
-      __syncthreads();  // (the previous reduction's partials have been read)
-      if (lane == 0) {
-        sSum[wave][0] = u;
-        sSum[wave][1] = v;
-        sSum[wave][2] = w;
-      }
-      __syncthreads();
-      const int w0 = wave - wsub;
-      u = v = w = 0.0f;
-#pragma unroll
-      for (int q = 0; q < WPP; ++q) {
-        u += sSum[w0 + q][0];
-        v += sSum[w0 + q][1];
-        w += sSum[w0 + q][2];
-      }
-    }
-  };
-  // One wave per node leaves at the first decision against it; two waves per node share barriers: every node of the
-  // workgroup runs every iteration slot, and one that is lost, held or converged only stops updating.
-  do {
-    if (WPP == 1 && !ok) break;
-    const PFTaps ta = pf_taps(xl, yl, P, a.sw, a.shift);
-    gconst_f32 pa = (gconst_f32)a.a, pax = (gconst_f32)a.ax, pay = (gconst_f32)a.ay, pb = (gconst_f32)a.b;
-    int off[NPL];
-    float T[NPL], Gx[NPL], Gy[NPL];
-    float hxx = 0.0f, hxy = 0.0f, hyy = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-      const int q = wsub * 64 + lane + 64 * WPP * i;
-      const bool in = q < n;
-      off[i] = in ? (q / P) * a.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
-      const int idx = ta.base + off[i];
-      const float t = pf_fetch(pa, idx, a.sw, ta), gx = pf_fetch(pax, idx, a.sw, ta), gy = pf_fetch(pay, idx, a.sw, ta);
-      T[i] = in ? t : 0.0f;
-      Gx[i] = in ? gx : 0.0f;
-      Gy[i] = in ? gy : 0.0f;
-      hxx += Gx[i] * Gx[i];
-      hxy += Gx[i] * Gy[i];
-      hyy += Gy[i] * Gy[i];
-    }
-    patch_sum3(hxx, hxy, hyy);
-    const float det = hxx * hyy - hxy * hxy;
-    const float tr = hxx + hyy;
-    if (ok && (!(det > a.min_det * tr * tr) || !(tr > 0.0f))) {  // textureless or 1-D structure
-      ok = false;
-      st = ICTR_C2F_HELD_COND;
-    }
-    if (WPP == 1 && !ok) break;
-    const float idet = 1.0f / det;
-    bool run = ok;  // this node still iterates
-    for (int it = 0; it < a.maxiter; ++it) {
-      if (WPP == 1 && !run) break;
-      const float cx = xl + px, cy = yl + py;
-      if (run && !pf_in_view(cx, cy, a.swo, a.sho)) {
-        ok = false;
-        run = false;
-        st = ICTR_C2F_HELD_VIEW;
-        if (WPP == 1) break;
-      }
-      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, a.sw, a.shift);  // (1,1): a harmless in-plane window
-      float bx = 0.0f, by = 0.0f, dummy = 0.0f;
-      PFWin w[NPL];
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) w[i] = pf_load(pb, tb.base + off[i], a.sw);  // all in flight before the first use
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) {
-        float r = T[i] - pf_blend(w[i], tb);
-        r = (wsub * 64 + lane + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
-        bx += Gx[i] * r;
-        by += Gy[i] * r;
-      }
-      patch_sum3(bx, by, dummy);
-      if (run) {
-        const float dx = (hyy * bx - hxy * by) * idet;
-        const float dy = (hxx * by - hxy * bx) * idet;
-        px += dx;
-        py += dy;
-        if (dx * dx + dy * dy < a.eps2) run = false;
-      }
-    }
-    if (ok) {  // a runaway patch: further than P from its start, or not finite (the test is written positively)
+  // One wave per node with a start out of view is done; two waves per node share the search's barriers.
+  if (WPP > 1 || st == ICTR_C2F_TRACKED) {
+    const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
+    int nit = 0;
+    const int why = pf_level_search<NPL, WPP, false>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter, a.eps2,
+                                                     a.min_det, sSum);
+    if (why) st = why == PF_STOP_COND ? ICTR_C2F_HELD_COND : ICTR_C2F_HELD_VIEW;
+    if (st == ICTR_C2F_TRACKED) {  // a runaway patch: further than P from its start, or not finite (a positive test)
       const float dx = px - ix, dy = py - iy;
-      if (!(dx * dx + dy * dy <= a.far2)) {
-        ok = false;
-        st = ICTR_C2F_HELD_FAR;
-      }
+      if (!(dx * dx + dy * dy <= a.far2)) st = ICTR_C2F_HELD_FAR;
     }
-  } while (0);
-  if (lane == 0 && wsub == 0 && valid) {
+  }
+  if (lane == 0 && wave % WPP == 0 && valid) {
     const float nanv = __int_as_float(0x7fc00000);
     const bool held = st >= ICTR_C2F_HELD_COND;
     a.d[2 * k] = st == ICTR_C2F_LOST ? nanv : held ? ix : px;  // a held node: its start's bits

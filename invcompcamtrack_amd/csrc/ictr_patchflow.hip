@@ -18,12 +18,6 @@
 // MI355X mapping: one wave64 per patch does ALL levels and ALL iterations of its patch inside one launch (the
 // problems are independent: no global reduction, no launch per iteration). The template T/Gx/Gy of the patch lives
 // in registers (<= 16 pixels per lane => P <= 32), H and b are wave shuffle reductions, every lane solves the 2x2.
-//
-// r02: an iteration is a latency chain per wave (4096 patches = 4096 waves = one round of four per SIMD), so what
-// counts is how few dependent steps it has: the four taps of a pixel are TWO 8-byte loads ((x-1,x) at y and at y-1),
-// every lane's loads of an iteration are issued before the first is consumed (pixels beyond the patch read the patch's
-// first pixel and carry zero templates: no branch in the loop), and the wave sums use DPP (11 instructions) instead of
-// six dependent ds_bpermute round trips each. Same expressions in the same order per pixel: same values.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,129 +29,51 @@
 
 namespace ictr {
 
-// pf_taps, pf_load, pf_blend, pf_fetch, pf_in_view, pf_wave_sum: ictr_patchflow_dev.h
-
-// WPP waves share a patch (pixels per lane NPL = ceil(P*P / (64 WPP))). One wave per patch needs no synchronisation at
-// all; for large patches (more than 4 pixels per lane) TWO waves per patch halve each wave's chain of pixels and double
-// the waves that hide each other's loads (+2 % at 4096 patches of 31x31, +9 % at 65536): the wave sums then meet in LDS (partials of the two waves added in wave order by
-// both: the same bits in both), one workgroup barrier per reduction. Barriers need a uniform loop structure: every
-// patch of a workgroup runs every level and iteration slot; a patch that is lost or converged only stops updating.
-template <int NPL, int WPP>
-__global__ __launch_bounds__(kBlock) void k_patchflow(PFArgs a) {
+// The search at one level (template, H sums, conditioning, iterations, the two-wave exchange) is pf_level_search of
+// ictr_patchflow_dev.h, for both kernels here. A kernel keeps the point, the walk down the pyramid with the doubling
+// and the level-entry view test, and the write-back. With two waves per patch (WPP = 2) every patch of a workgroup
+// runs every level: a patch that is lost only stops updating.
+template <int NPL, int WPP, bool XONLY>
+__device__ __forceinline__ void pf_track(const PFArgs &a) {
   constexpr int PPB = kWaves / WPP;  // patches per workgroup
   __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int wsub = wave % WPP;
   const int k = blockIdx.x * PPB + wave / WPP;
   const bool valid = k < a.K;
   if (WPP == 1 && !valid) return;
-  const int P = a.P, n = P * P;
   const int kk = valid ? k : 0;
   const float x0 = a.pts[kk], y0 = a.pts[kk + a.K];
   float px = 0.0f, py = 0.0f;
   bool ok = valid & (x0 == x0) & (y0 == y0);
   int nit = 0;
-  int off[NPL];
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) off[i] = 0;
-  // sum over the patch's WPP waves of three / two per-wave totals (all waves of the patch get the same bits)
-  auto patch_sum3 = [&](float &u, float &v, float &w) {
-    u = pf_wave_sum(u);
-    v = pf_wave_sum(v);
-    w = pf_wave_sum(w);
-    if constexpr (WPP > 1) {
-      __syncthreads();  // (the previous reduction's partials have been read)
-      if (lane == 0) {
-        sSum[wave][0] = u;
-        sSum[wave][1] = v;
-        sSum[wave][2] = w;
-      }
-      __syncthreads();
-      const int w0 = wave - wsub;
-      u = v = w = 0.0f;
-#pragma unroll
-      for (int q = 0; q < WPP; ++q) {
-        u += sSum[w0 + q][0];
-        v += sSum[w0 + q][1];
-        w += sSum[w0 + q][2];
-      }
-    }
-  };
-
   for (int l = a.lv_f; l >= a.lv_l && (WPP > 1 || ok); --l) {
-    const PFLevel L = a.lv[l];
+    const PFLevel &lv = a.lv[l];
+    const PFPlanes L{(gconst_f32)lv.a, (gconst_f32)lv.ax, (gconst_f32)lv.ay, (gconst_f32)lv.b,
+                     lv.sw, lv.shift, lv.swo, lv.sho};
     if (l != a.lv_f) {
       px *= 2.0f;
       py *= 2.0f;
     }
-    const float xl = x0 * L.scale, yl = y0 * L.scale;
+    const float xl = x0 * lv.scale, yl = y0 * lv.scale;
     if (ok && !pf_in_view(xl, yl, L.swo, L.sho)) ok = false;
     if (WPP == 1 && !ok) break;
-    const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);  // (1,1): a harmless in-plane window
-    gconst_f32 pa = (gconst_f32)L.a, pax = (gconst_f32)L.ax, pay = (gconst_f32)L.ay, pb = (gconst_f32)L.b;
-    float T[NPL], Gx[NPL], Gy[NPL];
-    float hxx = 0.0f, hxy = 0.0f, hyy = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-      const int q = wsub * 64 + lane + 64 * WPP * i;
-      const bool in = q < n;
-      off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
-      const int idx = ta.base + off[i];
-      const float t = pf_fetch(pa, idx, L.sw, ta), gx = pf_fetch(pax, idx, L.sw, ta), gy = pf_fetch(pay, idx, L.sw, ta);
-      T[i] = in ? t : 0.0f;
-      Gx[i] = in ? gx : 0.0f;
-      Gy[i] = in ? gy : 0.0f;
-      hxx += Gx[i] * Gx[i];
-      hxy += Gx[i] * Gy[i];
-      hyy += Gy[i] * Gy[i];
-    }
-    patch_sum3(hxx, hxy, hyy);
-    const float det = hxx * hyy - hxy * hxy;
-    const float tr = hxx + hyy;
-    if (ok && (!(det > a.min_det * tr * tr) || !(tr > 0.0f))) ok = false;  // textureless or 1-D structure
-    if (WPP == 1 && !ok) break;
-    const float idet = 1.0f / det;
-    bool run = ok;  // this patch still iterates at this level
-    for (int it = 0; it < a.maxiter; ++it) {
-      if (WPP == 1 && !run) break;
-      const float cx = xl + px, cy = yl + py;
-      if (run && !pf_in_view(cx, cy, L.swo, L.sho)) {
-        ok = false;
-        run = false;
-        if (WPP == 1) break;
-      }
-      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
-      float bx = 0.0f, by = 0.0f, dummy = 0.0f;
-      PFWin w[NPL];
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) w[i] = pf_load(pb, tb.base + off[i], L.sw);  // all in flight before the first use
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) {
-        float r = T[i] - pf_blend(w[i], tb);
-        r = (wsub * 64 + lane + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
-        bx += Gx[i] * r;
-        by += Gy[i] * r;
-      }
-      patch_sum3(bx, by, dummy);
-      if (run) {
-        const float dx = (hyy * bx - hxy * by) * idet;
-        const float dy = (hxx * by - hxy * bx) * idet;
-        px += dx;
-        py += dy;
-        ++nit;
-        if (dx * dx + dy * dy < a.eps2) run = false;
-      }
-    }
+    const float min_cond = XONLY ? a.min_hx : a.min_det;
+    if (pf_level_search<NPL, WPP, XONLY>(L, a.P, xl, yl, ok, px, py, nit, a.maxiter, a.eps2, min_cond, sSum)) ok = false;
   }
-  if (lane == 0 && wsub == 0 && valid) {
+  if (lane == 0 && wave % WPP == 0 && valid) {
     const float s = 1.0f / a.lv[a.lv_l].scale;  // back to level-0 pixels
     const float nanv = __int_as_float(0x7fc00000);
     a.out[k] = ok ? x0 + px * s : nanv;
-    a.out[k + a.K] = ok ? y0 + py * s : nanv;
+    a.out[k + a.K] = !ok ? nanv : XONLY ? y0 : y0 + py * s;  // (1-D: the input's bits)
     a.status[k] = ok ? 1 : 0;
     a.iters[k] = nit;
   }
+}
+
+template <int NPL, int WPP>
+__global__ __launch_bounds__(kBlock) void k_patchflow(PFArgs a) {
+  pf_track<NPL, WPP, false>(a);
 }
 
 static thread_local int g_pf_form = 0;
@@ -167,7 +83,7 @@ void launch_patchflow(const PFArgs &a, hipStream_t s) {
   const int n = a.P * a.P;
   const int npl = (n + 63) / 64;
   const dim3 blk(kBlock);
-  // few large patches: two waves per patch (see k_patchflow); ICTR_PF_WPP=1 keeps one wave per patch (A/B)
+  // few large patches: two waves per patch (see pf_patch_sum); ICTR_PF_WPP=1 keeps one wave per patch (A/B)
   static const int wpp_env = [] {
     const char *e = getenv("ICTR_PF_WPP");
     return e ? atoi(e) : 0;
@@ -191,129 +107,11 @@ void launch_patchflow(const PFArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- 1-D (x only) search for a rectified stereo pair
-// The same patches, pyramid walk and stopping rule as k_patchflow with ONE parameter: p moves along x, y never moves.
-//     hxx = sum Gx^2 (once per level),  bx = sum Gx (T - I(x + p, y)),  p += bx * (1 / hxx).
-// Conditioning: the patch is lost iff !(tr > 0) or !(hxx > min_hx * tr), tr = hxx + hyy: horizontal edges alone carry
-// no disparity, vertical edges alone (which the 2x2 system refuses) are kept. Gy lives only until hyy is summed; T and
-// Gx stay in registers; one wave sum per iteration sits on the chain. Forms and the two-wave exchange are
-// k_patchflow's (above): every patch of a two-wave workgroup runs every level and iteration slot.
+// The same patches, pyramid walk and stopping rule with ONE parameter: p moves along x, y never moves (pf_level_search's
+// XONLY rule). Forms and the two-wave exchange are k_patchflow's.
 template <int NPL, int WPP>
 __global__ __launch_bounds__(kBlock) void k_patchdisp(PFArgs a) {
-  constexpr int PPB = kWaves / WPP;  // patches per workgroup
-  __shared__ float sSum[WPP > 1 ? kWaves : 1][2];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wsub = wave % WPP;
-  const int k = blockIdx.x * PPB + wave / WPP;
-  const bool valid = k < a.K;
-  if (WPP == 1 && !valid) return;
-  const int P = a.P, n = P * P;
-  const int kk = valid ? k : 0;
-  const float x0 = a.pts[kk], y0 = a.pts[kk + a.K];
-  float px = 0.0f;
-  bool ok = valid & (x0 == x0) & (y0 == y0);
-  int nit = 0;
-  int off[NPL];
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) off[i] = 0;
-  // sum over the patch's WPP waves of two / one per-wave totals (all waves of the patch get the same bits)
-  auto patch_sum2 = [&](float &u, float &v) {
-    u = pf_wave_sum(u);
-    v = pf_wave_sum(v);
-    if constexpr (WPP > 1) {
-      __syncthreads();  // (the previous reduction's partials have been read)
-      if (lane == 0) {
-        sSum[wave][0] = u;
-        sSum[wave][1] = v;
-      }
-      __syncthreads();
-      const int w0 = wave - wsub;
-      u = v = 0.0f;
-#pragma unroll
-      for (int q = 0; q < WPP; ++q) {
-        u += sSum[w0 + q][0];
-        v += sSum[w0 + q][1];
-      }
-    }
-  };
-  auto patch_sum1 = [&](float &u) {
-    u = pf_wave_sum(u);
-    if constexpr (WPP > 1) {
-      __syncthreads();
-      if (lane == 0) sSum[wave][0] = u;
-      __syncthreads();
-      const int w0 = wave - wsub;
-      u = 0.0f;
-#pragma unroll
-      for (int q = 0; q < WPP; ++q) u += sSum[w0 + q][0];
-    }
-  };
-
-  for (int l = a.lv_f; l >= a.lv_l && (WPP > 1 || ok); --l) {
-    const PFLevel L = a.lv[l];
-    if (l != a.lv_f) px *= 2.0f;
-    const float xl = x0 * L.scale, yl = y0 * L.scale;
-    if (ok && !pf_in_view(xl, yl, L.swo, L.sho)) ok = false;
-    if (WPP == 1 && !ok) break;
-    const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);  // (1,1): a harmless in-plane window
-    gconst_f32 pa = (gconst_f32)L.a, pax = (gconst_f32)L.ax, pay = (gconst_f32)L.ay, pb = (gconst_f32)L.b;
-    float T[NPL], Gx[NPL];
-    float hxx = 0.0f, hyy = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-      const int q = wsub * 64 + lane + 64 * WPP * i;
-      const bool in = q < n;
-      off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
-      const int idx = ta.base + off[i];
-      const float t = pf_fetch(pa, idx, L.sw, ta), gx = pf_fetch(pax, idx, L.sw, ta), gy = pf_fetch(pay, idx, L.sw, ta);
-      T[i] = in ? t : 0.0f;
-      Gx[i] = in ? gx : 0.0f;
-      const float gyi = in ? gy : 0.0f;
-      hxx += Gx[i] * Gx[i];
-      hyy += gyi * gyi;
-    }
-    patch_sum2(hxx, hyy);
-    const float tr = hxx + hyy;
-    if (ok && (!(tr > 0.0f) || !(hxx > a.min_hx * tr))) ok = false;  // textureless, or horizontal edges alone
-    if (WPP == 1 && !ok) break;
-    const float ihx = 1.0f / hxx;
-    bool run = ok;  // this patch still iterates at this level
-    for (int it = 0; it < a.maxiter; ++it) {
-      if (WPP == 1 && !run) break;
-      const float cx = xl + px;
-      if (run && !pf_in_view(cx, yl, L.swo, L.sho)) {
-        ok = false;
-        run = false;
-        if (WPP == 1) break;
-      }
-      const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? yl : 1.0f, P, L.sw, L.shift);
-      float bx = 0.0f;
-      PFWin w[NPL];
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) w[i] = pf_load(pb, tb.base + off[i], L.sw);  // all in flight before the first use
-#pragma unroll
-      for (int i = 0; i < NPL; ++i) {
-        float r = T[i] - pf_blend(w[i], tb);
-        r = (wsub * 64 + lane + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
-        bx += Gx[i] * r;
-      }
-      patch_sum1(bx);
-      if (run) {
-        const float dx = bx * ihx;
-        px += dx;
-        ++nit;
-        if (dx * dx < a.eps2) run = false;
-      }
-    }
-  }
-  if (lane == 0 && wsub == 0 && valid) {
-    const float s = 1.0f / a.lv[a.lv_l].scale;  // back to level-0 pixels
-    const float nanv = __int_as_float(0x7fc00000);
-    a.out[k] = ok ? x0 + px * s : nanv;
-    a.out[k + a.K] = ok ? y0 : nanv;  // the input's bits
-    a.status[k] = ok ? 1 : 0;
-    a.iters[k] = nit;
-  }
+  pf_track<NPL, WPP, true>(a);
 }
 
 static thread_local int g_pd_form = 0;

@@ -1,7 +1,8 @@
-// ictr_patchflow_dev.h -- the patch sampling of the patch searches, stated once for the kernels of ictr_patchflow.hip
+// ictr_patchflow_dev.h -- the patch search at one pyramid level, stated once for the kernels of ictr_patchflow.hip
 // (k_patchflow, k_patchdisp) and of ictr_c2fflow.hip (k_c2f_level): the four tap weights and the first pixel of a patch
-// (pf_taps), a pixel's two 8-byte loads (pf_load), their blend (pf_blend), the view test (pf_in_view) and the wave sum
-// (pf_wave_sum). tests/patchflow_f32.py restates these expressions in NumPy f32.
+// (pf_taps), a pixel's two 8-byte loads (pf_load), their blend (pf_blend), the view test (pf_in_view), the sum over a
+// patch's waves (pf_patch_sum) and the search itself, from the template to the last iteration (pf_level_search, 2-D or
+// along x only). tests/patchflow_f32.py restates these expressions in NumPy f32 (level_search there).
 #pragma once
 
 #include "ictr_dev.h"
@@ -45,6 +46,136 @@ __device__ __forceinline__ float pf_fetch(gconst_f32 img, int idx, int sw, const
 }
 __device__ __forceinline__ bool pf_in_view(float x, float y, float swo, float sho) {
   return (x >= 0.0f) & (y >= 0.0f) & (x <= swo) & (y <= sho);
+}
+
+// WPP waves share a patch (pixels per lane NPL = ceil(P*P / (64 WPP))). One wave per patch needs no synchronisation at
+// all; for large patches (more than 4 pixels per lane) TWO waves per patch halve each wave's chain of pixels and double
+// the waves that hide each other's loads: the wave sums then meet in LDS, one workgroup barrier per reduction.
+// pf_patch_sum: N per-wave totals summed over the patch's WPP waves, the partials added in wave order from 0 by every
+// wave (all waves of the patch get the same bits). sSum: the workgroup's [kWaves][4] floats (unused with one wave).
+template <int WPP, int N>
+__device__ __forceinline__ void pf_patch_sum(float (&v)[N], float (*sSum)[4]) {
+  static_assert(N <= 4, "a wave's row of sSum holds four partials");
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = pf_wave_sum(v[j]);
+  if constexpr (WPP > 1) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // (the previous reduction's partials have been read)
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) sSum[wave][j] = v[j];
+    }
+    __syncthreads();
+    const int w0 = wave - wave % WPP;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      v[j] = 0.0f;
+#pragma unroll
+      for (int q = 0; q < WPP; ++q) v[j] += sSum[w0 + q][j];
+    }
+  }
+}
+
+// one level's planes and geometry, as PFLevel and C2fArgs carry them
+struct PFPlanes {
+  gconst_f32 a, ax, ay, b;  // frame A image + gradients, frame B image (padded planes)
+  int sw, shift;            // row stride; (pad - P) * (sw + 1)
+  float swo, sho;           // the level's unpadded size
+};
+enum { PF_STOP_NONE = 0, PF_STOP_COND = 1, PF_STOP_VIEW = 2 };  // why a patch stopped being tracked at a level
+
+// The search of one P x P patch at (xl, yl) of one level, from the displacement (px, py): the template T/Gx/Gy in
+// registers, H summed once, then up to maxiter Gauss-Newton steps p += H^-1 b, b = sum [Gx Gy]^T (T - I(x + p)), until
+// |dp|^2 < eps2. XONLY is the 1-D rule: hxx and hyy alone (Gy lives only until hyy is summed), the patch is refused iff
+// !(tr > 0) or !(hxx > min_cond * tr) (horizontal edges alone carry no disparity; vertical edges alone, which the 2x2
+// system refuses, are kept), p += bx * (1 / hxx) and y never moves. Returns why the patch is no longer tracked, if so.
+// An iteration is a latency chain per wave: the four taps of a pixel are TWO 8-byte loads, every lane's loads of an
+// iteration are issued before the first is consumed (pixels beyond the patch read the patch's first pixel and carry
+// zero templates: no branch in the loop), and the wave sums use DPP.
+// One wave per patch leaves at the first decision against it (and is not to be called with !ok). Two waves per patch
+// share barriers, which need a uniform loop structure: every patch of the workgroup runs every iteration slot, and one
+// that is not ok, stopped or converged only stops updating (its windows are the harmless in-plane one at (1,1)).
+template <int NPL, int WPP, bool XONLY>
+__device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float xl, float yl, bool ok, float &px, float &py,
+                                               int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4]) {
+  const int n = P * P;
+  const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
+  const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);
+  int off[NPL];
+  float T[NPL], Gx[NPL], Gy[XONLY ? 1 : NPL];
+  float h[XONLY ? 2 : 3] = {};  // hxx, (hxy,) hyy
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) {
+    const int q = slot0 + 64 * WPP * i;
+    const bool in = q < n;
+    off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
+    const int idx = ta.base + off[i];
+    const float t = pf_fetch(L.a, idx, L.sw, ta), gx = pf_fetch(L.ax, idx, L.sw, ta), gy = pf_fetch(L.ay, idx, L.sw, ta);
+    T[i] = in ? t : 0.0f;
+    Gx[i] = in ? gx : 0.0f;
+    const float gyi = in ? gy : 0.0f;
+    h[0] += Gx[i] * Gx[i];
+    if constexpr (XONLY) {
+      h[1] += gyi * gyi;
+    } else {
+      Gy[i] = gyi;
+      h[1] += Gx[i] * gyi;
+      h[2] += gyi * gyi;
+    }
+  }
+  pf_patch_sum<WPP>(h, sSum);
+  const float hxx = h[0], hxy = XONLY ? 0.0f : h[1], hyy = h[XONLY ? 1 : 2];
+  const float tr = hxx + hyy;
+  float inv;  // of what the solve divides by
+  bool cond;
+  if constexpr (XONLY) {
+    cond = (tr > 0.0f) && (hxx > min_cond * tr);
+    inv = 1.0f / hxx;
+  } else {
+    const float det = hxx * hyy - hxy * hxy;
+    cond = (det > min_cond * tr * tr) && (tr > 0.0f);  // else textureless or 1-D structure
+    inv = 1.0f / det;
+  }
+  int why = PF_STOP_NONE;
+  if (ok && !cond) why = PF_STOP_COND;
+  if (WPP == 1 && why) return why;
+  bool run = ok && !why;  // this patch still iterates at this level
+  for (int it = 0; it < maxiter; ++it) {
+    if (WPP == 1 && !run) break;
+    const float cx = xl + px, cy = XONLY ? yl : yl + py;
+    if (run && !pf_in_view(cx, cy, L.swo, L.sho)) {
+      why = PF_STOP_VIEW;
+      run = false;
+      if (WPP == 1) break;
+    }
+    const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
+    float b[XONLY ? 1 : 2] = {};  // bx, (by)
+    PFWin w[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) w[i] = pf_load(L.b, tb.base + off[i], L.sw);  // all in flight before the first use
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      float r = T[i] - pf_blend(w[i], tb);
+      r = (slot0 + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+      b[0] += Gx[i] * r;
+      if constexpr (!XONLY) b[1] += Gy[i] * r;
+    }
+    pf_patch_sum<WPP>(b, sSum);
+    if (run) {
+      float dx, dy = 0.0f;
+      if constexpr (XONLY) {
+        dx = b[0] * inv;
+      } else {
+        dx = (hyy * b[0] - hxy * b[1]) * inv;
+        dy = (hxx * b[1] - hxy * b[0]) * inv;
+        py += dy;
+      }
+      px += dx;
+      ++nit;
+      if ((XONLY ? dx * dx : dx * dx + dy * dy) < eps2) run = false;
+    }
+  }
+  return why;
 }
 
 }  // namespace ictr

@@ -1,9 +1,9 @@
 """The coarse-to-fine dense flow as csrc/ictr_c2fflow.hip computes it, restated in NumPy float32. It is written from the
 kernel k_c2f_level and its launcher, not from the host function: the node position from the node index, the start as one
-record of the coarser field times two, the template and H sums, the iterations at this level alone, the hold rules with
-their f32 comparisons, and what is written. It composes, unchanged, the pieces the other stages are restated with:
+record of the coarser field times two, the search at this level alone, the hold rules with their f32 comparisons, and
+what is written. It composes, unchanged, the pieces the other stages are restated with:
 
-  patchflow_f32._taps / _fetch / _sum   the sampling and the sum shape of k_patchflow (lane-serial slots, DPP tree, wave order)
+  patchflow_f32.level_search            pf_level_search: k_patchflow's search at one level, in the form's sum shape
   densify_f32.densify                   k_densify on the level's planes
   flowrefine_f32.refine                 the refinement launches on the level's planes
 
@@ -24,7 +24,7 @@ import numpy as np
 
 import densify_f32 as DZ
 import flowrefine_f32 as FR
-from patchflow_f32 import ONE, _fetch, _sum, _taps, f32
+from patchflow_f32 import STOP_COND, STOP_NONE, STOP_VIEW, f32, level_search
 
 DEFECTS = ("init not doubled", "init row up", "no clamp", "held lost", "far psz", "held keeps p")
 LOST, TRACKED, HELD_COND, HELD_VIEW, HELD_FAR = range(5)
@@ -79,43 +79,19 @@ def search(pyr_a, pyr_b, l, init, step, psz, maxiter=10, eps=0.01, min_det=1e-4,
     d = np.full((ny, nx, 2), np.nan, f32)
     status = np.zeros((ny, nx), np.uint8)
 
-    def in_view(x, y):
-        return x >= 0 and y >= 0 and x <= wl and y <= hl
-
     for j, Y in enumerate(ys):
         for i, X in enumerate(xs):
             xl, yl = f32(X), f32(Y)
             ix, iy = init[j, i]
-            if not (np.isfinite(ix) and np.isfinite(iy) and in_view(f32(xl + ix), f32(yl + iy))):
+            sx, sy = f32(xl + ix), f32(yl + iy)
+            if not (np.isfinite(ix) and np.isfinite(iy) and sx >= 0 and sy >= 0 and sx <= wl and sy <= hl):
                 continue
-            px, py = ix, iy
-            st = TRACKED
-            ta = _taps(xl, yl, P, None)
-            T, Gx, Gy = _fetch(va, ta, P), _fetch(vax, ta, P), _fetch(vay, ta, P)
-            hxx, hxy, hyy = _sum(Gx * Gx, shape, None), _sum(Gx * Gy, shape, None), _sum(Gy * Gy, shape, None)
-            det = f32(f32(hxx * hyy) - f32(hxy * hxy))
-            tr = f32(hxx + hyy)
-            if not (det > f32(f32(min_det * tr) * tr)) or not (tr > 0):
-                st = HELD_COND
-            else:
-                with np.errstate(over="ignore"):
-                    idet = f32(ONE / det)
-                for _ in range(maxiter):
-                    cx, cy = f32(xl + px), f32(yl + py)
-                    if not in_view(cx, cy):
-                        st = HELD_VIEW
-                        break
-                    r = T - _fetch(vb, _taps(cx, cy, P, None), P)
-                    bx, by = _sum(Gx * r, shape, None), _sum(Gy * r, shape, None)
-                    dx = f32(f32(f32(hyy * bx) - f32(hxy * by)) * idet)
-                    dy = f32(f32(f32(hxx * by) - f32(hxy * bx)) * idet)
-                    px, py = f32(px + dx), f32(py + dy)
-                    if f32(f32(dx * dx) + f32(dy * dy)) < eps2:
-                        break
-                if st == TRACKED:
-                    ex, ey = f32(px - ix), f32(py - iy)
-                    if not (f32(f32(ex * ex) + f32(ey * ey)) <= far2):
-                        st = HELD_FAR
+            px, py, _, why = level_search(va, vax, vay, vb, wl, hl, xl, yl, ix, iy, P, maxiter, eps2, min_det, shape=shape)
+            st = {STOP_NONE: TRACKED, STOP_COND: HELD_COND, STOP_VIEW: HELD_VIEW}[why]
+            if st == TRACKED:
+                ex, ey = f32(px - ix), f32(py - iy)
+                if not (f32(f32(ex * ex) + f32(ey * ey)) <= far2):
+                    st = HELD_FAR
             held = st >= HELD_COND
             if held and defect == "held lost":
                 continue

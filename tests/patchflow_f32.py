@@ -1,6 +1,9 @@
-"""f32 NumPy restatement of k_patchflow (csrc/ictr_patchflow.hip) for test_patchflow_cpu.py: the kernel's per-pixel
-expressions in their order, every operation rounded to f32 (the build has -ffp-contract=off: no fused multiply-add), and
-a selectable summation shape. It is written from the kernel, not from oracle/np_patchflow.py, and shares no code with it.
+"""f32 NumPy restatement of the patch searches: level_search is pf_level_search (csrc/ictr_patchflow_dev.h), the search at
+one pyramid level that k_patchflow, k_patchdisp and k_c2f_level share, 2-D or along x only; track_points is the walk of
+k_patchflow and k_patchdisp around it (patchdisp_f32.py, c2fflow_f32.py hold what their kernels keep). The kernel's
+per-pixel expressions in their order, every operation rounded to f32 (the build has -ffp-contract=off: no fused
+multiply-add), and a selectable summation shape. It is written from the kernels, not from oracle/np_patchflow.py or
+patchdisp_np.py, and shares no code with them.
 
 shape = (NPL, WPP): pixel q of the patch belongs to wave (q // 64) % WPP, lane q % 64, slot q // (64 WPP); a lane adds its
 slots serially from 0, the 64 lanes meet in a pairwise tree (wave_sum_dpp: 1, 2, half row, row, then (r0 + r1) + (r2 + r3)),
@@ -82,27 +85,67 @@ def _sum(terms, shape, defect):
     return tot
 
 
-def track_points(pyr_a, pyr_b, pts, psz, lv_f, lv_l=0, maxiter=10, eps=0.01, min_det=1e-4, shape=None, defect=None):
-    """The kernel's control flow for one patch after the other. pyr_*: oracle.Pyramid."""
+STOP_NONE, STOP_COND, STOP_VIEW = range(3)    # why a patch stopped being tracked at a level (pf_level_search's result)
+
+
+def level_search(va, vax, vay, vb, wl, hl, xl, yl, px, py, P, maxiter, eps2, min_cond, x_only=False, shape=None,
+                 defect=None):
+    """pf_level_search for one patch: the search at (xl, yl) of one level from the displacement (px, py), on the level's
+    planes of frame A (image, gradients) and B as views padded by exactly P, (wl, hl) the level's unpadded size in f32.
+    x_only is the 1-D rule of k_patchdisp: hxx and hyy alone, refused iff not tr > 0 or not hxx > min_cond tr, the solve
+    bx * (1 / hxx), y never moves. Returns (px, py, iterations, STOP_*)."""
+    def in_view(x, y):
+        return x >= 0 and y >= 0 and x <= wl and y <= hl
+
+    q = np.arange(P * P)
+    keep = q % P != P - 1 if defect == "drop last column" else q // P != P - 1 if defect == "drop last row" else q >= 0
+    ta = _taps(xl, yl, P, defect)
+    T, Gx, Gy = (np.where(keep, _fetch(v, ta, P), ZERO) for v in (va, vax, vay))
+    hxx, hyy = _sum(Gx * Gx, shape, defect), _sum(Gy * Gy, shape, defect)
+    tr = f32(hxx + hyy)
+    if x_only:
+        lost = not (tr > 0) or not (hxx > f32(min_cond * tr))
+        div = tr if defect == "solve by tr" else hxx
+    else:
+        hxy = _sum(Gx * Gy, shape, defect)
+        div = det = f32(f32(hxx * hyy) - f32(hxy * hxy))
+        lost = not (det > f32(f32(min_cond * tr) * tr)) or not (tr > 0)
+    if lost:
+        return px, py, 0, STOP_COND
+    with np.errstate(over="ignore"):
+        inv = f32(ONE / div)
+    for nit in range(maxiter):
+        cx, cy = f32(xl + px), f32(yl + py)
+        if x_only:
+            cy = f32(yl + px) if defect == "y follows x" else yl
+        if not in_view(cx, cy):
+            return px, py, nit, STOP_VIEW
+        r = np.where(keep, T - _fetch(vb, _taps(cx, cy, P, defect), P), ZERO)
+        bx = _sum(Gx * r, shape, defect)
+        if x_only:
+            dx, dy = f32(bx * inv), ZERO
+            step2 = f32(dx * dx)
+        else:
+            by = _sum(Gy * r, shape, defect)
+            dx = f32(f32(f32(hyy * bx) - f32(hxy * by)) * inv)
+            dy = f32(f32(f32(hxx * by) - f32(hxy * bx)) * inv)
+            step2 = f32(f32(dx * dx) + f32(dy * dy))
+        px, py = f32(px + dx), f32(py + dy)
+        if step2 < eps2:
+            return px, py, nit + 1, STOP_NONE
+    return px, py, maxiter, STOP_NONE
+
+
+def track_points(pyr_a, pyr_b, pts, psz, lv_f, lv_l=0, maxiter=10, eps=0.01, min_cond=1e-4, shape=None, defect=None,
+                 x_only=False):
+    """The control flow of k_patchflow (x_only: of k_patchdisp) for one patch after the other: the point, the walk down
+    the pyramid with the doubling and the level-entry view test, the rescale. pyr_*: oracle.Pyramid."""
     pts = np.asarray(pts, f32)
     K, P = len(pts), psz
     out = np.full((K, 2), np.nan, f32)
     status, iters = np.zeros(K, bool), np.zeros(K, np.int32)
     sh = pyr_a.pad - P
-    eps2, min_det = f32(f32(eps) * f32(eps)), f32(min_det)
-    q = np.arange(P * P)
-    keep = np.ones(P * P, bool)
-    if defect == "drop last column":
-        keep = q % P != P - 1
-    elif defect == "drop last row":
-        keep = q // P != P - 1
-
-    def view(plane):
-        return plane[sh:, sh:] if sh else plane
-
-    def in_view(x, y, w, h):
-        return x >= 0 and y >= 0 and x <= w and y <= h
-
+    eps2, min_cond = f32(f32(eps) * f32(eps)), f32(min_cond)
     for k in range(K):
         x0, y0 = pts[k]
         ok = bool(x0 == x0 and y0 == y0)
@@ -111,41 +154,20 @@ def track_points(pyr_a, pyr_b, pts, psz, lv_f, lv_l=0, maxiter=10, eps=0.01, min
         for l in range(lv_f, lv_l - 1, -1):
             if not ok:
                 break
-            if l != lv_f:
+            if l != lv_f and defect != "no doubling":
                 px, py = f32(px * f32(2)), f32(py * f32(2))
             scale = f32(1 / 2 ** l)
             wl, hl = f32(pyr_a.img[l].shape[1] - 2 * pyr_a.pad), f32(pyr_a.img[l].shape[0] - 2 * pyr_a.pad)
             xl, yl = f32(x0 * scale), f32(y0 * scale)
-            if not in_view(xl, yl, wl, hl):
+            if not (xl >= 0 and yl >= 0 and xl <= wl and yl <= hl):
                 ok = False
                 break
-            ta = _taps(xl, yl, P, defect)
-            T = np.where(keep, _fetch(view(pyr_a.img[l]), ta, P), ZERO)
-            Gx = np.where(keep, _fetch(view(pyr_a.dx[l]), ta, P), ZERO)
-            Gy = np.where(keep, _fetch(view(pyr_a.dy[l]), ta, P), ZERO)
-            hxx, hxy, hyy = _sum(Gx * Gx, shape, defect), _sum(Gx * Gy, shape, defect), _sum(Gy * Gy, shape, defect)
-            det = f32(f32(hxx * hyy) - f32(hxy * hxy))
-            tr = f32(hxx + hyy)
-            if not (det > f32(f32(min_det * tr) * tr)) or not (tr > 0):
-                ok = False
-                break
-            with np.errstate(over="ignore"):
-                idet = f32(ONE / det)
-            for _ in range(maxiter):
-                cx, cy = f32(xl + px), f32(yl + py)
-                if not in_view(cx, cy, wl, hl):
-                    ok = False
-                    break
-                r = np.where(keep, T - _fetch(view(pyr_b.img[l]), _taps(cx, cy, P, defect), P), ZERO)
-                bx, by = _sum(Gx * r, shape, defect), _sum(Gy * r, shape, defect)
-                dx = f32(f32(f32(hyy * bx) - f32(hxy * by)) * idet)
-                dy = f32(f32(f32(hxx * by) - f32(hxy * bx)) * idet)
-                px, py = f32(px + dx), f32(py + dy)
-                nit += 1
-                if f32(f32(dx * dx) + f32(dy * dy)) < eps2:
-                    break
+            planes = (p[sh:, sh:] for p in (pyr_a.img[l], pyr_a.dx[l], pyr_a.dy[l], pyr_b.img[l]))
+            px, py, n, why = level_search(*planes, wl, hl, xl, yl, px, py, P, maxiter, eps2, min_cond, x_only, shape, defect)
+            nit += n
+            ok = why == STOP_NONE
         if ok:
             s = f32(ONE / f32(1 / 2 ** (lv_f if defect == "rescale by lv_f" else lv_l)))
-            out[k] = (f32(x0 + f32(px * s)), f32(y0 + f32(py * s)))
+            out[k] = (f32(x0 + f32(px * s)), y0 if x_only else f32(y0 + f32(py * s)))
         status[k], iters[k] = ok, nit
     return out, status, iters

@@ -54,6 +54,17 @@ def test_the_table_covers_what_it_names():
         "field"].shape[0]
 
 
+@pytest.mark.parametrize("case", CC.STATUS_FORMS, ids=lambda c: f"psz{c[1]}")
+def test_the_status_pair_reaches_every_status_in_the_other_forms(case):
+    """A condition on the input: over the three levels of the restatement's run, every status value 0..4 occurs."""
+    assert R.form_shape(case[1]) == {15: (4, 1), 17: (8, 2)}[case[1]]
+    seen = np.zeros(5, int)
+    for _, _, _, status in CC.restated(case)[1]:
+        seen += np.bincount(status.ravel(), minlength=5)
+    print("psz", case[1], "pad", CC.pad_of(case), "status counts over the levels:", seen.tolist())
+    assert len(CC.restated(case)[1]) == 3 and (seen > 0).all(), seen
+
+
 def test_restatement_differences_are_within_their_records():
     worst = {}
     left, field = (0.0, None), 0.0

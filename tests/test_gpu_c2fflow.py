@@ -69,6 +69,19 @@ def test_table_has_the_restatements_bits(case):
     _same_as_restatement(c, case)
 
 
+@pytest.mark.parametrize("case", CC.STATUS_FORMS, ids=lambda c: f"psz{c[1]}")
+def test_every_status_has_the_restatements_bits_in_the_other_forms(case):
+    """The status pair at psz 15 (form <4,1>) and 17 (form <8,2>): the restatement's run holds every status value 0..4,
+    and at every level d, status and the field have its bits."""
+    want = CC.restated(case)
+    seen = np.zeros(5, int)
+    for _, _, _, status in want[1]:
+        seen += np.bincount(status.ravel(), minlength=5)
+    assert len(want[1]) == 3 and (seen > 0).all(), seen
+    c = _flow(case).run(*pyramids(case[0], CC.pad_of(case)))
+    _same_as_restatement(c, case, want)
+
+
 def test_same_bits_twice_on_a_stream_and_timed():
     from test_gpu_flowrefine import _hip_runtime
     case = CC.TABLE[0]
