@@ -578,6 +578,8 @@ class CoarseFlowClass {
                  float omega = 1.6f) {
     check(ictr_c2fflow_set_refine(h_, on ? 1 : 0, alpha, gamma, delta, n_outer, n_sor, omega), "SetRefine");
   }
+  // patch-mean normalisation of the next runs (ictr_c2fflow_set_patnorm); default off
+  void SetPatnorm(bool on) { check(ictr_c2fflow_set_patnorm(h_, on ? 1 : 0), "SetPatnorm"); }
   // a, b: pyramids of the object's size with levels 0 .. lv_f, padded by at least psz, a with gradient planes
   void Run(const Pyramid &a, const Pyramid &b, void *hip_stream = nullptr) {
     check(ictr_c2fflow_run(h_, a.handle(), b.handle(), hip_stream), "Run");
@@ -595,6 +597,8 @@ class CoarseFlowClass {
   void ReadLevel(int level, float *field, float *d, unsigned char *status) {
     check(ictr_c2fflow_read_level(h_, level, field, d, status), "ReadLevel");
   }
+  // bias [ny][nx]: the node bias of a run with patch-mean normalisation
+  void ReadLevelBias(int level, float *bias) { check(ictr_c2fflow_read_level_bias(h_, level, bias), "ReadLevelBias"); }
 
  private:
   ictr_c2fflow *h_;

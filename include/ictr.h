@@ -996,6 +996,8 @@ int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field, float *d, 
  * search (k_c2f_level and the fill), the densification and the refinement, zeros when timing was off */
 int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on);
 int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
+/* the stage's patch-mean normalisation: its switch and the reader of the node bias */
+#include "ictr_c2f_patnorm.h"
 
 #ifdef __cplusplus
 }

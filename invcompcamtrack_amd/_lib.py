@@ -366,6 +366,11 @@ SIGNATURES_REFERENCE_NAMES = {
     "ictr_triangulate_full3D_LM": (C.c_int, [FP, FP, FP, FP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                              C.c_float]),
 }
+# the coarse-to-fine flow's patch-mean normalisation (declared in include/ictr_c2f_patnorm.h, which ictr.h includes)
+SIGNATURES_PATNORM = {
+    "ictr_c2fflow_set_patnorm": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_read_level_bias": (C.c_int, [VP, C.c_int, FP]),
+}
 
 _lib = None
 
@@ -408,7 +413,8 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
+                              + list(SIGNATURES_PATNORM.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

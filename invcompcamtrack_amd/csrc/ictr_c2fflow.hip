@@ -10,10 +10,16 @@
 // level alone is k_patchflow's (pf_level_search of ictr_patchflow_dev.h: a node's step is the same f32 value as a
 // k_patchflow step at the same position), then the hold rules, and the node's displacement, lost byte and status byte
 // written directly. f32 throughout, plain vector loads and stores, no atomics.
+//
+// MEAN is patch-mean normalisation (DESIGN.md "Patch-mean normalisation"): the search removes the patch means
+// (pf_level_search<.., MEAN>), and the kernel's tail takes every voting node's brightness offset, beta = mean(B at the
+// node's final position) - mean(T), with one more window pass (pf_window_sum), into the level's bias table; a node that is
+// lost or whose final position is out of view gets +0.0. restated by tests/patnorm_f32.py.
 #include <math.h>
 #include <string.h>
 
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "ictr_dev.h"
@@ -35,9 +41,13 @@ struct C2fArgs {
   float *d;                      // [K][2] raw node displacements (the fill's input)
   unsigned char *lost, *status;  // [K], [K]
 };
+// the MEAN forms' arguments (the plain forms keep theirs, and with them their code, to the instruction)
+struct C2fMeanArgs : C2fArgs {
+  float *bias;  // [K] node brightness offsets
+};
 
-template <int NPL, int WPP>
-__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
+template <int NPL, int WPP, bool MEAN>
+__global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> a) {
   constexpr int PPB = kWaves / WPP;  // nodes per workgroup
   __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
   const int lane = threadIdx.x & 63;
@@ -58,16 +68,29 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
   const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
   int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
   float px = ix, py = iy;
+  float mean_t = 0.0f;
   // One wave per node with a start out of view is done; two waves per node share the search's barriers.
   if (WPP > 1 || st == ICTR_C2F_TRACKED) {
     const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
     int nit = 0;
-    const int why = pf_level_search<NPL, WPP, false>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter, a.eps2,
-                                                     a.min_det, sSum);
+    const int why = pf_level_search<NPL, WPP, false, MEAN>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter,
+                                                           a.eps2, a.min_det, sSum, mean_t);
     if (why) st = why == PF_STOP_COND ? ICTR_C2F_HELD_COND : ICTR_C2F_HELD_VIEW;
     if (st == ICTR_C2F_TRACKED) {  // a runaway patch: further than P from its start, or not finite (a positive test)
       const float dx = px - ix, dy = py - iy;
       if (!(dx * dx + dy * dy <= a.far2)) st = ICTR_C2F_HELD_FAR;
+    }
+  }
+  float beta = 0.0f;
+  if constexpr (MEAN) {
+    // the node's final position: where it votes from. Two waves per node: every node of the workgroup makes the pass.
+    const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
+    const bool held = st >= ICTR_C2F_HELD_COND;
+    const float fx = xl + (held ? ix : px), fy = yl + (held ? iy : py);
+    const bool votes = valid && st != ICTR_C2F_LOST && pf_in_view(fx, fy, a.swo, a.sho);
+    if (WPP > 1 || votes) {
+      const float sb = pf_window_sum<NPL, WPP>(L, a.P, votes ? fx : 1.0f, votes ? fy : 1.0f, sSum);
+      if (votes) beta = sb / (float)(a.P * a.P) - mean_t;
     }
   }
   if (lane == 0 && wave % WPP == 0 && valid) {
@@ -77,22 +100,24 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs a) {
     a.d[2 * k + 1] = st == ICTR_C2F_LOST ? nanv : held ? iy : py;
     a.lost[k] = st == ICTR_C2F_LOST ? 1 : 0;
     a.status[k] = (unsigned char)st;
+    if constexpr (MEAN) a.bias[k] = beta;
   }
 }
 
 // the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
-static void launch_c2f_level(const C2fArgs &a, hipStream_t s) {
+template <bool MEAN>
+static void launch_c2f_level(const std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> &a, hipStream_t s) {
   const int npl = (a.P * a.P + 63) / 64;
   const dim3 blk(kBlock);
   if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level<8, 2>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
     return;
   }
   const dim3 g((a.K + kWaves - 1) / kWaves);
   if (npl <= 1)
-    hipLaunchKernelGGL((k_c2f_level<1, 1>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN>), g, blk, 0, s, a);
   else
-    hipLaunchKernelGGL((k_c2f_level<4, 1>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN>), g, blk, 0, s, a);
 }
 
 }  // namespace ictr
@@ -113,6 +138,7 @@ struct RefDel {
 struct C2fLevel {
   int w = 0, h = 0, nx = 0, ny = 0;
   unsigned char *status = nullptr;  // [ny][nx], in the object's status block
+  float *bias = nullptr;            // [ny][nx], in the object's bias block
   std::unique_ptr<ictr_flowgrid, GridDel> grid;
   std::unique_ptr<ictr_flowdensify, DensDel> dens;
   std::unique_ptr<ictr_flowrefine, RefDel> ref;  // made when the refinement is switched on
@@ -125,9 +151,11 @@ struct ictr_c2fflow {
   int maxiter = 10;
   float eps = 0.01f;
   int refine = 0;  // refiners exist for every level and hold their parameters
-  int timing = 0, timed = 0, ran = 0, ran_refined = 0;
+  int patnorm = 0;
+  int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
   std::vector<C2fLevel> lv;  // [lv_f + 1]
   DevBuf<unsigned char> status;
+  DevBuf<float> bias;  // next to it: the node bias of a run with patch-mean normalisation
   Event done;  // behind the last run
 };
 
@@ -171,10 +199,14 @@ extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, i
     nodes += (size_t)L.nx * L.ny;
   }
   if (int rc = c->status.alloc(nodes, true)) return rc;
+  if (int rc = c->bias.alloc(sizeof(float) * nodes, true)) return rc;
   unsigned char *cur = c->status.get();
+  float *curb = c->bias.get();
   for (C2fLevel &L : c->lv) {
     L.status = cur;
+    L.bias = curb;
     cur += (size_t)L.nx * L.ny;
+    curb += (size_t)L.nx * L.ny;
   }
   if (int rc = c->done.create(hipEventDisableTiming)) return rc;
   *out = c.release();
@@ -212,6 +244,11 @@ extern "C" int ictr_c2fflow_set_refine(ictr_c2fflow *c, int on, float alpha, flo
   c->refine = 1;
   return ICTR_OK;
 }
+extern "C" int ictr_c2fflow_set_patnorm(ictr_c2fflow *c, int on) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  c->patnorm = on ? 1 : 0;
+  return ICTR_OK;
+}
 extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
   c->timing = on ? 1 : 0;
@@ -227,7 +264,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
       return fail(ICTR_ERR_INVALID, "c2fflow_run: level %d of the pyramids is %d x %d, of the object %d x %d", l,
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
   hipStream_t s = (hipStream_t)hip_stream;
-  const int refined = c->refine;
+  const int refined = c->refine, patnorm = c->patnorm;
   c->timed = c->timing;
   for (int l = c->lv_f; l >= 0; --l) {
     C2fLevel &L = c->lv[l];
@@ -254,10 +291,19 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
     if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
     a.status = L.status;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
-    launch_c2f_level(a, s);
+    if (patnorm) {
+      C2fMeanArgs m;
+      static_cast<C2fArgs &>(m) = a;
+      m.bias = L.bias;
+      launch_c2f_level<true>(m, s);
+    } else {
+      launch_c2f_level<false>(a, s);
+    }
     if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
-    if (int rc = ictr_flowdensify_run_level_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l, s)) return rc;
+    if (int rc = ictr_flowdensify_run_level_bias_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l,
+                                                  patnorm ? L.bias : nullptr, s))
+      return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[2].get(), s));
     if (refined) {
       ictr_field f;
@@ -274,6 +320,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
   HIPCHK(hipEventRecord(c->done.get(), s));
   c->ran = 1;
   c->ran_refined = refined;
+  c->ran_patnorm = patnorm;
   return ICTR_OK;
 }
 
@@ -314,6 +361,16 @@ extern "C" int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field,
   if (d)
     if (int rc = ictr_flowgrid_nodes(L.grid.get(), d, nullptr)) return rc;
   if (status) HIPCHK(hipMemcpy(status, L.status, K, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *bias) {
+  if (int rc = c2f_wait(c, "c2fflow_read_level_bias")) return rc;
+  if (level < 0 || level > c->lv_f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: level is %d (0 .. %d)", level, c->lv_f);
+  if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: bias is NULL");
+  if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias: the last run had patnorm off");
+  const C2fLevel &L = c->lv[level];
+  HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * (size_t)L.nx * L.ny, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {

@@ -15,10 +15,13 @@
 // a constant table and a single vote come back to the bit (d - d0 = 0, and d0 + 0 = d0; a d0 of -0.0 comes back +0.0).
 // B's taps come from global memory: neighbouring lanes share the node for most votes, so a vote's four tap loads of a
 // wave are four contiguous row segments. Plain vector loads and stores, no atomics; enqueued on the caller's stream.
+// k_densify<true> is the form of the coarse-to-fine flow's patch-mean normalisation: the record carries the node's
+// brightness offset beta next to (dx, dy) and the residual is (Bw - A) - beta (tests/patnorm_f32.py restates it).
 #include <math.h>
 #include <string.h>
 
 #include <memory>
+#include <type_traits>
 
 #include "ictr_dev.h"
 #include "ictr_launch.h"
@@ -40,6 +43,7 @@ struct DzArgs {
   int power;
   float2 *out;       // [h][w]
   float *cnt, *sw;   // [h][w]: votes taken, and their summed weight
+  const float *bias; // [ny][nx] node brightness offsets (k_densify<true> only)
 };
 
 // the nodes i >= 0 with a <= i step, and those i <= n - 1 with i step <= b (-1: none)
@@ -49,8 +53,18 @@ __host__ __device__ __forceinline__ int dz_last(int b, int step, int n) { return
 // of span - 1 + psz - 1 pixels
 static int dz_capacity(int span, int psz, int step) { return (span + psz - 2) / step + 1; }
 
+// the LDS record of a node: (dx, dy), and with BIAS the node's brightness offset beta next to them
+struct DzRecBias {
+  float x, y, beta;
+};
+template <bool BIAS>
+using DzRec = std::conditional_t<BIAS, DzRecBias, float2>;
+
+// BIAS: the vote weighs |Bw - A - beta| with the node's beta (the coarse-to-fine flow under patch-mean normalisation).
+template <bool BIAS>
 __global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
-  extern __shared__ float2 s_node[];  // [ncy][ncx] records of the nodes i0 .. i1 x j0 .. j1
+  extern __shared__ float2 s_node_raw[];  // [ncy][ncx] records of the nodes i0 .. i1 x j0 .. j1
+  DzRec<BIAS> *s_node = reinterpret_cast<DzRec<BIAS> *>(s_node_raw);
   const int step = a.g.step, half = step / 2;
   const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * kWaves;
   const int i0 = dz_first(bx0 - a.hi - half, step), i1 = dz_last(bx0 + 63 + a.lo - half, step, a.g.nx);
@@ -62,7 +76,10 @@ __global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
     const int k = (j0 + jj) * a.g.nx + (i0 + ii);
     float2 d = reinterpret_cast<const float2 *>(a.g.d)[k];
     if (a.lost[k]) d.x = nanv;
-    s_node[q] = d;
+    if constexpr (BIAS)
+      s_node[q] = DzRecBias{d.x, d.y, a.bias[k]};
+    else
+      s_node[q] = d;
   }
   __syncthreads();
   const int X = bx0 + (threadIdx.x & 63), Y = by0 + (threadIdx.x >> 6);
@@ -75,17 +92,18 @@ __global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
   float2 d0 = make_float2(0.0f, 0.0f);  // the first vote's displacement
   int n = 0;
   for (int j = lj0; j <= lj1; ++j) {
-    const float2 *row = s_node + (j - j0) * ncx - i0;
+    const DzRec<BIAS> *row = s_node + (j - j0) * ncx - i0;
     for (int i = li0; i <= li1; ++i) {
-      const float2 d = row[i];
+      const DzRec<BIAS> d = row[i];
       const float px = (float)X + d.x, py = (float)Y + d.y;
       if (!fr_inside(px, py, a.w, a.h)) continue;  // a lost node (NaN) too
-      const float r = fr_bilinear(a.B, a.sb, a.w, a.h, px, py) - av;
+      float r = fr_bilinear(a.B, a.sb, a.w, a.h, px, py) - av;
+      if constexpr (BIAS) r = r - d.beta;
       const float m = fmaxf(fabsf(r), a.minerr);
       const float m2 = m * m;
       const float mp = a.power == 1 ? m : a.power == 2 ? m2 : a.power == 3 ? m2 * m : m2 * m2;
       const float wgt = 1.0f / mp;
-      if (n == 0) d0 = d;
+      if (n == 0) d0 = make_float2(d.x, d.y);
       su = su + wgt * (d.x - d0.x);
       sv = sv + wgt * (d.y - d0.y);
       sw = sw + wgt;
@@ -160,6 +178,12 @@ extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *gr
 // the run on level `level` of the pyramids (grid and object of that level's size)
 extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
                                            const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream) {
+  return ictr_flowdensify_run_level_bias_(z, grid, pyr_a, pyr_b, psz, level, nullptr, hip_stream);
+}
+// the same with the grid's node bias [ny][nx] on the device (NULL: none, k_densify<false>)
+extern "C" int ictr_flowdensify_run_level_bias_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                                const ictr_pyramid *pyr_b, int psz, int level, const float *bias,
+                                                void *hip_stream) {
   if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
   if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
   DzArgs a;
@@ -184,14 +208,19 @@ extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowg
   a.out = reinterpret_cast<float2 *>(z->res.get());
   a.cnt = z->cnt;
   a.sw = z->sw;
-  const size_t lds = sizeof(float2) * (size_t)dz_capacity(64, psz, a.g.step) * dz_capacity(kWaves, psz, a.g.step);
+  a.bias = bias;
+  const size_t lds = (bias ? sizeof(DzRecBias) : sizeof(float2)) * (size_t)dz_capacity(64, psz, a.g.step) *
+                     dz_capacity(kWaves, psz, a.g.step);
   if (lds > kDzMaxLds)
     return fail(ICTR_ERR_INVALID, "flowdensify_run: step %d with psz %d needs a node table of %zu bytes of LDS (limit %zu)",
                 a.g.step, psz, lds, kDzMaxLds);
   hipStream_t s = (hipStream_t)hip_stream;
   z->timed = z->timing;
   if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
-  hipLaunchKernelGGL(k_densify, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
+  if (bias)
+    hipLaunchKernelGGL(k_densify<true>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
+  else
+    hipLaunchKernelGGL(k_densify<false>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
   if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
   HIPCHK(hipGetLastError());
   return z->res.record(s);

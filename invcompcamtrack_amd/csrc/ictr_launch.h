@@ -46,6 +46,10 @@ extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsig
 extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream);  // ictr_frontend.hip
 extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
                                            const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream);
+// the same with the grid's node bias [ny][nx] on the device, as the coarse-to-fine flow's patch-mean normalisation has it
+extern "C" int ictr_flowdensify_run_level_bias_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                                const ictr_pyramid *pyr_b, int psz, int level, const float *bias,
+                                                void *hip_stream);
 extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                           const ictr_field *src, int x_only, int level, void *hip_stream);
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)

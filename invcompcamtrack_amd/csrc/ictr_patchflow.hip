@@ -59,7 +59,9 @@ __device__ __forceinline__ void pf_track(const PFArgs &a) {
     if (ok && !pf_in_view(xl, yl, L.swo, L.sho)) ok = false;
     if (WPP == 1 && !ok) break;
     const float min_cond = XONLY ? a.min_hx : a.min_det;
-    if (pf_level_search<NPL, WPP, XONLY>(L, a.P, xl, yl, ok, px, py, nit, a.maxiter, a.eps2, min_cond, sSum)) ok = false;
+    float mean_t;  // (only patch-mean normalisation writes it; these kernels have none)
+    if (pf_level_search<NPL, WPP, XONLY, false>(L, a.P, xl, yl, ok, px, py, nit, a.maxiter, a.eps2, min_cond, sSum, mean_t))
+      ok = false;
   }
   if (lane == 0 && wave % WPP == 0 && valid) {
     const float s = 1.0f / a.lv[a.lv_l].scale;  // back to level-0 pixels

@@ -2,7 +2,8 @@
 // (k_patchflow, k_patchdisp) and of ictr_c2fflow.hip (k_c2f_level): the four tap weights and the first pixel of a patch
 // (pf_taps), a pixel's two 8-byte loads (pf_load), their blend (pf_blend), the view test (pf_in_view), the sum over a
 // patch's waves (pf_patch_sum) and the search itself, from the template to the last iteration (pf_level_search, 2-D or
-// along x only). tests/patchflow_f32.py restates these expressions in NumPy f32 (level_search there).
+// along x only; with MEAN, k_c2f_level's patch-mean normalisation) and one more window pass of frame B (pf_window_sum).
+// tests/patchflow_f32.py restates these expressions in NumPy f32 (level_search there), tests/patnorm_f32.py the MEAN form.
 #pragma once
 
 #include "ictr_dev.h"
@@ -95,15 +96,22 @@ enum { PF_STOP_NONE = 0, PF_STOP_COND = 1, PF_STOP_VIEW = 2 };  // why a patch s
 // One wave per patch leaves at the first decision against it (and is not to be called with !ok). Two waves per patch
 // share barriers, which need a uniform loop structure: every patch of the workgroup runs every iteration slot, and one
 // that is not ok, stopped or converged only stops updating (its windows are the harmless in-plane one at (1,1)).
-template <int NPL, int WPP, bool XONLY>
+// MEAN (2-D only) is patch-mean normalisation: T' = T - mean(T) once and r = T' - (I - mean(I)) in every iteration. The
+// sum of T joins the three sums of H in their one reduction, the sums of Gx and Gy are taken once in a second, and an
+// iteration keeps its single reduction, now of three: with s = sum G (T' - I), b = s + (sum I / n) sum G. The direct form
+// would need the frame mean before the residual, two reductions on the chain and in the two-wave form four barriers.
+// mean_t receives mean(T) = sum T / n (also when the patch is refused by the conditioning test).
+template <int NPL, int WPP, bool XONLY, bool MEAN>
 __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float xl, float yl, bool ok, float &px, float &py,
-                                               int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4]) {
+                                               int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4],
+                                               float &mean_t) {
+  static_assert(!(MEAN && XONLY), "patch-mean normalisation is built for the 2-D search");
   const int n = P * P;
   const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
   const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);
   int off[NPL];
   float T[NPL], Gx[NPL], Gy[XONLY ? 1 : NPL];
-  float h[XONLY ? 2 : 3] = {};  // hxx, (hxy,) hyy
+  float h[XONLY ? 2 : MEAN ? 4 : 3] = {};  // hxx, (hxy,) hyy(, sum T)
 #pragma unroll
   for (int i = 0; i < NPL; ++i) {
     const int q = slot0 + 64 * WPP * i;
@@ -122,8 +130,19 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       h[1] += Gx[i] * gyi;
       h[2] += gyi * gyi;
     }
+    if constexpr (MEAN) h[3] += T[i];
   }
   pf_patch_sum<WPP>(h, sSum);
+  float sg[2] = {};  // MEAN: sum Gx, sum Gy
+  if constexpr (MEAN) {
+    mean_t = h[3] / (float)n;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      T[i] = (slot0 + 64 * WPP * i < n) ? T[i] - mean_t : 0.0f;
+      sg[0] += Gx[i];
+      sg[1] += Gy[i];
+    }
+  }
   const float hxx = h[0], hxy = XONLY ? 0.0f : h[1], hyy = h[XONLY ? 1 : 2];
   const float tr = hxx + hyy;
   float inv;  // of what the solve divides by
@@ -139,6 +158,7 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
   int why = PF_STOP_NONE;
   if (ok && !cond) why = PF_STOP_COND;
   if (WPP == 1 && why) return why;
+  if constexpr (MEAN) pf_patch_sum<WPP>(sg, sSum);
   bool run = ok && !why;  // this patch still iterates at this level
   for (int it = 0; it < maxiter; ++it) {
     if (WPP == 1 && !run) break;
@@ -149,18 +169,26 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       if (WPP == 1) break;
     }
     const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
-    float b[XONLY ? 1 : 2] = {};  // bx, (by)
+    float b[XONLY ? 1 : MEAN ? 3 : 2] = {};  // bx, (by)(, sum I)
     PFWin w[NPL];
 #pragma unroll
     for (int i = 0; i < NPL; ++i) w[i] = pf_load(L.b, tb.base + off[i], L.sw);  // all in flight before the first use
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
-      float r = T[i] - pf_blend(w[i], tb);
-      r = (slot0 + 64 * WPP * i < n) ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+      const bool in = slot0 + 64 * WPP * i < n;
+      const float iv = pf_blend(w[i], tb);
+      float r = T[i] - iv;
+      r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
       b[0] += Gx[i] * r;
       if constexpr (!XONLY) b[1] += Gy[i] * r;
+      if constexpr (MEAN) b[2] += in ? iv : 0.0f;
     }
     pf_patch_sum<WPP>(b, sSum);
+    if constexpr (MEAN) {
+      const float mi = b[2] / (float)n;
+      b[0] = b[0] + mi * sg[0];
+      b[1] = b[1] + mi * sg[1];
+    }
     if (run) {
       float dx, dy = 0.0f;
       if constexpr (XONLY) {
@@ -176,6 +204,30 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
     }
   }
   return why;
+}
+
+// The sum of frame B over the P x P patch at (x, y), in the search's sampling, lane order and sum shape: one more window
+// pass, as an iteration makes it. Two waves per patch: every patch of the workgroup calls it (the barriers), one without a
+// use for the sum at the harmless window (1, 1).
+template <int NPL, int WPP>
+__device__ __forceinline__ float pf_window_sum(const PFPlanes &L, int P, float x, float y, float (*sSum)[4]) {
+  const int n = P * P;
+  const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
+  const PFTaps tb = pf_taps(x, y, P, L.sw, L.shift);
+  PFWin w[NPL];
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) {
+    const int q = slot0 + 64 * WPP * i;
+    w[i] = pf_load(L.b, tb.base + (q < n ? (q / P) * L.sw + (q % P) : 0), L.sw);
+  }
+  float s[1] = {};
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) {
+    const float iv = pf_blend(w[i], tb);
+    s[0] += (slot0 + 64 * WPP * i < n) ? iv : 0.0f;
+  }
+  pf_patch_sum<WPP>(s, sSum);
+  return s[0];
 }
 
 }  // namespace ictr

@@ -452,7 +452,7 @@ def _dz_check(img_a, img_b, d, lost, step, psz, minerr, power):
     return A, B, d, lost
 
 
-def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _stages=None):
+def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _stages=None, bias=None):
     """Photometric densification of a flow grid A -> B at level 0: the definition (build-defined; NumPy, f64 arithmetic on
     the f32 inputs; DESIGN.md §4 "Densification of a flow grid" states the rule). img_a, img_b: (H, W) grey frames; d
     (ny, nx, 2), lost (ny, nx): the node table of a grid of `step` (nodes at step // 2 + k step) tracked with patches of
@@ -460,6 +460,8 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     ascending node row, then column: a vote whose position (x, y) + d is not inside the frame is dropped; otherwise
     wgt = 1 / max(|Bw - A[y, x]|, minerr)^power with Bw by refine_flow_host's warp (_fr_warp). A pixel without a vote
     takes dense_flow's value. The sums are plain f64 sums of exact products, the quotient is rounded to f32 once.
+    bias: an (ny, nx) array of per-node brightness offsets beta (the coarse-to-fine flow's node bias under patch-mean
+    normalisation); the weight is then 1 / max(|Bw - A[y, x] - beta_node|, minerr)^power. None: the operations above.
     Returns (H, W, 2) float32. _stages: a dict that receives "count" (votes taken, int), "wsum" (their summed weight,
     f64) and "edge" (the least distance of a pixel's vote positions to the inside boundary in px, inf without one)."""
     A32, B32, d, lost = _dz_check(img_a, img_b, d, lost, step, psz, minerr, power)
@@ -469,6 +471,10 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     i0, i1 = _dz_nodes(w, nx, step, psz)
     j0, j1 = _dz_nodes(h, ny, step, psz)
     d64 = d.astype(np.float64)
+    if bias is not None:
+        bias = np.asarray(bias, np.float64)
+        if bias.shape != (ny, nx):
+            raise ValueError(f"densify needs bias ({ny}, {nx})")
     yy, xx = np.mgrid[0:h, 0:w]
     su, sv, sw = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
     cnt = np.zeros((h, w), np.int64)
@@ -485,7 +491,8 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
                 near = np.minimum(np.minimum(np.abs(px), np.abs(px - (w - 1))), np.minimum(np.abs(py), np.abs(py - (h - 1))))
                 edge = np.where(votes & (near < edge), near, edge)
                 ok = votes & (inside > 0)
-                wgt = 1.0 / _dz_power(np.fmax(np.abs(bw - A), float(minerr)), power)
+                res = bw - A if bias is None else bw - A - bias[j][:, i]
+                wgt = 1.0 / _dz_power(np.fmax(np.abs(res), float(minerr)), power)
                 su, sv, sw = np.where(ok, su + wgt * dx, su), np.where(ok, sv + wgt * dy, sv), np.where(ok, sw + wgt, sw)
             cnt += ok
     out = _dense_from_nodes(d.copy(), lost, w, h, step)
@@ -558,8 +565,9 @@ def _c2f_init(coarse, w, h, step):
     return np.float32(2) * coarse[np.minimum(ys >> 1, ch - 1)][:, np.minimum(xs >> 1, cw - 1)]
 
 
-def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det):
-    """Step 3 of c2f_flow_host at level l from the starts `init` (ny, nx, 2) float32. Returns (d (ny, nx, 2) float32
+def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm=False):
+    """Step 3 of c2f_flow_host at level l from the starts `init` (ny, nx, 2) float32. patnorm: patch-mean normalisation,
+    T <- T - mean(T) once and r = T - (I - mean(I)) in every iteration, nothing else changed. Returns (d (ny, nx, 2) float32
     before the fill (NaN at a lost node), status (ny, nx) uint8, margins): margins is a dict of (ny, nx) f64 arrays, the
     least distance of a node's decisions from their thresholds (inf where the decision was not taken):
       "eps"   | |step| - eps | over the steps taken, in px
@@ -596,6 +604,8 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det):
             if not (det > min_det * tr * tr) or not (tr > 0):
                 status[j, i] = C2F_HELD_COND
                 continue
+            if patnorm:
+                T = T - T.mean()
             p = i0.copy()
             st = C2F_TRACKED
             for _ in range(maxiter):
@@ -603,7 +613,8 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det):
                 if not in_view(j, i, cx, cy):
                     st = C2F_HELD_VIEW
                     break
-                r = T - _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, cx, cy)
+                I = _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, cx, cy)
+                r = T - (I - I.mean()) if patnorm else T - I
                 bx, by = (Gx * r).sum(), (Gy * r).sum()
                 dx, dy = (hyy * bx - hxy * by) / det, (hxx * by - hxy * bx) / det
                 p += (dx, dy)
@@ -621,6 +632,30 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det):
             if st == C2F_TRACKED:
                 d[j, i] = p
     return d, status, m
+
+
+def _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins=None):
+    """The node bias of c2f_flow_host under patnorm at level l: (ny, nx) f64. A node with status != 0 has a final float32
+    d (a tracked node's p, a held node's init); where its final position (X, Y) + d passes the search's view test,
+    beta = mean(patch of B there) - mean(patch of A at (X, Y)), both sampled as the search samples them. Every other
+    node has beta = 0: a tracked node may end up to psz out of view, and no tap then leaves a plane padded by psz.
+    margins: _c2f_search_host's dict; the distance of this view decision from its border joins "view"."""
+    w, h = _c2f_level_size(pyr_a, l)
+    xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
+    beta = np.zeros((len(ys), len(xs)))
+    for j, Y in enumerate(ys):
+        for i, X in enumerate(xs):
+            if status[j, i] == C2F_LOST:
+                continue
+            x, y = X + float(d[j, i, 0]), Y + float(d[j, i, 1])
+            near = min(abs(x), abs(y), abs(x - w), abs(y - h))
+            if margins is not None and np.isfinite(near):
+                margins["view"][j, i] = min(margins["view"][j, i], near)
+            if not (0 <= x <= w and 0 <= y <= h):
+                continue
+            beta[j, i] = (_c2f_sample(pyr_b.img[l], pyr_b.pad, psz, x, y).mean()
+                          - _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y)).mean())
+    return beta
 
 
 def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine):
@@ -653,7 +688,7 @@ def _c2f_plane(pyr, l):
 
 
 def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, min_det=1e-4, densify=None, refine=None,
-                  _stages=None):
+                  _stages=None, patnorm=False):
     """Coarse-to-fine dense flow A -> B: the definition (build-defined; NumPy, f64 arithmetic on the f32 planes; DESIGN.md
     §4 "Coarse-to-fine dense flow" states the rule). pyr_a, pyr_b: host pyramids with ``.img / .dx / .dy[l]`` padded by
     ``.pad >= psz`` (oracle.Pyramid's shape). For l = lv_f .. 0: nodes at step // 2 + k step of the level's own size; a
@@ -663,33 +698,40 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     conditioning test, 3 held because it left the view while iterating, 4 held because |p - init| > psz (or not finite);
     a held node keeps d = init, bit for bit, and votes. U_l = densify_flow_host(A_l, B_l, d, lost, step, psz, **densify),
     then with `refine` a dict U_l = refine_flow_host(A_l, B_l, U_l, **refine). Returns U_0 (H, W, 2) float32.
+    patnorm: patch-mean normalisation, for frames whose brightness differs by a locally constant offset. The search
+    removes the patch means (_c2f_search_host), every node gets its brightness offset beta (_c2f_bias_host), and the
+    densifier's vote of a node weighs |Bw - A - beta| (densify_flow_host's bias). The refinement is unchanged: its
+    brightness term still sees the offset.
     _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
-    "margins" (_c2f_search_host's) and "field" (U_l)."""
+    "margins" (_c2f_search_host's), "field" (U_l) and "bias" (the node bias, None without patnorm)."""
     lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine)
     U = None
     for l in range(lv_f, -1, -1):
         w, h = _c2f_level_size(pyr_a, l)
         init = _c2f_init(U, w, h, step)
-        d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det)
+        d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm)
         lost = status == C2F_LOST
+        bias = _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins) if patnorm else None
         A, B = _c2f_plane(pyr_a, l), _c2f_plane(pyr_b, l)
-        U = densify_flow_host(A, B, np.where(lost[..., None], np.float32(0), d), lost, step, psz, **(densify or {}))
+        U = densify_flow_host(A, B, np.where(lost[..., None], np.float32(0), d), lost, step, psz, bias=bias,
+                              **(densify or {}))
         if refine is not None:
             U = refine_flow_host(A, B, U, **refine)
         if _stages is not None:
             filled = d.copy()
             _dense_from_nodes(filled, lost, w, h, step)
-            _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U))
+            _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U, bias=bias))
     return U
 
 
 class CoarseToFineFlow:
     """c2f_flow_host on the device (``ictr_c2fflow_*``: k_c2f_level, the grid's fill, k_densify and optionally the
     refinement per level) for w x h frames and levels lv_f .. 0. densify / refine: the per-level parameters
-    (DENSIFY_DEFAULTS' / REFINE_DEFAULTS' names; refine=None: no refinement). ``run`` enqueues and returns; ``dense``
-    (level 0's field) and ``level`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
+    (DENSIFY_DEFAULTS' / REFINE_DEFAULTS' names; refine=None: no refinement). patnorm: c2f_flow_host's patch-mean
+    normalisation (k_c2f_level's MEAN forms with the node bias, k_densify<true>). ``run`` enqueues and returns; ``dense``
+    (level 0's field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 
-    def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None):
+    def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False):
         dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
         unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
         if unknown:
@@ -707,6 +749,9 @@ class CoarseToFineFlow:
             r = self.params["refine"]
             check(L.ictr_c2fflow_set_refine(self._h, 1, float(r["alpha"]), float(r["gamma"]), float(r["delta"]),
                                             int(r["n_outer"]), int(r["n_sor"]), float(r["omega"])))
+        self.patnorm = bool(patnorm)
+        if self.patnorm:
+            check(L.ictr_c2fflow_set_patnorm(self._h, 1))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -739,6 +784,13 @@ class CoarseToFineFlow:
         check(_lib.load().ictr_c2fflow_read_level(self._h, int(l), fp(field), fp(d), status.ctypes.data_as(_lib.U8P)))
         return field, d, status
 
+    def level_bias(self, l):
+        """The node bias (ny, nx) float32 of level l of the last run; patnorm only."""
+        _, _, nx, ny = self.level_dims(l)
+        bias = np.empty((ny, nx), np.float32)
+        check(_lib.load().ictr_c2fflow_read_level_bias(self._h, int(l), fp(bias)))
+        return bias
+
     def set_timing(self, on=True):
         check(_lib.load().ictr_c2fflow_set_timing(self._h, int(bool(on))))
 
@@ -751,7 +803,8 @@ class CoarseToFineFlow:
 
 
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
-    """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call."""
+    """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call
+    (params: its keywords, patnorm among them)."""
     lv_f = pyr_a.lv_f if lv_f is None else lv_f
     return CoarseToFineFlow(pyr_a.w, pyr_a.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
 

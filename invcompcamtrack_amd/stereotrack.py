@@ -297,17 +297,23 @@ class StereoPointTracker:
     patchflow.CoarseToFineFlow objects instead (the stereo ones 2-D, y dropped by the window): no grid, densifier or
     refiner of the tracker's own is made; densify and refine are then the per-level parameters (densify=None: the
     densifier's defaults), and keep_grids=True keeps the objects in ``flows`` (same layout). disparity="1d" is refused
-    with flow="c2f": the 1-D form is not built."""
+    with flow="c2f": the 1-D form is not built. patnorm=True switches on the coarse-to-fine objects' patch-mean
+    normalisation (CoarseToFineFlow's patnorm: for a right camera or a next frame of another brightness); it is
+    refused with flow="grid", whose whole-pyramid kernels have no such form."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
-                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid"):
+                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         if flow not in ("grid", "c2f"):
             raise ValueError(f"flow is 'grid' (a FlowGrid per field) or 'c2f' (a CoarseToFineFlow per field), not {flow!r}")
         if flow == "c2f" and disparity == "1d":
             raise ValueError("flow='c2f' with disparity='1d': the 1-D form of the coarse-to-fine flow is not built")
+        if patnorm and flow != "c2f":
+            raise ValueError("patnorm=True needs flow='c2f': patch-mean normalisation is built for the coarse-to-fine flow "
+                             "alone, not for the flow grids of flow='grid'")
         self.flow = flow
+        self.patnorm = bool(patnorm)
         self.flows = []
         self._fsets = [None, None]
         self.disparity = disparity
@@ -390,7 +396,8 @@ class StereoPointTracker:
         """push_frames with flow="c2f": one CoarseToFineFlow per field, handed to the window."""
         from .patchflow import CoarseToFineFlow
         c = self._set(self._fsets, k, lambda: CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter,
-                                                                self.eps, densify=self.densify, refine=self.refine))
+                                                                self.eps, densify=self.densify, refine=self.refine,
+                                                                patnorm=self.patnorm))
         for n, a, b, _ in fields:
             c[n].run(a, b)
         if k == 0:

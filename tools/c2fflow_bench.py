@@ -14,6 +14,14 @@ StereoPointTracker.push_frames with flow="grid" (wall time per stereo frame, 4 f
 measured in child processes of this tree and of that one in turn (two each, `reps` runs per child after a warm-up). The one
 bar (exit status 1): this tree's median is not above the parent's own maximum; whether it is below the parent's minimum is
 recorded too.
+
+  python tools/c2fflow_bench.py --patnorm [--reps 7] [--out profiles/c2fflow_patnorm_bench.json] [--parent-root DIR]
+
+The cost of patch-mean normalisation instead: per shape and patch size two CoarseToFineFlow objects, patnorm off and on, run
+in turn; per level the search and densification medians of each and their ratio, and the whole runs. Recorded without a bar.
+--parent-root then measures the default paths this option must leave alone, CoarseToFineFlow.run with patnorm off (psz 8
+and 15) and FlowDensifier.run (psz 15), in child processes of the two builds in turn (two each). The bar (exit status 1):
+this tree's median exceeds the parent's by at most the parent's own max - min spread.
 """
 import argparse
 import json
@@ -68,17 +76,115 @@ def default_child(root, reps):
     print("DEFAULT " + json.dumps(out), flush=True)
 
 
+def patnorm_child(root, reps):
+    """Runs in a child process: CoarseToFineFlow.run (no patnorm keyword: the parent has none) and FlowDensifier.run of
+    the tree at `root`, HIP events around each."""
+    sys.path.insert(0, root)
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from tools.patchdisp_bench import frames
+    out = {}
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        rec = {}
+        for psz in PSZS:
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            c = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz)
+            rec[f"c2f_run_psz{psz}_ms"] = [float(_timed(torch, lambda: c.run(pa, pb))) for _ in range(reps + 1)][1:]
+            if psz == PSZS[1]:
+                grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
+                grid.compute(pa, pb, psz=psz, lv_f=LV_F)
+                rec["flowdensifier_run_ms"] = [float(_timed(torch, lambda: dz.run(grid, pa, pb, psz)))
+                                               for _ in range(reps + 1)][1:]
+        out[f"{w}x{h}"] = rec
+    print("DEFAULT " + json.dumps(out), flush=True)
+
+
+def patnorm_main(a):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from tools.patchdisp_bench import frames, stats
+    if ic.device_count() < 1:
+        raise SystemExit("no HIP device: nothing is measured without one")
+    out = {"bench": "c2fflow_patnorm", "step": STEP, "lv_f": LV_F, "reps": a.reps, "densify": pf.DENSIFY_DEFAULTS,
+           "refine": None, "shapes": []}
+    ok = True
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        for psz in PSZS:
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, patnorm=on) for on in (False, True)}
+            levels, total = {False: [], True: []}, {False: [], True: []}
+            for rep in range(a.reps + 1):  # the first round warms everything up
+                for on, c in cs.items():
+                    c.set_timing(True)
+                    tt = _timed(torch, lambda: c.run(pa, pb))
+                    if rep:
+                        levels[on].append(c.kernel_ms())
+                        total[on].append(float(tt))
+            lv = {on: np.stack(v) for on, v in levels.items()}  # [rep][level][search, densify, refine]
+            rec = {"w": w, "h": h, "psz": psz, "levels": [],
+                   "total_ms": {"off": stats(total[False]), "on": stats(total[True])}}
+            for l in range(LV_F, -1, -1):
+                lw, lh, nx, ny = cs[True].level_dims(l)
+                e = {"level": l, "w": lw, "h": lh, "nodes": nx * ny}
+                for k, name in enumerate(("search_ms", "densify_ms")):
+                    off, on = stats(lv[False][:, l, k]), stats(lv[True][:, l, k])
+                    e[name] = {"off": off, "on": on, "on_over_off": round(on["median"] / off["median"], 3)}
+                rec["levels"].append(e)
+            rec["total_on_over_off"] = round(rec["total_ms"]["on"]["median"] / rec["total_ms"]["off"]["median"], 3)
+            out["shapes"].append(rec)
+            print(json.dumps(rec), flush=True)
+    if a.parent_root:
+        runs = {"this": {}, "parent": {}}
+        for _ in range(2):
+            for side, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--patnorm-child", root, "--reps", str(a.reps)],
+                                   capture_output=True, text=True, timeout=600, cwd=root)
+                if r.returncode != 0:
+                    raise SystemExit(f"the {side} child failed:\n{r.stdout}\n{r.stderr}")
+                line = [ln for ln in r.stdout.splitlines() if ln.startswith("DEFAULT ")][-1]
+                for shape, d in json.loads(line[8:]).items():
+                    for key, v in d.items():
+                        runs[side].setdefault((shape, key), []).extend(v)
+        out["default_paths"] = {}
+        for (shape, key), v in runs["this"].items():
+            t, q = stats(v), stats(runs["parent"][shape, key])
+            bar = bool(t["median"] <= q["median"] + (q["max"] - q["min"]))
+            out["default_paths"].setdefault(shape, {})[key] = {
+                "this_tree": t, "parent": q, "bar_median_within_parent_median_plus_spread": bar}
+            ok &= bar
+        print(json.dumps(out["default_paths"]), flush=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "c2fflow_patnorm_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "c2fflow_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/c2fflow_bench.json (c2fflow_patnorm_bench.json)")
+    ap.add_argument("--patnorm", action="store_true", help="measure the cost of patch-mean normalisation instead")
+    ap.add_argument("--patnorm-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.default_child:
         return default_child(a.default_child, a.reps)
+    if a.patnorm_child:
+        return patnorm_child(a.patnorm_child, a.reps)
     if a.reps < 7:
         ap.error("at least 7 runs each")
+    if a.patnorm:
+        return patnorm_main(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "c2fflow_bench.json")
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
