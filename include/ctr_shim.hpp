@@ -580,6 +580,13 @@ class CoarseFlowClass {
   }
   // patch-mean normalisation of the next runs (ictr_c2fflow_set_patnorm); default off
   void SetPatnorm(bool on) { check(ictr_c2fflow_set_patnorm(h_, on ? 1 : 0), "SetPatnorm"); }
+  // the 1-D form of the next runs, for a rectified stereo pair (ictr_c2fflow_set_x_only): v is +0.0; default off
+  void SetXOnly(bool on) { check(ictr_c2fflow_set_x_only(h_, on ? 1 : 0), "SetXOnly"); }
+  bool XOnly() const {
+    int on = 0;
+    check(ictr_c2fflow_get_x_only(h_, &on), "XOnly");
+    return on != 0;
+  }
   // a, b: pyramids of the object's size with levels 0 .. lv_f, padded by at least psz, a with gradient planes
   void Run(const Pyramid &a, const Pyramid &b, void *hip_stream = nullptr) {
     check(ictr_c2fflow_run(h_, a.handle(), b.handle(), hip_stream), "Run");

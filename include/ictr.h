@@ -998,6 +998,8 @@ int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on);
 int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
 /* the stage's patch-mean normalisation: its switch and the reader of the node bias */
 #include "ictr_c2f_patnorm.h"
+/* the stage's 1-D (x only) form for rectified stereo pairs: its switch */
+#include "ictr_c2f_xonly.h"
 
 #ifdef __cplusplus
 }

@@ -371,6 +371,11 @@ SIGNATURES_PATNORM = {
     "ictr_c2fflow_set_patnorm": (C.c_int, [VP, C.c_int]),
     "ictr_c2fflow_read_level_bias": (C.c_int, [VP, C.c_int, FP]),
 }
+# the coarse-to-fine flow's 1-D form (declared in include/ictr_c2f_xonly.h, which ictr.h includes)
+SIGNATURES_XONLY = {
+    "ictr_c2fflow_set_x_only": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_get_x_only": (C.c_int, [VP, C.POINTER(C.c_int)]),
+}
 
 _lib = None
 
@@ -414,7 +419,7 @@ def load():
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
-                              + list(SIGNATURES_PATNORM.items())):
+                              + list(SIGNATURES_PATNORM.items()) + list(SIGNATURES_XONLY.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,11 @@
 // (pf_level_search<.., MEAN>), and the kernel's tail takes every voting node's brightness offset, beta = mean(B at the
 // node's final position) - mean(T), with one more window pass (pf_window_sum), into the level's bias table; a node that is
 // lost or whose final position is out of view gets +0.0. restated by tests/patnorm_f32.py.
+//
+// XONLY is the 1-D form for rectified stereo pairs (DESIGN.md "The 1-D form"): the start is the x component of the coarser
+// field alone (ONE 4-byte load), the search is pf_level_search's XONLY rule at this level (min_det then carries min_hx),
+// the rejection is scalar, the MEAN tail stays in the node's row, and a node's y displacement is +0.0 to the bit.
+// Restated by tests/c2fdisp_f32.py.
 #include <math.h>
 #include <string.h>
 
@@ -37,7 +42,7 @@ struct C2fArgs {
   const float2 *coarse;          // the coarser level's dense field [ch][cw], NULL at the coarsest level
   int cw, ch;
   int P, maxiter;
-  float eps2, min_det, far2;     // stop when |dp|^2 < eps2; conditioning; (float)(P * P)
+  float eps2, min_det, far2;     // stop when |dp|^2 < eps2; conditioning (XONLY: min_hx); (float)(P * P)
   float *d;                      // [K][2] raw node displacements (the fill's input)
   unsigned char *lost, *status;  // [K], [K]
 };
@@ -46,7 +51,7 @@ struct C2fMeanArgs : C2fArgs {
   float *bias;  // [K] node brightness offsets
 };
 
-template <int NPL, int WPP, bool MEAN>
+template <int NPL, int WPP, bool MEAN, bool XONLY>
 __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> a) {
   constexpr int PPB = kWaves / WPP;  // nodes per workgroup
   __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
@@ -61,9 +66,13 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
   const float xl = (float)X, yl = (float)Y;
   float ix = 0.0f, iy = 0.0f;
   if (a.coarse) {
-    const float2 c = a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)];
-    ix = 2.0f * c.x;
-    iy = 2.0f * c.y;
+    if constexpr (XONLY) {  // y is not read and stays +0.0
+      ix = 2.0f * a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)].x;
+    } else {
+      const float2 c = a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)];
+      ix = 2.0f * c.x;
+      iy = 2.0f * c.y;
+    }
   }
   const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
   int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
@@ -73,12 +82,16 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
   if (WPP > 1 || st == ICTR_C2F_TRACKED) {
     const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
     int nit = 0;
-    const int why = pf_level_search<NPL, WPP, false, MEAN>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter,
+    const int why = pf_level_search<NPL, WPP, XONLY, MEAN>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter,
                                                            a.eps2, a.min_det, sSum, mean_t);
     if (why) st = why == PF_STOP_COND ? ICTR_C2F_HELD_COND : ICTR_C2F_HELD_VIEW;
     if (st == ICTR_C2F_TRACKED) {  // a runaway patch: further than P from its start, or not finite (a positive test)
       const float dx = px - ix, dy = py - iy;
-      if (!(dx * dx + dy * dy <= a.far2)) st = ICTR_C2F_HELD_FAR;
+      if constexpr (XONLY) {
+        if (!(dx * dx <= a.far2)) st = ICTR_C2F_HELD_FAR;
+      } else {
+        if (!(dx * dx + dy * dy <= a.far2)) st = ICTR_C2F_HELD_FAR;
+      }
     }
   }
   float beta = 0.0f;
@@ -105,19 +118,19 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
 }
 
 // the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
-template <bool MEAN>
+template <bool MEAN, bool XONLY>
 static void launch_c2f_level(const std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> &a, hipStream_t s) {
   const int npl = (a.P * a.P + 63) / 64;
   const dim3 blk(kBlock);
   if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
     return;
   }
   const dim3 g((a.K + kWaves - 1) / kWaves);
   if (npl <= 1)
-    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN, XONLY>), g, blk, 0, s, a);
   else
-    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY>), g, blk, 0, s, a);
 }
 
 }  // namespace ictr
@@ -152,6 +165,7 @@ struct ictr_c2fflow {
   float eps = 0.01f;
   int refine = 0;  // refiners exist for every level and hold their parameters
   int patnorm = 0;
+  int x_only = 0;  // the 1-D form: the XONLY kernels and the refinement along x
   int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
   std::vector<C2fLevel> lv;  // [lv_f + 1]
   DevBuf<unsigned char> status;
@@ -249,6 +263,16 @@ extern "C" int ictr_c2fflow_set_patnorm(ictr_c2fflow *c, int on) {
   c->patnorm = on ? 1 : 0;
   return ICTR_OK;
 }
+extern "C" int ictr_c2fflow_set_x_only(ictr_c2fflow *c, int on) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  c->x_only = on ? 1 : 0;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_get_x_only(const ictr_c2fflow *c, int *on) {
+  if (!c || !on) return fail(ICTR_ERR_INVALID, "c2fflow_get_x_only: c2fflow or on is NULL");
+  *on = c->x_only;
+  return ICTR_OK;
+}
 extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
   c->timing = on ? 1 : 0;
@@ -264,7 +288,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
       return fail(ICTR_ERR_INVALID, "c2fflow_run: level %d of the pyramids is %d x %d, of the object %d x %d", l,
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
   hipStream_t s = (hipStream_t)hip_stream;
-  const int refined = c->refine, patnorm = c->patnorm;
+  const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
   c->timed = c->timing;
   for (int l = c->lv_f; l >= 0; --l) {
     C2fLevel &L = c->lv[l];
@@ -286,7 +310,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
     a.P = c->psz;
     a.maxiter = c->maxiter;
     a.eps2 = pf.eps2;
-    a.min_det = pf.min_det;
+    a.min_det = x_only ? pf.min_hx : pf.min_det;
     a.far2 = (float)(c->psz * c->psz);
     if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
     a.status = L.status;
@@ -295,9 +319,14 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
       C2fMeanArgs m;
       static_cast<C2fArgs &>(m) = a;
       m.bias = L.bias;
-      launch_c2f_level<true>(m, s);
+      if (x_only)
+        launch_c2f_level<true, true>(m, s);
+      else
+        launch_c2f_level<true, false>(m, s);
+    } else if (x_only) {
+      launch_c2f_level<false, true>(a, s);
     } else {
-      launch_c2f_level<false>(a, s);
+      launch_c2f_level<false, false>(a, s);
     }
     if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
@@ -312,7 +341,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
       f.sign = 1;
       f.on_device = 1;
       f.data = ictr_flowdensify_device_ptr(L.dens.get());
-      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, &f, 0, l, s)) return rc;
+      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, &f, x_only, l, s)) return rc;
     }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
   }

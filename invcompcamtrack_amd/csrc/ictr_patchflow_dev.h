@@ -96,22 +96,23 @@ enum { PF_STOP_NONE = 0, PF_STOP_COND = 1, PF_STOP_VIEW = 2 };  // why a patch s
 // One wave per patch leaves at the first decision against it (and is not to be called with !ok). Two waves per patch
 // share barriers, which need a uniform loop structure: every patch of the workgroup runs every iteration slot, and one
 // that is not ok, stopped or converged only stops updating (its windows are the harmless in-plane one at (1,1)).
-// MEAN (2-D only) is patch-mean normalisation: T' = T - mean(T) once and r = T' - (I - mean(I)) in every iteration. The
-// sum of T joins the three sums of H in their one reduction, the sums of Gx and Gy are taken once in a second, and an
-// iteration keeps its single reduction, now of three: with s = sum G (T' - I), b = s + (sum I / n) sum G. The direct form
-// would need the frame mean before the residual, two reductions on the chain and in the two-wave form four barriers.
+// MEAN is patch-mean normalisation: T' = T - mean(T) once and r = T' - (I - mean(I)) in every iteration. The sum of T
+// joins the sums of H in their one reduction (of four; XONLY of three), the sums of Gx and Gy (XONLY: of Gx alone) are
+// taken once in a second, and an iteration keeps its single reduction, now of three (XONLY of two): with
+// s = sum G (T' - I), b = s + (sum I / n) sum G. The direct form would need the frame mean before the residual, two
+// reductions on the chain and in the two-wave form four barriers.
 // mean_t receives mean(T) = sum T / n (also when the patch is refused by the conditioning test).
 template <int NPL, int WPP, bool XONLY, bool MEAN>
 __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float xl, float yl, bool ok, float &px, float &py,
                                                int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4],
                                                float &mean_t) {
-  static_assert(!(MEAN && XONLY), "patch-mean normalisation is built for the 2-D search");
   const int n = P * P;
   const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
   const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);
   int off[NPL];
   float T[NPL], Gx[NPL], Gy[XONLY ? 1 : NPL];
-  float h[XONLY ? 2 : MEAN ? 4 : 3] = {};  // hxx, (hxy,) hyy(, sum T)
+  constexpr int NH = XONLY ? 2 : 3, NB = XONLY ? 1 : 2;  // the sums of H and of b; MEAN: sum T, sum I behind them
+  float h[MEAN ? NH + 1 : NH] = {};  // hxx, (hxy,) hyy(, sum T)
 #pragma unroll
   for (int i = 0; i < NPL; ++i) {
     const int q = slot0 + 64 * WPP * i;
@@ -130,17 +131,17 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       h[1] += Gx[i] * gyi;
       h[2] += gyi * gyi;
     }
-    if constexpr (MEAN) h[3] += T[i];
+    if constexpr (MEAN) h[NH] += T[i];
   }
   pf_patch_sum<WPP>(h, sSum);
-  float sg[2] = {};  // MEAN: sum Gx, sum Gy
+  float sg[NB] = {};  // MEAN: sum Gx(, sum Gy)
   if constexpr (MEAN) {
-    mean_t = h[3] / (float)n;
+    mean_t = h[NH] / (float)n;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
       T[i] = (slot0 + 64 * WPP * i < n) ? T[i] - mean_t : 0.0f;
       sg[0] += Gx[i];
-      sg[1] += Gy[i];
+      if constexpr (!XONLY) sg[1] += Gy[i];
     }
   }
   const float hxx = h[0], hxy = XONLY ? 0.0f : h[1], hyy = h[XONLY ? 1 : 2];
@@ -169,7 +170,7 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       if (WPP == 1) break;
     }
     const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
-    float b[XONLY ? 1 : MEAN ? 3 : 2] = {};  // bx, (by)(, sum I)
+    float b[MEAN ? NB + 1 : NB] = {};  // bx, (by)(, sum I)
     PFWin w[NPL];
 #pragma unroll
     for (int i = 0; i < NPL; ++i) w[i] = pf_load(L.b, tb.base + off[i], L.sw);  // all in flight before the first use
@@ -181,13 +182,13 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
       b[0] += Gx[i] * r;
       if constexpr (!XONLY) b[1] += Gy[i] * r;
-      if constexpr (MEAN) b[2] += in ? iv : 0.0f;
+      if constexpr (MEAN) b[NB] += in ? iv : 0.0f;
     }
     pf_patch_sum<WPP>(b, sSum);
     if constexpr (MEAN) {
-      const float mi = b[2] / (float)n;
+      const float mi = b[NB] / (float)n;
       b[0] = b[0] + mi * sg[0];
-      b[1] = b[1] + mi * sg[1];
+      if constexpr (!XONLY) b[1] = b[1] + mi * sg[1];
     }
     if (run) {
       float dx, dy = 0.0f;

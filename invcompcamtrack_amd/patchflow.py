@@ -554,15 +554,19 @@ def _c2f_sample(plane, pad, psz, x, y):
     return ((r0 * r1) * a.astype(np.float64) + ((1 - r0) * r1) * b + (r0 * (1 - r1)) * c) + ((1 - r0) * (1 - r1)) * d
 
 
-def _c2f_init(coarse, w, h, step):
+def _c2f_init(coarse, w, h, step, x_only=False):
     """Step 2 of c2f_flow_host: (ny, nx, 2) float32 starts of a level's nodes from the coarser level's field (None: the
-    coarsest level, zeros). Nearest neighbour at (min(X >> 1, w' - 1), min(Y >> 1, h' - 1)), times 2: exact in f32."""
+    coarsest level, zeros). Nearest neighbour at (min(X >> 1, w' - 1), min(Y >> 1, h' - 1)), times 2: exact in f32.
+    x_only: the y component of the coarser field is not read, and a start's y is +0.0."""
     xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
     if coarse is None:
         return np.zeros((len(ys), len(xs), 2), np.float32)
     coarse = np.asarray(coarse, np.float32)
     ch, cw = coarse.shape[:2]
-    return np.float32(2) * coarse[np.minimum(ys >> 1, ch - 1)][:, np.minimum(xs >> 1, cw - 1)]
+    init = np.float32(2) * coarse[np.minimum(ys >> 1, ch - 1)][:, np.minimum(xs >> 1, cw - 1)]
+    if x_only:
+        init[..., 1] = np.float32(0)
+    return init
 
 
 def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm=False):
@@ -634,6 +638,69 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
     return d, status, m
 
 
+def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm=False):
+    """Step 3 of c2f_flow_host(x_only=True) at level l from the starts `init` (ny, nx, 2) float32 whose y is +0.0: the
+    1-D rule of k_patchdisp at this level alone. hxx = sum Gx^2, hyy = sum Gy^2, tr = hxx + hyy; the node is held by
+    conditioning iff not tr > 0 or not hxx > min_hx tr; an iteration tests the view at (X + p, Y), samples I there, takes
+    dx = sum Gx (T - I) / hxx (patnorm: T - mean(T) and I - mean(I)), p += dx, and stops when dx^2 < eps^2; the rejection
+    is not (p - init.x)^2 <= psz^2. y never moves: d = (p, +0.0) when tracked, (init.x, +0.0) when held. Returns what
+    _c2f_search_host returns; margins["det"] is | hxx / tr - min_hx |, "eps" | |dx| - eps |, "far" | |p - init.x| - psz |."""
+    w, h = _c2f_level_size(pyr_a, l)
+    xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
+    ny, nx = len(ys), len(xs)
+    d = np.full((ny, nx, 2), np.nan, np.float32)
+    status = np.zeros((ny, nx), np.uint8)
+    m = {k: np.full((ny, nx), np.inf) for k in ("eps", "view", "far", "det")}
+
+    def in_view(j, i, x):
+        near = min(abs(x), abs(x - w)) if np.isfinite(x) else np.inf
+        if np.isfinite(near):
+            m["view"][j, i] = min(m["view"][j, i], near)
+        return bool(0 <= x <= w)
+
+    for j, Y in enumerate(ys):
+        for i, X in enumerate(xs):
+            ix = float(init[j, i, 0])
+            if not (np.isfinite(ix) and in_view(j, i, X + ix)):
+                continue  # lost
+            d[j, i] = (init[j, i, 0], np.float32(0))
+            T = _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y))
+            Gx = _c2f_sample(pyr_a.dx[l], pyr_a.pad, psz, float(X), float(Y))
+            Gy = _c2f_sample(pyr_a.dy[l], pyr_a.pad, psz, float(X), float(Y))
+            hxx, hyy = (Gx * Gx).sum(), (Gy * Gy).sum()
+            tr = hxx + hyy
+            if tr > 0:
+                m["det"][j, i] = abs(hxx / tr - min_hx)
+            if not (tr > 0) or not (hxx > min_hx * tr):
+                status[j, i] = C2F_HELD_COND
+                continue
+            if patnorm:
+                T = T - T.mean()
+            p = ix
+            st = C2F_TRACKED
+            for _ in range(maxiter):
+                if not in_view(j, i, X + p):
+                    st = C2F_HELD_VIEW
+                    break
+                I = _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, X + p, float(Y))
+                r = T - (I - I.mean()) if patnorm else T - I
+                dx = (Gx * r).sum() / hxx
+                p += dx
+                m["eps"][j, i] = min(m["eps"][j, i], abs(abs(dx) - eps))
+                if dx * dx < eps * eps:
+                    break
+            if st == C2F_TRACKED:
+                far = abs(p - ix)
+                if np.isfinite(far):
+                    m["far"][j, i] = abs(far - psz)
+                if not (far * far <= psz * psz):
+                    st = C2F_HELD_FAR
+            status[j, i] = st
+            if st == C2F_TRACKED:
+                d[j, i, 0] = p
+    return d, status, m
+
+
 def _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins=None):
     """The node bias of c2f_flow_host under patnorm at level l: (ny, nx) f64. A node with status != 0 has a final float32
     d (a tracked node's p, a held node's init); where its final position (X, Y) + d passes the search's view test,
@@ -688,7 +755,7 @@ def _c2f_plane(pyr, l):
 
 
 def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, min_det=1e-4, densify=None, refine=None,
-                  _stages=None, patnorm=False):
+                  _stages=None, patnorm=False, x_only=False, min_hx=1e-2):
     """Coarse-to-fine dense flow A -> B: the definition (build-defined; NumPy, f64 arithmetic on the f32 planes; DESIGN.md
     §4 "Coarse-to-fine dense flow" states the rule). pyr_a, pyr_b: host pyramids with ``.img / .dx / .dy[l]`` padded by
     ``.pad >= psz`` (oracle.Pyramid's shape). For l = lv_f .. 0: nodes at step // 2 + k step of the level's own size; a
@@ -702,21 +769,29 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     removes the patch means (_c2f_search_host), every node gets its brightness offset beta (_c2f_bias_host), and the
     densifier's vote of a node weighs |Bw - A - beta| (densify_flow_host's bias). The refinement is unchanged: its
     brightness term still sees the offset.
+    x_only: the 1-D form for a rectified stereo pair (DESIGN.md "The 1-D form"). A node starts from the x component of
+    the coarser field alone, the search is _c2f_search_x_host (k_patchdisp's rule at the level, conditioning by min_hx; a
+    held node's status values keep their meaning), the densifier is called unchanged on the table whose y is +0.0, and
+    the refinement is refine_flow_host(..., x_only=True). Every level's field has +0.0 bits in its y component. It
+    combines with patnorm, whose bias is taken at (X + d.x, Y).
     _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
     "margins" (_c2f_search_host's), "field" (U_l) and "bias" (the node bias, None without patnorm)."""
     lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine)
     U = None
     for l in range(lv_f, -1, -1):
         w, h = _c2f_level_size(pyr_a, l)
-        init = _c2f_init(U, w, h, step)
-        d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm)
+        init = _c2f_init(U, w, h, step, x_only)
+        if x_only:
+            d, status, margins = _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm)
+        else:
+            d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm)
         lost = status == C2F_LOST
         bias = _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins) if patnorm else None
         A, B = _c2f_plane(pyr_a, l), _c2f_plane(pyr_b, l)
         U = densify_flow_host(A, B, np.where(lost[..., None], np.float32(0), d), lost, step, psz, bias=bias,
                               **(densify or {}))
         if refine is not None:
-            U = refine_flow_host(A, B, U, **refine)
+            U = refine_flow_host(A, B, U, x_only=bool(x_only), **refine)
         if _stages is not None:
             filled = d.copy()
             _dense_from_nodes(filled, lost, w, h, step)
@@ -728,10 +803,12 @@ class CoarseToFineFlow:
     """c2f_flow_host on the device (``ictr_c2fflow_*``: k_c2f_level, the grid's fill, k_densify and optionally the
     refinement per level) for w x h frames and levels lv_f .. 0. densify / refine: the per-level parameters
     (DENSIFY_DEFAULTS' / REFINE_DEFAULTS' names; refine=None: no refinement). patnorm: c2f_flow_host's patch-mean
-    normalisation (k_c2f_level's MEAN forms with the node bias, k_densify<true>). ``run`` enqueues and returns; ``dense``
+    normalisation (k_c2f_level's MEAN forms with the node bias, k_densify<true>). x_only: c2f_flow_host's 1-D form for a
+    rectified stereo pair (k_c2f_level's XONLY forms, the refinement along x; v is +0.0 at every level). ``run`` enqueues and returns; ``dense``
     (level 0's field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 
-    def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False):
+    def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False,
+                 x_only=False):
         dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
         unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
         if unknown:
@@ -752,6 +829,9 @@ class CoarseToFineFlow:
         self.patnorm = bool(patnorm)
         if self.patnorm:
             check(L.ictr_c2fflow_set_patnorm(self._h, 1))
+        self.x_only = bool(x_only)
+        if self.x_only:
+            check(L.ictr_c2fflow_set_x_only(self._h, 1))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -804,7 +884,7 @@ class CoarseToFineFlow:
 
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
     """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call
-    (params: its keywords, patnorm among them)."""
+    (params: its keywords, patnorm and x_only among them)."""
     lv_f = pyr_a.lv_f if lv_f is None else lv_f
     return CoarseToFineFlow(pyr_a.w, pyr_a.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
 

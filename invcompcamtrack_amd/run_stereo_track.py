@@ -2,7 +2,8 @@
 
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
          [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
-         [--refine [alpha,gamma,delta,outer,sor,omega]] [--densify [minerr,power]] [--flow grid|c2f] [--patnorm]
+         [--refine [alpha,gamma,delta,outer,sor,omega]] [--densify [minerr,power]] [--flow grid|c2f|c2f-1d]
+         [--patnorm]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
@@ -12,8 +13,9 @@ the 2-D tracker with y dropped. --refine refines every grid's dense field per pi
 densifies every grid photometrically first (patchflow.FlowDensifier; without a value its defaults 2,1): grid -> densify
 -> refine. --flow c2f computes every field coarse to fine instead (patchflow.CoarseToFineFlow: search, densification and,
 with --refine, refinement per pyramid level; --densify and --refine then give the per-level parameters; not with
---disparity 1d). --patnorm switches on the coarse-to-fine flow's patch-mean normalisation, for cameras or frames of
-differing brightness (with --flow c2f only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+--disparity 1d). --flow c2f-1d is --flow c2f with the stereo pair searched along x only (CoarseToFineFlow's x_only; the
+temporal fields stay 2-D; --disparity is not consulted). --patnorm switches on the coarse-to-fine flow's patch-mean normalisation, for cameras or frames of
+differing brightness (with --flow c2f or c2f-1d only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -32,9 +34,9 @@ from . import stereotrack as S
 
 def dense_fields_of(tracker):
     """The dense fields of a StereoPointTracker built with keep_grids=True, in the host function's layout: of its
-    coarse-to-fine objects with flow="c2f", else of its refiners when it refines, else of its densifiers when it
+    coarse-to-fine objects with flow="c2f" or "c2f-1d", else of its refiners when it refines, else of its densifiers when it
     densifies, else of its grids."""
-    g = (tracker.flows if tracker.flow == "c2f" else tracker.refiners if tracker.refine is not None else
+    g = (tracker.flows if tracker.flow in ("c2f", "c2f-1d") else tracker.refiners if tracker.refine is not None else
          tracker.densifiers if tracker.densify is not None else tracker.grids)
     lr = [-x["lr"].dense()[:, :, 0] for x in g]  # a left -> right grid is the script's -imgs_d[fr][0]
     rl = [np.ascontiguousarray(x["rl"].dense()[:, :, 0]) for x in g]
@@ -82,12 +84,12 @@ def main(argv=None):
     ap.add_argument("--disparity", choices=("2d", "1d"), default="2d")
     ap.add_argument("--refine", nargs="?", const="", default=None, type=refine_params)
     ap.add_argument("--densify", nargs="?", const="", default=None, type=densify_params)
-    ap.add_argument("--flow", choices=("grid", "c2f"), default="grid")
+    ap.add_argument("--flow", choices=("grid", "c2f", "c2f-1d"), default="grid")
     ap.add_argument("--patnorm", action="store_true")
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
     if a.flow == "c2f" and a.disparity == "1d":
-        ap.error("--flow c2f with --disparity 1d: the 1-D form of the coarse-to-fine flow is not built")
-    if a.patnorm and a.flow != "c2f":
+        ap.error("--flow c2f with --disparity 1d: the 1-D form of the coarse-to-fine flow is --flow c2f-1d")
+    if a.patnorm and a.flow not in ("c2f", "c2f-1d"):
         ap.error("--patnorm needs --flow c2f: patch-mean normalisation is built for the coarse-to-fine flow alone")
     th = dict(th_ratio=a.th_ratio, th_abs=a.th_abs)
     if a.fields:

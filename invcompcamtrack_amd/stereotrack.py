@@ -297,25 +297,30 @@ class StereoPointTracker:
     patchflow.CoarseToFineFlow objects instead (the stereo ones 2-D, y dropped by the window): no grid, densifier or
     refiner of the tracker's own is made; densify and refine are then the per-level parameters (densify=None: the
     densifier's defaults), and keep_grids=True keeps the objects in ``flows`` (same layout). disparity="1d" is refused
-    with flow="c2f": the 1-D form is not built. patnorm=True switches on the coarse-to-fine objects' patch-mean
-    normalisation (CoarseToFineFlow's patnorm: for a right camera or a next frame of another brightness); it is
-    refused with flow="grid", whose whole-pyramid kernels have no such form."""
+    with flow="c2f": its stereo fields are 2-D; the 1-D form is flow="c2f-1d". flow="c2f-1d" is flow="c2f" with the
+    stereo pair (lr, rl) computed by CoarseToFineFlow(x_only=True), the 1-D search along x per level (vertical edges
+    kept, tilted structure not misleading, v = +0.0), and the four temporal fields 2-D as before; patnorm, densify,
+    refine and keep_grids behave as with flow="c2f", and `disparity` is not consulted. patnorm=True switches on the coarse-to-fine objects' patch-mean
+    normalisation (CoarseToFineFlow's patnorm: for a right camera or a next frame of another brightness); it
+    needs flow="c2f" or "c2f-1d" and is refused with flow="grid", whose whole-pyramid kernels have no such form."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
                  xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
-        if flow not in ("grid", "c2f"):
-            raise ValueError(f"flow is 'grid' (a FlowGrid per field) or 'c2f' (a CoarseToFineFlow per field), not {flow!r}")
+        if flow not in ("grid", "c2f", "c2f-1d"):
+            raise ValueError("flow is 'grid' (a FlowGrid per field), 'c2f' (a CoarseToFineFlow per field) or 'c2f-1d' (the "
+                             f"same with the stereo pair searched along x only), not {flow!r}")
         if flow == "c2f" and disparity == "1d":
-            raise ValueError("flow='c2f' with disparity='1d': the 1-D form of the coarse-to-fine flow is not built")
-        if patnorm and flow != "c2f":
+            raise ValueError("flow='c2f' with disparity='1d': the 1-D form of the coarse-to-fine flow is flow='c2f-1d'")
+        if patnorm and flow not in ("c2f", "c2f-1d"):
             raise ValueError("patnorm=True needs flow='c2f': patch-mean normalisation is built for the coarse-to-fine flow "
                              "alone, not for the flow grids of flow='grid'")
         self.flow = flow
         self.patnorm = bool(patnorm)
         self.flows = []
         self._fsets = [None, None]
+        self._xsets = [None, None]  # flow="c2f-1d": the stereo pair's objects
         self.disparity = disparity
         self.refine = None if refine is None else dict(refine)
         self.refiners = []
@@ -332,10 +337,9 @@ class StereoPointTracker:
         self._pyr = [None, None]  # (left, right) of the previous frame and of the one before, reused in turn
         self._sets = [None, None]
 
-    def _set(self, cache, k, make):
+    def _set(self, cache, k, make, names=("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")):
         """Frame k's six objects of one kind, by name: new ones when the grids are kept, else one of the two sets of
         `cache`, reused in turn."""
-        names = ("lr", "rl", "l_fwd", "l_bwd", "r_fwd", "r_bwd")
         if self.keep_grids:
             return {n: make() for n in names}
         if cache[k & 1] is None:
@@ -366,7 +370,7 @@ class StereoPointTracker:
             ql, qr = self._pyr[(k - 1) & 1]
             fields += [("l_fwd", ql, pl, False), ("l_bwd", pl, ql, False), ("r_fwd", qr, pr, False),
                        ("r_bwd", pr, qr, False)]
-        if self.flow == "c2f":
+        if self.flow in ("c2f", "c2f-1d"):
             return self._push_c2f(k, fields)
         g = self._set(self._sets, k, lambda: FlowGrid(self.w, self.h, self.step))
         z = r = None  # made when the stereo group reaches them
@@ -393,11 +397,19 @@ class StereoPointTracker:
         self.nframes = k + 1
 
     def _push_c2f(self, k, fields):
-        """push_frames with flow="c2f": one CoarseToFineFlow per field, handed to the window."""
+        """push_frames with flow="c2f" or "c2f-1d": one CoarseToFineFlow per field, handed to the window. With "c2f-1d"
+        the stereo pair's objects search along x only; they are a set of their own."""
         from .patchflow import CoarseToFineFlow
-        c = self._set(self._fsets, k, lambda: CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter,
-                                                                self.eps, densify=self.densify, refine=self.refine,
-                                                                patnorm=self.patnorm))
+
+        def make(x_only=False):
+            return CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter, self.eps,
+                                    densify=self.densify, refine=self.refine, patnorm=self.patnorm, x_only=x_only)
+
+        if self.flow == "c2f-1d":
+            c = dict(self._set(self._fsets, k, make, ("l_fwd", "l_bwd", "r_fwd", "r_bwd")))
+            c.update(self._set(self._xsets, k, lambda: make(True), ("lr", "rl")))
+        else:
+            c = self._set(self._fsets, k, make)
         for n, a, b, _ in fields:
             c[n].run(a, b)
         if k == 0:

@@ -22,6 +22,12 @@ in turn; per level the search and densification medians of each and their ratio,
 --parent-root then measures the default paths this option must leave alone, CoarseToFineFlow.run with patnorm off (psz 8
 and 15) and FlowDensifier.run (psz 15), in child processes of the two builds in turn (two each). The bar (exit status 1):
 this tree's median exceeds the parent's by at most the parent's own max - min spread.
+
+  python tools/c2fflow_bench.py --x-only [--reps 7] [--out profiles/c2fflow_xonly_bench.json] [--parent-root DIR]
+
+The 1-D form against the 2-D one in the same way, on a stereo pair (the gratings move along x only): two objects per shape
+and patch size, x_only off and on, run in turn. Recorded without a bar. --parent-root measures CoarseToFineFlow.run with
+x_only and patnorm off (psz 8 and 15) and FlowGrid.compute_x (psz 15) on the same pair, with the same bar.
 """
 import argparse
 import json
@@ -76,9 +82,9 @@ def default_child(root, reps):
     print("DEFAULT " + json.dumps(out), flush=True)
 
 
-def patnorm_child(root, reps):
-    """Runs in a child process: CoarseToFineFlow.run (no patnorm keyword: the parent has none) and FlowDensifier.run of
-    the tree at `root`, HIP events around each."""
+def option_child(root, reps, option):
+    """Runs in a child process: CoarseToFineFlow.run (no keyword of the option: the parent has none) and, for "patnorm",
+    FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair, of the tree at `root`, HIP events around each."""
     sys.path.insert(0, root)
     import torch
 
@@ -90,10 +96,15 @@ def patnorm_child(root, reps):
         fr = frames(w, h)
         rec = {}
         for psz in PSZS:
-            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            second = fr[0][1] if option == "x_only" else fr[1][0]
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(second, LV_F, psz, True)
             c = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz)
             rec[f"c2f_run_psz{psz}_ms"] = [float(_timed(torch, lambda: c.run(pa, pb))) for _ in range(reps + 1)][1:]
-            if psz == PSZS[1]:
+            if psz == PSZS[1] and option == "x_only":
+                grid = pf.FlowGrid(w, h, STEP)
+                rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
+                                                for _ in range(reps + 1)][1:]
+            elif psz == PSZS[1]:
                 grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
                 grid.compute(pa, pb, psz=psz, lv_f=LV_F)
                 rec["flowdensifier_run_ms"] = [float(_timed(torch, lambda: dz.run(grid, pa, pb, psz)))
@@ -102,7 +113,8 @@ def patnorm_child(root, reps):
     print("DEFAULT " + json.dumps(out), flush=True)
 
 
-def patnorm_main(a):
+def option_main(a, option):
+    """--patnorm / --x-only: the option off and on in turn, then the default paths against the parent's."""
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -112,14 +124,16 @@ def patnorm_main(a):
     from tools.patchdisp_bench import frames, stats
     if ic.device_count() < 1:
         raise SystemExit("no HIP device: nothing is measured without one")
-    out = {"bench": "c2fflow_patnorm", "step": STEP, "lv_f": LV_F, "reps": a.reps, "densify": pf.DENSIFY_DEFAULTS,
+    name = {"patnorm": "c2fflow_patnorm", "x_only": "c2fflow_xonly"}[option]
+    out = {"bench": name, "step": STEP, "lv_f": LV_F, "reps": a.reps, "densify": pf.DENSIFY_DEFAULTS,
            "refine": None, "shapes": []}
     ok = True
     for w, h in SHAPES:
         fr = frames(w, h)
         for psz in PSZS:
-            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
-            cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, patnorm=on) for on in (False, True)}
+            second = fr[0][1] if option == "x_only" else fr[1][0]
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(second, LV_F, psz, True)
+            cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, **{option: on}) for on in (False, True)}
             levels, total = {False: [], True: []}, {False: [], True: []}
             for rep in range(a.reps + 1):  # the first round warms everything up
                 for on, c in cs.items():
@@ -145,7 +159,8 @@ def patnorm_main(a):
         runs = {"this": {}, "parent": {}}
         for _ in range(2):
             for side, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--patnorm-child", root, "--reps", str(a.reps)],
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--option-child", root, "--option", option,
+                                    "--reps", str(a.reps)],
                                    capture_output=True, text=True, timeout=600, cwd=root)
                 if r.returncode != 0:
                     raise SystemExit(f"the {side} child failed:\n{r.stdout}\n{r.stderr}")
@@ -161,7 +176,7 @@ def patnorm_main(a):
                 "this_tree": t, "parent": q, "bar_median_within_parent_median_plus_spread": bar}
             ok &= bar
         print(json.dumps(out["default_paths"]), flush=True)
-    with open(a.out or os.path.join(ROOT, "profiles", "c2fflow_patnorm_bench.json"), "w") as f:
+    with open(a.out or os.path.join(ROOT, "profiles", name + "_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     return 0 if ok else 1
@@ -170,20 +185,22 @@ def patnorm_main(a):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None, help="default: profiles/c2fflow_bench.json (c2fflow_patnorm_bench.json)")
+    ap.add_argument("--out", default=None, help="default: profiles/c2fflow_bench.json (c2fflow_patnorm_bench.json, c2fflow_xonly_bench.json)")
     ap.add_argument("--patnorm", action="store_true", help="measure the cost of patch-mean normalisation instead")
-    ap.add_argument("--patnorm-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--x-only", action="store_true", help="measure the 1-D form against the 2-D one instead")
+    ap.add_argument("--option-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only"), help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.default_child:
         return default_child(a.default_child, a.reps)
-    if a.patnorm_child:
-        return patnorm_child(a.patnorm_child, a.reps)
+    if a.option_child:
+        return option_child(a.option_child, a.reps, a.option)
     if a.reps < 7:
         ap.error("at least 7 runs each")
-    if a.patnorm:
-        return patnorm_main(a)
+    if a.patnorm or a.x_only:
+        return option_main(a, "x_only" if a.x_only else "patnorm")
     a.out = a.out or os.path.join(ROOT, "profiles", "c2fflow_bench.json")
     sys.path.insert(0, ROOT)
     import numpy as np
