@@ -896,8 +896,8 @@ typedef struct ictr_flowrefine ictr_flowrefine;
 /* 4 <= w, h <= 32768 */
 int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h);
 void ictr_flowrefine_destroy(ictr_flowrefine *r);
-/* defaults 16, 13, 4.5, 8, 5, 1.6. Refused: a negative or non-finite value, n_outer or n_sor above 1024, omega outside
- * (0, 2). n_outer = 0 returns the source's bits. */
+/* defaults 16, 13, 4.5, 8, 5, 1.6. Refused: a negative or non-finite value, alpha = 0 (no coupling: 0 / 0 at every pixel
+ * without data), n_outer or n_sor above 1024, omega outside (0, 2). n_outer = 0 returns the source's bits. */
 int ictr_flowrefine_set_params(ictr_flowrefine *r, float alpha, float gamma, float delta, int n_outer, int n_sor,
                                float omega);
 /* src: an ICTR_FIELD_FLOW in host memory (checked for finiteness and copied before the call returns; a value that is not

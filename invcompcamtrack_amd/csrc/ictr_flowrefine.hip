@@ -280,10 +280,10 @@ extern "C" int ictr_flowrefine_create(ictr_flowrefine **out, int w, int h) {
 extern "C" int ictr_flowrefine_set_params(ictr_flowrefine *r, float alpha, float gamma, float delta, int n_outer, int n_sor,
                                           float omega) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
-  if (!isfinite(alpha) || !isfinite(gamma) || !isfinite(delta) || !isfinite(omega) || alpha < 0 || gamma < 0 || delta < 0 ||
-      n_outer < 0 || n_sor < 0 || n_outer > 1024 || n_sor > 1024 || !(omega > 0.0f) || !(omega < 2.0f))
+  if (!isfinite(alpha) || !isfinite(gamma) || !isfinite(delta) || !isfinite(omega) || !(alpha > 0.0f) || gamma < 0 ||
+      delta < 0 || n_outer < 0 || n_sor < 0 || n_outer > 1024 || n_sor > 1024 || !(omega > 0.0f) || !(omega < 2.0f))
     return fail(ICTR_ERR_INVALID,
-                "flowrefine_set_params: finite alpha, gamma, delta >= 0, 0 <= n_outer, n_sor <= 1024, 0 < omega < 2");
+                "flowrefine_set_params: finite alpha > 0, gamma, delta >= 0, 0 <= n_outer, n_sor <= 1024, 0 < omega < 2");
   r->alpha = alpha;
   r->gamma = gamma;
   r->delta = delta;

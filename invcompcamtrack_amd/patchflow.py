@@ -329,8 +329,8 @@ def refine_flow_host(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_ou
     h, w = A.shape
     if B.shape != A.shape or f0.shape != (h, w, 2) or w < 4 or h < 4:
         raise ValueError("refine_flow_host needs two (H, W) frames and an (H, W, 2) flow, H, W >= 4")
-    if not (0 < omega < 2) or min(alpha, gamma, delta, n_outer, n_sor) < 0:
-        raise ValueError("refine_flow_host: negative parameter, or omega outside (0, 2)")
+    if not (0 < omega < 2) or not alpha > 0 or min(gamma, delta, n_outer, n_sor) < 0:
+        raise ValueError("refine_flow_host: negative parameter, alpha <= 0, or omega outside (0, 2)")
     if n_outer == 0:
         return f0.copy()
     u, v = f0[..., 0].astype(np.float64), f0[..., 1].astype(np.float64)
@@ -736,6 +736,8 @@ def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine):
     lv_f = have if lv_f is None else int(lv_f)
     if not 0 <= lv_f <= have:
         raise ValueError(f"c2f flow: lv_f is {lv_f}, the pyramids have levels 0 .. {have}")
+    if refine is not None and not dict(REFINE_DEFAULTS, **refine)["alpha"] > 0:
+        raise ValueError("c2f flow: the refinement needs alpha > 0")
     for l in range(lv_f + 1):
         w, h = _c2f_level_size(pyr_a, l)
         if _c2f_level_size(pyr_b, l) != (w, h):

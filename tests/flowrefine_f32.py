@@ -2,7 +2,7 @@
 the kernels' operation order (every product and sum rounded to f32, nothing contracted), the coefficient stage tile by
 tile with the kernel's 16 x 16 tiles and 2-pixel halo. It is written from the kernel, not from the host function: the
 CPU module measures its distance to patchflow.refine_flow_host (the definition, f64), and the GPU tests hold the device
-to 4 x that distance.
+to 4 x that distance and, stage plane by stage plane, to this file's bits.
 
 `defect` injects one mistake a kernel of this shape can make; test_flowrefine_cpu.py shows that each is seen:
   "colour"   the half-sweeps run colour 1 first
@@ -11,6 +11,10 @@ to 4 x that distance.
   "inside"   the inside mask is left out of the data weights
   "edge"     an edge weight is its own pixel's s, not the mean of the two
   "clamp"    the warp position is not clamped (the taps are, so that the restatement can still index)
+and two that the tolerances of the stage checks need not see and a comparison of bits does:
+  "fused"    a11, a12, a22 with their outer sum contracted: w0 * (..) + wg * (..) as one product-sum rounded once (formed
+             in f64, where both products of f32 factors are exact), which is what a build that lost -ffp-contract=off does
+  "border2"  the second derivatives are also zero in column / row 1 and w - 2 / h - 2
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ F = np.float32
 TILE, HALO = 16, 2
 EPS2 = F(1e-3) * F(1e-3)
 ZETA2 = F(0.1) * F(0.1)
-DEFECTS = ("colour", "old_du", "halo1", "inside", "edge", "clamp")
+DEFECTS = ("colour", "old_du", "halo1", "inside", "edge", "clamp", "fused", "border2")
 STAGES = ("bw", "a11", "a12", "a22", "b1", "b2", "wr", "wd", "du", "dv", "u", "v")
 
 
@@ -71,6 +75,8 @@ class _T:
         X, Y = gx0 + np.arange(side), gy0 + np.arange(side)
         self.bx = ((X <= 0) | (X >= w - 1))[None, :]
         self.by = ((Y <= 0) | (Y >= h - 1))[:, None]
+        self.bx2 = ((X <= 1) | (X >= w - 2))[None, :]  # the "border2" defect
+        self.by2 = ((Y <= 1) | (Y >= h - 2))[:, None]
 
     def dx(self, p):
         out = np.zeros_like(p)
@@ -81,6 +87,12 @@ class _T:
         out = np.zeros_like(p)
         out[1:-1, :] = F(0.5) * (p[2:, :] - p[:-2, :])
         return np.where(self.by, F(0), out)
+
+
+def _fused(a, b, c, d):
+    """a * b + c * d rounded once."""
+    f64 = np.float64
+    return (a.astype(f64) * b.astype(f64) + c.astype(f64) * d.astype(f64)).astype(F)
 
 
 def coef(A, bw, u, v, alpha, gamma, delta, defect=None):
@@ -97,6 +109,8 @@ def coef(A, bw, u, v, alpha, gamma, delta, defect=None):
             tb, ta, tu, tv = (_tile(p, gx0, gy0, halo) for p in (bw, A, u, v))
             Ix, Iy, Iz = T.dx(tb), T.dy(tb), tb - ta
             Ixx, Ixy, Iyy = T.dx(Ix), T.dy(Ix), T.dy(Iy)
+            if defect == "border2":
+                Ixx, Ixy, Iyy = np.where(T.bx2, F(0), Ixx), np.where(T.by2, F(0), Ixy), np.where(T.by2, F(0), Iyy)
             Ixz, Iyz = Ix - T.dx(ta), Iy - T.dy(ta)
             n0 = one / ((Ix * Ix + Iy * Iy) + ZETA2)
             n1 = one / ((Ixx * Ixx + Ixy * Ixy) + ZETA2)
@@ -112,6 +126,10 @@ def coef(A, bw, u, v, alpha, gamma, delta, defect=None):
             a11 = w0 * (Ix * Ix) + wg * (n1 * (Ixx * Ixx) + n2 * (Ixy * Ixy))
             a12 = w0 * (Ix * Iy) + wg * (n1 * (Ixx * Ixy) + n2 * (Ixy * Iyy))
             a22 = w0 * (Iy * Iy) + wg * (n1 * (Ixy * Ixy) + n2 * (Iyy * Iyy))
+            if defect == "fused":
+                a11, a12, a22 = (_fused(w0, p, wg, q) for p, q in ((Ix * Ix, n1 * (Ixx * Ixx) + n2 * (Ixy * Ixy)),
+                                                                   (Ix * Iy, n1 * (Ixx * Ixy) + n2 * (Ixy * Iyy)),
+                                                                   (Iy * Iy, n1 * (Ixy * Ixy) + n2 * (Iyy * Iyy))))
             b1 = -(w0 * (Ix * Iz) + wg * (n1 * (Ixx * Ixz) + n2 * (Ixy * Iyz)))
             b2 = -(w0 * (Iy * Iz) + wg * (n1 * (Ixy * Ixz) + n2 * (Iyy * Iyz)))
             ux, uy, vx, vy = T.dx(tu), T.dy(tu), T.dx(tv), T.dy(tv)
