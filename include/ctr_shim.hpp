@@ -565,8 +565,15 @@ class FlowDensifyClass {
 // FlowRefineClass::Run and the stereo track window.
 class CoarseFlowClass {
  public:
-  CoarseFlowClass(int w, int h, int lv_f, int step = 4, int psz = 8) : h_(nullptr) {
-    check(ictr_c2fflow_create(&h_, w, h, lv_f, step, psz), "CoarseFlowClass");
+  // lv_l: the finest level (ictr_c2fflow_create_lvl); above 0 the runs stop there and Result / Field are that level's field
+  // up-sampled to w x h
+  CoarseFlowClass(int w, int h, int lv_f, int step = 4, int psz = 8, int lv_l = 0) : h_(nullptr) {
+    check(ictr_c2fflow_create_lvl(&h_, w, h, lv_f, lv_l, step, psz), "CoarseFlowClass");
+  }
+  int LvL() const {
+    int lv_l = 0;
+    check(ictr_c2fflow_get_lv_l(h_, &lv_l), "LvL");
+    return lv_l;
   }
   ~CoarseFlowClass() { ictr_c2fflow_destroy(h_); }
   CoarseFlowClass(const CoarseFlowClass &) = delete;
@@ -610,5 +617,12 @@ class CoarseFlowClass {
  private:
   ictr_c2fflow *h_;
 };
+
+// A field of level lv of a w x h pyramid at the frame's size (ictr_flow_upsample): src [h_l][w_l][2], out [h][w][2], both
+// in host memory (the call waits) or, on_device, both in device memory (enqueued on hip_stream).
+inline void UpsampleFlow(const float *src, int w_l, int h_l, int lv, float *out, int w, int h, bool x_only = false,
+                         bool on_device = false, void *hip_stream = nullptr) {
+  check(ictr_flow_upsample(src, w_l, h_l, lv, out, w, h, x_only ? 1 : 0, on_device ? 1 : 0, hip_stream), "UpsampleFlow");
+}
 
 }  // namespace CTR

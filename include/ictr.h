@@ -1000,6 +1000,8 @@ int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
 #include "ictr_c2f_patnorm.h"
 /* the stage's 1-D (x only) form for rectified stereo pairs: its switch */
 #include "ictr_c2f_xonly.h"
+/* a finest level above 0, and the up-sampling kernel that finishes such a run */
+#include "ictr_c2f_lvl.h"
 
 #ifdef __cplusplus
 }

@@ -376,6 +376,14 @@ SIGNATURES_XONLY = {
     "ictr_c2fflow_set_x_only": (C.c_int, [VP, C.c_int]),
     "ictr_c2fflow_get_x_only": (C.c_int, [VP, C.POINTER(C.c_int)]),
 }
+# the coarse-to-fine flow's finest level above 0 and its up-sampling (declared in include/ictr_c2f_lvl.h, which ictr.h
+# includes)
+SIGNATURES_LVL = {
+    "ictr_c2fflow_create_lvl": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ictr_c2fflow_get_lv_l": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fflow_get_upsample_ms": (C.c_int, [VP, FP]),
+    "ictr_flow_upsample": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
+}
 
 _lib = None
 
@@ -419,7 +427,8 @@ def load():
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
-                              + list(SIGNATURES_PATNORM.items()) + list(SIGNATURES_XONLY.items())):
+                              + list(SIGNATURES_PATNORM.items()) + list(SIGNATURES_XONLY.items())
+                              + list(SIGNATURES_LVL.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

@@ -20,6 +20,12 @@
 // field alone (ONE 4-byte load), the search is pf_level_search's XONLY rule at this level (min_det then carries min_hx),
 // the rejection is scalar, the MEAN tail stays in the node's row, and a node's y displacement is +0.0 to the bit.
 // Restated by tests/c2fdisp_f32.py.
+//
+// k_flow_upsample<XONLY> finishes a run whose finest level is above 0 (DESIGN.md "A finest level above 0"): the field of
+// level lv to the w x h frame, bilinear with half-pixel centres at the fixed factor 2^-lv, the vectors times 2^lv. One lane
+// per output pixel, a wave per 64 consecutive columns of a row and kWaves rows per workgroup, so that a workgroup's source
+// taps are two or three rows' worth of at most 34 records; one whole float2 store per lane, 512 contiguous bytes per wave.
+// No LDS, no atomics. Restated by tests/c2fup_f32.py; the definition is patchflow.upsample_flow_host.
 #include <math.h>
 #include <string.h>
 
@@ -133,6 +139,50 @@ static void launch_c2f_level(const std::conditional_t<MEAN, C2fMeanArgs, C2fArgs
     hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY>), g, blk, 0, s, a);
 }
 
+// s = 2^lv, inv_s = 2^-lv. Everything before the taps is exact in f32 (x + 0.5, the product with 2^-lv, - 0.5, rx,
+// 1 - rx); the six products and three sums are taken in the order written, each rounded (no contraction), then s * val.
+template <bool XONLY>
+__global__ __launch_bounds__(kBlock) void k_flow_upsample(const float2 *__restrict__ src, int wl, int hl, float inv_s,
+                                                          float s, float2 *__restrict__ out, int w, int h) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  const float fx = fminf(fmaxf(((float)x + 0.5f) * inv_s - 0.5f, 0.0f), (float)(wl - 1));
+  const float fy = fminf(fmaxf(((float)y + 0.5f) * inv_s - 0.5f, 0.0f), (float)(hl - 1));
+  const int x0 = (int)fx, y0 = (int)fy;  // fx, fy >= 0: the cast is the floor
+  const int x1 = min(x0 + 1, wl - 1), y1 = min(y0 + 1, hl - 1);
+  const float rx = fx - (float)x0, ry = fy - (float)y0;
+  const float qx = 1.0f - rx, qy = 1.0f - ry;
+  const size_t r0 = (size_t)y0 * wl, r1 = (size_t)y1 * wl;
+  float2 o;
+  if constexpr (XONLY) {  // y is not read and is +0.0
+    const float *f = reinterpret_cast<const float *>(src);
+    const float top = qx * f[2 * (r0 + x0)] + rx * f[2 * (r0 + x1)];
+    const float bot = qx * f[2 * (r1 + x0)] + rx * f[2 * (r1 + x1)];
+    o.x = s * (qy * top + ry * bot);
+    o.y = 0.0f;
+  } else {
+    const float2 a = src[r0 + x0], b = src[r0 + x1], c = src[r1 + x0], d = src[r1 + x1];
+    const float tx = qx * a.x + rx * b.x, bx = qx * c.x + rx * d.x;
+    const float ty = qx * a.y + rx * b.y, by = qx * c.y + rx * d.y;
+    o.x = s * (qy * tx + ry * bx);
+    o.y = s * (qy * ty + ry * by);
+  }
+  out[(size_t)y * w + x] = o;
+}
+
+// src [hl][wl][2] and out [h][w][2] on the device; the caller has checked the sizes
+static void launch_flow_upsample(const float *src, int wl, int hl, int lv, float *out, int w, int h, int x_only,
+                                 hipStream_t s) {
+  const float sc = (float)(1 << lv), inv = 1.0f / sc;
+  const dim3 g = pixel_rows_grid(w, h), blk(kBlock);
+  if (x_only)
+    hipLaunchKernelGGL((k_flow_upsample<true>), g, blk, 0, s, reinterpret_cast<const float2 *>(src), wl, hl, inv, sc,
+                       reinterpret_cast<float2 *>(out), w, h);
+  else
+    hipLaunchKernelGGL((k_flow_upsample<false>), g, blk, 0, s, reinterpret_cast<const float2 *>(src), wl, hl, inv, sc,
+                       reinterpret_cast<float2 *>(out), w, h);
+}
+
 }  // namespace ictr
 
 using namespace ictr;
@@ -160,16 +210,18 @@ struct C2fLevel {
 }  // namespace
 
 struct ictr_c2fflow {
-  int w = 0, h = 0, lv_f = 0, step = 0, psz = 0;
+  int w = 0, h = 0, lv_f = 0, lv_l = 0, step = 0, psz = 0;
   int maxiter = 10;
   float eps = 0.01f;
   int refine = 0;  // refiners exist for every level and hold their parameters
   int patnorm = 0;
   int x_only = 0;  // the 1-D form: the XONLY kernels and the refinement along x
   int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
-  std::vector<C2fLevel> lv;  // [lv_f + 1]
+  std::vector<C2fLevel> lv;  // [lv_f + 1]; the levels below lv_l hold their size and nothing else
   DevBuf<unsigned char> status;
   DevBuf<float> bias;  // next to it: the node bias of a run with patch-mean normalisation
+  DevBuf<float> up;    // lv_l > 0: the result plane [h][w][2], level lv_l's field up-sampled
+  Event up_done;       // behind k_flow_upsample in a timed run (it starts at level lv_l's last event)
   Event done;  // behind the last run
 };
 
@@ -178,19 +230,29 @@ static const float *c2f_field(const C2fLevel &L, int refined) {
   return refined ? ictr_flowrefine_device_ptr(L.ref.get()) : ictr_flowdensify_device_ptr(L.dens.get());
 }
 
+// the w x h result: level 0's field, or the result plane of an object whose finest level is above 0
+static const float *c2f_result(const ictr_c2fflow *c, int refined) {
+  return c->lv_l > 0 ? c->up.get() : c2f_field(c->lv[0], refined);
+}
+
 extern "C" void ictr_c2fflow_destroy(ictr_c2fflow *c) {
   if (c && c->ran) (void)hipEventSynchronize(c->done.get());  // before any buffer of a run in flight is released
   delete c;
 }
 extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, int step, int psz) {
+  return ictr_c2fflow_create_lvl(out, w, h, lv_f, 0, step, psz);
+}
+extern "C" int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_f, int lv_l, int step, int psz) {
   if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f > 15 || step < 1)
     return fail(ICTR_ERR_INVALID, "c2fflow: bad arguments (w, h, step >= 1, 0 <= lv_f <= 15)");
   if (psz < 1 || psz > 32) return fail(ICTR_ERR_INVALID, "c2fflow: psz is %d (1 .. 32)", psz);
+  if (lv_l < 0 || lv_l > lv_f) return fail(ICTR_ERR_INVALID, "c2fflow: lv_l is %d (0 .. lv_f = %d)", lv_l, lv_f);
   if (int rc = need_device()) return rc;
   auto c = std::make_unique<ictr_c2fflow>();
   c->w = w;
   c->h = h;
   c->lv_f = lv_f;
+  c->lv_l = lv_l;
   c->step = step;
   c->psz = psz;
   c->lv.resize((size_t)lv_f + 1);
@@ -198,6 +260,7 @@ extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, i
   for (int l = 0; l <= lv_f; ++l) {
     C2fLevel &L = c->lv[l];
     pyramid_level_size(w, h, l, &L.w, &L.h);
+    if (l < lv_l) continue;
     if (L.w < 2 || L.h < 2) return fail(ICTR_ERR_INVALID, "c2fflow: level %d is %d x %d, smaller than 2 px", l, L.w, L.h);
     if (step / 2 >= L.w || step / 2 >= L.h)
       return fail(ICTR_ERR_INVALID, "c2fflow: level %d (%d x %d) has no node at step %d", l, L.w, L.h, step);
@@ -216,11 +279,15 @@ extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, i
   if (int rc = c->bias.alloc(sizeof(float) * nodes, true)) return rc;
   unsigned char *cur = c->status.get();
   float *curb = c->bias.get();
-  for (C2fLevel &L : c->lv) {
+  for (C2fLevel &L : c->lv) {  // (a level below lv_l has no nodes)
     L.status = cur;
     L.bias = curb;
     cur += (size_t)L.nx * L.ny;
     curb += (size_t)L.nx * L.ny;
+  }
+  if (lv_l > 0) {
+    if (int rc = c->up.alloc(sizeof(float) * 2 * (size_t)w * h, true)) return rc;
+    if (int rc = c->up_done.create()) return rc;
   }
   if (int rc = c->done.create(hipEventDisableTiming)) return rc;
   *out = c.release();
@@ -230,8 +297,8 @@ extern "C" int ictr_c2fflow_set_params(ictr_c2fflow *c, int maxiter, float eps, 
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
   if (maxiter < 0 || !isfinite(eps) || eps < 0.0f)
     return fail(ICTR_ERR_INVALID, "c2fflow_set_params: maxiter >= 0, finite eps >= 0");
-  for (C2fLevel &L : c->lv)
-    if (int rc = ictr_flowdensify_set_params(L.dens.get(), minerr, power)) return rc;
+  for (int l = c->lv_l; l <= c->lv_f; ++l)
+    if (int rc = ictr_flowdensify_set_params(c->lv[l].dens.get(), minerr, power)) return rc;
   c->maxiter = maxiter;
   c->eps = eps;
   return ICTR_OK;
@@ -243,11 +310,12 @@ extern "C" int ictr_c2fflow_set_refine(ictr_c2fflow *c, int on, float alpha, flo
     c->refine = 0;
     return ICTR_OK;
   }
-  for (size_t l = 0; l < c->lv.size(); ++l)
+  for (size_t l = (size_t)c->lv_l; l < c->lv.size(); ++l)
     if (c->lv[l].w < 4 || c->lv[l].h < 4)
       return fail(ICTR_ERR_INVALID, "c2fflow_set_refine: level %d is %d x %d, the refinement needs 4 x 4", (int)l, c->lv[l].w,
                   c->lv[l].h);
-  for (C2fLevel &L : c->lv) {
+  for (int l = c->lv_l; l <= c->lv_f; ++l) {
+    C2fLevel &L = c->lv[l];
     if (!L.ref) {
       ictr_flowrefine *r = nullptr;
       if (int rc = ictr_flowrefine_create(&r, L.w, L.h)) return rc;
@@ -290,7 +358,7 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
   hipStream_t s = (hipStream_t)hip_stream;
   const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
   c->timed = c->timing;
-  for (int l = c->lv_f; l >= 0; --l) {
+  for (int l = c->lv_f; l >= c->lv_l; --l) {
     C2fLevel &L = c->lv[l];
     C2fArgs a;
     memset(&a, 0, sizeof(a));
@@ -345,6 +413,11 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
     }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
   }
+  if (c->lv_l > 0) {  // the finest level's field to the frame's size
+    const C2fLevel &L = c->lv[c->lv_l];
+    launch_flow_upsample(c2f_field(L, refined), L.w, L.h, c->lv_l, c->up.get(), c->w, c->h, x_only, s);
+    if (c->timed) HIPCHK(hipEventRecord(c->up_done.get(), s));
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->done.get(), s));
   c->ran = 1;
@@ -362,17 +435,18 @@ static int c2f_wait(ictr_c2fflow *c, const char *what) {
 extern "C" int ictr_c2fflow_result(ictr_c2fflow *c, float *out, int on_device) {
   if (int rc = c2f_wait(c, "c2fflow_result")) return rc;
   if (!out) return fail(ICTR_ERR_INVALID, "c2fflow_result: out is NULL");
-  HIPCHK(hipMemcpy(out, c2f_field(c->lv[0], c->ran_refined), sizeof(float) * 2 * (size_t)c->w * c->h,
+  HIPCHK(hipMemcpy(out, c2f_result(c, c->ran_refined), sizeof(float) * 2 * (size_t)c->w * c->h,
                    on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 extern "C" const float *ictr_c2fflow_device_ptr(const ictr_c2fflow *c) {
   if (!c) return nullptr;
-  return c2f_field(c->lv[0], c->ran ? c->ran_refined : c->refine);
+  return c2f_result(c, c->ran ? c->ran_refined : c->refine);
 }
 extern "C" int ictr_c2fflow_level_dims(const ictr_c2fflow *c, int level, int *w, int *h, int *nx, int *ny) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
-  if (level < 0 || level > c->lv_f) return fail(ICTR_ERR_INVALID, "c2fflow_level_dims: level is %d (0 .. %d)", level, c->lv_f);
+  if (level < c->lv_l || level > c->lv_f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_level_dims: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
   const C2fLevel &L = c->lv[level];
   if (w) *w = L.w;
   if (h) *h = L.h;
@@ -382,7 +456,8 @@ extern "C" int ictr_c2fflow_level_dims(const ictr_c2fflow *c, int level, int *w,
 }
 extern "C" int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field, float *d, unsigned char *status) {
   if (int rc = c2f_wait(c, "c2fflow_read_level")) return rc;
-  if (level < 0 || level > c->lv_f) return fail(ICTR_ERR_INVALID, "c2fflow_read_level: level is %d (0 .. %d)", level, c->lv_f);
+  if (level < c->lv_l || level > c->lv_f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_read_level: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
   const C2fLevel &L = c->lv[level];
   const size_t K = (size_t)L.nx * L.ny;
   if (field)
@@ -394,8 +469,8 @@ extern "C" int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field,
 }
 extern "C" int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *bias) {
   if (int rc = c2f_wait(c, "c2fflow_read_level_bias")) return rc;
-  if (level < 0 || level > c->lv_f)
-    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: level is %d (0 .. %d)", level, c->lv_f);
+  if (level < c->lv_l || level > c->lv_f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
   if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: bias is NULL");
   if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias: the last run had patnorm off");
   const C2fLevel &L = c->lv[level];
@@ -408,7 +483,48 @@ extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {
   for (int l = 0; l <= c->lv_f; ++l)
     for (int k = 0; k < 3; ++k) {
       ms[3 * l + k] = 0.0f;
-      if (c->timed) HIPCHK(hipEventElapsedTime(&ms[3 * l + k], c->lv[l].ev[k].get(), c->lv[l].ev[k + 1].get()));
+      if (c->timed && l >= c->lv_l)  // (a level below lv_l has no events)
+        HIPCHK(hipEventElapsedTime(&ms[3 * l + k], c->lv[l].ev[k].get(), c->lv[l].ev[k + 1].get()));
     }
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_get_lv_l(const ictr_c2fflow *c, int *lv_l) {
+  if (!c || !lv_l) return fail(ICTR_ERR_INVALID, "c2fflow_get_lv_l: c2fflow or lv_l is NULL");
+  *lv_l = c->lv_l;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_get_upsample_ms(ictr_c2fflow *c, float *ms) {
+  if (int rc = c2f_wait(c, "c2fflow_get_upsample_ms")) return rc;
+  if (!ms) return fail(ICTR_ERR_INVALID, "c2fflow_get_upsample_ms: ms is NULL");
+  *ms = 0.0f;
+  if (c->timed && c->lv_l > 0) HIPCHK(hipEventElapsedTime(ms, c->lv[c->lv_l].ev[3].get(), c->up_done.get()));
+  return ICTR_OK;
+}
+extern "C" int ictr_flow_upsample(const float *src, int w_l, int h_l, int lv, float *out, int w, int h, int x_only,
+                                  int on_device, void *hip_stream) {
+  if (!src || !out) return fail(ICTR_ERR_INVALID, "flow_upsample: src or out is NULL");
+  if (w < 1 || h < 1 || lv < 1 || lv > 15) return fail(ICTR_ERR_INVALID, "flow_upsample: w, h >= 1, lv is 1 .. 15");
+  int ew = 0, eh = 0;
+  pyramid_level_size(w, h, lv, &ew, &eh);
+  if (ew < 1 || eh < 1) return fail(ICTR_ERR_INVALID, "flow_upsample: level %d of %d x %d is empty", lv, w, h);
+  if (w_l != ew || h_l != eh)
+    return fail(ICTR_ERR_INVALID, "flow_upsample: the field is %d x %d, level %d of %d x %d is %d x %d", w_l, h_l, lv, w, h,
+                ew, eh);
+  if (int rc = need_device()) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (on_device) {
+    launch_flow_upsample(src, w_l, h_l, lv, out, w, h, x_only, s);
+    HIPCHK(hipGetLastError());
+    return ICTR_OK;
+  }
+  const size_t nsrc = sizeof(float) * 2 * (size_t)w_l * h_l, nout = sizeof(float) * 2 * (size_t)w * h;
+  DevBuf<float> dsrc, dout;
+  if (int rc = dsrc.alloc(nsrc)) return rc;
+  if (int rc = dout.alloc(nout)) return rc;
+  HIPCHK(hipMemcpyAsync(dsrc.get(), src, nsrc, hipMemcpyHostToDevice, s));
+  launch_flow_upsample(dsrc.get(), w_l, h_l, lv, dout.get(), w, h, x_only, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dout.get(), nout, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ICTR_OK;
 }

@@ -725,7 +725,7 @@ def _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins=None):
     return beta
 
 
-def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine):
+def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine, lv_l=0):
     if int(psz) != psz or not 1 <= psz <= 32:
         raise ValueError("c2f flow: psz is 1 .. 32")
     if int(step) != step or step < 1:
@@ -738,7 +738,9 @@ def _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine):
         raise ValueError(f"c2f flow: lv_f is {lv_f}, the pyramids have levels 0 .. {have}")
     if refine is not None and not dict(REFINE_DEFAULTS, **refine)["alpha"] > 0:
         raise ValueError("c2f flow: the refinement needs alpha > 0")
-    for l in range(lv_f + 1):
+    if int(lv_l) != lv_l or not 0 <= lv_l <= lv_f:
+        raise ValueError(f"c2f flow: lv_l is {lv_l} (0 .. lv_f = {lv_f})")
+    for l in range(int(lv_l), lv_f + 1):
         w, h = _c2f_level_size(pyr_a, l)
         if _c2f_level_size(pyr_b, l) != (w, h):
             raise ValueError(f"c2f flow: the two pyramids differ in size at level {l}")
@@ -756,8 +758,71 @@ def _c2f_plane(pyr, l):
     return np.ascontiguousarray(pyr.img[l][p:pyr.img[l].shape[0] - p, p:pyr.img[l].shape[1] - p])
 
 
+def pyramid_level_size(w, h, lv):
+    """(w_l, h_l) of level lv of a w x h pyramid: lv halvings, each rounded half to even (cvRound(v * 0.5))."""
+    def half(v):
+        q = v // 2
+        return q if v % 2 == 0 or q % 2 == 0 else q + 1
+    for _ in range(int(lv)):
+        w, h = half(w), half(h)
+    return w, h
+
+
+def _upsample_check(field, w, h, lv):
+    field = np.asarray(field)
+    if int(lv) != lv or not 1 <= lv <= 15:
+        raise ValueError(f"upsample_flow: lv is {lv} (1 .. 15)")
+    if int(w) != w or int(h) != h or w < 1 or h < 1:
+        raise ValueError("upsample_flow: w, h are integers >= 1")
+    wl, hl = pyramid_level_size(int(w), int(h), int(lv))
+    if wl < 1 or hl < 1:
+        raise ValueError(f"upsample_flow: level {lv} of {w} x {h} is empty")
+    if field.shape != (hl, wl, 2):
+        raise ValueError(f"upsample_flow: the field is {field.shape}, level {lv} of {w} x {h} is ({hl}, {wl}, 2)")
+    return np.ascontiguousarray(field, np.float32), wl, hl
+
+
+def _upsample_taps(n, nl, s):
+    """(i0, i1, r) of the n output positions along an axis whose level has nl samples: f64, every value exact."""
+    f = np.clip((np.arange(n, dtype=np.float64) + 0.5) / s - 0.5, 0.0, nl - 1.0)
+    i0 = np.floor(f).astype(np.int64)
+    return i0, np.minimum(i0 + 1, nl - 1), f - i0
+
+
+def upsample_flow_host(field, w, h, lv, x_only=False):
+    """The field (h_l, w_l, 2) of level lv (1 .. 15) of a w x h pyramid at the frame's size: the definition (build-defined;
+    f64 arithmetic on the f32 taps, rounded to f32 once; DESIGN.md §4 "A finest level above 0"). (w_l, h_l) must be
+    pyramid_level_size(w, h, lv), else ValueError. With s = 2^lv, output pixel (x, y): fx = clamp((x + 0.5) / s - 0.5, 0,
+    w_l - 1), x0 = floor(fx), x1 = min(x0 + 1, w_l - 1), rx = fx - x0, and fy, y0, y1, ry alike with h_l; per component
+    top = (1 - rx) F[y0, x0] + rx F[y0, x1], bot = (1 - rx) F[y1, x0] + rx F[y1, x1], val = (1 - ry) top + ry bot, and the
+    output is s val. These are cv::resize(INTER_LINEAR)'s half-pixel centres at the fixed factor 2^-lv (not w_l / w: odd
+    halving makes w_l s larger or smaller than w, and the clamp takes care of the last columns and rows), and the
+    vectors times s. x_only: the y component of `field` is not read, and the output's y is +0.0 to the bit."""
+    F, wl, hl = _upsample_check(field, w, h, lv)
+    s = float(1 << int(lv))
+    x0, x1, rx = _upsample_taps(int(w), wl, s)
+    y0, y1, ry = _upsample_taps(int(h), hl, s)
+    rx, ry = rx[None, :], ry[:, None]
+    out = np.zeros((int(h), int(w), 2), np.float32)
+    for k in range(1 if x_only else 2):
+        P = F[..., k].astype(np.float64)
+        top = (1 - rx) * P[y0][:, x0] + rx * P[y0][:, x1]
+        bot = (1 - rx) * P[y1][:, x0] + rx * P[y1][:, x1]
+        out[..., k] = s * ((1 - ry) * top + ry * bot)
+    return out
+
+
+def upsample_flow(field, w, h, lv, x_only=False):
+    """upsample_flow_host's result from the device (k_flow_upsample through ``ictr_flow_upsample``): a host array in, a
+    host array (h, w, 2) float32 out; the call waits. The same size checks."""
+    F, wl, hl = _upsample_check(field, w, h, lv)
+    out = np.empty((int(h), int(w), 2), np.float32)
+    check(_lib.load().ictr_flow_upsample(fp(F), wl, hl, int(lv), fp(out), int(w), int(h), int(bool(x_only)), 0, None))
+    return out
+
+
 def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, min_det=1e-4, densify=None, refine=None,
-                  _stages=None, patnorm=False, x_only=False, min_hx=1e-2):
+                  _stages=None, patnorm=False, x_only=False, min_hx=1e-2, lv_l=0):
     """Coarse-to-fine dense flow A -> B: the definition (build-defined; NumPy, f64 arithmetic on the f32 planes; DESIGN.md
     §4 "Coarse-to-fine dense flow" states the rule). pyr_a, pyr_b: host pyramids with ``.img / .dx / .dy[l]`` padded by
     ``.pad >= psz`` (oracle.Pyramid's shape). For l = lv_f .. 0: nodes at step // 2 + k step of the level's own size; a
@@ -776,11 +841,15 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     held node's status values keep their meaning), the densifier is called unchanged on the table whose y is +0.0, and
     the refinement is refine_flow_host(..., x_only=True). Every level's field has +0.0 bits in its y component. It
     combines with patnorm, whose bias is taken at (X + d.x, Y).
+    lv_l (0 .. lv_f; DESIGN.md "A finest level above 0"): the levels lv_f .. lv_l run as above (a level's field does not
+    depend on finer levels), and the result is upsample_flow_host(U_lv_l, W, H, lv_l, x_only). With lv_l = 0 nothing is
+    up-sampled. The size rules hold for the levels lv_l .. lv_f.
     _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
     "margins" (_c2f_search_host's), "field" (U_l) and "bias" (the node bias, None without patnorm)."""
-    lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine)
+    lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine, lv_l)
+    lv_l = int(lv_l)
     U = None
-    for l in range(lv_f, -1, -1):
+    for l in range(lv_f, lv_l - 1, -1):
         w, h = _c2f_level_size(pyr_a, l)
         init = _c2f_init(U, w, h, step, x_only)
         if x_only:
@@ -798,6 +867,9 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
             filled = d.copy()
             _dense_from_nodes(filled, lost, w, h, step)
             _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U, bias=bias))
+    if lv_l > 0:
+        w0, h0 = _c2f_level_size(pyr_a, 0)
+        return upsample_flow_host(U, w0, h0, lv_l, bool(x_only))
     return U
 
 
@@ -806,11 +878,14 @@ class CoarseToFineFlow:
     refinement per level) for w x h frames and levels lv_f .. 0. densify / refine: the per-level parameters
     (DENSIFY_DEFAULTS' / REFINE_DEFAULTS' names; refine=None: no refinement). patnorm: c2f_flow_host's patch-mean
     normalisation (k_c2f_level's MEAN forms with the node bias, k_densify<true>). x_only: c2f_flow_host's 1-D form for a
-    rectified stereo pair (k_c2f_level's XONLY forms, the refinement along x; v is +0.0 at every level). ``run`` enqueues and returns; ``dense``
-    (level 0's field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
+    rectified stereo pair (k_c2f_level's XONLY forms, the refinement along x; v is +0.0 at every level). lv_l:
+    c2f_flow_host's finest level (default 0); above 0 only the levels lv_f .. lv_l exist and run, and a run ends with
+    k_flow_upsample from level lv_l's field into the object's w x h result plane, which ``dense`` and ``device_ptr`` then
+    hand out. ``run`` enqueues and returns; ``dense``
+    (the w x h field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 
     def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False,
-                 x_only=False):
+                 x_only=False, lv_l=0):
         dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
         unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
         if unknown:
@@ -819,8 +894,11 @@ class CoarseToFineFlow:
             raise ValueError("CoarseToFineFlow: power is an integer 1 .. 4")
         L = _lib.load()
         self._h = C.c_void_p()
-        check(L.ictr_c2fflow_create(C.byref(self._h), int(w), int(h), int(lv_f), int(step), int(psz)))
+        if int(lv_l) != lv_l:
+            raise ValueError("CoarseToFineFlow: lv_l is an integer 0 .. lv_f")
+        check(L.ictr_c2fflow_create_lvl(C.byref(self._h), int(w), int(h), int(lv_f), int(lv_l), int(step), int(psz)))
         self.w, self.h, self.lv_f, self.step, self.psz = int(w), int(h), int(lv_f), int(step), int(psz)
+        self.lv_l = int(lv_l)
         self.params = dict(maxiter=int(maxiter), eps=float(eps), densify=dz,
                            refine=None if refine is None else dict(REFINE_DEFAULTS, **refine))
         check(L.ictr_c2fflow_set_params(self._h, int(maxiter), float(eps), float(dz["minerr"]), int(dz["power"])))
@@ -878,15 +956,21 @@ class CoarseToFineFlow:
 
     def kernel_ms(self):
         """(lv_f + 1, 3) ms of the last run: per level from 0 the search with its fill, the densification, the refinement;
-        zeros when timing was off."""
+        zeros when timing was off, and in the rows below lv_l."""
         ms = np.zeros((self.lv_f + 1, 3), np.float32)
         check(_lib.load().ictr_c2fflow_get_kernel_ms(self._h, fp(ms)))
         return ms
 
+    def upsample_ms(self):
+        """ms of k_flow_upsample in the last run; 0 when timing was off or lv_l = 0."""
+        ms = C.c_float()
+        check(_lib.load().ictr_c2fflow_get_upsample_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
 
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
     """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call
-    (params: its keywords, patnorm and x_only among them)."""
+    (params: its keywords, patnorm, x_only and lv_l among them)."""
     lv_f = pyr_a.lv_f if lv_f is None else lv_f
     return CoarseToFineFlow(pyr_a.w, pyr_a.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
 

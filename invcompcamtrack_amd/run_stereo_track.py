@@ -3,7 +3,7 @@
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
          [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
          [--refine [alpha,gamma,delta,outer,sor,omega]] [--densify [minerr,power]] [--flow grid|c2f|c2f-1d]
-         [--patnorm]
+         [--patnorm] [--lv-l N]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
@@ -15,7 +15,8 @@ densifies every grid photometrically first (patchflow.FlowDensifier; without a v
 with --refine, refinement per pyramid level; --densify and --refine then give the per-level parameters; not with
 --disparity 1d). --flow c2f-1d is --flow c2f with the stereo pair searched along x only (CoarseToFineFlow's x_only; the
 temporal fields stay 2-D; --disparity is not consulted). --patnorm switches on the coarse-to-fine flow's patch-mean normalisation, for cameras or frames of
-differing brightness (with --flow c2f or c2f-1d only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+differing brightness (with --flow c2f or c2f-1d only). --lv-l N stops every coarse-to-fine object at level N and up-samples that
+level's field to the frame (CoarseToFineFlow's lv_l; default 0; with --flow c2f or c2f-1d only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -86,11 +87,14 @@ def main(argv=None):
     ap.add_argument("--densify", nargs="?", const="", default=None, type=densify_params)
     ap.add_argument("--flow", choices=("grid", "c2f", "c2f-1d"), default="grid")
     ap.add_argument("--patnorm", action="store_true")
+    ap.add_argument("--lv-l", dest="lv_l", type=int, default=0)
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
     if a.flow == "c2f" and a.disparity == "1d":
         ap.error("--flow c2f with --disparity 1d: the 1-D form of the coarse-to-fine flow is --flow c2f-1d")
     if a.patnorm and a.flow not in ("c2f", "c2f-1d"):
         ap.error("--patnorm needs --flow c2f: patch-mean normalisation is built for the coarse-to-fine flow alone")
+    if a.lv_l and a.flow not in ("c2f", "c2f-1d"):
+        ap.error("--lv-l needs --flow c2f or c2f-1d: a finest level above 0 is built for the coarse-to-fine flow alone")
     th = dict(th_ratio=a.th_ratio, th_abs=a.th_abs)
     if a.fields:
         with np.load(a.fields) as z:
@@ -106,7 +110,8 @@ def main(argv=None):
         frames = [[np.asarray(iof.read_image_gray(fn), np.float32) for fn in p] for p in pairs]
         h, w = frames[0][0].shape
         t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity,
-                                 refine=a.refine, densify=a.densify, flow=a.flow, patnorm=a.patnorm, **th)
+                                 refine=a.refine, densify=a.densify, flow=a.flow, patnorm=a.patnorm, lv_l=a.lv_l,
+                                 **th)
         for left, right in frames:
             t.push_frames(left, right)
         xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()

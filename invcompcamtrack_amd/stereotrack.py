@@ -302,10 +302,14 @@ class StereoPointTracker:
     kept, tilted structure not misleading, v = +0.0), and the four temporal fields 2-D as before; patnorm, densify,
     refine and keep_grids behave as with flow="c2f", and `disparity` is not consulted. patnorm=True switches on the coarse-to-fine objects' patch-mean
     normalisation (CoarseToFineFlow's patnorm: for a right camera or a next frame of another brightness); it
-    needs flow="c2f" or "c2f-1d" and is refused with flow="grid", whose whole-pyramid kernels have no such form."""
+    needs flow="c2f" or "c2f-1d" and is refused with flow="grid", whose whole-pyramid kernels have no such form.
+    lv_l (default 0) is the finest level of every coarse-to-fine object of both sets (CoarseToFineFlow's lv_l: the levels
+    lv_f .. lv_l run and the field of level lv_l is up-sampled to the frame); above 0 it likewise needs flow="c2f" or
+    "c2f-1d"."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
-                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False):
+                 xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False,
+                 lv_l=0):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         if flow not in ("grid", "c2f", "c2f-1d"):
@@ -316,7 +320,11 @@ class StereoPointTracker:
         if patnorm and flow not in ("c2f", "c2f-1d"):
             raise ValueError("patnorm=True needs flow='c2f': patch-mean normalisation is built for the coarse-to-fine flow "
                              "alone, not for the flow grids of flow='grid'")
+        if lv_l and flow not in ("c2f", "c2f-1d"):
+            raise ValueError("lv_l > 0 needs flow='c2f' or 'c2f-1d': a finest level above 0 is built for the coarse-to-fine "
+                             "flow alone, not for the flow grids of flow='grid'")
         self.flow = flow
+        self.lv_l = int(lv_l)
         self.patnorm = bool(patnorm)
         self.flows = []
         self._fsets = [None, None]
@@ -403,7 +411,8 @@ class StereoPointTracker:
 
         def make(x_only=False):
             return CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter, self.eps,
-                                    densify=self.densify, refine=self.refine, patnorm=self.patnorm, x_only=x_only)
+                                    densify=self.densify, refine=self.refine, patnorm=self.patnorm, x_only=x_only,
+                                    lv_l=self.lv_l)
 
         if self.flow == "c2f-1d":
             c = dict(self._set(self._fsets, k, make, ("l_fwd", "l_bwd", "r_fwd", "r_bwd")))

@@ -28,6 +28,12 @@ this tree's median exceeds the parent's by at most the parent's own max - min sp
 The 1-D form against the 2-D one in the same way, on a stereo pair (the gratings move along x only): two objects per shape
 and patch size, x_only off and on, run in turn. Recorded without a bar. --parent-root measures CoarseToFineFlow.run with
 x_only and patnorm off (psz 8 and 15) and FlowGrid.compute_x (psz 15) on the same pair, with the same bar.
+
+  python tools/c2fflow_bench.py --lv-l [--reps 7] [--out profiles/c2fflow_lvl_bench.json] [--parent-root DIR]
+
+A finest level above 0: per shape and patch size three objects with lv_l 0, 1 and 2, run in turn; the whole runs of each,
+their ratios to lv_l = 0, and k_flow_upsample's own time (the object's event) next to the 16 B per pixel copy of the same
+round. Recorded without a bar. --parent-root measures CoarseToFineFlow.run at lv_l = 0 (psz 8 and 15), with the same bar.
 """
 import argparse
 import json
@@ -84,7 +90,8 @@ def default_child(root, reps):
 
 def option_child(root, reps, option):
     """Runs in a child process: CoarseToFineFlow.run (no keyword of the option: the parent has none) and, for "patnorm",
-    FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair, of the tree at `root`, HIP events around each."""
+    FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair (for "lv_l" nothing more), of the tree at `root`,
+    HIP events around each."""
     sys.path.insert(0, root)
     import torch
 
@@ -104,13 +111,97 @@ def option_child(root, reps, option):
                 grid = pf.FlowGrid(w, h, STEP)
                 rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
                                                 for _ in range(reps + 1)][1:]
-            elif psz == PSZS[1]:
+            elif psz == PSZS[1] and option == "patnorm":
                 grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
                 grid.compute(pa, pb, psz=psz, lv_f=LV_F)
                 rec["flowdensifier_run_ms"] = [float(_timed(torch, lambda: dz.run(grid, pa, pb, psz)))
                                                for _ in range(reps + 1)][1:]
         out[f"{w}x{h}"] = rec
     print("DEFAULT " + json.dumps(out), flush=True)
+
+
+def _option_against_parent(a, option, out):
+    """The default paths an option must leave alone, in child processes of the parent's build and of this one in turn (two
+    each), into out["default_paths"]. True when every median of this tree exceeds the parent's by at most the parent's own
+    max - min spread."""
+    from tools.patchdisp_bench import stats
+    ok = True
+    runs = {"this": {}, "parent": {}}
+    for _ in range(2):
+        for side, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--option-child", root, "--option", option,
+                                "--reps", str(a.reps)],
+                               capture_output=True, text=True, timeout=600, cwd=root)
+            if r.returncode != 0:
+                raise SystemExit(f"the {side} child failed:\n{r.stdout}\n{r.stderr}")
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("DEFAULT ")][-1]
+            for shape, d in json.loads(line[8:]).items():
+                for key, v in d.items():
+                    runs[side].setdefault((shape, key), []).extend(v)
+    out["default_paths"] = {}
+    for (shape, key), v in runs["this"].items():
+        t, q = stats(v), stats(runs["parent"][shape, key])
+        bar = bool(t["median"] <= q["median"] + (q["max"] - q["min"]))
+        out["default_paths"].setdefault(shape, {})[key] = {
+            "this_tree": t, "parent": q, "bar_median_within_parent_median_plus_spread": bar}
+        ok &= bar
+    print(json.dumps(out["default_paths"]), flush=True)
+    return ok
+
+
+def lvl_main(a):
+    """--lv-l: objects with lv_l 0, 1, 2 in turn, the up-sampling kernel against the copy, then lv_l = 0 against the
+    parent's."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from tools.patchdisp_bench import frames, stats
+    if ic.device_count() < 1:
+        raise SystemExit("no HIP device: nothing is measured without one")
+    lv_ls = (0, 1, 2)
+    out = {"bench": "c2fflow_lvl", "step": STEP, "lv_f": LV_F, "lv_l": list(lv_ls), "reps": a.reps,
+           "densify": pf.DENSIFY_DEFAULTS, "refine": None, "copy_bytes_per_pixel": BYTES_COPY,
+           "upsample_bytes_written_per_pixel": 8, "shapes": []}
+    ok = True
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        n = w * h
+        for psz in PSZS:
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            cs = {k: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, lv_l=k) for k in lv_ls}
+            nf = int(BYTES_COPY * n / 2) // 4  # floats copied: as many bytes read as written
+            src, dst = torch.zeros(nf, dtype=torch.float32, device="cuda"), torch.empty(nf, dtype=torch.float32, device="cuda")
+            total, up, copy = {k: [] for k in lv_ls}, {k: [] for k in lv_ls[1:]}, []
+            for rep in range(a.reps + 1):  # the first round warms everything up
+                for lv_l, c in cs.items():
+                    c.set_timing(True)
+                    tt = _timed(torch, lambda: c.run(pa, pb))
+                    if rep:
+                        total[lv_l].append(float(tt))
+                        if lv_l:
+                            up[lv_l].append(c.upsample_ms())
+                tcopy = _timed(torch, lambda: dst.copy_(src))
+                if rep:
+                    copy.append(float(tcopy))
+            rec = {"w": w, "h": h, "psz": psz, "total_ms": {str(k): stats(total[k]) for k in lv_ls},
+                   "upsample_ms": {str(k): stats(up[k]) for k in lv_ls[1:]}, "copy_ms": stats(copy)}
+            rec["total_over_lv_l_0"] = {str(k): round(rec["total_ms"][str(k)]["median"] / rec["total_ms"]["0"]["median"], 3)
+                                        for k in lv_ls[1:]}
+            rec["upsample_over_copy"] = {str(k): round(rec["upsample_ms"][str(k)]["median"] / rec["copy_ms"]["median"], 2)
+                                         for k in lv_ls[1:]}
+            rec["mean_abs_difference_to_lv_l_0_px"] = {
+                str(k): round(float(np.abs(cs[k].dense() - cs[0].dense()).mean()), 4) for k in lv_ls[1:]}
+            out["shapes"].append(rec)
+            print(json.dumps(rec), flush=True)
+    if a.parent_root:
+        ok &= _option_against_parent(a, "lv_l", out)
+    with open(a.out or os.path.join(ROOT, "profiles", "c2fflow_lvl_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
 
 
 def option_main(a, option):
@@ -156,26 +247,7 @@ def option_main(a, option):
             out["shapes"].append(rec)
             print(json.dumps(rec), flush=True)
     if a.parent_root:
-        runs = {"this": {}, "parent": {}}
-        for _ in range(2):
-            for side, root in (("parent", os.path.abspath(a.parent_root)), ("this", ROOT)):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--option-child", root, "--option", option,
-                                    "--reps", str(a.reps)],
-                                   capture_output=True, text=True, timeout=600, cwd=root)
-                if r.returncode != 0:
-                    raise SystemExit(f"the {side} child failed:\n{r.stdout}\n{r.stderr}")
-                line = [ln for ln in r.stdout.splitlines() if ln.startswith("DEFAULT ")][-1]
-                for shape, d in json.loads(line[8:]).items():
-                    for key, v in d.items():
-                        runs[side].setdefault((shape, key), []).extend(v)
-        out["default_paths"] = {}
-        for (shape, key), v in runs["this"].items():
-            t, q = stats(v), stats(runs["parent"][shape, key])
-            bar = bool(t["median"] <= q["median"] + (q["max"] - q["min"]))
-            out["default_paths"].setdefault(shape, {})[key] = {
-                "this_tree": t, "parent": q, "bar_median_within_parent_median_plus_spread": bar}
-            ok &= bar
-        print(json.dumps(out["default_paths"]), flush=True)
+        ok &= _option_against_parent(a, option, out)
     with open(a.out or os.path.join(ROOT, "profiles", name + "_bench.json"), "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
@@ -185,11 +257,12 @@ def option_main(a, option):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None, help="default: profiles/c2fflow_bench.json (c2fflow_patnorm_bench.json, c2fflow_xonly_bench.json)")
+    ap.add_argument("--out", default=None, help="default: profiles/c2fflow_bench.json (c2fflow_patnorm_bench.json, c2fflow_xonly_bench.json, c2fflow_lvl_bench.json)")
     ap.add_argument("--patnorm", action="store_true", help="measure the cost of patch-mean normalisation instead")
     ap.add_argument("--x-only", action="store_true", help="measure the 1-D form against the 2-D one instead")
+    ap.add_argument("--lv-l", dest="lv_l", action="store_true", help="measure a finest level above 0 instead")
     ap.add_argument("--option-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only"), help=argparse.SUPPRESS)
+    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l"), help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -199,6 +272,8 @@ def main():
         return option_child(a.option_child, a.reps, a.option)
     if a.reps < 7:
         ap.error("at least 7 runs each")
+    if a.lv_l:
+        return lvl_main(a)
     if a.patnorm or a.x_only:
         return option_main(a, "x_only" if a.x_only else "patnorm")
     a.out = a.out or os.path.join(ROOT, "profiles", "c2fflow_bench.json")
