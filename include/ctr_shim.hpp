@@ -613,6 +613,23 @@ class CoarseFlowClass {
   }
   // bias [ny][nx]: the node bias of a run with patch-mean normalisation
   void ReadLevelBias(int level, float *bias) { check(ictr_c2fflow_read_level_bias(h_, level, bias), "ReadLevelBias"); }
+  // Colour frames (include/ictr_c2f_rgb.h): n = 1 or 3, before the first run. With 3 a frame is three pyramids, one per
+  // channel and equal in geometry, the run is RunRGB and the node bias has three values per node.
+  void SetChannels(int n) { check(ictr_c2fflow_set_channels(h_, n), "SetChannels"); }
+  int Channels() const {
+    int n = 0;
+    check(ictr_c2fflow_get_channels(h_, &n), "Channels");
+    return n;
+  }
+  void RunRGB(const Pyramid *const a[3], const Pyramid *const b[3], void *hip_stream = nullptr) {
+    const ictr_pyramid *pa[3] = {a[0]->handle(), a[1]->handle(), a[2]->handle()};
+    const ictr_pyramid *pb[3] = {b[0]->handle(), b[1]->handle(), b[2]->handle()};
+    check(ictr_c2fflow_run_rgb(h_, pa, pb, hip_stream), "RunRGB");
+  }
+  // bias [ny][nx][3]
+  void ReadLevelBiasRGB(int level, float *bias) {
+    check(ictr_c2fflow_read_level_bias_rgb(h_, level, bias), "ReadLevelBiasRGB");
+  }
 
  private:
   ictr_c2fflow *h_;

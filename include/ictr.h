@@ -1002,6 +1002,8 @@ int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
 #include "ictr_c2f_xonly.h"
 /* a finest level above 0, and the up-sampling kernel that finishes such a run */
 #include "ictr_c2f_lvl.h"
+/* colour frames: three pyramids per frame */
+#include "ictr_c2f_rgb.h"
 
 #ifdef __cplusplus
 }

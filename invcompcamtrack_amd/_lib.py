@@ -385,6 +385,15 @@ SIGNATURES_LVL = {
     "ictr_flow_upsample": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
 }
 
+# the coarse-to-fine flow on colour frames, three pyramids per frame (declared in include/ictr_c2f_rgb.h, which ictr.h
+# includes)
+SIGNATURES_RGB = {
+    "ictr_c2fflow_set_channels": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_get_channels": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fflow_run_rgb": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
+    "ictr_c2fflow_read_level_bias_rgb": (C.c_int, [VP, C.c_int, FP]),
+}
+
 _lib = None
 
 
@@ -428,7 +437,7 @@ def load():
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
                               + list(SIGNATURES_PATNORM.items()) + list(SIGNATURES_XONLY.items())
-                              + list(SIGNATURES_LVL.items())):
+                              + list(SIGNATURES_LVL.items()) + list(SIGNATURES_RGB.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

@@ -21,6 +21,11 @@
 // the rejection is scalar, the MEAN tail stays in the node's row, and a node's y displacement is +0.0 to the bit.
 // Restated by tests/c2fdisp_f32.py.
 //
+// NCH = 3 is the colour form (DESIGN.md "Colour"; include/ictr_c2f_rgb.h): a frame is three pyramids of one geometry, the
+// search is pf_level_search_ch over three channel planes (H and b summed over the channels, one decision and one step per
+// node), the MEAN tail writes three betas per node, and a level's densifier and refiner runs are their colour ones
+// (ictr_flowdensify_run_level_rgb_, ictr_flowrefine_run_level_rgb_). Restated by tests/c2frgb_f32.py.
+//
 // k_flow_upsample<XONLY> finishes a run whose finest level is above 0 (DESIGN.md "A finest level above 0"): the field of
 // level lv to the w x h frame, bilinear with half-pixel centres at the fixed factor 2^-lv, the vectors times 2^lv. One lane
 // per output pixel, a wave per 64 consecutive columns of a row and kWaves rows per workgroup, so that a workgroup's source
@@ -57,10 +62,41 @@ struct C2fMeanArgs : C2fArgs {
   float *bias;  // [K] node brightness offsets
 };
 
-template <int NPL, int WPP, bool MEAN, bool XONLY>
-__global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> a) {
+// the colour forms' arguments (the grey forms keep theirs): three channel planes per frame, of one geometry
+struct C2fRgbArgs {
+  const float *a[3], *ax[3], *ay[3], *b[3];  // per channel: frame A image + gradients, frame B image
+  int sw, shift;
+  float swo, sho;
+  int nx, K, step;
+  const float2 *coarse;
+  int cw, ch;
+  int P, maxiter;
+  float eps2, min_det, far2;
+  float *d;
+  unsigned char *lost, *status;
+  float *bias;  // [K][3] node brightness offsets per channel (the MEAN forms alone)
+};
+template <bool MEAN, int NCH>
+using C2fArgsOf = std::conditional_t<NCH == 3, C2fRgbArgs, std::conditional_t<MEAN, C2fMeanArgs, C2fArgs>>;
+
+// channel c's planes of a level
+__device__ __forceinline__ PFPlanes c2f_planes(const C2fArgs &a, int) {
+  return PFPlanes{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
+}
+__device__ __forceinline__ PFPlanes c2f_planes(const C2fRgbArgs &a, int c) {
+  return PFPlanes{(gconst_f32)a.a[c], (gconst_f32)a.ax[c], (gconst_f32)a.ay[c], (gconst_f32)a.b[c],
+                  a.sw,               a.shift,             a.swo,               a.sho};
+}
+
+// NCH = 3 is the colour form (DESIGN.md "Colour"): pf_level_search_ch over three channel planes, one decision and one
+// step per node, and with MEAN three betas per node, bias[k][c]. A reduction's row of sSum is then 8 floats wide: the
+// widest (H with three sums of T) carries six values in one trip. Restated by tests/c2frgb_f32.py.
+template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH = 1>
+__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgsOf<MEAN, NCH> a) {
+  static_assert(NCH == 1 || NCH == 3, "one channel or three");
   constexpr int PPB = kWaves / WPP;  // nodes per workgroup
-  __shared__ float sSum[WPP > 1 ? kWaves : 1][4];
+  constexpr int SW = NCH == 1 ? 4 : 8;
+  __shared__ float sSum[WPP > 1 ? kWaves : 1][SW];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int k = blockIdx.x * PPB + wave / WPP;
@@ -83,13 +119,16 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
   const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
   int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
   float px = ix, py = iy;
-  float mean_t = 0.0f;
+  float mean_t[NCH] = {};
+  // (formed once, ahead of both uses: the grey forms then report the registers they had with one set of planes per use)
+  PFPlanes L[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) L[c] = c2f_planes(a, c);
   // One wave per node with a start out of view is done; two waves per node share the search's barriers.
   if (WPP > 1 || st == ICTR_C2F_TRACKED) {
-    const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
     int nit = 0;
-    const int why = pf_level_search<NPL, WPP, XONLY, MEAN>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit, a.maxiter,
-                                                           a.eps2, a.min_det, sSum, mean_t);
+    const int why = pf_level_search_ch<NPL, WPP, XONLY, MEAN, NCH, SW>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit,
+                                                                       a.maxiter, a.eps2, a.min_det, sSum, mean_t);
     if (why) st = why == PF_STOP_COND ? ICTR_C2F_HELD_COND : ICTR_C2F_HELD_VIEW;
     if (st == ICTR_C2F_TRACKED) {  // a runaway patch: further than P from its start, or not finite (a positive test)
       const float dx = px - ix, dy = py - iy;
@@ -100,16 +139,19 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
       }
     }
   }
-  float beta = 0.0f;
+  float beta[NCH] = {};
   if constexpr (MEAN) {
     // the node's final position: where it votes from. Two waves per node: every node of the workgroup makes the pass.
-    const PFPlanes L{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
     const bool held = st >= ICTR_C2F_HELD_COND;
     const float fx = xl + (held ? ix : px), fy = yl + (held ? iy : py);
     const bool votes = valid && st != ICTR_C2F_LOST && pf_in_view(fx, fy, a.swo, a.sho);
     if (WPP > 1 || votes) {
-      const float sb = pf_window_sum<NPL, WPP>(L, a.P, votes ? fx : 1.0f, votes ? fy : 1.0f, sSum);
-      if (votes) beta = sb / (float)(a.P * a.P) - mean_t;
+      float sb[NCH];
+      pf_window_sum_ch<NPL, WPP, NCH, SW>(L, a.P, votes ? fx : 1.0f, votes ? fy : 1.0f, sSum, sb);
+      if (votes) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) beta[c] = sb[c] / (float)(a.P * a.P) - mean_t[c];
+      }
     }
   }
   if (lane == 0 && wave % WPP == 0 && valid) {
@@ -119,24 +161,27 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(std::conditional_t<MEAN, C
     a.d[2 * k + 1] = st == ICTR_C2F_LOST ? nanv : held ? iy : py;
     a.lost[k] = st == ICTR_C2F_LOST ? 1 : 0;
     a.status[k] = (unsigned char)st;
-    if constexpr (MEAN) a.bias[k] = beta;
+    if constexpr (MEAN) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) a.bias[NCH * k + c] = beta[c];
+    }
   }
 }
 
 // the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
-template <bool MEAN, bool XONLY>
-static void launch_c2f_level(const std::conditional_t<MEAN, C2fMeanArgs, C2fArgs> &a, hipStream_t s) {
+template <bool MEAN, bool XONLY, int NCH = 1>
+static void launch_c2f_level(const C2fArgsOf<MEAN, NCH> &a, hipStream_t s) {
   const int npl = (a.P * a.P + 63) / 64;
   const dim3 blk(kBlock);
   if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY, NCH>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
     return;
   }
   const dim3 g((a.K + kWaves - 1) / kWaves);
   if (npl <= 1)
-    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN, XONLY>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN, XONLY, NCH>), g, blk, 0, s, a);
   else
-    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY, NCH>), g, blk, 0, s, a);
 }
 
 // s = 2^lv, inv_s = 2^-lv. Everything before the taps is exact in f32 (x + 0.5, the product with 2^-lv, - 0.5, rx,
@@ -201,7 +246,7 @@ struct RefDel {
 struct C2fLevel {
   int w = 0, h = 0, nx = 0, ny = 0;
   unsigned char *status = nullptr;  // [ny][nx], in the object's status block
-  float *bias = nullptr;            // [ny][nx], in the object's bias block
+  float *bias = nullptr;            // [ny][nx][channels], in the object's bias block
   std::unique_ptr<ictr_flowgrid, GridDel> grid;
   std::unique_ptr<ictr_flowdensify, DensDel> dens;
   std::unique_ptr<ictr_flowrefine, RefDel> ref;  // made when the refinement is switched on
@@ -216,10 +261,13 @@ struct ictr_c2fflow {
   int refine = 0;  // refiners exist for every level and hold their parameters
   int patnorm = 0;
   int x_only = 0;  // the 1-D form: the XONLY kernels and the refinement along x
+  int channels = 1;  // 3: colour frames, three pyramids per frame (ictr_c2fflow_run_rgb)
   int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
   std::vector<C2fLevel> lv;  // [lv_f + 1]; the levels below lv_l hold their size and nothing else
   DevBuf<unsigned char> status;
   DevBuf<float> bias;  // next to it: the node bias of a run with patch-mean normalisation
+  DevBuf<float> bw12;  // two planes of the finest level's size, the refinement's Bw of channels 1 and 2: made by the first
+                       // refined run of a 3-channel object
   DevBuf<float> up;    // lv_l > 0: the result plane [h][w][2], level lv_l's field up-sampled
   Event up_done;       // behind k_flow_upsample in a timed run (it starts at level lv_l's last event)
   Event done;  // behind the last run
@@ -233,6 +281,23 @@ static const float *c2f_field(const C2fLevel &L, int refined) {
 // the w x h result: level 0's field, or the result plane of an object whose finest level is above 0
 static const float *c2f_result(const ictr_c2fflow *c, int refined) {
   return c->lv_l > 0 ? c->up.get() : c2f_field(c->lv[0], refined);
+}
+
+// the bias block for `channels` channels: per level [ny][nx][channels] floats, the levels one behind the other from 0. The
+// new block is allocated first; on failure the object keeps its block, its rows and its channel count.
+static int c2f_place_bias(ictr_c2fflow *c, int channels) {
+  size_t nodes = 0;
+  for (const C2fLevel &L : c->lv) nodes += (size_t)L.nx * L.ny;
+  DevBuf<float> block;
+  if (int rc = block.alloc(sizeof(float) * nodes * (size_t)channels, true)) return rc;
+  c->bias = std::move(block);
+  float *cur = c->bias.get();
+  for (C2fLevel &L : c->lv) {
+    L.bias = cur;
+    cur += (size_t)L.nx * L.ny * (size_t)channels;
+  }
+  c->channels = channels;
+  return ICTR_OK;
 }
 
 extern "C" void ictr_c2fflow_destroy(ictr_c2fflow *c) {
@@ -276,15 +341,12 @@ extern "C" int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_
     nodes += (size_t)L.nx * L.ny;
   }
   if (int rc = c->status.alloc(nodes, true)) return rc;
-  if (int rc = c->bias.alloc(sizeof(float) * nodes, true)) return rc;
   unsigned char *cur = c->status.get();
-  float *curb = c->bias.get();
   for (C2fLevel &L : c->lv) {  // (a level below lv_l has no nodes)
     L.status = cur;
-    L.bias = curb;
     cur += (size_t)L.nx * L.ny;
-    curb += (size_t)L.nx * L.ny;
   }
+  if (int rc = c2f_place_bias(c.get(), 1)) return rc;
   if (lv_l > 0) {
     if (int rc = c->up.alloc(sizeof(float) * 2 * (size_t)w * h, true)) return rc;
     if (int rc = c->up_done.create()) return rc;
@@ -347,16 +409,30 @@ extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   return ICTR_OK;
 }
 
-extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, void *hip_stream) {
-  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
-  PFArgs pf;  // the argument checks and the level table of a patch search: pads, gradient planes, equal sizes
-  if (int rc = patchflow_args(pyr_a, pyr_b, c->psz, c->lv_f, 0, c->maxiter, c->eps, &pf)) return rc;
+// a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
+static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
+                   void *hip_stream) {
+  const int nch = c->channels;
+  PFArgs pfc[3];  // the argument checks and the level table of a patch search: pads, gradient planes, equal sizes
+  for (int ch = 0; ch < nch; ++ch)
+    if (int rc = patchflow_args(pyr_a[ch], pyr_b[ch], c->psz, c->lv_f, 0, c->maxiter, c->eps, &pfc[ch])) return rc;
+  const PFArgs &pf = pfc[0];
+  for (int ch = 1; ch < nch; ++ch)
+    for (int l = 0; l <= c->lv_f; ++l)
+      if (pfc[ch].lv[l].sw != pf.lv[l].sw || pfc[ch].lv[l].shift != pf.lv[l].shift || pfc[ch].lv[l].swo != pf.lv[l].swo ||
+          pfc[ch].lv[l].sho != pf.lv[l].sho)
+        return fail(ICTR_ERR_INVALID, "%s: the three pyramids of a frame differ in geometry at level %d (channel %d)", who, l,
+                    ch);
   for (int l = 0; l <= c->lv_f; ++l)
     if ((int)pf.lv[l].swo != c->lv[l].w || (int)pf.lv[l].sho != c->lv[l].h)
       return fail(ICTR_ERR_INVALID, "c2fflow_run: level %d of the pyramids is %d x %d, of the object %d x %d", l,
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
   hipStream_t s = (hipStream_t)hip_stream;
   const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
+  if (nch == 3 && refined && !c->bw12) {  // the first refined colour run: Bw of channels 1 and 2, the finest level's size
+    const C2fLevel &L = c->lv[c->lv_l];
+    if (int rc = c->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
+  }
   c->timed = c->timing;
   for (int l = c->lv_f; l >= c->lv_l; --l) {
     C2fLevel &L = c->lv[l];
@@ -383,7 +459,27 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
     if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
     a.status = L.status;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
-    if (patnorm) {
+    if (nch == 3) {
+      C2fRgbArgs r;
+      memset(&r, 0, sizeof(r));
+      for (int ch = 0; ch < 3; ++ch)
+        r.a[ch] = pfc[ch].lv[l].a, r.ax[ch] = pfc[ch].lv[l].ax, r.ay[ch] = pfc[ch].lv[l].ay, r.b[ch] = pfc[ch].lv[l].b;
+      r.sw = a.sw, r.shift = a.shift, r.swo = a.swo, r.sho = a.sho;
+      r.nx = a.nx, r.K = a.K, r.step = a.step;
+      r.coarse = a.coarse, r.cw = a.cw, r.ch = a.ch;
+      r.P = a.P, r.maxiter = a.maxiter;
+      r.eps2 = a.eps2, r.min_det = a.min_det, r.far2 = a.far2;
+      r.d = a.d, r.lost = a.lost, r.status = a.status;
+      r.bias = L.bias;
+      if (patnorm && x_only)
+        launch_c2f_level<true, true, 3>(r, s);
+      else if (patnorm)
+        launch_c2f_level<true, false, 3>(r, s);
+      else if (x_only)
+        launch_c2f_level<false, true, 3>(r, s);
+      else
+        launch_c2f_level<false, false, 3>(r, s);
+    } else if (patnorm) {
       C2fMeanArgs m;
       static_cast<C2fArgs &>(m) = a;
       m.bias = L.bias;
@@ -398,9 +494,14 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
     }
     if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
-    if (int rc = ictr_flowdensify_run_level_bias_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l,
-                                                  patnorm ? L.bias : nullptr, s))
+    if (nch == 3) {
+      if (int rc = ictr_flowdensify_run_level_rgb_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l,
+                                                   patnorm ? L.bias : nullptr, s))
+        return rc;
+    } else if (int rc = ictr_flowdensify_run_level_bias_(L.dens.get(), L.grid.get(), pyr_a[0], pyr_b[0], c->psz, l,
+                                                         patnorm ? L.bias : nullptr, s)) {
       return rc;
+    }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[2].get(), s));
     if (refined) {
       ictr_field f;
@@ -409,7 +510,13 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
       f.sign = 1;
       f.on_device = 1;
       f.data = ictr_flowdensify_device_ptr(L.dens.get());
-      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, &f, x_only, l, s)) return rc;
+      if (nch == 3) {
+        if (int rc = ictr_flowrefine_run_level_rgb_(L.ref.get(), pyr_a, pyr_b, static_cast<const float *>(f.data), x_only, l,
+                                                    c->bw12.get(), s))
+          return rc;
+      } else if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a[0], pyr_b[0], &f, x_only, l, s)) {
+        return rc;
+      }
     }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
   }
@@ -423,6 +530,33 @@ extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, cons
   c->ran = 1;
   c->ran_refined = refined;
   c->ran_patnorm = patnorm;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, void *hip_stream) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (c->channels != 1)
+    return fail(ICTR_ERR_INVALID, "c2fflow_run: the object has %d channels; a colour run is ictr_c2fflow_run_rgb", c->channels);
+  return c2f_run(c, &pyr_a, &pyr_b, "c2fflow_run", hip_stream);
+}
+extern "C" int ictr_c2fflow_run_rgb(ictr_c2fflow *c, const ictr_pyramid *const pyr_a[3], const ictr_pyramid *const pyr_b[3],
+                                    void *hip_stream) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (c->channels != 3)
+    return fail(ICTR_ERR_INVALID, "c2fflow_run_rgb: the object has %d channel; set 3 with ictr_c2fflow_set_channels",
+                c->channels);
+  if (!pyr_a || !pyr_b) return fail(ICTR_ERR_INVALID, "c2fflow_run_rgb: a pyramid triple is NULL");
+  return c2f_run(c, pyr_a, pyr_b, "c2fflow_run_rgb", hip_stream);
+}
+extern "C" int ictr_c2fflow_set_channels(ictr_c2fflow *c, int n) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (n != 1 && n != 3) return fail(ICTR_ERR_INVALID, "c2fflow_set_channels: n is %d (1: grey, or 3: colour)", n);
+  if (c->ran) return fail(ICTR_ERR_STATE, "c2fflow_set_channels: the object has run; set the channels before the first run");
+  if (n == c->channels) return ICTR_OK;
+  return c2f_place_bias(c, n);  // (sets c->channels once the block is there)
+}
+extern "C" int ictr_c2fflow_get_channels(const ictr_c2fflow *c, int *n) {
+  if (!c || !n) return fail(ICTR_ERR_INVALID, "c2fflow_get_channels: c2fflow or n is NULL");
+  *n = c->channels;
   return ICTR_OK;
 }
 
@@ -473,8 +607,22 @@ extern "C" int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *b
     return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
   if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: bias is NULL");
   if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias: the last run had patnorm off");
+  if (c->channels != 1)
+    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: the object has %d channels; use ictr_c2fflow_read_level_bias_rgb",
+                c->channels);
   const C2fLevel &L = c->lv[level];
   HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * (size_t)L.nx * L.ny, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, float *bias) {
+  if (int rc = c2f_wait(c, "c2fflow_read_level_bias_rgb")) return rc;
+  if (level < c->lv_l || level > c->lv_f)
+    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
+  if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: bias is NULL");
+  if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias_rgb: the last run had patnorm off");
+  if (c->channels != 3) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: the object has 1 channel");
+  const C2fLevel &L = c->lv[level];
+  HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * 3 * (size_t)L.nx * L.ny, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
 extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {

@@ -12,6 +12,8 @@
 //   k_fr_sor<c> one half-sweep: a lane per pixel of colour (x + y) & 1 == c. All four neighbours have the other colour,
 //               which this launch does not write: no order inside a half-sweep, the result is deterministic. The five
 //               coefficient planes are stored compacted by colour (fr_ci).
+// k_fr_warp_rgb and k_fr_coef_rgb are the two stages on colour frames (three planes per frame; the coarse-to-fine flow's
+// colour runs alone): per-channel derivatives, robust weights joint over the channels, coefficients as channel means.
 // k_fr_final adds the last (du, dv) into the interleaved result. Memory bound throughout: plain vector loads and stores,
 // no atomics. Everything is enqueued on the caller's stream; run waits for nothing but the copy of a field that lives in
 // host memory.
@@ -160,6 +162,102 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgs a) {
   a.wr[i] = X < a.w - 1 ? 0.5f * (s0 + fr_smooth(tu, tv, cx + 1, cy, ha)) : 0.0f;
   a.wd[i] = Y < a.h - 1 ? 0.5f * (s0 + fr_smooth(tu, tv, cx, cy + 1, ha)) : 0.0f;
   // step 5 starts from du = dv = 0
+  a.du[i] = 0.0f;
+  a.dv[i] = 0.0f;
+}
+
+// The colour forms of the warp and the coefficient stage (DESIGN.md §4 "Colour"; reached through
+// ictr_flowrefine_run_level_rgb_ alone): three planes per frame and three Bw planes. Steps 1 and 2 run per channel, n0,
+// n1, n2 are per channel; the two robust weights are joint over the channels, taken on the channel mean, and the
+// coefficients are channel means. Every sum over the channels starts from 0.0f and adds channel 0, 1, 2 in order; the
+// mean is the quotient by 3.0f. k_fr_sor, k_fr_init and k_fr_final are the grey ones. Restated by tests/c2frgb_f32.py.
+struct FrRgbArgs {
+  const float *A[3], *B[3];  // per channel, level planes at pixel (0, 0), strides sa, sb
+  float *bw[3];              // per channel [h][w]
+  int sa, sb, w, h;
+  float *u, *v, *du, *dv, *a11, *a12, *a22, *b1, *b2, *wr, *wd;
+  float alpha, gamma, delta;
+  int x_only;
+};
+
+__global__ __launch_bounds__(kBlock) void k_fr_warp_rgb(FrRgbArgs a, int fold) {
+  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (X >= a.w || Y >= a.h) return;
+  const int i = Y * a.w + X;
+  float u = a.u[i], v = a.v[i];
+  if (fold) {
+    u += a.du[i];
+    a.u[i] = u;
+    if (!a.x_only) {
+      v += a.dv[i];
+      a.v[i] = v;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.bw[c][i] = fr_bilinear(a.B[c], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
+}
+
+// U and V are staged once, and with them the three channels' tiles of Bw and A: 8 tiles x 1600 B = 12.8 KB of LDS. A
+// lane keeps the eleven per-channel values of all three channels (the joint weights need every channel's Iz, Ixz, Iyz
+// before any coefficient is final); the register report shows no scratch.
+__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrRgbArgs a) {
+  __shared__ float sB[3][kFrSide][kFrSide], sA[3][kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
+  const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
+  for (int q = threadIdx.x; q < kFrSide * kFrSide; q += kBlock) {
+    const int cy = q / kFrSide, cx = q - cy * kFrSide;
+    const int X = min(max(gx0 + cx, 0), a.w - 1), Y = min(max(gy0 + cy, 0), a.h - 1);
+    const int i = Y * a.w + X;
+    sU[cy][cx] = a.u[i];
+    sV[cy][cx] = a.v[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      sB[c][cy][cx] = a.bw[c][i];
+      sA[c][cy][cx] = a.A[c][(size_t)Y * a.sa + X];
+    }
+  }
+  __syncthreads();
+  const int cx = (threadIdx.x & (kFrTile - 1)) + kFrHalo, cy = threadIdx.x / kFrTile + kFrHalo;
+  const int X = gx0 + cx, Y = gy0 + cy;
+  if (X >= a.w || Y >= a.h) return;
+  const int i = Y * a.w + X;
+  const FrTile tu{sU, gx0, gy0, a.w, a.h}, tv{sV, gx0, gy0, a.w, a.h};
+  const bool in = fr_inside((float)X + tu.at(cx, cy), (float)Y + tv.at(cx, cy), a.w, a.h);
+  float Ix[3], Iy[3], Iz[3], Ixx[3], Ixy[3], Iyy[3], Ixz[3], Iyz[3], n0[3], n1[3], n2[3];
+  float s0 = 0.0f, sg = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const FrTile tb{sB[c], gx0, gy0, a.w, a.h}, ta{sA[c], gx0, gy0, a.w, a.h};
+    Ix[c] = tb.dx(cx, cy), Iy[c] = tb.dy(cx, cy), Iz[c] = tb.at(cx, cy) - ta.at(cx, cy);
+    Ixx[c] = tb.dxx(cx, cy), Ixy[c] = tb.dxy(cx, cy), Iyy[c] = tb.dyy(cx, cy);
+    Ixz[c] = Ix[c] - ta.dx(cx, cy), Iyz[c] = Iy[c] - ta.dy(cx, cy);
+    n0[c] = 1.0f / ((Ix[c] * Ix[c] + Iy[c] * Iy[c]) + kFrZeta2);
+    n1[c] = 1.0f / ((Ixx[c] * Ixx[c] + Ixy[c] * Ixy[c]) + kFrZeta2);
+    n2[c] = 1.0f / ((Ixy[c] * Ixy[c] + Iyy[c] * Iyy[c]) + kFrZeta2);
+    s0 = s0 + (n0[c] * Iz[c]) * Iz[c];
+    sg = sg + ((n1[c] * Ixz[c]) * Ixz[c] + (n2[c] * Iyz[c]) * Iyz[c]);
+  }
+  const float q0 = in ? (a.delta * 0.5f) / sqrtf(s0 / 3.0f + kFrEps2) : 0.0f;
+  const float qg = in ? (a.gamma * 0.5f) / sqrtf(sg / 3.0f + kFrEps2) : 0.0f;
+  float a11 = 0.0f, a12 = 0.0f, a22 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float w0 = q0 * n0[c];
+    a11 = a11 + (w0 * (Ix[c] * Ix[c]) + qg * (n1[c] * (Ixx[c] * Ixx[c]) + n2[c] * (Ixy[c] * Ixy[c])));
+    a12 = a12 + (w0 * (Ix[c] * Iy[c]) + qg * (n1[c] * (Ixx[c] * Ixy[c]) + n2[c] * (Ixy[c] * Iyy[c])));
+    a22 = a22 + (w0 * (Iy[c] * Iy[c]) + qg * (n1[c] * (Ixy[c] * Ixy[c]) + n2[c] * (Iyy[c] * Iyy[c])));
+    b1 = b1 + (w0 * (Ix[c] * Iz[c]) + qg * (n1[c] * (Ixx[c] * Ixz[c]) + n2[c] * (Ixy[c] * Iyz[c])));
+    b2 = b2 + (w0 * (Iy[c] * Iz[c]) + qg * (n1[c] * (Ixy[c] * Ixz[c]) + n2[c] * (Iyy[c] * Iyz[c])));
+  }
+  const int ci = fr_ci(X, Y, a.w, a.h);
+  a.a11[ci] = a11 / 3.0f;
+  a.a12[ci] = a12 / 3.0f;
+  a.a22[ci] = a22 / 3.0f;
+  a.b1[ci] = -(b1 / 3.0f);
+  a.b2[ci] = -(b2 / 3.0f);
+  const float ha = a.alpha * 0.5f;
+  const float sm = fr_smooth(tu, tv, cx, cy, ha);
+  a.wr[i] = X < a.w - 1 ? 0.5f * (sm + fr_smooth(tu, tv, cx + 1, cy, ha)) : 0.0f;
+  a.wd[i] = Y < a.h - 1 ? 0.5f * (sm + fr_smooth(tu, tv, cx, cy + 1, ha)) : 0.0f;
   a.du[i] = 0.0f;
   a.dv[i] = 0.0f;
 }
@@ -372,6 +470,58 @@ extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid
     mark();
     hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, a, reinterpret_cast<float2 *>(r->res.get()));
     mark();
+  }
+  HIPCHK(hipGetLastError());
+  return r->res.record(s);
+}
+
+// the colour run of the coarse-to-fine flow: three pyramids per frame (the caller has checked that they agree in
+// geometry), the field a device ICTR_FIELD_FLOW, and bw12 two more Bw planes [2][h][w] of the caller's on the device (the
+// refiner's own is channel 0's)
+extern "C" int ictr_flowrefine_run_level_rgb_(ictr_flowrefine *r, const ictr_pyramid *const pyr_a[3],
+                                              const ictr_pyramid *const pyr_b[3], const float *field, int x_only, int level,
+                                              float *bw12, void *hip_stream) {
+  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  if (!field || !bw12) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field or the Bw planes are NULL");
+  const FrArgs g = fr_args(r, x_only);
+  FrRgbArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < 3; ++c) {
+    ictr_level0 l[2];
+    for (int k = 0; k < 2; ++k) {
+      if (int rc = ictr_pyramid_level0(k ? pyr_b[c] : pyr_a[c], "flowrefine_run", &l[k], level)) return rc;
+      if (l[k].w != r->w || l[k].h != r->h)
+        return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
+    }
+    if (c > 0 && (l[0].stride != a.sa || l[1].stride != a.sb))
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: the channels' planes differ in stride");
+    a.A[c] = l[0].img, a.sa = l[0].stride;
+    a.B[c] = l[1].img, a.sb = l[1].stride;
+  }
+  const size_t n = (size_t)r->w * r->h;
+  a.bw[0] = g.bw, a.bw[1] = bw12, a.bw[2] = bw12 + n;
+  a.w = r->w, a.h = r->h;
+  a.u = g.u, a.v = g.v, a.du = g.du, a.dv = g.dv;
+  a.a11 = g.a11, a.a12 = g.a12, a.a22 = g.a22, a.b1 = g.b1, a.b2 = g.b2, a.wr = g.wr, a.wd = g.wd;
+  a.alpha = g.alpha, a.gamma = g.gamma, a.delta = g.delta;
+  a.x_only = g.x_only;
+  hipStream_t s = (hipStream_t)hip_stream;
+  r->nev = 0;  // (the stage's events are the coarse-to-fine object's)
+  if (r->n_outer == 0) {  // the input's bits
+    HIPCHK(hipMemcpyAsync(r->res.get(), field, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
+  } else {
+    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
+    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
+    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(field), a.u, a.v, (int)n);
+    for (int o = 0; o < r->n_outer; ++o) {
+      hipLaunchKernelGGL(k_fr_warp_rgb, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
+      hipLaunchKernelGGL(k_fr_coef_rgb, tiles, blk, 0, s, a);
+      for (int k = 0; k < r->n_sor; ++k) {
+        fr_half_sweep(r, g, 0, s);
+        fr_half_sweep(r, g, 1, s);
+      }
+    }
+    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, g, reinterpret_cast<float2 *>(r->res.get()));
   }
   HIPCHK(hipGetLastError());
   return r->res.record(s);

@@ -50,8 +50,17 @@ extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowg
 extern "C" int ictr_flowdensify_run_level_bias_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
                                                 const ictr_pyramid *pyr_b, int psz, int level, const float *bias,
                                                 void *hip_stream);
+// the densifier's colour run: three pyramids per frame of one geometry, the node bias [ny][nx][3] (NULL: none)
+extern "C" int ictr_flowdensify_run_level_rgb_(ictr_flowdensify *z, const ictr_flowgrid *grid,
+                                               const ictr_pyramid *const pyr_a[3], const ictr_pyramid *const pyr_b[3], int psz,
+                                               int level, const float *bias, void *hip_stream);
 extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                           const ictr_field *src, int x_only, int level, void *hip_stream);
+// the refiner's colour run: three pyramids per frame of one geometry, a device field [h][w][2], two more Bw planes
+// [2][h][w] of the caller's on the device
+extern "C" int ictr_flowrefine_run_level_rgb_(ictr_flowrefine *r, const ictr_pyramid *const pyr_a[3],
+                                              const ictr_pyramid *const pyr_b[3], const float *field, int x_only, int level,
+                                              float *bw12, void *hip_stream);
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);

@@ -4,6 +4,8 @@
 // patch's waves (pf_patch_sum) and the search itself, from the template to the last iteration (pf_level_search, 2-D or
 // along x only; with MEAN, k_c2f_level's patch-mean normalisation) and one more window pass of frame B (pf_window_sum).
 // tests/patchflow_f32.py restates these expressions in NumPy f32 (level_search there), tests/patnorm_f32.py the MEAN form.
+// pf_level_search_ch and pf_window_sum_ch are the same two for NCH channels (1: the grey code; 3: colour frames, DESIGN.md
+// "Colour"), restated for three channels by tests/c2frgb_f32.py.
 #pragma once
 
 #include "ictr_dev.h"
@@ -53,10 +55,11 @@ __device__ __forceinline__ bool pf_in_view(float x, float y, float swo, float sh
 // all; for large patches (more than 4 pixels per lane) TWO waves per patch halve each wave's chain of pixels and double
 // the waves that hide each other's loads: the wave sums then meet in LDS, one workgroup barrier per reduction.
 // pf_patch_sum: N per-wave totals summed over the patch's WPP waves, the partials added in wave order from 0 by every
-// wave (all waves of the patch get the same bits). sSum: the workgroup's [kWaves][4] floats (unused with one wave).
-template <int WPP, int N>
-__device__ __forceinline__ void pf_patch_sum(float (&v)[N], float (*sSum)[4]) {
-  static_assert(N <= 4, "a wave's row of sSum holds four partials");
+// wave (all waves of the patch get the same bits). sSum: the workgroup's [kWaves][SW] floats (unused with one wave); SW
+// is 4 for one channel and 8 for three, whose widest reduction carries six values in one trip.
+template <int WPP, int N, int SW>
+__device__ __forceinline__ void pf_patch_sum(float (&v)[N], float (*sSum)[SW]) {
+  static_assert(N <= SW, "a wave's row of sSum holds SW partials");
 #pragma unroll
   for (int j = 0; j < N; ++j) v[j] = pf_wave_sum(v[j]);
   if constexpr (WPP > 1) {
@@ -102,46 +105,62 @@ enum { PF_STOP_NONE = 0, PF_STOP_COND = 1, PF_STOP_VIEW = 2 };  // why a patch s
 // s = sum G (T' - I), b = s + (sum I / n) sum G. The direct form would need the frame mean before the residual, two
 // reductions on the chain and in the two-wave form four barriers.
 // mean_t receives mean(T) = sum T / n (also when the patch is refused by the conditioning test).
-template <int NPL, int WPP, bool XONLY, bool MEAN>
-__device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float xl, float yl, bool ok, float &px, float &py,
-                                               int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4],
-                                               float &mean_t) {
+// NCH channels (pf_level_search_ch; 1 is the grey search, to the operation): a frame is NCH planes of one geometry
+// (L[0]'s). T, Gx, Gy of every channel stay in registers; H = sum_c sum_px G_c G_c^T and b = sum_c sum_px G_c r_c with
+// r_c = T_c - I_c, ONE conditioning decision and ONE step per patch. The summation order is fixed: a lane adds channel 0,
+// then 1, then 2 into the same accumulators, the pixels of a channel in the grey order, and the wave and patch sums follow
+// once, so that an iteration keeps its single reduction. A channel's window loads of an iteration are all issued before
+// their first use. MEAN: every channel loses its own mean; the reduction of H carries the NCH sums of T behind it (six
+// values in 2-D), the second the NCH sums of Gx(, Gy), an iteration's the NCH sums of I behind b (five in 2-D), and
+// b = s + sum_c (sum I_c / n) sum G_c, the channels added in order. mean_t[c] = mean(T_c).
+template <int NPL, int WPP, bool XONLY, bool MEAN, int NCH, int SW>
+__device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int P, float xl, float yl, bool ok, float &px,
+                                                  float &py, int &nit, int maxiter, float eps2, float min_cond,
+                                                  float (*sSum)[SW], float (&mean_t)[NCH]) {
+  const PFPlanes &L = Lc[0];  // the geometry of every channel
   const int n = P * P;
   const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
   const PFTaps ta = pf_taps(ok ? xl : 1.0f, ok ? yl : 1.0f, P, L.sw, L.shift);
   int off[NPL];
-  float T[NPL], Gx[NPL], Gy[XONLY ? 1 : NPL];
-  constexpr int NH = XONLY ? 2 : 3, NB = XONLY ? 1 : 2;  // the sums of H and of b; MEAN: sum T, sum I behind them
-  float h[MEAN ? NH + 1 : NH] = {};  // hxx, (hxy,) hyy(, sum T)
+  float T[NCH][NPL], Gx[NCH][NPL], Gy[NCH][XONLY ? 1 : NPL];
+  constexpr int NH = XONLY ? 2 : 3, NB = XONLY ? 1 : 2;  // the sums of H and of b; MEAN: sum T_c, sum I_c behind them
+  float h[MEAN ? NH + NCH : NH] = {};  // hxx, (hxy,) hyy(, sum T_c)
 #pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int q = slot0 + 64 * WPP * i;
-    const bool in = q < n;
-    off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
-    const int idx = ta.base + off[i];
-    const float t = pf_fetch(L.a, idx, L.sw, ta), gx = pf_fetch(L.ax, idx, L.sw, ta), gy = pf_fetch(L.ay, idx, L.sw, ta);
-    T[i] = in ? t : 0.0f;
-    Gx[i] = in ? gx : 0.0f;
-    const float gyi = in ? gy : 0.0f;
-    h[0] += Gx[i] * Gx[i];
-    if constexpr (XONLY) {
-      h[1] += gyi * gyi;
-    } else {
-      Gy[i] = gyi;
-      h[1] += Gx[i] * gyi;
-      h[2] += gyi * gyi;
-    }
-    if constexpr (MEAN) h[NH] += T[i];
-  }
-  pf_patch_sum<WPP>(h, sSum);
-  float sg[NB] = {};  // MEAN: sum Gx(, sum Gy)
-  if constexpr (MEAN) {
-    mean_t = h[NH] / (float)n;
+  for (int c = 0; c < NCH; ++c) {
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
-      T[i] = (slot0 + 64 * WPP * i < n) ? T[i] - mean_t : 0.0f;
-      sg[0] += Gx[i];
-      if constexpr (!XONLY) sg[1] += Gy[i];
+      const int q = slot0 + 64 * WPP * i;
+      const bool in = q < n;
+      if (c == 0) off[i] = in ? (q / P) * L.sw + (q % P) : 0;  // beyond the patch: its first pixel, with zero templates
+      const int idx = ta.base + off[i];
+      const float t = pf_fetch(Lc[c].a, idx, L.sw, ta), gx = pf_fetch(Lc[c].ax, idx, L.sw, ta),
+                  gy = pf_fetch(Lc[c].ay, idx, L.sw, ta);
+      T[c][i] = in ? t : 0.0f;
+      Gx[c][i] = in ? gx : 0.0f;
+      const float gyi = in ? gy : 0.0f;
+      h[0] += Gx[c][i] * Gx[c][i];
+      if constexpr (XONLY) {
+        h[1] += gyi * gyi;
+      } else {
+        Gy[c][i] = gyi;
+        h[1] += Gx[c][i] * gyi;
+        h[2] += gyi * gyi;
+      }
+      if constexpr (MEAN) h[NH + c] += T[c][i];
+    }
+  }
+  pf_patch_sum<WPP>(h, sSum);
+  float sg[NB * NCH] = {};  // MEAN: per channel sum Gx(, sum Gy)
+  if constexpr (MEAN) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      mean_t[c] = h[NH + c] / (float)n;
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) {
+        T[c][i] = (slot0 + 64 * WPP * i < n) ? T[c][i] - mean_t[c] : 0.0f;
+        sg[NB * c] += Gx[c][i];
+        if constexpr (!XONLY) sg[NB * c + 1] += Gy[c][i];
+      }
     }
   }
   const float hxx = h[0], hxy = XONLY ? 0.0f : h[1], hyy = h[XONLY ? 1 : 2];
@@ -170,25 +189,31 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
       if (WPP == 1) break;
     }
     const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
-    float b[MEAN ? NB + 1 : NB] = {};  // bx, (by)(, sum I)
-    PFWin w[NPL];
+    float b[MEAN ? NB + NCH : NB] = {};  // bx, (by)(, sum I_c)
 #pragma unroll
-    for (int i = 0; i < NPL; ++i) w[i] = pf_load(L.b, tb.base + off[i], L.sw);  // all in flight before the first use
+    for (int c = 0; c < NCH; ++c) {
+      PFWin w[NPL];
 #pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-      const bool in = slot0 + 64 * WPP * i < n;
-      const float iv = pf_blend(w[i], tb);
-      float r = T[i] - iv;
-      r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
-      b[0] += Gx[i] * r;
-      if constexpr (!XONLY) b[1] += Gy[i] * r;
-      if constexpr (MEAN) b[NB] += in ? iv : 0.0f;
+      for (int i = 0; i < NPL; ++i) w[i] = pf_load(Lc[c].b, tb.base + off[i], L.sw);  // all in flight before the first use
+#pragma unroll
+      for (int i = 0; i < NPL; ++i) {
+        const bool in = slot0 + 64 * WPP * i < n;
+        const float iv = pf_blend(w[i], tb);
+        float r = T[c][i] - iv;
+        r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+        b[0] += Gx[c][i] * r;
+        if constexpr (!XONLY) b[1] += Gy[c][i] * r;
+        if constexpr (MEAN) b[NB + c] += in ? iv : 0.0f;
+      }
     }
     pf_patch_sum<WPP>(b, sSum);
     if constexpr (MEAN) {
-      const float mi = b[NB] / (float)n;
-      b[0] = b[0] + mi * sg[0];
-      if constexpr (!XONLY) b[1] = b[1] + mi * sg[1];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const float mi = b[NB + c] / (float)n;
+        b[0] = b[0] + mi * sg[NB * c];
+        if constexpr (!XONLY) b[1] = b[1] + mi * sg[NB * c + 1];
+      }
     }
     if (run) {
       float dx, dy = 0.0f;
@@ -206,28 +231,51 @@ __device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float x
   }
   return why;
 }
+// one channel: the search as k_patchflow, k_patchdisp and the grey k_c2f_level call it
+template <int NPL, int WPP, bool XONLY, bool MEAN>
+__device__ __forceinline__ int pf_level_search(const PFPlanes &L, int P, float xl, float yl, bool ok, float &px, float &py,
+                                               int &nit, int maxiter, float eps2, float min_cond, float (*sSum)[4],
+                                               float &mean_t) {
+  const PFPlanes Lc[1] = {L};
+  float m[1] = {mean_t};
+  const int why = pf_level_search_ch<NPL, WPP, XONLY, MEAN, 1, 4>(Lc, P, xl, yl, ok, px, py, nit, maxiter, eps2, min_cond,
+                                                                  sSum, m);
+  mean_t = m[0];
+  return why;
+}
 
 // The sum of frame B over the P x P patch at (x, y), in the search's sampling, lane order and sum shape: one more window
 // pass, as an iteration makes it. Two waves per patch: every patch of the workgroup calls it (the barriers), one without a
-// use for the sum at the harmless window (1, 1).
-template <int NPL, int WPP>
-__device__ __forceinline__ float pf_window_sum(const PFPlanes &L, int P, float x, float y, float (*sSum)[4]) {
+// use for the sum at the harmless window (1, 1). NCH channels: s[c] per channel, one reduction of NCH values.
+template <int NPL, int WPP, int NCH, int SW>
+__device__ __forceinline__ void pf_window_sum_ch(const PFPlanes (&Lc)[NCH], int P, float x, float y, float (*sSum)[SW],
+                                                 float (&s)[NCH]) {
+  const PFPlanes &L = Lc[0];
   const int n = P * P;
   const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
   const PFTaps tb = pf_taps(x, y, P, L.sw, L.shift);
-  PFWin w[NPL];
 #pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const int q = slot0 + 64 * WPP * i;
-    w[i] = pf_load(L.b, tb.base + (q < n ? (q / P) * L.sw + (q % P) : 0), L.sw);
-  }
-  float s[1] = {};
+  for (int c = 0; c < NCH; ++c) {
+    PFWin w[NPL];
 #pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    const float iv = pf_blend(w[i], tb);
-    s[0] += (slot0 + 64 * WPP * i < n) ? iv : 0.0f;
+    for (int i = 0; i < NPL; ++i) {
+      const int q = slot0 + 64 * WPP * i;
+      w[i] = pf_load(Lc[c].b, tb.base + (q < n ? (q / P) * L.sw + (q % P) : 0), L.sw);
+    }
+    s[c] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      const float iv = pf_blend(w[i], tb);
+      s[c] += (slot0 + 64 * WPP * i < n) ? iv : 0.0f;
+    }
   }
   pf_patch_sum<WPP>(s, sSum);
+}
+template <int NPL, int WPP>
+__device__ __forceinline__ float pf_window_sum(const PFPlanes &L, int P, float x, float y, float (*sSum)[4]) {
+  const PFPlanes Lc[1] = {L};
+  float s[1];
+  pf_window_sum_ch<NPL, WPP, 1, 4>(Lc, P, x, y, sSum, s);
   return s[0];
 }
 

@@ -108,6 +108,61 @@ def read_image_gray(filename):
     return np.asarray(Image.open(filename).convert("L"), np.float32)
 
 
+def _read_ppm(data):
+    """Binary PPM: exactly four header tokens (magic, width, height, maxval) separated by whitespace, '#' comments to the
+    end of their line, ONE whitespace byte behind maxval, then the raster."""
+    ws = b" \t\r\n\v\f"
+    pos, tokens = 0, []
+    while len(tokens) < 4:
+        while pos < len(data) and (data[pos:pos + 1] in ws or data[pos:pos + 1] == b"#"):
+            if data[pos:pos + 1] == b"#":
+                while pos < len(data) and data[pos:pos + 1] not in b"\r\n":
+                    pos += 1
+            else:
+                pos += 1
+        start = pos
+        while pos < len(data) and data[pos:pos + 1] not in ws and data[pos:pos + 1] != b"#":
+            pos += 1
+        if start == pos:
+            raise ValueError("truncated PPM header")
+        tokens.append(data[start:pos])
+    if tokens[0] != b"P6":
+        raise ValueError("only binary PPM (P6) is supported")
+    try:
+        w, h, maxv = (int(t) for t in tokens[1:])
+    except ValueError:
+        raise ValueError("a PPM header holds width, height and maxval as decimal numbers") from None
+    if w < 1 or h < 1 or not 1 <= maxv <= 65535:
+        raise ValueError(f"PPM header: {w} x {h}, maxval {maxv}")
+    if data[pos:pos + 1] not in ws or pos >= len(data):
+        raise ValueError("a PPM raster follows maxval after one whitespace byte")
+    dt = np.dtype(np.uint8 if maxv < 256 else ">u2")
+    raster = data[pos + 1:]
+    if len(raster) < w * h * 3 * dt.itemsize:
+        raise ValueError(f"truncated PPM raster: {len(raster)} bytes for {w} x {h} x 3 samples of {dt.itemsize} byte(s)")
+    return np.frombuffer(raster, dt, count=w * h * 3).reshape(h, w, 3).astype(np.float32)
+
+
+def read_image_rgb(filename):
+    """Colour float32 image (h, w, 3), values as stored (0..255 for 8-bit sources), channels in the file's order (R, G,
+    B for .ppm and through PIL). .npy of shape (h, w, 3) and binary .ppm are read natively, everything else goes through
+    PIL when it is installed. A grey source is refused: use read_image_gray."""
+    ext = os.path.splitext(filename)[1].lower()
+    if ext == ".npy":
+        a = np.load(filename, allow_pickle=False)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{filename}: a colour .npy is (h, w, 3), not {a.shape}")
+        return np.ascontiguousarray(a, np.float32)
+    if ext == ".ppm":
+        with open(filename, "rb") as f:
+            return _read_ppm(f.read())
+    try:
+        from PIL import Image
+    except ImportError as exc:
+        raise RuntimeError(f"cannot decode {filename}: only .npy/.ppm are built in and PIL is not installed") from exc
+    return np.asarray(Image.open(filename).convert("RGB"), np.float32)
+
+
 def read_nposes_input(filename):
     """run_track_nposes.cpp:39-103. Returns a dict; poses (S,6); inlids: list of 1-based id arrays."""
     with open(filename) as f:

@@ -54,6 +54,14 @@ def partition_patches(npatches, world):
     return out
 
 
+def _grey_only(who, *pyrs):
+    """Colour frames (three pyramids per frame) are CoarseToFineFlow(channels=3)'s alone; everything else stays grey."""
+    for p in pyrs:
+        if isinstance(p, (list, tuple)):
+            raise ValueError(f"{who} takes grey frames, one pyramid per frame: colour frames (three pyramids) are "
+                             "CoarseToFineFlow(channels=3)'s alone")
+
+
 def track_points(pyr_a, pyr_b, pts, psz=15, lv_f=None, lv_l=0, maxiter=10, eps=0.01, dist=None, group=None, _local=None):
     """Track K points from frame A to frame B. pts: (K,2) level-0 pixel coordinates (x,y).
     Returns (new_pts (K,2) float32 with NaN rows for lost points, status (K,) bool, iters (K,) int32).
@@ -63,6 +71,7 @@ def track_points(pyr_a, pyr_b, pts, psz=15, lv_f=None, lv_l=0, maxiter=10, eps=0
     patches; rank 0 gathers the ranges in rank order and returns the full arrays, the other ranks return None. The
     result on rank 0 equals the single-process result bit for bit (a patch's arithmetic does not depend on what else
     is in its launch). `_local` replaces the GPU call in the CPU tests of the partition / gather logic."""
+    _grey_only("track_points", pyr_a, pyr_b)
     pts = np.atleast_2d(np.asarray(pts, np.float32))
     if dist is not None:
         world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -103,6 +112,7 @@ def track_disparity(pyr_a, pyr_b, pts, psz=15, lv_f=None, lv_l=0, maxiter=10, ep
     """track_points for a rectified stereo pair (``ictr_patchdisp``): a 1-parameter search along x. Same arguments and
     types; new[:, 1] has pts[:, 1]'s bits for a tracked point. A patch of vertical edges alone is kept (track_points
     loses it), a patch of horizontal edges alone is lost."""
+    _grey_only("track_disparity", pyr_a, pyr_b)
     pts = np.atleast_2d(np.asarray(pts, np.float32))
     K = pts.shape[0]
     lv_f = pyr_a.lv_f if lv_f is None else lv_f
@@ -291,6 +301,40 @@ def _fr_coef(A, bw, inside, u, v, alpha, gamma, delta):
     return a11, a12, a22, b1, b2, wr, wd
 
 
+def _fr_coef_rgb(A, bw, inside, u, v, alpha, gamma, delta):
+    """_fr_coef on colour frames: A, bw are three planes each. Steps 1 and 2 run per channel, n0_c, n1_c, n2_c are per
+    channel; the two robust weights are joint over the channels and taken on the channel mean,
+    q0 = delta inside / 2 / sqrt((1/3) sum_c n0_c Iz_c^2 + eps^2),
+    qg = gamma inside / 2 / sqrt((1/3) sum_c (n1_c Ixz_c^2 + n2_c Iyz_c^2) + eps^2); the coefficients are channel means,
+    a11 = (1/3) sum_c [q0 n0_c Ix_c^2 + qg (n1_c Ixx_c^2 + n2_c Ixy_c^2)] and a12, a22, b1, b2 likewise. Three equal
+    channels give _fr_coef in real arithmetic. The smoothness term is unchanged."""
+    e2, z2 = _FR_EPS ** 2, _FR_ZETA ** 2
+    ch = []
+    for c in range(3):
+        Ix, Iy, Iz = _fr_dx(bw[c]), _fr_dy(bw[c]), bw[c] - A[c]
+        Ixx, Ixy, Iyy = _fr_dx(Ix), _fr_dy(Ix), _fr_dy(Iy)
+        Ixz, Iyz = Ix - _fr_dx(A[c]), Iy - _fr_dy(A[c])
+        n0 = 1 / (Ix * Ix + Iy * Iy + z2)
+        n1 = 1 / (Ixx * Ixx + Ixy * Ixy + z2)
+        n2 = 1 / (Ixy * Ixy + Iyy * Iyy + z2)
+        ch.append((Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz, n0, n1, n2))
+    q0 = delta * inside * 0.5 / np.sqrt(sum(n0 * Iz * Iz for (_, _, Iz, _, _, _, _, _, n0, _, _) in ch) / 3 + e2)
+    qg = gamma * inside * 0.5 / np.sqrt(
+        sum(n1 * Ixz * Ixz + n2 * Iyz * Iyz for (_, _, _, _, _, _, Ixz, Iyz, _, n1, n2) in ch) / 3 + e2)
+    a11 = a12 = a22 = b1 = b2 = 0.0
+    for Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz, n0, n1, n2 in ch:
+        a11 = a11 + (q0 * n0 * Ix * Ix + qg * (n1 * Ixx * Ixx + n2 * Ixy * Ixy))
+        a12 = a12 + (q0 * n0 * Ix * Iy + qg * (n1 * Ixx * Ixy + n2 * Ixy * Iyy))
+        a22 = a22 + (q0 * n0 * Iy * Iy + qg * (n1 * Ixy * Ixy + n2 * Iyy * Iyy))
+        b1 = b1 + (q0 * n0 * Ix * Iz + qg * (n1 * Ixx * Ixz + n2 * Ixy * Iyz))
+        b2 = b2 + (q0 * n0 * Iy * Iz + qg * (n1 * Ixy * Ixz + n2 * Iyy * Iyz))
+    s = alpha * 0.5 / np.sqrt(_fr_dx(u) ** 2 + _fr_dy(u) ** 2 + _fr_dx(v) ** 2 + _fr_dy(v) ** 2 + e2)
+    wr, wd = np.zeros_like(s), np.zeros_like(s)
+    wr[:, :-1] = 0.5 * (s[:, :-1] + s[:, 1:])
+    wd[:-1, :] = 0.5 * (s[:-1, :] + s[1:, :])
+    return a11 / 3, a12 / 3, a22 / 3, -b1 / 3, -b2 / 3, wr, wd
+
+
 def _fr_shift(a):
     """The four neighbours' values (left, right, up, down), 0 beyond the frame (where the edge weight is 0 too)."""
     p = np.pad(a, 1)
@@ -320,13 +364,17 @@ def refine_flow_host(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_ou
                      _trace=None):
     """Variational refinement of the dense flow A -> B at level 0: the definition (build-defined; NumPy, f64 arithmetic
     on the f32 inputs; DESIGN.md §4 "Variational refinement of a dense field" states the rule). img_a, img_b: (H, W) grey
-    frames; flow: (H, W, 2). Returns (H, W, 2) float32. x_only (a stereo pair): only u moves, v keeps its input bits.
+    frames, or three (H, W) planes each for colour frames (the joint robust weights of _fr_coef_rgb; "bw" in _trace is
+    then (3, H, W)); flow: (H, W, 2). Returns (H, W, 2) float32. x_only (a stereo pair): only u moves, v keeps its input bits.
     n_outer = 0 returns the input's bits. _trace: a list that receives one dict of the stage planes per outer iteration
     (FR_STAGES' names, and "px", "py", the warp positions)."""
     f0 = np.ascontiguousarray(flow, np.float32)
     A = np.asarray(np.asarray(img_a, np.float32), np.float64)
     B = np.asarray(np.asarray(img_b, np.float32), np.float64)
-    h, w = A.shape
+    rgb = A.ndim == 3  # colour frames: three (H, W) planes each (DESIGN.md §4 "Colour"; _fr_coef_rgb states the rule)
+    if rgb and (A.shape[0] != 3 or B.shape != A.shape):
+        raise ValueError("refine_flow_host: colour frames are three (H, W) planes each")
+    h, w = A.shape[-2:]
     if B.shape != A.shape or f0.shape != (h, w, 2) or w < 4 or h < 4:
         raise ValueError("refine_flow_host needs two (H, W) frames and an (H, W, 2) flow, H, W >= 4")
     if not (0 < omega < 2) or not alpha > 0 or min(gamma, delta, n_outer, n_sor) < 0:
@@ -337,8 +385,13 @@ def refine_flow_host(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_ou
     yy, xx = np.mgrid[0:h, 0:w]
     for _ in range(n_outer):
         px, py = xx + u, yy + v
-        bw, inside = _fr_warp(B, px, py)
-        a11, a12, a22, b1, b2, wr, wd = _fr_coef(A, bw, inside, u, v, alpha, gamma, delta)
+        if rgb:
+            warped = [_fr_warp(B[c], px, py) for c in range(3)]
+            bw, inside = np.stack([q[0] for q in warped]), warped[0][1]
+            a11, a12, a22, b1, b2, wr, wd = _fr_coef_rgb(A, bw, inside, u, v, alpha, gamma, delta)
+        else:
+            bw, inside = _fr_warp(B, px, py)
+            a11, a12, a22, b1, b2, wr, wd = _fr_coef(A, bw, inside, u, v, alpha, gamma, delta)
         du, dv = np.zeros_like(u), np.zeros_like(v)
         for _k in range(n_sor):
             for colour in (0, 1):
@@ -385,6 +438,7 @@ class FlowRefiner(_DenseStage):
         FlowDensifier or CoarseToFineFlow that has run (its buffer on the device, read when the run executes: run it on the
         same stream), or a
         device tensor / object with ``data_ptr()`` holding (H, W, 2) float32 (read when the run executes)."""
+        _grey_only("FlowRefiner.run", pyr_a, pyr_b)
         f, _keep = self._source(src)
         check(self._c("run")(self._h, pyr_a._h, pyr_b._h, C.byref(f), int(bool(x_only)), C.c_void_p(stream or 0)))
         return self
@@ -462,8 +516,11 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     takes dense_flow's value. The sums are plain f64 sums of exact products, the quotient is rounded to f32 once.
     bias: an (ny, nx) array of per-node brightness offsets beta (the coarse-to-fine flow's node bias under patch-mean
     normalisation); the weight is then 1 / max(|Bw - A[y, x] - beta_node|, minerr)^power. None: the operations above.
+    Colour frames: img_a, img_b are three (H, W) planes each and bias is (ny, nx, 3) (_densify_flow_rgb_host).
     Returns (H, W, 2) float32. _stages: a dict that receives "count" (votes taken, int), "wsum" (their summed weight,
     f64) and "edge" (the least distance of a pixel's vote positions to the inside boundary in px, inf without one)."""
+    if np.ndim(img_a) == 3:
+        return _densify_flow_rgb_host(img_a, img_b, d, lost, step, psz, minerr, power, _stages, bias)
     A32, B32, d, lost = _dz_check(img_a, img_b, d, lost, step, psz, minerr, power)
     A, B = A32.astype(np.float64), B32.astype(np.float64)
     h, w = A.shape
@@ -504,6 +561,58 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     return out
 
 
+def _densify_flow_rgb_host(img_a, img_b, d, lost, step, psz, minerr, power, _stages, bias):
+    """densify_flow_host on colour frames (DESIGN.md §4 "Colour"): img_a, img_b are three (H, W) planes each, bias None or
+    (ny, nx, 3), one offset per channel. A vote warps the three channels of B at its one position, with one inside
+    decision, and its weight is 1 / max(e, minerr)^power with e = (1/3) sum_c |Bw_c - A_c[y, x] - beta_c|: the channel
+    mean, so that minerr keeps its meaning in grey levels. Everything else is densify_flow_host's."""
+    A3, B3 = np.asarray(img_a, np.float32), np.asarray(img_b, np.float32)
+    if A3.ndim != 3 or A3.shape[0] != 3 or B3.shape != A3.shape:
+        raise ValueError("densify: colour frames are three (H, W) planes each")
+    _, _, d, lost = _dz_check(A3[0], B3[0], d, lost, step, psz, minerr, power)
+    A, B = A3.astype(np.float64), B3.astype(np.float64)
+    h, w = A.shape[1:]
+    ny, nx = lost.shape
+    i0, i1 = _dz_nodes(w, nx, step, psz)
+    j0, j1 = _dz_nodes(h, ny, step, psz)
+    d64 = d.astype(np.float64)
+    if bias is not None:
+        bias = np.asarray(bias, np.float64)
+        if bias.shape != (ny, nx, 3):
+            raise ValueError(f"densify needs bias ({ny}, {nx}, 3)")
+    yy, xx = np.mgrid[0:h, 0:w]
+    su, sv, sw = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
+    cnt = np.zeros((h, w), np.int64)
+    edge = np.full((h, w), np.inf)
+    for a in range(max(int((j1 - j0).max()) + 1, 0)):
+        j, vj = np.minimum(j0 + a, ny - 1), j0 + a <= j1
+        for b in range(max(int((i1 - i0).max()) + 1, 0)):
+            i, vi = np.minimum(i0 + b, nx - 1), i0 + b <= i1
+            votes = vj[:, None] & vi[None, :] & ~lost[j][:, i]
+            dx, dy = d64[j][:, i, 0], d64[j][:, i, 1]
+            px, py = xx + dx, yy + dy
+            with np.errstate(invalid="ignore"):
+                e = 0.0
+                for c in range(3):
+                    bw, inside = _fr_warp(B[c], px, py)
+                    res = bw - A[c] if bias is None else bw - A[c] - bias[j][:, i, c]
+                    e = e + np.abs(res)
+                e = e / 3.0
+                near = np.minimum(np.minimum(np.abs(px), np.abs(px - (w - 1))), np.minimum(np.abs(py), np.abs(py - (h - 1))))
+                edge = np.where(votes & (near < edge), near, edge)
+                ok = votes & (inside > 0)
+                wgt = 1.0 / _dz_power(np.fmax(e, float(minerr)), power)
+                su, sv, sw = np.where(ok, su + wgt * dx, su), np.where(ok, sv + wgt * dy, sv), np.where(ok, sw + wgt, sw)
+            cnt += ok
+    out = _dense_from_nodes(d.copy(), lost, w, h, step)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[..., 0] = np.where(cnt > 0, su / sw, out[..., 0])
+        out[..., 1] = np.where(cnt > 0, sv / sw, out[..., 1])
+    if _stages is not None:
+        _stages.update(count=cnt, wsum=sw, edge=edge)
+    return out
+
+
 class FlowDensifier(_DenseStage):
     """densify_flow_host on the device (``ictr_flowdensify_*``, one k_densify launch per field) for w x h frames;
     parameters as DENSIFY_DEFAULTS. ``run`` enqueues and returns; ``dense`` (the densified field) waits. The object is a
@@ -519,6 +628,7 @@ class FlowDensifier(_DenseStage):
         """grid: a FlowGrid of the object's size that holds a field, tracked A -> B with patches of psz."""
         if not isinstance(grid, FlowGrid):
             raise TypeError("FlowDensifier.run needs a FlowGrid")
+        _grey_only("FlowDensifier.run", pyr_a, pyr_b)
         check(self._c("run")(self._h, grid._h, pyr_a._h, pyr_b._h, int(psz), C.c_void_p(stream or 0)))
         return self
 
@@ -569,16 +679,38 @@ def _c2f_init(coarse, w, h, step, x_only=False):
     return init
 
 
+def _c2f_channels(pyr):
+    """A frame's pyramids as a list: one for a grey frame (a pyramid), three for a colour frame (a sequence of three)."""
+    if hasattr(pyr, "img"):
+        return [pyr]
+    pyrs = list(pyr)
+    if len(pyrs) != 3:
+        raise ValueError(f"c2f flow: a colour frame is three pyramids, one per channel, not {len(pyrs)}")
+    return pyrs
+
+
+def _csum(vals):
+    """The sum over the channels in their order (one channel: its value, untouched)."""
+    s = vals[0]
+    for v in vals[1:]:
+        s = s + v
+    return s
+
+
 def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm=False):
     """Step 3 of c2f_flow_host at level l from the starts `init` (ny, nx, 2) float32. patnorm: patch-mean normalisation,
-    T <- T - mean(T) once and r = T - (I - mean(I)) in every iteration, nothing else changed. Returns (d (ny, nx, 2) float32
+    T <- T - mean(T) once and r = T - (I - mean(I)) in every iteration, nothing else changed. A colour frame (three
+    pyramids per frame, DESIGN.md "Colour"): T_c, Gx_c, Gy_c are sampled per channel, H = sum_c sum_px G_c G_c^T and
+    b = sum_c sum_px G_c r_c with r_c = T_c - I_c (patnorm: each channel less its own means), one conditioning decision
+    and one step per node; nothing else changes. Returns (d (ny, nx, 2) float32
     before the fill (NaN at a lost node), status (ny, nx) uint8, margins): margins is a dict of (ny, nx) f64 arrays, the
     least distance of a node's decisions from their thresholds (inf where the decision was not taken):
       "eps"   | |step| - eps | over the steps taken, in px
       "view"  distance of a tested position from the border it is tested against, in px
       "far"   | |p - init| - psz | at the rejection test, in px
       "det"   | det / tr^2 - min_det |"""
-    w, h = _c2f_level_size(pyr_a, l)
+    pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
+    w, h = _c2f_level_size(pas[0], l)
     xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
     ny, nx = len(ys), len(xs)
     d = np.full((ny, nx, 2), np.nan, np.float32)
@@ -598,10 +730,11 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
             if not (np.isfinite(i0).all() and in_view(j, i, X + i0[0], Y + i0[1])):
                 continue  # lost
             d[j, i] = init[j, i]
-            T = _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y))
-            Gx = _c2f_sample(pyr_a.dx[l], pyr_a.pad, psz, float(X), float(Y))
-            Gy = _c2f_sample(pyr_a.dy[l], pyr_a.pad, psz, float(X), float(Y))
-            hxx, hxy, hyy = (Gx * Gx).sum(), (Gx * Gy).sum(), (Gy * Gy).sum()
+            T = [_c2f_sample(q.img[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            Gx = [_c2f_sample(q.dx[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            Gy = [_c2f_sample(q.dy[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            hxx, hxy, hyy = (_csum([(gx * gx).sum() for gx in Gx]), _csum([(gx * gy).sum() for gx, gy in zip(Gx, Gy)]),
+                             _csum([(gy * gy).sum() for gy in Gy]))
             det, tr = hxx * hyy - hxy * hxy, hxx + hyy
             if tr > 0:
                 m["det"][j, i] = abs(det / (tr * tr) - min_det)
@@ -609,7 +742,7 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
                 status[j, i] = C2F_HELD_COND
                 continue
             if patnorm:
-                T = T - T.mean()
+                T = [t - t.mean() for t in T]
             p = i0.copy()
             st = C2F_TRACKED
             for _ in range(maxiter):
@@ -617,9 +750,9 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
                 if not in_view(j, i, cx, cy):
                     st = C2F_HELD_VIEW
                     break
-                I = _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, cx, cy)
-                r = T - (I - I.mean()) if patnorm else T - I
-                bx, by = (Gx * r).sum(), (Gy * r).sum()
+                I = [_c2f_sample(q.img[l], q.pad, psz, cx, cy) for q in pbs]
+                r = [t - (v - v.mean()) if patnorm else t - v for t, v in zip(T, I)]
+                bx, by = _csum([(g * e).sum() for g, e in zip(Gx, r)]), _csum([(g * e).sum() for g, e in zip(Gy, r)])
                 dx, dy = (hyy * bx - hxy * by) / det, (hxx * by - hxy * bx) / det
                 p += (dx, dy)
                 n = np.hypot(dx, dy)
@@ -644,8 +777,10 @@ def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, p
     conditioning iff not tr > 0 or not hxx > min_hx tr; an iteration tests the view at (X + p, Y), samples I there, takes
     dx = sum Gx (T - I) / hxx (patnorm: T - mean(T) and I - mean(I)), p += dx, and stops when dx^2 < eps^2; the rejection
     is not (p - init.x)^2 <= psz^2. y never moves: d = (p, +0.0) when tracked, (init.x, +0.0) when held. Returns what
-    _c2f_search_host returns; margins["det"] is | hxx / tr - min_hx |, "eps" | |dx| - eps |, "far" | |p - init.x| - psz |."""
-    w, h = _c2f_level_size(pyr_a, l)
+    _c2f_search_host returns; margins["det"] is | hxx / tr - min_hx |, "eps" | |dx| - eps |, "far" | |p - init.x| - psz |.
+    Colour frames (three pyramids per frame): hxx, hyy and sum Gx r are summed over the channels, as in _c2f_search_host."""
+    pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
+    w, h = _c2f_level_size(pas[0], l)
     xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
     ny, nx = len(ys), len(xs)
     d = np.full((ny, nx, 2), np.nan, np.float32)
@@ -664,10 +799,10 @@ def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, p
             if not (np.isfinite(ix) and in_view(j, i, X + ix)):
                 continue  # lost
             d[j, i] = (init[j, i, 0], np.float32(0))
-            T = _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y))
-            Gx = _c2f_sample(pyr_a.dx[l], pyr_a.pad, psz, float(X), float(Y))
-            Gy = _c2f_sample(pyr_a.dy[l], pyr_a.pad, psz, float(X), float(Y))
-            hxx, hyy = (Gx * Gx).sum(), (Gy * Gy).sum()
+            T = [_c2f_sample(q.img[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            Gx = [_c2f_sample(q.dx[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            Gy = [_c2f_sample(q.dy[l], q.pad, psz, float(X), float(Y)) for q in pas]
+            hxx, hyy = _csum([(gx * gx).sum() for gx in Gx]), _csum([(gy * gy).sum() for gy in Gy])
             tr = hxx + hyy
             if tr > 0:
                 m["det"][j, i] = abs(hxx / tr - min_hx)
@@ -675,16 +810,16 @@ def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, p
                 status[j, i] = C2F_HELD_COND
                 continue
             if patnorm:
-                T = T - T.mean()
+                T = [t - t.mean() for t in T]
             p = ix
             st = C2F_TRACKED
             for _ in range(maxiter):
                 if not in_view(j, i, X + p):
                     st = C2F_HELD_VIEW
                     break
-                I = _c2f_sample(pyr_b.img[l], pyr_b.pad, psz, X + p, float(Y))
-                r = T - (I - I.mean()) if patnorm else T - I
-                dx = (Gx * r).sum() / hxx
+                I = [_c2f_sample(q.img[l], q.pad, psz, X + p, float(Y)) for q in pbs]
+                r = [t - (v - v.mean()) if patnorm else t - v for t, v in zip(T, I)]
+                dx = _csum([(g * e).sum() for g, e in zip(Gx, r)]) / hxx
                 p += dx
                 m["eps"][j, i] = min(m["eps"][j, i], abs(abs(dx) - eps))
                 if dx * dx < eps * eps:
@@ -706,10 +841,12 @@ def _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins=None):
     d (a tracked node's p, a held node's init); where its final position (X, Y) + d passes the search's view test,
     beta = mean(patch of B there) - mean(patch of A at (X, Y)), both sampled as the search samples them. Every other
     node has beta = 0: a tracked node may end up to psz out of view, and no tap then leaves a plane padded by psz.
-    margins: _c2f_search_host's dict; the distance of this view decision from its border joins "view"."""
-    w, h = _c2f_level_size(pyr_a, l)
+    margins: _c2f_search_host's dict; the distance of this view decision from its border joins "view".
+    Colour frames (three pyramids per frame): (ny, nx, 3), one offset per channel, at the same nodes."""
+    pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
+    w, h = _c2f_level_size(pas[0], l)
     xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
-    beta = np.zeros((len(ys), len(xs)))
+    beta = np.zeros((len(ys), len(xs)) if len(pas) == 1 else (len(ys), len(xs), len(pas)))
     for j, Y in enumerate(ys):
         for i, X in enumerate(xs):
             if status[j, i] == C2F_LOST:
@@ -720,8 +857,13 @@ def _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins=None):
                 margins["view"][j, i] = min(margins["view"][j, i], near)
             if not (0 <= x <= w and 0 <= y <= h):
                 continue
-            beta[j, i] = (_c2f_sample(pyr_b.img[l], pyr_b.pad, psz, x, y).mean()
-                          - _c2f_sample(pyr_a.img[l], pyr_a.pad, psz, float(X), float(Y)).mean())
+            if len(pas) == 1:
+                beta[j, i] = (_c2f_sample(pbs[0].img[l], pbs[0].pad, psz, x, y).mean()
+                              - _c2f_sample(pas[0].img[l], pas[0].pad, psz, float(X), float(Y)).mean())
+            else:
+                for c, (qa, qb) in enumerate(zip(pas, pbs)):
+                    beta[j, i, c] = (_c2f_sample(qb.img[l], qb.pad, psz, x, y).mean()
+                                     - _c2f_sample(qa.img[l], qa.pad, psz, float(X), float(Y)).mean())
     return beta
 
 
@@ -844,13 +986,27 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     lv_l (0 .. lv_f; DESIGN.md "A finest level above 0"): the levels lv_f .. lv_l run as above (a level's field does not
     depend on finer levels), and the result is upsample_flow_host(U_lv_l, W, H, lv_l, x_only). With lv_l = 0 nothing is
     up-sampled. The size rules hold for the levels lv_l .. lv_f.
+    Colour (DESIGN.md "Colour"): pyr_a and pyr_b are each a sequence of THREE pyramids, one per channel, equal in size,
+    levels and padding. The nodes, the starts, the view tests, the eps stop, the rejection, the status values, the fill
+    and the up-sampling are unchanged; the search sums H and b over the channels and takes one decision and one step per
+    node (_c2f_search_host), the node bias under patnorm is (ny, nx, 3), one offset per channel (_c2f_bias_host), and a
+    vote weighs the channel mean of the absolute residuals (densify_flow_host on three planes). Three equal channels
+    give the grey rule in real arithmetic. The refinement takes the three planes per frame: its steps 1 and 2 run per
+    channel and its two robust weights are joint over the channels (refine_flow_host, _fr_coef_rgb).
     _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
     "margins" (_c2f_search_host's), "field" (U_l) and "bias" (the node bias, None without patnorm)."""
-    lv_f = _c2f_check(pyr_a, pyr_b, step, psz, lv_f, refine, lv_l)
+    pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
+    if len(pas) != len(pbs):
+        raise ValueError("c2f flow: one frame is grey and the other colour")
+    if len(pas) == 3:
+        geo = [[(q.pad, len(q.img)) + tuple(i.shape for i in q.img) for q in qs] for qs in (pas, pbs)]
+        if any(g != gs[0] for gs in geo for g in gs):
+            raise ValueError("c2f flow: the three pyramids of a frame differ in geometry")
+    lv_f = _c2f_check(pas[0], pbs[0], step, psz, lv_f, refine, lv_l)
     lv_l = int(lv_l)
     U = None
     for l in range(lv_f, lv_l - 1, -1):
-        w, h = _c2f_level_size(pyr_a, l)
+        w, h = _c2f_level_size(pas[0], l)
         init = _c2f_init(U, w, h, step, x_only)
         if x_only:
             d, status, margins = _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm)
@@ -858,7 +1014,9 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
             d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm)
         lost = status == C2F_LOST
         bias = _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins) if patnorm else None
-        A, B = _c2f_plane(pyr_a, l), _c2f_plane(pyr_b, l)
+        A, B = _c2f_plane(pas[0], l), _c2f_plane(pbs[0], l)
+        if len(pas) == 3:
+            A, B = np.stack([_c2f_plane(q, l) for q in pas]), np.stack([_c2f_plane(q, l) for q in pbs])
         U = densify_flow_host(A, B, np.where(lost[..., None], np.float32(0), d), lost, step, psz, bias=bias,
                               **(densify or {}))
         if refine is not None:
@@ -868,7 +1026,7 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
             _dense_from_nodes(filled, lost, w, h, step)
             _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U, bias=bias))
     if lv_l > 0:
-        w0, h0 = _c2f_level_size(pyr_a, 0)
+        w0, h0 = _c2f_level_size(pas[0], 0)
         return upsample_flow_host(U, w0, h0, lv_l, bool(x_only))
     return U
 
@@ -881,12 +1039,16 @@ class CoarseToFineFlow:
     rectified stereo pair (k_c2f_level's XONLY forms, the refinement along x; v is +0.0 at every level). lv_l:
     c2f_flow_host's finest level (default 0); above 0 only the levels lv_f .. lv_l exist and run, and a run ends with
     k_flow_upsample from level lv_l's field into the object's w x h result plane, which ``dense`` and ``device_ptr`` then
-    hand out. ``run`` enqueues and returns; ``dense``
+    hand out. channels: 1 (grey frames, one pyramid each) or 3 (colour frames, c2f_flow_host's rule on triples: ``run``
+    then takes two sequences of three pyramids, k_c2f_level's NCH = 3 forms, k_densify_rgb and k_fr_warp_rgb /
+    k_fr_coef_rgb run, and ``level_bias`` is (ny, nx, 3)). ``run`` enqueues and returns; ``dense``
     (the w x h field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 
     def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False,
-                 x_only=False, lv_l=0):
+                 x_only=False, lv_l=0, channels=1):
         dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
+        if channels not in (1, 3):
+            raise ValueError(f"CoarseToFineFlow: channels is {channels} (1: grey, or 3: colour)")
         unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
         if unknown:
             raise TypeError(f"CoarseToFineFlow: unknown parameter(s) {sorted(unknown)}")
@@ -912,6 +1074,9 @@ class CoarseToFineFlow:
         self.x_only = bool(x_only)
         if self.x_only:
             check(L.ictr_c2fflow_set_x_only(self._h, 1))
+        self.channels = int(channels)
+        if self.channels != 1:
+            check(L.ictr_c2fflow_set_channels(self._h, self.channels))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -919,6 +1084,17 @@ class CoarseToFineFlow:
             self._h = None
 
     def run(self, pyr_a, pyr_b, stream=None):
+        """channels == 3: pyr_a and pyr_b are each a sequence of three device pyramids, one per channel."""
+        if self.channels == 3:
+            trip = []
+            for p in (pyr_a, pyr_b):
+                if hasattr(p, "_h") or len(p) != 3:
+                    raise ValueError("CoarseToFineFlow.run: with channels=3 a frame is three pyramids, one per channel")
+                trip.append((C.c_void_p * 3)(*[q._h.value for q in p]))
+            check(_lib.load().ictr_c2fflow_run_rgb(self._h, trip[0], trip[1], C.c_void_p(stream or 0)))
+            return self
+        if not hasattr(pyr_a, "_h") or not hasattr(pyr_b, "_h"):
+            raise ValueError("CoarseToFineFlow.run: with channels=1 a frame is one pyramid (colour needs channels=3)")
         check(_lib.load().ictr_c2fflow_run(self._h, pyr_a._h, pyr_b._h, C.c_void_p(stream or 0)))
         return self
 
@@ -945,8 +1121,12 @@ class CoarseToFineFlow:
         return field, d, status
 
     def level_bias(self, l):
-        """The node bias (ny, nx) float32 of level l of the last run; patnorm only."""
+        """The node bias (ny, nx) float32 of level l of the last run, (ny, nx, 3) with channels=3; patnorm only."""
         _, _, nx, ny = self.level_dims(l)
+        if self.channels == 3:
+            bias = np.empty((ny, nx, 3), np.float32)
+            check(_lib.load().ictr_c2fflow_read_level_bias_rgb(self._h, int(l), fp(bias)))
+            return bias
         bias = np.empty((ny, nx), np.float32)
         check(_lib.load().ictr_c2fflow_read_level_bias(self._h, int(l), fp(bias)))
         return bias
@@ -971,8 +1151,11 @@ class CoarseToFineFlow:
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
     """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call
     (params: its keywords, patnorm, x_only and lv_l among them)."""
-    lv_f = pyr_a.lv_f if lv_f is None else lv_f
-    return CoarseToFineFlow(pyr_a.w, pyr_a.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
+    first = pyr_a if hasattr(pyr_a, "_h") else pyr_a[0]
+    if first is not pyr_a:
+        params.setdefault("channels", 3)
+    lv_f = first.lv_f if lv_f is None else lv_f
+    return CoarseToFineFlow(first.w, first.h, lv_f, step, psz, **params).run(pyr_a, pyr_b).dense()
 
 
 def good_features(img, maxcorners=1000, quality=0.001, mindist=5, win=3):
@@ -1075,6 +1258,7 @@ class FlowGrid:
 
     def compute(self, pyr_a, pyr_b, psz=15, lv_f=None, maxiter=10, eps=0.01, stream=None):
         """Track the nodes A -> B (k_patchflow), d = out - pts, fill the lost nodes. Enqueued, no host wait."""
+        _grey_only("FlowGrid.compute", pyr_a, pyr_b)
         lv_f = pyr_a.lv_f if lv_f is None else lv_f
         check(_lib.load().ictr_flowgrid_compute(self._h, pyr_a._h, pyr_b._h, int(psz), int(lv_f), int(maxiter),
                                                 float(eps), C.c_void_p(stream or 0)))
@@ -1083,6 +1267,7 @@ class FlowGrid:
     def compute_x(self, pyr_a, pyr_b, psz=15, lv_f=None, maxiter=10, eps=0.01, stream=None):
         """compute for a rectified stereo pair: the nodes are tracked along x only (k_patchdisp); every y displacement
         of the grid is +0.0. The field equals dense_disparity's. Enqueued, no host wait."""
+        _grey_only("FlowGrid.compute_x", pyr_a, pyr_b)
         lv_f = pyr_a.lv_f if lv_f is None else lv_f
         check(_lib.load().ictr_flowgrid_compute_x(self._h, pyr_a._h, pyr_b._h, int(psz), int(lv_f), int(maxiter),
                                                   float(eps), C.c_void_p(stream or 0)))
@@ -1138,6 +1323,9 @@ class PointTracker:
 
     def push_frame(self, img):
         img = _lib.f32c(img)
+        if img.ndim == 3:
+            raise ValueError("PointTracker.push_frame takes grey (h, w) frames: colour frames are "
+                             "CoarseToFineFlow(channels=3)'s alone")
         if img.shape != (self.h, self.w):
             raise ValueError(f"push_frame needs a {self.w}x{self.h} frame, got {img.shape[1]}x{img.shape[0]}")
         check(_lib.load().ictr_pointtrack_push_frame(self._h, fp(img)))

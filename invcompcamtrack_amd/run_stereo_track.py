@@ -3,7 +3,7 @@
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
          [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
          [--refine [alpha,gamma,delta,outer,sor,omega]] [--densify [minerr,power]] [--flow grid|c2f|c2f-1d]
-         [--patnorm] [--lv-l N]
+         [--patnorm] [--lv-l N] [--colour]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
@@ -16,7 +16,9 @@ with --refine, refinement per pyramid level; --densify and --refine then give th
 --disparity 1d). --flow c2f-1d is --flow c2f with the stereo pair searched along x only (CoarseToFineFlow's x_only; the
 temporal fields stay 2-D; --disparity is not consulted). --patnorm switches on the coarse-to-fine flow's patch-mean normalisation, for cameras or frames of
 differing brightness (with --flow c2f or c2f-1d only). --lv-l N stops every coarse-to-fine object at level N and up-samples that
-level's field to the frame (CoarseToFineFlow's lv_l; default 0; with --flow c2f or c2f-1d only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+level's field to the frame (CoarseToFineFlow's lv_l; default 0; with --flow c2f or c2f-1d only). --colour reads the frames
+as three channels (io_formats.read_image_rgb: .npy of (h, w, 3), binary .ppm, else PIL) and computes every field on colour
+frames (CoarseToFineFlow's channels=3; with --flow c2f or c2f-1d only). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -88,7 +90,12 @@ def main(argv=None):
     ap.add_argument("--flow", choices=("grid", "c2f", "c2f-1d"), default="grid")
     ap.add_argument("--patnorm", action="store_true")
     ap.add_argument("--lv-l", dest="lv_l", type=int, default=0)
+    ap.add_argument("--colour", action="store_true")
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
+    if a.colour and a.flow not in ("c2f", "c2f-1d"):
+        ap.error("--colour needs --flow c2f or c2f-1d: colour frames are built for the coarse-to-fine flow alone")
+    if a.colour and a.fields:
+        ap.error("--colour reads frames; --fields brings fields that are computed already")
     if a.flow == "c2f" and a.disparity == "1d":
         ap.error("--flow c2f with --disparity 1d: the 1-D form of the coarse-to-fine flow is --flow c2f-1d")
     if a.patnorm and a.flow not in ("c2f", "c2f-1d"):
@@ -107,11 +114,12 @@ def main(argv=None):
         if not pairs or any(len(p) != 2 for p in pairs):
             print("the list needs a left and a right path per line", file=sys.stderr)
             return 2
-        frames = [[np.asarray(iof.read_image_gray(fn), np.float32) for fn in p] for p in pairs]
-        h, w = frames[0][0].shape
+        read = iof.read_image_rgb if a.colour else iof.read_image_gray
+        frames = [[np.asarray(read(fn), np.float32) for fn in p] for p in pairs]
+        h, w = frames[0][0].shape[:2]
         t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity,
                                  refine=a.refine, densify=a.densify, flow=a.flow, patnorm=a.patnorm, lv_l=a.lv_l,
-                                 **th)
+                                 colour=a.colour, **th)
         for left, right in frames:
             t.push_frames(left, right)
         xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()

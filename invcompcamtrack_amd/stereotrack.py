@@ -305,11 +305,13 @@ class StereoPointTracker:
     needs flow="c2f" or "c2f-1d" and is refused with flow="grid", whose whole-pyramid kernels have no such form.
     lv_l (default 0) is the finest level of every coarse-to-fine object of both sets (CoarseToFineFlow's lv_l: the levels
     lv_f .. lv_l run and the field of level lv_l is up-sampled to the frame); above 0 it likewise needs flow="c2f" or
-    "c2f-1d"."""
+    "c2f-1d". colour=True (likewise flow="c2f" or "c2f-1d" alone): push_frames takes (h, w, 3) frames and holds three
+    pyramids per side, one per channel, and every object is a CoarseToFineFlow(channels=3); the fields the window reads
+    are the same w x h flow planes."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
                  xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False,
-                 lv_l=0):
+                 lv_l=0, colour=False):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         if flow not in ("grid", "c2f", "c2f-1d"):
@@ -323,7 +325,11 @@ class StereoPointTracker:
         if lv_l and flow not in ("c2f", "c2f-1d"):
             raise ValueError("lv_l > 0 needs flow='c2f' or 'c2f-1d': a finest level above 0 is built for the coarse-to-fine "
                              "flow alone, not for the flow grids of flow='grid'")
+        if colour and flow not in ("c2f", "c2f-1d"):
+            raise ValueError("colour=True needs flow='c2f' or 'c2f-1d': colour frames are built for the coarse-to-fine flow "
+                             "alone, not for the flow grids of flow='grid'")
         self.flow = flow
+        self.colour = bool(colour)
         self.lv_l = int(lv_l)
         self.patnorm = bool(patnorm)
         self.flows = []
@@ -361,15 +367,29 @@ class StereoPointTracker:
         if k >= self.bsize:
             raise ValueError(f"the window holds {self.bsize} frames")
         imgs = [_lib.f32c(left), _lib.f32c(right)]
-        for im in imgs:
-            if im.shape != (self.h, self.w):
-                raise ValueError(f"push_frames needs {self.w}x{self.h} frames, got {im.shape[1]}x{im.shape[0]}")
-        slot = self._pyr[k & 1]
-        if slot is None:
-            slot = self._pyr[k & 1] = [Pyramid(im, self.lv_f, self.psz, True) for im in imgs]
+        if self.colour:  # three pyramids per side, one per channel, rebuilt in place like the grey ones
+            for im in imgs:
+                if im.shape != (self.h, self.w, 3):
+                    raise ValueError(f"push_frames needs ({self.h}, {self.w}, 3) colour frames with colour=True, got "
+                                     f"{im.shape}")
+            chans = [[np.ascontiguousarray(im[..., c]) for c in range(3)] for im in imgs]
+            slot = self._pyr[k & 1]
+            if slot is None:
+                slot = self._pyr[k & 1] = [[Pyramid(ch, self.lv_f, self.psz, True) for ch in side] for side in chans]
+            else:
+                for ps, side in zip(slot, chans):
+                    for p, ch in zip(ps, side):
+                        p.rebuild(ch)
         else:
-            for p, im in zip(slot, imgs):
-                p.rebuild(im)
+            for im in imgs:
+                if im.shape != (self.h, self.w):
+                    raise ValueError(f"push_frames needs {self.w}x{self.h} frames, got {im.shape[1]}x{im.shape[0]}")
+            slot = self._pyr[k & 1]
+            if slot is None:
+                slot = self._pyr[k & 1] = [Pyramid(im, self.lv_f, self.psz, True) for im in imgs]
+            else:
+                for p, im in zip(slot, imgs):
+                    p.rebuild(im)
         pl, pr = slot
         kw = dict(psz=self.psz, lv_f=self.lv_f, maxiter=self.maxiter, eps=self.eps)
         # the frame's fields (name, A, B, x_only): the stereo pair, then from the second frame on the four temporal ones
@@ -412,7 +432,7 @@ class StereoPointTracker:
         def make(x_only=False):
             return CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter, self.eps,
                                     densify=self.densify, refine=self.refine, patnorm=self.patnorm, x_only=x_only,
-                                    lv_l=self.lv_l)
+                                    lv_l=self.lv_l, channels=3 if self.colour else 1)
 
         if self.flow == "c2f-1d":
             c = dict(self._set(self._fsets, k, make, ("l_fwd", "l_bwd", "r_fwd", "r_bwd")))

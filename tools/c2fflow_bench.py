@@ -34,6 +34,14 @@ x_only and patnorm off (psz 8 and 15) and FlowGrid.compute_x (psz 15) on the sam
 A finest level above 0: per shape and patch size three objects with lv_l 0, 1 and 2, run in turn; the whole runs of each,
 their ratios to lv_l = 0, and k_flow_upsample's own time (the object's event) next to the 16 B per pixel copy of the same
 round. Recorded without a bar. --parent-root measures CoarseToFineFlow.run at lv_l = 0 (psz 8 and 15), with the same bar.
+
+  python tools/c2fflow_bench.py --colour [--reps 7] [--out profiles/c2fflow_rgb_bench.json] [--parent-root DIR]
+
+Colour frames next to grey ones: per shape and patch size two objects, channels 1 and 3, run in turn (the colour frame's
+channel 0 is the grey frame, the other two channels are textures of their own under the same motion); per level the search
+and densification medians of each and their ratio, and the whole runs. Recorded without a bar. --parent-root measures the
+default paths colour must leave alone, CoarseToFineFlow.run grey (psz 8 and 15) and FlowDensifier.run (psz 15), with the
+same bar.
 """
 import argparse
 import json
@@ -111,7 +119,7 @@ def option_child(root, reps, option):
                 grid = pf.FlowGrid(w, h, STEP)
                 rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
                                                 for _ in range(reps + 1)][1:]
-            elif psz == PSZS[1] and option == "patnorm":
+            elif psz == PSZS[1] and option in ("patnorm", "colour"):
                 grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
                 grid.compute(pa, pb, psz=psz, lv_f=LV_F)
                 rec["flowdensifier_run_ms"] = [float(_timed(torch, lambda: dz.run(grid, pa, pb, psz)))
@@ -215,21 +223,28 @@ def option_main(a, option):
     from tools.patchdisp_bench import frames, stats
     if ic.device_count() < 1:
         raise SystemExit("no HIP device: nothing is measured without one")
-    name = {"patnorm": "c2fflow_patnorm", "x_only": "c2fflow_xonly"}[option]
+    name = {"patnorm": "c2fflow_patnorm", "x_only": "c2fflow_xonly", "colour": "c2fflow_rgb"}[option]
     out = {"bench": name, "step": STEP, "lv_f": LV_F, "reps": a.reps, "densify": pf.DENSIFY_DEFAULTS,
            "refine": None, "shapes": []}
     ok = True
     for w, h in SHAPES:
         fr = frames(w, h)
+        more = (frames(w, h, seed=6), frames(w, h, seed=7)) if option == "colour" else None
         for psz in PSZS:
             second = fr[0][1] if option == "x_only" else fr[1][0]
             pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(second, LV_F, psz, True)
-            cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, **{option: on}) for on in (False, True)}
+            args = {False: (pa, pb), True: (pa, pb)}
+            if option == "colour":  # channel 0 is the grey run's frame; the other two have textures of their own
+                tri = [[ic.Pyramid(f[k][0], LV_F, psz, True) for f in (fr, more[0], more[1])] for k in (0, 1)]
+                args[True] = (tri[0], tri[1])
+                cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, channels=3 if on else 1) for on in (False, True)}
+            else:
+                cs = {on: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, **{option: on}) for on in (False, True)}
             levels, total = {False: [], True: []}, {False: [], True: []}
             for rep in range(a.reps + 1):  # the first round warms everything up
                 for on, c in cs.items():
                     c.set_timing(True)
-                    tt = _timed(torch, lambda: c.run(pa, pb))
+                    tt = _timed(torch, lambda: c.run(*args[on]))
                     if rep:
                         levels[on].append(c.kernel_ms())
                         total[on].append(float(tt))
@@ -261,8 +276,9 @@ def main():
     ap.add_argument("--patnorm", action="store_true", help="measure the cost of patch-mean normalisation instead")
     ap.add_argument("--x-only", action="store_true", help="measure the 1-D form against the 2-D one instead")
     ap.add_argument("--lv-l", dest="lv_l", action="store_true", help="measure a finest level above 0 instead")
+    ap.add_argument("--colour", action="store_true", help="measure colour frames against grey ones instead")
     ap.add_argument("--option-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l"), help=argparse.SUPPRESS)
+    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l", "colour"), help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -274,8 +290,8 @@ def main():
         ap.error("at least 7 runs each")
     if a.lv_l:
         return lvl_main(a)
-    if a.patnorm or a.x_only:
-        return option_main(a, "x_only" if a.x_only else "patnorm")
+    if a.patnorm or a.x_only or a.colour:
+        return option_main(a, "x_only" if a.x_only else "colour" if a.colour else "patnorm")
     a.out = a.out or os.path.join(ROOT, "profiles", "c2fflow_bench.json")
     sys.path.insert(0, ROOT)
     import numpy as np
