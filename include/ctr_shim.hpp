@@ -613,7 +613,7 @@ class CoarseFlowClass {
   }
   // bias [ny][nx]: the node bias of a run with patch-mean normalisation
   void ReadLevelBias(int level, float *bias) { check(ictr_c2fflow_read_level_bias(h_, level, bias), "ReadLevelBias"); }
-  // Colour frames (include/ictr_c2f_rgb.h): n = 1 or 3, before the first run. With 3 a frame is three pyramids, one per
+  // Colour frames (ictr.h, "colour (three-channel) frames"): n = 1 or 3, before the first run. With 3 a frame is three pyramids, one per
   // channel and equal in geometry, the run is RunRGB and the node bias has three values per node.
   void SetChannels(int n) { check(ictr_c2fflow_set_channels(h_, n), "SetChannels"); }
   int Channels() const {

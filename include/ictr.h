@@ -996,14 +996,72 @@ int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field, float *d, 
  * search (k_c2f_level and the fill), the densification and the refinement, zeros when timing was off */
 int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on);
 int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms);
-/* the stage's patch-mean normalisation: its switch and the reader of the node bias */
-#include "ictr_c2f_patnorm.h"
-/* the stage's 1-D (x only) form for rectified stereo pairs: its switch */
-#include "ictr_c2f_xonly.h"
-/* a finest level above 0, and the up-sampling kernel that finishes such a run */
-#include "ictr_c2f_lvl.h"
-/* colour frames: three pyramids per frame */
-#include "ictr_c2f_rgb.h"
+/* -- patch-mean normalisation (DESIGN.md §4 "Patch-mean normalisation"): its switch and the reader of the node bias */
+/* on != 0: patch-mean normalisation for the next runs, for frames whose brightness differs by a locally constant offset
+ * (the two cameras of a rig, auto-exposure). The search removes the mean of the template and of every frame window;
+ * every node that votes from inside the view gets its brightness offset beta = mean(B at its final position) -
+ * mean(A at the node), any other node +0.0; a node's vote in the densification weighs |Bw - A - beta|. The refinement is
+ * unchanged: its brightness term still sees the offset. Default off: the runs are then, bit for bit and kernel for
+ * kernel, those of an object that never had this call. */
+int ictr_c2fflow_set_patnorm(ictr_c2fflow *c, int on);
+/* of the last run (waits for it), which had patnorm on (refused otherwise): the level's node bias [ny][nx] */
+int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *bias);
+/* -- the 1-D (x only) form for rectified stereo pairs (DESIGN.md §4 "The 1-D form"): its switch */
+/* on != 0: the next runs search along x only. A node starts from the x component of the coarser field alone, the search is
+ * k_patchdisp's rule at the level (hxx and hyy; held by conditioning iff !(tr > 0) or !(hxx > 1e-2 tr); p += bx / hxx),
+ * the rejection is (p - init)^2 > psz^2, the refinement (when on) moves u alone, and the y component of every node and of
+ * every level's field is +0.0 to the bit. It combines with patch-mean normalisation. Default off: the runs are then, bit
+ * for bit, those of an object that never had this call. */
+int ictr_c2fflow_set_x_only(ictr_c2fflow *c, int on);
+int ictr_c2fflow_get_x_only(const ictr_c2fflow *c, int *on);
+/* -- a finest level above 0, and the up-sampling that finishes such a run (DESIGN.md §4 "A finest level above 0").
+ * The rule (patchflow.upsample_flow_host states it in f64): with s = 2^lv and a field F of level lv's size w_l x h_l, output
+ * pixel (x, y) of the w x h frame takes fx = clamp((x + 0.5) / s - 0.5, 0, w_l - 1), x0 = floor(fx), x1 = min(x0 + 1,
+ * w_l - 1), rx = fx - x0 (fy, y0, y1, ry alike with h_l) and, per component, top = (1 - rx) F[y0][x0] + rx F[y0][x1],
+ * bot = (1 - rx) F[y1][x0] + rx F[y1][x1], val = (1 - ry) top + ry bot; the output is s val. The device takes the six
+ * products and three sums in f32 in that order, each rounded. */
+/* ictr_c2fflow_create with a finest level lv_l (0 <= lv_l <= lv_f, refused otherwise): the runs search, densify and refine
+ * the levels lv_f .. lv_l alone, and only those get a grid, a densifier, events, status and bias rows and a refiner; their
+ * results are, bit for bit, those of the same levels of an object with lv_l = 0. With lv_l > 0 the object owns one
+ * w x h x 2 result plane: a run ends with ONE launch of k_flow_upsample from level lv_l's field (the refiner's when the run
+ * refined; with x_only set the y component is not read and is written as +0.0), and ictr_c2fflow_result and
+ * ictr_c2fflow_device_ptr hand out that plane. The size rules of ictr_c2fflow_create hold for the levels lv_l .. lv_f;
+ * ictr_c2fflow_level_dims, _read_level and _read_level_bias refuse a level below lv_l; ictr_c2fflow_get_kernel_ms keeps
+ * its 3 (lv_f + 1) values, zeros below lv_l. lv_l = 0 is ictr_c2fflow_create. */
+int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_f, int lv_l, int step, int psz);
+int ictr_c2fflow_get_lv_l(const ictr_c2fflow *c, int *lv_l);
+/* *ms of k_flow_upsample in the last run (waits for it); 0 when timing was off or lv_l = 0 */
+int ictr_c2fflow_get_upsample_ms(ictr_c2fflow *c, float *ms);
+/* The rule on a caller's field: src [h_l][w_l][2], out [h][w][2], 1 <= lv <= 15, and (w_l, h_l) must be the size of level lv
+ * of a w x h pyramid (round-half-even halving), refused otherwise. x_only != 0: the y component of src is not read and the
+ * y component of out is +0.0. on_device = 0: both are host arrays, staged by the call, which waits. on_device != 0: both are
+ * device pointers and the kernel is enqueued on hip_stream (NULL: the null stream); the call does not wait. */
+int ictr_flow_upsample(const float *src, int w_l, int h_l, int lv, float *out, int w, int h, int x_only, int on_device,
+                       void *hip_stream);
+/* -- colour (three-channel) frames (DESIGN.md §4 "Colour").
+ * A colour frame is THREE pyramids, one per channel, built by ictr_pyramid_create as any other and equal in size, levels
+ * and padding. The rule (patchflow.c2f_flow_host on triples states it in f64): the nodes, the starts, the view tests, the
+ * stop, the rejection, the status values, the fill and the up-sampling are those of one channel; the search sums
+ * H = sum_c sum_px G_c G_c^T and b = sum_c sum_px G_c (T_c - I_c) and takes one conditioning decision and one step per
+ * node; with patnorm every channel loses its own patch mean and a node has one brightness offset per channel; a
+ * densifier's vote weighs the channel mean e = (1/3) sum_c |Bw_c - A_c - beta_c|; the refinement warps and differentiates
+ * per channel, takes its two robust weights jointly over the channels on the channel mean,
+ * q0 = delta inside / 2 / sqrt((1/3) sum_c n0_c Iz_c^2 + eps^2) and qg likewise, and its coefficients as channel means.
+ * Three equal channels give the grey rule in real arithmetic. The number of channels is 1 or 3. */
+/* n = 1 (the object as created) or 3; anything else is refused. To be called before the first run (refused after one): it
+ * sizes the node bias block, [ny][nx][n] floats per level; if that allocation fails the object keeps its channel count.
+ * (The refinement's two more warp planes are made by the first refined run of a 3-channel object.) */
+int ictr_c2fflow_set_channels(ictr_c2fflow *c, int n);
+int ictr_c2fflow_get_channels(const ictr_c2fflow *c, int *n);
+/* ictr_c2fflow_run of a 3-channel object: pyr_a[ch], pyr_b[ch] are channel ch of frames A and B. Refused with a message:
+ * on a 1-channel object (and ictr_c2fflow_run on a 3-channel one), and when the three pyramids of a frame differ in
+ * geometry (size, levels' strides or padding). Every other check is ictr_c2fflow_run's, per channel. The result plane, the
+ * levels' fields, node displacements and status bytes are read as after ictr_c2fflow_run. */
+int ictr_c2fflow_run_rgb(ictr_c2fflow *c, const ictr_pyramid *const pyr_a[3], const ictr_pyramid *const pyr_b[3],
+                         void *hip_stream);
+/* of the last run, which had patnorm on, of a 3-channel object (waits for it): the node bias [ny][nx][3] of a level;
+ * ictr_c2fflow_read_level_bias refuses such an object */
+int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, float *bias);
 
 #ifdef __cplusplus
 }

@@ -358,6 +358,18 @@ SIGNATURES = {
     "ictr_c2fflow_read_level": (C.c_int, [VP, C.c_int, FP, FP, U8P]),
     "ictr_c2fflow_set_timing": (C.c_int, [VP, C.c_int]),
     "ictr_c2fflow_get_kernel_ms": (C.c_int, [VP, FP]),
+    "ictr_c2fflow_set_patnorm": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_read_level_bias": (C.c_int, [VP, C.c_int, FP]),
+    "ictr_c2fflow_set_x_only": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_get_x_only": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fflow_create_lvl": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ictr_c2fflow_get_lv_l": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fflow_get_upsample_ms": (C.c_int, [VP, FP]),
+    "ictr_flow_upsample": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
+    "ictr_c2fflow_set_channels": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fflow_get_channels": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fflow_run_rgb": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
+    "ictr_c2fflow_read_level_bias_rgb": (C.c_int, [VP, C.c_int, FP]),
 }
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {
@@ -366,34 +378,6 @@ SIGNATURES_REFERENCE_NAMES = {
     "ictr_triangulate_full3D_LM": (C.c_int, [FP, FP, FP, FP, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                              C.c_float]),
 }
-# the coarse-to-fine flow's patch-mean normalisation (declared in include/ictr_c2f_patnorm.h, which ictr.h includes)
-SIGNATURES_PATNORM = {
-    "ictr_c2fflow_set_patnorm": (C.c_int, [VP, C.c_int]),
-    "ictr_c2fflow_read_level_bias": (C.c_int, [VP, C.c_int, FP]),
-}
-# the coarse-to-fine flow's 1-D form (declared in include/ictr_c2f_xonly.h, which ictr.h includes)
-SIGNATURES_XONLY = {
-    "ictr_c2fflow_set_x_only": (C.c_int, [VP, C.c_int]),
-    "ictr_c2fflow_get_x_only": (C.c_int, [VP, C.POINTER(C.c_int)]),
-}
-# the coarse-to-fine flow's finest level above 0 and its up-sampling (declared in include/ictr_c2f_lvl.h, which ictr.h
-# includes)
-SIGNATURES_LVL = {
-    "ictr_c2fflow_create_lvl": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ictr_c2fflow_get_lv_l": (C.c_int, [VP, C.POINTER(C.c_int)]),
-    "ictr_c2fflow_get_upsample_ms": (C.c_int, [VP, FP]),
-    "ictr_flow_upsample": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
-}
-
-# the coarse-to-fine flow on colour frames, three pyramids per frame (declared in include/ictr_c2f_rgb.h, which ictr.h
-# includes)
-SIGNATURES_RGB = {
-    "ictr_c2fflow_set_channels": (C.c_int, [VP, C.c_int]),
-    "ictr_c2fflow_get_channels": (C.c_int, [VP, C.POINTER(C.c_int)]),
-    "ictr_c2fflow_run_rgb": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
-    "ictr_c2fflow_read_level_bias_rgb": (C.c_int, [VP, C.c_int, FP]),
-}
-
 _lib = None
 
 
@@ -435,9 +419,7 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
-                              + list(SIGNATURES_PATNORM.items()) + list(SIGNATURES_XONLY.items())
-                              + list(SIGNATURES_LVL.items()) + list(SIGNATURES_RGB.items())):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items()):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

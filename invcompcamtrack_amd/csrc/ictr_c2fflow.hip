@@ -21,10 +21,10 @@
 // the rejection is scalar, the MEAN tail stays in the node's row, and a node's y displacement is +0.0 to the bit.
 // Restated by tests/c2fdisp_f32.py.
 //
-// NCH = 3 is the colour form (DESIGN.md "Colour"; include/ictr_c2f_rgb.h): a frame is three pyramids of one geometry, the
-// search is pf_level_search_ch over three channel planes (H and b summed over the channels, one decision and one step per
-// node), the MEAN tail writes three betas per node, and a level's densifier and refiner runs are their colour ones
-// (ictr_flowdensify_run_level_rgb_, ictr_flowrefine_run_level_rgb_). Restated by tests/c2frgb_f32.py.
+// NCH = 3 is the colour form (DESIGN.md "Colour"): a frame is three pyramids of one geometry, the search is
+// pf_level_search_ch over three channel planes (H and b summed over the channels, one decision and one step per node), the
+// MEAN tail writes three betas per node, and a level's densifier and refiner runs take the three pyramids per frame
+// (k_densify<BIAS, 3>, k_fr_warp<3>, k_fr_coef_rgb). Restated by tests/c2frgb_f32.py.
 //
 // k_flow_upsample<XONLY> finishes a run whose finest level is above 0 (DESIGN.md "A finest level above 0"): the field of
 // level lv to the w x h frame, bilinear with half-pixel centres at the fixed factor 2^-lv, the vectors times 2^lv. One lane
@@ -45,8 +45,11 @@
 
 namespace ictr {
 
+// The plain forms' arguments ...
+template <bool MEAN, int NCH>
 struct C2fArgs {
-  const float *a, *ax, *ay, *b;  // this level: frame A image + gradients, frame B image (padded planes)
+  const float *a[NCH], *ax[NCH], *ay[NCH], *b[NCH];  // this level, per channel: frame A image + gradients, frame B image
+                                                     // (padded planes of one geometry)
   int sw, shift;                 // row stride; (pad - P) * (sw + 1), as PFLevel
   float swo, sho;                // the level's unpadded size
   int nx, K, step;               // nodes per row, nodes, node spacing
@@ -57,33 +60,16 @@ struct C2fArgs {
   float *d;                      // [K][2] raw node displacements (the fill's input)
   unsigned char *lost, *status;  // [K], [K]
 };
-// the MEAN forms' arguments (the plain forms keep theirs, and with them their code, to the instruction)
-struct C2fMeanArgs : C2fArgs {
-  float *bias;  // [K] node brightness offsets
+// ... and behind them bias for the MEAN forms alone (the plain forms keep their arguments, and with them their code, to
+// the instruction)
+template <int NCH>
+struct C2fArgs<true, NCH> : C2fArgs<false, NCH> {
+  float *bias;  // [K][NCH] node brightness offsets per channel
 };
-
-// the colour forms' arguments (the grey forms keep theirs): three channel planes per frame, of one geometry
-struct C2fRgbArgs {
-  const float *a[3], *ax[3], *ay[3], *b[3];  // per channel: frame A image + gradients, frame B image
-  int sw, shift;
-  float swo, sho;
-  int nx, K, step;
-  const float2 *coarse;
-  int cw, ch;
-  int P, maxiter;
-  float eps2, min_det, far2;
-  float *d;
-  unsigned char *lost, *status;
-  float *bias;  // [K][3] node brightness offsets per channel (the MEAN forms alone)
-};
-template <bool MEAN, int NCH>
-using C2fArgsOf = std::conditional_t<NCH == 3, C2fRgbArgs, std::conditional_t<MEAN, C2fMeanArgs, C2fArgs>>;
 
 // channel c's planes of a level
-__device__ __forceinline__ PFPlanes c2f_planes(const C2fArgs &a, int) {
-  return PFPlanes{(gconst_f32)a.a, (gconst_f32)a.ax, (gconst_f32)a.ay, (gconst_f32)a.b, a.sw, a.shift, a.swo, a.sho};
-}
-__device__ __forceinline__ PFPlanes c2f_planes(const C2fRgbArgs &a, int c) {
+template <bool MEAN, int NCH>
+__device__ __forceinline__ PFPlanes c2f_planes(const C2fArgs<MEAN, NCH> &a, int c) {
   return PFPlanes{(gconst_f32)a.a[c], (gconst_f32)a.ax[c], (gconst_f32)a.ay[c], (gconst_f32)a.b[c],
                   a.sw,               a.shift,             a.swo,               a.sho};
 }
@@ -92,7 +78,7 @@ __device__ __forceinline__ PFPlanes c2f_planes(const C2fRgbArgs &a, int c) {
 // step per node, and with MEAN three betas per node, bias[k][c]. A reduction's row of sSum is then 8 floats wide: the
 // widest (H with three sums of T) carries six values in one trip. Restated by tests/c2frgb_f32.py.
 template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH = 1>
-__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgsOf<MEAN, NCH> a) {
+__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs<MEAN, NCH> a) {
   static_assert(NCH == 1 || NCH == 3, "one channel or three");
   constexpr int PPB = kWaves / WPP;  // nodes per workgroup
   constexpr int SW = NCH == 1 ? 4 : 8;
@@ -169,8 +155,8 @@ __global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgsOf<MEAN, NCH> a) {
 }
 
 // the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
-template <bool MEAN, bool XONLY, int NCH = 1>
-static void launch_c2f_level(const C2fArgsOf<MEAN, NCH> &a, hipStream_t s) {
+template <bool MEAN, bool XONLY, int NCH>
+static void launch_c2f_level(const C2fArgs<MEAN, NCH> &a, hipStream_t s) {
   const int npl = (a.P * a.P + 63) / 64;
   const dim3 blk(kBlock);
   if (npl > 4) {
@@ -409,6 +395,45 @@ extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   return ICTR_OK;
 }
 
+// level l's search of a run: pfc[ch] the level tables of the channels' pyramids, which agree in geometry
+template <bool MEAN, bool XONLY, int NCH>
+static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, hipStream_t s) {
+  const C2fLevel &L = c->lv[l];
+  const PFArgs &pf = pfc[0];
+  C2fArgs<MEAN, NCH> a;
+  memset(&a, 0, sizeof(a));
+  for (int ch = 0; ch < NCH; ++ch)
+    a.a[ch] = pfc[ch].lv[l].a, a.ax[ch] = pfc[ch].lv[l].ax, a.ay[ch] = pfc[ch].lv[l].ay, a.b[ch] = pfc[ch].lv[l].b;
+  a.sw = pf.lv[l].sw;
+  a.shift = pf.lv[l].shift;
+  a.swo = pf.lv[l].swo;
+  a.sho = pf.lv[l].sho;
+  a.nx = L.nx;
+  a.K = L.nx * L.ny;
+  a.step = c->step;
+  if (l < c->lv_f) {
+    a.coarse = reinterpret_cast<const float2 *>(c2f_field(c->lv[l + 1], refined));
+    a.cw = c->lv[l + 1].w;
+    a.ch = c->lv[l + 1].h;
+  }
+  a.P = c->psz;
+  a.maxiter = c->maxiter;
+  a.eps2 = pf.eps2;
+  a.min_det = XONLY ? pf.min_hx : pf.min_det;
+  a.far2 = (float)(c->psz * c->psz);
+  if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
+  a.status = L.status;
+  if constexpr (MEAN) a.bias = L.bias;
+  if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
+  launch_c2f_level<MEAN, XONLY, NCH>(a, s);
+  return ICTR_OK;
+}
+// the search's form by [patnorm][x_only][channels == 3]
+using C2fSearch = int (*)(const ictr_c2fflow *, const PFArgs *, int, int, hipStream_t);
+static const C2fSearch kC2fSearch[2][2][2] = {
+    {{c2f_search<false, false, 1>, c2f_search<false, false, 3>}, {c2f_search<false, true, 1>, c2f_search<false, true, 3>}},
+    {{c2f_search<true, false, 1>, c2f_search<true, false, 3>}, {c2f_search<true, true, 1>, c2f_search<true, true, 3>}}};
+
 // a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
 static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
                    void *hip_stream) {
@@ -436,88 +461,17 @@ static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr
   c->timed = c->timing;
   for (int l = c->lv_f; l >= c->lv_l; --l) {
     C2fLevel &L = c->lv[l];
-    C2fArgs a;
-    memset(&a, 0, sizeof(a));
-    a.a = pf.lv[l].a, a.ax = pf.lv[l].ax, a.ay = pf.lv[l].ay, a.b = pf.lv[l].b;
-    a.sw = pf.lv[l].sw;
-    a.shift = pf.lv[l].shift;
-    a.swo = pf.lv[l].swo;
-    a.sho = pf.lv[l].sho;
-    a.nx = L.nx;
-    a.K = L.nx * L.ny;
-    a.step = c->step;
-    if (l < c->lv_f) {
-      a.coarse = reinterpret_cast<const float2 *>(c2f_field(c->lv[l + 1], refined));
-      a.cw = c->lv[l + 1].w;
-      a.ch = c->lv[l + 1].h;
-    }
-    a.P = c->psz;
-    a.maxiter = c->maxiter;
-    a.eps2 = pf.eps2;
-    a.min_det = x_only ? pf.min_hx : pf.min_det;
-    a.far2 = (float)(c->psz * c->psz);
-    if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
-    a.status = L.status;
-    if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
-    if (nch == 3) {
-      C2fRgbArgs r;
-      memset(&r, 0, sizeof(r));
-      for (int ch = 0; ch < 3; ++ch)
-        r.a[ch] = pfc[ch].lv[l].a, r.ax[ch] = pfc[ch].lv[l].ax, r.ay[ch] = pfc[ch].lv[l].ay, r.b[ch] = pfc[ch].lv[l].b;
-      r.sw = a.sw, r.shift = a.shift, r.swo = a.swo, r.sho = a.sho;
-      r.nx = a.nx, r.K = a.K, r.step = a.step;
-      r.coarse = a.coarse, r.cw = a.cw, r.ch = a.ch;
-      r.P = a.P, r.maxiter = a.maxiter;
-      r.eps2 = a.eps2, r.min_det = a.min_det, r.far2 = a.far2;
-      r.d = a.d, r.lost = a.lost, r.status = a.status;
-      r.bias = L.bias;
-      if (patnorm && x_only)
-        launch_c2f_level<true, true, 3>(r, s);
-      else if (patnorm)
-        launch_c2f_level<true, false, 3>(r, s);
-      else if (x_only)
-        launch_c2f_level<false, true, 3>(r, s);
-      else
-        launch_c2f_level<false, false, 3>(r, s);
-    } else if (patnorm) {
-      C2fMeanArgs m;
-      static_cast<C2fArgs &>(m) = a;
-      m.bias = L.bias;
-      if (x_only)
-        launch_c2f_level<true, true>(m, s);
-      else
-        launch_c2f_level<true, false>(m, s);
-    } else if (x_only) {
-      launch_c2f_level<false, true>(a, s);
-    } else {
-      launch_c2f_level<false, false>(a, s);
-    }
+    if (int rc = kC2fSearch[patnorm][x_only][nch == 3](c, pfc, l, refined, s)) return rc;
     if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
-    if (nch == 3) {
-      if (int rc = ictr_flowdensify_run_level_rgb_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, c->psz, l,
-                                                   patnorm ? L.bias : nullptr, s))
-        return rc;
-    } else if (int rc = ictr_flowdensify_run_level_bias_(L.dens.get(), L.grid.get(), pyr_a[0], pyr_b[0], c->psz, l,
-                                                         patnorm ? L.bias : nullptr, s)) {
+    if (int rc = ictr_flowdensify_run_level_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, nch, c->psz, l,
+                                             patnorm ? L.bias : nullptr, s))
       return rc;
-    }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[2].get(), s));
-    if (refined) {
-      ictr_field f;
-      memset(&f, 0, sizeof(f));
-      f.kind = ICTR_FIELD_FLOW;
-      f.sign = 1;
-      f.on_device = 1;
-      f.data = ictr_flowdensify_device_ptr(L.dens.get());
-      if (nch == 3) {
-        if (int rc = ictr_flowrefine_run_level_rgb_(L.ref.get(), pyr_a, pyr_b, static_cast<const float *>(f.data), x_only, l,
-                                                    c->bw12.get(), s))
-          return rc;
-      } else if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a[0], pyr_b[0], &f, x_only, l, s)) {
+    if (refined)
+      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, nch, ictr_flowdensify_device_ptr(L.dens.get()),
+                                              x_only, l, c->bw12.get(), s))
         return rc;
-      }
-    }
     if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
   }
   if (c->lv_l > 0) {  // the finest level's field to the frame's size
@@ -601,29 +555,24 @@ extern "C" int ictr_c2fflow_read_level(ictr_c2fflow *c, int level, float *field,
   if (status) HIPCHK(hipMemcpy(status, L.status, K, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
-extern "C" int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *bias) {
-  if (int rc = c2f_wait(c, "c2fflow_read_level_bias")) return rc;
+// the two bias readers: `who` names the caller; wrong_channels: its refusal of an object of the other channel count
+static int c2f_read_bias(ictr_c2fflow *c, int level, float *bias, const char *who, int channels, const char *wrong_channels) {
+  if (int rc = c2f_wait(c, who)) return rc;
   if (level < c->lv_l || level > c->lv_f)
-    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
-  if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: bias is NULL");
-  if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias: the last run had patnorm off");
-  if (c->channels != 1)
-    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias: the object has %d channels; use ictr_c2fflow_read_level_bias_rgb",
-                c->channels);
+    return fail(ICTR_ERR_INVALID, "%s: level is %d (%d .. %d)", who, level, c->lv_l, c->lv_f);
+  if (!bias) return fail(ICTR_ERR_INVALID, "%s: bias is NULL", who);
+  if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "%s: the last run had patnorm off", who);
+  if (c->channels != channels) return fail(ICTR_ERR_INVALID, wrong_channels, who, c->channels);
   const C2fLevel &L = c->lv[level];
-  HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * (size_t)L.nx * L.ny, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * (size_t)channels * L.nx * L.ny, hipMemcpyDeviceToHost));
   return ICTR_OK;
 }
+extern "C" int ictr_c2fflow_read_level_bias(ictr_c2fflow *c, int level, float *bias) {
+  return c2f_read_bias(c, level, bias, "c2fflow_read_level_bias", 1,
+                       "%s: the object has %d channels; use ictr_c2fflow_read_level_bias_rgb");
+}
 extern "C" int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, float *bias) {
-  if (int rc = c2f_wait(c, "c2fflow_read_level_bias_rgb")) return rc;
-  if (level < c->lv_l || level > c->lv_f)
-    return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: level is %d (%d .. %d)", level, c->lv_l, c->lv_f);
-  if (!bias) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: bias is NULL");
-  if (!c->ran_patnorm) return fail(ICTR_ERR_STATE, "c2fflow_read_level_bias_rgb: the last run had patnorm off");
-  if (c->channels != 3) return fail(ICTR_ERR_INVALID, "c2fflow_read_level_bias_rgb: the object has 1 channel");
-  const C2fLevel &L = c->lv[level];
-  HIPCHK(hipMemcpy(bias, L.bias, sizeof(float) * 3 * (size_t)L.nx * L.ny, hipMemcpyDeviceToHost));
-  return ICTR_OK;
+  return c2f_read_bias(c, level, bias, "c2fflow_read_level_bias_rgb", 3, "%s: the object has %d channel");
 }
 extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {
   if (int rc = c2f_wait(c, "c2fflow_get_kernel_ms")) return rc;

@@ -15,10 +15,12 @@
 // a constant table and a single vote come back to the bit (d - d0 = 0, and d0 + 0 = d0; a d0 of -0.0 comes back +0.0).
 // B's taps come from global memory: neighbouring lanes share the node for most votes, so a vote's four tap loads of a
 // wave are four contiguous row segments. Plain vector loads and stores, no atomics; enqueued on the caller's stream.
-// k_densify<true> is the form of the coarse-to-fine flow's patch-mean normalisation: the record carries the node's
-// brightness offset beta next to (dx, dy) and the residual is (Bw - A) - beta (tests/patnorm_f32.py restates it).
-// k_densify_rgb<BIAS> is the form of the coarse-to-fine flow's colour frames: three planes per frame, a vote weighs the
-// channel mean of the three absolute residuals (tests/c2frgb_f32.py restates it).
+// k_densify<BIAS, NCH>: BIAS is the form of the coarse-to-fine flow's patch-mean normalisation, where the record carries
+// the node's brightness offset beta next to (dx, dy) and the residual is (Bw - A) - beta (tests/patnorm_f32.py restates
+// it). NCH = 3 is the form of the coarse-to-fine flow's colour frames (DESIGN.md "Colour"): three planes per frame and,
+// with BIAS, three betas per node; a vote warps the three channels of B at ONE position, with one inside decision, and
+// weighs the channel mean e = ((|r0| + |r1|) + |r2|) / 3 of r_c = (Bw_c - A_c)(- beta_c), so that minerr keeps its meaning
+// in grey levels (tests/c2frgb_f32.py restates it).
 #include <math.h>
 #include <string.h>
 
@@ -35,8 +37,9 @@ namespace ictr {
 constexpr int kDzMaxPsz = 32;          // the tracker's forms allow 1 .. 32
 constexpr size_t kDzMaxLds = 65536;    // bytes of LDS a workgroup may ask for
 
-struct DzArgs {
-  const float *A, *B;  // level-0 planes at pixel (0, 0), strides sa, sb
+template <int NCH>
+struct DzArgsT {
+  const float *A[NCH], *B[NCH];  // per channel, level planes at pixel (0, 0), strides sa, sb
   int sa, sb, w, h;
   FgDev g;
   const unsigned char *lost;  // [ny][nx]
@@ -45,7 +48,7 @@ struct DzArgs {
   int power;
   float2 *out;       // [h][w]
   float *cnt, *sw;   // [h][w]: votes taken, and their summed weight
-  const float *bias; // [ny][nx] node brightness offsets (k_densify<true> only)
+  const float *bias; // [ny][nx][NCH] node brightness offsets (k_densify<true, NCH> only)
 };
 
 // the nodes i >= 0 with a <= i step, and those i <= n - 1 with i step <= b (-1: none)
@@ -55,18 +58,21 @@ __host__ __device__ __forceinline__ int dz_last(int b, int step, int n) { return
 // of span - 1 + psz - 1 pixels
 static int dz_capacity(int span, int psz, int step) { return (span + psz - 2) / step + 1; }
 
-// the LDS record of a node: (dx, dy), and with BIAS the node's brightness offset beta next to them
+// the LDS record of a node: (dx, dy), and with BIAS the node's brightness offsets beta next to them
+template <int NCH>
 struct DzRecBias {
-  float x, y, beta;
+  float x, y, beta[NCH];
 };
-template <bool BIAS>
-using DzRec = std::conditional_t<BIAS, DzRecBias, float2>;
+template <bool BIAS, int NCH>
+using DzRec = std::conditional_t<BIAS, DzRecBias<NCH>, float2>;
 
 // BIAS: the vote weighs |Bw - A - beta| with the node's beta (the coarse-to-fine flow under patch-mean normalisation).
-template <bool BIAS>
-__global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
+// NCH: the planes per frame. The rule's only fork is how e is formed: one channel takes |r|, with no division.
+template <bool BIAS, int NCH>
+__global__ __launch_bounds__(kBlock) void k_densify(DzArgsT<NCH> a) {
+  static_assert(NCH == 1 || NCH == 3, "one channel or three");
   extern __shared__ float2 s_node_raw[];  // [ncy][ncx] records of the nodes i0 .. i1 x j0 .. j1
-  DzRec<BIAS> *s_node = reinterpret_cast<DzRec<BIAS> *>(s_node_raw);
+  DzRec<BIAS, NCH> *s_node = reinterpret_cast<DzRec<BIAS, NCH> *>(s_node_raw);
   const int step = a.g.step, half = step / 2;
   const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * kWaves;
   const int i0 = dz_first(bx0 - a.hi - half, step), i1 = dz_last(bx0 + 63 + a.lo - half, step, a.g.nx);
@@ -78,10 +84,14 @@ __global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
     const int k = (j0 + jj) * a.g.nx + (i0 + ii);
     float2 d = reinterpret_cast<const float2 *>(a.g.d)[k];
     if (a.lost[k]) d.x = nanv;
-    if constexpr (BIAS)
-      s_node[q] = DzRecBias{d.x, d.y, a.bias[k]};
-    else
+    if constexpr (BIAS) {
+      DzRecBias<NCH> rec{d.x, d.y, {}};
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) rec.beta[c] = a.bias[NCH * k + c];
+      s_node[q] = rec;
+    } else {
       s_node[q] = d;
+    }
   }
   __syncthreads();
   const int X = bx0 + (threadIdx.x & 63), Y = by0 + (threadIdx.x >> 6);
@@ -89,108 +99,29 @@ __global__ __launch_bounds__(kBlock) void k_densify(DzArgs a) {
   // this pixel's nodes: a part of the workgroup's, since bx0 <= X <= bx0 + 63 and by0 <= Y <= by0 + kWaves - 1
   const int li0 = dz_first(X - a.hi - half, step), li1 = dz_last(X + a.lo - half, step, a.g.nx);
   const int lj0 = dz_first(Y - a.hi - half, step), lj1 = dz_last(Y + a.lo - half, step, a.g.ny);
-  const float av = a.A[(size_t)Y * a.sa + X];
+  float av[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) av[c] = a.A[c][(size_t)Y * a.sa + X];
   float su = 0.0f, sv = 0.0f, sw = 0.0f;
   float2 d0 = make_float2(0.0f, 0.0f);  // the first vote's displacement
   int n = 0;
   for (int j = lj0; j <= lj1; ++j) {
-    const DzRec<BIAS> *row = s_node + (j - j0) * ncx - i0;
+    const DzRec<BIAS, NCH> *row = s_node + (j - j0) * ncx - i0;
     for (int i = li0; i <= li1; ++i) {
-      const DzRec<BIAS> d = row[i];
+      const DzRec<BIAS, NCH> d = row[i];
       const float px = (float)X + d.x, py = (float)Y + d.y;
       if (!fr_inside(px, py, a.w, a.h)) continue;  // a lost node (NaN) too
-      float r = fr_bilinear(a.B, a.sb, a.w, a.h, px, py) - av;
-      if constexpr (BIAS) r = r - d.beta;
-      const float m = fmaxf(fabsf(r), a.minerr);
-      const float m2 = m * m;
-      const float mp = a.power == 1 ? m : a.power == 2 ? m2 : a.power == 3 ? m2 * m : m2 * m2;
-      const float wgt = 1.0f / mp;
-      if (n == 0) d0 = make_float2(d.x, d.y);
-      su = su + wgt * (d.x - d0.x);
-      sv = sv + wgt * (d.y - d0.y);
-      sw = sw + wgt;
-      ++n;
-    }
-  }
-  float u, v;
-  if (n > 0) {
-    u = d0.x + su / sw;
-    v = d0.y + sv / sw;
-  } else {
-    fg_value(a.g, X, Y, &u, &v);
-  }
-  const size_t o = (size_t)Y * a.w + X;
-  a.out[o] = make_float2(u, v);
-  a.cnt[o] = (float)n;
-  a.sw[o] = sw;
-}
-
-// The colour form (DESIGN.md "Colour"; reached through ictr_flowdensify_run_level_rgb_ alone): three planes per frame
-// and, with BIAS, three betas per node. A vote warps the three channels of B at ONE position, with one inside decision,
-// and weighs the channel mean e = ((|r0| + |r1|) + |r2|) / 3 of r_c = (Bw_c - A_c)(- beta_c), so that minerr keeps its
-// meaning in grey levels. Everything else is k_densify's. Restated by tests/c2frgb_f32.py.
-struct DzRgbArgs {
-  const float *A[3], *B[3];  // per channel, level planes at pixel (0, 0), strides sa, sb
-  int sa, sb, w, h;
-  FgDev g;
-  const unsigned char *lost;
-  int lo, hi;
-  float minerr;
-  int power;
-  float2 *out;
-  float *cnt, *sw;
-  const float *bias;  // [ny][nx][3] (k_densify_rgb<true> only)
-};
-struct DzRecBiasRgb {
-  float x, y, beta[3];
-};
-template <bool BIAS>
-using DzRecRgb = std::conditional_t<BIAS, DzRecBiasRgb, float2>;
-
-template <bool BIAS>
-__global__ __launch_bounds__(kBlock) void k_densify_rgb(DzRgbArgs a) {
-  extern __shared__ float2 s_node_raw[];
-  DzRecRgb<BIAS> *s_node = reinterpret_cast<DzRecRgb<BIAS> *>(s_node_raw);
-  const int step = a.g.step, half = step / 2;
-  const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * kWaves;
-  const int i0 = dz_first(bx0 - a.hi - half, step), i1 = dz_last(bx0 + 63 + a.lo - half, step, a.g.nx);
-  const int j0 = dz_first(by0 - a.hi - half, step), j1 = dz_last(by0 + kWaves - 1 + a.lo - half, step, a.g.ny);
-  const int ncx = max(i1 - i0 + 1, 0), ncy = max(j1 - j0 + 1, 0);
-  const float nanv = __int_as_float(0x7fc00000);
-  for (int q = threadIdx.x; q < ncx * ncy; q += kBlock) {
-    const int jj = q / ncx, ii = q - jj * ncx;
-    const int k = (j0 + jj) * a.g.nx + (i0 + ii);
-    float2 d = reinterpret_cast<const float2 *>(a.g.d)[k];
-    if (a.lost[k]) d.x = nanv;
-    if constexpr (BIAS)
-      s_node[q] = DzRecBiasRgb{d.x, d.y, {a.bias[3 * k], a.bias[3 * k + 1], a.bias[3 * k + 2]}};
-    else
-      s_node[q] = d;
-  }
-  __syncthreads();
-  const int X = bx0 + (threadIdx.x & 63), Y = by0 + (threadIdx.x >> 6);
-  if (X >= a.w || Y >= a.h) return;
-  const int li0 = dz_first(X - a.hi - half, step), li1 = dz_last(X + a.lo - half, step, a.g.nx);
-  const int lj0 = dz_first(Y - a.hi - half, step), lj1 = dz_last(Y + a.lo - half, step, a.g.ny);
-  float av[3];
+      float r[NCH];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) av[c] = a.A[c][(size_t)Y * a.sa + X];
-  float su = 0.0f, sv = 0.0f, sw = 0.0f;
-  float2 d0 = make_float2(0.0f, 0.0f);
-  int n = 0;
-  for (int j = lj0; j <= lj1; ++j) {
-    const DzRecRgb<BIAS> *row = s_node + (j - j0) * ncx - i0;
-    for (int i = li0; i <= li1; ++i) {
-      const DzRecRgb<BIAS> d = row[i];
-      const float px = (float)X + d.x, py = (float)Y + d.y;
-      if (!fr_inside(px, py, a.w, a.h)) continue;  // a lost node (NaN) too
-      float r[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
+      for (int c = 0; c < NCH; ++c) {
         r[c] = fr_bilinear(a.B[c], a.sb, a.w, a.h, px, py) - av[c];
         if constexpr (BIAS) r[c] = r[c] - d.beta[c];
       }
-      const float e = ((fabsf(r[0]) + fabsf(r[1])) + fabsf(r[2])) / 3.0f;
+      float e;
+      if constexpr (NCH == 1)
+        e = fabsf(r[0]);
+      else
+        e = ((fabsf(r[0]) + fabsf(r[1])) + fabsf(r[2])) / 3.0f;
       const float m = fmaxf(e, a.minerr);
       const float m2 = m * m;
       const float mp = a.power == 1 ? m : a.power == 2 ? m2 : a.power == 3 ? m2 * m : m2 * m2;
@@ -263,74 +194,19 @@ extern "C" int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on) {
   return ICTR_OK;
 }
 
-extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                    const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
-  return ictr_flowdensify_run_level_(z, grid, pyr_a, pyr_b, psz, 0, hip_stream);
-}
-// the run on level `level` of the pyramids (grid and object of that level's size)
-extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                           const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream) {
-  return ictr_flowdensify_run_level_bias_(z, grid, pyr_a, pyr_b, psz, level, nullptr, hip_stream);
-}
-// the same with the grid's node bias [ny][nx] on the device (NULL: none, k_densify<false>)
-extern "C" int ictr_flowdensify_run_level_bias_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                                const ictr_pyramid *pyr_b, int psz, int level, const float *bias,
-                                                void *hip_stream) {
+// One run on level `level` of NCH pyramids per frame (grid and object of that level's size); bias: the grid's node bias
+// [ny][nx][NCH] on the device (NULL: none, k_densify<false, NCH>)
+template <int NCH>
+static int dz_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
+                  const ictr_pyramid *const *pyr_b, int psz, int level, const float *bias, hipStream_t s) {
   if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
   if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
-  DzArgs a;
+  DzArgsT<NCH> a;
   memset(&a, 0, sizeof(a));
   if (int rc = ictr_flowgrid_view_lost_(grid, &a.g, &a.lost)) return rc;
   if (a.g.w != z->w || a.g.h != z->h)
     return fail(ICTR_ERR_INVALID, "flowdensify_run: the flow grid is %d x %d, the object %d x %d", a.g.w, a.g.h, z->w, z->h);
-  ictr_level0 l[2];
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowdensify_run", &l[k], level)) return rc;
-    if (l[k].w != z->w || l[k].h != z->h)
-      return fail(ICTR_ERR_INVALID, "flowdensify_run: a pyramid is %d x %d, the object %d x %d", l[k].w, l[k].h, z->w, z->h);
-  }
-  a.A = l[0].img, a.sa = l[0].stride;
-  a.B = l[1].img, a.sb = l[1].stride;
-  a.w = z->w;
-  a.h = z->h;
-  a.lo = psz - psz / 2;
-  a.hi = psz / 2 - 1;
-  a.minerr = z->minerr;
-  a.power = z->power;
-  a.out = reinterpret_cast<float2 *>(z->res.get());
-  a.cnt = z->cnt;
-  a.sw = z->sw;
-  a.bias = bias;
-  const size_t lds = (bias ? sizeof(DzRecBias) : sizeof(float2)) * (size_t)dz_capacity(64, psz, a.g.step) *
-                     dz_capacity(kWaves, psz, a.g.step);
-  if (lds > kDzMaxLds)
-    return fail(ICTR_ERR_INVALID, "flowdensify_run: step %d with psz %d needs a node table of %zu bytes of LDS (limit %zu)",
-                a.g.step, psz, lds, kDzMaxLds);
-  hipStream_t s = (hipStream_t)hip_stream;
-  z->timed = z->timing;
-  if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
-  if (bias)
-    hipLaunchKernelGGL(k_densify<true>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
-  else
-    hipLaunchKernelGGL(k_densify<false>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
-  if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
-  HIPCHK(hipGetLastError());
-  return z->res.record(s);
-}
-
-// the colour run of the coarse-to-fine flow: three pyramids per frame (the caller has checked that they agree in geometry)
-// and the node bias [ny][nx][3] on the device (NULL: none)
-extern "C" int ictr_flowdensify_run_level_rgb_(ictr_flowdensify *z, const ictr_flowgrid *grid,
-                                               const ictr_pyramid *const pyr_a[3], const ictr_pyramid *const pyr_b[3], int psz,
-                                               int level, const float *bias, void *hip_stream) {
-  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
-  if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
-  DzRgbArgs a;
-  memset(&a, 0, sizeof(a));
-  if (int rc = ictr_flowgrid_view_lost_(grid, &a.g, &a.lost)) return rc;
-  if (a.g.w != z->w || a.g.h != z->h)
-    return fail(ICTR_ERR_INVALID, "flowdensify_run: the flow grid is %d x %d, the object %d x %d", a.g.w, a.g.h, z->w, z->h);
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < NCH; ++c) {
     ictr_level0 l[2];
     for (int k = 0; k < 2; ++k) {
       if (int rc = ictr_pyramid_level0(k ? pyr_b[c] : pyr_a[c], "flowdensify_run", &l[k], level)) return rc;
@@ -352,21 +228,32 @@ extern "C" int ictr_flowdensify_run_level_rgb_(ictr_flowdensify *z, const ictr_f
   a.cnt = z->cnt;
   a.sw = z->sw;
   a.bias = bias;
-  const size_t lds = (bias ? sizeof(DzRecBiasRgb) : sizeof(float2)) * (size_t)dz_capacity(64, psz, a.g.step) *
-                     dz_capacity(kWaves, psz, a.g.step);
+  const size_t lds = (bias ? sizeof(DzRec<true, NCH>) : sizeof(DzRec<false, NCH>)) *
+                     (size_t)dz_capacity(64, psz, a.g.step) * dz_capacity(kWaves, psz, a.g.step);
   if (lds > kDzMaxLds)
     return fail(ICTR_ERR_INVALID, "flowdensify_run: step %d with psz %d needs a node table of %zu bytes of LDS (limit %zu)",
                 a.g.step, psz, lds, kDzMaxLds);
-  hipStream_t s = (hipStream_t)hip_stream;
   z->timed = z->timing;
   if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
   if (bias)
-    hipLaunchKernelGGL(k_densify_rgb<true>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL((k_densify<true, NCH>), pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
   else
-    hipLaunchKernelGGL(k_densify_rgb<false>, pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL((k_densify<false, NCH>), pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
   if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
   HIPCHK(hipGetLastError());
   return z->res.record(s);
+}
+
+extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                    const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
+  return dz_run<1>(z, grid, &pyr_a, &pyr_b, psz, 0, nullptr, (hipStream_t)hip_stream);
+}
+// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per frame
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
+                                           const ictr_pyramid *const *pyr_b, int channels, int psz, int level,
+                                           const float *bias, void *hip_stream) {
+  return channels == 3 ? dz_run<3>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream)
+                       : dz_run<1>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream);
 }
 
 extern "C" int ictr_flowdensify_result(ictr_flowdensify *z, float *out, int on_device) {

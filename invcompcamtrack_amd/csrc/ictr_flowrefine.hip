@@ -2,7 +2,7 @@
 // a dense field"). The rule is build-defined; its statement of record is patchflow.refine_flow_host (NumPy, f64). This
 // file is the same rule in f32 with one fixed operation order, restated in NumPy f32 by tests/flowrefine_f32.py.
 //
-// One outer iteration is   k_fr_warp -> k_fr_coef -> n_sor x (k_fr_sor<0>, k_fr_sor<1>)   on planes of the frame's size:
+// One outer iteration is   k_fr_warp<1> -> k_fr_coef -> n_sor x (k_fr_sor<0>, k_fr_sor<1>)   on planes of the frame's size:
 //   k_fr_warp   (u, v) += (du, dv) of the previous outer iteration (step 6 folded in), then Bw = bilinear(B, x + u, y + v).
 //               The position is clamped with fmaxf / fminf BEFORE any index is formed: no index depends on a non-finite
 //               value, every tap lies in the frame.
@@ -12,7 +12,7 @@
 //   k_fr_sor<c> one half-sweep: a lane per pixel of colour (x + y) & 1 == c. All four neighbours have the other colour,
 //               which this launch does not write: no order inside a half-sweep, the result is deterministic. The five
 //               coefficient planes are stored compacted by colour (fr_ci).
-// k_fr_warp_rgb and k_fr_coef_rgb are the two stages on colour frames (three planes per frame; the coarse-to-fine flow's
+// k_fr_warp<3> and k_fr_coef_rgb are the two stages on colour frames (three planes per frame; the coarse-to-fine flow's
 // colour runs alone): per-channel derivatives, robust weights joint over the channels, coefficients as channel means.
 // k_fr_final adds the last (du, dv) into the interleaved result. Memory bound throughout: plain vector loads and stores,
 // no atomics. Everything is enqueued on the caller's stream; run waits for nothing but the copy of a field that lives in
@@ -37,13 +37,20 @@ constexpr float kFrEps2 = 1e-3f * 1e-3f;
 constexpr float kFrZeta2 = 0.1f * 0.1f;
 static_assert(kFrTile * kFrTile == kBlock, "k_fr_coef maps one lane to one pixel of its tile");
 
-struct FrArgs {
-  const float *A, *B;  // level-0 planes at pixel (0, 0), strides sa, sb
+// NCH planes per frame: 1 for grey frames, 3 for colour
+template <int NCH>
+struct FrArgsT {
+  const float *A[NCH], *B[NCH];  // per channel, level planes at pixel (0, 0), strides sa, sb
   int sa, sb, w, h;
-  float *u, *v, *du, *dv, *bw, *a11, *a12, *a22, *b1, *b2, *wr, *wd;  // planes [h][w]
+  float *u, *v, *du, *dv;        // planes [h][w], and so are those below
+  float *bw[NCH];                // per channel
+  float *a11, *a12, *a22, *b1, *b2, *wr, *wd;
   float alpha, gamma, delta, omega;
   int x_only;
 };
+// The half-sweeps and k_fr_final read neither the frames nor Bw: they take the one-channel arguments whatever the frames
+// are (fr_args<1>).
+using FrArgs = FrArgsT<1>;
 
 // interleaved (u, v) -> the two working planes
 __global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v,
@@ -66,7 +73,9 @@ __host__ __device__ __forceinline__ int fr_ci(int X, int Y, int w, int h) {
 
 // fr_inside, fr_bilinear: ictr_warp_dev.h
 
-__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgs a, int fold) {
+// (the channels of B are warped at ONE position)
+template <int NCH>
+__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgsT<NCH> a, int fold) {
   const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
   if (X >= a.w || Y >= a.h) return;
   const int i = Y * a.w + X;
@@ -79,7 +88,14 @@ __global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgs a, int fold) {
       a.v[i] = v;
     }
   }
-  a.bw[i] = fr_bilinear(a.B, a.sb, a.w, a.h, (float)X + u, (float)Y + v);
+  // (no loop statement in the grey form, not even one of one trip: with one the compiler moves the argument loads of the
+  // fold into its branch, three scalar loads and a branch more: DESIGN.md "Colour")
+  if constexpr (NCH == 1) {
+    a.bw[0][i] = fr_bilinear(a.B[0], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) a.bw[c][i] = fr_bilinear(a.B[c], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
+  }
 }
 
 // a tile with its halo; (cx, cy) are tile coordinates, the frame coordinate is (gx0 + cx, gy0 + cy)
@@ -119,7 +135,10 @@ __device__ __forceinline__ float fr_smooth(const FrTile &tu, const FrTile &tv, i
   return half_alpha / sqrtf(t);
 }
 
-__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgs a) {
+// k_fr_coef and k_fr_coef_rgb (below) are two kernels and not one template over the channel count: this one forms
+// w0 = ((delta n0) / 2) / sqrt(n0 Iz^2 + eps^2) per pixel, the colour one q0 on the channel mean, then q0 n0[c], and divides
+// the coefficients by 3. These are different roundings, so a template would be these two bodies under `if constexpr`.
+__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) {
   __shared__ float sB[kFrSide][kFrSide], sA[kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
   const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
   // the halo is read at the nearest pixel of the frame; what lies outside is never used (the border rules above)
@@ -127,10 +146,10 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgs a) {
     const int cy = q / kFrSide, cx = q - cy * kFrSide;
     const int X = min(max(gx0 + cx, 0), a.w - 1), Y = min(max(gy0 + cy, 0), a.h - 1);
     const int i = Y * a.w + X;
-    sB[cy][cx] = a.bw[i];
+    sB[cy][cx] = a.bw[0][i];
     sU[cy][cx] = a.u[i];
     sV[cy][cx] = a.v[i];
-    sA[cy][cx] = a.A[(size_t)Y * a.sa + X];
+    sA[cy][cx] = a.A[0][(size_t)Y * a.sa + X];
   }
   __syncthreads();
   const int cx = (threadIdx.x & (kFrTile - 1)) + kFrHalo, cy = threadIdx.x / kFrTile + kFrHalo;
@@ -166,41 +185,14 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgs a) {
   a.dv[i] = 0.0f;
 }
 
-// The colour forms of the warp and the coefficient stage (DESIGN.md §4 "Colour"; reached through
-// ictr_flowrefine_run_level_rgb_ alone): three planes per frame and three Bw planes. Steps 1 and 2 run per channel, n0,
-// n1, n2 are per channel; the two robust weights are joint over the channels, taken on the channel mean, and the
-// coefficients are channel means. Every sum over the channels starts from 0.0f and adds channel 0, 1, 2 in order; the
-// mean is the quotient by 3.0f. k_fr_sor, k_fr_init and k_fr_final are the grey ones. Restated by tests/c2frgb_f32.py.
-struct FrRgbArgs {
-  const float *A[3], *B[3];  // per channel, level planes at pixel (0, 0), strides sa, sb
-  float *bw[3];              // per channel [h][w]
-  int sa, sb, w, h;
-  float *u, *v, *du, *dv, *a11, *a12, *a22, *b1, *b2, *wr, *wd;
-  float alpha, gamma, delta;
-  int x_only;
-};
-
-__global__ __launch_bounds__(kBlock) void k_fr_warp_rgb(FrRgbArgs a, int fold) {
-  const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (X >= a.w || Y >= a.h) return;
-  const int i = Y * a.w + X;
-  float u = a.u[i], v = a.v[i];
-  if (fold) {
-    u += a.du[i];
-    a.u[i] = u;
-    if (!a.x_only) {
-      v += a.dv[i];
-      a.v[i] = v;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) a.bw[c][i] = fr_bilinear(a.B[c], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
-}
-
+// The colour form of the coefficient stage (DESIGN.md §4 "Colour"): three planes per frame and three Bw planes. Steps 1
+// and 2 run per channel, n0, n1, n2 are per channel; the two robust weights are joint over the channels, taken on the
+// channel mean, and the coefficients are channel means. Every sum over the channels starts from 0.0f and adds channel 0,
+// 1, 2 in order; the mean is the quotient by 3.0f. Restated by tests/c2frgb_f32.py.
 // U and V are staged once, and with them the three channels' tiles of Bw and A: 8 tiles x 1600 B = 12.8 KB of LDS. A
 // lane keeps the eleven per-channel values of all three channels (the joint weights need every channel's Iz, Ixz, Iyz
 // before any coefficient is final); the register report shows no scratch.
-__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrRgbArgs a) {
+__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrArgsT<3> a) {
   __shared__ float sB[3][kFrSide][kFrSide], sA[3][kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
   const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
   for (int q = threadIdx.x; q < kFrSide * kFrSide; q += kBlock) {
@@ -327,8 +319,10 @@ static const int kFrStage[ICTR_FLOWREFINE_STAGES] = {FR_BW, FR_A11, FR_A12, FR_A
 static bool fr_compacted(int plane) { return plane >= FR_A11 && plane <= FR_B2; }  // stored in fr_ci's order
 static size_t fr_plane_floats(const ictr_flowrefine *r) { return (size_t)2 * ((r->w + 1) / 2) * r->h; }
 
-static FrArgs fr_args(const ictr_flowrefine *r, int x_only) {
-  FrArgs a;
+// the working planes and the parameters; Bw of channel 0 is the refiner's own
+template <int NCH>
+static FrArgsT<NCH> fr_args(const ictr_flowrefine *r, int x_only) {
+  FrArgsT<NCH> a;
   memset(&a, 0, sizeof(a));
   a.w = r->w;
   a.h = r->h;
@@ -336,7 +330,7 @@ static FrArgs fr_args(const ictr_flowrefine *r, int x_only) {
   a.v = r->plane[FR_V];
   a.du = r->plane[FR_DU];
   a.dv = r->plane[FR_DV];
-  a.bw = r->plane[FR_BW];
+  a.bw[0] = r->plane[FR_BW];
   a.a11 = r->plane[FR_A11];
   a.a12 = r->plane[FR_A12];
   a.a22 = r->plane[FR_A22];
@@ -396,25 +390,75 @@ extern "C" int ictr_flowrefine_set_timing(ictr_flowrefine *r, int on) {
   return ICTR_OK;
 }
 
+// fr_args and the frames' planes of a run on level `level` of NCH pyramids per frame (the refiner of that level's size);
+// bw12 (NCH = 3): Bw of channels 1 and 2, [2][h][w]
+template <int NCH>
+static int fr_frame_args(const ictr_flowrefine *r, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b,
+                         int x_only, int level, float *bw12, FrArgsT<NCH> *a) {
+  *a = fr_args<NCH>(r, x_only);
+  for (int c = 0; c < NCH; ++c) {
+    ictr_level0 l[2];
+    for (int k = 0; k < 2; ++k) {
+      if (int rc = ictr_pyramid_level0(k ? pyr_b[c] : pyr_a[c], "flowrefine_run", &l[k], level)) return rc;
+      if (l[k].w != r->w || l[k].h != r->h)
+        return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
+    }
+    if (c > 0 && (l[0].stride != a->sa || l[1].stride != a->sb))
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: the channels' planes differ in stride");
+    a->A[c] = l[0].img, a->sa = l[0].stride;
+    a->B[c] = l[1].img, a->sb = l[1].stride;
+    if (c > 0) a->bw[c] = bw12 + (size_t)(c - 1) * r->w * r->h;
+  }
+  return ICTR_OK;
+}
+
+// The launch sequence of a run from the device field f0 [h][w][2]. timed: an event of r->ev at every mark.
+template <int NCH>
+static int fr_run(ictr_flowrefine *r, const FrArgsT<NCH> &a, const float *f0, bool timed, hipStream_t s) {
+  const size_t n = (size_t)r->w * r->h;
+  const FrArgs g = fr_args<1>(r, a.x_only);  // of the half-sweeps and k_fr_final
+  r->nev = 0;
+  auto mark = [&]() {
+    if (timed) (void)hipEventRecord(r->ev[r->nev++].get(), s);
+  };
+  if (r->n_outer == 0) {  // the input's bits
+    HIPCHK(hipMemcpyAsync(r->res.get(), f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
+  } else {
+    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
+    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
+    mark();
+    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(f0), a.u, a.v, (int)n);
+    mark();
+    for (int o = 0; o < r->n_outer; ++o) {
+      mark();
+      hipLaunchKernelGGL(k_fr_warp<NCH>, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
+      mark();
+      if constexpr (NCH == 1)
+        hipLaunchKernelGGL(k_fr_coef, tiles, blk, 0, s, a);
+      else
+        hipLaunchKernelGGL(k_fr_coef_rgb, tiles, blk, 0, s, a);
+      mark();
+      for (int k = 0; k < r->n_sor; ++k) {
+        fr_half_sweep(r, g, 0, s);
+        fr_half_sweep(r, g, 1, s);
+      }
+      mark();
+    }
+    mark();
+    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, g, reinterpret_cast<float2 *>(r->res.get()));
+    mark();
+  }
+  HIPCHK(hipGetLastError());
+  return r->res.record(s);
+}
+
 extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                    const ictr_field *src, int x_only, void *hip_stream) {
-  return ictr_flowrefine_run_level_(r, pyr_a, pyr_b, src, x_only, 0, hip_stream);
-}
-// the run on level `level` of the pyramids (field and refiner of that level's size)
-extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
-                                          const ictr_field *src, int x_only, int level, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
   if (!src || !src->data) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field (or its data) is NULL");
   if (src->sign != 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field's sign is %d (+1)", src->sign);
-  FrArgs a = fr_args(r, x_only);
-  ictr_level0 l[2];
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = ictr_pyramid_level0(k ? pyr_b : pyr_a, "flowrefine_run", &l[k], level)) return rc;
-    if (l[k].w != r->w || l[k].h != r->h)
-      return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
-  }
-  a.A = l[0].img, a.sa = l[0].stride;
-  a.B = l[1].img, a.sb = l[1].stride;
+  FrArgsT<1> a;
+  if (int rc = fr_frame_args<1>(r, &pyr_a, &pyr_b, x_only, 0, nullptr, &a)) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t n = (size_t)r->w * r->h;
   const float *f0 = r->f0;
@@ -443,88 +487,24 @@ extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid
     r->ev.emplace_back();
     if (int rc = r->ev.back().create()) return rc;
   }
-  r->nev = 0;
-  auto mark = [&]() {
-    if (r->timing) (void)hipEventRecord(r->ev[r->nev++].get(), s);
-  };
-  if (r->n_outer == 0) {  // the input's bits
-    HIPCHK(hipMemcpyAsync(r->res.get(), f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
-  } else {
-    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
-    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
-    mark();
-    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(f0), a.u, a.v, (int)n);
-    mark();
-    for (int o = 0; o < r->n_outer; ++o) {
-      mark();
-      hipLaunchKernelGGL(k_fr_warp, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
-      mark();
-      hipLaunchKernelGGL(k_fr_coef, tiles, blk, 0, s, a);
-      mark();
-      for (int k = 0; k < r->n_sor; ++k) {
-        fr_half_sweep(r, a, 0, s);
-        fr_half_sweep(r, a, 1, s);
-      }
-      mark();
-    }
-    mark();
-    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, a, reinterpret_cast<float2 *>(r->res.get()));
-    mark();
-  }
-  HIPCHK(hipGetLastError());
-  return r->res.record(s);
+  return fr_run<1>(r, a, f0, r->timing != 0, s);
 }
 
-// the colour run of the coarse-to-fine flow: three pyramids per frame (the caller has checked that they agree in
-// geometry), the field a device ICTR_FIELD_FLOW, and bw12 two more Bw planes [2][h][w] of the caller's on the device (the
-// refiner's own is channel 0's)
-extern "C" int ictr_flowrefine_run_level_rgb_(ictr_flowrefine *r, const ictr_pyramid *const pyr_a[3],
-                                              const ictr_pyramid *const pyr_b[3], const float *field, int x_only, int level,
-                                              float *bw12, void *hip_stream) {
+// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per frame, the field
+// on the device; untimed (the stage's events are the coarse-to-fine object's)
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *const *pyr_a,
+                                          const ictr_pyramid *const *pyr_b, int channels, const float *field, int x_only,
+                                          int level, float *bw12, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
-  if (!field || !bw12) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field or the Bw planes are NULL");
-  const FrArgs g = fr_args(r, x_only);
-  FrRgbArgs a;
-  memset(&a, 0, sizeof(a));
-  for (int c = 0; c < 3; ++c) {
-    ictr_level0 l[2];
-    for (int k = 0; k < 2; ++k) {
-      if (int rc = ictr_pyramid_level0(k ? pyr_b[c] : pyr_a[c], "flowrefine_run", &l[k], level)) return rc;
-      if (l[k].w != r->w || l[k].h != r->h)
-        return fail(ICTR_ERR_INVALID, "flowrefine_run: a pyramid is %d x %d, the refiner %d x %d", l[k].w, l[k].h, r->w, r->h);
-    }
-    if (c > 0 && (l[0].stride != a.sa || l[1].stride != a.sb))
-      return fail(ICTR_ERR_INVALID, "flowrefine_run: the channels' planes differ in stride");
-    a.A[c] = l[0].img, a.sa = l[0].stride;
-    a.B[c] = l[1].img, a.sb = l[1].stride;
+  if (!field || (channels == 3 && !bw12)) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field or the Bw planes are NULL");
+  if (channels == 3) {
+    FrArgsT<3> a;
+    if (int rc = fr_frame_args<3>(r, pyr_a, pyr_b, x_only, level, bw12, &a)) return rc;
+    return fr_run<3>(r, a, field, false, (hipStream_t)hip_stream);
   }
-  const size_t n = (size_t)r->w * r->h;
-  a.bw[0] = g.bw, a.bw[1] = bw12, a.bw[2] = bw12 + n;
-  a.w = r->w, a.h = r->h;
-  a.u = g.u, a.v = g.v, a.du = g.du, a.dv = g.dv;
-  a.a11 = g.a11, a.a12 = g.a12, a.a22 = g.a22, a.b1 = g.b1, a.b2 = g.b2, a.wr = g.wr, a.wd = g.wd;
-  a.alpha = g.alpha, a.gamma = g.gamma, a.delta = g.delta;
-  a.x_only = g.x_only;
-  hipStream_t s = (hipStream_t)hip_stream;
-  r->nev = 0;  // (the stage's events are the coarse-to-fine object's)
-  if (r->n_outer == 0) {  // the input's bits
-    HIPCHK(hipMemcpyAsync(r->res.get(), field, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
-  } else {
-    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
-    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
-    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(field), a.u, a.v, (int)n);
-    for (int o = 0; o < r->n_outer; ++o) {
-      hipLaunchKernelGGL(k_fr_warp_rgb, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
-      hipLaunchKernelGGL(k_fr_coef_rgb, tiles, blk, 0, s, a);
-      for (int k = 0; k < r->n_sor; ++k) {
-        fr_half_sweep(r, g, 0, s);
-        fr_half_sweep(r, g, 1, s);
-      }
-    }
-    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, g, reinterpret_cast<float2 *>(r->res.get()));
-  }
-  HIPCHK(hipGetLastError());
-  return r->res.record(s);
+  FrArgsT<1> a;
+  if (int rc = fr_frame_args<1>(r, pyr_a, pyr_b, x_only, level, nullptr, &a)) return rc;
+  return fr_run<1>(r, a, field, false, (hipStream_t)hip_stream);
 }
 
 extern "C" int ictr_flowrefine_result(ictr_flowrefine *r, float *out, int on_device) {
@@ -583,7 +563,7 @@ extern "C" int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, 
 }
 extern "C" int ictr_debug_flowrefine_half_sweep(ictr_flowrefine *r, int colour, int x_only) {
   if (!r || (colour != 0 && colour != 1)) return fail(ICTR_ERR_INVALID, "flowrefine_half_sweep: colour is 0 or 1");
-  fr_half_sweep(r, fr_args(r, x_only), colour, nullptr);
+  fr_half_sweep(r, fr_args<1>(r, x_only), colour, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(nullptr));
   return ICTR_OK;

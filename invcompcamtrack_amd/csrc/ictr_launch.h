@@ -38,29 +38,21 @@ inline int ictr_pyramid_level0(const ictr_pyramid *p, const char *who, ictr_leve
 }
 // The stages that the coarse-to-fine flow (ictr_c2fflow.hip) runs per level on objects of the level's size: the node
 // buffers of a flow grid that its search kernel writes (raw displacements [K][2] and the lost bytes [K]) and the grid's fill
-// on a stream; the densifier's and the refiner's run reading level `level` of the pyramids (the public runs pass 0).
+// on a stream; the densifier's and the refiner's run reading level `level` of `channels` (1 or 3) pyramids per frame, which
+// the caller has checked to agree in geometry.
 struct ictr_flowgrid;
 struct ictr_flowdensify;
 struct ictr_flowrefine;
 extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsigned char **lost);  // ictr_frontend.hip
 extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream);  // ictr_frontend.hip
-extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                           const ictr_pyramid *pyr_b, int psz, int level, void *hip_stream);
-// the same with the grid's node bias [ny][nx] on the device, as the coarse-to-fine flow's patch-mean normalisation has it
-extern "C" int ictr_flowdensify_run_level_bias_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                                const ictr_pyramid *pyr_b, int psz, int level, const float *bias,
-                                                void *hip_stream);
-// the densifier's colour run: three pyramids per frame of one geometry, the node bias [ny][nx][3] (NULL: none)
-extern "C" int ictr_flowdensify_run_level_rgb_(ictr_flowdensify *z, const ictr_flowgrid *grid,
-                                               const ictr_pyramid *const pyr_a[3], const ictr_pyramid *const pyr_b[3], int psz,
-                                               int level, const float *bias, void *hip_stream);
-extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
-                                          const ictr_field *src, int x_only, int level, void *hip_stream);
-// the refiner's colour run: three pyramids per frame of one geometry, a device field [h][w][2], two more Bw planes
-// [2][h][w] of the caller's on the device
-extern "C" int ictr_flowrefine_run_level_rgb_(ictr_flowrefine *r, const ictr_pyramid *const pyr_a[3],
-                                              const ictr_pyramid *const pyr_b[3], const float *field, int x_only, int level,
-                                              float *bw12, void *hip_stream);
+// bias: the grid's node bias [ny][nx][channels] on the device, as patch-mean normalisation has it (NULL: none)
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
+                                           const ictr_pyramid *const *pyr_b, int channels, int psz, int level,
+                                           const float *bias, void *hip_stream);
+// field: a device field [h][w][2]; bw12: two more Bw planes [2][h][w] of the caller's on the device (3 channels alone)
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *const *pyr_a,
+                                          const ictr_pyramid *const *pyr_b, int channels, const float *field, int x_only,
+                                          int level, float *bw12, void *hip_stream);
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);

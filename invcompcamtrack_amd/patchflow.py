@@ -516,70 +516,30 @@ def densify_flow_host(img_a, img_b, d, lost, step, psz, minerr=2.0, power=1, _st
     takes dense_flow's value. The sums are plain f64 sums of exact products, the quotient is rounded to f32 once.
     bias: an (ny, nx) array of per-node brightness offsets beta (the coarse-to-fine flow's node bias under patch-mean
     normalisation); the weight is then 1 / max(|Bw - A[y, x] - beta_node|, minerr)^power. None: the operations above.
-    Colour frames: img_a, img_b are three (H, W) planes each and bias is (ny, nx, 3) (_densify_flow_rgb_host).
+    Colour frames (DESIGN.md §4 "Colour"): img_a, img_b are three (H, W) planes each and bias is None or (ny, nx, 3), one
+    offset per channel. A vote warps the three channels of B at its one position, with one inside decision, and its weight
+    is 1 / max(e, minerr)^power with e = (1/3) sum_c |Bw_c - A_c[y, x] - beta_c|: the channel mean, so that minerr keeps
+    its meaning in grey levels. (The sum starts at 0.0 and adds the channels in order; for one channel 0.0 + |res| and the
+    quotient by 1.0 are exact, so a grey frame's e is |res| to the bit.)
     Returns (H, W, 2) float32. _stages: a dict that receives "count" (votes taken, int), "wsum" (their summed weight,
     f64) and "edge" (the least distance of a pixel's vote positions to the inside boundary in px, inf without one)."""
-    if np.ndim(img_a) == 3:
-        return _densify_flow_rgb_host(img_a, img_b, d, lost, step, psz, minerr, power, _stages, bias)
-    A32, B32, d, lost = _dz_check(img_a, img_b, d, lost, step, psz, minerr, power)
-    A, B = A32.astype(np.float64), B32.astype(np.float64)
-    h, w = A.shape
-    ny, nx = lost.shape
-    i0, i1 = _dz_nodes(w, nx, step, psz)
-    j0, j1 = _dz_nodes(h, ny, step, psz)
-    d64 = d.astype(np.float64)
-    if bias is not None:
-        bias = np.asarray(bias, np.float64)
-        if bias.shape != (ny, nx):
-            raise ValueError(f"densify needs bias ({ny}, {nx})")
-    yy, xx = np.mgrid[0:h, 0:w]
-    su, sv, sw = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
-    cnt = np.zeros((h, w), np.int64)
-    edge = np.full((h, w), np.inf)
-    for a in range(max(int((j1 - j0).max()) + 1, 0)):
-        j, vj = np.minimum(j0 + a, ny - 1), j0 + a <= j1
-        for b in range(max(int((i1 - i0).max()) + 1, 0)):
-            i, vi = np.minimum(i0 + b, nx - 1), i0 + b <= i1
-            votes = vj[:, None] & vi[None, :] & ~lost[j][:, i]
-            dx, dy = d64[j][:, i, 0], d64[j][:, i, 1]
-            px, py = xx + dx, yy + dy
-            with np.errstate(invalid="ignore"):
-                bw, inside = _fr_warp(B, px, py)
-                near = np.minimum(np.minimum(np.abs(px), np.abs(px - (w - 1))), np.minimum(np.abs(py), np.abs(py - (h - 1))))
-                edge = np.where(votes & (near < edge), near, edge)
-                ok = votes & (inside > 0)
-                res = bw - A if bias is None else bw - A - bias[j][:, i]
-                wgt = 1.0 / _dz_power(np.fmax(np.abs(res), float(minerr)), power)
-                su, sv, sw = np.where(ok, su + wgt * dx, su), np.where(ok, sv + wgt * dy, sv), np.where(ok, sw + wgt, sw)
-            cnt += ok
-    out = _dense_from_nodes(d.copy(), lost, w, h, step)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        out[..., 0] = np.where(cnt > 0, su / sw, out[..., 0])
-        out[..., 1] = np.where(cnt > 0, sv / sw, out[..., 1])
-    if _stages is not None:
-        _stages.update(count=cnt, wsum=sw, edge=edge)
-    return out
-
-
-def _densify_flow_rgb_host(img_a, img_b, d, lost, step, psz, minerr, power, _stages, bias):
-    """densify_flow_host on colour frames (DESIGN.md §4 "Colour"): img_a, img_b are three (H, W) planes each, bias None or
-    (ny, nx, 3), one offset per channel. A vote warps the three channels of B at its one position, with one inside
-    decision, and its weight is 1 / max(e, minerr)^power with e = (1/3) sum_c |Bw_c - A_c[y, x] - beta_c|: the channel
-    mean, so that minerr keeps its meaning in grey levels. Everything else is densify_flow_host's."""
-    A3, B3 = np.asarray(img_a, np.float32), np.asarray(img_b, np.float32)
-    if A3.ndim != 3 or A3.shape[0] != 3 or B3.shape != A3.shape:
+    A32, B32 = np.asarray(img_a, np.float32), np.asarray(img_b, np.float32)
+    colour = A32.ndim == 3
+    if colour and (A32.shape[0] != 3 or B32.shape != A32.shape):
         raise ValueError("densify: colour frames are three (H, W) planes each")
-    _, _, d, lost = _dz_check(A3[0], B3[0], d, lost, step, psz, minerr, power)
-    A, B = A3.astype(np.float64), B3.astype(np.float64)
-    h, w = A.shape[1:]
+    _, _, d, lost = _dz_check(A32[0] if colour else A32, B32[0] if colour else B32, d, lost, step, psz, minerr, power)
+    h, w = A32.shape[-2:]
+    A, B = A32.astype(np.float64).reshape(-1, h, w), B32.astype(np.float64).reshape(-1, h, w)
+    nch = len(A)
     ny, nx = lost.shape
     i0, i1 = _dz_nodes(w, nx, step, psz)
     j0, j1 = _dz_nodes(h, ny, step, psz)
     d64 = d.astype(np.float64)
     if bias is not None:
         bias = np.asarray(bias, np.float64)
-        if bias.shape != (ny, nx, 3):
-            raise ValueError(f"densify needs bias ({ny}, {nx}, 3)")
+        if bias.shape != ((ny, nx, 3) if colour else (ny, nx)):
+            raise ValueError(f"densify needs bias ({ny}, {nx}, 3)" if colour else f"densify needs bias ({ny}, {nx})")
+        bias = bias.reshape(ny, nx, nch)
     yy, xx = np.mgrid[0:h, 0:w]
     su, sv, sw = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
     cnt = np.zeros((h, w), np.int64)
@@ -593,11 +553,11 @@ def _densify_flow_rgb_host(img_a, img_b, d, lost, step, psz, minerr, power, _sta
             px, py = xx + dx, yy + dy
             with np.errstate(invalid="ignore"):
                 e = 0.0
-                for c in range(3):
+                for c in range(nch):
                     bw, inside = _fr_warp(B[c], px, py)
                     res = bw - A[c] if bias is None else bw - A[c] - bias[j][:, i, c]
                     e = e + np.abs(res)
-                e = e / 3.0
+                e = e / float(nch)
                 near = np.minimum(np.minimum(np.abs(px), np.abs(px - (w - 1))), np.minimum(np.abs(py), np.abs(py - (h - 1))))
                 edge = np.where(votes & (near < edge), near, edge)
                 ok = votes & (inside > 0)
@@ -1040,7 +1000,7 @@ class CoarseToFineFlow:
     c2f_flow_host's finest level (default 0); above 0 only the levels lv_f .. lv_l exist and run, and a run ends with
     k_flow_upsample from level lv_l's field into the object's w x h result plane, which ``dense`` and ``device_ptr`` then
     hand out. channels: 1 (grey frames, one pyramid each) or 3 (colour frames, c2f_flow_host's rule on triples: ``run``
-    then takes two sequences of three pyramids, k_c2f_level's NCH = 3 forms, k_densify_rgb and k_fr_warp_rgb /
+    then takes two sequences of three pyramids, k_c2f_level's, k_densify's and k_fr_warp's NCH = 3 forms and
     k_fr_coef_rgb run, and ``level_bias`` is (ny, nx, 3)). ``run`` enqueues and returns; ``dense``
     (the w x h field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 

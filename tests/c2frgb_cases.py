@@ -1,5 +1,5 @@
 """Cases, recorded differences and usefulness scenes for the coarse-to-fine dense flow on colour frames (the NCH = 3 forms of
-csrc/ictr_c2fflow.hip and k_densify_rgb of csrc/ictr_densify.hip), shared by test_c2frgb_cpu.py and test_gpu_c2frgb.py.
+csrc/ictr_c2fflow.hip and k_densify<BIAS, 3> of csrc/ictr_densify.hip), shared by test_c2frgb_cpu.py and test_gpu_c2frgb.py.
 
 The definition is patchflow.c2f_flow_host on triples of pyramids (f64). c2frgb_f32.py restates the kernels in f32; the GPU
 tests demand its bits of the device, per level and of the final field. The CPU module compares the restatement with the

@@ -1,6 +1,6 @@
 """The coarse-to-fine dense flow on colour frames as the device computes it, restated in NumPy float32: the NCH = 3 forms of
 pf_level_search_ch and pf_window_sum_ch (csrc/ictr_patchflow_dev.h), of k_c2f_level (csrc/ictr_c2fflow.hip) and
-k_densify_rgb (csrc/ictr_densify.hip). Written from the kernels. A frame is three pyramids; the search samples T, Gx, Gy
+of k_densify (csrc/ictr_densify.hip). Written from the kernels. A frame is three pyramids; the search samples T, Gx, Gy
 per channel with ONE set of taps; a lane adds channel 0, then 1, then 2 into the same accumulators (the pixels of a channel
 in the grey slot order), then the wave tree and the wave order follow once (sum_ch); H and b are such sums, the decision
 and the step are taken once. With patnorm every channel loses its own mean: the sums of T_c, of Gx_c (and Gy_c) and of I_c
@@ -174,7 +174,7 @@ def search(pyrs_a, pyrs_b, l, init, step, psz, maxiter=10, eps=0.01, patnorm=Fal
 
 
 def densify(img_a, img_b, d_filled, lost, bias, step, psz, minerr=2.0, power=1, defect=None):
-    """k_densify_rgb<bias is not None>: img_a, img_b (3, H, W); bias (ny, nx, 3) or None. (H, W, 2) f32."""
+    """k_densify<bias is not None, 3>: img_a, img_b (3, H, W); bias (ny, nx, 3) or None. (H, W, 2) f32."""
     A, B = np.ascontiguousarray(img_a, F), np.ascontiguousarray(img_b, F)
     d = np.ascontiguousarray(d_filled, F)
     lost = np.asarray(lost).astype(bool)
@@ -301,8 +301,8 @@ def coef(A, bw, u, v, alpha, gamma, delta, defect=None):
 
 def refine(img_a, img_b, flow, alpha=16.0, gamma=13.0, delta=4.5, n_outer=8, n_sor=5, omega=1.6, x_only=False,
            defect=None):
-    """ictr_flowrefine_run_level_rgb_: (H, W, 2) f32; img_a, img_b (3, H, W). k_fr_warp_rgb is flowrefine_f32.warp per
-    channel, the half-sweeps are the grey ones."""
+    """ictr_flowrefine_run_level_ on three channels: (H, W, 2) f32; img_a, img_b (3, H, W). k_fr_warp<3> is
+    flowrefine_f32.warp per channel, the half-sweeps are the grey ones."""
     A, B = np.ascontiguousarray(img_a, F), np.ascontiguousarray(img_b, F)
     f0 = np.ascontiguousarray(flow, F)
     if n_outer == 0:

@@ -1,5 +1,5 @@
 """Cases, recorded differences and usefulness figures for the patch-mean normalisation of the coarse-to-fine dense flow
-(patnorm: the MEAN forms of k_c2f_level with their bias tail, k_densify<true>), shared by test_patnorm_cpu.py and
+(patnorm: the MEAN forms of k_c2f_level with their bias tail, k_densify<true, 1>), shared by test_patnorm_cpu.py and
 test_gpu_patnorm.py.
 
 The definition is patchflow.c2f_flow_host(..., patnorm=True) (f64). patnorm_f32.py restates the kernels in f32; the GPU

@@ -1,6 +1,6 @@
 """Patch-mean normalisation of the coarse-to-fine dense flow as the device computes it, restated in NumPy float32: the
 MEAN forms of pf_level_search (csrc/ictr_patchflow_dev.h) and k_c2f_level with its bias tail (csrc/ictr_c2fflow.hip), and
-k_densify<true> (csrc/ictr_densify.hip). Written from the kernels: the sum of T joins the three sums of H, the sums of Gx
+k_densify<true, 1> (csrc/ictr_densify.hip). Written from the kernels: the sum of T joins the three sums of H, the sums of Gx
 and Gy are taken once, an iteration has ONE reduction of (sum Gx (T' - I), sum Gy (T' - I), sum I) and
 b = s + (sum I / n) sum G; the bias is sum(B at the final position) / n - sum(T) / n. The unchanged pieces (taps, fetch, the
 sum shapes, the fill, the warp, the refinement) are those of patchflow_f32.py, c2fflow_f32.py, densify_f32.py.
@@ -115,7 +115,7 @@ def search(pyr_a, pyr_b, l, init, step, psz, maxiter=10, eps=0.01, min_det=1e-4,
 
 
 def densify(img_a, img_b, d_filled, lost, bias, step, psz, minerr=2.0, power=1, defect=None):
-    """k_densify<true>: densify_f32.densify with the node's beta taken off the residual, r = (Bw - A) - beta."""
+    """k_densify<true, 1>: densify_f32.densify with the node's beta taken off the residual, r = (Bw - A) - beta."""
     A, B = np.ascontiguousarray(img_a, F), np.ascontiguousarray(img_b, F)
     d = np.ascontiguousarray(d_filled, F)
     beta = np.zeros_like(bias) if defect == "vote ignores beta" else np.ascontiguousarray(bias, F)

@@ -191,9 +191,14 @@ def test_the_library_exports_the_stage():
     """The symbols of the stage in include/ictr.h, in the library and in the ctypes table."""
     from invcompcamtrack_amd import _lib
     want = ["ictr_c2fflow_" + n for n in ("create", "destroy", "set_params", "set_refine", "run", "result", "device_ptr",
-                                           "level_dims", "read_level", "set_timing", "get_kernel_ms")]
+                                           "level_dims", "read_level", "set_timing", "get_kernel_ms",
+                                           "set_patnorm", "read_level_bias", "set_x_only", "get_x_only", "create_lvl",
+                                           "get_lv_l", "get_upsample_ms", "set_channels", "get_channels", "run_rgb",
+                                           "read_level_bias_rgb")]
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr.h")).read(), flags=re.S)
     assert sorted(set(re.findall(r"\b(ictr_c2fflow_[a-z0-9_]+)\s*\(", txt))) == sorted(want)
+    assert re.search(r"\bictr_flow_upsample\s*\(", txt)  # the up-sampling of a finest level above 0 is declared with them
+    want.append("ictr_flow_upsample")
     import __graft_entry__ as g
     g.build()
     raw = C.CDLL(_lib.LIB_PATH)

@@ -5,6 +5,7 @@ colour on an isoluminant scene, on the definition alone; and the C interface's t
 restatement's bits of the device, so that every figure here is the device's too."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 import re
 
@@ -274,8 +275,18 @@ def test_tracker_and_cli_refuse_colour_with_the_flow_grids():
 def test_header_declares_what_the_ctypes_table_holds():
     want = ["ictr_c2fflow_get_channels", "ictr_c2fflow_read_level_bias_rgb", "ictr_c2fflow_run_rgb",
             "ictr_c2fflow_set_channels"]
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr_c2f_rgb.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(ictr_[a-z0-9_]+)\s*\(", txt))) == want == sorted(_lib.SIGNATURES_RGB)
-    assert '#include "ictr_c2f_rgb.h"' in open(os.path.join(ROOT, "include", "ictr.h")).read()
+    i, vp = C.c_int, C.c_void_p
+    sigs = {"ictr_c2fflow_set_channels": (i, [vp, i]),
+            "ictr_c2fflow_get_channels": (i, [vp, C.POINTER(i)]),
+            "ictr_c2fflow_run_rgb": (i, [vp, C.POINTER(vp), C.POINTER(vp), vp]),
+            "ictr_c2fflow_read_level_bias_rgb": (i, [vp, i, C.POINTER(C.c_float)])}
+    assert sorted(sigs) == want
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ictr_[a-z0-9_]+)\s*\(", txt))
+    assert all(n in declared for n in want)
+    assert {n: _lib.SIGNATURES[n] for n in want} == sigs
     import __graft_entry__ as G
-    assert any(h.endswith("ictr_c2f_rgb.h") for h in G.HEADERS)
+    assert any(os.path.normpath(h).endswith(os.path.join("include", "ictr.h")) for h in G.HEADERS)
+    G.build()
+    raw = C.CDLL(_lib.LIB_PATH)
+    assert all(hasattr(raw, n) for n in want)

@@ -238,12 +238,19 @@ def test_the_shapes_overshoot_and_undershoot_the_frame_along_both_axes():
 
 
 def test_the_library_exports_the_option():
-    """The symbols in their header, in the library and in their ctypes table; ictr.h includes the header."""
+    """The symbols declared in include/ictr.h's text, in the ctypes table with their signatures, and in the library."""
     from invcompcamtrack_amd import _lib
     want = ["ictr_c2fflow_create_lvl", "ictr_c2fflow_get_lv_l", "ictr_c2fflow_get_upsample_ms", "ictr_flow_upsample"]
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr_c2f_lvl.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(ictr_[a-z0-9_]+)\s*\(", txt))) == want == sorted(_lib.SIGNATURES_LVL)
-    assert '#include "ictr_c2f_lvl.h"' in open(os.path.join(ROOT, "include", "ictr.h")).read()
+    i, vp = C.c_int, C.c_void_p
+    sigs = {"ictr_c2fflow_create_lvl": (i, [C.POINTER(vp), i, i, i, i, i, i]),
+            "ictr_c2fflow_get_lv_l": (i, [vp, C.POINTER(i)]),
+            "ictr_c2fflow_get_upsample_ms": (i, [vp, C.POINTER(C.c_float)]),
+            "ictr_flow_upsample": (i, [vp, i, i, i, vp, i, i, i, i, vp])}
+    assert sorted(sigs) == want
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ictr.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ictr_[a-z0-9_]+)\s*\(", txt))
+    assert all(n in declared for n in want)
+    assert {n: _lib.SIGNATURES[n] for n in want} == sigs
     import __graft_entry__ as g
     g.build()
     raw = C.CDLL(_lib.LIB_PATH)

@@ -1,5 +1,5 @@
-"""The coarse-to-fine dense flow on colour frames on the device (the NCH = 3 forms of k_c2f_level, k_densify_rgb, k_fr_warp_rgb
-and k_fr_coef_rgb) against its f32 restatement (c2frgb_f32.py), bit for bit and with nothing left out: per table entry and
+"""The coarse-to-fine dense flow on colour frames on the device (the NCH = 3 forms of k_c2f_level, k_densify and k_fr_warp, and
+k_fr_coef_rgb) against its f32 restatement (c2frgb_f32.py), bit for bit and with nothing left out: per table entry and
 per level the node displacements, the status bytes, the node bias and the level's field, and the final field, so that every
 figure c2frgb_cases.py records for the restatement against the definition (patchflow.c2f_flow_host on triples) is the
 device's too. Then the exact properties of the rule on the device and the refusals.
@@ -114,6 +114,43 @@ def test_one_channel_of_the_same_frames_has_the_grey_restatements_bits():
             assert np.array_equal(_bits(c.run(pa[ch], pb[ch]).dense()), _bits(want)), (patnorm, ch)
             if patnorm:
                 assert c.level_bias(0).ndim == 2
+
+
+def test_grey_and_colour_objects_in_turn_keep_their_bits():
+    """Both channel counts through the shared paths in one process: the densifier's and the refiner's one run function
+    take the channel count, the densifier's LDS byte count follows the record's size, and the colour refinement's two more
+    Bw planes are the object's. 33 x 17 frames (level 1 is 16 x 8: the refiner's 4 x 4 holds, two workgroup columns'
+    worth of tiles, odd sizes), lv_f 1, step 4, psz 8, patnorm on, refinement (1, 5, 1.6). Colour, grey, colour, grey:
+    every run has the bits of c2frgb_f32.run and patnorm_f32.run respectively, and each second run those of the first."""
+    import patnorm_f32 as PN
+    from invcompcamtrack_amd import synth
+    from oracle import oracle as O
+    w, h, lv_f, step, psz, pad = 33, 17, 1, 4, 8, 9
+    refine = dict(n_outer=1, n_sor=5, omega=1.6)
+    sc = [synth.make_scene(w, h, n_points=4, seed=9, tex_seed=1234 + k, margin=4.0,
+                           dp_gt=np.array([0.1, -0.06, 0.05, 0.02, -0.015, 0.01])) for k in range(3)]
+    a = [np.ascontiguousarray(s["img_a"], np.float32) for s in sc]
+    b = [np.ascontiguousarray(s["img_b"].astype(np.float64) + off, np.float32) for s, off in zip(sc, RC.OFFSETS)]
+    ha, hb = [O.Pyramid(x, lv_f, pad) for x in a], [O.Pyramid(x, lv_f, pad) for x in b]
+    pa, pb = ([ic.Pyramid(lv_f=lv_f, imgpadding=pad, wh=(w, h), host_planes=(o.img, o.dx, o.dy)) for o in side]
+              for side in (ha, hb))
+    want = {}
+    for nch in (3, 1):
+        st = []
+        if nch == 3:
+            out = R.run(ha, hb, step, psz, lv_f, 0, patnorm=True, stages=st, refine_params=refine)
+        else:
+            out = PN.run(ha[0], hb[0], step, psz, lv_f, refine=refine, stages=st)
+        want[nch] = (out, st)
+    flow = {nch: pf.CoarseToFineFlow(w, h, lv_f, step, psz, patnorm=True, refine=refine, channels=nch) for nch in (3, 1)}
+    first = {}
+    for nch in (3, 1, 3, 1):
+        c = flow[nch].run(pa, pb) if nch == 3 else flow[nch].run(pa[0], pb[0])
+        _same_as_restatement(c, ("33x17", nch), True, want[nch])
+        got = [c.dense()] + [x for level in range(lv_f, -1, -1) for x in list(c.level(level)) + [c.level_bias(level)]]
+        assert got[-1].shape[2:] == ((3,) if nch == 3 else ())
+        again = first.setdefault(nch, got)
+        assert len(got) == 9 and all(x.tobytes() == y.tobytes() for x, y in zip(got, again)), nch
 
 
 # ---------------------------------------------------------------- exact and near-exact properties, on the device

@@ -1,5 +1,5 @@
 """Patch-mean normalisation of the coarse-to-fine dense flow on the device (the MEAN forms of k_c2f_level with their bias
-tail, k_densify<true>) against its f32 restatement (patnorm_f32.py), bit for bit and with nothing left out: per table entry
+tail, k_densify<true, 1>) against its f32 restatement (patnorm_f32.py), bit for bit and with nothing left out: per table entry
 and per level the node displacements, the status bytes, the node bias and the level's field, and the final field, so that
 every figure patnorm_cases.py records for the restatement against the definition is the device's too. Then the switch
 (off: today's bits), the stereo pipeline, the CLI, the C++ facade and the refusals.

@@ -42,6 +42,13 @@ channel 0 is the grey frame, the other two channels are textures of their own un
 and densification medians of each and their ratio, and the whole runs. Recorded without a bar. --parent-root measures the
 default paths colour must leave alone, CoarseToFineFlow.run grey (psz 8 and 15) and FlowDensifier.run (psz 15), with the
 same bar.
+
+  python tools/c2fflow_bench.py --fold --parent-root DIR [--reps 7] [--out profiles/c2fflow_fold_bench.json]
+
+Nothing but the comparison with the parent, for a change that must leave every path as fast as it was: CoarseToFineFlow.run
+grey (psz 8 and 15), FlowDensifier.run (psz 15), FlowRefiner.run at its defaults on the densifier's field, and
+CoarseToFineFlow(channels=3).run with patnorm and the refinement on (psz 8 and 15), in child processes of the two builds in
+turn (two each), with the same bar.
 """
 import argparse
 import json
@@ -98,8 +105,9 @@ def default_child(root, reps):
 
 def option_child(root, reps, option):
     """Runs in a child process: CoarseToFineFlow.run (no keyword of the option: the parent has none) and, for "patnorm",
-    FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair (for "lv_l" nothing more), of the tree at `root`,
-    HIP events around each."""
+    FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair (for "lv_l" nothing more), for "fold"
+    FlowDensifier.run, FlowRefiner.run and the colour run with patnorm and the refinement (the parent has them), of the
+    tree at `root`, HIP events around each."""
     sys.path.insert(0, root)
     import torch
 
@@ -119,11 +127,21 @@ def option_child(root, reps, option):
                 grid = pf.FlowGrid(w, h, STEP)
                 rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
                                                 for _ in range(reps + 1)][1:]
-            elif psz == PSZS[1] and option in ("patnorm", "colour"):
+            elif psz == PSZS[1] and option in ("patnorm", "colour", "fold"):
                 grid, dz = pf.FlowGrid(w, h, STEP), pf.FlowDensifier(w, h)
                 grid.compute(pa, pb, psz=psz, lv_f=LV_F)
                 rec["flowdensifier_run_ms"] = [float(_timed(torch, lambda: dz.run(grid, pa, pb, psz)))
                                                for _ in range(reps + 1)][1:]
+                if option == "fold":
+                    rf = pf.FlowRefiner(w, h)
+                    rec["flowrefiner_run_ms"] = [float(_timed(torch, lambda: rf.run(pa, pb, dz)))
+                                                 for _ in range(reps + 1)][1:]
+            if option == "fold":  # channel 0 is the grey run's frame; the other two have textures of their own
+                tri = [[ic.Pyramid(f[k][0], LV_F, psz, True) for f in (fr, frames(w, h, seed=6), frames(w, h, seed=7))]
+                       for k in (0, 1)]
+                c3 = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, channels=3, patnorm=True, refine={})
+                rec[f"c2f_colour_patnorm_refine_run_psz{psz}_ms"] = [float(_timed(torch, lambda: c3.run(*tri)))
+                                                                     for _ in range(reps + 1)][1:]
         out[f"{w}x{h}"] = rec
     print("DEFAULT " + json.dumps(out), flush=True)
 
@@ -155,6 +173,19 @@ def _option_against_parent(a, option, out):
         ok &= bar
     print(json.dumps(out["default_paths"]), flush=True)
     return ok
+
+
+def fold_main(a):
+    """--fold: the comparison with the parent alone."""
+    sys.path.insert(0, ROOT)
+    if not a.parent_root:
+        raise SystemExit("--fold compares with --parent-root")
+    out = {"bench": "c2fflow_fold", "step": STEP, "lv_f": LV_F, "reps": a.reps}
+    ok = _option_against_parent(a, "fold", out)
+    with open(a.out or os.path.join(ROOT, "profiles", "c2fflow_fold_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
 
 
 def lvl_main(a):
@@ -278,7 +309,9 @@ def main():
     ap.add_argument("--lv-l", dest="lv_l", action="store_true", help="measure a finest level above 0 instead")
     ap.add_argument("--colour", action="store_true", help="measure colour frames against grey ones instead")
     ap.add_argument("--option-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l", "colour"), help=argparse.SUPPRESS)
+    ap.add_argument("--fold", action="store_true", help="compare every flow path with the parent's instead")
+    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l", "colour", "fold"),
+                    help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -288,6 +321,8 @@ def main():
         return option_child(a.option_child, a.reps, a.option)
     if a.reps < 7:
         ap.error("at least 7 runs each")
+    if a.fold:
+        return fold_main(a)
     if a.lv_l:
         return lvl_main(a)
     if a.patnorm or a.x_only or a.colour:
