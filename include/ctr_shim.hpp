@@ -594,6 +594,11 @@ class CoarseFlowClass {
     check(ictr_c2fflow_get_x_only(h_, &on), "XOnly");
     return on != 0;
   }
+  // the patch cost of the next runs (ictr_c2fflow_set_cost): ICTR_C2F_COST_L2 (default) or ICTR_C2F_COST_HUBER, which clips
+  // every residual of the search to [-huber_k, +huber_k] grey levels. Cost 1 (L1), unknown codes and a huber_k that is not
+  // finite and > 0 throw, and the object stays as it was.
+  void SetCost(int cost, float huber_k = 5.0f) { check(ictr_c2fflow_set_cost(h_, cost, huber_k), "SetCost"); }
+  void GetCost(int *cost, float *huber_k) const { check(ictr_c2fflow_get_cost(h_, cost, huber_k), "GetCost"); }
   // a, b: pyramids of the object's size with levels 0 .. lv_f, padded by at least psz, a with gradient planes
   void Run(const Pyramid &a, const Pyramid &b, void *hip_stream = nullptr) {
     check(ictr_c2fflow_run(h_, a.handle(), b.handle(), hip_stream), "Run");

@@ -1062,6 +1062,9 @@ int ictr_c2fflow_run_rgb(ictr_c2fflow *c, const ictr_pyramid *const pyr_a[3], co
 /* of the last run, which had patnorm on, of a 3-channel object (waits for it): the node bias [ny][nx][3] of a level;
  * ictr_c2fflow_read_level_bias refuses such an object */
 int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, float *bias);
+/* -- the patch cost of the search (DESIGN.md §4 "Robust patch cost"): ictr_c2fflow_set_cost, ictr_c2fflow_get_cost,
+ * ICTR_C2F_COST_L2, ICTR_C2F_COST_HUBER */
+#include "ictr_c2f_cost.h"
 
 #ifdef __cplusplus
 }

@@ -371,6 +371,11 @@ SIGNATURES = {
     "ictr_c2fflow_run_rgb": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
     "ictr_c2fflow_read_level_bias_rgb": (C.c_int, [VP, C.c_int, FP]),
 }
+# the patch cost of the coarse-to-fine flow's search, declared in include/ictr_c2f_cost.h (which ictr.h includes)
+SIGNATURES_COST = {
+    "ictr_c2fflow_set_cost": (C.c_int, [VP, C.c_int, C.c_float]),
+    "ictr_c2fflow_get_cost": (C.c_int, [VP, C.POINTER(C.c_int), FP]),
+}
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {
     "ictr_triangulate_DLT": (C.c_int, [FP, FP, FP, FP, C.c_int]),
@@ -419,7 +424,8 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
+                              + list(SIGNATURES_COST.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

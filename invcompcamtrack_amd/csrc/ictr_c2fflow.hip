@@ -26,6 +26,11 @@
 // MEAN tail writes three betas per node, and a level's densifier and refiner runs take the three pyramids per frame
 // (k_densify<BIAS, 3>, k_fr_warp<3>, k_fr_coef_rgb). Restated by tests/c2frgb_f32.py.
 //
+// ROBUST is the Huber patch cost (DESIGN.md "Robust patch cost"): pf_level_search_ch's ROBUST forms, every residual clipped
+// to [-huber_k, +huber_k]; nothing else of the kernel changes. k_c2f_level, its arguments and its launcher live in
+// ictr_c2fflow_dev.h; this file instantiates the L2 forms and ictr_c2fflow_robust.hip the ROBUST ones, which
+// launch_c2f_level_robust reaches. Restated by tests/c2fcost_f32.py.
+//
 // k_flow_upsample<XONLY> finishes a run whose finest level is above 0 (DESIGN.md "A finest level above 0"): the field of
 // level lv to the w x h frame, bilinear with half-pixel centres at the fixed factor 2^-lv, the vectors times 2^lv. One lane
 // per output pixel, a wave per 64 consecutive columns of a row and kWaves rows per workgroup, so that a workgroup's source
@@ -42,133 +47,9 @@
 #include "ictr_launch.h"
 #include "ictr_devfn.h"
 #include "ictr_patchflow_dev.h"
+#include "ictr_c2fflow_dev.h"
 
 namespace ictr {
-
-// The plain forms' arguments ...
-template <bool MEAN, int NCH>
-struct C2fArgs {
-  const float *a[NCH], *ax[NCH], *ay[NCH], *b[NCH];  // this level, per channel: frame A image + gradients, frame B image
-                                                     // (padded planes of one geometry)
-  int sw, shift;                 // row stride; (pad - P) * (sw + 1), as PFLevel
-  float swo, sho;                // the level's unpadded size
-  int nx, K, step;               // nodes per row, nodes, node spacing
-  const float2 *coarse;          // the coarser level's dense field [ch][cw], NULL at the coarsest level
-  int cw, ch;
-  int P, maxiter;
-  float eps2, min_det, far2;     // stop when |dp|^2 < eps2; conditioning (XONLY: min_hx); (float)(P * P)
-  float *d;                      // [K][2] raw node displacements (the fill's input)
-  unsigned char *lost, *status;  // [K], [K]
-};
-// ... and behind them bias for the MEAN forms alone (the plain forms keep their arguments, and with them their code, to
-// the instruction)
-template <int NCH>
-struct C2fArgs<true, NCH> : C2fArgs<false, NCH> {
-  float *bias;  // [K][NCH] node brightness offsets per channel
-};
-
-// channel c's planes of a level
-template <bool MEAN, int NCH>
-__device__ __forceinline__ PFPlanes c2f_planes(const C2fArgs<MEAN, NCH> &a, int c) {
-  return PFPlanes{(gconst_f32)a.a[c], (gconst_f32)a.ax[c], (gconst_f32)a.ay[c], (gconst_f32)a.b[c],
-                  a.sw,               a.shift,             a.swo,               a.sho};
-}
-
-// NCH = 3 is the colour form (DESIGN.md "Colour"): pf_level_search_ch over three channel planes, one decision and one
-// step per node, and with MEAN three betas per node, bias[k][c]. A reduction's row of sSum is then 8 floats wide: the
-// widest (H with three sums of T) carries six values in one trip. Restated by tests/c2frgb_f32.py.
-template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH = 1>
-__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgs<MEAN, NCH> a) {
-  static_assert(NCH == 1 || NCH == 3, "one channel or three");
-  constexpr int PPB = kWaves / WPP;  // nodes per workgroup
-  constexpr int SW = NCH == 1 ? 4 : 8;
-  __shared__ float sSum[WPP > 1 ? kWaves : 1][SW];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int k = blockIdx.x * PPB + wave / WPP;
-  const bool valid = k < a.K;
-  if (WPP == 1 && !valid) return;
-  const int kk = valid ? k : 0;
-  const int nj = kk / a.nx, ni = kk - nj * a.nx;
-  const int X = a.step / 2 + ni * a.step, Y = a.step / 2 + nj * a.step;  // inside the level: the template needs no test
-  const float xl = (float)X, yl = (float)Y;
-  float ix = 0.0f, iy = 0.0f;
-  if (a.coarse) {
-    if constexpr (XONLY) {  // y is not read and stays +0.0
-      ix = 2.0f * a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)].x;
-    } else {
-      const float2 c = a.coarse[(size_t)min(Y >> 1, a.ch - 1) * a.cw + min(X >> 1, a.cw - 1)];
-      ix = 2.0f * c.x;
-      iy = 2.0f * c.y;
-    }
-  }
-  const bool finite = (fabsf(ix) <= 3.402823466e+38f) & (fabsf(iy) <= 3.402823466e+38f);  // false for NaN
-  int st = (valid && finite && pf_in_view(xl + ix, yl + iy, a.swo, a.sho)) ? ICTR_C2F_TRACKED : ICTR_C2F_LOST;
-  float px = ix, py = iy;
-  float mean_t[NCH] = {};
-  // (formed once, ahead of both uses: the grey forms then report the registers they had with one set of planes per use)
-  PFPlanes L[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) L[c] = c2f_planes(a, c);
-  // One wave per node with a start out of view is done; two waves per node share the search's barriers.
-  if (WPP > 1 || st == ICTR_C2F_TRACKED) {
-    int nit = 0;
-    const int why = pf_level_search_ch<NPL, WPP, XONLY, MEAN, NCH, SW>(L, a.P, xl, yl, st == ICTR_C2F_TRACKED, px, py, nit,
-                                                                       a.maxiter, a.eps2, a.min_det, sSum, mean_t);
-    if (why) st = why == PF_STOP_COND ? ICTR_C2F_HELD_COND : ICTR_C2F_HELD_VIEW;
-    if (st == ICTR_C2F_TRACKED) {  // a runaway patch: further than P from its start, or not finite (a positive test)
-      const float dx = px - ix, dy = py - iy;
-      if constexpr (XONLY) {
-        if (!(dx * dx <= a.far2)) st = ICTR_C2F_HELD_FAR;
-      } else {
-        if (!(dx * dx + dy * dy <= a.far2)) st = ICTR_C2F_HELD_FAR;
-      }
-    }
-  }
-  float beta[NCH] = {};
-  if constexpr (MEAN) {
-    // the node's final position: where it votes from. Two waves per node: every node of the workgroup makes the pass.
-    const bool held = st >= ICTR_C2F_HELD_COND;
-    const float fx = xl + (held ? ix : px), fy = yl + (held ? iy : py);
-    const bool votes = valid && st != ICTR_C2F_LOST && pf_in_view(fx, fy, a.swo, a.sho);
-    if (WPP > 1 || votes) {
-      float sb[NCH];
-      pf_window_sum_ch<NPL, WPP, NCH, SW>(L, a.P, votes ? fx : 1.0f, votes ? fy : 1.0f, sSum, sb);
-      if (votes) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) beta[c] = sb[c] / (float)(a.P * a.P) - mean_t[c];
-      }
-    }
-  }
-  if (lane == 0 && wave % WPP == 0 && valid) {
-    const float nanv = __int_as_float(0x7fc00000);
-    const bool held = st >= ICTR_C2F_HELD_COND;
-    a.d[2 * k] = st == ICTR_C2F_LOST ? nanv : held ? ix : px;  // a held node: its start's bits
-    a.d[2 * k + 1] = st == ICTR_C2F_LOST ? nanv : held ? iy : py;
-    a.lost[k] = st == ICTR_C2F_LOST ? 1 : 0;
-    a.status[k] = (unsigned char)st;
-    if constexpr (MEAN) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) a.bias[NCH * k + c] = beta[c];
-    }
-  }
-}
-
-// the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
-template <bool MEAN, bool XONLY, int NCH>
-static void launch_c2f_level(const C2fArgs<MEAN, NCH> &a, hipStream_t s) {
-  const int npl = (a.P * a.P + 63) / 64;
-  const dim3 blk(kBlock);
-  if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY, NCH>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s, a);
-    return;
-  }
-  const dim3 g((a.K + kWaves - 1) / kWaves);
-  if (npl <= 1)
-    hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN, XONLY, NCH>), g, blk, 0, s, a);
-  else
-    hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY, NCH>), g, blk, 0, s, a);
-}
 
 // s = 2^lv, inv_s = 2^-lv. Everything before the taps is exact in f32 (x + 0.5, the product with 2^-lv, - 0.5, rx,
 // 1 - rx); the six products and three sums are taken in the order written, each rounded (no contraction), then s * val.
@@ -248,6 +129,8 @@ struct ictr_c2fflow {
   int patnorm = 0;
   int x_only = 0;  // the 1-D form: the XONLY kernels and the refinement along x
   int channels = 1;  // 3: colour frames, three pyramids per frame (ictr_c2fflow_run_rgb)
+  int cost = ICTR_C2F_COST_L2;  // ICTR_C2F_COST_HUBER: the ROBUST kernels with huber_k
+  float huber_k = 5.0f;
   int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
   std::vector<C2fLevel> lv;  // [lv_f + 1]; the levels below lv_l hold their size and nothing else
   DevBuf<unsigned char> status;
@@ -389,6 +272,26 @@ extern "C" int ictr_c2fflow_get_x_only(const ictr_c2fflow *c, int *on) {
   *on = c->x_only;
   return ICTR_OK;
 }
+extern "C" int ictr_c2fflow_set_cost(ictr_c2fflow *c, int cost, float huber_k) {
+  if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
+  if (cost == 1)
+    return fail(ICTR_ERR_INVALID,
+                "c2fflow_set_cost: cost 1 (L1) is not built: with H fixed its influence sign(r) has no scale; use "
+                "ICTR_C2F_COST_HUBER (2) with a small huber_k");
+  if (cost != ICTR_C2F_COST_L2 && cost != ICTR_C2F_COST_HUBER)
+    return fail(ICTR_ERR_INVALID, "c2fflow_set_cost: cost is %d (0: L2, or 2: Huber)", cost);
+  if (!(huber_k > 0.0f) || !isfinite(huber_k))
+    return fail(ICTR_ERR_INVALID, "c2fflow_set_cost: huber_k must be finite and > 0");
+  c->cost = cost;
+  c->huber_k = huber_k;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fflow_get_cost(const ictr_c2fflow *c, int *cost, float *huber_k) {
+  if (!c || !cost || !huber_k) return fail(ICTR_ERR_INVALID, "c2fflow_get_cost: c2fflow, cost or huber_k is NULL");
+  *cost = c->cost;
+  *huber_k = c->huber_k;
+  return ICTR_OK;
+}
 extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
   c->timing = on ? 1 : 0;
@@ -396,11 +299,11 @@ extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
 }
 
 // level l's search of a run: pfc[ch] the level tables of the channels' pyramids, which agree in geometry
-template <bool MEAN, bool XONLY, int NCH>
+template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
 static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, hipStream_t s) {
   const C2fLevel &L = c->lv[l];
   const PFArgs &pf = pfc[0];
-  C2fArgs<MEAN, NCH> a;
+  C2fArgsOf<MEAN, NCH, ROBUST> a;
   memset(&a, 0, sizeof(a));
   for (int ch = 0; ch < NCH; ++ch)
     a.a[ch] = pfc[ch].lv[l].a, a.ax[ch] = pfc[ch].lv[l].ax, a.ay[ch] = pfc[ch].lv[l].ay, a.b[ch] = pfc[ch].lv[l].b;
@@ -424,15 +327,25 @@ static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refin
   if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
   a.status = L.status;
   if constexpr (MEAN) a.bias = L.bias;
+  if constexpr (ROBUST) a.huber_k = c->huber_k;
   if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
-  launch_c2f_level<MEAN, XONLY, NCH>(a, s);
+  if constexpr (ROBUST)
+    launch_c2f_level_robust(a, XONLY, s);  // (instantiated in ictr_c2fflow_robust.hip)
+  else
+    launch_c2f_level<MEAN, XONLY, NCH, false>(a, s);
   return ICTR_OK;
 }
-// the search's form by [patnorm][x_only][channels == 3]
+// the search's form by [cost == Huber][patnorm][x_only][channels == 3]
 using C2fSearch = int (*)(const ictr_c2fflow *, const PFArgs *, int, int, hipStream_t);
-static const C2fSearch kC2fSearch[2][2][2] = {
-    {{c2f_search<false, false, 1>, c2f_search<false, false, 3>}, {c2f_search<false, true, 1>, c2f_search<false, true, 3>}},
-    {{c2f_search<true, false, 1>, c2f_search<true, false, 3>}, {c2f_search<true, true, 1>, c2f_search<true, true, 3>}}};
+#define ICTR_C2F_FORMS(R)                                                                                                  \
+  {                                                                                                                        \
+    {{c2f_search<false, false, 1, R>, c2f_search<false, false, 3, R>},                                                     \
+     {c2f_search<false, true, 1, R>, c2f_search<false, true, 3, R>}},                                                      \
+    {{c2f_search<true, false, 1, R>, c2f_search<true, false, 3, R>},                                                       \
+     {c2f_search<true, true, 1, R>, c2f_search<true, true, 3, R>}}                                                         \
+  }
+static const C2fSearch kC2fSearch[2][2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
+#undef ICTR_C2F_FORMS
 
 // a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
 static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
@@ -454,6 +367,7 @@ static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
   hipStream_t s = (hipStream_t)hip_stream;
   const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
+  const int robust = c->cost == ICTR_C2F_COST_HUBER;
   if (nch == 3 && refined && !c->bw12) {  // the first refined colour run: Bw of channels 1 and 2, the finest level's size
     const C2fLevel &L = c->lv[c->lv_l];
     if (int rc = c->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
@@ -461,7 +375,7 @@ static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr
   c->timed = c->timing;
   for (int l = c->lv_f; l >= c->lv_l; --l) {
     C2fLevel &L = c->lv[l];
-    if (int rc = kC2fSearch[patnorm][x_only][nch == 3](c, pfc, l, refined, s)) return rc;
+    if (int rc = kC2fSearch[robust][patnorm][x_only][nch == 3](c, pfc, l, refined, s)) return rc;
     if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
     if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
     if (int rc = ictr_flowdensify_run_level_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, nch, c->psz, l,

@@ -113,10 +113,21 @@ enum { PF_STOP_NONE = 0, PF_STOP_COND = 1, PF_STOP_VIEW = 2 };  // why a patch s
 // their first use. MEAN: every channel loses its own mean; the reduction of H carries the NCH sums of T behind it (six
 // values in 2-D), the second the NCH sums of Gx(, Gy), an iteration's the NCH sums of I behind b (five in 2-D), and
 // b = s + sum_c (sum I_c / n) sum G_c, the channels added in order. mean_t[c] = mean(T_c).
-template <int NPL, int WPP, bool XONLY, bool MEAN, int NCH, int SW>
+// ROBUST is the Huber patch cost (DESIGN.md "Robust patch cost"): every pixel's and channel's residual is clipped,
+// r <- fminf(fmaxf(r, -k), k), between T - iv and the two products; T, Gx, Gy, H, the conditioning decision, the view
+// tests, the solve and the stop are the L2 forms', and without MEAN an iteration keeps its single reduction. k = huber_k
+// travels behind the existing arguments and is read by the ROBUST forms alone: the others are today's code.
+// ROBUST with MEAN cannot use b = s + mean(I) sum G, which rests on a linear residual; its iteration is the direct form in
+// two passes. Pass 1: per channel all window loads issued, iv blended and KEPT in registers (NPL NCH values), sum I_c; one
+// reduction of NCH values. Pass 2: r = T' - (iv - sum I_c / n), clipped, into b; one reduction of NB values. A window is
+// still loaded once per iteration; the second reduction is on the chain (two waves per patch: two more barriers, every
+// patch of the workgroup running every slot as before). The operation order is fixed: channels 0, 1, 2 into the same
+// accumulators, the pixels of a channel in the grey order; (iv - mean) is formed first, then T' minus it. The sums of Gx
+// and Gy of the L2 MEAN forms are not taken. tests/c2fcost_f32.py restates the ROBUST forms.
+template <int NPL, int WPP, bool XONLY, bool MEAN, int NCH, int SW, bool ROBUST = false>
 __device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int P, float xl, float yl, bool ok, float &px,
                                                   float &py, int &nit, int maxiter, float eps2, float min_cond,
-                                                  float (*sSum)[SW], float (&mean_t)[NCH]) {
+                                                  float (*sSum)[SW], float (&mean_t)[NCH], float huber_k = 0.0f) {
   const PFPlanes &L = Lc[0];  // the geometry of every channel
   const int n = P * P;
   const int slot0 = (WPP > 1 ? ((threadIdx.x >> 6) % WPP) * 64 : 0) + (threadIdx.x & 63);
@@ -150,7 +161,7 @@ __device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int
     }
   }
   pf_patch_sum<WPP>(h, sSum);
-  float sg[NB * NCH] = {};  // MEAN: per channel sum Gx(, sum Gy)
+  float sg[NB * NCH] = {};  // MEAN (L2): per channel sum Gx(, sum Gy)
   if constexpr (MEAN) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -158,8 +169,10 @@ __device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int
 #pragma unroll
       for (int i = 0; i < NPL; ++i) {
         T[c][i] = (slot0 + 64 * WPP * i < n) ? T[c][i] - mean_t[c] : 0.0f;
-        sg[NB * c] += Gx[c][i];
-        if constexpr (!XONLY) sg[NB * c + 1] += Gy[c][i];
+        if constexpr (!ROBUST) {
+          sg[NB * c] += Gx[c][i];
+          if constexpr (!XONLY) sg[NB * c + 1] += Gy[c][i];
+        }
       }
     }
   }
@@ -178,7 +191,7 @@ __device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int
   int why = PF_STOP_NONE;
   if (ok && !cond) why = PF_STOP_COND;
   if (WPP == 1 && why) return why;
-  if constexpr (MEAN) pf_patch_sum<WPP>(sg, sSum);
+  if constexpr (MEAN && !ROBUST) pf_patch_sum<WPP>(sg, sSum);
   bool run = ok && !why;  // this patch still iterates at this level
   for (int it = 0; it < maxiter; ++it) {
     if (WPP == 1 && !run) break;
@@ -189,30 +202,60 @@ __device__ __forceinline__ int pf_level_search_ch(const PFPlanes (&Lc)[NCH], int
       if (WPP == 1) break;
     }
     const PFTaps tb = pf_taps(run ? cx : 1.0f, run ? cy : 1.0f, P, L.sw, L.shift);
-    float b[MEAN ? NB + NCH : NB] = {};  // bx, (by)(, sum I_c)
+    float b[(MEAN && !ROBUST) ? NB + NCH : NB] = {};  // bx, (by)(, sum I_c)
+    if constexpr (ROBUST && MEAN) {
+      float iv[NCH][NPL], si[NCH] = {};
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      PFWin w[NPL];
+      for (int c = 0; c < NCH; ++c) {  // pass 1: the windows, once
+        PFWin w[NPL];
 #pragma unroll
-      for (int i = 0; i < NPL; ++i) w[i] = pf_load(Lc[c].b, tb.base + off[i], L.sw);  // all in flight before the first use
+        for (int i = 0; i < NPL; ++i) w[i] = pf_load(Lc[c].b, tb.base + off[i], L.sw);  // all in flight before the first use
 #pragma unroll
-      for (int i = 0; i < NPL; ++i) {
-        const bool in = slot0 + 64 * WPP * i < n;
-        const float iv = pf_blend(w[i], tb);
-        float r = T[c][i] - iv;
-        r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
-        b[0] += Gx[c][i] * r;
-        if constexpr (!XONLY) b[1] += Gy[c][i] * r;
-        if constexpr (MEAN) b[NB + c] += in ? iv : 0.0f;
+        for (int i = 0; i < NPL; ++i) {
+          iv[c][i] = pf_blend(w[i], tb);
+          si[c] += (slot0 + 64 * WPP * i < n) ? iv[c][i] : 0.0f;
+        }
       }
-    }
-    pf_patch_sum<WPP>(b, sSum);
-    if constexpr (MEAN) {
+      pf_patch_sum<WPP>(si, sSum);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {  // pass 2: the clipped residual of the mean-free window
+        const float mi = si[c] / (float)n;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+          float r = T[c][i] - (iv[c][i] - mi);
+          r = (slot0 + 64 * WPP * i < n) ? r : 0.0f;
+          r = fminf(fmaxf(r, -huber_k), huber_k);
+          b[0] += Gx[c][i] * r;
+          if constexpr (!XONLY) b[1] += Gy[c][i] * r;
+        }
+      }
+      pf_patch_sum<WPP>(b, sSum);
+    } else {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        const float mi = b[NB + c] / (float)n;
-        b[0] = b[0] + mi * sg[NB * c];
-        if constexpr (!XONLY) b[1] = b[1] + mi * sg[NB * c + 1];
+        PFWin w[NPL];
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) w[i] = pf_load(Lc[c].b, tb.base + off[i], L.sw);  // all in flight before the first use
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+          const bool in = slot0 + 64 * WPP * i < n;
+          const float iv = pf_blend(w[i], tb);
+          float r = T[c][i] - iv;
+          r = in ? r : 0.0f;  // (T = 0 there, but the frame value is not)
+          if constexpr (ROBUST) r = fminf(fmaxf(r, -huber_k), huber_k);
+          b[0] += Gx[c][i] * r;
+          if constexpr (!XONLY) b[1] += Gy[c][i] * r;
+          if constexpr (MEAN) b[NB + c] += in ? iv : 0.0f;
+        }
+      }
+      pf_patch_sum<WPP>(b, sSum);
+      if constexpr (MEAN) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const float mi = b[NB + c] / (float)n;
+          b[0] = b[0] + mi * sg[NB * c];
+          if constexpr (!XONLY) b[1] = b[1] + mi * sg[NB * c + 1];
+        }
       }
     }
     if (run) {

@@ -657,9 +657,47 @@ def _csum(vals):
     return s
 
 
-def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm=False):
+C2F_COST_L2, C2F_COST_HUBER = 0, 2  # ICTR_C2F_COST_*: the cost field of OF_DIS's parameter string as remembered (1 is L1)
+
+
+def _c2f_cost(cost, huber_k, who="c2f flow"):
+    """(ICTR_C2F_COST_* code, huber_k as a float) of the keywords cost ("l2" | "huber", or the code 0 | 2) and huber_k
+    (finite and > 0, checked for both costs); ValueError otherwise, for L1 with the reason."""
+    if cost in ("l1", "L1") or (not isinstance(cost, str) and cost == 1):
+        raise ValueError(f"{who}: cost L1 (code 1) is not built: with H fixed its influence sign(r) has no scale; "
+                         "use cost='huber' with a small huber_k")
+    if isinstance(cost, str):
+        code = {"l2": C2F_COST_L2, "huber": C2F_COST_HUBER}.get(cost)
+    else:
+        code = cost if cost in (C2F_COST_L2, C2F_COST_HUBER) and int(cost) == cost else None
+    if code is None:
+        raise ValueError(f"{who}: cost is {cost!r} ('l2' or 'huber')")
+    try:
+        k = float(huber_k)
+    except (TypeError, ValueError):
+        k = float("nan")
+    if not (np.isfinite(k) and k > 0):
+        raise ValueError(f"{who}: huber_k is {huber_k!r}; it must be finite and > 0")
+    return int(code), k
+
+
+def _c2f_clip(r, huber_k, clipped=None):
+    """The Huber cost's residual: r clipped to [-huber_k, +huber_k] (the derivative of the Huber loss); None: r (L2).
+    clipped: a two-item list that counts the residuals the clip changed and all residuals."""
+    if huber_k is None:
+        return r
+    if clipped is not None:
+        clipped[0] += int((np.abs(r) > huber_k).sum())
+        clipped[1] += r.size
+    return np.clip(r, -huber_k, huber_k)
+
+
+def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm=False, huber_k=None, _clipped=None):
     """Step 3 of c2f_flow_host at level l from the starts `init` (ny, nx, 2) float32. patnorm: patch-mean normalisation,
-    T <- T - mean(T) once and r = T - (I - mean(I)) in every iteration, nothing else changed. A colour frame (three
+    T <- T - mean(T) once and r = T - (I - mean(I)) in every iteration, nothing else changed. huber_k (None: the L2 cost):
+    the Huber patch cost (DESIGN.md "Robust patch cost"), every pixel's and channel's residual r <- clip(r, -huber_k,
+    +huber_k) in every iteration, after the means are removed under patnorm; T, Gx, Gy, H, the conditioning decision, the
+    view tests, the step, the eps stop and the rejection are unchanged. _clipped: _c2f_clip's counter. A colour frame (three
     pyramids per frame, DESIGN.md "Colour"): T_c, Gx_c, Gy_c are sampled per channel, H = sum_c sum_px G_c G_c^T and
     b = sum_c sum_px G_c r_c with r_c = T_c - I_c (patnorm: each channel less its own means), one conditioning decision
     and one step per node; nothing else changes. Returns (d (ny, nx, 2) float32
@@ -711,7 +749,7 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
                     st = C2F_HELD_VIEW
                     break
                 I = [_c2f_sample(q.img[l], q.pad, psz, cx, cy) for q in pbs]
-                r = [t - (v - v.mean()) if patnorm else t - v for t, v in zip(T, I)]
+                r = [_c2f_clip(t - (v - v.mean()) if patnorm else t - v, huber_k, _clipped) for t, v in zip(T, I)]
                 bx, by = _csum([(g * e).sum() for g, e in zip(Gx, r)]), _csum([(g * e).sum() for g, e in zip(Gy, r)])
                 dx, dy = (hyy * bx - hxy * by) / det, (hxx * by - hxy * bx) / det
                 p += (dx, dy)
@@ -731,14 +769,16 @@ def _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, pa
     return d, status, m
 
 
-def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm=False):
+def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm=False, huber_k=None,
+                       _clipped=None):
     """Step 3 of c2f_flow_host(x_only=True) at level l from the starts `init` (ny, nx, 2) float32 whose y is +0.0: the
     1-D rule of k_patchdisp at this level alone. hxx = sum Gx^2, hyy = sum Gy^2, tr = hxx + hyy; the node is held by
     conditioning iff not tr > 0 or not hxx > min_hx tr; an iteration tests the view at (X + p, Y), samples I there, takes
     dx = sum Gx (T - I) / hxx (patnorm: T - mean(T) and I - mean(I)), p += dx, and stops when dx^2 < eps^2; the rejection
     is not (p - init.x)^2 <= psz^2. y never moves: d = (p, +0.0) when tracked, (init.x, +0.0) when held. Returns what
     _c2f_search_host returns; margins["det"] is | hxx / tr - min_hx |, "eps" | |dx| - eps |, "far" | |p - init.x| - psz |.
-    Colour frames (three pyramids per frame): hxx, hyy and sum Gx r are summed over the channels, as in _c2f_search_host."""
+    Colour frames (three pyramids per frame): hxx, hyy and sum Gx r are summed over the channels, as in _c2f_search_host.
+    huber_k: the Huber patch cost, every residual clipped to [-huber_k, +huber_k] as in _c2f_search_host."""
     pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
     w, h = _c2f_level_size(pas[0], l)
     xs, ys = np.arange(step // 2, w, step), np.arange(step // 2, h, step)
@@ -778,7 +818,7 @@ def _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, p
                     st = C2F_HELD_VIEW
                     break
                 I = [_c2f_sample(q.img[l], q.pad, psz, X + p, float(Y)) for q in pbs]
-                r = [t - (v - v.mean()) if patnorm else t - v for t, v in zip(T, I)]
+                r = [_c2f_clip(t - (v - v.mean()) if patnorm else t - v, huber_k, _clipped) for t, v in zip(T, I)]
                 dx = _csum([(g * e).sum() for g, e in zip(Gx, r)]) / hxx
                 p += dx
                 m["eps"][j, i] = min(m["eps"][j, i], abs(abs(dx) - eps))
@@ -924,7 +964,7 @@ def upsample_flow(field, w, h, lv, x_only=False):
 
 
 def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, min_det=1e-4, densify=None, refine=None,
-                  _stages=None, patnorm=False, x_only=False, min_hx=1e-2, lv_l=0):
+                  _stages=None, patnorm=False, x_only=False, min_hx=1e-2, lv_l=0, cost="l2", huber_k=5.0):
     """Coarse-to-fine dense flow A -> B: the definition (build-defined; NumPy, f64 arithmetic on the f32 planes; DESIGN.md
     §4 "Coarse-to-fine dense flow" states the rule). pyr_a, pyr_b: host pyramids with ``.img / .dx / .dy[l]`` padded by
     ``.pad >= psz`` (oracle.Pyramid's shape). For l = lv_f .. 0: nodes at step // 2 + k step of the level's own size; a
@@ -953,8 +993,17 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     vote weighs the channel mean of the absolute residuals (densify_flow_host on three planes). Three equal channels
     give the grey rule in real arithmetic. The refinement takes the three planes per frame: its steps 1 and 2 run per
     channel and its two robust weights are joint over the channels (refine_flow_host, _fr_coef_rgb).
+    cost ("l2", the default, or "huber"; DESIGN.md "Robust patch cost"): with "huber" the search clips every pixel's and
+    channel's residual of every iteration to [-huber_k, +huber_k] (huber_k in grey levels on the frames' own scale, finite
+    and > 0; its default 5.0 is a choice, not a measurement), after the patch means are removed under patnorm. That is
+    the derivative of the Huber loss with H left as the template's. T, Gx, Gy, H, the conditioning decision, the view
+    tests, the step, the eps stop, the rejection, the status values, the node bias, the densifier and the refinement are
+    unchanged. L1 (OF_DIS's cost code 1) is refused: with H fixed its influence sign(r) has no scale.
     _stages: a list that receives one dict per level from lv_f down: "level", "init", "d" (after the fill), "status",
-    "margins" (_c2f_search_host's), "field" (U_l) and "bias" (the node bias, None without patnorm)."""
+    "margins" (_c2f_search_host's), "field" (U_l), "bias" (the node bias, None without patnorm) and "clipped" (with
+    cost="huber": the count of residuals the clip changed and of all residuals of the level's iterations)."""
+    code, huber_k = _c2f_cost(cost, huber_k, "c2f_flow_host")
+    hk = huber_k if code == C2F_COST_HUBER else None
     pas, pbs = _c2f_channels(pyr_a), _c2f_channels(pyr_b)
     if len(pas) != len(pbs):
         raise ValueError("c2f flow: one frame is grey and the other colour")
@@ -968,10 +1017,13 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
     for l in range(lv_f, lv_l - 1, -1):
         w, h = _c2f_level_size(pas[0], l)
         init = _c2f_init(U, w, h, step, x_only)
+        clipped = [0, 0]
         if x_only:
-            d, status, margins = _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm)
+            d, status, margins = _c2f_search_x_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_hx, patnorm, hk,
+                                                    clipped)
         else:
-            d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm)
+            d, status, margins = _c2f_search_host(pyr_a, pyr_b, l, init, step, psz, maxiter, eps, min_det, patnorm, hk,
+                                                  clipped)
         lost = status == C2F_LOST
         bias = _c2f_bias_host(pyr_a, pyr_b, l, d, status, step, psz, margins) if patnorm else None
         A, B = _c2f_plane(pas[0], l), _c2f_plane(pbs[0], l)
@@ -984,7 +1036,8 @@ def c2f_flow_host(pyr_a, pyr_b, step=4, psz=8, lv_f=None, maxiter=10, eps=0.01, 
         if _stages is not None:
             filled = d.copy()
             _dense_from_nodes(filled, lost, w, h, step)
-            _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U, bias=bias))
+            _stages.append(dict(level=l, init=init, d=filled, status=status, margins=margins, field=U, bias=bias,
+                                clipped=tuple(clipped) if hk is not None else None))
     if lv_l > 0:
         w0, h0 = _c2f_level_size(pas[0], 0)
         return upsample_flow_host(U, w0, h0, lv_l, bool(x_only))
@@ -1001,12 +1054,14 @@ class CoarseToFineFlow:
     k_flow_upsample from level lv_l's field into the object's w x h result plane, which ``dense`` and ``device_ptr`` then
     hand out. channels: 1 (grey frames, one pyramid each) or 3 (colour frames, c2f_flow_host's rule on triples: ``run``
     then takes two sequences of three pyramids, k_c2f_level's, k_densify's and k_fr_warp's NCH = 3 forms and
-    k_fr_coef_rgb run, and ``level_bias`` is (ny, nx, 3)). ``run`` enqueues and returns; ``dense``
+    k_fr_coef_rgb run, and ``level_bias`` is (ny, nx, 3)). cost, huber_k: c2f_flow_host's patch cost ("huber":
+    k_c2f_level's ROBUST forms; ``.cost`` is "l2" or "huber", ``.huber_k`` the float the object holds). ``run`` enqueues and returns; ``dense``
     (the w x h field), ``level`` and ``level_bias`` wait. The object is a device ICTR_FIELD_FLOW wherever a FlowDensifier is one."""
 
     def __init__(self, w, h, lv_f, step=4, psz=8, maxiter=10, eps=0.01, densify=None, refine=None, patnorm=False,
-                 x_only=False, lv_l=0, channels=1):
+                 x_only=False, lv_l=0, channels=1, cost="l2", huber_k=5.0):
         dz = dict(DENSIFY_DEFAULTS, **(densify or {}))
+        code, huber_k = _c2f_cost(cost, huber_k, "CoarseToFineFlow")
         if channels not in (1, 3):
             raise ValueError(f"CoarseToFineFlow: channels is {channels} (1: grey, or 3: colour)")
         unknown = set(dz) - set(DENSIFY_DEFAULTS) | (set(refine or {}) - set(REFINE_DEFAULTS))
@@ -1037,6 +1092,26 @@ class CoarseToFineFlow:
         self.channels = int(channels)
         if self.channels != 1:
             check(L.ictr_c2fflow_set_channels(self._h, self.channels))
+        if code != C2F_COST_L2:  # (an L2 object makes the calls it made before the cost existed)
+            check(L.ictr_c2fflow_set_cost(self._h, code, huber_k))
+
+    @property
+    def cost(self):
+        return "huber" if self._get_cost()[0] == C2F_COST_HUBER else "l2"
+
+    @property
+    def huber_k(self):
+        return self._get_cost()[1]
+
+    def _get_cost(self):
+        code, k = C.c_int(), C.c_float()
+        check(_lib.load().ictr_c2fflow_get_cost(self._h, C.byref(code), C.byref(k)))
+        return int(code.value), float(k.value)
+
+    def set_cost(self, cost="l2", huber_k=5.0):
+        """The patch cost of the runs that follow; a refused call leaves the object as it was."""
+        code, k = _c2f_cost(cost, huber_k, "CoarseToFineFlow.set_cost")
+        check(_lib.load().ictr_c2fflow_set_cost(self._h, code, k))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -1110,7 +1185,7 @@ class CoarseToFineFlow:
 
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):
     """c2f_flow_host's result from the device: device pyramids in, a host array out, one CoarseToFineFlow for the call
-    (params: its keywords, patnorm, x_only and lv_l among them)."""
+    (params: its keywords, patnorm, x_only, lv_l, cost and huber_k among them)."""
     first = pyr_a if hasattr(pyr_a, "_h") else pyr_a[0]
     if first is not pyr_a:
         params.setdefault("channels", 3)

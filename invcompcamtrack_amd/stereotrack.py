@@ -307,11 +307,13 @@ class StereoPointTracker:
     lv_f .. lv_l run and the field of level lv_l is up-sampled to the frame); above 0 it likewise needs flow="c2f" or
     "c2f-1d". colour=True (likewise flow="c2f" or "c2f-1d" alone): push_frames takes (h, w, 3) frames and holds three
     pyramids per side, one per channel, and every object is a CoarseToFineFlow(channels=3); the fields the window reads
-    are the same w x h flow planes."""
+    are the same w x h flow planes. cost="huber" (with huber_k, default 5.0 grey levels) searches every coarse-to-fine
+    field with the Huber patch cost (CoarseToFineFlow's cost and huber_k); it likewise needs flow="c2f" or "c2f-1d" and is
+    refused with flow="grid", whose whole-pyramid kernels have no such form."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
                  xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False,
-                 lv_l=0, colour=False):
+                 lv_l=0, colour=False, cost="l2", huber_k=5.0):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         if flow not in ("grid", "c2f", "c2f-1d"):
@@ -328,6 +330,12 @@ class StereoPointTracker:
         if colour and flow not in ("c2f", "c2f-1d"):
             raise ValueError("colour=True needs flow='c2f' or 'c2f-1d': colour frames are built for the coarse-to-fine flow "
                              "alone, not for the flow grids of flow='grid'")
+        from .patchflow import C2F_COST_HUBER, _c2f_cost
+        code, self.huber_k = _c2f_cost(cost, huber_k, "StereoPointTracker")
+        self.cost = "huber" if code == C2F_COST_HUBER else "l2"
+        if self.cost == "huber" and flow not in ("c2f", "c2f-1d"):
+            raise ValueError("cost='huber' needs flow='c2f' or 'c2f-1d': the robust patch cost is built for the "
+                             "coarse-to-fine flow alone, not for the flow grids of flow='grid'")
         self.flow = flow
         self.colour = bool(colour)
         self.lv_l = int(lv_l)
@@ -432,7 +440,8 @@ class StereoPointTracker:
         def make(x_only=False):
             return CoarseToFineFlow(self.w, self.h, self.lv_f, self.step, self.psz, self.maxiter, self.eps,
                                     densify=self.densify, refine=self.refine, patnorm=self.patnorm, x_only=x_only,
-                                    lv_l=self.lv_l, channels=3 if self.colour else 1)
+                                    lv_l=self.lv_l, channels=3 if self.colour else 1, cost=self.cost,
+                                    huber_k=self.huber_k)
 
         if self.flow == "c2f-1d":
             c = dict(self._set(self._fsets, k, make, ("l_fwd", "l_bwd", "r_fwd", "r_bwd")))

@@ -49,6 +49,14 @@ Nothing but the comparison with the parent, for a change that must leave every p
 grey (psz 8 and 15), FlowDensifier.run (psz 15), FlowRefiner.run at its defaults on the densifier's field, and
 CoarseToFineFlow(channels=3).run with patnorm and the refinement on (psz 8 and 15), in child processes of the two builds in
 turn (two each), with the same bar.
+
+  python tools/c2fflow_bench.py --cost [--reps 7] [--out profiles/c2fflow_cost_bench.json] [--parent-root DIR]
+
+The Huber patch cost next to L2: per shape and patch size, with patnorm off and on, two objects, cost "l2" and "huber"
+(huber_k 5), run in turn; per level the search medians of each with the Huber / L2 ratio of every round (minimum / median /
+maximum), and the whole runs likewise. Recorded without a bar. --parent-root measures the paths the cost must leave alone:
+CoarseToFineFlow.run at L2 (psz 8 and 15, patnorm off and on) and FlowGrid.compute and compute_x (psz 15), whose kernels
+include the changed header, with the same bar.
 """
 import argparse
 import json
@@ -104,7 +112,8 @@ def default_child(root, reps):
 
 
 def option_child(root, reps, option):
-    """Runs in a child process: CoarseToFineFlow.run (no keyword of the option: the parent has none) and, for "patnorm",
+    """Runs in a child process: CoarseToFineFlow.run (no keyword of the option: the parent has none) and, for "cost", the
+    same with patnorm on and FlowGrid.compute and compute_x, for "patnorm",
     FlowDensifier.run, for "x_only" FlowGrid.compute_x on the stereo pair (for "lv_l" nothing more), for "fold"
     FlowDensifier.run, FlowRefiner.run and the colour run with patnorm and the refinement (the parent has them), of the
     tree at `root`, HIP events around each."""
@@ -123,7 +132,17 @@ def option_child(root, reps, option):
             pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(second, LV_F, psz, True)
             c = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz)
             rec[f"c2f_run_psz{psz}_ms"] = [float(_timed(torch, lambda: c.run(pa, pb))) for _ in range(reps + 1)][1:]
-            if psz == PSZS[1] and option == "x_only":
+            if option == "cost":
+                cp = pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, patnorm=True)
+                rec[f"c2f_patnorm_run_psz{psz}_ms"] = [float(_timed(torch, lambda: cp.run(pa, pb)))
+                                                       for _ in range(reps + 1)][1:]
+                if psz == PSZS[1]:
+                    grid = pf.FlowGrid(w, h, STEP)
+                    rec["flowgrid_compute_ms"] = [float(_timed(torch, lambda: grid.compute(pa, pb, psz=psz, lv_f=LV_F)))
+                                                  for _ in range(reps + 1)][1:]
+                    rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
+                                                    for _ in range(reps + 1)][1:]
+            elif psz == PSZS[1] and option == "x_only":
                 grid = pf.FlowGrid(w, h, STEP)
                 rec["flowgrid_compute_x_ms"] = [float(_timed(torch, lambda: grid.compute_x(pa, pb, psz=psz, lv_f=LV_F)))
                                                 for _ in range(reps + 1)][1:]
@@ -243,6 +262,55 @@ def lvl_main(a):
     return 0 if ok else 1
 
 
+def cost_main(a):
+    """--cost: L2 and Huber objects in turn, with patnorm off and on, then the L2 paths against the parent's."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import invcompcamtrack_amd as ic
+    from invcompcamtrack_amd import patchflow as pf
+    from tools.patchdisp_bench import frames, stats
+    if ic.device_count() < 1:
+        raise SystemExit("no HIP device: nothing is measured without one")
+    out = {"bench": "c2fflow_cost", "step": STEP, "lv_f": LV_F, "reps": a.reps, "huber_k": 5.0,
+           "densify": pf.DENSIFY_DEFAULTS, "refine": None, "shapes": []}
+    ratio = lambda hu, l2: {k: round(float(f(np.asarray(hu) / np.asarray(l2))), 3)
+                            for k, f in (("min", np.min), ("median", np.median), ("max", np.max))}
+    ok = True
+    for w, h in SHAPES:
+        fr = frames(w, h)
+        for psz in PSZS:
+            pa, pb = ic.Pyramid(fr[0][0], LV_F, psz, True), ic.Pyramid(fr[1][0], LV_F, psz, True)
+            for patnorm in (False, True):
+                cs = {cost: pf.CoarseToFineFlow(w, h, LV_F, STEP, psz, patnorm=patnorm, cost=cost) for cost in ("l2", "huber")}
+                levels, total = {c: [] for c in cs}, {c: [] for c in cs}
+                for rep in range(a.reps + 1):  # the first round warms everything up
+                    for cost, c in cs.items():
+                        c.set_timing(True)
+                        tt = _timed(torch, lambda: c.run(pa, pb))
+                        if rep:
+                            levels[cost].append(c.kernel_ms())
+                            total[cost].append(float(tt))
+                lv = {c: np.stack(v) for c, v in levels.items()}  # [rep][level][search, densify, refine]
+                rec = {"w": w, "h": h, "psz": psz, "patnorm": patnorm, "levels": [],
+                       "total_ms": {c: stats(total[c]) for c in cs},
+                       "total_huber_over_l2": ratio(total["huber"], total["l2"])}
+                for l in range(LV_F, -1, -1):
+                    lw, lh, nx, ny = cs["l2"].level_dims(l)
+                    rec["levels"].append({"level": l, "w": lw, "h": lh, "nodes": nx * ny,
+                                          "search_ms": {c: stats(lv[c][:, l, 0]) for c in cs},
+                                          "search_huber_over_l2": ratio(lv["huber"][:, l, 0], lv["l2"][:, l, 0])})
+                out["shapes"].append(rec)
+                print(json.dumps(rec), flush=True)
+    if a.parent_root:
+        ok &= _option_against_parent(a, "cost", out)
+    with open(a.out or os.path.join(ROOT, "profiles", "c2fflow_cost_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
+
+
 def option_main(a, option):
     """--patnorm / --x-only: the option off and on in turn, then the default paths against the parent's."""
     sys.path.insert(0, ROOT)
@@ -310,7 +378,8 @@ def main():
     ap.add_argument("--colour", action="store_true", help="measure colour frames against grey ones instead")
     ap.add_argument("--option-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--fold", action="store_true", help="compare every flow path with the parent's instead")
-    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l", "colour", "fold"),
+    ap.add_argument("--cost", action="store_true", help="measure the Huber patch cost against L2 instead")
+    ap.add_argument("--option", default="patnorm", choices=("patnorm", "x_only", "lv_l", "colour", "fold", "cost"),
                     help=argparse.SUPPRESS)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--default-child", default=None, help=argparse.SUPPRESS)
@@ -325,6 +394,8 @@ def main():
         return fold_main(a)
     if a.lv_l:
         return lvl_main(a)
+    if a.cost:
+        return cost_main(a)
     if a.patnorm or a.x_only or a.colour:
         return option_main(a, "x_only" if a.x_only else "colour" if a.colour else "patnorm")
     a.out = a.out or os.path.join(ROOT, "profiles", "c2fflow_bench.json")
