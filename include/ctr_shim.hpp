@@ -635,9 +635,56 @@ class CoarseFlowClass {
   void ReadLevelBiasRGB(int level, float *bias) {
     check(ictr_c2fflow_read_level_bias_rgb(h_, level, bias), "ReadLevelBiasRGB");
   }
+  ictr_c2fflow *handle() const { return h_; }  // for CoarseFlowSet
 
  private:
   ictr_c2fflow *h_;
+};
+
+// 1 .. ICTR_C2FSET_MAX CoarseFlowClass objects of equal shape and parameters run in lockstep, one launch per level and
+// stage for all of them (ictr_c2fset_* in include/ictr_c2f_set.h): Run leaves every member as its own Run on its pair would
+// have, bit for bit. The members are the caller's and outlive the set; a refused call throws with the library's message,
+// which names the member and the field.
+class CoarseFlowSet {
+ public:
+  CoarseFlowSet(CoarseFlowClass *const *members, int n) : h_(nullptr), n_(n) {
+    ictr_c2fflow *m[ICTR_C2FSET_MAX] = {};
+    for (int i = 0; i < n && i < ICTR_C2FSET_MAX; ++i) m[i] = members[i] ? members[i]->handle() : nullptr;
+    check(ictr_c2fset_create(&h_, m, n), "CoarseFlowSet");
+  }
+  ~CoarseFlowSet() { ictr_c2fset_destroy(h_); }
+  CoarseFlowSet(const CoarseFlowSet &) = delete;
+  CoarseFlowSet &operator=(const CoarseFlowSet &) = delete;
+  int Size() const {
+    int n = 0;
+    check(ictr_c2fset_size(h_, &n), "Size");
+    return n;
+  }
+  // a[m], b[m]: member m's frames (grey members)
+  void Run(const Pyramid *const *a, const Pyramid *const *b, void *hip_stream = nullptr) {
+    const ictr_pyramid *pa[ICTR_C2FSET_MAX], *pb[ICTR_C2FSET_MAX];
+    for (int i = 0; i < n_; ++i) pa[i] = a[i]->handle(), pb[i] = b[i]->handle();
+    check(ictr_c2fset_run(h_, pa, pb, hip_stream), "CoarseFlowSet::Run");
+  }
+  // a[3 * m + ch], b[3 * m + ch]: channel ch of member m's frames (3-channel members)
+  void RunRGB(const Pyramid *const *a, const Pyramid *const *b, void *hip_stream = nullptr) {
+    const ictr_pyramid *pa[3 * ICTR_C2FSET_MAX], *pb[3 * ICTR_C2FSET_MAX];
+    for (int i = 0; i < 3 * n_; ++i) pa[i] = a[i]->handle(), pb[i] = b[i]->handle();
+    check(ictr_c2fset_run_rgb(h_, pa, pb, hip_stream), "CoarseFlowSet::RunRGB");
+  }
+  // kernel launches plus memsets of the last run: the same for any number of members
+  int Operations() const {
+    int ops = 0;
+    check(ictr_c2fset_last_operations(h_, &ops), "Operations");
+    return ops;
+  }
+  void SetTiming(bool on) { check(ictr_c2fset_set_timing(h_, on ? 1 : 0), "SetTiming"); }
+  // ms [lv_f + 1][3], upsample_ms (may be NULL): ictr_c2fset_get_kernel_ms
+  void KernelMs(float *ms, float *upsample_ms = nullptr) { check(ictr_c2fset_get_kernel_ms(h_, ms, upsample_ms), "KernelMs"); }
+
+ private:
+  ictr_c2fset *h_;
+  int n_;
 };
 
 // A field of level lv of a w x h pyramid at the frame's size (ictr_flow_upsample): src [h_l][w_l][2], out [h][w][2], both

@@ -1065,6 +1065,9 @@ int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, float *bias);
 /* -- the patch cost of the search (DESIGN.md §4 "Robust patch cost"): ictr_c2fflow_set_cost, ictr_c2fflow_get_cost,
  * ICTR_C2F_COST_L2, ICTR_C2F_COST_HUBER */
 #include "ictr_c2f_cost.h"
+/* -- a lockstep set of coarse-to-fine flows, one launch per stage for all members (DESIGN.md §4 "Lockstep sets"):
+ * ictr_c2fset_create, _destroy, _run, _run_rgb, _size, _last_operations, _set_timing, _get_kernel_ms */
+#include "ictr_c2f_set.h"
 
 #ifdef __cplusplus
 }

@@ -376,6 +376,17 @@ SIGNATURES_COST = {
     "ictr_c2fflow_set_cost": (C.c_int, [VP, C.c_int, C.c_float]),
     "ictr_c2fflow_get_cost": (C.c_int, [VP, C.POINTER(C.c_int), FP]),
 }
+# a lockstep set of coarse-to-fine flows, declared in include/ictr_c2f_set.h (which ictr.h includes)
+SIGNATURES_SET = {
+    "ictr_c2fset_create": (C.c_int, [C.POINTER(VP), C.POINTER(VP), C.c_int]),
+    "ictr_c2fset_destroy": (None, [VP]),
+    "ictr_c2fset_run": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
+    "ictr_c2fset_run_rgb": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP), VP]),
+    "ictr_c2fset_size": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fset_last_operations": (C.c_int, [VP, C.POINTER(C.c_int)]),
+    "ictr_c2fset_set_timing": (C.c_int, [VP, C.c_int]),
+    "ictr_c2fset_get_kernel_ms": (C.c_int, [VP, FP, FP]),
+}
 # the other three entry points that keep the reference library's mixed-case names (declared in include/ictr.h as well)
 SIGNATURES_REFERENCE_NAMES = {
     "ictr_triangulate_DLT": (C.c_int, [FP, FP, FP, FP, C.c_int]),
@@ -425,7 +436,7 @@ def load():
     except OSError as exc:  # e.g. libamdhip64 missing
         raise IctrError(f"cannot load {LIB_PATH}: {exc}") from exc
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_REFERENCE_NAMES.items())
-                              + list(SIGNATURES_COST.items())):
+                              + list(SIGNATURES_COST.items()) + list(SIGNATURES_SET.items())):
         fn = getattr(L, name)  # AttributeError here means the .so is stale w.r.t. include/ictr.h
         fn.restype = res
         fn.argtypes = args

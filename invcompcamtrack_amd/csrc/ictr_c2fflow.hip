@@ -40,6 +40,7 @@
 #include <string.h>
 
 #include <memory>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -51,35 +52,11 @@
 
 namespace ictr {
 
-// s = 2^lv, inv_s = 2^-lv. Everything before the taps is exact in f32 (x + 0.5, the product with 2^-lv, - 0.5, rx,
-// 1 - rx); the six products and three sums are taken in the order written, each rounded (no contraction), then s * val.
+// the body: flow_upsample_body of ictr_c2fflow_dev.h, which the lockstep twin (ictr_c2fset.hip) shares
 template <bool XONLY>
 __global__ __launch_bounds__(kBlock) void k_flow_upsample(const float2 *__restrict__ src, int wl, int hl, float inv_s,
                                                           float s, float2 *__restrict__ out, int w, int h) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (x >= w || y >= h) return;
-  const float fx = fminf(fmaxf(((float)x + 0.5f) * inv_s - 0.5f, 0.0f), (float)(wl - 1));
-  const float fy = fminf(fmaxf(((float)y + 0.5f) * inv_s - 0.5f, 0.0f), (float)(hl - 1));
-  const int x0 = (int)fx, y0 = (int)fy;  // fx, fy >= 0: the cast is the floor
-  const int x1 = min(x0 + 1, wl - 1), y1 = min(y0 + 1, hl - 1);
-  const float rx = fx - (float)x0, ry = fy - (float)y0;
-  const float qx = 1.0f - rx, qy = 1.0f - ry;
-  const size_t r0 = (size_t)y0 * wl, r1 = (size_t)y1 * wl;
-  float2 o;
-  if constexpr (XONLY) {  // y is not read and is +0.0
-    const float *f = reinterpret_cast<const float *>(src);
-    const float top = qx * f[2 * (r0 + x0)] + rx * f[2 * (r0 + x1)];
-    const float bot = qx * f[2 * (r1 + x0)] + rx * f[2 * (r1 + x1)];
-    o.x = s * (qy * top + ry * bot);
-    o.y = 0.0f;
-  } else {
-    const float2 a = src[r0 + x0], b = src[r0 + x1], c = src[r1 + x0], d = src[r1 + x1];
-    const float tx = qx * a.x + rx * b.x, bx = qx * c.x + rx * d.x;
-    const float ty = qx * a.y + rx * b.y, by = qx * c.y + rx * d.y;
-    o.x = s * (qy * tx + ry * bx);
-    o.y = s * (qy * ty + ry * by);
-  }
-  out[(size_t)y * w + x] = o;
+  flow_upsample_body<XONLY>(src, wl, hl, inv_s, s, out, w, h);
 }
 
 // src [hl][wl][2] and out [h][w][2] on the device; the caller has checked the sizes
@@ -120,6 +97,9 @@ struct C2fLevel {
   Event ev[4];                                    // before the search, after the fill, the densifier, the refiner
 };
 }  // namespace
+
+constexpr int kC2fMaxLevels = 16;  // levels 0 .. 15: the level table of a patch search (PFArgs) holds as many
+static_assert(kC2fMaxLevels == sizeof(PFArgs::lv) / sizeof(PFLevel), "the levels of a coarse-to-fine flow are PFArgs' levels");
 
 struct ictr_c2fflow {
   int w = 0, h = 0, lv_f = 0, lv_l = 0, step = 0, psz = 0;
@@ -177,7 +157,7 @@ extern "C" int ictr_c2fflow_create(ictr_c2fflow **out, int w, int h, int lv_f, i
   return ictr_c2fflow_create_lvl(out, w, h, lv_f, 0, step, psz);
 }
 extern "C" int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_f, int lv_l, int step, int psz) {
-  if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f > 15 || step < 1)
+  if (!out || w < 1 || h < 1 || lv_f < 0 || lv_f >= kC2fMaxLevels || step < 1)
     return fail(ICTR_ERR_INVALID, "c2fflow: bad arguments (w, h, step >= 1, 0 <= lv_f <= 15)");
   if (psz < 1 || psz > 32) return fail(ICTR_ERR_INVALID, "c2fflow: psz is %d (1 .. 32)", psz);
   if (lv_l < 0 || lv_l > lv_f) return fail(ICTR_ERR_INVALID, "c2fflow: lv_l is %d (0 .. lv_f = %d)", lv_l, lv_f);
@@ -298,12 +278,13 @@ extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   return ICTR_OK;
 }
 
-// level l's search of a run: pfc[ch] the level tables of the channels' pyramids, which agree in geometry
+// the kernel arguments of level l's search of a run: pfc[ch] the level tables of the channels' pyramids, which agree in
+// geometry
 template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
-static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, hipStream_t s) {
+static int c2f_search_args(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, C2fArgsOf<MEAN, NCH, ROBUST> *out) {
   const C2fLevel &L = c->lv[l];
   const PFArgs &pf = pfc[0];
-  C2fArgsOf<MEAN, NCH, ROBUST> a;
+  C2fArgsOf<MEAN, NCH, ROBUST> &a = *out;
   memset(&a, 0, sizeof(a));
   for (int ch = 0; ch < NCH; ++ch)
     a.a[ch] = pfc[ch].lv[l].a, a.ax[ch] = pfc[ch].lv[l].ax, a.ay[ch] = pfc[ch].lv[l].ay, a.b[ch] = pfc[ch].lv[l].b;
@@ -328,6 +309,14 @@ static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refin
   a.status = L.status;
   if constexpr (MEAN) a.bias = L.bias;
   if constexpr (ROBUST) a.huber_k = c->huber_k;
+  return ICTR_OK;
+}
+// level l's search of a run
+template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
+static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, hipStream_t s) {
+  const C2fLevel &L = c->lv[l];
+  C2fArgsOf<MEAN, NCH, ROBUST> a;
+  if (int rc = c2f_search_args<MEAN, XONLY, NCH, ROBUST>(c, pfc, l, refined, &a)) return rc;
   if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
   if constexpr (ROBUST)
     launch_c2f_level_robust(a, XONLY, s);  // (instantiated in ictr_c2fflow_robust.hip)
@@ -347,11 +336,11 @@ using C2fSearch = int (*)(const ictr_c2fflow *, const PFArgs *, int, int, hipStr
 static const C2fSearch kC2fSearch[2][2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
 #undef ICTR_C2F_FORMS
 
-// a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
-static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
-                   void *hip_stream) {
+// the argument checks of a run and pfc[ch], the level tables of a patch search on the channels' pyramids: pads, gradient
+// planes, equal sizes; `who` opens the messages
+static int c2f_run_args(const ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b,
+                        const char *who, PFArgs *pfc) {
   const int nch = c->channels;
-  PFArgs pfc[3];  // the argument checks and the level table of a patch search: pads, gradient planes, equal sizes
   for (int ch = 0; ch < nch; ++ch)
     if (int rc = patchflow_args(pyr_a[ch], pyr_b[ch], c->psz, c->lv_f, 0, c->maxiter, c->eps, &pfc[ch])) return rc;
   const PFArgs &pf = pfc[0];
@@ -363,8 +352,16 @@ static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr
                     ch);
   for (int l = 0; l <= c->lv_f; ++l)
     if ((int)pf.lv[l].swo != c->lv[l].w || (int)pf.lv[l].sho != c->lv[l].h)
-      return fail(ICTR_ERR_INVALID, "c2fflow_run: level %d of the pyramids is %d x %d, of the object %d x %d", l,
+      return fail(ICTR_ERR_INVALID, "%s: level %d of the pyramids is %d x %d, of the object %d x %d", who, l,
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
+  return ICTR_OK;
+}
+// a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
+static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
+                   void *hip_stream) {
+  const int nch = c->channels;
+  PFArgs pfc[3];
+  if (int rc = c2f_run_args(c, pyr_a, pyr_b, who, pfc)) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
   const int robust = c->cost == ICTR_C2F_COST_HUBER;
@@ -537,5 +534,257 @@ extern "C" int ictr_flow_upsample(const float *src, int w_l, int h_l, int lv, fl
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, dout.get(), nout, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  return ICTR_OK;
+}
+
+// ---------------------------------------------------------------- lockstep sets (include/ictr_c2f_set.h)
+// A set of coarse-to-fine flows of equal shape and parameters, run in lockstep (DESIGN.md §4 "Lockstep sets"): c2f_run's
+// walk over the levels with every stage enqueued once, through the lockstep twins of the kernels. The set holds its
+// members' addresses and owns what no member can: the rowhas block of the fill for all members, the events of a timed
+// run, and the event behind the last run.
+static_assert(ICTR_C2FSET_MAX == kSetMax, "ictr_c2f_set.h and ictr_dev.h disagree on the members of a set");
+struct ictr_c2fset {
+  int n = 0;
+  ictr_c2fflow *m[kSetMax] = {};
+  int timing = 0, timed = 0, ran = 0, ops = 0;
+  DevBuf<int> rowhas;  // [n][the most node rows of a level]
+  Event ev[kC2fMaxLevels][4];  // per level: before the search, after the fill, the densifier, the refiner
+  Event up_done, done;
+};
+
+// the refusals of members that are missing, doubled or differ from member 0; `who` opens the message
+static int c2fset_compare(ictr_c2fflow *const *m, int n, const char *who) {
+  if (!m) return fail(ICTR_ERR_INVALID, "%s: members is NULL", who);
+  if (n < 1 || n > kSetMax) return fail(ICTR_ERR_INVALID, "%s: n is %d (1 .. %d)", who, n, kSetMax);
+  for (int i = 0; i < n; ++i) {
+    if (!m[i]) return fail(ICTR_ERR_INVALID, "%s: member %d is NULL", who, i);
+    for (int j = 0; j < i; ++j)
+      if (m[j] == m[i]) return fail(ICTR_ERR_INVALID, "%s: member %d is the same object as member %d", who, i, j);
+  }
+  const ictr_c2fflow *a = m[0];
+  for (int i = 1; i < n; ++i) {
+    const ictr_c2fflow *b = m[i];
+    const struct {
+      const char *name;
+      double vb, va;
+    } f[] = {{"w", (double)b->w, (double)a->w},
+             {"h", (double)b->h, (double)a->h},
+             {"lv_f", (double)b->lv_f, (double)a->lv_f},
+             {"lv_l", (double)b->lv_l, (double)a->lv_l},
+             {"step", (double)b->step, (double)a->step},
+             {"psz", (double)b->psz, (double)a->psz},
+             {"maxiter", (double)b->maxiter, (double)a->maxiter},
+             {"eps", (double)b->eps, (double)a->eps},
+             {"refine", (double)b->refine, (double)a->refine},
+             {"patnorm", (double)b->patnorm, (double)a->patnorm},
+             {"x_only", (double)b->x_only, (double)a->x_only},
+             {"channels", (double)b->channels, (double)a->channels},
+             {"cost", (double)b->cost, (double)a->cost},
+             {"huber_k", (double)b->huber_k, (double)a->huber_k}};
+    for (const auto &e : f)
+      if (!(e.vb == e.va))
+        return fail(ICTR_ERR_INVALID, "%s: member %d differs from member 0 in %s (%g, member 0 has %g)", who, i, e.name, e.vb,
+                    e.va);
+    // the stages' parameters are those of every level of an object: the finest stands for all
+    float ea = 0.0f, eb = 0.0f;
+    int pa = 0, pb = 0;
+    if (int rc = ictr_flowdensify_get_params_(a->lv[a->lv_l].dens.get(), &ea, &pa)) return rc;
+    if (int rc = ictr_flowdensify_get_params_(b->lv[b->lv_l].dens.get(), &eb, &pb)) return rc;
+    if (!(ea == eb))
+      return fail(ICTR_ERR_INVALID, "%s: member %d differs from member 0 in the densifier's minerr (%g, member 0 has %g)", who,
+                  i, (double)eb, (double)ea);
+    if (pa != pb)
+      return fail(ICTR_ERR_INVALID, "%s: member %d differs from member 0 in the densifier's power (%d, member 0 has %d)", who,
+                  i, pb, pa);
+    if (a->refine) {
+      static const char *const fname[4] = {"alpha", "gamma", "delta", "omega"}, *const iname[2] = {"n_outer", "n_sor"};
+      float fa[4], fb[4];
+      int ia[2], ib[2];
+      if (int rc = ictr_flowrefine_get_params_(a->lv[a->lv_l].ref.get(), fa, ia)) return rc;
+      if (int rc = ictr_flowrefine_get_params_(b->lv[b->lv_l].ref.get(), fb, ib)) return rc;
+      for (int k = 0; k < 4; ++k)
+        if (!(fa[k] == fb[k]))
+          return fail(ICTR_ERR_INVALID, "%s: member %d differs from member 0 in the refinement's %s (%g, member 0 has %g)", who,
+                      i, fname[k], (double)fb[k], (double)fa[k]);
+      for (int k = 0; k < 2; ++k)
+        if (ia[k] != ib[k])
+          return fail(ICTR_ERR_INVALID, "%s: member %d differs from member 0 in the refinement's %s (%d, member 0 has %d)", who,
+                      i, iname[k], ib[k], ia[k]);
+    }
+  }
+  return ICTR_OK;
+}
+
+extern "C" void ictr_c2fset_destroy(ictr_c2fset *s) {
+  if (s && s->ran) (void)hipEventSynchronize(s->done.get());  // before the rowhas block of a run in flight is released
+  delete s;
+}
+extern "C" int ictr_c2fset_create(ictr_c2fset **out, ictr_c2fflow *const *members, int n) {
+  if (!out) return fail(ICTR_ERR_INVALID, "c2fset_create: out is NULL");
+  if (int rc = c2fset_compare(members, n, "c2fset_create")) return rc;
+  if (int rc = need_device()) return rc;
+  auto s = std::make_unique<ictr_c2fset>();
+  s->n = n;
+  const ictr_c2fflow *c = members[0];
+  int ny = 1;
+  for (int l = c->lv_l; l <= c->lv_f; ++l) {
+    ny = c->lv[l].ny > ny ? c->lv[l].ny : ny;
+    for (Event &e : s->ev[l])
+      if (int rc = e.create()) return rc;
+  }
+  for (int i = 0; i < n; ++i) s->m[i] = members[i];
+  if (int rc = s->rowhas.alloc(sizeof(int) * (size_t)n * ny, true)) return rc;
+  if (int rc = s->up_done.create()) return rc;
+  if (int rc = s->done.create(hipEventDisableTiming)) return rc;
+  *out = s.release();
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fset_size(const ictr_c2fset *s, int *n) {
+  if (!s || !n) return fail(ICTR_ERR_INVALID, "c2fset_size: the set or n is NULL");
+  *n = s->n;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fset_last_operations(const ictr_c2fset *s, int *ops) {
+  if (!s || !ops) return fail(ICTR_ERR_INVALID, "c2fset_last_operations: the set or ops is NULL");
+  *ops = s->ops;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fset_set_timing(ictr_c2fset *s, int on) {
+  if (!s) return fail(ICTR_ERR_INVALID, "c2fset is NULL");
+  s->timing = on ? 1 : 0;
+  return ICTR_OK;
+}
+
+// level l's search of a lockstep run: pfc[m] the level tables of member m's channels
+template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
+static int c2fset_search(const ictr_c2fset *set, const PFArgs (*pfc)[3], int l, int refined, hipStream_t s) {
+  SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> a;
+  memset(&a, 0, sizeof(a));
+  for (int m = 0; m < set->n; ++m)
+    if (int rc = c2f_search_args<MEAN, XONLY, NCH, ROBUST>(set->m[m], pfc[m], l, refined, &a.m[m])) return rc;
+  launch_c2f_level_set(a, set->n, XONLY, s);  // (instantiated in ictr_c2fset.hip and ictr_c2fset_robust.hip)
+  return ICTR_OK;
+}
+using C2fSetSearch = int (*)(const ictr_c2fset *, const PFArgs (*)[3], int, int, hipStream_t);
+#define ICTR_C2F_FORMS(R)                                                                                                  \
+  {                                                                                                                        \
+    {{c2fset_search<false, false, 1, R>, c2fset_search<false, false, 3, R>},                                               \
+     {c2fset_search<false, true, 1, R>, c2fset_search<false, true, 3, R>}},                                                \
+    {{c2fset_search<true, false, 1, R>, c2fset_search<true, false, 3, R>},                                                 \
+     {c2fset_search<true, true, 1, R>, c2fset_search<true, true, 3, R>}}                                                   \
+  }
+static const C2fSetSearch kC2fSetSearch[2][2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
+#undef ICTR_C2F_FORMS
+
+// a lockstep run on `nch` pyramids per member and frame; everything that can be refused is checked before anything is
+// enqueued or any member touched
+static int c2fset_run(ictr_c2fset *set, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int nch,
+                      const char *who, void *hip_stream) {
+  if (!set) return fail(ICTR_ERR_INVALID, "%s: the set is NULL", who);
+  if (!pyr_a || !pyr_b) return fail(ICTR_ERR_INVALID, "%s: a pyramid table is NULL", who);
+  const int n = set->n;
+  if (int rc = c2fset_compare(set->m, n, who)) return rc;
+  ictr_c2fflow *const c0 = set->m[0];
+  if (c0->channels != nch)
+    return fail(ICTR_ERR_INVALID, "%s: the members have %d channel%s; %s", who, c0->channels, c0->channels == 1 ? "" : "s",
+                nch == 1 ? "a colour run is ictr_c2fset_run_rgb" : "a grey run is ictr_c2fset_run");
+  std::vector<PFArgs> store((size_t)n * 3);
+  PFArgs(*pfc)[3] = reinterpret_cast<PFArgs(*)[3]>(store.data());
+  for (int m = 0; m < n; ++m)
+    if (int rc = c2f_run_args(set->m[m], pyr_a + m * nch, pyr_b + m * nch, who, pfc[m])) {
+      std::string why = ictr_last_error();  // the member's number goes behind the call's name, where the reason opens with it
+      const std::string head = std::string(who) + ": ";
+      if (why.compare(0, head.size(), head) == 0) why.erase(0, head.size());
+      return fail(rc, "%s: member %d: %s", who, m, why.c_str());
+    }
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int refined = c0->refine, patnorm = c0->patnorm, x_only = c0->x_only;
+  const int robust = c0->cost == ICTR_C2F_COST_HUBER;
+  if (nch == 3 && refined)  // as a member's own first refined colour run: each member owns its Bw planes
+    for (int m = 0; m < n; ++m) {
+      ictr_c2fflow *c = set->m[m];
+      const C2fLevel &L = c->lv[c->lv_l];
+      if (!c->bw12)
+        if (int rc = c->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
+    }
+  set->timed = set->timing;
+  int ops = 0;
+  ictr_flowgrid *grid[kSetMax] = {};
+  ictr_flowdensify *dens[kSetMax] = {};
+  ictr_flowrefine *ref[kSetMax] = {};
+  const float *bias[kSetMax] = {}, *field[kSetMax] = {};
+  float *bw12[kSetMax] = {};
+  for (int l = c0->lv_f; l >= c0->lv_l; --l) {
+    for (int m = 0; m < n; ++m) {
+      C2fLevel &L = set->m[m]->lv[l];
+      grid[m] = L.grid.get(), dens[m] = L.dens.get(), ref[m] = L.ref.get();
+      bias[m] = patnorm ? L.bias : nullptr;
+      field[m] = ictr_flowdensify_device_ptr(L.dens.get());
+      bw12[m] = set->m[m]->bw12.get();
+    }
+    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][0].get(), s));
+    if (int rc = kC2fSetSearch[robust][patnorm][x_only][nch == 3](set, pfc, l, refined, s)) return rc;
+    if (int rc = ictr_flowgrid_fill_set_(grid, n, set->rowhas.get(), s)) return rc;
+    ops += 4;  // the search, the memset of rowhas and the fill's two launches
+    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][1].get(), s));
+    if (int rc = ictr_flowdensify_run_level_set_(dens, grid, pyr_a, pyr_b, n, nch, c0->psz, l, bias, s)) return rc;
+    ops += 1;
+    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][2].get(), s));
+    if (refined) {
+      int k = 0;
+      if (int rc = ictr_flowrefine_run_level_set_(ref, pyr_a, pyr_b, n, nch, field, x_only, l, bw12, &k, s)) return rc;
+      ops += k;
+    }
+    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][3].get(), s));
+  }
+  if (c0->lv_l > 0) {  // the finest level's fields to the frame's size
+    UpSetArgs u;
+    memset(&u, 0, sizeof(u));
+    for (int m = 0; m < n; ++m) {
+      u.src[m] = reinterpret_cast<const float2 *>(c2f_field(set->m[m]->lv[c0->lv_l], refined));
+      u.out[m] = reinterpret_cast<float2 *>(set->m[m]->up.get());
+    }
+    const C2fLevel &L = c0->lv[c0->lv_l];
+    launch_flow_upsample_set(u, n, L.w, L.h, c0->lv_l, c0->w, c0->h, x_only, s);
+    ops += 1;
+    if (set->timed) HIPCHK(hipEventRecord(set->up_done.get(), s));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(set->done.get(), s));
+  for (int m = 0; m < n; ++m) {  // each member as behind its own run, untimed
+    ictr_c2fflow *c = set->m[m];
+    HIPCHK(hipEventRecord(c->done.get(), s));
+    c->timed = 0;
+    c->ran = 1;
+    c->ran_refined = refined;
+    c->ran_patnorm = patnorm;
+  }
+  set->ran = 1;
+  set->ops = ops;
+  return ICTR_OK;
+}
+extern "C" int ictr_c2fset_run(ictr_c2fset *s, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b,
+                               void *hip_stream) {
+  return c2fset_run(s, pyr_a, pyr_b, 1, "c2fset_run", hip_stream);
+}
+extern "C" int ictr_c2fset_run_rgb(ictr_c2fset *s, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b,
+                                   void *hip_stream) {
+  return c2fset_run(s, pyr_a, pyr_b, 3, "c2fset_run_rgb", hip_stream);
+}
+extern "C" int ictr_c2fset_get_kernel_ms(ictr_c2fset *s, float *ms, float *upsample_ms) {
+  if (!s) return fail(ICTR_ERR_INVALID, "c2fset is NULL");
+  if (!s->ran) return fail(ICTR_ERR_STATE, "c2fset_get_kernel_ms: no run yet");
+  if (!ms) return fail(ICTR_ERR_INVALID, "c2fset_get_kernel_ms: ms is NULL");
+  HIPCHK(hipEventSynchronize(s->done.get()));
+  const ictr_c2fflow *c = s->m[0];
+  for (int l = 0; l <= c->lv_f; ++l)
+    for (int k = 0; k < 3; ++k) {
+      ms[3 * l + k] = 0.0f;
+      if (s->timed && l >= c->lv_l) HIPCHK(hipEventElapsedTime(&ms[3 * l + k], s->ev[l][k].get(), s->ev[l][k + 1].get()));
+    }
+  if (upsample_ms) {
+    *upsample_ms = 0.0f;
+    if (s->timed && c->lv_l > 0) HIPCHK(hipEventElapsedTime(upsample_ms, s->ev[c->lv_l][3].get(), s->up_done.get()));
+  }
   return ICTR_OK;
 }

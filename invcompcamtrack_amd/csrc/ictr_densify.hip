@@ -68,8 +68,9 @@ using DzRec = std::conditional_t<BIAS, DzRecBias<NCH>, float2>;
 
 // BIAS: the vote weighs |Bw - A - beta| with the node's beta (the coarse-to-fine flow under patch-mean normalisation).
 // NCH: the planes per frame. The rule's only fork is how e is formed: one channel takes |r|, with no division.
+// The body is stated once, for k_densify and for its lockstep twin k_densify_set.
 template <bool BIAS, int NCH>
-__global__ __launch_bounds__(kBlock) void k_densify(DzArgsT<NCH> a) {
+__device__ __forceinline__ void dz_body(DzArgsT<NCH> a) {
   static_assert(NCH == 1 || NCH == 3, "one channel or three");
   extern __shared__ float2 s_node_raw[];  // [ncy][ncx] records of the nodes i0 .. i1 x j0 .. j1
   DzRec<BIAS, NCH> *s_node = reinterpret_cast<DzRec<BIAS, NCH> *>(s_node_raw);
@@ -145,6 +146,17 @@ __global__ __launch_bounds__(kBlock) void k_densify(DzArgsT<NCH> a) {
   a.cnt[o] = (float)n;
   a.sw[o] = sw;
 }
+template <bool BIAS, int NCH>
+__global__ __launch_bounds__(kBlock) void k_densify(DzArgsT<NCH> a) {
+  dz_body<BIAS, NCH>(a);
+}
+// The lockstep twin (DESIGN.md §4 "Lockstep sets"): k_densify's workgroups along x and y, once per member along z. The
+// members agree in geometry, so one count of dynamic LDS serves them all.
+template <bool BIAS, int NCH>
+__global__ __launch_bounds__(kBlock) void k_densify_set(SetArgs<DzArgsT<NCH>> s) {
+  static_assert(sizeof(s) <= kKernargLimit, "the argument block of a set exceeds the kernel-argument limit");
+  dz_body<BIAS, NCH>(s.m[blockIdx.z]);
+}
 
 }  // namespace ictr
 
@@ -194,14 +206,13 @@ extern "C" int ictr_flowdensify_set_timing(ictr_flowdensify *z, int on) {
   return ICTR_OK;
 }
 
-// One run on level `level` of NCH pyramids per frame (grid and object of that level's size); bias: the grid's node bias
-// [ny][nx][NCH] on the device (NULL: none, k_densify<false, NCH>)
+// the checks of a run (below), its kernel arguments and its bytes of LDS
 template <int NCH>
-static int dz_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
-                  const ictr_pyramid *const *pyr_b, int psz, int level, const float *bias, hipStream_t s) {
+static int dz_args(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
+                   const ictr_pyramid *const *pyr_b, int psz, int level, const float *bias, DzArgsT<NCH> *out, size_t *out_lds) {
   if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
   if (psz < 1 || psz > kDzMaxPsz) return fail(ICTR_ERR_INVALID, "flowdensify_run: psz is %d (1 .. %d)", psz, kDzMaxPsz);
-  DzArgsT<NCH> a;
+  DzArgsT<NCH> &a = *out;
   memset(&a, 0, sizeof(a));
   if (int rc = ictr_flowgrid_view_lost_(grid, &a.g, &a.lost)) return rc;
   if (a.g.w != z->w || a.g.h != z->h)
@@ -233,6 +244,17 @@ static int dz_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyr
   if (lds > kDzMaxLds)
     return fail(ICTR_ERR_INVALID, "flowdensify_run: step %d with psz %d needs a node table of %zu bytes of LDS (limit %zu)",
                 a.g.step, psz, lds, kDzMaxLds);
+  *out_lds = lds;
+  return ICTR_OK;
+}
+// One run on level `level` of NCH pyramids per frame (grid and object of that level's size); bias: the grid's node bias
+// [ny][nx][NCH] on the device (NULL: none, k_densify<false, NCH>)
+template <int NCH>
+static int dz_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
+                  const ictr_pyramid *const *pyr_b, int psz, int level, const float *bias, hipStream_t s) {
+  DzArgsT<NCH> a;
+  size_t lds = 0;
+  if (int rc = dz_args<NCH>(z, grid, pyr_a, pyr_b, psz, level, bias, &a, &lds)) return rc;
   z->timed = z->timing;
   if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
   if (bias)
@@ -254,6 +276,49 @@ extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowg
                                            const float *bias, void *hip_stream) {
   return channels == 3 ? dz_run<3>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream)
                        : dz_run<1>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream);
+}
+
+// n densifiers of one size in lockstep, one launch: member m reads grid[m], bias[m] (all NULL, or none) and the pyramids
+// pyr_a[m * channels + c], pyr_b[m * channels + c]. Untimed, and no member's own event is recorded: the caller's event
+// behind the whole run stands for them.
+template <int NCH>
+static int dz_run_set(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid, const ictr_pyramid *const *pyr_a,
+                      const ictr_pyramid *const *pyr_b, int n, int psz, int level, const float *const *bias, hipStream_t s) {
+  SetArgs<DzArgsT<NCH>> a;
+  memset(&a, 0, sizeof(a));
+  size_t lds = 0;
+  for (int m = 0; m < n; ++m) {
+    size_t l = 0;
+    if (int rc = dz_args<NCH>(z[m], grid[m], pyr_a + m * NCH, pyr_b + m * NCH, psz, level, bias[m], &a.m[m], &l)) return rc;
+    if (m > 0 && (l != lds || z[m]->w != z[0]->w || z[m]->h != z[0]->h || !bias[m] != !bias[0]))
+      return fail(ICTR_ERR_INVALID, "flowdensify_run_set: member %d differs in geometry", m);
+    lds = l;
+  }
+  dim3 g = pixel_rows_grid(z[0]->w, z[0]->h);
+  g.z = n;
+  if (bias[0])
+    hipLaunchKernelGGL((k_densify_set<true, NCH>), g, dim3(kBlock), lds, s, a);
+  else
+    hipLaunchKernelGGL((k_densify_set<false, NCH>), g, dim3(kBlock), lds, s, a);
+  HIPCHK(hipGetLastError());
+  for (int m = 0; m < n; ++m) z[m]->timed = 0;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowdensify_run_level_set_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
+                                               const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                                               int channels, int psz, int level, const float *const *bias, void *hip_stream) {
+  if (!z || !grid || !pyr_a || !pyr_b || !bias || n < 1 || n > kSetMax)
+    return fail(ICTR_ERR_INVALID, "flowdensify_run_set: bad arguments");
+  return channels == 3 ? dz_run_set<3>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream)
+                       : dz_run_set<1>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream);
+}
+
+// the parameters a set compares its members' densifiers by
+extern "C" int ictr_flowdensify_get_params_(const ictr_flowdensify *z, float *minerr, int *power) {
+  if (!z || !minerr || !power) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  *minerr = z->minerr;
+  *power = z->power;
+  return ICTR_OK;
 }
 
 extern "C" int ictr_flowdensify_result(ictr_flowdensify *z, float *out, int on_device) {

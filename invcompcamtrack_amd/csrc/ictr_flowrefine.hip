@@ -53,13 +53,17 @@ struct FrArgsT {
 using FrArgs = FrArgsT<1>;
 
 // interleaved (u, v) -> the two working planes
-__global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v,
-                                                    int n) {
+// Every kernel's body is stated once, for the kernel and for its lockstep twin (k_fr_*_set, below the kernels).
+__device__ __forceinline__ void fr_init_body(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v, int n) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const float2 f = f0[i];
   u[i] = f.x;
   v[i] = f.y;
+}
+__global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v,
+                                                    int n) {
+  fr_init_body(f0, u, v, n);
 }
 // (a flow grid's dense field is formed by launch_fg_dense: ictr_flowgrid_dev.h)
 
@@ -75,7 +79,7 @@ __host__ __device__ __forceinline__ int fr_ci(int X, int Y, int w, int h) {
 
 // (the channels of B are warped at ONE position)
 template <int NCH>
-__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgsT<NCH> a, int fold) {
+__device__ __forceinline__ void fr_warp_body(FrArgsT<NCH> a, int fold) {
   const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
   if (X >= a.w || Y >= a.h) return;
   const int i = Y * a.w + X;
@@ -96,6 +100,10 @@ __global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgsT<NCH> a, int fold) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) a.bw[c][i] = fr_bilinear(a.B[c], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
   }
+}
+template <int NCH>
+__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgsT<NCH> a, int fold) {
+  fr_warp_body<NCH>(a, fold);
 }
 
 // a tile with its halo; (cx, cy) are tile coordinates, the frame coordinate is (gx0 + cx, gy0 + cy)
@@ -138,7 +146,7 @@ __device__ __forceinline__ float fr_smooth(const FrTile &tu, const FrTile &tv, i
 // k_fr_coef and k_fr_coef_rgb (below) are two kernels and not one template over the channel count: this one forms
 // w0 = ((delta n0) / 2) / sqrt(n0 Iz^2 + eps^2) per pixel, the colour one q0 on the channel mean, then q0 n0[c], and divides
 // the coefficients by 3. These are different roundings, so a template would be these two bodies under `if constexpr`.
-__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) {
+__device__ __forceinline__ void fr_coef_body(FrArgsT<1> a) {
   __shared__ float sB[kFrSide][kFrSide], sA[kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
   const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
   // the halo is read at the nearest pixel of the frame; what lies outside is never used (the border rules above)
@@ -184,6 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) {
   a.du[i] = 0.0f;
   a.dv[i] = 0.0f;
 }
+__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) { fr_coef_body(a); }
 
 // The colour form of the coefficient stage (DESIGN.md §4 "Colour"): three planes per frame and three Bw planes. Steps 1
 // and 2 run per channel, n0, n1, n2 are per channel; the two robust weights are joint over the channels, taken on the
@@ -192,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) {
 // U and V are staged once, and with them the three channels' tiles of Bw and A: 8 tiles x 1600 B = 12.8 KB of LDS. A
 // lane keeps the eleven per-channel values of all three channels (the joint weights need every channel's Iz, Ixz, Iyz
 // before any coefficient is final); the register report shows no scratch.
-__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrArgsT<3> a) {
+__device__ __forceinline__ void fr_coef_rgb_body(FrArgsT<3> a) {
   __shared__ float sB[3][kFrSide][kFrSide], sA[3][kFrSide][kFrSide], sU[kFrSide][kFrSide], sV[kFrSide][kFrSide];
   const int gx0 = blockIdx.x * kFrTile - kFrHalo, gy0 = blockIdx.y * kFrTile - kFrHalo;
   for (int q = threadIdx.x; q < kFrSide * kFrSide; q += kBlock) {
@@ -253,12 +262,13 @@ __global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrArgsT<3> a) {
   a.du[i] = 0.0f;
   a.dv[i] = 0.0f;
 }
+__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrArgsT<3> a) { fr_coef_rgb_body(a); }
 
 // One half-sweep. A lane owns one pixel of the active colour: x = 2 p + ((y + COLOUR) & 1). The reads of du / dv / u / v
 // of a wave cover whole lines (the pixel and its two row neighbours alternate), and so do those of the coefficient
 // planes, which are compacted by colour; only wd is read at stride 2.
 template <int COLOUR>
-__global__ __launch_bounds__(kBlock) void k_fr_sor(FrArgs a) {
+__device__ __forceinline__ void fr_sor_body(FrArgs a) {
   const int Y = blockIdx.y * kWaves + (threadIdx.x >> 6);
   if (Y >= a.h) return;
   const int X = 2 * (blockIdx.x * 64 + (threadIdx.x & 63)) + ((Y + COLOUR) & 1);
@@ -284,13 +294,47 @@ __global__ __launch_bounds__(kBlock) void k_fr_sor(FrArgs a) {
   const float sv = ((sl + sr) + st) + sd;
   a.dv[i] = (1.0f - om) * dv + om * ((((a.b2[c] - a12 * dun) + sv) - sw * v) / (a.a22[c] + sw));
 }
+template <int COLOUR>
+__global__ __launch_bounds__(kBlock) void k_fr_sor(FrArgs a) {
+  fr_sor_body<COLOUR>(a);
+}
 
 // step 6 of the last outer iteration, into the interleaved result; u and v keep the last outer iteration's field
-__global__ __launch_bounds__(kBlock) void k_fr_final(FrArgs a, float2 *__restrict__ out) {
+__device__ __forceinline__ void fr_final_body(FrArgs a, float2 *__restrict__ out) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.w * a.h) return;
   const float v = a.v[i];
   out[i] = make_float2(a.u[i] + a.du[i], a.x_only ? v : v + a.dv[i]);
+}
+__global__ __launch_bounds__(kBlock) void k_fr_final(FrArgs a, float2 *__restrict__ out) { fr_final_body(a, out); }
+
+// The lockstep twins (DESIGN.md §4 "Lockstep sets"): the refiners of a set of coarse-to-fine flows, which agree in size
+// and parameters. Each runs its kernel's body on member m's arguments, m the block index along the grid dimension the
+// kernel does not use: y for the two linear kernels, z for the others.
+struct FrIoSet {
+  const float2 *f0[kSetMax];  // per member the field a run starts from ...
+  float2 *out[kSetMax];       // ... and its result
+};
+using FrSet = SetArgs<FrArgs>;
+static_assert(sizeof(SetArgs<FrArgsT<3>>) <= kKernargLimit && sizeof(FrSet) + sizeof(FrIoSet) <= kKernargLimit,
+              "the argument block of a set exceeds the kernel-argument limit");
+__global__ __launch_bounds__(kBlock) void k_fr_init_set(FrSet s, FrIoSet io, int n) {
+  const int m = blockIdx.y;
+  fr_init_body(io.f0[m], s.m[m].u, s.m[m].v, n);
+}
+template <int NCH>
+__global__ __launch_bounds__(kBlock) void k_fr_warp_set(SetArgs<FrArgsT<NCH>> s, int fold) {
+  fr_warp_body<NCH>(s.m[blockIdx.z], fold);
+}
+__global__ __launch_bounds__(kBlock) void k_fr_coef_set(SetArgs<FrArgsT<1>> s) { fr_coef_body(s.m[blockIdx.z]); }
+__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb_set(SetArgs<FrArgsT<3>> s) { fr_coef_rgb_body(s.m[blockIdx.z]); }
+template <int COLOUR>
+__global__ __launch_bounds__(kBlock) void k_fr_sor_set(FrSet s) {
+  fr_sor_body<COLOUR>(s.m[blockIdx.z]);
+}
+__global__ __launch_bounds__(kBlock) void k_fr_final_set(FrSet s, FrIoSet io) {
+  const int m = blockIdx.y;
+  fr_final_body(s.m[m], io.out[m]);
 }
 
 }  // namespace ictr
@@ -505,6 +549,77 @@ extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid
   FrArgsT<1> a;
   if (int rc = fr_frame_args<1>(r, pyr_a, pyr_b, x_only, level, nullptr, &a)) return rc;
   return fr_run<1>(r, a, field, false, (hipStream_t)hip_stream);
+}
+
+// n refiners of one size and one set of parameters in lockstep: fr_run's launch sequence, each stage once. Member m starts
+// from field[m] and reads the pyramids pyr_a[m * channels + c], pyr_b[m * channels + c]; bw12[m] as in run_level_. Untimed,
+// and no member's own event is recorded: the caller's event behind the whole run stands for them. *ops takes the launches
+// (and, with n_outer = 0, the copies, one per member) enqueued.
+template <int NCH>
+static int fr_run_set(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                      const float *const *field, int x_only, int level, float *const *bw12, int *ops, hipStream_t s) {
+  SetArgs<FrArgsT<NCH>> a;
+  FrSet g;
+  FrIoSet io;
+  memset(&a, 0, sizeof(a));
+  memset(&g, 0, sizeof(g));
+  memset(&io, 0, sizeof(io));
+  const ictr_flowrefine *r0 = r[0];
+  for (int m = 0; m < n; ++m) {
+    if (!r[m] || !field[m] || (NCH == 3 && !bw12[m]))
+      return fail(ICTR_ERR_INVALID, "flowrefine_run_set: member %d: the refiner, the field or the Bw planes are NULL", m);
+    if (r[m]->w != r0->w || r[m]->h != r0->h || r[m]->n_outer != r0->n_outer || r[m]->n_sor != r0->n_sor)
+      return fail(ICTR_ERR_INVALID, "flowrefine_run_set: member %d differs in size or iteration counts", m);
+    if (int rc = fr_frame_args<NCH>(r[m], pyr_a + m * NCH, pyr_b + m * NCH, x_only, level, bw12[m], &a.m[m])) return rc;
+    g.m[m] = fr_args<1>(r[m], x_only);
+    io.f0[m] = reinterpret_cast<const float2 *>(field[m]);
+    io.out[m] = reinterpret_cast<float2 *>(r[m]->res.get());
+  }
+  const size_t np = (size_t)r0->w * r0->h;
+  int count = 0;
+  if (r0->n_outer == 0) {  // the input's bits
+    for (int m = 0; m < n; ++m, ++count)
+      HIPCHK(hipMemcpyAsync(r[m]->res.get(), field[m], sizeof(float) * 2 * np, hipMemcpyDeviceToDevice, s));
+  } else {
+    const dim3 blk(kBlock), lin((unsigned)((np + kBlock - 1) / kBlock), n);
+    const dim3 tiles((r0->w + kFrTile - 1) / kFrTile, (r0->h + kFrTile - 1) / kFrTile, n);
+    dim3 rows = pixel_rows_grid(r0->w, r0->h), half = pixel_rows_grid((r0->w + 1) / 2, r0->h);
+    rows.z = half.z = n;
+    hipLaunchKernelGGL(k_fr_init_set, lin, blk, 0, s, g, io, (int)np);
+    for (int o = 0; o < r0->n_outer; ++o) {
+      hipLaunchKernelGGL(k_fr_warp_set<NCH>, rows, blk, 0, s, a, o > 0 ? 1 : 0);
+      if constexpr (NCH == 1)
+        hipLaunchKernelGGL(k_fr_coef_set, tiles, blk, 0, s, a);
+      else
+        hipLaunchKernelGGL(k_fr_coef_rgb_set, tiles, blk, 0, s, a);
+      for (int k = 0; k < r0->n_sor; ++k) {
+        hipLaunchKernelGGL(k_fr_sor_set<0>, half, blk, 0, s, g);
+        hipLaunchKernelGGL(k_fr_sor_set<1>, half, blk, 0, s, g);
+      }
+    }
+    hipLaunchKernelGGL(k_fr_final_set, lin, blk, 0, s, g, io);
+    count = 2 + r0->n_outer * (2 + 2 * r0->n_sor);
+  }
+  HIPCHK(hipGetLastError());
+  for (int m = 0; m < n; ++m) r[m]->nev = 0;
+  if (ops) *ops = count;
+  return ICTR_OK;
+}
+extern "C" int ictr_flowrefine_run_level_set_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
+                                              const ictr_pyramid *const *pyr_b, int n, int channels,
+                                              const float *const *field, int x_only, int level, float *const *bw12, int *ops,
+                                              void *hip_stream) {
+  if (!r || !r[0] || !pyr_a || !pyr_b || !field || !bw12 || n < 1 || n > kSetMax)
+    return fail(ICTR_ERR_INVALID, "flowrefine_run_set: bad arguments");
+  return channels == 3 ? fr_run_set<3>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, (hipStream_t)hip_stream)
+                       : fr_run_set<1>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, (hipStream_t)hip_stream);
+}
+// the parameters a set compares its members' refiners by
+extern "C" int ictr_flowrefine_get_params_(const ictr_flowrefine *r, float *p4, int *n2) {
+  if (!r || !p4 || !n2) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
+  p4[0] = r->alpha, p4[1] = r->gamma, p4[2] = r->delta, p4[3] = r->omega;
+  n2[0] = r->n_outer, n2[1] = r->n_sor;
+  return ICTR_OK;
 }
 
 extern "C" int ictr_flowrefine_result(ictr_flowrefine *r, float *out, int on_device) {

@@ -53,6 +53,21 @@ extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowg
 extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *const *pyr_a,
                                           const ictr_pyramid *const *pyr_b, int channels, const float *field, int x_only,
                                           int level, float *bw12, void *hip_stream);
+// The same stages for a lockstep set of n (1 .. kSetMax) coarse-to-fine flows (DESIGN.md §4 "Lockstep sets"): objects of
+// one size and one set of parameters, one launch per stage for all of them. Member m's pyramids are pyr_a[m * channels + c]
+// and pyr_b[m * channels + c]. rowhas: the set's block of n * ny ints, cleared by the one memset. No member's own event is
+// recorded: the event the caller records behind the run stands for them. *ops: the launches the refinement enqueued.
+extern "C" int ictr_flowgrid_fill_set_(ictr_flowgrid *const *g, int n, int *rowhas, void *hip_stream);  // ictr_frontend.hip
+extern "C" int ictr_flowdensify_run_level_set_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
+                                               const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                                               int channels, int psz, int level, const float *const *bias, void *hip_stream);
+extern "C" int ictr_flowrefine_run_level_set_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
+                                              const ictr_pyramid *const *pyr_b, int n, int channels,
+                                              const float *const *field, int x_only, int level, float *const *bw12, int *ops,
+                                              void *hip_stream);
+// what a set compares its members' stages by: minerr and power; alpha, gamma, delta, omega and n_outer, n_sor
+extern "C" int ictr_flowdensify_get_params_(const ictr_flowdensify *z, float *minerr, int *power);
+extern "C" int ictr_flowrefine_get_params_(const ictr_flowrefine *r, float *p4, int *n2);
 // the mailboxes of a connected p2p object as a kernel argument of the resident launch; non-zero: not connected (ictr_p2p.hip)
 extern "C" int ictr_p2p_fill_xchg_(const ictr_p2p *p, ictr::ResXchg *x);
 extern "C" const char *ictr_last_error(void);

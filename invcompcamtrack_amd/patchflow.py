@@ -27,7 +27,8 @@ __all__ = ["track_points", "partition_patches", "dense_flow", "good_features", "
            "last_form", "track_disparity", "dense_disparity", "disparity_last_kernel_ms", "disparity_last_form",
            "good_features_hip", "FlowGrid", "PointTracker", "run_OF_point_track_hip", "refine_flow_host", "refine_flow",
            "FlowRefiner", "REFINE_DEFAULTS", "FR_STAGES", "densify_flow_host", "densify_flow", "FlowDensifier",
-           "DENSIFY_DEFAULTS", "DZ_STAGES", "c2f_flow_host", "c2f_flow", "CoarseToFineFlow"]
+           "DENSIFY_DEFAULTS", "DZ_STAGES", "c2f_flow_host", "c2f_flow", "CoarseToFineFlow",
+           "CoarseToFineFlowSet"]
 
 
 def last_kernel_ms():
@@ -1181,6 +1182,91 @@ class CoarseToFineFlow:
         ms = C.c_float()
         check(_lib.load().ictr_c2fflow_get_upsample_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+C2FSET_MAX = 8  # ICTR_C2FSET_MAX
+
+
+class CoarseToFineFlowSet:
+    """1 .. 8 CoarseToFineFlow objects of equal shape and parameters run in lockstep (``ictr_c2fset_*``): per level and
+    stage one launch covers all members, the member index a grid dimension. ``run(pairs)`` leaves every member in the
+    state its own ``run(*pairs[m])`` would have left it in, bit for bit (``dense``, ``level``, ``level_bias``,
+    ``device_ptr``); only the stage times are the set's (``kernel_ms``), a member's are zeros after a lockstep run. The
+    set keeps its members alive. Members are compared at every run: they may be reconfigured between runs, together."""
+
+    def __init__(self, flows):
+        flows = list(flows)
+        if not 1 <= len(flows) <= C2FSET_MAX:
+            raise ValueError(f"CoarseToFineFlowSet: {len(flows)} members (1 .. {C2FSET_MAX})")
+        for i, f in enumerate(flows):
+            if not isinstance(f, CoarseToFineFlow):
+                raise TypeError(f"CoarseToFineFlowSet: member {i} is a {type(f).__name__}, not a CoarseToFineFlow")
+            if any(f is g for g in flows[:i]):
+                raise ValueError(f"CoarseToFineFlowSet: member {i} is the same object as member "
+                                 f"{[g is f for g in flows].index(True)}")
+        self.members = tuple(flows)
+        self._h = C.c_void_p()
+        arr = (C.c_void_p * len(flows))(*[f._h.value for f in flows])
+        check(_lib.load().ictr_c2fset_create(C.byref(self._h), arr, len(flows)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.load().ictr_c2fset_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        n = C.c_int()
+        check(_lib.load().ictr_c2fset_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def run(self, pairs, stream=None):
+        """pairs: one (pyr_a, pyr_b) per member; with colour members each of the two is a sequence of three pyramids.
+        Two members may read the same pyramid. Enqueues and returns."""
+        pairs = list(pairs)
+        n, nch = len(self.members), self.members[0].channels
+        if len(pairs) != n:
+            raise ValueError(f"CoarseToFineFlowSet.run: {len(pairs)} pairs for {n} members")
+        tabs = ([], [])
+        for m, pair in enumerate(pairs):
+            if hasattr(pair, "_h") or len(pair) != 2:
+                raise ValueError(f"CoarseToFineFlowSet.run: pair {m} is not a (pyr_a, pyr_b)")
+            for tab, p in zip(tabs, pair):
+                if nch == 3:
+                    if hasattr(p, "_h") or len(p) != 3:
+                        raise ValueError(f"CoarseToFineFlowSet.run: pair {m}: with channels=3 a frame is three pyramids, "
+                                         "one per channel")
+                    tab.extend(q._h.value for q in p)
+                else:
+                    if not hasattr(p, "_h"):
+                        raise ValueError(f"CoarseToFineFlowSet.run: pair {m}: with channels=1 a frame is one pyramid "
+                                         "(colour needs channels=3)")
+                    tab.append(p._h.value)
+        a, b = ((C.c_void_p * len(t))(*t) for t in tabs)
+        fn = _lib.load().ictr_c2fset_run_rgb if nch == 3 else _lib.load().ictr_c2fset_run
+        check(fn(self._h, a, b, C.c_void_p(stream or 0)))
+        return self
+
+    def operations(self):
+        """Kernel launches plus memsets the last run enqueued: the same for any number of members."""
+        n = C.c_int()
+        check(_lib.load().ictr_c2fset_last_operations(self._h, C.byref(n)))
+        return int(n.value)
+
+    def set_timing(self, on=True):
+        check(_lib.load().ictr_c2fset_set_timing(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """(lv_f + 1, 3) ms of the last run, each for the whole set: per level from 0 the search with its fill, the
+        densification, the refinement; zeros when timing was off, and in the rows below lv_l."""
+        ms = np.zeros((self.members[0].lv_f + 1, 3), np.float32)
+        check(_lib.load().ictr_c2fset_get_kernel_ms(self._h, fp(ms), None))
+        return ms
+
+    def upsample_ms(self):
+        """ms of the lockstep k_flow_upsample in the last run; 0 when timing was off or lv_l = 0."""
+        ms, up = np.zeros((self.members[0].lv_f + 1, 3), np.float32), C.c_float()
+        check(_lib.load().ictr_c2fset_get_kernel_ms(self._h, fp(ms), C.byref(up)))
+        return float(up.value)
 
 
 def c2f_flow(pyr_a, pyr_b, step=4, psz=8, lv_f=None, **params):

@@ -3,7 +3,7 @@
   python -m invcompcamtrack_amd.run_stereo_track listfile out.npz [--bsize 14] [--fields in.npz] [--host]
          [--psz 15] [--lv_f 3] [--step 4] [--th_ratio 0.2] [--th_abs 1.0] [--disparity 2d|1d]
          [--refine [alpha,gamma,delta,outer,sor,omega]] [--densify [minerr,power]] [--flow grid|c2f|c2f-1d]
-         [--patnorm] [--lv-l N] [--colour] [--cost l2|huber] [--huber-k K]
+         [--patnorm] [--lv-l N] [--colour] [--cost l2|huber] [--huber-k K] [--lockstep]
 
 listfile holds a left and a right image path per line (PGM or .npy), the frames in order; the first bsize lines are read.
 Per frame the stereo flow grids and per frame pair the temporal ones are computed on the device and handed to the window
@@ -20,7 +20,9 @@ level's field to the frame (CoarseToFineFlow's lv_l; default 0; with --flow c2f 
 as three channels (io_formats.read_image_rgb: .npy of (h, w, 3), binary .ppm, else PIL) and computes every field on colour
 frames (CoarseToFineFlow's channels=3; with --flow c2f or c2f-1d only). --cost huber searches every coarse-to-fine field with
 the Huber patch cost, the residuals clipped to +-K grey levels (CoarseToFineFlow's cost and huber_k; --huber-k K, default 5;
-with --flow c2f or c2f-1d only; --cost l1 is refused: L1 is not built). With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
+with --flow c2f or c2f-1d only; --cost l1 is refused: L1 is not built). --lockstep runs a frame's coarse-to-fine objects in
+lockstep, one launch per level and stage for all of them (patchflow.CoarseToFineFlowSet; with --flow c2f or c2f-1d only):
+the same fields and the same file, bit for bit; with --host it changes nothing. With --fields the dense fields come from in.npz as the script reads them from .flo / .pfm files
 instead (listfile is not read and may be ``-``): ``disp_lr``, ``disp_rl`` (bsize, H, W), ``flow_l``, ``flow_r``
 (>= bsize-1, 2 = fwd / bwd, H, W, 2) and optionally ``xy0`` (N, 2). out.npz: ``xy_t`` (M, 4, bsize) and ``rows`` (M,), the
 keys that run_static_split --stereo and run_fit_cameras --stereo read. The window runs on the GPU; --host runs the host
@@ -95,6 +97,9 @@ def main(argv=None):
     ap.add_argument("--colour", action="store_true")
     ap.add_argument("--cost", default="l2")
     ap.add_argument("--huber-k", dest="huber_k", type=float, default=None)
+    ap.add_argument("--lockstep", action="store_true",
+                    help="run a frame's coarse-to-fine objects in lockstep, one launch per level and stage for all of them "
+                         "(--flow c2f or c2f-1d): the same output bit for bit; with --host it changes nothing")
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
     if a.colour and a.flow not in ("c2f", "c2f-1d"):
         ap.error("--colour needs --flow c2f or c2f-1d: colour frames are built for the coarse-to-fine flow alone")
@@ -108,6 +113,9 @@ def main(argv=None):
         ap.error("--lv-l needs --flow c2f or c2f-1d: a finest level above 0 is built for the coarse-to-fine flow alone")
     if (a.cost != "l2" or a.huber_k is not None) and a.flow not in ("c2f", "c2f-1d"):
         ap.error("--cost and --huber-k need --flow c2f or c2f-1d: the patch cost is built for the coarse-to-fine flow alone")
+    lockstep = a.lockstep and not a.host  # (--host: nothing changes)
+    if lockstep and a.flow not in ("c2f", "c2f-1d"):
+        ap.error("--lockstep needs --flow c2f or c2f-1d: lockstep sets are built for the coarse-to-fine flow alone")
     try:
         from .patchflow import _c2f_cost
         _c2f_cost(a.cost, 5.0 if a.huber_k is None else a.huber_k, "--cost")
@@ -131,7 +139,7 @@ def main(argv=None):
         h, w = frames[0][0].shape[:2]
         t = S.StereoPointTracker(w, h, len(frames), a.step, a.psz, a.lv_f, keep_grids=a.host, disparity=a.disparity,
                                  refine=a.refine, densify=a.densify, flow=a.flow, patnorm=a.patnorm, lv_l=a.lv_l,
-                                 colour=a.colour, **cost, **th)
+                                 colour=a.colour, lockstep=lockstep, **cost, **th)
         for left, right in frames:
             t.push_frames(left, right)
         xy_t, rows = S.stereo_track_window_host(*dense_fields_of(t), **th) if a.host else t.window()

@@ -309,11 +309,15 @@ class StereoPointTracker:
     pyramids per side, one per channel, and every object is a CoarseToFineFlow(channels=3); the fields the window reads
     are the same w x h flow planes. cost="huber" (with huber_k, default 5.0 grey levels) searches every coarse-to-fine
     field with the Huber patch cost (CoarseToFineFlow's cost and huber_k); it likewise needs flow="c2f" or "c2f-1d" and is
-    refused with flow="grid", whose whole-pyramid kernels have no such form."""
+    refused with flow="grid", whose whole-pyramid kernels have no such form. lockstep=True (likewise flow="c2f" or
+    "c2f-1d" alone; default False) runs a frame's coarse-to-fine objects as patchflow.CoarseToFineFlowSet objects, one
+    launch per level and stage for all of them: with flow="c2f" one set of the six fields (of the two stereo ones at the
+    window's first frame), with flow="c2f-1d" a set of the two stereo fields (x_only) and a set of the four temporal
+    ones. The fields, and with them the window, are the same bit for bit."""
 
     def __init__(self, w, h, bsize=14, step=4, psz=15, lv_f=3, maxiter=10, eps=0.01, th_ratio=0.2, th_abs=1.0,
                  xy0=None, keep_grids=False, disparity="2d", refine=None, densify=None, flow="grid", patnorm=False,
-                 lv_l=0, colour=False, cost="l2", huber_k=5.0):
+                 lv_l=0, colour=False, cost="l2", huber_k=5.0, lockstep=False):
         if disparity not in ("2d", "1d"):
             raise ValueError(f"disparity is '2d' (the 2-D tracker, y dropped) or '1d' (the 1-D search), not {disparity!r}")
         if flow not in ("grid", "c2f", "c2f-1d"):
@@ -336,6 +340,11 @@ class StereoPointTracker:
         if self.cost == "huber" and flow not in ("c2f", "c2f-1d"):
             raise ValueError("cost='huber' needs flow='c2f' or 'c2f-1d': the robust patch cost is built for the "
                              "coarse-to-fine flow alone, not for the flow grids of flow='grid'")
+        if lockstep and flow not in ("c2f", "c2f-1d"):
+            raise ValueError("lockstep=True needs flow='c2f' or 'c2f-1d': lockstep sets are built for the coarse-to-fine "
+                             "flow alone, not for the flow grids of flow='grid'")
+        self.lockstep = bool(lockstep)
+        self._locksets = {}  # lockstep=True: the sets by their members
         self.flow = flow
         self.colour = bool(colour)
         self.lv_l = int(lv_l)
@@ -448,8 +457,16 @@ class StereoPointTracker:
             c.update(self._set(self._xsets, k, lambda: make(True), ("lr", "rl")))
         else:
             c = self._set(self._fsets, k, make)
-        for n, a, b, _ in fields:
-            c[n].run(a, b)
+        if self.lockstep and self.keep_grids:  # every frame has new objects: the sets of earlier frames are not needed again
+            self._locksets.clear()
+        if self.lockstep:  # the stereo pair apart where its objects differ (x_only) from the temporal ones
+            groups = (fields[:2], fields[2:]) if self.flow == "c2f-1d" else (fields,)
+            for group in groups:
+                if group:
+                    self._lockset([c[n] for n, _, _, _ in group]).run([(a, b) for _, a, b, _ in group])
+        else:
+            for n, a, b, _ in fields:
+                c[n].run(a, b)
         if k == 0:
             self.win.open(c["lr"], c["rl"], self.xy0)
         else:
@@ -457,6 +474,14 @@ class StereoPointTracker:
         if self.keep_grids:
             self.flows.append(c if k else {n: c[n] for n in ("lr", "rl")})
         self.nframes = k + 1
+
+    def _lockset(self, flows):
+        """The CoarseToFineFlowSet of these objects: made once per group of objects (which it keeps alive)."""
+        from .patchflow import CoarseToFineFlowSet
+        key = tuple(id(f) for f in flows)
+        if key not in self._locksets:
+            self._locksets[key] = CoarseToFineFlowSet(flows)
+        return self._locksets[key]
 
     def window(self):
         """(xy_t (M, 4, bsize), rows (M,)) once bsize frames have been pushed."""
