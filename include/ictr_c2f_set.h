@@ -1,5 +1,5 @@
-/* ictr_c2f_set.h -- a lockstep set of coarse-to-fine dense flows (ictr_c2fflow.hip, ictr_c2fset.hip,
- * ictr_c2fset_robust.hip; DESIGN.md §4 "Lockstep sets"). Part of ictr.h, which includes it inside its extern "C" block; not
+/* ictr_c2f_set.h -- a lockstep set of coarse-to-fine dense flows (ictr_c2fflow.hip; DESIGN.md §4 "Lockstep sets"). Part
+ * of ictr.h, which includes it inside its extern "C" block; not
  * to be included alone. It is a file of its own because tests/test_c2fflow_cpu.py pins the list of ictr_c2fflow_*
  * declarations in ictr.h's own text; the ctypes table of these is _lib.SIGNATURES_SET. */
 #ifndef ICTR_C2F_SET_H

@@ -28,8 +28,12 @@
 //
 // ROBUST is the Huber patch cost (DESIGN.md "Robust patch cost"): pf_level_search_ch's ROBUST forms, every residual clipped
 // to [-huber_k, +huber_k]; nothing else of the kernel changes. k_c2f_level, its arguments and its launcher live in
-// ictr_c2fflow_dev.h; this file instantiates the L2 forms and ictr_c2fflow_robust.hip the ROBUST ones, which
-// launch_c2f_level_robust reaches. Restated by tests/c2fcost_f32.py.
+// ictr_c2fflow_dev.h; this file instantiates the L2 forms and ictr_c2fflow_robust.hip the ROBUST ones. Restated by
+// tests/c2fcost_f32.py.
+//
+// Every kernel of a run takes the arguments of 1 .. kSetMax flows of one shape and runs a member's workgroups on the
+// member its block index names (DESIGN.md "Lockstep sets"); an object's own run is a set of one, and ictr_c2fset_run the
+// same walk over the levels (c2f_walk) on several.
 //
 // k_flow_upsample<XONLY> finishes a run whose finest level is above 0 (DESIGN.md "A finest level above 0"): the field of
 // level lv to the w x h frame, bilinear with half-pixel centres at the fixed factor 2^-lv, the vectors times 2^lv. One lane
@@ -52,24 +56,53 @@
 
 namespace ictr {
 
-// the body: flow_upsample_body of ictr_c2fflow_dev.h, which the lockstep twin (ictr_c2fset.hip) shares
+// the fields k_flow_upsample reads and writes, per member
+struct UpArgs {
+  const float2 *src[kSetMax];
+  float2 *out[kSetMax];
+};
+// s = 2^lv, inv_s = 2^-lv; member blockIdx.z's field. Everything before the taps is exact in f32 (x + 0.5, the product
+// with 2^-lv, - 0.5, rx, 1 - rx); the six products and three sums are taken in the order written, each rounded (no
+// contraction), then s * val.
 template <bool XONLY>
-__global__ __launch_bounds__(kBlock) void k_flow_upsample(const float2 *__restrict__ src, int wl, int hl, float inv_s,
-                                                          float s, float2 *__restrict__ out, int w, int h) {
-  flow_upsample_body<XONLY>(src, wl, hl, inv_s, s, out, w, h);
+__global__ __launch_bounds__(kBlock) void k_flow_upsample(UpArgs io, int wl, int hl, float inv_s, float s, int w, int h) {
+  const float2 *__restrict__ src = io.src[blockIdx.z];
+  float2 *__restrict__ out = io.out[blockIdx.z];
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * kWaves + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  const float fx = fminf(fmaxf(((float)x + 0.5f) * inv_s - 0.5f, 0.0f), (float)(wl - 1));
+  const float fy = fminf(fmaxf(((float)y + 0.5f) * inv_s - 0.5f, 0.0f), (float)(hl - 1));
+  const int x0 = (int)fx, y0 = (int)fy;  // fx, fy >= 0: the cast is the floor
+  const int x1 = min(x0 + 1, wl - 1), y1 = min(y0 + 1, hl - 1);
+  const float rx = fx - (float)x0, ry = fy - (float)y0;
+  const float qx = 1.0f - rx, qy = 1.0f - ry;
+  const size_t r0 = (size_t)y0 * wl, r1 = (size_t)y1 * wl;
+  float2 o;
+  if constexpr (XONLY) {  // y is not read and is +0.0
+    const float *f = reinterpret_cast<const float *>(src);
+    const float top = qx * f[2 * (r0 + x0)] + rx * f[2 * (r0 + x1)];
+    const float bot = qx * f[2 * (r1 + x0)] + rx * f[2 * (r1 + x1)];
+    o.x = s * (qy * top + ry * bot);
+    o.y = 0.0f;
+  } else {
+    const float2 a = src[r0 + x0], b = src[r0 + x1], c = src[r1 + x0], d = src[r1 + x1];
+    const float tx = qx * a.x + rx * b.x, bx = qx * c.x + rx * d.x;
+    const float ty = qx * a.y + rx * b.y, by = qx * c.y + rx * d.y;
+    o.x = s * (qy * tx + ry * bx);
+    o.y = s * (qy * ty + ry * by);
+  }
+  out[(size_t)y * w + x] = o;
 }
 
-// src [hl][wl][2] and out [h][w][2] on the device; the caller has checked the sizes
-static void launch_flow_upsample(const float *src, int wl, int hl, int lv, float *out, int w, int h, int x_only,
-                                 hipStream_t s) {
+// n fields src[m] [hl][wl][2] to out[m] [h][w][2], all on the device; the caller has checked the sizes
+static void launch_flow_upsample(const UpArgs &a, int n, int wl, int hl, int lv, int w, int h, int x_only, hipStream_t s) {
   const float sc = (float)(1 << lv), inv = 1.0f / sc;
-  const dim3 g = pixel_rows_grid(w, h), blk(kBlock);
+  dim3 g = pixel_rows_grid(w, h);
+  g.z = n;
   if (x_only)
-    hipLaunchKernelGGL((k_flow_upsample<true>), g, blk, 0, s, reinterpret_cast<const float2 *>(src), wl, hl, inv, sc,
-                       reinterpret_cast<float2 *>(out), w, h);
+    hipLaunchKernelGGL((k_flow_upsample<true>), g, dim3(kBlock), 0, s, a, wl, hl, inv, sc, w, h);
   else
-    hipLaunchKernelGGL((k_flow_upsample<false>), g, blk, 0, s, reinterpret_cast<const float2 *>(src), wl, hl, inv, sc,
-                       reinterpret_cast<float2 *>(out), w, h);
+    hipLaunchKernelGGL((k_flow_upsample<false>), g, dim3(kBlock), 0, s, a, wl, hl, inv, sc, w, h);
 }
 
 }  // namespace ictr
@@ -94,12 +127,38 @@ struct C2fLevel {
   std::unique_ptr<ictr_flowgrid, GridDel> grid;
   std::unique_ptr<ictr_flowdensify, DensDel> dens;
   std::unique_ptr<ictr_flowrefine, RefDel> ref;  // made when the refinement is switched on
-  Event ev[4];                                    // before the search, after the fill, the densifier, the refiner
 };
 }  // namespace
 
 constexpr int kC2fMaxLevels = 16;  // levels 0 .. 15: the level table of a patch search (PFArgs) holds as many
 static_assert(kC2fMaxLevels == sizeof(PFArgs::lv) / sizeof(PFLevel), "the levels of a coarse-to-fine flow are PFArgs' levels");
+
+// The stage events of a timed run over the levels lv_l .. lv_f, an object's own or a set's.
+struct C2fEvents {
+  int timing = 0, timed = 0;    // asked for; recorded by the last run
+  Event lv[kC2fMaxLevels][4];   // per level: before the search, after the fill, the densifier, the refiner
+  Event up_done;                // lv_l > 0: behind k_flow_upsample (it starts at level lv_l's last event)
+  int create(int lv_l, int lv_f) {
+    for (int l = lv_l; l <= lv_f; ++l)
+      for (Event &e : lv[l])
+        if (int rc = e.create()) return rc;
+    return lv_l > 0 ? up_done.create() : ICTR_OK;
+  }
+  // ms [3 (lv_f + 1)]: search + fill, densifier, refiner per level; *up_ms: the up-sampling. Either may be NULL; zeros
+  // behind an untimed run and at the levels below lv_l
+  int read(int lv_l, int lv_f, float *ms, float *up_ms) const {
+    for (int l = 0; ms && l <= lv_f; ++l)
+      for (int k = 0; k < 3; ++k) {
+        ms[3 * l + k] = 0.0f;
+        if (timed && l >= lv_l) HIPCHK(hipEventElapsedTime(&ms[3 * l + k], lv[l][k].get(), lv[l][k + 1].get()));
+      }
+    if (up_ms) {
+      *up_ms = 0.0f;
+      if (timed && lv_l > 0) HIPCHK(hipEventElapsedTime(up_ms, lv[lv_l][3].get(), up_done.get()));
+    }
+    return ICTR_OK;
+  }
+};
 
 struct ictr_c2fflow {
   int w = 0, h = 0, lv_f = 0, lv_l = 0, step = 0, psz = 0;
@@ -111,15 +170,15 @@ struct ictr_c2fflow {
   int channels = 1;  // 3: colour frames, three pyramids per frame (ictr_c2fflow_run_rgb)
   int cost = ICTR_C2F_COST_L2;  // ICTR_C2F_COST_HUBER: the ROBUST kernels with huber_k
   float huber_k = 5.0f;
-  int timing = 0, timed = 0, ran = 0, ran_refined = 0, ran_patnorm = 0;
+  int ran = 0, ran_refined = 0, ran_patnorm = 0;
   std::vector<C2fLevel> lv;  // [lv_f + 1]; the levels below lv_l hold their size and nothing else
   DevBuf<unsigned char> status;
   DevBuf<float> bias;  // next to it: the node bias of a run with patch-mean normalisation
   DevBuf<float> bw12;  // two planes of the finest level's size, the refinement's Bw of channels 1 and 2: made by the first
                        // refined run of a 3-channel object
   DevBuf<float> up;    // lv_l > 0: the result plane [h][w][2], level lv_l's field up-sampled
-  Event up_done;       // behind k_flow_upsample in a timed run (it starts at level lv_l's last event)
-  Event done;  // behind the last run
+  C2fEvents ev;        // of the object's own timed run
+  Event done;  // behind the last run, its own or a set's
 };
 
 // the field a level hands on: the refiner's when the run refined, else the densifier's
@@ -185,8 +244,6 @@ extern "C" int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_
     ictr_flowdensify *z = nullptr;
     if (int rc = ictr_flowdensify_create(&z, L.w, L.h)) return rc;
     L.dens.reset(z);
-    for (Event &e : L.ev)
-      if (int rc = e.create()) return rc;
     nodes += (size_t)L.nx * L.ny;
   }
   if (int rc = c->status.alloc(nodes, true)) return rc;
@@ -196,10 +253,9 @@ extern "C" int ictr_c2fflow_create_lvl(ictr_c2fflow **out, int w, int h, int lv_
     cur += (size_t)L.nx * L.ny;
   }
   if (int rc = c2f_place_bias(c.get(), 1)) return rc;
-  if (lv_l > 0) {
+  if (lv_l > 0)
     if (int rc = c->up.alloc(sizeof(float) * 2 * (size_t)w * h, true)) return rc;
-    if (int rc = c->up_done.create()) return rc;
-  }
+  if (int rc = c->ev.create(lv_l, lv_f)) return rc;
   if (int rc = c->done.create(hipEventDisableTiming)) return rc;
   *out = c.release();
   return ICTR_OK;
@@ -274,13 +330,13 @@ extern "C" int ictr_c2fflow_get_cost(const ictr_c2fflow *c, int *cost, float *hu
 }
 extern "C" int ictr_c2fflow_set_timing(ictr_c2fflow *c, int on) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
-  c->timing = on ? 1 : 0;
+  c->ev.timing = on ? 1 : 0;
   return ICTR_OK;
 }
 
 // the kernel arguments of level l's search of a run: pfc[ch] the level tables of the channels' pyramids, which agree in
 // geometry
-template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
+template <bool MEAN, int NCH, bool ROBUST>
 static int c2f_search_args(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, C2fArgsOf<MEAN, NCH, ROBUST> *out) {
   const C2fLevel &L = c->lv[l];
   const PFArgs &pf = pfc[0];
@@ -303,7 +359,7 @@ static int c2f_search_args(const ictr_c2fflow *c, const PFArgs *pfc, int l, int 
   a.P = c->psz;
   a.maxiter = c->maxiter;
   a.eps2 = pf.eps2;
-  a.min_det = XONLY ? pf.min_hx : pf.min_det;
+  a.min_det = c->x_only ? pf.min_hx : pf.min_det;
   a.far2 = (float)(c->psz * c->psz);
   if (int rc = ictr_flowgrid_node_buffers_(L.grid.get(), &a.d, &a.lost)) return rc;
   a.status = L.status;
@@ -311,29 +367,21 @@ static int c2f_search_args(const ictr_c2fflow *c, const PFArgs *pfc, int l, int 
   if constexpr (ROBUST) a.huber_k = c->huber_k;
   return ICTR_OK;
 }
-// level l's search of a run
-template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
-static int c2f_search(const ictr_c2fflow *c, const PFArgs *pfc, int l, int refined, hipStream_t s) {
-  const C2fLevel &L = c->lv[l];
-  C2fArgsOf<MEAN, NCH, ROBUST> a;
-  if (int rc = c2f_search_args<MEAN, XONLY, NCH, ROBUST>(c, pfc, l, refined, &a)) return rc;
-  if (c->timed) HIPCHK(hipEventRecord(L.ev[0].get(), s));
-  if constexpr (ROBUST)
-    launch_c2f_level_robust(a, XONLY, s);  // (instantiated in ictr_c2fflow_robust.hip)
-  else
-    launch_c2f_level<MEAN, XONLY, NCH, false>(a, s);
+// level l's search of n members: pfc[m] the level tables of member m's channels
+template <bool MEAN, int NCH, bool ROBUST>
+static int c2f_search(ictr_c2fflow *const *m, int n, const PFArgs (*pfc)[3], int l, int refined, hipStream_t s) {
+  SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n; ++i)
+    if (int rc = c2f_search_args<MEAN, NCH, ROBUST>(m[i], pfc[i], l, refined, &a.m[i])) return rc;
+  launch_c2f_level<MEAN, NCH, ROBUST>(a, n, m[0]->x_only, s);
   return ICTR_OK;
 }
-// the search's form by [cost == Huber][patnorm][x_only][channels == 3]
-using C2fSearch = int (*)(const ictr_c2fflow *, const PFArgs *, int, int, hipStream_t);
-#define ICTR_C2F_FORMS(R)                                                                                                  \
-  {                                                                                                                        \
-    {{c2f_search<false, false, 1, R>, c2f_search<false, false, 3, R>},                                                     \
-     {c2f_search<false, true, 1, R>, c2f_search<false, true, 3, R>}},                                                      \
-    {{c2f_search<true, false, 1, R>, c2f_search<true, false, 3, R>},                                                       \
-     {c2f_search<true, true, 1, R>, c2f_search<true, true, 3, R>}}                                                         \
-  }
-static const C2fSearch kC2fSearch[2][2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
+// the search's form by [cost == Huber][patnorm][channels == 3]
+using C2fSearch = int (*)(ictr_c2fflow *const *, int, const PFArgs (*)[3], int, int, hipStream_t);
+#define ICTR_C2F_FORMS(R) \
+  {{c2f_search<false, 1, R>, c2f_search<false, 3, R>}, {c2f_search<true, 1, R>, c2f_search<true, 3, R>}}
+static const C2fSearch kC2fSearch[2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
 #undef ICTR_C2F_FORMS
 
 // the argument checks of a run and pfc[ch], the level tables of a patch search on the channels' pyramids: pads, gradient
@@ -356,46 +404,83 @@ static int c2f_run_args(const ictr_c2fflow *c, const ictr_pyramid *const *pyr_a,
                   (int)pf.lv[l].swo, (int)pf.lv[l].sho, c->lv[l].w, c->lv[l].h);
   return ICTR_OK;
 }
-// a run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]); `who` opens the messages
-static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
-                   void *hip_stream) {
-  const int nch = c->channels;
-  PFArgs pfc[3];
-  if (int rc = c2f_run_args(c, pyr_a, pyr_b, who, pfc)) return rc;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int refined = c->refine, patnorm = c->patnorm, x_only = c->x_only;
-  const int robust = c->cost == ICTR_C2F_COST_HUBER;
-  if (nch == 3 && refined && !c->bw12) {  // the first refined colour run: Bw of channels 1 and 2, the finest level's size
-    const C2fLevel &L = c->lv[c->lv_l];
-    if (int rc = c->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
+// The walk over the levels lv_f .. lv_l for the n members m[] (1 .. kSetMax, which agree in shape and parameters: member
+// 0's stand for all), every stage enqueued once. pfc[i]: member i's level tables (c2f_run_args); member i's pyramids are
+// pyr_a[i * channels + ch], pyr_b[i * channels + ch]. ev: the stage events, recorded when ev.timing is on; rowhas: the
+// fill's block for n members (NULL: the one grid's own). *ops takes the launches and memsets enqueued. Behind the run every
+// member is as behind its own: `done` recorded, the stage events not its own unless ev is.
+static int c2f_walk(ictr_c2fflow *const *m, int n, const PFArgs (*pfc)[3], const ictr_pyramid *const *pyr_a,
+                    const ictr_pyramid *const *pyr_b, C2fEvents &ev, int *rowhas, int *ops, hipStream_t s) {
+  ictr_c2fflow *const c0 = m[0];
+  const int nch = c0->channels, refined = c0->refine, patnorm = c0->patnorm, x_only = c0->x_only;
+  const int robust = c0->cost == ICTR_C2F_COST_HUBER;
+  if (nch == 3 && refined)  // the first refined colour run: Bw of channels 1 and 2, the finest level's size, per member
+    for (int i = 0; i < n; ++i) {
+      const C2fLevel &L = m[i]->lv[c0->lv_l];
+      if (!m[i]->bw12)
+        if (int rc = m[i]->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
+    }
+  for (int i = 0; i < n; ++i) m[i]->ev.timed = 0;
+  const int timed = ev.timed = ev.timing;
+  int count = 0;
+  ictr_flowgrid *grid[kSetMax] = {};
+  ictr_flowdensify *dens[kSetMax] = {};
+  ictr_flowrefine *ref[kSetMax] = {};
+  const float *bias[kSetMax] = {}, *field[kSetMax] = {};
+  float *bw12[kSetMax] = {};
+  for (int l = c0->lv_f; l >= c0->lv_l; --l) {
+    for (int i = 0; i < n; ++i) {
+      C2fLevel &L = m[i]->lv[l];
+      grid[i] = L.grid.get(), dens[i] = L.dens.get(), ref[i] = L.ref.get();
+      bias[i] = patnorm ? L.bias : nullptr;
+      field[i] = ictr_flowdensify_device_ptr(L.dens.get());
+      bw12[i] = m[i]->bw12.get();
+    }
+    if (timed) HIPCHK(hipEventRecord(ev.lv[l][0].get(), s));
+    if (int rc = kC2fSearch[robust][patnorm][nch == 3](m, n, pfc, l, refined, s)) return rc;
+    if (int rc = ictr_flowgrid_fill_(grid, n, rowhas, s)) return rc;
+    count += 4;  // the search, the memset of rowhas and the fill's two launches
+    if (timed) HIPCHK(hipEventRecord(ev.lv[l][1].get(), s));
+    if (int rc = ictr_flowdensify_run_level_(dens, grid, pyr_a, pyr_b, n, nch, c0->psz, l, bias, s)) return rc;
+    count += 1;
+    if (timed) HIPCHK(hipEventRecord(ev.lv[l][2].get(), s));
+    if (refined) {
+      int k = 0;
+      if (int rc = ictr_flowrefine_run_level_(ref, pyr_a, pyr_b, n, nch, field, x_only, l, bw12, &k, s)) return rc;
+      count += k;
+    }
+    if (timed) HIPCHK(hipEventRecord(ev.lv[l][3].get(), s));
   }
-  c->timed = c->timing;
-  for (int l = c->lv_f; l >= c->lv_l; --l) {
-    C2fLevel &L = c->lv[l];
-    if (int rc = kC2fSearch[robust][patnorm][x_only][nch == 3](c, pfc, l, refined, s)) return rc;
-    if (int rc = ictr_flowgrid_fill_(L.grid.get(), s)) return rc;
-    if (c->timed) HIPCHK(hipEventRecord(L.ev[1].get(), s));
-    if (int rc = ictr_flowdensify_run_level_(L.dens.get(), L.grid.get(), pyr_a, pyr_b, nch, c->psz, l,
-                                             patnorm ? L.bias : nullptr, s))
-      return rc;
-    if (c->timed) HIPCHK(hipEventRecord(L.ev[2].get(), s));
-    if (refined)
-      if (int rc = ictr_flowrefine_run_level_(L.ref.get(), pyr_a, pyr_b, nch, ictr_flowdensify_device_ptr(L.dens.get()),
-                                              x_only, l, c->bw12.get(), s))
-        return rc;
-    if (c->timed) HIPCHK(hipEventRecord(L.ev[3].get(), s));
-  }
-  if (c->lv_l > 0) {  // the finest level's field to the frame's size
-    const C2fLevel &L = c->lv[c->lv_l];
-    launch_flow_upsample(c2f_field(L, refined), L.w, L.h, c->lv_l, c->up.get(), c->w, c->h, x_only, s);
-    if (c->timed) HIPCHK(hipEventRecord(c->up_done.get(), s));
+  if (c0->lv_l > 0) {  // the finest level's fields to the frame's size
+    UpArgs u;
+    memset(&u, 0, sizeof(u));
+    for (int i = 0; i < n; ++i) {
+      u.src[i] = reinterpret_cast<const float2 *>(c2f_field(m[i]->lv[c0->lv_l], refined));
+      u.out[i] = reinterpret_cast<float2 *>(m[i]->up.get());
+    }
+    const C2fLevel &L = c0->lv[c0->lv_l];
+    launch_flow_upsample(u, n, L.w, L.h, c0->lv_l, c0->w, c0->h, x_only, s);
+    count += 1;
+    if (timed) HIPCHK(hipEventRecord(ev.up_done.get(), s));
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->done.get(), s));
-  c->ran = 1;
-  c->ran_refined = refined;
-  c->ran_patnorm = patnorm;
+  for (int i = 0; i < n; ++i) {
+    ictr_c2fflow *c = m[i];
+    HIPCHK(hipEventRecord(c->done.get(), s));
+    c->ran = 1;
+    c->ran_refined = refined;
+    c->ran_patnorm = patnorm;
+  }
+  if (ops) *ops = count;
   return ICTR_OK;
+}
+// an object's own run on c->channels pyramids per frame (pyr_a[ch], pyr_b[ch]): the walk on a set of one; `who` opens
+// the messages
+static int c2f_run(ictr_c2fflow *c, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, const char *who,
+                   void *hip_stream) {
+  PFArgs pfc[1][3];
+  if (int rc = c2f_run_args(c, pyr_a, pyr_b, who, pfc[0])) return rc;
+  return c2f_walk(&c, 1, pfc, pyr_a, pyr_b, c->ev, nullptr, nullptr, (hipStream_t)hip_stream);
 }
 extern "C" int ictr_c2fflow_run(ictr_c2fflow *c, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b, void *hip_stream) {
   if (!c) return fail(ICTR_ERR_INVALID, "c2fflow is NULL");
@@ -488,13 +573,7 @@ extern "C" int ictr_c2fflow_read_level_bias_rgb(ictr_c2fflow *c, int level, floa
 extern "C" int ictr_c2fflow_get_kernel_ms(ictr_c2fflow *c, float *ms) {
   if (int rc = c2f_wait(c, "c2fflow_get_kernel_ms")) return rc;
   if (!ms) return fail(ICTR_ERR_INVALID, "c2fflow_get_kernel_ms: ms is NULL");
-  for (int l = 0; l <= c->lv_f; ++l)
-    for (int k = 0; k < 3; ++k) {
-      ms[3 * l + k] = 0.0f;
-      if (c->timed && l >= c->lv_l)  // (a level below lv_l has no events)
-        HIPCHK(hipEventElapsedTime(&ms[3 * l + k], c->lv[l].ev[k].get(), c->lv[l].ev[k + 1].get()));
-    }
-  return ICTR_OK;
+  return c->ev.read(c->lv_l, c->lv_f, ms, nullptr);
 }
 extern "C" int ictr_c2fflow_get_lv_l(const ictr_c2fflow *c, int *lv_l) {
   if (!c || !lv_l) return fail(ICTR_ERR_INVALID, "c2fflow_get_lv_l: c2fflow or lv_l is NULL");
@@ -504,9 +583,7 @@ extern "C" int ictr_c2fflow_get_lv_l(const ictr_c2fflow *c, int *lv_l) {
 extern "C" int ictr_c2fflow_get_upsample_ms(ictr_c2fflow *c, float *ms) {
   if (int rc = c2f_wait(c, "c2fflow_get_upsample_ms")) return rc;
   if (!ms) return fail(ICTR_ERR_INVALID, "c2fflow_get_upsample_ms: ms is NULL");
-  *ms = 0.0f;
-  if (c->timed && c->lv_l > 0) HIPCHK(hipEventElapsedTime(ms, c->lv[c->lv_l].ev[3].get(), c->up_done.get()));
-  return ICTR_OK;
+  return c->ev.read(c->lv_l, c->lv_f, nullptr, ms);
 }
 extern "C" int ictr_flow_upsample(const float *src, int w_l, int h_l, int lv, float *out, int w, int h, int x_only,
                                   int on_device, void *hip_stream) {
@@ -520,36 +597,37 @@ extern "C" int ictr_flow_upsample(const float *src, int w_l, int h_l, int lv, fl
                 ew, eh);
   if (int rc = need_device()) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
-  if (on_device) {
-    launch_flow_upsample(src, w_l, h_l, lv, out, w, h, x_only, s);
-    HIPCHK(hipGetLastError());
-    return ICTR_OK;
-  }
   const size_t nsrc = sizeof(float) * 2 * (size_t)w_l * h_l, nout = sizeof(float) * 2 * (size_t)w * h;
   DevBuf<float> dsrc, dout;
-  if (int rc = dsrc.alloc(nsrc)) return rc;
-  if (int rc = dout.alloc(nout)) return rc;
-  HIPCHK(hipMemcpyAsync(dsrc.get(), src, nsrc, hipMemcpyHostToDevice, s));
-  launch_flow_upsample(dsrc.get(), w_l, h_l, lv, dout.get(), w, h, x_only, s);
+  if (!on_device) {
+    if (int rc = dsrc.alloc(nsrc)) return rc;
+    if (int rc = dout.alloc(nout)) return rc;
+    HIPCHK(hipMemcpyAsync(dsrc.get(), src, nsrc, hipMemcpyHostToDevice, s));
+  }
+  UpArgs u;  // a set of one
+  memset(&u, 0, sizeof(u));
+  u.src[0] = reinterpret_cast<const float2 *>(on_device ? src : dsrc.get());
+  u.out[0] = reinterpret_cast<float2 *>(on_device ? out : dout.get());
+  launch_flow_upsample(u, 1, w_l, h_l, lv, w, h, x_only, s);
   HIPCHK(hipGetLastError());
+  if (on_device) return ICTR_OK;
   HIPCHK(hipMemcpyAsync(out, dout.get(), nout, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return ICTR_OK;
 }
 
 // ---------------------------------------------------------------- lockstep sets (include/ictr_c2f_set.h)
-// A set of coarse-to-fine flows of equal shape and parameters, run in lockstep (DESIGN.md §4 "Lockstep sets"): c2f_run's
-// walk over the levels with every stage enqueued once, through the lockstep twins of the kernels. The set holds its
-// members' addresses and owns what no member can: the rowhas block of the fill for all members, the events of a timed
-// run, and the event behind the last run.
+// A set of coarse-to-fine flows of equal shape and parameters, run in lockstep (DESIGN.md §4 "Lockstep sets"): c2f_walk
+// on all of them, every stage enqueued once. The set holds its members' addresses and owns what no member can: the rowhas
+// block of the fill for all members, the events of a timed run, and the event behind the last run.
 static_assert(ICTR_C2FSET_MAX == kSetMax, "ictr_c2f_set.h and ictr_dev.h disagree on the members of a set");
 struct ictr_c2fset {
   int n = 0;
   ictr_c2fflow *m[kSetMax] = {};
-  int timing = 0, timed = 0, ran = 0, ops = 0;
+  int ran = 0, ops = 0;
   DevBuf<int> rowhas;  // [n][the most node rows of a level]
-  Event ev[kC2fMaxLevels][4];  // per level: before the search, after the fill, the densifier, the refiner
-  Event up_done, done;
+  C2fEvents ev;
+  Event done;
 };
 
 // the refusals of members that are missing, doubled or differ from member 0; `who` opens the message
@@ -627,14 +705,10 @@ extern "C" int ictr_c2fset_create(ictr_c2fset **out, ictr_c2fflow *const *member
   s->n = n;
   const ictr_c2fflow *c = members[0];
   int ny = 1;
-  for (int l = c->lv_l; l <= c->lv_f; ++l) {
-    ny = c->lv[l].ny > ny ? c->lv[l].ny : ny;
-    for (Event &e : s->ev[l])
-      if (int rc = e.create()) return rc;
-  }
+  for (int l = c->lv_l; l <= c->lv_f; ++l) ny = c->lv[l].ny > ny ? c->lv[l].ny : ny;
   for (int i = 0; i < n; ++i) s->m[i] = members[i];
   if (int rc = s->rowhas.alloc(sizeof(int) * (size_t)n * ny, true)) return rc;
-  if (int rc = s->up_done.create()) return rc;
+  if (int rc = s->ev.create(c->lv_l, c->lv_f)) return rc;
   if (int rc = s->done.create(hipEventDisableTiming)) return rc;
   *out = s.release();
   return ICTR_OK;
@@ -651,30 +725,9 @@ extern "C" int ictr_c2fset_last_operations(const ictr_c2fset *s, int *ops) {
 }
 extern "C" int ictr_c2fset_set_timing(ictr_c2fset *s, int on) {
   if (!s) return fail(ICTR_ERR_INVALID, "c2fset is NULL");
-  s->timing = on ? 1 : 0;
+  s->ev.timing = on ? 1 : 0;
   return ICTR_OK;
 }
-
-// level l's search of a lockstep run: pfc[m] the level tables of member m's channels
-template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
-static int c2fset_search(const ictr_c2fset *set, const PFArgs (*pfc)[3], int l, int refined, hipStream_t s) {
-  SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> a;
-  memset(&a, 0, sizeof(a));
-  for (int m = 0; m < set->n; ++m)
-    if (int rc = c2f_search_args<MEAN, XONLY, NCH, ROBUST>(set->m[m], pfc[m], l, refined, &a.m[m])) return rc;
-  launch_c2f_level_set(a, set->n, XONLY, s);  // (instantiated in ictr_c2fset.hip and ictr_c2fset_robust.hip)
-  return ICTR_OK;
-}
-using C2fSetSearch = int (*)(const ictr_c2fset *, const PFArgs (*)[3], int, int, hipStream_t);
-#define ICTR_C2F_FORMS(R)                                                                                                  \
-  {                                                                                                                        \
-    {{c2fset_search<false, false, 1, R>, c2fset_search<false, false, 3, R>},                                               \
-     {c2fset_search<false, true, 1, R>, c2fset_search<false, true, 3, R>}},                                                \
-    {{c2fset_search<true, false, 1, R>, c2fset_search<true, false, 3, R>},                                                 \
-     {c2fset_search<true, true, 1, R>, c2fset_search<true, true, 3, R>}}                                                   \
-  }
-static const C2fSetSearch kC2fSetSearch[2][2][2][2] = {ICTR_C2F_FORMS(false), ICTR_C2F_FORMS(true)};
-#undef ICTR_C2F_FORMS
 
 // a lockstep run on `nch` pyramids per member and frame; everything that can be refused is checked before anything is
 // enqueued or any member touched
@@ -698,69 +751,9 @@ static int c2fset_run(ictr_c2fset *set, const ictr_pyramid *const *pyr_a, const 
       return fail(rc, "%s: member %d: %s", who, m, why.c_str());
     }
   hipStream_t s = (hipStream_t)hip_stream;
-  const int refined = c0->refine, patnorm = c0->patnorm, x_only = c0->x_only;
-  const int robust = c0->cost == ICTR_C2F_COST_HUBER;
-  if (nch == 3 && refined)  // as a member's own first refined colour run: each member owns its Bw planes
-    for (int m = 0; m < n; ++m) {
-      ictr_c2fflow *c = set->m[m];
-      const C2fLevel &L = c->lv[c->lv_l];
-      if (!c->bw12)
-        if (int rc = c->bw12.alloc(sizeof(float) * 2 * (size_t)L.w * L.h, true)) return rc;
-    }
-  set->timed = set->timing;
-  int ops = 0;
-  ictr_flowgrid *grid[kSetMax] = {};
-  ictr_flowdensify *dens[kSetMax] = {};
-  ictr_flowrefine *ref[kSetMax] = {};
-  const float *bias[kSetMax] = {}, *field[kSetMax] = {};
-  float *bw12[kSetMax] = {};
-  for (int l = c0->lv_f; l >= c0->lv_l; --l) {
-    for (int m = 0; m < n; ++m) {
-      C2fLevel &L = set->m[m]->lv[l];
-      grid[m] = L.grid.get(), dens[m] = L.dens.get(), ref[m] = L.ref.get();
-      bias[m] = patnorm ? L.bias : nullptr;
-      field[m] = ictr_flowdensify_device_ptr(L.dens.get());
-      bw12[m] = set->m[m]->bw12.get();
-    }
-    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][0].get(), s));
-    if (int rc = kC2fSetSearch[robust][patnorm][x_only][nch == 3](set, pfc, l, refined, s)) return rc;
-    if (int rc = ictr_flowgrid_fill_set_(grid, n, set->rowhas.get(), s)) return rc;
-    ops += 4;  // the search, the memset of rowhas and the fill's two launches
-    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][1].get(), s));
-    if (int rc = ictr_flowdensify_run_level_set_(dens, grid, pyr_a, pyr_b, n, nch, c0->psz, l, bias, s)) return rc;
-    ops += 1;
-    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][2].get(), s));
-    if (refined) {
-      int k = 0;
-      if (int rc = ictr_flowrefine_run_level_set_(ref, pyr_a, pyr_b, n, nch, field, x_only, l, bw12, &k, s)) return rc;
-      ops += k;
-    }
-    if (set->timed) HIPCHK(hipEventRecord(set->ev[l][3].get(), s));
-  }
-  if (c0->lv_l > 0) {  // the finest level's fields to the frame's size
-    UpSetArgs u;
-    memset(&u, 0, sizeof(u));
-    for (int m = 0; m < n; ++m) {
-      u.src[m] = reinterpret_cast<const float2 *>(c2f_field(set->m[m]->lv[c0->lv_l], refined));
-      u.out[m] = reinterpret_cast<float2 *>(set->m[m]->up.get());
-    }
-    const C2fLevel &L = c0->lv[c0->lv_l];
-    launch_flow_upsample_set(u, n, L.w, L.h, c0->lv_l, c0->w, c0->h, x_only, s);
-    ops += 1;
-    if (set->timed) HIPCHK(hipEventRecord(set->up_done.get(), s));
-  }
-  HIPCHK(hipGetLastError());
+  if (int rc = c2f_walk(set->m, n, pfc, pyr_a, pyr_b, set->ev, set->rowhas.get(), &set->ops, s)) return rc;
   HIPCHK(hipEventRecord(set->done.get(), s));
-  for (int m = 0; m < n; ++m) {  // each member as behind its own run, untimed
-    ictr_c2fflow *c = set->m[m];
-    HIPCHK(hipEventRecord(c->done.get(), s));
-    c->timed = 0;
-    c->ran = 1;
-    c->ran_refined = refined;
-    c->ran_patnorm = patnorm;
-  }
   set->ran = 1;
-  set->ops = ops;
   return ICTR_OK;
 }
 extern "C" int ictr_c2fset_run(ictr_c2fset *s, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b,
@@ -776,15 +769,5 @@ extern "C" int ictr_c2fset_get_kernel_ms(ictr_c2fset *s, float *ms, float *upsam
   if (!s->ran) return fail(ICTR_ERR_STATE, "c2fset_get_kernel_ms: no run yet");
   if (!ms) return fail(ICTR_ERR_INVALID, "c2fset_get_kernel_ms: ms is NULL");
   HIPCHK(hipEventSynchronize(s->done.get()));
-  const ictr_c2fflow *c = s->m[0];
-  for (int l = 0; l <= c->lv_f; ++l)
-    for (int k = 0; k < 3; ++k) {
-      ms[3 * l + k] = 0.0f;
-      if (s->timed && l >= c->lv_l) HIPCHK(hipEventElapsedTime(&ms[3 * l + k], s->ev[l][k].get(), s->ev[l][k + 1].get()));
-    }
-  if (upsample_ms) {
-    *upsample_ms = 0.0f;
-    if (s->timed && c->lv_l > 0) HIPCHK(hipEventElapsedTime(upsample_ms, s->ev[c->lv_l][3].get(), s->up_done.get()));
-  }
-  return ICTR_OK;
+  return s->ev.read(s->m[0]->lv_l, s->m[0]->lv_f, ms, upsample_ms);
 }

@@ -1,11 +1,11 @@
 // ictr_c2fflow_dev.h -- k_c2f_level, the per-level search kernel of the coarse-to-fine dense flow, with its arguments and
-// its launcher, for the two files that instantiate it: ictr_c2fflow.hip the L2 forms (which keeps that file's device code
-// what it was before the ROBUST forms existed, to the instruction: more kernels in one module move the compiler's
-// schedule of three of the two-wave forms by an instruction or two), ictr_c2fflow_robust.hip the ROBUST forms (the Huber
-// patch cost, DESIGN.md "Robust patch cost"). The forms are described at the head of ictr_c2fflow.hip.
-// The kernel's body is c2f_level_body, which the lockstep twin k_c2f_level_set runs per member of a set of coarse-to-fine
-// flows (DESIGN.md "Lockstep sets"); its forms are instantiated in ictr_c2fset.hip (L2) and ictr_c2fset_robust.hip
-// (ROBUST). k_flow_upsample's body is here for the same reason.
+// its launcher, for the two files that instantiate it: ictr_c2fflow.hip the L2 forms, ictr_c2fflow_robust.hip the ROBUST
+// forms (the Huber patch cost, DESIGN.md "Robust patch cost"), in a module of their own because more kernels in one module
+// move the compiler's schedule of some of the two-wave forms by an instruction or two. The forms are described at the head
+// of ictr_c2fflow.hip.
+// The kernel runs on 1 .. kSetMax coarse-to-fine flows of one shape at once (DESIGN.md "Lockstep sets"): its argument is
+// a SetArgs block, the arguments of one flow per member, and a workgroup runs c2f_level_body on member blockIdx.y's. A
+// single object's run is a set of one.
 #pragma once
 
 #include <type_traits>
@@ -59,7 +59,7 @@ __device__ __forceinline__ PFPlanes c2f_planes(const C2fArgs<MEAN, NCH> &a, int 
 // widest (H with three sums of T) carries six values in one trip. Restated by tests/c2frgb_f32.py.
 // ROBUST is the Huber patch cost: pf_level_search_ch's ROBUST forms with a.huber_k; the start, the hold rules, the MEAN
 // tail and what is written are unchanged. Restated by tests/c2fcost_f32.py.
-// The body is stated once, for k_c2f_level and for its lockstep twin k_c2f_level_set (below).
+// The body of k_c2f_level (below) for one member, whose arguments it takes by value.
 template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH, bool ROBUST>
 __device__ __forceinline__ void c2f_level_body(C2fArgsOf<MEAN, NCH, ROBUST> a) {
   static_assert(NCH == 1 || NCH == 3, "one channel or three");
@@ -142,104 +142,41 @@ __device__ __forceinline__ void c2f_level_body(C2fArgsOf<MEAN, NCH, ROBUST> a) {
   }
 }
 
+// a member's workgroups along x, the members along y
 template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH = 1, bool ROBUST = false>
-__global__ __launch_bounds__(kBlock) void k_c2f_level(C2fArgsOf<MEAN, NCH, ROBUST> a) {
-  c2f_level_body<NPL, WPP, MEAN, XONLY, NCH, ROBUST>(a);
-}
-// The lockstep twin (DESIGN.md "Lockstep sets"): the same workgroups along x, once per member along y.
-template <int NPL, int WPP, bool MEAN, bool XONLY, int NCH = 1, bool ROBUST = false>
-__global__ __launch_bounds__(kBlock) void k_c2f_level_set(SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> s) {
+__global__ __launch_bounds__(kBlock) void k_c2f_level(SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> s) {
   static_assert(sizeof(s) <= kKernargLimit, "the argument block of a set exceeds the kernel-argument limit");
   c2f_level_body<NPL, WPP, MEAN, XONLY, NCH, ROBUST>(s.m[blockIdx.y]);
 }
 
-// the form follows from the patch size alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two
+// The search of n members (1 .. kSetMax, of one shape: member 0's stands for all). The form follows from the patch size
+// alone, as launch_patchdisp's: up to 4 pixels per lane one wave per node, above two; x_only selects the XONLY forms.
 template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
-inline void launch_c2f_level(const C2fArgsOf<MEAN, NCH, ROBUST> &a, hipStream_t s) {
-  const int npl = (a.P * a.P + 63) / 64;
+inline void launch_c2f_level_form(const SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> &a, int n, hipStream_t s) {
+  const int npl = (a.m[0].P * a.m[0].P + 63) / 64, K = a.m[0].K;
   const dim3 blk(kBlock);
   if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY, NCH, ROBUST>), dim3((a.K + kWaves / 2 - 1) / (kWaves / 2)), blk, 0, s,
+    hipLaunchKernelGGL((k_c2f_level<8, 2, MEAN, XONLY, NCH, ROBUST>), dim3((K + kWaves / 2 - 1) / (kWaves / 2), n), blk, 0, s,
                        a);
     return;
   }
-  const dim3 g((a.K + kWaves - 1) / kWaves);
+  const dim3 g((K + kWaves - 1) / kWaves, n);
   if (npl <= 1)
     hipLaunchKernelGGL((k_c2f_level<1, 1, MEAN, XONLY, NCH, ROBUST>), g, blk, 0, s, a);
   else
     hipLaunchKernelGGL((k_c2f_level<4, 1, MEAN, XONLY, NCH, ROBUST>), g, blk, 0, s, a);
 }
-
-// k_flow_upsample's body (the kernel is described at the head of ictr_c2fflow.hip), for it and for its lockstep twin.
-// s = 2^lv, inv_s = 2^-lv. Everything before the taps is exact in f32 (x + 0.5, the product with 2^-lv, - 0.5, rx,
-// 1 - rx); the six products and three sums are taken in the order written, each rounded (no contraction), then s * val.
-template <bool XONLY>
-__device__ __forceinline__ void flow_upsample_body(const float2 *__restrict__ src, int wl, int hl, float inv_s, float s,
-                                                   float2 *__restrict__ out, int w, int h) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * kWaves + (threadIdx.x >> 6);
-  if (x >= w || y >= h) return;
-  const float fx = fminf(fmaxf(((float)x + 0.5f) * inv_s - 0.5f, 0.0f), (float)(wl - 1));
-  const float fy = fminf(fmaxf(((float)y + 0.5f) * inv_s - 0.5f, 0.0f), (float)(hl - 1));
-  const int x0 = (int)fx, y0 = (int)fy;  // fx, fy >= 0: the cast is the floor
-  const int x1 = min(x0 + 1, wl - 1), y1 = min(y0 + 1, hl - 1);
-  const float rx = fx - (float)x0, ry = fy - (float)y0;
-  const float qx = 1.0f - rx, qy = 1.0f - ry;
-  const size_t r0 = (size_t)y0 * wl, r1 = (size_t)y1 * wl;
-  float2 o;
-  if constexpr (XONLY) {  // y is not read and is +0.0
-    const float *f = reinterpret_cast<const float *>(src);
-    const float top = qx * f[2 * (r0 + x0)] + rx * f[2 * (r0 + x1)];
-    const float bot = qx * f[2 * (r1 + x0)] + rx * f[2 * (r1 + x1)];
-    o.x = s * (qy * top + ry * bot);
-    o.y = 0.0f;
-  } else {
-    const float2 a = src[r0 + x0], b = src[r0 + x1], c = src[r1 + x0], d = src[r1 + x1];
-    const float tx = qx * a.x + rx * b.x, bx = qx * c.x + rx * d.x;
-    const float ty = qx * a.y + rx * b.y, by = qx * c.y + rx * d.y;
-    o.x = s * (qy * tx + ry * bx);
-    o.y = s * (qy * ty + ry * by);
-  }
-  out[(size_t)y * w + x] = o;
-}
-
-// the fields a lockstep k_flow_upsample reads and writes, per member
-struct UpSetArgs {
-  const float2 *src[kSetMax];
-  float2 *out[kSetMax];
-};
-void launch_flow_upsample_set(const UpSetArgs &a, int n, int wl, int hl, int lv, int w, int h, int x_only, hipStream_t s);
-
-// the lockstep twin's launch: k_c2f_level's grid along x, the n members along y
-template <bool MEAN, bool XONLY, int NCH, bool ROBUST>
-inline void launch_c2f_level_set(const SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> &a, int n, hipStream_t s) {
-  const int npl = (a.m[0].P * a.m[0].P + 63) / 64, K = a.m[0].K;
-  const dim3 blk(kBlock);
-  if (npl > 4) {
-    hipLaunchKernelGGL((k_c2f_level_set<8, 2, MEAN, XONLY, NCH, ROBUST>), dim3((K + kWaves / 2 - 1) / (kWaves / 2), n), blk, 0,
-                       s, a);
-    return;
-  }
-  const dim3 g((K + kWaves - 1) / kWaves, n);
-  if (npl <= 1)
-    hipLaunchKernelGGL((k_c2f_level_set<1, 1, MEAN, XONLY, NCH, ROBUST>), g, blk, 0, s, a);
+template <bool MEAN, int NCH, bool ROBUST>
+void launch_c2f_level(const SetArgs<C2fArgsOf<MEAN, NCH, ROBUST>> &a, int n, int x_only, hipStream_t s) {
+  if (x_only)
+    launch_c2f_level_form<MEAN, true, NCH, ROBUST>(a, n, s);
   else
-    hipLaunchKernelGGL((k_c2f_level_set<4, 1, MEAN, XONLY, NCH, ROBUST>), g, blk, 0, s, a);
+    launch_c2f_level_form<MEAN, false, NCH, ROBUST>(a, n, s);
 }
-// the lockstep forms' launchers, by [patnorm][channels]; x_only selects the XONLY form: the L2 forms (ictr_c2fset.hip)
-// and the ROBUST ones (ictr_c2fset_robust.hip), in modules of their own like the ROBUST twins
-void launch_c2f_level_set(const SetArgs<C2fArgs<false, 1>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgs<false, 3>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgs<true, 1>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgs<true, 3>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgsRobust<false, 1>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgsRobust<false, 3>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgsRobust<true, 1>> &a, int n, int x_only, hipStream_t s);
-void launch_c2f_level_set(const SetArgs<C2fArgsRobust<true, 3>> &a, int n, int x_only, hipStream_t s);
-
-// the ROBUST forms' launchers (ictr_c2fflow_robust.hip), by [patnorm][channels]; x_only selects the XONLY form
-void launch_c2f_level_robust(const C2fArgsRobust<false, 1> &a, int x_only, hipStream_t s);
-void launch_c2f_level_robust(const C2fArgsRobust<false, 3> &a, int x_only, hipStream_t s);
-void launch_c2f_level_robust(const C2fArgsRobust<true, 1> &a, int x_only, hipStream_t s);
-void launch_c2f_level_robust(const C2fArgsRobust<true, 3> &a, int x_only, hipStream_t s);
+// the ROBUST forms are instantiated in ictr_c2fflow_robust.hip alone
+extern template void launch_c2f_level<false, 1, true>(const SetArgs<C2fArgsRobust<false, 1>> &, int, int, hipStream_t);
+extern template void launch_c2f_level<false, 3, true>(const SetArgs<C2fArgsRobust<false, 3>> &, int, int, hipStream_t);
+extern template void launch_c2f_level<true, 1, true>(const SetArgs<C2fArgsRobust<true, 1>> &, int, int, hipStream_t);
+extern template void launch_c2f_level<true, 3, true>(const SetArgs<C2fArgsRobust<true, 3>> &, int, int, hipStream_t);
 
 }  // namespace ictr

@@ -6,16 +6,9 @@
 
 namespace ictr {
 
-template <bool MEAN, int NCH>
-static void launch_robust(const C2fArgsRobust<MEAN, NCH> &a, int x_only, hipStream_t s) {
-  if (x_only)
-    launch_c2f_level<MEAN, true, NCH, true>(a, s);
-  else
-    launch_c2f_level<MEAN, false, NCH, true>(a, s);
-}
-void launch_c2f_level_robust(const C2fArgsRobust<false, 1> &a, int x_only, hipStream_t s) { launch_robust(a, x_only, s); }
-void launch_c2f_level_robust(const C2fArgsRobust<false, 3> &a, int x_only, hipStream_t s) { launch_robust(a, x_only, s); }
-void launch_c2f_level_robust(const C2fArgsRobust<true, 1> &a, int x_only, hipStream_t s) { launch_robust(a, x_only, s); }
-void launch_c2f_level_robust(const C2fArgsRobust<true, 3> &a, int x_only, hipStream_t s) { launch_robust(a, x_only, s); }
+template void launch_c2f_level<false, 1, true>(const SetArgs<C2fArgsRobust<false, 1>> &, int, int, hipStream_t);
+template void launch_c2f_level<false, 3, true>(const SetArgs<C2fArgsRobust<false, 3>> &, int, int, hipStream_t);
+template void launch_c2f_level<true, 1, true>(const SetArgs<C2fArgsRobust<true, 1>> &, int, int, hipStream_t);
+template void launch_c2f_level<true, 3, true>(const SetArgs<C2fArgsRobust<true, 3>> &, int, int, hipStream_t);
 
 }  // namespace ictr

@@ -68,7 +68,7 @@ using DzRec = std::conditional_t<BIAS, DzRecBias<NCH>, float2>;
 
 // BIAS: the vote weighs |Bw - A - beta| with the node's beta (the coarse-to-fine flow under patch-mean normalisation).
 // NCH: the planes per frame. The rule's only fork is how e is formed: one channel takes |r|, with no division.
-// The body is stated once, for k_densify and for its lockstep twin k_densify_set.
+// The body of k_densify (below) for one member, whose arguments it takes by value.
 template <bool BIAS, int NCH>
 __device__ __forceinline__ void dz_body(DzArgsT<NCH> a) {
   static_assert(NCH == 1 || NCH == 3, "one channel or three");
@@ -146,14 +146,10 @@ __device__ __forceinline__ void dz_body(DzArgsT<NCH> a) {
   a.cnt[o] = (float)n;
   a.sw[o] = sw;
 }
+// 1 .. kSetMax densifiers of one geometry at once (DESIGN.md §4 "Lockstep sets"; a single densifier is a set of one): a
+// member's workgroups along x and y, the members along z. One count of dynamic LDS serves them all.
 template <bool BIAS, int NCH>
-__global__ __launch_bounds__(kBlock) void k_densify(DzArgsT<NCH> a) {
-  dz_body<BIAS, NCH>(a);
-}
-// The lockstep twin (DESIGN.md §4 "Lockstep sets"): k_densify's workgroups along x and y, once per member along z. The
-// members agree in geometry, so one count of dynamic LDS serves them all.
-template <bool BIAS, int NCH>
-__global__ __launch_bounds__(kBlock) void k_densify_set(SetArgs<DzArgsT<NCH>> s) {
+__global__ __launch_bounds__(kBlock) void k_densify(SetArgs<DzArgsT<NCH>> s) {
   static_assert(sizeof(s) <= kKernargLimit, "the argument block of a set exceeds the kernel-argument limit");
   dz_body<BIAS, NCH>(s.m[blockIdx.z]);
 }
@@ -247,43 +243,13 @@ static int dz_args(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_py
   *out_lds = lds;
   return ICTR_OK;
 }
-// One run on level `level` of NCH pyramids per frame (grid and object of that level's size); bias: the grid's node bias
-// [ny][nx][NCH] on the device (NULL: none, k_densify<false, NCH>)
+// n densifiers of one size on level `level` of NCH pyramids per member and frame (grids and objects of that level's
+// size), one launch: member m reads grid[m], the node bias bias[m] [ny][nx][NCH] on the device (all NULL: none,
+// k_densify<false, NCH>) and the pyramids pyr_a[m * NCH + c], pyr_b[m * NCH + c]. Untimed, and no member's own event is
+// recorded: that is the caller's to do behind the run.
 template <int NCH>
-static int dz_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
-                  const ictr_pyramid *const *pyr_b, int psz, int level, const float *bias, hipStream_t s) {
-  DzArgsT<NCH> a;
-  size_t lds = 0;
-  if (int rc = dz_args<NCH>(z, grid, pyr_a, pyr_b, psz, level, bias, &a, &lds)) return rc;
-  z->timed = z->timing;
-  if (z->timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
-  if (bias)
-    hipLaunchKernelGGL((k_densify<true, NCH>), pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
-  else
-    hipLaunchKernelGGL((k_densify<false, NCH>), pixel_rows_grid(z->w, z->h), dim3(kBlock), lds, s, a);
-  if (z->timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
-  HIPCHK(hipGetLastError());
-  return z->res.record(s);
-}
-
-extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
-                                    const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
-  return dz_run<1>(z, grid, &pyr_a, &pyr_b, psz, 0, nullptr, (hipStream_t)hip_stream);
-}
-// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per frame
-extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
-                                           const ictr_pyramid *const *pyr_b, int channels, int psz, int level,
-                                           const float *bias, void *hip_stream) {
-  return channels == 3 ? dz_run<3>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream)
-                       : dz_run<1>(z, grid, pyr_a, pyr_b, psz, level, bias, (hipStream_t)hip_stream);
-}
-
-// n densifiers of one size in lockstep, one launch: member m reads grid[m], bias[m] (all NULL, or none) and the pyramids
-// pyr_a[m * channels + c], pyr_b[m * channels + c]. Untimed, and no member's own event is recorded: the caller's event
-// behind the whole run stands for them.
-template <int NCH>
-static int dz_run_set(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid, const ictr_pyramid *const *pyr_a,
-                      const ictr_pyramid *const *pyr_b, int n, int psz, int level, const float *const *bias, hipStream_t s) {
+static int dz_run(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid, const ictr_pyramid *const *pyr_a,
+                  const ictr_pyramid *const *pyr_b, int n, int psz, int level, const float *const *bias, hipStream_t s) {
   SetArgs<DzArgsT<NCH>> a;
   memset(&a, 0, sizeof(a));
   size_t lds = 0;
@@ -291,26 +257,40 @@ static int dz_run_set(ictr_flowdensify *const *z, const ictr_flowgrid *const *gr
     size_t l = 0;
     if (int rc = dz_args<NCH>(z[m], grid[m], pyr_a + m * NCH, pyr_b + m * NCH, psz, level, bias[m], &a.m[m], &l)) return rc;
     if (m > 0 && (l != lds || z[m]->w != z[0]->w || z[m]->h != z[0]->h || !bias[m] != !bias[0]))
-      return fail(ICTR_ERR_INVALID, "flowdensify_run_set: member %d differs in geometry", m);
+      return fail(ICTR_ERR_INVALID, "flowdensify_run: member %d differs in geometry", m);
     lds = l;
   }
   dim3 g = pixel_rows_grid(z[0]->w, z[0]->h);
   g.z = n;
   if (bias[0])
-    hipLaunchKernelGGL((k_densify_set<true, NCH>), g, dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL((k_densify<true, NCH>), g, dim3(kBlock), lds, s, a);
   else
-    hipLaunchKernelGGL((k_densify_set<false, NCH>), g, dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL((k_densify<false, NCH>), g, dim3(kBlock), lds, s, a);
   HIPCHK(hipGetLastError());
   for (int m = 0; m < n; ++m) z[m]->timed = 0;
   return ICTR_OK;
 }
-extern "C" int ictr_flowdensify_run_level_set_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
-                                               const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
-                                               int channels, int psz, int level, const float *const *bias, void *hip_stream) {
+// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per member and frame
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
+                                           const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                                           int channels, int psz, int level, const float *const *bias, void *hip_stream) {
   if (!z || !grid || !pyr_a || !pyr_b || !bias || n < 1 || n > kSetMax)
-    return fail(ICTR_ERR_INVALID, "flowdensify_run_set: bad arguments");
-  return channels == 3 ? dz_run_set<3>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream)
-                       : dz_run_set<1>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream);
+    return fail(ICTR_ERR_INVALID, "flowdensify_run: bad arguments");
+  return channels == 3 ? dz_run<3>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream)
+                       : dz_run<1>(z, grid, pyr_a, pyr_b, n, psz, level, bias, (hipStream_t)hip_stream);
+}
+// a densifier's own run: a set of one at level 0 without bias, with its timing events around it and its result event behind
+extern "C" int ictr_flowdensify_run(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *pyr_a,
+                                    const ictr_pyramid *pyr_b, int psz, void *hip_stream) {
+  if (!z) return fail(ICTR_ERR_INVALID, "flowdensify is NULL");
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int timed = z->timing;
+  const float *bias = nullptr;
+  if (timed) HIPCHK(hipEventRecord(z->ev0.get(), s));
+  if (int rc = ictr_flowdensify_run_level_(&z, &grid, &pyr_a, &pyr_b, 1, 1, psz, 0, &bias, s)) return rc;
+  if (timed) HIPCHK(hipEventRecord(z->ev1.get(), s));
+  z->timed = timed;
+  return z->res.record(s);
 }
 
 // the parameters a set compares its members' densifiers by

@@ -212,9 +212,10 @@ struct PFArgs {
   float min_hx;      // k_patchdisp: the patch is kept iff hxx > min_hx * (hxx + hyy)
 };
 
-// The argument block of a lockstep kernel (DESIGN.md §4 "Lockstep sets"): the arguments of its twin once per member of a
-// set of coarse-to-fine flows, by value in the kernel arguments. A workgroup takes item m = its block index along the grid
-// dimension the twin does not use: the index is uniform, so the item's fields come by scalar loads as the twin's do.
+// The argument block of a kernel of the coarse-to-fine flow (DESIGN.md §4 "Lockstep sets"): a stage's arguments once per
+// member of a set of flows (a single object is a set of one), by value in the kernel arguments. A workgroup takes item
+// m = its block index along the grid dimension the stage does not use: the index is uniform, so the item's fields come by
+// scalar loads at a computed offset.
 constexpr int kSetMax = 8;
 constexpr size_t kKernargLimit = 4096;  // bytes of kernel arguments a launch may carry
 template <class A>

@@ -17,6 +17,9 @@
 // k_fr_final adds the last (du, dv) into the interleaved result. Memory bound throughout: plain vector loads and stores,
 // no atomics. Everything is enqueued on the caller's stream; run waits for nothing but the copy of a field that lives in
 // host memory.
+// Every kernel takes the arguments of 1 .. kSetMax refiners of one size and one set of parameters (DESIGN.md §4 "Lockstep
+// sets") and runs its body on member m's, m the block index along the grid dimension the stage does not use: y for the
+// two linear kernels, z for the others. A refiner's own run is a set of one.
 #include <math.h>
 #include <string.h>
 
@@ -52,18 +55,14 @@ struct FrArgsT {
 // are (fr_args<1>).
 using FrArgs = FrArgsT<1>;
 
+// The bodies, each for one member, whose arguments it takes by value; the kernels are below them.
 // interleaved (u, v) -> the two working planes
-// Every kernel's body is stated once, for the kernel and for its lockstep twin (k_fr_*_set, below the kernels).
 __device__ __forceinline__ void fr_init_body(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v, int n) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const float2 f = f0[i];
   u[i] = f.x;
   v[i] = f.y;
-}
-__global__ __launch_bounds__(kBlock) void k_fr_init(const float2 *__restrict__ f0, float *__restrict__ u, float *__restrict__ v,
-                                                    int n) {
-  fr_init_body(f0, u, v, n);
 }
 // (a flow grid's dense field is formed by launch_fg_dense: ictr_flowgrid_dev.h)
 
@@ -100,10 +99,6 @@ __device__ __forceinline__ void fr_warp_body(FrArgsT<NCH> a, int fold) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) a.bw[c][i] = fr_bilinear(a.B[c], a.sb, a.w, a.h, (float)X + u, (float)Y + v);
   }
-}
-template <int NCH>
-__global__ __launch_bounds__(kBlock) void k_fr_warp(FrArgsT<NCH> a, int fold) {
-  fr_warp_body<NCH>(a, fold);
 }
 
 // a tile with its halo; (cx, cy) are tile coordinates, the frame coordinate is (gx0 + cx, gy0 + cy)
@@ -192,7 +187,6 @@ __device__ __forceinline__ void fr_coef_body(FrArgsT<1> a) {
   a.du[i] = 0.0f;
   a.dv[i] = 0.0f;
 }
-__global__ __launch_bounds__(kBlock) void k_fr_coef(FrArgsT<1> a) { fr_coef_body(a); }
 
 // The colour form of the coefficient stage (DESIGN.md §4 "Colour"): three planes per frame and three Bw planes. Steps 1
 // and 2 run per channel, n0, n1, n2 are per channel; the two robust weights are joint over the channels, taken on the
@@ -262,7 +256,6 @@ __device__ __forceinline__ void fr_coef_rgb_body(FrArgsT<3> a) {
   a.du[i] = 0.0f;
   a.dv[i] = 0.0f;
 }
-__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(FrArgsT<3> a) { fr_coef_rgb_body(a); }
 
 // One half-sweep. A lane owns one pixel of the active colour: x = 2 p + ((y + COLOUR) & 1). The reads of du / dv / u / v
 // of a wave cover whole lines (the pixel and its two row neighbours alternate), and so do those of the coefficient
@@ -294,10 +287,6 @@ __device__ __forceinline__ void fr_sor_body(FrArgs a) {
   const float sv = ((sl + sr) + st) + sd;
   a.dv[i] = (1.0f - om) * dv + om * ((((a.b2[c] - a12 * dun) + sv) - sw * v) / (a.a22[c] + sw));
 }
-template <int COLOUR>
-__global__ __launch_bounds__(kBlock) void k_fr_sor(FrArgs a) {
-  fr_sor_body<COLOUR>(a);
-}
 
 // step 6 of the last outer iteration, into the interleaved result; u and v keep the last outer iteration's field
 __device__ __forceinline__ void fr_final_body(FrArgs a, float2 *__restrict__ out) {
@@ -306,33 +295,30 @@ __device__ __forceinline__ void fr_final_body(FrArgs a, float2 *__restrict__ out
   const float v = a.v[i];
   out[i] = make_float2(a.u[i] + a.du[i], a.x_only ? v : v + a.dv[i]);
 }
-__global__ __launch_bounds__(kBlock) void k_fr_final(FrArgs a, float2 *__restrict__ out) { fr_final_body(a, out); }
 
-// The lockstep twins (DESIGN.md §4 "Lockstep sets"): the refiners of a set of coarse-to-fine flows, which agree in size
-// and parameters. Each runs its kernel's body on member m's arguments, m the block index along the grid dimension the
-// kernel does not use: y for the two linear kernels, z for the others.
-struct FrIoSet {
+// The kernels: each body on member m's arguments.
+struct FrIo {
   const float2 *f0[kSetMax];  // per member the field a run starts from ...
   float2 *out[kSetMax];       // ... and its result
 };
 using FrSet = SetArgs<FrArgs>;
-static_assert(sizeof(SetArgs<FrArgsT<3>>) <= kKernargLimit && sizeof(FrSet) + sizeof(FrIoSet) <= kKernargLimit,
+static_assert(sizeof(SetArgs<FrArgsT<3>>) <= kKernargLimit && sizeof(FrSet) + sizeof(FrIo) <= kKernargLimit,
               "the argument block of a set exceeds the kernel-argument limit");
-__global__ __launch_bounds__(kBlock) void k_fr_init_set(FrSet s, FrIoSet io, int n) {
+__global__ __launch_bounds__(kBlock) void k_fr_init(FrSet s, FrIo io, int n) {
   const int m = blockIdx.y;
   fr_init_body(io.f0[m], s.m[m].u, s.m[m].v, n);
 }
 template <int NCH>
-__global__ __launch_bounds__(kBlock) void k_fr_warp_set(SetArgs<FrArgsT<NCH>> s, int fold) {
+__global__ __launch_bounds__(kBlock) void k_fr_warp(SetArgs<FrArgsT<NCH>> s, int fold) {
   fr_warp_body<NCH>(s.m[blockIdx.z], fold);
 }
-__global__ __launch_bounds__(kBlock) void k_fr_coef_set(SetArgs<FrArgsT<1>> s) { fr_coef_body(s.m[blockIdx.z]); }
-__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb_set(SetArgs<FrArgsT<3>> s) { fr_coef_rgb_body(s.m[blockIdx.z]); }
+__global__ __launch_bounds__(kBlock) void k_fr_coef(SetArgs<FrArgsT<1>> s) { fr_coef_body(s.m[blockIdx.z]); }
+__global__ __launch_bounds__(kBlock) void k_fr_coef_rgb(SetArgs<FrArgsT<3>> s) { fr_coef_rgb_body(s.m[blockIdx.z]); }
 template <int COLOUR>
-__global__ __launch_bounds__(kBlock) void k_fr_sor_set(FrSet s) {
+__global__ __launch_bounds__(kBlock) void k_fr_sor(FrSet s) {
   fr_sor_body<COLOUR>(s.m[blockIdx.z]);
 }
-__global__ __launch_bounds__(kBlock) void k_fr_final_set(FrSet s, FrIoSet io) {
+__global__ __launch_bounds__(kBlock) void k_fr_final(FrSet s, FrIo io) {
   const int m = blockIdx.y;
   fr_final_body(s.m[m], io.out[m]);
 }
@@ -389,8 +375,10 @@ static FrArgsT<NCH> fr_args(const ictr_flowrefine *r, int x_only) {
   a.x_only = x_only ? 1 : 0;
   return a;
 }
-static void fr_half_sweep(const ictr_flowrefine *r, const FrArgs &a, int colour, hipStream_t s) {
-  const dim3 g = pixel_rows_grid((r->w + 1) / 2, r->h);
+// one half-sweep of n refiners of r's size
+static void fr_half_sweep(const ictr_flowrefine *r, const FrSet &a, int n, int colour, hipStream_t s) {
+  dim3 g = pixel_rows_grid((r->w + 1) / 2, r->h);
+  g.z = n;
   if (colour == 0)
     hipLaunchKernelGGL(k_fr_sor<0>, g, dim3(kBlock), 0, s, a);
   else
@@ -456,52 +444,93 @@ static int fr_frame_args(const ictr_flowrefine *r, const ictr_pyramid *const *py
   return ICTR_OK;
 }
 
-// The launch sequence of a run from the device field f0 [h][w][2]. timed: an event of r->ev at every mark.
+// The launch sequence of a run of n refiners of one size and one set of parameters, each stage once, on level `level` of
+// NCH pyramids per member and frame. Member m starts from the device field field[m] [h][w][2] and reads the pyramids
+// pyr_a[m * NCH + c], pyr_b[m * NCH + c]; bw12[m] as in fr_frame_args. ev (NULL: untimed): the events of a timed run, one
+// recorded at every mark; *nev takes their number. No member's result event is recorded: that is the caller's to do behind
+// the run. *ops takes the launches (and, with n_outer = 0, the copies, one per member) enqueued.
 template <int NCH>
-static int fr_run(ictr_flowrefine *r, const FrArgsT<NCH> &a, const float *f0, bool timed, hipStream_t s) {
-  const size_t n = (size_t)r->w * r->h;
-  const FrArgs g = fr_args<1>(r, a.x_only);  // of the half-sweeps and k_fr_final
-  r->nev = 0;
+static int fr_run(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                  const float *const *field, int x_only, int level, float *const *bw12, int *ops,
+                  const std::vector<Event> *ev, int *nev, hipStream_t s) {
+  SetArgs<FrArgsT<NCH>> a;
+  FrSet g;  // of the half-sweeps, k_fr_init and k_fr_final
+  FrIo io;
+  memset(&a, 0, sizeof(a));
+  memset(&g, 0, sizeof(g));
+  memset(&io, 0, sizeof(io));
+  const ictr_flowrefine *r0 = r[0];
+  for (int m = 0; m < n; ++m) {
+    if (!r[m] || !field[m] || (NCH == 3 && !bw12[m]))
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: member %d: the refiner, the field or the Bw planes are NULL", m);
+    if (r[m]->w != r0->w || r[m]->h != r0->h || r[m]->n_outer != r0->n_outer || r[m]->n_sor != r0->n_sor)
+      return fail(ICTR_ERR_INVALID, "flowrefine_run: member %d differs in size or iteration counts", m);
+    if (int rc = fr_frame_args<NCH>(r[m], pyr_a + m * NCH, pyr_b + m * NCH, x_only, level, bw12[m], &a.m[m])) return rc;
+    g.m[m] = fr_args<1>(r[m], x_only);
+    io.f0[m] = reinterpret_cast<const float2 *>(field[m]);
+    io.out[m] = reinterpret_cast<float2 *>(r[m]->res.get());
+  }
+  const size_t np = (size_t)r0->w * r0->h;
+  int count = 0, marks = 0;
   auto mark = [&]() {
-    if (timed) (void)hipEventRecord(r->ev[r->nev++].get(), s);
+    if (ev) (void)hipEventRecord((*ev)[marks++].get(), s);
   };
-  if (r->n_outer == 0) {  // the input's bits
-    HIPCHK(hipMemcpyAsync(r->res.get(), f0, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, s));
+  if (r0->n_outer == 0) {  // the input's bits
+    for (int m = 0; m < n; ++m, ++count)
+      HIPCHK(hipMemcpyAsync(r[m]->res.get(), field[m], sizeof(float) * 2 * np, hipMemcpyDeviceToDevice, s));
   } else {
-    const dim3 blk(kBlock), lin((unsigned)((n + kBlock - 1) / kBlock));
-    const dim3 tiles((r->w + kFrTile - 1) / kFrTile, (r->h + kFrTile - 1) / kFrTile);
+    const dim3 blk(kBlock), lin((unsigned)((np + kBlock - 1) / kBlock), n);
+    const dim3 tiles((r0->w + kFrTile - 1) / kFrTile, (r0->h + kFrTile - 1) / kFrTile, n);
+    dim3 rows = pixel_rows_grid(r0->w, r0->h);
+    rows.z = n;
     mark();
-    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, reinterpret_cast<const float2 *>(f0), a.u, a.v, (int)n);
+    hipLaunchKernelGGL(k_fr_init, lin, blk, 0, s, g, io, (int)np);
     mark();
-    for (int o = 0; o < r->n_outer; ++o) {
+    for (int o = 0; o < r0->n_outer; ++o) {
       mark();
-      hipLaunchKernelGGL(k_fr_warp<NCH>, pixel_rows_grid(r->w, r->h), blk, 0, s, a, o > 0 ? 1 : 0);
+      hipLaunchKernelGGL(k_fr_warp<NCH>, rows, blk, 0, s, a, o > 0 ? 1 : 0);
       mark();
       if constexpr (NCH == 1)
         hipLaunchKernelGGL(k_fr_coef, tiles, blk, 0, s, a);
       else
         hipLaunchKernelGGL(k_fr_coef_rgb, tiles, blk, 0, s, a);
       mark();
-      for (int k = 0; k < r->n_sor; ++k) {
-        fr_half_sweep(r, g, 0, s);
-        fr_half_sweep(r, g, 1, s);
+      for (int k = 0; k < r0->n_sor; ++k) {
+        fr_half_sweep(r0, g, n, 0, s);
+        fr_half_sweep(r0, g, n, 1, s);
       }
       mark();
     }
     mark();
-    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, g, reinterpret_cast<float2 *>(r->res.get()));
+    hipLaunchKernelGGL(k_fr_final, lin, blk, 0, s, g, io);
     mark();
+    count = 2 + r0->n_outer * (2 + 2 * r0->n_sor);
   }
   HIPCHK(hipGetLastError());
-  return r->res.record(s);
+  for (int m = 0; m < n; ++m) r[m]->nev = 0;
+  if (ops) *ops = count;
+  if (nev) *nev = marks;
+  return ICTR_OK;
+}
+// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per member and frame,
+// the fields on the device; untimed (the stage's events are the caller's)
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
+                                          const ictr_pyramid *const *pyr_b, int n, int channels, const float *const *field,
+                                          int x_only, int level, float *const *bw12, int *ops, void *hip_stream) {
+  if (!r || !r[0] || !pyr_a || !pyr_b || !field || !bw12 || n < 1 || n > kSetMax)
+    return fail(ICTR_ERR_INVALID, "flowrefine_run: bad arguments");
+  hipStream_t s = (hipStream_t)hip_stream;
+  return channels == 3 ? fr_run<3>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, nullptr, nullptr, s)
+                       : fr_run<1>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, nullptr, nullptr, s);
 }
 
+// a refiner's own run: a set of one at level 0, with the events of a timed run and its result event behind
 extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a, const ictr_pyramid *pyr_b,
                                    const ictr_field *src, int x_only, void *hip_stream) {
   if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
   if (!src || !src->data) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field (or its data) is NULL");
   if (src->sign != 1) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field's sign is %d (+1)", src->sign);
-  FrArgsT<1> a;
+  FrArgsT<1> a;  // (the frames' refusals come before the field's, and before anything is enqueued)
   if (int rc = fr_frame_args<1>(r, &pyr_a, &pyr_b, x_only, 0, nullptr, &a)) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const size_t n = (size_t)r->w * r->h;
@@ -531,89 +560,14 @@ extern "C" int ictr_flowrefine_run(ictr_flowrefine *r, const ictr_pyramid *pyr_a
     r->ev.emplace_back();
     if (int rc = r->ev.back().create()) return rc;
   }
-  return fr_run<1>(r, a, f0, r->timing != 0, s);
+  float *const no_bw12 = nullptr;
+  int nev = 0;
+  if (int rc = fr_run<1>(&r, &pyr_a, &pyr_b, 1, &f0, x_only, 0, &no_bw12, nullptr, r->timing ? &r->ev : nullptr, &nev, s))
+    return rc;
+  r->nev = nev;
+  return r->res.record(s);
 }
 
-// the coarse-to-fine flow's run (ictr_launch.h): `channels` (1 or 3, the caller's to keep) pyramids per frame, the field
-// on the device; untimed (the stage's events are the coarse-to-fine object's)
-extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *const *pyr_a,
-                                          const ictr_pyramid *const *pyr_b, int channels, const float *field, int x_only,
-                                          int level, float *bw12, void *hip_stream) {
-  if (!r) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
-  if (!field || (channels == 3 && !bw12)) return fail(ICTR_ERR_INVALID, "flowrefine_run: the field or the Bw planes are NULL");
-  if (channels == 3) {
-    FrArgsT<3> a;
-    if (int rc = fr_frame_args<3>(r, pyr_a, pyr_b, x_only, level, bw12, &a)) return rc;
-    return fr_run<3>(r, a, field, false, (hipStream_t)hip_stream);
-  }
-  FrArgsT<1> a;
-  if (int rc = fr_frame_args<1>(r, pyr_a, pyr_b, x_only, level, nullptr, &a)) return rc;
-  return fr_run<1>(r, a, field, false, (hipStream_t)hip_stream);
-}
-
-// n refiners of one size and one set of parameters in lockstep: fr_run's launch sequence, each stage once. Member m starts
-// from field[m] and reads the pyramids pyr_a[m * channels + c], pyr_b[m * channels + c]; bw12[m] as in run_level_. Untimed,
-// and no member's own event is recorded: the caller's event behind the whole run stands for them. *ops takes the launches
-// (and, with n_outer = 0, the copies, one per member) enqueued.
-template <int NCH>
-static int fr_run_set(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
-                      const float *const *field, int x_only, int level, float *const *bw12, int *ops, hipStream_t s) {
-  SetArgs<FrArgsT<NCH>> a;
-  FrSet g;
-  FrIoSet io;
-  memset(&a, 0, sizeof(a));
-  memset(&g, 0, sizeof(g));
-  memset(&io, 0, sizeof(io));
-  const ictr_flowrefine *r0 = r[0];
-  for (int m = 0; m < n; ++m) {
-    if (!r[m] || !field[m] || (NCH == 3 && !bw12[m]))
-      return fail(ICTR_ERR_INVALID, "flowrefine_run_set: member %d: the refiner, the field or the Bw planes are NULL", m);
-    if (r[m]->w != r0->w || r[m]->h != r0->h || r[m]->n_outer != r0->n_outer || r[m]->n_sor != r0->n_sor)
-      return fail(ICTR_ERR_INVALID, "flowrefine_run_set: member %d differs in size or iteration counts", m);
-    if (int rc = fr_frame_args<NCH>(r[m], pyr_a + m * NCH, pyr_b + m * NCH, x_only, level, bw12[m], &a.m[m])) return rc;
-    g.m[m] = fr_args<1>(r[m], x_only);
-    io.f0[m] = reinterpret_cast<const float2 *>(field[m]);
-    io.out[m] = reinterpret_cast<float2 *>(r[m]->res.get());
-  }
-  const size_t np = (size_t)r0->w * r0->h;
-  int count = 0;
-  if (r0->n_outer == 0) {  // the input's bits
-    for (int m = 0; m < n; ++m, ++count)
-      HIPCHK(hipMemcpyAsync(r[m]->res.get(), field[m], sizeof(float) * 2 * np, hipMemcpyDeviceToDevice, s));
-  } else {
-    const dim3 blk(kBlock), lin((unsigned)((np + kBlock - 1) / kBlock), n);
-    const dim3 tiles((r0->w + kFrTile - 1) / kFrTile, (r0->h + kFrTile - 1) / kFrTile, n);
-    dim3 rows = pixel_rows_grid(r0->w, r0->h), half = pixel_rows_grid((r0->w + 1) / 2, r0->h);
-    rows.z = half.z = n;
-    hipLaunchKernelGGL(k_fr_init_set, lin, blk, 0, s, g, io, (int)np);
-    for (int o = 0; o < r0->n_outer; ++o) {
-      hipLaunchKernelGGL(k_fr_warp_set<NCH>, rows, blk, 0, s, a, o > 0 ? 1 : 0);
-      if constexpr (NCH == 1)
-        hipLaunchKernelGGL(k_fr_coef_set, tiles, blk, 0, s, a);
-      else
-        hipLaunchKernelGGL(k_fr_coef_rgb_set, tiles, blk, 0, s, a);
-      for (int k = 0; k < r0->n_sor; ++k) {
-        hipLaunchKernelGGL(k_fr_sor_set<0>, half, blk, 0, s, g);
-        hipLaunchKernelGGL(k_fr_sor_set<1>, half, blk, 0, s, g);
-      }
-    }
-    hipLaunchKernelGGL(k_fr_final_set, lin, blk, 0, s, g, io);
-    count = 2 + r0->n_outer * (2 + 2 * r0->n_sor);
-  }
-  HIPCHK(hipGetLastError());
-  for (int m = 0; m < n; ++m) r[m]->nev = 0;
-  if (ops) *ops = count;
-  return ICTR_OK;
-}
-extern "C" int ictr_flowrefine_run_level_set_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
-                                              const ictr_pyramid *const *pyr_b, int n, int channels,
-                                              const float *const *field, int x_only, int level, float *const *bw12, int *ops,
-                                              void *hip_stream) {
-  if (!r || !r[0] || !pyr_a || !pyr_b || !field || !bw12 || n < 1 || n > kSetMax)
-    return fail(ICTR_ERR_INVALID, "flowrefine_run_set: bad arguments");
-  return channels == 3 ? fr_run_set<3>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, (hipStream_t)hip_stream)
-                       : fr_run_set<1>(r, pyr_a, pyr_b, n, field, x_only, level, bw12, ops, (hipStream_t)hip_stream);
-}
 // the parameters a set compares its members' refiners by
 extern "C" int ictr_flowrefine_get_params_(const ictr_flowrefine *r, float *p4, int *n2) {
   if (!r || !p4 || !n2) return fail(ICTR_ERR_INVALID, "flowrefine is NULL");
@@ -678,7 +632,10 @@ extern "C" int ictr_debug_flowrefine_write_stage(ictr_flowrefine *r, int which, 
 }
 extern "C" int ictr_debug_flowrefine_half_sweep(ictr_flowrefine *r, int colour, int x_only) {
   if (!r || (colour != 0 && colour != 1)) return fail(ICTR_ERR_INVALID, "flowrefine_half_sweep: colour is 0 or 1");
-  fr_half_sweep(r, fr_args<1>(r, x_only), colour, nullptr);
+  FrSet g;  // a set of one
+  memset(&g, 0, sizeof(g));
+  g.m[0] = fr_args<1>(r, x_only);
+  fr_half_sweep(r, g, 1, colour, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(nullptr));
   return ICTR_OK;

@@ -306,11 +306,22 @@ __global__ __launch_bounds__(kBlock) void k_fg_diff(const float *__restrict__ pt
   draw[2 * k + 1] = out[k + K] - pts[k + K];
   lost[k] = status[k] ? 0 : 1;
 }
+// The fill runs on 1 .. kSetMax grids of one geometry at once (DESIGN.md §4 "Lockstep sets"; a grid's own fill is a set
+// of one): member blockIdx.y's node buffers, and its ny rows of the rowhas block.
+struct FgFillArgs {
+  const float *draw[kSetMax];
+  const unsigned char *lost[kSetMax];
+  float *d[kSetMax];
+  int *rowhas;  // [n][ny]
+};
 // a lost node takes the nearest tracked node to its left in its row, else the nearest to its right; rowhas[y] = the row has
 // a tracked node (cleared before the launch). Nodes of a row without one are left for k_fg_colfill.
-// (the body, for k_fg_rowfill and its lockstep twin)
-__device__ __forceinline__ void fg_rowfill_body(const float *__restrict__ draw, const unsigned char *__restrict__ lost, int nx,
-                                                int K, float *__restrict__ d, int *__restrict__ rowhas) {
+__global__ __launch_bounds__(kBlock) void k_fg_rowfill(FgFillArgs a, int nx, int ny, int K) {
+  const int m = blockIdx.y;
+  const float *__restrict__ draw = a.draw[m];
+  const unsigned char *__restrict__ lost = a.lost[m];
+  float *__restrict__ d = a.d[m];
+  int *__restrict__ rowhas = a.rowhas + (size_t)m * ny;
   const int k = blockIdx.x * kBlock + threadIdx.x;
   if (k >= K) return;
   const int j = k / nx, i = k - j * nx;
@@ -325,12 +336,11 @@ __device__ __forceinline__ void fg_rowfill_body(const float *__restrict__ draw, 
   d[2 * k + 1] = draw[2 * (j * nx + src) + 1];
   if (src == i) rowhas[j] = 1;
 }
-__global__ __launch_bounds__(kBlock) void k_fg_rowfill(const float *__restrict__ draw, const unsigned char *__restrict__ lost,
-                                                       int nx, int K, float *__restrict__ d, int *__restrict__ rowhas) {
-  fg_rowfill_body(draw, lost, nx, K, d, rowhas);
-}
 // a row without a tracked node takes, node by node, the nearest row above that has one, else the nearest below, else 0
-__device__ __forceinline__ void fg_colfill_body(float *__restrict__ d, const int *__restrict__ rowhas, int nx, int ny, int K) {
+__global__ __launch_bounds__(kBlock) void k_fg_colfill(FgFillArgs a, int nx, int ny, int K) {
+  const int m = blockIdx.y;
+  float *__restrict__ d = a.d[m];
+  const int *__restrict__ rowhas = a.rowhas + (size_t)m * ny;
   const int k = blockIdx.x * kBlock + threadIdx.x;
   if (k >= K) return;
   const int j = k / nx, i = k - j * nx;
@@ -342,26 +352,6 @@ __device__ __forceinline__ void fg_colfill_body(float *__restrict__ d, const int
     if (rowhas[q]) src = q;
   d[2 * k] = src >= 0 ? d[2 * (src * nx + i)] : 0.0f;  // rows that have a tracked node are not written by this launch
   d[2 * k + 1] = src >= 0 ? d[2 * (src * nx + i) + 1] : 0.0f;
-}
-__global__ __launch_bounds__(kBlock) void k_fg_colfill(float *__restrict__ d, const int *__restrict__ rowhas, int nx, int ny,
-                                                       int K) {
-  fg_colfill_body(d, rowhas, nx, ny, K);
-}
-// The fill of a lockstep set of coarse-to-fine flows (DESIGN.md §4 "Lockstep sets"): grids of one geometry, member
-// blockIdx.y's node buffers, and its ny rows of the set's rowhas block.
-struct FgFillSet {
-  const float *draw[kSetMax];
-  const unsigned char *lost[kSetMax];
-  float *d[kSetMax];
-  int *rowhas;  // [n][ny]
-};
-__global__ __launch_bounds__(kBlock) void k_fg_rowfill_set(FgFillSet a, int nx, int ny, int K) {
-  const int m = blockIdx.y;
-  fg_rowfill_body(a.draw[m], a.lost[m], nx, K, a.d[m], a.rowhas + (size_t)m * ny);
-}
-__global__ __launch_bounds__(kBlock) void k_fg_colfill_set(FgFillSet a, int nx, int ny, int K) {
-  const int m = blockIdx.y;
-  fg_colfill_body(a.d[m], a.rowhas + (size_t)m * ny, nx, ny, K);
 }
 __global__ __launch_bounds__(kBlock) void k_fg_gather(FgDev g, const double *__restrict__ xy, int K, double *__restrict__ out) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -538,34 +528,22 @@ extern "C" int ictr_flowgrid_dims(const ictr_flowgrid *g, int *nx, int *ny) {
   if (ny) *ny = g->ny;
   return ICTR_OK;
 }
-// draw + lost -> d
-static int fg_fill(ictr_flowgrid *g, hipStream_t s) {
-  const dim3 grid((g->K + kBlock - 1) / kBlock), blk(kBlock);
-  HIPCHK(hipMemsetAsync(g->rowhas, 0, sizeof(int) * (size_t)g->ny, s));
-  hipLaunchKernelGGL(k_fg_rowfill, grid, blk, 0, s, g->draw, g->lost, g->nx, g->K, g->d, g->rowhas);
-  hipLaunchKernelGGL(k_fg_colfill, grid, blk, 0, s, g->d, g->rowhas, g->nx, g->ny, g->K);
-  HIPCHK(hipGetLastError());
-  g->filled = 1;
-  return ICTR_OK;
-}
 extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsigned char **lost) {
   if (!g || !draw || !lost) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
   *draw = g->draw;
   *lost = g->lost;
   return ICTR_OK;
 }
-extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream) {
-  if (!g) return fail(ICTR_ERR_INVALID, "flowgrid is NULL");
-  return fg_fill(g, (hipStream_t)hip_stream);
-}
-// the fill of n grids of one geometry in lockstep: one memset of rowhas [n][ny] (the caller's block), two launches
-extern "C" int ictr_flowgrid_fill_set_(ictr_flowgrid *const *g, int n, int *rowhas, void *hip_stream) {
-  if (!g || n < 1 || n > kSetMax || !rowhas) return fail(ICTR_ERR_INVALID, "flowgrid_fill_set: bad arguments");
-  FgFillSet a;
+// draw + lost -> d, of n grids of one geometry at once: one memset of rowhas [n][ny] (the caller's block; NULL with
+// n = 1: the grid's own), two launches
+extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *const *g, int n, int *rowhas, void *hip_stream) {
+  if (!g || n < 1 || n > kSetMax || !g[0] || (!rowhas && n != 1)) return fail(ICTR_ERR_INVALID, "flowgrid_fill: bad arguments");
+  if (!rowhas) rowhas = g[0]->rowhas;
+  FgFillArgs a;
   memset(&a, 0, sizeof(a));
   for (int m = 0; m < n; ++m) {
     if (!g[m] || g[m]->nx != g[0]->nx || g[m]->ny != g[0]->ny)
-      return fail(ICTR_ERR_INVALID, "flowgrid_fill_set: grid %d is NULL or differs in geometry", m);
+      return fail(ICTR_ERR_INVALID, "flowgrid_fill: grid %d is NULL or differs in geometry", m);
     a.draw[m] = g[m]->draw, a.lost[m] = g[m]->lost, a.d[m] = g[m]->d;
   }
   a.rowhas = rowhas;
@@ -573,8 +551,8 @@ extern "C" int ictr_flowgrid_fill_set_(ictr_flowgrid *const *g, int n, int *rowh
   const int nx = g[0]->nx, ny = g[0]->ny, K = g[0]->K;
   const dim3 grid((K + kBlock - 1) / kBlock, n), blk(kBlock);
   HIPCHK(hipMemsetAsync(rowhas, 0, sizeof(int) * (size_t)n * ny, s));
-  hipLaunchKernelGGL(k_fg_rowfill_set, grid, blk, 0, s, a, nx, ny, K);
-  hipLaunchKernelGGL(k_fg_colfill_set, grid, blk, 0, s, a, nx, ny, K);
+  hipLaunchKernelGGL(k_fg_rowfill, grid, blk, 0, s, a, nx, ny, K);
+  hipLaunchKernelGGL(k_fg_colfill, grid, blk, 0, s, a, nx, ny, K);
   HIPCHK(hipGetLastError());
   for (int m = 0; m < n; ++m) g[m]->filled = 1;
   return ICTR_OK;
@@ -597,7 +575,7 @@ static int fg_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyram
   hipLaunchKernelGGL(k_fg_nodes, grid, blk, 0, s, g->pts, g->nx, g->K, g->step);
   launch(a, s);
   hipLaunchKernelGGL(k_fg_diff, grid, blk, 0, s, g->pts, g->out, g->status, g->K, g->draw, g->lost);
-  return fg_fill(g, s);
+  return ictr_flowgrid_fill_(&g, 1, nullptr, s);
 }
 extern "C" int ictr_flowgrid_compute(ictr_flowgrid *g, const ictr_pyramid *pa, const ictr_pyramid *pb, int psz, int lv_f,
                                      int maxiter, float eps, void *hip_stream) {
@@ -612,7 +590,7 @@ extern "C" int ictr_flowgrid_set_nodes(ictr_flowgrid *g, const float *d, const u
   if (!g || !d || !lost) return fail(ICTR_ERR_INVALID, "flowgrid_set_nodes: NULL argument");
   HIPCHK(hipMemcpy(g->draw, d, sizeof(float) * 2 * (size_t)g->K, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(g->lost, lost, (size_t)g->K, hipMemcpyHostToDevice));
-  if (int rc = fg_fill(g, nullptr)) return rc;
+  if (int rc = ictr_flowgrid_fill_(&g, 1, nullptr, nullptr)) return rc;
   HIPCHK(hipStreamSynchronize(nullptr));
   return ICTR_OK;
 }

@@ -36,35 +36,28 @@ inline int ictr_pyramid_level0(const ictr_pyramid *p, const char *who, ictr_leve
   *l = ictr_level0{v.img[level] + (size_t)v.pad * v.sw[level] + v.pad, v.sw[level], v.w[level], v.h[level]};
   return ICTR_OK;
 }
-// The stages that the coarse-to-fine flow (ictr_c2fflow.hip) runs per level on objects of the level's size: the node
-// buffers of a flow grid that its search kernel writes (raw displacements [K][2] and the lost bytes [K]) and the grid's fill
-// on a stream; the densifier's and the refiner's run reading level `level` of `channels` (1 or 3) pyramids per frame, which
-// the caller has checked to agree in geometry.
+// The stages that the coarse-to-fine flow (ictr_c2fflow.hip) runs per level, on n (1 .. kSetMax) objects of the level's
+// size and of one set of parameters at once, one launch per stage for all of them (DESIGN.md §4 "Lockstep sets"; a single
+// object is n = 1): the node buffers of a flow grid that its search kernel writes (raw displacements [K][2] and the lost
+// bytes [K]) and the grids' fill on a stream; the densifiers' and the refiners' run reading level `level` of `channels`
+// (1 or 3) pyramids per member and frame, pyr_a[m * channels + c] and pyr_b[m * channels + c], which the caller has
+// checked to agree in geometry. No object's own event is recorded: the event the caller records behind the run stands
+// for them.
 struct ictr_flowgrid;
 struct ictr_flowdensify;
 struct ictr_flowrefine;
 extern "C" int ictr_flowgrid_node_buffers_(ictr_flowgrid *g, float **draw, unsigned char **lost);  // ictr_frontend.hip
-extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *g, void *hip_stream);  // ictr_frontend.hip
-// bias: the grid's node bias [ny][nx][channels] on the device, as patch-mean normalisation has it (NULL: none)
-extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *z, const ictr_flowgrid *grid, const ictr_pyramid *const *pyr_a,
-                                           const ictr_pyramid *const *pyr_b, int channels, int psz, int level,
-                                           const float *bias, void *hip_stream);
-// field: a device field [h][w][2]; bw12: two more Bw planes [2][h][w] of the caller's on the device (3 channels alone)
-extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *r, const ictr_pyramid *const *pyr_a,
-                                          const ictr_pyramid *const *pyr_b, int channels, const float *field, int x_only,
-                                          int level, float *bw12, void *hip_stream);
-// The same stages for a lockstep set of n (1 .. kSetMax) coarse-to-fine flows (DESIGN.md §4 "Lockstep sets"): objects of
-// one size and one set of parameters, one launch per stage for all of them. Member m's pyramids are pyr_a[m * channels + c]
-// and pyr_b[m * channels + c]. rowhas: the set's block of n * ny ints, cleared by the one memset. No member's own event is
-// recorded: the event the caller records behind the run stands for them. *ops: the launches the refinement enqueued.
-extern "C" int ictr_flowgrid_fill_set_(ictr_flowgrid *const *g, int n, int *rowhas, void *hip_stream);  // ictr_frontend.hip
-extern "C" int ictr_flowdensify_run_level_set_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
-                                               const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
-                                               int channels, int psz, int level, const float *const *bias, void *hip_stream);
-extern "C" int ictr_flowrefine_run_level_set_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
-                                              const ictr_pyramid *const *pyr_b, int n, int channels,
-                                              const float *const *field, int x_only, int level, float *const *bw12, int *ops,
-                                              void *hip_stream);
+// rowhas: the caller's block of n * ny ints, cleared by the one memset (NULL with n = 1: the grid's own)
+extern "C" int ictr_flowgrid_fill_(ictr_flowgrid *const *g, int n, int *rowhas, void *hip_stream);  // ictr_frontend.hip
+// bias[m]: grid m's node bias [ny][nx][channels] on the device, as patch-mean normalisation has it (all NULL: none)
+extern "C" int ictr_flowdensify_run_level_(ictr_flowdensify *const *z, const ictr_flowgrid *const *grid,
+                                           const ictr_pyramid *const *pyr_a, const ictr_pyramid *const *pyr_b, int n,
+                                           int channels, int psz, int level, const float *const *bias, void *hip_stream);
+// field[m]: a device field [h][w][2]; bw12[m]: two more Bw planes [2][h][w] of the caller's on the device (3 channels
+// alone); *ops: the launches (with n_outer = 0 the copies, one per member) enqueued
+extern "C" int ictr_flowrefine_run_level_(ictr_flowrefine *const *r, const ictr_pyramid *const *pyr_a,
+                                          const ictr_pyramid *const *pyr_b, int n, int channels, const float *const *field,
+                                          int x_only, int level, float *const *bw12, int *ops, void *hip_stream);
 // what a set compares its members' stages by: minerr and power; alpha, gamma, delta, omega and n_outer, n_sor
 extern "C" int ictr_flowdensify_get_params_(const ictr_flowdensify *z, float *minerr, int *power);
 extern "C" int ictr_flowrefine_get_params_(const ictr_flowrefine *r, float *p4, int *n2);

@@ -1,5 +1,6 @@
-"""Lockstep sets of coarse-to-fine flows on the device (patchflow.CoarseToFineFlowSet, ictr_c2fset_*; the lockstep twins of
-the kernels in csrc/ictr_c2fset.hip, ictr_c2fset_robust.hip, ictr_frontend.hip, ictr_densify.hip and ictr_flowrefine.hip).
+"""Lockstep sets of coarse-to-fine flows on the device (patchflow.CoarseToFineFlowSet, ictr_c2fset_*; the kernels of
+csrc/ictr_c2fflow.hip, ictr_c2fflow_robust.hip, ictr_frontend.hip, ictr_densify.hip and ictr_flowrefine.hip at members
+1 .. 7, where a single object's run is member 0 alone).
 
 The judge of a set is each member's own ``run`` on the same pyramids (an object of its own, made with the same parameters),
 and the single objects keep their own judges, the f32 restatements of the other test files. Every comparison is bit for bit
@@ -178,6 +179,26 @@ def test_twice_then_a_members_own_run_then_lockstep_again_and_on_a_stream():
         same_as_judge(s.run(pairs, stream=stream.value).members, want, "on a stream")
     finally:
         assert hip.hipStreamDestroy(stream) == 0
+
+
+def test_a_set_of_one_and_the_objects_own_run_alternate_on_one_object():
+    """33 x 17, lv_f 1, psz 8, refined: the set, the object's own timed run, the set again, all on one object and one
+    pair: the same bytes each time, and stage times only behind the object's own run."""
+    case = (33, 17, 1, 8, 1, dict(refine=REFINE))
+    (pair,) = member_pairs(case)
+    c = flow(case)
+    c.set_timing(True)
+    s = pf.CoarseToFineFlowSet([c])
+    first = snapshot(s.run([pair]).members[0])
+    assert not c.kernel_ms().any() and c.upsample_ms() == 0.0
+    own = snapshot(c.run(*pair))
+    ms = c.kernel_ms()
+    print("own kernel_ms", ms.tolist())
+    assert ms.shape == (2, 3) and (ms > 0).all()
+    again = snapshot(s.run([pair]).members[0])
+    assert not c.kernel_ms().any() and not s.kernel_ms().any()  # (the set's own timing is off)
+    assert first == own == again
+    assert first == judge(case, [pair], case_id(case))[0]
 
 
 def test_operations_do_not_depend_on_the_member_count():

@@ -188,6 +188,30 @@ def test_n_outer_0_and_x_only_keep_bits():
     assert np.array_equal(_bits(refiner(frame, n_outer=0).run(pa, pb, g).dense()), _bits(g.dense()))
 
 
+@pytest.mark.parametrize("x_only", (False, True))
+def test_a_timed_run_has_four_stage_times_and_the_untimed_runs_bits(x_only):
+    """A refiner's own run with timing on, at 37 x 23 (odd width: the two colours' rows differ in length; 23 rows: the
+    second row of tiles is partial) with one outer iteration of one sweep: every entry of kernel_ms (warp, coefficients,
+    half-sweeps, init + final) is above 0, and the field has the bits of the untimed run and of the f32 restatement."""
+    w, h, run = 37, 23, dict(n_outer=1, n_sor=1, omega=1.6)
+    a = FC._noisy(FC.texture(w, h, 1237), 2237)
+    b = FC._noisy(FC.texture(w, h, 1237, lambda X, Y: (X - 0.6, Y + 0.4)), 3237)
+    f = FC.smooth_field(w, h, 5237, (0.6, -0.4), amp=0.3)
+    pa, pb = ic.Pyramid(a, 0, PSZ, True), ic.Pyramid(b, 0, PSZ, False)
+    r = pf.FlowRefiner(w, h, **run)
+    plain = r.run(pa, pb, f, x_only=x_only).dense()
+    assert not r.kernel_ms().any()
+    r.set_timing(True)
+    timed = r.run(pa, pb, f, x_only=x_only).dense()
+    ms = r.kernel_ms()
+    print(f"timed 37x23 x_only={x_only}: kernel_ms {ms.tolist()}")
+    assert ms.shape == (4,) and (ms > 0).all()
+    assert timed.tobytes() == plain.tobytes()
+    _assert_bits(timed, R.refine(a, b, f, x_only=x_only, **run), f"timed 37x23 x_only={x_only}")
+    r.set_timing(False)
+    assert r.run(pa, pb, f, x_only=x_only).dense().tobytes() == plain.tobytes() and not r.kernel_ms().any()
+
+
 def _hip_runtime():
     """The HIP runtime that libictr_hip.so runs on (already in the process), for a stream of the test's own."""
     import ctypes as C
