@@ -74,6 +74,11 @@ int ictr_stream_read_bandwidth(size_t bytes, int reps, double *gbps_out);
  * 2 * patch_of_lane[lane] + kind_of_lane[lane] (all host arrays; 64 entries each) */
 int ictr_debug_transpose_reduce(const float *vals, float *out, int *patch_of_lane, int *kind_of_lane,
                                 int patches_per_wave /* 16 or 32: the kernel's two instantiations; 16 uses values 0..31 */);
+/* inspection: the half-window fetch path of the resident-iteration kernel alone, one wave, eight 9x9 windows of a
+ * caller plane[rows][sw] (all host arrays). top_left[8] = texel index of each window's top-left texel; the windows must
+ * lie in the plane. out[8][64][4]: for window g and lane = pixel (row lane / 8, column lane % 8) the four bilinear taps
+ * a, b, c, d = window texels (row + 1, col + 1), (row + 1, col), (row, col + 1), (row, col) */
+int ictr_debug_half_window(const float *plane, int rows, int sw, const int *top_left, float *out);
 /* inspection: the solver turn's 6x6 full-pivot LU on the device (one wave per system, n systems, all host arrays):
  * H36[n][36] symmetric (the kernel reads the upper triangle), b6[n][6] -> x6[n][6], rank[n], nonzero[n] (non-zero
  * pivots), the composed permutations rowmap6 / colmap6 [n][6] (c[i] = b[rowmap[i]], x[i] = c[colmap[i]]) and the

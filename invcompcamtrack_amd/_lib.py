@@ -87,6 +87,7 @@ SIGNATURES = {
     "ictr_set_device": (C.c_int, [C.c_int]),
     "ictr_stream_read_bandwidth": (C.c_int, [C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "ictr_debug_transpose_reduce": (C.c_int, [FP, FP, IP, IP, C.c_int]),
+    "ictr_debug_half_window": (C.c_int, [FP, C.c_int, C.c_int, IP, FP]),
     "ictr_debug_wave_solve": (C.c_int, [FP, FP, I64, C.c_int, FP, IP, IP, IP, IP, FP]),
     "ictr_debug_se3": (C.c_int, [FP, I64, C.c_int, FP]),
     "ictr_cam_create": (C.c_int, [C.POINTER(VP), C.c_int, FP, FP, IP, C.c_int]),

@@ -387,6 +387,67 @@ __device__ __forceinline__ int lane_gather(int v, int src_lane) { return __built
 __device__ __forceinline__ int rlane_dyn(int v, int uniform_lane) {
   return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(uniform_lane));
 }
+// six wave sums at once: every sum adds in wave_sum_dpp's order (the same bits), the six chains interleaved step by
+// step so that no DPP step waits behind its own predecessor
+__device__ __forceinline__ void wave_sum6_dpp(float (&v)[6]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] += dpp_mov<0xB1>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] += dpp_mov<0x4E>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] += dpp_mov<0x141>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] += dpp_mov<0x140>(v[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = (rlane(v[k], 0) + rlane(v[k], 16)) + (rlane(v[k], 32) + rlane(v[k], 48));
+}
+
+// ---------------------------------------------------------------- half windows (the resident form's current-frame taps)
+// A lane (pixel row r = lane >> 3, column c = lane & 7 of an 8x8 patch) needs the texels (c, c + 1) of the rows r + 1
+// ("ab") and r ("cd") of the patch's 9x9 window. cd of row r is ab of row r - 1, so a lane loads only its ab pair and
+// takes c, d from the lane eight below when the patch is blended (ds_bpermute). Window row 0, which no lane holds, is
+// nine texels; it comes for FOUR patches in one one-register load: lanes 16 g .. 16 g + 8 load the texels of row 0 of
+// the window of patch 4 k + g, the other lanes' offsets lie beyond the resource (zeros, no memory traffic).
+// All byte offsets are relative to a buffer resource over the plane; base = the window's top-left texel.
+constexpr int kHwNoLoad = 0x7fffffff;  // an offset beyond every resource used here
+struct HalfWinLane {
+  int up4;  // ds_bpermute address of the lane eight below (lanes 0..7: unused)
+  int t16;  // (lane & 15) * 4: the ds_bpermute address of texel (lane & 15) of a row-0 load's lane group 0
+};
+__device__ __forceinline__ HalfWinLane hw_lane(int lane) { return HalfWinLane{(lane - 8) << 2, (lane & 15) << 2}; }
+// byte offset of this lane's row-0 texel for patches 4 k + g (base_v: lane p holds the window base of patch p). The lane
+// terms are formed from an opaque copy of the lane next to their use: as loop invariants they would be kept in registers,
+// one set per k, over the whole iteration loop.
+__device__ __forceinline__ int hw_row_voff(int base_v, int k, int lane) {
+  asm volatile("" : "+v"(lane));
+  const int v = lane_gather(base_v, 4 * k + (lane >> 4)) + ((lane & 15) << 2);
+  return (lane & 15) <= 8 ? v : kHwNoLoad;
+}
+__device__ __forceinline__ f32x2_a4 hw_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
+  return __builtin_bit_cast(f32x2_a4, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+}
+__device__ __forceinline__ float hw_load_row(__amdgpu_buffer_rsrc_t r, int voff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
+}
+// the lane moves of patch 4 k + G, requested ahead of their use: q[0], q[1] = ab of the lane eight below, q[2] = in lanes
+// 0..8 the texels 0..8 of row 0. (the row address t16 + 64 G by one plain add, kept where it is used -- three more loop
+// invariants otherwise; the builtin has no offset operand)
+template <int G>
+__device__ __forceinline__ void hw_cd_issue(const f32x2_a4 &ab, float row, const HalfWinLane &h, int (&q)[3]) {
+  int a0 = h.t16;
+  if constexpr (G != 0) asm volatile("v_add_u32 %0, %1, %2" : "=v"(a0) : "n"(64 * G), "v"(h.t16));
+  const float b = ab.x, a = ab.y;  // (by value: a bit cast of the vector's element lvalue reads element 0 for both)
+  q[0] = __builtin_amdgcn_ds_bpermute(h.up4, __builtin_bit_cast(int, b));
+  q[1] = __builtin_amdgcn_ds_bpermute(h.up4, __builtin_bit_cast(int, a));
+  q[2] = __builtin_amdgcn_ds_bpermute(a0, __builtin_bit_cast(int, row));
+}
+// (x-1,y-1),(x,y-1): lanes 0..7 (DPP row 0, banks 0 and 1) take texels c and c + 1 (row_shl:1) of row 0, the others keep
+// what the lane eight below gave: move and select in one instruction each
+__device__ __forceinline__ f32x2_a4 hw_cd_take(const int (&q)[3]) {
+  const int d = __builtin_amdgcn_update_dpp(q[0], q[2], 0xE4, 0x1, 0x3, false);   // quad_perm [0,1,2,3]
+  const int c = __builtin_amdgcn_update_dpp(q[1], q[2], 0x101, 0x1, 0x3, false);  // row_shl:1
+  return f32x2_a4{__builtin_bit_cast(float, d), __builtin_bit_cast(float, c)};
+}
 
 // ---------------------------------------------------------------- transposing wave reduction
 // merge(u, v) on lane bit k: the lanes with bit k = 0 end up with u summed over the lane pair {l, l ^ (1 << k)}, the

@@ -90,6 +90,30 @@ extern "C" int ictr_debug_transpose_reduce(const float *vals, float *out, int *p
   return ICTR_OK;
 }
 
+// inspection: the resident-iteration kernel's half-window fetch path alone (ictr_devfn.h hw_*), one wave, eight windows.
+// plane[rows][sw]; top_left[8] = texel index of each window's top-left texel (the 9x9 window must lie in the plane) ->
+// out[window][lane = pixel][4] = the taps a, b, c, d = (x,y), (x-1,y), (x,y-1), (x-1,y-1) of the lane's pixel
+extern "C" int ictr_debug_half_window(const float *plane, int rows, int sw, const int *top_left, float *out) {
+  if (!plane || !top_left || !out || rows < 9 || sw < 9 || (int64_t)rows * sw > (1 << 24))
+    return fail(ICTR_ERR_INVALID, "debug_half_window: bad arguments (a plane of at least 9 x 9 texels)");
+  for (int g = 0; g < 8; ++g) {
+    const int r = top_left[g] / sw, c = top_left[g] % sw;
+    if (top_left[g] < 0 || r + 9 > rows || c + 9 > sw) return fail(ICTR_ERR_INVALID, "debug_half_window: a window leaves the plane");
+  }
+  if (int rc = need_device()) return rc;
+  const int n = rows * sw;
+  DevBuf<float> dpl, dout;
+  DevBuf<int> dtl;
+  if (int rc = dpl.alloc(sizeof(float) * n)) return rc;
+  if (int rc = dout.alloc(sizeof(float) * 8 * 64 * 4)) return rc;
+  if (int rc = dtl.alloc(sizeof(int) * 8)) return rc;
+  HIPCHK(hipMemcpy(dpl.get(), plane, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dtl.get(), top_left, sizeof(int) * 8, hipMemcpyHostToDevice));
+  HIPCHK(launch_debug_half_window(dpl.get(), n, sw, dtl.get(), dout.get(), nullptr));
+  HIPCHK(hipMemcpy(out, dout.get(), sizeof(float) * 8 * 64 * 4, hipMemcpyDeviceToHost));
+  return ICTR_OK;
+}
+
 // inspection: the solver turn's linear algebra (WaveSolver, ictr_devfn.h) alone on caller systems, one wave each.
 // through_state: the factors go through ProbState (ws_store_factor) and a second launch reloads them (ws_load_factor).
 extern "C" int ictr_debug_wave_solve(const float *H36, const float *b6, int64_t n, int through_state, float *x6, int *rank,

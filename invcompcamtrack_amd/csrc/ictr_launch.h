@@ -225,6 +225,8 @@ hipError_t launch_level_resident(const EngineDev &e, const LevelCam &lc, int lev
 // inspection: the transposing wave reduction alone, np = 16 or 32 patches per wave
 hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *patch_of_lane, int *kind_of_lane, int np,
                                          hipStream_t s);
+// inspection: the half-window fetch path alone (one wave, eight windows of a plane of ntexels floats, row stride sw)
+hipError_t launch_debug_half_window(const float *plane, int ntexels, int sw, const int *top_left, float *out, hipStream_t s);
 
 // ---------------------------------------------------------------- ictr_sequence.hip, ictr_ransac.hip, ictr_fsplit.hip, ictr_patchflow.hip
 // the between-pairs step (three launches), or with a.tail the last frame's bookkeeping (one)

@@ -22,6 +22,12 @@
 //     partials); the pair's SOLVER workgroup polls them in one round trip (256 lanes x 8 granules), adds in a fixed
 //     order in f64, one wave runs the solver turn (WaveSolver, ictr_devfn.h: substitution with the level's LU factors,
 //     pose update, exp map, loop condition; odometer.cpp:407-418, 509-515) and broadcasts cpos_G + the loop flag.
+//   * current-frame windows (r05, ICTR_RES_WIN = 1): a lane loads only the row pair (a, b) of its own pixel row; (c, d) is
+//     the (a, b) of the lane eight below and arrives by two ds_bpermute when the patch is blended; the window's top row
+//     (nine texels, which no lane holds) comes for four patches in one one-register load and one more ds_bpermute. Two
+//     registers per window in flight instead of four and 40 instead of 64 load instructions per wave and iteration;
+//     kResD windows in flight (ICTR_RES_D). The blend's operands and order are those of the full-window form
+//     (ICTR_RES_WIN = 0, kept as the A/B reference), so b and the poses keep their bits.
 // The mailbox protocol and this form's mailbox layout: ictr_xchg.h.
 // H partials come from the level's setup launch (k_ref8: three sums per patch) and are reduced + factored by the pair's
 // solver workgroup at the start of the pair (what k_level_tail does in the other launch forms); templates and (possibly
@@ -45,10 +51,16 @@ constexpr int kResThreads = 64 * kResWaves;
 #ifndef ICTR_RES_AUX
 #define ICTR_RES_AUX 2  // template loads of the pair prologue: slc (streamed)
 #endif
-#ifndef ICTR_RES_D
-#define ICTR_RES_D 4
+// window form: 1 = half windows (a lane loads its own row pair; the pair of the row above comes from the lane eight below,
+// the window's top row for four patches in one load: two registers per window in flight), 0 = full windows (four registers)
+#ifndef ICTR_RES_WIN
+#define ICTR_RES_WIN 1
 #endif
-constexpr int kResD = ICTR_RES_D;           // current-frame windows in flight per wave (4 registers each)
+#ifndef ICTR_RES_D
+#define ICTR_RES_D (ICTR_RES_WIN ? 8 : 4)
+#endif
+constexpr int kResD = ICTR_RES_D;           // current-frame windows in flight per wave
+static_assert(kResD >= 1 && kResD <= 16, "windows in flight: at most the patches of a wave");
 
 struct ResArgs {
   LevelCam lc;
@@ -133,6 +145,31 @@ hipError_t launch_debug_transpose_reduce(const float *vals, float *out, int *pl,
     hipLaunchKernelGGL(k_debug_transpose_reduce<16>, dim3(1), dim3(64), 0, s, vals, out, pl, kl);
   else
     hipLaunchKernelGGL(k_debug_transpose_reduce<32>, dim3(1), dim3(64), 0, s, vals, out, pl, kl);
+  return hipGetLastError();
+}
+
+// inspection (tests/test_gpu_resident_windows.py): the half-window fetch path alone, one wave, eight windows of a caller
+// plane: top_left[g] = texel index of window g's top-left texel -> out[g][lane] = {a, b, c, d}. The resource is bounded by
+// the plane, so a window that leaves it reads zeros.
+__global__ __launch_bounds__(64) void k_debug_half_window(const float *__restrict__ plane, int ntexels, int sw,
+                                                          const int *__restrict__ top_left, float4 *__restrict__ out) {
+  const int lane = threadIdx.x;
+  const HalfWinLane hwl = hw_lane(lane);
+  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(plane), 0, ntexels * 4, 0x00020000);
+  const int off_ab = ((lane >> 3) * sw + (lane & 7) + sw) * 4;
+  const int base_v = top_left[lane & 7] * 4;
+  const float row[2] = {hw_load_row(rp, hw_row_voff(base_v, 0, lane)), hw_load_row(rp, hw_row_voff(base_v, 1, lane))};
+  tr_for_each_patch<8, 0>([&](auto gc) {
+    constexpr int g = decltype(gc)::value;
+    const f32x2_a4 ab = hw_load(rp, off_ab, rlane(base_v, g));
+    int q[3];
+    hw_cd_issue<g % 4>(ab, row[g / 4], hwl, q);
+    const f32x2_a4 cd = hw_cd_take(q);
+    out[g * 64 + lane] = make_float4(ab.y, ab.x, cd.y, cd.x);
+  });
+}
+hipError_t launch_debug_half_window(const float *plane, int ntexels, int sw, const int *top_left, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_debug_half_window, dim3(1), dim3(64), 0, s, plane, ntexels, sw, top_left, reinterpret_cast<float4 *>(out));
   return hipGetLastError();
 }
 
@@ -380,6 +417,7 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
   const int sw = lc.sw;
   const unsigned off_cd = (unsigned)((lane >> 3) * sw + (lane & 7)) * 4u;  // bytes from the window's top-left texel
   const unsigned off_ab = off_cd + (unsigned)sw * 4u;
+  const HalfWinLane hwl = hw_lane(lane);
   float4 *const recs = sRecW[wave];
   float *const tw = sT[wave] + lane;
   const int my_patch = tr_patch_of_lane<NP>(lane);  // the (patch, A|B) whose complete sum this lane holds after stage 2
@@ -473,6 +511,57 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
       // ---- stage 2: thirty-two patches from registers, kResD windows in flight. Per pixel: blend (utilities.cpp:107,
       // reference operand order, not contracted), residual (odometer.cpp:381), Gx r and Gy r; the per-patch sums by the
       // transposing reduction: a patch's (A, B) pair merges on lane bit 2, then a binary counter of pending registers
+#if ICTR_RES_WIN
+      // half windows (ictr_devfn.h): W holds the lanes' own row pairs, Rw the windows' top rows of two groups of four
+      // patches (group k + 2 is requested into group k's register behind that group's last lane move); a patch's lane
+      // moves are requested one patch ahead, like its weights and T
+      constexpr int kRowK = kResPPW / 4;
+      f32x2_a4 W[kResD];
+      float Rw[2];
+      auto issue = [&](int j) {
+#if defined(ICTR_RES_ABL) && ICTR_RES_ABL == 2  // timing ablations (diagnostic builds, wrong results): no window loads in the loop
+        if (j >= kResD) return;
+#endif
+#if defined(ICTR_RES_ABL) && ICTR_RES_ABL == 1  // ... every window = the plane's first (cache-resident)
+        const int soff = 0;
+#else
+        const int soff = rlane(base_v, j);
+#endif
+        W[j % kResD] = hw_load(rcur, (int)off_ab, soff);
+      };
+      Rw[0] = hw_load_row(rcur, hw_row_voff(base_v, 0, lane));
+#pragma unroll
+      for (int j = 0; j < kResD; ++j) issue(j);
+      TrAcc<NP> acc;
+      float4 wv_n = recs[0];  // the next patch's weights, T and lane moves: one patch ahead of the arithmetic
+      float t_n = tw[0];
+      int q_n[3], vrow_n = 0;
+      hw_cd_issue<0>(W[0], Rw[0], hwl, q_n);
+      tr_for_each_patch<NP, 0>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const float4 wv = wv_n;
+        const float t = t_n;
+        const f32x2_a4 cd = hw_cd_take(q_n);
+        asm volatile("" ::: "memory");  // (the LDS reads of later patches stay behind this point: two patches' worth live)
+        if constexpr (j + 1 < kResPPW) {
+          wv_n = recs[j + 1];
+          t_n = tw[(j + 1) * 64];
+        }
+        const f32x2_a4 ab = W[j % kResD];
+        // w0 a + w1 b + w2 c + w3 d in the reference's order; the four products as two packed multiplies (each product
+        // rounded on its own, like the scalar form)
+        const f32x2_t pab = f32x2_t{wv.x, wv.y} * f32x2_t{ab.x, ab.y}, pcd = f32x2_t{wv.z, wv.w} * f32x2_t{cd.x, cd.y};
+        const float inew = ((pab.y + pab.x) + pcd.y) + pcd.x;
+        if constexpr (j + kResD < kResPPW) issue(j + kResD);
+        if constexpr (j + 1 < kResPPW) hw_cd_issue<(j + 1) % 4>(W[(j + 1) % kResD], Rw[((j + 1) / 4) & 1], hwl, q_n);
+        if constexpr (j == 0) Rw[1] = hw_load_row(rcur, hw_row_voff(base_v, 1, lane));  // (not with the first windows: registers)
+        if constexpr (j % 4 == 1 && j / 4 + 2 < kRowK) vrow_n = hw_row_voff(base_v, j / 4 + 2, lane);
+        if constexpr (j % 4 == 3 && j / 4 + 2 < kRowK) Rw[(j / 4) & 1] = hw_load_row(rcur, vrow_n);
+        const float r = t - inew;  // pdiff (odometer.cpp:381); visibility is applied to the patch sums below
+        const f32x2_t gr = Gxy[j] * f32x2_t{r, r};
+        acc.template push<j>(gr.x, gr.y, lane);
+      });
+#else
       ResWin W[kResD];
       auto issue = [&](int j) {
 #if defined(ICTR_RES_ABL) && ICTR_RES_ABL == 2  // timing ablations (diagnostic builds, wrong results): no window loads in the loop
@@ -510,19 +599,22 @@ __global__ __launch_bounds__(kResThreads, 4) void k_level_resident(EngineDev e, 
         const f32x2_t gr = Gxy[j] * f32x2_t{r, r};
         acc.template push<j>(gr.x, gr.y, lane);
       });
+#endif
       const float F = acc.F;
       RES_MARK(2)  // worker: stage 2
       RES_STAMP(tr_row, tr_it, 1)
       // ---- lane = (patch, A|B): its point's visibility and coefficients, then the six sums over the wave
       {
         const float val = F * lane_gather(vis_f, my_patch);  // 0 out of the new view (ind_new) and beyond the wave's points
-        float o = 0.0f;
+        float o = 0.0f, v6[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          const float v = wave_sum_dpp(c6[k] * val);  // b_k = sum_patches cx_k A + cy_k B (odometer.cpp:386-404)
-          o = lane == k ? v : o;
-        }
-        if (lane < 6) sPart[wave][lane] = o;
+        for (int k = 0; k < 6; ++k) v6[k] = c6[k] * val;
+        wave_sum6_dpp(v6);  // b_k = sum_patches cx_k A + cy_k B (odometer.cpp:386-404)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o = lane == k ? v6[k] : o;
+        int lane_w = lane;  // (opaque copy: the LDS address is formed here, not kept in a register over the loop)
+        asm volatile("" : "+v"(lane_w));
+        if (lane < 6) sPart[wave][lane_w] = o;
       }
       __syncthreads();
       RES_MARK(3)  // worker: wave reduction + barrier
